@@ -14,14 +14,19 @@ A "step" is one render pass = one BlockedRenderProcess of the reference: every p
 the SD-tree, accumulated into the film.  The timed region is a complete GuidedPathTracer::render() of K passes following the
 reference's iteration schedule 1, 2, 4, ... (guided_path.cpp:1342-1426): SD-tree refine / reset / build between iterations and the
 rounds of the sampling-fraction optimiser ARE inside the timed region; scene upload and BVH build are not.
-Warm-up = one throw-away render of W passes.  value = pixels x spp x K / seconds, whole job over all GPUs.
+Warm-up = one throw-away render of W passes.  value = pixels x spp x K / seconds, whole job over all GPUs; ms_per_step = seconds x 1000 / K.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what that line needs: scene setup, the warm-up, ONE timed render of K
+passes and the JSON line.  `--full` adds everything below, and `--repeats` defaults to 5 there (value = the median).
+`--dump-outputs DIR` writes what the last timed render returned (rank 0): the film, its per-iteration statistics and the learned
+SD-tree, as DIR/*.npy (dump_outputs); the inputs (scene, settings, seed) are fixed, so two builds can be compared output for output.
 
 Multi-GPU (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`, or plain `python bench.py --gpus N`, which starts
 its N ranks itself): the fixed image is sharded by 32x32 tiles over the ranks (strong scaling); per iteration the building SD-tree
 statistics are all-reduced over RCCL, per round of the optimiser its records go to the owners of their D-trees, the final iteration's
 groups of passes are dealt whole to the ranks or rendered by tiles (ppg_host/distributed.py, include/ppg.h).
 
-Added to the JSON line (rank 0):
+Added to the JSON line with --full (rank 0):
   roofline      the kernel with the largest accumulated time of an instrumented render of the same K passes: HIP-event durations on
                 the kernels' own stream, algorithmic bytes per DESIGN.md §3 — for k_trace on a BVH scene 48 B per ray + 64 B per
                 BVH4 node visited + 48 B per triangle tested, the visits counted by the kernel itself in that run
@@ -161,6 +166,38 @@ def rmse(a, b):
     return float(np.sqrt(np.nanmean(d)))
 
 
+DUMP_LIMIT = 64 << 20
+PASS_FIELDS = ("passes_rendered_total", "passes_rendered_local", "variance", "samples", "rays", "path_length_sum", "vertices_committed")
+
+
+def dump_outputs(directory, img, iterations, tree):
+    """--dump-outputs: what a caller of the timed render() receives, as float32 / float64 .npy files —
+      image.npy             the film render() returned (height x width x 3)
+      pass_stats.npy        one row per iteration: iteration, then PASS_FIELDS of its statistics (no clock readings)
+      sdtree_*.npy          the guiding distribution the render learned (ppg_host.Engine.read_sdtree): S-tree children, the sampling
+                            D-trees' node sums and children, the learned BSDF-sampling fractions (theta)
+    Above DUMP_LIMIT in all, each array keeps a fixed, seeded sample of its rows in proportion (DIR/<name>_rows.npy: the row indices)."""
+    import numpy as np
+    arrays = {
+        "image": np.asarray(img, np.float32),
+        "pass_stats": np.array([[it["iter"]] + [float(s[f]) for f in PASS_FIELDS] for it in iterations for s in it["stats"]], np.float64),
+        "sdtree_stree_children": tree["children"].astype(np.float64),
+        "sdtree_node_sums": tree["sampling"]["node_sums"].astype(np.float32),
+        "sdtree_node_children": tree["sampling"]["node_children"].astype(np.float32),
+        "sdtree_theta": tree["theta"].astype(np.float32),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT and a.shape[0] > 1:
+            row_bytes = a.nbytes // a.shape[0]
+            keep = min(a.shape[0], int(DUMP_LIMIT * a.nbytes / total) // (row_bytes + 8))
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], keep, replace=False))
+            np.save(os.path.join(directory, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+
+
 def run(args):
     import numpy as np
     import ppg_host
@@ -290,7 +327,10 @@ def run(args):
             print("[bench] timed render %d" % k_, file=sys.stderr, flush=True)
         g_ = make(args.steps)
         gc.collect()  # (a full collection of the interpreter's heap takes tens of ms with torch loaded: not inside a 120 ms render)
-        _, dt_ = timed_render(g_)
+        img_, dt_ = timed_render(g_)
+        if rank == 0 and args.dump_outputs and k_ == max(1, args.repeats) - 1:  # (after the clock stopped; before the context is closed)
+            dump_outputs(args.dump_outputs, img_, g_.iterations, g_.engine.read_sdtree())
+        del img_
         runs.append((dt_, g_.iterations))
         g_.engine.close()  # (not left to the garbage collector: the fifth render of five used to run beside the contexts of the four before it)
         del g_
@@ -583,7 +623,10 @@ def main():
     ap.add_argument("--cpu-passes", type=int, default=0, help="passes timed on the CPU baseline (bounded sample); 0 = min(--steps, 20): the GPU's own schedule for the driver's command")
     ap.add_argument("--no-cpu-1core", action="store_true", help="skip the one-core leg of the CPU baseline")
     ap.add_argument("--secondary-passes", type=int, default=63)
-    ap.add_argument("--repeats", type=int, default=5, help="timed renders; value = their median (min / max reported)")
+    ap.add_argument("--repeats", type=int, default=None, help="timed renders; value = their median (min / max reported); default 1, 5 with --full")
+    ap.add_argument("--full", action="store_true", help="also the figures beside the headline: single_call, cpu_baseline, roofline, time_to_rmse, "
+                                                        "secondary (each can still be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the film, statistics and SD-tree of the last timed render to DIR/*.npy (float32 / float64)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-rmse", action="store_true")
@@ -592,6 +635,10 @@ def main():
     ap.add_argument("--all-diffuse", action="store_true", help="experiment: replace every BSDF of a scene file by a grey two-sided Lambertian")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and run the reducer even with one rank (plumbing check)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline figure only
+        args.no_cpu = args.no_roofline = args.no_rmse = args.no_secondary = args.no_single_call = True
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     if args.gpus > 1 and "RANK" not in os.environ:
         # the plain command `python bench.py --gpus N ...`: start the N ranks ourselves (one process per GPU over RCCL), as the launcher would
         import socket

@@ -481,12 +481,10 @@ def test_cpp_loader_on_the_reference_spaceship_scene(ppg_render, tmp_path):
     assert np.allclose(c["c2w"], np.asarray(desc.camera["camera_to_world"]).reshape(-1), atol=1e-6) and list(c["size"]) == [640, 360]
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/mitsuba/data/ior/Au.eta.spd"), reason="Mitsuba data tables not mounted")
 def test_cpp_named_conductors_equal_the_python_loader(ppg_render, tmp_path):
     import ppg_host
     from ppg_host.bindings import Material
-    from test_mitsuba_xml import _write
-    data = "/root/reference/mitsuba/data"
+    from test_mitsuba_xml import MITSUBA_DATA as data, _write
     xml = _write(tmp_path, '<shape type="rectangle"><bsdf type="conductor"><string name="material" value="Au"/></bsdf></shape>'
                            '<shape type="rectangle"><bsdf type="roughconductor"><float name="extEta" value="1.33"/></bsdf></shape>'
                            '<shape type="rectangle"><bsdf type="conductor"><string name="material" value="W"/><rgb name="k" value="1, 2, 3"/></bsdf></shape>')
@@ -556,12 +554,12 @@ def test_cpp_scene_xml_loader_errors(ppg_render, tmp_path):
     assert r.returncode == 0 and len(c["indices"]) == 9
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/scenes/cbox/cbox.xml"), reason="reference checkout not present (GPU box)")
 def test_cpp_loader_reads_the_reference_cbox(ppg_render, tmp_path):
     import ppg_host
-    r, c = _cpp_load(ppg_render, "/root/reference/scenes/cbox/cbox.xml", tmp_path)
+    from test_mitsuba_xml import REF_CBOX
+    r, c = _cpp_load(ppg_render, REF_CBOX, tmp_path)
     assert r.returncode == 0, r.stderr
-    desc, _, _ = ppg_host.load_scene("/root/reference/scenes/cbox/cbox.xml")
+    desc, _, _ = ppg_host.load_scene(REF_CBOX)
     assert np.array_equal(c["indices"], desc.indices) and np.allclose(c["positions"], desc.positions, atol=1e-4)
     assert np.allclose(c["normals"], desc.normals, atol=1e-5)
     mats = np.array([np.frombuffer(m, np.float32)[1:4] for m in c["materials"]])

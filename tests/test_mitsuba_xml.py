@@ -11,7 +11,9 @@ from ppg_host import mitsuba_xml, spectrum
 from ppg_host.imageio import read_exr, write_exr, write_pfm
 from ppg_host.scenes import CBOX_EMITTER_RGB, CBOX_RGB
 
-REF_CBOX = "/root/reference/scenes/cbox/cbox.xml"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+REF_CBOX = os.path.join(GOLDEN, "cbox", "cbox.xml")                 # the reference's scenes/cbox/cbox.xml + meshes/*.obj, as shipped
+MITSUBA_DATA = os.path.join(GOLDEN, "mitsuba_data")                  # Mitsuba's data/ior/{Ag,Au,Cu,W}.{eta,k}.spd, as shipped
 
 
 def test_spectrum_values_reproduce_the_committed_cbox_constants():
@@ -28,7 +30,6 @@ def test_spectrum_values_reproduce_the_committed_cbox_constants():
         spectrum.parse("blackbody", "5000")
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CBOX), reason="reference checkout not present (GPU box)")
 def test_reference_cbox_xml_equals_the_procedural_restatement():
     desc, props, info = ppg_host.load_scene(REF_CBOX)
     assert props == dict(strictNormals=1, maxDepth=10, rrDepth=10, budgetType="spp", budget=127.0)  # cbox.xml:8-24
@@ -538,11 +539,10 @@ def test_spectrum_from_a_file(tmp_path):
         ppg_host.load_scene(_write(tmp_path, '<shape type="rectangle"><bsdf type="diffuse"><spectrum name="reflectance" filename="nope.spd"/></bsdf></shape>'), defines=dict(nee="never"))
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/mitsuba/data/ior/Au.eta.spd"), reason="Mitsuba data tables not mounted")
 def test_named_conductor_materials_come_from_the_mitsuba_data_directory(tmp_path):
     """conductor.cpp:160-186 / roughconductor.cpp:174-186: `material` names data/ior/<name>.{eta,k}.spd, integrated against the CIE curves
     without zero extension or clamping; Mitsuba's default is copper.  Gold gives the familiar (0.143, 0.375, 1.442) / (3.98, 2.39, 1.60)."""
-    data = "/root/reference/mitsuba/data"
+    data = MITSUBA_DATA
     xml = _write(tmp_path, '<shape type="rectangle"><bsdf type="roughconductor"><string name="material" value="Au"/><string name="distribution" value="ggx"/></bsdf></shape>'
                            '<shape type="rectangle"><bsdf type="conductor"/></shape>'
                            '<shape type="rectangle"><bsdf type="conductor"><string name="material" value="Ag"/><float name="extEta" value="1.33"/></bsdf></shape>')

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp; ulimit -c 0
 NR=--no-roofline; [ -n "$PPG_AB_KERNELS" ] && NR=""
-B="timeout 300 python $R/bench.py --steps $PASSES --warmup 5 --no-cpu --no-rmse --no-secondary $NR --no-single-call"
+B="timeout 300 python $R/bench.py --full --steps $PASSES --warmup 5 --no-cpu --no-rmse --no-secondary $NR --no-single-call"
 lib() { if [ "$1" = "-" ] || [ -z "$1" ]; then echo $R/practical-path-guiding_amd/lib/libppg_hip.so; else echo $R/practical-path-guiding_amd/lib/$1; fi; }
 if [ -n "$PPG_AB_TESTS" ]; then
   for v in "$@"; do

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "gpurun_out")
 STEPS = int(sys.argv[1]) if len(sys.argv) > 1 else 31
 W, H, SPP = 1280, 720, 4
-BENCH = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(STEPS), "--warmup", "0", "--no-cpu", "--no-roofline"]
+BENCH = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(STEPS), "--warmup", "0", "--no-cpu", "--no-roofline"]
 env = dict(os.environ, TMPDIR="/tmp")
 
 

@@ -20,7 +20,7 @@ PROF = os.path.join(OUT, "profiles")
 os.makedirs(PROF, exist_ok=True)
 STEPS = 20
 DRIVER = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5"]
-ONE = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(STEPS), "--warmup", "0", "--no-cpu", "--no-rmse", "--no-secondary", "--no-roofline"]
+ONE = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", str(STEPS), "--warmup", "0", "--no-cpu", "--no-rmse", "--no-secondary", "--no-roofline"]
 env = dict(os.environ, TMPDIR="/tmp")
 
 

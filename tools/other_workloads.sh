@@ -4,7 +4,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/other
 mkdir -p $OUT $R/gpurun_out/profiles
 cd /tmp; export TMPDIR=/tmp
-F="--warmup 3 --no-cpu --no-rmse --no-secondary --no-roofline --no-single-call"
+F="--full --warmup 3 --no-cpu --no-rmse --no-secondary --no-roofline --no-single-call"
 python $R/bench.py --scene-file $R/scratch/spaceship.ppgs --steps 255 $F --size-override --width 1920 --height 1080 > $OUT/spaceship1080.json 2>> $OUT/err.log
 python $R/bench.py --scene torus --steps 255 $F > $OUT/torus.json 2>> $OUT/err.log
 python $R/bench.py --scene room --steps 63 $F > $OUT/room.json 2>> $OUT/err.log
