@@ -258,6 +258,38 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *scene);
 int ppg_set_shard(ppg_ctx *ctx, int32_t rank, int32_t world, int32_t tile_size);
 
 /* ------------------------------------------------------------------------------------------------
+ * Film reconstruction filter: the <rfilter> of the scene's hdrfilm (mitsuba/src/rfilters/; Mitsuba's default is gaussian,
+ * mitsuba/src/librender/film.cpp:89-95).  Parameters, defaults and radius as in Mitsuba:
+ *   box         radius (0.5) + 1e-5           tent        radius 1
+ *   gaussian    stddev (0.5), radius 4 stddev  mitchell    B, C (1/3, 1/3), radius 2
+ *   catmullrom  radius 2                      lanczos     lobes (3), radius lobes
+ * A sample at samplePos is splatted like ImageBlock::put (imageblock.h:147-190): pos = samplePos - 0.5, the pixels x in
+ * [ceil(pos.x - r), floor(pos.x + r)] (likewise y) clipped to the film, weight = evalDiscretized(x - pos.x) * evalDiscretized(y - pos.y)
+ * from the 32-entry table of ReconstructionFilter::configure (rfilter.cpp:37-55); image += w L, squared image += w L², weights += w, for
+ * the film and for the per-pass image of the variance estimate alike (renderBlock puts every sample into both blocks, GP:1604-1640).
+ *   - The default box (radius 0.5) keeps the own-pixel, unit-weight film.  Deviation: Mitsuba's box radius is 0.5 + 1e-5, so a sample
+ *     within 1e-5 of a pixel edge also reaches the neighbouring pixel; this build ignores that sliver.
+ *   - Every other filter (a box of another radius included) splats into at most (2B + 1)² pixels, B = ceil(r - 0.5) <= 3 (7 x 7);
+ *     a larger border is PPG_ERR_INVALID.  A pixel the reference would reach outside that window (only when r + 0.5 is an integer and
+ *     the sample lies exactly on a pixel edge: its weight is the table's 0 entry) is left out.
+ *   - No float atomics; the sums have ONE association, independent of batch size, launch schedule and thread count: per source pixel,
+ *     its samples in sample order into a footprint slot per target pixel (tap); per target pixel, its taps in the order dy = -B .. B and,
+ *     within each dy, dx = -B .. B, starting from zero; then, in a final iteration ("groups of passes" below), the groups in group order.
+ *     A sharded version can exchange footprints and reproduce one GPU's bits; it does not exist yet: a filter other than the default
+ *     box together with ppg_set_shard(world > 1) is PPG_ERR_INVALID, whichever of the two calls comes second.
+ * ---------------------------------------------------------------------------------------------- */
+enum { PPG_RFILTER_BOX = 0, PPG_RFILTER_TENT, PPG_RFILTER_GAUSSIAN, PPG_RFILTER_MITCHELL, PPG_RFILTER_CATMULLROM, PPG_RFILTER_LANCZOS };
+typedef struct ppg_rfilter {
+    int32_t type;   /* PPG_RFILTER_* */
+    float radius;   /* box */
+    float stddev;   /* gaussian */
+    float B, C;     /* mitchell */
+    int32_t lobes;  /* lanczos */
+} ppg_rfilter;
+void ppg_rfilter_default(ppg_rfilter *f);                 /* box, radius 0.5 (and the other types' defaults in their fields) */
+int ppg_set_rfilter(ppg_ctx *ctx, const ppg_rfilter *f); /* before ppg_begin_render; NULL = default */
+
+/* ------------------------------------------------------------------------------------------------
  * Rendering.  ppg_render() is GuidedPathTracer::render() (GP:1516-1585, IH:74-75) in one call.
  * The stepwise calls expose its phases so a multi-GPU driver can all-reduce the SD-tree statistics
  * between ppg_render_passes() and ppg_build_sdtree(); ppg_render() is exactly their composition

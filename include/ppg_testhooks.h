@@ -20,6 +20,12 @@ extern "C" {
 int ppg_debug_build_bvh(const float *positions, const uint32_t *indices, uint32_t n_triangles, float pad_abs, int32_t max_leaf,
                         void *nodes_out, uint32_t nodes_cap, uint32_t *n_nodes, uint32_t *order_out);
 
+/* Host only (no GPU is touched): the discretised filter ppg_set_rfilter would use — table[32] = ReconstructionFilter::m_values (31
+   normalised samples and a 0), *radius = m_radius, *border = m_borderSize (rfilter.cpp:37-55).  Returns what ppg_set_rfilter would for
+   the filter's own checks (PPG_ERR_INVALID for bad parameters or a border above 3). */
+struct ppg_rfilter;
+int ppg_debug_rfilter_table(const struct ppg_rfilter *f, float table[32], float *radius, int32_t *border);
+
 /* The depth beyond which a path is a STRAGGLER (include/ppg.h: PPG_ADAM_DEFER_DEPTH = 64, part of the result).  One path in 10^4 gets there
    in a real scene and none in most test scenes; the parity tests lower it (1 .. 64; the oracle has the same switch, ppgo_debug_set_defer_depth)
    so that thousands of paths go through the stragglers' machinery — hand-over inside k_tail, the second launch beside the next round, the

@@ -498,7 +498,9 @@ struct KernelTimer {
 // groupPasses passes (the last one may be shorter; or a part of ONE group when groupPasses >= batch), the first starting at pass
 // firstPass of the render, consecutive groups of the launch stridePasses apart; group k accumulates into slot slot0 + k * slotStride.
 // addCount > 0 (one GPU): the launch's slots are added to image and film right after its film kernel (k_add_groups).
-struct GroupLaunch { unsigned int firstPass, groupPasses, stridePasses, slot0, slotStride; bool wholeFilm; unsigned int addCount; };
+// groupsDone: the launch ends every group it renders (false: a part of one group that later launches continue) — a filtered film resolves
+// a group's footprint into its slot then (ppg_set_rfilter).
+struct GroupLaunch { unsigned int firstPass, groupPasses, stridePasses, slot0, slotStride; bool wholeFilm; unsigned int addCount; bool groupsDone = true; };
 
 struct ppg_ctx {
     // properties (GP:1014-1085)
@@ -610,6 +612,12 @@ struct ppg_ctx {
     bool partialsPending = false;     // sharded: this rank's slots wait for the exchange (ppg_final_partials / ppg_final_partials_commit)
     bool partialsExported = false;
     unsigned int pendingGroups = 0;
+    // reconstruction filter (ppg_set_rfilter): `filtered` = anything but the default box, whose path (own pixel, unit weight: k_film,
+    // k_film_groups) stays as it is; a filtered film goes through the footprint partials of k_film_filter / k_film_resolve (ppg_kernels.h)
+    bool filtered = false;
+    int rfBorder = 0;
+    FilmFilter rf{};
+    DevBuf<float> d_foot;             // float[(2 rfBorder + 1)^2][7][W * H]: ONE footprint, whatever the batch schedule
     uint64_t samplesLocal = 0;        // samples this rank rendered in the current performRenderPasses
 
     // path state
@@ -1423,6 +1431,40 @@ int flushStragglers(ppg_ctx *ctx, bool hookRound) {
     return rc;
 }
 
+// Filtered film (ppg_set_rfilter).  The footprint: zeroed at the start of every ppg_render_passes() call, then source pixels add their
+// samples to it launch by launch (k_film_filter), and a resolve (k_film_resolve) moves it — zeroing it — into the call's image and the
+// iteration's film at the end of the call, or into a final group's slot when the group is complete.
+int prepareFootprint(ppg_ctx *ctx) {
+    const size_t T = 2 * (size_t)ctx->rfBorder + 1, floats = T * T * 7 * (size_t)ctx->W * (size_t)ctx->H;
+    HIP_CHECK(ctx->d_foot.reserve(floats));
+    HIP_CHECK(hipMemsetAsync(ctx->d_foot.p, 0, floats * 4, ctx->stream));
+    ctx->rf.W = ctx->W; ctx->rf.H = ctx->H;
+    return PPG_OK;
+}
+void launchFilmFilter(ppg_ctx *ctx, const PathState &P, unsigned long long seed, unsigned int base, unsigned int gs, unsigned int gstride, int j0, int j1) {
+    timedLaunch(ctx, "k_film_filter", (uint64_t)P.n_pix * (uint64_t)(j1 - j0), [&] {
+        const dim3 g((P.n_pix + 255) / 256), b(256);
+        switch (ctx->rfBorder) {
+        case 0: hipLaunchKernelGGL(k_film_filter<0>, g, b, 0, ctx->stream, P, ctx->rf, seed, base, gs, gstride, j0, j1, ctx->d_foot.p); break;
+        case 1: hipLaunchKernelGGL(k_film_filter<1>, g, b, 0, ctx->stream, P, ctx->rf, seed, base, gs, gstride, j0, j1, ctx->d_foot.p); break;
+        case 2: hipLaunchKernelGGL(k_film_filter<2>, g, b, 0, ctx->stream, P, ctx->rf, seed, base, gs, gstride, j0, j1, ctx->d_foot.p); break;
+        default: hipLaunchKernelGGL(k_film_filter<3>, g, b, 0, ctx->stream, P, ctx->rf, seed, base, gs, gstride, j0, j1, ctx->d_foot.p); break;
+        }
+    });
+}
+void launchFilmResolve(ppg_ctx *ctx, float *im, float *sq, float *w, float *film, float *film_w) {
+    const unsigned int n = (unsigned int)ctx->W * (unsigned int)ctx->H;
+    timedLaunch(ctx, "k_film_resolve", n, [&] {
+        const dim3 g((n + 255) / 256), b(256);
+        switch (ctx->rfBorder) {
+        case 0: hipLaunchKernelGGL(k_film_resolve<0>, g, b, 0, ctx->stream, ctx->rf, ctx->d_foot.p, im, sq, w, film, film_w); break;
+        case 1: hipLaunchKernelGGL(k_film_resolve<1>, g, b, 0, ctx->stream, ctx->rf, ctx->d_foot.p, im, sq, w, film, film_w); break;
+        case 2: hipLaunchKernelGGL(k_film_resolve<2>, g, b, 0, ctx->stream, ctx->rf, ctx->d_foot.p, im, sq, w, film, film_w); break;
+        default: hipLaunchKernelGGL(k_film_resolve<3>, g, b, 0, ctx->stream, ctx->rf, ctx->d_foot.p, im, sq, w, film, film_w); break;
+        }
+    });
+}
+
 // `batch` BlockedRenderProcesses (GP:1087-1106 / renderBlock GP:1587-1641) over all owned pixels in one set of launches.
 // adamRound: this batch is one round of the sampling-fraction optimiser.
 // A launch of whole groups of a final iteration's passes (include/ppg.h "Final iteration: groups of passes"): `batch` passes = groups of
@@ -1784,8 +1826,24 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
         const int sppBatch = ctx->sppPerPass * batch;
         const bool hasGl = gl != nullptr;
         const GroupLaunch glv = gl ? *gl : GroupLaunch{};
-        auto film = [ctx, Pf, sppBatch, hasGl, glv] {
+        const unsigned long long seed = R.seed;
+        const unsigned int base = R.pass_index_spp, gs = R.group_samples, gstride = R.group_stride;
+        auto film = [ctx, Pf, sppBatch, hasGl, glv, seed, base, gs, gstride] {
             hipStream_t st = ctx->stream;
+            if (ctx->filtered) {  // footprint partials; a final launch's groups one by one, each resolved into its slot once it is complete
+                if (!hasGl) launchFilmFilter(ctx, Pf, seed, base, 0u, 0u, 0, sppBatch);
+                else {
+                    const size_t n = ctx->nPixAll;
+                    for (int j0 = 0, k = 0; j0 < sppBatch; j0 += (int)gs, ++k) {
+                        launchFilmFilter(ctx, Pf, seed, base, gs, gstride, j0, std::min(sppBatch, j0 + (int)gs));
+                        if (!glv.groupsDone) continue;
+                        float *slot = ctx->d_partials.p + (size_t)(glv.slot0 + (unsigned int)k * glv.slotStride) * 7u * n;
+                        launchFilmResolve(ctx, slot, slot + 3 * n, slot + 6 * n, nullptr, nullptr);
+                    }
+                }
+                if (hasGl && glv.addCount) (void)addGroups(ctx, 0, glv.addCount);
+                return;
+            }
             timedLaunch(ctx, "k_film", Pf.n_pix, [&] {
                 if (hasGl) hipLaunchKernelGGL(k_film_groups, dim3((Pf.n_pix + 255) / 256), dim3(256), 0, st, Pf, sppBatch, glv.groupPasses * (unsigned int)ctx->sppPerPass,
                                               ctx->d_partials.p + (ctx->shardWorld > 1 ? 4 * (size_t)ctx->nPixAll : 0), glv.slot0, glv.slotStride, ctx->nPixAll);
@@ -1871,7 +1929,7 @@ int renderFinalGroups(ppg_ctx *ctx, int numPasses) {
                 if (ctx->seesCancel()) { stop = true; break; }
                 const unsigned int batch = std::min(launchPasses, total - done);
                 const bool lastPart = done + batch >= total;
-                GroupLaunch gl{firstPassAbs + g * G + done, batch, batch, world > 1 ? g : 0u, 1u, byRank, (world == 1 && lastPart) ? 1u : 0u};
+                GroupLaunch gl{firstPassAbs + g * G + done, batch, batch, world > 1 ? g : 0u, 1u, byRank, (world == 1 && lastPart) ? 1u : 0u, lastPart};
                 int rc = renderBatch(ctx, (int)batch, false, &gl, lastPart && m + 1 >= mine.size());
                 if (rc) return rc;
                 ctx->samplesLocal += pixelsMine * batch * ctx->sppPerPass;
@@ -1930,6 +1988,7 @@ int renderPassesNoStat(ppg_ctx *ctx, int numPasses) {  // GP:1217-1286
     const int roundPasses = rounds ? (int)ppg_adam_round_passes(ctx->sppPerPass, ctx->W, ctx->H, numPasses) : (ctx->isFinalIter ? ctx->maxBatchFinal : ctx->maxBatch);
     ctx->samplesLocal = 0;
     ctx->partialsPending = false; ctx->partialsExported = false;
+    if (ctx->filtered) { int rc = prepareFootprint(ctx); if (rc) return rc; }
     if (ctx->isFinalIter && ctx->budgetType == 0 && numPasses > 0) return renderFinalGroups(ctx, numPasses);
     // Cancelled while a round hook is installed (a sharded render with a learned sampling fraction): the other ranks enter the hook of
     // EVERY remaining round of this call, so this rank keeps entering it too — with empty rounds (no paths, no records; the host marks its
@@ -1982,6 +2041,8 @@ int renderPassesNoStat(ppg_ctx *ctx, int numPasses) {  // GP:1217-1286
         int rc = flushStragglers(ctx, deferRounds && ctx->passHook != nullptr);
         if (rc) return rc;
     }
+    // a filtered film: the call's footprint becomes its image / squared image / weights and is added to the iteration's film
+    if (ctx->filtered) launchFilmResolve(ctx, ctx->d_image.p, ctx->d_sq.p, ctx->d_imageW.p, ctx->d_film.p, ctx->d_filmW.p);
     return ctx->seesCancel() ? PPG_ERR_CANCELLED : PPG_OK;
 }
 
@@ -2788,10 +2849,13 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
     return PPG_OK;
 }
 
+static const char *kShardedFilter = "sharded filtered renders are not supported yet: a reconstruction filter other than the default box needs world = 1";
+
 int ppg_set_shard(ppg_ctx *ctx, int32_t rank, int32_t world, int32_t tile_size) {
     (void)hipSetDevice(ctx->device);
     ctx->quiesce();
     if (world < 1 || rank < 0 || rank >= world || tile_size < 1) { ctx->error = "bad shard"; return PPG_ERR_INVALID; }
+    if (world > 1 && ctx->filtered) { ctx->error = kShardedFilter; return PPG_ERR_INVALID; }
     ctx->shardRank = rank; ctx->shardWorld = world; ctx->tileSize = tile_size;
     ctx->pathsReady = false;
     if (ctx->haveScene) {
@@ -2837,6 +2901,94 @@ int ppg_debug_build_bvh(const float *positions, const uint32_t *indices, uint32_
     if (order_out) memcpy(order_out, bb.order.data(), (size_t)n_triangles * sizeof(uint32_t));
     return PPG_OK;
 }
+// ReconstructionFilter::configure (rfilter.cpp:37-55) with the eval() of src/rfilters/*.cpp, in the reference's float arithmetic
+static int rfilterTable(const ppg_rfilter *f, float table[32], float *radius, int32_t *border, std::string &err) {
+    const int type = f->type;
+    float r = 0.0f;
+    switch (type) {
+    case PPG_RFILTER_BOX:
+        if (!(std::isfinite(f->radius) && f->radius > 0.0f)) { err = "box filter: radius must be positive"; return PPG_ERR_INVALID; }
+        r = f->radius + 1e-5f; break;                                                        // box.cpp
+    case PPG_RFILTER_TENT: r = 1.0f; break;                                                  // tent.cpp
+    case PPG_RFILTER_GAUSSIAN:
+        if (!(std::isfinite(f->stddev) && f->stddev > 0.0f)) { err = "gaussian filter: stddev must be positive"; return PPG_ERR_INVALID; }
+        r = 4 * f->stddev; break;                                                            // gaussian.cpp
+    case PPG_RFILTER_MITCHELL:
+        if (!(std::isfinite(f->B) && std::isfinite(f->C))) { err = "mitchell filter: B and C must be finite"; return PPG_ERR_INVALID; }
+        r = 2.0f; break;                                                                     // mitchell.cpp
+    case PPG_RFILTER_CATMULLROM: r = 2.0f; break;                                            // catmullrom.cpp
+    case PPG_RFILTER_LANCZOS:
+        if (f->lobes < 1) { err = "lanczos filter: lobes must be >= 1"; return PPG_ERR_INVALID; }
+        r = (float)f->lobes; break;                                                          // lanczos.cpp
+    default: err = "unknown reconstruction filter type"; return PPG_ERR_INVALID;
+    }
+    const float stddev = f->stddev, B = f->B, C = f->C;
+    auto mitchell = [](float x, float B, float C) {
+        x = std::fabs(x);
+        const float x2 = x * x, x3 = x2 * x;
+        if (x < 1) return 1.0f / 6.0f * ((12 - 9 * B - 6 * C) * x3 + (-18 + 12 * B + 6 * C) * x2 + (6 - 2 * B));
+        if (x < 2) return 1.0f / 6.0f * ((-B - 6 * C) * x3 + (6 * B + 30 * C) * x2 + (-12 * B - 48 * C) * x + (8 * B + 24 * C));
+        return 0.0f;
+    };
+    auto eval = [&](float x) -> float {
+        switch (type) {
+        case PPG_RFILTER_BOX: return std::fabs(x) <= r ? 1.0f : 0.0f;
+        case PPG_RFILTER_TENT: return std::max(0.0f, 1.0f - std::fabs(x / r));
+        case PPG_RFILTER_GAUSSIAN: {
+            const float alpha = -1.0f / (2.0f * stddev * stddev);  // math::fastexp: (float) exp((double) x)
+            return std::max(0.0f, (float)std::exp((double)(alpha * x * x)) - (float)std::exp((double)(alpha * r * r)));
+        }
+        case PPG_RFILTER_MITCHELL: return mitchell(x, B, C);
+        case PPG_RFILTER_CATMULLROM: return mitchell(x, 0.0f, 0.5f);
+        default: {
+            x = std::fabs(x);
+            if (x < 1e-4f) return 1.0f;  // Epsilon (single precision)
+            if (x > r) return 0.0f;
+            const float x1 = (float)(M_PI * (double)x), x2 = x1 / r;
+            return (std::sin(x1) * std::sin(x2)) / (x1 * x2);
+        }
+        }
+    };
+    float sum = 0.0f;
+    for (int i = 0; i < 31; ++i) { table[i] = eval((r * (float)i) / 31); sum += table[i]; }
+    table[31] = 0.0f;
+    sum *= 2 * r / 31;
+    const float normalization = 1.0f / sum;
+    for (int i = 0; i < 31; ++i) table[i] *= normalization;
+    *radius = r;
+    *border = (int32_t)std::ceil(r - 0.5f);
+    if (!std::isfinite(normalization)) { err = "reconstruction filter: its samples sum to zero"; return PPG_ERR_INVALID; }
+    if (*border > PPG_RFILTER_MAX_BORDER) { err = "reconstruction filter: radius too large (border > 3, more than 7x7 pixels per sample)"; return PPG_ERR_INVALID; }
+    return PPG_OK;
+}
+
+void ppg_rfilter_default(ppg_rfilter *f) {
+    f->type = PPG_RFILTER_BOX; f->radius = 0.5f; f->stddev = 0.5f; f->B = 1.0f / 3.0f; f->C = 1.0f / 3.0f; f->lobes = 3;
+}
+
+int ppg_set_rfilter(ppg_ctx *ctx, const ppg_rfilter *f) {
+    ppg_rfilter d;
+    ppg_rfilter_default(&d);
+    if (!f) f = &d;
+    float table[32], r = 0.0f;
+    int32_t border = 0;
+    std::string err;
+    if (int rc = rfilterTable(f, table, &r, &border, err)) { ctx->error = err; return rc; }
+    const bool filtered = !(f->type == PPG_RFILTER_BOX && f->radius == 0.5f);
+    if (filtered && ctx->shardWorld > 1) { ctx->error = kShardedFilter; return PPG_ERR_INVALID; }
+    ctx->filtered = filtered;
+    ctx->rfBorder = border;
+    memcpy(ctx->rf.table, table, sizeof table);
+    ctx->rf.radius = r; ctx->rf.scale = 31 / r;  // m_scaleFactor = MTS_FILTER_RESOLUTION / m_radius
+    return PPG_OK;
+}
+
+int ppg_debug_rfilter_table(const ppg_rfilter *f, float table[32], float *radius, int32_t *border) {
+    if (!f || !table || !radius || !border) return PPG_ERR_INVALID;
+    std::string err;
+    return rfilterTable(f, table, radius, border, err);
+}
+
 int ppg_release_cached_memory(int32_t device) {
     int prev = 0;
     (void)hipGetDevice(&prev);

@@ -2329,6 +2329,118 @@ static __global__ void k_add_groups(unsigned int n_img, float *partials, unsigne
     image_w[i] = iw; film_w[i] = fw;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Reconstruction filters other than the default box (include/ppg.h ppg_set_rfilter): ImageBlock::put (imageblock.h:147-190) with the
+// discretised table of ReconstructionFilter::configure (rfilter.cpp:37-55), made deterministic through FOOTPRINT partials.
+//   F = float[taps][7][W * H], taps = (2B + 1)², tap o = (dy + B) * (2B + 1) + (dx + B); the slot (o, c) that source pixel s adds to target
+//   pixel s + (dx, dy) lives at F[(o * 7 + c) * W * H + s] — indexed by the SOURCE pixel, so the 64 lanes of a wave (neighbouring source
+//   pixels of a row) read and write 64 consecutive floats per (o, c), and the resolve's lanes (neighbouring targets) read 64 consecutive
+//   floats too (DESIGN.md "Film reconstruction filter").  c = image RGB, squared image RGB, weight.
+// ------------------------------------------------------------------------------------------------
+#define PPG_RFILTER_MAX_BORDER 3
+struct FilmFilter {
+    float table[32];     // m_values: 31 normalised samples of eval at radius * i / 31, then 0
+    float radius, scale; // m_radius, m_scaleFactor = 31 / m_radius
+    int W, H;            // film size
+};
+
+// Source pixel P.pixels[k] (one thread each) adds the launch's samples [j0, j1) — w·L, w·L², w per tap, in sample order — to its footprint
+// slots.  The sample position is recomputed from the path key exactly as k_generate draws it (same sample index formula, dims 0 and 1).
+// Taps are walked row by row: one row's (2B + 1) x 7 accumulators stay in registers while the samples go by.
+template <int B>
+__global__ __launch_bounds__(256) void k_film_filter(PathState P, FilmFilter ff, unsigned long long seed, unsigned int pass_index_spp,
+                                                     unsigned int group_samples, unsigned int group_stride, int j0, int j1, float *foot) {
+    constexpr int T = 2 * B + 1;
+    __shared__ float tab[32];
+    if (threadIdx.x < 32) tab[threadIdx.x] = ff.table[threadIdx.x];
+    __syncthreads();
+    const unsigned int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= P.n_pix) return;
+    const unsigned int pixel = P.pixels[k];
+    const int W = ff.W, H = ff.H;
+    const size_t n = (size_t)W * (size_t)H;
+    const int px = (int)(pixel % (unsigned int)W), py = (int)(pixel / (unsigned int)W);
+    const float r = ff.radius, scale = ff.scale;
+    for (int dy = -B; dy <= B; ++dy) {
+        const int ty = py + dy;
+        if (ty < 0 || ty >= H) continue;
+        float acc[T][7];
+#pragma unroll
+        for (int dx = -B; dx <= B; ++dx) {
+            const int tx = px + dx;
+            const size_t o = (size_t)((dy + B) * T + (dx + B));
+#pragma unroll
+            for (int c = 0; c < 7; ++c) acc[dx + B][c] = (tx >= 0 && tx < W) ? foot[(o * 7 + c) * n + pixel] : 0.0f;
+        }
+        for (int j = j0; j < j1; ++j) {
+            const unsigned int ju = (unsigned int)j;
+            const unsigned int sample = group_samples ? pass_index_spp + (ju / group_samples) * group_stride + (ju % group_samples) : pass_index_spp + ju;
+            const unsigned int key = ppg_path_key(seed, pixel, sample);
+            const float u1 = ppg_rand(key, 0u), u2 = ppg_rand(key, 1u);
+            const float posx = ((float)px + u1) - 0.5f, posy = ((float)py + u2) - 0.5f;  // samplePos (GP:1620) - 0.5
+            const int ylo = max((int)ceilf(posy - r), 0), yhi = min((int)floorf(posy + r), H - 1);
+            if (ty < ylo || ty > yhi) continue;
+            const int xlo = max((int)ceilf(posx - r), 0), xhi = min((int)floorf(posx + r), W - 1);
+            const float wy = tab[min((int)fabsf(((float)ty - posy) * scale), 31)];
+            const float4 l = P.li[(size_t)j * P.n_pix + k];
+            const float qx = l.x * l.x, qy = l.y * l.y, qz = l.z * l.z;  // spec * spec, put into the squared block
+#pragma unroll
+            for (int dx = -B; dx <= B; ++dx) {
+                const int tx = px + dx;
+                if (tx < xlo || tx > xhi) continue;
+                const float w = tab[min((int)fabsf(((float)tx - posx) * scale), 31)] * wy;
+                acc[dx + B][0] += w * l.x; acc[dx + B][1] += w * l.y; acc[dx + B][2] += w * l.z;
+                acc[dx + B][3] += w * qx; acc[dx + B][4] += w * qy; acc[dx + B][5] += w * qz;
+                acc[dx + B][6] += w;
+            }
+        }
+#pragma unroll
+        for (int dx = -B; dx <= B; ++dx) {
+            const int tx = px + dx;
+            if (tx < 0 || tx >= W) continue;
+            const size_t o = (size_t)((dy + B) * T + (dx + B));
+#pragma unroll
+            for (int c = 0; c < 7; ++c) foot[(o * 7 + c) * n + pixel] = acc[dx + B][c];
+        }
+    }
+}
+
+// Target pixel t (one thread each, the whole film) sums its taps from zero — dy = -B .. B, within each dy dx = -B .. B; the tap (dx, dy)
+// holds what source pixel t - (dx, dy) put there — zeroes them, and adds the sums to im (3 n) / sq (3 n) / w (n) and, if film != nullptr, to
+// film / film_w: the image of a ppg_render_passes() call and the iteration's film, or (film == nullptr) a final group's partial slot.
+template <int B>
+__global__ __launch_bounds__(256) void k_film_resolve(FilmFilter ff, float *foot, float *im, float *sq, float *w, float *film, float *film_w) {
+    constexpr int T = 2 * B + 1;
+    const int W = ff.W, H = ff.H;
+    const size_t n = (size_t)W * (size_t)H;
+    const unsigned int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n) return;
+    const int tx = (int)(t % (unsigned int)W), ty = (int)(t / (unsigned int)W);
+    float s[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (int dy = -B; dy <= B; ++dy) {
+        const int sy = ty - dy;
+        if (sy < 0 || sy >= H) continue;
+#pragma unroll
+        for (int dx = -B; dx <= B; ++dx) {
+            const int sx = tx - dx;
+            if (sx < 0 || sx >= W) continue;
+            const size_t o = (size_t)((dy + B) * T + (dx + B)), src = (size_t)sy * W + sx;
+#pragma unroll
+            for (int c = 0; c < 7; ++c) {
+                float *f = foot + (o * 7 + c) * n + src;
+                s[c] += *f;
+                *f = 0.0f;
+            }
+        }
+    }
+    for (int c = 0; c < 3; ++c) { im[3 * (size_t)t + c] += s[c]; sq[3 * (size_t)t + c] += s[3 + c]; }
+    w[t] += s[6];
+    if (film) {
+        for (int c = 0; c < 3; ++c) film[3 * (size_t)t + c] += s[c];
+        film_w[t] += s[6];
+    }
+}
+
 // per-pixel variance estimate of performRenderPasses (GP:1300-1311); the clamped luminance goes to `lum`, stored x-major
 // (index x * H + y) — the order the reference's serial loop sums it in, so the host adds a contiguous array
 static __global__ void k_variance(int n, int W, int N, const float *image, const float *sq_image, const float *image_w, float *var_rgb, float *lum) {

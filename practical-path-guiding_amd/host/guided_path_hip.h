@@ -49,6 +49,8 @@ struct SceneData {
     std::vector<float> texcoords;                  // per-vertex texture coordinates (NaN rows: none) or empty
     mutable std::vector<ppg_texture> textures;     // bitmap textures; their pixels in texturePixels
     std::vector<std::vector<float>> texturePixels;
+    bool hasRFilter = false;                       // the film's reconstruction filter (ppg_set_rfilter) when it is not the default box
+    ppg_rfilter rfilter{};
 
     ppg_scene view() const {
         ppg_scene s{};
@@ -150,10 +152,13 @@ public:
         // ppg_begin_render consumes it; m_cancelled, which the hooks read, is reset when the render is over)
         struct Reset { std::atomic<bool> &f; ~Reset() { f.store(false); } } reset{m_cancelled};
         m_filmComplete = false;
+        // (refused before the first exchange: every rank holds the same scene and fails here alike)
+        if (reducer && reducer->world() > 1 && scene.hasRFilter) throw std::runtime_error("sharded filtered renders are not supported yet: the scene's film has a reconstruction filter other than the default box");
         if (reducer) reducer->beginRender();
         const bool spp = std::string(m_cfg.budgetType) == "spp";
         ppg_scene sv = scene.view();
         check(ppg_set_scene(m_ctx, &sv), "ppg_set_scene");
+        check(ppg_set_rfilter(m_ctx, scene.hasRFilter ? &scene.rfilter : nullptr), "ppg_set_rfilter");
         if (reducer) check(ppg_set_shard(m_ctx, reducer->rank(), reducer->world(), 32), "ppg_set_shard");
         m_w = scene.camera.width; m_h = scene.camera.height;
         {

@@ -60,6 +60,8 @@ public:
         pointStrings();
     }
     void setSeed(uint64_t seed) { m_cfg.seed = seed; }
+    // the film's reconstruction filter (the scene's <rfilter>); nullptr = the default box
+    void setRFilter(const ppg_rfilter *f) { m_hasRFilter = f != nullptr; if (f) m_rfilter = *f; }
     const ppg_config &config() const { return m_cfg; }
 
     // PPG_OK, PPG_ERR_CANCELLED, or an error code with `err` set.  May be called again (a new context per render, like a new RenderJob).
@@ -83,6 +85,8 @@ public:
         }
         m_hasFilm = false;
         rc = ppg_set_scene(ctx, &scene);  // (a cancel() during these seconds of BVH build stays set in the context: ppg_render returns at once)
+        if (rc != PPG_OK) { err = ppg_last_error(ctx); return rc; }
+        rc = ppg_set_rfilter(ctx, m_hasRFilter ? &m_rfilter : nullptr);
         if (rc != PPG_OK) { err = ppg_last_error(ctx); return rc; }
         m_hasFilm = true;  // (the film exists from here on: black if the cancel came before the first pass)
         rc = ppg_render(ctx);
@@ -118,6 +122,8 @@ private:
     std::atomic<ppg_ctx *> m_ctx{nullptr};
     std::atomic<bool> m_cancelRequested{false};
     bool m_hasFilm = false;
+    bool m_hasRFilter = false;
+    ppg_rfilter m_rfilter{};
     std::mutex m_mutex;
 };
 

@@ -98,6 +98,11 @@ static bool loadSceneChecked(const char *path, SceneData &s) {
             s.textures.push_back(t); s.texturePixels.push_back(std::move(px));
         }
     }
+    if (hdr[5] & 64) {  // bit 6: the film's reconstruction filter (ppg_rfilter), only when it is not the default box
+        if (!fits(sizeof(ppg_rfilter))) return false;
+        f.read((char *)&s.rfilter, sizeof(ppg_rfilter));
+        s.hasRFilter = true;
+    }
     return (bool)f;
 }
 
@@ -167,7 +172,7 @@ static bool saveScene(const char *path, const SceneData &s) {
     std::ofstream f(path, std::ios::binary);
     const uint32_t hdr[6] = {(uint32_t)(s.positions.size() / 3), (uint32_t)(s.indices.size() / 3), (uint32_t)s.materials.size(), (uint32_t)s.emitters.size(),
                              s.normals.empty() ? 0u : 1u, (s.hasEnvironment ? 1u : 0u) | (s.rtrans.empty() ? 0u : 2u) | (s.spheres.empty() ? 0u : 4u) | (s.hasEnvmap ? 8u : 0u) |
-                                 (s.texcoords.empty() ? 0u : 16u) | (s.textures.empty() ? 0u : 32u)};
+                                 (s.texcoords.empty() ? 0u : 16u) | (s.textures.empty() ? 0u : 32u) | (s.hasRFilter ? 64u : 0u)};
     f.write("PPGS", 4); f.write((const char *)hdr, sizeof hdr);
     f.write((const char *)s.positions.data(), s.positions.size() * 4);
     if (!s.normals.empty()) f.write((const char *)s.normals.data(), s.normals.size() * 4);
@@ -204,6 +209,7 @@ static bool saveScene(const char *path, const SceneData &s) {
             f.write((const char *)s.texturePixels[k].data(), s.texturePixels[k].size() * 4);
         }
     }
+    if (s.hasRFilter) f.write((const char *)&s.rfilter, sizeof(ppg_rfilter));
     return (bool)f;
 }
 
@@ -298,6 +304,7 @@ int main(int argc, char **argv) {
     if (pluginCore) {
         PluginCore core;
         core.configure(props);
+        core.setRFilter(scene.hasRFilter ? &scene.rfilter : nullptr);
         core.setSeed((uint64_t)std::stoull(props.getString("seed", "0")));
         std::string dest = out;
         const size_t dot = dest.find_last_of('.');
@@ -322,6 +329,8 @@ int main(int argc, char **argv) {
         std::unique_ptr<RcclReducer> reducer;
         if (!ncclIdFile.empty()) {
             if (world < 1 || rank < 0 || rank >= world) { std::cerr << "--rank / --world out of range\n"; return 2; }
+            // (before the communicator exists: every rank reads the same scene and stops here alike)
+            if (world > 1 && scene.hasRFilter) { std::cerr << "sharded filtered renders are not supported yet: the scene's film has a reconstruction filter other than the default box\n"; return 2; }
             if (!props.values.count("device")) props.values["device"] = std::to_string(rank);  // one GPU per rank of the node
             const auto t0 = std::chrono::steady_clock::now();
             // the run tag keeps a rank from accepting the id file a crashed earlier run left at the same path: any string all ranks of THIS run share

@@ -729,7 +729,7 @@ public:
         if (film) {
             fp = props(*film);
             const XmlNode *rf = film->child("rfilter");
-            if (rf && rf->get("type") != "box") throw std::runtime_error("rfilter type '" + rf->get("type") + "' is not supported (box only; hdrfilm's default 'gaussian' neither)");
+            if (rf) rfilter(*rf, out.scene);
             if (!rf) out.warnings.push_back("no <rfilter>: Mitsuba would default to gaussian; the box filter is used");
         }
         const int W = m_w ? m_w : (fp.count("width") ? std::stoi(fp["width"]) : 768), H = m_h ? m_h : (fp.count("height") ? std::stoi(fp["height"]) : 576);
@@ -983,6 +983,39 @@ private:
         }
         return o;
     }
+    // <rfilter> of the hdrfilm (mitsuba/src/rfilters/): the six types with Mitsuba's parameters and defaults (include/ppg.h ppg_set_rfilter);
+    // the default box (radius 0.5) leaves the scene without one.  Unknown types / parameters and values the filter cannot take throw.
+    void rfilter(const XmlNode &e, SceneData &scene) const {
+        static const char *types[] = {"box", "tent", "gaussian", "mitchell", "catmullrom", "lanczos"};
+        const std::string t = e.get("type");
+        int type = -1;
+        for (int i = 0; i < 6; ++i) if (t == types[i]) type = i;
+        if (type < 0) throw std::runtime_error("rfilter type '" + t + "' is not supported (box, tent, gaussian, mitchell, catmullrom, lanczos)");
+        ppg_rfilter f{type, 0.5f, 0.5f, 1.0f / 3.0f, 1.0f / 3.0f, 3};  // Mitsuba's defaults (= ppg_rfilter_default)
+        for (auto &c : e.children) {
+            const std::string n = c.get("name"), v = sub(c.get("value"));
+            const bool isFloat = c.tag == "float", isInt = c.tag == "integer";
+            size_t used = 0;
+            try {
+                if (type == PPG_RFILTER_BOX && n == "radius" && isFloat) f.radius = std::stof(v, &used);
+                else if (type == PPG_RFILTER_GAUSSIAN && n == "stddev" && isFloat) f.stddev = std::stof(v, &used);
+                else if (type == PPG_RFILTER_MITCHELL && n == "B" && isFloat) f.B = std::stof(v, &used);
+                else if (type == PPG_RFILTER_MITCHELL && n == "C" && isFloat) f.C = std::stof(v, &used);
+                else if (type == PPG_RFILTER_LANCZOS && n == "lobes" && isInt) f.lobes = std::stoi(v, &used);
+                else throw std::runtime_error("rfilter '" + t + "': unsupported parameter <" + c.tag + " name='" + n + "'>");
+            } catch (const std::logic_error &) { used = 0; }
+            if (used == 0 || used != v.size()) throw std::runtime_error("rfilter '" + t + "': bad value '" + v + "' for '" + n + "'");
+        }
+        // the radius as the filter sets it, and m_borderSize = ceil(radius - 0.5) (rfilter.cpp:37-55): at most 3 (7x7 pixels per sample)
+        const float radius = type == PPG_RFILTER_BOX ? f.radius + 1e-5f : type == PPG_RFILTER_TENT ? 1.0f : type == PPG_RFILTER_GAUSSIAN ? 4 * f.stddev
+                             : type == PPG_RFILTER_LANCZOS ? (float)f.lobes : 2.0f;
+        const bool ok = std::isfinite(f.radius) && std::isfinite(f.stddev) && std::isfinite(f.B) && std::isfinite(f.C) && f.lobes >= 1 &&
+                        std::isfinite(radius) && radius > 0 && (int)std::ceil(radius - 0.5f) <= 3;
+        if (!ok) throw std::runtime_error("rfilter '" + t + "': parameter out of range (radius must be positive, at most 7x7 pixels per sample)");
+        scene.hasRFilter = !(type == PPG_RFILTER_BOX && f.radius == 0.5f);
+        scene.rfilter = f;
+    }
+
     std::map<std::string, std::string> props(const XmlNode &e) const {
         std::map<std::string, std::string> o;
         for (auto &c : e.children)

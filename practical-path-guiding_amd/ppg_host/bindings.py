@@ -150,6 +150,48 @@ class Texture(C.Structure):
         return o
 
 
+class RFilter(C.Structure):
+    """ppg_rfilter — the film's reconstruction filter (mitsuba/src/rfilters/).  As a dict (SceneDesc.rfilter): {"type": name} plus the
+    type's own parameters — box: radius, gaussian: stddev, mitchell: B, C, lanczos: lobes; None = the default box (radius 0.5)."""
+    _fields_ = [("type", C.c_int32), ("radius", C.c_float), ("stddev", C.c_float), ("B", C.c_float), ("C", C.c_float), ("lobes", C.c_int32)]
+    TYPES = ("box", "tent", "gaussian", "mitchell", "catmullrom", "lanczos")
+    PARAMS = dict(box=("radius",), tent=(), gaussian=("stddev",), mitchell=("B", "C"), catmullrom=(), lanczos=("lobes",))
+    DEFAULTS = dict(radius=0.5, stddev=0.5, B=1.0 / 3.0, C=1.0 / 3.0, lobes=3)
+
+    @classmethod
+    def from_dict(cls, d):
+        d = d or {"type": "box"}
+        t = d["type"]
+        if t not in cls.TYPES:
+            raise ValueError("unknown reconstruction filter %r" % (t,))
+        unknown = set(d) - {"type"} - set(cls.PARAMS[t])
+        if unknown:
+            raise ValueError("%s filter: unknown parameters %s" % (t, sorted(unknown)))
+        v = dict(cls.DEFAULTS, **{k: d[k] for k in cls.PARAMS[t] if k in d})
+        return cls(cls.TYPES.index(t), v["radius"], v["stddev"], v["B"], v["C"], int(v["lobes"]))
+
+    def as_dict(self):
+        """None for the default box, else {"type", the type's parameters}"""
+        t = self.TYPES[self.type]
+        if t == "box" and self.radius == np.float32(0.5):
+            return None
+        d = {"type": t}
+        for k in self.PARAMS[t]:
+            d[k] = int(self.lobes) if k == "lobes" else float(getattr(self, k))
+        return d
+
+
+def rfilter_table(desc):
+    """ppg_debug_rfilter_table (host only): (table float32[32], radius, border) of a filter dict (None = default box)."""
+    lib = C.CDLL(hip_library_path())
+    f = RFilter.from_dict(desc)
+    table, r, b = np.zeros(32, np.float32), C.c_float(), C.c_int32()
+    rc = lib.ppg_debug_rfilter_table(C.byref(f), _p(table, C.c_float), C.byref(r), C.byref(b))
+    if rc != 0:
+        raise PPGError(rc, "invalid reconstruction filter %r" % (desc,))
+    return table, float(r.value), int(b.value)
+
+
 class Emitter(C.Structure):
     _fields_ = [("radiance", C.c_float * 3), ("_pad", C.c_float)]
 
@@ -317,6 +359,19 @@ class Engine:
         self._scene_keep = (pos, idx, tm, te, nrm, mats, ems, rt, sph_arr, envmap, uvs, tex_arr, tex_keep)
         self._call("set_scene", C.byref(s))
         self.width, self.height = cam["width"], cam["height"]
+        # the film's reconstruction filter comes with the scene description (None / absent: the default box)
+        # (a context that never had a filter is left alone: ppg_set_rfilter is only called for a filtered scene or to reset one)
+        rf = getattr(desc, "rfilter", None)
+        if self.prefix == "ppg_":
+            if rf is not None or getattr(self, "_rfilter", None) is not None:
+                self.set_rfilter(rf)
+        elif rf is not None:
+            raise NotImplementedError("%s: reconstruction filters other than the default box are not implemented here" % self.prefix)
+
+    def set_rfilter(self, rfilter):
+        """ppg_set_rfilter: rfilter = a filter dict (RFilter) or None for the default box"""
+        self._rfilter = RFilter.from_dict(rfilter)
+        self._call("set_rfilter", C.byref(self._rfilter))
 
     def set_shard(self, rank, world, tile_size=32):
         self._call("set_shard", C.c_int32(rank), C.c_int32(world), C.c_int32(tile_size))

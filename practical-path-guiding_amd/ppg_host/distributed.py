@@ -21,6 +21,17 @@ import ctypes as C
 import numpy as np
 
 
+SHARDED_FILTER_MSG = "sharded filtered renders are not supported yet: the scene's reconstruction filter %r needs a one-GPU render"
+
+
+def check_shardable(desc):
+    """Raise before any collective is set up if a sharded render cannot take this scene: a film filter other than the default box
+    (include/ppg.h ppg_set_rfilter).  Every rank holds the same scene description, so every rank fails here alike."""
+    rf = getattr(desc, "rfilter", None)
+    if rf is not None:
+        raise ValueError(SHARDED_FILTER_MSG % (rf,))
+
+
 class _DevArray:
     """Exposes a raw device pointer to torch through __cuda_array_interface__ (zero copy)."""
 

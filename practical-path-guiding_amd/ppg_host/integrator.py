@@ -74,7 +74,10 @@ class GuidedPathTracer:
     def render(self, scene=None):
         e, p = self.engine, self.props
         if scene is not None:
-            e.set_scene(scene)
+            if self.reducer is not None:  # (before the first exchange: all ranks refuse the same scene alike)
+                from .distributed import check_shardable
+                check_shardable(scene)
+            e.set_scene(scene)  # (the film's reconstruction filter comes with it: Engine.set_rfilter)
         # (cancel() is sticky in the library: one that arrived before this call cancels this render in begin_render below; the flag the hooks
         # read is cleared BEFORE that, so that a cancel() arriving any time after this line is seen by them)
         self._cancelled = False

@@ -3,7 +3,7 @@
   integrator  guided_path (every property of GP:1014-1085 and integrator.cpp:192-218)
   sensor      perspective (fov, fovAxis, nearClip, farClip, toWorld; focusDistance ignored: pinhole),
               nested sampler (independent; sampleCount / seed do not steer guided_path, GP:1342-1374) and
-              film hdrfilm (width, height; rfilter box)
+              film hdrfilm (width, height; rfilter box / tent / gaussian / mitchell / catmullrom / lanczos)
   shapes      obj (filename, toWorld, faceNormals, maxSmoothAngle, flipNormals, flipTexCoords, collapse),
               serialized (filename, shapeIndex, toWorld, faceNormals, maxSmoothAngle, flipNormals), ply (filename, toWorld, faceNormals, maxSmoothAngle, flipNormals), rectangle / cube (toWorld, flipNormals),
               sphere (center, radius, toWorld = rotation x uniform scale, flipNormals) — analytic, not tessellated
@@ -553,6 +553,45 @@ def _props(elem, sub):
     return out
 
 
+def parse_rfilter(elem, sub=lambda v: v):
+    """<rfilter type=...> of an hdrfilm (mitsuba/src/rfilters/): a SceneDesc.rfilter dict, None for the default box (radius 0.5).
+    Parameters and defaults are Mitsuba's; an unknown type or parameter, or a value the filter cannot take, raises."""
+    t = elem.get("type")
+    allowed = dict(box={"radius": "float"}, tent={}, gaussian={"stddev": "float"}, mitchell={"B": "float", "C": "float"}, catmullrom={},
+                   lanczos={"lobes": "integer"})
+    if t not in allowed:
+        raise SceneError("rfilter type %r is not supported (box, tent, gaussian, mitchell, catmullrom, lanczos)" % (t,))
+    out = {"type": t}
+    for c in elem:
+        if not isinstance(c.tag, str):
+            continue  # comments
+        n = c.get("name")
+        if n not in allowed[t] or c.tag != allowed[t][n]:
+            raise SceneError("rfilter %r: unsupported parameter <%s name=%r>" % (t, c.tag, n))
+        try:
+            out[n] = int(sub(c.get("value"))) if c.tag == "integer" else float(sub(c.get("value")))
+        except (TypeError, ValueError):
+            raise SceneError("rfilter %r: bad value %r for %r" % (t, c.get("value"), n))
+    bad = ((t == "box" and not out.get("radius", 0.5) > 0) or (t == "gaussian" and not out.get("stddev", 0.5) > 0) or
+           (t == "lanczos" and out.get("lobes", 3) < 1) or any(not math.isfinite(v) for k, v in out.items() if k != "type"))
+    if bad:
+        raise SceneError("rfilter %r: parameter out of range: %r" % (t, out))
+    from .bindings import RFilter
+    desc = RFilter.from_dict(out).as_dict()  # (None for the default box)
+    if _rfilter_border(RFilter.from_dict(out)) > 3:
+        raise SceneError("rfilter %r: radius too large (more than 7x7 pixels per sample): %r" % (t, out))
+    return desc
+
+
+def _rfilter_border(f):
+    """m_borderSize = ceil(radius - 0.5) of ReconstructionFilter::configure (rfilter.cpp:37-55), radius as the filters set it"""
+    f32 = np.float32
+    t = f.TYPES[f.type]
+    r = {"box": f32(f.radius) + f32(1e-5), "tent": f32(1), "gaussian": f32(4) * f32(f.stddev), "mitchell": f32(2), "catmullrom": f32(2),
+         "lanczos": f32(f.lobes)}[t]
+    return int(np.ceil(f32(r) - f32(0.5)))
+
+
 def load_scene(path, defines=None, strict=True, width=None, height=None, data_dir=None, mitsuba_src=None):
     """Parse `path` → (SceneDesc, integrator properties for ppg_create, info dict).
 
@@ -601,8 +640,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
     if film is not None and film.get("type") not in ("hdrfilm", "ldrfilm", None):
         raise SceneError("film type %r is not supported" % film.get("type"))
     rf = film.find("rfilter") if film is not None else None
-    if rf is not None and rf.get("type") != "box":
-        raise SceneError("rfilter type %r is not supported (box only; hdrfilm's default 'gaussian' neither)" % rf.get("type"))
+    rfilter = parse_rfilter(rf, sub) if rf is not None else None
     if rf is None:
         warnings.append("no <rfilter>: Mitsuba would default to gaussian; the box filter is used")
     W = int(width or fp.get("width", 768)); H = int(height or fp.get("height", 576))
@@ -1084,7 +1122,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         pos, idx, tmat, tem = [np.zeros((0, 3), f32)], [np.zeros((0, 3), np.uint32)], [np.zeros(0, np.uint32)], [np.zeros(0, np.int32)]
     desc = SceneDesc(np.concatenate(pos).astype(f32), np.concatenate(idx).astype(np.uint32), np.concatenate(tmat), np.concatenate(tem),
                      materials, emitters, camera, normals, environment, np.stack(rt_slices).astype(f32) if rt_slices else None, spheres, envmap,
-                     np.concatenate(uvl).astype(f32) if any_uvs else None, textures)
+                     np.concatenate(uvl).astype(f32) if any_uvs else None, textures, rfilter)
     info["warnings"] = warnings
     return desc, props, info
 
