@@ -290,6 +290,26 @@ void ppg_rfilter_default(ppg_rfilter *f);                 /* box, radius 0.5 (an
 int ppg_set_rfilter(ppg_ctx *ctx, const ppg_rfilter *f); /* before ppg_begin_render; NULL = default */
 
 /* ------------------------------------------------------------------------------------------------
+ * Thin-lens camera (mitsuba/src/sensors/thinlens.cpp: ThinLens::sampleRayDifferential, :321-356).  The scene's ppg_camera stays what it
+ * is (sample_to_camera, camera_to_world, clip distances: the perspective camera's own); the lens adds an aperture disk of radius
+ * aperture_radius (world units) and a focal plane at focus_distance along the camera's z axis.  Per sample:
+ *   dims 0, 1  pixel position, as for the pinhole;  dims 2, 3  aperture sample (renderBlock draws it right after the pixel sample when the
+ *   sensor needs one, GP:1613-1630); the path continues from dim 4 (a pinhole's path still starts at dim 2).
+ *   (tx, ty) = squareToUniformDiskConcentric(dims 2, 3) * aperture_radius;  apertureP = (tx, ty, 0)
+ *   nearP = sample_to_camera(pixel / resolution);  focusP = nearP * (focus_distance / nearP.z);  d = normalize(focusP - apertureP)
+ *   mint = near_clip / d.z, maxt = far_clip / d.z;  origin = camera_to_world.transformAffine(apertureP), direction = camera_to_world(d)
+ * The scene's box (the SD-tree's domain, the environment's bounding sphere) takes in the aperture disk instead of the pinhole position
+ * (Scene::initializeBidirectional, thinlens.cpp:516-520).
+ * NULL = pinhole (the default).  Call before ppg_begin_render.  The lens belongs to the context, not to the scene: ppg_set_scene keeps it
+ * (like the reconstruction filter).  A radius or distance that is not finite and above 0 is PPG_ERR_INVALID (the loaders turn Mitsuba's
+ * apertureRadius 0 into Epsilon = 1e-4 first, as ThinLens does).  Sharded renders need nothing more: the lens acts per sample.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ppg_lens {
+    float aperture_radius, focus_distance;
+} ppg_lens;
+int ppg_set_lens(ppg_ctx *ctx, const ppg_lens *lens);
+
+/* ------------------------------------------------------------------------------------------------
  * Rendering.  ppg_render() is GuidedPathTracer::render() (GP:1516-1585, IH:74-75) in one call.
  * The stepwise calls expose its phases so a multi-GPU driver can all-reduce the SD-tree statistics
  * between ppg_render_passes() and ppg_build_sdtree(); ppg_render() is exactly their composition

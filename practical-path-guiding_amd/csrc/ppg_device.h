@@ -122,6 +122,8 @@ struct DevCamera {
     float s2c[16], c2w[16];
     float near_clip, far_clip, inv_w, inv_h;
     int width, height;
+    int lens;                 // thin lens (ppg_set_lens): 0 = pinhole
+    float aperture, focus;    // its aperture radius and focus distance
 };
 
 #define PPG_MAT_STRIDE 6  // float4 per material: (reflectance, type) (specular, alpha) (eta, flags) (k, fdrInt) (opacity, rtrans slice) (texture word, -, -, -)

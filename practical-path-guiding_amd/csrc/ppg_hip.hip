@@ -595,6 +595,9 @@ struct ppg_ctx {
     DevBuf<float4> d_bvhTop;  // BvhBuilder::topCut
     DevScene scene{};
     float aabbMin[3], aabbMax[3];  // Scene::getAABB()
+    float geomMin[3], geomMax[3];  // the kd-tree's box (m_kdtree->getAABB()): Scene::getAABB() before the sensor's box is added
+    bool lensOn = false;           // ppg_set_lens: thin lens (kept across ppg_set_scene; copied into scene.cam)
+    ppg_lens lens{};
     int W = 0, H = 0;
 
     // shard
@@ -2490,6 +2493,40 @@ void ppg_destroy(ppg_ctx *ctx) {
 
 const char *ppg_last_error(const ppg_ctx *ctx) { return ctx ? ctx->error.c_str() : g_createError.c_str(); }
 
+// Scene::getAABB() (scene.cpp:386-414): the kd-tree's box expanded by the sensor's box — the pinhole position (perspective.cpp:444-446) or,
+// with a thin lens, the aperture disk (-r, -r, 0) .. (r, r, 0) through the camera's world transform (thinlens.cpp:516-520, track.cpp:123-143)
+static void sceneBox(ppg_ctx *ctx, const float *c2w) {
+    for (int a = 0; a < 3; ++a) { ctx->aabbMin[a] = ctx->geomMin[a]; ctx->aabbMax[a] = ctx->geomMax[a]; }
+    if (!ctx->lensOn) {
+        for (int a = 0; a < 3; ++a) {
+            float c = c2w[4 * a + 3];
+            ctx->aabbMin[a] = ppg_min(ctx->aabbMin[a], c);
+            ctx->aabbMax[a] = ppg_max(ctx->aabbMax[a], c);
+        }
+        return;
+    }
+    const float r = ctx->lens.aperture_radius;
+    for (int j = 0; j < 8; ++j) {  // AABB::getCorner(j) of the flat box, Transform::operator()(Point)
+        const float p[3] = {(j & 1) ? r : -r, (j & 2) ? r : -r, 0.0f};
+        float q[4];
+        for (int a = 0; a < 4; ++a) q[a] = c2w[4 * a] * p[0] + c2w[4 * a + 1] * p[1] + c2w[4 * a + 2] * p[2] + c2w[4 * a + 3];
+        for (int a = 0; a < 3; ++a) {
+            const float v = q[3] == 1.0f ? q[a] : q[a] / q[3];
+            ctx->aabbMin[a] = ppg_min(ctx->aabbMin[a], v);
+            ctx->aabbMax[a] = ppg_max(ctx->aabbMax[a], v);
+        }
+    }
+}
+
+// Constant / EnvironmentMap: bounding sphere of createShape() (constant.cpp:67-78, envmap.cpp:330-355) around Scene::getAABB()
+static void envBSphere(ppg_ctx *ctx) {
+    float c[3], r2 = 0;
+    for (int a = 0; a < 3; ++a) { c[a] = (ctx->aabbMax[a] + ctx->aabbMin[a]) * 0.5f; }
+    const float dx = c[0] - ctx->aabbMax[0], dy = c[1] - ctx->aabbMax[1], dz = c[2] - ctx->aabbMax[2];
+    r2 = dx * dx + dy * dy + dz * dz;
+    ctx->scene.bsphere = make_float4(c[0], c[1], c[2], ppg_max(PPG_EPSILON, std::sqrt(r2) * 1.5f));
+}
+
 int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
     // a scene needs materials and at least one primitive; triangle arrays may be absent when it consists of analytic spheres only
     if (!s || !s->materials || (s->n_triangles == 0 && s->n_spheres == 0) ||
@@ -2526,12 +2563,10 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
         for (int a = 0; a < 3; ++a) { mn[a] = ppg_min(mn[a], s->spheres[k].center[a] - s->spheres[k].radius); mx[a] = ppg_max(mx[a], s->spheres[k].center[a] + s->spheres[k].radius); }
     const float eps = 1e-3f;
     for (int a = 0; a < 3; ++a) {
-        ctx->aabbMin[a] = mn[a] - ((mx[a] - mn[a]) * eps + eps);
-        ctx->aabbMax[a] = mx[a] + ((mx[a] - ctx->aabbMin[a]) * eps + eps);
-        float c = s->camera.camera_to_world[4 * a + 3];
-        ctx->aabbMin[a] = ppg_min(ctx->aabbMin[a], c);
-        ctx->aabbMax[a] = ppg_max(ctx->aabbMax[a], c);
+        ctx->geomMin[a] = mn[a] - ((mx[a] - mn[a]) * eps + eps);
+        ctx->geomMax[a] = mx[a] + ((mx[a] - ctx->geomMin[a]) * eps + eps);
     }
+    sceneBox(ctx, s->camera.camera_to_world);
     float ext = 0;
     for (int a = 0; a < 3; ++a) ext = std::max(ext, mx[a] - mn[a]);
     if (!(ext < 1e9f)) { ctx->error = "scene extent of 1e9 units or more (or not finite)"; return PPG_ERR_INVALID; }  // BvhBuilder::quantise
@@ -2785,14 +2820,10 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
         HIP_CHECK(ctx->d_emTris.reserve(etris.size())); HIP_CHECK(hipMemcpy(ctx->d_emTris.p, etris.data(), etris.size() * sizeof(float4), hipMemcpyHostToDevice));
         if (!enrm.empty()) { HIP_CHECK(ctx->d_emNrm.reserve(enrm.size())); HIP_CHECK(hipMemcpy(ctx->d_emNrm.p, enrm.data(), enrm.size() * sizeof(float4), hipMemcpyHostToDevice)); }
         DevScene &S = ctx->scene;
-        if (s->environment || s->envmap) {  // Constant / EnvironmentMap: bounding sphere of createShape() (constant.cpp:67-78, envmap.cpp:330-355) around Scene::getAABB()
-            float c[3], r2 = 0;
-            for (int a = 0; a < 3; ++a) { c[a] = (ctx->aabbMax[a] + ctx->aabbMin[a]) * 0.5f; }
-            const float dx = c[0] - ctx->aabbMax[0], dy = c[1] - ctx->aabbMax[1], dz = c[2] - ctx->aabbMax[2];
-            r2 = dx * dx + dy * dy + dz * dz;
+        if (s->environment || s->envmap) {
             if (s->environment) S.env = make_float4(s->environment[0], s->environment[1], s->environment[2], 1.0f);
             else S.env = make_float4(0, 0, 0, 2.0f);  // image based: DevScene::em_*
-            S.bsphere = make_float4(c[0], c[1], c[2], ppg_max(PPG_EPSILON, std::sqrt(r2) * 1.5f));
+            envBSphere(ctx);
             ctx->fullMaterials = true;  // the environment code lives in the FULL kernel variants
         } else {
             S.env = make_float4(0, 0, 0, 0); S.bsphere = make_float4(0, 0, 0, 0);
@@ -2823,6 +2854,7 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
     S.cam.near_clip = s->camera.near_clip; S.cam.far_clip = s->camera.far_clip;
     S.cam.width = s->camera.width; S.cam.height = s->camera.height;
     S.cam.inv_w = 1.0f / (float)s->camera.width; S.cam.inv_h = 1.0f / (float)s->camera.height;
+    S.cam.lens = ctx->lensOn ? 1 : 0; S.cam.aperture = ctx->lens.aperture_radius; S.cam.focus = ctx->lens.focus_distance;
     ctx->W = s->camera.width; ctx->H = s->camera.height;
     {   // LDS budget of k_trace: 32 KB keeps 5 workgroups per CU resident
         const size_t budget = 32 * 1024;
@@ -2980,6 +3012,22 @@ int ppg_set_rfilter(ppg_ctx *ctx, const ppg_rfilter *f) {
     ctx->rfBorder = border;
     memcpy(ctx->rf.table, table, sizeof table);
     ctx->rf.radius = r; ctx->rf.scale = 31 / r;  // m_scaleFactor = MTS_FILTER_RESOLUTION / m_radius
+    return PPG_OK;
+}
+
+int ppg_set_lens(ppg_ctx *ctx, const ppg_lens *lens) {
+    if (lens && !(std::isfinite(lens->aperture_radius) && lens->aperture_radius > 0)) { ctx->error = "thin lens: aperture_radius must be finite and > 0"; return PPG_ERR_INVALID; }
+    if (lens && !(std::isfinite(lens->focus_distance) && lens->focus_distance > 0)) { ctx->error = "thin lens: focus_distance must be finite and > 0"; return PPG_ERR_INVALID; }
+    (void)hipSetDevice(ctx->device);
+    ctx->quiesce();
+    ctx->lensOn = lens != nullptr;
+    ctx->lens = lens ? *lens : ppg_lens{};
+    DevScene &S = ctx->scene;
+    S.cam.lens = ctx->lensOn ? 1 : 0; S.cam.aperture = ctx->lens.aperture_radius; S.cam.focus = ctx->lens.focus_distance;
+    if (ctx->haveScene) {  // the scene's box and what depends on it, with the new sensor box
+        sceneBox(ctx, S.cam.c2w);
+        if (S.env.w != 0) envBSphere(ctx);
+    }
     return PPG_OK;
 }
 

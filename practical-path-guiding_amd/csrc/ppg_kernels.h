@@ -315,7 +315,8 @@ D Hit trace_small(const float4 *lds_tris, const DevScene &S, F3 o, F3 d, float r
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_generate — renderBlock's sample loop head (GP:1613-1630) + PerspectiveCamera::sampleRayDifferential
+// k_generate — renderBlock's sample loop head (GP:1613-1630) + PerspectiveCamera::sampleRayDifferential (or ThinLens's: S.cam.lens,
+// a uniform branch; the pinhole's arithmetic is the same as without it)
 // ------------------------------------------------------------------------------------------------
 // FUSED (small scenes): the camera ray is traced right here from the LDS copy of the scene.
 template <bool FUSED>
@@ -339,10 +340,25 @@ __global__ __launch_bounds__(PPG_BLOCK) void k_generate(PathState P, DevScene S,
         int px = (int)(pixel % (unsigned int)S.cam.width), py = (int)(pixel / (unsigned int)S.cam.width);
         float sx = (float)px + u1, sy = (float)py + u2;  // GP:1620
         F3 nearP = xf_point(S.cam.s2c, f3(sx * S.cam.inv_w, sy * S.cam.inv_h, 0.0f));
-        F3 dl = norm3(nearP);
+        F3 dl, o;
+        if (S.cam.lens) {
+            // ThinLens::sampleRayDifferential (thinlens.cpp:321-356): the aperture sample is dims 2, 3 (GP:1613-1630); every path has
+            // its own origin on the aperture disk
+            const float u3 = ppg_rand(key, dim++);
+            const float u4 = ppg_rand(key, dim++);
+            float ax, ay;
+            disk_concentric(u3, u4, ax, ay);
+            ax = ax * S.cam.aperture; ay = ay * S.cam.aperture;
+            const float fDist = S.cam.focus / nearP.z;
+            dl = norm3(nearP * fDist - f3(ax, ay, 0.0f));
+            const float *m = S.cam.c2w;  // Transform::transformAffine(apertureP)
+            o = f3(m[0] * ax + m[1] * ay + m[2] * 0.0f + m[3], m[4] * ax + m[5] * ay + m[6] * 0.0f + m[7], m[8] * ax + m[9] * ay + m[10] * 0.0f + m[11]);
+        } else {
+            dl = norm3(nearP);
+            o = f3(S.cam.c2w[3], S.cam.c2w[7], S.cam.c2w[11]);
+        }
         float invZ = 1.0f / dl.z;
         float mint = S.cam.near_clip * invZ, maxt = S.cam.far_clip * invZ;
-        F3 o = f3(S.cam.c2w[3], S.cam.c2w[7], S.cam.c2w[11]);
         F3 d = xf_vec(S.cam.c2w, dl);
         if (FUSED) {
             Hit h = trace_small(lds_tris, S, o, d, mint, maxt);

@@ -51,6 +51,8 @@ struct SceneData {
     std::vector<std::vector<float>> texturePixels;
     bool hasRFilter = false;                       // the film's reconstruction filter (ppg_set_rfilter) when it is not the default box
     ppg_rfilter rfilter{};
+    bool hasLens = false;                          // thin-lens camera (ppg_set_lens); false = pinhole
+    ppg_lens lens{};
 
     ppg_scene view() const {
         ppg_scene s{};
@@ -159,6 +161,7 @@ public:
         ppg_scene sv = scene.view();
         check(ppg_set_scene(m_ctx, &sv), "ppg_set_scene");
         check(ppg_set_rfilter(m_ctx, scene.hasRFilter ? &scene.rfilter : nullptr), "ppg_set_rfilter");
+        check(ppg_set_lens(m_ctx, scene.hasLens ? &scene.lens : nullptr), "ppg_set_lens");
         if (reducer) check(ppg_set_shard(m_ctx, reducer->rank(), reducer->world(), 32), "ppg_set_shard");
         m_w = scene.camera.width; m_h = scene.camera.height;
         {

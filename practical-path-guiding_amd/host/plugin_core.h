@@ -62,6 +62,8 @@ public:
     void setSeed(uint64_t seed) { m_cfg.seed = seed; }
     // the film's reconstruction filter (the scene's <rfilter>); nullptr = the default box
     void setRFilter(const ppg_rfilter *f) { m_hasRFilter = f != nullptr; if (f) m_rfilter = *f; }
+    // the sensor's thin lens (ppg_set_lens); nullptr = pinhole
+    void setLens(const ppg_lens *l) { m_hasLens = l != nullptr; if (l) m_lens = *l; }
     const ppg_config &config() const { return m_cfg; }
 
     // PPG_OK, PPG_ERR_CANCELLED, or an error code with `err` set.  May be called again (a new context per render, like a new RenderJob).
@@ -87,6 +89,8 @@ public:
         rc = ppg_set_scene(ctx, &scene);  // (a cancel() during these seconds of BVH build stays set in the context: ppg_render returns at once)
         if (rc != PPG_OK) { err = ppg_last_error(ctx); return rc; }
         rc = ppg_set_rfilter(ctx, m_hasRFilter ? &m_rfilter : nullptr);
+        if (rc != PPG_OK) { err = ppg_last_error(ctx); return rc; }
+        rc = ppg_set_lens(ctx, m_hasLens ? &m_lens : nullptr);
         if (rc != PPG_OK) { err = ppg_last_error(ctx); return rc; }
         m_hasFilm = true;  // (the film exists from here on: black if the cancel came before the first pass)
         rc = ppg_render(ctx);
@@ -124,6 +128,8 @@ private:
     bool m_hasFilm = false;
     bool m_hasRFilter = false;
     ppg_rfilter m_rfilter{};
+    bool m_hasLens = false;
+    ppg_lens m_lens{};
     std::mutex m_mutex;
 };
 

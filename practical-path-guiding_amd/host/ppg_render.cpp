@@ -103,6 +103,11 @@ static bool loadSceneChecked(const char *path, SceneData &s) {
         f.read((char *)&s.rfilter, sizeof(ppg_rfilter));
         s.hasRFilter = true;
     }
+    if (hdr[5] & 128) {  // bit 7: the thin lens (ppg_lens), only for a thin-lens camera
+        if (!fits(sizeof(ppg_lens))) return false;
+        f.read((char *)&s.lens, sizeof(ppg_lens));
+        s.hasLens = true;
+    }
     return (bool)f;
 }
 
@@ -172,7 +177,7 @@ static bool saveScene(const char *path, const SceneData &s) {
     std::ofstream f(path, std::ios::binary);
     const uint32_t hdr[6] = {(uint32_t)(s.positions.size() / 3), (uint32_t)(s.indices.size() / 3), (uint32_t)s.materials.size(), (uint32_t)s.emitters.size(),
                              s.normals.empty() ? 0u : 1u, (s.hasEnvironment ? 1u : 0u) | (s.rtrans.empty() ? 0u : 2u) | (s.spheres.empty() ? 0u : 4u) | (s.hasEnvmap ? 8u : 0u) |
-                                 (s.texcoords.empty() ? 0u : 16u) | (s.textures.empty() ? 0u : 32u) | (s.hasRFilter ? 64u : 0u)};
+                                 (s.texcoords.empty() ? 0u : 16u) | (s.textures.empty() ? 0u : 32u) | (s.hasRFilter ? 64u : 0u) | (s.hasLens ? 128u : 0u)};
     f.write("PPGS", 4); f.write((const char *)hdr, sizeof hdr);
     f.write((const char *)s.positions.data(), s.positions.size() * 4);
     if (!s.normals.empty()) f.write((const char *)s.normals.data(), s.normals.size() * 4);
@@ -210,6 +215,7 @@ static bool saveScene(const char *path, const SceneData &s) {
         }
     }
     if (s.hasRFilter) f.write((const char *)&s.rfilter, sizeof(ppg_rfilter));
+    if (s.hasLens) f.write((const char *)&s.lens, sizeof(ppg_lens));
     return (bool)f;
 }
 
@@ -305,6 +311,7 @@ int main(int argc, char **argv) {
         PluginCore core;
         core.configure(props);
         core.setRFilter(scene.hasRFilter ? &scene.rfilter : nullptr);
+        core.setLens(scene.hasLens ? &scene.lens : nullptr);
         core.setSeed((uint64_t)std::stoull(props.getString("seed", "0")));
         std::string dest = out;
         const size_t dot = dest.find_last_of('.');

@@ -722,7 +722,8 @@ public:
         // sensor
         const XmlNode *sensor = root.child("sensor");
         if (!sensor) throw std::runtime_error("no <sensor>");
-        if (sensor->get("type") != "perspective") throw std::runtime_error("sensor type '" + sensor->get("type") + "' is not supported (perspective only)");
+        const std::string stype = sensor->get("type");
+        if (stype != "perspective" && stype != "thinlens") throw std::runtime_error("sensor type '" + stype + "' is not supported (perspective, thinlens)");
         auto sp = props(*sensor);
         const XmlNode *film = sensor->child("film");
         std::map<std::string, std::string> fp;
@@ -733,13 +734,27 @@ public:
             if (!rf) out.warnings.push_back("no <rfilter>: Mitsuba would default to gaussian; the box filter is used");
         }
         const int W = m_w ? m_w : (fp.count("width") ? std::stoi(fp["width"]) : 768), H = m_h ? m_h : (fp.count("height") ? std::stoi(fp["height"]) : 576);
-        if (!sp.count("fov")) throw std::runtime_error("perspective sensor without 'fov' (focalLength is not supported)");
+        // PerspectiveCamera: fov or focalLength, not both (sensor.cpp:226-228); neither = focalLength 50mm
+        if (sp.count("fov") && sp.count("focalLength")) throw std::runtime_error(stype + " sensor: please specify either a focal length ('focalLength') or a field of view ('fov')");
         Mat4 c2w = Mat4::identity();
         if (const XmlNode *tw = sensor->child("transform")) c2w = transform(*tw);
         std::string axis = sp.count("fovAxis") ? sp["fovAxis"] : "x";
         std::transform(axis.begin(), axis.end(), axis.begin(), ::tolower);
-        makeCamera(out.scene.camera, c2w, std::stod(sp["fov"]), axis, sp.count("nearClip") ? std::stod(sp["nearClip"]) : 1e-2,
-                   sp.count("farClip") ? std::stod(sp["farClip"]) : 1e4, W, H);
+        double fov;
+        if (sp.count("fov")) fov = std::stod(sp["fov"]);
+        else { fov = focalLengthFov(sp.count("focalLength") ? sp["focalLength"] : "50mm"); axis = "diagonal"; }
+        const double farC = sp.count("farClip") ? std::stod(sp["farClip"]) : 1e4;
+        makeCamera(out.scene.camera, c2w, fov, axis, sp.count("nearClip") ? std::stod(sp["nearClip"]) : 1e-2, farC, W, H);
+        if (stype == "thinlens") {  // ThinLens::ThinLens (thinlens.cpp:124-142); focusDistance defaults to farClip (sensor.cpp:162)
+            if (!sp.count("apertureRadius")) throw std::runtime_error("thinlens sensor without 'apertureRadius'");
+            float r = (float)std::stod(sp["apertureRadius"]);
+            if (r == 0) { out.warnings.push_back("thinlens: can't have a zero aperture radius -- setting to 0.0001"); r = 1e-4f; }
+            const float focus = (float)(sp.count("focusDistance") ? std::stod(sp["focusDistance"]) : farC);
+            if (hasScale(c2w)) throw std::runtime_error("thinlens sensor: scale factors in the camera-to-world transformation are not allowed");
+            if (!(std::isfinite(r) && r > 0 && std::isfinite(focus) && focus > 0)) throw std::runtime_error("thinlens sensor: apertureRadius and focusDistance must be finite and > 0");
+            out.scene.hasLens = true;
+            out.scene.lens.aperture_radius = r; out.scene.lens.focus_distance = focus;
+        }
         // bsdfs
         for (auto &b : root.children) if (b.tag == "bsdf" && b.attr("id")) m_byId[b.get("id")] = intern(makeBsdf(b, true, out), out);
         {   // an id may also sit on a NESTED bsdf (KITCHEN references the twosided element inside a bumpmap): every element with an id is a named object
@@ -1134,6 +1149,25 @@ private:
             for (uint32_t id : {b, b + 1, b + 2, b + 3, b, b + 2}) r.indices.push_back(id);
         }
         return r;
+    }
+    // focalLength "<x>mm" → diagonal field of view (PerspectiveCamera::configure, sensor.cpp:264-276), in the reference's float arithmetic
+    static double focalLengthFov(std::string f) {
+        if (f.size() >= 2 && f.compare(f.size() - 2, 2, "mm") == 0) f = f.substr(0, f.size() - 2);
+        char *end = nullptr;
+        const float value = (float)strtod(f.c_str(), &end);
+        if (f.empty() || *end != '\0') throw std::runtime_error("could not parse the focal length '" + f + "' (must be of the form <x>mm, where <x> is a positive number)");
+        const float a = std::atan(std::sqrt((float)(36 * 36 + 24 * 24)) / (2 * value));
+        return (double)(float)(2 * 180 / 3.14159265358979323846 * a);
+    }
+    // Transform::hasScale (transform.h:76-90)
+    static bool hasScale(const Mat4 &t) {
+        for (int i = 0; i < 3; ++i)
+            for (int j = i; j < 3; ++j) {
+                float sum = 0;
+                for (int k = 0; k < 3; ++k) sum += t.m[4 * i + k] * t.m[4 * j + k];
+                if (i == j ? std::abs(sum - 1) > 1e-3f : std::abs(sum) > 1e-3f) return true;
+            }
+        return false;
     }
     static void makeCamera(ppg_camera &cam, const Mat4 &c2w, double fov, const std::string &axisIn, double nearC, double farC, int W, int H) {
         // sensor.cpp:239-264, 301-305; perspective.cpp:150-164 (m_sampleToCamera), inverted in closed form

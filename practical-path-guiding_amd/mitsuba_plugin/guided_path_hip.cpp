@@ -24,7 +24,8 @@
  *               the Python loader).  Unsupported plug-ins end the render with an error that names them.
  *   emitters    `area` emitters by shape (radiance from the emitter's Properties), `constant`, `envmap` (level 0 of the bitmap it was given)
  *               and `sunsky` / `sky` / `sun` through the environment map Mitsuba itself rasterised (getEnvironmentEmitter() → its bitmap)
- *   sensor      PerspectiveCamera: m_sampleToCamera rebuilt from getXFov / clip planes / crop (perspective.cpp:150-164), world transform
+ *   sensor      PerspectiveCamera: m_sampleToCamera rebuilt from getXFov / clip planes / crop (perspective.cpp:150-164), world transform;
+ *               ThinLens: the same + apertureRadius and getFocusDistance() (ppg_set_lens)
  *   result      film->setBitmap(weight-normalised RGB), false when cancelled (GP:1584)
  */
 #include <mitsuba/render/scene.h>
@@ -73,6 +74,7 @@ public:
             return false;                 /* (EError normally throws; if it is configured not to, stop here) */
         }
         const ppg_scene desc = data.view();
+        m_core.setLens(data.hasLens ? &data.lens : nullptr);
         Log(EInfo, "Starting render job (%ix%i, MI355X, %i triangles, %i analytic spheres) ..", film->getCropSize().x, film->getCropSize().y,
             (int) (data.indices.size() / 3), (int) data.spheres.size());
         /* create → scene → render; SD-tree dumps to "<dest>-NN.sdt" (GP:1192-1195) */
@@ -269,8 +271,17 @@ private:
             }
         }
 
-        /* PerspectiveCamera (perspective.cpp:150-164): m_sampleToCamera for the film's crop window; world transform at time 0 */
-        if (sensor->getProperties().getPluginName() != "perspective") { why = "sensor plug-in '" + sensor->getProperties().getPluginName() + "' is not supported"; return false; }
+        /* PerspectiveCamera (perspective.cpp:150-164): m_sampleToCamera for the film's crop window; world transform at time 0.  ThinLens builds
+           the same matrix (thinlens.cpp:155-180) and adds the aperture: apertureRadius, 0 → Epsilon as in its constructor (thinlens.cpp:133-139) */
+        const std::string sensorName = sensor->getProperties().getPluginName();
+        if (sensorName != "perspective" && sensorName != "thinlens") { why = "sensor plug-in '" + sensorName + "' is not supported (perspective, thinlens)"; return false; }
+        if (sensorName == "thinlens") {
+            Float r = sensor->getProperties().getFloat("apertureRadius");
+            if (r == 0) r = Epsilon;
+            data.hasLens = true;
+            data.lens.aperture_radius = (float) r;
+            data.lens.focus_distance = (float) static_cast<const ProjectiveCamera *>(sensor)->getFocusDistance();
+        }
         const PerspectiveCamera *cam = static_cast<const PerspectiveCamera *>(sensor);
         const Vector2i size = film->getSize(), crop = film->getCropSize();
         const Point2i off = film->getCropOffset();

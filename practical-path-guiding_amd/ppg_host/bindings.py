@@ -192,6 +192,22 @@ def rfilter_table(desc):
     return table, float(r.value), int(b.value)
 
 
+class Lens(C.Structure):
+    """ppg_lens — a thin-lens camera (mitsuba/src/sensors/thinlens.cpp).  As a dict (SceneDesc.lens): {"aperture_radius", "focus_distance"}
+    in world units; None = pinhole."""
+    _fields_ = [("aperture_radius", C.c_float), ("focus_distance", C.c_float)]
+
+    @classmethod
+    def from_dict(cls, d):
+        unknown = set(d) - {"aperture_radius", "focus_distance"}
+        if unknown:
+            raise ValueError("thin lens: unknown parameters %s" % sorted(unknown))
+        return cls(float(d["aperture_radius"]), float(d["focus_distance"]))
+
+    def as_dict(self):
+        return dict(aperture_radius=float(self.aperture_radius), focus_distance=float(self.focus_distance))
+
+
 class Emitter(C.Structure):
     _fields_ = [("radiance", C.c_float * 3), ("_pad", C.c_float)]
 
@@ -367,6 +383,19 @@ class Engine:
                 self.set_rfilter(rf)
         elif rf is not None:
             raise NotImplementedError("%s: reconstruction filters other than the default box are not implemented here" % self.prefix)
+        # the thin lens, likewise (None / absent: pinhole).  The context keeps its lens across ppg_set_scene; it is re-applied here so that
+        # a scene without one renders with the pinhole after a scene with one.
+        lens = getattr(desc, "lens", None)
+        if self.prefix == "ppg_":
+            if lens is not None or getattr(self, "_lens", None) is not None:
+                self.set_lens(lens)
+        elif lens is not None:
+            raise NotImplementedError("%s: the thin-lens camera is not implemented here" % self.prefix)
+
+    def set_lens(self, lens):
+        """ppg_set_lens: lens = {"aperture_radius", "focus_distance"} (Lens) or None for the pinhole"""
+        self._lens = None if lens is None else Lens.from_dict(lens)
+        self._call("set_lens", None if self._lens is None else C.byref(self._lens))
 
     def set_rfilter(self, rfilter):
         """ppg_set_rfilter: rfilter = a filter dict (RFilter) or None for the default box"""

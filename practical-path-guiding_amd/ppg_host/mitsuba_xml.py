@@ -1,7 +1,8 @@
 """Loader for the subset of Mitsuba 0.6 scene XML the reference's bundled scenes use:
 
   integrator  guided_path (every property of GP:1014-1085 and integrator.cpp:192-218)
-  sensor      perspective (fov, fovAxis, nearClip, farClip, toWorld; focusDistance ignored: pinhole),
+  sensor      perspective (fov, fovAxis or focalLength, nearClip, farClip, toWorld; focusDistance ignored: pinhole),
+              thinlens (the same + apertureRadius, focusDistance: SceneDesc.lens; toWorld without scale),
               nested sampler (independent; sampleCount / seed do not steer guided_path, GP:1342-1374) and
               film hdrfilm (width, height; rfilter box / tent / gaussian / mitchell / catmullrom / lanczos)
   shapes      obj (filename, toWorld, faceNormals, maxSmoothAngle, flipNormals, flipTexCoords, collapse),
@@ -592,6 +593,31 @@ def _rfilter_border(f):
     return int(np.ceil(f32(r) - f32(0.5)))
 
 
+def focal_length_fov(text):
+    """focalLength "<x>mm" → the diagonal field of view it stands for (PerspectiveCamera::configure, sensor.cpp:264-276), in the
+    reference's float arithmetic: 2 · 180/π · atan(√(36² + 24²) / (2x))"""
+    f = text[:-2] if text.endswith("mm") else text
+    try:
+        value = f32(float(f))
+    except ValueError:
+        raise SceneError("could not parse the focal length %r (must be of the form <x>mm, where <x> is a positive number)" % text)
+    a = f32(np.arctan(f32(np.sqrt(f32(36 * 36 + 24 * 24))) / (f32(2) * value)))
+    return float(f32(2 * 180 / math.pi * float(a)))
+
+
+def _has_scale(m):
+    """Transform::hasScale (transform.h:76-90): the rows of the 3x3 part are not orthonormal within 1e-3"""
+    m = np.asarray(m, f32).reshape(4, 4)
+    for i in range(3):
+        for j in range(i, 3):
+            acc = f32(0)
+            for k in range(3):
+                acc = f32(acc + m[i, k] * m[j, k])
+            if (i == j and abs(acc - f32(1)) > f32(1e-3)) or (i != j and abs(acc) > f32(1e-3)):
+                return True
+    return False
+
+
 def load_scene(path, defines=None, strict=True, width=None, height=None, data_dir=None, mitsuba_src=None):
     """Parse `path` → (SceneDesc, integrator properties for ppg_create, info dict).
 
@@ -632,8 +658,9 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
     sensor = root.find("sensor")
     if sensor is None:
         raise SceneError("no <sensor>")
-    if sensor.get("type") != "perspective":
-        raise SceneError("sensor type %r is not supported (perspective only)" % sensor.get("type"))
+    stype = sensor.get("type")
+    if stype not in ("perspective", "thinlens"):
+        raise SceneError("sensor type %r is not supported (perspective, thinlens)" % stype)
     sp = _props(sensor, sub)
     film = sensor.find("film")
     fp = _props(film, sub) if film is not None else {}
@@ -644,11 +671,29 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
     if rf is None:
         warnings.append("no <rfilter>: Mitsuba would default to gaussian; the box filter is used")
     W = int(width or fp.get("width", 768)); H = int(height or fp.get("height", 576))
-    if "fov" not in sp:
-        raise SceneError("perspective sensor without 'fov' (focalLength is not supported)")
+    if "fov" in sp and "focalLength" in sp:  # PerspectiveCamera::PerspectiveCamera, sensor.cpp:226-228
+        raise SceneError("%s sensor: please specify either a focal length ('focalLength') or a field of view ('fov')" % stype)
+    if "fov" in sp:
+        fov, fov_axis = sp["fov"], str(sp.get("fovAxis", "x")).lower()
+    else:
+        fov, fov_axis = focal_length_fov(str(sp.get("focalLength", "50mm"))), "diagonal"
     tw = sensor.find("transform")
     c2w = _transform(tw, sub) if tw is not None else np.eye(4, dtype=f32)
-    camera = perspective_camera_from_matrix(c2w, sp["fov"], str(sp.get("fovAxis", "x")).lower(), sp.get("nearClip", 1e-2), sp.get("farClip", 1e4), W, H)
+    camera = perspective_camera_from_matrix(c2w, fov, fov_axis, sp.get("nearClip", 1e-2), sp.get("farClip", 1e4), W, H)
+    lens = None
+    if stype == "thinlens":  # ThinLens::ThinLens, thinlens.cpp:124-142; focusDistance defaults to farClip (sensor.cpp:162)
+        if "apertureRadius" not in sp:
+            raise SceneError("thinlens sensor without 'apertureRadius'")
+        r = f32(sp["apertureRadius"])
+        if r == 0:
+            warnings.append("thinlens: can't have a zero aperture radius -- setting to 0.0001")
+            r = f32(1e-4)
+        focus = f32(sp.get("focusDistance", sp.get("farClip", 1e4)))
+        if _has_scale(c2w):
+            raise SceneError("thinlens sensor: scale factors in the camera-to-world transformation are not allowed")
+        if not (np.isfinite(r) and r > 0 and np.isfinite(focus) and focus > 0):
+            raise SceneError("thinlens sensor: apertureRadius and focusDistance must be finite and > 0 (got %r, %r)" % (float(r), float(focus)))
+        lens = dict(aperture_radius=float(r), focus_distance=float(focus))
     sampler = sensor.find("sampler")
     info = dict(width=W, height=H, sample_count=_props(sampler, sub).get("sampleCount") if sampler is not None else None)
 
@@ -1122,7 +1167,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         pos, idx, tmat, tem = [np.zeros((0, 3), f32)], [np.zeros((0, 3), np.uint32)], [np.zeros(0, np.uint32)], [np.zeros(0, np.int32)]
     desc = SceneDesc(np.concatenate(pos).astype(f32), np.concatenate(idx).astype(np.uint32), np.concatenate(tmat), np.concatenate(tem),
                      materials, emitters, camera, normals, environment, np.stack(rt_slices).astype(f32) if rt_slices else None, spheres, envmap,
-                     np.concatenate(uvl).astype(f32) if any_uvs else None, textures, rfilter)
+                     np.concatenate(uvl).astype(f32) if any_uvs else None, textures, rfilter, lens)
     info["warnings"] = warnings
     return desc, props, info
 
@@ -1147,11 +1192,14 @@ def save_scene_xml(desc, props, directory, name="scene"):
             out.append('\t\t<float name="%s" value="%r"/>' % (k, float(v)))
         else:
             out.append('\t\t<string name="%s" value="%s"/>' % (k, v))
-    out += ['\t</integrator>', '\t<sensor type="perspective">',
+    lens = getattr(desc, "lens", None)
+    out += ['\t</integrator>', '\t<sensor type="%s">' % ("perspective" if lens is None else "thinlens"),
             '\t\t<string name="fovAxis" value="%s"/>' % cam.get("fov_axis", "x"), '\t\t<float name="fov" value="%r"/>' % float(cam["fov"]),
             '\t\t<float name="nearClip" value="%r"/>' % float(cam["near_clip"]), '\t\t<float name="farClip" value="%r"/>' % float(cam["far_clip"]),
             '\t\t<transform name="toWorld">', '\t\t\t<matrix value="%s"/>' % " ".join(repr(float(x)) for x in np.asarray(cam["camera_to_world"]).reshape(-1)),
-            '\t\t</transform>', '\t\t<sampler type="independent"/>', '\t\t<film type="hdrfilm">',
+            '\t\t</transform>'] + ([] if lens is None else [
+            '\t\t<float name="apertureRadius" value="%r"/>' % float(lens["aperture_radius"]),
+            '\t\t<float name="focusDistance" value="%r"/>' % float(lens["focus_distance"])]) + ['\t\t<sampler type="independent"/>', '\t\t<film type="hdrfilm">',
             '\t\t\t<integer name="width" value="%d"/>' % cam["width"], '\t\t\t<integer name="height" value="%d"/>' % cam["height"],
             '\t\t\t<boolean name="banner" value="false"/>', '\t\t\t<rfilter type="box"/>', '\t\t</film>', '\t</sensor>']
     from .bindings import Material
