@@ -71,10 +71,15 @@ PPG_HD float ppg_atan(float xx) {
     return (xx < 0.0f) ? -y : y;
 }
 
-/* atan2(y, x) with the usual quadrant rules (finite inputs). */
+/* atan2(y, x) with the usual quadrant rules (finite inputs), the signed zeros of C99 F.9.1.4 included: atan2(+-0, +0) = +-0 and
+   atan2(+-0, -0) = +-pi — the reference's dirToCanonical (GP:597-608) sends the pole direction (-0, +-0, +-1), which its own
+   canonicalToDir produces (sinTheta * cosPhi = 0 * negative), to phi = pi, not to phi = 0. */
 PPG_HD float ppg_atan2(float y, float x) {
     if (x == 0.0f) {
-        if (y == 0.0f) return 0.0f;
+        if (y == 0.0f) {
+            if ((ppg_f2u(x) >> 31) == 0u) return y;
+            return (ppg_f2u(y) >> 31) ? -PPG_PI_F : PPG_PI_F;
+        }
         return (y > 0.0f) ? 1.5707963267948966192f : -1.5707963267948966192f;
     }
     float a = ppg_atan(y / x);

@@ -3429,6 +3429,12 @@ int ppgo_set_scene(ppgo_ctx *ctx, const ppg_scene *s) {
         for (int k = 0; k < 3; ++k) if (sc.idx[3 * t + k] >= s->n_vertices) { ctx->gpt.error = "vertex index out of range"; return PPG_ERR_INVALID; }
     }
     sc.cam = s->camera;
+    // include/ppg.h "Limits": bit PPG_ADAM_PATH_BITS - 1 of the key's path field is PPG_ADAM_DEFER_PATH_BIT, so a round's paths must fit below it
+    if (ctx->gpt.m_bsdfSamplingFractionLoss != ENone &&
+        (uint64_t)std::max(0, sc.cam.width) * (uint64_t)std::max(0, sc.cam.height) * (uint64_t)std::max(0, ctx->gpt.m_sppPerPass) > (uint64_t)PPG_ADAM_DEFER_PATH_BIT) {
+        ctx->gpt.error = "width * height * sppPerPass exceeds 2^26 = 67108864 with a bsdfSamplingFractionLoss";
+        return PPG_ERR_INVALID;
+    }
     sc.finalize();
     ctx->gpt.haveScene = true;
     return PPG_OK;

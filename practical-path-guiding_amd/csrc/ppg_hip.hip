@@ -1020,7 +1020,8 @@ int allocPaths(ppg_ctx *ctx) {
         if (ctx->tuneBatchPaths) target = ctx->tuneBatchPaths;
         ctx->maxBatch = ctx->budgetType == 1 ? 1 : (int)std::max<size_t>(1, std::min<size_t>(64, target / perPass));
         if (ctx->loss != LOSS_NONE) {
-            if ((uint64_t)ctx->W * ctx->H * ctx->sppPerPass > (1ull << PPG_ADAM_PATH_BITS)) { ctx->error = "width * height * sppPerPass exceeds 2^27 with a bsdfSamplingFractionLoss"; return PPG_ERR_INVALID; }
+            // bit PPG_ADAM_PATH_BITS - 1 of the key's path field is PPG_ADAM_DEFER_PATH_BIT (include/ppg.h "Limits")
+            if ((uint64_t)ctx->W * ctx->H * ctx->sppPerPass > (uint64_t)PPG_ADAM_DEFER_PATH_BIT) { ctx->error = "width * height * sppPerPass exceeds 2^26 = 67108864 with a bsdfSamplingFractionLoss"; return PPG_ERR_INVALID; }
             ctx->maxBatch = std::max(ctx->maxBatch, (int)ppg_adam_round_passes(ctx->sppPerPass, ctx->W, ctx->H, 1 << 30));
         }
     }

@@ -31,6 +31,11 @@ def test_atan2(oracle_lib):
     assert np.abs(a - np.arctan2(y.astype(np.float64), x.astype(np.float64))).max() < 4e-7  # < 2 ulp at pi
     a, _ = _eval(oracle_lib, 1, np.array([0, 1, -1, 0], np.float32), np.array([0, 0, 0, -1], np.float32))
     assert np.allclose(a, [0, np.pi / 2, -np.pi / 2, np.pi], atol=3e-7)
+    # the signed zeros of C99 F.9.1.4: the pole direction (-0, +-0, +-1) goes to phi = +-pi in the reference's dirToCanonical, not to 0
+    y0, x0 = np.array([0.0, -0.0, 0.0, -0.0], np.float32), np.array([0.0, 0.0, -0.0, -0.0], np.float32)
+    a, _ = _eval(oracle_lib, 1, y0, x0)
+    want = np.arctan2(y0, x0)
+    assert np.array_equal(np.signbit(a), np.signbit(want)) and np.abs(a - want).max() < 3e-7
 
 
 def test_exp(oracle_lib):

@@ -4,6 +4,8 @@ import ctypes as C
 
 import numpy as np
 
+import ref_sdtree as R  # the reference's own classes where oracle/_ref exists: a second opinion on the known answers below
+
 
 def test_fresh_reset_is_depth4_85_nodes(oracle_lib):
     # every reference log: "Depth = [4, 4, 4] ... Node count = [85, 85, 85]" at iteration 0 (GP:456-514, rho = 0.01)
@@ -22,6 +24,15 @@ def test_refine_known_answer(oracle_lib):
     assert nl.value == 1  # split only if weight > threshold (GP:953-955)
     oracle_lib.ppgo_ka_refine(C.c_float(16971), C.c_uint64(16970), C.byref(nl), C.byref(nn))
     assert nl.value == 2
+    ref = R.second_opinion()  # the same three answers from STree::refine of the reference's text
+    if ref is not None:
+        for W, leaves in ((4349763, 512), (16970, 1), (16971, 2)):
+            one = {"offset": np.zeros(1, np.uint64), "num_nodes": np.ones(1, np.uint32), "max_depth": np.zeros(1, np.int32), "sum": np.zeros(1, np.float32),
+                   "stat_weight": np.float32([W]), "node_sums": np.zeros((1, 4), np.float32), "node_children": np.zeros((1, 4), np.uint16)}
+            ref.load({"axis": np.zeros(1, np.int32), "children": np.zeros((1, 2), np.uint32), "theta": np.zeros(1, np.float32),
+                      "aabb_min": np.zeros(3, np.float32), "aabb_max": np.ones(3, np.float32), "sampling": one, "building": one})
+            ref.refine_reset(16970, -1, 20, 0.01)
+            assert ref.read()["n_leaves"] == leaves
 
 
 def test_adam_known_answer(oracle_lib):
@@ -30,8 +41,16 @@ def test_adam_known_answer(oracle_lib):
     fr = C.c_float()
     oracle_lib.ppgo_ka_adam(10, C.c_float(.5), C.c_float(.2), C.c_float(.3), C.c_float(.1), C.c_float(1), 1, C.byref(fr))
     assert abs(fr.value - 0.512494385) < 2e-7
+    fr_ten = fr.value
     oracle_lib.ppgo_ka_adam(1, C.c_float(.5), C.c_float(.2), C.c_float(.3), C.c_float(.1), C.c_float(1), 1, C.byref(fr))
     assert fr.value == 0.5  # batchAccumulation 1 > batchSize 1 is false: no step yet (GP:89)
+    ref = R.second_opinion()  # the reference's own optimizeBsdfSamplingFraction / AdamOptimizer with libm's exp and pow
+    if ref is not None:
+        st = ref.adam_replay(np.zeros(6, np.uint32), np.tile(np.float32([.5, .2, .3, .1, 1]), (10, 1)), 1)
+        assert st[1] == 5 and abs(1 / (1 + np.exp(-float(st[:1].view(np.float32)[0]))) - 0.512494385) < 1e-7
+        assert abs(1 / (1 + np.exp(-float(st[:1].view(np.float32)[0]))) - fr_ten) < 2e-7
+        st = ref.adam_replay(np.zeros(6, np.uint32), np.float32([[.5, .2, .3, .1, 1]]), 1)
+        assert st[0] == 0 and st[1] == 0
 
 
 def test_canonical_direction_maps(oracle_lib):
@@ -51,6 +70,25 @@ def test_canonical_direction_maps(oracle_lib):
     xy = (C.c_float * 2)()
     oracle_lib.ppgo_dir_to_canonical(bad, xy)
     assert (xy[0], xy[1]) == (0.0, 0.0)  # GP:598-600
+    ref = R.second_opinion()  # against the reference's canonicalToDir (libm sincos) and dirToCanonical (libm atan2)
+    if ref is not None:
+        pts = rng.rand(20000, 2).astype(np.float32)
+        pts[:6] = [[0, 0], [1, 1], [0.5, 0.5], [1, 0], [0, 1], [0.25, 0.75]]
+        ours = np.zeros((len(pts), 3), np.float32)
+        for i, (x, y) in enumerate(pts):
+            oracle_lib.ppgo_canonical_to_dir(C.c_float(x), C.c_float(y), d)
+            ours[i] = d[:]
+        theirs = ref.canonical_to_dir(pts)
+        assert np.abs(ours.astype(np.float64) - theirs).max() <= R.SINCOS_TOL
+        back = np.zeros((len(pts), 2), np.float32)
+        for i in range(len(pts)):
+            oracle_lib.ppgo_dir_to_canonical((C.c_float * 3)(*theirs[i]), xy)
+            back[i] = xy[:]
+        want = ref.dir_to_canonical(theirs)
+        dy = np.abs(back[:, 1].astype(np.float64) - want[:, 1])
+        dy = np.minimum(dy, 1 - dy)  # phi = 2 pi is phi = 0
+        # x has no transcendental in it: exact.  y: the 4e-7 atan2 bound of test_detmath.py / 2 pi, plus an ulp at 1 for the two roundings of phi / (2 pi)
+        assert np.array_equal(back[:, 0], want[:, 0]) and dy.max() <= 4e-7 / (2 * np.pi) + 2.0 ** -23
 
 
 def _exercise(lib, acc, dfilter, xy, irr, w, q, seed=5, rho=0.01):
