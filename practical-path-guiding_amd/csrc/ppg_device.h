@@ -54,13 +54,9 @@ D F3 ld3(const float4 *p) { float4 v = *p; return f3(v.x, v.y, v.z); }
 // include/ppg_detmath.h on the device: ONE out-of-line copy of each transcendental per kernel module instead of one inlined copy per
 // call site.  Pure register-in / register-out functions (no pointers: nothing is forced into scratch memory); the arithmetic is the
 // header's, so results are unchanged.  Inlined everywhere they were 4 400 of k_tail<FULL>'s 25 000 instructions — a kernel of 135 KB
-// (330 KB before the BSDF call sites were merged) against a 64 KB instruction cache.  -DPPG_INLINE_MATH restores the inlined calls.
+// (330 KB before the BSDF call sites were merged) against a 64 KB instruction cache.
 // ------------------------------------------------------------------------------------------------
-#ifdef PPG_INLINE_MATH
-#define DM_ATTR __device__ __forceinline__
-#else
 #define DM_ATTR static __device__ __attribute__((noinline))
-#endif
 DM_ATTR float2 dm_sincos(float x) { float s_, c_; ppg_sincos(x, &s_, &c_); return make_float2(s_, c_); }
 DM_ATTR float dm_atan2(float y, float x) { return ppg_atan2(y, x); }
 DM_ATTR float dm_exp(float x) { return ppg_exp(x); }
@@ -440,7 +436,7 @@ D void leaf_pairs(PairLds *W, const float4 *accel, int first, int cnt, unsigned 
 
 // Closest hit by (t, original primitive index) through the BVH4 — equals brute force (conservative culling).
 // ANY: return at the first triangle hit (shadow rays; only prim >= 0 is meaningful then).
-// VOTE: as in k_trace, lanes holding a leaf wait until PPG_LEAF_VOTE lanes of the wave do (or none has an interior node left) — for callers
+// VOTE: lanes holding a leaf wait until PPG_LEAF_VOTE_TAIL lanes of the wave do (or none has an interior node left) — for callers
 // whose whole wave traverses at once (k_tail); lanes that are done have left the loop and do not count.
 template <bool ANY = false, bool SPH = false, bool VOTE = false>
 D Hit trace_closest4(const DevScene &S, int *lds_stack_col, int stride, F3 o, F3 d, float mint, float maxt) {

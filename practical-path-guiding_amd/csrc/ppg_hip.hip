@@ -197,16 +197,6 @@ struct HostSNode {  // host mirror of one S-tree node (STreeNode, GP:740-845)
     bool isLeaf() const { return child[0] == 0; }
 };
 
-// The stream of the commits that run beside the tail.  PPG_STREAM2_LOW=1: at the device's least priority, so that the tail's crowd phase is
-// served first (experiment).
-static hipError_t createSecondStream(hipStream_t *st) {
-    const char *e = getenv("PPG_STREAM2_LOW");
-    if (!e || !atoi(e)) return hipStreamCreate(st);
-    int least = 0, greatest = 0;
-    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-    return hipStreamCreateWithPriority(st, hipStreamDefault, least);
-}
-
 int parseEnum(const char *s, const char *dflt, std::initializer_list<const char *> names) {
     std::string v = s ? s : dflt;
     int i = 0;
@@ -628,8 +618,7 @@ struct ppg_ctx {
     DevBuf<uint4> d_misc;
     DevBuf<float4> d_pathRec, d_vertexRec;  // interleaved layout (PathState Field, ppg_kernels.h): 8 float4 per path, 4 / 6 per vertex slot
     DevBuf<uint4> d_miscCompact;
-    bool aosPaths = false;
-    int pathLayout = 1;  // 1 soa, 2 aos, 3 pack (allocPaths; PPG_PATH_LAYOUT)
+    bool aosPaths = false;  // the layout in use (allocPaths; PPG_PATH_LAYOUT)
     DevBuf<unsigned int> d_queue[2], d_qcount[2], d_qtotal, d_queueSorted, d_qcommon;
     DevBuf<unsigned char> d_sortKeys;
     int maxBatchFinal = 1;  // passes per batch in the final iteration (nothing is recorded: no vertex slots needed)
@@ -693,7 +682,6 @@ struct ppg_ctx {
     size_t tuneBatchPaths = 0;        // PPG_BATCH_PATHS: paths in flight per batch of passes (0 = automatic)
     int tuneBlocks = 0;               // PPG_BLOCKS: persistent workgroups of the path kernels (0 = 4096)
     bool tuneForceBvh = false;        // PPG_FORCE_BVH: trace small scenes through the BVH as well
-    bool tuneFuse = false;            // PPG_FUSE: trace small scenes inside k_generate / k_shade
     bool tuneNoSort = false;          // PPG_NO_SORT: do not sort the queue slices by BSDF type before k_shade<FULL>
     bool tuneNoSortFirst = false;     // PPG_NO_SORT_FIRST: the first bounce of a batch unsorted through the complete k_shade<FULL>
     bool tuneNoSplit = false;         // PPG_NO_SPLIT: one k_shade<FULL> over the whole sorted slice instead of k_shade<.., MSET_COMMON> + the rest
@@ -706,11 +694,10 @@ struct ppg_ctx {
     bool debugBatch = false;          // PPG_DEBUG_BATCH: one line per batch on stderr (paths, live paths after every bulk bounce, tail time)
     int tuneFinalBatch = 0;           // PPG_FINAL_BATCH: passes per batch of the final iteration (0 = 64)
     int tuneTailBlocks = 0;           // PPG_TAIL_BLOCKS: workgroups of k_tail when k_commit runs beside it (0 = automatic)
-    int tunePathLayout = 0;           // PPG_PATH_LAYOUT = soa | aos | pack: layout of the per-path state (0 = automatic, allocPaths)
+    int tunePathLayout = 0;           // PPG_PATH_LAYOUT = soa (1) | aos (2): layout of the per-path state (0 = automatic, allocPaths)
     int tuneBlocksSmall = 2048;       // PPG_BLOCKS_SMALL: workgroups of the wavefront kernels for batches of at most tuneSmallPaths paths (0 = nBlocks for every batch)
     size_t tuneSmallPaths = 13000000; // PPG_SMALL_PATHS.  KITCHEN 720p (r06_experiments.json s23, s27): 2048 for batches up to 4 M / 16 M / 32 M paths: +0.1 / +1.1 / +1.2 % on the
                                       // driver's command (its final iteration is one batch of 12 M), +0.2 % at 127 passes, -0.3 % at 1023 with 16 M (its 14.7 M-path rounds): 13 M
-    bool tuneSortKernel = false;      // PPG_SORT_KERNEL=1: the BSDF-type sort of the queue slices as a launch of its own (k_sort_slices) instead of inside k_trace
     int tuneBvhLeaf = 4;              // PPG_BVH_LEAF: triangles per BVH leaf (1..8).  KITCHEN 720p, driver's command: 4 -> 3 +3.5 % once the node test had become
                                       // cheap (130.9 -> 135.6, A/B on one box; with the world-space decode 2 / 3 / 4 / 6 / 8 gave 125.8 / 125.9 / 124.5 / 119.6 / 115.2)
     float tuneBvhPad = 2e-6f;         // PPG_BVH_PAD: box padding relative to the scene extent
@@ -770,16 +757,9 @@ struct ppg_ctx {
     }
 };
 
-namespace {
-
-}  // namespace
 void ppg_launch_shade(int variant, const ShadeLaunch &a) {
-    switch (variant >> 1) {
-        case 0: ppg_launch_shade_pair0(variant, a); break;
-        case 1: ppg_launch_shade_pair1(variant, a); break;
-        case 2: ppg_launch_shade_pair2(variant, a); break;
-        default: ppg_launch_shade_pair3(variant, a); break;
-    }
+    if (variant >> 1) ppg_launch_shade_pair1(variant, a);
+    else ppg_launch_shade_pair0(variant, a);
 }
 void ppg_launch_tail(int variant, const TailLaunch &a) {
     switch (variant >> 1) {
@@ -789,9 +769,6 @@ void ppg_launch_tail(int variant, const TailLaunch &a) {
         default: ppg_launch_tail_pair3(variant, a); break;
     }
 }
-void ppg_launch_commit(int sf, int df, const CommitLaunch &a) { ppg_launch_commit_all(sf, df, a); }
-void ppg_launch_commit_records(int sf, const CommitLaunch &a) { ppg_launch_commit_records_all(sf, a); }
-void ppg_launch_splat(int df, const SplatLaunch &a) { ppg_launch_splat_all(df, a); }
 namespace {
 
 template <typename F> void timedLaunch(ppg_ctx *ctx, const char *name, uint64_t units, F &&launch) {
@@ -1042,17 +1019,13 @@ int allocPaths(ppg_ctx *ctx) {
     size_t nn = std::max<size_t>(1, std::max(n, nFinal));
     ctx->maxVertices = PPG_MAX_VERTICES;
     if (ctx->maxDepth > 0) ctx->maxVertices = std::max(1, std::min(PPG_MAX_VERTICES, ctx->maxDepth - 1));
-    // layout of the per-path state: one array per field (soa), interleaved 128-byte records (aos), or two 64-byte records (pack).  Interleaving
+    // layout of the per-path state: one array per field (soa) or interleaved 128-byte records (aos).  Interleaving
     // helps the late, scattered bounces — after compaction and the sort by material a lane holds an arbitrary path, and five 16-byte accesses
     // to five arrays cost five sectors — and hurts the early, coalesced ones.  Measured on MI355X, round 4 (profiles/r04_experiments.json,
-    // Msamples/s soa / pack / aos): KITCHEN 1023 passes 202 / 207 / 209, 127 passes 183 / 185 / 187, 20 passes equal; torus-class 1080p
-    // 129 / 138 / 142; SPACESHIP 1080p 1008 / 925 / 874; cbox-720p 1350 / 1170 / 1038.  So: interleaved for paths of unbounded depth over a BVH
-    // scene (long random walks: most bounces are late ones), one array per field otherwise; PPG_PATH_LAYOUT = soa | aos | pack overrides.
-    if (ctx->tunePathLayout == 0) ctx->pathLayout = (ctx->maxDepth < 0 && ctx->scene.n_tris > 64) ? 2 : 1; else ctx->pathLayout = ctx->tunePathLayout;
-    // PPG_PATH_LAYOUT=pack: two 64-byte records per path — (throughput, Li, key / flags) and (ray origin, direction, hit) — so that a scattered
-    // path costs k_shade two sectors to read and two to write instead of five and five, and k_trace one; the vertex slots stay one array per field
-    const bool packPaths = ctx->pathLayout == 3;
-    ctx->aosPaths = ctx->pathLayout == 2 || packPaths;
+    // Msamples/s soa / aos): KITCHEN 1023 passes 202 / 209, 127 passes 183 / 187, 20 passes equal; torus-class 1080p 129 / 142; SPACESHIP 1080p
+    // 1008 / 874; cbox-720p 1350 / 1038.  So: interleaved for paths of unbounded depth over a BVH scene (long random walks: most bounces are
+    // late ones), one array per field otherwise; PPG_PATH_LAYOUT = soa | aos overrides.
+    ctx->aosPaths = ctx->tunePathLayout ? ctx->tunePathLayout == 2 : (ctx->maxDepth < 0 && ctx->scene.n_tris > 64);
     if (ctx->aosPaths) { HIP_CHECK(ctx->d_pathRec.reserve(nn * 8)); HIP_CHECK(ctx->d_miscCompact.reserve(nn)); }
     else {
         HIP_CHECK(ctx->d_ray_o.reserve(nn)); HIP_CHECK(ctx->d_ray_d.reserve(nn)); HIP_CHECK(ctx->d_thr.reserve(nn));
@@ -1082,15 +1055,7 @@ int allocPaths(ppg_ctx *ctx) {
     const bool filtered = ctx->spatialFilter != SF_NEAREST;
     PathState &P = ctx->paths;
     P.n_paths = (unsigned int)n; P.n_pix = ctx->nPix; P.pixels = ctx->d_pixels.p;
-    if (packPaths) {
-        float4 *a = ctx->d_pathRec.p, *b = ctx->d_pathRec.p + 4 * nn;
-        P.thr = {a, 4}; P.li = {a + 1, 4}; P.misc = {reinterpret_cast<uint4 *>(a + 2), 4};
-        P.ray_o = {b, 4}; P.ray_d = {b + 1, 4}; P.hit = {b + 2, 4};
-        HIP_CHECK(ctx->d_vd.reserve(nv)); HIP_CHECK(ctx->d_vthr.reserve(nv)); HIP_CHECK(ctx->d_vbsdf.reserve(nv)); HIP_CHECK(ctx->d_vrad.reserve(nv));
-        if (filtered) { HIP_CHECK(ctx->d_vo.reserve(nv)); HIP_CHECK(ctx->d_vvox.reserve(nv)); }
-        P.v_d = {ctx->d_vd.p, 1}; P.v_thr = {ctx->d_vthr.p, 1}; P.v_bsdf = {ctx->d_vbsdf.p, 1}; P.v_rad = {ctx->d_vrad.p, 1};
-        P.v_o = {filtered ? ctx->d_vo.p : nullptr, 1}; P.v_vox = {filtered ? ctx->d_vvox.p : nullptr, 1};
-    } else if (ctx->aosPaths) {
+    if (ctx->aosPaths) {
         const unsigned int vs = filtered ? 6u : 4u;
         HIP_CHECK(ctx->d_vertexRec.reserve(nv * vs));
         float4 *r = ctx->d_pathRec.p, *v = ctx->d_vertexRec.p;
@@ -1513,27 +1478,20 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
     }
     const int gridAll = gridFor(P.n_paths);
     const bool smallScene = ctx->scene.n_tris <= 64 && ctx->ldsTris == ctx->scene.n_tris && ctx->scene.n_spheres == 0 && !ctx->tuneForceBvh;
-    // Tracing inside k_generate / k_shade (no k_trace launch, no ray/hit round trip) was measured SLOWER on MI355X
-    // (cbox-720p, 63 passes: 184 ms vs 172 ms for generate+trace+shade): the fused kernel needs 142 VGPRs (3 waves/SIMD)
-    // and only the surviving lanes trace.  Kept selectable for re-measurement on other scenes.
-    // (not in a round whose stragglers' records are deferred: which paths those are is decided where k_tail takes them, include/ppg.h "STRAGGLERS")
-    const bool fused = smallScene && ctx->tuneFuse && !(adamRound && ctx->adamFast && ctx->maxDepth < 0);
+    // (small scenes go through k_trace too: tracing them inside k_generate / k_shade was measured slower, DESIGN.md "Tuning switches")
     const bool neeOn = ctx->doNee;  // m_doNee of this iteration (doNeeWithSpp, GP:1331-1340)
     const bool fullMats = ctx->fullMaterials;  // any BSDF beyond diffuse / two-sided diffuse / mirror: the FULL kernel variants
     const size_t triBytes = (size_t)ctx->scene.n_tris * 48;
     const bool unbounded = ctx->maxDepth < 0;
     const size_t ldsBytes = smallScene ? (size_t)ctx->ldsTris * 48 : (size_t)PPG_LDS_STACK * PPG_BLOCK * 4;
-    const size_t traceLds = smallScene ? ldsBytes : (size_t)PPG_TRACE_STACK * PPG_BLOCK * 4 + (PPG_TRACE_PAIRS ? (PPG_BLOCK / 64) * sizeof(PairLds) : 0);  // k_trace: + a wave's pair scratch
+    const size_t traceLds = smallScene ? ldsBytes : (size_t)PPG_TRACE_STACK * PPG_BLOCK * 4 + (PPG_BLOCK / 64) * sizeof(PairLds);  // k_trace: + a wave's pair scratch
     // live paths below which the wavefront stops (unbounded paths: k_tail takes over; bounded paths: nothing is left)
     const unsigned int stopBelow = unbounded ? (ctx->tailThreshold ? ctx->tailThreshold : std::max(ctx->tailMin, P.n_paths / ctx->tailDiv)) : 1u;
     unsigned int hostCount = P.n_paths;
     int bouncesRun = 0;
     if (P.n_paths > 0) {
         int qin = QIN_FIRST;
-        timedLaunch(ctx, "k_generate", P.n_paths, [&] {
-            if (fused) hipLaunchKernelGGL(k_generate<true>, dim3(gridAll), dim3(PPG_BLOCK), triBytes, s, P, S, R, Q);
-            else hipLaunchKernelGGL(k_generate<false>, dim3(gridAll), dim3(PPG_BLOCK), 0, s, P, S, R, Q);
-        });
+        timedLaunch(ctx, "k_generate", P.n_paths, [&] { hipLaunchKernelGGL(k_generate, dim3(gridAll), dim3(PPG_BLOCK), 0, s, P, S, R, Q); });
         // Bounce 1 works on all paths of the batch; every later bounce on the dense list of live paths that k_scan_counts + k_gather_slices
         // rebuild from k_shade's output slices (ppg_kernels.h "Queues").  Bounded paths (maxDepth > 0) run maxDepth bounces.  Unbounded
         // paths run wavefront bounces until fewer than `stopBelow` paths are alive and hand those to the persistent-thread tail (k_tail).
@@ -1542,8 +1500,7 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
         // bounces launched beyond that point return at once.  The host synchronises once per batch.
         int maxBounces = ctx->maxDepth;
         if (unbounded) {
-            if (fused) maxBounces = 1 << 20;
-            else if (ctx->tuneBulkBounces >= 0) maxBounces = std::min(64, ctx->tuneBulkBounces);
+            if (ctx->tuneBulkBounces >= 0) maxBounces = std::min(64, ctx->tuneBulkBounces);
             else {
                 // live(b) of this batch ~ (live(b) / paths of the previous batch) * paths of this one; beyond what was observed, the last ratio
                 int need = 8;
@@ -1566,35 +1523,26 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
             }
             // (a round whose stragglers' records are deferred: a path alive after wavefront bounce b has depth b, and which paths are
             // stragglers is decided where k_tail takes them — never beyond the depth of the rule, include/ppg.h "STRAGGLERS")
-            if (adamRound && ctx->adamFast && !fused) maxBounces = std::min(maxBounces, std::max(1, ctx->deferDepthAdam));
+            if (adamRound && ctx->adamFast) maxBounces = std::min(maxBounces, std::max(1, ctx->deferDepthAdam));
         }
-        const bool liveCount = ctx->timer.enabled || (unbounded && fused);  // kernel timing wants the units of every launch
+        const bool liveCount = ctx->timer.enabled;  // kernel timing wants the units of every launch
         unsigned int *counts = ctx->d_bounceCounts.p;  // [0..63] live paths after bounce b, [64] the stop flag
         HIP_CHECK(hipMemsetAsync(counts, 0, 72 * 4, s));
         Q.stop = counts + 64;
         Q.dense_n = ctx->d_total.p;
         for (int b = 0; b < maxBounces; ++b) {
             // (the first bounce — every path of the batch, camera rays — is sorted only for the sake of the split into material classes)
-            const bool sortSlices = fullMats && !fused && (qin == QIN_DENSE || (Q.n_common && !neeOn && !ctx->tuneNoSortFirst)) && ctx->d_queueSorted.p;
-            // k_trace sorts its own slices when it has traced them (sort_slice, ppg_kernels.h); PPG_SORT_KERNEL=1: k_sort_slices as a launch of its own
-            const bool sortInTrace = sortSlices && !ctx->tuneSortKernel;
-            unsigned int *const trSorted = sortInTrace ? ctx->d_queueSorted.p : nullptr;
-            unsigned char *const trKeys = sortInTrace ? ctx->d_sortKeys.p : nullptr;
-            if (!fused)
-                timedLaunch(ctx, "k_trace", hostCount, [&] {
-                    if (smallScene) hipLaunchKernelGGL((k_trace<true, false>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, 0, ctx->ldsTris, trSorted, trKeys);
-                    else if (ctx->timer.enabled) hipLaunchKernelGGL((k_trace<false, true>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
-                    else hipLaunchKernelGGL((k_trace<false, false>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
-                });
-            int shadeIn = qin;
-            if (sortSlices) {
-                if (!sortInTrace)
-                    timedLaunch(ctx, "k_sort_slices", hostCount, [&] {
-                        hipLaunchKernelGGL(k_sort_slices, dim3(grid), dim3(PPG_BLOCK), 0, s, P, S, Q, qin, ctx->d_queueSorted.p, ctx->d_sortKeys.p);
-                    });
-                shadeIn = QIN_SORTED;
-            }
-            ctx->joinTree();  // (k_generate, the first k_trace and k_sort_slices ran beside the previous round's optimiser: k_shade needs its result)
+            const bool sortSlices = fullMats && (qin == QIN_DENSE || (Q.n_common && !neeOn && !ctx->tuneNoSortFirst)) && ctx->d_queueSorted.p;
+            // k_trace sorts its own slice when it has traced it (sort_slice, ppg_kernels.h)
+            unsigned int *const trSorted = sortSlices ? ctx->d_queueSorted.p : nullptr;
+            unsigned char *const trKeys = sortSlices ? ctx->d_sortKeys.p : nullptr;
+            timedLaunch(ctx, "k_trace", hostCount, [&] {
+                if (smallScene) hipLaunchKernelGGL((k_trace<true, false>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, 0, ctx->ldsTris, trSorted, trKeys);
+                else if (ctx->timer.enabled) hipLaunchKernelGGL((k_trace<false, true>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
+                else hipLaunchKernelGGL((k_trace<false, false>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
+            });
+            int shadeIn = sortSlices ? QIN_SORTED : qin;
+            ctx->joinTree();  // (k_generate and the first k_trace ran beside the previous round's optimiser: k_shade needs its result)
             // FULL scene, sorted slice, no luminaire sampling: the common material classes first, in their own leaner kernel (MSET_COMMON)
             const bool split = shadeIn == QIN_SORTED && Q.n_common && !neeOn;
             if (split) {
@@ -1604,12 +1552,12 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
                 });
                 shadeIn = QIN_SORTED_REST;
             }
-            timedLaunch(ctx, fused ? "k_shade<fused>" : (neeOn ? "k_shade<nee>" : (fullMats ? (split ? "k_shade<rest>" : "k_shade<full>") : "k_shade")), hostCount, [&] {
+            timedLaunch(ctx, neeOn ? "k_shade<nee>" : (fullMats ? (split ? "k_shade<rest>" : "k_shade<full>") : "k_shade"), hostCount, [&] {
                 const int small = smallScene ? 1 : 0;
-                // dynamic LDS: the staged triangles (fused, or luminaire sampling on a small scene) or the shadow rays' BVH stack columns
+                // dynamic LDS: the staged triangles (luminaire sampling on a small scene) or the shadow rays' BVH stack columns
                 const size_t neeBytes = smallScene ? triBytes : (size_t)PPG_LDS_STACK * PPG_BLOCK * 4;
-                const size_t lds = fused ? triBytes : ((neeOn || ctx->scene.has_null) ? neeBytes : 0);
-                const int variant = (fused ? 4 : 0) | (neeOn ? 2 : 0) | (fullMats ? 1 : 0);
+                const size_t lds = (neeOn || ctx->scene.has_null) ? neeBytes : 0;
+                const int variant = (neeOn ? 2 : 0) | (fullMats ? 1 : 0);
                 ShadeLaunch a{grid, lds, s, P, S, T, R, Q, shadeIn, small, ctx->d_queueSorted.p};
                 ppg_launch_shade(variant, a);
             });
@@ -1621,7 +1569,7 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
             if (liveCount) {
                 HIP_CHECK(hipMemcpyAsync(&hostCount, ctx->d_total.p, 4, hipMemcpyDeviceToHost, s));
                 HIP_CHECK(hipStreamSynchronize(s));
-                if (hostCount == 0 || (unbounded && !fused && hostCount < stopBelow)) break;
+                if (hostCount == 0 || (unbounded && hostCount < stopBelow)) break;
             }
         }
     }
@@ -1634,7 +1582,7 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
     // stragglers afterwards.  Integer accumulation makes the split invisible in the result.  In a round of the optimiser, the record
     // positions must then be known before the tail has run: a straggler reserves max_vertices positions (unused ones stay holes).
     ctx->joinTree();  // (a batch without a wavefront bounce)
-    const bool tail = unbounded && !fused && P.n_paths > 0;
+    const bool tail = unbounded && P.n_paths > 0;
     const bool commit = !ctx->isFinalIter && P.n_paths > 0;
     const bool fastRound = adamRound && ctx->adamFast && P.n_paths > 0;
     // STRAGGLERS.  k_tail hands the paths still alive at depth `deferDepth` over to a second launch that runs beside the NEXT batch (see
@@ -2425,7 +2373,6 @@ int ppg_create(const ppg_config *cfg, ppg_ctx **out) {
         if (const char *e = getenv("PPG_BATCH_PATHS")) c->tuneBatchPaths = (size_t)std::max(1ll, atoll(e));
         if (const char *e = getenv("PPG_BLOCKS")) c->tuneBlocks = std::max(1, atoi(e));
         c->tuneForceBvh = getenv("PPG_FORCE_BVH") != nullptr;
-        c->tuneFuse = getenv("PPG_FUSE") != nullptr;
         c->tuneNoSort = getenv("PPG_NO_SORT") != nullptr;
         c->tuneNoSplit = getenv("PPG_NO_SPLIT") != nullptr;
         c->tuneNoSortFirst = getenv("PPG_NO_SORT_FIRST") != nullptr;
@@ -2439,8 +2386,7 @@ int ppg_create(const ppg_config *cfg, ppg_ctx **out) {
         c->debugBatch = getenv("PPG_DEBUG_BATCH") != nullptr;
         if (const char *e = getenv("PPG_TAIL_BLOCKS")) c->tuneTailBlocks = std::max(1, atoi(e));
         if (const char *e = getenv("PPG_FINAL_BATCH")) c->tuneFinalBatch = std::max(1, atoi(e));
-        if (const char *e = getenv("PPG_PATH_LAYOUT")) c->tunePathLayout = !strcmp(e, "aos") ? 2 : (!strcmp(e, "pack") ? 3 : (!strcmp(e, "soa") ? 1 : 0));
-        if (const char *e = getenv("PPG_SORT_KERNEL")) c->tuneSortKernel = atoi(e) != 0;
+        if (const char *e = getenv("PPG_PATH_LAYOUT")) c->tunePathLayout = !strcmp(e, "aos") ? 2 : (!strcmp(e, "soa") ? 1 : 0);
         if (const char *e = getenv("PPG_BLOCKS_SMALL")) c->tuneBlocksSmall = std::max(0, atoi(e));
         if (const char *e = getenv("PPG_SMALL_PATHS")) c->tuneSmallPaths = (size_t)std::max(0ll, atoll(e));
         if (const char *e = getenv("PPG_BVH_LEAF")) c->tuneBvhLeaf = std::max(1, std::min(8, atoi(e)));
@@ -2453,7 +2399,7 @@ int ppg_create(const ppg_config *cfg, ppg_ctx **out) {
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0) { g_createError = std::string("no HIP device available: ") + hipGetErrorString(e); return PPG_ERR_DEVICE; }
     if (c->device < 0 || c->device >= ndev) { g_createError = "device ordinal out of range"; return PPG_ERR_INVALID; }
-    if ((e = hipSetDevice(c->device)) != hipSuccess || (e = hipStreamCreate(&c->stream)) != hipSuccess || (e = createSecondStream(&c->stream2)) != hipSuccess ||
+    if ((e = hipSetDevice(c->device)) != hipSuccess || (e = hipStreamCreate(&c->stream)) != hipSuccess || (e = hipStreamCreate(&c->stream2)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&c->evFork, hipEventDisableTiming)) != hipSuccess || (e = hipEventCreateWithFlags(&c->evJoin, hipEventDisableTiming)) != hipSuccess ||
         (e = hipStreamCreate(&c->stream3)) != hipSuccess || (e = hipEventCreateWithFlags(&c->evTreeFork, hipEventDisableTiming)) != hipSuccess ||
         (e = hipStreamCreate(&c->stream4)) != hipSuccess || (e = hipEventCreateWithFlags(&c->evStragFork, hipEventDisableTiming)) != hipSuccess ||
@@ -3302,7 +3248,7 @@ int ppg_kernel_times(ppg_ctx *ctx, ppg_kernel_time *out, uint32_t cap, uint32_t 
     uint32_t k = 0;
     for (size_t i = 0; i < ctx->timer.names.size() && k < cap; ++i, ++k) {
         out[k].name = ctx->timer.names[i].c_str(); out[k].ms = ctx->timer.ms[i]; out[k].launches = ctx->timer.launches[i]; out[k].units = ctx->timer.units[i];
-        // the two launches over a sorted slice were both booked with the slice's rays: the common classes' share was counted by k_sort_slices
+        // the two launches over a sorted slice were both booked with the slice's rays: the common classes' share was counted by sort_slice
         if (ctx->timer.names[i] == "k_shade<common>") out[k].units = ctx->shadeCommonRays;
         else if (ctx->timer.names[i] == "k_shade<rest>") out[k].units = ctx->timer.units[i] > ctx->shadeCommonRays ? ctx->timer.units[i] - ctx->shadeCommonRays : 0;
     }

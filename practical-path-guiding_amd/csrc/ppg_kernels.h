@@ -19,10 +19,6 @@
 #ifndef PPG_SHADE_WAVES
 #define PPG_SHADE_WAVES 4  // waves per SIMD requested for k_shade: 128 VGPRs without spilling (5 or 6 spill and are slower, 2-3 waste occupancy)
 #endif
-#ifndef PPG_LEAF_VOTE
-#define PPG_LEAF_VOTE 16  // k_trace: lanes holding a leaf wait until this many lanes of the wave do (0 = test leaves at once).  KITCHEN 720p,
-                          // k_trace over 127 passes: 0 → 486 ms, 8 → 412, 16 → 387, 32 → 390
-#endif
 #ifndef PPG_SHADE_WAVES_FULL
 #define PPG_SHADE_WAVES_FULL 3  // ... for the FULL material set (k_shade<.., FULL>, k_tail<.., FULL>), whose BSDF code needs more registers: at 128 VGPRs it
                                 // spills 257 of them (KITCHEN 720p: 4 waves 76.5, 3 waves 81.3, 2 waves 79.6 Msamples/s)
@@ -36,7 +32,7 @@
 #define PPG_SHADE_WAVES_COMMON 3  // ... for k_shade<.., FULL, MSET_COMMON>: the common lobes of a FULL scene (see MSET_COMMON)
 #endif
 
-// Material subsets of the FULL kernels.  A FULL scene's queue slices are counting-sorted by the BSDF at the new hit (k_sort_slices); the
+// Material subsets of the FULL kernels.  A FULL scene's queue slices are counting-sorted by the BSDF at the new hit (sort_slice); the
 // COMMON classes — diffuse / two-sided diffuse, smooth and rough conductor, plastic, rough plastic on a triangle, no mask, no bump map —
 // come first and are shaded by k_shade<.., FULL, MSET_COMMON>, a variant from which everything else is compiled out: analytic spheres, rays
 // that left the scene (environment lookup), null components and the look-through trace, glass / thin glass / rough dielectric lobes, the
@@ -150,7 +146,7 @@ struct BlockStats {
     unsigned long long rays, path_len, committed;
     unsigned long long bvh_nodes, bvh_tris;  // k_trace<.., COUNT>: BVH4 nodes visited / triangles tested (kernel timing runs only: the roofline's n, t)
     unsigned long long max_len;              // longest path finished by k_tail (diagnostics: PPG_DEBUG_BATCH)
-    unsigned long long shade_common;         // rays k_sort_slices dealt to k_shade<.., MSET_COMMON> (the units of its roofline line)
+    unsigned long long shade_common;         // rays sort_slice dealt to k_shade<.., MSET_COMMON> (the units of its roofline line)
 };
 
 // Queues.  Every wavefront bounce reads the DENSE list of live paths (items[1], dense_n entries), dealt to the persistent workgroups in
@@ -161,7 +157,7 @@ struct BlockStats {
 // in flight: k_trace took 0.5 ms per bounce whether 920 k or 300 k rays were left.)
 struct Queues {
     unsigned int *items[2];  // [0]: k_shade's output slices; [1]: the dense list
-    unsigned int *count[2];  // [0][b]: entries of output slice b; [1][b]: entries of workgroup b's slice of the sorted list (k_sort_slices)
+    unsigned int *count[2];  // [0][b]: entries of output slice b; [1][b]: entries of workgroup b's slice of the sorted list (sort_slice)
     unsigned int *n_common;  // [b]: how many of them, at the front, belong to the COMMON material classes (MSET_COMMON); nullptr: no split
     unsigned int cap;        // entries per workgroup slice
     unsigned int n_blocks;
@@ -173,7 +169,7 @@ struct Queues {
 // what a wavefront kernel reads (its `qin` argument)
 #define QIN_FIRST (-1)   // bounce 1: every path of the batch, dealt in chunks of PPG_CHUNK (a wave = 64 neighbouring pixels)
 #define QIN_DENSE (-2)   // the dense list, dealt in chunks of PPG_DCHUNK
-#define QIN_SORTED (-3)  // k_shade after k_sort_slices: the workgroup's share of the dense list, re-ordered, in its slice of `sorted_items`
+#define QIN_SORTED (-3)  // k_shade after sort_slice: the workgroup's share of the dense list, re-ordered, in its slice of `sorted_items`
 #define QIN_SORTED_COMMON (-4)  // ... its front part: the hits on the common material classes (k_shade<.., MSET_COMMON>)
 #define QIN_SORTED_REST (-5)    // ... the rest of it (the complete k_shade, launched second: it APPENDS to the first launch's output slice)
 #ifndef PPG_DCHUNK
@@ -318,17 +314,7 @@ D Hit trace_small(const float4 *lds_tris, const DevScene &S, F3 o, F3 d, float r
 // k_generate — renderBlock's sample loop head (GP:1613-1630) + PerspectiveCamera::sampleRayDifferential (or ThinLens's: S.cam.lens,
 // a uniform branch; the pinhole's arithmetic is the same as without it)
 // ------------------------------------------------------------------------------------------------
-// FUSED (small scenes): the camera ray is traced right here from the LDS copy of the scene.
-template <bool FUSED>
-__global__ __launch_bounds__(PPG_BLOCK) void k_generate(PathState P, DevScene S, RenderParams R, Queues Q) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    __shared__ unsigned long long acc;
-    const float4 *lds_tris = (const float4 *)lds_raw;
-    if (FUSED) {
-        for (int k = threadIdx.x; k < 3 * S.n_tris; k += blockDim.x) ((float4 *)lds_raw)[k] = S.accel_small[k];
-        __syncthreads();
-    }
-    unsigned int traced = 0;
+static __global__ __launch_bounds__(PPG_BLOCK) void k_generate(PathState P, DevScene S, RenderParams R, Queues Q) {
     for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < P.n_paths; i += gridDim.x * blockDim.x) {
         unsigned int k = i % P.n_pix, j = i / P.n_pix;
         unsigned int pixel = P.pixels[k];
@@ -360,19 +346,12 @@ __global__ __launch_bounds__(PPG_BLOCK) void k_generate(PathState P, DevScene S,
         float invZ = 1.0f / dl.z;
         float mint = S.cam.near_clip * invZ, maxt = S.cam.far_clip * invZ;
         F3 d = xf_vec(S.cam.c2w, dl);
-        if (FUSED) {
-            Hit h = trace_small(lds_tris, S, o, d, mint, maxt);
-            P.hit[i] = make_float4(h.t, h.u, h.v, __int_as_float(h.prim));
-            ++traced;
-        } else {
-            P.ray_o[i] = make_float4(o.x, o.y, o.z, mint);
-        }
+        P.ray_o[i] = make_float4(o.x, o.y, o.z, mint);
         P.ray_d[i] = make_float4(d.x, d.y, d.z, maxt);
         P.thr[i] = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
         P.li[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         P.misc[i] = make_uint4(key, dim, 1u | FL_EMITTED_OK, 0u);
     }
-    if (FUSED) block_add_u64(&acc, &Q.stats[blockIdx.x % Q.n_blocks].rays, traced);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -396,13 +375,9 @@ D LdsScene stage_scene(const DevScene &S, unsigned char *lds_raw, int lds_nodes,
 // BVH4 traversal of one queue slice with ray replacement: a lane whose ray is finished immediately takes the next
 // entry of the slice (LDS ticket), so a wave stays full until the slice is empty instead of idling until its
 // longest ray is done — secondary rays are incoherent and their traversal lengths differ by an order of magnitude.
-#ifndef PPG_TRACE_PAIRS
-#define PPG_TRACE_PAIRS 1  // k_trace: the leaf phase of a wave tests compacted (ray, triangle) pairs (leaf_pairs, ppg_device.h); 0 = a leaf per lane
-#endif
 #ifndef PPG_TRACE_STACK
-#define PPG_TRACE_STACK (PPG_TRACE_PAIRS ? 12 : 16)  // rows of k_trace's LDS stack columns (with the pair scratch: 19 KB a workgroup, eight to a CU)
+#define PPG_TRACE_STACK 12  // rows of k_trace's LDS stack columns (with the pair scratch: 19 KB a workgroup, eight to a CU)
 #endif
-#if PPG_TRACE_PAIRS
 // The traversal with (ray, triangle)-pair compaction.  Lanes stay in the loop until the whole wave is out of rays (a lane without a ray
 // still tests other lanes' triangles); per iteration the wave first runs its leaf phase if the vote passes, then the node step of every
 // lane holding an interior node — a lane that popped a node after its leaf takes that step in the same iteration.
@@ -474,88 +449,13 @@ D void trace_slice_bvh4(const PathState &P, const DevScene &S, int *lds_stack, u
     if (COUNT && (threadIdx.x & 63) == 0) { n_nodes += w_nodes; n_tris += w_tris; }
     __syncthreads();
 }
-#else
-template <bool COUNT>
-D void trace_slice_bvh4(const PathState &P, const DevScene &S, int *lds_stack, unsigned int *ticket, const Work &work,
-                        unsigned int b, unsigned int nb, unsigned int &traced, unsigned long long &n_nodes, unsigned long long &n_tris) {
-    const unsigned int count = work.count;
-    if (threadIdx.x == 0) *ticket = 0;
-    __syncthreads();
-    TStack st;
-    int st_over[48 - PPG_TRACE_STACK];
-    st.over = st_over;
-    st.lds = lds_stack + threadIdx.x; st.stride = PPG_BLOCK; st.sp = 0; st.cap = PPG_TRACE_STACK;
-    bool have = false;
-    unsigned int i = 0;
-    F3 o = f3s(0.0f), d = f3s(0.0f), id = f3s(0.0f);
-    float mint = 0, maxt = 0;
-    Hit best;
-    best.t = 0; best.u = 0; best.v = 0; best.prim = -1;
-    int bestOrig = 0, cur = 0;
-    for (;;) {
-        if (!have) {
-            unsigned int k = atomicAdd(ticket, 1u);
-            if (k >= count) break;
-            i = work_item(work, k, b, nb);
-            if (i >= P.n_paths) continue;
-            float4 ro = P.ray_o[i], rd = P.ray_d[i];
-            o = f3(ro.x, ro.y, ro.z); d = f3(rd.x, rd.y, rd.z);
-            mint = ro.w; maxt = rd.w;
-            if (mint == PPG_EPSILON)  // adaptive ray epsilon
-                mint *= ppg_max(ppg_max(ppg_max(ppg_abs(o.x), ppg_abs(o.y)), ppg_abs(o.z)), PPG_EPSILON);
-            id = f3(safe_inv(d.x), safe_inv(d.y), safe_inv(d.z));
-            best.t = __builtin_inff(); best.u = 0; best.v = 0; best.prim = -1;
-            bestOrig = 0x7fffffff; cur = 0; st.sp = 0;
-            have = true;
-        }
-        // One step per iteration and lane: either an interior node (test its four child boxes, continue with the nearest child, push the
-        // others) or a leaf popped from the stack (test its triangles).  Leaves are NOT tested inside the node step: a wave executes the
-        // union of its lanes' branches, and with the triangle loops nested in the node step almost every iteration ran up to four
-        // divergent triangle loops for the few lanes that had a leaf child (measured on KITCHEN: the traversal was bound by issue slots,
-        // not by bytes — 64-byte nodes alone changed nothing).
-#if PPG_LEAF_VOTE > 0
-        // leaves wait until PPG_LEAF_VOTE lanes of the wave have one (or no lane has an interior node left): the triangle code then runs
-        // for many lanes at once instead of in almost every iteration for one or two of them
-        const unsigned long long leafLanes = __ballot(cur < 0), nodeLanes = __ballot(cur >= 0 && cur != PPG_BVH4_EMPTY);
-        const bool doLeaves = __popcll(leafLanes) >= PPG_LEAF_VOTE || nodeLanes == 0ull;
-#else
-        const bool doLeaves = true;
-#endif
-        if (cur >= 0) {
-            if (COUNT) ++n_nodes;
-            const Bvh4Hits hc = bvh4_children(S.bvh4 + cur, o, id, mint, fminf(maxt, best.t));
-            if (hc.m > 0) {
-                st.push_children(hc.m, hc.c1, hc.c2, hc.c3);
-                cur = hc.c0;
-            } else cur = st.sp > 0 ? st.pop() : PPG_BVH4_EMPTY;
-        } else if (doLeaves) {
-            const int code = ~cur;
-            const int first = code >> 3, cnt = (code & 7) + 1;
-            if (COUNT) n_tris += (unsigned long long)cnt;
-            for (int q = first; q < first + cnt; ++q) {
-                float tt, uu, vv;
-                const float4 *T = S.accel + 3 * q;
-                int orig;
-                if (tri_hit(T, o, d, mint, fminf(maxt, best.t), tt, uu, vv, orig)) {
-                    if (tt < best.t || (tt == best.t && orig < bestOrig)) { best.t = tt; best.u = uu; best.v = vv; best.prim = q; bestOrig = orig; }
-                }
-            }
-            cur = st.sp > 0 ? st.pop() : PPG_BVH4_EMPTY;
-        }
-        if (cur == PPG_BVH4_EMPTY) {  // stack empty: this ray is done
-            if (S.n_spheres) sphere_pass<false>(S, o, d, mint, maxt, best);
-            P.hit[i] = make_float4(best.t, best.u, best.v, __int_as_float(best.prim));
-            ++traced;
-            have = false;
-        }
-    }
-    __syncthreads();
-}
-#endif
 
-// The counting sort of one workgroup's queue slice by the BSDF type at the new hit (see k_sort_slices below, which is this function as a
-// kernel).  Since round 6 k_trace runs it for its own slice when the slice is traced: one launch per bounce fewer, and a workgroup that
-// waits for its three dependent loads per ray (hit -> triangle -> material) does so while the CU's other workgroups still trace.
+// Scenes with many BSDF types (k_shade<FULL>): after the first bounce the rays of a wave hit unrelated surfaces, and a wave executes the
+// union of its lanes' BSDF branches (rough plastic, rough conductor, glass, ...).  Every workgroup therefore counting-sorts its queue
+// slice by the BSDF type at the new hit (16 bins; rays that left the scene last, so that the lanes of their waves finish together).
+// The order of a slice has no influence on any result: per-path random numbers, integer accumulation.
+// k_trace runs the sort for its own slice when the slice is traced: no launch of its own per bounce, and a workgroup that waits for its
+// three dependent loads per ray (hit -> triangle -> material) does so while the CU's other workgroups still trace.
 struct SortArgs {
     Field<float4> hit;
     const float4 *tris, *materials;
@@ -643,7 +543,7 @@ D void trace_slice(const PathState &P, const DevScene &S, const LdsScene &L, int
 // SMALL: the whole scene (<= 64 triangles) is tested from LDS without a BVH.
 // (with the pair compaction the kernel would take 72 VGPRs and seven waves a SIMD; held to 64 and eight it spills nothing and was measured
 // 1.3 % (20 passes) / 1.7 % (127) faster on KITCHEN — profiles/r06_experiments.json)
-#if !defined(PPG_TRACE_WAVES) && PPG_TRACE_PAIRS
+#ifndef PPG_TRACE_WAVES
 #define PPG_TRACE_WAVES 8
 #endif
 template <bool SMALL, bool COUNT = false>
@@ -988,7 +888,6 @@ struct NeeLds {
     int *stack_col;            // BVH4 stack column of this lane
 };
 
-// One queue slice through Li's loop body.  FUSED (small scenes): the ray sampled here is traced here too.
 // NEE: the variant with luminaire sampling (GP:1962-2021) and MIS against it (GP:2083-2088); the shadow ray is
 // traced and the direct-light vertex committed in place, as in the reference's loop.
 // FULL: the complete material set (ppg_device.h "Full material set"); otherwise only diffuse / two-sided diffuse / mirror.
@@ -1003,9 +902,9 @@ struct Carried {
     unsigned long long *plds, pt, prt; bool pon;
 #endif
 };
-template <bool FUSED, bool NEE, bool FULL, bool CARRY = false, int MSET = MSET_ALL>
+template <bool NEE, bool FULL, bool CARRY = false, int MSET = MSET_ALL>
 D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const RenderParams &R, const unsigned int i, const LdsColumn &fcol,
-                 const float4 *lds_tris, unsigned long long &plen, unsigned int &traced, const NeeLds &nee, unsigned long long &committed,
+                 unsigned long long &plen, unsigned int &traced, const NeeLds &nee, unsigned long long &committed,
                  Carried *cs = nullptr) {
     bool alive = false;
     {
@@ -1173,7 +1072,7 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
         Mat M;
         if (FULL) {
             M = load_material(S, I.material);
-            if (MSET == MSET_COMMON) {  // what k_sort_slices put into the common part of the slice
+            if (MSET == MSET_COMMON) {  // what sort_slice put into the common part of the slice
                 if (!(M.type == PPG_BSDF_DIFFUSE || M.type == PPG_BSDF_MIRROR || M.type == PPG_BSDF_CONDUCTOR || M.type == PPG_BSDF_ROUGHCONDUCTOR ||
                       M.type == PPG_BSDF_PLASTIC || M.type == PPG_BSDF_ROUGHPLASTIC)) __builtin_unreachable();
                 if (M.flags & PPG_MAT_MASK) __builtin_unreachable();
@@ -1377,15 +1276,8 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
                 thr = mul3(thr, bsdfWeight);  // GP:2039-2040
                 if (FULL) eta *= sampledEta;
                 d = wo;
-                if (FUSED) {
-                    Hit hn = trace_small(lds_tris, S, I.p, wo, PPG_EPSILON, __builtin_inff());
-                    P.hit[i] = make_float4(hn.t, hn.u, hn.v, __int_as_float(hn.prim));
-                    ++traced;
-                } else if (CARRY) {
-                    cs->ro = make_float4(I.p.x, I.p.y, I.p.z, PPG_EPSILON);
-                } else {
-                    P.ray_o[i] = make_float4(I.p.x, I.p.y, I.p.z, PPG_EPSILON);
-                }
+                if (CARRY) cs->ro = make_float4(I.p.x, I.p.y, I.p.z, PPG_EPSILON);
+                else P.ray_o[i] = make_float4(I.p.x, I.p.y, I.p.z, PPG_EPSILON);
                 if (CARRY) cs->rd = make_float4(wo.x, wo.y, wo.z, __builtin_inff());
                 else P.ray_d[i] = make_float4(wo.x, wo.y, wo.z, __builtin_inff());
                 if (smooth && nV < PPG_MAX_VERTICES && nV < (unsigned int)R.max_vertices && !R.is_final_iter) {
@@ -1436,11 +1328,10 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
 }
 
 // One queue slice through Li's loop body.
-template <bool FUSED, bool NEE, bool FULL, int MSET = MSET_ALL>
+template <bool NEE, bool FULL, int MSET = MSET_ALL>
 D void shade_slice(const PathState &P, const DevScene &S, const DevTree &T, const RenderParams &R, const Work &work,
                    unsigned int b, unsigned int nb, unsigned int *out_items, unsigned int *out_count, const LdsColumn &fcol,
-                   const float4 *lds_tris, unsigned long long &plen_sum, unsigned int &traced, const NeeLds &nee,
-                   unsigned long long &committed) {
+                   unsigned long long &plen_sum, unsigned int &traced, const NeeLds &nee, unsigned long long &committed) {
     const unsigned int rounds = (work.count + PPG_BLOCK - 1) / PPG_BLOCK;
     for (unsigned int r = 0; r < rounds; ++r) {
         unsigned int q = r * PPG_BLOCK + threadIdx.x;
@@ -1453,7 +1344,7 @@ D void shade_slice(const PathState &P, const DevScene &S, const DevTree &T, cons
             active = i < P.n_paths;
         }
         if (active) {
-            alive = shade_one<FUSED, NEE, FULL, false, MSET>(P, S, T, R, i, fcol, lds_tris, plen, traced, nee, committed);
+            alive = shade_one<NEE, FULL, false, MSET>(P, S, T, R, i, fcol, plen, traced, nee, committed);
         }
         unsigned int slot = queue_append(out_count, alive);
         if (alive) out_items[slot] = i;
@@ -1461,7 +1352,7 @@ D void shade_slice(const PathState &P, const DevScene &S, const DevTree &T, cons
     }
 }
 
-template <bool FUSED, bool NEE, bool FULL, int MSET = MSET_ALL>
+template <bool NEE, bool FULL, int MSET = MSET_ALL>
 __global__ __launch_bounds__(PPG_BLOCK, (MSET == MSET_COMMON ? PPG_SHADE_WAVES_COMMON : (FULL ? PPG_SHADE_WAVES_FULL : PPG_SHADE_WAVES))) void k_shade(PathState P, DevScene S, DevTree T, RenderParams R, Queues Q, int qin,
                                                                      int small_scene, const unsigned int *sorted_items) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -1470,7 +1361,7 @@ __global__ __launch_bounds__(PPG_BLOCK, (MSET == MSET_COMMON ? PPG_SHADE_WAVES_C
     __shared__ unsigned long long acc;
     const float4 *lds_tris = (const float4 *)lds_raw;
     // dynamic LDS: the triangles (small scenes) or the BVH stack columns of the rays traced in place (shadow rays, look-through)
-    const bool staged = FUSED || ((NEE || (FULL && S.has_null)) && small_scene);
+    const bool staged = (NEE || (FULL && S.has_null)) && small_scene;
     if (staged) {
         for (int k = threadIdx.x; k < 3 * S.n_tris; k += blockDim.x) ((float4 *)lds_raw)[k] = S.accel_small[k];
     }
@@ -1480,18 +1371,17 @@ __global__ __launch_bounds__(PPG_BLOCK, (MSET == MSET_COMMON ? PPG_SHADE_WAVES_C
     const LdsColumn fcol{pdf_factors + threadIdx.x, PPG_BLOCK};
     const unsigned int b = blockIdx.x, nb = gridDim.x;
     if (Q.stop && *Q.stop) return;
-    // QIN_SORTED: the workgroup's share of the dense list re-ordered by the BSDF type at the new hit (k_sort_slices); same paths, other order
+    // QIN_SORTED: the workgroup's share of the dense list re-ordered by the BSDF type at the new hit (sort_slice); same paths, other order
     const Work work = work_of(P, Q, qin, sorted_items, b, nb);
     if (threadIdx.x == 0) out_count = qin == QIN_SORTED_REST ? Q.count[0][b] : 0;  // the second launch over a slice appends to the first one's output
     __syncthreads();
     unsigned long long plen_sum = 0, committed = 0;
     unsigned int traced = 0;
-    shade_slice<FUSED, NEE, FULL, MSET>(P, S, T, R, work, b, nb, Q.items[0] + (size_t)b * Q.cap, &out_count, fcol, lds_tris, plen_sum, traced,
-                                        nee, committed);
+    shade_slice<NEE, FULL, MSET>(P, S, T, R, work, b, nb, Q.items[0] + (size_t)b * Q.cap, &out_count, fcol, plen_sum, traced, nee, committed);
     __syncthreads();
     if (threadIdx.x == 0) Q.count[0][b] = out_count;
     block_add_u64(&acc, &Q.stats[b].path_len, plen_sum);
-    if (FUSED || NEE || FULL) block_add_u64(&acc, &Q.stats[b].rays, traced);
+    if (NEE || FULL) block_add_u64(&acc, &Q.stats[b].rays, traced);
     if (NEE) block_add_u64(&acc, &Q.stats[b].committed, committed);
 }
 
@@ -1638,7 +1528,7 @@ __global__ __launch_bounds__(PPG_BLOCK, (FULL ? PPG_TAIL_WAVES_FULL : PPG_SHADE_
             if (!traced_coop) { cs.hit = make_float4(h.t, h.u, h.v, __int_as_float(h.prim)); if (!pending) ++traced; }
             if (!pending) {
                 unsigned long long plen = 0;
-                const bool alive = shade_one<false, NEE, FULL, true>(P, S, T, R, i, fcol, L.tris, plen, traced, nee, committed, &cs);
+                const bool alive = shade_one<NEE, FULL, true>(P, S, T, R, i, fcol, plen, traced, nee, committed, &cs);
                 plen_sum += plen;
                 if (plen > plen_max) plen_max = plen;
                 if (!alive) have = false;
@@ -1658,19 +1548,6 @@ __global__ __launch_bounds__(PPG_BLOCK, (FULL ? PPG_TAIL_WAVES_FULL : PPG_SHADE_
     block_add_u64(&acc, &stats[blockIdx.x].path_len, plen_sum);
     block_add_u64(&acc, &stats[blockIdx.x].rays, traced);
     if (NEE) block_add_u64(&acc, &stats[blockIdx.x].committed, committed);
-}
-
-// Scenes with many BSDF types (k_shade<FULL>): after the first bounce the rays of a wave hit unrelated surfaces, and a wave executes the
-// union of its lanes' BSDF branches (rough plastic, rough conductor, glass, ...).  Every workgroup therefore counting-sorts its queue
-// slice by the BSDF type at the new hit (16 bins; rays that left the scene last, so that the lanes of their waves finish together).
-// The order of a slice has no influence on any result: per-path random numbers, integer accumulation.
-static __global__ __launch_bounds__(PPG_BLOCK) void k_sort_slices(PathState P, DevScene S, Queues Q, int qin, unsigned int *sorted, unsigned char *keys) {
-    __shared__ unsigned int hist[16], offs[16];
-    const unsigned int b = blockIdx.x, nb = gridDim.x;
-    if (Q.stop && *Q.stop) return;
-    const Work work = work_of(P, Q, qin, nullptr, b, nb);  // QIN_FIRST (every path of the batch) or QIN_DENSE
-    if (work.count == 0) { if (threadIdx.x == 0) { Q.count[1][b] = 0; if (Q.n_common) Q.n_common[b] = 0; } return; }
-    sort_slice(sort_args(P, S, Q, b, sorted, keys), work, b, nb, hist, offs);
 }
 
 // copy every workgroup's queue slice into one dense array (offsets = exclusive scan of the slice counts)

@@ -1,7 +1,8 @@
 /*
- * ppg_launch.h — launchers of the large path kernels.  k_shade and k_tail exist in eight instantiations each (FUSED / SMALL x NEE x FULL)
- * and k_commit in six (spatial x directional filter); each pair of instantiations is its own translation unit (ppg_inst.hip compiled with
- * -DPPG_INST=n), so the library builds in parallel instead of in one 2.5-minute compile.  No device code crosses a translation unit.
+ * ppg_launch.h — launchers of the large path kernels.  k_shade exists in five instantiations (NEE x FULL, and MSET_COMMON), k_tail in eight
+ * (SMALL x NEE x FULL) and k_commit in six (spatial x directional filter); each pair of instantiations is its own translation unit
+ * (ppg_inst.hip compiled with -DPPG_INST=n), so the library builds in parallel instead of in one 2.5-minute compile.  No device code
+ * crosses a translation unit.
  */
 #ifndef PPG_LAUNCH_H
 #define PPG_LAUNCH_H
@@ -51,10 +52,11 @@ struct SplatLaunch {
     unsigned int lds_nodes;     // D-trees of up to this many nodes are staged in LDS (<= PPG_SPLAT_NODES)
 };
 
-// variant = (FUSED ? 4 : 0) | (NEE ? 2 : 0) | (FULL ? 1 : 0)
+// variant = (NEE ? 2 : 0) | (FULL ? 1 : 0)
 void ppg_launch_shade(int variant, const ShadeLaunch &a);
 // variant = (SMALL ? 4 : 0) | (NEE ? 2 : 0) | (FULL ? 1 : 0)
 void ppg_launch_tail(int variant, const TailLaunch &a);
+// (these three are defined in the commit unit itself)
 void ppg_launch_commit(int spatial_filter, int directional_filter, const CommitLaunch &a);
 // a round of the optimiser: k_commit_records (nearest / stochastic spatial filter), then — after the sort — k_splat_sorted
 void ppg_launch_commit_records(int spatial_filter, const CommitLaunch &a);
@@ -63,16 +65,11 @@ void ppg_launch_splat(int directional_filter, const SplatLaunch &a);
 // one function per translation unit (pair = variant >> 1)
 void ppg_launch_shade_pair0(int variant, const ShadeLaunch &a);
 void ppg_launch_shade_pair1(int variant, const ShadeLaunch &a);
-void ppg_launch_shade_pair2(int variant, const ShadeLaunch &a);
-void ppg_launch_shade_pair3(int variant, const ShadeLaunch &a);
 void ppg_launch_tail_pair0(int variant, const TailLaunch &a);
 void ppg_launch_tail_pair1(int variant, const TailLaunch &a);
 void ppg_launch_tail_pair2(int variant, const TailLaunch &a);
 void ppg_launch_tail_pair3(int variant, const TailLaunch &a);
-void ppg_launch_commit_all(int spatial_filter, int directional_filter, const CommitLaunch &a);
-void ppg_launch_commit_records_all(int spatial_filter, const CommitLaunch &a);
-void ppg_launch_splat_all(int directional_filter, const SplatLaunch &a);
-// k_shade<false, false, FULL, MSET_COMMON> over the front part of the sorted slices (a.qin = QIN_SORTED_COMMON)
+// k_shade<false, FULL, MSET_COMMON> over the front part of the sorted slices (a.qin = QIN_SORTED_COMMON)
 void ppg_launch_shade_common(const ShadeLaunch &a);
 
 #endif

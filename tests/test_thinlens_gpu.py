@@ -89,7 +89,7 @@ def _render(desc, **extra):
     return film
 
 
-@pytest.mark.parametrize("env", ["", "PPG_FUSE", "PPG_FORCE_BVH"])
+@pytest.mark.parametrize("env", ["", "PPG_FORCE_BVH"])
 def test_defocused_film_is_the_numpy_lens_coverage(monkeypatch, env):
     """black emitter plane between camera and focal plane: the film of 16 samples is (samples that hit) / 16 in every pixel"""
     if env:
