@@ -275,8 +275,10 @@ int ppg_set_shard(ppg_ctx *ctx, int32_t rank, int32_t world, int32_t tile_size);
  *   - No float atomics; the sums have ONE association, independent of batch size, launch schedule and thread count: per source pixel,
  *     its samples in sample order into a footprint slot per target pixel (tap); per target pixel, its taps in the order dy = -B .. B and,
  *     within each dy, dx = -B .. B, starting from zero; then, in a final iteration ("groups of passes" below), the groups in group order.
- *     A sharded version can exchange footprints and reproduce one GPU's bits; it does not exist yet: a filter other than the default
- *     box together with ppg_set_shard(world > 1) is PPG_ERR_INVALID, whichever of the two calls comes second.
+ *   - Sharded by tiles (ppg_set_shard, world > 1) a rank holds the footprint slots of ITS source pixels only; the ranks exchange the slots
+ *     that cross a tile border between two of them through the footprint hook ("Footprint hook" below), each rank resolves its own
+ *     target pixels in the order above, and the film is one GPU's, bit for bit.  Without a hook on the context a filter other than the
+ *     default box together with world > 1 stays PPG_ERR_INVALID, whichever of ppg_set_rfilter / ppg_set_shard comes second.
  * ---------------------------------------------------------------------------------------------- */
 enum { PPG_RFILTER_BOX = 0, PPG_RFILTER_TENT, PPG_RFILTER_GAUSSIAN, PPG_RFILTER_MITCHELL, PPG_RFILTER_CATMULLROM, PPG_RFILTER_LANCZOS };
 typedef struct ppg_rfilter {
@@ -434,6 +436,42 @@ int ppg_exchange_stream(ppg_ctx *ctx, void **hip_stream);
 int32_t ppg_final_group_passes(int32_t n_passes);
 int ppg_final_partials(ppg_ctx *ctx, void **dev /* float[n_floats] */, uint64_t *n_floats);
 int ppg_final_partials_commit(ppg_ctx *ctx);
+
+/* ------------------------------------------------------------------------------------------------
+ * Footprint hook: a filtered film (ppg_set_rfilter) in a render sharded by tiles.
+ *
+ * The footprint is indexed by SOURCE pixel: slot (tap, c) of source s holds what s adds to target s + (dx, dy), tap = (dy + B) * (2B + 1)
+ * + (dx + B), |dx|, |dy| <= B (the filter's border, at most 3), c = image RGB, squared image RGB, weight.  A BORDER SLOT is a pair (s, tap)
+ * whose target lies inside the film AND on a tile of another rank than s's tile (owner of a tile = tile % world, tiles of tile_size²
+ * pixels in row-major order; with tile_size < B the target may lie several tiles away).  The set depends on (width, height, tile_size,
+ * world, B) only, so every rank numbers the same M slots alike: tap by tap (tap ascending) and, within a tap, by source pixel in row-major
+ * order — the lanes of a wave touch consecutive source pixels of one tap.  The halo buffer is channel-major: float halo[7][M],
+ * halo[c * M + m] = channel c of slot m.  ppg_footprint_halo_floats() = 7 M; 0 for world <= 1 or border < 1 (the default box keeps its
+ * own-pixel film and has no footprint).
+ *
+ * Whenever a footprint is complete the library packs the border slots of ITS sources into the zeroed halo buffer (zeroing them in the
+ * footprint), synchronises its stream and calls the hook, which all-reduces (sum, float) the n_floats at dev_halo in place together with
+ * the ranks' status words — on the stream of ppg_exchange_stream, or on another one it synchronises before it returns — and returns
+ * non-zero if any rank reported a failure.  Every float is non-zero on one rank at most: the sum is exact.  The library then writes the
+ * slots whose TARGET it owns into its footprint and resolves its own target pixels only, taps in the usual order from zero; all other
+ * pixels of image / squared image / weights / film (or of a final group's slot) stay untouched, so the image, film and final-partials
+ * exchanges keep their disjoint supports.  The hook is called
+ *   - once at the end of every ppg_render_passes_nostat() call that is not rendered in final groups (training passes, rounds by region, a
+ *     seconds budget), after the last stragglers were flushed;
+ *   - once per group in a final call (final flag, budgetType = spp) whose groups are rendered by tiles (groups < 2 * world): the groups are
+ *     then rendered one at a time, each one's stragglers flushed before its exchange;
+ *   - never at world = 1, with the default box, or in a final call whose groups are dealt whole to the ranks (a rank renders the whole film
+ *     there and resolves it as one GPU does).
+ * The number of calls in a ppg_render_passes_nostat() call thus depends only on what every rank knows.  A rank that is cancelled or fails
+ * before a due call still makes that ONE next call, with a zeroed buffer (dev_halo may be NULL if it could not be allocated: zeros of the
+ * hook's own) and local_status != 0; the hook then returns non-zero on all ranks, none of them makes a further call in this
+ * ppg_render_passes_nostat(), and all return an error — to meet again in the image / final-partials exchange that follows.
+ * ppg_set_footprint_hook comes BEFORE the filter and the shard meet (ppg_set_rfilter / ppg_set_shard refuse the combination without it);
+ * clearing it (NULL) while a filter other than the default box and world > 1 are both set is PPG_ERR_INVALID.
+ * ---------------------------------------------------------------------------------------------- */
+typedef int (*ppg_footprint_hook)(void *user, void *dev_halo /* float[n_floats], device memory */, uint64_t n_floats, int32_t local_status);
+int ppg_set_footprint_hook(ppg_ctx *ctx, ppg_footprint_hook hook, void *user);
+uint64_t ppg_footprint_halo_floats(int32_t width, int32_t height, int32_t tile_size, int32_t world, int32_t border);
 
 /* ------------------------------------------------------------------------------------------------
  * Learning the BSDF sampling fraction (bsdfSamplingFractionLoss = "kl" | "var"; AdamOptimizer GP:69-133,

@@ -489,8 +489,9 @@ struct KernelTimer {
 // firstPass of the render, consecutive groups of the launch stridePasses apart; group k accumulates into slot slot0 + k * slotStride.
 // addCount > 0 (one GPU): the launch's slots are added to image and film right after its film kernel (k_add_groups).
 // groupsDone: the launch ends every group it renders (false: a part of one group that later launches continue) — a filtered film resolves
-// a group's footprint into its slot then (ppg_set_rfilter).
-struct GroupLaunch { unsigned int firstPass, groupPasses, stridePasses, slot0, slotStride; bool wholeFilm; unsigned int addCount; bool groupsDone = true; };
+// a group's footprint into its slot then (ppg_set_rfilter) — unless `exchange`: the group is rendered by tiles with a filtered film, and the
+// caller resolves it once the ranks have exchanged their footprints' borders (include/ppg.h "Footprint hook").
+struct GroupLaunch { unsigned int firstPass, groupPasses, stridePasses, slot0, slotStride; bool wholeFilm; unsigned int addCount; bool groupsDone = true; bool exchange = false; };
 
 struct ppg_ctx {
     // properties (GP:1014-1085)
@@ -611,6 +612,19 @@ struct ppg_ctx {
     int rfBorder = 0;
     FilmFilter rf{};
     DevBuf<float> d_foot;             // float[(2 rfBorder + 1)^2][7][W * H]: ONE footprint, whatever the batch schedule
+    // A filtered film sharded by tiles (include/ppg.h "Footprint hook"): the table of border slots (ppg_kernels.h k_halo_pack), built when
+    // the shard, the film or the filter changed (haloKey), the halo buffer the hook all-reduces, and the hook calls of the current
+    // ppg_render_passes_nostat call: footDue of them are owed — a number every rank computes alike —, footDone were made.
+    ppg_footprint_hook footHook = nullptr;
+    void *footHookUser = nullptr;
+    DevBuf<unsigned int> d_haloSrc, d_haloPack, d_haloUnpack;
+    DevBuf<unsigned char> d_haloTap;
+    DevBuf<float> d_halo;             // float[7][haloM]
+    unsigned int haloM = 0, haloPackN = 0, haloUnpackN = 0;
+    int haloKey[6] = {0, 0, 0, 0, 0, 0};  // width, height, tile size, world, rank, border the table was built for
+    unsigned int footDue = 0, footDone = 0;
+    bool footFailed = false;          // an exchange carried a failure: every rank saw it there, no further hook calls in this call
+    bool exchangesFootprints() const { return filtered && shardWorld > 1; }
     uint64_t samplesLocal = 0;        // samples this rank rendered in the current performRenderPasses
 
     // path state
@@ -1403,11 +1417,66 @@ int flushStragglers(ppg_ctx *ctx, bool hookRound) {
 // Filtered film (ppg_set_rfilter).  The footprint: zeroed at the start of every ppg_render_passes() call, then source pixels add their
 // samples to it launch by launch (k_film_filter), and a resolve (k_film_resolve) moves it — zeroing it — into the call's image and the
 // iteration's film at the end of the call, or into a final group's slot when the group is complete.
+// Sharded by tiles, the footprint of a rank lacks what foreign source pixels within the filter's border of its tiles put on its targets:
+// the BORDER SLOTS (include/ppg.h "Footprint hook"; forEachBorderSlot below gives their order).  prepareHalo builds their table when the
+// shard, the film or the filter has changed; exchangeFootprint packs this rank's share into the halo buffer, has the hook all-reduce it,
+// unpacks what this rank's targets need and resolves those targets only.
+template <typename F> void forEachBorderSlot(int W, int H, int ts, int world, int B, F &&fn) {
+    const int T = 2 * B + 1, tilesX = (W + ts - 1) / ts;
+    std::vector<int> col((size_t)W), row((size_t)H);  // owner of pixel (x, y) = (row[y] + col[x]) % world
+    for (int x = 0; x < W; ++x) col[(size_t)x] = (x / ts) % world;
+    for (int y = 0; y < H; ++y) row[(size_t)y] = (int)(((long long)(y / ts) * tilesX) % world);
+    for (int dy = -B; dy <= B; ++dy)
+        for (int dx = -B; dx <= B; ++dx) {
+            const unsigned int o = (unsigned int)((dy + B) * T + (dx + B));
+            for (int y = std::max(0, -dy); y < std::min(H, H - dy); ++y)
+                for (int x = std::max(0, -dx); x < std::min(W, W - dx); ++x) {
+                    const int so = (row[(size_t)y] + col[(size_t)x]) % world, to = (row[(size_t)(y + dy)] + col[(size_t)(x + dx)]) % world;
+                    if (so != to) fn(o, (unsigned int)y * (unsigned int)W + (unsigned int)x, so, to);
+                }
+        }
+}
+const char *kShardedFilter = "sharded filtered renders are not supported yet without a footprint hook: a reconstruction filter other than the default box "
+                             "needs world = 1, or ppg_set_footprint_hook before the filter and the shard meet";
+int prepareHalo(ppg_ctx *ctx) {
+    const int key[6] = {ctx->W, ctx->H, ctx->tileSize, ctx->shardWorld, ctx->shardRank, ctx->rfBorder};
+    if (memcmp(key, ctx->haloKey, sizeof key) != 0) {
+        std::vector<unsigned int> src, pack, unpack;
+        std::vector<unsigned char> tap;
+        const int rank = ctx->shardRank;
+        bool tooMany = false;
+        forEachBorderSlot(ctx->W, ctx->H, ctx->tileSize, ctx->shardWorld, ctx->rfBorder, [&](unsigned int o, unsigned int s, int so, int to) {
+            if (src.size() >= 0xffffffffu / 7u) { tooMany = true; return; }
+            const unsigned int m = (unsigned int)src.size();
+            src.push_back(s); tap.push_back((unsigned char)o);
+            if (so == rank) pack.push_back(m);
+            if (to == rank) unpack.push_back(m);
+        });
+        if (tooMany) { ctx->error = "sharded filtered film: too many border slots"; return PPG_ERR_NOMEM; }
+        memset(ctx->haloKey, 0, sizeof ctx->haloKey);
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (an earlier call's kernels may still read the old table)
+        HIP_CHECK(ctx->d_haloSrc.reserve(std::max<size_t>(1, src.size())));
+        HIP_CHECK(ctx->d_haloTap.reserve(std::max<size_t>(1, tap.size())));
+        HIP_CHECK(ctx->d_haloPack.reserve(std::max<size_t>(1, pack.size())));
+        HIP_CHECK(ctx->d_haloUnpack.reserve(std::max<size_t>(1, unpack.size())));
+        HIP_CHECK(ctx->d_halo.reserve(std::max<size_t>(1, 7 * src.size())));
+        if (!src.empty()) {
+            HIP_CHECK(hipMemcpy(ctx->d_haloSrc.p, src.data(), src.size() * 4, hipMemcpyHostToDevice));
+            HIP_CHECK(hipMemcpy(ctx->d_haloTap.p, tap.data(), tap.size(), hipMemcpyHostToDevice));
+        }
+        if (!pack.empty()) HIP_CHECK(hipMemcpy(ctx->d_haloPack.p, pack.data(), pack.size() * 4, hipMemcpyHostToDevice));
+        if (!unpack.empty()) HIP_CHECK(hipMemcpy(ctx->d_haloUnpack.p, unpack.data(), unpack.size() * 4, hipMemcpyHostToDevice));
+        ctx->haloM = (unsigned int)src.size(); ctx->haloPackN = (unsigned int)pack.size(); ctx->haloUnpackN = (unsigned int)unpack.size();
+        memcpy(ctx->haloKey, key, sizeof key);
+    }
+    return PPG_OK;
+}
 int prepareFootprint(ppg_ctx *ctx) {
     const size_t T = 2 * (size_t)ctx->rfBorder + 1, floats = T * T * 7 * (size_t)ctx->W * (size_t)ctx->H;
     HIP_CHECK(ctx->d_foot.reserve(floats));
     HIP_CHECK(hipMemsetAsync(ctx->d_foot.p, 0, floats * 4, ctx->stream));
     ctx->rf.W = ctx->W; ctx->rf.H = ctx->H;
+    if (ctx->exchangesFootprints()) return prepareHalo(ctx);
     return PPG_OK;
 }
 void launchFilmFilter(ppg_ctx *ctx, const PathState &P, unsigned long long seed, unsigned int base, unsigned int gs, unsigned int gstride, int j0, int j1) {
@@ -1432,6 +1501,55 @@ void launchFilmResolve(ppg_ctx *ctx, float *im, float *sq, float *w, float *film
         default: hipLaunchKernelGGL(k_film_resolve<3>, g, b, 0, ctx->stream, ctx->rf, ctx->d_foot.p, im, sq, w, film, film_w); break;
         }
     });
+}
+void launchFilmResolveOwned(ppg_ctx *ctx, float *im, float *sq, float *w, float *film, float *film_w) {
+    const unsigned int n = ctx->nPix;
+    if (!n) return;
+    timedLaunch(ctx, "k_film_resolve_owned", n, [&] {
+        const dim3 g((n + 255) / 256), b(256);
+        switch (ctx->rfBorder) {
+        case 0: hipLaunchKernelGGL(k_film_resolve_owned<0>, g, b, 0, ctx->stream, ctx->rf, ctx->d_pixels.p, n, ctx->d_foot.p, im, sq, w, film, film_w); break;
+        case 1: hipLaunchKernelGGL(k_film_resolve_owned<1>, g, b, 0, ctx->stream, ctx->rf, ctx->d_pixels.p, n, ctx->d_foot.p, im, sq, w, film, film_w); break;
+        case 2: hipLaunchKernelGGL(k_film_resolve_owned<2>, g, b, 0, ctx->stream, ctx->rf, ctx->d_pixels.p, n, ctx->d_foot.p, im, sq, w, film, film_w); break;
+        default: hipLaunchKernelGGL(k_film_resolve_owned<3>, g, b, 0, ctx->stream, ctx->rf, ctx->d_pixels.p, n, ctx->d_foot.p, im, sq, w, film, film_w); break;
+        }
+    });
+}
+// One due call of the footprint hook.  localStatus != 0 (this rank was cancelled or failed): a zeroed buffer and the status, so that the
+// peers, who are in this exchange, learn of it there.  Any failure — this rank's, or a peer's through the hook's return value — ends the
+// call's exchanges on every rank alike (footFailed).
+int callFootprintHook(ppg_ctx *ctx, int localStatus) {
+    const uint64_t floats = 7ull * ctx->haloM;
+    int sync = (int)hipStreamSynchronize(ctx->stream);  // the hook may read the buffer from the host, or work on a stream of its own
+    if (sync != 0 && !localStatus) { (void)hipGetLastError(); localStatus = 1; }
+    ++ctx->footDone;
+    const int hrc = ctx->footHook(ctx->footHookUser, ctx->d_halo.p, floats, localStatus);
+    if (hrc != 0 || localStatus) {
+        ctx->footFailed = true;
+        if (!localStatus || ctx->error.empty()) ctx->error = "footprint hook failed";
+        return PPG_ERR_INVALID;
+    }
+    return PPG_OK;
+}
+// The footprint is complete on this rank's tiles: pack, hook, unpack, and resolve this rank's targets into im / sq / w (and film / film_w).
+int exchangeFootprint(ppg_ctx *ctx, float *im, float *sq, float *w, float *film, float *film_w) {
+    const size_t n = (size_t)ctx->W * (size_t)ctx->H;
+    const unsigned int M = ctx->haloM;
+    hipStream_t s = ctx->stream;
+    HIP_CHECK(hipMemsetAsync(ctx->d_halo.p, 0, std::max<size_t>(1, 7 * (size_t)M) * 4, s));
+    if (ctx->seesCancel()) { (void)callFootprintHook(ctx, 1); return PPG_ERR_CANCELLED; }
+    if (ctx->haloPackN) timedLaunch(ctx, "k_halo_pack", ctx->haloPackN, [&] {
+        hipLaunchKernelGGL(k_halo_pack, dim3((ctx->haloPackN + 255) / 256), dim3(256), 0, s, ctx->d_haloPack.p, ctx->haloPackN, ctx->d_haloSrc.p, ctx->d_haloTap.p, M, n,
+                           ctx->d_foot.p, ctx->d_halo.p);
+    });
+    { int rc = callFootprintHook(ctx, 0); if (rc) return rc; }
+    if (ctx->haloUnpackN) timedLaunch(ctx, "k_halo_unpack", ctx->haloUnpackN, [&] {
+        hipLaunchKernelGGL(k_halo_unpack, dim3((ctx->haloUnpackN + 255) / 256), dim3(256), 0, s, ctx->d_haloUnpack.p, ctx->haloUnpackN, ctx->d_haloSrc.p, ctx->d_haloTap.p, M, n,
+                           ctx->d_foot.p, ctx->d_halo.p);
+    });
+    launchFilmResolveOwned(ctx, im, sq, w, film, film_w);
+    HIP_CHECK(hipGetLastError());
+    return PPG_OK;
 }
 
 // `batch` BlockedRenderProcesses (GP:1087-1106 / renderBlock GP:1587-1641) over all owned pixels in one set of launches.
@@ -1788,8 +1906,8 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
                     const size_t n = ctx->nPixAll;
                     for (int j0 = 0, k = 0; j0 < sppBatch; j0 += (int)gs, ++k) {
                         launchFilmFilter(ctx, Pf, seed, base, gs, gstride, j0, std::min(sppBatch, j0 + (int)gs));
-                        if (!glv.groupsDone) continue;
-                        float *slot = ctx->d_partials.p + (size_t)(glv.slot0 + (unsigned int)k * glv.slotStride) * 7u * n;
+                        if (!glv.groupsDone || glv.exchange) continue;
+                        float *slot = ctx->d_partials.p + (ctx->shardWorld > 1 ? 4 * n : 0) + (size_t)(glv.slot0 + (unsigned int)k * glv.slotStride) * 7u * n;
                         launchFilmResolve(ctx, slot, slot + 3 * n, slot + 6 * n, nullptr, nullptr);
                     }
                 }
@@ -1851,7 +1969,16 @@ int renderFinalGroups(ppg_ctx *ctx, int numPasses) {
             if (G < launchPasses) launchPasses = std::max(G, launchPasses / G * G);  // whole groups per launch
         }
     }
-    const unsigned int perLaunch = std::max(1u, launchPasses / G);  // whole groups per launch (G <= launchPasses), else parts of one group
+    // A filtered film rendered by tiles (include/ppg.h "Footprint hook"): one group at a time — its stragglers flushed, so that its footprint
+    // is complete, then the borders exchanged and this rank's targets resolved into the group's slot.
+    const bool exch = ctx->exchangesFootprints() && !byRank;
+    auto exchangeGroup = [&](unsigned int g) -> int {
+        int rc = flushStragglers(ctx, false);
+        if (rc) return rc;
+        float *slot = ctx->d_partials.p + 4 * n + (size_t)g * 7u * n;
+        return exchangeFootprint(ctx, slot, slot + 3 * n, slot + 6 * n, nullptr, nullptr);
+    };
+    const unsigned int perLaunch = exch ? 1u : std::max(1u, launchPasses / G);  // whole groups per launch (G <= launchPasses), else parts of one group
     const unsigned int slots = world > 1 ? nGroups : std::max(perLaunch, std::max(1u, (unsigned int)ctx->maxBatchFinal / G));
     const size_t floats = (world > 1 ? 4 * n : 0) + (size_t)slots * 7 * n;
     if (ctx->d_partials.cap < floats || ctx->partialSlots != slots) {
@@ -1871,9 +1998,11 @@ int renderFinalGroups(ppg_ctx *ctx, int numPasses) {
             for (size_t q = 0; q < cnt; ++q) batch += passesOf(mine[m + q]);
             // (one GPU: the launch's slots are added to image and film right behind its film kernel)
             GroupLaunch gl{firstPassAbs + mine[m] * G, G, step * G, world > 1 ? mine[m] : 0u, world > 1 ? step : 1u, byRank, world == 1 ? (unsigned int)cnt : 0u};
+            gl.exchange = exch;
             int rc = renderBatch(ctx, (int)batch, false, &gl, m + cnt >= mine.size());
             if (rc) return rc;
             ctx->samplesLocal += pixelsMine * batch * ctx->sppPerPass;
+            if (exch && (rc = exchangeGroup(mine[m]))) return rc;
             m += cnt;
         } else {  // a group larger than a launch: its parts accumulate into the same slot one after the other
             const unsigned int g = mine[m], total = passesOf(g);
@@ -1882,11 +2011,13 @@ int renderFinalGroups(ppg_ctx *ctx, int numPasses) {
                 const unsigned int batch = std::min(launchPasses, total - done);
                 const bool lastPart = done + batch >= total;
                 GroupLaunch gl{firstPassAbs + g * G + done, batch, batch, world > 1 ? g : 0u, 1u, byRank, (world == 1 && lastPart) ? 1u : 0u, lastPart};
+                gl.exchange = exch;
                 int rc = renderBatch(ctx, (int)batch, false, &gl, lastPart && m + 1 >= mine.size());
                 if (rc) return rc;
                 ctx->samplesLocal += pixelsMine * batch * ctx->sppPerPass;
                 done += batch;
             }
+            if (exch && !stop) { int rc = exchangeGroup(g); if (rc) return rc; }
             ++m;
         }
         HIP_CHECK(hipStreamSynchronize(ctx->stream));  // bound the launch queue; lets ppg_cancel() take effect
@@ -1924,7 +2055,7 @@ int buildRegionLists(ppg_ctx *ctx, int regions) {
     return PPG_OK;
 }
 
-int renderPassesNoStat(ppg_ctx *ctx, int numPasses) {  // GP:1217-1286
+int renderPassesBody(ppg_ctx *ctx, int numPasses) {  // GP:1217-1286
     size_t n = (size_t)ctx->W * ctx->H;
     HIP_CHECK(hipMemsetAsync(ctx->d_image.p, 0, 3 * n * 4, ctx->stream));
     HIP_CHECK(hipMemsetAsync(ctx->d_sq.p, 0, 3 * n * 4, ctx->stream));
@@ -1994,8 +2125,39 @@ int renderPassesNoStat(ppg_ctx *ctx, int numPasses) {  // GP:1217-1286
         if (rc) return rc;
     }
     // a filtered film: the call's footprint becomes its image / squared image / weights and is added to the iteration's film
-    if (ctx->filtered) launchFilmResolve(ctx, ctx->d_image.p, ctx->d_sq.p, ctx->d_imageW.p, ctx->d_film.p, ctx->d_filmW.p);
+    // (sharded by tiles: once the ranks have exchanged their footprints' borders, this rank's targets only — a cancelled rank says so there)
+    if (ctx->exchangesFootprints()) { int rc = exchangeFootprint(ctx, ctx->d_image.p, ctx->d_sq.p, ctx->d_imageW.p, ctx->d_film.p, ctx->d_filmW.p); if (rc) return rc; }
+    else if (ctx->filtered) launchFilmResolve(ctx, ctx->d_image.p, ctx->d_sq.p, ctx->d_imageW.p, ctx->d_film.p, ctx->d_filmW.p);
     return ctx->seesCancel() ? PPG_ERR_CANCELLED : PPG_OK;
+}
+
+// The footprint hook's calls of a call (include/ppg.h "Footprint hook") are counted by what every rank knows — final flag, budget type, pass
+// count, world —, and no way out of the call may skip one the peers are making: a rank that left early (cancelled, a failed launch, a failed
+// round hook) still makes its NEXT due call, with zeros and its status, where all ranks then learn of it and make no further ones.
+int renderPassesNoStat(ppg_ctx *ctx, int numPasses) {
+    ctx->footDue = 0; ctx->footDone = 0; ctx->footFailed = false;
+    if (ctx->exchangesFootprints()) {
+        if (!ctx->footHook) { ctx->error = kShardedFilter; return PPG_ERR_STATE; }
+        if (ctx->isFinalIter && ctx->budgetType == 0 && numPasses > 0) {
+            const unsigned int G = (unsigned int)ppg_final_group_passes(numPasses), nGroups = ((unsigned int)numPasses + G - 1) / G;
+            ctx->footDue = finalGroupsByRank(nGroups, (unsigned int)ctx->shardWorld) ? 0u : nGroups;
+        } else ctx->footDue = 1;
+    }
+    int rc = renderPassesBody(ctx, numPasses);
+    if (ctx->footDone < ctx->footDue && !ctx->footFailed) {
+        const std::string why = ctx->error;
+        const uint64_t floats = ppg_footprint_halo_floats(ctx->W, ctx->H, ctx->tileSize, ctx->shardWorld, ctx->rfBorder);
+        void *buf = nullptr;  // (a rank that could not even allocate the buffer joins without one: the hook gives zeros of its own)
+        if (ctx->d_halo.reserve(std::max<size_t>(1, (size_t)floats)) == hipSuccess && hipMemsetAsync(ctx->d_halo.p, 0, std::max<size_t>(1, (size_t)floats) * 4, ctx->stream) == hipSuccess &&
+            hipStreamSynchronize(ctx->stream) == hipSuccess) buf = ctx->d_halo.p;
+        else (void)hipGetLastError();
+        ++ctx->footDone;
+        (void)ctx->footHook(ctx->footHookUser, buf, floats, 1);
+        ctx->footFailed = true;
+        ctx->error = why.empty() ? "footprint hook failed" : why;
+        if (rc == PPG_OK) rc = PPG_ERR_INVALID;
+    }
+    return rc;
 }
 
 int finishPasses(ppg_ctx *ctx, ppg_pass_stats *st) {  // GP:1288-1328
@@ -2828,13 +2990,11 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
     return PPG_OK;
 }
 
-static const char *kShardedFilter = "sharded filtered renders are not supported yet: a reconstruction filter other than the default box needs world = 1";
-
 int ppg_set_shard(ppg_ctx *ctx, int32_t rank, int32_t world, int32_t tile_size) {
     (void)hipSetDevice(ctx->device);
     ctx->quiesce();
     if (world < 1 || rank < 0 || rank >= world || tile_size < 1) { ctx->error = "bad shard"; return PPG_ERR_INVALID; }
-    if (world > 1 && ctx->filtered) { ctx->error = kShardedFilter; return PPG_ERR_INVALID; }
+    if (world > 1 && ctx->filtered && !ctx->footHook) { ctx->error = kShardedFilter; return PPG_ERR_INVALID; }
     ctx->shardRank = rank; ctx->shardWorld = world; ctx->tileSize = tile_size;
     ctx->pathsReady = false;
     if (ctx->haveScene) {
@@ -2954,7 +3114,7 @@ int ppg_set_rfilter(ppg_ctx *ctx, const ppg_rfilter *f) {
     std::string err;
     if (int rc = rfilterTable(f, table, &r, &border, err)) { ctx->error = err; return rc; }
     const bool filtered = !(f->type == PPG_RFILTER_BOX && f->radius == 0.5f);
-    if (filtered && ctx->shardWorld > 1) { ctx->error = kShardedFilter; return PPG_ERR_INVALID; }
+    if (filtered && ctx->shardWorld > 1 && !ctx->footHook) { ctx->error = kShardedFilter; return PPG_ERR_INVALID; }
     ctx->filtered = filtered;
     ctx->rfBorder = border;
     memcpy(ctx->rf.table, table, sizeof table);
@@ -3135,6 +3295,20 @@ int ppg_final_partials_commit(ppg_ctx *ctx) {
     return PPG_OK;
 }
 int ppg_set_pass_hook(ppg_ctx *ctx, ppg_pass_hook hook, void *user) { ctx->passHook = hook; ctx->passHookUser = user; return PPG_OK; }
+int ppg_set_footprint_hook(ppg_ctx *ctx, ppg_footprint_hook hook, void *user) {
+    if (!hook && ctx->exchangesFootprints()) {
+        ctx->error = "ppg_set_footprint_hook: a sharded filtered render is set up on this context — it cannot do without the hook";
+        return PPG_ERR_INVALID;
+    }
+    ctx->footHook = hook; ctx->footHookUser = user;
+    return PPG_OK;
+}
+uint64_t ppg_footprint_halo_floats(int32_t width, int32_t height, int32_t tile_size, int32_t world, int32_t border) {
+    if (width < 1 || height < 1 || tile_size < 1 || world <= 1 || border < 1) return 0;
+    uint64_t m = 0;
+    forEachBorderSlot(width, height, tile_size, world, border, [&](unsigned int, unsigned int, int, int) { ++m; });
+    return 7 * m;
+}
 int ppg_adam_records(ppg_ctx *ctx, void **dev_records, uint64_t *n) {
     NEED_TREE
     if (!ctx->inHook) { ctx->error = "ppg_adam_records: only valid inside the round hook"; return PPG_ERR_STATE; }

@@ -2334,6 +2334,77 @@ __global__ __launch_bounds__(256) void k_film_resolve(FilmFilter ff, float *foot
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// A filtered film sharded by tiles (include/ppg.h "Footprint hook").  A BORDER SLOT is a (source pixel s, tap o) whose target s + (dx, dy)
+// lies inside the film on a tile of ANOTHER rank than s's; the M border slots are numbered tap by tap (o ascending) and, within a tap, by
+// source pixel (row-major) — the same numbering on every rank.  slot_src[m] = s, slot_tap[m] = o.  The halo buffer is channel-major,
+// halo[c * M + m], c = 0 .. 6: the lanes of a wave take consecutive slots — neighbouring source pixels of one tap — and so read and write
+// consecutive floats of the footprint (source-major) and of the halo alike.
+//   k_halo_pack    list = the slots whose SOURCE this rank owns: footprint → halo, and the footprint slot is zeroed.  The rest of the halo
+//                  was zeroed beforehand, so every float of it is non-zero on one rank at most and the all-reduce (sum) is exact.
+//   k_halo_unpack  list = the slots whose TARGET this rank owns: halo (after the exchange) → footprint, at the foreign source's position,
+//                  which no kernel of this rank wrote.
+// ------------------------------------------------------------------------------------------------
+static __global__ __launch_bounds__(256) void k_halo_pack(const unsigned int *list, unsigned int count, const unsigned int *slot_src, const unsigned char *slot_tap,
+                                                   unsigned int M, size_t n, float *foot, float *halo) {
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const unsigned int m = list[i];
+    float *f = foot + (size_t)slot_tap[m] * 7 * n + slot_src[m];
+#pragma unroll
+    for (int c = 0; c < 7; ++c) {
+        halo[(size_t)c * M + m] = f[(size_t)c * n];
+        f[(size_t)c * n] = 0.0f;
+    }
+}
+static __global__ __launch_bounds__(256) void k_halo_unpack(const unsigned int *list, unsigned int count, const unsigned int *slot_src, const unsigned char *slot_tap,
+                                                     unsigned int M, size_t n, float *foot, const float *halo) {
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const unsigned int m = list[i];
+    float *f = foot + (size_t)slot_tap[m] * 7 * n + slot_src[m];
+#pragma unroll
+    for (int c = 0; c < 7; ++c) f[(size_t)c * n] = halo[(size_t)c * M + m];
+}
+// k_film_resolve for the targets this rank owns only (pixels = its owned-pixel list, row-major inside its tiles): the same taps in the same
+// order from zero, so a pixel's sums are the unsharded resolve's bit for bit once the foreign slots have been unpacked; every other pixel of
+// im / sq / w / film / film_w stays untouched (the image and film exchanges keep their disjoint supports).  The slots read are zeroed; those
+// of own sources towards foreign targets were zeroed by k_halo_pack, and nothing else was ever written: the whole footprint is zero again.
+template <int B>
+__global__ __launch_bounds__(256) void k_film_resolve_owned(FilmFilter ff, const unsigned int *pixels, unsigned int n_own, float *foot, float *im, float *sq, float *w,
+                                                            float *film, float *film_w) {
+    constexpr int T = 2 * B + 1;
+    const int W = ff.W, H = ff.H;
+    const size_t n = (size_t)W * (size_t)H;
+    const unsigned int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_own) return;
+    const unsigned int t = pixels[k];
+    const int tx = (int)(t % (unsigned int)W), ty = (int)(t / (unsigned int)W);
+    float s[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (int dy = -B; dy <= B; ++dy) {
+        const int sy = ty - dy;
+        if (sy < 0 || sy >= H) continue;
+#pragma unroll
+        for (int dx = -B; dx <= B; ++dx) {
+            const int sx = tx - dx;
+            if (sx < 0 || sx >= W) continue;
+            const size_t o = (size_t)((dy + B) * T + (dx + B)), src = (size_t)sy * W + sx;
+#pragma unroll
+            for (int c = 0; c < 7; ++c) {
+                float *f = foot + (o * 7 + c) * n + src;
+                s[c] += *f;
+                *f = 0.0f;
+            }
+        }
+    }
+    for (int c = 0; c < 3; ++c) { im[3 * (size_t)t + c] += s[c]; sq[3 * (size_t)t + c] += s[3 + c]; }
+    w[t] += s[6];
+    if (film) {
+        for (int c = 0; c < 3; ++c) film[3 * (size_t)t + c] += s[c];
+        film_w[t] += s[6];
+    }
+}
+
 // per-pixel variance estimate of performRenderPasses (GP:1300-1311); the clamped luminance goes to `lum`, stored x-major
 // (index x * H + y) — the order the reference's serial loop sums it in, so the host adds a contiguous array
 static __global__ void k_variance(int n, int W, int N, const float *image, const float *sq_image, const float *image_w, float *var_rgb, float *lum) {

@@ -99,6 +99,9 @@ public:
     virtual void reduceFilm(ppg_ctx *ctx, int width, int height) = 0;     // before the film is read (not with inverse-variance combination)
     // a final iteration's groups of passes (include/ppg.h "Final iteration: groups of passes"): all-reduce the n floats at dev, then ppg_final_partials_commit
     virtual void reduceFinalPartials(ppg_ctx *ctx, void *dev, uint64_t nFloats) = 0;
+    // footprint hook of a filtered film (include/ppg.h "Footprint hook"): all-reduce the n floats at dev in place, with the status words; throws
+    // on every rank when any of them reported a failure.  dev == nullptr: this rank has nothing to give and joins with zeros.
+    virtual void reduceFootprint(void *dev, uint64_t nFloats) = 0;
     virtual double broadcast(double value) = 0;                            // rank 0's value on every rank (the clock readings of a time budget)
     // the stop decision of a time budget (include/ppg.h ppg_set_stop_hook): rank 0's `localStop`, or "stop" if any rank's status word is set —
     // a cancelled rank meets the others HERE, and they all leave the batch loop for the image exchange, where the status aborts the render
@@ -154,9 +157,9 @@ public:
         // ppg_begin_render consumes it; m_cancelled, which the hooks read, is reset when the render is over)
         struct Reset { std::atomic<bool> &f; ~Reset() { f.store(false); } } reset{m_cancelled};
         m_filmComplete = false;
-        // (refused before the first exchange: every rank holds the same scene and fails here alike)
-        if (reducer && reducer->world() > 1 && scene.hasRFilter) throw std::runtime_error("sharded filtered renders are not supported yet: the scene's film has a reconstruction filter other than the default box");
         if (reducer) reducer->beginRender();
+        // (the footprint hook of a filtered film comes before the filter and the shard meet: the library refuses the combination without it)
+        if (reducer) check(ppg_set_footprint_hook(m_ctx, &GuidedPathTracerHIP::footprintHook, this), "ppg_set_footprint_hook");
         const bool spp = std::string(m_cfg.budgetType) == "spp";
         ppg_scene sv = scene.view();
         check(ppg_set_scene(m_ctx, &sv), "ppg_set_scene");
@@ -345,6 +348,12 @@ private:
         // (PPG_STOP_CANCELLED: the library's render was cancelled — also by a ppg_cancel() that did not come through cancel())
         if (g->m_cancelled.load() || localStop == PPG_STOP_CANCELLED) g->m_reducer->setLocalStatus(1);
         try { return g->m_reducer->stopDecision(localStop); } catch (...) { if (!g->m_hookError) g->m_hookError = std::current_exception(); return 1; }
+    }
+    static int footprintHook(void *self, void *dev, uint64_t nFloats, int32_t localStatus) {  // C callback: no exception may cross the C-ABI
+        GuidedPathTracerHIP *g = static_cast<GuidedPathTracerHIP *>(self);
+        if (!g->m_reducer) return 1;
+        if (localStatus != 0 || g->m_cancelled.load()) g->m_reducer->setLocalStatus(1);
+        try { g->m_reducer->reduceFootprint(dev, nFloats); return 0; } catch (...) { if (!g->m_hookError) g->m_hookError = std::current_exception(); return 1; }
     }
     static int roundHook(void *self) {  // C callback: no exception may cross the C-ABI
         GuidedPathTracerHIP *g = static_cast<GuidedPathTracerHIP *>(self);

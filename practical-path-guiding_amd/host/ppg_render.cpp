@@ -336,8 +336,6 @@ int main(int argc, char **argv) {
         std::unique_ptr<RcclReducer> reducer;
         if (!ncclIdFile.empty()) {
             if (world < 1 || rank < 0 || rank >= world) { std::cerr << "--rank / --world out of range\n"; return 2; }
-            // (before the communicator exists: every rank reads the same scene and stops here alike)
-            if (world > 1 && scene.hasRFilter) { std::cerr << "sharded filtered renders are not supported yet: the scene's film has a reconstruction filter other than the default box\n"; return 2; }
             if (!props.values.count("device")) props.values["device"] = std::to_string(rank);  // one GPU per rank of the node
             const auto t0 = std::chrono::steady_clock::now();
             // the run tag keeps a rank from accepting the id file a crashed earlier run left at the same path: any string all ranks of THIS run share

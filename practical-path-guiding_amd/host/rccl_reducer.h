@@ -11,6 +11,8 @@
  *                                                 phase 0 — every record goes to the owner of its D-tree (grouped ncclSend / ncclRecv = all-to-all-v, a rank
  *                                                 receives 1 / world of the records), which sorts and applies them in key order; phase 1 — the owners'
  *                                                 optimiser state (24 B per S-tree node) is all-gathered in place.  Same key order at the owner ⇒ same bits
+ *   per complete footprint of a filtered film     the footprint's border slots (include/ppg.h "Footprint hook"): at the end of a call of training passes and
+ *                                                 per group of a final iteration rendered by tiles; each float non-zero on one rank, in place
  *   at the end                                    the film (not with inverse-variance combination: the retained iteration images were reduced)
  *
  * Each exchange is ONE collective: the arrays of an exchange are packed into a staging buffer on the device (they are separate allocations of
@@ -116,6 +118,18 @@ public:
             allReduce(p, 1, ncclFloat, true);
         }
         check(ctx, ppg_final_partials_commit(ctx), "ppg_final_partials_commit");
+    }
+    void reduceFootprint(void *dev, uint64_t nFloats) override {
+        // the border slots of a filtered film's footprint (include/ppg.h "Footprint hook"): every float is non-zero on one rank at most, the
+        // sums are exact.  As reduceFinalPartials: ONE piece reduced in place, the status word in a small collective behind it; a rank without
+        // a buffer joins with zeros from the staging block.  (The library synchronised its stream before the hook; allReduce synchronises ours.)
+        if (dev) {
+            if (nFloats) { nccl(ncclAllReduce(dev, dev, (size_t)nFloats, ncclFloat, ncclSum, m_comm, m_stream), "ncclAllReduce(footprint)"); ++m_collectives; m_bytes += (size_t)nFloats * 4; }
+            allReduce(nullptr, 0, ncclFloat);
+        } else {
+            Piece p[1] = {{nullptr, (size_t)nFloats * 4}};
+            if (nFloats) allReduce(p, 1, ncclFloat, true); else allReduce(nullptr, 0, ncclFloat);
+        }
     }
     // a rank that was cancelled or failed announces it in the next exchange (status word, see the header comment)
     void setLocalStatus(int status) override { m_status = status; }

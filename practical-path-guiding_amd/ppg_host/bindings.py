@@ -192,6 +192,14 @@ def rfilter_table(desc):
     return table, float(r.value), int(b.value)
 
 
+def footprint_halo_floats(width, height, tile_size, world, border, lib=None):
+    """ppg_footprint_halo_floats (host only): floats of the halo buffer a sharded filtered film exchanges — 7 per border slot, 0 for
+    world <= 1 or border < 1 (include/ppg.h "Footprint hook")."""
+    f = (lib or C.CDLL(hip_library_path())).ppg_footprint_halo_floats
+    f.restype, f.argtypes = C.c_uint64, [C.c_int32] * 5
+    return int(f(int(width), int(height), int(tile_size), int(world), int(border)))
+
+
 class Lens(C.Structure):
     """ppg_lens — a thin-lens camera (mitsuba/src/sensors/thinlens.cpp).  As a dict (SceneDesc.lens): {"aperture_radius", "focus_distance"}
     in world units; None = pinhole."""
@@ -604,6 +612,29 @@ class Engine:
                 return 1
         self._hook_keep = HOOK(tramp) if fn is not None else HOOK(0)
         self._call("set_pass_hook", self._hook_keep, None)
+
+    def set_footprint_hook(self, fn):
+        """fn(dev_halo, n_floats, local_status): called whenever a sharded filtered film's footprint is complete (include/ppg.h "Footprint
+        hook"); all-reduces the floats in place with the ranks' status words and raises if any rank failed.  dev_halo is None when the rank
+        has no buffer to give (local_status != 0).  Install it BEFORE the filter and the shard meet; None clears it."""
+        HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32)
+
+        def tramp(_user, ptr, n, status):
+            try:
+                fn(ptr, int(n), int(status))
+                return 0
+            except Exception as ex:  # surfaced as PPG_ERR_INVALID by the library
+                if type(ex).__name__ != "RenderAborted":  # (an abort the peers announced is the protocol at work, not a fault to report)
+                    import traceback
+                    traceback.print_exc()
+                return 1
+        keep = HOOK(tramp) if fn is not None else HOOK(0)
+        self._call("set_footprint_hook", keep, None)
+        self._foot_keep = keep  # (replaced only once the library has taken the new one: a refused clear leaves the old trampoline in use)
+
+    def footprint_halo_floats(self, tile_size, world, border, width=None, height=None):
+        """ppg_footprint_halo_floats for this engine's film (or width x height): 7 floats per border slot."""
+        return footprint_halo_floats(self.width if width is None else width, self.height if height is None else height, tile_size, world, border, self.lib)
 
     def set_stop_hook(self, fn):
         """fn(local_stop) -> stop: asked after every batch of passes of a budgetType = seconds render (include/ppg.h ppg_set_stop_hook)."""

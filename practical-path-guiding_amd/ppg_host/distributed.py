@@ -21,14 +21,16 @@ import ctypes as C
 import numpy as np
 
 
-SHARDED_FILTER_MSG = "sharded filtered renders are not supported yet: the scene's reconstruction filter %r needs a one-GPU render"
+SHARDED_FILTER_MSG = ("sharded filtered renders are not supported yet by this reducer: the scene's reconstruction filter %r needs a one-GPU render, "
+                      "or a reducer that exchanges footprints (TorchReducer.install -> ppg_set_footprint_hook)")
 
 
-def check_shardable(desc):
+def check_shardable(desc, reducer=None):
     """Raise before any collective is set up if a sharded render cannot take this scene: a film filter other than the default box
-    (include/ppg.h ppg_set_rfilter).  Every rank holds the same scene description, so every rank fails here alike."""
+    (include/ppg.h ppg_set_rfilter) needs a reducer that exchanges footprints (`exchanges_footprints`: the HIP engine's reducers; not
+    HostReducer — the oracle has no film filter).  Every rank holds the same scene description, so every rank fails here alike."""
     rf = getattr(desc, "rfilter", None)
-    if rf is not None:
+    if rf is not None and not getattr(reducer, "exchanges_footprints", False):
         raise ValueError(SHARDED_FILTER_MSG % (rf,))
 
 
@@ -197,6 +199,22 @@ class TorchReducer(_Status):
         self._exchange([buf])
         e.final_partials_commit()
 
+    exchanges_footprints = True
+
+    def reduce_footprint(self, ptr, n, status):
+        """Footprint hook of a sharded filtered film (include/ppg.h "Footprint hook"): the border slots of every rank's footprint, each
+        float non-zero on one rank at most, all-reduced in place together with the status word.  ptr = None: this rank has no buffer to give
+        (it failed) and joins with zeros.  Raises RenderAborted on every rank when any of them reported a failure."""
+        if status:
+            self.status = 1
+        buf = self._view(ptr, n, "<f4") if ptr else self.torch.zeros(n, dtype=self.torch.float32, **self._tensor_kw())
+        self._exchange([buf])
+
+    def install(self, engine):
+        """Give `engine` the hooks that belong to the reducer rather than to one render: the footprint hook, which must be there BEFORE
+        set_scene / set_shard bring a film filter and world > 1 together (the library refuses the combination without it)."""
+        engine.set_footprint_hook(self.reduce_footprint)
+
     def reduce_adam(self, e):
         """Round hook of the sampling-fraction optimiser (called twice per round, include/ppg.h "Sharded optimiser").
         Phase 0: this rank's records, in key order, are split by OWNER of their D-tree and exchanged with ONE all-to-all (32-byte records
@@ -302,6 +320,11 @@ class HostReducer(TorchReducer):
     def __init__(self, dist, gather_all=False):
         import torch
         super().__init__(dist, torch.device("cpu"), gather_all)
+
+    exchanges_footprints = False  # (the oracle has no film filter)
+
+    def install(self, engine):
+        pass
 
     def _tensor_kw(self):
         return {}

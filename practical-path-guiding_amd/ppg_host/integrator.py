@@ -76,7 +76,8 @@ class GuidedPathTracer:
         if scene is not None:
             if self.reducer is not None:  # (before the first exchange: all ranks refuse the same scene alike)
                 from .distributed import check_shardable
-                check_shardable(scene)
+                check_shardable(scene, self.reducer)
+                self.reducer.install(e)  # (the footprint hook: before the scene's film filter meets the engine's shard)
             e.set_scene(scene)  # (the film's reconstruction filter comes with it: Engine.set_rfilter)
         # (cancel() is sticky in the library: one that arrived before this call cancels this render in begin_render below; the flag the hooks
         # read is cleared BEFORE that, so that a cancel() arriving any time after this line is seen by them)
