@@ -312,6 +312,44 @@ typedef struct ppg_lens {
 int ppg_set_lens(ppg_ctx *ctx, const ppg_lens *lens);
 
 /* ------------------------------------------------------------------------------------------------
+ * Delta emitters: Mitsuba's `point`, `spot` and `directional` plug-ins (mitsuba/src/emitters/point.cpp, spot.cpp, directional.cpp).  They
+ * are sampled by next-event estimation only (Emitter::sampleDirect); nothing can hit them, so with nee = never — and in every iteration
+ * in which kickstart has switched NEE off — they contribute nothing, as in the reference.  Per direct-light sample at `ref`:
+ *   point        d = position - ref, dist = |d|, d *= 1 / dist;  value = intensity * (1 / dist)^2
+ *   spot         the same, times falloffCurve(to_local * (-d)): with cosTheta = the z component, 0 for cosTheta <= cos(cutoff_angle),
+ *                1 for cosTheta >= cos(beam_width), else (cutoff_angle - acos(cosTheta)) / (cutoff_angle - beam_width)   (spot.cpp:89-125)
+ *   directional  distance = dot(ref - diskCenter, direction), diskCenter = centre - direction * radius of the bounding sphere of the
+ *                GEOMETRY's box (the kd-tree's, not the box enlarged by sensor and emitters) with its radius * 1.1; a negative distance
+ *                gives zero; else d = -direction, n = direction, dist = distance, value = irradiance   (directional.cpp:56-101, 159-180)
+ *   all three    n = 0 (directional: the direction), pdf = 1, discrete measure: the integrator does not evaluate the BSDF / D-tree
+ *                densities, miWeight(pdf, 0) = 1 (GP:1987-1994), and no area-emitter facing test applies.  The shadow segment runs to
+ *                the light's point undiminished (the emitter is not on a surface, scene.cpp:625).
+ * Emitter numbering (the uniform emitter choice of Scene::configure, scene.cpp:375-380): the scene's area emitters 0 .. n_emitters - 1,
+ * then the delta emitters in the order given here, then the environment emitter.  With no delta emitters every index and table is what
+ * it is without this call.
+ * Scene box (Scene::initializeBidirectional, scene.cpp:400-413): the box — the SD-tree's domain, the basis of the environment emitter's
+ * bounding sphere — takes in the positions of point and spot emitters; a directional emitter adds nothing.
+ * Call before ppg_set_scene, which consumes the list; the context keeps the list until it is replaced (n = 0 clears it), and a later
+ * ppg_set_scene uses it again.  Between ppg_begin_render and ppg_end_render the call is PPG_ERR_STATE.  PPG_ERR_INVALID: an unknown type, a
+ * value that is not finite, a negative intensity, angles outside 0 < beam_width <= cutoff_angle < pi/2 (spot), a zero direction
+ * (directional).  The scene then renders with the FULL kernel variants, like one with an environment emitter.
+ * The CPU oracle does not know these emitters: nothing pins them against it.  They are pinned by a restatement of every sample of a
+ * direct-light-only scene and statistically against a tiny spherical area emitter, which the oracle does pin.
+ * ---------------------------------------------------------------------------------------------- */
+#define PPG_EMITTER_POINT 0
+#define PPG_EMITTER_SPOT 1
+#define PPG_EMITTER_DIRECTIONAL 2
+typedef struct ppg_delta_emitter {
+    int32_t type;          /* PPG_EMITTER_* */
+    float intensity[3];    /* RGB intensity (point, spot: power per unit solid angle) or irradiance (directional) */
+    float position[3];     /* point, spot: world position */
+    float to_local[9];     /* spot: row-major 3x3 of toWorld's inverse — takes world directions into the light's frame, whose +z is the axis */
+    float direction[3];    /* directional: the direction the light travels in (toWorld applied to (0, 0, 1)): a unit vector, used as given */
+    float cutoff_angle, beam_width; /* spot: radians */
+} ppg_delta_emitter;
+int ppg_set_delta_emitters(ppg_ctx *ctx, const ppg_delta_emitter *emitters, uint32_t n);
+
+/* ------------------------------------------------------------------------------------------------
  * Rendering.  ppg_render() is GuidedPathTracer::render() (GP:1516-1585, IH:74-75) in one call.
  * The stepwise calls expose its phases so a multi-GPU driver can all-reduce the SD-tree statistics
  * between ppg_render_passes() and ppg_build_sdtree(); ppg_render() is exactly their composition

@@ -173,7 +173,14 @@ struct DevScene {
     // bitmap textures (FULL kernels): texture coordinates, 3 x float2 per triangle in leaf order (NaN = the mesh has none) or nullptr
     const float2 *uvs;
     const DevTex *textures;
+    // delta emitters (ppg_set_delta_emitters; FULL kernels): PPG_DELTA_STRIDE float4 each = (intensity rgb, type) (position or direction,
+    // cutoff angle) (row 2 of the world-to-light rotation, 1 / (cutoff - beam width)) (cos cutoff, cos beam width, -, -); they are emitters
+    // n_emitters .. n_emitters + n_delta - 1, and the environment emitter is number n_emitters + n_delta
+    const float4 *delta;
+    int n_delta;
+    float4 dir_sphere;         // DirectionalEmitter::m_bsphere: the geometry box's bounding sphere, radius * 1.1 (directional.cpp:88-94)
 };
+#define PPG_DELTA_STRIDE 4
 
 struct Hit {
     float t, u, v;
@@ -870,6 +877,7 @@ struct DirectSample {
     F3 n, d;
     float dist, pdf, em_pdf;
     bool is_env;
+    bool is_delta;  // point / spot / directional: discrete measure, not on a surface (no BSDF / D-tree density in the MIS weight, GP:1987-1994)
     F3 sd;        // direction and length of the shadow ray: Scene::evalTransmittance recomputes them from the two end points
     float sdist;  // (scene.cpp:621-623) — identical to (d, dist) for area emitters, a rounding apart for the environment emitter
 };
@@ -1121,18 +1129,54 @@ D float sphere_pdf_direct(const float4 *Q, F3 ref, F3 d, F3 n, float dist) {
     const float invSurfaceArea = 1 / (4 * PPG_PI_F * c4.w * c4.w);
     return invSurfaceArea * dist * dist / ppg_abs(dot3(d, n));
 }
+// PointEmitter / SpotEmitter / DirectionalEmitter::sampleDirect (point.cpp:131-147, spot.cpp:105-125, 184-200, directional.cpp:159-180)
+D F3 delta_sample_direct(const DevScene &S, const float4 *Q, F3 ref, DirectSample &ds) {
+    const float4 q0 = Q[0], q1 = Q[1];
+    const int type = __float_as_int(q0.w);
+    const F3 I = f3(q0.x, q0.y, q0.z);
+    ds.is_delta = true;
+    if (type == PPG_EMITTER_DIRECTIONAL) {
+        const F3 d = f3(q1.x, q1.y, q1.z);
+        const F3 diskCenter = f3(S.dir_sphere.x, S.dir_sphere.y, S.dir_sphere.z) - d * S.dir_sphere.w;
+        const float distance = dot3(ref - diskCenter, d);
+        if (distance < 0) return f3s(0.0f);
+        const F3 p = ref - d * distance;
+        ds.d = d * -1.0f; ds.n = d; ds.dist = distance; ds.pdf = 1.0f;
+        const F3 pd = p - ref;  // the shadow ray goes to dRec.p (scene.cpp:621-623, 889-893)
+        ds.sdist = len3(pd);
+        ds.sd = div3(pd, ds.sdist);
+        return I;
+    }
+    F3 d = f3(q1.x, q1.y, q1.z) - ref;
+    ds.dist = len3(d);
+    const float invDist = 1.0f / ds.dist;
+    ds.sd = div3(d, ds.dist); ds.sdist = ds.dist;
+    d = d * invDist;
+    ds.d = d; ds.pdf = 1.0f;
+    if (type == PPG_EMITTER_POINT) return I * (invDist * invDist);
+    // falloffCurve(trafo.inverse()(-d)): Frame::cosTheta = the z component
+    const float4 q2 = Q[2], q3 = Q[3];
+    const F3 md = d * -1.0f;
+    const float cosTheta = q2.x * md.x + q2.y * md.y + q2.z * md.z;
+    if (cosTheta <= q3.x) return f3s(0.0f);
+    if (cosTheta >= q3.y) return I * (invDist * invDist);
+    return mul3(I, f3s((q1.w - dm_acos(cosTheta)) * q2.w)) * (invDist * invDist);
+}
+template <bool FULL>
 D F3 emitter_sample_direct(const DevScene &S, F3 ref, F3 refN, float sx, float sy, DirectSample &ds) {
-    ds.pdf = 0; ds.em_pdf = 0; ds.dist = 0; ds.n = f3s(0.0f); ds.d = f3s(0.0f); ds.is_env = false; ds.sd = f3s(0.0f); ds.sdist = 0;
-    const int n_sel = S.n_emitters + (S.env.w != 0 ? 1 : 0);
+    ds.pdf = 0; ds.em_pdf = 0; ds.dist = 0; ds.n = f3s(0.0f); ds.d = f3s(0.0f); ds.is_env = false; ds.is_delta = false; ds.sd = f3s(0.0f); ds.sdist = 0;
+    const int n_delta = FULL ? S.n_delta : 0;
+    const int n_sel = S.n_emitters + n_delta + (S.env.w != 0 ? 1 : 0);
     if (n_sel == 0) return f3s(0.0f);
     const int e = pmf_sample(S.em_sel_cdf, n_sel + 1, sx);
     const float c0 = S.em_sel_cdf[e], c1 = S.em_sel_cdf[e + 1];
     ds.em_pdf = c1 - c0;
     sx = (sx - c0) / (c1 - c0);  // sampleReuse, pmf.h:183-188
-    if (e == S.n_emitters) {  // the environment emitter is the last one
+    if (e == S.n_emitters + n_delta) {  // the environment emitter is the last one
         ds.is_env = true;
         return env_sample_direct(S, ref, refN, sx, sy, ds);
     }
+    if (FULL && e >= S.n_emitters) return delta_sample_direct(S, S.delta + PPG_DELTA_STRIDE * (e - S.n_emitters), ref, ds);
     const int4 info = S.em_info[e];
     if (info.y == 0) return f3s(0.0f);
     if (info.y < 0) {  // the emitter is an analytic sphere: AreaLight::sampleDirect (area.cpp:158-173) on Sphere::sampleDirect

@@ -589,6 +589,9 @@ struct ppg_ctx {
     float geomMin[3], geomMax[3];  // the kd-tree's box (m_kdtree->getAABB()): Scene::getAABB() before the sensor's box is added
     bool lensOn = false;           // ppg_set_lens: thin lens (kept across ppg_set_scene; copied into scene.cam)
     ppg_lens lens{};
+    std::vector<ppg_delta_emitter> deltaEmitters;  // ppg_set_delta_emitters: kept until replaced; ppg_set_scene builds d_delta from it
+    DevBuf<float4> d_delta;
+    bool renderOpen = false;       // between ppg_begin_render and ppg_end_render
     int W = 0, H = 0;
 
     // shard
@@ -2272,6 +2275,7 @@ int beginRender(ppg_ctx *ctx) {  // GP:1519-1550
     ctx->startTime = std::chrono::steady_clock::now();
     ctx->passesRendered = 0; ctx->passesRenderedThisIter = 0;
     ctx->treeAlive = true;
+    ctx->renderOpen = true;
     // ppg_cancel() is sticky: a cancel no render has acted on yet — it arrived while the scene was being set up, say, seconds of BVH build —
     // cancels THIS render; the flag is consumed here (it used to be cleared, and that cancel was lost).  One the previous render DID act on
     // (it returned PPG_ERR_CANCELLED, or left through a failing hook) is spent.
@@ -2307,6 +2311,7 @@ int endIteration(ppg_ctx *ctx) {  // GP:1417-1422
 
 int endRender(ppg_ctx *ctx) {  // GP:1567-1582
     ctx->joinTree();
+    ctx->renderOpen = false;
 #ifdef PPG_PROBE
     if (ctx->d_probe.p) {
         unsigned long long h[PPG_PROBE_SLOTS];
@@ -2604,6 +2609,17 @@ const char *ppg_last_error(const ppg_ctx *ctx) { return ctx ? ctx->error.c_str()
 
 // Scene::getAABB() (scene.cpp:386-414): the kd-tree's box expanded by the sensor's box — the pinhole position (perspective.cpp:444-446) or,
 // with a thin lens, the aperture disk (-r, -r, 0) .. (r, r, 0) through the camera's world transform (thinlens.cpp:516-520, track.cpp:123-143)
+// ... and by every emitter's box (scene.cpp:400-413): the position of a point or spot emitter (getTranslationBounds of its static
+// transform); a directional emitter's box is empty
+static void deltaBox(ppg_ctx *ctx) {
+    for (const ppg_delta_emitter &e : ctx->deltaEmitters) {
+        if (e.type == PPG_EMITTER_DIRECTIONAL) continue;
+        for (int a = 0; a < 3; ++a) {
+            ctx->aabbMin[a] = ppg_min(ctx->aabbMin[a], e.position[a]);
+            ctx->aabbMax[a] = ppg_max(ctx->aabbMax[a], e.position[a]);
+        }
+    }
+}
 static void sceneBox(ppg_ctx *ctx, const float *c2w) {
     for (int a = 0; a < 3; ++a) { ctx->aabbMin[a] = ctx->geomMin[a]; ctx->aabbMax[a] = ctx->geomMax[a]; }
     if (!ctx->lensOn) {
@@ -2612,19 +2628,20 @@ static void sceneBox(ppg_ctx *ctx, const float *c2w) {
             ctx->aabbMin[a] = ppg_min(ctx->aabbMin[a], c);
             ctx->aabbMax[a] = ppg_max(ctx->aabbMax[a], c);
         }
-        return;
-    }
-    const float r = ctx->lens.aperture_radius;
-    for (int j = 0; j < 8; ++j) {  // AABB::getCorner(j) of the flat box, Transform::operator()(Point)
-        const float p[3] = {(j & 1) ? r : -r, (j & 2) ? r : -r, 0.0f};
-        float q[4];
-        for (int a = 0; a < 4; ++a) q[a] = c2w[4 * a] * p[0] + c2w[4 * a + 1] * p[1] + c2w[4 * a + 2] * p[2] + c2w[4 * a + 3];
-        for (int a = 0; a < 3; ++a) {
-            const float v = q[3] == 1.0f ? q[a] : q[a] / q[3];
-            ctx->aabbMin[a] = ppg_min(ctx->aabbMin[a], v);
-            ctx->aabbMax[a] = ppg_max(ctx->aabbMax[a], v);
+    } else {
+        const float r = ctx->lens.aperture_radius;
+        for (int j = 0; j < 8; ++j) {  // AABB::getCorner(j) of the flat box, Transform::operator()(Point)
+            const float p[3] = {(j & 1) ? r : -r, (j & 2) ? r : -r, 0.0f};
+            float q[4];
+            for (int a = 0; a < 4; ++a) q[a] = c2w[4 * a] * p[0] + c2w[4 * a + 1] * p[1] + c2w[4 * a + 2] * p[2] + c2w[4 * a + 3];
+            for (int a = 0; a < 3; ++a) {
+                const float v = q[3] == 1.0f ? q[a] : q[a] / q[3];
+                ctx->aabbMin[a] = ppg_min(ctx->aabbMin[a], v);
+                ctx->aabbMax[a] = ppg_max(ctx->aabbMax[a], v);
+            }
         }
     }
+    deltaBox(ctx);
 }
 
 // Constant / EnvironmentMap: bounding sphere of createShape() (constant.cpp:67-78, envmap.cpp:330-355) around Scene::getAABB()
@@ -2918,6 +2935,7 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
             if (emitterSphere[e] >= 0) info[e].y = -(emitterSphere[e] + 1);  // sampled analytically (sphere_sample_direct)
             selCdf.push_back(selCdf.back() + 1.0f);
         }
+        for (size_t k = 0; k < ctx->deltaEmitters.size(); ++k) selCdf.push_back(selCdf.back() + 1.0f);  // delta emitters follow the area emitters
         if (s->environment || s->envmap) selCdf.push_back(selCdf.back() + 1.0f);  // the environment emitter is the last one
         float selSum = 0, selNorm = 0;
         if (selCdf.size() > 1) selNorm = normalize(selCdf, 0, selCdf.size(), selSum);
@@ -2945,6 +2963,32 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
     S.materials = ctx->d_materials.p; S.emitters = ctx->d_emitters.p; S.n_tris = (int)s->n_triangles; S.has_null = hasNull ? 1 : 0;
     S.rtrans = s->n_rtrans ? ctx->d_rtrans.p : nullptr; S.rtrans_n = (int)s->rtrans_samples;
     S.spheres = nullptr; S.n_spheres = (int)s->n_spheres;
+    S.delta = nullptr; S.n_delta = (int)ctx->deltaEmitters.size(); S.dir_sphere = make_float4(0, 0, 0, 0);
+    if (S.n_delta) {
+        std::vector<float4> tab(PPG_DELTA_STRIDE * ctx->deltaEmitters.size());
+        for (size_t k = 0; k < ctx->deltaEmitters.size(); ++k) {
+            const ppg_delta_emitter &e = ctx->deltaEmitters[k];
+            const float *v = e.type == PPG_EMITTER_DIRECTIONAL ? e.direction : e.position;
+            float4 *Q = &tab[PPG_DELTA_STRIDE * k];
+            Q[0] = make_float4(e.intensity[0], e.intensity[1], e.intensity[2], __builtin_bit_cast(float, (int)e.type));
+            Q[1] = make_float4(v[0], v[1], v[2], e.cutoff_angle);
+            Q[2] = Q[3] = make_float4(0, 0, 0, 0);
+            if (e.type == PPG_EMITTER_SPOT) {  // SpotEmitter::configure (spot.cpp:89-94)
+                Q[2] = make_float4(e.to_local[6], e.to_local[7], e.to_local[8], 1.0f / (e.cutoff_angle - e.beam_width));
+                Q[3] = make_float4(std::cos(e.cutoff_angle), std::cos(e.beam_width), 0, 0);
+            }
+        }
+        HIP_CHECK(ctx->d_delta.reserve(tab.size()));
+        HIP_CHECK(hipMemcpy(ctx->d_delta.p, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice));
+        S.delta = ctx->d_delta.p;
+        {   // DirectionalEmitter::createShape (directional.cpp:88-94): AABB::getBSphere (aabb.h) of the kd-tree's box, radius * 1.1
+            float c[3];
+            for (int a = 0; a < 3; ++a) c[a] = (ctx->geomMax[a] + ctx->geomMin[a]) * 0.5f;
+            const float dx = c[0] - ctx->geomMax[0], dy = c[1] - ctx->geomMax[1], dz = c[2] - ctx->geomMax[2];
+            S.dir_sphere = make_float4(c[0], c[1], c[2], std::sqrt(dx * dx + dy * dy + dz * dz) * 1.1f);
+        }
+        ctx->fullMaterials = true;  // the delta-emitter code lives in the FULL kernel variants
+    }
     if (s->n_spheres) {
         std::vector<float4> sph(4 * (size_t)s->n_spheres);
         for (uint32_t k = 0; k < s->n_spheres; ++k) {
@@ -2973,12 +3017,13 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
     }
     // Every array the path kernels walk must be there before a launch can chase it: an unset pointer here is a hung GPU, not a wrong pixel
     // (round 5 lost 40 GPU minutes to five assignments that an edit had turned into a comment).
-    if (!S.materials || !S.bvh4 || (S.n_tris > 0 && (!S.tris || !S.accel || !S.bvh)) || (S.n_spheres > 0 && !S.spheres)) {
+    if (!S.materials || !S.bvh4 || (S.n_tris > 0 && (!S.tris || !S.accel || !S.bvh)) || (S.n_spheres > 0 && !S.spheres) || (S.n_delta > 0 && !S.delta)) {
         ctx->error = "internal: device scene incomplete";
         return PPG_ERR_STATE;
     }
     ctx->haveScene = true;
     ctx->treeAlive = false;
+    ctx->renderOpen = false;
     ctx->pathsReady = false;
     {   // scene preprocessing also sizes the per-pass buffers (path state, vertex slots, queues, film)
         int rc = allocPaths(ctx);
@@ -3138,6 +3183,26 @@ int ppg_set_lens(ppg_ctx *ctx, const ppg_lens *lens) {
     return PPG_OK;
 }
 
+int ppg_set_delta_emitters(ppg_ctx *ctx, const ppg_delta_emitter *em, uint32_t n) {
+    if (ctx->renderOpen) { ctx->error = "delta emitters: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (n && !em) { ctx->error = "delta emitters: no list"; return PPG_ERR_INVALID; }
+    auto finite = [](const float *v, int k) { for (int i = 0; i < k; ++i) if (!std::isfinite(v[i])) return false; return true; };
+    for (uint32_t k = 0; k < n; ++k) {
+        const ppg_delta_emitter &e = em[k];
+        const std::string who = "delta emitter " + std::to_string(k) + ": ";
+        if (e.type != PPG_EMITTER_POINT && e.type != PPG_EMITTER_SPOT && e.type != PPG_EMITTER_DIRECTIONAL) { ctx->error = who + "unknown type"; return PPG_ERR_INVALID; }
+        if (!finite(e.intensity, 3) || !finite(e.position, 3) || !finite(e.to_local, 9) || !finite(e.direction, 3) || !std::isfinite(e.cutoff_angle) ||
+            !std::isfinite(e.beam_width)) { ctx->error = who + "a value is not finite"; return PPG_ERR_INVALID; }
+        if (e.intensity[0] < 0 || e.intensity[1] < 0 || e.intensity[2] < 0) { ctx->error = who + "negative intensity"; return PPG_ERR_INVALID; }
+        if (e.type == PPG_EMITTER_SPOT && !(0 < e.beam_width && e.beam_width <= e.cutoff_angle && e.cutoff_angle < 0.5f * PPG_PI_F)) {
+            ctx->error = who + "spot angles must satisfy 0 < beam_width <= cutoff_angle < pi/2"; return PPG_ERR_INVALID;
+        }
+        if (e.type == PPG_EMITTER_DIRECTIONAL && e.direction[0] == 0 && e.direction[1] == 0 && e.direction[2] == 0) { ctx->error = who + "zero direction"; return PPG_ERR_INVALID; }
+    }
+    ctx->deltaEmitters.assign(em, em + n);
+    return PPG_OK;
+}
+
 int ppg_debug_rfilter_table(const ppg_rfilter *f, float table[32], float *radius, int32_t *border) {
     if (!f || !table || !radius || !border) return PPG_ERR_INVALID;
     std::string err;
@@ -3158,7 +3223,7 @@ int ppg_render(ppg_ctx *ctx) {  // GP:1516-1585
     int rc = beginRender(ctx);
     if (rc) return rc;
     rc = ctx->budgetType == 0 ? renderSPP(ctx) : renderTime(ctx);
-    if (rc) return rc;
+    if (rc) { ctx->renderOpen = false; return rc; }
     return endRender(ctx);
 }
 

@@ -953,7 +953,7 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
         int em_id = I.emitter;
         if (FULL && MSET != MSET_COMMON && !valid && S.env.w != 0) {  // GP:2236-2243: the ray left the scene
             const float4 ro4 = ray_origin();
-            if (env_fill_direct(S, f3(ro4.x, ro4.y, ro4.z), d)) { value = env_radiance(S, d); em_id = S.n_emitters; }
+            if (env_fill_direct(S, f3(ro4.x, ro4.y, ro4.z), d)) { value = env_radiance(S, d); em_id = S.n_emitters + S.n_delta; }
         }
         if (FULL && MSET != MSET_COMMON && S.has_null && valid && I.emitter < 0) {
             // rayIntersectAndLookForEmitter GP:2184-2245: the path continues from THIS hit, but the search for an emitter
@@ -986,7 +986,7 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
                     em_n = Ic.n; em_dist = hc.t; em_id = Ic.emitter;  // dist from the LAST ray origin, as in the reference
                 } else if (!abandoned && !surface && S.env.w != 0 && env_fill_direct(S, ro, d)) {
                     value = mul3(transmittance, env_radiance(S, d));
-                    em_id = S.n_emitters;
+                    em_id = S.n_emitters + S.n_delta;
                 }
             }
         }
@@ -997,7 +997,7 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
         if (NEE && R.do_nee && !isDelta && !iszero3(value)) {
             float pdfDirect = 0.0f;
             const float dn = dot3(d, em_n);
-            if (FULL && em_id == S.n_emitters) {
+            if (FULL && em_id == S.n_emitters + S.n_delta) {
                 pdfDirect = S.env.w == 2.0f ? envmap_pdf_direction(S, envmap_to_local(S, d)) : env_pdf_direct(P.nee_cos[i]);
             } else if ((flags & FL_PEND_REFN) && dn < 0) {
                 const int4 info = S.em_info[em_id];
@@ -1207,16 +1207,16 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
             const float ex = ppg_rand(key, dim++);
             const float ey = ppg_rand(key, dim++);
             DirectSample ds;
-            F3 value = emitter_sample_direct(S, I.p, refN, ex, ey, ds);
+            F3 value = emitter_sample_direct<FULL>(S, I.p, refN, ex, ey, ds);
             if (ds.pdf != 0) {
                 if (FULL && S.has_null) {  // value *= evalTransmittance(...) / emPdf, scene.cpp:887-889
-                    const F3 tr = shadow_transmittance(S, nee.small_tris, nee.stack_col, I.p, ds.sd, ds.sdist, ds.is_env ? 1.0f : 1 - PPG_SHADOW_EPSILON,
+                    const F3 tr = shadow_transmittance(S, nee.small_tris, nee.stack_col, I.p, ds.sd, ds.sdist, (ds.is_env || ds.is_delta) ? 1.0f : 1 - PPG_SHADOW_EPSILON,
                                                        R.max_depth - (int)depth - 1, traced);
                     if (iszero3(tr)) value = f3s(0.0f);
                     else { value = div3(mul3(value, tr), ds.em_pdf); ds.pdf *= ds.em_pdf; }
                 } else {
                     ++traced;
-                    if (shadow_occluded<FULL>(S, nee.small_tris, nee.stack_col, I.p, ds.sd, ds.sdist * ((FULL && ds.is_env) ? 1.0f : 1 - PPG_SHADOW_EPSILON))) {
+                    if (shadow_occluded<FULL>(S, nee.small_tris, nee.stack_col, I.p, ds.sd, ds.sdist * ((FULL && (ds.is_env || ds.is_delta)) ? 1.0f : 1 - PPG_SHADOW_EPSILON))) {
                         value = f3s(0.0f);
                     } else {
                         value = div3(value, ds.em_pdf);
@@ -1230,7 +1230,9 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
                 if (!R.strict_normals || woDotGeoNE * wo_e.z > 0) {
                     const F3 bsdfVal = b_eval(I.wi, wo_e);
                     float woPdfE = 0, bsdfPdfE = 0, dTreePdfE = 0;  // pdfMat, GP:1693-1710
-                    if (!T.is_built) {
+                    if (FULL && ds.is_delta) {
+                        // not on a surface, discrete measure: pdfMat is not called (GP:1987-1991), miWeight(dRec.pdf, 0) = 1
+                    } else if (!T.is_built) {
                         woPdfE = bsdfPdfE = b_pdf(I.wi, wo_e);
                     } else {
                         bsdfPdfE = b_pdf(I.wi, wo_e);

@@ -53,6 +53,7 @@ struct SceneData {
     ppg_rfilter rfilter{};
     bool hasLens = false;                          // thin-lens camera (ppg_set_lens); false = pinhole
     ppg_lens lens{};
+    std::vector<ppg_delta_emitter> deltaEmitters;  // point / spot / directional emitters (ppg_set_delta_emitters, before ppg_set_scene)
 
     ppg_scene view() const {
         ppg_scene s{};
@@ -162,6 +163,7 @@ public:
         if (reducer) check(ppg_set_footprint_hook(m_ctx, &GuidedPathTracerHIP::footprintHook, this), "ppg_set_footprint_hook");
         const bool spp = std::string(m_cfg.budgetType) == "spp";
         ppg_scene sv = scene.view();
+        check(ppg_set_delta_emitters(m_ctx, scene.deltaEmitters.data(), (uint32_t)scene.deltaEmitters.size()), "ppg_set_delta_emitters");
         check(ppg_set_scene(m_ctx, &sv), "ppg_set_scene");
         check(ppg_set_rfilter(m_ctx, scene.hasRFilter ? &scene.rfilter : nullptr), "ppg_set_rfilter");
         check(ppg_set_lens(m_ctx, scene.hasLens ? &scene.lens : nullptr), "ppg_set_lens");

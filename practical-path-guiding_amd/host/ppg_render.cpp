@@ -108,6 +108,14 @@ static bool loadSceneChecked(const char *path, SceneData &s) {
         f.read((char *)&s.lens, sizeof(ppg_lens));
         s.hasLens = true;
     }
+    if (hdr[5] & 256) {  // bit 8: point / spot / directional emitters (uint32 n, n x ppg_delta_emitter), only when there are any
+        uint32_t n = 0;
+        if (!fits(4)) return false;
+        f.read((char *)&n, 4);
+        if (!fits((uint64_t)n * sizeof(ppg_delta_emitter))) return false;
+        s.deltaEmitters.resize(n);
+        f.read((char *)s.deltaEmitters.data(), (std::streamsize)(n * sizeof(ppg_delta_emitter)));
+    }
     return (bool)f;
 }
 
@@ -177,7 +185,8 @@ static bool saveScene(const char *path, const SceneData &s) {
     std::ofstream f(path, std::ios::binary);
     const uint32_t hdr[6] = {(uint32_t)(s.positions.size() / 3), (uint32_t)(s.indices.size() / 3), (uint32_t)s.materials.size(), (uint32_t)s.emitters.size(),
                              s.normals.empty() ? 0u : 1u, (s.hasEnvironment ? 1u : 0u) | (s.rtrans.empty() ? 0u : 2u) | (s.spheres.empty() ? 0u : 4u) | (s.hasEnvmap ? 8u : 0u) |
-                                 (s.texcoords.empty() ? 0u : 16u) | (s.textures.empty() ? 0u : 32u) | (s.hasRFilter ? 64u : 0u) | (s.hasLens ? 128u : 0u)};
+                                 (s.texcoords.empty() ? 0u : 16u) | (s.textures.empty() ? 0u : 32u) | (s.hasRFilter ? 64u : 0u) | (s.hasLens ? 128u : 0u) |
+                                 (s.deltaEmitters.empty() ? 0u : 256u)};
     f.write("PPGS", 4); f.write((const char *)hdr, sizeof hdr);
     f.write((const char *)s.positions.data(), s.positions.size() * 4);
     if (!s.normals.empty()) f.write((const char *)s.normals.data(), s.normals.size() * 4);
@@ -216,6 +225,11 @@ static bool saveScene(const char *path, const SceneData &s) {
     }
     if (s.hasRFilter) f.write((const char *)&s.rfilter, sizeof(ppg_rfilter));
     if (s.hasLens) f.write((const char *)&s.lens, sizeof(ppg_lens));
+    if (!s.deltaEmitters.empty()) {
+        const uint32_t n = (uint32_t)s.deltaEmitters.size();
+        f.write((const char *)&n, 4);
+        f.write((const char *)s.deltaEmitters.data(), (std::streamsize)(n * sizeof(ppg_delta_emitter)));
+    }
     return (bool)f;
 }
 
@@ -312,6 +326,7 @@ int main(int argc, char **argv) {
         core.configure(props);
         core.setRFilter(scene.hasRFilter ? &scene.rfilter : nullptr);
         core.setLens(scene.hasLens ? &scene.lens : nullptr);
+        core.setDeltaEmitters(scene.deltaEmitters.data(), scene.deltaEmitters.size());
         core.setSeed((uint64_t)std::stoull(props.getString("seed", "0")));
         std::string dest = out;
         const size_t dot = dest.find_last_of('.');

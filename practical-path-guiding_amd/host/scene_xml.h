@@ -7,7 +7,7 @@
  *   shapes      sphere (center, radius, toWorld = rotation x uniform scale, flipNormals; analytic), obj (filename, toWorld, faceNormals, flipNormals, flipTexCoords, collapse), rectangle (toWorld, flipNormals)
  *   bsdfs       diffuse, conductor, roughconductor / roughdielectric / roughplastic (ggx / beckmann, isotropic; roughplastic reads Mitsuba's data/microfacet tables), plastic, dielectric, thindielectric, mask (constant opacity),
  *               twosided(BRDF) — top level with id, nested, or <ref id>
- *   emitters    area (nested in a shape), constant (environment), envmap (latitude-longitude .exr / .pfm / .hdr; filename, scale, toWorld = rotation),
+ *   emitters    point, spot, directional (SceneData::deltaEmitters; ppg_set_delta_emitters), area (nested in a shape), constant (environment), envmap (latitude-longitude .exr / .pfm / .hdr; filename, scale, toWorld = rotation),
  *               sunsky (baked into an envmap at load time, host/sunsky.h; its tables are parsed from the operator's Mitsuba source tree)
  *   values      <spectrum>, <rgb>, <srgb>; <transform> of translate / rotate / scale / lookAt / matrix; <default> and $name
  *
@@ -832,8 +832,15 @@ public:
                 out.scene.hasEnvmap = true;
                 continue;
             }
+            if (e.get("type") == "point" || e.get("type") == "spot" || e.get("type") == "directional") { out.scene.deltaEmitters.push_back(makeDeltaEmitter(e)); continue; }
             if (!m_strict) { out.warnings.push_back("emitter '" + e.get("type") + "' skipped (not supported)"); continue; }
-            throw std::runtime_error("emitter type '" + e.get("type") + "' is not supported (area emitters on shapes and one `constant`, `envmap` or `sunsky` environment emitter; SURVEY.md §8 f2)");
+            throw std::runtime_error("emitter type '" + e.get("type") + "' is not supported (area emitters on shapes, `point`, `spot` and `directional` emitters, and one `constant`, `envmap` or `sunsky` environment emitter; SURVEY.md §8 f2)");
+        }
+        if (!out.scene.deltaEmitters.empty()) {
+            const std::string nee = out.integrator.values.count("nee") ? out.integrator.values["nee"] : "never";
+            if (nee != "always")
+                out.warnings.push_back("point / spot / directional emitters are reached by next-event estimation only: with nee = " + nee +
+                                       " they contribute nothing in every iteration that runs without it (as in Mitsuba)");
         }
         // shapes
         struct Part { Mesh mesh; uint32_t mat; int em; };
@@ -1149,6 +1156,71 @@ private:
             for (uint32_t id : {b, b + 1, b + 2, b + 3, b, b + 2}) r.indices.push_back(id);
         }
         return r;
+    }
+    // <emitter type="point" | "spot" | "directional"> (point.cpp:57-69, spot.cpp:68-94, directional.cpp:55-73) → ppg_delta_emitter; the same
+    // values, in the same arithmetic, as ppg_host/mitsuba_xml.py parse_delta_emitter
+    ppg_delta_emitter makeDeltaEmitter(const XmlNode &e) const {
+        const std::string t = e.get("type");
+        auto ep = props(e);
+        const XmlNode *tw = nullptr;
+        for (auto &c : e.children) if (c.tag == "transform" && (!c.attr("name") || c.get("name") == "toWorld")) { tw = &c; break; }
+        const Mat4 m = tw ? transform(*tw) : Mat4::identity();
+        auto xyz = [&](const char *tag, const char *name, float v[3]) {
+            for (auto &c : e.children)
+                if (c.tag == tag && c.get("name") == name) {
+                    const char *ax[3] = {"x", "y", "z"};
+                    for (int a = 0; a < 3; ++a) v[a] = c.attr(ax[a]) ? (float)std::stod(sub(c.get(ax[a]))) : 0.0f;
+                    return true;
+                }
+            return false;
+        };
+        if (ep.count("samplingWeight") && std::stod(ep["samplingWeight"]) != 1.0) throw std::runtime_error(t + " emitter: a samplingWeight other than 1 is not supported");
+        ppg_delta_emitter d{};
+        d.to_local[0] = d.to_local[4] = d.to_local[8] = 1.0f;
+        if (t == "point") {
+            d.type = PPG_EMITTER_POINT;
+            const bool hasPos = xyz("point", "position", d.position);
+            if (hasPos && tw) throw std::runtime_error("point emitter: only one of the parameters 'position' and 'toWorld' can be used");
+            if (!hasPos) for (int a = 0; a < 3; ++a) d.position[a] = m.m[4 * a + 3];
+            colour(e, "intensity", 1.0f, d.intensity);
+            return d;
+        }
+        if (t == "spot") {
+            d.type = PPG_EMITTER_SPOT;
+            for (auto &c : e.children) if (c.get("name") == "texture" || c.tag == "texture") throw std::runtime_error("spot emitter: a projection 'texture' is not supported");
+            const float rad = 3.14159265358979323846f / 180.0f;  // degToRad, util.h
+            const float cutoffDeg = ep.count("cutoffAngle") ? (float)std::stod(ep["cutoffAngle"]) : 20.0f;
+            const float beamDeg = ep.count("beamWidth") ? (float)std::stod(ep["beamWidth"]) : cutoffDeg * 3.0f / 4.0f;
+            d.cutoff_angle = cutoffDeg * rad; d.beam_width = beamDeg * rad;
+            if (d.cutoff_angle < d.beam_width) throw std::runtime_error("spot emitter: cutoffAngle must not be smaller than beamWidth");
+            if (!(0 < d.beam_width && cutoffDeg < 90)) throw std::runtime_error("spot emitter: the angles must satisfy 0 < beamWidth <= cutoffAngle < 90 degrees");
+            for (int a = 0; a < 3; ++a) d.position[a] = m.m[4 * a + 3];
+            inverse3(m, d.to_local);
+            colour(e, "intensity", 1.0f, d.intensity);
+            return d;
+        }
+        d.type = PPG_EMITTER_DIRECTIONAL;
+        float v[3];
+        const bool hasDir = xyz("vector", "direction", v);
+        if (hasDir && tw) throw std::runtime_error("directional emitter: only one of the parameters 'direction' and 'toWorld' can be used at a time");
+        if (hasDir) {
+            const float ln = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+            if (!(ln > 0)) throw std::runtime_error("directional emitter: 'direction' is zero");
+            for (int a = 0; a < 3; ++a) d.direction[a] = v[a] / ln;
+        } else {
+            if (hasScale(m)) throw std::runtime_error("directional emitter: scale factors in the emitter-to-world transformation are not allowed");
+            for (int a = 0; a < 3; ++a) d.direction[a] = m.m[4 * a + 2];
+        }
+        colour(e, "irradiance", 1.0f, d.intensity);
+        return d;
+    }
+    // inverse of the upper 3x3 by cofactors in double, rounded to float (ppg_host/mitsuba_xml.py inverse3: the same operations)
+    static void inverse3(const Mat4 &m, float out[9]) {
+        const double a = m.m[0], b = m.m[1], c = m.m[2], d = m.m[4], e = m.m[5], f = m.m[6], g = m.m[8], h = m.m[9], i = m.m[10];
+        const double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
+        const double inv[9] = {(e * i - f * h) / det, (c * h - b * i) / det, (b * f - c * e) / det, (f * g - d * i) / det, (a * i - c * g) / det,
+                               (c * d - a * f) / det, (d * h - e * g) / det, (b * g - a * h) / det, (a * e - b * d) / det};
+        for (int k = 0; k < 9; ++k) out[k] = (float)inv[k];
     }
     // focalLength "<x>mm" → diagonal field of view (PerspectiveCamera::configure, sensor.cpp:264-276), in the reference's float arithmetic
     static double focalLengthFov(std::string f) {

@@ -22,7 +22,8 @@
  *               adapters the <bsdf> element is re-read from the scene file (scene->getSourceFile(), matched by id, scene.h:1107) with the
  *               parser of this repository's stand-alone driver (host/scene_xml.h — the same code path tests/test_cpp_host.py pins against
  *               the Python loader).  Unsupported plug-ins end the render with an error that names them.
- *   emitters    `area` emitters by shape (radiance from the emitter's Properties), `constant`, `envmap` (level 0 of the bitmap it was given)
+ *   emitters    `area` emitters by shape (radiance from the emitter's Properties), `point`, `spot` (no projection texture) and `directional`
+ *               from the scene's emitter list (world transform, Properties; samplingWeight 1), `constant`, `envmap` (level 0 of the bitmap it was given)
  *               and `sunsky` / `sky` / `sun` through the environment map Mitsuba itself rasterised (getEnvironmentEmitter() → its bitmap)
  *   sensor      PerspectiveCamera: m_sampleToCamera rebuilt from getXFov / clip planes / crop (perspective.cpp:150-164), world transform;
  *               ThinLens: the same + apertureRadius and getFocusDistance() (ppg_set_lens)
@@ -75,6 +76,7 @@ public:
         }
         const ppg_scene desc = data.view();
         m_core.setLens(data.hasLens ? &data.lens : nullptr);
+        m_core.setDeltaEmitters(data.deltaEmitters.data(), data.deltaEmitters.size());
         Log(EInfo, "Starting render job (%ix%i, MI355X, %i triangles, %i analytic spheres) ..", film->getCropSize().x, film->getCropSize().y,
             (int) (data.indices.size() / 3), (int) data.spheres.size());
         /* create → scene → render; SD-tree dumps to "<dest>-NN.sdt" (GP:1192-1195) */
@@ -249,6 +251,39 @@ private:
                 why = "shape plug-in '" + shape->getProperties().getPluginName() + "' is not supported (triangle meshes and spheres are)";
                 return false;
             }
+        }
+
+        /* point / spot / directional emitters, in the order of the scene's emitter list (point.cpp:57-69, spot.cpp:68-94, directional.cpp:55-73);
+           each constructor has put `position` / `direction` into the world transform */
+        const ref_vector<Emitter> &emitters = scene->getEmitters();
+        for (size_t i = 0; i < emitters.size(); ++i) {
+            const Emitter *em = emitters[i].get();
+            const Properties &ep = em->getProperties();
+            const std::string name = ep.getPluginName();
+            if (name != "point" && name != "spot" && name != "directional") continue;
+            if (em->getSamplingWeight() != 1) { why = "emitter plug-in '" + name + "': a samplingWeight other than 1 is not supported"; return false; }
+            const Transform trafo = em->getWorldTransform()->eval(0);
+            const Matrix4x4 &w = trafo.getMatrix(), &inv = trafo.getInverseMatrix();
+            ppg_delta_emitter d = ppg_delta_emitter();
+            Float r, g, b;
+            if (name == "directional") {
+                d.type = PPG_EMITTER_DIRECTIONAL;
+                ep.getSpectrum("irradiance", Spectrum(1.0f)).toLinearRGB(r, g, b);
+                for (int k = 0; k < 3; ++k) d.direction[k] = (float) w(k, 2);
+            } else {
+                d.type = name == "point" ? PPG_EMITTER_POINT : PPG_EMITTER_SPOT;
+                ep.getSpectrum("intensity", Spectrum(1.0f)).toLinearRGB(r, g, b);
+                for (int k = 0; k < 3; ++k) d.position[k] = (float) w(k, 3);
+            }
+            for (int q = 0; q < 3; ++q) for (int k = 0; k < 3; ++k) d.to_local[3 * q + k] = (float) inv(q, k);
+            if (name == "spot") {
+                if (ep.hasProperty("texture")) { why = "emitter plug-in 'spot': a projection texture is not supported"; return false; }
+                const Float cutoff = ep.getFloat("cutoffAngle", 20);
+                d.cutoff_angle = (float) degToRad(cutoff);
+                d.beam_width = (float) degToRad(ep.getFloat("beamWidth", cutoff * 3.0f / 4.0f));
+            }
+            d.intensity[0] = (float) r; d.intensity[1] = (float) g; d.intensity[2] = (float) b;
+            data.deltaEmitters.push_back(d);
         }
 
         /* environment emitter: constant, or whatever map Mitsuba holds (envmap, and sunsky / sky / sun after their own rasterisation) */

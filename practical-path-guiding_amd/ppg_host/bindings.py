@@ -216,6 +216,43 @@ class Lens(C.Structure):
         return dict(aperture_radius=float(self.aperture_radius), focus_distance=float(self.focus_distance))
 
 
+class DeltaEmitter(C.Structure):
+    """ppg_delta_emitter — a point, spot or directional emitter (mitsuba/src/emitters/point.cpp, spot.cpp, directional.cpp).  As a dict
+    (SceneDesc.delta_emitters): {"type": "point" | "spot" | "directional", "intensity": rgb (directional: the irradiance), and per type
+    "position" (point, spot), "to_local": the 3x3 of toWorld's inverse, row-major, "cutoff_angle", "beam_width" in radians (spot),
+    "direction" (directional)}."""
+    TYPES = ("point", "spot", "directional")
+    _fields_ = [("type", C.c_int32), ("intensity", C.c_float * 3), ("position", C.c_float * 3), ("to_local", C.c_float * 9),
+                ("direction", C.c_float * 3), ("cutoff_angle", C.c_float), ("beam_width", C.c_float)]
+
+    @classmethod
+    def from_dict(cls, d):
+        unknown = set(d) - {"type", "intensity", "position", "to_local", "direction", "cutoff_angle", "beam_width"}
+        if unknown:
+            raise ValueError("delta emitter: unknown parameters %s" % sorted(unknown))
+        if d.get("type") not in cls.TYPES:
+            raise ValueError("delta emitter: unknown type %r (point, spot, directional)" % (d.get("type"),))
+        e = cls()
+        e.type = cls.TYPES.index(d["type"])
+        e.intensity[:] = [float(v) for v in d["intensity"]]
+        e.position[:] = [float(v) for v in d.get("position", (0, 0, 0))]
+        e.to_local[:] = [float(v) for v in np.asarray(d.get("to_local", np.eye(3)), np.float32).reshape(-1)]
+        e.direction[:] = [float(v) for v in d.get("direction", (0, 0, 0))]
+        e.cutoff_angle, e.beam_width = float(d.get("cutoff_angle", 0.0)), float(d.get("beam_width", 0.0))
+        return e
+
+    def as_dict(self):
+        t = self.TYPES[self.type]
+        d = dict(type=t, intensity=tuple(float(v) for v in self.intensity))
+        if t != "directional":
+            d["position"] = tuple(float(v) for v in self.position)
+        if t == "spot":
+            d.update(to_local=[float(v) for v in self.to_local], cutoff_angle=float(self.cutoff_angle), beam_width=float(self.beam_width))
+        if t == "directional":
+            d["direction"] = tuple(float(v) for v in self.direction)
+        return d
+
+
 class Emitter(C.Structure):
     _fields_ = [("radiance", C.c_float * 3), ("_pad", C.c_float)]
 
@@ -381,6 +418,14 @@ class Engine:
         s.camera.near_clip, s.camera.far_clip = cam["near_clip"], cam["far_clip"]
         s.camera.width, s.camera.height = cam["width"], cam["height"]
         self._scene_keep = (pos, idx, tm, te, nrm, mats, ems, rt, sph_arr, envmap, uvs, tex_arr, tex_keep)
+        # the point / spot / directional emitters go first: ppg_set_scene consumes the context's list.  (A context that never had any is
+        # left alone; after a scene with such lights an empty list clears them.)
+        delta = getattr(desc, "delta_emitters", None) or []
+        if self.prefix == "ppg_":
+            if delta or getattr(self, "_delta", None):
+                self.set_delta_emitters(delta)
+        elif delta:
+            raise NotImplementedError("%s: point, spot and directional emitters are not implemented here" % self.prefix)
         self._call("set_scene", C.byref(s))
         self.width, self.height = cam["width"], cam["height"]
         # the film's reconstruction filter comes with the scene description (None / absent: the default box)
@@ -399,6 +444,15 @@ class Engine:
                 self.set_lens(lens)
         elif lens is not None:
             raise NotImplementedError("%s: the thin-lens camera is not implemented here" % self.prefix)
+
+    def set_delta_emitters(self, emitters):
+        """ppg_set_delta_emitters: a list of emitter dicts (DeltaEmitter); an empty list clears it.  Takes effect at the next set_scene."""
+        emitters = list(emitters or [])
+        arr = (DeltaEmitter * max(1, len(emitters)))()
+        for i, d in enumerate(emitters):
+            arr[i] = d if isinstance(d, DeltaEmitter) else DeltaEmitter.from_dict(d)
+        self._call("set_delta_emitters", arr, C.c_uint32(len(emitters)))
+        self._delta = emitters
 
     def set_lens(self, lens):
         """ppg_set_lens: lens = {"aperture_radius", "focus_distance"} (Lens) or None for the pinhole"""

@@ -11,7 +11,9 @@
   bsdfs       diffuse, conductor (material none, explicit eta / k, or a named material read from Mitsuba's data/ior), roughconductor / roughdielectric / roughplastic (ggx / beckmann, isotropic; roughplastic reads Mitsuba's data/microfacet tables),
               plastic, dielectric, thindielectric,
               mask (constant opacity), twosided(any of the BRDFs) — top level with id, nested, or <ref id>
-  emitters    area (nested in a shape), constant (environment), envmap (latitude-longitude .exr / .pfm / .hdr; filename, scale, toWorld = rotation)
+  emitters    point (position or toWorld, intensity), spot (toWorld, intensity, cutoffAngle, beamWidth; no texture), directional (direction or
+              toWorld without scale, irradiance): SceneDesc.delta_emitters, samplingWeight 1 only;
+              area (nested in a shape), constant (environment), envmap (latitude-longitude .exr / .pfm / .hdr; filename, scale, toWorld = rotation)
   values      <spectrum>, <rgb>, <srgb>, <blackbody> (spectrum.py), <transform> of translate / rotate / scale / lookAt / matrix,
               <default name value> and $name substitution (mitsuba -D, mitsuba.cpp:58-87)
 
@@ -618,6 +620,59 @@ def _has_scale(m):
     return False
 
 
+def inverse3(m):
+    """Inverse of the upper 3x3 of `m` by cofactors in double, rounded to float (host/scene_xml.h inverse3: the same operations)"""
+    a, b, c, d, e, f, g, h, i = (float(m[r][k]) for r in range(3) for k in range(3))
+    det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g)
+    return np.array([(e * i - f * h) / det, (c * h - b * i) / det, (b * f - c * e) / det, (f * g - d * i) / det, (a * i - c * g) / det,
+                     (c * d - a * f) / det, (d * h - e * g) / det, (b * g - a * h) / det, (a * e - b * d) / det], np.float64).astype(f32)
+
+
+def parse_delta_emitter(em, sub, colour):
+    """<emitter type="point" | "spot" | "directional"> (mitsuba/src/emitters/point.cpp:57-69, spot.cpp:68-94, directional.cpp:55-73) → a
+    SceneDesc.delta_emitters dict (bindings.DeltaEmitter).  `colour` reads a spectrum property (default 1: the loader's D65)."""
+    t = em.get("type")
+    ep = _props(em, sub)
+    for c in em:
+        if c.tag == "vector":
+            ep[c.get("name")] = tuple(float(sub(c.get(k, "0"))) for k in "xyz")
+    tw = next((c for c in em if c.tag == "transform" and c.get("name", "toWorld") == "toWorld"), None)
+    m = _transform(tw, sub) if tw is not None else np.eye(4, dtype=f32)
+    if float(ep.get("samplingWeight", 1.0)) != 1.0:
+        raise SceneError("%s emitter: a samplingWeight other than 1 is not supported" % t)
+    if t == "point":
+        if "position" in ep and tw is not None:
+            raise SceneError("point emitter: only one of the parameters 'position' and 'toWorld' can be used")
+        pos = ep["position"] if "position" in ep else (m[0, 3], m[1, 3], m[2, 3])
+        return dict(type="point", intensity=tuple(float(v) for v in colour(em, "intensity", 1.0)), position=tuple(float(f32(v)) for v in pos))
+    if t == "spot":
+        if any(c.get("name") == "texture" or c.tag == "texture" for c in em):
+            raise SceneError("spot emitter: a projection 'texture' is not supported")
+        rad = f32(f32(math.pi) / f32(180))  # degToRad, util.h
+        cutoff_deg = f32(ep.get("cutoffAngle", 20.0))
+        beam_deg = f32(ep["beamWidth"]) if "beamWidth" in ep else f32(f32(cutoff_deg * f32(3)) / f32(4))
+        cutoff, beam = f32(cutoff_deg * rad), f32(beam_deg * rad)
+        if cutoff < beam:
+            raise SceneError("spot emitter: cutoffAngle must not be smaller than beamWidth")
+        if not (0 < beam and cutoff_deg < 90):
+            raise SceneError("spot emitter: the angles must satisfy 0 < beamWidth <= cutoffAngle < 90 degrees")
+        return dict(type="spot", intensity=tuple(float(v) for v in colour(em, "intensity", 1.0)), position=(float(m[0, 3]), float(m[1, 3]), float(m[2, 3])),
+                    to_local=[float(v) for v in inverse3(m)], cutoff_angle=float(cutoff), beam_width=float(beam))
+    if "direction" in ep and tw is not None:
+        raise SceneError("directional emitter: only one of the parameters 'direction' and 'toWorld' can be used at a time")
+    if "direction" in ep:
+        x, y, z = (f32(v) for v in ep["direction"])
+        ln = f32(np.sqrt(f32(f32(f32(x * x) + f32(y * y)) + f32(z * z))))
+        if not ln > 0:
+            raise SceneError("directional emitter: 'direction' is zero")
+        d = (float(f32(x / ln)), float(f32(y / ln)), float(f32(z / ln)))
+    else:
+        if _has_scale(m):
+            raise SceneError("directional emitter: scale factors in the emitter-to-world transformation are not allowed")
+        d = (float(m[0, 2]), float(m[1, 2]), float(m[2, 2]))
+    return dict(type="directional", intensity=tuple(float(v) for v in colour(em, "irradiance", 1.0)), direction=d)
+
+
 def load_scene(path, defines=None, strict=True, width=None, height=None, data_dir=None, mitsuba_src=None):
     """Parse `path` → (SceneDesc, integrator properties for ppg_create, info dict).
 
@@ -976,7 +1031,11 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             if b is not top and b.get("id") and b.get("id") not in by_id:
                 by_id[b.get("id")] = intern(make_bsdf(b))
     environment = envmap = None
+    delta_emitters = []
     for em in root.findall("emitter"):
+        if em.get("type") in ("point", "spot", "directional"):
+            delta_emitters.append(parse_delta_emitter(em, sub, colour))
+            continue
         if em.get("type") == "constant" and environment is None and envmap is None:
             environment = tuple(float(v) for v in colour(em, "radiance", 1.0))
             continue
@@ -1028,8 +1087,8 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         if not strict:
             warnings.append("emitter %r skipped (not supported)" % em.get("type"))
             continue
-        raise SceneError("emitter type %r is not supported (area emitters on shapes and one `constant`, `envmap` or `sunsky` environment emitter; "
-                         "SURVEY.md §8 f2)" % em.get("type"))
+        raise SceneError("emitter type %r is not supported (area emitters on shapes, `point`, `spot` and `directional` emitters, and one "
+                         "`constant`, `envmap` or `sunsky` environment emitter; SURVEY.md §8 f2)" % em.get("type"))
 
     # ---- shapes
     collected, emitters, spheres = [], [], []
@@ -1167,7 +1226,10 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         pos, idx, tmat, tem = [np.zeros((0, 3), f32)], [np.zeros((0, 3), np.uint32)], [np.zeros(0, np.uint32)], [np.zeros(0, np.int32)]
     desc = SceneDesc(np.concatenate(pos).astype(f32), np.concatenate(idx).astype(np.uint32), np.concatenate(tmat), np.concatenate(tem),
                      materials, emitters, camera, normals, environment, np.stack(rt_slices).astype(f32) if rt_slices else None, spheres, envmap,
-                     np.concatenate(uvl).astype(f32) if any_uvs else None, textures, rfilter, lens)
+                     np.concatenate(uvl).astype(f32) if any_uvs else None, textures, rfilter, lens, delta_emitters)
+    if delta_emitters and str(props.get("nee", "never")) != "always":
+        warnings.append("point / spot / directional emitters are reached by next-event estimation only: with nee = %s they contribute nothing in "
+                        "every iteration that runs without it (as in Mitsuba)" % props.get("nee", "never"))
     info["warnings"] = warnings
     return desc, props, info
 
@@ -1282,6 +1344,19 @@ def save_scene_xml(desc, props, directory, name="scene"):
         if em >= 0:
             out.append('\t\t<emitter type="area"><rgb name="radiance" value="%s"/></emitter>' % c(desc.emitters[em]["radiance"]))
         out.append('\t</shape>')
+    for e in getattr(desc, "delta_emitters", None) or []:  # (the loader turns the values back into the same struct up to rounding)
+        xyz = lambda v: 'x="%r" y="%r" z="%r"' % tuple(float(t) for t in v)  # noqa: E731
+        if e["type"] == "point":
+            out.append('\t<emitter type="point"><point name="position" %s/><rgb name="intensity" value="%s"/></emitter>' % (xyz(e["position"]), c(e["intensity"])))
+        elif e["type"] == "directional":
+            out.append('\t<emitter type="directional"><vector name="direction" %s/><rgb name="irradiance" value="%s"/></emitter>' % (xyz(e["direction"]), c(e["intensity"])))
+        else:
+            m = np.eye(4)
+            m[:3, :3] = np.linalg.inv(np.asarray(e["to_local"], np.float64).reshape(3, 3))
+            m[:3, 3] = e["position"]
+            out.append('\t<emitter type="spot"><transform name="toWorld"><matrix value="%s"/></transform><float name="cutoffAngle" value="%r"/>'
+                       '<float name="beamWidth" value="%r"/><rgb name="intensity" value="%s"/></emitter>'
+                       % (" ".join(repr(float(x)) for x in m.reshape(-1)), math.degrees(e["cutoff_angle"]), math.degrees(e["beam_width"]), c(e["intensity"])))
     if getattr(desc, "environment", None) is not None:
         out.append('\t<emitter type="constant"><rgb name="radiance" value="%s"/></emitter>' % c(desc.environment))
     if getattr(desc, "envmap", None) is not None:

@@ -17,7 +17,7 @@ import numpy as np
 
 class SceneDesc:
     def __init__(self, positions, indices, tri_material, tri_emitter, materials, emitters, camera, normals=None, environment=None, rtrans=None, spheres=None, envmap=None,
-                 texcoords=None, textures=None, rfilter=None, lens=None):
+                 texcoords=None, textures=None, rfilter=None, lens=None, delta_emitters=None):
         self.positions, self.indices = positions, indices
         self.tri_material, self.tri_emitter = tri_material, tri_emitter
         self.materials, self.emitters, self.camera, self.normals = materials, emitters, camera, normals
@@ -30,6 +30,8 @@ class SceneDesc:
                                         # to them by index: material["texture"] (diffuse reflectance), material["bump"] (bumpmap displacement)
         self.rfilter = rfilter          # None (the default box) or the film's reconstruction filter: dict (bindings.RFilter)
         self.lens = lens                # None (pinhole) or a thin lens: {"aperture_radius", "focus_distance"} (bindings.Lens)
+        self.delta_emitters = list(delta_emitters or [])  # point / spot / directional emitters: dicts (bindings.DeltaEmitter); they are numbered
+                                                          # after the area emitters and before the environment emitter
 
     @property
     def n_triangles(self):
@@ -38,20 +40,22 @@ class SceneDesc:
 
 def save_scene(desc, path):
     """Write the flat binary scene read by host/ppg_render.cpp: "PPGS", 6 x uint32 {n_vertices, n_triangles, n_materials,
-    n_emitters, has_normals, blocks (bit 0: environment, bit 1: rtrans, bit 2: spheres, bit 3: envmap, bit 4: texcoords, bit 5: textures, bit 6: rfilter, bit 7: lens)}, then positions, [normals], indices, tri_material,
+    n_emitters, has_normals, blocks (bit 0: environment, bit 1: rtrans, bit 2: spheres, bit 3: envmap, bit 4: texcoords, bit 5: textures, bit 6: rfilter, bit 7: lens, bit 8: delta emitters)}, then positions, [normals], indices, tri_material,
     tri_emitter, materials (ppg_material, 80 bytes each), emitters (4 floats), camera (ppg_camera), [environment radiance:
     3 floats], [rtrans: 2 x uint32 {n_slices, samples}, then n_slices x (samples + 1) floats], [spheres: uint32 n, then n x ppg_sphere
     (64 bytes)], [envmap: 2 x uint32 {width, height}, float scale, 9 floats to_world, then height x width x 3 floats], [texcoords: n_vertices x 2
     floats], [textures: uint32 n, then per texture 2 x uint32 {width, height}, 4 floats uv scale / offset, 3 x int32 {wrap_u, wrap_v, nearest}, uint32
     storage (0: float32 RGB, 1: uint8 sRGB-encoded RGB — decoded on load with the exact 256-entry table of the 8-bit → float conversion), pixels],
     [rfilter: ppg_rfilter, 24 bytes {int32 type, float radius, stddev, B, C, int32 lobes} — only for a filter other than the default box],
-    [lens: ppg_lens, 2 floats {aperture_radius, focus_distance} — only for a thin-lens camera]."""
+    [lens: ppg_lens, 2 floats {aperture_radius, focus_distance} — only for a thin-lens camera],
+    [delta emitters: uint32 n, then n x ppg_delta_emitter (84 bytes) — only when there are point / spot / directional emitters]."""
     import struct
-    from .bindings import Lens, RFilter
+    from .bindings import DeltaEmitter, Lens, RFilter
     rf = RFilter.from_dict(getattr(desc, "rfilter", None))
     rf = rf if rf.as_dict() is not None else None
     lens = getattr(desc, "lens", None)
     lens = None if lens is None else Lens.from_dict(lens)
+    delta = [DeltaEmitter.from_dict(d) for d in (getattr(desc, "delta_emitters", None) or [])]
     pos = np.ascontiguousarray(desc.positions, np.float32)
     idx = np.ascontiguousarray(desc.indices, np.uint32)
     with open(path, "wb") as f:
@@ -62,7 +66,7 @@ def save_scene(desc, path):
         f.write(struct.pack("<6I", pos.shape[0], idx.shape[0], len(desc.materials), len(desc.emitters), 0 if desc.normals is None else 1,
                             (0 if env is None else 1) | (0 if rt is None else 2) | (4 if getattr(desc, "spheres", None) else 0) | (8 if getattr(desc, "envmap", None) is not None else 0)
                             | (16 if getattr(desc, "texcoords", None) is not None else 0) | (32 if getattr(desc, "textures", None) else 0) | (0 if rf is None else 64)
-                            | (0 if lens is None else 128)))
+                            | (0 if lens is None else 128) | (256 if delta else 0)))
         f.write(pos.tobytes())
         if desc.normals is not None:
             f.write(np.ascontiguousarray(desc.normals, np.float32).tobytes())
@@ -111,6 +115,10 @@ def save_scene(desc, path):
             f.write(bytes(rf))
         if lens is not None:
             f.write(bytes(lens))
+        if delta:
+            f.write(struct.pack("<I", len(delta)))
+            for d in delta:
+                f.write(bytes(d))
 
 
 def srgb8_table():
@@ -210,13 +218,22 @@ def load_scene_file(path):
     if blocks & 128:
         from .bindings import Lens
         lens = Lens.from_buffer_copy(bytes(take(np.uint8, C_LENS_BYTES))).as_dict()
+    delta = []
+    if blocks & 256:
+        from .bindings import DeltaEmitter
+        for _ in range(int(take(np.uint32, 1)[0])):
+            e = DeltaEmitter.from_buffer_copy(bytes(take(np.uint8, C_DELTA_EMITTER_BYTES)))
+            if not 0 <= e.type < len(DeltaEmitter.TYPES):
+                raise ValueError("%s: unknown delta emitter type %d" % (path, e.type))
+            delta.append(e.as_dict())
     if off[0] != len(buf):
         raise ValueError("%s: trailing bytes" % path)
-    return SceneDesc(pos, idx, tm, te, mats, ems, cam, nrm, env, rt, spheres, envmap, uvs, textures, rfilter, lens)
+    return SceneDesc(pos, idx, tm, te, mats, ems, cam, nrm, env, rt, spheres, envmap, uvs, textures, rfilter, lens, delta)
 
 
 C_RFILTER_BYTES = 24  # sizeof(ppg_rfilter)
 C_LENS_BYTES = 8      # sizeof(ppg_lens)
+C_DELTA_EMITTER_BYTES = 84  # sizeof(ppg_delta_emitter)
 
 
 def _sample_to_camera(fov_deg, fov_axis, near, far, width, height):
