@@ -20,6 +20,30 @@ extern "C" {
 int ppg_debug_build_bvh(const float *positions, const uint32_t *indices, uint32_t n_triangles, float pad_abs, int32_t max_leaf,
                         void *nodes_out, uint32_t nodes_cap, uint32_t *n_nodes, uint32_t *order_out);
 
+/* Host only: the quality of the tree ppg_debug_build_bvh returns, measured on the finished QUANTISED nodes with every child box decoded
+   as the kernels decode it (origin + byte * cell).  sa_* are the expected-step figures of the surface area heuristic for a ray that
+   enters the root's box: sa_interior = sum of area(child box) / area(root) over interior children (node steps below the root's own),
+   sa_leaf the same over leaf children (leaf visits), sa_tris = sum of area / area(root) * triangles over leaf children (triangle tests).
+   depth = 4-wide levels on the longest path; build_seconds = wall time of the builder alone. */
+struct ppg_bvh_stats {
+    uint32_t n_nodes, n_leaves, depth, n_binary_nodes;
+    uint32_t leaf_hist[9]; /* [k] = leaves of k triangles */
+    uint32_t reserved;
+    double sa_interior, sa_leaf, sa_tris;
+    double build_seconds;
+};
+int ppg_debug_bvh_stats(const float *positions, const uint32_t *indices, uint32_t n_triangles, float pad_abs, int32_t max_leaf,
+                        struct ppg_bvh_stats *out);
+
+/* Host only: ordered closest-hit traversal of that tree on the CPU, in the kernels' float arithmetic (csrc/ppg_device.h bvh4_children,
+   tri_hit_regs, trace_slice_bvh4: nearest child first, the others pushed farthest first, every test culled against the best hit so far,
+   ties by original index).  rays = n_rays x { ox, oy, oz, mint, dx, dy, dz, maxt } (mint is taken as it stands).  Per ray: t_out (+inf
+   without a hit), orig_out (original triangle index, -1 without), steps_out (node steps), tests_out (triangle tests); any may be NULL.
+   *max_stack (may be NULL) receives the deepest traversal stack of all rays (the kernels' holds 48 entries). */
+int ppg_debug_bvh_trace(const float *positions, const uint32_t *indices, uint32_t n_triangles, float pad_abs, int32_t max_leaf,
+                        const float *rays, uint32_t n_rays, float *t_out, int32_t *orig_out, uint32_t *steps_out, uint32_t *tests_out,
+                        uint32_t *max_stack);
+
 /* Host only (no GPU is touched): the discretised filter ppg_set_rfilter would use — table[32] = ReconstructionFilter::m_values (31
    normalised samples and a 0), *radius = m_radius, *border = m_borderSize (rfilter.cpp:37-55).  Returns what ppg_set_rfilter would for
    the filter's own checks (PPG_ERR_INVALID for bad parameters or a border above 3). */

@@ -229,12 +229,48 @@ struct BvhBuilder {
         return b;
     }
 
-    // returns (ref, n): n > 0 leaf [ref, ref+n), n == 0 interior node ref
-    void build(int first, int count, int &ref, int &n, Box &box) {
-        box = boundsOf(first, count);
-        if (count <= maxLeaf) { ref = first; n = count; return; }
-        Box cb = empty();
-        for (int i = first; i < first + count; ++i) grow(cb, &cent[3 * order[i]], &cent[3 * order[i]]);
+    // ---- the binary tree: one triangle per leaf; which subtrees become leaves of up to maxLeaf triangles is decided by collapse() ----
+    struct N2 {
+        float lo[3], hi[3];  // unpadded
+        int parent, c0, c1;  // c0 < 0: a leaf
+        int tri;             // leaf: its triangle
+        int first, count;    // range in `order` (layout())
+    };
+    std::vector<N2> t2;
+    static float areaN(const N2 &n) { const float d[3] = {n.hi[0] - n.lo[0], n.hi[1] - n.lo[1], n.hi[2] - n.lo[2]}; return 2 * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0]); }
+    static float areaU(const N2 &p, const N2 &q) {
+        float d[3];
+        for (int a = 0; a < 3; ++a) d[a] = std::max(p.hi[a], q.hi[a]) - std::min(p.lo[a], q.lo[a]);
+        return 2 * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0]);
+    }
+    // Ranges of up to SWEEP triangles: the exact SAH — all 3 (count - 1) object partitions along the sorted centroids; above: 16 bins per axis
+    // (the sweep matters in the lower levels, where a bin holds a handful of triangles; higher up the bins see the same planes.  On KITCHEN
+    // thresholds of 0 / 64 / 256 trace 10.8 / 10.0 - 10.6 / 10.7 node steps per ray after the re-optimisation: profiles/bvh_quality.json)
+    static constexpr int SWEEP = 64;
+    std::vector<uint32_t> swCur, swBest;
+    std::vector<float> swArea;
+    int sweepSplit(int first, int count) {
+        swCur.resize((size_t)count); swBest.resize((size_t)count); swArea.resize((size_t)count);
+        float bestCost = INFINITY; int bestI = -1;
+        for (int a = 0; a < 3; ++a) {
+            std::copy(order.begin() + first, order.begin() + first + count, swCur.begin());
+            std::sort(swCur.begin(), swCur.end(), [&](uint32_t x, uint32_t y) { const float cx = cent[3 * x + a], cy = cent[3 * y + a]; return cx < cy || (cx == cy && x < y); });
+            Box acc = empty();
+            for (int i = count - 1; i >= 1; --i) { grow(acc, &bmin[3 * swCur[i]], &bmax[3 * swCur[i]]); swArea[i] = area(acc); }
+            acc = empty();
+            bool better = false;
+            for (int i = 1; i < count; ++i) {
+                grow(acc, &bmin[3 * swCur[i - 1]], &bmax[3 * swCur[i - 1]]);
+                const float cost = area(acc) * i + swArea[i] * (count - i);
+                if (cost < bestCost) { bestCost = cost; bestI = i; better = true; }
+            }
+            if (better) swBest.swap(swCur);
+        }
+        if (bestI < 0) return first + count / 2;  // (areas not finite)
+        std::copy(swBest.begin(), swBest.end(), order.begin() + first);
+        return first + bestI;
+    }
+    int binnedSplit(int first, int count, const Box &cb) {
         int bestAxis = -1, bestSplit = -1; float bestCost = INFINITY;
         const int NB = 16;
         for (int a = 0; a < 3; ++a) {
@@ -256,65 +292,227 @@ struct BvhBuilder {
                 if (cost < bestCost) { bestCost = cost; bestAxis = a; bestSplit = k; }
             }
         }
-        int mid;
-        if (bestAxis < 0) {
-            mid = first + count / 2;
-        } else {
-            float ext = cb.hi[bestAxis] - cb.lo[bestAxis], lo = cb.lo[bestAxis];
-            auto it = std::partition(order.begin() + first, order.begin() + first + count, [&](uint32_t t) {
-                int k = std::min(NB - 1, (int)((cent[3 * t + bestAxis] - lo) / ext * NB));
-                return k < bestSplit;
-            });
-            mid = (int)(it - order.begin());
-            if (mid == first || mid == first + count) mid = first + count / 2;
+        if (bestAxis < 0) return first + count / 2;
+        float ext = cb.hi[bestAxis] - cb.lo[bestAxis], lo = cb.lo[bestAxis];
+        auto it = std::partition(order.begin() + first, order.begin() + first + count, [&](uint32_t t) {
+            int k = std::min(NB - 1, (int)((cent[3 * t + bestAxis] - lo) / ext * NB));
+            return k < bestSplit;
+        });
+        int mid = (int)(it - order.begin());
+        if (mid == first || mid == first + count) mid = first + count / 2;
+        return mid;
+    }
+    int build2(int first, int count, int parent) {
+        const int me = (int)t2.size();
+        t2.emplace_back();
+        {
+            N2 &n = t2[(size_t)me];
+            const Box b = boundsOf(first, count);
+            for (int a = 0; a < 3; ++a) { n.lo[a] = b.lo[a]; n.hi[a] = b.hi[a]; }
+            n.parent = parent; n.c0 = n.c1 = -1; n.tri = (int)order[first]; n.first = first; n.count = count;
         }
-        int me = (int)nodes.size();
-        nodes.emplace_back();
-        int r0, n0, r1, n1; Box b0, b1;
-        build(first, mid - first, r0, n0, b0);
-        build(mid, first + count - mid, r1, n1, b1);
-        BvhNode &nd = nodes[me];
-        for (int a = 0; a < 3; ++a) { nd.lo0[a] = b0.lo[a] - pad; nd.hi0[a] = b0.hi[a] + pad; nd.lo1[a] = b1.lo[a] - pad; nd.hi1[a] = b1.hi[a] + pad; }
-        nd.c0 = r0; nd.n0 = n0; nd.c1 = r1; nd.n1 = n1;
-        ref = me; n = 0;
+        if (count == 1) return me;
+        Box cb = empty();
+        for (int i = first; i < first + count; ++i) grow(cb, &cent[3 * order[i]], &cent[3 * order[i]]);
+        int mid;
+        if (!(cb.hi[0] > cb.lo[0]) && !(cb.hi[1] > cb.lo[1]) && !(cb.hi[2] > cb.lo[2])) mid = first + count / 2;  // coincident centroids: median
+        else mid = count <= SWEEP ? sweepSplit(first, count) : binnedSplit(first, count, cb);
+        const int l = build2(first, mid - first, me), r = build2(mid, first + count - mid, me);
+        t2[(size_t)me].c0 = l; t2[(size_t)me].c1 = r;
+        return me;
     }
 
-    // ---- collapse the binary tree to 4-wide nodes (children = the 2..4 descendants obtained by repeatedly opening
-    // the interior child with the largest surface area) ----
-    std::vector<Bvh4Node> nodes4;
-    struct Ref { int ref, n; float lo[3], hi[3]; };
-    static float areaRef(const Ref &r) { float d[3] = {r.hi[0] - r.lo[0], r.hi[1] - r.lo[1], r.hi[2] - r.lo[2]}; return 2 * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0]); }
-    void childrenOf(int node2, Ref out[2]) const {
-        const BvhNode &nd = nodes[node2];
-        out[0].ref = nd.c0; out[0].n = nd.n0; out[1].ref = nd.c1; out[1].n = nd.n1;
-        for (int a = 0; a < 3; ++a) { out[0].lo[a] = nd.lo0[a]; out[0].hi[a] = nd.hi0[a]; out[1].lo[a] = nd.lo1[a]; out[1].hi[a] = nd.hi1[a]; }
-    }
-    int make4(int node2) {
-        Ref ch[4]; int m = 2;
-        childrenOf(node2, ch);
-        if (ch[1].n < 0) m = 1;  // single-leaf root
-        while (m < 4) {
-            int pick = -1; float best = -1;
-            for (int k = 0; k < m; ++k) if (ch[k].n == 0 && areaRef(ch[k]) > best) { best = areaRef(ch[k]); pick = k; }
-            if (pick < 0) break;
-            Ref two[2]; childrenOf(ch[pick].ref, two);
-            ch[pick] = two[0]; ch[m++] = two[1];
+    // ---- insertion-based re-optimisation of the binary tree (Bittner, Hapala, Havran: Fast insertion-based optimization of bounding volume
+    // hierarchies, CGF 2013).  A top-down build never revisits a split: a large triangle (a wall, a table top) inflates every box above it.
+    // Per batch the interior nodes that promise most (large, with a child much smaller than themselves) are taken out one after the other; the two
+    // subtrees below a removed node are put back where a branch-and-bound search finds the least increase of the tree's total surface area.
+    // Deterministic: one thread, a fixed number of batches, every tie broken by the node index — the same scene gives the same tree on every
+    // rank and in every run. ----
+    void refit(int v) {
+        for (; v >= 0; v = t2[(size_t)v].parent) {
+            N2 &n = t2[(size_t)v];
+            const N2 &p = t2[(size_t)n.c0], &q = t2[(size_t)n.c1];
+            bool same = true;
+            for (int a = 0; a < 3; ++a) {
+                const float lo = std::min(p.lo[a], q.lo[a]), hi = std::max(p.hi[a], q.hi[a]);
+                same = same && lo == n.lo[a] && hi == n.hi[a];
+                n.lo[a] = lo; n.hi[a] = hi;
+            }
+            if (same) break;
         }
-        int me = (int)nodes4.size();
+    }
+    void replaceChild(int p, int was, int now) { N2 &n = t2[(size_t)p]; if (n.c0 == was) n.c0 = now; else n.c1 = now; t2[(size_t)now].parent = p; }
+    typedef std::pair<float, int> QEnt;  // (area the ancestors grow by, node)
+    std::vector<QEnt> heap;
+    int findTarget(int x) {
+        auto later = [](const QEnt &p, const QEnt &q) { return p.first > q.first || (p.first == q.first && p.second > q.second); };
+        const float ax = areaN(t2[(size_t)x]);
+        float best = INFINITY; int bestNode = -1;
+        heap.clear();
+        heap.push_back(QEnt(0.0f, 0));
+        while (!heap.empty()) {
+            std::pop_heap(heap.begin(), heap.end(), later);
+            const QEnt e = heap.back();
+            heap.pop_back();
+            if (e.first + ax >= best && bestNode >= 0) break;
+            const N2 &v = t2[(size_t)e.second];
+            const float total = e.first + areaU(v, t2[(size_t)x]);
+            if (e.second != 0 && (total < best || bestNode < 0)) { best = total; bestNode = e.second; }
+            const float below = total - areaN(v);
+            if (v.c0 >= 0 && (below + ax < best || bestNode < 0)) {
+                heap.push_back(QEnt(below, v.c0)); std::push_heap(heap.begin(), heap.end(), later);
+                heap.push_back(QEnt(below, v.c1)); std::push_heap(heap.begin(), heap.end(), later);
+            }
+        }
+        return bestNode;
+    }
+    void insertAt(int x, int spare) {
+        const int b = findTarget(x), bp = t2[(size_t)b].parent;
+        replaceChild(bp, b, spare);
+        N2 &f = t2[(size_t)spare];
+        f.c0 = b; f.c1 = x;
+        t2[(size_t)b].parent = spare; t2[(size_t)x].parent = spare;
+        for (int a = 0; a < 3; ++a) { f.lo[a] = std::min(t2[(size_t)b].lo[a], t2[(size_t)x].lo[a]); f.hi[a] = std::max(t2[(size_t)b].hi[a], t2[(size_t)x].hi[a]); }
+        refit(bp);
+    }
+    bool movable(int n) const { return n > 0 && t2[(size_t)n].c0 >= 0 && t2[(size_t)n].parent > 0; }
+    void reinsert(int n) {
+        const int p = t2[(size_t)n].parent, g = t2[(size_t)p].parent;
+        const int s = t2[(size_t)p].c0 == n ? t2[(size_t)p].c1 : t2[(size_t)p].c0;
+        replaceChild(g, p, s);
+        refit(g);
+        int l = t2[(size_t)n].c0, r = t2[(size_t)n].c1;
+        if (areaN(t2[(size_t)l]) < areaN(t2[(size_t)r])) std::swap(l, r);
+        insertAt(l, n);   // the two nodes the removal set free carry the two subtrees back
+        insertAt(r, p);
+    }
+    // Eight batches, each the most promising 1 % of the interior nodes — fixed numbers, never a clock.  profiles/bvh_quality.json: KITCHEN's
+    // traced node steps per ray are 10.0 - 10.8 for 4 to 40 batches of 1 - 4 % (14.2 without any) while the build grows from 3.2 to 13 s.
+    static constexpr int REOPT_PART = 100, REOPT_BATCHES = 8;
+    void reoptimise() {
+        if (t2.size() < 16) return;
+        std::vector<QEnt> cand;
+        for (int batch = 0; batch < REOPT_BATCHES; ++batch) {
+            cand.clear();
+            for (int v = 1; v < (int)t2.size(); ++v) {
+                if (!movable(v)) continue;
+                const float a = areaN(t2[(size_t)v]), a0 = areaN(t2[(size_t)t2[(size_t)v].c0]), a1 = areaN(t2[(size_t)t2[(size_t)v].c1]);
+                const float tiny = 1e-30f;
+                const float prio = a * (a / std::max(std::min(a0, a1), tiny)) * (a / std::max(0.5f * (a0 + a1), tiny));  // M_AREA M_MIN M_SUM of the paper
+                if (prio == prio) cand.push_back(QEnt(prio, v));
+            }
+            const size_t k = std::min(cand.size(), std::max<size_t>(1, t2.size() / (2 * REOPT_PART)));
+            auto first = [](const QEnt &p, const QEnt &q) { return p.first > q.first || (p.first == q.first && p.second < q.second); };
+            std::partial_sort(cand.begin(), cand.begin() + (long)k, cand.end(), first);
+            for (size_t i = 0; i < k; ++i) if (movable(cand[i].second)) reinsert(cand[i].second);
+        }
+    }
+
+    // leaf order = the tree's depth-first order, so that every subtree's triangles are contiguous (a leaf is a range); `pre` = the nodes
+    // parents first
+    std::vector<int> pre;
+    void layout() {
+        std::vector<uint32_t> fresh;
+        fresh.reserve(order.size());
+        pre.clear(); pre.reserve(t2.size());
+        std::vector<int> stack(1, 0);
+        while (!stack.empty()) {
+            const int v = stack.back();
+            stack.pop_back();
+            pre.push_back(v);
+            N2 &n = t2[(size_t)v];
+            if (n.c0 < 0) { n.first = (int)fresh.size(); n.count = 1; fresh.push_back((uint32_t)n.tri); }
+            else { stack.push_back(n.c1); stack.push_back(n.c0); }
+        }
+        for (size_t i = pre.size(); i-- > 0;) {
+            N2 &n = t2[(size_t)pre[i]];
+            if (n.c0 >= 0) { n.first = t2[(size_t)n.c0].first; n.count = t2[(size_t)n.c0].count + t2[(size_t)n.c1].count; }
+        }
+        order.swap(fresh);
+    }
+
+    // ---- collapse to 4-wide nodes: a dynamic programme over the binary tree, bottom up.  cost[v][k - 1] = the least expected cost of
+    // presenting v's triangles as exactly k children of a 4-wide node; for k = 1 the cheaper of ONE LEAF with all its triangles (where they are
+    // at most maxLeaf) and a 4-wide node of its own over the best cut of 2..4 descendants.  A child costs its box's area times C_NODE (an
+    // interior child: one more node step) or C_LEAF + C_TRI per triangle.  The constants are in node steps of k_trace: a triangle test in
+    // the (ray, triangle)-pair compaction costs about a quarter of a node step, a leaf visit (pop, vote) about as much once ----
+    static constexpr double C_NODE = 1.0, C_LEAF = 0.25, C_TRI = 0.25;
+    struct Cost4 { double k[4]; };
+    std::vector<Cost4> cost;
+    std::vector<unsigned char> asLeaf;
+    double paddedArea(const N2 &n) const {
+        const double d[3] = {(double)n.hi[0] - n.lo[0] + 2.0 * pad, (double)n.hi[1] - n.lo[1] + 2.0 * pad, (double)n.hi[2] - n.lo[2] + 2.0 * pad};
+        return 2 * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0]);
+    }
+    void collapse() {
+        cost.resize(t2.size()); asLeaf.assign(t2.size(), 0);
+        for (size_t i = pre.size(); i-- > 0;) {
+            const int v = pre[i];
+            const N2 &n = t2[(size_t)v];
+            const double A = paddedArea(n);
+            Cost4 &c = cost[(size_t)v];
+            if (n.c0 < 0) { c.k[0] = A * (C_LEAF + C_TRI); c.k[1] = c.k[2] = c.k[3] = INFINITY; asLeaf[(size_t)v] = 1; continue; }
+            const Cost4 &l = cost[(size_t)n.c0], &r = cost[(size_t)n.c1];
+            double cut = INFINITY;
+            for (int k = 2; k <= 4; ++k) {
+                double best = INFINITY;
+                for (int j = 1; j < k; ++j) best = std::min(best, l.k[j - 1] + r.k[k - j - 1]);
+                c.k[k - 1] = best;
+                cut = std::min(cut, best);
+            }
+            const double node = A * C_NODE + cut, leaf = n.count <= maxLeaf ? A * (C_LEAF + C_TRI * n.count) : INFINITY;
+            asLeaf[(size_t)v] = leaf <= node;
+            c.k[0] = std::min(leaf, node);
+        }
+    }
+    void cut4(int v, int k, int *ch, int &m) const {  // the k descendants of v that cost[v][k - 1] stands for
+        if (k == 1) { ch[m++] = v; return; }
+        const N2 &n = t2[(size_t)v];
+        const Cost4 &l = cost[(size_t)n.c0], &r = cost[(size_t)n.c1];
+        int bj = 1;
+        for (int j = 2; j < k; ++j) if (l.k[j - 1] + r.k[k - j - 1] < l.k[bj - 1] + r.k[k - bj - 1]) bj = j;
+        cut4(n.c0, bj, ch, m);
+        cut4(n.c1, k - bj, ch, m);
+    }
+    std::vector<Bvh4Node> nodes4;
+    int emit4(int v) {
+        int ch[4], m = 0, bk = 2;
+        for (int k = 3; k <= 4; ++k) if (cost[(size_t)v].k[k - 1] < cost[(size_t)v].k[bk - 1]) bk = k;
+        cut4(v, bk, ch, m);
+        const int me = (int)nodes4.size();
         nodes4.emplace_back();
         Bvh4Node nd;
         for (int k = 0; k < 4; ++k) {
             if (k < m) {
-                nd.lox[k] = ch[k].lo[0]; nd.loy[k] = ch[k].lo[1]; nd.loz[k] = ch[k].lo[2];
-                nd.hix[k] = ch[k].hi[0]; nd.hiy[k] = ch[k].hi[1]; nd.hiz[k] = ch[k].hi[2];
-                if (ch[k].n > 0) nd.child[k] = ~((ch[k].ref << 3) | (ch[k].n - 1));
-                else nd.child[k] = make4(ch[k].ref);
+                const N2 &c = t2[(size_t)ch[k]];
+                nd.lox[k] = c.lo[0] - pad; nd.loy[k] = c.lo[1] - pad; nd.loz[k] = c.lo[2] - pad;
+                nd.hix[k] = c.hi[0] + pad; nd.hiy[k] = c.hi[1] + pad; nd.hiz[k] = c.hi[2] + pad;
+                if (asLeaf[(size_t)ch[k]]) nd.child[k] = ~((c.first << 3) | (c.count - 1));
+                else nd.child[k] = emit4(ch[k]);
             } else {
                 nd.lox[k] = nd.loy[k] = nd.loz[k] = 0; nd.hix[k] = nd.hiy[k] = nd.hiz[k] = 0; nd.child[k] = PPG_BVH4_EMPTY;
             }
             nd.pad[k] = 0;
         }
-        nodes4[me] = nd;
+        nodes4[(size_t)me] = nd;
+        return me;
+    }
+    // the binary node array (BvhNode) with the same leaves
+    int emit2(int v) {
+        const int me = (int)nodes.size();
+        nodes.emplace_back();
+        BvhNode nd;
+        const int ch[2] = {t2[(size_t)v].c0, t2[(size_t)v].c1};
+        int ref[2], cnt[2];
+        for (int k = 0; k < 2; ++k) {
+            const N2 &c = t2[(size_t)ch[k]];
+            if (asLeaf[(size_t)ch[k]]) { ref[k] = c.first; cnt[k] = c.count; }
+            else { ref[k] = emit2(ch[k]); cnt[k] = 0; }
+            float *lo = k ? nd.lo1 : nd.lo0, *hi = k ? nd.hi1 : nd.hi0;
+            for (int a = 0; a < 3; ++a) { lo[a] = c.lo[a] - pad; hi[a] = c.hi[a] + pad; }
+        }
+        nd.c0 = ref[0]; nd.n0 = cnt[0]; nd.c1 = ref[1]; nd.n1 = cnt[1];
+        nodes[(size_t)me] = nd;
         return me;
     }
 
@@ -432,7 +630,6 @@ struct BvhBuilder {
         }
         nodes.clear();
         nodes.reserve(nTris);
-        int ref, n; Box b;
         nodes.emplace_back();  // root placeholder, must be an interior node
         if (nTris == 0) {  // spheres only: one node without children
             nodes4.assign(1, Bvh4Node{});
@@ -440,21 +637,55 @@ struct BvhBuilder {
             quantise();
             return;
         }
-        if (nTris <= 4) {
+        if (nTris <= 4) {  // one node with one leaf
             BvhNode &nd = nodes[0];
             Box bb = boundsOf(0, (int)nTris);
             for (int a = 0; a < 3; ++a) { nd.lo0[a] = bb.lo[a] - pad; nd.hi0[a] = bb.hi[a] + pad; nd.lo1[a] = 0; nd.hi1[a] = 0; }
             nd.c0 = 0; nd.n0 = (int)nTris; nd.c1 = 0; nd.n1 = -1;
-            nodes4.clear(); make4(0); quantise();
+            Bvh4Node n4{};
+            for (int k = 0; k < 4; ++k) n4.child[k] = PPG_BVH4_EMPTY;
+            n4.lox[0] = nd.lo0[0]; n4.loy[0] = nd.lo0[1]; n4.loz[0] = nd.lo0[2]; n4.hix[0] = nd.hi0[0]; n4.hiy[0] = nd.hi0[1]; n4.hiz[0] = nd.hi0[2];
+            n4.child[0] = ~((0 << 3) | ((int)nTris - 1));
+            nodes4.assign(1, n4);
+            quantise();
             return;
         }
         nodes.pop_back();
-        build(0, (int)nTris, ref, n, b);  // nTris > 4 ⇒ root is interior and lands at index 0
-        nodes4.clear(); nodes4.reserve(nodes.size() / 2 + 1);
-        make4(0);
+        t2.clear(); t2.reserve(2 * (size_t)nTris);
+        build2(0, (int)nTris, -1);  // nTris > 4 ⇒ the root is interior
+        reoptimise();
+        layout();
+        collapse();
+        nodes4.clear(); nodes4.reserve(t2.size() / 4 + 1);
+        emit4(0);
+        emit2(0);
         quantise();
     }
 };
+
+// TriAccel::load (triaccel.h:62-97), same float operations as the oracle's: the three words of a triangle's record (tri_hit_regs), orig in a2.w
+static void triAccelLoad(const float *A, const float *B, const float *C, int orig, float4 out[3]) {
+    static const int waldModulo[4] = {1, 2, 0, 1};
+    const float b[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]}, c[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
+    const float N[3] = {c[1] * b[2] - c[2] * b[1], c[2] * b[0] - c[0] * b[2], c[0] * b[1] - c[1] * b[0]};
+    int kk = 0;
+    for (int j = 0; j < 3; j++) if (ppg_abs(N[j]) > ppg_abs(N[kk])) kk = j;
+    const int u = waldModulo[kk], v = waldModulo[kk + 1];
+    const float n_k = N[kk], denom = b[u] * c[v] - b[v] * c[u];
+    float n_u = 0, n_v = 0, n_d = 0, a_u = 0, a_v = 0, b_nu = 0, b_nv = 0, c_nu = 0, c_nv = 0;
+    if (denom == 0) {
+        kk = 3;
+    } else {
+        n_u = N[u] / n_k; n_v = N[v] / n_k;
+        n_d = (A[0] * N[0] + A[1] * N[1] + A[2] * N[2]) / n_k;
+        b_nu = b[u] / denom; b_nv = -b[v] / denom;
+        a_u = A[u]; a_v = A[v];
+        c_nu = c[v] / denom; c_nv = -c[u] / denom;
+    }
+    out[0] = make_float4(n_u, n_v, n_d, __builtin_bit_cast(float, kk));
+    out[1] = make_float4(a_u, a_v, b_nu, b_nv);
+    out[2] = make_float4(c_nu, c_nv, 0.0f, __builtin_bit_cast(float, orig));
+}
 
 struct KernelTimer {
     struct Rec { hipEvent_t a, b; int id; uint64_t units; };
@@ -2707,29 +2938,7 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
     if (s->normals) nrm.resize(tris.size());
     for (uint32_t k = 0; k < s->n_triangles; ++k) {
         uint32_t t = bb.order[k];
-        {   // TriAccel::load (triaccel.h:62-97), same float operations as the oracle's
-            const float *A = s->positions + 3 * s->indices[3 * t], *B = s->positions + 3 * s->indices[3 * t + 1], *C = s->positions + 3 * s->indices[3 * t + 2];
-            static const int waldModulo[4] = {1, 2, 0, 1};
-            const float b[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]}, c[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
-            const float N[3] = {c[1] * b[2] - c[2] * b[1], c[2] * b[0] - c[0] * b[2], c[0] * b[1] - c[1] * b[0]};
-            int kk = 0;
-            for (int j = 0; j < 3; j++) if (ppg_abs(N[j]) > ppg_abs(N[kk])) kk = j;
-            const int u = waldModulo[kk], v = waldModulo[kk + 1];
-            const float n_k = N[kk], denom = b[u] * c[v] - b[v] * c[u];
-            float n_u = 0, n_v = 0, n_d = 0, a_u = 0, a_v = 0, b_nu = 0, b_nv = 0, c_nu = 0, c_nv = 0;
-            if (denom == 0) {
-                kk = 3;
-            } else {
-                n_u = N[u] / n_k; n_v = N[v] / n_k;
-                n_d = (A[0] * N[0] + A[1] * N[1] + A[2] * N[2]) / n_k;
-                b_nu = b[u] / denom; b_nv = -b[v] / denom;
-                a_u = A[u]; a_v = A[v];
-                c_nu = c[v] / denom; c_nv = -c[u] / denom;
-            }
-            accel[3 * k + 0] = make_float4(n_u, n_v, n_d, __builtin_bit_cast(float, kk));
-            accel[3 * k + 1] = make_float4(a_u, a_v, b_nu, b_nv);
-            accel[3 * k + 2] = make_float4(c_nu, c_nv, 0.0f, __builtin_bit_cast(float, (int)t));
-        }
+        triAccelLoad(s->positions + 3 * s->indices[3 * t], s->positions + 3 * s->indices[3 * t + 1], s->positions + 3 * s->indices[3 * t + 2], (int)t, &accel[3 * k]);
         for (int v = 0; v < 3; ++v) {
             const float *p = s->positions + 3 * s->indices[3 * t + v];
             float w = v == 0 ? __builtin_bit_cast(float, (int)s->tri_material[t]) : (v == 1 ? __builtin_bit_cast(float, (int)s->tri_emitter[t]) : __builtin_bit_cast(float, (int)t));
@@ -3083,6 +3292,152 @@ int ppg_debug_build_bvh(const float *positions, const uint32_t *indices, uint32_
     *n_nodes = (uint32_t)bb.nodes4q.size();
     if (nodes_out) memcpy(nodes_out, bb.nodes4q.data(), std::min<size_t>(nodes_cap, bb.nodes4q.size()) * sizeof(Bvh4QNode));
     if (order_out) memcpy(order_out, bb.order.data(), (size_t)n_triangles * sizeof(uint32_t));
+    return PPG_OK;
+}
+// child k's box of a quantised node as the kernels' float decode gives it (bvh4q_load, trace_closest4_wave)
+static void decodeChildBox(const Bvh4QNode &q, int k, float lo[3], float hi[3]) {
+    const float s[3] = {BvhBuilder::scaleOf(q.exps & 255u), BvhBuilder::scaleOf((q.exps >> 8) & 255u), BvhBuilder::scaleOf((q.exps >> 16) & 255u)};
+    const float org[3] = {q.ox, q.oy, q.oz};
+    const unsigned int ql[3] = {q.qlox, q.qloy, q.qloz}, qh[3] = {q.qhix, q.qhiy, q.qhiz};
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = org[a] + (float)((ql[a] >> (8 * k)) & 255u) * s[a];
+        hi[a] = org[a] + (float)((qh[a] >> (8 * k)) & 255u) * s[a];
+    }
+}
+int ppg_debug_bvh_stats(const float *positions, const uint32_t *indices, uint32_t n_triangles, float pad_abs, int32_t max_leaf, ppg_bvh_stats *out) {
+    if (!positions || !indices || !out || n_triangles == 0) return PPG_ERR_INVALID;
+    BvhBuilder bb;
+    bb.maxLeaf = std::max(1, std::min(8, (int)max_leaf));
+    const auto t0 = std::chrono::steady_clock::now();
+    bb.run(positions, indices, n_triangles, pad_abs);
+    const auto t1 = std::chrono::steady_clock::now();
+    memset(out, 0, sizeof(*out));
+    out->build_seconds = std::chrono::duration<double>(t1 - t0).count();
+    out->n_nodes = (uint32_t)bb.nodes4q.size();
+    out->n_binary_nodes = (uint32_t)bb.nodes.size();
+    auto areaOf = [](const float lo[3], const float hi[3]) {
+        const double d[3] = {(double)hi[0] - lo[0], (double)hi[1] - lo[1], (double)hi[2] - lo[2]};
+        return d[0] < 0 || d[1] < 0 || d[2] < 0 ? 0.0 : 2 * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0]);
+    };
+    double rootArea = 0;
+    {   // the root has no box of its own: the union of its children's
+        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (int k = 0; k < 4; ++k) {
+            if (bb.nodes4q[0].child[k] == PPG_BVH4_EMPTY) continue;
+            float l[3], h[3];
+            decodeChildBox(bb.nodes4q[0], k, l, h);
+            for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], l[a]); hi[a] = std::max(hi[a], h[a]); }
+        }
+        rootArea = areaOf(lo, hi);
+    }
+    const double inv = rootArea > 0 ? 1.0 / rootArea : 0.0;
+    std::vector<std::pair<int, uint32_t>> stack(1, {0, 1u});
+    while (!stack.empty()) {
+        const std::pair<int, uint32_t> e = stack.back();
+        stack.pop_back();
+        out->depth = std::max(out->depth, e.second);
+        const Bvh4QNode &q = bb.nodes4q[(size_t)e.first];
+        for (int k = 0; k < 4; ++k) {
+            if (q.child[k] == PPG_BVH4_EMPTY) continue;
+            float l[3], h[3];
+            decodeChildBox(q, k, l, h);
+            const double a = areaOf(l, h) * inv;
+            if (q.child[k] >= 0) { out->sa_interior += a; stack.push_back({q.child[k], e.second + 1}); }
+            else {
+                const int cnt = (~q.child[k] & 7) + 1;
+                out->sa_leaf += a; out->sa_tris += a * cnt; out->n_leaves++; out->leaf_hist[cnt]++;
+            }
+        }
+    }
+    return PPG_OK;
+}
+int ppg_debug_bvh_trace(const float *positions, const uint32_t *indices, uint32_t n_triangles, float pad_abs, int32_t max_leaf, const float *rays,
+                        uint32_t n_rays, float *t_out, int32_t *orig_out, uint32_t *steps_out, uint32_t *tests_out, uint32_t *max_stack) {
+    if (!positions || !indices || n_triangles == 0 || (n_rays && !rays)) return PPG_ERR_INVALID;
+    BvhBuilder bb;
+    bb.maxLeaf = std::max(1, std::min(8, (int)max_leaf));
+    bb.run(positions, indices, n_triangles, pad_abs);
+    std::vector<float4> accel(3 * (size_t)n_triangles);
+    for (uint32_t k = 0; k < n_triangles; ++k) {
+        const uint32_t t = bb.order[k];
+        triAccelLoad(positions + 3 * indices[3 * t], positions + 3 * indices[3 * t + 1], positions + 3 * indices[3 * t + 2], (int)t, &accel[3 * (size_t)k]);
+    }
+    auto bits = [](unsigned int u) { float f; memcpy(&f, &u, 4); return f; };
+    uint32_t deepest = 0;
+    std::vector<int> stack;
+    for (uint32_t r = 0; r < n_rays; ++r) {
+        const float *R = rays + 8 * (size_t)r;
+        const float o[3] = {R[0], R[1], R[2]}, d[3] = {R[4], R[5], R[6]}, mint = R[3], maxt = R[7];
+        const float id[3] = {d[0] == 0.0f ? 1e30f : 1.0f / d[0], d[1] == 0.0f ? 1e30f : 1.0f / d[1], d[2] == 0.0f ? 1e30f : 1.0f / d[2]};  // safe_inv
+        float bestT = INFINITY;
+        int bestOrig = 0x7fffffff;
+        bool found = false;
+        uint32_t steps = 0, tests = 0;
+        stack.clear();
+        int cur = 0;
+        for (;;) {
+            if (cur >= 0) {  // bvh4_children
+                ++steps;
+                const Bvh4QNode &q = bb.nodes4q[(size_t)cur];
+                const float tlim = std::min(maxt, bestT);
+                const float org[3] = {q.ox, q.oy, q.oz};
+                const unsigned int ql[3] = {q.qlox, q.qloy, q.qloz}, qh[3] = {q.qhix, q.qhiy, q.qhiz};
+                float os[3], ids[3];
+                for (int a = 0; a < 3; ++a) {
+                    const unsigned int e = (q.exps >> (8 * a)) & 255u;
+                    os[a] = (o[a] - org[a]) * bits((254u - e) << 23);
+                    ids[a] = id[a] * bits(e << 23);
+                }
+                float ts[4]; int cs[4], m = 0;
+                for (int k = 0; k < 4; ++k) {
+                    float n = mint, f = INFINITY;
+                    for (int a = 0; a < 3; ++a) {
+                        const float lo = (float)((ql[a] >> (8 * k)) & 255u), hi = (float)((qh[a] >> (8 * k)) & 255u);
+                        const float tn = ((id[a] < 0 ? hi : lo) - os[a]) * ids[a], tf = ((id[a] < 0 ? lo : hi) - os[a]) * ids[a];
+                        n = std::max(n, tn); f = std::min(f, tf);
+                    }
+                    f = std::min(f * 1.0000008f, tlim);
+                    const bool hit = n <= f && q.child[k] != PPG_BVH4_EMPTY;
+                    ts[k] = hit ? n : INFINITY; cs[k] = q.child[k];
+                    m += hit ? 1 : 0;
+                }
+                auto cswap = [&](int i, int j) { if (ts[i] > ts[j]) { std::swap(ts[i], ts[j]); std::swap(cs[i], cs[j]); } };
+                cswap(0, 1); cswap(2, 3); cswap(0, 2); cswap(1, 3); cswap(1, 2);
+                if (m > 0) {
+                    for (int k = m - 1; k >= 1; --k) stack.push_back(cs[k]);
+                    deepest = std::max<uint32_t>(deepest, (uint32_t)stack.size());
+                    cur = cs[0];
+                    continue;
+                }
+            } else {  // leaf: tri_hit_regs on every triangle
+                const int code = ~cur, first = code >> 3, cnt = (code & 7) + 1;
+                for (int qd = first; qd < first + cnt; ++qd) {
+                    ++tests;
+                    const float4 a0 = accel[3 * (size_t)qd], a1 = accel[3 * (size_t)qd + 1], a2 = accel[3 * (size_t)qd + 2];
+                    int k; memcpy(&k, &a0.w, 4);
+                    if ((unsigned int)k > 2u) continue;
+                    const bool k0 = k == 0, k1 = k == 1;
+                    const float o_u = k0 ? o[1] : (k1 ? o[2] : o[0]), o_v = k0 ? o[2] : (k1 ? o[0] : o[1]), o_k = k0 ? o[0] : (k1 ? o[1] : o[2]);
+                    const float d_u = k0 ? d[1] : (k1 ? d[2] : d[0]), d_v = k0 ? d[2] : (k1 ? d[0] : d[1]), d_k = k0 ? d[0] : (k1 ? d[1] : d[2]);
+                    const float t = (a0.z - o_u * a0.x - o_v * a0.y - o_k) / (d_u * a0.x + d_v * a0.y + d_k);
+                    if (t < mint || t > std::min(maxt, bestT)) continue;
+                    const float hu = o_u + t * d_u - a1.x, hv = o_v + t * d_v - a1.y;
+                    const float u = hv * a1.z + hu * a1.w, v = hu * a2.x + hv * a2.y;
+                    if (!(u >= 0 && v >= 0 && u + v <= 1.0f)) continue;
+                    int orig; memcpy(&orig, &a2.w, 4);
+                    if (!found || t < bestT || (t == bestT && orig < bestOrig)) { bestT = t; bestOrig = orig; found = true; }
+                }
+            }
+            if (stack.empty()) break;
+            cur = stack.back();
+            stack.pop_back();
+        }
+        if (t_out) t_out[r] = found ? bestT : INFINITY;
+        if (orig_out) orig_out[r] = found ? bestOrig : -1;
+        if (steps_out) steps_out[r] = steps;
+        if (tests_out) tests_out[r] = tests;
+    }
+    if (max_stack) *max_stack = deepest;
     return PPG_OK;
 }
 // ReconstructionFilter::configure (rfilter.cpp:37-55) with the eval() of src/rfilters/*.cpp, in the reference's float arithmetic
