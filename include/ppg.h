@@ -133,12 +133,13 @@ typedef struct ppg_material {
     int32_t flags;        /* PPG_MAT_* */
     int32_t rtrans;       /* roughplastic: index of this material's slice in ppg_scene.rtrans; otherwise 0 */
     float opacity[3];     /* PPG_MAT_MASK: opacity (mask.cpp, default 0.5) */
-    uint32_t texture;     /* bits 0..15: 1 + index (ppg_scene.textures) of the bitmap on the diffuse reflectance — `reflectance` of diffuse,
-                             `diffuseReflectance` of plastic / roughplastic — in which case reflectance[] holds the texture's average
+    uint32_t texture;     /* bits 0..15: 1 + index (ppg_scene.textures) of the bitmap on `reflectance` — `reflectance` of diffuse,
+                             `diffuseReflectance` of plastic / roughplastic, `specularReflectance` of conductor / roughconductor / dielectric /
+                             thindielectric / roughdielectric — in which case reflectance[] holds the texture's average
                              (Texture::getAverage, used by the plug-ins' configure() for the component sampling weights, plastic.cpp:191-204);
                              bits 16..31: 1 + index of the displacement texture of a `bumpmap` adapter around this BSDF (bumpmap.cpp:135-219:
                              shading frame perturbed by the texture's gradient); 0 = none */
-} ppg_material;           /* 80 bytes */
+} ppg_material;           /* 80 bytes; bitmaps on specular / alpha / opacity: ppg_set_material_textures */
 
 typedef struct ppg_emitter {
     float radiance[3]; /* area light, mitsuba/src/emitters/area.cpp:104-109 */
@@ -348,6 +349,33 @@ typedef struct ppg_delta_emitter {
     float cutoff_angle, beam_width; /* spot: radians */
 } ppg_delta_emitter;
 int ppg_set_delta_emitters(ppg_ctx *ctx, const ppg_delta_emitter *emitters, uint32_t n);
+
+/* ------------------------------------------------------------------------------------------------
+ * Bitmaps on the other material parameters (ppg_material keeps its 80 bytes: this is a side list, one entry per material in
+ * ppg_scene.materials' order).  Each slot is 1 + an index into ppg_scene.textures, 0 = none, and names the ppg_material field it replaces
+ * at every intersection by the texture's value at its.uv (wherever the plug-ins call m_...->eval(bRec.its)):
+ *   specular  `specularReflectance` of plastic / roughplastic; `specularTransmittance` of dielectric / thindielectric / roughdielectric
+ *   alpha     `alpha` of roughconductor / roughdielectric: eval(its).average() = (r + g + b) / 3, then clamped to >= 1e-4 like the constant
+ *   opacity   `opacity` of a PPG_MAT_MASK material (mask.cpp:115): looked up at the shading hit AND at every surface a shadow segment
+ *             (Scene::evalTransmittance) or the search for an emitter behind null surfaces (GP:2184-2245) passes through
+ * The lookup is ppg_texture's (same filter flag, wrap modes, uv scale / offset; uv = the barycentrics on a mesh without texture coordinates).
+ * The record's field holds the texture's average (Texture::getAverage), as reflectance[] does under ppg_material.texture: the plug-ins'
+ * configure() derives the component sampling weights of plastic / roughplastic from the averages, not from the looked-up values
+ * (plastic.cpp:199-200, roughplastic.cpp:275-276).  A material with a slot has the shading frame of a textured one (the UV tangents).
+ * Call before ppg_set_scene, which validates and consumes the list; the context keeps the list until it is replaced (n_materials = 0
+ * clears it), and a later ppg_set_scene uses it again.  Between ppg_begin_render and ppg_end_render the call is PPG_ERR_STATE.
+ * ppg_set_scene then returns PPG_ERR_INVALID, naming material and slot in ppg_last_error, for: a list whose length is neither 0 nor the
+ * scene's n_materials; an index beyond n_textures; a slot on a BSDF type that does not read the field (above); opacity without
+ * PPG_MAT_MASK; alpha on roughplastic (its rough-transmittance slice is tabulated for ONE alpha, roughplastic.cpp:295-298); _reserved != 0;
+ * a material with a slot on an analytic sphere.  Any non-zero slot selects the FULL kernel variants, as ppg_material.texture does.
+ * The CPU oracle does not know these slots: nothing pins them against it.  They are pinned by reduction — a constant texture renders bit
+ * for bit what the constant does, which the oracle pins; a shared texture what per-material 1x1 textures do — and by closed forms for a
+ * directly seen specular colour and for cut-outs seen directly and as shadows.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ppg_material_textures {
+    uint32_t specular, alpha, opacity, _reserved;
+} ppg_material_textures;
+int ppg_set_material_textures(ppg_ctx *ctx, const ppg_material_textures *slots, uint32_t n_materials);
 
 /* ------------------------------------------------------------------------------------------------
  * Rendering.  ppg_render() is GuidedPathTracer::render() (GP:1516-1585, IH:74-75) in one call.

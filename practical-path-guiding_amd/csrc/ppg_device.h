@@ -122,7 +122,7 @@ struct DevCamera {
     float aperture, focus;    // its aperture radius and focus distance
 };
 
-#define PPG_MAT_STRIDE 6  // float4 per material: (reflectance, type) (specular, alpha) (eta, flags) (k, fdrInt) (opacity, rtrans slice) (texture word, -, -, -)
+#define PPG_MAT_STRIDE 6  // float4 per material: (reflectance, type) (specular, alpha) (eta, flags) (k, fdrInt) (opacity, rtrans slice) (texture word, specular / alpha / opacity texture: 1 + index as bits, 0 = none)
 
 // ppg_texture on the device: texels as (rgb, -)
 struct DevTex {
@@ -720,7 +720,15 @@ struct TexInfo {
 };
 // fillIntersectionRecord for a triangle whose BSDF may read a bitmap: as fill_isect, plus the texture coordinates (skdtree.h:403-410)
 // and — on meshes that carry them — TriMesh::computeUVTangents' tangents (trimesh.cpp:683-735) as dpdu / dpdv (skdtree.h:374-381),
-// which then also span the shading frame.
+// which then also span the shading frame.  SLOTS: the material may carry a bitmap on specular / alpha / opacity (ppg_set_material_textures),
+// which asks for the same as the texture word does; false where sort_slice has sent such surfaces elsewhere (MSET_COMMON).
+// (the two pieces of its.uv that tex_eval_hit shares with it: a NaN row = the mesh carries no texture coordinates; the interpolation)
+D bool tri_has_uvs(float2 t0, float2 t1, float2 t2) { return !(t0.x != t0.x) && !(t1.x != t1.x) && !(t2.x != t2.x); }
+D void tri_uv_at(float2 t0, float2 t1, float2 t2, F3 b, float &u, float &v) {
+    u = t0.x * b.x + t1.x * b.y + t2.x * b.z;
+    v = t0.y * b.x + t1.y * b.y + t2.y * b.z;
+}
+template <bool SLOTS = true>
 D void fill_isect_tex(const DevScene &S, const Hit &h, F3 d, Isect &I, TexInfo &X) {
     const float4 *T = S.tris + 3 * h.prim;
     float4 q0 = T[0], q1 = T[1];
@@ -744,16 +752,23 @@ D void fill_isect_tex(const DevScene &S, const Hit &h, F3 d, Isect &I, TexInfo &
     I.n = shN;
     I.material = __float_as_int(q0.w);
     I.emitter = __float_as_int(q1.w);
-    X.tex = __float_as_uint(S.materials[PPG_MAT_STRIDE * (size_t)I.material + 5].x);
+    bool textured;
+    if (SLOTS) {
+        const float4 row = S.materials[PPG_MAT_STRIDE * (size_t)I.material + 5];
+        X.tex = __float_as_uint(row.x);
+        textured = (X.tex | __float_as_uint(row.y) | __float_as_uint(row.z) | __float_as_uint(row.w)) != 0u;
+    } else {
+        X.tex = __float_as_uint(S.materials[PPG_MAT_STRIDE * (size_t)I.material + 5].x);
+        textured = X.tex != 0u;
+    }
     F3 dpdu = side1;
-    if (X.tex) {
+    if (textured) {
         X.u = b.y; X.v = b.z;
         X.dpdu = side1; X.dpdv = side2;
         if (S.uvs) {
             const float2 t0 = S.uvs[3 * (size_t)h.prim], t1 = S.uvs[3 * (size_t)h.prim + 1], t2 = S.uvs[3 * (size_t)h.prim + 2];
-            if (!(t0.x != t0.x) && !(t1.x != t1.x) && !(t2.x != t2.x)) {
-                X.u = t0.x * b.x + t1.x * b.y + t2.x * b.z;
-                X.v = t0.y * b.x + t1.y * b.y + t2.y * b.z;
+            if (tri_has_uvs(t0, t1, t2)) {
+                tri_uv_at(t0, t1, t2, b, X.u, X.v);
                 const float dUV1x = t1.x - t0.x, dUV1y = t1.y - t0.y, dUV2x = t2.x - t0.x, dUV2y = t2.y - t0.y;
                 if (len != 0) {
                     const float determinant = dUV1x * dUV2y - dUV1y * dUV2x;
@@ -1314,12 +1329,26 @@ D F3 bsdf_sample(int type, F3 refl, F3 wi, float sx, float sy, F3 &wo, float &pd
 // Full material set (kernel variants instantiated with FULL = true; scenes with only diffuse / two-sided diffuse / mirror
 // materials keep the lean functions above).  Expression order follows the cited reference code, like the oracle's.
 // ------------------------------------------------------------------------------------------------
+// PPG_PARAM_TEXTURES = 0: no kernel of this translation unit calls mat_apply_textures, and Mat has no spec_lum (see mat_spec_lum).  Mat then
+// has another layout than in the other translation units.  That is sound only because no Mat ever crosses a translation-unit boundary:
+// every function that takes one is __forceinline__ or static, and the library is built without relocatable device code.  Whoever adds a
+// non-inline device function taking a Mat, or turns -fgpu-rdc on, must give the switch up first.
+#ifndef PPG_PARAM_TEXTURES
+#define PPG_PARAM_TEXTURES 1
+#endif
+// upload-time bit of the record's flags word (beside the PPG_MAT_* of include/ppg.h): mat_eval_null reads a bitmap on this material — a
+// mask's opacity, a thin dielectric's specularTransmittance
+#define PPG_MATF_NULL_TEXTURED 0x10000
 struct Mat {
     int type, flags;          // type normalised: TWOSIDED_DIFFUSE → DIFFUSE + PPG_MAT_TWOSIDED
     F3 refl, spec, eta, k, opacity;
     float alpha, fdr_int;
     const float *rt;          // roughplastic: its rough-transmittance slice, rt_n samples
     int rt_n;
+#if PPG_PARAM_TEXTURES
+    float spec_lum;           // luminance of the record's specular, likewise, for the kernels in which `spec` may have been read from a bitmap
+                              // (mat_apply_textures; plastic.cpp:199-200, roughplastic.cpp:275-276) — see mat_spec_lum
+#endif
     float refl_lum;           // luminance of the material record's reflectance = of the texture's average when `refl` was read from a bitmap:
                               // what the plug-ins' configure() derives the component sampling weights from (plastic.cpp:191-204)
 };
@@ -1336,7 +1365,47 @@ D Mat load_material(const DevScene &S, int id) {
     M.rt_n = S.rtrans_n;
     M.rt = S.rtrans + (size_t)__float_as_int(e.w) * (size_t)(S.rtrans_n + 1);
     M.refl_lum = a.x * 0.212671f + a.y * 0.715160f + a.z * 0.072169f;
+#if PPG_PARAM_TEXTURES
+    M.spec_lum = b.x * 0.212671f + b.y * 0.715160f + b.z * 0.072169f;
+#endif
     return M;
+}
+// One bitmap lookup of those below, as a CALL: inlined, the three slots at the four places that read them added 53 KB to each FULL kernel
+// (k_shade<FULL, MSET_ALL> 112 -> 165 KB), far more than the instruction cache holds; as calls they add about a tenth of that.
+static __device__ __attribute__((noinline)) float4 tex_eval_slot(const DevTex *textures, unsigned int slot, float u, float v) {
+    const F3 c = tex_eval(textures[slot - 1u], u, v);
+    return make_float4(c.x, c.y, c.z, 0.0f);
+}
+// ... at a hit that has no TexInfo (the surfaces a shadow segment or the search for an emitter passes through): its.uv as fill_isect_tex
+// computes it — the interpolated texture coordinates, or the barycentrics on a mesh without them — then the lookup.
+static __device__ __attribute__((noinline)) float4 tex_eval_hit(const float2 *uvs, const DevTex *textures, unsigned int slot, int prim, float hu, float hv) {
+    float u = hu, v = hv;
+    if (uvs) {
+        const float2 t0 = uvs[3 * (size_t)prim], t1 = uvs[3 * (size_t)prim + 1], t2 = uvs[3 * (size_t)prim + 2];
+        if (tri_has_uvs(t0, t1, t2)) tri_uv_at(t0, t1, t2, f3(1 - hu - hv, hu, hv), u, v);
+    }
+    return tex_eval_slot(textures, slot, u, v);
+}
+// Bitmaps on the record's specular / alpha / opacity (ppg_set_material_textures), looked up at (u, v) = its.uv: m_specularReflectance /
+// m_specularTransmittance->eval(its), m_alpha->eval(its).average() (roughconductor.cpp:259-262, roughdielectric.cpp:283-286, clamped as
+// MicrofacetDistribution does, microfacet.h:135), m_opacity->eval(its) (mask.cpp:115).  The record's row is read again here rather than
+// carried from fill_isect_tex: nothing more stays live between the two.  spec_lum / refl_lum keep the record's values (the averages).
+D void mat_apply_textures(const DevScene &S, int id, float u, float v, Mat &M) {
+    const float4 row = S.materials[PPG_MAT_STRIDE * (size_t)id + 5];
+    const unsigned int ts = __float_as_uint(row.y), ta = __float_as_uint(row.z), to = __float_as_uint(row.w);
+    if ((ts | ta | to) == 0u) return;
+    if (ts) { const float4 t = tex_eval_slot(S.textures, ts, u, v); M.spec = f3(t.x, t.y, t.z); }
+    if (ta) { const float4 t = tex_eval_slot(S.textures, ta, u, v); M.alpha = ppg_max((t.x + t.y + t.z) / 3.0f, 1e-4f); }
+    if (to) { const float4 t = tex_eval_slot(S.textures, to, u, v); M.opacity = f3(t.x, t.y, t.z); }
+}
+// What mat_eval_null reads of a surface passed through: a mask's opacity, a thin dielectric's specularTransmittance.  (Materials of
+// analytic spheres carry no slot: h is a triangle wherever one is set.)
+D void mat_apply_null_textures(const DevScene &S, const Hit &h, int id, Mat &M) {
+    if (!(M.flags & PPG_MATF_NULL_TEXTURED)) return;  // (the flags word came with the record: a constant mask or pane reads nothing more)
+    const float4 row = S.materials[PPG_MAT_STRIDE * (size_t)id + 5];
+    const unsigned int ts = __float_as_uint(row.y), to = __float_as_uint(row.w);
+    if (to) { const float4 t = tex_eval_hit(S.uvs, S.textures, to, h.prim, h.u, h.v); M.opacity = f3(t.x, t.y, t.z); }
+    if (ts) { const float4 t = tex_eval_hit(S.uvs, S.textures, ts, h.prim, h.u, h.v); M.spec = f3(t.x, t.y, t.z); }
 }
 D bool mat_is_smooth(const Mat &M) {
     return M.type == PPG_BSDF_DIFFUSE || M.type == PPG_BSDF_ROUGHCONDUCTOR || M.type == PPG_BSDF_PLASTIC || M.type == PPG_BSDF_ROUGHDIELECTRIC ||
@@ -1352,6 +1421,16 @@ D bool mat_backside_or_transmission(const Mat &M) {
 }
 D bool mat_has_null(const Mat &M) { return mat_masked(M) || M.type == PPG_BSDF_THINDIELECTRIC; }  // getType() & ENull
 
+// sAvg of plastic / roughplastic: the luminance of the RECORD's specular.  The translation unit of k_shade<.., MSET_COMMON>, which never
+// looks a parameter texture up, is compiled with PPG_PARAM_TEXTURES = 0 (ppg_inst.hip): the record's value is then M.spec itself and the
+// kernel is, instruction for instruction, the one built before these textures existed.
+D float mat_spec_lum(const Mat &M) {
+#if PPG_PARAM_TEXTURES
+    return M.spec_lum;
+#else
+    return M.spec.x * 0.212671f + M.spec.y * 0.715160f + M.spec.z * 0.072169f;
+#endif
+}
 D F3 cdiv3(F3 a, F3 b) { return f3(a.x / b.x, a.y / b.y, a.z / b.z); }
 D F3 safe_sqrt3(F3 s) { return f3(__builtin_sqrtf(ppg_max(0.0f, s.x)), __builtin_sqrtf(ppg_max(0.0f, s.y)), __builtin_sqrtf(ppg_max(0.0f, s.z))); }
 D float lum3(F3 s) { return s.x * 0.212671f + s.y * 0.715160f + s.z * 0.072169f; }
@@ -1541,7 +1620,7 @@ D F3 ggx_sample_visible(Mfd d, F3 _wi, float u, float v) {
 
 // plastic.cpp:191-204 (configure) — recomputed per call from the material record, same arithmetic as the oracle's configure()
 D float plastic_prob_specular(const Mat &M, float Fi) {
-    float dAvg = M.refl_lum, sAvg = lum3(M.spec);
+    float dAvg = M.refl_lum, sAvg = mat_spec_lum(M);
     float w = sAvg / (dAvg + sAvg);
     return (Fi * w) / (Fi * w + (1 - Fi) * (1 - w));
 }
@@ -1574,7 +1653,7 @@ D float rough_T(const Mat &M, float cosTheta) {
     return ppg_min(1.0f, ppg_max(0.0f, cubic_interp_1d(warped, M.rt, M.rt_n)));
 }
 D float roughplastic_prob_specular(const Mat &M, float cosThetaI) {  // roughplastic.cpp:406-412
-    const float dAvg = M.refl_lum, sAvg = lum3(M.spec);
+    const float dAvg = M.refl_lum, sAvg = mat_spec_lum(M);
     const float w = sAvg / (dAvg + sAvg);
     const float pS = 1 - rough_T(M, cosThetaI);
     return (pS * w) / (pS * w + (1 - pS) * (1 - w));

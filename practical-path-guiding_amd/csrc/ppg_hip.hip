@@ -820,6 +820,7 @@ struct ppg_ctx {
     float geomMin[3], geomMax[3];  // the kd-tree's box (m_kdtree->getAABB()): Scene::getAABB() before the sensor's box is added
     bool lensOn = false;           // ppg_set_lens: thin lens (kept across ppg_set_scene; copied into scene.cam)
     ppg_lens lens{};
+    std::vector<ppg_material_textures> materialTextures;  // ppg_set_material_textures: kept until replaced; ppg_set_scene validates and packs it
     std::vector<ppg_delta_emitter> deltaEmitters;  // ppg_set_delta_emitters: kept until replaced; ppg_set_scene builds d_delta from it
     DevBuf<float4> d_delta;
     bool renderOpen = false;       // between ppg_begin_render and ppg_end_render
@@ -2952,8 +2953,13 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
     std::vector<float4> mats(PPG_MAT_STRIDE * (size_t)s->n_materials), ems(std::max<uint32_t>(1, s->n_emitters));
     ctx->fullMaterials = false;
     bool hasNull = false;
+    if (!ctx->materialTextures.empty() && ctx->materialTextures.size() != s->n_materials) {
+        ctx->error = "material textures: the list has " + std::to_string(ctx->materialTextures.size()) + " entries, the scene " + std::to_string(s->n_materials) + " materials";
+        return PPG_ERR_INVALID;
+    }
     for (uint32_t i = 0; i < s->n_materials; ++i) {
         ppg_material m = s->materials[i];
+        const ppg_material_textures mt = ctx->materialTextures.empty() ? ppg_material_textures{0u, 0u, 0u, 0u} : ctx->materialTextures[i];
         if (m.type == PPG_BSDF_DIFFUSE && m.flags == PPG_MAT_TWOSIDED) { m.type = PPG_BSDF_TWOSIDED_DIFFUSE; m.flags = 0; }
         if (m.type == PPG_BSDF_TWOSIDED_DIFFUSE) m.flags &= ~PPG_MAT_TWOSIDED;
         if (m.type == PPG_BSDF_MIRROR) for (int c = 0; c < 3; ++c) { m.eta[c] = 0.0f; m.k[c] = 1.0f; }
@@ -2975,15 +2981,39 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
         {   // bitmap on the diffuse reflectance / bump map around the BSDF
             const uint32_t ta = m.texture & 0xffffu, tb = m.texture >> 16;
             if (ta > s->n_textures || tb > s->n_textures || (m.texture && !s->textures)) { ctx->error = "material.texture: index out of range"; return PPG_ERR_INVALID; }
-            if (ta && m.type != PPG_BSDF_DIFFUSE && m.type != PPG_BSDF_TWOSIDED_DIFFUSE && m.type != PPG_BSDF_PLASTIC && m.type != PPG_BSDF_ROUGHPLASTIC) {
-                ctx->error = "material.texture: only the diffuse reflectance of diffuse / plastic / roughplastic can carry a bitmap"; return PPG_ERR_INVALID;
+            // (every BSDF type reads `reflectance`: the diffuse reflectance, or the specularReflectance of conductors and dielectrics)
+            // bitmaps on specular / alpha / opacity: ppg_set_material_textures
+            const std::string who = "material " + std::to_string(i) + ": texture slot ";
+            const bool readsSpecular = m.type == PPG_BSDF_PLASTIC || m.type == PPG_BSDF_ROUGHPLASTIC || m.type == PPG_BSDF_DIELECTRIC ||
+                                       m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_ROUGHDIELECTRIC;
+            if (mt._reserved) { ctx->error = who + "_reserved must be 0"; return PPG_ERR_INVALID; }
+            if ((mt.specular || mt.alpha || mt.opacity) && !s->textures) { ctx->error = who + "set, but the scene has no textures"; return PPG_ERR_INVALID; }
+            if (mt.specular > s->n_textures) { ctx->error = who + "specular: index out of range"; return PPG_ERR_INVALID; }
+            if (mt.alpha > s->n_textures) { ctx->error = who + "alpha: index out of range"; return PPG_ERR_INVALID; }
+            if (mt.opacity > s->n_textures) { ctx->error = who + "opacity: index out of range"; return PPG_ERR_INVALID; }
+            if (mt.specular && !readsSpecular) { ctx->error = who + "specular: only plastic, roughplastic and the dielectrics read `specular`"; return PPG_ERR_INVALID; }
+            if (mt.alpha && m.type == PPG_BSDF_ROUGHPLASTIC) {
+                ctx->error = who + "alpha: roughplastic's rough-transmittance slice is tabulated for one alpha; a roughness map is not supported"; return PPG_ERR_INVALID;
             }
-            if (m.texture) ctx->fullMaterials = true;  // the texture code lives in the FULL kernel variants
-            mats[PPG_MAT_STRIDE * i + 5] = make_float4(__builtin_bit_cast(float, m.texture), 0.0f, 0.0f, 0.0f);
+            if (mt.alpha && m.type != PPG_BSDF_ROUGHCONDUCTOR && m.type != PPG_BSDF_ROUGHDIELECTRIC) {
+                ctx->error = who + "alpha: only roughconductor and roughdielectric read `alpha`"; return PPG_ERR_INVALID;
+            }
+            if (mt.opacity && !(m.flags & PPG_MAT_MASK)) { ctx->error = who + "opacity: the material is not masked (PPG_MAT_MASK)"; return PPG_ERR_INVALID; }
+            if (m.texture || mt.specular || mt.alpha || mt.opacity) ctx->fullMaterials = true;  // the texture code lives in the FULL kernel variants
+            if (mt.opacity || (mt.specular && m.type == PPG_BSDF_THINDIELECTRIC))  // what mat_eval_null reads is a bitmap (ppg_device.h)
+                mats[PPG_MAT_STRIDE * i + 2].w = __builtin_bit_cast(float, m.flags | PPG_MATF_NULL_TEXTURED);
+            mats[PPG_MAT_STRIDE * i + 5] = make_float4(__builtin_bit_cast(float, m.texture), __builtin_bit_cast(float, mt.specular), __builtin_bit_cast(float, mt.alpha),
+                                                       __builtin_bit_cast(float, mt.opacity));
         }
     }
-    for (uint32_t k = 0; k < s->n_spheres; ++k)
-        if (s->materials[s->spheres[k].material].texture) { ctx->error = "sphere: textured BSDFs are only supported on triangle meshes"; return PPG_ERR_INVALID; }
+    for (uint32_t k = 0; k < s->n_spheres; ++k) {
+        const uint32_t sm = s->spheres[k].material;
+        if (s->materials[sm].texture) { ctx->error = "sphere: textured BSDFs are only supported on triangle meshes"; return PPG_ERR_INVALID; }
+        if (!ctx->materialTextures.empty() && (ctx->materialTextures[sm].specular || ctx->materialTextures[sm].alpha || ctx->materialTextures[sm].opacity)) {
+            ctx->error = "sphere: material " + std::to_string(sm) + ": a texture slot (specular / alpha / opacity) is set; textured BSDFs are only supported on triangle meshes";
+            return PPG_ERR_INVALID;
+        }
+    }
     ctx->scene.uvs = nullptr; ctx->scene.textures = nullptr;
     if (s->texcoords) {
         std::vector<float2> uv(3 * (size_t)s->n_triangles);
@@ -3535,6 +3565,13 @@ int ppg_set_lens(ppg_ctx *ctx, const ppg_lens *lens) {
         sceneBox(ctx, S.cam.c2w);
         if (S.env.w != 0) envBSphere(ctx);
     }
+    return PPG_OK;
+}
+
+int ppg_set_material_textures(ppg_ctx *ctx, const ppg_material_textures *slots, uint32_t n_materials) {
+    if (ctx->renderOpen) { ctx->error = "material textures: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (n_materials && !slots) { ctx->error = "material textures: no list"; return PPG_ERR_INVALID; }
+    ctx->materialTextures.assign(slots, slots + n_materials);  // validated against the scene by ppg_set_scene
     return PPG_OK;
 }
 

@@ -5,6 +5,9 @@
  */
 #include <hip/hip_runtime.h>
 
+#if defined(PPG_INST) && PPG_INST == 7
+#define PPG_PARAM_TEXTURES 0  // k_shade<.., MSET_COMMON> reads no bitmap on specular / alpha / opacity (ppg_device.h mat_spec_lum)
+#endif
 #include "ppg_launch.h"
 
 #ifndef PPG_INST

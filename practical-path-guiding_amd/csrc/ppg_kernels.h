@@ -491,8 +491,9 @@ D void sort_slice(const SortArgs &a, const Work &work, unsigned int b, unsigned 
                     const int m = __float_as_int(a.tris[3 * (size_t)prim].w);
                     const float4 *mr = a.materials + PPG_MAT_STRIDE * (size_t)m;
                     const int type = (int)mr[0].w, flags = __float_as_int(mr[2].w);
-                    const unsigned int tex = __float_as_uint(mr[5].x);
-                    if ((flags & PPG_MAT_MASK) || (tex >> 16)) key = 13u;
+                    const float4 tw = mr[5];  // (texture word, specular, alpha, opacity texture)
+                    const unsigned int tex = __float_as_uint(tw.x), slots = __float_as_uint(tw.y) | __float_as_uint(tw.z) | __float_as_uint(tw.w);
+                    if ((flags & PPG_MAT_MASK) || (tex >> 16) || slots) key = 13u;
                     else if (mset_common_type(type)) key = type == PPG_BSDF_ROUGHPLASTIC ? 6u : (unsigned int)type;  // 0..6
                     else key = 8u + ((unsigned int)type & 3u);  // dielectric 10, thin dielectric 11, rough dielectric 8
                 }
@@ -854,6 +855,14 @@ D void fill_isect_full(const DevScene &S, const Hit &h, F3 o, F3 d, Isect &I) {
     if (h.prim >= S.n_tris) fill_isect_sphere(S, h, o, d, I);
     else fill_isect(S, h, d, I);
 }
+// ... and its material, of a hit whose null component may be evaluated (shadow_transmittance, the look-through loop of shade_one): with
+// the bitmaps on what mat_eval_null reads.  Only its.uv is needed for them — the null component does not look at the tangents — so the
+// record is filled as before; a surface without such a slot (a flag of the record's flags word says so) pays nothing.
+D void fill_isect_null(const DevScene &S, const Hit &h, F3 o, F3 d, Isect &I, Mat &M) {
+    fill_isect_full(S, h, o, d, I);
+    M = load_material(S, I.material);
+    if (mat_has_null(M)) mat_apply_null_textures(S, h, I.material, M);
+}
 
 // Scene::evalTransmittance (scene.cpp:619-679), surfaces only, for scenes with null-component BSDFs: zero behind an occluder,
 // otherwise the product of the null components (evaluated in the geometric frame) of the surfaces passed.
@@ -869,7 +878,7 @@ D F3 shadow_transmittance(const DevScene &S, const float4 *small_tris, int *stac
         const bool surface = h.prim >= 0;
         Mat M;
         Isect I;
-        if (surface) { fill_isect_full(S, h, o, d, I); M = load_material(S, I.material); }
+        if (surface) fill_isect_null(S, h, o, d, I, M);
         if (surface && (interactions == maxInteractions || !mat_has_null(M))) return f3s(0.0f);
         if (!surface || iszero3(transmittance)) break;
         const float cosThetaI = dot3(I.geoN, -d);
@@ -931,7 +940,7 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
         if (FULL && MSET != MSET_COMMON && h.prim >= S.n_tris) {
             const float4 ro4 = ray_origin();
             fill_isect_sphere(S, h, f3(ro4.x, ro4.y, ro4.z), d, I);
-        } else if (FULL) fill_isect_tex(S, h, d, I, X);
+        } else if (FULL) fill_isect_tex<MSET != MSET_COMMON>(S, h, d, I, X);
         else fill_isect(S, h, d, I);
     }
     PROBE_MARK(cs, 2);
@@ -960,6 +969,7 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
             // goes on through surfaces that have a null component (traced in place)
             Mat Mc = load_material(S, I.material);
             if (mat_has_null(Mc)) {
+                mat_apply_textures(S, I.material, X.u, X.v, Mc);  // (X holds this hit's uv whenever a slot is set)
                 const float4 ro4 = ray_origin();
                 F3 ro = f3(ro4.x, ro4.y, ro4.z);
                 F3 transmittance = f3s(1.0f);
@@ -978,8 +988,7 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
                     hc = trace_inline(S, nee.small_tris, nee.stack_col, ro, d, __builtin_inff());
                     ++traced;
                     if (hc.prim < 0) { surface = false; break; }
-                    fill_isect_full(S, hc, ro, d, Ic);
-                    Mc = load_material(S, Ic.material);
+                    fill_isect_null(S, hc, ro, d, Ic, Mc);
                 }
                 if (!abandoned && surface && Ic.emitter >= 0) {
                     value = mul3(transmittance, eval_Le(S, Ic, -d));
@@ -1090,6 +1099,9 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
             if (X.tex & 0xffffu) M.refl = tex_eval(S.textures[(X.tex & 0xffffu) - 1u], X.u, X.v);
             if (MSET != MSET_COMMON && (X.tex >> 16)) { bump_frame(S, I, X, ps, pt, pn); bumped = true; }
         }
+        // bitmaps on specular / alpha / opacity (never in the COMMON part: sort_slice keeps such surfaces out of it)
+        static_assert(PPG_PARAM_TEXTURES || MSET == MSET_COMMON, "this translation unit was compiled without Mat::spec_lum");
+        if (FULL && MSET != MSET_COMMON) mat_apply_textures(S, I.material, X.u, X.v, M);
         // (one call site per BSDF function: the bumped variant only transforms the arguments first — two inlined copies of the whole
         // material switch per function made the FULL kernels 330 KB of code, five times the instruction cache)
         auto to_pert = [&](F3 v_) { const F3 w_ = to_world(I, v_); return f3(dot3(w_, ps), dot3(w_, pt), dot3(w_, pn)); };

@@ -116,6 +116,12 @@ static bool loadSceneChecked(const char *path, SceneData &s) {
         s.deltaEmitters.resize(n);
         f.read((char *)s.deltaEmitters.data(), (std::streamsize)(n * sizeof(ppg_delta_emitter)));
     }
+    if (hdr[5] & 512) {  // bit 9: bitmaps on specular / alpha / opacity (n_materials x ppg_material_textures), only when a material has one
+        if (!fits((uint64_t)nm * sizeof(ppg_material_textures))) return false;
+        s.materialTextures.resize(nm);
+        f.read((char *)s.materialTextures.data(), (std::streamsize)((size_t)nm * sizeof(ppg_material_textures)));
+    }
+    if (hdr[5] >> 10) return false;  // a block this reader does not know
     return (bool)f;
 }
 
@@ -186,7 +192,7 @@ static bool saveScene(const char *path, const SceneData &s) {
     const uint32_t hdr[6] = {(uint32_t)(s.positions.size() / 3), (uint32_t)(s.indices.size() / 3), (uint32_t)s.materials.size(), (uint32_t)s.emitters.size(),
                              s.normals.empty() ? 0u : 1u, (s.hasEnvironment ? 1u : 0u) | (s.rtrans.empty() ? 0u : 2u) | (s.spheres.empty() ? 0u : 4u) | (s.hasEnvmap ? 8u : 0u) |
                                  (s.texcoords.empty() ? 0u : 16u) | (s.textures.empty() ? 0u : 32u) | (s.hasRFilter ? 64u : 0u) | (s.hasLens ? 128u : 0u) |
-                                 (s.deltaEmitters.empty() ? 0u : 256u)};
+                                 (s.deltaEmitters.empty() ? 0u : 256u) | (s.materialTextures.empty() ? 0u : 512u)};
     f.write("PPGS", 4); f.write((const char *)hdr, sizeof hdr);
     f.write((const char *)s.positions.data(), s.positions.size() * 4);
     if (!s.normals.empty()) f.write((const char *)s.normals.data(), s.normals.size() * 4);
@@ -230,6 +236,7 @@ static bool saveScene(const char *path, const SceneData &s) {
         f.write((const char *)&n, 4);
         f.write((const char *)s.deltaEmitters.data(), (std::streamsize)(n * sizeof(ppg_delta_emitter)));
     }
+    if (!s.materialTextures.empty()) f.write((const char *)s.materialTextures.data(), (std::streamsize)(s.materialTextures.size() * sizeof(ppg_material_textures)));
     return (bool)f;
 }
 
@@ -327,6 +334,7 @@ int main(int argc, char **argv) {
         core.setRFilter(scene.hasRFilter ? &scene.rfilter : nullptr);
         core.setLens(scene.hasLens ? &scene.lens : nullptr);
         core.setDeltaEmitters(scene.deltaEmitters.data(), scene.deltaEmitters.size());
+        core.setMaterialTextures(scene.materialTextures.data(), scene.materialTextures.size());
         core.setSeed((uint64_t)std::stoull(props.getString("seed", "0")));
         std::string dest = out;
         const size_t dot = dest.find_last_of('.');

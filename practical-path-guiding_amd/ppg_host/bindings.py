@@ -93,6 +93,25 @@ class Material(C.Structure):
         return o
 
 
+class MaterialTextures(C.Structure):
+    """ppg_material_textures (include/ppg.h): per material, 1 + index into SceneDesc.textures of the bitmap on `specular`, `alpha`, `opacity`
+    (0 = none).  Material dicts carry them as specular_texture / alpha_texture / opacity_texture = the index."""
+    _fields_ = [("specular", C.c_uint32), ("alpha", C.c_uint32), ("opacity", C.c_uint32), ("_reserved", C.c_uint32)]
+
+    KEYS = ("specular_texture", "alpha_texture", "opacity_texture")
+
+    @classmethod
+    def from_dict(cls, m):
+        o = cls()
+        o.specular, o.alpha, o.opacity = (0 if m.get(k) is None else int(m[k]) + 1 for k in cls.KEYS)
+        return o
+
+
+def has_parameter_textures(desc):
+    """Whether a material of `desc` carries a bitmap on specular / alpha / opacity (what the CPU oracle does not implement)."""
+    return any(m.get(k) is not None for m in desc.materials for k in MaterialTextures.KEYS)
+
+
 class Sphere(C.Structure):
     """ppg_sphere (include/ppg.h).  Scene descriptions carry spheres as dicts: center, radius, material, emitter (-1), flip_normals,
     to_world (9 floats, row-major rotation; identity by default)."""
@@ -426,6 +445,12 @@ class Engine:
                 self.set_delta_emitters(delta)
         elif delta:
             raise NotImplementedError("%s: point, spot and directional emitters are not implemented here" % self.prefix)
+        # the bitmaps on specular / alpha / opacity: always sent — one entry per material, or the empty list that clears the context's
+        if self.prefix == "ppg_":
+            self.set_material_textures(desc.materials if has_parameter_textures(desc) else [])
+        elif has_parameter_textures(desc):
+            raise NotImplementedError("%s: bitmaps on specular / alpha / opacity (specular_texture, alpha_texture, opacity_texture) are not implemented here"
+                                      % self.prefix)
         self._call("set_scene", C.byref(s))
         self.width, self.height = cam["width"], cam["height"]
         # the film's reconstruction filter comes with the scene description (None / absent: the default box)
@@ -453,6 +478,15 @@ class Engine:
             arr[i] = d if isinstance(d, DeltaEmitter) else DeltaEmitter.from_dict(d)
         self._call("set_delta_emitters", arr, C.c_uint32(len(emitters)))
         self._delta = emitters
+
+    def set_material_textures(self, slots):
+        """ppg_set_material_textures: one entry per material — a material dict (its specular_texture / alpha_texture / opacity_texture keys) or
+        a MaterialTextures; an empty list clears it.  Takes effect at the next set_scene."""
+        slots = list(slots or [])
+        arr = (MaterialTextures * max(1, len(slots)))()
+        for i, d in enumerate(slots):
+            arr[i] = d if isinstance(d, MaterialTextures) else MaterialTextures.from_dict(d)
+        self._call("set_material_textures", arr, C.c_uint32(len(slots)))
 
     def set_lens(self, lens):
         """ppg_set_lens: lens = {"aperture_radius", "focus_distance"} (Lens) or None for the pinhole"""

@@ -43,6 +43,9 @@ GUIDED_PATH_PROPS = {  # name → type (GP:1014-1085, integrator.cpp:192-218)
 }
 
 
+TEXTURE_KEYS = ("texture", "bump", "specular_texture", "alpha_texture", "opacity_texture")  # material keys that hold a texture index
+
+
 class SceneError(ValueError):
     pass
 
@@ -776,7 +779,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                     return spectrum.blackbody_to_rgb(float(t[:-1] if t[-1:] in "kK" else t), float(sub(c.get("scale", "1"))))
                 if c.tag == "texture" or c.tag == "ref":
                     if strict:
-                        raise SceneError("a texture on %r is not supported (bitmaps on diffuse reflectances and bump maps are)" % name)
+                        raise SceneError("a texture on %r is not supported (bitmaps on reflectances, specular colours, roughconductor / roughdielectric alpha, mask opacity and bump maps are)" % name)
                     warnings.append("texture on %r ignored: the plug-in's default value is used" % name)
                     break
         return np.full(3, default, f32)
@@ -814,8 +817,9 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             return tex_index[key]
         if not os.path.exists(full):
             raise SceneError("bitmap: file '%s' not found" % full)
-        if tp.get("channel"):
-            raise SceneError("bitmap: the `channel` parameter is not supported")
+        channel = str(tp.get("channel", "")).lower()
+        if channel and channel not in ("r", "g", "b", "a"):
+            raise SceneError("bitmap: channel %r is not supported (r, g, b, a)" % tp.get("channel"))
         from . import imageio
         from .scenes import srgb8_table
         t = dict(uv_scale=(float(tp.get("uscale", 1.0)), float(tp.get("vscale", 1.0))), uv_offset=(float(tp.get("uoffset", 0.0)), float(tp.get("voffset", 0.0))),
@@ -823,6 +827,33 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         ext = os.path.splitext(full)[1].lower()
         if ext in (".exr", ".pfm", ".hdr", ".rgbe"):
             t["rgb"] = np.ascontiguousarray(imageio.read_image(full), f32)  # floating point data is linear (bitmap.cpp:190-192)
+            if channel:  # a monochrome texture of that channel (bitmap.cpp:238-256)
+                if channel == "a":
+                    raise SceneError("bitmap: '%s' has no channel 'a' (channels present: r, g, b)" % full)
+                t["rgb"] = np.ascontiguousarray(np.repeat(t["rgb"][:, :, "rgb".index(channel)][:, :, None], 3, 2))
+        elif channel:  # one channel of the file as a monochrome texture, replicated to RGB (bitmap.cpp:238-256)
+            try:
+                from PIL import Image
+            except ImportError:
+                raise SceneError("bitmap: decoding '%s' needs PIL (scene conversion only)" % full)
+            im = Image.open(full)
+            if im.mode in ("P", "CMYK", "1"):
+                im = im.convert("RGBA" if "transparency" in im.info else "RGB")
+            names = {"L": "y", "LA": "ya", "RGB": "rgb", "RGBA": "rgba"}.get(im.mode)
+            a = np.asarray(im)
+            if names is None or a.dtype != np.uint8:
+                raise SceneError("bitmap: '%s': only 8-bit images are decoded here" % full)
+            if channel not in names:
+                raise SceneError("bitmap: '%s' has no channel %r (channels present: %s)" % (full, channel, ", ".join(names)))
+            a = np.ascontiguousarray(np.repeat(a.reshape(a.shape[0], a.shape[1], -1)[:, :, names.index(channel)][:, :, None], 3, 2))
+            g = 1.0 if channel == "a" else gamma  # alpha is never gamma-corrected (bitmap.cpp:258-263)
+            if g == 0.0 or g == -1.0:
+                t["srgb8"] = a
+                t["rgb"] = srgb8_table()[a]
+            elif g == 1.0:
+                t["rgb"] = (a.astype(f32) / f32(255.0)).astype(f32)
+            else:
+                t["rgb"] = np.power(a.astype(np.float64) / 255.0, g).astype(f32)
         else:
             try:
                 from PIL import Image
@@ -848,14 +879,17 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         textures.append(t)
         return tex_index[key]
 
-    def colour_or_texture(elem, name, default):
-        """(rgb, texture index or None) of a reflectance that may be a bitmap; rgb is then the bitmap's average."""
+    def colour_or_texture(elem, name, default, wrap=False):
+        """(rgb, texture index or None) of a parameter that may be a bitmap; rgb is then the bitmap's average.  `wrap`: a loader failure is
+        reported as "texture on <name>: ..." (the parameters other than the diffuse reflectance)."""
         for c in elem:
             if c.get("name") == name and c.tag in ("texture", "ref") and (c.tag == "texture" or c.get("id") in tex_by_id):
                 try:
                     ti = bitmap_texture(c, name)
                 except SceneError as e:
                     if strict:
+                        if wrap:
+                            raise SceneError("texture on %r: %s" % (name, e))
                         raise
                     warnings.append("texture on %r ignored (%s): the plug-in's default value is used" % (name, e))
                     return np.full(3, default, f32), None
@@ -908,11 +942,26 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         t = elem.get("type")
         p = _props(elem, sub)
         rgb = lambda name, d: tuple(float(v) for v in colour(elem, name, d))  # noqa: E731
-        def textured(m, name, d):  # a bitmap on the diffuse reflectance: constant = its average, plus the texture index
-            c, ti = colour_or_texture(elem, name, d)
-            m["reflectance"] = tuple(float(v) for v in c)
+        def textured(m, name, d, field="reflectance", key="texture"):  # a bitmap on a colour: constant = its average, plus the texture index
+            c, ti = colour_or_texture(elem, name, d, wrap=name != "reflectance" and name != "diffuseReflectance")
+            m[field] = tuple(float(v) for v in c)
             if ti is not None:
-                m["texture"] = ti
+                m[key] = ti
+            return m
+        def specular(m, name):  # the `specular` field: plastic specularReflectance, dielectric specularTransmittance
+            return textured(m, name, 1.0, "specular", "specular_texture")
+        def rough(m, what):  # roughness `alpha` of roughconductor / roughdielectric: a number, or a bitmap read as eval(its).average()
+            for c in elem:
+                if c.get("name") in ("alphaU", "alphaV") and c.tag in ("texture", "ref"):
+                    raise SceneError("%s: a texture on %r is not supported (anisotropic roughness)" % (what, c.get("name")))
+            if any(c.get("name") == "alpha" and c.tag in ("texture", "ref") for c in elem):
+                microfacet_alpha(dict(p, alpha=0.1), what)
+                c, ti = colour_or_texture(elem, "alpha", 0.1, wrap=True)
+                m["alpha"] = float((f32(c[0]) + f32(c[1]) + f32(c[2])) / f32(3.0))  # Spectrum::average (spectrum.h:481-486) of the texture's average
+                if ti is not None:
+                    m["alpha_texture"] = ti
+            else:
+                m["alpha"] = microfacet_alpha(p, what)
             return m
         if t == "diffuse":
             return textured(dict(type=0), "reflectance", 0.5)
@@ -923,7 +972,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 if m["type"] in (6, 7, 8):
                     raise SceneError("twosided(dielectric): only BRDFs can be two-sided (twosided.cpp:84-88)")
                 if m["type"] == 0 and not m.get("_substituted"):
-                    return dict({k: v for k, v in m.items() if k in ("texture", "bump")}, type=1, reflectance=m["reflectance"])
+                    return dict({k: v for k, v in m.items() if k in TEXTURE_KEYS}, type=1, reflectance=m["reflectance"])
                 return dict(m, twosided=True)
             t = "twosided(%s)" % ",".join(c.get("type", "?") for c in inner)
         elif t == "mask" and allow_twosided:
@@ -933,32 +982,35 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 if "opacity" in m:
                     raise SceneError("mask(mask(...)) is not supported")
                 if m["type"] == 1:
-                    m = dict({k: v for k, v in m.items() if k in ("texture", "bump")}, type=0, reflectance=m["reflectance"], twosided=True)
-                return dict(m, opacity=rgb("opacity", 0.5))
+                    m = dict({k: v for k, v in m.items() if k in TEXTURE_KEYS}, type=0, reflectance=m["reflectance"], twosided=True)
+                return textured(dict(m), "opacity", 0.5, "opacity", "opacity_texture")
             t = "mask(%s)" % ",".join(c.get("type", "?") for c in inner)
         elif t == "conductor":
             if str(p.get("material", "Cu")).lower() == "none":
-                return dict(type=2, reflectance=rgb("specularReflectance", 1.0))
+                return textured(dict(type=2), "specularReflectance", 1.0)
             eta, k = conductor_ior(elem, p, t)
-            return dict(type=3, reflectance=rgb("specularReflectance", 1.0), eta=eta, k=k)
+            return textured(dict(type=3, eta=eta, k=k), "specularReflectance", 1.0)
         elif t == "roughconductor":
             eta, k = conductor_ior(elem, p, t)
-            m = dict(type=4, reflectance=rgb("specularReflectance", 1.0), eta=eta, k=k, alpha=microfacet_alpha(p, t))
+            m = rough(textured(dict(type=4, eta=eta, k=k), "specularReflectance", 1.0), t)
             if str(p.get("distribution", "beckmann")).lower() == "beckmann":  # Mitsuba's default (microfacet.h:99)
                 m["distribution"] = "beckmann"
             return m
         elif t == "plastic":
             eta = lookup_ior(p, "intIOR", "polypropylene") / lookup_ior(p, "extIOR", "air")
-            return textured(dict(type=5, specular=rgb("specularReflectance", 1.0), eta=float(f32(eta)), nonlinear=bool(p.get("nonlinear", False))),
+            return textured(specular(dict(type=5, eta=float(f32(eta)), nonlinear=bool(p.get("nonlinear", False))), "specularReflectance"),
                             "diffuseReflectance", 0.5)
         elif t == "dielectric":
             eta = lookup_ior(p, "intIOR", "bk7") / lookup_ior(p, "extIOR", "air")
-            return dict(type=6, reflectance=rgb("specularReflectance", 1.0), specular=rgb("specularTransmittance", 1.0), eta=float(f32(eta)))
+            return specular(textured(dict(type=6, eta=float(f32(eta))), "specularReflectance", 1.0), "specularTransmittance")
         elif t == "thindielectric":
             eta = lookup_ior(p, "intIOR", "bk7") / lookup_ior(p, "extIOR", "air")
-            return dict(type=7, reflectance=rgb("specularReflectance", 1.0), specular=rgb("specularTransmittance", 1.0), eta=float(f32(eta)))
+            return specular(textured(dict(type=7, eta=float(f32(eta))), "specularReflectance", 1.0), "specularTransmittance")
         elif t == "roughplastic":  # roughplastic.cpp:197-227, 285-305
             from . import rtrans as _rt
+            if any(c.get("name") in ("alpha", "alphaU", "alphaV") and c.tag in ("texture", "ref") for c in elem):
+                # its rough-transmittance slice is reduced to ONE alpha at conversion; a varying alpha needs the 2-D table (roughplastic.cpp:295-298)
+                raise SceneError("roughplastic: a texture on 'alpha' is not supported (roughness maps are, on roughconductor and roughdielectric)")
             int_ior, ext_ior = lookup_ior(p, "intIOR", "polypropylene"), lookup_ior(p, "extIOR", "air")
             if int_ior < 0 or ext_ior < 0 or int_ior == ext_ior:
                 raise SceneError("roughplastic: the interior and exterior indices of refraction must be positive and differ")
@@ -971,7 +1023,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 except _rt.RoughTransmittanceError as e:
                     raise SceneError("roughplastic: %s" % e)
                 rt_index[key] = len(rt_slices) - 1
-            m = textured(dict(type=9, specular=rgb("specularReflectance", 1.0), eta=eta, alpha=alpha, nonlinear=bool(p.get("nonlinear", False)), rtrans=rt_index[key]),
+            m = textured(specular(dict(type=9, eta=eta, alpha=alpha, nonlinear=bool(p.get("nonlinear", False)), rtrans=rt_index[key]), "specularReflectance"),
                          "diffuseReflectance", 0.5)
             if distr == "beckmann":
                 m["distribution"] = "beckmann"
@@ -980,8 +1032,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             int_ior, ext_ior = lookup_ior(p, "intIOR", "bk7"), lookup_ior(p, "extIOR", "air")
             if int_ior < 0 or ext_ior < 0 or int_ior == ext_ior:
                 raise SceneError("roughdielectric: the interior and exterior indices of refraction must be positive and differ")
-            m = dict(type=8, reflectance=rgb("specularReflectance", 1.0), specular=rgb("specularTransmittance", 1.0), eta=float(f32(int_ior / ext_ior)),
-                     alpha=microfacet_alpha(p, t))
+            m = rough(specular(textured(dict(type=8, eta=float(f32(int_ior / ext_ior))), "specularReflectance", 1.0), "specularTransmittance"), t)
             if str(p.get("distribution", "beckmann")).lower() == "beckmann":
                 m["distribution"] = "beckmann"
             return m
@@ -1199,13 +1250,13 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
     # un-shared and its face normals written out (same shading frame as "no normals": skdtree.h:388-401)
     any_normals = any(m["normals"] is not None for m, _, _ in collected)
     # texture coordinates only matter on meshes whose BSDF reads a bitmap; the others get NaN rows (= none)
-    any_uvs = any(m.get("uvs") is not None and ("texture" in materials[mat] or "bump" in materials[mat]) for m, mat, _ in collected)
+    any_uvs = any(m.get("uvs") is not None and any(k in materials[mat] for k in TEXTURE_KEYS) for m, mat, _ in collected)
     uvl = []
     pos, nrm, idx, tmat, tem = [], [], [], [], []
     nv = 0
     for mesh, mat, em in collected:
         p, i, n = mesh["positions"], mesh["indices"], mesh["normals"]
-        uv = mesh.get("uvs") if ("texture" in materials[mat] or "bump" in materials[mat]) else None
+        uv = mesh.get("uvs") if any(k in materials[mat] for k in TEXTURE_KEYS) else None
         if any_normals and n is None:
             if uv is not None:
                 uv = uv[i.reshape(-1)]

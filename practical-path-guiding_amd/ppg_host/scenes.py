@@ -40,7 +40,7 @@ class SceneDesc:
 
 def save_scene(desc, path):
     """Write the flat binary scene read by host/ppg_render.cpp: "PPGS", 6 x uint32 {n_vertices, n_triangles, n_materials,
-    n_emitters, has_normals, blocks (bit 0: environment, bit 1: rtrans, bit 2: spheres, bit 3: envmap, bit 4: texcoords, bit 5: textures, bit 6: rfilter, bit 7: lens, bit 8: delta emitters)}, then positions, [normals], indices, tri_material,
+    n_emitters, has_normals, blocks (bit 0: environment, bit 1: rtrans, bit 2: spheres, bit 3: envmap, bit 4: texcoords, bit 5: textures, bit 6: rfilter, bit 7: lens, bit 8: delta emitters, bit 9: material textures)}, then positions, [normals], indices, tri_material,
     tri_emitter, materials (ppg_material, 80 bytes each), emitters (4 floats), camera (ppg_camera), [environment radiance:
     3 floats], [rtrans: 2 x uint32 {n_slices, samples}, then n_slices x (samples + 1) floats], [spheres: uint32 n, then n x ppg_sphere
     (64 bytes)], [envmap: 2 x uint32 {width, height}, float scale, 9 floats to_world, then height x width x 3 floats], [texcoords: n_vertices x 2
@@ -48,9 +48,11 @@ def save_scene(desc, path):
     storage (0: float32 RGB, 1: uint8 sRGB-encoded RGB — decoded on load with the exact 256-entry table of the 8-bit → float conversion), pixels],
     [rfilter: ppg_rfilter, 24 bytes {int32 type, float radius, stddev, B, C, int32 lobes} — only for a filter other than the default box],
     [lens: ppg_lens, 2 floats {aperture_radius, focus_distance} — only for a thin-lens camera],
-    [delta emitters: uint32 n, then n x ppg_delta_emitter (84 bytes) — only when there are point / spot / directional emitters]."""
+    [delta emitters: uint32 n, then n x ppg_delta_emitter (84 bytes) — only when there are point / spot / directional emitters],
+    [material textures: n_materials x ppg_material_textures (16 bytes) — only when a material has a bitmap on specular / alpha / opacity]."""
     import struct
-    from .bindings import DeltaEmitter, Lens, RFilter
+    from .bindings import DeltaEmitter, Lens, MaterialTextures, RFilter, has_parameter_textures
+    mat_tex = [MaterialTextures.from_dict(m) for m in desc.materials] if has_parameter_textures(desc) else []
     rf = RFilter.from_dict(getattr(desc, "rfilter", None))
     rf = rf if rf.as_dict() is not None else None
     lens = getattr(desc, "lens", None)
@@ -66,7 +68,7 @@ def save_scene(desc, path):
         f.write(struct.pack("<6I", pos.shape[0], idx.shape[0], len(desc.materials), len(desc.emitters), 0 if desc.normals is None else 1,
                             (0 if env is None else 1) | (0 if rt is None else 2) | (4 if getattr(desc, "spheres", None) else 0) | (8 if getattr(desc, "envmap", None) is not None else 0)
                             | (16 if getattr(desc, "texcoords", None) is not None else 0) | (32 if getattr(desc, "textures", None) else 0) | (0 if rf is None else 64)
-                            | (0 if lens is None else 128) | (256 if delta else 0)))
+                            | (0 if lens is None else 128) | (256 if delta else 0) | (512 if mat_tex else 0)))
         f.write(pos.tobytes())
         if desc.normals is not None:
             f.write(np.ascontiguousarray(desc.normals, np.float32).tobytes())
@@ -119,6 +121,8 @@ def save_scene(desc, path):
             f.write(struct.pack("<I", len(delta)))
             for d in delta:
                 f.write(bytes(d))
+        for mt in mat_tex:
+            f.write(bytes(mt))
 
 
 def srgb8_table():
@@ -226,6 +230,15 @@ def load_scene_file(path):
             if not 0 <= e.type < len(DeltaEmitter.TYPES):
                 raise ValueError("%s: unknown delta emitter type %d" % (path, e.type))
             delta.append(e.as_dict())
+    if blocks & 512:
+        from .bindings import MaterialTextures
+        for d in mats:
+            mt = MaterialTextures.from_buffer_copy(bytes(take(np.uint8, C_MATERIAL_TEXTURES_BYTES)))
+            for k, v in zip(MaterialTextures.KEYS, (mt.specular, mt.alpha, mt.opacity)):
+                if v > len(textures) or mt._reserved:
+                    raise ValueError("%s: material texture slot out of range" % path)
+                if v:
+                    d[k] = int(v) - 1
     if off[0] != len(buf):
         raise ValueError("%s: trailing bytes" % path)
     return SceneDesc(pos, idx, tm, te, mats, ems, cam, nrm, env, rt, spheres, envmap, uvs, textures, rfilter, lens, delta)
@@ -233,6 +246,7 @@ def load_scene_file(path):
 
 C_RFILTER_BYTES = 24  # sizeof(ppg_rfilter)
 C_LENS_BYTES = 8      # sizeof(ppg_lens)
+C_MATERIAL_TEXTURES_BYTES = 16  # sizeof(ppg_material_textures)
 C_DELTA_EMITTER_BYTES = 84  # sizeof(ppg_delta_emitter)
 
 
