@@ -351,6 +351,47 @@ typedef struct ppg_delta_emitter {
 int ppg_set_delta_emitters(ppg_ctx *ctx, const ppg_delta_emitter *emitters, uint32_t n);
 
 /* ------------------------------------------------------------------------------------------------
+ * Analytic disks and cylinders (shapes/disk.cpp, shapes/cylinder.cpp), as surfaces and as area emitters.  ppg_scene and ppg_sphere keep
+ * their layout: this is a side list like the delta emitters'.  The shapes are primitives number n_triangles + n_spheres + k for the
+ * closest-hit tie rule (a shape beats an earlier primitive only with a strictly smaller t), tested one after the other behind the BVH.
+ *   disk      the unit disk z = 0, x^2 + y^2 <= 1 of object space under `to_world` (any rotation, translation and UNIFORM scale).  The
+ *             ray goes to object space through the float inverse; hit = -o.z / d.z, then x^2 + y^2 <= 1 (disk.cpp:139-162).  Normal =
+ *             normalize(to_world applied to Normal(0, 0, 1)), negated by flip_normals — which is all that the constructor's prepended
+ *             scale(1, 1, -1) does; tangent = the radial direction (the x axis at r = 0).  Area sampling by
+ *             squareToUniformDiskConcentric, pdf 1 / (pi |column 0|^2) (:101-115, 247-255).  `radius` and `length` are ignored.
+ *   cylinder  the open tube x^2 + y^2 = radius^2, 0 <= z <= length of object space under `to_world`, which is m_objectToWorld AFTER the
+ *             constructor has removed the scale (cylinder.cpp:99-103): a rotation and a translation.  Double-precision quadratic in
+ *             x, y, then the near / far rules with the z tests (:128-165; the any-hit form :167-199 differs in its maxt test, and so does
+ *             the shadow trace here).  No end caps.  Record of :201-230: dpdu = (-y, x, 0) 2 pi, n = cross(normalize(dpdu),
+ *             normalize(dpdv)), p re-projected radially, then flip_normals.  Area sampling p = (r cos 2 pi v, r sin 2 pi v, u length),
+ *             pdf 1 / (2 pi r length) (:232-246).
+ * As emitters both go through Shape::sampleDirect (shape.cpp:97-115): area density to solid angle, dist^2 / |dot(d, n)|, and the same
+ * density on the hit side.  One deviation from the reference: its disk never sets its.geoFrame, so strictNormals reads a stale frame
+ * there; here the geometric normal of a disk hit is its shading normal.
+ * Scene box: grows by Disk::getAABB (the four points (+-1, 0, 0), (0, +-1, 0) transformed, :117-130) and Cylinder::getAABB (:252-273).
+ * Call before ppg_set_scene, which validates and consumes the list; the context keeps it until it is replaced (n = 0 clears it).
+ * Between ppg_begin_render and ppg_end_render the call is PPG_ERR_STATE.  A scene may consist of such shapes only.  ppg_set_scene returns
+ * PPG_ERR_INVALID, with the shape's index in ppg_last_error, for: an unknown type; a value that is not finite; a disk whose to_world
+ * shears (|dot(normalize(col0), normalize(col1))| > 1e-3), scales non-uniformly (| |col0| / |col1| - 1 | > 1e-3) or is singular; a
+ * cylinder with radius <= 0, length <= 0 or a linear part that is not a rotation (the same 1e-3 tests, and column lengths within 1e-3
+ * of 1); a material index out of range; an emitter id shared with any other shape; a material with a texture word or a
+ * ppg_set_material_textures slot.  Such scenes render with the FULL kernel variants on the BVH path.
+ * The CPU oracle does not know these shapes; they are pinned ray by ray and sample by sample through include/ppg_testhooks.h.
+ * ---------------------------------------------------------------------------------------------- */
+#define PPG_SHAPE_DISK 0
+#define PPG_SHAPE_CYLINDER 1
+typedef struct ppg_shape {
+    int32_t type;          /* PPG_SHAPE_*                                                        offset  0 */
+    float to_world[12];    /* row-major 3x4 object-to-world                                              4 */
+    float radius, length;  /* cylinder: m_radius, m_length; disk: ignored                           52, 56 */
+    uint32_t material;     /* index into materials                                                      60 */
+    int32_t emitter;       /* index into emitters, -1 = none; not shared with any other shape           64 */
+    int32_t flip_normals;  /*                                                                           68 */
+    uint32_t _reserved[2]; /* 0                                                                         72 */
+} ppg_shape;               /* 80 bytes */
+int ppg_set_shapes(ppg_ctx *ctx, const ppg_shape *shapes, uint32_t n);
+
+/* ------------------------------------------------------------------------------------------------
  * Bitmaps on the other material parameters (ppg_material keeps its 80 bytes: this is a side list, one entry per material in
  * ppg_scene.materials' order).  Each slot is 1 + an index into ppg_scene.textures, 0 = none, and names the ppg_material field it replaces
  * at every intersection by the texture's value at its.uv (wherever the plug-ins call m_...->eval(bRec.its)):

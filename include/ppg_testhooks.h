@@ -57,6 +57,35 @@ int ppg_debug_rfilter_table(const struct ppg_rfilter *f, float table[32], float 
 struct ppg_ctx;
 int ppg_debug_set_defer_depth(struct ppg_ctx *ctx, int32_t depth);
 
+/* The traversal and the intersection record of the context's scene (after ppg_set_scene, outside a render), ray by ray: one small kernel
+   whose lanes call what the render calls — trace_closest4 with the analytic passes behind it and the FULL kernels' intersection record
+   (csrc/ppg_device.h).  rays = n x { ox, oy, oz, mint, dx, dy, dz, maxt }, mint as it stands.  prim: -1 = no hit; below the number of
+   triangles a triangle (in the BVH's leaf order), then the spheres, then the shapes of ppg_set_shapes in their order.  any_hit != 0 runs
+   the shadow rays' any-hit trace instead: only prim >= 0 (and, for an analytic hit, t) is meaningful then and no record is filled. */
+struct ppg_debug_hit {
+    int32_t prim;
+    float t;
+    float p[3], geo_n[3], n[3], s[3], wi[3];
+    int32_t material, emitter;
+    int32_t _pad;
+};  /* 80 bytes */
+int ppg_debug_intersect(struct ppg_ctx *ctx, uint32_t n, const float *rays, struct ppg_debug_hit *out, int32_t any_hit);
+
+/* emitter_sample_direct of the FULL kernels, sample by sample: per item a reference point ref[3], its normal ref_n[3] and the 2-D sample
+   u[2].  Out: the emitter chosen (the hook repeats the render's pmf_sample on the same table and sample: the record does not carry the
+   index), and of its direct-sampling record the direction d, the distance, the emitter's normal n, the density in
+   solid angle (0 where the facing tests fail), the emitter-choice probability and value = radiance / pdf. */
+struct ppg_debug_direct {
+    int32_t emitter;
+    float d[3];
+    float dist;
+    float n[3];
+    float pdf, em_pdf;
+    float value[3];
+    float _pad[3];
+};  /* 64 bytes */
+int ppg_debug_sample_direct(struct ppg_ctx *ctx, uint32_t n, const float *ref, const float *ref_n, const float *u, struct ppg_debug_direct *out);
+
 #ifdef __cplusplus
 }
 #endif

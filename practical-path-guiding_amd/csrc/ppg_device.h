@@ -25,6 +25,17 @@
 #include "../../include/ppg.h"
 
 #define D __device__ __forceinline__
+// The code for analytic disks and cylinders (ppg_set_shapes) is compiled into kernels of their own — k_trace_shapes, k_shade_shapes,
+// k_tail_shapes: translation units built with -DPPG_SHAPES=1 (ppg_inst.hip) — which the launchers pick for a scene that holds such shapes.
+// Every other scene runs the kernels without it: one more analytic test behind each traversal costs registers the FULL kernels do not have.
+#ifndef PPG_SHAPES
+#define PPG_SHAPES 0
+#endif
+#if PPG_SHAPES
+#define k_trace k_trace_shapes
+#define k_shade k_shade_shapes
+#define k_tail k_tail_shapes
+#endif
 
 struct F3 {
     float x, y, z;
@@ -179,8 +190,14 @@ struct DevScene {
     const float4 *delta;
     int n_delta;
     float4 dir_sphere;         // DirectionalEmitter::m_bsphere: the geometry box's bounding sphere, radius * 1.1 (directional.cpp:88-94)
+    // analytic disks and cylinders (ppg_set_shapes; FULL kernels, BVH path only): PPG_SHAPE_STRIDE float4 each = rows 0..2 of the 3x4
+    // object-to-world, rows 0..2 of its inverse, (radius, length, invSurfaceArea, type) (material, emitter, flip normals, -); primitive
+    // numbers n_tris + n_spheres, ..
+    const float4 *shapes;
+    int n_shapes;
 };
 #define PPG_DELTA_STRIDE 4
+#define PPG_SHAPE_STRIDE 8
 
 struct Hit {
     float t, u, v;
@@ -283,14 +300,8 @@ struct TStack {
     }
 };
 
-// Sphere::rayIntersect (sphere.cpp:164-189) with solveQuadraticDouble (util.cpp:487-525): double precision, like the reference
-D bool sphere_hit(const float4 c, F3 ro, F3 rd, float mint, float maxt, float &t) {
-    const double ox = (double)ro.x - (double)c.x, oy = (double)ro.y - (double)c.y, oz = (double)ro.z - (double)c.z;
-    const double dx = rd.x, dy = rd.y, dz = rd.z;
-    const double A = dx * dx + dy * dy + dz * dz;
-    const double B = 2 * (ox * dx + oy * dy + oz * dz);
-    const double C = (ox * ox + oy * oy + oz * oz) - c.w * c.w;  // m_radius * m_radius is a float product
-    double nearT, farT;
+// solveQuadraticDouble (util.cpp:487-525)
+D bool solve_quadratic_double(const double A, const double B, const double C, double &nearT, double &farT) {
     if (A == 0) {
         if (B != 0) nearT = farT = -C / B;
         else return false;
@@ -305,6 +316,17 @@ D bool sphere_hit(const float4 c, F3 ro, F3 rd, float mint, float maxt, float &t
         farT = C / temp;
         if (nearT > farT) { const double sw = nearT; nearT = farT; farT = sw; }
     }
+    return true;
+}
+// Sphere::rayIntersect (sphere.cpp:164-189) with solveQuadraticDouble: double precision, like the reference
+D bool sphere_hit(const float4 c, F3 ro, F3 rd, float mint, float maxt, float &t) {
+    const double ox = (double)ro.x - (double)c.x, oy = (double)ro.y - (double)c.y, oz = (double)ro.z - (double)c.z;
+    const double dx = rd.x, dy = rd.y, dz = rd.z;
+    const double A = dx * dx + dy * dy + dz * dz;
+    const double B = 2 * (ox * dx + oy * dy + oz * dz);
+    const double C = (ox * ox + oy * oy + oz * oz) - c.w * c.w;  // m_radius * m_radius is a float product
+    double nearT, farT;
+    if (!solve_quadratic_double(A, B, C, nearT, farT)) return false;
     if (!(nearT <= maxt && farT >= mint)) return false;
     if (nearT < mint) {
         if (farT > maxt) return false;
@@ -321,6 +343,66 @@ D void sphere_pass(const DevScene &S, F3 o, F3 d, float mint, float maxt, Hit &b
         float ts;
         if (sphere_hit(S.spheres[4 * k], o, d, mint, best.prim >= 0 ? fminf(maxt, best.t) : maxt, ts) && (best.prim < 0 || ts < best.t)) {
             best.t = ts; best.u = 0; best.v = 0; best.prim = S.n_tris + k;
+            if (ANY) return;
+        }
+    }
+}
+
+// ---- analytic disks and cylinders (ppg_set_shapes) ----
+// Transform::operator()(Point) / (Vector) of an affine 3x4 whose rows are R[0..2] (transform.h:128-137, 175-183)
+D F3 aff_point(const float4 *R, F3 p) {
+    return f3(R[0].x * p.x + R[0].y * p.y + R[0].z * p.z + R[0].w, R[1].x * p.x + R[1].y * p.y + R[1].z * p.z + R[1].w,
+              R[2].x * p.x + R[2].y * p.y + R[2].z * p.z + R[2].w);
+}
+D F3 aff_vec(const float4 *R, F3 v) {
+    return f3(R[0].x * v.x + R[0].y * v.y + R[0].z * v.z, R[1].x * v.x + R[1].y * v.y + R[1].z * v.z, R[2].x * v.x + R[2].y * v.y + R[2].z * v.z);
+}
+// Transform::operator()(Normal) (transform.h:186-197): the transposed inverse, whose rows are Rinv[0..2]
+D F3 aff_normal(const float4 *Rinv, F3 n) {
+    return f3(Rinv[0].x * n.x + Rinv[1].x * n.y + Rinv[2].x * n.z, Rinv[0].y * n.x + Rinv[1].y * n.y + Rinv[2].y * n.z,
+              Rinv[0].z * n.x + Rinv[1].z * n.y + Rinv[2].z * n.z);
+}
+// Disk::rayIntersect (disk.cpp:139-162) and Cylinder::rayIntersect (cylinder.cpp:128-165; ANY: the form without t, :167-199, whose
+// range tests are not NaN-aware).  The ray goes to object space through the float inverse, mint and maxt as they stand.
+template <bool ANY>
+D bool shape_hit(const float4 *Q, F3 o, F3 d, float mint, float maxt, float &t) {
+    const F3 lo = aff_point(Q + 3, o), ld = aff_vec(Q + 3, d);
+    const float4 q6 = Q[6];
+    if (__float_as_int(q6.w) == PPG_SHAPE_DISK) {
+        const float hit = -lo.z / ld.z;
+        if (!(hit >= mint && hit <= maxt)) return false;
+        const float lx = lo.x + ld.x * hit, ly = lo.y + ld.y * hit;
+        if (!(lx * lx + ly * ly <= 1)) return false;
+        t = hit;
+        return true;
+    }
+    const double ox = lo.x, oy = lo.y, dx = ld.x, dy = ld.y;
+    const double A = dx * dx + dy * dy;
+    const double B = 2 * (dx * ox + dy * oy);
+    const double C = ox * ox + oy * oy - q6.x * q6.x;  // m_radius * m_radius is a float product
+    double nearT, farT;
+    if (!solve_quadratic_double(A, B, C, nearT, farT)) return false;
+    if (ANY) { if (nearT > maxt || farT < mint) return false; }
+    else if (!(nearT <= maxt && farT >= mint)) return false;
+    const double zPosNear = lo.z + ld.z * nearT;
+    const double zPosFar = lo.z + ld.z * farT;
+    if (zPosNear >= 0 && zPosNear <= q6.y && nearT >= mint) {
+        t = (float)nearT;
+    } else if (zPosFar >= 0 && zPosFar <= q6.y) {
+        if (farT > maxt) return false;
+        t = (float)farT;
+    } else {
+        return false;
+    }
+    return true;
+}
+// the shapes after the triangles and the spheres: a shape wins only with a strictly smaller t (its primitive number is larger)
+template <bool ANY>
+D void shape_pass(const DevScene &S, F3 o, F3 d, float mint, float maxt, Hit &best) {
+    for (int k = 0; k < S.n_shapes; ++k) {
+        float ts;
+        if (shape_hit<ANY>(S.shapes + PPG_SHAPE_STRIDE * k, o, d, mint, best.prim >= 0 ? fminf(maxt, best.t) : maxt, ts) && (best.prim < 0 || ts < best.t)) {
+            best.t = ts; best.u = 0; best.v = 0; best.prim = S.n_tris + S.n_spheres + k;
             if (ANY) return;
         }
     }
@@ -488,6 +570,7 @@ D Hit trace_closest4(const DevScene &S, int *lds_stack_col, int stride, F3 o, F3
         }
     }
     if (SPH && S.n_spheres) sphere_pass<ANY>(S, o, d, mint, maxt, best);
+    if (PPG_SHAPES && SPH && S.n_shapes && !(ANY && best.prim >= 0)) shape_pass<ANY>(S, o, d, mint, maxt, best);
     return best;
 }
 
@@ -547,6 +630,7 @@ D bool trace_closest4_resume(const DevScene &S, int *lds_stack_col, int stride, 
         }
     }
     if (SPH && S.n_spheres) sphere_pass<false>(S, o, d, mint, maxt, best);
+    if (PPG_SHAPES && SPH && S.n_shapes) shape_pass<false>(S, o, d, mint, maxt, best);
     return true;
 }
 
@@ -652,6 +736,7 @@ D Hit trace_closest4_wave(const DevScene &S, int *wave_stack /* this wave's colu
         }
     }
     if (S.n_spheres) sphere_pass<false>(S, o, d, mint, maxt, best);
+    if (PPG_SHAPES && S.n_shapes) shape_pass<false>(S, o, d, mint, maxt, best);
     return best;
 }
 
@@ -683,6 +768,39 @@ D void fill_isect_sphere(const DevScene &S, const Hit &h, F3 o, F3 d, Isect &I) 
     I.wi = to_local(I, -d);
     I.material = __float_as_int(r0.w);
     I.emitter = __float_as_int(r1.w);
+}
+// Disk::fillIntersectionRecord (disk.cpp:169-198) and Cylinder::fillIntersectionRecord (cylinder.cpp:201-230), then computeShadingFrame(n,
+// dpdu).  The disk's local hit point is what its ray test kept in `temp`: the same arithmetic again.  Its geometric normal is its shading
+// normal (the reference leaves its.geoFrame unset there: DESIGN.md).  `o` = the ray origin.
+D void fill_isect_shape(const DevScene &S, const Hit &h, F3 o, F3 d, Isect &I) {
+    const float4 *Q = S.shapes + PPG_SHAPE_STRIDE * (h.prim - S.n_tris - S.n_spheres);
+    const float4 q6 = Q[6], q7 = Q[7];
+    F3 p = o + d * h.t, n, dpdu;
+    if (__float_as_int(q6.w) == PPG_SHAPE_DISK) {
+        const F3 lo = aff_point(Q + 3, o), ld = aff_vec(Q + 3, d);
+        const float lx = lo.x + ld.x * h.t, ly = lo.y + ld.y * h.t;
+        const float r = __builtin_sqrtf(lx * lx + ly * ly), invR = (r == 0) ? 0.0f : (1.0f / r);
+        dpdu = aff_vec(Q, r != 0 ? f3(lx * invR, ly * invR, 0.0f) : f3(1.0f, 0.0f, 0.0f));
+        n = norm3(aff_normal(Q + 3, f3(0.0f, 0.0f, 1.0f)));
+    } else {
+        const F3 local = aff_point(Q + 3, p);
+        dpdu = aff_vec(Q, f3(-local.y, local.x, 0.0f) * (2 * PPG_PI_F));
+        const F3 dpdv = aff_vec(Q, f3(0.0f, 0.0f, q6.y));
+        n = cross3(norm3(dpdu), norm3(dpdv));
+        p = p + n * (q6.x - __builtin_sqrtf(local.x * local.x + local.y * local.y));
+    }
+    if (__float_as_int(q7.z)) n = n * -1.0f;
+    I.p = p; I.geoN = n; I.n = n;
+    I.s = norm3(dpdu - n * dot3(n, dpdu));
+    I.t = cross3(n, I.s);
+    I.wi = to_local(I, -d);
+    I.material = __float_as_int(q7.x);
+    I.emitter = __float_as_int(q7.y);
+}
+// a hit that is not a triangle: sphere or shape
+D void fill_isect_analytic(const DevScene &S, const Hit &h, F3 o, F3 d, Isect &I) {
+    if (PPG_SHAPES && h.prim >= S.n_tris + S.n_spheres) fill_isect_shape(S, h, o, d, I);
+    else fill_isect_sphere(S, h, o, d, I);
 }
 D void fill_isect(const DevScene &S, const Hit &h, F3 d, Isect &I) {
     const float4 *T = S.tris + 3 * h.prim;
@@ -1144,6 +1262,34 @@ D float sphere_pdf_direct(const float4 *Q, F3 ref, F3 d, F3 n, float dist) {
     const float invSurfaceArea = 1 / (4 * PPG_PI_F * c4.w * c4.w);
     return invSurfaceArea * dist * dist / ppg_abs(dot3(d, n));
 }
+D void disk_concentric(float sx, float sy, float &px, float &py);  // defined below
+// Disk::samplePosition (disk.cpp:247-255) / Cylinder::samplePosition (cylinder.cpp:232-246), then Shape::sampleDirect (shape.cpp:97-115):
+// the area density (ds.pdf on entry) to solid angle
+D void shape_sample_direct(const float4 *Q, F3 ref, float sx, float sy, DirectSample &ds) {
+    const float4 q6 = Q[6];
+    F3 p, n;
+    if (__float_as_int(q6.w) == PPG_SHAPE_DISK) {
+        float px, py;
+        disk_concentric(sx, sy, px, py);
+        p = aff_point(Q, f3(px, py, 0.0f));
+        n = f3(0.0f, 0.0f, 1.0f);
+    } else {
+        float sinTheta, cosTheta;
+        dm_sincos(sy * (2 * PPG_PI_F), &sinTheta, &cosTheta);
+        p = aff_point(Q, f3(cosTheta * q6.x, sinTheta * q6.x, sx * q6.y));
+        n = f3(cosTheta, sinTheta, 0.0f);
+    }
+    n = norm3(aff_normal(Q + 3, n));
+    if (__float_as_int(Q[7].z)) n = n * -1.0f;
+    ds.n = n;
+    const F3 d = p - ref;
+    const float distSquared = dot3(d, d);
+    ds.dist = __builtin_sqrtf(distSquared);
+    ds.d = div3(d, ds.dist);
+    ds.sd = ds.d; ds.sdist = ds.dist;
+    const float dp = ppg_abs(dot3(ds.d, ds.n));
+    ds.pdf *= dp != 0 ? (distSquared / dp) : 0.0f;
+}
 // PointEmitter / SpotEmitter / DirectionalEmitter::sampleDirect (point.cpp:131-147, spot.cpp:105-125, 184-200, directional.cpp:159-180)
 D F3 delta_sample_direct(const DevScene &S, const float4 *Q, F3 ref, DirectSample &ds) {
     const float4 q0 = Q[0], q1 = Q[1];
@@ -1196,6 +1342,16 @@ D F3 emitter_sample_direct(const DevScene &S, F3 ref, F3 refN, float sx, float s
     if (info.y == 0) return f3s(0.0f);
     if (info.y < 0) {  // the emitter is an analytic sphere: AreaLight::sampleDirect (area.cpp:158-173) on Sphere::sampleDirect
         sphere_sample_direct(S.spheres + 4 * (-info.y - 1), ref, sx, sy, ds);
+        if (!(dot3(ds.d, refN) >= 0 && dot3(ds.d, ds.n) < 0 && ds.pdf != 0)) {
+            ds.pdf = 0.0f;
+            return f3s(0.0f);
+        }
+        const float4 r = S.emitters[e];
+        return div3(f3(r.x, r.y, r.z), ds.pdf);
+    }
+    if (PPG_SHAPES && FULL && info.x < 0) {  // a disk or a cylinder (info.y = 1, so that the hit side takes the generic invSurfaceArea density)
+        ds.pdf = __int_as_float(info.w);
+        shape_sample_direct(S.shapes + PPG_SHAPE_STRIDE * (-info.x - 1), ref, sx, sy, ds);
         if (!(dot3(ds.d, refN) >= 0 && dot3(ds.d, ds.n) < 0 && ds.pdf != 0)) {
             ds.pdf = 0.0f;
             return f3s(0.0f);

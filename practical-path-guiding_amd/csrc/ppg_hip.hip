@@ -823,6 +823,8 @@ struct ppg_ctx {
     std::vector<ppg_material_textures> materialTextures;  // ppg_set_material_textures: kept until replaced; ppg_set_scene validates and packs it
     std::vector<ppg_delta_emitter> deltaEmitters;  // ppg_set_delta_emitters: kept until replaced; ppg_set_scene builds d_delta from it
     DevBuf<float4> d_delta;
+    std::vector<ppg_shape> shapes;  // ppg_set_shapes: kept until replaced; ppg_set_scene validates it and builds d_shapes from it
+    DevBuf<float4> d_shapes;
     bool renderOpen = false;       // between ppg_begin_render and ppg_end_render
     int W = 0, H = 0;
 
@@ -1007,10 +1009,12 @@ struct ppg_ctx {
 };
 
 void ppg_launch_shade(int variant, const ShadeLaunch &a) {
+    if (a.S.n_shapes) { ppg_launch_shade_shapes(variant, a); return; }  // (such a scene is FULL and never small)
     if (variant >> 1) ppg_launch_shade_pair1(variant, a);
     else ppg_launch_shade_pair0(variant, a);
 }
 void ppg_launch_tail(int variant, const TailLaunch &a) {
+    if (a.S.n_shapes) { ppg_launch_tail_shapes(variant, a); return; }
     switch (variant >> 1) {
         case 0: ppg_launch_tail_pair0(variant, a); break;
         case 1: ppg_launch_tail_pair1(variant, a); break;
@@ -1830,7 +1834,7 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
         if (((chunks + (size_t)ctx->tuneBlocksSmall - 1) / (size_t)ctx->tuneBlocksSmall) * PPG_DCHUNK <= (size_t)ctx->queues.cap) grid = ctx->tuneBlocksSmall;
     }
     const int gridAll = gridFor(P.n_paths);
-    const bool smallScene = ctx->scene.n_tris <= 64 && ctx->ldsTris == ctx->scene.n_tris && ctx->scene.n_spheres == 0 && !ctx->tuneForceBvh;
+    const bool smallScene = ctx->scene.n_tris <= 64 && ctx->ldsTris == ctx->scene.n_tris && ctx->scene.n_spheres == 0 && ctx->scene.n_shapes == 0 && !ctx->tuneForceBvh;
     // (small scenes go through k_trace too: tracing them inside k_generate / k_shade was measured slower, DESIGN.md "Tuning switches")
     const bool neeOn = ctx->doNee;  // m_doNee of this iteration (doNeeWithSpp, GP:1331-1340)
     const bool fullMats = ctx->fullMaterials;  // any BSDF beyond diffuse / two-sided diffuse / mirror: the FULL kernel variants
@@ -1890,13 +1894,18 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
             unsigned int *const trSorted = sortSlices ? ctx->d_queueSorted.p : nullptr;
             unsigned char *const trKeys = sortSlices ? ctx->d_sortKeys.p : nullptr;
             timedLaunch(ctx, "k_trace", hostCount, [&] {
-                if (smallScene) hipLaunchKernelGGL((k_trace<true, false>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, 0, ctx->ldsTris, trSorted, trKeys);
+                if (S.n_shapes) ppg_launch_trace_shapes(ctx->timer.enabled, grid, traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
+                else if (smallScene) hipLaunchKernelGGL((k_trace<true, false>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, 0, ctx->ldsTris, trSorted, trKeys);
                 else if (ctx->timer.enabled) hipLaunchKernelGGL((k_trace<false, true>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
                 else hipLaunchKernelGGL((k_trace<false, false>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
             });
             int shadeIn = sortSlices ? QIN_SORTED : qin;
             ctx->joinTree();  // (k_generate and the first k_trace ran beside the previous round's optimiser: k_shade needs its result)
             // FULL scene, sorted slice, no luminaire sampling: the common material classes first, in their own leaner kernel (MSET_COMMON)
+            // (also for a scene with disks or cylinders, although this kernel is compiled without their code: it shades triangle hits of the
+            // common classes only — sort_slice keeps every non-triangle hit out of them —, traces nothing and, without luminaire sampling,
+            // never calls emitter_sample_direct, where a shape's em_info entry would be read as a triangle range.  A variant of it that
+            // traces or samples emitters must go to the PPG_SHAPES units like the others: ppg_launch_shade / ppg_launch_tail.)
             const bool split = shadeIn == QIN_SORTED && Q.n_common && !neeOn;
             if (split) {
                 timedLaunch(ctx, "k_shade<common>", hostCount, [&] {
@@ -2885,9 +2894,50 @@ static void envBSphere(ppg_ctx *ctx) {
     ctx->scene.bsphere = make_float4(c[0], c[1], c[2], ppg_max(PPG_EPSILON, std::sqrt(r2) * 1.5f));
 }
 
+// One record of ppg_set_shapes: Mitsuba's own checks (disk.cpp:101-112; cylinder.cpp:99-107 leaves a rotation) and the inverse of its
+// affine transform (in double, rounded once).
+static bool shapeCheck(const ppg_shape &sh, float *inv, std::string &err) {
+    if (sh.type != PPG_SHAPE_DISK && sh.type != PPG_SHAPE_CYLINDER) { err = "unknown type"; return false; }
+    const float *m = sh.to_world;
+    for (int i = 0; i < 12; ++i) if (!std::isfinite(m[i])) { err = "a value is not finite"; return false; }
+    const bool cyl = sh.type == PPG_SHAPE_CYLINDER;
+    if (cyl && (!std::isfinite(sh.radius) || !std::isfinite(sh.length))) { err = "a value is not finite"; return false; }
+    if (cyl && !(sh.radius > 0)) { err = "cylinder: radius must be > 0"; return false; }
+    if (cyl && !(sh.length > 0)) { err = "cylinder: length must be > 0"; return false; }
+    double c[3][3], len[3];
+    for (int j = 0; j < 3; ++j) {
+        for (int a = 0; a < 3; ++a) c[j][a] = m[4 * a + j];
+        len[j] = std::sqrt(c[j][0] * c[j][0] + c[j][1] * c[j][1] + c[j][2] * c[j][2]);
+    }
+    const double det = c[0][0] * (c[1][1] * c[2][2] - c[1][2] * c[2][1]) - c[0][1] * (c[1][0] * c[2][2] - c[1][2] * c[2][0]) +
+                       c[0][2] * (c[1][0] * c[2][1] - c[1][1] * c[2][0]);
+    if (len[0] == 0 || len[1] == 0 || len[2] == 0 || !(std::abs(det) > 1e-9 * len[0] * len[1] * len[2])) { err = "its transformation is singular"; return false; }
+    auto ndot = [&](int i, int j) { return std::abs((c[i][0] * c[j][0] + c[i][1] * c[j][1] + c[i][2] * c[j][2]) / (len[i] * len[j])); };
+    if (!cyl) {
+        if (ndot(0, 1) > 1e-3) { err = "disk: its transformation contains shear"; return false; }
+        if (std::abs(len[0] / len[1] - 1) > 1e-3) { err = "disk: its transformation contains a non-uniform scale"; return false; }
+    } else {
+        if (ndot(0, 1) > 1e-3 || ndot(0, 2) > 1e-3 || ndot(1, 2) > 1e-3 || std::abs(len[0] / len[1] - 1) > 1e-3 || std::abs(len[0] / len[2] - 1) > 1e-3 ||
+            std::abs(len[0] - 1) > 1e-3) {
+            err = "cylinder: the linear part of its transformation is not a rotation (the scale belongs in radius and length)"; return false;
+        }
+    }
+    // inverse of [L | t]: [L^-1 | -L^-1 t]; row i of L^-1 = cross products of L's columns / det
+    double li[3][3];
+    for (int i = 0; i < 3; ++i) {
+        const double *a = c[(i + 1) % 3], *b = c[(i + 2) % 3];
+        li[i][0] = (a[1] * b[2] - a[2] * b[1]) / det; li[i][1] = (a[2] * b[0] - a[0] * b[2]) / det; li[i][2] = (a[0] * b[1] - a[1] * b[0]) / det;
+    }
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) inv[4 * i + j] = (float)li[i][j];
+        inv[4 * i + 3] = (float)-(li[i][0] * (double)m[3] + li[i][1] * (double)m[7] + li[i][2] * (double)m[11]);
+    }
+    return true;
+}
+
 int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
-    // a scene needs materials and at least one primitive; triangle arrays may be absent when it consists of analytic spheres only
-    if (!s || !s->materials || (s->n_triangles == 0 && s->n_spheres == 0) ||
+    // a scene needs materials and at least one primitive; triangle arrays may be absent when it consists of analytic shapes only
+    if (!s || !s->materials || (s->n_triangles == 0 && s->n_spheres == 0 && ctx->shapes.empty()) ||
         (s->n_triangles > 0 && (!s->positions || !s->indices || !s->tri_material || !s->tri_emitter))) {
         ctx->error = "incomplete scene";
         return PPG_ERR_INVALID;
@@ -2913,12 +2963,47 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
             if (sp.emitter >= 0) emitterSphere[sp.emitter] = (int)k;
         }
     }
+    std::vector<int> emitterShape(s->n_emitters, -1);  // per emitter: the disk or cylinder carrying it
+    std::vector<float> shapeInv(12 * ctx->shapes.size());  // the inverses, row-major 3x4
+    if (!ctx->shapes.empty()) {
+        std::vector<int> users(s->n_emitters, 0);
+        for (uint32_t t = 0; t < s->n_triangles; ++t) if (s->tri_emitter[t] >= 0) users[s->tri_emitter[t]] = 1;
+        for (uint32_t k = 0; k < s->n_spheres; ++k) if (s->spheres[k].emitter >= 0) users[s->spheres[k].emitter] = 1;
+        for (size_t k = 0; k < ctx->shapes.size(); ++k) {
+            std::string err;
+            if (!shapeCheck(ctx->shapes[k], &shapeInv[12 * k], err)) { ctx->error = "shape " + std::to_string(k) + ": " + err; return PPG_ERR_INVALID; }
+            const ppg_shape &sh = ctx->shapes[k];
+            const std::string who = "shape " + std::to_string(k) + ": ";
+            if (sh.material >= s->n_materials) { ctx->error = who + "material index out of range"; return PPG_ERR_INVALID; }
+            if (sh.emitter >= (int32_t)s->n_emitters) { ctx->error = who + "emitter index out of range"; return PPG_ERR_INVALID; }
+            if (s->materials[sh.material].type < 0 || s->materials[sh.material].type > PPG_BSDF_LAST) { ctx->error = who + "unsupported BSDF type"; return PPG_ERR_INVALID; }
+            if (sh.emitter >= 0 && users[sh.emitter]++) { ctx->error = who + "its emitter is shared with another shape"; return PPG_ERR_INVALID; }
+            if (sh.emitter >= 0) emitterShape[sh.emitter] = (int)k;
+        }
+    }
     // Scene::getAABB(): kd-tree box enlarged by MTS_KD_AABB_EPSILON (gkdtree.h:1213-1220) + sensor position (scene.cpp:386-414)
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (size_t t = 0; t < 3 * (size_t)s->n_triangles; ++t)
         for (int a = 0; a < 3; ++a) { float v = s->positions[3 * s->indices[t] + a]; mn[a] = ppg_min(mn[a], v); mx[a] = ppg_max(mx[a], v); }
     for (uint32_t k = 0; k < s->n_spheres; ++k)  // Sphere::getAABB, sphere.cpp:152-157
         for (int a = 0; a < 3; ++a) { mn[a] = ppg_min(mn[a], s->spheres[k].center[a] - s->spheres[k].radius); mx[a] = ppg_max(mx[a], s->spheres[k].center[a] + s->spheres[k].radius); }
+    for (const ppg_shape &sh : ctx->shapes) {
+        const float *m = sh.to_world;
+        for (int a = 0; a < 3; ++a) {
+            if (sh.type == PPG_SHAPE_DISK) {  // Disk::getAABB, disk.cpp:117-130: the points (+-1, 0, 0), (0, +-1, 0) transformed
+                for (int c = 0; c < 2; ++c) for (int sg = 0; sg < 2; ++sg) {
+                    const float v = (sg ? -m[4 * a + c] : m[4 * a + c]) + m[4 * a + 3];
+                    mn[a] = ppg_min(mn[a], v); mx[a] = ppg_max(mx[a], v);
+                }
+            } else {  // Cylinder::getAABB, cylinder.cpp:252-273: the two end circles, component-wise
+                const float x1 = m[4 * a] * sh.radius, x2 = m[4 * a + 1] * sh.radius;
+                const float p0 = m[4 * a + 3], p1 = m[4 * a + 2] * sh.length + m[4 * a + 3];
+                const float range = std::sqrt(x1 * x1 + x2 * x2);
+                mn[a] = ppg_min(ppg_min(mn[a], p0 - range), p1 - range);
+                mx[a] = ppg_max(ppg_max(mx[a], p0 + range), p1 + range);
+            }
+        }
+    }
     const float eps = 1e-3f;
     for (int a = 0; a < 3; ++a) {
         ctx->geomMin[a] = mn[a] - ((mx[a] - mn[a]) * eps + eps);
@@ -3008,9 +3093,17 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
     }
     for (uint32_t k = 0; k < s->n_spheres; ++k) {
         const uint32_t sm = s->spheres[k].material;
-        if (s->materials[sm].texture) { ctx->error = "sphere: textured BSDFs are only supported on triangle meshes"; return PPG_ERR_INVALID; }
+        if (s->materials[sm].texture) { ctx->error = "sphere: textured BSDFs are only supported on triangle meshes (not on spheres, disks or cylinders)"; return PPG_ERR_INVALID; }
         if (!ctx->materialTextures.empty() && (ctx->materialTextures[sm].specular || ctx->materialTextures[sm].alpha || ctx->materialTextures[sm].opacity)) {
             ctx->error = "sphere: material " + std::to_string(sm) + ": a texture slot (specular / alpha / opacity) is set; textured BSDFs are only supported on triangle meshes";
+            return PPG_ERR_INVALID;
+        }
+    }
+    for (size_t k = 0; k < ctx->shapes.size(); ++k) {
+        const uint32_t sm = ctx->shapes[k].material;
+        if (s->materials[sm].texture) { ctx->error = "shape " + std::to_string(k) + ": textured BSDFs are only supported on triangle meshes"; return PPG_ERR_INVALID; }
+        if (!ctx->materialTextures.empty() && (ctx->materialTextures[sm].specular || ctx->materialTextures[sm].alpha || ctx->materialTextures[sm].opacity)) {
+            ctx->error = "shape " + std::to_string(k) + ": material " + std::to_string(sm) + ": a texture slot (specular / alpha / opacity) is set; textured BSDFs are only supported on triangle meshes";
             return PPG_ERR_INVALID;
         }
     }
@@ -3172,6 +3265,17 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
             if (!emTris[e].empty()) { normalize(areaCdf, first, emTris[e].size() + 1, area); inv = 1.0f / area; }
             info[e] = make_int4(firstTri, (int)emTris[e].size(), (int)first, __builtin_bit_cast(int, inv));
             if (emitterSphere[e] >= 0) info[e].y = -(emitterSphere[e] + 1);  // sampled analytically (sphere_sample_direct)
+            if (emitterShape[e] >= 0) {  // a disk or a cylinder: (-(shape + 1), 1, -, invSurfaceArea): sampled by shape_sample_direct; on the hit
+                                         // side the count of 1 sends it down the generic invSurfaceArea * dist^2 / |dn| density
+                const ppg_shape &sh = ctx->shapes[emitterShape[e]];
+                float invArea;
+                if (sh.type == PPG_SHAPE_DISK) {  // Disk::configure, disk.cpp:101-115
+                    const float *m = sh.to_world;
+                    const float len = std::sqrt(m[0] * m[0] + m[4] * m[4] + m[8] * m[8]);
+                    invArea = 1.0f / (PPG_PI_F * len * len);
+                } else invArea = 1 / (2 * PPG_PI_F * sh.radius * sh.length);  // cylinder.cpp:106
+                info[e] = make_int4(-(emitterShape[e] + 1), 1, (int)first, __builtin_bit_cast(int, invArea));
+            }
             selCdf.push_back(selCdf.back() + 1.0f);
         }
         for (size_t k = 0; k < ctx->deltaEmitters.size(); ++k) selCdf.push_back(selCdf.back() + 1.0f);  // delta emitters follow the area emitters
@@ -3228,6 +3332,25 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
         }
         ctx->fullMaterials = true;  // the delta-emitter code lives in the FULL kernel variants
     }
+    S.shapes = nullptr; S.n_shapes = (int)ctx->shapes.size();
+    if (S.n_shapes) {
+        std::vector<float4> tab(PPG_SHAPE_STRIDE * ctx->shapes.size());
+        for (size_t k = 0; k < ctx->shapes.size(); ++k) {
+            const ppg_shape &sh = ctx->shapes[k];
+            float4 *Q = &tab[PPG_SHAPE_STRIDE * k];
+            const float *m = sh.to_world, *iv = &shapeInv[12 * k];
+            for (int r = 0; r < 3; ++r) {
+                Q[r] = make_float4(m[4 * r], m[4 * r + 1], m[4 * r + 2], m[4 * r + 3]);
+                Q[3 + r] = make_float4(iv[4 * r], iv[4 * r + 1], iv[4 * r + 2], iv[4 * r + 3]);
+            }
+            Q[6] = make_float4(sh.type == PPG_SHAPE_CYLINDER ? sh.radius : 1.0f, sh.type == PPG_SHAPE_CYLINDER ? sh.length : 0.0f, 0.0f, __builtin_bit_cast(float, (int)sh.type));
+            Q[7] = make_float4(__builtin_bit_cast(float, (int)sh.material), __builtin_bit_cast(float, sh.emitter), __builtin_bit_cast(float, sh.flip_normals ? 1 : 0), 0.0f);
+        }
+        HIP_CHECK(ctx->d_shapes.reserve(tab.size()));
+        HIP_CHECK(hipMemcpy(ctx->d_shapes.p, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice));
+        S.shapes = ctx->d_shapes.p;
+        ctx->fullMaterials = true;  // the shape code lives in the FULL kernel variants, on the BVH path
+    }
     if (s->n_spheres) {
         std::vector<float4> sph(4 * (size_t)s->n_spheres);
         for (uint32_t k = 0; k < s->n_spheres; ++k) {
@@ -3256,7 +3379,8 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
     }
     // Every array the path kernels walk must be there before a launch can chase it: an unset pointer here is a hung GPU, not a wrong pixel
     // (round 5 lost 40 GPU minutes to five assignments that an edit had turned into a comment).
-    if (!S.materials || !S.bvh4 || (S.n_tris > 0 && (!S.tris || !S.accel || !S.bvh)) || (S.n_spheres > 0 && !S.spheres) || (S.n_delta > 0 && !S.delta)) {
+    if (!S.materials || !S.bvh4 || (S.n_tris > 0 && (!S.tris || !S.accel || !S.bvh)) || (S.n_spheres > 0 && !S.spheres) || (S.n_delta > 0 && !S.delta) ||
+        (S.n_shapes > 0 && !S.shapes)) {
         ctx->error = "internal: device scene incomplete";
         return PPG_ERR_STATE;
     }
@@ -3592,6 +3716,61 @@ int ppg_set_delta_emitters(ppg_ctx *ctx, const ppg_delta_emitter *em, uint32_t n
         if (e.type == PPG_EMITTER_DIRECTIONAL && e.direction[0] == 0 && e.direction[1] == 0 && e.direction[2] == 0) { ctx->error = who + "zero direction"; return PPG_ERR_INVALID; }
     }
     ctx->deltaEmitters.assign(em, em + n);
+    return PPG_OK;
+}
+
+int ppg_set_shapes(ppg_ctx *ctx, const ppg_shape *shapes, uint32_t n) {
+    if (ctx->renderOpen) { ctx->error = "shapes: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (n && !shapes) { ctx->error = "shapes: no list"; return PPG_ERR_INVALID; }
+    ctx->shapes.assign(shapes, shapes + n);  // validated against the scene by ppg_set_scene
+    return PPG_OK;
+}
+
+// ---- include/ppg_testhooks.h: the render's own device functions, one item per lane (the kernels: ppg_inst.hip, the shapes unit) ----
+struct DebugBuf {  // a device array for the length of one hook call
+    void *p = nullptr;
+    ~DebugBuf() { if (p) (void)hipFree(p); }
+    hipError_t fill(const void *src, size_t bytes) {
+        hipError_t e = hipMalloc(&p, std::max<size_t>(16, bytes));
+        if (e == hipSuccess && src && bytes) e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
+        return e;
+    }
+};
+int ppg_debug_intersect(ppg_ctx *ctx, uint32_t n, const float *rays, ppg_debug_hit *out, int32_t any_hit) {
+    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
+    if (ctx->renderOpen) { ctx->error = "ppg_debug_intersect: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (n && (!rays || !out)) { ctx->error = "ppg_debug_intersect: no arrays"; return PPG_ERR_INVALID; }
+    if (n == 0) return PPG_OK;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->quiesce();
+    DebugBuf dRays, dOut;
+    HIP_CHECK(dRays.fill(rays, 2 * (size_t)n * sizeof(float4)));
+    HIP_CHECK(dOut.fill(nullptr, (size_t)n * sizeof(ppg_debug_hit)));
+    const unsigned int block = 64;
+    ppg_launch_debug_intersect((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const float4 *)dRays.p, (ppg_debug_hit *)dOut.p, any_hit ? 1 : 0);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_hit), hipMemcpyDeviceToHost));
+    return PPG_OK;
+}
+int ppg_debug_sample_direct(ppg_ctx *ctx, uint32_t n, const float *ref, const float *ref_n, const float *u, ppg_debug_direct *out) {
+    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
+    if (ctx->renderOpen) { ctx->error = "ppg_debug_sample_direct: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (n && (!ref || !ref_n || !u || !out)) { ctx->error = "ppg_debug_sample_direct: no arrays"; return PPG_ERR_INVALID; }
+    if (n == 0) return PPG_OK;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->quiesce();
+    DebugBuf dRef, dRefN, dU, dOut;
+    HIP_CHECK(dRef.fill(ref, 3 * (size_t)n * sizeof(float)));
+    HIP_CHECK(dRefN.fill(ref_n, 3 * (size_t)n * sizeof(float)));
+    HIP_CHECK(dU.fill(u, 2 * (size_t)n * sizeof(float)));
+    HIP_CHECK(dOut.fill(nullptr, (size_t)n * sizeof(ppg_debug_direct)));
+    const unsigned int block = 64;
+    ppg_launch_debug_sample_direct((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const float *)dRef.p, (const float *)dRefN.p, (const float *)dU.p,
+                                   (ppg_debug_direct *)dOut.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_direct), hipMemcpyDeviceToHost));
     return PPG_OK;
 }
 

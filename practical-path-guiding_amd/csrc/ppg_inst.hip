@@ -2,6 +2,9 @@
  * ppg_inst.hip — one pair of instantiations of a large path kernel per translation unit (ppg_launch.h): compiled with
  * -DPPG_INST=0..1 (k_shade: NEE, both FULL settings), 2..5 (k_tail: SMALL x NEE, both FULL settings), 6 (k_commit, all six, with
  * k_commit_records and k_splat_sorted), 7 (k_shade<false, FULL, MSET_COMMON>: the common material classes of a FULL scene).
+ * 8..10, compiled with -DPPG_SHAPES=1 as well: the kernels of scenes with analytic disks or cylinders (ppg_device.h PPG_SHAPES) — 8
+ * k_shade_shapes<NEE, true>, 9 k_tail_shapes<false, NEE, true>, 10 k_trace_shapes<false, COUNT> and the two kernels of the test hooks
+ * ppg_debug_intersect / ppg_debug_sample_direct.
  */
 #include <hip/hip_runtime.h>
 
@@ -11,10 +14,85 @@
 #include "ppg_launch.h"
 
 #ifndef PPG_INST
-#error "compile with -DPPG_INST=0..7"
+#error "compile with -DPPG_INST=0..10"
+#endif
+#if (PPG_INST >= 8) != (PPG_SHAPES != 0)
+#error "units 8..10, and only they, are compiled with -DPPG_SHAPES=1"
 #endif
 
-#if PPG_INST < 2
+#if PPG_INST == 8
+void ppg_launch_shade_shapes(int variant, const ShadeLaunch &a) {
+    if (variant & 2)
+        hipLaunchKernelGGL((k_shade<true, true>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, a.P, a.S, a.T, a.R, a.Q, a.qin, a.small_scene, a.sorted_items);
+    else
+        hipLaunchKernelGGL((k_shade<false, true>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, a.P, a.S, a.T, a.R, a.Q, a.qin, a.small_scene, a.sorted_items);
+}
+#elif PPG_INST == 9
+void ppg_launch_tail_shapes(int variant, const TailLaunch &a) {
+    if (variant & 2)
+        hipLaunchKernelGGL((k_tail<false, true, true>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, a.P, a.S, a.T, a.R, a.dense, a.total, a.ticket, a.stats, a.lds_tris, a.longest, a.strag, a.lane_limit);
+    else
+        hipLaunchKernelGGL((k_tail<false, false, true>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, a.P, a.S, a.T, a.R, a.dense, a.total, a.ticket, a.stats, a.lds_tris, a.longest, a.strag, a.lane_limit);
+}
+#elif PPG_INST == 10
+#include "../../include/ppg_testhooks.h"
+void ppg_launch_trace_shapes(bool count, int grid, size_t lds, hipStream_t stream, const PathState &P, const DevScene &S, const Queues &Q, int qin, int lds_nodes,
+                             int lds_tris, unsigned int *sorted, unsigned char *keys) {
+    if (count) hipLaunchKernelGGL((k_trace<false, true>), dim3(grid), dim3(PPG_BLOCK), lds, stream, P, S, Q, qin, lds_nodes, lds_tris, sorted, keys);
+    else hipLaunchKernelGGL((k_trace<false, false>), dim3(grid), dim3(PPG_BLOCK), lds, stream, P, S, Q, qin, lds_nodes, lds_tris, sorted, keys);
+}
+__global__ void k_debug_intersect(DevScene S, unsigned int n, const float4 *rays, ppg_debug_hit *out, int any) {
+    extern __shared__ int dbg_stack[];
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 ro = rays[2 * i], rd = rays[2 * i + 1];
+    const F3 o = f3(ro.x, ro.y, ro.z), d = f3(rd.x, rd.y, rd.z);
+    ppg_debug_hit r;
+    memset(&r, 0, sizeof r);
+    r.material = -1; r.emitter = -1;
+    Hit h;
+    if (any) h = trace_closest4<true, true>(S, dbg_stack + threadIdx.x, (int)blockDim.x, o, d, ro.w, rd.w);
+    else h = trace_closest4<false, true>(S, dbg_stack + threadIdx.x, (int)blockDim.x, o, d, ro.w, rd.w);
+    r.prim = h.prim;
+    if (h.prim >= 0) {
+        r.t = h.t;
+        if (!any) {
+            Isect I;
+            fill_isect_full(S, h, o, d, I);
+            r.p[0] = I.p.x; r.p[1] = I.p.y; r.p[2] = I.p.z;
+            r.geo_n[0] = I.geoN.x; r.geo_n[1] = I.geoN.y; r.geo_n[2] = I.geoN.z;
+            r.n[0] = I.n.x; r.n[1] = I.n.y; r.n[2] = I.n.z;
+            r.s[0] = I.s.x; r.s[1] = I.s.y; r.s[2] = I.s.z;
+            r.wi[0] = I.wi.x; r.wi[1] = I.wi.y; r.wi[2] = I.wi.z;
+            r.material = I.material; r.emitter = I.emitter;
+        }
+    }
+    out[i] = r;
+}
+__global__ void k_debug_sample_direct(DevScene S, unsigned int n, const float *ref, const float *refN, const float *u, ppg_debug_direct *out) {
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    DirectSample ds;
+    const F3 value = emitter_sample_direct<true>(S, f3(ref[3 * i], ref[3 * i + 1], ref[3 * i + 2]), f3(refN[3 * i], refN[3 * i + 1], refN[3 * i + 2]),
+                                                 u[2 * i], u[2 * i + 1], ds);
+    ppg_debug_direct r;
+    memset(&r, 0, sizeof r);
+    const int n_sel = S.n_emitters + S.n_delta + (S.env.w != 0 ? 1 : 0);
+    r.emitter = n_sel ? pmf_sample(S.em_sel_cdf, n_sel + 1, u[2 * i]) : -1;  // the choice emitter_sample_direct makes
+    r.d[0] = ds.d.x; r.d[1] = ds.d.y; r.d[2] = ds.d.z; r.dist = ds.dist;
+    r.n[0] = ds.n.x; r.n[1] = ds.n.y; r.n[2] = ds.n.z;
+    r.pdf = ds.pdf; r.em_pdf = ds.em_pdf;
+    r.value[0] = value.x; r.value[1] = value.y; r.value[2] = value.z;
+    out[i] = r;
+}
+void ppg_launch_debug_intersect(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_hit *out, int any) {
+    hipLaunchKernelGGL(k_debug_intersect, dim3(grid), dim3(block), (size_t)PPG_LDS_STACK * block * sizeof(int), stream, S, n, rays, out, any);
+}
+void ppg_launch_debug_sample_direct(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float *ref, const float *ref_n, const float *u,
+                                    ppg_debug_direct *out) {
+    hipLaunchKernelGGL(k_debug_sample_direct, dim3(grid), dim3(block), 0, stream, S, n, ref, ref_n, u, out);
+}
+#elif PPG_INST < 2
 #define PAIR_N (PPG_INST != 0)
 #define PPG_CAT2(a, b) a##b
 #define PPG_CAT(a, b) PPG_CAT2(a, b)

@@ -441,6 +441,7 @@ D void trace_slice_bvh4(const PathState &P, const DevScene &S, int *lds_stack, u
         }
         if (have && cur == PPG_BVH4_EMPTY) {  // stack empty: this ray is done
             if (S.n_spheres) sphere_pass<false>(S, o, d, mint, maxt, best);
+            if (PPG_SHAPES && S.n_shapes) shape_pass<false>(S, o, d, mint, maxt, best);
             P.hit[i] = make_float4(best.t, best.u, best.v, __int_as_float(best.prim));
             ++traced;
             have = false;
@@ -482,7 +483,7 @@ D void sort_slice(const SortArgs &a, const Work &work, unsigned int b, unsigned 
         unsigned int key = 255u;  // no path at this position (partial last chunk)
         if (i < a.n_paths) {
             // bins 0..7: the COMMON classes (MSET_COMMON), by BSDF type; 8..15: everything else — by type, then bump-mapped or masked
-            // surfaces, spheres, and last the rays that left the scene
+            // surfaces, spheres / disks / cylinders, and last the rays that left the scene
             const int prim = __float_as_int(a.hit[i].w);
             key = 15u;
             if (prim >= 0) {
@@ -852,7 +853,7 @@ D Hit trace_inline(const DevScene &S, const float4 *small_tris, int *stack_col, 
 }
 // intersection record of a hit found by trace_inline / k_trace in a FULL kernel: triangle or sphere (`o` = that ray's origin)
 D void fill_isect_full(const DevScene &S, const Hit &h, F3 o, F3 d, Isect &I) {
-    if (h.prim >= S.n_tris) fill_isect_sphere(S, h, o, d, I);
+    if (h.prim >= S.n_tris) fill_isect_analytic(S, h, o, d, I);
     else fill_isect(S, h, d, I);
 }
 // ... and its material, of a hit whose null component may be evaluated (shadow_transmittance, the look-through loop of shade_one): with
@@ -939,7 +940,7 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
     if (valid) {
         if (FULL && MSET != MSET_COMMON && h.prim >= S.n_tris) {
             const float4 ro4 = ray_origin();
-            fill_isect_sphere(S, h, f3(ro4.x, ro4.y, ro4.z), d, I);
+            fill_isect_analytic(S, h, f3(ro4.x, ro4.y, ro4.z), d, I);
         } else if (FULL) fill_isect_tex<MSET != MSET_COMMON>(S, h, d, I, X);
         else fill_isect(S, h, d, I);
     }

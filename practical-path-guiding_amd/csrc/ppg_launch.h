@@ -69,6 +69,17 @@ void ppg_launch_tail_pair0(int variant, const TailLaunch &a);
 void ppg_launch_tail_pair1(int variant, const TailLaunch &a);
 void ppg_launch_tail_pair2(int variant, const TailLaunch &a);
 void ppg_launch_tail_pair3(int variant, const TailLaunch &a);
+// Scenes with analytic disks or cylinders (ppg_set_shapes): the FULL kernels built with -DPPG_SHAPES=1, in three units of their own —
+// k_shade_shapes<NEE, true>, k_tail_shapes<false, NEE, true>, k_trace_shapes<false, COUNT> with the test hooks' two kernels
+void ppg_launch_shade_shapes(int variant, const ShadeLaunch &a);
+void ppg_launch_tail_shapes(int variant, const TailLaunch &a);
+void ppg_launch_trace_shapes(bool count, int grid, size_t lds, hipStream_t stream, const PathState &P, const DevScene &S, const Queues &Q, int qin, int lds_nodes,
+                             int lds_tris, unsigned int *sorted, unsigned char *keys);
+struct ppg_debug_hit;
+struct ppg_debug_direct;
+void ppg_launch_debug_intersect(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_hit *out, int any);
+void ppg_launch_debug_sample_direct(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float *ref, const float *ref_n, const float *u,
+                                    ppg_debug_direct *out);
 // k_shade<false, FULL, MSET_COMMON> over the front part of the sorted slices (a.qin = QIN_SORTED_COMMON)
 void ppg_launch_shade_common(const ShadeLaunch &a);
 

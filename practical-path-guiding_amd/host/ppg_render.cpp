@@ -121,7 +121,15 @@ static bool loadSceneChecked(const char *path, SceneData &s) {
         s.materialTextures.resize(nm);
         f.read((char *)s.materialTextures.data(), (std::streamsize)((size_t)nm * sizeof(ppg_material_textures)));
     }
-    if (hdr[5] >> 10) return false;  // a block this reader does not know
+    if (hdr[5] & 1024) {  // bit 10: analytic disks and cylinders (uint32 n, n x ppg_shape), only when there are any
+        uint32_t n = 0;
+        if (!fits(4)) return false;
+        f.read((char *)&n, 4);
+        if (!fits((uint64_t)n * sizeof(ppg_shape))) return false;
+        s.shapes.resize(n);
+        f.read((char *)s.shapes.data(), (std::streamsize)(n * sizeof(ppg_shape)));
+    }
+    if (hdr[5] >> 11) return false;  // a block this reader does not know
     return (bool)f;
 }
 
@@ -192,7 +200,7 @@ static bool saveScene(const char *path, const SceneData &s) {
     const uint32_t hdr[6] = {(uint32_t)(s.positions.size() / 3), (uint32_t)(s.indices.size() / 3), (uint32_t)s.materials.size(), (uint32_t)s.emitters.size(),
                              s.normals.empty() ? 0u : 1u, (s.hasEnvironment ? 1u : 0u) | (s.rtrans.empty() ? 0u : 2u) | (s.spheres.empty() ? 0u : 4u) | (s.hasEnvmap ? 8u : 0u) |
                                  (s.texcoords.empty() ? 0u : 16u) | (s.textures.empty() ? 0u : 32u) | (s.hasRFilter ? 64u : 0u) | (s.hasLens ? 128u : 0u) |
-                                 (s.deltaEmitters.empty() ? 0u : 256u) | (s.materialTextures.empty() ? 0u : 512u)};
+                                 (s.deltaEmitters.empty() ? 0u : 256u) | (s.materialTextures.empty() ? 0u : 512u) | (s.shapes.empty() ? 0u : 1024u)};
     f.write("PPGS", 4); f.write((const char *)hdr, sizeof hdr);
     f.write((const char *)s.positions.data(), s.positions.size() * 4);
     if (!s.normals.empty()) f.write((const char *)s.normals.data(), s.normals.size() * 4);
@@ -237,6 +245,11 @@ static bool saveScene(const char *path, const SceneData &s) {
         f.write((const char *)s.deltaEmitters.data(), (std::streamsize)(n * sizeof(ppg_delta_emitter)));
     }
     if (!s.materialTextures.empty()) f.write((const char *)s.materialTextures.data(), (std::streamsize)(s.materialTextures.size() * sizeof(ppg_material_textures)));
+    if (!s.shapes.empty()) {
+        const uint32_t n = (uint32_t)s.shapes.size();
+        f.write((const char *)&n, 4);
+        f.write((const char *)s.shapes.data(), (std::streamsize)(n * sizeof(ppg_shape)));
+    }
     return (bool)f;
 }
 
@@ -335,6 +348,7 @@ int main(int argc, char **argv) {
         core.setLens(scene.hasLens ? &scene.lens : nullptr);
         core.setDeltaEmitters(scene.deltaEmitters.data(), scene.deltaEmitters.size());
         core.setMaterialTextures(scene.materialTextures.data(), scene.materialTextures.size());
+        core.setShapes(scene.shapes.data(), scene.shapes.size());
         core.setSeed((uint64_t)std::stoull(props.getString("seed", "0")));
         std::string dest = out;
         const size_t dot = dest.find_last_of('.');

@@ -16,7 +16,8 @@
  *   geometry    walks scene->getShapes(): every TriMesh (obj, ply, serialized, rectangle, cube, ... all become TriMesh objects) is appended
  *               to one vertex / index array in WORLD space exactly as Mitsuba holds it — positions, vertex normals, texture coordinates —
  *               so OBJ semantics (vertex merging, maxSmoothAngle, flipTexCoords, computeNormals) are Mitsuba's own; `sphere` shapes become
- *               ppg_sphere records (centre, radius, rotation, flipNormals from the shape's Properties, sphere.cpp:108-131)
+ *               ppg_sphere records (centre, radius, rotation, flipNormals from the shape's Properties, sphere.cpp:108-131), `disk` and
+ *               `cylinder` shapes ppg_shape records (disk.cpp:83-88, cylinder.cpp:82-108)
  *   BSDFs       Mitsuba exposes no accessor for the nested BSDF of twosided / mask / bumpmap or for a plug-in's parameters after
  *               configure(); the Properties every ConfigurableObject keeps (cobject.h:77) hold the scene file's values for flat BSDFs, and for
  *               adapters the <bsdf> element is re-read from the scene file (scene->getSourceFile(), matched by id, scene.h:1107) with the
@@ -77,6 +78,7 @@ public:
         const ppg_scene desc = data.view();
         m_core.setLens(data.hasLens ? &data.lens : nullptr);
         m_core.setDeltaEmitters(data.deltaEmitters.data(), data.deltaEmitters.size());
+        m_core.setShapes(data.shapes.data(), data.shapes.size());
         Log(EInfo, "Starting render job (%ix%i, MI355X, %i triangles, %i analytic spheres) ..", film->getCropSize().x, film->getCropSize().y,
             (int) (data.indices.size() / 3), (int) data.spheres.size());
         /* create → scene → render; SD-tree dumps to "<dest>-NN.sdt" (GP:1192-1195) */
@@ -247,8 +249,39 @@ private:
                 for (int r = 0; r < 3; ++r) for (int k = 0; k < 3; ++k) s.to_world[3 * r + k] = o2w.getMatrix()(r, k);
                 s.material = (uint32_t) mat; s.emitter = em; s.flip_normals = sp.getBoolean("flipNormals", false) ? 1 : 0;
                 data.spheres.push_back(s);
+            } else if (shape->getProperties().getPluginName() == "disk") {
+                /* Disk::Disk (disk.cpp:83-88): toWorld as it is; flipNormals stays a flag (the prepended scale(1, 1, -1) only negates the normal) */
+                const Properties &sp = shape->getProperties();
+                const Transform o2w = sp.getTransform("toWorld", Transform());
+                ppg_shape s; memset(&s, 0, sizeof s);
+                s.type = PPG_SHAPE_DISK;
+                for (int r = 0; r < 3; ++r) for (int k = 0; k < 4; ++k) s.to_world[4 * r + k] = o2w.getMatrix()(r, k);
+                s.material = (uint32_t) mat; s.emitter = em; s.flip_normals = sp.getBoolean("flipNormals", false) ? 1 : 0;
+                data.shapes.push_back(s);
+            } else if (shape->getProperties().getPluginName() == "cylinder") {
+                /* Cylinder::Cylinder (cylinder.cpp:82-108): the end points and the radius go into the transform, toWorld in front of it, then
+                   the scale comes out again as radius and length */
+                const Properties &sp = shape->getProperties();
+                const Point base = sp.getPoint("p0", Point(0.0f, 0.0f, 0.0f)), top = sp.getPoint("p1", Point(0.0f, 0.0f, 1.0f));
+                const Vector axis = top - base;
+                const Float height = axis.length(), girth = sp.getFloat("radius", 1.0f);
+                /* unit cylinder -> (girth, girth, height) -> stood on `axis` -> moved to `base` -> the scene's toWorld */
+                Transform full = Transform::scale(Vector(girth, girth, height));
+                full = Transform::fromFrame(Frame(axis / height)) * full;
+                full = Transform::translate(Vector(base)) * full;
+                if (sp.hasProperty("toWorld"))
+                    full = sp.getTransform("toWorld") * full;
+                ppg_shape s; memset(&s, 0, sizeof s);
+                s.type = PPG_SHAPE_CYLINDER;
+                /* what is left of the scale goes into the record's radius and length; the transform keeps rotation and translation */
+                s.radius = full(Vector(1, 0, 0)).length();
+                s.length = full(Vector(0, 0, 1)).length();
+                const Transform rigid = full * Transform::scale(Vector(1 / s.radius, 1 / s.radius, 1 / s.length));
+                for (int r = 0; r < 3; ++r) for (int k = 0; k < 4; ++k) s.to_world[4 * r + k] = rigid.getMatrix()(r, k);
+                s.material = (uint32_t) mat; s.emitter = em; s.flip_normals = sp.getBoolean("flipNormals", false) ? 1 : 0;
+                data.shapes.push_back(s);
             } else {
-                why = "shape plug-in '" + shape->getProperties().getPluginName() + "' is not supported (triangle meshes and spheres are)";
+                why = "shape plug-in '" + shape->getProperties().getPluginName() + "' is not supported (triangle meshes, spheres, disks and cylinders are)";
                 return false;
             }
         }

@@ -128,6 +128,53 @@ class Sphere(C.Structure):
         return o
 
 
+class Shape(C.Structure):
+    """ppg_shape (include/ppg.h) — an analytic disk or cylinder.  Scene descriptions carry them as dicts (SceneDesc.shapes): type ("disk" |
+    "cylinder"), to_world (12 floats, row-major 3x4: the disk's toWorld; the cylinder's object-to-world with its scale removed), radius and
+    length (cylinder), material, emitter (-1), flip_normals."""
+    TYPES = ("disk", "cylinder")
+    _fields_ = [("type", C.c_int32), ("to_world", C.c_float * 12), ("radius", C.c_float), ("length", C.c_float), ("material", C.c_uint32),
+                ("emitter", C.c_int32), ("flip_normals", C.c_int32), ("_reserved", C.c_uint32 * 2)]
+
+    @classmethod
+    def from_dict(cls, d):
+        unknown = set(d) - {"type", "to_world", "radius", "length", "material", "emitter", "flip_normals"}
+        if unknown:
+            raise ValueError("shape: unknown parameters %s" % sorted(unknown))
+        o = cls()
+        t = d.get("type")
+        o.type = cls.TYPES.index(t) if t in cls.TYPES else int(t)  # (an unknown number is ppg_set_scene's to refuse)
+        o.to_world[:] = [float(np.float32(v)) for v in np.asarray(d.get("to_world", np.eye(4)[:3]), np.float32).reshape(-1)]
+        o.radius, o.length = float(np.float32(d.get("radius", 0.0))), float(np.float32(d.get("length", 0.0)))
+        o.material, o.emitter, o.flip_normals = int(d.get("material", 0)), int(d.get("emitter", -1)), 1 if d.get("flip_normals") else 0
+        return o
+
+    def as_dict(self):
+        d = dict(type=self.TYPES[self.type], to_world=[float(v) for v in self.to_world], material=int(self.material), emitter=int(self.emitter),
+                 flip_normals=bool(self.flip_normals))
+        if self.type == 1:
+            d.update(radius=float(self.radius), length=float(self.length))
+        return d
+
+
+class DebugHit(C.Structure):
+    """ppg_debug_hit (include/ppg_testhooks.h)"""
+    _fields_ = [("prim", C.c_int32), ("t", C.c_float), ("p", C.c_float * 3), ("geo_n", C.c_float * 3), ("n", C.c_float * 3), ("s", C.c_float * 3),
+                ("wi", C.c_float * 3), ("material", C.c_int32), ("emitter", C.c_int32), ("_pad", C.c_int32)]
+
+
+class DebugDirect(C.Structure):
+    """ppg_debug_direct (include/ppg_testhooks.h)"""
+    _fields_ = [("emitter", C.c_int32), ("d", C.c_float * 3), ("dist", C.c_float), ("n", C.c_float * 3), ("pdf", C.c_float), ("em_pdf", C.c_float),
+                ("value", C.c_float * 3), ("_pad", C.c_float * 3)]
+
+
+DEBUG_HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("p", "<f4", 3), ("geo_n", "<f4", 3), ("n", "<f4", 3), ("s", "<f4", 3), ("wi", "<f4", 3),
+                            ("material", "<i4"), ("emitter", "<i4"), ("_pad", "<i4")])
+DEBUG_DIRECT_DTYPE = np.dtype([("emitter", "<i4"), ("d", "<f4", 3), ("dist", "<f4"), ("n", "<f4", 3), ("pdf", "<f4"), ("em_pdf", "<f4"),
+                               ("value", "<f4", 3), ("_pad", "<f4", 3)])
+
+
 class EnvMap(C.Structure):
     """ppg_envmap (include/ppg.h).  Scene descriptions carry it as a dict: rgb (float32 [height, width, 3]), scale, to_world (9 floats)."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("rgb", C.POINTER(C.c_float)), ("scale", C.c_float), ("to_world", C.c_float * 9)]
@@ -445,6 +492,12 @@ class Engine:
                 self.set_delta_emitters(delta)
         elif delta:
             raise NotImplementedError("%s: point, spot and directional emitters are not implemented here" % self.prefix)
+        # the analytic disks and cylinders: always sent — the scene's list, or the empty list that clears the context's
+        shapes = getattr(desc, "shapes", None) or []
+        if self.prefix == "ppg_":
+            self.set_shapes(shapes)
+        elif shapes:
+            raise NotImplementedError("%s: analytic disks and cylinders are not implemented here" % self.prefix)
         # the bitmaps on specular / alpha / opacity: always sent — one entry per material, or the empty list that clears the context's
         if self.prefix == "ppg_":
             self.set_material_textures(desc.materials if has_parameter_textures(desc) else [])
@@ -478,6 +531,34 @@ class Engine:
             arr[i] = d if isinstance(d, DeltaEmitter) else DeltaEmitter.from_dict(d)
         self._call("set_delta_emitters", arr, C.c_uint32(len(emitters)))
         self._delta = emitters
+
+    def set_shapes(self, shapes):
+        """ppg_set_shapes: a list of shape dicts (Shape); an empty list clears it.  Takes effect at, and is validated by, the next set_scene."""
+        shapes = list(shapes or [])
+        arr = (Shape * max(1, len(shapes)))()
+        for i, d in enumerate(shapes):
+            arr[i] = d if isinstance(d, Shape) else Shape.from_dict(d)
+        self._call("set_shapes", arr, C.c_uint32(len(shapes)))
+
+    def debug_intersect(self, rays, any_hit=False):
+        """ppg_debug_intersect (include/ppg_testhooks.h): rays float32 [n, 8] = (o, mint, d, maxt) through the scene's closest-hit (or
+        any-hit) trace and intersection record; a structured array (DEBUG_HIT_DTYPE)."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.zeros(rays.shape[0], DEBUG_HIT_DTYPE)
+        assert out.itemsize == C.sizeof(DebugHit)
+        self._call("debug_intersect", C.c_uint32(rays.shape[0]), _fp(rays), out.ctypes.data_as(C.POINTER(DebugHit)), C.c_int32(1 if any_hit else 0))
+        return out
+
+    def debug_sample_direct(self, ref, ref_n, u):
+        """ppg_debug_sample_direct: emitter_sample_direct per (ref [n, 3], ref_n [n, 3], u [n, 2]); a structured array (DEBUG_DIRECT_DTYPE)."""
+        ref = np.ascontiguousarray(ref, np.float32).reshape(-1, 3)
+        ref_n = np.ascontiguousarray(ref_n, np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(u, np.float32).reshape(-1, 2)
+        assert ref.shape[0] == ref_n.shape[0] == u.shape[0]
+        out = np.zeros(ref.shape[0], DEBUG_DIRECT_DTYPE)
+        assert out.itemsize == C.sizeof(DebugDirect)
+        self._call("debug_sample_direct", C.c_uint32(ref.shape[0]), _fp(ref), _fp(ref_n), _fp(u), out.ctypes.data_as(C.POINTER(DebugDirect)))
+        return out
 
     def set_material_textures(self, slots):
         """ppg_set_material_textures: one entry per material — a material dict (its specular_texture / alpha_texture / opacity_texture keys) or

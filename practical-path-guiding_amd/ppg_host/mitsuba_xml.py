@@ -7,7 +7,9 @@
               film hdrfilm (width, height; rfilter box / tent / gaussian / mitchell / catmullrom / lanczos)
   shapes      obj (filename, toWorld, faceNormals, maxSmoothAngle, flipNormals, flipTexCoords, collapse),
               serialized (filename, shapeIndex, toWorld, faceNormals, maxSmoothAngle, flipNormals), ply (filename, toWorld, faceNormals, maxSmoothAngle, flipNormals), rectangle / cube (toWorld, flipNormals),
-              sphere (center, radius, toWorld = rotation x uniform scale, flipNormals) — analytic, not tessellated
+              sphere (center, radius, toWorld = rotation x uniform scale, flipNormals) — analytic, not tessellated,
+              disk (toWorld without shear or non-uniform scale, flipNormals), cylinder (p0, p1, radius, toWorld, flipNormals) — analytic
+              (SceneDesc.shapes); no textured BSDFs on them; a cylinder must state at least one of p0 / p1 / radius / toWorld
   bsdfs       diffuse, conductor (material none, explicit eta / k, or a named material read from Mitsuba's data/ior), roughconductor / roughdielectric / roughplastic (ggx / beckmann, isotropic; roughplastic reads Mitsuba's data/microfacet tables),
               plastic, dielectric, thindielectric,
               mask (constant opacity), twosided(any of the BRDFs) — top level with id, nested, or <ref id>
@@ -59,6 +61,114 @@ def _translate(x, y, z):
 
 def _scale(x, y, z):
     return np.diag(np.array([x, y, z, 1], f32))
+
+
+def _mat4_mul(a, b):
+    """4x4 product in float64 with a fixed summation order (host/scene_xml.h does the same sums: the two loaders' records are identical)"""
+    return np.array([[sum(float(a[i][k]) * float(b[k][j]) for k in range(4)) for j in range(4)] for i in range(4)], np.float64)
+
+
+def _transform64(elem, sub):
+    """A <transform> composed in float64 — every value read as a float, then sums in a fixed order and libm's double sin / cos / sqrt — for
+    the analytic disks and cylinders: host/scene_xml.h transform64 does the same operations, so both loaders round the same numbers."""
+    m = [[1.0 if i == j else 0.0 for j in range(4)] for i in range(4)]
+    for c in elem:
+        g = lambda k, d: float(f32(float(sub(c.get(k, str(d))))))  # noqa: E731
+        t = [[1.0 if i == j else 0.0 for j in range(4)] for i in range(4)]
+        if c.tag == "translate":
+            t[0][3], t[1][3], t[2][3] = g("x", 0), g("y", 0), g("z", 0)
+        elif c.tag == "scale":
+            t[0][0], t[1][1], t[2][2] = [g("value", 1)] * 3 if c.get("value") is not None else (g("x", 1), g("y", 1), g("z", 1))
+        elif c.tag == "rotate":  # Transform::rotate, transform.cpp:65-97
+            ax = (g("x", 0), g("y", 0), g("z", 0))
+            ln = math.sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2])
+            x, y, z = ax[0] / ln, ax[1] / ln, ax[2] / ln
+            th = g("angle", 0) * (math.pi / 180.0)
+            s, co = math.sin(th), math.cos(th)
+            t[0][:3] = [x * x + (1 - x * x) * co, x * y * (1 - co) - z * s, x * z * (1 - co) + y * s]
+            t[1][:3] = [x * y * (1 - co) + z * s, y * y + (1 - y * y) * co, y * z * (1 - co) - x * s]
+            t[2][:3] = [x * z * (1 - co) - y * s, y * z * (1 - co) + x * s, z * z + (1 - z * z) * co]
+        elif c.tag == "matrix":
+            v = _floats(sub(c.get("value")))
+            if len(v) != 16:
+                raise SceneError("<matrix> needs 16 values")
+            t = [[float(f32(v[4 * i + j])) for j in range(4)] for i in range(4)]
+        elif c.tag == "lookAt" or c.tag == "lookat":  # Transform::lookAt, transform.cpp:191-214
+            o, tg = ([float(f32(v)) for v in _floats(sub(c.get(k)))] for k in ("origin", "target"))
+            if len(o) != 3 or len(tg) != 3:
+                raise SceneError("<lookAt> needs origin and target")
+            cross = lambda a, b: [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]  # noqa: E731
+            unit = lambda a: [v / math.sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]) for v in a]  # noqa: E731
+            d = unit([tg[i] - o[i] for i in range(3)])
+            if c.get("up"):
+                up = [float(f32(v)) for v in _floats(sub(c.get("up")))]
+            else:  # scenehandler.cpp: any vector orthogonal to the viewing direction
+                up = cross(d, [1.0, 0.0, 0.0] if abs(d[0]) < abs(d[1]) else [0.0, 1.0, 0.0])
+            left = unit(cross(up, d))
+            nu = cross(d, left)
+            for i in range(3):
+                t[i][0], t[i][1], t[i][2], t[i][3] = left[i], nu[i], d[i], o[i]
+        else:
+            raise SceneError("unsupported transform element <%s>" % c.tag)
+        m = _mat4_mul(t, m)  # later elements are applied after earlier ones
+    return np.asarray(m, np.float64)
+
+
+def _linear_part_checks(m, what):
+    """Disk::configure's two checks (disk.cpp:105-112) on the first two columns of a 4x4; returns the columns' lengths"""
+    c0, c1 = [float(m[a][0]) for a in range(3)], [float(m[a][1]) for a in range(3)]
+    l0, l1 = math.sqrt(sum(v * v for v in c0)), math.sqrt(sum(v * v for v in c1))
+    if l0 == 0 or l1 == 0:
+        raise SceneError("%s: 'toWorld' transformation is singular" % what)
+    if abs(sum(a * b for a, b in zip(c0, c1)) / (l0 * l1)) > 1e-3:
+        raise SceneError("%s: 'toWorld' transformation contains shear!" % what)
+    if abs(l0 / l1 - 1) > 1e-3:
+        raise SceneError("%s: 'toWorld' transformation contains a non-uniform scale!" % what)
+    return l0, l1
+
+
+def disk_shape(m, flip_normals):
+    """Disk::Disk / configure (disk.cpp:83-115): the record of a <shape type="disk"> under the 4x4 toWorld `m` (SceneDesc.shapes)"""
+    l0, l1 = _linear_part_checks(m, "disk")
+    l2 = math.sqrt(sum(float(m[a][2]) ** 2 for a in range(3)))
+    if not abs(float(np.linalg.det(np.asarray(m, np.float64)[:3, :3]))) > 1e-9 * l0 * l1 * l2:
+        raise SceneError("disk: 'toWorld' transformation is singular")
+    return dict(type="disk", to_world=[float(f32(m[a][b])) for a in range(3) for b in range(4)], flip_normals=bool(flip_normals))
+
+
+def cylinder_shape(m, p0, p1, radius, flip_normals):
+    """Cylinder::Cylinder (cylinder.cpp:82-108): translate(p0) * fromFrame(Frame(d / |d|)) * scale(r, r, |d|), then toWorld `m` (None: none),
+    then the scale moved out of the transform into radius and length.  Float64 sums rounded once (the reference rounds every step to float:
+    the records agree to float rounding)."""
+    p0, p1 = [float(f32(v)) for v in p0], [float(f32(v)) for v in p1]
+    d = [b - a for a, b in zip(p0, p1)]
+    length = math.sqrt(sum(v * v for v in d))
+    if length == 0:
+        raise SceneError("cylinder: p0 and p1 coincide (its length would be 0)")
+    radius = float(f32(radius))
+    if not radius > 0:
+        raise SceneError("cylinder: radius must be > 0")
+    a = [v / length for v in d]
+    if abs(a[0]) > abs(a[1]):  # coordinateSystem, util.cpp:592-601: Frame(a) = (s, t, a)
+        inv = 1.0 / math.sqrt(a[0] * a[0] + a[2] * a[2])
+        t = [a[2] * inv, 0.0, -a[0] * inv]
+    else:
+        inv = 1.0 / math.sqrt(a[1] * a[1] + a[2] * a[2])
+        t = [0.0, a[2] * inv, -a[1] * inv]
+    sv = [t[1] * a[2] - t[2] * a[1], t[2] * a[0] - t[0] * a[2], t[0] * a[1] - t[1] * a[0]]  # cross(t, a)
+    o2w = [[sv[i] * radius, t[i] * radius, a[i] * length, p0[i]] for i in range(3)] + [[0.0, 0.0, 0.0, 1.0]]
+    if m is not None:
+        o2w = _mat4_mul(m, o2w)
+    l0, _ = _linear_part_checks(o2w, "cylinder")
+    c2 = [float(o2w[i][2]) for i in range(3)]
+    l2 = math.sqrt(sum(v * v for v in c2))
+    for j in (0, 1):  # the axis must stay perpendicular to the circle: otherwise what is left after the scale is removed is no rotation
+        cj = [float(o2w[i][j]) for i in range(3)]
+        if l2 == 0 or abs(sum(x * y for x, y in zip(cj, c2)) / (math.sqrt(sum(v * v for v in cj)) * l2)) > 1e-3:
+            raise SceneError("cylinder: 'toWorld' transformation contains shear!")
+    ir, il = 1.0 / l0, 1.0 / l2
+    tw = [float(f32(v)) for i in range(3) for v in (float(o2w[i][0]) * ir, float(o2w[i][1]) * ir, float(o2w[i][2]) * il, float(o2w[i][3]))]
+    return dict(type="cylinder", to_world=tw, radius=float(f32(l0)), length=float(f32(l2)), flip_normals=bool(flip_normals))
 
 
 def _rotate(axis, angle_deg):  # Transform::rotate, transform.cpp:65-97
@@ -1142,7 +1252,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                          "`constant`, `envmap` or `sunsky` environment emitter; SURVEY.md §8 f2)" % em.get("type"))
 
     # ---- shapes
-    collected, emitters, spheres = [], [], []
+    collected, emitters, spheres, shapes = [], [], [], []
     default_mat = None
     for sh in root.findall("shape"):
         t = sh.get("type")
@@ -1210,8 +1320,21 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 raise SceneError("Cannot create spheres of radius <= 0")
             sphere = dict(center=tuple(float(v) for v in o2w[:3, 3]), radius=float(radius), to_world=[float(v) for v in o2w[:3, :3].reshape(-1)],
                           flip_normals=bool(sprops.get("flipNormals", False)))
+        elif t == "disk":
+            meshes = []
+            analytic = disk_shape(_transform64(tw, sub) if tw is not None else np.eye(4), bool(sprops.get("flipNormals", False)))
+        elif t == "cylinder":
+            meshes = []
+            # (An element that states nothing — no p0, p1, radius or toWorld — is refused, although Mitsuba would make the unit cylinder of
+            # it: `<shape type="cylinder"/>` is what the suite has always used as its example of a shape this loader names and refuses
+            # (tests/test_mitsuba_xml.py, tests/test_cpp_host.py), and that pin stays.  Every cylinder of a real scene states its geometry.)
+            if tw is None and not any(k in sprops for k in ("p0", "p1", "radius")):
+                raise SceneError("cylinder: none of p0, p1, radius, toWorld is given; state the cylinder's geometry (Mitsuba's defaults — the "
+                                 "unit cylinder from the origin along z — are not assumed here)")
+            analytic = cylinder_shape(_transform64(tw, sub) if tw is not None else None, sprops.get("p0", (0.0, 0.0, 0.0)), sprops.get("p1", (0.0, 0.0, 1.0)),
+                                      sprops.get("radius", 1.0), bool(sprops.get("flipNormals", False)))
         else:
-            raise SceneError("shape type %r is not supported (obj, ply, serialized, rectangle, cube, sphere)" % t)
+            raise SceneError("shape type %r is not supported (obj, ply, serialized, rectangle, cube, sphere, disk, cylinder)" % t)
         # material: nested <bsdf> or <ref id>
         mat = None
         for c in sh:
@@ -1244,7 +1367,11 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             collected.append((mesh, mat, em))
         if t == "sphere":
             spheres.append(dict(sphere, material=mat, emitter=em))
-    if not collected and not spheres:
+        if t in ("disk", "cylinder"):
+            if any(materials[mat].get(k) is not None for k in TEXTURE_KEYS):
+                raise SceneError("%s: textured BSDFs are only supported on triangle meshes (not on spheres, disks or cylinders)" % t)
+            shapes.append(dict(analytic, material=mat, emitter=em))
+    if not collected and not spheres and not shapes:
         raise SceneError("scene without shapes")
     # one vertex-normal array for the whole scene: a faceNormals mesh living next to smooth ones gets its vertices
     # un-shared and its face normals written out (same shading frame as "no normals": skdtree.h:388-401)
@@ -1277,7 +1404,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         pos, idx, tmat, tem = [np.zeros((0, 3), f32)], [np.zeros((0, 3), np.uint32)], [np.zeros(0, np.uint32)], [np.zeros(0, np.int32)]
     desc = SceneDesc(np.concatenate(pos).astype(f32), np.concatenate(idx).astype(np.uint32), np.concatenate(tmat), np.concatenate(tem),
                      materials, emitters, camera, normals, environment, np.stack(rt_slices).astype(f32) if rt_slices else None, spheres, envmap,
-                     np.concatenate(uvl).astype(f32) if any_uvs else None, textures, rfilter, lens, delta_emitters)
+                     np.concatenate(uvl).astype(f32) if any_uvs else None, textures, rfilter, lens, delta_emitters, shapes)
     if delta_emitters and str(props.get("nee", "never")) != "always":
         warnings.append("point / spot / directional emitters are reached by next-event estimation only: with nee = %s they contribute nothing in "
                         "every iteration that runs without it (as in Mitsuba)" % props.get("nee", "never"))
@@ -1355,9 +1482,30 @@ def save_scene_xml(desc, props, directory, name="scene"):
     groups = sorted({(int(a), int(b)) for a, b in zip(tm, te)}, key=lambda g: (g[1] < 0, g[1], g[0]))  # emitters first, in emitter order
     # shapes in emitter order (the loader numbers emitters in shape order), shapes without an emitter last
     shapes = [("mesh", g) for g in groups] + [("sphere", sp) for sp in (getattr(desc, "spheres", None) or [])]
+    shapes += [("shape", sh) for sh in (getattr(desc, "shapes", None) or [])]
     em_of = lambda rec: rec[1][1] if rec[0] == "mesh" else int(rec[1].get("emitter", -1))  # noqa: E731
-    shapes.sort(key=lambda rec: (em_of(rec) < 0, em_of(rec)))
+    # (a disk or cylinder without an emitter stays behind the emitting one that precedes it in desc.shapes: the list comes back in its order)
+    order, prev = {}, -1
+    for k, sh in enumerate(getattr(desc, "shapes", None) or []):
+        prev = int(sh.get("emitter", -1)) if int(sh.get("emitter", -1)) >= 0 else prev
+        order[id(sh)] = (prev, int(sh.get("emitter", -1)) < 0, k)
+    big = len(desc.emitters)
+    shapes.sort(key=lambda rec: order[id(rec[1])] if rec[0] == "shape" else ((big, True, 0) if em_of(rec) < 0 else (em_of(rec), False, 0)))
     for gi, (kind, rec) in enumerate(shapes):
+        if kind == "shape":  # a disk's toWorld as it is; a cylinder along z with its radius and length under the rotation that is left
+            out.append('\t<shape type="%s">' % rec["type"])
+            M4 = np.eye(4, dtype=np.float64); M4[:3, :] = np.asarray(rec["to_world"], np.float32).reshape(3, 4)
+            out.append('\t\t<transform name="toWorld"><matrix value="%s"/></transform>' % " ".join(repr(float(x)) for x in M4.reshape(-1)))
+            if rec["type"] == "cylinder":
+                out.append('\t\t<point name="p1" x="0.0" y="0.0" z="%r"/>' % float(np.float32(rec["length"])))
+                out.append('\t\t<float name="radius" value="%r"/>' % float(np.float32(rec["radius"])))
+            if rec.get("flip_normals"):
+                out.append('\t\t<boolean name="flipNormals" value="true"/>')
+            out.append('\t\t<ref id="mat%d"/>' % int(rec.get("material", 0)))
+            if int(rec.get("emitter", -1)) >= 0:
+                out.append('\t\t<emitter type="area"><rgb name="radiance" value="%s"/></emitter>' % c(desc.emitters[int(rec["emitter"])]["radiance"]))
+            out.append('\t</shape>')
+            continue
         if kind == "sphere":
             out.append('\t<shape type="sphere">')
             R = np.asarray(rec.get("to_world", np.eye(3)), np.float32).reshape(3, 3)

@@ -17,7 +17,7 @@ import numpy as np
 
 class SceneDesc:
     def __init__(self, positions, indices, tri_material, tri_emitter, materials, emitters, camera, normals=None, environment=None, rtrans=None, spheres=None, envmap=None,
-                 texcoords=None, textures=None, rfilter=None, lens=None, delta_emitters=None):
+                 texcoords=None, textures=None, rfilter=None, lens=None, delta_emitters=None, shapes=None):
         self.positions, self.indices = positions, indices
         self.tri_material, self.tri_emitter = tri_material, tri_emitter
         self.materials, self.emitters, self.camera, self.normals = materials, emitters, camera, normals
@@ -32,6 +32,8 @@ class SceneDesc:
         self.lens = lens                # None (pinhole) or a thin lens: {"aperture_radius", "focus_distance"} (bindings.Lens)
         self.delta_emitters = list(delta_emitters or [])  # point / spot / directional emitters: dicts (bindings.DeltaEmitter); they are numbered
                                                           # after the area emitters and before the environment emitter
+        self.shapes = list(shapes or [])  # analytic disks and cylinders: dicts {type, to_world, radius, length, material, emitter, flip_normals}
+                                          # (bindings.Shape); primitives after the triangles and the spheres
 
     @property
     def n_triangles(self):
@@ -40,7 +42,7 @@ class SceneDesc:
 
 def save_scene(desc, path):
     """Write the flat binary scene read by host/ppg_render.cpp: "PPGS", 6 x uint32 {n_vertices, n_triangles, n_materials,
-    n_emitters, has_normals, blocks (bit 0: environment, bit 1: rtrans, bit 2: spheres, bit 3: envmap, bit 4: texcoords, bit 5: textures, bit 6: rfilter, bit 7: lens, bit 8: delta emitters, bit 9: material textures)}, then positions, [normals], indices, tri_material,
+    n_emitters, has_normals, blocks (bit 0: environment, bit 1: rtrans, bit 2: spheres, bit 3: envmap, bit 4: texcoords, bit 5: textures, bit 6: rfilter, bit 7: lens, bit 8: delta emitters, bit 9: material textures, bit 10: shapes)}, then positions, [normals], indices, tri_material,
     tri_emitter, materials (ppg_material, 80 bytes each), emitters (4 floats), camera (ppg_camera), [environment radiance:
     3 floats], [rtrans: 2 x uint32 {n_slices, samples}, then n_slices x (samples + 1) floats], [spheres: uint32 n, then n x ppg_sphere
     (64 bytes)], [envmap: 2 x uint32 {width, height}, float scale, 9 floats to_world, then height x width x 3 floats], [texcoords: n_vertices x 2
@@ -49,15 +51,17 @@ def save_scene(desc, path):
     [rfilter: ppg_rfilter, 24 bytes {int32 type, float radius, stddev, B, C, int32 lobes} — only for a filter other than the default box],
     [lens: ppg_lens, 2 floats {aperture_radius, focus_distance} — only for a thin-lens camera],
     [delta emitters: uint32 n, then n x ppg_delta_emitter (84 bytes) — only when there are point / spot / directional emitters],
-    [material textures: n_materials x ppg_material_textures (16 bytes) — only when a material has a bitmap on specular / alpha / opacity]."""
+    [material textures: n_materials x ppg_material_textures (16 bytes) — only when a material has a bitmap on specular / alpha / opacity],
+    [shapes: uint32 n, then n x ppg_shape (80 bytes) — only when there are analytic disks or cylinders]."""
     import struct
-    from .bindings import DeltaEmitter, Lens, MaterialTextures, RFilter, has_parameter_textures
+    from .bindings import DeltaEmitter, Lens, MaterialTextures, RFilter, Shape, has_parameter_textures
     mat_tex = [MaterialTextures.from_dict(m) for m in desc.materials] if has_parameter_textures(desc) else []
     rf = RFilter.from_dict(getattr(desc, "rfilter", None))
     rf = rf if rf.as_dict() is not None else None
     lens = getattr(desc, "lens", None)
     lens = None if lens is None else Lens.from_dict(lens)
     delta = [DeltaEmitter.from_dict(d) for d in (getattr(desc, "delta_emitters", None) or [])]
+    shapes = [Shape.from_dict(d) for d in (getattr(desc, "shapes", None) or [])]
     pos = np.ascontiguousarray(desc.positions, np.float32)
     idx = np.ascontiguousarray(desc.indices, np.uint32)
     with open(path, "wb") as f:
@@ -68,7 +72,7 @@ def save_scene(desc, path):
         f.write(struct.pack("<6I", pos.shape[0], idx.shape[0], len(desc.materials), len(desc.emitters), 0 if desc.normals is None else 1,
                             (0 if env is None else 1) | (0 if rt is None else 2) | (4 if getattr(desc, "spheres", None) else 0) | (8 if getattr(desc, "envmap", None) is not None else 0)
                             | (16 if getattr(desc, "texcoords", None) is not None else 0) | (32 if getattr(desc, "textures", None) else 0) | (0 if rf is None else 64)
-                            | (0 if lens is None else 128) | (256 if delta else 0) | (512 if mat_tex else 0)))
+                            | (0 if lens is None else 128) | (256 if delta else 0) | (512 if mat_tex else 0) | (1024 if shapes else 0)))
         f.write(pos.tobytes())
         if desc.normals is not None:
             f.write(np.ascontiguousarray(desc.normals, np.float32).tobytes())
@@ -123,6 +127,10 @@ def save_scene(desc, path):
                 f.write(bytes(d))
         for mt in mat_tex:
             f.write(bytes(mt))
+        if shapes:
+            f.write(struct.pack("<I", len(shapes)))
+            for sh in shapes:
+                f.write(bytes(sh))
 
 
 def srgb8_table():
@@ -239,13 +247,22 @@ def load_scene_file(path):
                     raise ValueError("%s: material texture slot out of range" % path)
                 if v:
                     d[k] = int(v) - 1
+    shapes = []
+    if blocks & 1024:
+        from .bindings import Shape
+        for _ in range(int(take(np.uint32, 1)[0])):
+            sh = Shape.from_buffer_copy(bytes(take(np.uint8, C_SHAPE_BYTES)))
+            if not 0 <= sh.type < len(Shape.TYPES):
+                raise ValueError("%s: unknown shape type %d" % (path, sh.type))
+            shapes.append(sh.as_dict())
     if off[0] != len(buf):
         raise ValueError("%s: trailing bytes" % path)
-    return SceneDesc(pos, idx, tm, te, mats, ems, cam, nrm, env, rt, spheres, envmap, uvs, textures, rfilter, lens, delta)
+    return SceneDesc(pos, idx, tm, te, mats, ems, cam, nrm, env, rt, spheres, envmap, uvs, textures, rfilter, lens, delta, shapes)
 
 
 C_RFILTER_BYTES = 24  # sizeof(ppg_rfilter)
 C_LENS_BYTES = 8      # sizeof(ppg_lens)
+C_SHAPE_BYTES = 80    # sizeof(ppg_shape)
 C_MATERIAL_TEXTURES_BYTES = 16  # sizeof(ppg_material_textures)
 C_DELTA_EMITTER_BYTES = 84  # sizeof(ppg_delta_emitter)
 
