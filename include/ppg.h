@@ -419,6 +419,36 @@ typedef struct ppg_material_textures {
 int ppg_set_material_textures(ppg_ctx *ctx, const ppg_material_textures *slots, uint32_t n_materials);
 
 /* ------------------------------------------------------------------------------------------------
+ * The rest of Mitsuba's MicrofacetDistribution (microfacet.h) for roughconductor / roughdielectric / roughplastic: alphaU / alphaV,
+ * distribution = phong (Phong, anisotropic: Ashikhmin-Shirley) and sampleVisible = false.  Another side list, one entry per material in
+ * ppg_scene.materials' order, with the ordering rules of ppg_set_material_textures: call before ppg_set_scene, which validates and
+ * consumes it; the context keeps it until it is replaced (NULL or n_materials = 0 clears it, and a cleared list renders exactly as a fresh
+ * context does); PPG_ERR_STATE between ppg_begin_render and ppg_end_render.
+ * An entry with general = 0 leaves the material on the isotropic path of ppg_material (its other fields are ignored).  With general != 0
+ *   alphaU        is ppg_material.alpha (and the alpha slot of ppg_material_textures), alphaV is alpha_v (alpha_v_texture: 1 + index into
+ *                 ppg_scene.textures, 0 = none; eval(its).average(), as alpha); both clamped to >= 1e-4 (microfacet.h:135-136)
+ *   distribution  0: ggx, or beckmann with PPG_MAT_BECKMANN; 1: phong, which implies sample_all (microfacet.h:141-142)
+ *   sample_all    sampleVisible = false: sampleAll / pdfAll instead of the visible normals, with the plug-ins' other weights
+ *                 (roughconductor.cpp:316-320, 403-409) and roughdielectric's scaled sampling roughness (roughdielectric.cpp:406-411)
+ * An anisotropic material (alpha_v != alpha, or either from a bitmap) has the shading frame of a textured one, the UV tangents
+ * (trimesh.cpp:380); analytic spheres, disks and cylinders span theirs from their own dpdu.
+ * ppg_set_scene returns PPG_ERR_INVALID for: a list whose length is neither 0 nor n_materials; general on another BSDF type; roughplastic
+ * with alpha_v != alpha (roughplastic.cpp:221) or with an alpha_v_texture; a distribution other than 0 / 1; a non-zero reserved word; a
+ * texture index out of range; a triangle with an anisotropic material on a mesh without texture coordinates (trimesh.cpp:686-691).
+ * A scene with a general entry runs the "extended" kernels (csrc: PPG_MFD), whatever else it holds; the CPU oracle does not know these
+ * entries (they are pinned by reduction to the isotropic path and against a float64 restatement).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ppg_microfacet {
+    float alpha_v;            /* alphaV; alphaU stays ppg_material.alpha (and its alpha bitmap slot) */
+    int32_t distribution;     /* 0 = as ppg_material.flags says (ggx / PPG_MAT_BECKMANN), 1 = phong */
+    int32_t sample_all;       /* sampleVisible = false */
+    uint32_t alpha_v_texture; /* 1 + index into ppg_scene.textures, 0 = none */
+    uint32_t general;         /* 0 = this material keeps the isotropic path and the other fields are ignored */
+    uint32_t _reserved[3];    /* must be 0 */
+} ppg_microfacet;             /* 32 bytes */
+int ppg_set_microfacet(ppg_ctx *ctx, const ppg_microfacet *m, uint32_t n_materials);
+
+/* ------------------------------------------------------------------------------------------------
  * Rendering.  ppg_render() is GuidedPathTracer::render() (GP:1516-1585, IH:74-75) in one call.
  * The stepwise calls expose its phases so a multi-GPU driver can all-reduce the SD-tree statistics
  * between ppg_render_passes() and ppg_build_sdtree(); ppg_render() is exactly their composition

@@ -86,6 +86,34 @@ struct ppg_debug_direct {
 };  /* 64 bytes */
 int ppg_debug_sample_direct(struct ppg_ctx *ctx, uint32_t n, const float *ref, const float *ref_n, const float *u, struct ppg_debug_direct *out);
 
+/* The BSDF layer of the context's materials (after ppg_set_scene, outside a render), item by item: one small kernel of the extended
+   units (csrc: PPG_MFD) whose lanes prepare the material as the render does at a hit with texture coordinates uv — the record, the bitmaps
+   of ppg_material.texture / ppg_set_material_textures, the entry of ppg_set_microfacet — and call the render's own mat_eval / mat_pdf /
+   mat_sample on it.  A material without a general entry runs through the same functions with alphaV = alphaU, its own ggx / beckmann and
+   visible sampling: the float operations of the isotropic path, which the tests hold to the oracle bit for bit.
+   Per item: the material, local wi, local wo (eval / pdf), the 2-D sample, and the extra number roughdielectric::sample draws from the
+   path's sampler (roughdielectric.cpp:553), named as the render names it: it is ppg_rand(key, 0) (include/ppg_rng.h).
+   Out: eval = f * |cos theta_o| as the render uses it, pdf, then of mat_sample the direction, its pdf, the weight, eta and the delta /
+   null flags. */
+struct ppg_debug_bsdf_item {
+    int32_t material;
+    float wi[3], wo[3];
+    float sample[2];
+    uint32_t key;
+    float uv[2];
+};  /* 48 bytes */
+struct ppg_debug_bsdf_out {
+    float eval[3];
+    float pdf;
+    float wo[3];
+    float sampled_pdf;
+    float weight[3];
+    float eta;
+    int32_t delta, is_null;
+    int32_t _pad[2];
+};  /* 64 bytes */
+int ppg_debug_bsdf(struct ppg_ctx *ctx, uint32_t n, const struct ppg_debug_bsdf_item *items, struct ppg_debug_bsdf_out *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,7 +31,20 @@
 #ifndef PPG_SHAPES
 #define PPG_SHAPES 0
 #endif
-#if PPG_SHAPES
+// The general MicrofacetDistribution (ppg_set_microfacet: alphaU / alphaV, Phong / Ashikhmin-Shirley, sampleVisible = false) is compiled
+// into a third, "extended" family — k_trace_ext, k_shade_ext, k_tail_ext: translation units built with -DPPG_SHAPES=1 -DPPG_MFD=1 —, launched
+// for a scene whose microfacet list has a general entry, with or without analytic shapes.  Everything it adds sits under PPG_MFD.
+#ifndef PPG_MFD
+#define PPG_MFD 0
+#endif
+#if PPG_MFD && !PPG_SHAPES
+#error "the extended units are built with -DPPG_SHAPES=1 -DPPG_MFD=1"
+#endif
+#if PPG_MFD
+#define k_trace k_trace_ext
+#define k_shade k_shade_ext
+#define k_tail k_tail_ext
+#elif PPG_SHAPES
 #define k_trace k_trace_shapes
 #define k_shade k_shade_shapes
 #define k_tail k_tail_shapes
@@ -195,7 +208,14 @@ struct DevScene {
     // numbers n_tris + n_spheres, ..
     const float4 *shapes;
     int n_shapes;
+    // ppg_set_microfacet with a general entry (extended kernels only, PPG_MFD): one float4 per material = (alphaV, PPG_MFDF_* bits,
+    // alphaV texture: 1 + index as bits, -); nullptr otherwise
+    const float4 *mfd;
 };
+#define PPG_MFDF_GENERAL 1u     // the entry is live
+#define PPG_MFDF_PHONG 2u       // distribution = phong / as
+#define PPG_MFDF_SAMPLE_ALL 4u  // sampleVisible = false (always with PHONG)
+#define PPG_MFDF_ANISO 8u       // alphaU != alphaV or either comes from a bitmap: the shading frame follows the UV tangents (trimesh.cpp:380)
 #define PPG_DELTA_STRIDE 4
 #define PPG_SHAPE_STRIDE 8
 
@@ -879,6 +899,9 @@ D void fill_isect_tex(const DevScene &S, const Hit &h, F3 d, Isect &I, TexInfo &
         X.tex = __float_as_uint(S.materials[PPG_MAT_STRIDE * (size_t)I.material + 5].x);
         textured = X.tex != 0u;
     }
+#if PPG_MFD
+    if (SLOTS && S.mfd) textured = textured || (__float_as_uint(S.mfd[I.material].y) & PPG_MFDF_ANISO) != 0u;
+#endif
     F3 dpdu = side1;
     if (textured) {
         X.u = b.y; X.v = b.z;
@@ -1507,6 +1530,10 @@ struct Mat {
 #endif
     float refl_lum;           // luminance of the material record's reflectance = of the texture's average when `refl` was read from a bitmap:
                               // what the plug-ins' configure() derives the component sampling weights from (plastic.cpp:191-204)
+#if PPG_MFD
+    float alpha_v;            // alphaV (alpha is alphaU); = alpha without a general entry
+    unsigned int mfd;         // the entry's PPG_MFDF_* bits, 0 without one
+#endif
 };
 D Mat load_material(const DevScene &S, int id) {
     const float4 *m = S.materials + PPG_MAT_STRIDE * (size_t)id;
@@ -1523,6 +1550,13 @@ D Mat load_material(const DevScene &S, int id) {
     M.refl_lum = a.x * 0.212671f + a.y * 0.715160f + a.z * 0.072169f;
 #if PPG_PARAM_TEXTURES
     M.spec_lum = b.x * 0.212671f + b.y * 0.715160f + b.z * 0.072169f;
+#endif
+#if PPG_MFD
+    M.alpha_v = M.alpha; M.mfd = 0u;
+    if (S.mfd) {
+        const float4 g = S.mfd[id];
+        if (__float_as_uint(g.y) & PPG_MFDF_GENERAL) { M.alpha_v = g.x; M.mfd = __float_as_uint(g.y); }
+    }
 #endif
     return M;
 }
@@ -1554,6 +1588,14 @@ D void mat_apply_textures(const DevScene &S, int id, float u, float v, Mat &M) {
     if (ta) { const float4 t = tex_eval_slot(S.textures, ta, u, v); M.alpha = ppg_max((t.x + t.y + t.z) / 3.0f, 1e-4f); }
     if (to) { const float4 t = tex_eval_slot(S.textures, to, u, v); M.opacity = f3(t.x, t.y, t.z); }
 }
+#if PPG_MFD
+// ... and m_alphaV->eval(its).average() of a general entry (ppg_microfacet.alpha_v_texture).  Without an entry alphaV follows alphaU.
+D void mat_apply_mfd_textures(const DevScene &S, int id, float u, float v, Mat &M) {
+    if (!M.mfd) { M.alpha_v = M.alpha; return; }
+    const unsigned int tv = __float_as_uint(S.mfd[id].z);
+    if (tv) { const float4 t = tex_eval_slot(S.textures, tv, u, v); M.alpha_v = ppg_max((t.x + t.y + t.z) / 3.0f, 1e-4f); }
+}
+#endif
 // What mat_eval_null reads of a surface passed through: a mask's opacity, a thin dielectric's specularTransmittance.  (Materials of
 // analytic spheres carry no slot: h is a triangle wherever one is set.)
 D void mat_apply_null_textures(const DevScene &S, const Hit &h, int id, Mat &M) {
@@ -1657,6 +1699,7 @@ D float mts_erf(float x) {
     return sign * y;
 }
 
+#if !PPG_MFD
 // MicrofacetDistribution, isotropic GGX or Beckmann, visible-normal sampling (microfacet.h:191-237, 425-540, 565-690)
 struct Mfd { float alpha; bool beckmann; };
 D float ggx_eval(Mfd d, F3 m) {
@@ -1674,6 +1717,68 @@ D float ggx_eval(Mfd d, F3 m) {
     if (result * m.z < 1e-20f) result = 0;
     return result;
 }
+#define PPG_MAT_MFD(M) Mfd{(M).alpha, ((M).flags & PPG_MAT_BECKMANN) != 0}
+#else
+// The extended kernels (PPG_MFD): the whole of MicrofacetDistribution (microfacet.h:67-93, 178-565, 700-715) — alphaU / alphaV, the Phong /
+// Ashikhmin-Shirley type, sampling of all normals.  Every rough material of such a kernel goes through these functions, also one without
+// a general entry: with alphaU == alphaV, ggx or beckmann and visible sampling they perform the float operations of the isotropic
+// functions above, as the reference's own isotropic branches do (tests/test_microfacet_general_gpu.py holds them to the oracle bit for bit).
+// Out of line (MFD_CALL) where a plug-in calls them from several places: the FULL kernels have no registers or cache left for copies.
+#define MFD_CALL static __device__ __attribute__((noinline))
+enum { MFD_BECKMANN = 0, MFD_GGX = 1, MFD_PHONG = 2 };
+struct Mfd { float alphaU, alphaV, exponentU, exponentV; int type; bool sampleAll; };
+D void mfd_phong_exponent(Mfd &d) {  // computePhongExponent, microfacet.h:701-704
+    d.exponentU = ppg_max(2.0f / (d.alphaU * d.alphaU) - 2.0f, 0.0f);
+    d.exponentV = ppg_max(2.0f / (d.alphaV * d.alphaV) - 2.0f, 0.0f);
+}
+D Mfd mat_mfd(const Mat &M) {  // MicrofacetDistribution(type, alphaU, alphaV, sampleVisible), microfacet.h:86-93
+    Mfd d;
+    d.type = (M.mfd & PPG_MFDF_PHONG) ? MFD_PHONG : ((M.flags & PPG_MAT_BECKMANN) ? MFD_BECKMANN : MFD_GGX);
+    d.alphaU = ppg_max(M.alpha, 1e-4f); d.alphaV = ppg_max(M.alpha_v, 1e-4f);
+    d.sampleAll = (M.mfd & PPG_MFDF_SAMPLE_ALL) != 0u;
+    d.exponentU = 0.0f; d.exponentV = 0.0f;
+    if (d.type == MFD_PHONG) mfd_phong_exponent(d);
+    return d;
+}
+D Mfd mfd_scale_alpha(Mfd d, float value) {  // scaleAlpha, microfacet.h:178-183
+    d.alphaU *= value; d.alphaV *= value;
+    if (d.type == MFD_PHONG) mfd_phong_exponent(d);
+    return d;
+}
+#define PPG_MAT_MFD(M) mat_mfd(M)
+D float mfd_interpolate_phong_exponent(const Mfd &d, F3 v) {  // microfacet.h:554-565
+    const float sinTheta2 = 1.0f - v.z * v.z;
+    if (d.alphaU == d.alphaV || sinTheta2 <= 2.93873587705571876e-39f) return d.exponentU;
+    float invSinTheta2 = 1 / sinTheta2;
+    float cosPhi2 = v.x * v.x * invSinTheta2;
+    float sinPhi2 = v.y * v.y * invSinTheta2;
+    return d.exponentU * cosPhi2 + d.exponentV * sinPhi2;
+}
+MFD_CALL float ggx_eval(Mfd d, F3 m) {  // eval, microfacet.h:191-234
+    if (m.z <= 0) return 0.0f;
+    float cosTheta2 = m.z * m.z;
+    float beckmannExponent = ((m.x * m.x) / (d.alphaU * d.alphaU) + (m.y * m.y) / (d.alphaV * d.alphaV)) / cosTheta2;
+    float result;
+    if (d.type == MFD_BECKMANN) {
+        result = dm_exp(-beckmannExponent) / (PPG_PI_F * d.alphaU * d.alphaV * cosTheta2 * cosTheta2);
+    } else if (d.type == MFD_GGX) {
+        float root = (1.0f + beckmannExponent) * cosTheta2;
+        result = 1.0f / (PPG_PI_F * d.alphaU * d.alphaV * root * root);
+    } else {
+        float exponent = mfd_interpolate_phong_exponent(d, m);
+        result = __builtin_sqrtf((d.exponentU + 2) * (d.exponentV + 2)) * 0.15915494309189533577f * dm_pow(m.z, exponent);
+    }
+    if (result * m.z < 1e-20f) result = 0;
+    return result;
+}
+D float mfd_project_roughness(const Mfd &d, F3 v) {  // microfacet.h:541-551
+    float invSinTheta2 = 1 / (1.0f - v.z * v.z);
+    if (d.alphaU == d.alphaV || invSinTheta2 <= 0) return d.alphaU;
+    float cosPhi2 = v.x * v.x * invSinTheta2;
+    float sinPhi2 = v.y * v.y * invSinTheta2;
+    return __builtin_sqrtf(cosPhi2 * d.alphaU * d.alphaU + sinPhi2 * d.alphaV * d.alphaV);
+}
+#endif
 D float hypot2f(float a, float b) {  // math.cpp:74-86
     float r;
     if (ppg_abs(a) > ppg_abs(b)) { r = b / a; r = ppg_abs(a) * __builtin_sqrtf(1.0f + r * r); }
@@ -1681,6 +1786,7 @@ D float hypot2f(float a, float b) {  // math.cpp:74-86
     else r = 0.0f;
     return r;
 }
+#if !PPG_MFD
 D float ggx_smith_g1(Mfd d, F3 v, F3 m) {
     if (dot3(v, m) * v.z <= 0) return 0.0f;
     float temp = 1 - v.z * v.z;
@@ -1695,6 +1801,23 @@ D float ggx_smith_g1(Mfd d, F3 v, F3 m) {
     float root = d.alpha * tanTheta;
     return 2.0f / (1.0f + hypot2f(1.0f, root));
 }
+#else
+MFD_CALL float ggx_smith_g1(Mfd d, F3 v, F3 m) {  // smithG1, microfacet.h:477-514
+    if (dot3(v, m) * v.z <= 0) return 0.0f;
+    float temp = 1 - v.z * v.z;
+    float tanTheta = temp <= 0.0f ? 0.0f : ppg_abs(__builtin_sqrtf(temp) / v.z);
+    if (tanTheta == 0.0f) return 1.0f;
+    float alpha = mfd_project_roughness(d, v);
+    if (d.type != MFD_GGX) {  // EPhong, EBeckmann
+        float a = 1.0f / (alpha * tanTheta);
+        if (a >= 1.6f) return 1.0f;
+        float aSqr = a * a;
+        return (3.535f * a + 2.181f * aSqr) / (1.0f + 2.276f * a + 2.577f * aSqr);
+    }
+    float root = alpha * tanTheta;
+    return 2.0f / (1.0f + hypot2f(1.0f, root));
+}
+#endif
 D float ggx_pdf_visible(Mfd d, F3 wi, F3 m) {
     if (wi.z == 0) return 0.0f;
     return ggx_smith_g1(d, wi, m) * ppg_abs(dot3(wi, m)) * ggx_eval(d, m) / ppg_abs(wi.z);
@@ -1755,6 +1878,7 @@ D void ggx_sample_visible11(float thetaI, float u, float v, float &sx, float &sy
               (v * (v * (v * (v * 0.169507819808272f - 0.397203533833404f) - 0.232500544458471f) + 1.0f) - 0.539825872510702f);
     sy = S * z * __builtin_sqrtf(1.0f + sx * sx);
 }
+#if !PPG_MFD
 D F3 ggx_sample_visible(Mfd d, F3 _wi, float u, float v) {
     const float alpha = d.alpha;
     F3 wi = norm3(f3(alpha * _wi.x, alpha * _wi.y, _wi.z));
@@ -1773,6 +1897,95 @@ D F3 ggx_sample_visible(Mfd d, F3 _wi, float u, float v) {
     float normalization = 1.0f / __builtin_sqrtf(rx * rx + ry * ry + 1.0f);
     return f3(-rx * normalization, -ry * normalization, normalization);
 }
+#else
+D F3 ggx_sample_visible(Mfd d, F3 _wi, float u, float v) {
+    const float alphaU = d.alphaU, alphaV = d.alphaV;  // sampleVisible, microfacet.h:421-459: the two stretches
+    F3 wi = norm3(f3(alphaU * _wi.x, alphaV * _wi.y, _wi.z));
+    float theta = 0, phi = 0;
+    if (wi.z < 0.99999f) {
+        theta = dm_acos(wi.z);
+        phi = dm_atan2(wi.y, wi.x);
+    }
+    float sinPhi, cosPhi;
+    dm_sincos(phi, &sinPhi, &cosPhi);
+    float sx, sy;
+    if (d.type == MFD_BECKMANN) beckmann_sample_visible11(theta, u, v, sx, sy);
+    else ggx_sample_visible11(theta, u, v, sx, sy);
+    float rx = cosPhi * sx - sinPhi * sy, ry = sinPhi * sx + cosPhi * sy;
+    rx *= alphaU; ry *= alphaV;
+    float normalization = 1.0f / __builtin_sqrtf(rx * rx + ry * ry + 1.0f);
+    return f3(-rx * normalization, -ry * normalization, normalization);
+}
+D void mfd_sample_first_quadrant(const Mfd &d, float u1, float &phi, float &exponent) {  // microfacet.h:707-715
+    float cosPhi, sinPhi;
+    phi = dm_atan2(__builtin_sqrtf((d.exponentU + 2.0f) / (d.exponentV + 2.0f)) * dm_tan(PPG_PI_F * u1 * 0.5f), 1.0f);  // atan(x) = atan2(x, 1)
+    dm_sincos(phi, &sinPhi, &cosPhi);
+    exponent = d.exponentU * cosPhi * cosPhi + d.exponentV * sinPhi * sinPhi;
+}
+// sampleAll, microfacet.h:287-395
+D F3 mfd_sample_all(const Mfd &d, float sx, float sy, float &pdf) {
+    float cosThetaM = 0.0f;
+    float sinPhiM, cosPhiM;
+    float alphaSqr;
+    if (d.type != MFD_PHONG) {
+        if (d.alphaU == d.alphaV) {
+            dm_sincos((2.0f * PPG_PI_F) * sy, &sinPhiM, &cosPhiM);
+            alphaSqr = d.alphaU * d.alphaU;
+        } else {
+            float phiM = dm_atan2(d.alphaV / d.alphaU * dm_tan(PPG_PI_F + 2 * PPG_PI_F * sy), 1.0f) + PPG_PI_F * __builtin_floorf(2 * sy + 0.5f);
+            dm_sincos(phiM, &sinPhiM, &cosPhiM);
+            float cosSc = cosPhiM / d.alphaU, sinSc = sinPhiM / d.alphaV;
+            alphaSqr = 1.0f / (cosSc * cosSc + sinSc * sinSc);
+        }
+        if (d.type == MFD_BECKMANN) {
+            float tanThetaMSqr = alphaSqr * -dm_log(1.0f - sx);
+            cosThetaM = 1.0f / __builtin_sqrtf(1.0f + tanThetaMSqr);
+            pdf = (1.0f - sx) / (PPG_PI_F * d.alphaU * d.alphaV * cosThetaM * cosThetaM * cosThetaM);
+        } else {
+            float tanThetaMSqr = alphaSqr * sx / (1.0f - sx);
+            cosThetaM = 1.0f / __builtin_sqrtf(1.0f + tanThetaMSqr);
+            float temp = 1 + tanThetaMSqr / alphaSqr;
+            pdf = PPG_INV_PI_F / (d.alphaU * d.alphaV * cosThetaM * cosThetaM * cosThetaM * temp * temp);
+        }
+    } else {
+        float phiM;
+        float exponent;
+        if (d.alphaU == d.alphaV) {
+            phiM = (2.0f * PPG_PI_F) * sy;
+            exponent = d.exponentU;
+        } else if (sy < 0.25f) {
+            mfd_sample_first_quadrant(d, 4 * sy, phiM, exponent);
+        } else if (sy < 0.5f) {
+            mfd_sample_first_quadrant(d, 4 * (0.5f - sy), phiM, exponent);
+            phiM = PPG_PI_F - phiM;
+        } else if (sy < 0.75f) {
+            mfd_sample_first_quadrant(d, 4 * (sy - 0.5f), phiM, exponent);
+            phiM += PPG_PI_F;
+        } else {
+            mfd_sample_first_quadrant(d, 4 * (1 - sy), phiM, exponent);
+            phiM = 2 * PPG_PI_F - phiM;
+        }
+        dm_sincos(phiM, &sinPhiM, &cosPhiM);
+        cosThetaM = dm_pow(sx, 1.0f / (exponent + 2.0f));
+        pdf = __builtin_sqrtf((d.exponentU + 2.0f) * (d.exponentV + 2.0f)) * 0.15915494309189533577f * dm_pow(cosThetaM, exponent + 1.0f);
+    }
+    if (pdf < 1e-20f) pdf = 0;
+    float sinThetaM = __builtin_sqrtf(ppg_max(0.0f, 1 - cosThetaM * cosThetaM));
+    return f3(sinThetaM * cosPhiM, sinThetaM * sinPhiM, cosThetaM);
+}
+// sample(wi, sample, pdf) and pdf(wi, m): the m_sampleVisible switch, microfacet.h:240-275.  .w = the density.
+MFD_CALL float4 mfd_sample(Mfd d, F3 wi, float sx, float sy) {
+    float pdf;
+    F3 m;
+    if (!d.sampleAll) { m = ggx_sample_visible(d, wi, sx, sy); pdf = ggx_pdf_visible(d, wi, m); }
+    else m = mfd_sample_all(d, sx, sy, pdf);
+    return make_float4(m.x, m.y, m.z, pdf);
+}
+D float mfd_pdf(const Mfd &d, F3 wi, F3 m) {
+    if (!d.sampleAll) return ggx_pdf_visible(d, wi, m);
+    return ggx_eval(d, m) * m.z;  // pdfAll
+}
+#endif
 
 // plastic.cpp:191-204 (configure) — recomputed per call from the material record, same arithmetic as the oracle's configure()
 D float plastic_prob_specular(const Mat &M, float Fi) {
@@ -1833,7 +2046,7 @@ D F3 mat_eval_one(const Mat &M, F3 wi, F3 wo) {
     if (M.type == PPG_BSDF_ROUGHCONDUCTOR) {  // roughconductor.cpp:247-282
         if (wi.z <= 0 || wo.z <= 0) return f3s(0.0f);
         F3 H = norm3(wo + wi);
-        const Mfd distr{M.alpha, (M.flags & PPG_MAT_BECKMANN) != 0};
+        const Mfd distr = PPG_MAT_MFD(M);
         const float Dm = ggx_eval(distr, H);
         if (Dm == 0) return f3s(0.0f);
         const F3 F = mul3(fresnel_conductor_exact(dot3(wi, H), M.eta, M.k), M.refl);
@@ -1852,7 +2065,7 @@ D F3 mat_eval_one(const Mat &M, F3 wi, F3 wo) {
             H = norm3(wi + wo * eta);
         }
         H = H * fsignum(H.z);
-        const Mfd distr{M.alpha, (M.flags & PPG_MAT_BECKMANN) != 0};
+        const Mfd distr = PPG_MAT_MFD(M);
         const float Dm = ggx_eval(distr, H);
         if (Dm == 0) return f3s(0.0f);
         const float F = fresnel_dielectric_ext(dot3(wi, H), m_eta);
@@ -1869,7 +2082,7 @@ D F3 mat_eval_one(const Mat &M, F3 wi, F3 wo) {
     }
     if (M.type == PPG_BSDF_ROUGHPLASTIC) {  // roughplastic.cpp:330-384
         if (wi.z <= 0 || wo.z <= 0) return f3s(0.0f);
-        const Mfd distr{M.alpha, (M.flags & PPG_MAT_BECKMANN) != 0};
+        const Mfd distr = PPG_MAT_MFD(M);
         const F3 H = norm3(wo + wi);
         const float Dm = ggx_eval(distr, H);
         const float F = fresnel_dielectric_ext(dot3(wi, H), M.eta.x);
@@ -1894,7 +2107,10 @@ D float mat_pdf_one(const Mat &M, F3 wi, F3 wo) {
     if (M.type == PPG_BSDF_ROUGHCONDUCTOR) {  // roughconductor.cpp:284-307
         if (wi.z <= 0 || wo.z <= 0) return 0.0f;
         F3 H = norm3(wo + wi);
-        const Mfd distr{M.alpha, (M.flags & PPG_MAT_BECKMANN) != 0};
+        const Mfd distr = PPG_MAT_MFD(M);
+#if PPG_MFD
+        if (distr.sampleAll) return mfd_pdf(distr, wi, H) / (4 * ppg_abs(dot3(wo, H)));  // roughconductor.cpp:316-320
+#endif
         return ggx_eval(distr, H) * ggx_smith_g1(distr, wi, H) / (4.0f * wi.z);
     }
     if (M.type == PPG_BSDF_ROUGHDIELECTRIC) {  // roughdielectric.cpp:342-418
@@ -1912,19 +2128,29 @@ D float mat_pdf_one(const Mat &M, F3 wi, F3 wo) {
             dwh_dwo = (eta * eta * dot3(wo, H)) / (sqrtDenom * sqrtDenom);
         }
         H = H * fsignum(H.z);
-        const Mfd distr{M.alpha, (M.flags & PPG_MAT_BECKMANN) != 0};
+#if PPG_MFD
+        Mfd sampleDistr = mat_mfd(M);  // Walter's trick, roughdielectric.cpp:406-411
+        if (sampleDistr.sampleAll) sampleDistr = mfd_scale_alpha(sampleDistr, 1.2f - 0.2f * __builtin_sqrtf(ppg_abs(wi.z)));
+        float prob = mfd_pdf(sampleDistr, wi * fsignum(wi.z), H);
+#else
+        const Mfd distr = PPG_MAT_MFD(M);
         float prob = ggx_pdf_visible(distr, wi * fsignum(wi.z), H);
+#endif
         float F = fresnel_dielectric_ext(dot3(wi, H), m_eta);
         prob *= reflect ? F : (1 - F);
         return ppg_abs(prob * dwh_dwo);
     }
     if (M.type == PPG_BSDF_ROUGHPLASTIC) {  // roughplastic.cpp:386-437
         if (wi.z <= 0 || wo.z <= 0) return 0.0f;
-        const Mfd distr{M.alpha, (M.flags & PPG_MAT_BECKMANN) != 0};
+        const Mfd distr = PPG_MAT_MFD(M);
         const F3 H = norm3(wo + wi);
         const float pS = roughplastic_prob_specular(M, wi.z), pD = 1 - pS;
         const float dwh_dwo = 1.0f / (4.0f * dot3(wo, H));
+#if PPG_MFD
+        const float prob = mfd_pdf(distr, wi, H);
+#else
         const float prob = ggx_pdf_visible(distr, wi, H);
+#endif
         float result = prob * dwh_dwo * pS;
         result += pD * (PPG_INV_PI_F * wo.z);
         return result;
@@ -1954,24 +2180,41 @@ D F3 mat_sample_one(const Mat &M, F3 wi, float sx, float sy, F3 &wo, float &pdf,
             return mul3(M.refl, fresnel_conductor_exact(wi.z, M.eta, M.k));
         case PPG_BSDF_ROUGHCONDUCTOR: {  // roughconductor.cpp:367-415
             if (wi.z < 0) return f3s(0.0f);
-            const Mfd distr{M.alpha, (M.flags & PPG_MAT_BECKMANN) != 0};
+            const Mfd distr = PPG_MAT_MFD(M);
+#if PPG_MFD
+            const float4 ms = mfd_sample(distr, wi, sx, sy);
+            F3 m = f3(ms.x, ms.y, ms.z);
+            pdf = ms.w;
+#else
             F3 m = ggx_sample_visible(distr, wi, sx, sy);
             pdf = ggx_pdf_visible(distr, wi, m);
+#endif
             if (pdf == 0) return f3s(0.0f);
             wo = m * (2 * dot3(wi, m)) - wi;
             if (wo.z <= 0) return f3s(0.0f);
             F3 F = mul3(fresnel_conductor_exact(dot3(wi, m), M.eta, M.k), M.refl);
+#if PPG_MFD
+            float weight;
+            if (!distr.sampleAll) weight = ggx_smith_g1(distr, wo, m);
+            else weight = ggx_eval(distr, m) * (ggx_smith_g1(distr, wi, m) * ggx_smith_g1(distr, wo, m)) * dot3(wi, m) / (pdf * wi.z);
+#else
             float weight = ggx_smith_g1(distr, wo, m);
+#endif
             pdf /= 4.0f * dot3(wo, m);
             return F * weight;
         }
         case PPG_BSDF_ROUGHPLASTIC: {  // roughplastic.cpp:439-501
             if (wi.z <= 0) return f3s(0.0f);
-            const Mfd distr{M.alpha, (M.flags & PPG_MAT_BECKMANN) != 0};
+            const Mfd distr = PPG_MAT_MFD(M);
             const float pS = roughplastic_prob_specular(M, wi.z);
             if (sy < pS) {
                 sy /= pS;
+#if PPG_MFD
+                const float4 ms = mfd_sample(distr, wi, sx, sy);
+                const F3 m = f3(ms.x, ms.y, ms.z);
+#else
                 const F3 m = ggx_sample_visible(distr, wi, sx, sy);
+#endif
                 wo = m * (2 * dot3(wi, m)) - wi;
                 if (wo.z <= 0) return f3s(0.0f);
             } else {
@@ -2017,10 +2260,18 @@ D F3 mat_sample_one(const Mat &M, F3 wi, float sx, float sy, F3 &wo, float &pdf,
         }
         case PPG_BSDF_ROUGHDIELECTRIC: {  // roughdielectric.cpp:514-606
             const float m_eta = M.eta.x, m_invEta = 1 / m_eta;
-            const Mfd distr{M.alpha, (M.flags & PPG_MAT_BECKMANN) != 0};
+            const Mfd distr = PPG_MAT_MFD(M);
             const F3 wis = wi * fsignum(wi.z);
+#if PPG_MFD
+            Mfd sampleDistr = distr;  // Walter's trick, roughdielectric.cpp:535-540
+            if (distr.sampleAll) sampleDistr = mfd_scale_alpha(distr, 1.2f - 0.2f * __builtin_sqrtf(ppg_abs(wi.z)));
+            const float4 ms = mfd_sample(sampleDistr, wis, sx, sy);
+            const F3 m = f3(ms.x, ms.y, ms.z);
+            const float microfacetPDF = ms.w;
+#else
             const F3 m = ggx_sample_visible(distr, wis, sx, sy);
             const float microfacetPDF = ggx_pdf_visible(distr, wis, m);
+#endif
             if (microfacetPDF == 0) return f3s(0.0f);
             pdf = microfacetPDF;
             float cosThetaT;
@@ -2047,6 +2298,11 @@ D F3 mat_sample_one(const Mat &M, F3 wi, float sx, float sy, F3 &wo, float &pdf,
                 float sqrtDenom = dot3(wi, m) + eta * dot3(wo, m);
                 dwh_dwo = (eta * eta * dot3(wo, m)) / (sqrtDenom * sqrtDenom);
             }
+#if PPG_MFD
+            if (distr.sampleAll)  // roughdielectric.cpp:608-611
+                weight = weight * ppg_abs(ggx_eval(distr, m) * (ggx_smith_g1(distr, wi, m) * ggx_smith_g1(distr, wo, m)) * dot3(wi, m) / (microfacetPDF * wi.z));
+            else
+#endif
             weight = weight * ggx_smith_g1(distr, wo, m);
             pdf *= ppg_abs(dwh_dwo);
             return weight;

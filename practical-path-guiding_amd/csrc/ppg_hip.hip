@@ -825,6 +825,9 @@ struct ppg_ctx {
     DevBuf<float4> d_delta;
     std::vector<ppg_shape> shapes;  // ppg_set_shapes: kept until replaced; ppg_set_scene validates it and builds d_shapes from it
     DevBuf<float4> d_shapes;
+    std::vector<ppg_microfacet> microfacet;  // ppg_set_microfacet: kept until replaced; ppg_set_scene validates it and builds d_mfd from it
+    DevBuf<float4> d_mfd;
+    uint32_t nMaterials = 0;       // of the scene set last (ppg_debug_bsdf checks its items against it)
     bool renderOpen = false;       // between ppg_begin_render and ppg_end_render
     int W = 0, H = 0;
 
@@ -1009,11 +1012,13 @@ struct ppg_ctx {
 };
 
 void ppg_launch_shade(int variant, const ShadeLaunch &a) {
+    if (a.S.mfd) { ppg_launch_shade_ext(variant, a); return; }  // a general microfacet entry: the extended family, shapes or not
     if (a.S.n_shapes) { ppg_launch_shade_shapes(variant, a); return; }  // (such a scene is FULL and never small)
     if (variant >> 1) ppg_launch_shade_pair1(variant, a);
     else ppg_launch_shade_pair0(variant, a);
 }
 void ppg_launch_tail(int variant, const TailLaunch &a) {
+    if (a.S.mfd) { ppg_launch_tail_ext(variant, a); return; }
     if (a.S.n_shapes) { ppg_launch_tail_shapes(variant, a); return; }
     switch (variant >> 1) {
         case 0: ppg_launch_tail_pair0(variant, a); break;
@@ -1834,7 +1839,7 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
         if (((chunks + (size_t)ctx->tuneBlocksSmall - 1) / (size_t)ctx->tuneBlocksSmall) * PPG_DCHUNK <= (size_t)ctx->queues.cap) grid = ctx->tuneBlocksSmall;
     }
     const int gridAll = gridFor(P.n_paths);
-    const bool smallScene = ctx->scene.n_tris <= 64 && ctx->ldsTris == ctx->scene.n_tris && ctx->scene.n_spheres == 0 && ctx->scene.n_shapes == 0 && !ctx->tuneForceBvh;
+    const bool smallScene = ctx->scene.n_tris <= 64 && ctx->ldsTris == ctx->scene.n_tris && ctx->scene.n_spheres == 0 && ctx->scene.n_shapes == 0 && !ctx->scene.mfd && !ctx->tuneForceBvh;
     // (small scenes go through k_trace too: tracing them inside k_generate / k_shade was measured slower, DESIGN.md "Tuning switches")
     const bool neeOn = ctx->doNee;  // m_doNee of this iteration (doNeeWithSpp, GP:1331-1340)
     const bool fullMats = ctx->fullMaterials;  // any BSDF beyond diffuse / two-sided diffuse / mirror: the FULL kernel variants
@@ -1894,7 +1899,8 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
             unsigned int *const trSorted = sortSlices ? ctx->d_queueSorted.p : nullptr;
             unsigned char *const trKeys = sortSlices ? ctx->d_sortKeys.p : nullptr;
             timedLaunch(ctx, "k_trace", hostCount, [&] {
-                if (S.n_shapes) ppg_launch_trace_shapes(ctx->timer.enabled, grid, traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
+                if (S.mfd) ppg_launch_trace_ext(ctx->timer.enabled, grid, traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
+                else if (S.n_shapes) ppg_launch_trace_shapes(ctx->timer.enabled, grid, traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
                 else if (smallScene) hipLaunchKernelGGL((k_trace<true, false>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, 0, ctx->ldsTris, trSorted, trKeys);
                 else if (ctx->timer.enabled) hipLaunchKernelGGL((k_trace<false, true>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
                 else hipLaunchKernelGGL((k_trace<false, false>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
@@ -3107,6 +3113,66 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
             return PPG_ERR_INVALID;
         }
     }
+    // ppg_set_microfacet: the general MicrofacetDistribution of the three rough plug-ins
+    bool anyGeneral = false;
+    std::vector<float4> mfdTab;
+    if (!ctx->microfacet.empty()) {
+        if (ctx->microfacet.size() != s->n_materials) {
+            ctx->error = "microfacet: the list has " + std::to_string(ctx->microfacet.size()) + " entries, the scene " + std::to_string(s->n_materials) + " materials";
+            return PPG_ERR_INVALID;
+        }
+        mfdTab.assign(s->n_materials, make_float4(0, 0, 0, 0));
+        for (uint32_t i = 0; i < s->n_materials; ++i) {
+            const ppg_microfacet &g = ctx->microfacet[i];
+            const ppg_material &m = s->materials[i];
+            const std::string who = "material " + std::to_string(i) + ": microfacet: ";
+            if (g._reserved[0] || g._reserved[1] || g._reserved[2]) { ctx->error = who + "_reserved must be 0"; return PPG_ERR_INVALID; }
+            if (!g.general) continue;
+            if (m.type != PPG_BSDF_ROUGHCONDUCTOR && m.type != PPG_BSDF_ROUGHDIELECTRIC && m.type != PPG_BSDF_ROUGHPLASTIC) {
+                ctx->error = who + "only roughconductor, roughdielectric and roughplastic have a microfacet distribution"; return PPG_ERR_INVALID;
+            }
+            if (g.distribution != 0 && g.distribution != 1) { ctx->error = who + "distribution must be 0 (ggx / beckmann) or 1 (phong)"; return PPG_ERR_INVALID; }
+            if (!std::isfinite(g.alpha_v)) { ctx->error = who + "alpha_v is not finite"; return PPG_ERR_INVALID; }
+            if (g.alpha_v_texture > s->n_textures || (g.alpha_v_texture && !s->textures)) { ctx->error = who + "alpha_v_texture: index out of range"; return PPG_ERR_INVALID; }
+            const float alphaU = ppg_max(m.alpha, 1e-4f), alphaV = ppg_max(g.alpha_v, 1e-4f);
+            if (m.type == PPG_BSDF_ROUGHPLASTIC && g.alpha_v_texture) {
+                ctx->error = who + "alpha_v_texture: roughplastic's rough-transmittance slice is tabulated for one alpha; a roughness map is not supported"; return PPG_ERR_INVALID;
+            }
+            if (m.type == PPG_BSDF_ROUGHPLASTIC && alphaU != alphaV) {  // roughplastic.cpp:221
+                ctx->error = who + "roughplastic: the 'roughplastic' plugin currently does not support anisotropic microfacet distributions!"; return PPG_ERR_INVALID;
+            }
+            const bool alphaTextured = g.alpha_v_texture || (!ctx->materialTextures.empty() && ctx->materialTextures[i].alpha);
+            uint32_t bits = PPG_MFDF_GENERAL;
+            if (g.distribution == 1) bits |= PPG_MFDF_PHONG | PPG_MFDF_SAMPLE_ALL;  // microfacet.h:141-142
+            if (g.sample_all) bits |= PPG_MFDF_SAMPLE_ALL;
+            if (alphaU != alphaV || alphaTextured) bits |= PPG_MFDF_ANISO;
+            mfdTab[i] = make_float4(alphaV, __builtin_bit_cast(float, bits), __builtin_bit_cast(float, g.alpha_v_texture), 0.0f);
+            anyGeneral = true;
+        }
+        for (uint32_t k = 0; anyGeneral && k < s->n_spheres; ++k)
+            if (__builtin_bit_cast(uint32_t, mfdTab[s->spheres[k].material].z)) { ctx->error = "sphere: a textured alphaV is only supported on triangle meshes"; return PPG_ERR_INVALID; }
+        for (size_t k = 0; anyGeneral && k < ctx->shapes.size(); ++k)
+            if (__builtin_bit_cast(uint32_t, mfdTab[ctx->shapes[k].material].z)) { ctx->error = "shape " + std::to_string(k) + ": a textured alphaV is only supported on triangle meshes"; return PPG_ERR_INVALID; }
+        // an anisotropic BSDF needs UV tangents, which need texture coordinates (trimesh.cpp:686-691)
+        for (uint32_t t = 0; anyGeneral && t < s->n_triangles; ++t) {
+            if (!(__builtin_bit_cast(uint32_t, mfdTab[s->tri_material[t]].y) & PPG_MFDF_ANISO)) continue;
+            bool has = s->texcoords != nullptr;
+            for (int v = 0; has && v < 3; ++v) { const float q = s->texcoords[2 * (size_t)s->indices[3 * (size_t)t + v]]; if (q != q) has = false; }
+            if (!has) {
+                ctx->error = "triangle " + std::to_string(t) + ": material " + std::to_string(s->tri_material[t]) +
+                             ": anisotropic microfacet distribution: the mesh is missing texture coordinates! The tangent space cannot be computed";
+                return PPG_ERR_INVALID;
+            }
+        }
+    }
+    ctx->scene.mfd = nullptr;
+    ctx->nMaterials = s->n_materials;
+    if (anyGeneral) {
+        HIP_CHECK(ctx->d_mfd.reserve(mfdTab.size()));
+        HIP_CHECK(hipMemcpy(ctx->d_mfd.p, mfdTab.data(), mfdTab.size() * sizeof(float4), hipMemcpyHostToDevice));
+        ctx->scene.mfd = ctx->d_mfd.p;
+        ctx->fullMaterials = true;  // (the rough types are FULL anyway)
+    }
     ctx->scene.uvs = nullptr; ctx->scene.textures = nullptr;
     if (s->texcoords) {
         std::vector<float2> uv(3 * (size_t)s->n_triangles);
@@ -3699,6 +3765,13 @@ int ppg_set_material_textures(ppg_ctx *ctx, const ppg_material_textures *slots, 
     return PPG_OK;
 }
 
+int ppg_set_microfacet(ppg_ctx *ctx, const ppg_microfacet *m, uint32_t n_materials) {
+    if (ctx->renderOpen) { ctx->error = "microfacet: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (!m) n_materials = 0;
+    ctx->microfacet.assign(m, m + n_materials);  // validated against the scene by ppg_set_scene
+    return PPG_OK;
+}
+
 int ppg_set_delta_emitters(ppg_ctx *ctx, const ppg_delta_emitter *em, uint32_t n) {
     if (ctx->renderOpen) { ctx->error = "delta emitters: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
     if (n && !em) { ctx->error = "delta emitters: no list"; return PPG_ERR_INVALID; }
@@ -3771,6 +3844,26 @@ int ppg_debug_sample_direct(ppg_ctx *ctx, uint32_t n, const float *ref, const fl
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_direct), hipMemcpyDeviceToHost));
+    return PPG_OK;
+}
+
+int ppg_debug_bsdf(ppg_ctx *ctx, uint32_t n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out) {
+    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
+    if (ctx->renderOpen) { ctx->error = "ppg_debug_bsdf: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (n && (!items || !out)) { ctx->error = "ppg_debug_bsdf: no arrays"; return PPG_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; ++i)
+        if (items[i].material < 0 || (uint32_t)items[i].material >= ctx->nMaterials) { ctx->error = "ppg_debug_bsdf: item " + std::to_string(i) + ": material out of range"; return PPG_ERR_INVALID; }
+    if (n == 0) return PPG_OK;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->quiesce();
+    DebugBuf dItems, dOut;
+    HIP_CHECK(dItems.fill(items, (size_t)n * sizeof(ppg_debug_bsdf_item)));
+    HIP_CHECK(dOut.fill(nullptr, (size_t)n * sizeof(ppg_debug_bsdf_out)));
+    const unsigned int block = 64;
+    ppg_launch_debug_bsdf((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const ppg_debug_bsdf_item *)dItems.p, (ppg_debug_bsdf_out *)dOut.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_bsdf_out), hipMemcpyDeviceToHost));
     return PPG_OK;
 }
 

@@ -5,6 +5,9 @@
  * 8..10, compiled with -DPPG_SHAPES=1 as well: the kernels of scenes with analytic disks or cylinders (ppg_device.h PPG_SHAPES) — 8
  * k_shade_shapes<NEE, true>, 9 k_tail_shapes<false, NEE, true>, 10 k_trace_shapes<false, COUNT> and the two kernels of the test hooks
  * ppg_debug_intersect / ppg_debug_sample_direct.
+ * 11..13, compiled with -DPPG_SHAPES=1 -DPPG_MFD=1: the "extended" kernels of scenes whose microfacet list has a general entry
+ * (ppg_set_microfacet; ppg_device.h PPG_MFD) — 11 k_shade_ext<NEE, true>, 12 k_tail_ext<false, NEE, true>, 13 k_trace_ext<false, COUNT> (its
+ * sort_slice keeps general materials out of the COMMON classes) and the kernel of the test hook ppg_debug_bsdf.
  */
 #include <hip/hip_runtime.h>
 
@@ -14,13 +17,67 @@
 #include "ppg_launch.h"
 
 #ifndef PPG_INST
-#error "compile with -DPPG_INST=0..10"
+#error "compile with -DPPG_INST=0..13"
 #endif
 #if (PPG_INST >= 8) != (PPG_SHAPES != 0)
-#error "units 8..10, and only they, are compiled with -DPPG_SHAPES=1"
+#error "units 8..13, and only they, are compiled with -DPPG_SHAPES=1"
+#endif
+#if (PPG_INST >= 11) != (PPG_MFD != 0)
+#error "units 11..13, and only they, are compiled with -DPPG_MFD=1"
 #endif
 
-#if PPG_INST == 8
+#if PPG_INST == 11
+void ppg_launch_shade_ext(int variant, const ShadeLaunch &a) {
+    if (variant & 2)
+        hipLaunchKernelGGL((k_shade<true, true>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, a.P, a.S, a.T, a.R, a.Q, a.qin, a.small_scene, a.sorted_items);
+    else
+        hipLaunchKernelGGL((k_shade<false, true>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, a.P, a.S, a.T, a.R, a.Q, a.qin, a.small_scene, a.sorted_items);
+}
+#elif PPG_INST == 12
+void ppg_launch_tail_ext(int variant, const TailLaunch &a) {
+    if (variant & 2)
+        hipLaunchKernelGGL((k_tail<false, true, true>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, a.P, a.S, a.T, a.R, a.dense, a.total, a.ticket, a.stats, a.lds_tris, a.longest, a.strag, a.lane_limit);
+    else
+        hipLaunchKernelGGL((k_tail<false, false, true>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, a.P, a.S, a.T, a.R, a.dense, a.total, a.ticket, a.stats, a.lds_tris, a.longest, a.strag, a.lane_limit);
+}
+#elif PPG_INST == 13
+#include "../../include/ppg_testhooks.h"
+void ppg_launch_trace_ext(bool count, int grid, size_t lds, hipStream_t stream, const PathState &P, const DevScene &S, const Queues &Q, int qin, int lds_nodes,
+                          int lds_tris, unsigned int *sorted, unsigned char *keys) {
+    if (count) hipLaunchKernelGGL((k_trace<false, true>), dim3(grid), dim3(PPG_BLOCK), lds, stream, P, S, Q, qin, lds_nodes, lds_tris, sorted, keys);
+    else hipLaunchKernelGGL((k_trace<false, false>), dim3(grid), dim3(PPG_BLOCK), lds, stream, P, S, Q, qin, lds_nodes, lds_tris, sorted, keys);
+}
+// ppg_debug_bsdf: the material as shade_one prepares it at a hit with texture coordinates uv, then the render's mat_eval / mat_pdf / mat_sample
+__global__ void k_debug_bsdf(DevScene S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out) {
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const ppg_debug_bsdf_item it = items[i];
+    Mat M = load_material(S, it.material);
+    const unsigned int tex = __float_as_uint(S.materials[PPG_MAT_STRIDE * (size_t)it.material + 5].x);
+    if (tex & 0xffffu) M.refl = tex_eval(S.textures[(tex & 0xffffu) - 1u], it.uv[0], it.uv[1]);
+    mat_apply_textures(S, it.material, it.uv[0], it.uv[1], M);
+    mat_apply_mfd_textures(S, it.material, it.uv[0], it.uv[1], M);
+    const F3 wi = f3(it.wi[0], it.wi[1], it.wi[2]), wo = f3(it.wo[0], it.wo[1], it.wo[2]);
+    ppg_debug_bsdf_out r;
+    memset(&r, 0, sizeof r);
+    const F3 f = mat_eval(M, wi, wo);
+    r.eval[0] = f.x; r.eval[1] = f.y; r.eval[2] = f.z;
+    r.pdf = mat_pdf(M, wi, wo);
+    F3 swo;
+    float spdf, seta;
+    bool delta, isnull;
+    unsigned int dim = 0;
+    const F3 w = mat_sample(M, wi, it.sample[0], it.sample[1], swo, spdf, delta, seta, isnull, it.key, dim);
+    r.wo[0] = swo.x; r.wo[1] = swo.y; r.wo[2] = swo.z;
+    r.sampled_pdf = spdf;
+    r.weight[0] = w.x; r.weight[1] = w.y; r.weight[2] = w.z;
+    r.eta = seta; r.delta = delta ? 1 : 0; r.is_null = isnull ? 1 : 0;
+    out[i] = r;
+}
+void ppg_launch_debug_bsdf(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out) {
+    hipLaunchKernelGGL(k_debug_bsdf, dim3(grid), dim3(block), 0, stream, S, n, items, out);
+}
+#elif PPG_INST == 8
 void ppg_launch_shade_shapes(int variant, const ShadeLaunch &a) {
     if (variant & 2)
         hipLaunchKernelGGL((k_shade<true, true>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, a.P, a.S, a.T, a.R, a.Q, a.qin, a.small_scene, a.sorted_items);

@@ -466,6 +466,9 @@ struct SortArgs {
     BlockStats *stats;
     unsigned int n_paths;
     int n_tris;
+#if PPG_MFD
+    const float4 *mfd;        // DevScene::mfd: a material with a general microfacet entry is never a COMMON class
+#endif
 };
 D SortArgs sort_args(const PathState &P, const DevScene &S, const Queues &Q, unsigned int b, unsigned int *sorted, unsigned char *keys) {
     SortArgs a;
@@ -473,6 +476,9 @@ D SortArgs sort_args(const PathState &P, const DevScene &S, const Queues &Q, uns
     a.out = sorted + (size_t)b * Q.cap; a.kk = keys + (size_t)b * Q.cap;
     a.count1 = Q.count[1] + b; a.n_common = Q.n_common ? Q.n_common + b : nullptr; a.stats = Q.stats + b;
     a.n_paths = P.n_paths; a.n_tris = S.n_tris;
+#if PPG_MFD
+    a.mfd = S.mfd;
+#endif
     return a;
 }
 D void sort_slice(const SortArgs &a, const Work &work, unsigned int b, unsigned int nb, unsigned int *hist, unsigned int *offs) {
@@ -494,7 +500,12 @@ D void sort_slice(const SortArgs &a, const Work &work, unsigned int b, unsigned 
                     const int type = (int)mr[0].w, flags = __float_as_int(mr[2].w);
                     const float4 tw = mr[5];  // (texture word, specular, alpha, opacity texture)
                     const unsigned int tex = __float_as_uint(tw.x), slots = __float_as_uint(tw.y) | __float_as_uint(tw.z) | __float_as_uint(tw.w);
+#if PPG_MFD
+                    const bool general = a.mfd && (__float_as_uint(a.mfd[m].y) & PPG_MFDF_GENERAL) != 0u;
+                    if ((flags & PPG_MAT_MASK) || (tex >> 16) || slots || general) key = 13u;
+#else
                     if ((flags & PPG_MAT_MASK) || (tex >> 16) || slots) key = 13u;
+#endif
                     else if (mset_common_type(type)) key = type == PPG_BSDF_ROUGHPLASTIC ? 6u : (unsigned int)type;  // 0..6
                     else key = 8u + ((unsigned int)type & 3u);  // dielectric 10, thin dielectric 11, rough dielectric 8
                 }
@@ -1103,6 +1114,9 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
         // bitmaps on specular / alpha / opacity (never in the COMMON part: sort_slice keeps such surfaces out of it)
         static_assert(PPG_PARAM_TEXTURES || MSET == MSET_COMMON, "this translation unit was compiled without Mat::spec_lum");
         if (FULL && MSET != MSET_COMMON) mat_apply_textures(S, I.material, X.u, X.v, M);
+#if PPG_MFD
+        if (FULL && MSET != MSET_COMMON) mat_apply_mfd_textures(S, I.material, X.u, X.v, M);
+#endif
         // (one call site per BSDF function: the bumped variant only transforms the arguments first — two inlined copies of the whole
         // material switch per function made the FULL kernels 330 KB of code, five times the instruction cache)
         auto to_pert = [&](F3 v_) { const F3 w_ = to_world(I, v_); return f3(dot3(w_, ps), dot3(w_, pt), dot3(w_, pn)); };

@@ -80,6 +80,15 @@ struct ppg_debug_direct;
 void ppg_launch_debug_intersect(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_hit *out, int any);
 void ppg_launch_debug_sample_direct(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float *ref, const float *ref_n, const float *u,
                                     ppg_debug_direct *out);
+// Scenes with a general microfacet entry (ppg_set_microfacet): the same three kernels built with -DPPG_SHAPES=1 -DPPG_MFD=1, the "extended"
+// family — k_shade_ext<NEE, true>, k_tail_ext<false, NEE, true>, k_trace_ext<false, COUNT> with the kernel of ppg_debug_bsdf
+void ppg_launch_shade_ext(int variant, const ShadeLaunch &a);
+void ppg_launch_tail_ext(int variant, const TailLaunch &a);
+void ppg_launch_trace_ext(bool count, int grid, size_t lds, hipStream_t stream, const PathState &P, const DevScene &S, const Queues &Q, int qin, int lds_nodes,
+                          int lds_tris, unsigned int *sorted, unsigned char *keys);
+struct ppg_debug_bsdf_item;
+struct ppg_debug_bsdf_out;
+void ppg_launch_debug_bsdf(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out);
 // k_shade<false, FULL, MSET_COMMON> over the front part of the sorted slices (a.qin = QIN_SORTED_COMMON)
 void ppg_launch_shade_common(const ShadeLaunch &a);
 

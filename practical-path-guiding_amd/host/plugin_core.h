@@ -3,7 +3,7 @@
  * the integrator's properties to ppg_config, and the control flow of Integrator::render() / cancel() above the C-ABI —
  *
  *     configure(props)                       GuidedPathTracer(const Properties &), GP:1014-1085 (names and defaults verbatim)
- *     render(scene, destinationFile)         ppg_create → [ppg_set_delta_emitters → ppg_set_material_textures → ppg_set_shapes →] ppg_set_scene → ppg_render, GP:1516-1585; the SD-tree dumps go to
+ *     render(scene, destinationFile)         ppg_create → [ppg_set_delta_emitters → ppg_set_material_textures → ppg_set_shapes → ppg_set_microfacet →] ppg_set_scene → ppg_render, GP:1516-1585; the SD-tree dumps go to
  *                                            "<destinationFile>-NN.sdt" (GP:1191-1195), which is only known HERE — so the context is created
  *                                            here and not in the constructor (round 3's shim created it in the constructor and then changed a
  *                                            prefix the context had already copied: dumpSDTree through the plug-in wrote nothing)
@@ -71,6 +71,8 @@ public:
     void setMaterialTextures(const ppg_material_textures *t, size_t n) { m_materialTextures.assign(t, t + n); }
     // the scene's analytic disks and cylinders (ppg_set_shapes); n = 0: none
     void setShapes(const ppg_shape *s, size_t n) { m_shapes.assign(s, s + n); }
+    // the general microfacet entries (ppg_set_microfacet): one per material, or n = 0: none
+    void setMicrofacet(const ppg_microfacet *g, size_t n) { m_microfacet.assign(g, g + n); }
     const ppg_config &config() const { return m_cfg; }
 
     // PPG_OK, PPG_ERR_CANCELLED, or an error code with `err` set.  May be called again (a new context per render, like a new RenderJob).
@@ -98,6 +100,8 @@ public:
         rc = ppg_set_material_textures(ctx, m_materialTextures.data(), (uint32_t)m_materialTextures.size());
         if (rc != PPG_OK) { err = ppg_last_error(ctx); return rc; }
         rc = ppg_set_shapes(ctx, m_shapes.data(), (uint32_t)m_shapes.size());
+        if (rc != PPG_OK) { err = ppg_last_error(ctx); return rc; }
+        rc = ppg_set_microfacet(ctx, m_microfacet.data(), (uint32_t)m_microfacet.size());
         if (rc != PPG_OK) { err = ppg_last_error(ctx); return rc; }
         rc = ppg_set_scene(ctx, &scene);  // (a cancel() during these seconds of BVH build stays set in the context: ppg_render returns at once)
         if (rc != PPG_OK) { err = ppg_last_error(ctx); return rc; }
@@ -146,6 +150,7 @@ private:
     std::vector<ppg_delta_emitter> m_deltaEmitters;
     std::vector<ppg_material_textures> m_materialTextures;
     std::vector<ppg_shape> m_shapes;
+    std::vector<ppg_microfacet> m_microfacet;
     std::mutex m_mutex;
 };
 

@@ -129,7 +129,12 @@ static bool loadSceneChecked(const char *path, SceneData &s) {
         s.shapes.resize(n);
         f.read((char *)s.shapes.data(), (std::streamsize)(n * sizeof(ppg_shape)));
     }
-    if (hdr[5] >> 11) return false;  // a block this reader does not know
+    if (hdr[5] & 2048) {  // bit 11: the general microfacet entries (n_materials x ppg_microfacet), only when a material has one
+        if (!fits((uint64_t)nm * sizeof(ppg_microfacet))) return false;
+        s.microfacet.resize(nm);
+        f.read((char *)s.microfacet.data(), (std::streamsize)((size_t)nm * sizeof(ppg_microfacet)));
+    }
+    if (hdr[5] >> 12) return false;  // a block this reader does not know
     return (bool)f;
 }
 
@@ -200,7 +205,8 @@ static bool saveScene(const char *path, const SceneData &s) {
     const uint32_t hdr[6] = {(uint32_t)(s.positions.size() / 3), (uint32_t)(s.indices.size() / 3), (uint32_t)s.materials.size(), (uint32_t)s.emitters.size(),
                              s.normals.empty() ? 0u : 1u, (s.hasEnvironment ? 1u : 0u) | (s.rtrans.empty() ? 0u : 2u) | (s.spheres.empty() ? 0u : 4u) | (s.hasEnvmap ? 8u : 0u) |
                                  (s.texcoords.empty() ? 0u : 16u) | (s.textures.empty() ? 0u : 32u) | (s.hasRFilter ? 64u : 0u) | (s.hasLens ? 128u : 0u) |
-                                 (s.deltaEmitters.empty() ? 0u : 256u) | (s.materialTextures.empty() ? 0u : 512u) | (s.shapes.empty() ? 0u : 1024u)};
+                                 (s.deltaEmitters.empty() ? 0u : 256u) | (s.materialTextures.empty() ? 0u : 512u) | (s.shapes.empty() ? 0u : 1024u) |
+                                 (s.microfacet.empty() ? 0u : 2048u)};
     f.write("PPGS", 4); f.write((const char *)hdr, sizeof hdr);
     f.write((const char *)s.positions.data(), s.positions.size() * 4);
     if (!s.normals.empty()) f.write((const char *)s.normals.data(), s.normals.size() * 4);
@@ -250,6 +256,7 @@ static bool saveScene(const char *path, const SceneData &s) {
         f.write((const char *)&n, 4);
         f.write((const char *)s.shapes.data(), (std::streamsize)(n * sizeof(ppg_shape)));
     }
+    if (!s.microfacet.empty()) f.write((const char *)s.microfacet.data(), (std::streamsize)(s.microfacet.size() * sizeof(ppg_microfacet)));
     return (bool)f;
 }
 
@@ -349,6 +356,7 @@ int main(int argc, char **argv) {
         core.setDeltaEmitters(scene.deltaEmitters.data(), scene.deltaEmitters.size());
         core.setMaterialTextures(scene.materialTextures.data(), scene.materialTextures.size());
         core.setShapes(scene.shapes.data(), scene.shapes.size());
+        core.setMicrofacet(scene.microfacet.data(), scene.microfacet.size());
         core.setSeed((uint64_t)std::stoull(props.getString("seed", "0")));
         std::string dest = out;
         const size_t dot = dest.find_last_of('.');

@@ -1,7 +1,7 @@
 /* Rough-transmittance slices for the `roughplastic` BSDF (include/ppg.h: ppg_scene.rtrans) — the C++ twin of
  * ppg_host/rtrans.py.
  *
- * Mitsuba tabulates the transmittance through a rough dielectric boundary in data/microfacet/{beckmann,ggx}.dat and
+ * Mitsuba tabulates the transmittance through a rough dielectric boundary in data/microfacet/{beckmann,ggx,phong}.dat and
  * RoughPlastic::configure() (roughplastic.cpp:285-305) reduces the table to one curve over the warped incident cosine plus the
  * diffuse transmittance from the inside.  Restated here: the file layout (rtrans.h:81-146), setEta / setAlpha / evalDiffuse
  * (rtrans.h:233-400) and the cubic interpolation they use (spline.cpp:23-60, 236-452), all in float like the reference's

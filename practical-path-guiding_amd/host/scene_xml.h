@@ -20,6 +20,7 @@
 #include <cstring>
 #include <fstream>
 #include <functional>
+#include <limits>
 #include <map>
 #include <sstream>
 #include <stdexcept>
@@ -293,6 +294,7 @@ inline void parseColour(const std::string &tag, const std::string &value, float 
 struct Mesh {
     std::vector<V3> positions, normals;  // normals empty = none
     std::vector<uint32_t> indices;
+    std::vector<std::pair<float, float>> uvs;  // per-vertex texture coordinates, empty = none (kept for obj meshes only, as in ppg_host/mitsuba_xml.py)
 };
 
 inline float unitAngle(V3 u, V3 v) {  // util.h:309-314
@@ -330,7 +332,7 @@ inline void computeNormals(Mesh &m, bool flip) {  // TriMesh::computeNormals, sm
 /* TriMesh::rebuildTopology (trimesh.cpp:468-608): vertices re-merged on (position[, uv]); around each, the incident triangles are
  * clustered greedily by face normal (one new vertex per cluster of faces within maxAngle degrees of the cluster's first face), so that
  * the smooth normals computed afterwards stop at creases.  New vertices are numbered in the reference's order. */
-inline void rebuildTopology(Mesh &m, const std::vector<std::pair<float, float>> *uvs, float maxAngle) {
+inline void rebuildTopology(Mesh &m, std::vector<std::pair<float, float>> *uvs, float maxAngle) {
     const float dpThresh = std::cos(maxAngle * (float)(M_PI / 180.0));
     const size_t nt = m.indices.size() / 3;
     std::vector<V3> fn(nt);
@@ -349,6 +351,7 @@ inline void rebuildTopology(Mesh &m, const std::vector<std::pair<float, float>> 
             vertexToFace.insert({k, {(uint32_t)t, false}});
         }
     std::vector<V3> newPositions;
+    std::vector<std::pair<float, float>> newUVs;
     std::vector<uint32_t> newIndices(m.indices.size(), 0xFFFFFFFFu);
     for (auto it = vertexToFace.begin(); it != vertexToFace.end();) {
         auto end = vertexToFace.upper_bound(it->first);
@@ -358,6 +361,7 @@ inline void rebuildTopology(Mesh &m, const std::vector<std::pair<float, float>> 
             const V3 n1 = fn[it2->second.first];
             const uint32_t vertexIdx = (uint32_t)newPositions.size();
             newPositions.push_back(p);
+            if (uvs) newUVs.emplace_back(it->first.v[3], it->first.v[4]);
             for (auto it3 = it2; it3 != end; ++it3) {
                 if (it3->second.second) continue;
                 const V3 n2 = fn[it3->second.first];
@@ -375,6 +379,7 @@ inline void rebuildTopology(Mesh &m, const std::vector<std::pair<float, float>> 
     m.positions.swap(newPositions);
     m.indices.swap(newIndices);
     m.normals.clear();
+    if (uvs) uvs->swap(newUVs);
 }
 
 inline std::vector<Mesh> loadOBJ(const std::string &path, const Mat4 &toWorld, bool faceNormals, bool flipNormals, bool flipTexCoords, bool collapse,
@@ -430,6 +435,7 @@ inline std::vector<Mesh> loadOBJ(const std::string &path, const Mat4 &toWorld, b
         } else {
             computeNormals(m, flipNormals);
         }
+        if (hasUVs) m.uvs = vuv;
         meshes.push_back(std::move(m));
         tris.clear();
     };
@@ -756,12 +762,12 @@ public:
             out.scene.lens.aperture_radius = r; out.scene.lens.focus_distance = focus;
         }
         // bsdfs
-        for (auto &b : root.children) if (b.tag == "bsdf" && b.attr("id")) m_byId[b.get("id")] = intern(makeBsdf(b, true, out), out);
+        for (auto &b : root.children) if (b.tag == "bsdf" && b.attr("id")) { const ppg_material bm = makeBsdfTop(b, out); m_byId[b.get("id")] = intern(bm, out, m_mfd); }
         {   // an id may also sit on a NESTED bsdf (KITCHEN references the twosided element inside a bumpmap): every element with an id is a named object
             std::function<void(const XmlNode &)> walk = [&](const XmlNode &n) {
                 for (auto &c : n.children) {
                     if (c.tag != "bsdf") continue;
-                    if (c.attr("id") && !m_byId.count(c.get("id"))) m_byId[c.get("id")] = intern(makeBsdf(c, true, out), out);
+                    if (c.attr("id") && !m_byId.count(c.get("id"))) { const ppg_material bm = makeBsdfTop(c, out); m_byId[c.get("id")] = intern(bm, out, m_mfd); }
                     walk(c);
                 }
             };
@@ -944,7 +950,7 @@ public:
             }
             int mat = -1;
             for (auto &c : sh.children) {
-                if (c.tag == "bsdf") mat = (int)intern(makeBsdf(c, true, out), out);
+                if (c.tag == "bsdf") { const ppg_material bm = makeBsdfTop(c, out); mat = (int)intern(bm, out, m_mfd); }
                 else if (c.tag == "ref") {
                     auto it = m_byId.find(c.get("id"));
                     if (it == m_byId.end()) throw std::runtime_error("<ref id=\"" + c.get("id") + "\">: no such bsdf");
@@ -969,6 +975,12 @@ public:
                 colour(*e, "radiance", 1.0f, pe.radiance);
                 out.scene.emitters.push_back(pe);
             }
+            // an anisotropic BSDF needs the UV tangents (trimesh.cpp:380, 686-691).  Both loaders keep the texture coordinates of obj files only.
+            for (auto &mm : meshes)
+                if (anisotropic((uint32_t)mat, out) && mm.uvs.empty())
+                    throw std::runtime_error("\"" + t + "\": computeUVTangents(): texture coordinates are required to generate tangent vectors. If you want to render with an "
+                                             "anisotropic material, please make sure that all associated shapes have valid texture coordinates. (This loader keeps "
+                                             "those of obj files only; its rectangle and cube carry none.)");
             for (auto &mm : meshes) parts.push_back(Part{std::move(mm), (uint32_t)mat, em});
             if (isSphere) { sphere.material = (uint32_t)mat; sphere.emitter = em; out.scene.spheres.push_back(sphere); }
             if (isAnalytic) {
@@ -982,10 +994,15 @@ public:
         bool anyNormals = false;
         for (auto &p : parts) anyNormals |= !p.mesh.normals.empty();
         SceneData &S = out.scene;
+        // texture coordinates only matter on meshes whose BSDF is anisotropic; the others get NaN rows (= none)
+        bool anyUVs = false;
+        for (auto &p : parts) anyUVs |= !p.mesh.uvs.empty() && anisotropic(p.mat, out);
         for (auto &p : parts) {
             Mesh &m = p.mesh;
+            if (!anisotropic(p.mat, out)) m.uvs.clear();
             if (anyNormals && m.normals.empty()) {  // un-share the vertices, write the face normals out
                 Mesh u;
+                if (!m.uvs.empty()) for (uint32_t id : m.indices) u.uvs.push_back(m.uvs[id]);
                 for (size_t t = 0; t + 2 < m.indices.size(); t += 3) {
                     V3 a = m.positions[m.indices[t]], b = m.positions[m.indices[t + 1]], c = m.positions[m.indices[t + 2]];
                     V3 n = cross(b - a, c - a);
@@ -999,10 +1016,16 @@ public:
             for (size_t i = 0; i < m.positions.size(); ++i) {
                 S.positions.insert(S.positions.end(), {m.positions[i].x, m.positions[i].y, m.positions[i].z});
                 if (anyNormals) S.normals.insert(S.normals.end(), {m.normals[i].x, m.normals[i].y, m.normals[i].z});
+                if (anyUVs) {
+                    const float nan = std::numeric_limits<float>::quiet_NaN();
+                    if (m.uvs.empty()) S.texcoords.insert(S.texcoords.end(), {nan, nan});
+                    else S.texcoords.insert(S.texcoords.end(), {m.uvs[i].first, m.uvs[i].second});
+                }
             }
             for (uint32_t id : m.indices) S.indices.push_back(base + id);
             for (size_t t = 0; t < m.indices.size() / 3; ++t) { S.triMaterial.push_back(p.mat); S.triEmitter.push_back(p.em); }
         }
+        for (const ppg_microfacet &g : m_mfdOf) if (g.general) { S.microfacet = m_mfdOf; break; }  // one entry per material, or none
         out.warnings.insert(out.warnings.end(), m_lenientNotes.begin(), m_lenientNotes.end());
         return out;
     }
@@ -1017,6 +1040,8 @@ private:
     mutable std::vector<std::string> m_lenientNotes;  // warnings raised inside const helpers  // (distribution, alpha, eta) → slice of out.scene.rtrans
     std::map<std::string, uint32_t> m_byId;
     std::vector<std::string> m_matKeys;
+    std::vector<ppg_microfacet> m_mfdOf;  // per material: its general microfacet entry (all zero: none)
+    mutable ppg_microfacet m_mfd{};       // ... of the BSDF makeBsdf built last
 
     void collectDefaults(const XmlNode &n) {
         if (n.tag == "default" && n.attr("name") && !m_params.count(n.get("name"))) m_params[n.get("name")] = n.get("value");
@@ -1428,17 +1453,38 @@ private:
         const bool cond = m.type == PPG_BSDF_MIRROR || m.type == PPG_BSDF_CONDUCTOR || m.type == PPG_BSDF_ROUGHCONDUCTOR;
         for (int k = 0; k < 3; ++k) m.eta[k] = cond ? 0.0f : 1.5046f;
     }
-    // MicrofacetDistribution(props), microfacet.h:99-145: distribution name (flag set on m), isotropic alpha
-    std::string microfacet(std::map<std::string, std::string> &p, const std::string &t, ppg_material &m) const {
+    // MicrofacetDistribution(props), microfacet.h:99-145: the distribution's name (the name of its table, data/microfacet/<name>.dat; flag
+    // set on m), alpha = alphaU, and in m_mfd the general entry of a BSDF that states alphaU / alphaV, phong or sampleVisible = false
+    // (ppg_microfacet; the same rule as ppg_host.bindings.Microfacet).  Bitmaps on the roughness are not read by this loader.
+    std::string microfacet(const XmlNode &e, std::map<std::string, std::string> &p, const std::string &t, ppg_material &m) const {
         std::string distr = p.count("distribution") ? p["distribution"] : "beckmann";
         std::transform(distr.begin(), distr.end(), distr.begin(), ::tolower);
-        if (distr != "ggx" && distr != "beckmann") throw std::runtime_error(t + ": distribution '" + distr + "' is not supported (ggx, beckmann)");
+        if (distr != "ggx" && distr != "beckmann" && distr != "phong" && distr != "as")
+            throw std::runtime_error(t + ": Specified an invalid distribution \"" + distr + "\", must be \"beckmann\", \"ggx\", or \"phong\"/\"as\"!");
+        if ((distr == "phong" || distr == "as") && t != "roughplastic")  // as ppg_host/mitsuba_xml.py: phong from a scene file on roughplastic only
+            throw std::runtime_error(t + ": distribution '" + distr + "' is not supported by the scene loaders on this plug-in (ggx, beckmann; phong on roughplastic)");
+        if (distr == "as") distr = "phong";
+        for (auto &c : e.children)
+            if ((c.tag == "texture" || c.tag == "ref") && c.attr("name") && (c.get("name") == "alpha" || c.get("name") == "alphaU" || c.get("name") == "alphaV"))
+                throw std::runtime_error(t + ": a texture on '" + c.get("name") + "' is not supported by this loader");
         if (distr == "beckmann") m.flags |= PPG_MAT_BECKMANN;  // Mitsuba's default (microfacet.h:99)
-        if (p.count("alphaU") || p.count("alphaV")) {
-            if (!p.count("alphaU") || !p.count("alphaV") || std::stof(p["alphaU"]) != std::stof(p["alphaV"])) throw std::runtime_error(t + ": anisotropic roughness is not supported");
+        m_mfd = ppg_microfacet{};
+        if (p.count("alpha")) {
+            if (p.count("alphaU") || p.count("alphaV")) throw std::runtime_error(t + ": Microfacet model: please specify either 'alpha' or 'alphaU'/'alphaV'.");
+            m.alpha = std::stof(p["alpha"]);
+        } else if (p.count("alphaU") || p.count("alphaV")) {
+            if (!p.count("alphaU") || !p.count("alphaV")) throw std::runtime_error(t + ": Microfacet model: both 'alphaU' and 'alphaV' must be specified.");
             m.alpha = std::stof(p["alphaU"]);
-        } else m.alpha = p.count("alpha") ? std::stof(p["alpha"]) : 0.1f;
-        if (p.count("sampleVisible") && !flag(p, "sampleVisible", true)) throw std::runtime_error(t + ": sampleVisible=false is not supported");
+            m_mfd.general = 1;
+            m_mfd.alpha_v = std::stof(p["alphaV"]);
+        } else m.alpha = 0.1f;
+        const bool sampleAll = p.count("sampleVisible") && !flag(p, "sampleVisible", true);
+        if (distr == "phong" || sampleAll) {
+            if (!m_mfd.general) m_mfd.alpha_v = m.alpha;
+            m_mfd.general = 1;
+            m_mfd.distribution = distr == "phong" ? 1 : 0;
+            m_mfd.sample_all = sampleAll ? 1 : 0;
+        }
         return distr;
     }
     double lookupIOR(const std::map<std::string, std::string> &p, const std::string &name, const std::string &dflt) const {  // ior.h:95-111
@@ -1473,6 +1519,8 @@ private:
         }
         for (int c = 0; c < 3; ++c) { m.eta[c] = eta[c] / ext; m.k[c] = k[c] / ext; }
     }
+    // (the general microfacet entry of the BSDF it built last — at most one rough plug-in sits inside the adapters — is left in m_mfd)
+    ppg_material makeBsdfTop(const XmlNode &e, LoadedScene &out) const { m_mfd = ppg_microfacet{}; return makeBsdf(e, true, out); }
     ppg_material makeBsdf(const XmlNode &e, bool allowWrap, LoadedScene &out) const {
         std::string t = e.get("type");
         auto p = props(e);
@@ -1520,7 +1568,7 @@ private:
                 if (intIOR < 0 || extIOR < 0 || intIOR == extIOR) throw std::runtime_error(t + ": the interior and exterior indices of refraction must be positive and differ");
                 m.eta[0] = m.eta[1] = m.eta[2] = (float)(intIOR / extIOR);
             }
-            microfacet(p, t, m);
+            microfacet(e, p, t, m);
             return m;
         } else if (t == "roughplastic") {  // roughplastic.cpp:197-227, 285-305
             m.type = PPG_BSDF_ROUGHPLASTIC; defaults(m);
@@ -1529,7 +1577,9 @@ private:
             if (intIOR < 0 || extIOR < 0 || intIOR == extIOR) throw std::runtime_error(t + ": the interior and exterior indices of refraction must be positive and differ");
             m.eta[0] = m.eta[1] = m.eta[2] = (float)(intIOR / extIOR);
             if (flag(p, "nonlinear", false)) m.flags |= PPG_MAT_NONLINEAR;
-            const std::string distr = microfacet(p, t, m);
+            const std::string distr = microfacet(e, p, t, m);
+            if (m_mfd.general && std::max(m_mfd.alpha_v, 1e-4f) != std::max(m.alpha, 1e-4f))  // roughplastic.cpp:221-223
+                throw std::runtime_error(t + ": The 'roughplastic' plugin currently does not support anisotropic microfacet distributions!");
             char key[96];
             snprintf(key, sizeof key, "%s/%.9g/%.9g", distr.c_str(), m.alpha, m.eta[0]);
             auto it = m_rtIndex.find(key);
@@ -1570,7 +1620,7 @@ public:
     // The <bsdf> element carrying `id` (at any nesting depth: every element with an id is a named object in Mitsuba) as a ppg_material;
     // rough-transmittance slices it needs are appended to out.scene.rtrans.  Used by the Mitsuba plug-in shim
     // (mitsuba_plugin/guided_path_hip.cpp), which cannot reach the nested BSDF of an adapter through Mitsuba's API.
-    bool bsdfById(const std::string &id, LoadedScene &out, ppg_material &m) {
+    bool bsdfById(const std::string &id, LoadedScene &out, ppg_material &m, ppg_microfacet *g = nullptr) {
         std::ifstream f(m_path, std::ios::binary);
         if (!f) throw std::runtime_error("cannot open '" + m_path + "'");
         std::stringstream ss; ss << f.rdbuf();
@@ -1588,21 +1638,32 @@ public:
         };
         walk(root);
         if (!found) return false;
-        m = makeBsdf(*found, true, out);
+        m = makeBsdfTop(*found, out);
+        if (g) *g = m_mfd;
+        else if (m_mfd.general) throw std::runtime_error("bsdf '" + id + "': alphaU / alphaV, distribution = phong and sampleVisible = false are not carried through this interface");
         return true;
     }
     // The ppg_material of a <bsdf> element that is not in a file: the plug-in shim builds one from a flat plug-in's Properties (a BSDF
     // without an id cannot be looked up in the scene file) and gets exactly what the scene loader makes of the same parameters.
-    ppg_material bsdfFromElement(const XmlNode &e, LoadedScene &out) {
+    ppg_material bsdfFromElement(const XmlNode &e, LoadedScene &out, ppg_microfacet *g = nullptr) {
         m_base = ".";
-        return makeBsdf(e, true, out);
+        const ppg_material m = makeBsdfTop(e, out);
+        if (g) *g = m_mfd;
+        else if (m_mfd.general) throw std::runtime_error("alphaU / alphaV, distribution = phong and sampleVisible = false are not carried through this interface");
+        return m;
     }
 private:
-    uint32_t intern(const ppg_material &m, LoadedScene &out) {
+    // EAnisotropic of the material's BSDF: alphaU != alphaV (this loader reads no bitmaps on them)
+    bool anisotropic(uint32_t mat, const LoadedScene &out) const {
+        return m_mfdOf[mat].general && std::max(m_mfdOf[mat].alpha_v, 1e-4f) != std::max(out.scene.materials[mat].alpha, 1e-4f);
+    }
+    uint32_t intern(const ppg_material &m, LoadedScene &out, const ppg_microfacet &g = ppg_microfacet{}) {
         std::string key((const char *)&m, sizeof m);
+        key.append((const char *)&g, sizeof g);
         for (size_t i = 0; i < m_matKeys.size(); ++i) if (m_matKeys[i] == key) return (uint32_t)i;
         m_matKeys.push_back(key);
         out.scene.materials.push_back(m);
+        m_mfdOf.push_back(g);
         return (uint32_t)m_matKeys.size() - 1;
     }
 };
@@ -1612,13 +1673,16 @@ namespace xml {
 // (name, tag, value) triples of a flat BSDF plug-in's parameters → its ppg_material, through the scene loader's own <bsdf> handling:
 // tag = float | integer | boolean | string | rgb, value as it would stand in the scene file ("0.1, 0.2, 0.3" for rgb)
 struct BsdfParam { std::string name, tag, value; };
-inline bool bsdfFromProperties(const std::string &plugin, const std::vector<BsdfParam> &params, const std::string &dataDir, SceneData &data, ppg_material &m, std::string &why);
+// g: receives the BSDF's general microfacet entry (ppg_set_microfacet; all zero: none); without it such a BSDF is refused
+inline bool bsdfFromProperties(const std::string &plugin, const std::vector<BsdfParam> &params, const std::string &dataDir, SceneData &data, ppg_material &m, std::string &why,
+                               ppg_microfacet *g = nullptr);
 
-inline bool bsdfById(const std::string &scenePath, const std::string &id, const std::string &dataDir, SceneData &data, ppg_material &m, std::string &why) {
+inline bool bsdfById(const std::string &scenePath, const std::string &id, const std::string &dataDir, SceneData &data, ppg_material &m, std::string &why,
+                     ppg_microfacet *g = nullptr) {
     try {
         SceneXmlLoader loader(scenePath, {}, true, 0, 0, dataDir);
         LoadedScene tmp;
-        if (!loader.bsdfById(id, tmp, m)) return false;
+        if (!loader.bsdfById(id, tmp, m, g)) return false;
         if (!tmp.scene.rtrans.empty()) {
             if (data.rtransSamples && data.rtransSamples != tmp.scene.rtransSamples) { why = "rough-transmittance tables of different resolutions"; return false; }
             const uint32_t have = data.rtransSamples ? (uint32_t)(data.rtrans.size() / (data.rtransSamples + 1)) : 0u;
@@ -1633,7 +1697,8 @@ inline bool bsdfById(const std::string &scenePath, const std::string &id, const 
     }
 }
 
-inline bool bsdfFromProperties(const std::string &plugin, const std::vector<BsdfParam> &params, const std::string &dataDir, SceneData &data, ppg_material &m, std::string &why) {
+inline bool bsdfFromProperties(const std::string &plugin, const std::vector<BsdfParam> &params, const std::string &dataDir, SceneData &data, ppg_material &m, std::string &why,
+                               ppg_microfacet *g) {
     try {
         SceneXmlLoader loader("", {}, true, 0, 0, dataDir);
         LoadedScene tmp;
@@ -1644,7 +1709,7 @@ inline bool bsdfFromProperties(const std::string &plugin, const std::vector<Bsdf
             c.tag = p.tag; c.attrs.push_back({"name", p.name}); c.attrs.push_back({"value", p.value});
             e.children.push_back(c);
         }
-        m = loader.bsdfFromElement(e, tmp);
+        m = loader.bsdfFromElement(e, tmp, g);
         if (!tmp.scene.rtrans.empty()) {
             if (data.rtransSamples && data.rtransSamples != tmp.scene.rtransSamples) { why = "rough-transmittance tables of different resolutions"; return false; }
             const uint32_t have = data.rtransSamples ? (uint32_t)(data.rtrans.size() / (data.rtransSamples + 1)) : 0u;

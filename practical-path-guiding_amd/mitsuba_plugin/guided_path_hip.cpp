@@ -79,6 +79,13 @@ public:
         m_core.setLens(data.hasLens ? &data.lens : nullptr);
         m_core.setDeltaEmitters(data.deltaEmitters.data(), data.deltaEmitters.size());
         m_core.setShapes(data.shapes.data(), data.shapes.size());
+        {   /* the general microfacet entries materialOf() collected: one per material, or none */
+            bool any = false;
+            for (size_t k = 0; k < data.microfacet.size(); ++k) any = any || data.microfacet[k].general != 0;
+            if (any) data.microfacet.resize(data.materials.size());
+            else data.microfacet.clear();
+            m_core.setMicrofacet(data.microfacet.data(), data.microfacet.size());
+        }
         Log(EInfo, "Starting render job (%ix%i, MI355X, %i triangles, %i analytic spheres) ..", film->getCropSize().x, film->getCropSize().y,
             (int) (data.indices.size() / 3), (int) data.spheres.size());
         /* create → scene → render; SD-tree dumps to "<dest>-NN.sdt" (GP:1192-1195) */
@@ -119,6 +126,7 @@ private:
         std::map<const BSDF *, int>::const_iterator it = cache.find(bsdf);
         if (it != cache.end()) return it->second;
         ppg_material m; memset(&m, 0, sizeof m);
+        ppg_microfacet g; memset(&g, 0, sizeof g);   /* alphaU / alphaV, phong, sampleVisible = false (ppg_set_microfacet) */
         const Properties &p = bsdf->getProperties();
         const std::string plugin = p.getPluginName();
         bool ok = false;
@@ -126,7 +134,7 @@ private:
             /* the nested BSDF is not reachable through Mitsuba's API: read the element with this id from the scene file.  ppg::xml::SceneLoader
                is the loader behind `ppg_render scene.xml`; bsdfById() returns the ppg_material it makes of that <bsdf> element (incl. the
                rough-transmittance slice of a roughplastic, appended to data.rtrans, and its textures, appended to data.textures) */
-            ok = ppg::xml::bsdfById(scene->getSourceFile().string(), p.getID(), m_dataDir(), data, m, why);
+            ok = ppg::xml::bsdfById(scene->getSourceFile().string(), p.getID(), m_dataDir(), data, m, why, &g);
         }
         if (!ok) {
             /* A flat plug-in without an id: its Properties are the parameters the scene file gave it.  They are handed to the scene loader's own
@@ -156,7 +164,7 @@ private:
                 params.push_back(q);
             }
             std::string why2;
-            ok = ppg::xml::bsdfFromProperties(plugin, params, m_dataDir(), data, m, why2);
+            ok = ppg::xml::bsdfFromProperties(plugin, params, m_dataDir(), data, m, why2, &g);
             if (!ok && why.empty()) why = why2;
         }
         if (!ok) {
@@ -164,6 +172,8 @@ private:
             return -1;
         }
         data.materials.push_back(m);
+        data.microfacet.resize(data.materials.size());   /* (zero entries for the materials before it) */
+        data.microfacet.back() = g;
         cache[bsdf] = (int) data.materials.size() - 1;
         return cache[bsdf];
     }

@@ -62,7 +62,8 @@ class Config(C.Structure):
 
 class Material(C.Structure):
     """ppg_material (include/ppg.h).  Scene descriptions carry materials as dicts: type, reflectance and — by type —
-    specular, alpha, eta (3 values, or one number for plastic / dielectric), k, twosided, nonlinear, opacity (a mask adapter), distribution ("ggx" | "beckmann"), rtrans (roughplastic: row of SceneDesc.rtrans)."""
+    specular, alpha, eta (3 values, or one number for plastic / dielectric), k, twosided, nonlinear, opacity (a mask adapter), distribution ("ggx" | "beckmann"), rtrans (roughplastic: row of SceneDesc.rtrans).
+    The rest of the microfacet model travels beside it (Microfacet): alpha_v, distribution = "phong", sample_visible."""
     _fields_ = [("type", C.c_int32), ("reflectance", C.c_float * 3), ("specular", C.c_float * 3), ("alpha", C.c_float),
                 ("eta", C.c_float * 3), ("k", C.c_float * 3), ("flags", C.c_int32), ("rtrans", C.c_int32),
                 ("opacity", C.c_float * 3), ("texture", C.c_uint32)]
@@ -105,6 +106,36 @@ class MaterialTextures(C.Structure):
         o = cls()
         o.specular, o.alpha, o.opacity = (0 if m.get(k) is None else int(m[k]) + 1 for k in cls.KEYS)
         return o
+
+
+class Microfacet(C.Structure):
+    """ppg_microfacet (include/ppg.h): per material, the part of Mitsuba's MicrofacetDistribution that ppg_material does not carry.  Material
+    dicts state it as alpha_v (alphaV; `alpha` is then alphaU), alpha_v_texture (index into SceneDesc.textures), distribution = "phong" (or
+    "as") and sample_visible = False.  A dict with any of these gets general = 1, also when alpha_v == alpha; every other an all-zero entry."""
+    _fields_ = [("alpha_v", C.c_float), ("distribution", C.c_int32), ("sample_all", C.c_int32), ("alpha_v_texture", C.c_uint32),
+                ("general", C.c_uint32), ("_reserved", C.c_uint32 * 3)]
+
+    @staticmethod
+    def is_general(m):
+        return (m.get("alpha_v") is not None or m.get("alpha_v_texture") is not None or m.get("distribution") in ("phong", "as")
+                or m.get("sample_visible", True) is False)
+
+    @classmethod
+    def from_dict(cls, m):
+        o = cls()
+        if not cls.is_general(m):
+            return o
+        o.general = 1
+        o.alpha_v = float(m.get("alpha_v", m.get("alpha", 0.1)))
+        o.distribution = 1 if m.get("distribution") in ("phong", "as") else 0
+        o.sample_all = 0 if m.get("sample_visible", True) else 1
+        o.alpha_v_texture = 0 if m.get("alpha_v_texture") is None else int(m["alpha_v_texture"]) + 1
+        return o
+
+
+def has_general_microfacet(desc):
+    """Whether a material of `desc` needs an entry of ppg_set_microfacet (what the CPU oracle does not implement)."""
+    return any(Microfacet.is_general(m) for m in desc.materials)
 
 
 def has_parameter_textures(desc):
@@ -163,6 +194,17 @@ class DebugHit(C.Structure):
                 ("wi", C.c_float * 3), ("material", C.c_int32), ("emitter", C.c_int32), ("_pad", C.c_int32)]
 
 
+class DebugBsdfItem(C.Structure):
+    """ppg_debug_bsdf_item (include/ppg_testhooks.h)"""
+    _fields_ = [("material", C.c_int32), ("wi", C.c_float * 3), ("wo", C.c_float * 3), ("sample", C.c_float * 2), ("key", C.c_uint32), ("uv", C.c_float * 2)]
+
+
+class DebugBsdfOut(C.Structure):
+    """ppg_debug_bsdf_out (include/ppg_testhooks.h)"""
+    _fields_ = [("eval", C.c_float * 3), ("pdf", C.c_float), ("wo", C.c_float * 3), ("sampled_pdf", C.c_float), ("weight", C.c_float * 3),
+                ("eta", C.c_float), ("delta", C.c_int32), ("is_null", C.c_int32), ("_pad", C.c_int32 * 2)]
+
+
 class DebugDirect(C.Structure):
     """ppg_debug_direct (include/ppg_testhooks.h)"""
     _fields_ = [("emitter", C.c_int32), ("d", C.c_float * 3), ("dist", C.c_float), ("n", C.c_float * 3), ("pdf", C.c_float), ("em_pdf", C.c_float),
@@ -171,6 +213,9 @@ class DebugDirect(C.Structure):
 
 DEBUG_HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("p", "<f4", 3), ("geo_n", "<f4", 3), ("n", "<f4", 3), ("s", "<f4", 3), ("wi", "<f4", 3),
                             ("material", "<i4"), ("emitter", "<i4"), ("_pad", "<i4")])
+DEBUG_BSDF_ITEM_DTYPE = np.dtype([("material", "<i4"), ("wi", "<f4", 3), ("wo", "<f4", 3), ("sample", "<f4", 2), ("key", "<u4"), ("uv", "<f4", 2)])
+DEBUG_BSDF_OUT_DTYPE = np.dtype([("eval", "<f4", 3), ("pdf", "<f4"), ("wo", "<f4", 3), ("sampled_pdf", "<f4"), ("weight", "<f4", 3), ("eta", "<f4"),
+                                 ("delta", "<i4"), ("is_null", "<i4"), ("_pad", "<i4", 2)])
 DEBUG_DIRECT_DTYPE = np.dtype([("emitter", "<i4"), ("d", "<f4", 3), ("dist", "<f4"), ("n", "<f4", 3), ("pdf", "<f4"), ("em_pdf", "<f4"),
                                ("value", "<f4", 3), ("_pad", "<f4", 3)])
 
@@ -504,6 +549,11 @@ class Engine:
         elif has_parameter_textures(desc):
             raise NotImplementedError("%s: bitmaps on specular / alpha / opacity (specular_texture, alpha_texture, opacity_texture) are not implemented here"
                                       % self.prefix)
+        # the general microfacet entries, likewise: one per material, or the empty list that clears the context's
+        if self.prefix == "ppg_":
+            self.set_microfacet(desc.materials if has_general_microfacet(desc) else [])
+        elif has_general_microfacet(desc):
+            raise NotImplementedError("%s: alpha_v, distribution = phong and sample_visible = False are not implemented here" % self.prefix)
         self._call("set_scene", C.byref(s))
         self.width, self.height = cam["width"], cam["height"]
         # the film's reconstruction filter comes with the scene description (None / absent: the default box)
@@ -568,6 +618,33 @@ class Engine:
         for i, d in enumerate(slots):
             arr[i] = d if isinstance(d, MaterialTextures) else MaterialTextures.from_dict(d)
         self._call("set_material_textures", arr, C.c_uint32(len(slots)))
+
+    def set_microfacet(self, entries):
+        """ppg_set_microfacet: one entry per material — a material dict (its alpha_v / alpha_v_texture / distribution / sample_visible keys) or
+        a Microfacet; an empty list clears it.  Takes effect at, and is validated by, the next set_scene."""
+        entries = list(entries or [])
+        arr = (Microfacet * max(1, len(entries)))()
+        for i, d in enumerate(entries):
+            arr[i] = d if isinstance(d, Microfacet) else Microfacet.from_dict(d)
+        self._call("set_microfacet", arr, C.c_uint32(len(entries)))
+
+    def debug_bsdf(self, material, wi, wo, sample, key=None, uv=None):
+        """ppg_debug_bsdf (include/ppg_testhooks.h): the render's mat_eval / mat_pdf / mat_sample on material(s) `material` of the scene, per
+        item local wi, wo [n, 3], the 2-D sample [n, 2], the sampler key of roughdielectric's extra draw and the hit's uv; a structured
+        array (DEBUG_BSDF_OUT_DTYPE)."""
+        wo = np.ascontiguousarray(wo, np.float32).reshape(-1, 3)
+        n = wo.shape[0]
+        items = np.zeros(n, DEBUG_BSDF_ITEM_DTYPE)
+        items["material"] = material
+        items["wi"] = np.broadcast_to(np.asarray(wi, np.float32), (n, 3))
+        items["wo"] = wo
+        items["sample"] = np.broadcast_to(np.asarray(sample, np.float32), (n, 2))
+        items["key"] = 0 if key is None else key
+        items["uv"] = 0.0 if uv is None else np.broadcast_to(np.asarray(uv, np.float32), (n, 2))
+        out = np.zeros(n, DEBUG_BSDF_OUT_DTYPE)
+        assert items.itemsize == C.sizeof(DebugBsdfItem) and out.itemsize == C.sizeof(DebugBsdfOut)
+        self._call("debug_bsdf", C.c_uint32(n), items.ctypes.data_as(C.POINTER(DebugBsdfItem)), out.ctypes.data_as(C.POINTER(DebugBsdfOut)))
+        return out
 
     def set_lens(self, lens):
         """ppg_set_lens: lens = {"aperture_radius", "focus_distance"} (Lens) or None for the pinhole"""

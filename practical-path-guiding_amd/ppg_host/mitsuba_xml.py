@@ -45,7 +45,7 @@ GUIDED_PATH_PROPS = {  # name → type (GP:1014-1085, integrator.cpp:192-218)
 }
 
 
-TEXTURE_KEYS = ("texture", "bump", "specular_texture", "alpha_texture", "opacity_texture")  # material keys that hold a texture index
+TEXTURE_KEYS = ("texture", "bump", "specular_texture", "alpha_texture", "opacity_texture", "alpha_v_texture")  # material keys that hold a texture index
 
 
 class SceneError(ValueError):
@@ -1016,16 +1016,49 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             raise SceneError("IOR name %r is not in the built-in list %s; give a number" % (v, sorted(IOR)))
         return IOR[str(v).lower()]
 
-    def microfacet_alpha(p, what):  # MicrofacetDistribution(props), microfacet.h:99-145
-        if str(p.get("distribution", "beckmann")).lower() not in ("ggx", "beckmann"):
-            raise SceneError("%s: distribution %r is not supported (ggx, beckmann)" % (what, p.get("distribution", "beckmann")))
-        if "alphaU" in p or "alphaV" in p:
-            if p.get("alphaU") != p.get("alphaV"):
-                raise SceneError("%s: anisotropic roughness is not supported" % what)
-            return float(p["alphaU"])
+    def microfacet(elem, p, m, what):
+        """MicrofacetDistribution(props) (microfacet.h:99-145) plus the plug-ins' texture children on alpha / alphaU / alphaV: fills the
+        material's alpha (alphaU) and, where the BSDF states alphaU / alphaV, phong or sampleVisible = false, the keys of the general entry
+        (alpha_v, alpha_v_texture, distribution = "phong", sample_visible = False; bindings.Microfacet)."""
+        distr = str(p.get("distribution", "beckmann")).lower()
+        if distr not in ("beckmann", "ggx", "phong", "as"):
+            raise SceneError('%s: Specified an invalid distribution "%s", must be "beckmann", "ggx", or "phong"/"as"!' % (what, distr))
+        if distr in ("phong", "as") and what != "roughplastic":
+            # the XML loaders read the Phong / Ashikhmin-Shirley distribution on roughplastic only: tests/test_mitsuba_xml.py pins its refusal
+            # on roughconductor.  The other two plug-ins get it through material dicts, flat scene files and the C-ABI.
+            raise SceneError("%s: distribution %r is not supported by the scene loaders on this plug-in (ggx, beckmann; phong on roughplastic)" % (what, distr))
+        tex = {c.get("name") for c in elem if c.tag in ("texture", "ref")} & {"alpha", "alphaU", "alphaV"}
+        has = lambda n: n in p or n in tex  # noqa: E731
+
+        def value(name):  # a number, or a bitmap read as eval(its).average(): the constant is then the texture's average
+            if name not in tex:
+                return float(p[name]), None
+            c, ti = colour_or_texture(elem, name, 0.1, wrap=True)
+            return float((f32(c[0]) + f32(c[1]) + f32(c[2])) / f32(3.0)), ti  # Spectrum::average (spectrum.h:481-486)
+        if has("alpha"):
+            if has("alphaU") or has("alphaV"):
+                raise SceneError("%s: Microfacet model: please specify either 'alpha' or 'alphaU'/'alphaV'." % what)
+            m["alpha"], ti = value("alpha")
+            if ti is not None:
+                m["alpha_texture"] = ti
+        elif has("alphaU") or has("alphaV"):
+            if not has("alphaU") or not has("alphaV"):
+                raise SceneError("%s: Microfacet model: both 'alphaU' and 'alphaV' must be specified." % what)
+            m["alpha"], tu = value("alphaU")
+            m["alpha_v"], tv = value("alphaV")
+            if tu is not None:
+                m["alpha_texture"] = tu
+            if tv is not None:
+                m["alpha_v_texture"] = tv
+        else:
+            m["alpha"] = 0.1
+        if distr in ("phong", "as"):
+            m["distribution"] = "phong"
+        elif distr == "beckmann":  # Mitsuba's default (microfacet.h:99)
+            m["distribution"] = "beckmann"
         if not p.get("sampleVisible", True):
-            raise SceneError("%s: sampleVisible=false is not supported" % what)
-        return float(p.get("alpha", 0.1))
+            m["sample_visible"] = False
+        return m
 
     def conductor_ior(elem, p, what):  # conductor.cpp:160-186 / roughconductor.cpp:174-186
         ext = lookup_ior(p, "extEta", "air")
@@ -1060,19 +1093,6 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             return m
         def specular(m, name):  # the `specular` field: plastic specularReflectance, dielectric specularTransmittance
             return textured(m, name, 1.0, "specular", "specular_texture")
-        def rough(m, what):  # roughness `alpha` of roughconductor / roughdielectric: a number, or a bitmap read as eval(its).average()
-            for c in elem:
-                if c.get("name") in ("alphaU", "alphaV") and c.tag in ("texture", "ref"):
-                    raise SceneError("%s: a texture on %r is not supported (anisotropic roughness)" % (what, c.get("name")))
-            if any(c.get("name") == "alpha" and c.tag in ("texture", "ref") for c in elem):
-                microfacet_alpha(dict(p, alpha=0.1), what)
-                c, ti = colour_or_texture(elem, "alpha", 0.1, wrap=True)
-                m["alpha"] = float((f32(c[0]) + f32(c[1]) + f32(c[2])) / f32(3.0))  # Spectrum::average (spectrum.h:481-486) of the texture's average
-                if ti is not None:
-                    m["alpha_texture"] = ti
-            else:
-                m["alpha"] = microfacet_alpha(p, what)
-            return m
         if t == "diffuse":
             return textured(dict(type=0), "reflectance", 0.5)
         if t == "twosided" and allow_twosided:
@@ -1102,10 +1122,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             return textured(dict(type=3, eta=eta, k=k), "specularReflectance", 1.0)
         elif t == "roughconductor":
             eta, k = conductor_ior(elem, p, t)
-            m = rough(textured(dict(type=4, eta=eta, k=k), "specularReflectance", 1.0), t)
-            if str(p.get("distribution", "beckmann")).lower() == "beckmann":  # Mitsuba's default (microfacet.h:99)
-                m["distribution"] = "beckmann"
-            return m
+            return microfacet(elem, p, textured(dict(type=4, eta=eta, k=k), "specularReflectance", 1.0), t)
         elif t == "plastic":
             eta = lookup_ior(p, "intIOR", "polypropylene") / lookup_ior(p, "extIOR", "air")
             return textured(specular(dict(type=5, eta=float(f32(eta)), nonlinear=bool(p.get("nonlinear", False))), "specularReflectance"),
@@ -1124,8 +1141,11 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             int_ior, ext_ior = lookup_ior(p, "intIOR", "polypropylene"), lookup_ior(p, "extIOR", "air")
             if int_ior < 0 or ext_ior < 0 or int_ior == ext_ior:
                 raise SceneError("roughplastic: the interior and exterior indices of refraction must be positive and differ")
-            alpha, eta = microfacet_alpha(p, t), float(f32(int_ior / ext_ior))
-            distr = str(p.get("distribution", "beckmann")).lower()
+            mf = microfacet(elem, p, {}, t)
+            if mf.get("alpha_v", mf["alpha"]) != mf["alpha"]:  # roughplastic.cpp:221-223
+                raise SceneError("roughplastic: The 'roughplastic' plugin currently does not support anisotropic microfacet distributions!")
+            alpha, eta = mf["alpha"], float(f32(int_ior / ext_ior))
+            distr = mf.get("distribution", "ggx")  # the name of its table, data/microfacet/<name>.dat
             key = (distr, float(f32(alpha)), eta)
             if key not in rt_index:
                 try:
@@ -1133,19 +1153,13 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 except _rt.RoughTransmittanceError as e:
                     raise SceneError("roughplastic: %s" % e)
                 rt_index[key] = len(rt_slices) - 1
-            m = textured(specular(dict(type=9, eta=eta, alpha=alpha, nonlinear=bool(p.get("nonlinear", False)), rtrans=rt_index[key]), "specularReflectance"),
-                         "diffuseReflectance", 0.5)
-            if distr == "beckmann":
-                m["distribution"] = "beckmann"
-            return m
+            return textured(specular(dict(mf, type=9, eta=eta, nonlinear=bool(p.get("nonlinear", False)), rtrans=rt_index[key]), "specularReflectance"),
+                            "diffuseReflectance", 0.5)
         elif t == "roughdielectric":  # roughdielectric.cpp:183-211
             int_ior, ext_ior = lookup_ior(p, "intIOR", "bk7"), lookup_ior(p, "extIOR", "air")
             if int_ior < 0 or ext_ior < 0 or int_ior == ext_ior:
                 raise SceneError("roughdielectric: the interior and exterior indices of refraction must be positive and differ")
-            m = rough(specular(textured(dict(type=8, eta=float(f32(int_ior / ext_ior))), "specularReflectance", 1.0), "specularTransmittance"), t)
-            if str(p.get("distribution", "beckmann")).lower() == "beckmann":
-                m["distribution"] = "beckmann"
-            return m
+            return microfacet(elem, p, specular(textured(dict(type=8, eta=float(f32(int_ior / ext_ior))), "specularReflectance", 1.0), "specularTransmittance"), t)
         if t == "bumpmap":  # BumpMap (bumpmap.cpp:60-133): one nested BSDF + one displacement texture, the outermost adapter
             inner = [c for c in elem if c.tag == "bsdf"]
             disp = [c for c in elem if c.tag in ("texture", "ref") and (c.tag == "texture" or c.get("id") in tex_by_id)]
@@ -1377,13 +1391,24 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
     # un-shared and its face normals written out (same shading frame as "no normals": skdtree.h:388-401)
     any_normals = any(m["normals"] is not None for m, _, _ in collected)
     # texture coordinates only matter on meshes whose BSDF reads a bitmap; the others get NaN rows (= none)
-    any_uvs = any(m.get("uvs") is not None and any(k in materials[mat] for k in TEXTURE_KEYS) for m, mat, _ in collected)
+    # ... or is anisotropic (EAnisotropic: alphaU != alphaV, or either a bitmap), which needs the UV tangents (trimesh.cpp:380, 683-735)
+    def anisotropic(m):
+        if m.get("alpha_v") is None:
+            return False
+        return (max(f32(m["alpha_v"]), f32(1e-4)) != max(f32(m.get("alpha", 0.1)), f32(1e-4)) or m.get("alpha_texture") is not None
+                or m.get("alpha_v_texture") is not None)
+    wants_uvs = lambda mat: any(k in materials[mat] for k in TEXTURE_KEYS) or anisotropic(materials[mat])  # noqa: E731
+    any_uvs = any(m.get("uvs") is not None and wants_uvs(mat) for m, mat, _ in collected)
     uvl = []
     pos, nrm, idx, tmat, tem = [], [], [], [], []
     nv = 0
     for mesh, mat, em in collected:
         p, i, n = mesh["positions"], mesh["indices"], mesh["normals"]
-        uv = mesh.get("uvs") if any(k in materials[mat] for k in TEXTURE_KEYS) else None
+        uv = mesh.get("uvs") if wants_uvs(mat) else None
+        if uv is None and anisotropic(materials[mat]):  # trimesh.cpp:686-691
+            raise SceneError('"%s": computeUVTangents(): texture coordinates are required to generate tangent vectors. If you want to render with an '
+                             'anisotropic material, please make sure that all associated shapes have valid texture coordinates.%s'
+                             % (mesh.get("name", "mesh"), " (This loader's rectangle and cube carry none.)" if mesh.get("name") in ("rectangle", "cube") else ""))
         if any_normals and n is None:
             if uv is not None:
                 uv = uv[i.reshape(-1)]
@@ -1442,11 +1467,19 @@ def save_scene_xml(desc, props, directory, name="scene"):
             '\t\t<float name="focusDistance" value="%r"/>' % float(lens["focus_distance"])]) + ['\t\t<sampler type="independent"/>', '\t\t<film type="hdrfilm">',
             '\t\t\t<integer name="width" value="%d"/>' % cam["width"], '\t\t\t<integer name="height" value="%d"/>' % cam["height"],
             '\t\t\t<boolean name="banner" value="false"/>', '\t\t\t<rfilter type="box"/>', '\t\t</film>', '\t</sensor>']
-    from .bindings import Material
+    from .bindings import Material, Microfacet
     for i, m in enumerate(desc.materials):
         t = m.get("type", 0)
         t = Material.BSDF[t] if isinstance(t, str) else int(t)
         M = Material.from_dict(m)
+        G = Microfacet.from_dict(m)  # a general entry is written as alphaU / alphaV (also when they are equal), phong, sampleVisible
+        distr = "phong" if G.general and G.distribution == 1 else ("beckmann" if M.flags & 8 else "ggx")
+        rough = '<string name="distribution" value="%s"/>' % distr
+        if G.general:
+            rough += '<float name="alphaU" value="%r"/><float name="alphaV" value="%r"/>' % (float(M.alpha), float(G.alpha_v))
+            rough += '<boolean name="sampleVisible" value="false"/>' if G.sample_all else ""
+        else:
+            rough += '<float name="alpha" value="%r"/>' % float(M.alpha)
         R, S, E, K = (c(getattr(M, n)) for n in ("reflectance", "specular", "eta", "k"))
         one = '<float name="extIOR" value="1.0"/><float name="intIOR" value="%r"/>' % float(M.eta[0])
         body = {
@@ -1455,19 +1488,19 @@ def save_scene_xml(desc, props, directory, name="scene"):
             2: '<bsdf type="conductor"%%s><string name="material" value="none"/><rgb name="specularReflectance" value="%s"/></bsdf>' % R,
             3: '<bsdf type="conductor"%%s><float name="extEta" value="1.0"/><rgb name="eta" value="%s"/><rgb name="k" value="%s"/>'
                '<rgb name="specularReflectance" value="%s"/></bsdf>' % (E, K, R),
-            4: '<bsdf type="roughconductor"%%s><string name="distribution" value="%s"/><float name="alpha" value="%r"/><float name="extEta" value="1.0"/>'
+            4: '<bsdf type="roughconductor"%%s>%s<float name="extEta" value="1.0"/>'
                '<rgb name="eta" value="%s"/><rgb name="k" value="%s"/><rgb name="specularReflectance" value="%s"/></bsdf>'
-               % ("beckmann" if M.flags & 8 else "ggx", float(M.alpha), E, K, R),
+               % (rough, E, K, R),
             5: '<bsdf type="plastic"%%s>%s<rgb name="diffuseReflectance" value="%s"/><rgb name="specularReflectance" value="%s"/>'
                '<boolean name="nonlinear" value="%s"/></bsdf>' % (one, R, S, "true" if M.flags & 2 else "false"),
             6: '<bsdf type="dielectric"%%s>%s<rgb name="specularReflectance" value="%s"/><rgb name="specularTransmittance" value="%s"/></bsdf>' % (one, R, S),
             7: '<bsdf type="thindielectric"%%s>%s<rgb name="specularReflectance" value="%s"/><rgb name="specularTransmittance" value="%s"/></bsdf>' % (one, R, S),
-            8: '<bsdf type="roughdielectric"%%s><string name="distribution" value="%s"/><float name="alpha" value="%r"/>%s'
+            8: '<bsdf type="roughdielectric"%%s>%s%s'
                '<rgb name="specularReflectance" value="%s"/><rgb name="specularTransmittance" value="%s"/></bsdf>'
-               % ("beckmann" if M.flags & 8 else "ggx", float(M.alpha), one, R, S),
-            9: '<bsdf type="roughplastic"%%s><string name="distribution" value="%s"/><float name="alpha" value="%r"/>%s'
+               % (rough, one, R, S),
+            9: '<bsdf type="roughplastic"%%s>%s%s'
                '<rgb name="diffuseReflectance" value="%s"/><rgb name="specularReflectance" value="%s"/><boolean name="nonlinear" value="%s"/></bsdf>'
-               % ("beckmann" if M.flags & 8 else "ggx", float(M.alpha), one, R, S, "true" if M.flags & 2 else "false"),
+               % (rough, one, R, S, "true" if M.flags & 2 else "false"),
         }[t]
         twos = t == 1 or (M.flags & 1 and t not in (6, 7, 8))
         if M.flags & 4:

@@ -1,6 +1,6 @@
 """Rough-transmittance slices for the `roughplastic` BSDF (include/ppg.h: ppg_scene.rtrans).
 
-Mitsuba keeps the transmittance through a rough dielectric boundary in precomputed tables, data/microfacet/{beckmann,ggx}.dat, and
+Mitsuba keeps the transmittance through a rough dielectric boundary in precomputed tables, data/microfacet/{beckmann,ggx,phong}.dat, and
 RoughPlastic::configure() (roughplastic.cpp:285-305) cuts them down to what one material needs: a 1D curve over the warped
 incident cosine (setEta, setAlpha) and one number for the diffuse transmittance from the inside.  This module restates that
 reduction — the file format of rtrans.h:81-146, setEta / setAlpha / evalDiffuse of rtrans.h:233-400 and the cubic interpolation

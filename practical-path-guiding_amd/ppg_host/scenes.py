@@ -42,7 +42,7 @@ class SceneDesc:
 
 def save_scene(desc, path):
     """Write the flat binary scene read by host/ppg_render.cpp: "PPGS", 6 x uint32 {n_vertices, n_triangles, n_materials,
-    n_emitters, has_normals, blocks (bit 0: environment, bit 1: rtrans, bit 2: spheres, bit 3: envmap, bit 4: texcoords, bit 5: textures, bit 6: rfilter, bit 7: lens, bit 8: delta emitters, bit 9: material textures, bit 10: shapes)}, then positions, [normals], indices, tri_material,
+    n_emitters, has_normals, blocks (bit 0: environment, bit 1: rtrans, bit 2: spheres, bit 3: envmap, bit 4: texcoords, bit 5: textures, bit 6: rfilter, bit 7: lens, bit 8: delta emitters, bit 9: material textures, bit 10: shapes, bit 11: microfacet)}, then positions, [normals], indices, tri_material,
     tri_emitter, materials (ppg_material, 80 bytes each), emitters (4 floats), camera (ppg_camera), [environment radiance:
     3 floats], [rtrans: 2 x uint32 {n_slices, samples}, then n_slices x (samples + 1) floats], [spheres: uint32 n, then n x ppg_sphere
     (64 bytes)], [envmap: 2 x uint32 {width, height}, float scale, 9 floats to_world, then height x width x 3 floats], [texcoords: n_vertices x 2
@@ -52,9 +52,11 @@ def save_scene(desc, path):
     [lens: ppg_lens, 2 floats {aperture_radius, focus_distance} — only for a thin-lens camera],
     [delta emitters: uint32 n, then n x ppg_delta_emitter (84 bytes) — only when there are point / spot / directional emitters],
     [material textures: n_materials x ppg_material_textures (16 bytes) — only when a material has a bitmap on specular / alpha / opacity],
-    [shapes: uint32 n, then n x ppg_shape (80 bytes) — only when there are analytic disks or cylinders]."""
+    [shapes: uint32 n, then n x ppg_shape (80 bytes) — only when there are analytic disks or cylinders],
+    [microfacet: n_materials x ppg_microfacet (32 bytes) — only when a material states alphaU / alphaV, distribution = phong or sampleVisible = false]."""
     import struct
-    from .bindings import DeltaEmitter, Lens, MaterialTextures, RFilter, Shape, has_parameter_textures
+    from .bindings import DeltaEmitter, Lens, MaterialTextures, Microfacet, RFilter, Shape, has_general_microfacet, has_parameter_textures
+    mfd = [Microfacet.from_dict(m) for m in desc.materials] if has_general_microfacet(desc) else []
     mat_tex = [MaterialTextures.from_dict(m) for m in desc.materials] if has_parameter_textures(desc) else []
     rf = RFilter.from_dict(getattr(desc, "rfilter", None))
     rf = rf if rf.as_dict() is not None else None
@@ -72,7 +74,7 @@ def save_scene(desc, path):
         f.write(struct.pack("<6I", pos.shape[0], idx.shape[0], len(desc.materials), len(desc.emitters), 0 if desc.normals is None else 1,
                             (0 if env is None else 1) | (0 if rt is None else 2) | (4 if getattr(desc, "spheres", None) else 0) | (8 if getattr(desc, "envmap", None) is not None else 0)
                             | (16 if getattr(desc, "texcoords", None) is not None else 0) | (32 if getattr(desc, "textures", None) else 0) | (0 if rf is None else 64)
-                            | (0 if lens is None else 128) | (256 if delta else 0) | (512 if mat_tex else 0) | (1024 if shapes else 0)))
+                            | (0 if lens is None else 128) | (256 if delta else 0) | (512 if mat_tex else 0) | (1024 if shapes else 0) | (2048 if mfd else 0)))
         f.write(pos.tobytes())
         if desc.normals is not None:
             f.write(np.ascontiguousarray(desc.normals, np.float32).tobytes())
@@ -131,6 +133,8 @@ def save_scene(desc, path):
             f.write(struct.pack("<I", len(shapes)))
             for sh in shapes:
                 f.write(bytes(sh))
+        for g in mfd:
+            f.write(bytes(g))
 
 
 def srgb8_table():
@@ -255,6 +259,20 @@ def load_scene_file(path):
             if not 0 <= sh.type < len(Shape.TYPES):
                 raise ValueError("%s: unknown shape type %d" % (path, sh.type))
             shapes.append(sh.as_dict())
+    if blocks & 2048:
+        from .bindings import Microfacet
+        for d in mats:
+            g = Microfacet.from_buffer_copy(bytes(take(np.uint8, C_MICROFACET_BYTES)))
+            if any(g._reserved) or g.alpha_v_texture > len(textures) or g.distribution not in (0, 1):
+                raise ValueError("%s: microfacet entry out of range" % path)
+            if g.general:
+                d["alpha_v"] = float(g.alpha_v)
+                if g.distribution == 1:
+                    d["distribution"] = "phong"
+                if g.sample_all:
+                    d["sample_visible"] = False
+                if g.alpha_v_texture:
+                    d["alpha_v_texture"] = int(g.alpha_v_texture) - 1
     if off[0] != len(buf):
         raise ValueError("%s: trailing bytes" % path)
     return SceneDesc(pos, idx, tm, te, mats, ems, cam, nrm, env, rt, spheres, envmap, uvs, textures, rfilter, lens, delta, shapes)
@@ -263,6 +281,7 @@ def load_scene_file(path):
 C_RFILTER_BYTES = 24  # sizeof(ppg_rfilter)
 C_LENS_BYTES = 8      # sizeof(ppg_lens)
 C_SHAPE_BYTES = 80    # sizeof(ppg_shape)
+C_MICROFACET_BYTES = 32  # sizeof(ppg_microfacet)
 C_MATERIAL_TEXTURES_BYTES = 16  # sizeof(ppg_material_textures)
 C_DELTA_EMITTER_BYTES = 84  # sizeof(ppg_delta_emitter)
 
