@@ -449,6 +449,41 @@ typedef struct ppg_microfacet {
 int ppg_set_microfacet(ppg_ctx *ctx, const ppg_microfacet *m, uint32_t n_materials);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mitsuba's `coating` (coating.cpp, SmoothCoating) and `roughcoating` (roughcoating.cpp, RoughCoating) adapters: a dielectric layer
+ * over the material's BSDF, inside its two-sided / mask / bump-map adapters: bumpmap( mask( twosided( coat( leaf )))).  One more side
+ * list, one entry per material in ppg_scene.materials' order, with the ordering rules of ppg_set_material_textures: call before
+ * ppg_set_scene, which validates and consumes it; the context keeps it until it is replaced (NULL or n_materials = 0 clears it);
+ * PPG_ERR_STATE between ppg_begin_render and ppg_end_render.  A list without an entry of kind != 0 renders exactly as no list does.
+ *   kind          0: none (the other fields are ignored), 1: coating, 2: roughcoating
+ *   eta           intIOR / extIOR;  thickness, sigma_a: the layer's absorption exp(-sigma_a * thickness * (1/|cos i'| + 1/|cos o'|))
+ *   specular      specularReflectance of the layer's own (delta / glossy) reflection, the BSDF's last component
+ *   kind 2:       alpha (clamped to >= 1e-4), distribution (0 beckmann, 1 ggx, 2 phong, which implies sample_all), sample_all
+ *                 (sampleVisible = false) and rtrans: the layer's rough-transmittance slice, a row of ppg_scene.rtrans — the reduction
+ *                 roughplastic uses, for (distribution, alpha, eta)
+ * specularSamplingWeight = 1 / (avg(exp(-2 * thickness * sigma_a)) + 1) is derived inside ppg_set_scene with the library's own exp.
+ * Nested BSDFs: coating takes diffuse, mirror / conductor, roughconductor, plastic and roughplastic; roughcoating those without a delta
+ * component — diffuse, roughconductor, roughplastic.  ppg_set_scene returns PPG_ERR_INVALID, and ppg_last_error names the material, for:
+ * a list whose length is neither 0 nor n_materials; another kind; a coat on dielectric, thindielectric or roughdielectric; a
+ * roughcoating over mirror, conductor or plastic; eta <= 0 or == 1; a value that is not finite; negative thickness or sigma_a; a
+ * distribution other than 0..2; rtrans out of range; a non-zero reserved word.
+ * A scene with a coat runs the "coat" kernels (csrc: PPG_COAT), whatever else it holds; the CPU oracle does not know these entries
+ * (they are pinned against a float64 restatement).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ppg_coating {
+    int32_t kind;          /* 0 = none, 1 = coating, 2 = roughcoating */
+    float eta;             /* intIOR / extIOR */
+    float thickness;
+    float sigma_a[3];
+    float specular[3];     /* specularReflectance */
+    float alpha;           /* kind 2 */
+    int32_t distribution;  /* kind 2: 0 = beckmann, 1 = ggx, 2 = phong */
+    int32_t sample_all;    /* kind 2: sampleVisible = false */
+    int32_t rtrans;        /* kind 2: row of ppg_scene.rtrans */
+    uint32_t _reserved[3]; /* must be 0 */
+} ppg_coating;             /* 64 bytes */
+int ppg_set_coatings(ppg_ctx *ctx, const ppg_coating *c, uint32_t n_materials);
+
+/* ------------------------------------------------------------------------------------------------
  * Rendering.  ppg_render() is GuidedPathTracer::render() (GP:1516-1585, IH:74-75) in one call.
  * The stepwise calls expose its phases so a multi-GPU driver can all-reduce the SD-tree statistics
  * between ppg_render_passes() and ppg_build_sdtree(); ppg_render() is exactly their composition

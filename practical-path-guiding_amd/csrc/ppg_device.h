@@ -40,7 +40,20 @@
 #if PPG_MFD && !PPG_SHAPES
 #error "the extended units are built with -DPPG_SHAPES=1 -DPPG_MFD=1"
 #endif
-#if PPG_MFD
+// The coating / roughcoating adapters (ppg_set_coatings) are compiled into a fourth, "coat" family — k_trace_coat, k_shade_coat, k_tail_coat:
+// translation units built with -DPPG_SHAPES=1 -DPPG_MFD=1 -DPPG_COAT=1 —, launched for a scene with a coated material, whatever else it holds.
+// Everything it adds sits under PPG_COAT.
+#ifndef PPG_COAT
+#define PPG_COAT 0
+#endif
+#if PPG_COAT && !PPG_MFD
+#error "the coat units are built with -DPPG_SHAPES=1 -DPPG_MFD=1 -DPPG_COAT=1"
+#endif
+#if PPG_COAT
+#define k_trace k_trace_coat
+#define k_shade k_shade_coat
+#define k_tail k_tail_coat
+#elif PPG_MFD
 #define k_trace k_trace_ext
 #define k_shade k_shade_ext
 #define k_tail k_tail_ext
@@ -211,7 +224,14 @@ struct DevScene {
     // ppg_set_microfacet with a general entry (extended kernels only, PPG_MFD): one float4 per material = (alphaV, PPG_MFDF_* bits,
     // alphaV texture: 1 + index as bits, -); nullptr otherwise
     const float4 *mfd;
+    // ppg_set_coatings with a coat (coat kernels only, PPG_COAT): PPG_COAT_STRIDE float4 per material = (eta, thickness,
+    // specularSamplingWeight, PPG_COATF_* bits), (sigmaA, alpha), (specularReflectance, rough-transmittance slice as int); nullptr otherwise
+    const float4 *coat;
 };
+#define PPG_COAT_STRIDE 3
+#define PPG_COATF_KIND 3u         // 0 none, 1 coating, 2 roughcoating
+#define PPG_COATF_TYPE_SHIFT 2    // bits 2..3: MFD_BECKMANN / MFD_GGX / MFD_PHONG of a roughcoating
+#define PPG_COATF_SAMPLE_ALL 16u  // roughcoating: sampleVisible = false (always with phong)
 #define PPG_MFDF_GENERAL 1u     // the entry is live
 #define PPG_MFDF_PHONG 2u       // distribution = phong / as
 #define PPG_MFDF_SAMPLE_ALL 4u  // sampleVisible = false (always with PHONG)
@@ -1534,6 +1554,9 @@ struct Mat {
     float alpha_v;            // alphaV (alpha is alphaU); = alpha without a general entry
     unsigned int mfd;         // the entry's PPG_MFDF_* bits, 0 without one
 #endif
+#if PPG_COAT
+    const float4 *coat;       // the material's rows of DevScene::coat when it is coated (ppg_set_coatings), nullptr otherwise
+#endif
 };
 D Mat load_material(const DevScene &S, int id) {
     const float4 *m = S.materials + PPG_MAT_STRIDE * (size_t)id;
@@ -1556,6 +1579,13 @@ D Mat load_material(const DevScene &S, int id) {
     if (S.mfd) {
         const float4 g = S.mfd[id];
         if (__float_as_uint(g.y) & PPG_MFDF_GENERAL) { M.alpha_v = g.x; M.mfd = __float_as_uint(g.y); }
+    }
+#endif
+#if PPG_COAT
+    M.coat = nullptr;
+    if (S.coat) {
+        const float4 *c = S.coat + PPG_COAT_STRIDE * (size_t)id;
+        if (__float_as_uint(c[0].w) & PPG_COATF_KIND) M.coat = c;
     }
 #endif
     return M;
@@ -1606,6 +1636,10 @@ D void mat_apply_null_textures(const DevScene &S, const Hit &h, int id, Mat &M) 
     if (ts) { const float4 t = tex_eval_hit(S.uvs, S.textures, ts, h.prim, h.u, h.v); M.spec = f3(t.x, t.y, t.z); }
 }
 D bool mat_is_smooth(const Mat &M) {
+#if PPG_COAT
+    // a roughcoating's own component is glossy, a coating's is a delta: "nested smooth, or roughcoating"
+    if (M.coat && (__float_as_uint(M.coat[0].w) & PPG_COATF_KIND) == 2u) return true;
+#endif
     return M.type == PPG_BSDF_DIFFUSE || M.type == PPG_BSDF_ROUGHCONDUCTOR || M.type == PPG_BSDF_PLASTIC || M.type == PPG_BSDF_ROUGHDIELECTRIC ||
            M.type == PPG_BSDF_ROUGHPLASTIC;
 }
@@ -2162,6 +2196,18 @@ D float mat_pdf_one(const Mat &M, F3 wi, F3 wo) {
     }
     return 0.0f;
 }
+#if PPG_COAT
+// The coat kernels (PPG_COAT) reach the nested BSDF's eval() / pdf() through real calls: a coat evaluates them once more on the refracted
+// pair, roughcoating's sample() after the nested sample() as well, and the FULL kernels have neither registers nor instruction cache for
+// further inlined copies of the material switch.  The arithmetic is that of the inlined functions: uncoated materials keep their bits.
+MFD_CALL F3 mat_eval_one_call(Mat M, F3 wi, F3 wo) { return mat_eval_one(M, wi, wo); }
+MFD_CALL float mat_pdf_one_call(Mat M, F3 wi, F3 wo) { return mat_pdf_one(M, wi, wo); }
+#define MAT_EVAL_ONE mat_eval_one_call
+#define MAT_PDF_ONE mat_pdf_one_call
+#else
+#define MAT_EVAL_ONE mat_eval_one
+#define MAT_PDF_ONE mat_pdf_one
+#endif
 D F3 mat_sample_one(const Mat &M, F3 wi, float sx, float sy, F3 &wo, float &pdf, bool &delta, float &eta, bool &isnull, unsigned int key,
                     unsigned int &dim) {
     delta = false; eta = 1.0f; pdf = 0.0f; wo = f3s(0.0f); isnull = false;
@@ -2221,9 +2267,9 @@ D F3 mat_sample_one(const Mat &M, F3 wi, float sx, float sy, F3 &wo, float &pdf,
                 sy = (sy - pS) / (1 - pS);
                 wo = cosine_hemisphere(sx, sy);
             }
-            pdf = mat_pdf_one(M, wi, wo);
+            pdf = MAT_PDF_ONE(M, wi, wo);
             if (pdf == 0) return f3s(0.0f);
-            return div3(mat_eval_one(M, wi, wo), pdf);
+            return div3(MAT_EVAL_ONE(M, wi, wo), pdf);
         }
         case PPG_BSDF_PLASTIC: {  // plastic.cpp:368-425
             if (wi.z <= 0) return f3s(0.0f);
@@ -2323,15 +2369,192 @@ D F3 mat_sample_one(const Mat &M, F3 wi, float sx, float sy, F3 &wo, float &pdf,
     }
     return f3s(0.0f);
 }
+#if PPG_COAT
+// ------------------------------------------------------------------------------------------------
+// The coating / roughcoating adapters (coating.cpp:202-371, roughcoating.cpp:229-451) around mat_*_one: a dielectric layer over the nested
+// BSDF, inside the two-sided adapter.  M.coat points at the material's rows of DevScene::coat (layout there).  All type masks are "all
+// components", as the integrator asks; the measure is the solid angle, except for a delta sample.
+// ------------------------------------------------------------------------------------------------
+D bool coat_rough(const Mat &M) { return (__float_as_uint(M.coat[0].w) & PPG_COATF_KIND) == 2u; }
+// refractIn (coating.cpp:207-212); refractOut (214-219) is the same function of (invEta, eta)
+D F3 coat_refract_in(F3 w, float eta, float invEta, float &R) {
+    float cosThetaT;
+    R = fresnel_dielectric_ext(ppg_abs(w.z), cosThetaT, eta);
+    return f3(invEta * w.x, invEta * w.y, -fsignum(w.z) * cosThetaT);
+}
+// refractTo (roughcoating.cpp:235-255): invEta = m_invEta towards the interior, m_eta towards the exterior; the zero vector = total
+// internal reflection
+D F3 coat_refract_to(F3 w, float invEta) {
+    const float sinThetaTSqr = invEta * invEta * (1.0f - w.z * w.z);
+    if (sinThetaTSqr >= 1.0f) return f3s(0.0f);
+    const float cosThetaT = __builtin_sqrtf(1.0f - sinThetaTSqr);
+    return f3(invEta * w.x, invEta * w.y, w.z > 0.0f ? cosThetaT : -cosThetaT);
+}
+// m_roughTransmittance->eval(cosTheta, alpha) on the coat's own slice (rtrans.h:185-196, 233).  The table keeps the slice's distance from
+// the nested material's, in rows of ppg_scene.rtrans: Mat carries one slice pointer.
+MFD_CALL float coat_rough_T(const float *rt, int rows, int rt_n, float cosTheta) {
+    const float warped = dm_pow(ppg_abs(cosTheta), 0.25f);
+    if (!(cosTheta >= 0)) return 0.0f;
+    return ppg_min(1.0f, ppg_max(0.0f, cubic_interp_1d(warped, rt + (ptrdiff_t)rows * (ptrdiff_t)(rt_n + 1), rt_n)));
+}
+D float coat_T(const Mat &M, float cosTheta) { return coat_rough_T(M.rt, __float_as_int(M.coat[2].w), M.rt_n, cosTheta); }
+D Mfd coat_mfd(const Mat &M) {  // MicrofacetDistribution(m_type, alpha, m_sampleVisible), microfacet.h:67-93
+    const unsigned int bits = __float_as_uint(M.coat[0].w);
+    Mfd d;
+    d.type = (int)((bits >> PPG_COATF_TYPE_SHIFT) & 3u);
+    d.alphaU = d.alphaV = ppg_max(M.coat[1].w, 1e-4f);
+    d.sampleAll = (bits & PPG_COATF_SAMPLE_ALL) != 0u;
+    d.exponentU = 0.0f; d.exponentV = 0.0f;
+    if (d.type == MFD_PHONG) mfd_phong_exponent(d);
+    return d;
+}
+// the reallocated probability of the coat's own component (coating.cpp:270-272, roughcoating.cpp:346-348)
+D float coat_prob_specular(float p, float w) { return (p * w) / (p * w + (1 - p) * (1 - w)); }
+// exp(-sigmaA * thickness * (1/|cos i'| + 1/|cos o'|)) (coating.cpp:243-247)
+D F3 coat_absorb(const Mat &M, F3 r, float cosI, float cosO) {
+    const float4 c1 = M.coat[1];
+    const F3 sigmaA = f3(c1.x, c1.y, c1.z) * M.coat[0].y;
+    if (iszero3(sigmaA)) return r;
+    const float t = 1 / ppg_abs(cosI) + 1 / ppg_abs(cosO);
+    return mul3(r, f3(dm_exp(-sigmaA.x * t), dm_exp(-sigmaA.y * t), dm_exp(-sigmaA.z * t)));
+}
+MFD_CALL F3 coat_eval(Mat M, F3 wi, F3 wo) {  // coating.cpp:221-258, roughcoating.cpp:257-318
+    const float eta = M.coat[0].x, invEta = 1 / eta;
+    F3 result = f3s(0.0f), wiP, woP;
+    float a, b;
+    if (!coat_rough(M)) {
+        wiP = coat_refract_in(wi, eta, invEta, a);
+        woP = coat_refract_in(wo, eta, invEta, b);
+        if (a == 1 || b == 1) return result;
+        a = 1 - a; b = 1 - b;
+    } else {
+        if (wo.z * wi.z > 0) {
+            const Mfd distr = coat_mfd(M);
+            const F3 H = norm3(wo + wi) * fsignum(wo.z);
+            const float Dm = ggx_eval(distr, H);
+            const float F = fresnel_dielectric_ext(ppg_abs(dot3(wi, H)), eta);
+            const float G = ggx_smith_g1(distr, wi, H) * ggx_smith_g1(distr, wo, H);
+            const float value = F * Dm * G / (4.0f * ppg_abs(wi.z));
+            const float4 c2 = M.coat[2];
+            result = f3(c2.x, c2.y, c2.z) * value;
+        }
+        wiP = coat_refract_to(wi, invEta);
+        woP = coat_refract_to(wo, invEta);
+        if (iszero3(wiP) || iszero3(woP)) return result;  // (only a layer with eta < 1 gets here)
+        a = coat_T(M, ppg_abs(wi.z)); b = coat_T(M, ppg_abs(wo.z));
+    }
+    F3 nested = MAT_EVAL_ONE(M, wiP, woP) * a * b;
+    nested = coat_absorb(M, nested, wiP.z, woP.z);
+    nested = nested * (invEta * invEta * wo.z / woP.z);
+    return result + nested;
+}
+MFD_CALL float coat_pdf(Mat M, F3 wi, F3 wo) {  // coating.cpp:260-296, roughcoating.cpp:320-382
+    const float4 c0 = M.coat[0];
+    const float eta = c0.x, invEta = 1 / eta;
+    float result = 0.0f, probSpecular;
+    F3 wiP, woP;
+    if (!coat_rough(M)) {
+        float R12, R21;
+        wiP = coat_refract_in(wi, eta, invEta, R12);
+        probSpecular = coat_prob_specular(R12, c0.z);
+        woP = coat_refract_in(wo, eta, invEta, R21);
+        if (R12 == 1 || R21 == 1) return 0.0f;
+    } else {
+        const F3 H = norm3(wo + wi) * fsignum(wo.z);
+        probSpecular = coat_prob_specular(1 - coat_T(M, ppg_abs(wi.z)), c0.z);
+        if (wo.z * wi.z > 0) {
+            const Mfd distr = coat_mfd(M);
+            const float dwh_dwo = 1.0f / (4.0f * ppg_abs(dot3(wo, H)));
+            const float prob = mfd_pdf(distr, wi, H);
+            result = prob * dwh_dwo * probSpecular;
+        }
+        wiP = coat_refract_to(wi, invEta);
+        woP = coat_refract_to(wo, invEta);
+        if (iszero3(wiP) || iszero3(woP)) return result;
+    }
+    float prob = MAT_PDF_ONE(M, wiP, woP);
+    prob *= invEta * invEta * wo.z / woP.z;
+    return result + prob * (1 - probSpecular);
+}
+// sample(), the part before the nested sample() (coating.cpp:298-339, roughcoating.cpp:384-433).  Returns what is left to do:
+enum { COAT_NESTED = 1,       // the nested lobes of a coating were chosen: sample the nested BSDF at wiN, then coat_sample_post
+       COAT_NESTED_ROUGH = 2, // ... of a roughcoating
+       COAT_DONE = 3,         // `result` is final
+       COAT_REEVAL = 4 };     // a roughcoating's own lobe was sampled: wo is set, pdf() and eval() / pdf remain
+D int coat_sample_pre(const Mat &M, F3 wi, float &sx, float &sy, F3 &wiN, float &ps, float &R12, F3 &result, F3 &wo, float &pdf, bool &delta,
+                      float &eta, bool &isnull) {
+    const float4 c0 = M.coat[0];
+    const float m_eta = c0.x, m_invEta = 1 / m_eta;
+    delta = false; eta = 1.0f; pdf = 0.0f; wo = f3s(0.0f); isnull = false;
+    result = f3s(0.0f);
+    if (!coat_rough(M)) {
+        wiN = coat_refract_in(wi, m_eta, m_invEta, R12);
+        ps = coat_prob_specular(R12, c0.z);
+        if (sx < ps) {
+            sx /= ps;  // (as the reference does; nothing reads it)
+            wo = f3(-wi.x, -wi.y, wi.z);
+            delta = true;
+            pdf = ps;
+            const float4 c2 = M.coat[2];
+            result = f3(c2.x, c2.y, c2.z) * (R12 / pdf);
+            return COAT_DONE;
+        }
+        sx = (sx - ps) / (1 - ps);
+        if (R12 == 1.0f) return COAT_DONE;
+        return COAT_NESTED;
+    }
+    ps = coat_prob_specular(1 - coat_T(M, ppg_abs(wi.z)), c0.z);
+    if (sy < ps) {
+        sy /= ps;
+        const float4 ms = mfd_sample(coat_mfd(M), wi, sx, sy);
+        const F3 m = f3(ms.x, ms.y, ms.z);
+        wo = m * (2 * dot3(wi, m)) - wi;
+        if (wo.z * wi.z <= 0) { wo = f3s(0.0f); return COAT_DONE; }
+        return COAT_REEVAL;
+    }
+    sy = (sy - ps) / (1 - ps);
+    wiN = coat_refract_to(wi, m_invEta);
+    if (iszero3(wiN)) return COAT_DONE;
+    return COAT_NESTED_ROUGH;
+}
+// ... and the part after it (coating.cpp:340-370, roughcoating.cpp:434-441): wo, pdf, delta are the nested sample's
+D int coat_sample_post(const Mat &M, int state, F3 wiN, float ps, float R12, F3 &result, F3 &wo, float &pdf, bool delta) {
+    const float m_eta = M.coat[0].x, m_invEta = 1 / m_eta;
+    if (iszero3(result)) { result = f3s(0.0f); wo = f3s(0.0f); pdf = 0.0f; return COAT_DONE; }
+    const F3 woP = wo;
+    if (state == COAT_NESTED_ROUGH) {
+        wo = coat_refract_to(woP, m_eta);
+        if (iszero3(wo)) { result = f3s(0.0f); pdf = 0.0f; return COAT_DONE; }
+        return COAT_REEVAL;
+    }
+    result = coat_absorb(M, result, wiN.z, woP.z);
+    float R21;
+    wo = coat_refract_in(woP, m_invEta, m_eta, R21);  // refractOut
+    if (R21 == 1.0f) { result = f3s(0.0f); wo = f3s(0.0f); pdf = 0.0f; return COAT_DONE; }
+    pdf *= 1.0f - ps;
+    result = div3(result, 1.0f - ps);
+    result = result * ((1 - R12) * (1 - R21));
+    if (!delta) pdf *= m_invEta * m_invEta * wo.z / woP.z;
+    return COAT_DONE;
+}
+#endif
 // + the TwoSided adapter (twosided.cpp:120-180) and, outside it, the Mask adapter (mask.cpp:108-214)
 D F3 mat_eval(const Mat &M, F3 wi, F3 wo) {
     if (mat_two_sided(M) && !(wi.z > 0)) { wi.z *= -1; wo.z *= -1; }
+#if PPG_COAT
+    F3 r = M.coat ? coat_eval(M, wi, wo) : MAT_EVAL_ONE(M, wi, wo);
+#else
     F3 r = mat_eval_one(M, wi, wo);
+#endif
     return mat_masked(M) ? mul3(r, M.opacity) : r;
 }
 D float mat_pdf(const Mat &M, F3 wi, F3 wo) {
     if (mat_two_sided(M) && !(wi.z > 0)) { wi.z *= -1; wo.z *= -1; }
+#if PPG_COAT
+    float r = M.coat ? coat_pdf(M, wi, wo) : MAT_PDF_ONE(M, wi, wo);
+#else
     float r = mat_pdf_one(M, wi, wo);
+#endif
     return mat_masked(M) ? r * lum3(M.opacity) : r;
 }
 D F3 mat_sample_ts(const Mat &M, F3 wi, float sx, float sy, F3 &wo, float &pdf, bool &delta, float &eta, bool &isnull, unsigned int key,
@@ -2362,7 +2585,28 @@ D F3 mat_sample_ts(const Mat &M, F3 wi, float sx, float sy, F3 &wo, float &pdf, 
                    unsigned int &dim) {
     bool flipped = false;
     if (mat_two_sided(M) && wi.z < 0) { wi.z *= -1; flipped = true; }
+#if PPG_COAT
+    // (still ONE call of the nested sample(): a coat only changes its arguments before and its results after)
+    F3 result, wiN = wi;
+    float ps = 0.0f, R12 = 0.0f;
+    int coat = 0;
+    if (M.coat) coat = coat_sample_pre(M, wi, sx, sy, wiN, ps, R12, result, wo, pdf, delta, eta, isnull);
+    if (coat < COAT_DONE) {
+        result = mat_sample_one(M, wiN, sx, sy, wo, pdf, delta, eta, isnull, key, dim);
+        if (coat) coat = coat_sample_post(M, coat, wiN, ps, R12, result, wo, pdf, delta);
+    }
+    if (coat == COAT_REEVAL) {  // roughcoating.cpp:443-450
+        pdf = coat_pdf(M, wi, wo);
+        if (pdf != 0) result = div3(coat_eval(M, wi, wo), pdf);
+        // (not finite: the layer's own lobe sampled from below a one-sided surface, where the visible normals of a direction under the
+        // horizon mean nothing — a failed sample, where the reference would hand its caller the NaN)
+        if (pdf == 0 || !ppg_isfinite(pdf) || !ppg_isfinite(result.x + result.y + result.z) || !ppg_isfinite(wo.x + wo.y + wo.z)) {
+            result = f3s(0.0f); wo = f3s(0.0f); pdf = 0.0f;
+        }
+    }
+#else
     F3 result = mat_sample_one(M, wi, sx, sy, wo, pdf, delta, eta, isnull, key, dim);
+#endif
     if (flipped && !iszero3(result) && pdf != 0) wo.z *= -1;
     return result;
 }

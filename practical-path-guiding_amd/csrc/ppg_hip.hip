@@ -827,6 +827,8 @@ struct ppg_ctx {
     DevBuf<float4> d_shapes;
     std::vector<ppg_microfacet> microfacet;  // ppg_set_microfacet: kept until replaced; ppg_set_scene validates it and builds d_mfd from it
     DevBuf<float4> d_mfd;
+    std::vector<ppg_coating> coatings;  // ppg_set_coatings: kept until replaced; ppg_set_scene validates it and builds d_coat from it
+    DevBuf<float4> d_coat;
     uint32_t nMaterials = 0;       // of the scene set last (ppg_debug_bsdf checks its items against it)
     bool renderOpen = false;       // between ppg_begin_render and ppg_end_render
     int W = 0, H = 0;
@@ -1012,12 +1014,14 @@ struct ppg_ctx {
 };
 
 void ppg_launch_shade(int variant, const ShadeLaunch &a) {
+    if (a.S.coat) { ppg_launch_shade_coat(variant, a); return; }  // a coated material: the coat family, whatever else the scene holds
     if (a.S.mfd) { ppg_launch_shade_ext(variant, a); return; }  // a general microfacet entry: the extended family, shapes or not
     if (a.S.n_shapes) { ppg_launch_shade_shapes(variant, a); return; }  // (such a scene is FULL and never small)
     if (variant >> 1) ppg_launch_shade_pair1(variant, a);
     else ppg_launch_shade_pair0(variant, a);
 }
 void ppg_launch_tail(int variant, const TailLaunch &a) {
+    if (a.S.coat) { ppg_launch_tail_coat(variant, a); return; }
     if (a.S.mfd) { ppg_launch_tail_ext(variant, a); return; }
     if (a.S.n_shapes) { ppg_launch_tail_shapes(variant, a); return; }
     switch (variant >> 1) {
@@ -1839,7 +1843,7 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
         if (((chunks + (size_t)ctx->tuneBlocksSmall - 1) / (size_t)ctx->tuneBlocksSmall) * PPG_DCHUNK <= (size_t)ctx->queues.cap) grid = ctx->tuneBlocksSmall;
     }
     const int gridAll = gridFor(P.n_paths);
-    const bool smallScene = ctx->scene.n_tris <= 64 && ctx->ldsTris == ctx->scene.n_tris && ctx->scene.n_spheres == 0 && ctx->scene.n_shapes == 0 && !ctx->scene.mfd && !ctx->tuneForceBvh;
+    const bool smallScene = ctx->scene.n_tris <= 64 && ctx->ldsTris == ctx->scene.n_tris && ctx->scene.n_spheres == 0 && ctx->scene.n_shapes == 0 && !ctx->scene.mfd && !ctx->scene.coat && !ctx->tuneForceBvh;
     // (small scenes go through k_trace too: tracing them inside k_generate / k_shade was measured slower, DESIGN.md "Tuning switches")
     const bool neeOn = ctx->doNee;  // m_doNee of this iteration (doNeeWithSpp, GP:1331-1340)
     const bool fullMats = ctx->fullMaterials;  // any BSDF beyond diffuse / two-sided diffuse / mirror: the FULL kernel variants
@@ -1899,7 +1903,8 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
             unsigned int *const trSorted = sortSlices ? ctx->d_queueSorted.p : nullptr;
             unsigned char *const trKeys = sortSlices ? ctx->d_sortKeys.p : nullptr;
             timedLaunch(ctx, "k_trace", hostCount, [&] {
-                if (S.mfd) ppg_launch_trace_ext(ctx->timer.enabled, grid, traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
+                if (S.coat) ppg_launch_trace_coat(ctx->timer.enabled, grid, traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
+                else if (S.mfd) ppg_launch_trace_ext(ctx->timer.enabled, grid, traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
                 else if (S.n_shapes) ppg_launch_trace_shapes(ctx->timer.enabled, grid, traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
                 else if (smallScene) hipLaunchKernelGGL((k_trace<true, false>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, 0, ctx->ldsTris, trSorted, trKeys);
                 else if (ctx->timer.enabled) hipLaunchKernelGGL((k_trace<false, true>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
@@ -3173,6 +3178,65 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
         ctx->scene.mfd = ctx->d_mfd.p;
         ctx->fullMaterials = true;  // (the rough types are FULL anyway)
     }
+    // ppg_set_coatings: the coating / roughcoating adapters
+    bool anyCoat = false;
+    std::vector<float4> coatTab;
+    if (!ctx->coatings.empty()) {
+        if (ctx->coatings.size() != s->n_materials) {
+            ctx->error = "coatings: the list has " + std::to_string(ctx->coatings.size()) + " entries, the scene " + std::to_string(s->n_materials) + " materials";
+            return PPG_ERR_INVALID;
+        }
+        coatTab.assign(PPG_COAT_STRIDE * (size_t)s->n_materials, make_float4(0, 0, 0, 0));
+        for (uint32_t i = 0; i < s->n_materials; ++i) {
+            const ppg_coating &c = ctx->coatings[i];
+            const ppg_material &m = s->materials[i];
+            const std::string who = "material " + std::to_string(i) + ": coating: ";
+            if (c._reserved[0] || c._reserved[1] || c._reserved[2]) { ctx->error = who + "_reserved must be 0"; return PPG_ERR_INVALID; }
+            if (c.kind == 0) continue;
+            if (c.kind != 1 && c.kind != 2) { ctx->error = who + "kind must be 0 (none), 1 (coating) or 2 (roughcoating)"; return PPG_ERR_INVALID; }
+            const char *name = c.kind == 1 ? "coating" : "roughcoating";
+            if (m.type == PPG_BSDF_DIELECTRIC || m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_ROUGHDIELECTRIC || m.type < 0 || m.type > PPG_BSDF_LAST) {
+                ctx->error = who + name + " over dielectric, thindielectric or roughdielectric is not supported"; return PPG_ERR_INVALID;
+            }
+            if (c.kind == 2 && (m.type == PPG_BSDF_MIRROR || m.type == PPG_BSDF_CONDUCTOR || m.type == PPG_BSDF_PLASTIC)) {
+                ctx->error = who + "roughcoating over a BSDF with a delta component (conductor, plastic) is not supported"; return PPG_ERR_INVALID;
+            }
+            bool finite = std::isfinite(c.eta) && std::isfinite(c.thickness);
+            for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(c.sigma_a[k]) && std::isfinite(c.specular[k]);
+            if (c.kind == 2) finite = finite && std::isfinite(c.alpha);
+            if (!finite) { ctx->error = who + "a value is not finite"; return PPG_ERR_INVALID; }
+            if (!(c.eta > 0) || c.eta == 1.0f) { ctx->error = who + "the interior and exterior indices of refraction must be positive and differ (eta > 0, eta != 1)"; return PPG_ERR_INVALID; }
+            if (c.thickness < 0) { ctx->error = who + "thickness must not be negative"; return PPG_ERR_INVALID; }
+            if (c.sigma_a[0] < 0 || c.sigma_a[1] < 0 || c.sigma_a[2] < 0) { ctx->error = who + "sigma_a must not be negative"; return PPG_ERR_INVALID; }
+            uint32_t bits = (uint32_t)c.kind;
+            int rows = 0;
+            if (c.kind == 2) {
+                if (c.distribution < 0 || c.distribution > 2) { ctx->error = who + "distribution must be 0 (beckmann), 1 (ggx) or 2 (phong)"; return PPG_ERR_INVALID; }
+                if (c.rtrans < 0 || (uint32_t)c.rtrans >= s->n_rtrans || !s->rtrans || s->rtrans_samples < 2) {
+                    ctx->error = who + "rtrans is not a slice of scene.rtrans"; return PPG_ERR_INVALID;
+                }
+                bits |= (uint32_t)c.distribution << PPG_COATF_TYPE_SHIFT;
+                if (c.sample_all || c.distribution == 2) bits |= PPG_COATF_SAMPLE_ALL;  // microfacet.h:141-142
+                rows = c.rtrans - (m.type == PPG_BSDF_ROUGHPLASTIC ? m.rtrans : 0);  // from the slice the material record names (Mat::rt)
+            }
+            // m_specularSamplingWeight (coating.cpp:178-181), once, with the library's own exp: every host gets the same bits
+            float sum = 0.0f;
+            for (int k = 0; k < 3; ++k) sum += ppg_exp(c.sigma_a[k] * (-2 * c.thickness));
+            const float avgAbsorption = sum * (1.0f / 3);
+            const float weight = 1.0f / (avgAbsorption + 1.0f);
+            coatTab[PPG_COAT_STRIDE * (size_t)i + 0] = make_float4(c.eta, c.thickness, weight, __builtin_bit_cast(float, bits));
+            coatTab[PPG_COAT_STRIDE * (size_t)i + 1] = make_float4(c.sigma_a[0], c.sigma_a[1], c.sigma_a[2], c.kind == 2 ? c.alpha : 0.0f);
+            coatTab[PPG_COAT_STRIDE * (size_t)i + 2] = make_float4(c.specular[0], c.specular[1], c.specular[2], __builtin_bit_cast(float, rows));
+            anyCoat = true;
+        }
+    }
+    ctx->scene.coat = nullptr;
+    if (anyCoat) {
+        HIP_CHECK(ctx->d_coat.reserve(coatTab.size()));
+        HIP_CHECK(hipMemcpy(ctx->d_coat.p, coatTab.data(), coatTab.size() * sizeof(float4), hipMemcpyHostToDevice));
+        ctx->scene.coat = ctx->d_coat.p;
+        ctx->fullMaterials = true;
+    }
     ctx->scene.uvs = nullptr; ctx->scene.textures = nullptr;
     if (s->texcoords) {
         std::vector<float2> uv(3 * (size_t)s->n_triangles);
@@ -3772,6 +3836,13 @@ int ppg_set_microfacet(ppg_ctx *ctx, const ppg_microfacet *m, uint32_t n_materia
     return PPG_OK;
 }
 
+int ppg_set_coatings(ppg_ctx *ctx, const ppg_coating *c, uint32_t n_materials) {
+    if (ctx->renderOpen) { ctx->error = "coatings: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (!c) n_materials = 0;
+    ctx->coatings.assign(c, c + n_materials);  // validated against the scene by ppg_set_scene
+    return PPG_OK;
+}
+
 int ppg_set_delta_emitters(ppg_ctx *ctx, const ppg_delta_emitter *em, uint32_t n) {
     if (ctx->renderOpen) { ctx->error = "delta emitters: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
     if (n && !em) { ctx->error = "delta emitters: no list"; return PPG_ERR_INVALID; }
@@ -3860,7 +3931,8 @@ int ppg_debug_bsdf(ppg_ctx *ctx, uint32_t n, const ppg_debug_bsdf_item *items, p
     HIP_CHECK(dItems.fill(items, (size_t)n * sizeof(ppg_debug_bsdf_item)));
     HIP_CHECK(dOut.fill(nullptr, (size_t)n * sizeof(ppg_debug_bsdf_out)));
     const unsigned int block = 64;
-    ppg_launch_debug_bsdf((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const ppg_debug_bsdf_item *)dItems.p, (ppg_debug_bsdf_out *)dOut.p);
+    if (ctx->scene.coat) ppg_launch_debug_bsdf_coat((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const ppg_debug_bsdf_item *)dItems.p, (ppg_debug_bsdf_out *)dOut.p);
+    else ppg_launch_debug_bsdf((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const ppg_debug_bsdf_item *)dItems.p, (ppg_debug_bsdf_out *)dOut.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_bsdf_out), hipMemcpyDeviceToHost));

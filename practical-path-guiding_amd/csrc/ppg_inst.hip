@@ -8,6 +8,9 @@
  * 11..13, compiled with -DPPG_SHAPES=1 -DPPG_MFD=1: the "extended" kernels of scenes whose microfacet list has a general entry
  * (ppg_set_microfacet; ppg_device.h PPG_MFD) — 11 k_shade_ext<NEE, true>, 12 k_tail_ext<false, NEE, true>, 13 k_trace_ext<false, COUNT> (its
  * sort_slice keeps general materials out of the COMMON classes) and the kernel of the test hook ppg_debug_bsdf.
+ * 14..16, compiled with -DPPG_SHAPES=1 -DPPG_MFD=1 -DPPG_COAT=1: the "coat" kernels of scenes with a coating / roughcoating
+ * (ppg_set_coatings; ppg_device.h PPG_COAT) — 14 k_shade_coat<NEE, true>, 15 k_tail_coat<false, NEE, true>, 16 k_trace_coat<false, COUNT>
+ * (its sort_slice keeps coated materials out of the COMMON classes too) and the hook's kernel for such a scene.  The same source as 11..13.
  */
 #include <hip/hip_runtime.h>
 
@@ -17,30 +20,40 @@
 #include "ppg_launch.h"
 
 #ifndef PPG_INST
-#error "compile with -DPPG_INST=0..13"
+#error "compile with -DPPG_INST=0..16"
 #endif
 #if (PPG_INST >= 8) != (PPG_SHAPES != 0)
-#error "units 8..13, and only they, are compiled with -DPPG_SHAPES=1"
+#error "units 8..16, and only they, are compiled with -DPPG_SHAPES=1"
 #endif
 #if (PPG_INST >= 11) != (PPG_MFD != 0)
-#error "units 11..13, and only they, are compiled with -DPPG_MFD=1"
+#error "units 11..16, and only they, are compiled with -DPPG_MFD=1"
+#endif
+#if (PPG_INST >= 14) != (PPG_COAT != 0)
+#error "units 14..16, and only they, are compiled with -DPPG_COAT=1"
+#endif
+#if PPG_COAT
+#define ppg_launch_shade_ext ppg_launch_shade_coat
+#define ppg_launch_tail_ext ppg_launch_tail_coat
+#define ppg_launch_trace_ext ppg_launch_trace_coat
+#define ppg_launch_debug_bsdf ppg_launch_debug_bsdf_coat
+#define k_debug_bsdf k_debug_bsdf_coat
 #endif
 
-#if PPG_INST == 11
+#if PPG_INST == 11 || PPG_INST == 14
 void ppg_launch_shade_ext(int variant, const ShadeLaunch &a) {
     if (variant & 2)
         hipLaunchKernelGGL((k_shade<true, true>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, a.P, a.S, a.T, a.R, a.Q, a.qin, a.small_scene, a.sorted_items);
     else
         hipLaunchKernelGGL((k_shade<false, true>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, a.P, a.S, a.T, a.R, a.Q, a.qin, a.small_scene, a.sorted_items);
 }
-#elif PPG_INST == 12
+#elif PPG_INST == 12 || PPG_INST == 15
 void ppg_launch_tail_ext(int variant, const TailLaunch &a) {
     if (variant & 2)
         hipLaunchKernelGGL((k_tail<false, true, true>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, a.P, a.S, a.T, a.R, a.dense, a.total, a.ticket, a.stats, a.lds_tris, a.longest, a.strag, a.lane_limit);
     else
         hipLaunchKernelGGL((k_tail<false, false, true>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, a.P, a.S, a.T, a.R, a.dense, a.total, a.ticket, a.stats, a.lds_tris, a.longest, a.strag, a.lane_limit);
 }
-#elif PPG_INST == 13
+#elif PPG_INST == 13 || PPG_INST == 16
 #include "../../include/ppg_testhooks.h"
 void ppg_launch_trace_ext(bool count, int grid, size_t lds, hipStream_t stream, const PathState &P, const DevScene &S, const Queues &Q, int qin, int lds_nodes,
                           int lds_tris, unsigned int *sorted, unsigned char *keys) {

@@ -469,6 +469,9 @@ struct SortArgs {
 #if PPG_MFD
     const float4 *mfd;        // DevScene::mfd: a material with a general microfacet entry is never a COMMON class
 #endif
+#if PPG_COAT
+    const float4 *coat;       // DevScene::coat: nor is a coated one
+#endif
 };
 D SortArgs sort_args(const PathState &P, const DevScene &S, const Queues &Q, unsigned int b, unsigned int *sorted, unsigned char *keys) {
     SortArgs a;
@@ -478,6 +481,9 @@ D SortArgs sort_args(const PathState &P, const DevScene &S, const Queues &Q, uns
     a.n_paths = P.n_paths; a.n_tris = S.n_tris;
 #if PPG_MFD
     a.mfd = S.mfd;
+#endif
+#if PPG_COAT
+    a.coat = S.coat;
 #endif
     return a;
 }
@@ -500,7 +506,11 @@ D void sort_slice(const SortArgs &a, const Work &work, unsigned int b, unsigned 
                     const int type = (int)mr[0].w, flags = __float_as_int(mr[2].w);
                     const float4 tw = mr[5];  // (texture word, specular, alpha, opacity texture)
                     const unsigned int tex = __float_as_uint(tw.x), slots = __float_as_uint(tw.y) | __float_as_uint(tw.z) | __float_as_uint(tw.w);
-#if PPG_MFD
+#if PPG_COAT
+                    const bool general = (a.mfd && (__float_as_uint(a.mfd[m].y) & PPG_MFDF_GENERAL) != 0u) ||
+                                         (a.coat && (__float_as_uint(a.coat[PPG_COAT_STRIDE * (size_t)m].w) & PPG_COATF_KIND) != 0u);
+                    if ((flags & PPG_MAT_MASK) || (tex >> 16) || slots || general) key = 13u;
+#elif PPG_MFD
                     const bool general = a.mfd && (__float_as_uint(a.mfd[m].y) & PPG_MFDF_GENERAL) != 0u;
                     if ((flags & PPG_MAT_MASK) || (tex >> 16) || slots || general) key = 13u;
 #else

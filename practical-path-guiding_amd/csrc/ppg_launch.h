@@ -89,6 +89,13 @@ void ppg_launch_trace_ext(bool count, int grid, size_t lds, hipStream_t stream, 
 struct ppg_debug_bsdf_item;
 struct ppg_debug_bsdf_out;
 void ppg_launch_debug_bsdf(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out);
+// Scenes with a coated material (ppg_set_coatings): the same again built with -DPPG_SHAPES=1 -DPPG_MFD=1 -DPPG_COAT=1, the "coat" family —
+// k_shade_coat<NEE, true>, k_tail_coat<false, NEE, true>, k_trace_coat<false, COUNT> with the hook's kernel for such a scene
+void ppg_launch_shade_coat(int variant, const ShadeLaunch &a);
+void ppg_launch_tail_coat(int variant, const TailLaunch &a);
+void ppg_launch_trace_coat(bool count, int grid, size_t lds, hipStream_t stream, const PathState &P, const DevScene &S, const Queues &Q, int qin, int lds_nodes,
+                           int lds_tris, unsigned int *sorted, unsigned char *keys);
+void ppg_launch_debug_bsdf_coat(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out);
 // k_shade<false, FULL, MSET_COMMON> over the front part of the sorted slices (a.qin = QIN_SORTED_COMMON)
 void ppg_launch_shade_common(const ShadeLaunch &a);
 

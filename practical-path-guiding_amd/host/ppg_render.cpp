@@ -134,7 +134,12 @@ static bool loadSceneChecked(const char *path, SceneData &s) {
         s.microfacet.resize(nm);
         f.read((char *)s.microfacet.data(), (std::streamsize)((size_t)nm * sizeof(ppg_microfacet)));
     }
-    if (hdr[5] >> 12) return false;  // a block this reader does not know
+    if (hdr[5] & 4096) {  // bit 12: the coatings (n_materials x ppg_coating), only when a material is coated
+        if (!fits((uint64_t)nm * sizeof(ppg_coating))) return false;
+        s.coatings.resize(nm);
+        f.read((char *)s.coatings.data(), (std::streamsize)((size_t)nm * sizeof(ppg_coating)));
+    }
+    if (hdr[5] >> 13) return false;  // a block this reader does not know
     return (bool)f;
 }
 
@@ -206,7 +211,7 @@ static bool saveScene(const char *path, const SceneData &s) {
                              s.normals.empty() ? 0u : 1u, (s.hasEnvironment ? 1u : 0u) | (s.rtrans.empty() ? 0u : 2u) | (s.spheres.empty() ? 0u : 4u) | (s.hasEnvmap ? 8u : 0u) |
                                  (s.texcoords.empty() ? 0u : 16u) | (s.textures.empty() ? 0u : 32u) | (s.hasRFilter ? 64u : 0u) | (s.hasLens ? 128u : 0u) |
                                  (s.deltaEmitters.empty() ? 0u : 256u) | (s.materialTextures.empty() ? 0u : 512u) | (s.shapes.empty() ? 0u : 1024u) |
-                                 (s.microfacet.empty() ? 0u : 2048u)};
+                                 (s.microfacet.empty() ? 0u : 2048u) | (s.coatings.empty() ? 0u : 4096u)};
     f.write("PPGS", 4); f.write((const char *)hdr, sizeof hdr);
     f.write((const char *)s.positions.data(), s.positions.size() * 4);
     if (!s.normals.empty()) f.write((const char *)s.normals.data(), s.normals.size() * 4);
@@ -257,6 +262,7 @@ static bool saveScene(const char *path, const SceneData &s) {
         f.write((const char *)s.shapes.data(), (std::streamsize)(n * sizeof(ppg_shape)));
     }
     if (!s.microfacet.empty()) f.write((const char *)s.microfacet.data(), (std::streamsize)(s.microfacet.size() * sizeof(ppg_microfacet)));
+    if (!s.coatings.empty()) f.write((const char *)s.coatings.data(), (std::streamsize)(s.coatings.size() * sizeof(ppg_coating)));
     return (bool)f;
 }
 
@@ -357,6 +363,7 @@ int main(int argc, char **argv) {
         core.setMaterialTextures(scene.materialTextures.data(), scene.materialTextures.size());
         core.setShapes(scene.shapes.data(), scene.shapes.size());
         core.setMicrofacet(scene.microfacet.data(), scene.microfacet.size());
+        core.setCoatings(scene.coatings.data(), scene.coatings.size());
         core.setSeed((uint64_t)std::stoull(props.getString("seed", "0")));
         std::string dest = out;
         const size_t dot = dest.find_last_of('.');

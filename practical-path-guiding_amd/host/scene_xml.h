@@ -762,12 +762,12 @@ public:
             out.scene.lens.aperture_radius = r; out.scene.lens.focus_distance = focus;
         }
         // bsdfs
-        for (auto &b : root.children) if (b.tag == "bsdf" && b.attr("id")) { const ppg_material bm = makeBsdfTop(b, out); m_byId[b.get("id")] = intern(bm, out, m_mfd); }
+        for (auto &b : root.children) if (b.tag == "bsdf" && b.attr("id")) { const ppg_material bm = makeBsdfTop(b, out); m_byId[b.get("id")] = intern(bm, out, m_mfd, m_coat); }
         {   // an id may also sit on a NESTED bsdf (KITCHEN references the twosided element inside a bumpmap): every element with an id is a named object
             std::function<void(const XmlNode &)> walk = [&](const XmlNode &n) {
                 for (auto &c : n.children) {
                     if (c.tag != "bsdf") continue;
-                    if (c.attr("id") && !m_byId.count(c.get("id"))) { const ppg_material bm = makeBsdfTop(c, out); m_byId[c.get("id")] = intern(bm, out, m_mfd); }
+                    if (c.attr("id") && !m_byId.count(c.get("id"))) { const ppg_material bm = makeBsdfTop(c, out); m_byId[c.get("id")] = intern(bm, out, m_mfd, m_coat); }
                     walk(c);
                 }
             };
@@ -950,7 +950,7 @@ public:
             }
             int mat = -1;
             for (auto &c : sh.children) {
-                if (c.tag == "bsdf") { const ppg_material bm = makeBsdfTop(c, out); mat = (int)intern(bm, out, m_mfd); }
+                if (c.tag == "bsdf") { const ppg_material bm = makeBsdfTop(c, out); mat = (int)intern(bm, out, m_mfd, m_coat); }
                 else if (c.tag == "ref") {
                     auto it = m_byId.find(c.get("id"));
                     if (it == m_byId.end()) throw std::runtime_error("<ref id=\"" + c.get("id") + "\">: no such bsdf");
@@ -1026,6 +1026,7 @@ public:
             for (size_t t = 0; t < m.indices.size() / 3; ++t) { S.triMaterial.push_back(p.mat); S.triEmitter.push_back(p.em); }
         }
         for (const ppg_microfacet &g : m_mfdOf) if (g.general) { S.microfacet = m_mfdOf; break; }  // one entry per material, or none
+        for (const ppg_coating &c : m_coatOf) if (c.kind) { S.coatings = m_coatOf; break; }  // likewise
         out.warnings.insert(out.warnings.end(), m_lenientNotes.begin(), m_lenientNotes.end());
         return out;
     }
@@ -1042,6 +1043,8 @@ private:
     std::vector<std::string> m_matKeys;
     std::vector<ppg_microfacet> m_mfdOf;  // per material: its general microfacet entry (all zero: none)
     mutable ppg_microfacet m_mfd{};       // ... of the BSDF makeBsdf built last
+    std::vector<ppg_coating> m_coatOf;    // per material: its coating / roughcoating (kind 0: none)
+    mutable ppg_coating m_coat{};         // ... of the BSDF makeBsdf built last
 
     void collectDefaults(const XmlNode &n) {
         if (n.tag == "default" && n.attr("name") && !m_params.count(n.get("name"))) m_params[n.get("name")] = n.get("value");
@@ -1461,7 +1464,7 @@ private:
         std::transform(distr.begin(), distr.end(), distr.begin(), ::tolower);
         if (distr != "ggx" && distr != "beckmann" && distr != "phong" && distr != "as")
             throw std::runtime_error(t + ": Specified an invalid distribution \"" + distr + "\", must be \"beckmann\", \"ggx\", or \"phong\"/\"as\"!");
-        if ((distr == "phong" || distr == "as") && t != "roughplastic")  // as ppg_host/mitsuba_xml.py: phong from a scene file on roughplastic only
+        if ((distr == "phong" || distr == "as") && t != "roughplastic" && t != "roughcoating")  // as ppg_host/mitsuba_xml.py: phong from a scene file on roughplastic only
             throw std::runtime_error(t + ": distribution '" + distr + "' is not supported by the scene loaders on this plug-in (ggx, beckmann; phong on roughplastic)");
         if (distr == "as") distr = "phong";
         for (auto &c : e.children)
@@ -1519,8 +1522,66 @@ private:
         }
         for (int c = 0; c < 3; ++c) { m.eta[c] = eta[c] / ext; m.k[c] = k[c] / ext; }
     }
-    // (the general microfacet entry of the BSDF it built last — at most one rough plug-in sits inside the adapters — is left in m_mfd)
-    ppg_material makeBsdfTop(const XmlNode &e, LoadedScene &out) const { m_mfd = ppg_microfacet{}; return makeBsdf(e, true, out); }
+    // (the general microfacet entry of the BSDF it built last — at most one rough plug-in sits inside the adapters — is left in m_mfd, its
+    // coating / roughcoating in m_coat)
+    ppg_material makeBsdfTop(const XmlNode &e, LoadedScene &out) const { m_mfd = ppg_microfacet{}; m_coat = ppg_coating{}; return makeBsdf(e, true, out); }
+    // The nested BSDF's record, with the adapter's parameters left in m_coat (ppg_coating; the same rules as ppg_host/mitsuba_xml.py).  The
+    // nesting order this build knows is bumpmap(mask(twosided(coating(leaf)))); the plug-ins' parameters are constants.
+    ppg_material coated(const XmlNode &e, std::map<std::string, std::string> &p, const std::string &t, const std::vector<const XmlNode *> &in, LoadedScene &out) const {
+        if (in.size() != 1) throw std::runtime_error(t + ": exactly one nested bsdf is required (found " + std::to_string(in.size()) + ")");
+        const std::string it = in[0]->get("type");
+        if (it == "coating" || it == "roughcoating" || it == "twosided" || it == "mask" || it == "bumpmap")
+            throw std::runtime_error(t + "(" + it + ") is not supported: the nesting order is bumpmap(mask(twosided(coating(..))))");
+        for (auto &c : e.children)
+            if ((c.tag == "texture" || c.tag == "ref") && c.attr("name") &&
+                (c.get("name") == "sigmaA" || c.get("name") == "specularReflectance" || c.get("name") == "alpha" || c.get("name") == "alphaU" || c.get("name") == "alphaV"))
+                throw std::runtime_error(t + ": a texture on '" + c.get("name") + "' is not supported");
+        ppg_material m = makeBsdf(*in[0], false, out);
+        if (m.type == PPG_BSDF_DIELECTRIC || m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_ROUGHDIELECTRIC)
+            throw std::runtime_error(t + "(" + it + "): a coat on dielectric, thindielectric or roughdielectric is not supported");
+        if (t == "roughcoating" && (m.type == PPG_BSDF_MIRROR || m.type == PPG_BSDF_CONDUCTOR || m.type == PPG_BSDF_PLASTIC))
+            throw std::runtime_error("roughcoating(" + it + "): a roughcoating over a BSDF with a delta component (conductor, plastic) is not supported");
+        const double intIOR = lookupIOR(p, "intIOR", "bk7"), extIOR = lookupIOR(p, "extIOR", "air");
+        if (intIOR < 0 || extIOR < 0 || intIOR == extIOR) throw std::runtime_error(t + ": The interior and exterior indices of refraction must be positive and differ!");
+        ppg_coating c{};
+        c.kind = t == "coating" ? 1 : 2;
+        c.eta = (float)(intIOR / extIOR);
+        c.thickness = p.count("thickness") ? std::stof(p["thickness"]) : 1.0f;
+        colour(e, "sigmaA", 0.0f, c.sigma_a);
+        colour(e, "specularReflectance", 1.0f, c.specular);
+        if (!(c.eta > 0 && c.eta != 1.0f)) throw std::runtime_error(t + ": The interior and exterior indices of refraction must be positive and differ!");
+        bool finite = std::isfinite(c.eta) && std::isfinite(c.thickness);
+        for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(c.sigma_a[k]) && std::isfinite(c.specular[k]);
+        if (!finite) throw std::runtime_error(t + ": a parameter is not finite");
+        if (c.thickness < 0 || c.sigma_a[0] < 0 || c.sigma_a[1] < 0 || c.sigma_a[2] < 0) throw std::runtime_error(t + ": thickness and sigmaA must not be negative");
+        if (c.kind == 2) {
+            const ppg_microfacet nested = m_mfd;  // (microfacet() leaves the layer's own entry there)
+            ppg_material tmp{};
+            const std::string distr = microfacet(e, p, t, tmp);
+            const ppg_microfacet own = m_mfd;
+            m_mfd = nested;
+            if (own.general && std::max(own.alpha_v, 1e-4f) != std::max(tmp.alpha, 1e-4f))  // roughcoating.cpp:143-145 (the plug-in's own words)
+                throw std::runtime_error("roughcoating: The 'roughplastic' plugin currently does not support anisotropic microfacet distributions!");
+            if (!std::isfinite(tmp.alpha)) throw std::runtime_error("roughcoating: a parameter is not finite");
+            c.alpha = tmp.alpha;
+            c.distribution = distr == "beckmann" ? 0 : (distr == "ggx" ? 1 : 2);
+            c.sample_all = own.general && own.sample_all ? 1 : 0;
+            char key[96];  // the reduction roughplastic uses, interned with its slices
+            snprintf(key, sizeof key, "%s/%.9g/%.9g", distr.c_str(), c.alpha, c.eta);
+            auto f = m_rtIndex.find(key);
+            if (f == m_rtIndex.end()) {
+                std::vector<float> slice;
+                try { slice = roughplasticSlice(distr, c.alpha, c.eta, m_dataDir); }
+                catch (const std::exception &ex) { throw std::runtime_error(t + ": " + ex.what()); }
+                out.scene.rtransSamples = (uint32_t)slice.size() - 1;
+                f = m_rtIndex.emplace(key, (int)(out.scene.rtrans.size() / slice.size())).first;
+                out.scene.rtrans.insert(out.scene.rtrans.end(), slice.begin(), slice.end());
+            }
+            c.rtrans = f->second;
+        }
+        m_coat = c;
+        return m;
+    }
     ppg_material makeBsdf(const XmlNode &e, bool allowWrap, LoadedScene &out) const {
         std::string t = e.get("type");
         auto p = props(e);
@@ -1606,7 +1667,19 @@ private:
             }
             return m;
         }
-        if (!m_strict && (t == "bumpmap" || t == "coating" || t == "roughcoating" || t == "normalmap")) {  // adapters around one nested BSDF: render the nested one
+        if (t == "coating" || t == "roughcoating") {  // SmoothCoating (coating.cpp:109-200), RoughCoating (roughcoating.cpp:114-227): the innermost adapter
+            auto in = inner();
+            try { return coated(e, p, t, in, out); }
+            catch (const std::runtime_error &ex) {
+                if (m_strict) throw;
+                m_coat = ppg_coating{};
+                if (in.size() == 1) {  // where a strict load refuses this coat, a lenient one renders the nested BSDF
+                    out.warnings.push_back("bsdf '" + t + "' dropped around its nested bsdf (" + ex.what() + ")");
+                    return makeBsdf(*in[0], allowWrap, out);
+                }
+            }
+        }
+        if (!m_strict && (t == "bumpmap" || t == "normalmap")) {  // adapters around one nested BSDF: render the nested one
             auto in = inner();
             if (in.size() == 1) { out.warnings.push_back("bsdf '" + t + "' dropped around its nested bsdf"); return makeBsdf(*in[0], allowWrap, out); }
         }
@@ -1620,7 +1693,7 @@ public:
     // The <bsdf> element carrying `id` (at any nesting depth: every element with an id is a named object in Mitsuba) as a ppg_material;
     // rough-transmittance slices it needs are appended to out.scene.rtrans.  Used by the Mitsuba plug-in shim
     // (mitsuba_plugin/guided_path_hip.cpp), which cannot reach the nested BSDF of an adapter through Mitsuba's API.
-    bool bsdfById(const std::string &id, LoadedScene &out, ppg_material &m, ppg_microfacet *g = nullptr) {
+    bool bsdfById(const std::string &id, LoadedScene &out, ppg_material &m, ppg_microfacet *g = nullptr, ppg_coating *k = nullptr) {
         std::ifstream f(m_path, std::ios::binary);
         if (!f) throw std::runtime_error("cannot open '" + m_path + "'");
         std::stringstream ss; ss << f.rdbuf();
@@ -1641,15 +1714,19 @@ public:
         m = makeBsdfTop(*found, out);
         if (g) *g = m_mfd;
         else if (m_mfd.general) throw std::runtime_error("bsdf '" + id + "': alphaU / alphaV, distribution = phong and sampleVisible = false are not carried through this interface");
+        if (k) *k = m_coat;
+        else if (m_coat.kind) throw std::runtime_error("bsdf '" + id + "': coating / roughcoating are not carried through this interface");
         return true;
     }
     // The ppg_material of a <bsdf> element that is not in a file: the plug-in shim builds one from a flat plug-in's Properties (a BSDF
     // without an id cannot be looked up in the scene file) and gets exactly what the scene loader makes of the same parameters.
-    ppg_material bsdfFromElement(const XmlNode &e, LoadedScene &out, ppg_microfacet *g = nullptr) {
+    ppg_material bsdfFromElement(const XmlNode &e, LoadedScene &out, ppg_microfacet *g = nullptr, ppg_coating *k = nullptr) {
         m_base = ".";
         const ppg_material m = makeBsdfTop(e, out);
         if (g) *g = m_mfd;
         else if (m_mfd.general) throw std::runtime_error("alphaU / alphaV, distribution = phong and sampleVisible = false are not carried through this interface");
+        if (k) *k = m_coat;
+        else if (m_coat.kind) throw std::runtime_error("coating / roughcoating are not carried through this interface");
         return m;
     }
 private:
@@ -1657,13 +1734,15 @@ private:
     bool anisotropic(uint32_t mat, const LoadedScene &out) const {
         return m_mfdOf[mat].general && std::max(m_mfdOf[mat].alpha_v, 1e-4f) != std::max(out.scene.materials[mat].alpha, 1e-4f);
     }
-    uint32_t intern(const ppg_material &m, LoadedScene &out, const ppg_microfacet &g = ppg_microfacet{}) {
+    uint32_t intern(const ppg_material &m, LoadedScene &out, const ppg_microfacet &g = ppg_microfacet{}, const ppg_coating &coat = ppg_coating{}) {
         std::string key((const char *)&m, sizeof m);
         key.append((const char *)&g, sizeof g);
+        key.append((const char *)&coat, sizeof coat);
         for (size_t i = 0; i < m_matKeys.size(); ++i) if (m_matKeys[i] == key) return (uint32_t)i;
         m_matKeys.push_back(key);
         out.scene.materials.push_back(m);
         m_mfdOf.push_back(g);
+        m_coatOf.push_back(coat);
         return (uint32_t)m_matKeys.size() - 1;
     }
 };
@@ -1676,19 +1755,22 @@ struct BsdfParam { std::string name, tag, value; };
 // g: receives the BSDF's general microfacet entry (ppg_set_microfacet; all zero: none); without it such a BSDF is refused
 inline bool bsdfFromProperties(const std::string &plugin, const std::vector<BsdfParam> &params, const std::string &dataDir, SceneData &data, ppg_material &m, std::string &why,
                                ppg_microfacet *g = nullptr);
+// (a coating / roughcoating is an adapter and has an id or a parent with one: it comes through bsdfById, k receiving its ppg_coating with
+// rtrans already moved to the row of data.rtrans)
 
 inline bool bsdfById(const std::string &scenePath, const std::string &id, const std::string &dataDir, SceneData &data, ppg_material &m, std::string &why,
-                     ppg_microfacet *g = nullptr) {
+                     ppg_microfacet *g = nullptr, ppg_coating *k = nullptr) {
     try {
         SceneXmlLoader loader(scenePath, {}, true, 0, 0, dataDir);
         LoadedScene tmp;
-        if (!loader.bsdfById(id, tmp, m, g)) return false;
+        if (!loader.bsdfById(id, tmp, m, g, k)) return false;
         if (!tmp.scene.rtrans.empty()) {
             if (data.rtransSamples && data.rtransSamples != tmp.scene.rtransSamples) { why = "rough-transmittance tables of different resolutions"; return false; }
             const uint32_t have = data.rtransSamples ? (uint32_t)(data.rtrans.size() / (data.rtransSamples + 1)) : 0u;
             data.rtransSamples = tmp.scene.rtransSamples;
             data.rtrans.insert(data.rtrans.end(), tmp.scene.rtrans.begin(), tmp.scene.rtrans.end());
             if (m.type == PPG_BSDF_ROUGHPLASTIC) m.rtrans += (int32_t)have;
+            if (k && k->kind == 2) k->rtrans += (int32_t)have;
         }
         return true;
     } catch (const std::exception &e) {

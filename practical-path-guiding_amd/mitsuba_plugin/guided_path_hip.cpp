@@ -86,6 +86,13 @@ public:
             else data.microfacet.clear();
             m_core.setMicrofacet(data.microfacet.data(), data.microfacet.size());
         }
+        {   /* the coating / roughcoating adapters materialOf() collected, likewise */
+            bool any = false;
+            for (size_t k = 0; k < data.coatings.size(); ++k) any = any || data.coatings[k].kind != 0;
+            if (any) data.coatings.resize(data.materials.size());
+            else data.coatings.clear();
+            m_core.setCoatings(data.coatings.data(), data.coatings.size());
+        }
         Log(EInfo, "Starting render job (%ix%i, MI355X, %i triangles, %i analytic spheres) ..", film->getCropSize().x, film->getCropSize().y,
             (int) (data.indices.size() / 3), (int) data.spheres.size());
         /* create → scene → render; SD-tree dumps to "<dest>-NN.sdt" (GP:1192-1195) */
@@ -127,14 +134,15 @@ private:
         if (it != cache.end()) return it->second;
         ppg_material m; memset(&m, 0, sizeof m);
         ppg_microfacet g; memset(&g, 0, sizeof g);   /* alphaU / alphaV, phong, sampleVisible = false (ppg_set_microfacet) */
+        ppg_coating coat; memset(&coat, 0, sizeof coat);   /* a coating / roughcoating around it (ppg_set_coatings) */
         const Properties &p = bsdf->getProperties();
         const std::string plugin = p.getPluginName();
         bool ok = false;
-        if (plugin == "twosided" || plugin == "mask" || plugin == "bumpmap" || p.getID() != "unnamed") {
+        if (plugin == "twosided" || plugin == "mask" || plugin == "bumpmap" || plugin == "coating" || plugin == "roughcoating" || p.getID() != "unnamed") {
             /* the nested BSDF is not reachable through Mitsuba's API: read the element with this id from the scene file.  ppg::xml::SceneLoader
                is the loader behind `ppg_render scene.xml`; bsdfById() returns the ppg_material it makes of that <bsdf> element (incl. the
                rough-transmittance slice of a roughplastic, appended to data.rtrans, and its textures, appended to data.textures) */
-            ok = ppg::xml::bsdfById(scene->getSourceFile().string(), p.getID(), m_dataDir(), data, m, why, &g);
+            ok = ppg::xml::bsdfById(scene->getSourceFile().string(), p.getID(), m_dataDir(), data, m, why, &g, &coat);
         }
         if (!ok) {
             /* A flat plug-in without an id: its Properties are the parameters the scene file gave it.  They are handed to the scene loader's own
@@ -174,6 +182,8 @@ private:
         data.materials.push_back(m);
         data.microfacet.resize(data.materials.size());   /* (zero entries for the materials before it) */
         data.microfacet.back() = g;
+        data.coatings.resize(data.materials.size());
+        data.coatings.back() = coat;
         cache[bsdf] = (int) data.materials.size() - 1;
         return cache[bsdf];
     }

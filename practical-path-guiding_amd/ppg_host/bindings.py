@@ -63,7 +63,8 @@ class Config(C.Structure):
 class Material(C.Structure):
     """ppg_material (include/ppg.h).  Scene descriptions carry materials as dicts: type, reflectance and — by type —
     specular, alpha, eta (3 values, or one number for plastic / dielectric), k, twosided, nonlinear, opacity (a mask adapter), distribution ("ggx" | "beckmann"), rtrans (roughplastic: row of SceneDesc.rtrans).
-    The rest of the microfacet model travels beside it (Microfacet): alpha_v, distribution = "phong", sample_visible."""
+    The rest of the microfacet model travels beside it (Microfacet): alpha_v, distribution = "phong", sample_visible; so does a coating /
+    roughcoating adapter around the BSDF (Coating): coating = dict(kind, eta, ...)."""
     _fields_ = [("type", C.c_int32), ("reflectance", C.c_float * 3), ("specular", C.c_float * 3), ("alpha", C.c_float),
                 ("eta", C.c_float * 3), ("k", C.c_float * 3), ("flags", C.c_int32), ("rtrans", C.c_int32),
                 ("opacity", C.c_float * 3), ("texture", C.c_uint32)]
@@ -131,6 +132,61 @@ class Microfacet(C.Structure):
         o.sample_all = 0 if m.get("sample_visible", True) else 1
         o.alpha_v_texture = 0 if m.get("alpha_v_texture") is None else int(m["alpha_v_texture"]) + 1
         return o
+
+
+class Coating(C.Structure):
+    """ppg_coating (include/ppg.h): per material, Mitsuba's `coating` / `roughcoating` adapter around its BSDF (inside twosided / mask /
+    bumpmap).  Material dicts state it as coating = dict(kind = "coating" | "roughcoating" (or 1 | 2; 0: none), eta (intIOR / extIOR,
+    default bk7 / air), thickness (1), sigma_a (0), specular (1) and, for a roughcoating, alpha (0.1), distribution ("beckmann" | "ggx" |
+    "phong"), sample_visible (True) and slice (or rtrans): the layer's row of SceneDesc.rtrans —
+    rtrans.roughplastic_slice(distribution, alpha, eta, data_dir)).  A dict without the key gets an all-zero entry."""
+    _fields_ = [("kind", C.c_int32), ("eta", C.c_float), ("thickness", C.c_float), ("sigma_a", C.c_float * 3), ("specular", C.c_float * 3),
+                ("alpha", C.c_float), ("distribution", C.c_int32), ("sample_all", C.c_int32), ("rtrans", C.c_int32), ("_reserved", C.c_uint32 * 3)]
+
+    KINDS = {"none": 0, "coating": 1, "roughcoating": 2}
+    DISTRIBUTIONS = {"beckmann": 0, "ggx": 1, "phong": 2, "as": 2}
+    BK7_OVER_AIR = 1.5046 / 1.000277  # ior.h: the plug-ins' default intIOR / extIOR
+
+    @classmethod
+    def from_dict(cls, m):
+        """m: a material dict (its `coating` key) or the coating dict itself"""
+        c = m if (m is not None and "kind" in m) else (m or {}).get("coating")
+        o = cls()
+        if c is None:
+            return o
+        def three(v, default):
+            v = default if v is None else v
+            v = [v] * 3 if np.isscalar(v) else list(v)
+            return [float(np.float32(x)) for x in v]
+        k = c.get("kind", 1)
+        o.kind = cls.KINDS[k] if isinstance(k, str) else int(k)
+        o.eta = float(np.float32(c.get("eta", cls.BK7_OVER_AIR)))
+        o.thickness = float(c.get("thickness", 1.0))
+        o.sigma_a[:] = three(c.get("sigma_a"), 0.0)
+        o.specular[:] = three(c.get("specular"), 1.0)
+        if o.kind == 2:
+            o.alpha = float(c.get("alpha", 0.1))
+            d = c.get("distribution", "beckmann")
+            o.distribution = cls.DISTRIBUTIONS[d] if isinstance(d, str) else int(d)
+            o.sample_all = 0 if c.get("sample_visible", True) else 1
+            o.rtrans = int(c.get("rtrans", c.get("slice", 0)))  # (an index, not the slice's samples)
+        return o
+
+    def as_dict(self):
+        """the material dict's `coating` value (None for kind 0)"""
+        if self.kind == 0:
+            return None
+        d = dict(kind={1: "coating", 2: "roughcoating"}.get(self.kind, self.kind), eta=float(self.eta), thickness=float(self.thickness),
+                 sigma_a=[float(v) for v in self.sigma_a], specular=[float(v) for v in self.specular])
+        if self.kind == 2:
+            d.update(alpha=float(self.alpha), distribution={0: "beckmann", 1: "ggx", 2: "phong"}.get(self.distribution, self.distribution),
+                     sample_visible=not self.sample_all, slice=int(self.rtrans))
+        return d
+
+
+def has_coatings(desc):
+    """Whether a material of `desc` carries a `coating` entry (what the CPU oracle does not implement)."""
+    return any(m.get("coating") is not None for m in desc.materials)
 
 
 def has_general_microfacet(desc):
@@ -554,6 +610,12 @@ class Engine:
             self.set_microfacet(desc.materials if has_general_microfacet(desc) else [])
         elif has_general_microfacet(desc):
             raise NotImplementedError("%s: alpha_v, distribution = phong and sample_visible = False are not implemented here" % self.prefix)
+        # the coatings, likewise (a description may also state the list itself, as `coatings`: Coating records or dicts)
+        if self.prefix == "ppg_":
+            explicit = getattr(desc, "coatings", None)
+            self.set_coatings(explicit if explicit is not None else (desc.materials if has_coatings(desc) else []))
+        elif has_coatings(desc):
+            raise NotImplementedError("%s: the coating / roughcoating adapters are not implemented here" % self.prefix)
         self._call("set_scene", C.byref(s))
         self.width, self.height = cam["width"], cam["height"]
         # the film's reconstruction filter comes with the scene description (None / absent: the default box)
@@ -627,6 +689,15 @@ class Engine:
         for i, d in enumerate(entries):
             arr[i] = d if isinstance(d, Microfacet) else Microfacet.from_dict(d)
         self._call("set_microfacet", arr, C.c_uint32(len(entries)))
+
+    def set_coatings(self, entries):
+        """ppg_set_coatings: one entry per material — a material dict (its `coating` key), a coating dict or a Coating; an empty list clears
+        it.  Takes effect at, and is validated by, the next set_scene."""
+        entries = list(entries or [])
+        arr = (Coating * max(1, len(entries)))()
+        for i, d in enumerate(entries):
+            arr[i] = d if isinstance(d, Coating) else Coating.from_dict(d)
+        self._call("set_coatings", arr, C.c_uint32(len(entries)))
 
     def debug_bsdf(self, material, wi, wo, sample, key=None, uv=None):
         """ppg_debug_bsdf (include/ppg_testhooks.h): the render's mat_eval / mat_pdf / mat_sample on material(s) `material` of the scene, per

@@ -1023,7 +1023,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         distr = str(p.get("distribution", "beckmann")).lower()
         if distr not in ("beckmann", "ggx", "phong", "as"):
             raise SceneError('%s: Specified an invalid distribution "%s", must be "beckmann", "ggx", or "phong"/"as"!' % (what, distr))
-        if distr in ("phong", "as") and what != "roughplastic":
+        if distr in ("phong", "as") and what not in ("roughplastic", "roughcoating"):
             # the XML loaders read the Phong / Ashikhmin-Shirley distribution on roughplastic only: tests/test_mitsuba_xml.py pins its refusal
             # on roughconductor.  The other two plug-ins get it through material dicts, flat scene files and the C-ABI.
             raise SceneError("%s: distribution %r is not supported by the scene loaders on this plug-in (ggx, beckmann; phong on roughplastic)" % (what, distr))
@@ -1102,7 +1102,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 if m["type"] in (6, 7, 8):
                     raise SceneError("twosided(dielectric): only BRDFs can be two-sided (twosided.cpp:84-88)")
                 if m["type"] == 0 and not m.get("_substituted"):
-                    return dict({k: v for k, v in m.items() if k in TEXTURE_KEYS}, type=1, reflectance=m["reflectance"])
+                    return dict({k: v for k, v in m.items() if k in TEXTURE_KEYS + ("coating",)}, type=1, reflectance=m["reflectance"])
                 return dict(m, twosided=True)
             t = "twosided(%s)" % ",".join(c.get("type", "?") for c in inner)
         elif t == "mask" and allow_twosided:
@@ -1112,7 +1112,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 if "opacity" in m:
                     raise SceneError("mask(mask(...)) is not supported")
                 if m["type"] == 1:
-                    m = dict({k: v for k, v in m.items() if k in TEXTURE_KEYS}, type=0, reflectance=m["reflectance"], twosided=True)
+                    m = dict({k: v for k, v in m.items() if k in TEXTURE_KEYS + ("coating",)}, type=0, reflectance=m["reflectance"], twosided=True)
                 return textured(dict(m), "opacity", 0.5, "opacity", "opacity_texture")
             t = "mask(%s)" % ",".join(c.get("type", "?") for c in inner)
         elif t == "conductor":
@@ -1160,6 +1160,16 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             if int_ior < 0 or ext_ior < 0 or int_ior == ext_ior:
                 raise SceneError("roughdielectric: the interior and exterior indices of refraction must be positive and differ")
             return microfacet(elem, p, specular(textured(dict(type=8, eta=float(f32(int_ior / ext_ior))), "specularReflectance", 1.0), "specularTransmittance"), t)
+        if t in ("coating", "roughcoating"):  # SmoothCoating (coating.cpp:109-200), RoughCoating (roughcoating.cpp:114-227): the innermost adapter
+            inner = [c for c in elem if c.tag == "bsdf"]
+            try:
+                return coated(elem, p, t, inner)
+            except SceneError as e:
+                if strict:
+                    raise
+                if len(inner) == 1:  # where a strict load refuses this coat, a lenient one renders the nested BSDF
+                    warnings.append("bsdf %r dropped around its nested bsdf (%s)" % (t, e))
+                    return make_bsdf(inner[0], allow_twosided)
         if t == "bumpmap":  # BumpMap (bumpmap.cpp:60-133): one nested BSDF + one displacement texture, the outermost adapter
             inner = [c for c in elem if c.tag == "bsdf"]
             disp = [c for c in elem if c.tag in ("texture", "ref") and (c.tag == "texture" or c.get("id") in tex_by_id)]
@@ -1176,7 +1186,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                         raise
                     warnings.append("bump map dropped around its nested bsdf (%s)" % e)
                     return m
-        if not strict and t in ("bumpmap", "coating", "roughcoating", "normalmap"):  # adapters around one nested BSDF: render the nested one
+        if not strict and t in ("bumpmap", "normalmap"):  # adapters around one nested BSDF: render the nested one
             inner = [c for c in elem if c.tag == "bsdf"]
             if len(inner) == 1:
                 warnings.append("bsdf %r dropped around its nested bsdf" % t)
@@ -1188,9 +1198,58 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         warnings.append("bsdf %r replaced by diffuse(0.5)" % t)
         return dict(type=0, reflectance=(0.5, 0.5, 0.5), _substituted=True)
 
+    def coated(elem, p, t, inner):
+        """the nested BSDF's dict with the adapter's parameters under `coating` (bindings.Coating).  The nesting order this build knows is
+        bumpmap(mask(twosided(coating(leaf)))); the plug-ins' parameters are constants."""
+        from . import rtrans as _rt
+        if len(inner) != 1:
+            raise SceneError("%s: exactly one nested bsdf is required (found %d)" % (t, len(inner)))
+        it = inner[0].get("type")
+        if it in ("coating", "roughcoating", "twosided", "mask", "bumpmap"):
+            raise SceneError("%s(%s) is not supported: the nesting order is bumpmap(mask(twosided(coating(..))))" % (t, it))
+        for c in elem:
+            if c.tag in ("texture", "ref") and c.get("name") in ("sigmaA", "specularReflectance", "alpha", "alphaU", "alphaV"):
+                raise SceneError("%s: a texture on %r is not supported" % (t, c.get("name")))
+        m = make_bsdf(inner[0], allow_twosided=False)
+        if m["type"] in (6, 7, 8):
+            raise SceneError("%s(%s): a coat on dielectric, thindielectric or roughdielectric is not supported" % (t, it))
+        if t == "roughcoating" and m["type"] in (2, 3, 5):
+            raise SceneError("roughcoating(%s): a roughcoating over a BSDF with a delta component (conductor, plastic) is not supported" % it)
+        int_ior, ext_ior = lookup_ior(p, "intIOR", "bk7"), lookup_ior(p, "extIOR", "air")
+        if int_ior < 0 or ext_ior < 0 or int_ior == ext_ior:
+            raise SceneError("%s: The interior and exterior indices of refraction must be positive and differ!" % t)
+        eta = float(f32(int_ior / ext_ior))
+        thickness = float(f32(p.get("thickness", 1.0)))
+        sigma_a = tuple(float(v) for v in colour(elem, "sigmaA", 0.0))
+        spec = tuple(float(v) for v in colour(elem, "specularReflectance", 1.0))
+        if not (eta > 0 and eta != 1.0):
+            raise SceneError("%s: The interior and exterior indices of refraction must be positive and differ!" % t)
+        if not all(math.isfinite(v) for v in (eta, thickness) + sigma_a + spec):
+            raise SceneError("%s: a parameter is not finite" % t)
+        if thickness < 0 or min(sigma_a) < 0:
+            raise SceneError("%s: thickness and sigmaA must not be negative" % t)
+        c = dict(kind=t, eta=eta, thickness=thickness, sigma_a=sigma_a, specular=spec)
+        if t == "roughcoating":
+            mf = microfacet(elem, p, {}, t)
+            if mf.get("alpha_v", mf["alpha"]) != mf["alpha"]:  # roughcoating.cpp:143-145 (the plug-in's own words)
+                raise SceneError("roughcoating: The 'roughplastic' plugin currently does not support anisotropic microfacet distributions!")
+            if not math.isfinite(mf["alpha"]):
+                raise SceneError("roughcoating: a parameter is not finite")
+            distr = mf.get("distribution", "ggx")
+            key = (distr, float(f32(mf["alpha"])), eta)  # the reduction roughplastic uses, interned with its slices
+            if key not in rt_index:
+                try:
+                    rt_slices.append(_rt.roughplastic_slice(distr, mf["alpha"], eta, data_dir))
+                except _rt.RoughTransmittanceError as e:
+                    raise SceneError("roughcoating: %s" % e)
+                rt_index[key] = len(rt_slices) - 1
+            c.update(alpha=float(f32(mf["alpha"])), distribution=distr, sample_visible=bool(mf.get("sample_visible", True)), slice=rt_index[key])
+        return dict(m, coating=c)
+
     def intern(m):
         m = {k: v for k, v in m.items() if not k.startswith("_")}
-        key = tuple(sorted((k, tuple(v) if isinstance(v, (tuple, list)) else v) for k, v in m.items()))
+        freeze = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (tuple(sorted((a, freeze(b)) for a, b in v.items())) if isinstance(v, dict) else v)  # noqa: E731
+        key = tuple(sorted((k, freeze(v)) for k, v in m.items()))
         if key not in mat_index:
             mat_index[key] = len(materials)
             materials.append(m)
@@ -1467,7 +1526,7 @@ def save_scene_xml(desc, props, directory, name="scene"):
             '\t\t<float name="focusDistance" value="%r"/>' % float(lens["focus_distance"])]) + ['\t\t<sampler type="independent"/>', '\t\t<film type="hdrfilm">',
             '\t\t\t<integer name="width" value="%d"/>' % cam["width"], '\t\t\t<integer name="height" value="%d"/>' % cam["height"],
             '\t\t\t<boolean name="banner" value="false"/>', '\t\t\t<rfilter type="box"/>', '\t\t</film>', '\t</sensor>']
-    from .bindings import Material, Microfacet
+    from .bindings import Coating, Material, Microfacet
     for i, m in enumerate(desc.materials):
         t = m.get("type", 0)
         t = Material.BSDF[t] if isinstance(t, str) else int(t)
@@ -1502,6 +1561,14 @@ def save_scene_xml(desc, props, directory, name="scene"):
                '<rgb name="diffuseReflectance" value="%s"/><rgb name="specularReflectance" value="%s"/><boolean name="nonlinear" value="%s"/></bsdf>'
                % (rough, one, R, S, "true" if M.flags & 2 else "false"),
         }[t]
+        K = Coating.from_dict(m)  # a coating / roughcoating goes around the leaf, inside the other adapters
+        if K.kind:
+            coat = '<float name="extIOR" value="1.0"/><float name="intIOR" value="%r"/><float name="thickness" value="%r"/>' % (float(K.eta), float(K.thickness))
+            coat += '<rgb name="sigmaA" value="%s"/><rgb name="specularReflectance" value="%s"/>' % (c(K.sigma_a), c(K.specular))
+            if K.kind == 2:
+                coat += '<float name="alpha" value="%r"/><string name="distribution" value="%s"/>' % (float(K.alpha), ("beckmann", "ggx", "phong")[K.distribution])
+                coat += '<boolean name="sampleVisible" value="false"/>' if K.sample_all else ""
+            body = '<bsdf type="%s"%%s>%s%s</bsdf>' % ("coating" if K.kind == 1 else "roughcoating", coat, body % "")
         twos = t == 1 or (M.flags & 1 and t not in (6, 7, 8))
         if M.flags & 4:
             inner = ('<bsdf type="twosided">%s</bsdf>' % (body % "")) if twos else body % ""
