@@ -25,43 +25,33 @@
 #include "../../include/ppg.h"
 
 #define D __device__ __forceinline__
-// The code for analytic disks and cylinders (ppg_set_shapes) is compiled into kernels of their own — k_trace_shapes, k_shade_shapes,
-// k_tail_shapes: translation units built with -DPPG_SHAPES=1 (ppg_inst.hip) — which the launchers pick for a scene that holds such shapes.
-// Every other scene runs the kernels without it: one more analytic test behind each traversal costs registers the FULL kernels do not have.
-#ifndef PPG_SHAPES
-#define PPG_SHAPES 0
+// The large path kernels — k_trace, k_shade, k_tail — are compiled once per kernel FAMILY: a translation unit is built with -DPPG_FAMILY=f
+// (ppg_inst.hip), a family holds every feature of the families below it, and a scene runs the lowest family that has all it needs
+// (sceneFamily, ppg_hip.hip).  Each feature costs registers the FULL kernels do not have — one more analytic test behind each traversal,
+// say —, so no scene pays for one it does not use.  Everything a family adds sits under its feature macro, and its kernels' symbols are
+// the names with its suffix: k_trace_shapes, k_shade_ext, k_tail_coat.
+#define PPG_FAMILY_BASE 0    //           every scene without what follows
+#define PPG_FAMILY_SHAPES 1  // _shapes   analytic disks and cylinders (ppg_set_shapes)
+#define PPG_FAMILY_EXT 2     // _ext      the general MicrofacetDistribution (ppg_set_microfacet: alphaU / alphaV, Phong / Ashikhmin-Shirley,
+                             //           sampleVisible = false), with or without analytic shapes
+#define PPG_FAMILY_COAT 3    // _coat     the coating / roughcoating adapters (ppg_set_coatings), whatever else the scene holds
+#define PPG_FAMILIES 4
+#define PPG_SUFFIX_0
+#define PPG_SUFFIX_1 _shapes
+#define PPG_SUFFIX_2 _ext
+#define PPG_SUFFIX_3 _coat
+#ifndef PPG_FAMILY
+#define PPG_FAMILY 0  // (a digit: it is pasted to PPG_SUFFIX_)
 #endif
-// The general MicrofacetDistribution (ppg_set_microfacet: alphaU / alphaV, Phong / Ashikhmin-Shirley, sampleVisible = false) is compiled
-// into a third, "extended" family — k_trace_ext, k_shade_ext, k_tail_ext: translation units built with -DPPG_SHAPES=1 -DPPG_MFD=1 —, launched
-// for a scene whose microfacet list has a general entry, with or without analytic shapes.  Everything it adds sits under PPG_MFD.
-#ifndef PPG_MFD
-#define PPG_MFD 0
-#endif
-#if PPG_MFD && !PPG_SHAPES
-#error "the extended units are built with -DPPG_SHAPES=1 -DPPG_MFD=1"
-#endif
-// The coating / roughcoating adapters (ppg_set_coatings) are compiled into a fourth, "coat" family — k_trace_coat, k_shade_coat, k_tail_coat:
-// translation units built with -DPPG_SHAPES=1 -DPPG_MFD=1 -DPPG_COAT=1 —, launched for a scene with a coated material, whatever else it holds.
-// Everything it adds sits under PPG_COAT.
-#ifndef PPG_COAT
-#define PPG_COAT 0
-#endif
-#if PPG_COAT && !PPG_MFD
-#error "the coat units are built with -DPPG_SHAPES=1 -DPPG_MFD=1 -DPPG_COAT=1"
-#endif
-#if PPG_COAT
-#define k_trace k_trace_coat
-#define k_shade k_shade_coat
-#define k_tail k_tail_coat
-#elif PPG_MFD
-#define k_trace k_trace_ext
-#define k_shade k_shade_ext
-#define k_tail k_tail_ext
-#elif PPG_SHAPES
-#define k_trace k_trace_shapes
-#define k_shade k_shade_shapes
-#define k_tail k_tail_shapes
-#endif
+#define PPG_SHAPES (PPG_FAMILY >= PPG_FAMILY_SHAPES)
+#define PPG_MFD (PPG_FAMILY >= PPG_FAMILY_EXT)
+#define PPG_COAT (PPG_FAMILY >= PPG_FAMILY_COAT)
+#define PPG_CAT2(a, b) a##b
+#define PPG_CAT(a, b) PPG_CAT2(a, b)
+#define PPG_FAMILY_NAME(name) PPG_CAT(name, PPG_CAT(PPG_SUFFIX_, PPG_FAMILY))
+#define k_trace PPG_FAMILY_NAME(k_trace)
+#define k_shade PPG_FAMILY_NAME(k_shade)
+#define k_tail PPG_FAMILY_NAME(k_tail)
 
 struct F3 {
     float x, y, z;

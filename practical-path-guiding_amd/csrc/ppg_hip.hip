@@ -21,6 +21,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <limits>
@@ -31,7 +32,7 @@
 
 #include "../../include/ppg.h"
 #include "../../include/ppg_testhooks.h"
-#include "ppg_kernels.h"
+#include "ppg_host_kernels.h"
 #include "ppg_launch.h"
 
 namespace {
@@ -1013,24 +1014,24 @@ struct ppg_ctx {
     }
 };
 
-void ppg_launch_shade(int variant, const ShadeLaunch &a) {
-    if (a.S.coat) { ppg_launch_shade_coat(variant, a); return; }  // a coated material: the coat family, whatever else the scene holds
-    if (a.S.mfd) { ppg_launch_shade_ext(variant, a); return; }  // a general microfacet entry: the extended family, shapes or not
-    if (a.S.n_shapes) { ppg_launch_shade_shapes(variant, a); return; }  // (such a scene is FULL and never small)
-    if (variant >> 1) ppg_launch_shade_pair1(variant, a);
-    else ppg_launch_shade_pair0(variant, a);
+PathKernels ppg_path_kernels[PPG_FAMILIES];  // filled by the units of ppg_inst.hip when the library is loaded
+
+// The kernel family a scene runs: the lowest that has everything the scene needs (ppg_device.h).
+static int sceneFamily(const DevScene &S) {
+    if (S.coat) return PPG_FAMILY_COAT;        // a coated material: the coat family, whatever else the scene holds
+    if (S.mfd) return PPG_FAMILY_EXT;          // a general microfacet entry: the extended family, shapes or not
+    if (S.n_shapes) return PPG_FAMILY_SHAPES;  // an analytic disk or cylinder
+    return PPG_FAMILY_BASE;                    // (only here is a scene ever small, or without the FULL material set)
 }
-void ppg_launch_tail(int variant, const TailLaunch &a) {
-    if (a.S.coat) { ppg_launch_tail_coat(variant, a); return; }
-    if (a.S.mfd) { ppg_launch_tail_ext(variant, a); return; }
-    if (a.S.n_shapes) { ppg_launch_tail_shapes(variant, a); return; }
-    switch (variant >> 1) {
-        case 0: ppg_launch_tail_pair0(variant, a); break;
-        case 1: ppg_launch_tail_pair1(variant, a); break;
-        case 2: ppg_launch_tail_pair2(variant, a); break;
-        default: ppg_launch_tail_pair3(variant, a); break;
-    }
+// a launcher of the table; one that no unit has entered is a fault in the build of the library
+template <typename F> static F launcher(F f) {
+    if (!f) { fprintf(stderr, "libppg_hip: no unit of this library holds the kernel asked for\n"); abort(); }
+    return f;
 }
+// variant = (NEE ? 2 : 0) | (FULL ? 1 : 0)
+static void ppg_launch_shade(int variant, const ShadeLaunch &a) { launcher(ppg_path_kernels[sceneFamily(a.S)].shade[variant >> 1])(variant, a); }
+// variant = (SMALL ? 4 : 0) | (NEE ? 2 : 0) | (FULL ? 1 : 0)
+static void ppg_launch_tail(int variant, const TailLaunch &a) { launcher(ppg_path_kernels[sceneFamily(a.S)].tail[variant >> 1])(variant, a); }
 namespace {
 
 template <typename F> void timedLaunch(ppg_ctx *ctx, const char *name, uint64_t units, F &&launch) {
@@ -1843,7 +1844,7 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
         if (((chunks + (size_t)ctx->tuneBlocksSmall - 1) / (size_t)ctx->tuneBlocksSmall) * PPG_DCHUNK <= (size_t)ctx->queues.cap) grid = ctx->tuneBlocksSmall;
     }
     const int gridAll = gridFor(P.n_paths);
-    const bool smallScene = ctx->scene.n_tris <= 64 && ctx->ldsTris == ctx->scene.n_tris && ctx->scene.n_spheres == 0 && ctx->scene.n_shapes == 0 && !ctx->scene.mfd && !ctx->scene.coat && !ctx->tuneForceBvh;
+    const bool smallScene = ctx->scene.n_tris <= 64 && ctx->ldsTris == ctx->scene.n_tris && ctx->scene.n_spheres == 0 && sceneFamily(ctx->scene) == PPG_FAMILY_BASE && !ctx->tuneForceBvh;
     // (small scenes go through k_trace too: tracing them inside k_generate / k_shade was measured slower, DESIGN.md "Tuning switches")
     const bool neeOn = ctx->doNee;  // m_doNee of this iteration (doNeeWithSpp, GP:1331-1340)
     const bool fullMats = ctx->fullMaterials;  // any BSDF beyond diffuse / two-sided diffuse / mirror: the FULL kernel variants
@@ -1903,12 +1904,8 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
             unsigned int *const trSorted = sortSlices ? ctx->d_queueSorted.p : nullptr;
             unsigned char *const trKeys = sortSlices ? ctx->d_sortKeys.p : nullptr;
             timedLaunch(ctx, "k_trace", hostCount, [&] {
-                if (S.coat) ppg_launch_trace_coat(ctx->timer.enabled, grid, traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
-                else if (S.mfd) ppg_launch_trace_ext(ctx->timer.enabled, grid, traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
-                else if (S.n_shapes) ppg_launch_trace_shapes(ctx->timer.enabled, grid, traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
-                else if (smallScene) hipLaunchKernelGGL((k_trace<true, false>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, 0, ctx->ldsTris, trSorted, trKeys);
-                else if (ctx->timer.enabled) hipLaunchKernelGGL((k_trace<false, true>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
-                else hipLaunchKernelGGL((k_trace<false, false>), dim3(grid), dim3(PPG_BLOCK), traceLds, s, P, S, Q, qin, ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys);
+                TraceLaunch a{grid, traceLds, s, P, S, Q, qin, smallScene ? 0 : ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys, smallScene, ctx->timer.enabled};
+                launcher(ppg_path_kernels[sceneFamily(S)].trace)(a);
             });
             int shadeIn = sortSlices ? QIN_SORTED : qin;
             ctx->joinTree();  // (k_generate and the first k_trace ran beside the previous round's optimiser: k_shade needs its result)
@@ -1916,7 +1913,7 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
             // (also for a scene with disks or cylinders, although this kernel is compiled without their code: it shades triangle hits of the
             // common classes only — sort_slice keeps every non-triangle hit out of them —, traces nothing and, without luminaire sampling,
             // never calls emitter_sample_direct, where a shape's em_info entry would be read as a triangle range.  A variant of it that
-            // traces or samples emitters must go to the PPG_SHAPES units like the others: ppg_launch_shade / ppg_launch_tail.)
+            // traces or samples emitters must go through the scene's family like the others: ppg_launch_shade / ppg_launch_tail.)
             const bool split = shadeIn == QIN_SORTED && Q.n_common && !neeOn;
             if (split) {
                 timedLaunch(ctx, "k_shade<common>", hostCount, [&] {
@@ -3891,7 +3888,7 @@ int ppg_debug_intersect(ppg_ctx *ctx, uint32_t n, const float *rays, ppg_debug_h
     HIP_CHECK(dRays.fill(rays, 2 * (size_t)n * sizeof(float4)));
     HIP_CHECK(dOut.fill(nullptr, (size_t)n * sizeof(ppg_debug_hit)));
     const unsigned int block = 64;
-    ppg_launch_debug_intersect((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const float4 *)dRays.p, (ppg_debug_hit *)dOut.p, any_hit ? 1 : 0);
+    launcher(ppg_path_kernels[PPG_FAMILY_SHAPES].debug_intersect)((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const float4 *)dRays.p, (ppg_debug_hit *)dOut.p, any_hit ? 1 : 0);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_hit), hipMemcpyDeviceToHost));
@@ -3910,8 +3907,8 @@ int ppg_debug_sample_direct(ppg_ctx *ctx, uint32_t n, const float *ref, const fl
     HIP_CHECK(dU.fill(u, 2 * (size_t)n * sizeof(float)));
     HIP_CHECK(dOut.fill(nullptr, (size_t)n * sizeof(ppg_debug_direct)));
     const unsigned int block = 64;
-    ppg_launch_debug_sample_direct((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const float *)dRef.p, (const float *)dRefN.p, (const float *)dU.p,
-                                   (ppg_debug_direct *)dOut.p);
+    launcher(ppg_path_kernels[PPG_FAMILY_SHAPES].debug_sample_direct)((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const float *)dRef.p,
+                                                                      (const float *)dRefN.p, (const float *)dU.p, (ppg_debug_direct *)dOut.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_direct), hipMemcpyDeviceToHost));
@@ -3931,8 +3928,8 @@ int ppg_debug_bsdf(ppg_ctx *ctx, uint32_t n, const ppg_debug_bsdf_item *items, p
     HIP_CHECK(dItems.fill(items, (size_t)n * sizeof(ppg_debug_bsdf_item)));
     HIP_CHECK(dOut.fill(nullptr, (size_t)n * sizeof(ppg_debug_bsdf_out)));
     const unsigned int block = 64;
-    if (ctx->scene.coat) ppg_launch_debug_bsdf_coat((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const ppg_debug_bsdf_item *)dItems.p, (ppg_debug_bsdf_out *)dOut.p);
-    else ppg_launch_debug_bsdf((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const ppg_debug_bsdf_item *)dItems.p, (ppg_debug_bsdf_out *)dOut.p);
+    const int family = std::max(sceneFamily(ctx->scene), PPG_FAMILY_EXT);  // (the lowest family that compiles the hook's kernel)
+    launcher(ppg_path_kernels[family].debug_bsdf)((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const ppg_debug_bsdf_item *)dItems.p, (ppg_debug_bsdf_out *)dOut.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_bsdf_out), hipMemcpyDeviceToHost));

@@ -1,8 +1,9 @@
 /*
- * ppg_launch.h — launchers of the large path kernels.  k_shade exists in five instantiations (NEE x FULL, and MSET_COMMON), k_tail in eight
- * (SMALL x NEE x FULL) and k_commit in six (spatial x directional filter); each pair of instantiations is its own translation unit
- * (ppg_inst.hip compiled with -DPPG_INST=n), so the library builds in parallel instead of in one 2.5-minute compile.  No device code
- * crosses a translation unit.
+ * ppg_launch.h — launchers of the large path kernels.  In the base family k_shade exists in five instantiations (NEE x FULL, and MSET_COMMON),
+ * k_tail in eight (SMALL x NEE x FULL), k_trace in three and k_commit in six (spatial x directional filter); every further family
+ * (ppg_device.h PPG_FAMILY) adds the FULL ones of k_shade, k_tail and k_trace.  Each pair of instantiations is its own translation unit
+ * (ppg_inst.hip compiled for a family and a role), so the library builds in parallel instead of in one 2.5-minute compile.  No device code
+ * crosses a translation unit: a unit hands the host a launcher — an argument struct per role, a table of launchers per family.
  */
 #ifndef PPG_LAUNCH_H
 #define PPG_LAUNCH_H
@@ -31,6 +32,17 @@ struct TailLaunch {
     StragOut strag;          // R.defer_depth > 0: where the paths still alive at that depth go
     unsigned int lane_limit; // paths a wave takes at a time (64; fewer for a launch over a handful of stragglers)
 };
+struct TraceLaunch {
+    int grid;
+    size_t lds;
+    hipStream_t stream;
+    PathState P; DevScene S; Queues Q;
+    int qin, lds_nodes, lds_tris;
+    unsigned int *sorted;    // sort_slice's output and key scratch; null: the slices are not sorted
+    unsigned char *keys;
+    bool small;              // the scene is traced from LDS (k_trace<true>: base family only)
+    bool count;              // count the BVH nodes and triangles visited (kernel timing)
+};
 struct CommitLaunch {
     int grid;
     hipStream_t stream;
@@ -52,51 +64,32 @@ struct SplatLaunch {
     unsigned int lds_nodes;     // D-trees of up to this many nodes are staged in LDS (<= PPG_SPLAT_NODES)
 };
 
-// variant = (NEE ? 2 : 0) | (FULL ? 1 : 0)
-void ppg_launch_shade(int variant, const ShadeLaunch &a);
-// variant = (SMALL ? 4 : 0) | (NEE ? 2 : 0) | (FULL ? 1 : 0)
-void ppg_launch_tail(int variant, const TailLaunch &a);
-// (these three are defined in the commit unit itself)
+
+// One row per kernel family (ppg_device.h PPG_FAMILY): the launchers of its k_shade, k_tail and k_trace.  Every unit of ppg_inst.hip enters the
+// launchers it defines into its family's row when the library is loaded; the host picks the row with sceneFamily (ppg_hip.hip).
+struct ppg_debug_hit;
+struct ppg_debug_direct;
+struct ppg_debug_bsdf_item;
+struct ppg_debug_bsdf_out;
+struct PathKernels {
+    void (*shade[2])(int variant, const ShadeLaunch &a);  // [NEE]; variant = (NEE ? 2 : 0) | (FULL ? 1 : 0)
+    void (*tail[4])(int variant, const TailLaunch &a);    // [SMALL * 2 + NEE]; variant = (SMALL ? 4 : 0) | (NEE ? 2 : 0) | (FULL ? 1 : 0)
+    void (*trace)(const TraceLaunch &a);
+    // The kernels of the test hooks (ppg_debug_kernels.h), in the families that compile them: the shapes family those of ppg_debug_intersect /
+    // ppg_debug_sample_direct, the families from ext on that of ppg_debug_bsdf
+    void (*debug_intersect)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_hit *out, int any);
+    void (*debug_sample_direct)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float *ref, const float *ref_n, const float *u,
+                                ppg_debug_direct *out);
+    void (*debug_bsdf)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out);
+};
+extern PathKernels ppg_path_kernels[PPG_FAMILIES];
+
+// The kernels outside the families, each defined in the unit that compiles it.
+// k_shade<false, FULL, MSET_COMMON> over the front part of the sorted slices (a.qin = QIN_SORTED_COMMON)
+void ppg_launch_shade_common(const ShadeLaunch &a);
 void ppg_launch_commit(int spatial_filter, int directional_filter, const CommitLaunch &a);
 // a round of the optimiser: k_commit_records (nearest / stochastic spatial filter), then — after the sort — k_splat_sorted
 void ppg_launch_commit_records(int spatial_filter, const CommitLaunch &a);
 void ppg_launch_splat(int directional_filter, const SplatLaunch &a);
-
-// one function per translation unit (pair = variant >> 1)
-void ppg_launch_shade_pair0(int variant, const ShadeLaunch &a);
-void ppg_launch_shade_pair1(int variant, const ShadeLaunch &a);
-void ppg_launch_tail_pair0(int variant, const TailLaunch &a);
-void ppg_launch_tail_pair1(int variant, const TailLaunch &a);
-void ppg_launch_tail_pair2(int variant, const TailLaunch &a);
-void ppg_launch_tail_pair3(int variant, const TailLaunch &a);
-// Scenes with analytic disks or cylinders (ppg_set_shapes): the FULL kernels built with -DPPG_SHAPES=1, in three units of their own —
-// k_shade_shapes<NEE, true>, k_tail_shapes<false, NEE, true>, k_trace_shapes<false, COUNT> with the test hooks' two kernels
-void ppg_launch_shade_shapes(int variant, const ShadeLaunch &a);
-void ppg_launch_tail_shapes(int variant, const TailLaunch &a);
-void ppg_launch_trace_shapes(bool count, int grid, size_t lds, hipStream_t stream, const PathState &P, const DevScene &S, const Queues &Q, int qin, int lds_nodes,
-                             int lds_tris, unsigned int *sorted, unsigned char *keys);
-struct ppg_debug_hit;
-struct ppg_debug_direct;
-void ppg_launch_debug_intersect(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_hit *out, int any);
-void ppg_launch_debug_sample_direct(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float *ref, const float *ref_n, const float *u,
-                                    ppg_debug_direct *out);
-// Scenes with a general microfacet entry (ppg_set_microfacet): the same three kernels built with -DPPG_SHAPES=1 -DPPG_MFD=1, the "extended"
-// family — k_shade_ext<NEE, true>, k_tail_ext<false, NEE, true>, k_trace_ext<false, COUNT> with the kernel of ppg_debug_bsdf
-void ppg_launch_shade_ext(int variant, const ShadeLaunch &a);
-void ppg_launch_tail_ext(int variant, const TailLaunch &a);
-void ppg_launch_trace_ext(bool count, int grid, size_t lds, hipStream_t stream, const PathState &P, const DevScene &S, const Queues &Q, int qin, int lds_nodes,
-                          int lds_tris, unsigned int *sorted, unsigned char *keys);
-struct ppg_debug_bsdf_item;
-struct ppg_debug_bsdf_out;
-void ppg_launch_debug_bsdf(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out);
-// Scenes with a coated material (ppg_set_coatings): the same again built with -DPPG_SHAPES=1 -DPPG_MFD=1 -DPPG_COAT=1, the "coat" family —
-// k_shade_coat<NEE, true>, k_tail_coat<false, NEE, true>, k_trace_coat<false, COUNT> with the hook's kernel for such a scene
-void ppg_launch_shade_coat(int variant, const ShadeLaunch &a);
-void ppg_launch_tail_coat(int variant, const TailLaunch &a);
-void ppg_launch_trace_coat(bool count, int grid, size_t lds, hipStream_t stream, const PathState &P, const DevScene &S, const Queues &Q, int qin, int lds_nodes,
-                           int lds_tris, unsigned int *sorted, unsigned char *keys);
-void ppg_launch_debug_bsdf_coat(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out);
-// k_shade<false, FULL, MSET_COMMON> over the front part of the sorted slices (a.qin = QIN_SORTED_COMMON)
-void ppg_launch_shade_common(const ShadeLaunch &a);
 
 #endif

@@ -696,6 +696,33 @@ def test_render_with_shapes_is_deterministic_and_an_empty_list_changes_nothing()
     assert np.array_equal(never, plain)
 
 
+def test_a_shape_renders_the_same_bits_in_every_family_above_its_own():
+    """The box with one emitting disk through the shapes kernels, then — an unused general microfacet entry — through the extended ones, then —
+    an unused coated material on top — through the coat ones: each family holds the code of those below it, so film and SD-tree are equal."""
+    import ppg_host
+    from test_bsdfs import GOLD
+    from test_coatings import DIFFUSE
+    from test_coatings_gpu import UNUSED_COATED, _render, with_slices
+
+    def box(extra):
+        d = ppg_host.cbox_scene(16, 12)
+        d.materials = list(d.materials) + [dict(type=0, reflectance=(0.0, 0.0, 0.0))]
+        d.emitters = list(d.emitters) + [dict(radiance=(9.0, 6.0, 3.0))]
+        d.shapes = [_disk((150.0, 400.0, 200.0), 60.0, _rot((1, 0, 0), 70), material=len(d.materials) - 1, emitter=len(d.emitters) - 1)]
+        if extra:
+            with_slices(d, extra)  # on no triangle and no shape: they only pick the family
+        return d
+    fa, ta = _render(box([]))
+    fb, tb = _render(box([dict(GOLD, alpha_v=0.1), DIFFUSE]))
+    fc, tc = _render(box([dict(GOLD, alpha_v=0.1), UNUSED_COATED]))
+    assert np.isfinite(fa).all() and fa.mean() > 0
+    assert np.array_equal(fa, fb) and np.array_equal(fa, fc)
+    _tree_equal(ta, tb)
+    _tree_equal(ta, tc)
+    # (the disk is in the picture: without it the film differs)
+    assert not np.array_equal(fa, _render(ppg_host.cbox_scene(16, 12))[0])
+
+
 def test_two_shards_in_one_process_equal_the_unsharded_film():
     """two contexts with shards 0 and 1 of 2, their buffers summed as a reducer would, against one context"""
     import torch

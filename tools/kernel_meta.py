@@ -99,7 +99,7 @@ def main():
                 continue
             line = "%-72s %5s %5s %6s %6s %8s %7s %8s" % (n[:72], r.get("vgpr_count"), r.get("sgpr_count"), r.get("vgpr_spill_count"), r.get("sgpr_spill_count"),
                                                         r.get("private_segment_fixed_size"), r.get("group_segment_fixed_size"), r.get("code_bytes"))
-            if line not in seen:  # static kernels are compiled into every translation unit
+            if line not in seen:  # (a kernel met twice, in a library and in one of its object files, is listed once)
                 seen.add(line)
                 print(line)
 
