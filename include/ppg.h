@@ -484,6 +484,46 @@ typedef struct ppg_coating {
 int ppg_set_coatings(ppg_ctx *ctx, const ppg_coating *c, uint32_t n_materials);
 
 /* ------------------------------------------------------------------------------------------------
+ * Mitsuba's `blendbsdf` (blendbsdf.cpp) and `mixturebsdf` (mixturebsdf.cpp) combinators: a material that interpolates, or linearly
+ * combines, other entries of ppg_scene.materials.  One more side list, one entry per material, with the ordering rules of
+ * ppg_set_coatings: call before ppg_set_scene, which validates and consumes it; the context keeps it until it is replaced (NULL or
+ * n_materials = 0 clears it); PPG_ERR_STATE between ppg_begin_render and ppg_end_render.  A list whose entries are all of kind 0 renders
+ * exactly as no list does.
+ *   kind     0: none (the other fields are ignored), 1: blendbsdf, 2: mixturebsdf
+ *   n        the number of children: 2 for blendbsdf, 1 .. PPG_BLEND_MAX for mixturebsdf
+ *   child    indices into ppg_scene.materials.  A child is an ordinary material — triangles may use it directly as well —: diffuse,
+ *            mirror / conductor, roughconductor, plastic or roughplastic, with its reflectance bitmap, its specular / alpha slots
+ *            (ppg_set_material_textures) and its entry of ppg_set_microfacet; not blended, coated, masked, two-sided or bump-mapped itself
+ *   weight   kind 1: weight[0] = `weight` (clamped to [0, 1]; the children get 1 - w and w); kind 2: the `weights`, >= 0 with a sum > 0
+ *   weight_texture  kind 1: 1 + index into ppg_scene.textures of a bitmap `weight` (its average at the hit's uv, clamped), 0 = none
+ *   ensure_energy_conservation  kind 2: weights whose sum exceeds 1 are multiplied by 1 / sum (mixturebsdf.cpp:130-141)
+ * The rescaled weights and the normalised DiscreteDistribution (pmf.h: running float sum, then normalize()) are derived inside
+ * ppg_set_scene with the library's own float arithmetic.
+ * The blended material's own ppg_material record supplies the adapters around the blend, bumpmap( mask( twosided( blend( .. )))): its
+ * flags (PPG_MAT_TWOSIDED, PPG_MAT_MASK), opacity, the opacity slot and the bump-map half of `texture` apply; its type must be
+ * PPG_BSDF_DIFFUSE and its BSDF fields are otherwise ignored.
+ * ppg_set_scene returns PPG_ERR_INVALID, and ppg_last_error names the material, for: a list whose length is neither 0 nor n_materials;
+ * another kind; n or a child index out of range; a child that is itself blended, coated, masked, two-sided or bump-mapped; a dielectric,
+ * thindielectric or roughdielectric child; a coat on the blended material; a reflectance bitmap, a parameter slot (other than opacity
+ * with PPG_MAT_MASK) or a microfacet entry on the blended record; a type other than PPG_BSDF_DIFFUSE there; a weight that is negative or
+ * not finite; a mixture whose weights sum to 0; a texture index out of range; a non-zero reserved word; a blend on an analytic sphere or
+ * shape when it or a child reads a bitmap; an anisotropic child on a mesh without texture coordinates.
+ * A scene with a blended material runs the "blend" kernels (csrc: PPG_BLEND), whatever else it holds; the CPU oracle does not know these
+ * entries (they are pinned against a float64 restatement).
+ * ---------------------------------------------------------------------------------------------- */
+#define PPG_BLEND_MAX 4
+typedef struct ppg_blend {
+    int32_t kind;                        /* 0 = none, 1 = blendbsdf, 2 = mixturebsdf */
+    uint32_t n;                          /* children */
+    uint32_t child[PPG_BLEND_MAX];       /* indices into ppg_scene.materials */
+    float weight[PPG_BLEND_MAX];
+    uint32_t weight_texture;             /* kind 1: 1 + texture index, 0 = none */
+    int32_t ensure_energy_conservation;  /* kind 2 */
+    uint32_t _reserved[4];               /* must be 0 */
+} ppg_blend;                             /* 64 bytes */
+int ppg_set_blends(ppg_ctx *ctx, const ppg_blend *b, uint32_t n_materials);
+
+/* ------------------------------------------------------------------------------------------------
  * Rendering.  ppg_render() is GuidedPathTracer::render() (GP:1516-1585, IH:74-75) in one call.
  * The stepwise calls expose its phases so a multi-GPU driver can all-reduce the SD-tree statistics
  * between ppg_render_passes() and ppg_build_sdtree(); ppg_render() is exactly their composition

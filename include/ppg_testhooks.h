@@ -89,7 +89,7 @@ int ppg_debug_sample_direct(struct ppg_ctx *ctx, uint32_t n, const float *ref, c
 /* The BSDF layer of the context's materials (after ppg_set_scene, outside a render), item by item: one small kernel of the extended
    units (csrc: PPG_MFD) whose lanes prepare the material as the render does at a hit with texture coordinates uv — the record, the bitmaps
    of ppg_material.texture / ppg_set_material_textures, the entry of ppg_set_microfacet, the coat of ppg_set_coatings (a scene with one runs the hook's kernel of
-   the coat units, PPG_COAT) — and call the render's own mat_eval / mat_pdf / mat_sample on it.  A material without a general entry runs through the same functions with alphaV = alphaU, its own ggx / beckmann and
+   the coat units, PPG_COAT), the blend of ppg_set_blends with its children prepared likewise at uv (the kernel of the blend units, PPG_BLEND) — and call the render's own mat_eval / mat_pdf / mat_sample on it.  A material without a general entry runs through the same functions with alphaV = alphaU, its own ggx / beckmann and
    visible sampling: the float operations of the isotropic path, which the tests hold to the oracle bit for bit.
    Per item: the material, local wi, local wo (eval / pdf), the 2-D sample, and the extra number roughdielectric::sample draws from the
    path's sampler (roughdielectric.cpp:553), named as the render names it: it is ppg_rand(key, 0) (include/ppg_rng.h).

@@ -1,7 +1,8 @@
 /*
  * ppg_debug_kernels.h — the kernels of the test hooks (include/ppg_testhooks.h) that run the render's own device functions, included by the
  * k_trace unit of a family (ppg_inst.hip): k_debug_intersect and k_debug_sample_direct in the shapes family, which the hooks always use;
- * k_debug_bsdf in the ext family and k_debug_bsdf_coat in the coat family, which ppg_debug_bsdf uses for a scene with a coated material.
+ * k_debug_bsdf in the ext family, k_debug_bsdf_coat in the coat family, which ppg_debug_bsdf uses for a scene with a coated material, and
+ * k_debug_bsdf_blend in the blend family, which it uses for a scene with a blended one.
  */
 #ifndef PPG_DEBUG_KERNELS_H
 #define PPG_DEBUG_KERNELS_H
@@ -77,17 +78,20 @@ __global__ void k_debug_bsdf(DevScene S, unsigned int n, const ppg_debug_bsdf_it
     if (tex & 0xffffu) M.refl = tex_eval(S.textures[(tex & 0xffffu) - 1u], it.uv[0], it.uv[1]);
     mat_apply_textures(S, it.material, it.uv[0], it.uv[1], M);
     mat_apply_mfd_textures(S, it.material, it.uv[0], it.uv[1], M);
+#if PPG_BLEND
+    M.bu = it.uv[0]; M.bv = it.uv[1];
+#endif
     const F3 wi = f3(it.wi[0], it.wi[1], it.wi[2]), wo = f3(it.wo[0], it.wo[1], it.wo[2]);
     ppg_debug_bsdf_out r;
     memset(&r, 0, sizeof r);
-    const F3 f = mat_eval(M, wi, wo);
+    const F3 f = mat_eval(M, wi, wo MAT_SCENE_ARG);
     r.eval[0] = f.x; r.eval[1] = f.y; r.eval[2] = f.z;
-    r.pdf = mat_pdf(M, wi, wo);
+    r.pdf = mat_pdf(M, wi, wo MAT_SCENE_ARG);
     F3 swo;
     float spdf, seta;
     bool delta, isnull;
     unsigned int dim = 0;
-    const F3 w = mat_sample(M, wi, it.sample[0], it.sample[1], swo, spdf, delta, seta, isnull, it.key, dim);
+    const F3 w = mat_sample(M, wi, it.sample[0], it.sample[1], swo, spdf, delta, seta, isnull, it.key, dim MAT_SCENE_ARG);
     r.wo[0] = swo.x; r.wo[1] = swo.y; r.wo[2] = swo.z;
     r.sampled_pdf = spdf;
     r.weight[0] = w.x; r.weight[1] = w.y; r.weight[2] = w.z;

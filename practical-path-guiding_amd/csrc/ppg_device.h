@@ -35,17 +35,20 @@
 #define PPG_FAMILY_EXT 2     // _ext      the general MicrofacetDistribution (ppg_set_microfacet: alphaU / alphaV, Phong / Ashikhmin-Shirley,
                              //           sampleVisible = false), with or without analytic shapes
 #define PPG_FAMILY_COAT 3    // _coat     the coating / roughcoating adapters (ppg_set_coatings), whatever else the scene holds
-#define PPG_FAMILIES 4
+#define PPG_FAMILY_BLEND 4   // _blend    the blendbsdf / mixturebsdf combinators (ppg_set_blends), whatever else the scene holds
+#define PPG_FAMILIES 5
 #define PPG_SUFFIX_0
 #define PPG_SUFFIX_1 _shapes
 #define PPG_SUFFIX_2 _ext
 #define PPG_SUFFIX_3 _coat
+#define PPG_SUFFIX_4 _blend
 #ifndef PPG_FAMILY
 #define PPG_FAMILY 0  // (a digit: it is pasted to PPG_SUFFIX_)
 #endif
 #define PPG_SHAPES (PPG_FAMILY >= PPG_FAMILY_SHAPES)
 #define PPG_MFD (PPG_FAMILY >= PPG_FAMILY_EXT)
 #define PPG_COAT (PPG_FAMILY >= PPG_FAMILY_COAT)
+#define PPG_BLEND (PPG_FAMILY >= PPG_FAMILY_BLEND)
 #define PPG_CAT2(a, b) a##b
 #define PPG_CAT(a, b) PPG_CAT2(a, b)
 #define PPG_FAMILY_NAME(name) PPG_CAT(name, PPG_CAT(PPG_SUFFIX_, PPG_FAMILY))
@@ -205,6 +208,11 @@ struct DevScene {
     // n_emitters .. n_emitters + n_delta - 1, and the environment emitter is number n_emitters + n_delta
     const float4 *delta;
     int n_delta;
+    // ppg_set_blends with a blended material (blend kernels only, PPG_BLEND): PPG_BLEND_STRIDE float4 = 16 words per material — the
+    // children (4 material indices), the eval weights (4), the normalised cdf (5: DiscreteDistribution::m_cdf), the PPG_BLENDF_* bits,
+    // the weight texture (1 + index), 0; nullptr otherwise.  (It stands here, in the padding in front of the next float4, so that no
+    // other member and no kernel argument behind the scene moves: the kernels of the other families stay what they were.)
+    const float4 *blend;
     float4 dir_sphere;         // DirectionalEmitter::m_bsphere: the geometry box's bounding sphere, radius * 1.1 (directional.cpp:88-94)
     // analytic disks and cylinders (ppg_set_shapes; FULL kernels, BVH path only): PPG_SHAPE_STRIDE float4 each = rows 0..2 of the 3x4
     // object-to-world, rows 0..2 of its inverse, (radius, length, invSurfaceArea, type) (material, emitter, flip normals, -); primitive
@@ -218,6 +226,16 @@ struct DevScene {
     // specularSamplingWeight, PPG_COATF_* bits), (sigmaA, alpha), (specularReflectance, rough-transmittance slice as int); nullptr otherwise
     const float4 *coat;
 };
+#define PPG_BLEND_STRIDE 4
+#define PPG_BLENDW_CHILD 0        // word offsets into a material's 16 words
+#define PPG_BLENDW_WEIGHT 4
+#define PPG_BLENDW_CDF 8
+#define PPG_BLENDW_BITS 13
+#define PPG_BLENDW_TEX 14
+#define PPG_BLENDF_KIND 3u        // 0 none, 1 blendbsdf, 2 mixturebsdf
+#define PPG_BLENDF_N_SHIFT 2      // bits 2..4: the number of children
+#define PPG_BLENDF_TEXTURED 32u   // the weight or a child reads a bitmap, or a child is anisotropic: the hit needs its.uv and the UV tangents
+#define PPG_BLENDF_SMOOTH 64u     // a child has a smooth component (getType() & ESmooth)
 #define PPG_COAT_STRIDE 3
 #define PPG_COATF_KIND 3u         // 0 none, 1 coating, 2 roughcoating
 #define PPG_COATF_TYPE_SHIFT 2    // bits 2..3: MFD_BECKMANN / MFD_GGX / MFD_PHONG of a roughcoating
@@ -912,6 +930,9 @@ D void fill_isect_tex(const DevScene &S, const Hit &h, F3 d, Isect &I, TexInfo &
 #if PPG_MFD
     if (SLOTS && S.mfd) textured = textured || (__float_as_uint(S.mfd[I.material].y) & PPG_MFDF_ANISO) != 0u;
 #endif
+#if PPG_BLEND
+    if (SLOTS && S.blend) textured = textured || (__float_as_uint(S.blend[PPG_BLEND_STRIDE * (size_t)I.material + 3].y) & PPG_BLENDF_TEXTURED) != 0u;
+#endif
     F3 dpdu = side1;
     if (textured) {
         X.u = b.y; X.v = b.z;
@@ -1547,6 +1568,10 @@ struct Mat {
 #if PPG_COAT
     const float4 *coat;       // the material's rows of DevScene::coat when it is coated (ppg_set_coatings), nullptr otherwise
 #endif
+#if PPG_BLEND
+    const float *blend;       // the material's 16 words of DevScene::blend when it is blended (ppg_set_blends), nullptr otherwise
+    float bu, bv;             // ... and the hit's its.uv, at which the children's bitmaps and the weight's are looked up
+#endif
 };
 D Mat load_material(const DevScene &S, int id) {
     const float4 *m = S.materials + PPG_MAT_STRIDE * (size_t)id;
@@ -1576,6 +1601,13 @@ D Mat load_material(const DevScene &S, int id) {
     if (S.coat) {
         const float4 *c = S.coat + PPG_COAT_STRIDE * (size_t)id;
         if (__float_as_uint(c[0].w) & PPG_COATF_KIND) M.coat = c;
+    }
+#endif
+#if PPG_BLEND
+    M.blend = nullptr; M.bu = 0.0f; M.bv = 0.0f;
+    if (S.blend) {
+        const float *b = reinterpret_cast<const float *>(S.blend + PPG_BLEND_STRIDE * (size_t)id);
+        if (__float_as_uint(b[PPG_BLENDW_BITS]) & PPG_BLENDF_KIND) M.blend = b;
     }
 #endif
     return M;
@@ -1626,6 +1658,9 @@ D void mat_apply_null_textures(const DevScene &S, const Hit &h, int id, Mat &M) 
     if (ts) { const float4 t = tex_eval_hit(S.uvs, S.textures, ts, h.prim, h.u, h.v); M.spec = f3(t.x, t.y, t.z); }
 }
 D bool mat_is_smooth(const Mat &M) {
+#if PPG_BLEND
+    if (M.blend) return (__float_as_uint(M.blend[PPG_BLENDW_BITS]) & PPG_BLENDF_SMOOTH) != 0u;  // smooth if any child is
+#endif
 #if PPG_COAT
     // a roughcoating's own component is glossy, a coating's is a delta: "nested smooth, or roughcoating"
     if (M.coat && (__float_as_uint(M.coat[0].w) & PPG_COATF_KIND) == 2u) return true;
@@ -2528,19 +2563,167 @@ D int coat_sample_post(const Mat &M, int state, F3 wiN, float ps, float R12, F3 
     return COAT_DONE;
 }
 #endif
-// + the TwoSided adapter (twosided.cpp:120-180) and, outside it, the Mask adapter (mask.cpp:108-214)
-D F3 mat_eval(const Mat &M, F3 wi, F3 wo) {
+#if PPG_BLEND
+// ------------------------------------------------------------------------------------------------
+// The blendbsdf / mixturebsdf combinators (blendbsdf.cpp:135-275, mixturebsdf.cpp:174-282) over mat_*_one, where a coat sits: inside the
+// two-sided adapter.  M.blend points at the material's 16 words of DevScene::blend (layout there); ppg_set_scene has checked every child
+// index and that no child is itself blended, coated or wrapped, so the loops below are bounded by PPG_BLEND_MAX and nothing recurses.  One
+// child's Mat is live at a time: it is loaded — record, bitmaps at the hit's uv, microfacet entry —, used and dropped.
+// ------------------------------------------------------------------------------------------------
+#define MAT_SCENE_PARAM , const DevScene &S
+#define MAT_SCENE_ARG , S
+D bool blend_is_mixture(const float *b) { return (__float_as_uint(b[PPG_BLENDW_BITS]) & PPG_BLENDF_KIND) == 2u; }
+D int blend_n(const float *b) { return (int)((__float_as_uint(b[PPG_BLENDW_BITS]) >> PPG_BLENDF_N_SHIFT) & 7u); }
+// blendbsdf's weight: min(1, max(0, m_weight->eval(its).average())) (blendbsdf.cpp:136-137); a constant was clamped by ppg_set_scene
+D float blend_w(const DevScene &S, const Mat &M) {
+    const unsigned int tw = __float_as_uint(M.blend[PPG_BLENDW_TEX]);
+    float w = M.blend[PPG_BLENDW_WEIGHT + 1];
+    if (tw) { const float4 t = tex_eval_slot(S.textures, tw, M.bu, M.bv); w = avg3(f3(t.x, t.y, t.z)); }
+    return ppg_min(1.0f, ppg_max(0.0f, w));
+}
+// child i's factor in eval() and in pdf(): blend (1 - w, w) for both; mixture m_weights[i] and m_pdf[i] = cdf[i + 1] - cdf[i] (pmf.h:100)
+D void blend_weight(const float *b, bool mix, float w1, int i, float &we, float &wp) {
+    if (mix) { we = b[PPG_BLENDW_WEIGHT + i]; wp = b[PPG_BLENDW_CDF + i + 1] - b[PPG_BLENDW_CDF + i]; }
+    else { we = i == 0 ? 1 - w1 : w1; wp = we; }
+}
+D Mat blend_child(const DevScene &S, const Mat &M, int i) {
+    const int id = __float_as_int(M.blend[PPG_BLENDW_CHILD + i]);
+    Mat C = load_material(S, id);
+    const unsigned int tex = __float_as_uint(S.materials[PPG_MAT_STRIDE * (size_t)id + 5].x) & 0xffffu;
+    if (tex) { const float4 t = tex_eval_slot(S.textures, tex, M.bu, M.bv); C.refl = f3(t.x, t.y, t.z); }
+    mat_apply_textures(S, id, M.bu, M.bv, C);
+    mat_apply_mfd_textures(S, id, M.bu, M.bv, C);
+    return C;
+}
+// eval() / pdf() of a child under the discrete measure, which a blend asks of the children it did not sample after a delta sample:
+// conductor.cpp:223-252, plastic.cpp:245-307 (the mirror-direction test against DeltaEpsilon = 1e-3); every other child answers 0
+D float mat_mirror_error(F3 wi, F3 wo) { return ppg_abs(dot3(f3(-wi.x, -wi.y, wi.z), wo) - 1); }
+D F3 mat_eval_one_discrete(const Mat &C, F3 wi, F3 wo) {
+    if (C.type == PPG_BSDF_MIRROR || C.type == PPG_BSDF_CONDUCTOR) {
+        if (wi.z <= 0 || wo.z <= 0 || mat_mirror_error(wi, wo) > 1e-3f) return f3s(0.0f);
+        return mul3(C.refl, fresnel_conductor_exact(wi.z, C.eta, C.k));
+    }
+    if (C.type == PPG_BSDF_PLASTIC) {
+        if (wo.z <= 0 || wi.z <= 0) return f3s(0.0f);
+        const float Fi = fresnel_dielectric_ext(wi.z, C.eta.x);
+        if (mat_mirror_error(wi, wo) < 1e-3f) return C.spec * Fi;
+    }
+    return f3s(0.0f);
+}
+D float mat_pdf_one_discrete(const Mat &C, F3 wi, F3 wo) {
+    if (C.type == PPG_BSDF_MIRROR || C.type == PPG_BSDF_CONDUCTOR) {
+        if (wi.z <= 0 || wo.z <= 0 || mat_mirror_error(wi, wo) > 1e-3f) return 0.0f;
+        return 1.0f;
+    }
+    if (C.type == PPG_BSDF_PLASTIC) {
+        if (wo.z <= 0 || wi.z <= 0) return 0.0f;
+        const float Fi = fresnel_dielectric_ext(wi.z, C.eta.x);
+        if (mat_mirror_error(wi, wo) < 1e-3f) return plastic_prob_specular(C, Fi);
+    }
+    return 0.0f;
+}
+D F3 blend_eval(const DevScene &S, const Mat &M, F3 wi, F3 wo) {  // blendbsdf.cpp:139-142, mixturebsdf.cpp:177-179
+    const float *b = M.blend;
+    const bool mix = blend_is_mixture(b);
+    const int n = blend_n(b);
+    const float w1 = mix ? 0.0f : blend_w(S, M);
+    F3 result = f3s(0.0f);
+#pragma unroll 1
+    for (int i = 0; i < n && i < PPG_BLEND_MAX; ++i) {
+        float we, wp;
+        blend_weight(b, mix, w1, i, we, wp);
+        const Mat C = blend_child(S, M, i);
+        result = result + MAT_EVAL_ONE(C, wi, wo) * we;
+    }
+    return result;
+}
+D float blend_pdf(const DevScene &S, const Mat &M, F3 wi, F3 wo) {  // blendbsdf.cpp:160-163, mixturebsdf.cpp:194-196
+    const float *b = M.blend;
+    const bool mix = blend_is_mixture(b);
+    const int n = blend_n(b);
+    const float w1 = mix ? 0.0f : blend_w(S, M);
+    float result = 0.0f;
+#pragma unroll 1
+    for (int i = 0; i < n && i < PPG_BLEND_MAX; ++i) {
+        float we, wp;
+        blend_weight(b, mix, w1, i, we, wp);
+        const Mat C = blend_child(S, M, i);
+        result += MAT_PDF_ONE(C, wi, wo) * wp;
+    }
+    return result;
+}
+// sample(), the part before the chosen child's sample() (blendbsdf.cpp:229-235, mixturebsdf.cpp:248 with sampleReuse, pmf.h:183-188): the
+// child, the reused sample, and the child's factors in eval() and pdf()
+D int blend_sample_pre(const DevScene &S, const Mat &M, float &sx, float &w1, float &we, float &wp) {
+    const float *b = M.blend;
+    const bool mix = blend_is_mixture(b);
+    int entry;
+    w1 = 0.0f;
+    if (!mix) {
+        w1 = blend_w(S, M);
+        const float w0 = 1 - w1;
+        if (sx < w0) { entry = 0; sx /= w0; }
+        else { entry = 1; sx = (sx - w0) / w1; }
+    } else {
+        entry = pmf_sample(b + PPG_BLENDW_CDF, blend_n(b) + 1, sx);
+        // (a sample of 1 or more — none comes from the sampler — would walk past a last child of weight 0: the index stays in the table)
+        const int last = (blend_n(b) < PPG_BLEND_MAX ? blend_n(b) : PPG_BLEND_MAX) - 1;
+        if (entry > last) entry = last;
+        if (entry < 0) entry = 0;
+        const float c0 = b[PPG_BLENDW_CDF + entry], c1 = b[PPG_BLENDW_CDF + entry + 1];
+        sx = (sx - c0) / (c1 - c0);
+    }
+    blend_weight(b, mix, w1, entry, we, wp);
+    return entry;
+}
+// ... and the part after it (blendbsdf.cpp:237-253, mixturebsdf.cpp:250-266): the other children's pdf() and eval() in the measure of
+// what was sampled.  A sum that is not a positive finite density is a failed sample, where the reference would divide by it.
+D F3 blend_sample_post(const DevScene &S, const Mat &M, int entry, float w1, float we, float wp, F3 wi, F3 result, F3 &wo, float &pdf, bool &delta) {
+    const float *b = M.blend;
+    const bool mix = blend_is_mixture(b);
+    const int n = blend_n(b);
+    if (iszero3(result)) { wo = f3s(0.0f); pdf = 0.0f; delta = false; return f3s(0.0f); }
+    result = result * (we * pdf);
+    pdf *= wp;
+#pragma unroll 1
+    for (int i = 0; i < n && i < PPG_BLEND_MAX; ++i) {
+        if (i == entry) continue;
+        float wei, wpi;
+        blend_weight(b, mix, w1, i, wei, wpi);
+        const Mat C = blend_child(S, M, i);
+        if (delta) {
+            pdf += mat_pdf_one_discrete(C, wi, wo) * wpi;
+            result = result + mat_eval_one_discrete(C, wi, wo) * wei;
+        } else {
+            pdf += MAT_PDF_ONE(C, wi, wo) * wpi;
+            result = result + MAT_EVAL_ONE(C, wi, wo) * wei;
+        }
+    }
+    if (!(pdf > 0) || !ppg_isfinite(pdf)) { wo = f3s(0.0f); pdf = 0.0f; delta = false; return f3s(0.0f); }
+    return div3(result, pdf);
+}
+#else
+#define MAT_SCENE_PARAM
+#define MAT_SCENE_ARG
+#endif
+// + the TwoSided adapter (twosided.cpp:120-180) and, outside it, the Mask adapter (mask.cpp:108-214).  (MAT_SCENE_PARAM: the blend family's
+// functions also take the scene, whose tables a blended material's children are read from.)
+D F3 mat_eval(const Mat &M, F3 wi, F3 wo MAT_SCENE_PARAM) {
     if (mat_two_sided(M) && !(wi.z > 0)) { wi.z *= -1; wo.z *= -1; }
-#if PPG_COAT
+#if PPG_BLEND
+    F3 r = M.blend ? blend_eval(S, M, wi, wo) : (M.coat ? coat_eval(M, wi, wo) : MAT_EVAL_ONE(M, wi, wo));
+#elif PPG_COAT
     F3 r = M.coat ? coat_eval(M, wi, wo) : MAT_EVAL_ONE(M, wi, wo);
 #else
     F3 r = mat_eval_one(M, wi, wo);
 #endif
     return mat_masked(M) ? mul3(r, M.opacity) : r;
 }
-D float mat_pdf(const Mat &M, F3 wi, F3 wo) {
+D float mat_pdf(const Mat &M, F3 wi, F3 wo MAT_SCENE_PARAM) {
     if (mat_two_sided(M) && !(wi.z > 0)) { wi.z *= -1; wo.z *= -1; }
-#if PPG_COAT
+#if PPG_BLEND
+    float r = M.blend ? blend_pdf(S, M, wi, wo) : (M.coat ? coat_pdf(M, wi, wo) : MAT_PDF_ONE(M, wi, wo));
+#elif PPG_COAT
     float r = M.coat ? coat_pdf(M, wi, wo) : MAT_PDF_ONE(M, wi, wo);
 #else
     float r = mat_pdf_one(M, wi, wo);
@@ -2548,10 +2731,10 @@ D float mat_pdf(const Mat &M, F3 wi, F3 wo) {
     return mat_masked(M) ? r * lum3(M.opacity) : r;
 }
 D F3 mat_sample_ts(const Mat &M, F3 wi, float sx, float sy, F3 &wo, float &pdf, bool &delta, float &eta, bool &isnull, unsigned int key,
-                   unsigned int &dim);
+                   unsigned int &dim MAT_SCENE_PARAM);
 // key / dim: the path's sampler, for plug-ins whose sample() draws from it (roughdielectric)
 D F3 mat_sample(const Mat &M, F3 wi, float sx, float sy, F3 &wo, float &pdf, bool &delta, float &eta, bool &isnull, unsigned int key,
-                unsigned int &dim) {
+                unsigned int &dim MAT_SCENE_PARAM) {
     // (ONE call of the nested BSDF's sample(): see the note on code size in shade_one)
     const bool masked = mat_masked(M);
     const float prob = masked ? lum3(M.opacity) : 1.0f;
@@ -2564,17 +2747,29 @@ D F3 mat_sample(const Mat &M, F3 wi, float sx, float sy, F3 &wo, float &pdf, boo
         return div3(f3s(1.0f) - M.opacity, pdf);
     }
     if (masked) sx /= prob;
-    F3 result = mat_sample_ts(M, wi, sx, sy, wo, pdf, delta, eta, isnull, key, dim);
+    F3 result = mat_sample_ts(M, wi, sx, sy, wo, pdf, delta, eta, isnull, key, dim MAT_SCENE_ARG);
     if (masked) {
         result = div3(mul3(result, M.opacity), prob);
         pdf *= prob;
     }
     return result;
 }
+#if PPG_BLEND
+D F3 mat_sample_ts(const Mat &M0, F3 wi, float sx, float sy, F3 &wo, float &pdf, bool &delta, float &eta, bool &isnull, unsigned int key,
+                   unsigned int &dim MAT_SCENE_PARAM) {
+    bool flipped = false;
+    if (mat_two_sided(M0) && wi.z < 0) { wi.z *= -1; flipped = true; }
+    // (a blend chooses the child whose sample() runs — still the ONE call below — and adds the other children afterwards)
+    Mat M = M0;
+    int entry = 0;
+    float bw1 = 0.0f, bwe = 1.0f, bwp = 1.0f;
+    if (M0.blend) { entry = blend_sample_pre(S, M0, sx, bw1, bwe, bwp); M = blend_child(S, M0, entry); }
+#else
 D F3 mat_sample_ts(const Mat &M, F3 wi, float sx, float sy, F3 &wo, float &pdf, bool &delta, float &eta, bool &isnull, unsigned int key,
                    unsigned int &dim) {
     bool flipped = false;
     if (mat_two_sided(M) && wi.z < 0) { wi.z *= -1; flipped = true; }
+#endif
 #if PPG_COAT
     // (still ONE call of the nested sample(): a coat only changes its arguments before and its results after)
     F3 result, wiN = wi;
@@ -2596,6 +2791,9 @@ D F3 mat_sample_ts(const Mat &M, F3 wi, float sx, float sy, F3 &wo, float &pdf, 
     }
 #else
     F3 result = mat_sample_one(M, wi, sx, sy, wo, pdf, delta, eta, isnull, key, dim);
+#endif
+#if PPG_BLEND
+    if (M0.blend) result = blend_sample_post(S, M0, entry, bw1, bwe, bwp, wi, result, wo, pdf, delta);
 #endif
     if (flipped && !iszero3(result) && pdf != 0) wo.z *= -1;
     return result;

@@ -830,6 +830,8 @@ struct ppg_ctx {
     DevBuf<float4> d_mfd;
     std::vector<ppg_coating> coatings;  // ppg_set_coatings: kept until replaced; ppg_set_scene validates it and builds d_coat from it
     DevBuf<float4> d_coat;
+    std::vector<ppg_blend> blends;  // ppg_set_blends: kept until replaced; ppg_set_scene validates it and builds d_blend from it
+    DevBuf<float4> d_blend;
     uint32_t nMaterials = 0;       // of the scene set last (ppg_debug_bsdf checks its items against it)
     bool renderOpen = false;       // between ppg_begin_render and ppg_end_render
     int W = 0, H = 0;
@@ -1018,7 +1020,8 @@ PathKernels ppg_path_kernels[PPG_FAMILIES];  // filled by the units of ppg_inst.
 
 // The kernel family a scene runs: the lowest that has everything the scene needs (ppg_device.h).
 static int sceneFamily(const DevScene &S) {
-    if (S.coat) return PPG_FAMILY_COAT;        // a coated material: the coat family, whatever else the scene holds
+    if (S.blend) return PPG_FAMILY_BLEND;      // a blended material: the blend family, whatever else the scene holds
+    if (S.coat) return PPG_FAMILY_COAT;        // a coated material: the coat family, shapes and general entries or not
     if (S.mfd) return PPG_FAMILY_EXT;          // a general microfacet entry: the extended family, shapes or not
     if (S.n_shapes) return PPG_FAMILY_SHAPES;  // an analytic disk or cylinder
     return PPG_FAMILY_BASE;                    // (only here is a scene ever small, or without the FULL material set)
@@ -3234,6 +3237,124 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
         ctx->scene.coat = ctx->d_coat.p;
         ctx->fullMaterials = true;
     }
+    // ppg_set_blends: the blendbsdf / mixturebsdf combinators.  Everything the device code relies on is checked here — every child index,
+    // and that a child is a plain leaf —, so its loops over the children are bounded and nothing recurses.
+    bool anyBlend = false;
+    std::vector<float4> blendTab;
+    if (!ctx->blends.empty()) {
+        if (ctx->blends.size() != s->n_materials) {
+            ctx->error = "blends: the list has " + std::to_string(ctx->blends.size()) + " entries, the scene " + std::to_string(s->n_materials) + " materials";
+            return PPG_ERR_INVALID;
+        }
+        blendTab.assign(PPG_BLEND_STRIDE * (size_t)s->n_materials, make_float4(0, 0, 0, 0));
+        std::vector<unsigned char> readsBitmap(s->n_materials, 0), anisoChild(s->n_materials, 0);
+        const auto mtOf = [&](uint32_t i) { return ctx->materialTextures.empty() ? ppg_material_textures{0u, 0u, 0u, 0u} : ctx->materialTextures[i]; };
+        for (uint32_t i = 0; i < s->n_materials; ++i) {
+            const ppg_blend &b = ctx->blends[i];
+            const ppg_material &m = s->materials[i];
+            const std::string who = "material " + std::to_string(i) + ": blend: ";
+            if (b._reserved[0] || b._reserved[1] || b._reserved[2] || b._reserved[3]) { ctx->error = who + "_reserved must be 0"; return PPG_ERR_INVALID; }
+            if (b.kind == 0) continue;
+            if (b.kind != 1 && b.kind != 2) { ctx->error = who + "kind must be 0 (none), 1 (blendbsdf) or 2 (mixturebsdf)"; return PPG_ERR_INVALID; }
+            const char *name = b.kind == 1 ? "blendbsdf" : "mixturebsdf";
+            if (b.kind == 1 && b.n != 2) { ctx->error = who + "blendbsdf takes exactly two nested BSDFs (n = " + std::to_string(b.n) + ")"; return PPG_ERR_INVALID; }
+            if (b.n < 1 || b.n > PPG_BLEND_MAX) { ctx->error = who + "mixturebsdf takes 1 .. " + std::to_string(PPG_BLEND_MAX) + " nested BSDFs (n = " + std::to_string(b.n) + ")"; return PPG_ERR_INVALID; }
+            if (m.type != PPG_BSDF_DIFFUSE) { ctx->error = who + "the blended material's own record must be of type PPG_BSDF_DIFFUSE (it only carries the adapters)"; return PPG_ERR_INVALID; }
+            if (!ctx->coatings.empty() && ctx->coatings[i].kind) { ctx->error = who + "coating(" + name + ") is not supported"; return PPG_ERR_INVALID; }
+            if (m.texture & 0xffffu) { ctx->error = who + "a reflectance bitmap on the blended record itself is not supported (set it on a child)"; return PPG_ERR_INVALID; }
+            if (mtOf(i).specular || mtOf(i).alpha) { ctx->error = who + "a specular / alpha texture slot on the blended record itself is not supported (set it on a child)"; return PPG_ERR_INVALID; }
+            if (!ctx->microfacet.empty() && ctx->microfacet[i].general) { ctx->error = who + "a microfacet entry on the blended record itself is not supported (set it on a child)"; return PPG_ERR_INVALID; }
+            for (uint32_t k = 0; k < b.n; ++k) {
+                const uint32_t c = b.child[k];
+                const std::string kid = who + "child " + std::to_string(k) + " (material " + std::to_string(c) + ")";
+                if (c >= s->n_materials) { ctx->error = kid + ": index out of range"; return PPG_ERR_INVALID; }
+                const ppg_material &cm = s->materials[c];
+                if (ctx->blends[c].kind) { ctx->error = kid + " is itself blended: blends of blends are not supported"; return PPG_ERR_INVALID; }
+                if (!ctx->coatings.empty() && ctx->coatings[c].kind) { ctx->error = kid + " is coated: coated children are not supported"; return PPG_ERR_INVALID; }
+                if (cm.type == PPG_BSDF_DIELECTRIC || cm.type == PPG_BSDF_THINDIELECTRIC || cm.type == PPG_BSDF_ROUGHDIELECTRIC || cm.type < 0 || cm.type > PPG_BSDF_LAST) {
+                    ctx->error = kid + ": dielectric, thindielectric and roughdielectric children are not supported"; return PPG_ERR_INVALID;
+                }
+                if ((cm.flags & (PPG_MAT_TWOSIDED | PPG_MAT_MASK)) || cm.type == PPG_BSDF_TWOSIDED_DIFFUSE || (cm.texture >> 16)) {
+                    ctx->error = kid + " is masked, two-sided or bump-mapped: the adapters go around the blend, on its own record"; return PPG_ERR_INVALID;
+                }
+                if ((cm.texture & 0xffffu) || mtOf(c).specular || mtOf(c).alpha || (!ctx->microfacet.empty() && ctx->microfacet[c].general && ctx->microfacet[c].alpha_v_texture))
+                    readsBitmap[i] = 1;
+                if (!mfdTab.empty() && (__builtin_bit_cast(uint32_t, mfdTab[c].y) & PPG_MFDF_ANISO)) anisoChild[i] = 1;
+            }
+            for (uint32_t k = b.n; k < PPG_BLEND_MAX; ++k)
+                if (b.child[k] || b.weight[k] != 0.0f) { ctx->error = who + "child and weight beyond n must be 0"; return PPG_ERR_INVALID; }
+            float we[PPG_BLEND_MAX] = {0, 0, 0, 0}, cdf[PPG_BLEND_MAX + 1] = {0, 0, 0, 0, 0};
+            uint32_t weightTex = 0;
+            if (b.kind == 1) {
+                if (!std::isfinite(b.weight[0]) || b.weight[0] < 0) { ctx->error = who + "weight must be finite and not negative"; return PPG_ERR_INVALID; }
+                if (b.weight[1] != 0.0f) { ctx->error = who + "blendbsdf reads weight[0] only; weight[1] must be 0"; return PPG_ERR_INVALID; }
+                if (b.ensure_energy_conservation) { ctx->error = who + "ensure_energy_conservation belongs to mixturebsdf; must be 0"; return PPG_ERR_INVALID; }
+                if (b.weight_texture > s->n_textures || (b.weight_texture && !s->textures)) { ctx->error = who + "weight_texture: index out of range"; return PPG_ERR_INVALID; }
+                weightTex = b.weight_texture;
+                if (weightTex) readsBitmap[i] = 1;
+                const float w = ppg_min(1.0f, ppg_max(0.0f, b.weight[0]));  // blendbsdf.cpp:136-137
+                we[0] = 1 - w; we[1] = w;
+                cdf[1] = we[0]; cdf[2] = 1.0f;  // (the device chooses by sample.x < weights[0], as the plug-in does: not read)
+            } else {
+                if (b.weight_texture) { ctx->error = who + "weight_texture belongs to blendbsdf; must be 0"; return PPG_ERR_INVALID; }
+                float total = 0.0f;
+                for (uint32_t k = 0; k < b.n; ++k) {
+                    if (!std::isfinite(b.weight[k]) || b.weight[k] < 0) { ctx->error = who + "weights must be finite and not negative"; return PPG_ERR_INVALID; }
+                    we[k] = b.weight[k];
+                    total += we[k];  // mixturebsdf.cpp:123-125
+                }
+                if (!std::isfinite(total)) { ctx->error = who + "weights must be finite and not negative"; return PPG_ERR_INVALID; }
+                if (!(total > 0)) { ctx->error = who + "The weights must sum to a value greater than zero!"; return PPG_ERR_INVALID; }
+                if (b.ensure_energy_conservation && total > 1) {  // mixturebsdf.cpp:130-141
+                    const float scale = 1.0f / total;
+                    for (uint32_t k = 0; k < b.n; ++k) we[k] *= scale;
+                }
+                for (uint32_t k = 0; k < b.n; ++k) cdf[k + 1] = cdf[k] + we[k];  // DiscreteDistribution::append, pmf.h:68-70
+                const float norm = 1.0f / cdf[b.n];                                // ... ::normalize, pmf.h:101-114
+                for (uint32_t k = 1; k <= b.n; ++k) cdf[k] *= norm;
+                cdf[b.n] = 1.0f;
+            }
+            bool smoothAny = false;
+            for (uint32_t k = 0; k < b.n; ++k) {
+                const int t = s->materials[b.child[k]].type;
+                smoothAny = smoothAny || t == PPG_BSDF_DIFFUSE || t == PPG_BSDF_ROUGHCONDUCTOR || t == PPG_BSDF_PLASTIC || t == PPG_BSDF_ROUGHPLASTIC;
+            }
+            uint32_t bits = (uint32_t)b.kind | (b.n << PPG_BLENDF_N_SHIFT);
+            if (readsBitmap[i] || anisoChild[i]) bits |= PPG_BLENDF_TEXTURED;
+            if (smoothAny) bits |= PPG_BLENDF_SMOOTH;
+            float4 *row = &blendTab[PPG_BLEND_STRIDE * (size_t)i];
+            row[0] = make_float4(__builtin_bit_cast(float, b.child[0]), __builtin_bit_cast(float, b.child[1]), __builtin_bit_cast(float, b.child[2]), __builtin_bit_cast(float, b.child[3]));
+            row[1] = make_float4(we[0], we[1], we[2], we[3]);
+            row[2] = make_float4(cdf[0], cdf[1], cdf[2], cdf[3]);
+            row[3] = make_float4(cdf[4], __builtin_bit_cast(float, bits), __builtin_bit_cast(float, weightTex), 0.0f);
+            anyBlend = true;
+        }
+        for (uint32_t k = 0; anyBlend && k < s->n_spheres; ++k)
+            if (readsBitmap[s->spheres[k].material]) {
+                ctx->error = "sphere: material " + std::to_string(s->spheres[k].material) + ": blend: textured BSDFs are only supported on triangle meshes"; return PPG_ERR_INVALID;
+            }
+        for (size_t k = 0; anyBlend && k < ctx->shapes.size(); ++k)
+            if (readsBitmap[ctx->shapes[k].material]) {
+                ctx->error = "shape " + std::to_string(k) + ": material " + std::to_string(ctx->shapes[k].material) + ": blend: textured BSDFs are only supported on triangle meshes"; return PPG_ERR_INVALID;
+            }
+        for (uint32_t t = 0; anyBlend && t < s->n_triangles; ++t) {  // an anisotropic child needs UV tangents, as an anisotropic material does
+            if (!anisoChild[s->tri_material[t]]) continue;
+            bool has = s->texcoords != nullptr;
+            for (int v = 0; has && v < 3; ++v) { const float q = s->texcoords[2 * (size_t)s->indices[3 * (size_t)t + v]]; if (q != q) has = false; }
+            if (!has) {
+                ctx->error = "triangle " + std::to_string(t) + ": material " + std::to_string(s->tri_material[t]) +
+                             ": blend: anisotropic microfacet distribution: the mesh is missing texture coordinates! The tangent space cannot be computed";
+                return PPG_ERR_INVALID;
+            }
+        }
+    }
+    ctx->scene.blend = nullptr;
+    if (anyBlend) {
+        HIP_CHECK(ctx->d_blend.reserve(blendTab.size()));
+        HIP_CHECK(hipMemcpy(ctx->d_blend.p, blendTab.data(), blendTab.size() * sizeof(float4), hipMemcpyHostToDevice));
+        ctx->scene.blend = ctx->d_blend.p;
+        ctx->fullMaterials = true;
+    }
     ctx->scene.uvs = nullptr; ctx->scene.textures = nullptr;
     if (s->texcoords) {
         std::vector<float2> uv(3 * (size_t)s->n_triangles);
@@ -3837,6 +3958,13 @@ int ppg_set_coatings(ppg_ctx *ctx, const ppg_coating *c, uint32_t n_materials) {
     if (ctx->renderOpen) { ctx->error = "coatings: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
     if (!c) n_materials = 0;
     ctx->coatings.assign(c, c + n_materials);  // validated against the scene by ppg_set_scene
+    return PPG_OK;
+}
+
+int ppg_set_blends(ppg_ctx *ctx, const ppg_blend *b, uint32_t n_materials) {
+    if (ctx->renderOpen) { ctx->error = "blends: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (!b) n_materials = 0;
+    ctx->blends.assign(b, b + n_materials);  // validated against the scene by ppg_set_scene
     return PPG_OK;
 }
 

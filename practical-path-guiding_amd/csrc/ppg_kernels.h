@@ -429,6 +429,9 @@ struct SortArgs {
 #if PPG_COAT
     const float4 *coat;       // DevScene::coat: nor is a coated one
 #endif
+#if PPG_BLEND
+    const float4 *blend;      // DevScene::blend: nor a blended one
+#endif
 };
 D SortArgs sort_args(const PathState &P, const DevScene &S, const Queues &Q, unsigned int b, unsigned int *sorted, unsigned char *keys) {
     SortArgs a;
@@ -442,6 +445,9 @@ D SortArgs sort_args(const PathState &P, const DevScene &S, const Queues &Q, uns
 #if PPG_COAT
     a.coat = S.coat;
 #endif
+#if PPG_BLEND
+    a.blend = S.blend;
+#endif
     return a;
 }
 // is material m kept out of the COMMON classes by a side table of this family?  (no table, no question: false at compile time; one
@@ -453,6 +459,9 @@ D bool sort_side_table(const SortArgs &a, int m) {
 #endif
 #if PPG_COAT
     kept_out = kept_out || (a.coat && (__float_as_uint(a.coat[PPG_COAT_STRIDE * (size_t)m].w) & PPG_COATF_KIND) != 0u);
+#endif
+#if PPG_BLEND
+    kept_out = kept_out || (a.blend && (__float_as_uint(a.blend[PPG_BLEND_STRIDE * (size_t)m + 3].y) & PPG_BLENDF_KIND) != 0u);
 #endif
     return kept_out;
 }
@@ -901,6 +910,9 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
     Isect I;
     TexInfo X;
     X.tex = 0u;
+#if PPG_BLEND
+    X.u = 0.0f; X.v = 0.0f;  // (handed to a blended material whether or not anything reads it)
+#endif
     if (valid) {
         if (FULL && MSET != MSET_COMMON && h.prim >= S.n_tris) {
             const float4 ro4 = ray_origin();
@@ -1070,6 +1082,9 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
 #if PPG_MFD
         if (FULL && MSET != MSET_COMMON) mat_apply_mfd_textures(S, I.material, X.u, X.v, M);
 #endif
+#if PPG_BLEND
+        if (FULL) { M.bu = X.u; M.bv = X.v; }  // (the children of a blended material read their bitmaps at this hit's uv)
+#endif
         // (one call site per BSDF function: the bumped variant only transforms the arguments first — two inlined copies of the whole
         // material switch per function made the FULL kernels 330 KB of code, five times the instruction cache)
         auto to_pert = [&](F3 v_) { const F3 w_ = to_world(I, v_); return f3(dot3(w_, ps), dot3(w_, pt), dot3(w_, pn)); };
@@ -1080,7 +1095,7 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
                 wia = to_pert(wi_); woa = to_pert(wo_);
                 if (wo_.z * woa.z <= 0) return f3s(0.0f);
             }
-            return mat_eval(M, wia, woa);
+            return mat_eval(M, wia, woa MAT_SCENE_ARG);
         };
         auto b_pdf = [&](F3 wi_, F3 wo_) {
             if (!FULL) return bsdf_pdf(M.type, wi_, wo_);
@@ -1089,14 +1104,14 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
                 wia = to_pert(wi_); woa = to_pert(wo_);
                 if (wo_.z * woa.z <= 0) return 0.0f;
             }
-            return mat_pdf(M, wia, woa);
+            return mat_pdf(M, wia, woa MAT_SCENE_ARG);
         };
         float sampledEta = 1.0f;
         bool sampledNull = false;
         auto b_sample = [&](float u_, float v_, F3 &wo_, float &pdf_, bool &delta_) {
             if (!FULL) return bsdf_sample(M.type, M.refl, I.wi, u_, v_, wo_, pdf_, delta_);
             F3 wop = f3s(0.0f);
-            F3 result = mat_sample(M, bumped ? to_pert(I.wi) : I.wi, u_, v_, wop, pdf_, delta_, sampledEta, sampledNull, key, dim);
+            F3 result = mat_sample(M, bumped ? to_pert(I.wi) : I.wi, u_, v_, wop, pdf_, delta_, sampledEta, sampledNull, key, dim MAT_SCENE_ARG);
             if (bumped) {
                 if (!iszero3(result)) {
                     wo_ = to_local(I, ps * wop.x + pt * wop.y + pn * wop.z);

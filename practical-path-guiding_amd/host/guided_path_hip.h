@@ -58,6 +58,7 @@ struct SceneData {
     std::vector<ppg_microfacet> microfacet;  // the general microfacet entries (alphaU / alphaV, phong, sampleVisible = false): empty, or one
                                              // per material (ppg_set_microfacet, before ppg_set_scene)
     std::vector<ppg_coating> coatings;  // the coating / roughcoating adapters: empty, or one per material (ppg_set_coatings, before ppg_set_scene)
+    std::vector<ppg_blend> blends;      // the blendbsdf / mixturebsdf combinators: empty, or one per material (ppg_set_blends, before ppg_set_scene)
     std::vector<ppg_material_textures> materialTextures;  // bitmaps on specular / alpha / opacity: empty, or one entry per material
                                                           // (ppg_set_material_textures, before ppg_set_scene)
 
@@ -174,6 +175,7 @@ public:
         check(ppg_set_shapes(m_ctx, scene.shapes.data(), (uint32_t)scene.shapes.size()), "ppg_set_shapes");
         check(ppg_set_microfacet(m_ctx, scene.microfacet.data(), (uint32_t)scene.microfacet.size()), "ppg_set_microfacet");
         check(ppg_set_coatings(m_ctx, scene.coatings.data(), (uint32_t)scene.coatings.size()), "ppg_set_coatings");
+        check(ppg_set_blends(m_ctx, scene.blends.data(), (uint32_t)scene.blends.size()), "ppg_set_blends");
         check(ppg_set_scene(m_ctx, &sv), "ppg_set_scene");
         check(ppg_set_rfilter(m_ctx, scene.hasRFilter ? &scene.rfilter : nullptr), "ppg_set_rfilter");
         check(ppg_set_lens(m_ctx, scene.hasLens ? &scene.lens : nullptr), "ppg_set_lens");

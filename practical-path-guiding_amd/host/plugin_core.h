@@ -3,7 +3,7 @@
  * the integrator's properties to ppg_config, and the control flow of Integrator::render() / cancel() above the C-ABI —
  *
  *     configure(props)                       GuidedPathTracer(const Properties &), GP:1014-1085 (names and defaults verbatim)
- *     render(scene, destinationFile)         ppg_create → [ppg_set_delta_emitters → ppg_set_material_textures → ppg_set_shapes → ppg_set_microfacet → ppg_set_coatings →] ppg_set_scene → ppg_render, GP:1516-1585; the SD-tree dumps go to
+ *     render(scene, destinationFile)         ppg_create → [ppg_set_delta_emitters → ppg_set_material_textures → ppg_set_shapes → ppg_set_microfacet → ppg_set_coatings → ppg_set_blends →] ppg_set_scene → ppg_render, GP:1516-1585; the SD-tree dumps go to
  *                                            "<destinationFile>-NN.sdt" (GP:1191-1195), which is only known HERE — so the context is created
  *                                            here and not in the constructor (round 3's shim created it in the constructor and then changed a
  *                                            prefix the context had already copied: dumpSDTree through the plug-in wrote nothing)
@@ -75,6 +75,8 @@ public:
     void setMicrofacet(const ppg_microfacet *g, size_t n) { m_microfacet.assign(g, g + n); }
     // the coating / roughcoating adapters (ppg_set_coatings): one per material, or n = 0: none
     void setCoatings(const ppg_coating *c, size_t n) { m_coatings.assign(c, c + n); }
+    // the blendbsdf / mixturebsdf combinators (ppg_set_blends): one per material, or n = 0: none
+    void setBlends(const ppg_blend *b, size_t n) { m_blends.assign(b, b + n); }
     const ppg_config &config() const { return m_cfg; }
 
     // PPG_OK, PPG_ERR_CANCELLED, or an error code with `err` set.  May be called again (a new context per render, like a new RenderJob).
@@ -106,6 +108,8 @@ public:
         rc = ppg_set_microfacet(ctx, m_microfacet.data(), (uint32_t)m_microfacet.size());
         if (rc != PPG_OK) { err = ppg_last_error(ctx); return rc; }
         rc = ppg_set_coatings(ctx, m_coatings.data(), (uint32_t)m_coatings.size());
+        if (rc != PPG_OK) { err = ppg_last_error(ctx); return rc; }
+        rc = ppg_set_blends(ctx, m_blends.data(), (uint32_t)m_blends.size());
         if (rc != PPG_OK) { err = ppg_last_error(ctx); return rc; }
         rc = ppg_set_scene(ctx, &scene);  // (a cancel() during these seconds of BVH build stays set in the context: ppg_render returns at once)
         if (rc != PPG_OK) { err = ppg_last_error(ctx); return rc; }
@@ -156,6 +160,7 @@ private:
     std::vector<ppg_shape> m_shapes;
     std::vector<ppg_microfacet> m_microfacet;
     std::vector<ppg_coating> m_coatings;
+    std::vector<ppg_blend> m_blends;
     std::mutex m_mutex;
 };
 

@@ -139,7 +139,12 @@ static bool loadSceneChecked(const char *path, SceneData &s) {
         s.coatings.resize(nm);
         f.read((char *)s.coatings.data(), (std::streamsize)((size_t)nm * sizeof(ppg_coating)));
     }
-    if (hdr[5] >> 13) return false;  // a block this reader does not know
+    if (hdr[5] & 8192) {  // bit 13: the blends (n_materials x ppg_blend), only when a material is blended
+        if (!fits((uint64_t)nm * sizeof(ppg_blend))) return false;
+        s.blends.resize(nm);
+        f.read((char *)s.blends.data(), (std::streamsize)((size_t)nm * sizeof(ppg_blend)));
+    }
+    if (hdr[5] >> 14) return false;  // a block this reader does not know
     return (bool)f;
 }
 
@@ -211,7 +216,7 @@ static bool saveScene(const char *path, const SceneData &s) {
                              s.normals.empty() ? 0u : 1u, (s.hasEnvironment ? 1u : 0u) | (s.rtrans.empty() ? 0u : 2u) | (s.spheres.empty() ? 0u : 4u) | (s.hasEnvmap ? 8u : 0u) |
                                  (s.texcoords.empty() ? 0u : 16u) | (s.textures.empty() ? 0u : 32u) | (s.hasRFilter ? 64u : 0u) | (s.hasLens ? 128u : 0u) |
                                  (s.deltaEmitters.empty() ? 0u : 256u) | (s.materialTextures.empty() ? 0u : 512u) | (s.shapes.empty() ? 0u : 1024u) |
-                                 (s.microfacet.empty() ? 0u : 2048u) | (s.coatings.empty() ? 0u : 4096u)};
+                                 (s.microfacet.empty() ? 0u : 2048u) | (s.coatings.empty() ? 0u : 4096u) | (s.blends.empty() ? 0u : 8192u)};
     f.write("PPGS", 4); f.write((const char *)hdr, sizeof hdr);
     f.write((const char *)s.positions.data(), s.positions.size() * 4);
     if (!s.normals.empty()) f.write((const char *)s.normals.data(), s.normals.size() * 4);
@@ -263,6 +268,7 @@ static bool saveScene(const char *path, const SceneData &s) {
     }
     if (!s.microfacet.empty()) f.write((const char *)s.microfacet.data(), (std::streamsize)(s.microfacet.size() * sizeof(ppg_microfacet)));
     if (!s.coatings.empty()) f.write((const char *)s.coatings.data(), (std::streamsize)(s.coatings.size() * sizeof(ppg_coating)));
+    if (!s.blends.empty()) f.write((const char *)s.blends.data(), (std::streamsize)(s.blends.size() * sizeof(ppg_blend)));
     return (bool)f;
 }
 
@@ -364,6 +370,7 @@ int main(int argc, char **argv) {
         core.setShapes(scene.shapes.data(), scene.shapes.size());
         core.setMicrofacet(scene.microfacet.data(), scene.microfacet.size());
         core.setCoatings(scene.coatings.data(), scene.coatings.size());
+        core.setBlends(scene.blends.data(), scene.blends.size());
         core.setSeed((uint64_t)std::stoull(props.getString("seed", "0")));
         std::string dest = out;
         const size_t dot = dest.find_last_of('.');

@@ -22,6 +22,7 @@
 #include <functional>
 #include <limits>
 #include <map>
+#include <set>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -686,6 +687,14 @@ inline Mesh loadPLY(const std::string &path, const Mat4 &toWorld, bool faceNorma
 }
 
 // ------------------------------------------------------------------------------------------------ the scene
+// A blendbsdf / mixturebsdf as the loader builds it: the entry of ppg_set_blends without its child indices, and the children's own records
+// (ppg_material, ppg_microfacet), which join the material list behind everything a shape refers to.
+struct BlendSpec {
+    ppg_blend b{};
+    std::vector<ppg_material> kids;
+    std::vector<ppg_microfacet> kidMfd;
+};
+
 struct LoadedScene {
     SceneData scene;
     Properties integrator;          // guided_path properties as given in the XML
@@ -761,13 +770,14 @@ public:
             out.scene.hasLens = true;
             out.scene.lens.aperture_radius = r; out.scene.lens.focus_distance = focus;
         }
+        for (auto &c : root.children) if (c.tag == "texture" && c.attr("id")) m_textureIds.insert(c.get("id"));
         // bsdfs
-        for (auto &b : root.children) if (b.tag == "bsdf" && b.attr("id")) { const ppg_material bm = makeBsdfTop(b, out); m_byId[b.get("id")] = intern(bm, out, m_mfd, m_coat); }
+        for (auto &b : root.children) if (b.tag == "bsdf" && b.attr("id")) { const ppg_material bm = makeBsdfTop(b, out); m_byId[b.get("id")] = intern(bm, out, m_mfd, m_coat, m_blend); }
         {   // an id may also sit on a NESTED bsdf (KITCHEN references the twosided element inside a bumpmap): every element with an id is a named object
             std::function<void(const XmlNode &)> walk = [&](const XmlNode &n) {
                 for (auto &c : n.children) {
                     if (c.tag != "bsdf") continue;
-                    if (c.attr("id") && !m_byId.count(c.get("id"))) { const ppg_material bm = makeBsdfTop(c, out); m_byId[c.get("id")] = intern(bm, out, m_mfd, m_coat); }
+                    if (c.attr("id") && !m_byId.count(c.get("id"))) { const ppg_material bm = makeBsdfTop(c, out); m_byId[c.get("id")] = intern(bm, out, m_mfd, m_coat, m_blend); }
                     walk(c);
                 }
             };
@@ -950,7 +960,7 @@ public:
             }
             int mat = -1;
             for (auto &c : sh.children) {
-                if (c.tag == "bsdf") { const ppg_material bm = makeBsdfTop(c, out); mat = (int)intern(bm, out, m_mfd, m_coat); }
+                if (c.tag == "bsdf") { const ppg_material bm = makeBsdfTop(c, out); mat = (int)intern(bm, out, m_mfd, m_coat, m_blend); }
                 else if (c.tag == "ref") {
                     auto it = m_byId.find(c.get("id"));
                     if (it == m_byId.end()) throw std::runtime_error("<ref id=\"" + c.get("id") + "\">: no such bsdf");
@@ -1025,6 +1035,24 @@ public:
             for (uint32_t id : m.indices) S.indices.push_back(base + id);
             for (size_t t = 0; t < m.indices.size() / 3; ++t) { S.triMaterial.push_back(p.mat); S.triEmitter.push_back(p.em); }
         }
+        {   // the children of blended materials join the list here, in the blended materials' order (as bindings.expand_blends does)
+            const size_t n0 = S.materials.size();
+            std::vector<ppg_blend> blends(n0);
+            bool any = false;
+            for (size_t i = 0; i < n0; ++i) {
+                if (!m_blendOf[i].b.kind) continue;
+                any = true;
+                ppg_blend b = m_blendOf[i].b;
+                for (size_t k = 0; k < m_blendOf[i].kids.size(); ++k) {
+                    b.child[k] = (uint32_t)S.materials.size();
+                    S.materials.push_back(m_blendOf[i].kids[k]);
+                    m_mfdOf.push_back(m_blendOf[i].kidMfd[k]);
+                    m_coatOf.push_back(ppg_coating{});
+                }
+                blends[i] = b;
+            }
+            if (any) { blends.resize(S.materials.size()); S.blends = blends; }
+        }
         for (const ppg_microfacet &g : m_mfdOf) if (g.general) { S.microfacet = m_mfdOf; break; }  // one entry per material, or none
         for (const ppg_coating &c : m_coatOf) if (c.kind) { S.coatings = m_coatOf; break; }  // likewise
         out.warnings.insert(out.warnings.end(), m_lenientNotes.begin(), m_lenientNotes.end());
@@ -1045,6 +1073,9 @@ private:
     mutable ppg_microfacet m_mfd{};       // ... of the BSDF makeBsdf built last
     std::vector<ppg_coating> m_coatOf;    // per material: its coating / roughcoating (kind 0: none)
     mutable ppg_coating m_coat{};         // ... of the BSDF makeBsdf built last
+    std::vector<BlendSpec> m_blendOf;     // per material: its blendbsdf / mixturebsdf (kind 0: none)
+    std::set<std::string> m_textureIds;   // the ids of the scene's top-level <texture> elements
+    mutable BlendSpec m_blend;            // ... of the BSDF makeBsdf built last
 
     void collectDefaults(const XmlNode &n) {
         if (n.tag == "default" && n.attr("name") && !m_params.count(n.get("name"))) m_params[n.get("name")] = n.get("value");
@@ -1524,7 +1555,100 @@ private:
     }
     // (the general microfacet entry of the BSDF it built last — at most one rough plug-in sits inside the adapters — is left in m_mfd, its
     // coating / roughcoating in m_coat)
-    ppg_material makeBsdfTop(const XmlNode &e, LoadedScene &out) const { m_mfd = ppg_microfacet{}; m_coat = ppg_coating{}; return makeBsdf(e, true, out); }
+    ppg_material makeBsdfTop(const XmlNode &e, LoadedScene &out) const { m_mfd = ppg_microfacet{}; m_coat = ppg_coating{}; m_blend = BlendSpec{}; return makeBsdf(e, true, out); }
+    // The blended material's own record — diffuse, carrying nothing but the adapters that go around it — with the combinator left in m_blend
+    // (the same rules as ppg_host/mitsuba_xml.py).  The nesting order this build knows is bumpmap(mask(twosided(blend(leaf, ..)))); a child is
+    // a nested <bsdf> or a <ref> to a <bsdf> with an id that stands before it.
+    ppg_material blended(const XmlNode &e, std::map<std::string, std::string> &p, const std::string &t, LoadedScene &out) const {
+        std::vector<const XmlNode *> in;
+        for (auto &c : e.children)  // (a <ref> to a texture is no child: as ppg_host/mitsuba_xml.py skips it)
+            if (c.tag == "bsdf" || (c.tag == "ref" && c.get("name") != "weight" && !m_textureIds.count(c.get("id")))) in.push_back(&c);
+        if (in.size() > PPG_BLEND_MAX) throw std::runtime_error(t + ": more than 4 nested bsdfs are not supported (found " + std::to_string(in.size()) + ")");
+        if (t == "blendbsdf" && in.size() != 2)
+            throw std::runtime_error("blendbsdf: BSDF count mismatch: expected two nested BSDF instances! (found " + std::to_string(in.size()) + ")");
+        BlendSpec spec;
+        for (const XmlNode *c : in) {
+            ppg_material m{};
+            ppg_microfacet g{};
+            std::string it;
+            bool isBlend = false, isCoated = false;
+            if (c->tag == "ref") {
+                auto f = m_byId.find(c->get("id"));
+                if (f == m_byId.end()) throw std::runtime_error(t + ": <ref id=\"" + c->get("id") + "\">: no such bsdf before it");
+                it = "ref " + c->get("id");
+                m = out.scene.materials[f->second]; g = m_mfdOf[f->second];
+                isBlend = m_blendOf[f->second].b.kind != 0; isCoated = m_coatOf[f->second].kind != 0;
+            } else {
+                it = c->get("type");
+                if (it == "twosided" || it == "mask" || it == "bumpmap")
+                    throw std::runtime_error(t + "(" + it + ") is not supported: the nesting order is bumpmap(mask(twosided(" + t + "(..))))");
+                m_mfd = ppg_microfacet{}; m_coat = ppg_coating{}; m_blend = BlendSpec{};
+                m = makeBsdf(*c, false, out);
+                g = m_mfd;
+                isBlend = m_blend.b.kind != 0; isCoated = m_coat.kind != 0;
+            }
+            m_mfd = ppg_microfacet{}; m_coat = ppg_coating{}; m_blend = BlendSpec{};
+            if (isBlend) throw std::runtime_error(t + "(" + it + "): blends of blends are not supported");
+            if (isCoated) throw std::runtime_error(t + "(" + it + "): coated children are not supported");
+            if (m.type == PPG_BSDF_DIELECTRIC || m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_ROUGHDIELECTRIC)
+                throw std::runtime_error(t + "(" + it + "): dielectric, thindielectric and roughdielectric children are not supported");
+            if (m.type == PPG_BSDF_TWOSIDED_DIFFUSE || (m.flags & (PPG_MAT_TWOSIDED | PPG_MAT_MASK)) || (m.texture >> 16))
+                throw std::runtime_error(t + "(" + it + ") is not supported: the nesting order is bumpmap(mask(twosided(" + t + "(..))))");
+            spec.kids.push_back(m);
+            spec.kidMfd.push_back(g);
+        }
+        ppg_blend &b = spec.b;
+        b.n = (uint32_t)in.size();
+        if (t == "blendbsdf") {
+            b.kind = 1;
+            if (p.count("weight")) {
+                char *end = nullptr;
+                const std::string ws = p["weight"];
+                b.weight[0] = (float)strtod(ws.c_str(), &end);
+                if (ws.empty() || *end != '\0') throw std::runtime_error("blendbsdf: Could not parse the weight!");
+            } else b.weight[0] = 0.5f;
+            for (auto &c : e.children)
+                if ((c.tag == "texture" || c.tag == "ref") && c.get("name") == "weight") {  // (this loader reads no bitmaps)
+                    if (m_strict) throw std::runtime_error("blendbsdf: textured 'weight' is not supported (SURVEY.md §8 f1)");
+                    m_lenientNotes.push_back("texture on 'weight' ignored: the plug-in's default value is used");
+                    b.weight[0] = 0.5f;
+                }
+            if (!std::isfinite(b.weight[0]) || b.weight[0] < 0) throw std::runtime_error("blendbsdf: weight must be finite and not negative");
+        } else {
+            b.kind = 2;
+            const std::string ws = p.count("weights") ? p["weights"] : "";
+            std::vector<float> w;
+            size_t pos = 0;
+            while (pos < ws.size()) {  // tokenize(.., " ,;"), mixturebsdf.cpp:70-84
+                const size_t a = ws.find_first_not_of(" ,;", pos);
+                if (a == std::string::npos) break;
+                size_t z = ws.find_first_of(" ,;", a);
+                if (z == std::string::npos) z = ws.size();
+                const std::string tok = ws.substr(a, z - a);
+                char *end = nullptr;
+                const double v = strtod(tok.c_str(), &end);
+                if (*end != '\0') throw std::runtime_error("mixturebsdf: Could not parse the BSDF weights!");
+                w.push_back((float)v);
+                pos = z;
+            }
+            if (w.empty()) throw std::runtime_error("mixturebsdf: No weights were supplied!");
+            if (w.size() != in.size())
+                throw std::runtime_error("mixturebsdf: BSDF count mismatch: " + std::to_string(in.size()) + " bsdfs, but specified " + std::to_string(w.size()) + " weights");
+            double sum = 0;
+            for (size_t k = 0; k < w.size(); ++k) {
+                if (!std::isfinite(w[k]) || w[k] < 0) throw std::runtime_error("mixturebsdf: weights must be finite and not negative");
+                b.weight[k] = w[k];
+                sum += w[k];
+            }
+            if (!(sum > 0)) throw std::runtime_error("mixturebsdf: The weights must sum to a value greater than zero!");
+            b.ensure_energy_conservation = flag(p, "ensureEnergyConservation", true) ? 1 : 0;
+        }
+        m_blend = spec;
+        ppg_material m{};
+        m.type = PPG_BSDF_DIFFUSE; defaults(m);
+        m.reflectance[0] = m.reflectance[1] = m.reflectance[2] = 0.5f;
+        return m;
+    }
     // The nested BSDF's record, with the adapter's parameters left in m_coat (ppg_coating; the same rules as ppg_host/mitsuba_xml.py).  The
     // nesting order this build knows is bumpmap(mask(twosided(coating(leaf)))); the plug-ins' parameters are constants.
     ppg_material coated(const XmlNode &e, std::map<std::string, std::string> &p, const std::string &t, const std::vector<const XmlNode *> &in, LoadedScene &out) const {
@@ -1532,6 +1656,7 @@ private:
         const std::string it = in[0]->get("type");
         if (it == "coating" || it == "roughcoating" || it == "twosided" || it == "mask" || it == "bumpmap")
             throw std::runtime_error(t + "(" + it + ") is not supported: the nesting order is bumpmap(mask(twosided(coating(..))))");
+        if (it == "blendbsdf" || it == "mixturebsdf") throw std::runtime_error(t + "(" + it + ") is not supported: neither a coat around a blend nor a coated child");
         for (auto &c : e.children)
             if ((c.tag == "texture" || c.tag == "ref") && c.attr("name") &&
                 (c.get("name") == "sigmaA" || c.get("name") == "specularReflectance" || c.get("name") == "alpha" || c.get("name") == "alphaU" || c.get("name") == "alphaV"))
@@ -1593,7 +1718,7 @@ private:
             if (in.size() == 1) {
                 m = makeBsdf(*in[0], false, out);
                 if (m.type == PPG_BSDF_DIELECTRIC || m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_ROUGHDIELECTRIC) throw std::runtime_error("twosided(dielectric): only BRDFs can be two-sided (twosided.cpp:84-88)");
-                if (m.type == PPG_BSDF_DIFFUSE && !(m.flags & PPG_MAT_MASK)) { m.type = PPG_BSDF_TWOSIDED_DIFFUSE; return m; }
+                if (m.type == PPG_BSDF_DIFFUSE && !(m.flags & PPG_MAT_MASK) && !m_blend.b.kind) { m.type = PPG_BSDF_TWOSIDED_DIFFUSE; return m; }
                 m.flags |= PPG_MAT_TWOSIDED;
                 return m;
             }
@@ -1679,6 +1804,17 @@ private:
                 }
             }
         }
+        if (t == "blendbsdf" || t == "mixturebsdf") {  // BlendBSDF (blendbsdf.cpp:70-133), MixtureBSDF (mixturebsdf.cpp:64-172): where a leaf stands
+            try { return blended(e, p, t, out); }
+            catch (const std::runtime_error &ex) {
+                if (m_strict) throw;
+                m_mfd = ppg_microfacet{}; m_coat = ppg_coating{}; m_blend = BlendSpec{};
+                out.warnings.push_back("bsdf '" + t + "' replaced by diffuse(0.5) (" + ex.what() + ")");
+                m = ppg_material{}; m.type = PPG_BSDF_DIFFUSE; defaults(m);
+                m.reflectance[0] = m.reflectance[1] = m.reflectance[2] = 0.5f;
+                return m;
+            }
+        }
         if (!m_strict && (t == "bumpmap" || t == "normalmap")) {  // adapters around one nested BSDF: render the nested one
             auto in = inner();
             if (in.size() == 1) { out.warnings.push_back("bsdf '" + t + "' dropped around its nested bsdf"); return makeBsdf(*in[0], allowWrap, out); }
@@ -1693,7 +1829,7 @@ public:
     // The <bsdf> element carrying `id` (at any nesting depth: every element with an id is a named object in Mitsuba) as a ppg_material;
     // rough-transmittance slices it needs are appended to out.scene.rtrans.  Used by the Mitsuba plug-in shim
     // (mitsuba_plugin/guided_path_hip.cpp), which cannot reach the nested BSDF of an adapter through Mitsuba's API.
-    bool bsdfById(const std::string &id, LoadedScene &out, ppg_material &m, ppg_microfacet *g = nullptr, ppg_coating *k = nullptr) {
+    bool bsdfById(const std::string &id, LoadedScene &out, ppg_material &m, ppg_microfacet *g = nullptr, ppg_coating *k = nullptr, BlendSpec *bl = nullptr) {
         std::ifstream f(m_path, std::ios::binary);
         if (!f) throw std::runtime_error("cannot open '" + m_path + "'");
         std::stringstream ss; ss << f.rdbuf();
@@ -1702,6 +1838,7 @@ public:
         size_t slash = m_path.find_last_of('/');
         m_base = slash == std::string::npos ? "." : m_path.substr(0, slash);
         collectDefaults(root);
+        for (auto &c : root.children) if (c.tag == "texture" && c.attr("id")) m_textureIds.insert(c.get("id"));
         const XmlNode *found = nullptr;
         std::function<void(const XmlNode &)> walk = [&](const XmlNode &n) {
             for (auto &c : n.children) {
@@ -1716,6 +1853,8 @@ public:
         else if (m_mfd.general) throw std::runtime_error("bsdf '" + id + "': alphaU / alphaV, distribution = phong and sampleVisible = false are not carried through this interface");
         if (k) *k = m_coat;
         else if (m_coat.kind) throw std::runtime_error("bsdf '" + id + "': coating / roughcoating are not carried through this interface");
+        if (bl) *bl = m_blend;
+        else if (m_blend.b.kind) throw std::runtime_error("bsdf '" + id + "': blendbsdf / mixturebsdf are not carried through this interface");
         return true;
     }
     // The ppg_material of a <bsdf> element that is not in a file: the plug-in shim builds one from a flat plug-in's Properties (a BSDF
@@ -1727,22 +1866,31 @@ public:
         else if (m_mfd.general) throw std::runtime_error("alphaU / alphaV, distribution = phong and sampleVisible = false are not carried through this interface");
         if (k) *k = m_coat;
         else if (m_coat.kind) throw std::runtime_error("coating / roughcoating are not carried through this interface");
+        if (m_blend.b.kind) throw std::runtime_error("blendbsdf / mixturebsdf are not carried through this interface");
         return m;
     }
 private:
-    // EAnisotropic of the material's BSDF: alphaU != alphaV (this loader reads no bitmaps on them)
+    // EAnisotropic of the material's BSDF: alphaU != alphaV (this loader reads no bitmaps on them); of a blended material: of any child
     bool anisotropic(uint32_t mat, const LoadedScene &out) const {
+        const BlendSpec &bl = m_blendOf[mat];
+        for (size_t k = 0; k < bl.kids.size(); ++k)
+            if (bl.kidMfd[k].general && std::max(bl.kidMfd[k].alpha_v, 1e-4f) != std::max(bl.kids[k].alpha, 1e-4f)) return true;
         return m_mfdOf[mat].general && std::max(m_mfdOf[mat].alpha_v, 1e-4f) != std::max(out.scene.materials[mat].alpha, 1e-4f);
     }
-    uint32_t intern(const ppg_material &m, LoadedScene &out, const ppg_microfacet &g = ppg_microfacet{}, const ppg_coating &coat = ppg_coating{}) {
+    uint32_t intern(const ppg_material &m, LoadedScene &out, const ppg_microfacet &g = ppg_microfacet{}, const ppg_coating &coat = ppg_coating{},
+                    const BlendSpec &blend = BlendSpec{}) {
         std::string key((const char *)&m, sizeof m);
         key.append((const char *)&g, sizeof g);
         key.append((const char *)&coat, sizeof coat);
+        key.append((const char *)&blend.b, sizeof blend.b);
+        for (const ppg_material &c : blend.kids) key.append((const char *)&c, sizeof c);
+        for (const ppg_microfacet &c : blend.kidMfd) key.append((const char *)&c, sizeof c);
         for (size_t i = 0; i < m_matKeys.size(); ++i) if (m_matKeys[i] == key) return (uint32_t)i;
         m_matKeys.push_back(key);
         out.scene.materials.push_back(m);
         m_mfdOf.push_back(g);
         m_coatOf.push_back(coat);
+        m_blendOf.push_back(blend);
         return (uint32_t)m_matKeys.size() - 1;
     }
 };
@@ -1759,11 +1907,11 @@ inline bool bsdfFromProperties(const std::string &plugin, const std::vector<Bsdf
 // rtrans already moved to the row of data.rtrans)
 
 inline bool bsdfById(const std::string &scenePath, const std::string &id, const std::string &dataDir, SceneData &data, ppg_material &m, std::string &why,
-                     ppg_microfacet *g = nullptr, ppg_coating *k = nullptr) {
+                     ppg_microfacet *g = nullptr, ppg_coating *k = nullptr, BlendSpec *bl = nullptr) {
     try {
         SceneXmlLoader loader(scenePath, {}, true, 0, 0, dataDir);
         LoadedScene tmp;
-        if (!loader.bsdfById(id, tmp, m, g, k)) return false;
+        if (!loader.bsdfById(id, tmp, m, g, k, bl)) return false;
         if (!tmp.scene.rtrans.empty()) {
             if (data.rtransSamples && data.rtransSamples != tmp.scene.rtransSamples) { why = "rough-transmittance tables of different resolutions"; return false; }
             const uint32_t have = data.rtransSamples ? (uint32_t)(data.rtrans.size() / (data.rtransSamples + 1)) : 0u;
@@ -1771,6 +1919,7 @@ inline bool bsdfById(const std::string &scenePath, const std::string &id, const 
             data.rtrans.insert(data.rtrans.end(), tmp.scene.rtrans.begin(), tmp.scene.rtrans.end());
             if (m.type == PPG_BSDF_ROUGHPLASTIC) m.rtrans += (int32_t)have;
             if (k && k->kind == 2) k->rtrans += (int32_t)have;
+            if (bl) for (ppg_material &c : bl->kids) if (c.type == PPG_BSDF_ROUGHPLASTIC) c.rtrans += (int32_t)have;
         }
         return true;
     } catch (const std::exception &e) {

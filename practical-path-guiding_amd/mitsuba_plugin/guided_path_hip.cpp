@@ -93,6 +93,13 @@ public:
             else data.coatings.clear();
             m_core.setCoatings(data.coatings.data(), data.coatings.size());
         }
+        {   /* the blendbsdf / mixturebsdf combinators materialOf() collected, likewise */
+            bool any = false;
+            for (size_t k = 0; k < data.blends.size(); ++k) any = any || data.blends[k].kind != 0;
+            if (any) data.blends.resize(data.materials.size());
+            else data.blends.clear();
+            m_core.setBlends(data.blends.data(), data.blends.size());
+        }
         Log(EInfo, "Starting render job (%ix%i, MI355X, %i triangles, %i analytic spheres) ..", film->getCropSize().x, film->getCropSize().y,
             (int) (data.indices.size() / 3), (int) data.spheres.size());
         /* create → scene → render; SD-tree dumps to "<dest>-NN.sdt" (GP:1192-1195) */
@@ -135,14 +142,16 @@ private:
         ppg_material m; memset(&m, 0, sizeof m);
         ppg_microfacet g; memset(&g, 0, sizeof g);   /* alphaU / alphaV, phong, sampleVisible = false (ppg_set_microfacet) */
         ppg_coating coat; memset(&coat, 0, sizeof coat);   /* a coating / roughcoating around it (ppg_set_coatings) */
+        ppg::BlendSpec blend;                               /* a blendbsdf / mixturebsdf in its place, with its children (ppg_set_blends) */
         const Properties &p = bsdf->getProperties();
         const std::string plugin = p.getPluginName();
         bool ok = false;
-        if (plugin == "twosided" || plugin == "mask" || plugin == "bumpmap" || plugin == "coating" || plugin == "roughcoating" || p.getID() != "unnamed") {
+        if (plugin == "twosided" || plugin == "mask" || plugin == "bumpmap" || plugin == "coating" || plugin == "roughcoating" || plugin == "blendbsdf" ||
+            plugin == "mixturebsdf" || p.getID() != "unnamed") {
             /* the nested BSDF is not reachable through Mitsuba's API: read the element with this id from the scene file.  ppg::xml::SceneLoader
                is the loader behind `ppg_render scene.xml`; bsdfById() returns the ppg_material it makes of that <bsdf> element (incl. the
                rough-transmittance slice of a roughplastic, appended to data.rtrans, and its textures, appended to data.textures) */
-            ok = ppg::xml::bsdfById(scene->getSourceFile().string(), p.getID(), m_dataDir(), data, m, why, &g, &coat);
+            ok = ppg::xml::bsdfById(scene->getSourceFile().string(), p.getID(), m_dataDir(), data, m, why, &g, &coat, &blend);
         }
         if (!ok) {
             /* A flat plug-in without an id: its Properties are the parameters the scene file gave it.  They are handed to the scene loader's own
@@ -184,8 +193,18 @@ private:
         data.microfacet.back() = g;
         data.coatings.resize(data.materials.size());
         data.coatings.back() = coat;
-        cache[bsdf] = (int) data.materials.size() - 1;
-        return cache[bsdf];
+        const int self = (int) data.materials.size() - 1;
+        for (size_t k = 0; k < blend.kids.size(); ++k) {   /* a blend's children are materials of their own, behind it */
+            blend.b.child[k] = (uint32_t) data.materials.size();
+            data.materials.push_back(blend.kids[k]);
+            data.microfacet.resize(data.materials.size());
+            data.microfacet.back() = blend.kidMfd[k];
+            data.coatings.resize(data.materials.size());
+        }
+        data.blends.resize(data.materials.size());
+        data.blends[self] = blend.b;
+        cache[bsdf] = self;
+        return self;
     }
 
     static std::string m_dataDir() {    /* data/microfacet/*.dat, data/ior/*.spd of the running Mitsuba */

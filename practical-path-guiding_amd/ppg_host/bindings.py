@@ -64,7 +64,8 @@ class Material(C.Structure):
     """ppg_material (include/ppg.h).  Scene descriptions carry materials as dicts: type, reflectance and — by type —
     specular, alpha, eta (3 values, or one number for plastic / dielectric), k, twosided, nonlinear, opacity (a mask adapter), distribution ("ggx" | "beckmann"), rtrans (roughplastic: row of SceneDesc.rtrans).
     The rest of the microfacet model travels beside it (Microfacet): alpha_v, distribution = "phong", sample_visible; so does a coating /
-    roughcoating adapter around the BSDF (Coating): coating = dict(kind, eta, ...)."""
+    roughcoating adapter around the BSDF (Coating): coating = dict(kind, eta, ...), and a blendbsdf / mixturebsdf of other materials (Blend):
+    blend = dict(kind, children, ...)."""
     _fields_ = [("type", C.c_int32), ("reflectance", C.c_float * 3), ("specular", C.c_float * 3), ("alpha", C.c_float),
                 ("eta", C.c_float * 3), ("k", C.c_float * 3), ("flags", C.c_int32), ("rtrans", C.c_int32),
                 ("opacity", C.c_float * 3), ("texture", C.c_uint32)]
@@ -182,6 +183,89 @@ class Coating(C.Structure):
             d.update(alpha=float(self.alpha), distribution={0: "beckmann", 1: "ggx", 2: "phong"}.get(self.distribution, self.distribution),
                      sample_visible=not self.sample_all, slice=int(self.rtrans))
         return d
+
+
+class Blend(C.Structure):
+    """ppg_blend (include/ppg.h): per material, Mitsuba's `blendbsdf` / `mixturebsdf` over other entries of the material list.  Material
+    dicts state it as blend = dict(kind = "blendbsdf" | "mixturebsdf" (or 1 | 2; 0: none), children = [material dicts, or indices into the
+    material list], and — blendbsdf — weight (0.5), weight_texture (index into SceneDesc.textures, or None) or — mixturebsdf — weights (one
+    per child) and ensure_energy_conservation (True)).  The dict that carries it is the blended material's own record: type 0, with
+    twosided / opacity / opacity_texture / bump around the blend.  expand_blends appends children given as dicts to the material list; a
+    dict without the key gets an all-zero entry."""
+    _fields_ = [("kind", C.c_int32), ("n", C.c_uint32), ("child", C.c_uint32 * 4), ("weight", C.c_float * 4), ("weight_texture", C.c_uint32),
+                ("ensure_energy_conservation", C.c_int32), ("_reserved", C.c_uint32 * 4)]
+
+    KINDS = {"none": 0, "blendbsdf": 1, "mixturebsdf": 2}
+    MAX = 4  # PPG_BLEND_MAX
+
+    @classmethod
+    def from_dict(cls, m):
+        """m: a material dict (its `blend` key) or the blend dict itself, its children given as indices"""
+        b = m if (m is not None and "children" in m) else (m or {}).get("blend")
+        o = cls()
+        if b is None:
+            return o
+        k = b.get("kind", 1)
+        o.kind = cls.KINDS[k] if isinstance(k, str) else int(k)
+        if o.kind == 0:
+            return o
+        kids = list(b["children"])
+        if any(isinstance(c, dict) for c in kids):
+            raise ValueError("blend: children given as dicts belong to a material list (bindings.expand_blends)")
+        if len(kids) > cls.MAX:
+            raise ValueError("blend: more than %d children are not supported (found %d)" % (cls.MAX, len(kids)))
+        o.n = len(kids)
+        for i, c in enumerate(kids):
+            o.child[i] = int(c)
+        if o.kind == 1:
+            o.weight[0] = float(b.get("weight", 0.5))
+            t = b.get("weight_texture")
+            o.weight_texture = 0 if t is None else int(t) + 1
+        else:
+            w = [float(v) for v in b.get("weights", [])]
+            if len(w) != len(kids):
+                raise ValueError("blend: BSDF count mismatch: %d bsdfs, but specified %d weights" % (len(kids), len(w)))
+            for i, v in enumerate(w):
+                o.weight[i] = v
+            o.ensure_energy_conservation = 1 if b.get("ensure_energy_conservation", True) else 0
+        return o
+
+    def as_dict(self):
+        """the material dict's `blend` value (None for kind 0)"""
+        if self.kind == 0:
+            return None
+        d = dict(kind={1: "blendbsdf", 2: "mixturebsdf"}.get(self.kind, self.kind), children=[int(self.child[i]) for i in range(min(self.n, self.MAX))])
+        if self.kind == 1:
+            d.update(weight=float(self.weight[0]), weight_texture=int(self.weight_texture) - 1 if self.weight_texture else None)
+        else:
+            d.update(weights=[float(self.weight[i]) for i in range(min(self.n, self.MAX))], ensure_energy_conservation=bool(self.ensure_energy_conservation))
+        return d
+
+
+def has_blends(desc):
+    """Whether a material of `desc` carries a `blend` entry (what the CPU oracle does not implement)."""
+    return any(m.get("blend") is not None for m in desc.materials)
+
+
+def expand_blends(materials):
+    """The material list with the children that blended materials state as dicts appended to it, in order, and named by their indices:
+    what the C-ABI and the flat scene file hold.  A list without such children comes back as it is."""
+    if not any(isinstance(c, dict) for m in materials if m.get("blend") is not None for c in m["blend"].get("children", [])):
+        return materials
+    out = list(materials)
+    for i, m in enumerate(materials):
+        b = m.get("blend")
+        if b is None:
+            continue
+        kids = []
+        for c in b.get("children", []):
+            if isinstance(c, dict):
+                out.append(c)
+                kids.append(len(out) - 1)
+            else:
+                kids.append(int(c))
+        out[i] = dict(m, blend=dict(b, children=kids))
+    return out
 
 
 def has_coatings(desc):
@@ -527,6 +611,12 @@ class Engine:
 
     # -- scene -------------------------------------------------------------------------------
     def set_scene(self, desc):
+        if has_blends(desc):  # children stated as dicts join the material list
+            if self.prefix != "ppg_":
+                raise NotImplementedError("%s: the blendbsdf / mixturebsdf combinators are not implemented here" % self.prefix)
+            import copy
+            desc = copy.copy(desc)
+            desc.materials = expand_blends(desc.materials)
         s = Scene()
         pos = np.ascontiguousarray(desc.positions, np.float32)
         idx = np.ascontiguousarray(desc.indices, np.uint32)
@@ -616,6 +706,10 @@ class Engine:
             self.set_coatings(explicit if explicit is not None else (desc.materials if has_coatings(desc) else []))
         elif has_coatings(desc):
             raise NotImplementedError("%s: the coating / roughcoating adapters are not implemented here" % self.prefix)
+        # the blends, likewise (or the list itself, as `blends`: Blend records or dicts)
+        if self.prefix == "ppg_":
+            explicit = getattr(desc, "blends", None)
+            self.set_blends(explicit if explicit is not None else (desc.materials if has_blends(desc) else []))
         self._call("set_scene", C.byref(s))
         self.width, self.height = cam["width"], cam["height"]
         # the film's reconstruction filter comes with the scene description (None / absent: the default box)
@@ -698,6 +792,15 @@ class Engine:
         for i, d in enumerate(entries):
             arr[i] = d if isinstance(d, Coating) else Coating.from_dict(d)
         self._call("set_coatings", arr, C.c_uint32(len(entries)))
+
+    def set_blends(self, entries):
+        """ppg_set_blends: one entry per material — a material dict (its `blend` key, children as indices), a blend dict or a Blend; an empty
+        list clears it.  Takes effect at, and is validated by, the next set_scene."""
+        entries = list(entries or [])
+        arr = (Blend * max(1, len(entries)))()
+        for i, d in enumerate(entries):
+            arr[i] = d if isinstance(d, Blend) else Blend.from_dict(d)
+        self._call("set_blends", arr, C.c_uint32(len(entries)))
 
     def debug_bsdf(self, material, wi, wo, sample, key=None, uv=None):
         """ppg_debug_bsdf (include/ppg_testhooks.h): the render's mat_eval / mat_pdf / mat_sample on material(s) `material` of the scene, per

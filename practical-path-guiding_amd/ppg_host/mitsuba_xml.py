@@ -1101,9 +1101,9 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 m = make_bsdf(inner[0], allow_twosided=False)
                 if m["type"] in (6, 7, 8):
                     raise SceneError("twosided(dielectric): only BRDFs can be two-sided (twosided.cpp:84-88)")
-                if m["type"] == 0 and not m.get("_substituted"):
+                if m["type"] == 0 and not m.get("_substituted") and "blend" not in m:
                     return dict({k: v for k, v in m.items() if k in TEXTURE_KEYS + ("coating",)}, type=1, reflectance=m["reflectance"])
-                return dict(m, twosided=True)
+                return dict(m, twosided=True)  # (a blended material's own record stays diffuse + two-sided: it only carries the adapters)
             t = "twosided(%s)" % ",".join(c.get("type", "?") for c in inner)
         elif t == "mask" and allow_twosided:
             inner = [c for c in elem if c.tag == "bsdf"]
@@ -1170,6 +1170,14 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 if len(inner) == 1:  # where a strict load refuses this coat, a lenient one renders the nested BSDF
                     warnings.append("bsdf %r dropped around its nested bsdf (%s)" % (t, e))
                     return make_bsdf(inner[0], allow_twosided)
+        if t in ("blendbsdf", "mixturebsdf"):  # BlendBSDF (blendbsdf.cpp:70-133), MixtureBSDF (mixturebsdf.cpp:64-172): where a leaf stands
+            try:
+                return blended(elem, p, t)
+            except SceneError as e:
+                if strict:
+                    raise
+                warnings.append("bsdf %r replaced by diffuse(0.5) (%s)" % (t, e))
+                return dict(type=0, reflectance=(0.5, 0.5, 0.5), _substituted=True)
         if t == "bumpmap":  # BumpMap (bumpmap.cpp:60-133): one nested BSDF + one displacement texture, the outermost adapter
             inner = [c for c in elem if c.tag == "bsdf"]
             disp = [c for c in elem if c.tag in ("texture", "ref") and (c.tag == "texture" or c.get("id") in tex_by_id)]
@@ -1207,6 +1215,8 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         it = inner[0].get("type")
         if it in ("coating", "roughcoating", "twosided", "mask", "bumpmap"):
             raise SceneError("%s(%s) is not supported: the nesting order is bumpmap(mask(twosided(coating(..))))" % (t, it))
+        if it in ("blendbsdf", "mixturebsdf"):
+            raise SceneError("%s(%s) is not supported: neither a coat around a blend nor a coated child" % (t, it))
         for c in elem:
             if c.tag in ("texture", "ref") and c.get("name") in ("sigmaA", "specularReflectance", "alpha", "alphaU", "alphaV"):
                 raise SceneError("%s: a texture on %r is not supported" % (t, c.get("name")))
@@ -1246,9 +1256,76 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             c.update(alpha=float(f32(mf["alpha"])), distribution=distr, sample_visible=bool(mf.get("sample_visible", True)), slice=rt_index[key])
         return dict(m, coating=c)
 
+    def blended(elem, p, t):
+        """the blended material's own record — diffuse, carrying nothing but the adapters that go around it — with the combinator under
+        `blend` (bindings.Blend), its children as material dicts.  The nesting order this build knows is bumpmap(mask(twosided(blend(leaf,
+        ..)))); a child is a nested <bsdf> or a <ref> to a <bsdf> with an id that stands before it."""
+        kids = [c for c in elem if c.tag == "bsdf" or (c.tag == "ref" and c.get("name") != "weight" and c.get("id") not in tex_by_id)]
+        if len(kids) > 4:
+            raise SceneError("%s: more than 4 nested bsdfs are not supported (found %d)" % (t, len(kids)))
+        if t == "blendbsdf" and len(kids) != 2:
+            raise SceneError("blendbsdf: BSDF count mismatch: expected two nested BSDF instances! (found %d)" % len(kids))
+        children = []
+        for c in kids:
+            if c.tag == "ref":
+                if c.get("id") not in by_id:
+                    raise SceneError('%s: <ref id="%s">: no such bsdf before it' % (t, c.get("id")))
+                m, it = dict(materials[by_id[c.get("id")]]), "ref " + c.get("id")
+            else:
+                it = c.get("type")
+                if it in ("twosided", "mask", "bumpmap"):
+                    raise SceneError("%s(%s) is not supported: the nesting order is bumpmap(mask(twosided(%s(..))))" % (t, it, t))
+                m = make_bsdf(c, allow_twosided=False)
+            if "blend" in m:
+                raise SceneError("%s(%s): blends of blends are not supported" % (t, it))
+            if "coating" in m:
+                raise SceneError("%s(%s): coated children are not supported" % (t, it))
+            if m["type"] in (6, 7, 8):
+                raise SceneError("%s(%s): dielectric, thindielectric and roughdielectric children are not supported" % (t, it))
+            if m["type"] == 1 or m.get("twosided") or "opacity" in m or "bump" in m:
+                raise SceneError("%s(%s) is not supported: the nesting order is bumpmap(mask(twosided(%s(..))))" % (t, it, t))
+            children.append({k: v for k, v in m.items() if not k.startswith("_")})
+        b = dict(kind=t, children=tuple(children))
+        if t == "blendbsdf":
+            if any(c.get("name") == "weight" and c.tag in ("texture", "ref") for c in elem):
+                w, ti = colour_or_texture(elem, "weight", 0.5, wrap=True)
+                b["weight"] = float((f32(w[0]) + f32(w[1]) + f32(w[2])) * (f32(1.0) / f32(3)))  # Spectrum::average (spectrum.h:481-486)
+                b["weight_texture"] = ti
+            else:
+                try:
+                    b["weight"], b["weight_texture"] = float(f32(float(p.get("weight", 0.5)))), None
+                except (TypeError, ValueError):
+                    raise SceneError("blendbsdf: Could not parse the weight!")
+            if not math.isfinite(b["weight"]) or b["weight"] < 0:
+                raise SceneError("blendbsdf: weight must be finite and not negative")
+        else:
+            tokens = [w for w in re.split("[ ,;]+", str(p.get("weights", ""))) if w]
+            if not tokens:
+                raise SceneError("mixturebsdf: No weights were supplied!")
+            try:
+                weights = tuple(float(f32(float(w))) for w in tokens)
+            except ValueError:
+                raise SceneError("mixturebsdf: Could not parse the BSDF weights!")
+            if len(weights) != len(children):
+                raise SceneError("mixturebsdf: BSDF count mismatch: %d bsdfs, but specified %d weights" % (len(children), len(weights)))
+            if not all(math.isfinite(w) and w >= 0 for w in weights):
+                raise SceneError("mixturebsdf: weights must be finite and not negative")
+            if not sum(weights) > 0:
+                raise SceneError("mixturebsdf: The weights must sum to a value greater than zero!")
+            b.update(weights=weights, ensure_energy_conservation=bool(p.get("ensureEnergyConservation", True)))
+        return dict(type=0, reflectance=(0.5, 0.5, 0.5), blend=b)
+
+    def blend_children(m):
+        return [c for c in (m.get("blend") or {}).get("children", ()) if isinstance(c, dict)]
+
+    def reads_bitmap(m):
+        """whether the material, the weight of its blend or a child of it reads a bitmap at the hit's uv"""
+        return (any(k in m for k in TEXTURE_KEYS) or (m.get("blend") or {}).get("weight_texture") is not None
+                or any(reads_bitmap(c) for c in blend_children(m)))
+
     def intern(m):
         m = {k: v for k, v in m.items() if not k.startswith("_")}
-        freeze = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (tuple(sorted((a, freeze(b)) for a, b in v.items())) if isinstance(v, dict) else v)  # noqa: E731
+        freeze = lambda v: tuple(freeze(x) for x in v) if isinstance(v, (tuple, list)) else (tuple(sorted((a, freeze(b)) for a, b in v.items())) if isinstance(v, dict) else v)  # noqa: E731
         key = tuple(sorted((k, freeze(v)) for k, v in m.items()))
         if key not in mat_index:
             mat_index[key] = len(materials)
@@ -1438,6 +1515,8 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             emitters.append(dict(radiance=tuple(float(v) for v in colour(e, "radiance", 1.0))))
         for mesh in meshes:
             collected.append((mesh, mat, em))
+        if t in ("sphere", "disk", "cylinder") and "blend" in materials[mat] and reads_bitmap(materials[mat]):
+            raise SceneError("%s: %s: textured BSDFs are only supported on triangle meshes (not on spheres, disks or cylinders)" % (t, materials[mat]["blend"]["kind"]))
         if t == "sphere":
             spheres.append(dict(sphere, material=mat, emitter=em))
         if t in ("disk", "cylinder"):
@@ -1451,12 +1530,15 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
     any_normals = any(m["normals"] is not None for m, _, _ in collected)
     # texture coordinates only matter on meshes whose BSDF reads a bitmap; the others get NaN rows (= none)
     # ... or is anisotropic (EAnisotropic: alphaU != alphaV, or either a bitmap), which needs the UV tangents (trimesh.cpp:380, 683-735)
+    # (a blended material asks for what its weight or any of its children asks for)
     def anisotropic(m):
+        if any(anisotropic(c) for c in blend_children(m)):
+            return True
         if m.get("alpha_v") is None:
             return False
         return (max(f32(m["alpha_v"]), f32(1e-4)) != max(f32(m.get("alpha", 0.1)), f32(1e-4)) or m.get("alpha_texture") is not None
                 or m.get("alpha_v_texture") is not None)
-    wants_uvs = lambda mat: any(k in materials[mat] for k in TEXTURE_KEYS) or anisotropic(materials[mat])  # noqa: E731
+    wants_uvs = lambda mat: reads_bitmap(materials[mat]) or anisotropic(materials[mat])  # noqa: E731
     any_uvs = any(m.get("uvs") is not None and wants_uvs(mat) for m, mat, _ in collected)
     uvl = []
     pos, nrm, idx, tmat, tem = [], [], [], [], []
@@ -1486,8 +1568,9 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
     normals = np.concatenate(nrm).astype(f32) if any_normals else None
     if not collected:  # analytic spheres only
         pos, idx, tmat, tem = [np.zeros((0, 3), f32)], [np.zeros((0, 3), np.uint32)], [np.zeros(0, np.uint32)], [np.zeros(0, np.int32)]
+    from .bindings import expand_blends  # (children of blended materials join the list, behind everything a shape refers to)
     desc = SceneDesc(np.concatenate(pos).astype(f32), np.concatenate(idx).astype(np.uint32), np.concatenate(tmat), np.concatenate(tem),
-                     materials, emitters, camera, normals, environment, np.stack(rt_slices).astype(f32) if rt_slices else None, spheres, envmap,
+                     expand_blends(materials), emitters, camera, normals, environment, np.stack(rt_slices).astype(f32) if rt_slices else None, spheres, envmap,
                      np.concatenate(uvl).astype(f32) if any_uvs else None, textures, rfilter, lens, delta_emitters, shapes)
     if delta_emitters and str(props.get("nee", "never")) != "always":
         warnings.append("point / spot / directional emitters are reached by next-event estimation only: with nee = %s they contribute nothing in "
@@ -1526,8 +1609,11 @@ def save_scene_xml(desc, props, directory, name="scene"):
             '\t\t<float name="focusDistance" value="%r"/>' % float(lens["focus_distance"])]) + ['\t\t<sampler type="independent"/>', '\t\t<film type="hdrfilm">',
             '\t\t\t<integer name="width" value="%d"/>' % cam["width"], '\t\t\t<integer name="height" value="%d"/>' % cam["height"],
             '\t\t\t<boolean name="banner" value="false"/>', '\t\t\t<rfilter type="box"/>', '\t\t</film>', '\t</sensor>']
-    from .bindings import Coating, Material, Microfacet
-    for i, m in enumerate(desc.materials):
+    from .bindings import Blend, Coating, Material, Microfacet, expand_blends
+    mats = expand_blends(desc.materials)
+
+    def leaf(m):
+        """(the <bsdf> element of a material without its two-sided / mask adapters — "%s" takes its id attribute —, its type, its record)"""
         t = m.get("type", 0)
         t = Material.BSDF[t] if isinstance(t, str) else int(t)
         M = Material.from_dict(m)
@@ -1569,6 +1655,18 @@ def save_scene_xml(desc, props, directory, name="scene"):
                 coat += '<float name="alpha" value="%r"/><string name="distribution" value="%s"/>' % (float(K.alpha), ("beckmann", "ggx", "phong")[K.distribution])
                 coat += '<boolean name="sampleVisible" value="false"/>' if K.sample_all else ""
             body = '<bsdf type="%s"%%s>%s%s</bsdf>' % ("coating" if K.kind == 1 else "roughcoating", coat, body % "")
+        return body, t, M
+
+    for i, m in enumerate(mats):
+        body, t, M = leaf(m)
+        B = Blend.from_dict(m)  # a blendbsdf / mixturebsdf stands where the leaf would, its children nested in it (a bitmap weight as its constant)
+        if B.kind:
+            kids = "".join(leaf(mats[B.child[k]])[0] % "" for k in range(B.n))
+            if B.kind == 1:
+                body = '<bsdf type="blendbsdf"%%s><float name="weight" value="%r"/>%s</bsdf>' % (float(B.weight[0]), kids)
+            else:
+                body = '<bsdf type="mixturebsdf"%%s><string name="weights" value="%s"/><boolean name="ensureEnergyConservation" value="%s"/>%s</bsdf>' % (
+                    ", ".join(repr(float(B.weight[k])) for k in range(B.n)), "true" if B.ensure_energy_conservation else "false", kids)
         twos = t == 1 or (M.flags & 1 and t not in (6, 7, 8))
         if M.flags & 4:
             inner = ('<bsdf type="twosided">%s</bsdf>' % (body % "")) if twos else body % ""

@@ -42,7 +42,7 @@ class SceneDesc:
 
 def save_scene(desc, path):
     """Write the flat binary scene read by host/ppg_render.cpp: "PPGS", 6 x uint32 {n_vertices, n_triangles, n_materials,
-    n_emitters, has_normals, blocks (bit 0: environment, bit 1: rtrans, bit 2: spheres, bit 3: envmap, bit 4: texcoords, bit 5: textures, bit 6: rfilter, bit 7: lens, bit 8: delta emitters, bit 9: material textures, bit 10: shapes, bit 11: microfacet, bit 12: coatings)}, then positions, [normals], indices, tri_material,
+    n_emitters, has_normals, blocks (bit 0: environment, bit 1: rtrans, bit 2: spheres, bit 3: envmap, bit 4: texcoords, bit 5: textures, bit 6: rfilter, bit 7: lens, bit 8: delta emitters, bit 9: material textures, bit 10: shapes, bit 11: microfacet, bit 12: coatings, bit 13: blends)}, then positions, [normals], indices, tri_material,
     tri_emitter, materials (ppg_material, 80 bytes each), emitters (4 floats), camera (ppg_camera), [environment radiance:
     3 floats], [rtrans: 2 x uint32 {n_slices, samples}, then n_slices x (samples + 1) floats], [spheres: uint32 n, then n x ppg_sphere
     (64 bytes)], [envmap: 2 x uint32 {width, height}, float scale, 9 floats to_world, then height x width x 3 floats], [texcoords: n_vertices x 2
@@ -54,9 +54,20 @@ def save_scene(desc, path):
     [material textures: n_materials x ppg_material_textures (16 bytes) — only when a material has a bitmap on specular / alpha / opacity],
     [shapes: uint32 n, then n x ppg_shape (80 bytes) — only when there are analytic disks or cylinders],
     [microfacet: n_materials x ppg_microfacet (32 bytes) — only when a material states alphaU / alphaV, distribution = phong or sampleVisible = false],
-    [coatings: n_materials x ppg_coating (64 bytes) — only when a material has a coating / roughcoating]."""
+    [coatings: n_materials x ppg_coating (64 bytes) — only when a material has a coating / roughcoating],
+    [blends: n_materials x ppg_blend (64 bytes) — only when a material is a blendbsdf / mixturebsdf; children that the description states
+    as dicts are appended to the material list first (bindings.expand_blends)]."""
     import struct
-    from .bindings import Coating, DeltaEmitter, Lens, MaterialTextures, Microfacet, RFilter, Shape, has_coatings, has_general_microfacet, has_parameter_textures
+    from .bindings import (Blend, Coating, DeltaEmitter, Lens, MaterialTextures, Microfacet, RFilter, Shape, expand_blends, has_blends, has_coatings,
+                           has_general_microfacet, has_parameter_textures)
+    blends = []
+    if has_blends(desc):
+        import copy
+        desc = copy.copy(desc)
+        desc.materials = expand_blends(desc.materials)
+        blends = [Blend.from_dict(m) for m in desc.materials]
+        if not any(b.kind for b in blends):
+            blends = []
     coats = [Coating.from_dict(m) for m in desc.materials] if has_coatings(desc) else []
     if not any(c.kind for c in coats):
         coats = []
@@ -78,7 +89,7 @@ def save_scene(desc, path):
         f.write(struct.pack("<6I", pos.shape[0], idx.shape[0], len(desc.materials), len(desc.emitters), 0 if desc.normals is None else 1,
                             (0 if env is None else 1) | (0 if rt is None else 2) | (4 if getattr(desc, "spheres", None) else 0) | (8 if getattr(desc, "envmap", None) is not None else 0)
                             | (16 if getattr(desc, "texcoords", None) is not None else 0) | (32 if getattr(desc, "textures", None) else 0) | (0 if rf is None else 64)
-                            | (0 if lens is None else 128) | (256 if delta else 0) | (512 if mat_tex else 0) | (1024 if shapes else 0) | (2048 if mfd else 0) | (4096 if coats else 0)))
+                            | (0 if lens is None else 128) | (256 if delta else 0) | (512 if mat_tex else 0) | (1024 if shapes else 0) | (2048 if mfd else 0) | (4096 if coats else 0) | (8192 if blends else 0)))
         f.write(pos.tobytes())
         if desc.normals is not None:
             f.write(np.ascontiguousarray(desc.normals, np.float32).tobytes())
@@ -141,6 +152,8 @@ def save_scene(desc, path):
             f.write(bytes(g))
         for c in coats:
             f.write(bytes(c))
+        for b in blends:
+            f.write(bytes(b))
 
 
 def srgb8_table():
@@ -288,7 +301,16 @@ def load_scene_file(path):
                 raise ValueError("%s: coating entry out of range" % path)
             if c.kind:
                 d["coating"] = c.as_dict()
-    if blocks >> 13:
+    if blocks & 8192:
+        from .bindings import Blend
+        n_tex = len(textures) if textures else 0
+        for d in mats:
+            b = Blend.from_buffer_copy(bytes(take(np.uint8, C_BLEND_BYTES)))
+            if any(b._reserved) or b.kind not in (0, 1, 2) or (b.kind and (not 1 <= b.n <= Blend.MAX or any(b.child[i] >= nm for i in range(b.n)) or b.weight_texture > n_tex)):
+                raise ValueError("%s: blend entry out of range" % path)
+            if b.kind:
+                d["blend"] = b.as_dict()
+    if blocks >> 14:
         raise ValueError("%s: a block this reader does not know" % path)
     if off[0] != len(buf):
         raise ValueError("%s: trailing bytes" % path)
@@ -300,6 +322,7 @@ C_LENS_BYTES = 8      # sizeof(ppg_lens)
 C_SHAPE_BYTES = 80    # sizeof(ppg_shape)
 C_MICROFACET_BYTES = 32  # sizeof(ppg_microfacet)
 C_COATING_BYTES = 64  # sizeof(ppg_coating)
+C_BLEND_BYTES = 64    # sizeof(ppg_blend)
 C_MATERIAL_TEXTURES_BYTES = 16  # sizeof(ppg_material_textures)
 C_DELTA_EMITTER_BYTES = 84  # sizeof(ppg_delta_emitter)
 
