@@ -24,11 +24,13 @@ int ppg_debug_build_bvh(const float *positions, const uint32_t *indices, uint32_
    as the kernels decode it (origin + byte * cell).  sa_* are the expected-step figures of the surface area heuristic for a ray that
    enters the root's box: sa_interior = sum of area(child box) / area(root) over interior children (node steps below the root's own),
    sa_leaf the same over leaf children (leaf visits), sa_tris = sum of area / area(root) * triangles over leaf children (triangle tests).
-   depth = 4-wide levels on the longest path; build_seconds = wall time of the builder alone. */
+   depth = 4-wide levels on the longest path; build_seconds = wall time of the builder alone.  stack_need = the most entries the ordered
+   walk can leave on its stack: the maximum, over the paths from the root to a node, of the sum of (non-empty children - 1) over the
+   interior nodes on the path.  The kernels' stacks hold 48 and ppg_set_scene hands them no tree that needs more. */
 struct ppg_bvh_stats {
     uint32_t n_nodes, n_leaves, depth, n_binary_nodes;
     uint32_t leaf_hist[9]; /* [k] = leaves of k triangles */
-    uint32_t reserved;
+    uint32_t stack_need;
     double sa_interior, sa_leaf, sa_tris;
     double build_seconds;
 };
@@ -70,6 +72,30 @@ struct ppg_debug_hit {
     int32_t _pad;
 };  /* 80 bytes */
 int ppg_debug_intersect(struct ppg_ctx *ctx, uint32_t n, const float *rays, struct ppg_debug_hit *out, int32_t any_hit);
+
+/* The same rays through the OTHER forms of the closest-hit traversal, each of which promises the same hit bit for bit (csrc/ppg_device.h,
+   csrc/ppg_kernels.h); rays and records as above, mint as it stands except where noted.  stats_out (4 words, may be NULL) is zeroed, then:
+     LANE, LANE_ANY, LANE_VOTE  trace_closest4<false | true, true, false | true>, one ray per lane in waves of 64 (LANE and LANE_ANY are what
+                ppg_debug_intersect runs; VOTE, the leaf vote of k_tail's traversals, wants n to be a multiple of 64: whole waves).
+     RESUME     trace_closest4_resume as k_tail's crowd phase drives it: a wave owns 512 consecutive rays; a lane that returned takes the
+                wave's next ray, a lane that was parked calls again with resume = true.  param = suspend_lanes (k_tail: 8; 0 never parks).
+                stats_out[0] / [1] = rays parked at least once / at least twice.
+     WAVE       trace_closest4_wave, one ray per wave; a ray it abandons (prim = -2: wave stack overrun) is walked again by one lane with
+                trace_closest4<false, true, false>, as in k_tail.  param = 1: a wave stack of one row (64 entries) instead of the render's
+                24.  stats_out[0] = rays that took the fallback, [1] = steps of the wave-wide walks.
+     KTRACE     the rays become the paths of a PathState and go through the real k_trace of the scene's kernel family, launched as
+                renderBatch launches a first bounce (all paths queued, no sort), SMALL exactly when a render of this context would use
+                it; the records are filled from its P.hit.  param = workgroups (0: one per 1024 rays, so that lanes replace their rays).
+                k_trace rescales a mint that equals PPG_EPSILON (1e-4f) exactly by max(|o|_inf, 1e-4), as Scene::rayIntersect does:
+                pass the scaled value to compare with the other modes.
+   In every mode stats_out[2] = the entries of the scene's top cut (DevScene::n_top; 0: the wave traversal starts at the root) and
+   stats_out[3] = 1 where KTRACE ran the SMALL kernel.  LANE_ANY fills prim (>= 0: occluded) and t only.  The record has no room for the
+   barycentrics: p, the frame and wi are functions of (prim, u, v) and the ray, so records that are equal byte for byte stand for them. */
+enum {
+    PPG_DEBUG_TRACE_LANE = 0, PPG_DEBUG_TRACE_LANE_ANY = 1, PPG_DEBUG_TRACE_LANE_VOTE = 2, PPG_DEBUG_TRACE_RESUME = 3, PPG_DEBUG_TRACE_WAVE = 4,
+    PPG_DEBUG_TRACE_KTRACE = 5
+};
+int ppg_debug_intersect_mode(struct ppg_ctx *ctx, uint32_t n, const float *rays, struct ppg_debug_hit *out, int32_t mode, int32_t param, uint32_t *stats_out);
 
 /* emitter_sample_direct of the FULL kernels, sample by sample: per item a reference point ref[3], its normal ref_n[3] and the 2-D sample
    u[2].  Out: the emitter chosen (the hook repeats the render's pmf_sample on the same table and sample: the record does not carry the

@@ -1583,6 +1583,7 @@ struct Scene {
         if (bvh.empty()) {
             for (uint32_t t = 0; t < nTris(); ++t) consider(t);
         } else {
+            // (buildRec splits at the median only: the tree is ceil(log2 n) deep and the stack holds at most depth + 1 entries)
             int stack[128], sp = 0;
             stack[sp++] = 0;
             while (sp) {

@@ -1,6 +1,6 @@
 /*
  * ppg_debug_kernels.h — the kernels of the test hooks (include/ppg_testhooks.h) that run the render's own device functions, included by the
- * k_trace unit of a family (ppg_inst.hip): k_debug_intersect and k_debug_sample_direct in the shapes family, which the hooks always use;
+ * k_trace unit of a family (ppg_inst.hip): k_debug_intersect, the kernels of ppg_debug_intersect_mode and k_debug_sample_direct in the shapes family, which the hooks always use;
  * k_debug_bsdf in the ext family, k_debug_bsdf_coat in the coat family, which ppg_debug_bsdf uses for a scene with a coated material, and
  * k_debug_bsdf_blend in the blend family, which it uses for a scene with a blended one.
  */
@@ -55,6 +55,127 @@ __global__ void k_debug_sample_direct(DevScene S, unsigned int n, const float *r
     r.value[0] = value.x; r.value[1] = value.y; r.value[2] = value.z;
     out[i] = r;
 }
+// ---- ppg_debug_intersect_mode: the other forms of the closest-hit traversal, ray by ray ----
+// the record of hit h on ray (o, d); closest = false: prim and t only (any-hit)
+D void debug_record(const DevScene &S, const Hit &h, F3 o, F3 d, bool closest, ppg_debug_hit *dst) {
+    ppg_debug_hit r;
+    memset(&r, 0, sizeof r);
+    r.material = -1; r.emitter = -1;
+    r.prim = h.prim;
+    if (h.prim >= 0) {
+        r.t = h.t;
+        if (closest) {
+            Isect I;
+            fill_isect_full(S, h, o, d, I);
+            r.p[0] = I.p.x; r.p[1] = I.p.y; r.p[2] = I.p.z;
+            r.geo_n[0] = I.geoN.x; r.geo_n[1] = I.geoN.y; r.geo_n[2] = I.geoN.z;
+            r.n[0] = I.n.x; r.n[1] = I.n.y; r.n[2] = I.n.z;
+            r.s[0] = I.s.x; r.s[1] = I.s.y; r.s[2] = I.s.z;
+            r.wi[0] = I.wi.x; r.wi[1] = I.wi.y; r.wi[2] = I.wi.z;
+            r.material = I.material; r.emitter = I.emitter;
+        }
+    }
+    *dst = r;
+}
+// LANE, LANE_ANY, LANE_VOTE: trace_closest4<ANY, true, VOTE>, one ray per lane, waves of 64 (VOTE: n is a multiple of 64)
+template <bool ANY, bool VOTE>
+__global__ __launch_bounds__(64) void k_debug_trace_lane(DevScene S, unsigned int n, const float4 *rays, ppg_debug_hit *out) {
+    extern __shared__ int dbg_stack[];
+    const unsigned int i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    const float4 ro = rays[2 * i], rd = rays[2 * i + 1];
+    const F3 o = f3(ro.x, ro.y, ro.z), d = f3(rd.x, rd.y, rd.z);
+    const Hit h = trace_closest4<ANY, true, VOTE>(S, dbg_stack + threadIdx.x, 64, o, d, ro.w, rd.w);
+    debug_record(S, h, o, d, !ANY, out + i);
+}
+// RESUME: a wave owns rays [blockIdx.x * per_wave, + per_wave) and follows k_tail's protocol: a lane without a ray takes the wave's next one,
+// the lanes that hold one call trace_closest4_resume together; a lane that comes back parked keeps its ray and calls again with resume =
+// true beside the other lanes' next rays.  stats[0] / [1]: rays parked at least once / twice.
+__global__ __launch_bounds__(64) void k_debug_trace_resume(DevScene S, unsigned int n, const float4 *rays, ppg_debug_hit *out, int suspend_lanes, unsigned int per_wave,
+                                                           unsigned int *stats) {
+    extern __shared__ int dbg_stack[];
+    __shared__ int park[3 * 64];
+    const int lane = (int)threadIdx.x;
+    unsigned int next = blockIdx.x * per_wave;
+    const unsigned int end = next + per_wave < n ? next + per_wave : n;
+    bool have = false, pending = false;
+    unsigned int i = 0, parks = 0;
+    float4 ro = make_float4(0, 0, 0, 0), rd = ro;
+    Hit h;
+    h.t = 0; h.u = 0; h.v = 0; h.prim = -1;
+    for (;;) {
+        const unsigned long long need = __ballot(!have);
+        if (!have) {
+            const unsigned int k = next + (unsigned int)__popcll(need & ((1ull << lane) - 1ull));
+            if (k < end) { i = k; have = true; pending = false; parks = 0; ro = rays[2 * i]; rd = rays[2 * i + 1]; }
+        }
+        next = next + (unsigned int)__popcll(need) < end ? next + (unsigned int)__popcll(need) : end;
+        if (__ballot(have) == 0ull) break;
+        if (have) {
+            const F3 o = f3(ro.x, ro.y, ro.z), d = f3(rd.x, rd.y, rd.z);
+            pending = !trace_closest4_resume<true>(S, dbg_stack + lane, 64, o, d, ro.w, rd.w, pending, park + lane, 64, h, suspend_lanes);
+            if (pending) ++parks;
+            else {
+                debug_record(S, h, o, d, true, out + i);
+                if (parks >= 1u) atomicAdd(stats, 1u);
+                if (parks >= 2u) atomicAdd(stats + 1, 1u);
+                have = false;
+            }
+        }
+    }
+}
+// WAVE: trace_closest4_wave<ROWS>, one ray per wave (all lanes with the same arguments); a ray it abandons (prim = -2) is walked again by
+// lane 0 as k_tail walks it.  stats[0]: rays that took that way, stats[1]: the steps of the wave-wide walks (probe_steps).
+template <int ROWS>
+__global__ __launch_bounds__(64) void k_debug_trace_wave(DevScene S, unsigned int n, const float4 *rays, ppg_debug_hit *out, unsigned int *stats) {
+    extern __shared__ int dbg_stack[];  // PPG_LDS_STACK rows of 64: the wave-wide stack (its first ROWS rows), then lane 0's column
+    for (unsigned int i = blockIdx.x; i < n; i += gridDim.x) {
+        const float4 ro = rays[2 * i], rd = rays[2 * i + 1];
+        const F3 o = f3(ro.x, ro.y, ro.z), d = f3(rd.x, rd.y, rd.z);
+        int steps = 0;
+        const Hit h = trace_closest4_wave<ROWS>(S, dbg_stack, 64, o, d, ro.w, rd.w, &steps);
+        if (threadIdx.x == 0) {
+            Hit hs = h;
+            if (h.prim == -2) { hs = trace_closest4<false, true, false>(S, dbg_stack, 64, o, d, ro.w, rd.w); atomicAdd(stats, 1u); }
+            atomicAdd(stats + 1, (unsigned int)steps);
+            debug_record(S, hs, o, d, true, out + i);
+        }
+        __syncthreads();  // (lane 0's column is the wave-wide stack's first one)
+    }
+}
+// KTRACE reads k_trace's P.hit: the record of hit (t, u, v, prim) on ray i
+__global__ void k_debug_hit_records(DevScene S, unsigned int n, const float4 *rays, const float4 *hits, ppg_debug_hit *out) {
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 ro = rays[2 * i], rd = rays[2 * i + 1], hv = hits[i];
+    Hit h;
+    h.t = hv.x; h.u = hv.y; h.v = hv.z; h.prim = __float_as_int(hv.w);
+    debug_record(S, h, f3(ro.x, ro.y, ro.z), f3(rd.x, rd.y, rd.z), true, out + i);
+}
+static void launch_debug_trace(int mode, int param, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_hit *out, unsigned int *stats) {
+    const size_t lds = (size_t)PPG_LDS_STACK * 64 * sizeof(int);
+    const dim3 waves((n + 63u) / 64u), block(64);
+    switch (mode) {
+    case PPG_DEBUG_TRACE_LANE: hipLaunchKernelGGL((k_debug_trace_lane<false, false>), waves, block, lds, stream, S, n, rays, out); break;
+    case PPG_DEBUG_TRACE_LANE_ANY: hipLaunchKernelGGL((k_debug_trace_lane<true, false>), waves, block, lds, stream, S, n, rays, out); break;
+    case PPG_DEBUG_TRACE_LANE_VOTE: hipLaunchKernelGGL((k_debug_trace_lane<false, true>), waves, block, lds, stream, S, n, rays, out); break;
+    case PPG_DEBUG_TRACE_RESUME: {
+        const unsigned int per_wave = 512;  // eight rays a lane
+        hipLaunchKernelGGL(k_debug_trace_resume, dim3((n + per_wave - 1) / per_wave), block, lds, stream, S, n, rays, out, param, per_wave, stats);
+        break;
+    }
+    case PPG_DEBUG_TRACE_WAVE: {
+        const dim3 grid(n < 1024u ? n : 1024u);
+        if (param == 1) hipLaunchKernelGGL((k_debug_trace_wave<1>), grid, block, lds, stream, S, n, rays, out, stats);
+        else hipLaunchKernelGGL((k_debug_trace_wave<PPG_LDS_STACK>), grid, block, lds, stream, S, n, rays, out, stats);
+        break;
+    }
+    default: break;  // (ppg_debug_intersect_mode has checked the mode)
+    }
+}
+static void launch_debug_hit_records(hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, const float4 *hits, ppg_debug_hit *out) {
+    hipLaunchKernelGGL(k_debug_hit_records, dim3((n + 63u) / 64u), dim3(64), 0, stream, S, n, rays, hits, out);
+}
 static void launch_debug_intersect(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_hit *out, int any) {
     hipLaunchKernelGGL(k_debug_intersect, dim3(grid), dim3(block), (size_t)PPG_LDS_STACK * block * sizeof(int), stream, S, n, rays, out, any);
 }
@@ -108,6 +229,8 @@ static void fill_debug_kernels(PathKernels &K) {
 #if PPG_FAMILY == PPG_FAMILY_SHAPES
     K.debug_intersect = launch_debug_intersect;
     K.debug_sample_direct = launch_debug_sample_direct;
+    K.debug_trace = launch_debug_trace;
+    K.debug_hit_records = launch_debug_hit_records;
 #endif
 #if PPG_FAMILY >= PPG_FAMILY_EXT
     K.debug_bsdf = launch_debug_bsdf;

@@ -694,6 +694,8 @@ D bool trace_closest4_resume(const DevScene &S, int *lds_stack_col, int stride, 
 #define PPG_COOP_MAX 16  // live lanes of a wave up to which k_tail traces cooperatively (measured per-iteration cycles, §7: 1 lane 36 k per-lane vs ~14 k).
                          // 6 until round 6; with the suspended traversals (which need more than 2 x PPG_TAIL_SUSPEND lanes) 10 and 16 measured +0.7 / +0.9 %
 #endif
+// ROWS: the rows of 64 entries the wave-wide stack may use (ppg_debug_intersect_mode runs it with 1 as well, to reach the overrun)
+template <int ROWS = PPG_LDS_STACK>
 D Hit trace_closest4_wave(const DevScene &S, int *wave_stack /* this wave's column 0 */, int stride, F3 o, F3 d, float mint, float maxt,
                           int *probe_steps = nullptr) {
     const int lane = threadIdx.x & 63, g = lane >> 2, c = lane & 3;
@@ -763,10 +765,11 @@ D Hit trace_closest4_wave(const DevScene &S, int *wave_stack /* this wave's colu
                 }
             }
         }
-        // children that were hit go onto the stack (any order).  The stack is PPG_LDS_STACK rows of 64: a traversal that would overrun it
-        // (never observed; heavily overlapping boxes could) is abandoned — prim = -2 — and the caller walks that ray with one lane instead.
+        // children that were hit go onto the stack (any order).  The stack is ROWS (PPG_LDS_STACK) rows of 64: a traversal that would overrun it
+        // (never observed in a render; heavily overlapping boxes could) is abandoned — prim = -2 — and the caller walks that ray with one lane
+        // instead (tests/test_traversal_gpu.py takes that way with a stack of one row).
         const unsigned long long pm = __ballot(push != PPG_BVH4_EMPTY);
-        if (count + (int)__popcll(pm) > PPG_LDS_STACK * 64) { best.prim = -2; return best; }
+        if (count + (int)__popcll(pm) > ROWS * 64) { best.prim = -2; return best; }
         if (push != PPG_BVH4_EMPTY) slot(count + (int)__popcll(pm & ((1ull << lane) - 1ull))) = push;
         count += (int)__popcll(pm);
         // the triangle hits of this step, folded into the closest hit so far by (t, original index): a step rarely has more than one, so

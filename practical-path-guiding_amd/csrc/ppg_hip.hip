@@ -475,11 +475,109 @@ struct BvhBuilder {
         cut4(n.c0, bj, ch, m);
         cut4(n.c1, k - bj, ch, m);
     }
-    std::vector<Bvh4Node> nodes4;
-    int emit4(int v) {
-        int ch[4], m = 0, bk = 2;
+    int cutOf(int v, int *ch) const {  // the children of the 4-wide node that emit4 makes of v
+        int m = 0, bk = 2;
         for (int k = 3; k <= 4; ++k) if (cost[(size_t)v].k[k - 1] < cost[(size_t)v].k[bk - 1]) bk = k;
         cut4(v, bk, ch, m);
+        return m;
+    }
+
+    // ---- the traversal stack's bound.  The ordered walk (trace_closest4, trace_slice_bvh4) descends into the nearest child of a node and
+    // leaves the other children that were hit on its stack: on the way to a node the stack holds at most the sum of (children - 1) over the
+    // interior nodes on the path, that node included.  The STACK NEED of a tree is the largest such sum, and the kernels' stacks hold
+    // STACK_MAX entries without a range check (ppg_device.h TStack).  The SAH has no such bound: on nested geometry the sweep peels one
+    // triangle per level and the collapsed tree is a chain.  Where the need of the tree the collapse would emit exceeds the bound, the
+    // offending subtrees are built again with median splits and the tree is laid out and collapsed again.  A subtree is rebuilt as far
+    // down the offending path as a balanced one is expected to fit, so that as little of the SAH tree as possible is given up (a scene
+    // of a million triangles whose tree needs 51 loses a few subtrees of some dozen triangles, not its top): a balanced subtree of c
+    // triangles is ceil(log2 c) binary levels deep, a 4-wide node takes one to three of them on a path and adds at most 3 — 1.5 per level
+    // where the collapse pairs the levels, at most 3.  The first rounds expect 1.5 per level; a round that has not reached the bound is
+    // followed by one that expects 2, then 3 (the certain figure), which rebuilds higher up; the last resort is medians throughout.
+    // A tree within the bound is not touched. ----
+    static constexpr int STACK_MAX = 48;
+    int stackNeed = 0;  // of the finished tree (run)
+    std::vector<int> need4;
+    int needOf(int v) {  // v heads a 4-wide node
+        int ch[4];
+        const int m = cutOf(v, ch);
+        int below = 0;
+        for (int k = 0; k < m; ++k) if (!asLeaf[(size_t)ch[k]]) below = std::max(below, needOf(ch[k]));
+        return need4[(size_t)v] = m - 1 + below;
+    }
+    int perLevel2 = 3;  // twice the entries per binary level that rebound expects of a balanced subtree
+    int balancedNeed(int count) const { int l = 0; while ((1ll << l) < count) ++l; return (perLevel2 * l + 1) / 2; }
+    int buildMedian(int first, int count, int parent) {
+        const int me = (int)t2.size();
+        t2.emplace_back();
+        {
+            N2 &n = t2[(size_t)me];
+            const Box b = boundsOf(first, count);
+            for (int a = 0; a < 3; ++a) { n.lo[a] = b.lo[a]; n.hi[a] = b.hi[a]; }
+            n.parent = parent; n.c0 = n.c1 = -1; n.tri = (int)order[first]; n.first = first; n.count = count;
+        }
+        if (count == 1) return me;
+        Box cb = empty();
+        for (int i = first; i < first + count; ++i) grow(cb, &cent[3 * order[i]], &cent[3 * order[i]]);
+        int a = 0;
+        for (int k = 1; k < 3; ++k) if (cb.hi[k] - cb.lo[k] > cb.hi[a] - cb.lo[a]) a = k;
+        std::sort(order.begin() + first, order.begin() + first + count, [&](uint32_t x, uint32_t y) { const float cx = cent[3 * x + a], cy = cent[3 * y + a]; return cx < cy || (cx == cy && x < y); });
+        const int mid = first + count / 2;
+        const int l = buildMedian(first, mid - first, me), r = buildMedian(mid, first + count - mid, me);
+        t2[(size_t)me].c0 = l; t2[(size_t)me].c1 = r;
+        return me;
+    }
+    void rebuildBalanced(int v) {  // v's triangles are order[first, first + count) (layout)
+        const int first = t2[(size_t)v].first, count = t2[(size_t)v].count, p = t2[(size_t)v].parent;
+        const int fresh = buildMedian(first, count, p);
+        if (p >= 0) { replaceChild(p, v, fresh); return; }
+        t2[0] = t2[(size_t)fresh];  // the root stays node 0
+        t2[0].parent = -1;
+        t2[(size_t)t2[0].c0].parent = 0; t2[(size_t)t2[0].c1].parent = 0;
+    }
+    // v heads a 4-wide node that `above` entries lie under and whose subtree overruns the bound; a balanced subtree in v's place is expected to fit
+    void rebound(int v, int above) {
+        int ch[4];
+        const int m = cutOf(v, ch), here = above + m - 1;
+        bool deeper = true;  // every offending child can be mended below v
+        for (int k = 0; k < m; ++k) {
+            const int c = ch[k];
+            if (!asLeaf[(size_t)c] && here + need4[(size_t)c] > STACK_MAX && here + balancedNeed(t2[(size_t)c].count) > STACK_MAX) deeper = false;
+        }
+        if (!deeper) { rebuildBalanced(v); return; }
+        for (int k = 0; k < m; ++k) if (!asLeaf[(size_t)ch[k]] && here + need4[(size_t)ch[k]] > STACK_MAX) rebound(ch[k], here);
+    }
+    void boundStack() {
+        for (int round = 0; round < 8; ++round) {
+            need4.assign(t2.size(), 0);
+            if (needOf(0) <= STACK_MAX) return;
+            perLevel2 = round < 3 ? 3 : (round < 5 ? 4 : 6);
+            if (round < 7) rebound(0, 0);
+            else rebuildBalanced(0);  // (the collapse above a mended subtree may change; should that never settle: medians throughout)
+            layout();
+            collapse();
+        }
+    }
+    // the stack need of the finished nodes
+    static int stackNeedOf(const std::vector<Bvh4Node> &nodes4) {
+        int need = 0;
+        std::vector<std::pair<int, int>> todo(1, {0, 0});
+        while (!todo.empty()) {
+            const std::pair<int, int> e = todo.back();
+            todo.pop_back();
+            const Bvh4Node &nd = nodes4[(size_t)e.first];
+            int m = 0;
+            for (int k = 0; k < 4; ++k) m += nd.child[k] != PPG_BVH4_EMPTY ? 1 : 0;
+            const int here = e.second + std::max(0, m - 1);
+            need = std::max(need, here);
+            for (int k = 0; k < 4; ++k) if (nd.child[k] >= 0 && nd.child[k] != PPG_BVH4_EMPTY) todo.push_back({nd.child[k], here});
+        }
+        return need;
+    }
+
+    std::vector<Bvh4Node> nodes4;
+    int emit4(int v) {
+        int ch[4];
+        const int m = cutOf(v, ch);
         const int me = (int)nodes4.size();
         nodes4.emplace_back();
         Bvh4Node nd;
@@ -657,9 +755,11 @@ struct BvhBuilder {
         reoptimise();
         layout();
         collapse();
+        boundStack();
         nodes4.clear(); nodes4.reserve(t2.size() / 4 + 1);
         emit4(0);
         emit2(0);
+        stackNeed = stackNeedOf(nodes4);
         quantise();
     }
 };
@@ -1035,6 +1135,10 @@ template <typename F> static F launcher(F f) {
 static void ppg_launch_shade(int variant, const ShadeLaunch &a) { launcher(ppg_path_kernels[sceneFamily(a.S)].shade[variant >> 1])(variant, a); }
 // variant = (SMALL ? 4 : 0) | (NEE ? 2 : 0) | (FULL ? 1 : 0)
 static void ppg_launch_tail(int variant, const TailLaunch &a) { launcher(ppg_path_kernels[sceneFamily(a.S)].tail[variant >> 1])(variant, a); }
+// the scene is traced from LDS without a BVH (k_trace<true>, k_tail<true, ..>)
+static bool isSmallScene(const ppg_ctx *ctx) {
+    return ctx->scene.n_tris <= 64 && ctx->ldsTris == ctx->scene.n_tris && ctx->scene.n_spheres == 0 && sceneFamily(ctx->scene) == PPG_FAMILY_BASE && !ctx->tuneForceBvh;
+}
 namespace {
 
 template <typename F> void timedLaunch(ppg_ctx *ctx, const char *name, uint64_t units, F &&launch) {
@@ -1847,7 +1951,7 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
         if (((chunks + (size_t)ctx->tuneBlocksSmall - 1) / (size_t)ctx->tuneBlocksSmall) * PPG_DCHUNK <= (size_t)ctx->queues.cap) grid = ctx->tuneBlocksSmall;
     }
     const int gridAll = gridFor(P.n_paths);
-    const bool smallScene = ctx->scene.n_tris <= 64 && ctx->ldsTris == ctx->scene.n_tris && ctx->scene.n_spheres == 0 && sceneFamily(ctx->scene) == PPG_FAMILY_BASE && !ctx->tuneForceBvh;
+    const bool smallScene = isSmallScene(ctx);
     // (small scenes go through k_trace too: tracing them inside k_generate / k_shade was measured slower, DESIGN.md "Tuning switches")
     const bool neeOn = ctx->doNee;  // m_doNee of this iteration (doNeeWithSpp, GP:1331-1340)
     const bool fullMats = ctx->fullMaterials;  // any BSDF beyond diffuse / two-sided diffuse / mirror: the FULL kernel variants
@@ -3031,6 +3135,10 @@ int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
     const float padRel = ctx->tuneBvhPad;
     bb.maxLeaf = ctx->tuneBvhLeaf;
     bb.run(s->positions, s->indices, s->n_triangles, padRel * ext + 1e-30f);
+    if (bb.stackNeed > BvhBuilder::STACK_MAX) {  // (not reached by medians below 2^16 triangles per offending subtree: BvhBuilder::boundStack)
+        ctx->error = "the scene's BVH needs a traversal stack of " + std::to_string(bb.stackNeed) + " entries, the kernels' holds " + std::to_string(BvhBuilder::STACK_MAX);
+        return PPG_ERR_INVALID;
+    }
     std::vector<float4> tris(3 * (size_t)s->n_triangles), nrm, accel(3 * (size_t)s->n_triangles);
     if (s->normals) nrm.resize(tris.size());
     for (uint32_t k = 0; k < s->n_triangles; ++k) {
@@ -3717,6 +3825,7 @@ int ppg_debug_bvh_stats(const float *positions, const uint32_t *indices, uint32_
     out->build_seconds = std::chrono::duration<double>(t1 - t0).count();
     out->n_nodes = (uint32_t)bb.nodes4q.size();
     out->n_binary_nodes = (uint32_t)bb.nodes.size();
+    out->stack_need = (uint32_t)BvhBuilder::stackNeedOf(bb.nodes4);
     auto areaOf = [](const float lo[3], const float hi[3]) {
         const double d[3] = {(double)hi[0] - lo[0], (double)hi[1] - lo[1], (double)hi[2] - lo[2]};
         return d[0] < 0 || d[1] < 0 || d[2] < 0 ? 0.0 : 2 * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0]);
@@ -4020,6 +4129,64 @@ int ppg_debug_intersect(ppg_ctx *ctx, uint32_t n, const float *rays, ppg_debug_h
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_hit), hipMemcpyDeviceToHost));
+    return PPG_OK;
+}
+int ppg_debug_intersect_mode(ppg_ctx *ctx, uint32_t n, const float *rays, ppg_debug_hit *out, int32_t mode, int32_t param, uint32_t *stats_out) {
+    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
+    if (ctx->renderOpen) { ctx->error = "ppg_debug_intersect_mode: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (n && (!rays || !out)) { ctx->error = "ppg_debug_intersect_mode: no arrays"; return PPG_ERR_INVALID; }
+    if (mode < PPG_DEBUG_TRACE_LANE || mode > PPG_DEBUG_TRACE_KTRACE || param < 0) { ctx->error = "ppg_debug_intersect_mode: no such mode or a negative parameter"; return PPG_ERR_INVALID; }
+    if (mode == PPG_DEBUG_TRACE_LANE_VOTE && n % 64u) { ctx->error = "ppg_debug_intersect_mode: the leaf vote runs whole waves, n must be a multiple of 64"; return PPG_ERR_INVALID; }
+    if (mode == PPG_DEBUG_TRACE_RESUME && param > 31) { ctx->error = "ppg_debug_intersect_mode: suspend_lanes above 31"; return PPG_ERR_INVALID; }
+    if (stats_out) memset(stats_out, 0, 4 * sizeof(uint32_t));
+    if (n == 0) return PPG_OK;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->quiesce();
+    DebugBuf dRays, dOut, dStats;
+    HIP_CHECK(dRays.fill(rays, 2 * (size_t)n * sizeof(float4)));
+    HIP_CHECK(dOut.fill(nullptr, (size_t)n * sizeof(ppg_debug_hit)));
+    HIP_CHECK(dStats.fill(nullptr, 4 * sizeof(uint32_t)));
+    HIP_CHECK(hipMemsetAsync(dStats.p, 0, 4 * sizeof(uint32_t), ctx->stream));
+    const PathKernels &K = ppg_path_kernels[PPG_FAMILY_SHAPES];
+    if (mode != PPG_DEBUG_TRACE_KTRACE) {
+        launcher(K.debug_trace)(mode, param, ctx->stream, ctx->scene, n, (const float4 *)dRays.p, (ppg_debug_hit *)dOut.p, (unsigned int *)dStats.p);
+    } else {
+        // the rays as the paths of a batch: k_trace at a first bounce reads ray_o / ray_d of every path and writes hit (renderBatch)
+        const int grid = param > 0 ? std::min(param, 4096) : (int)((n + 1023u) / 1024u);
+        DebugBuf dO, dD, dHit, dBlock;
+        std::vector<float4> ro(n), rd(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            const float *r = rays + 8 * (size_t)i;
+            ro[i] = make_float4(r[0], r[1], r[2], r[3]); rd[i] = make_float4(r[4], r[5], r[6], r[7]);
+        }
+        HIP_CHECK(dO.fill(ro.data(), (size_t)n * sizeof(float4)));
+        HIP_CHECK(dD.fill(rd.data(), (size_t)n * sizeof(float4)));
+        HIP_CHECK(dHit.fill(nullptr, (size_t)n * sizeof(float4)));
+        HIP_CHECK(dBlock.fill(nullptr, (size_t)grid * sizeof(BlockStats)));
+        HIP_CHECK(hipMemsetAsync(dHit.p, 0xff, (size_t)n * sizeof(float4), ctx->stream));  // (prim -1 wherever k_trace writes nothing)
+        HIP_CHECK(hipMemsetAsync(dBlock.p, 0, (size_t)grid * sizeof(BlockStats), ctx->stream));
+        PathState P{};
+        P.n_paths = n; P.n_pix = n;
+        P.ray_o = {(float4 *)dO.p, 1u}; P.ray_d = {(float4 *)dD.p, 1u}; P.hit = {(float4 *)dHit.p, 1u};
+        Queues Q{};
+        Q.cap = n; Q.n_blocks = (unsigned int)grid; Q.stats = (BlockStats *)dBlock.p;
+        const bool smallScene = isSmallScene(ctx);
+        const size_t traceLds = smallScene ? (size_t)ctx->ldsTris * 48 : (size_t)PPG_TRACE_STACK * PPG_BLOCK * 4 + (PPG_BLOCK / 64) * sizeof(PairLds);
+        TraceLaunch a{grid, traceLds, ctx->stream, P, ctx->scene, Q, QIN_FIRST, smallScene ? 0 : ctx->ldsNodes, ctx->ldsTris, nullptr, nullptr, smallScene, false};
+        launcher(ppg_path_kernels[sceneFamily(ctx->scene)].trace)(a);
+        HIP_CHECK(hipGetLastError());
+        launcher(K.debug_hit_records)(ctx->stream, ctx->scene, n, (const float4 *)dRays.p, (const float4 *)dHit.p, (ppg_debug_hit *)dOut.p);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));  // (the buffers of this branch go out of scope)
+    }
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_hit), hipMemcpyDeviceToHost));
+    if (stats_out) {
+        HIP_CHECK(hipMemcpy(stats_out, dStats.p, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        stats_out[2] = (uint32_t)ctx->scene.n_top;
+        stats_out[3] = mode == PPG_DEBUG_TRACE_KTRACE && isSmallScene(ctx) ? 1u : 0u;
+    }
     return PPG_OK;
 }
 int ppg_debug_sample_direct(ppg_ctx *ctx, uint32_t n, const float *ref, const float *ref_n, const float *u, ppg_debug_direct *out) {

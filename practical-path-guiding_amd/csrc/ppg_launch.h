@@ -78,6 +78,8 @@ struct PathKernels {
     // The kernels of the test hooks (ppg_debug_kernels.h), in the families that compile them: the shapes family those of ppg_debug_intersect /
     // ppg_debug_sample_direct, the families from ext on that of ppg_debug_bsdf
     void (*debug_intersect)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_hit *out, int any);
+    void (*debug_trace)(int mode, int param, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_hit *out, unsigned int *stats);
+    void (*debug_hit_records)(hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, const float4 *hits, ppg_debug_hit *out);
     void (*debug_sample_direct)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float *ref, const float *ref_n, const float *u,
                                 ppg_debug_direct *out);
     void (*debug_bsdf)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out);

@@ -755,6 +755,18 @@ class Engine:
         self._call("debug_intersect", C.c_uint32(rays.shape[0]), _fp(rays), out.ctypes.data_as(C.POINTER(DebugHit)), C.c_int32(1 if any_hit else 0))
         return out
 
+    DEBUG_TRACE_MODES = dict(lane=0, lane_any=1, lane_vote=2, resume=3, wave=4, ktrace=5)
+
+    def debug_intersect_mode(self, rays, mode, param=0):
+        """ppg_debug_intersect_mode (include/ppg_testhooks.h): the rays through another form of the closest-hit traversal — mode is a key of
+        DEBUG_TRACE_MODES — -> (structured array (DEBUG_HIT_DTYPE), stats uint32 [4])."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.zeros(rays.shape[0], DEBUG_HIT_DTYPE)
+        stats = np.zeros(4, np.uint32)
+        self._call("debug_intersect_mode", C.c_uint32(rays.shape[0]), _fp(rays), out.ctypes.data_as(C.POINTER(DebugHit)),
+                   C.c_int32(self.DEBUG_TRACE_MODES[mode]), C.c_int32(int(param)), stats.ctypes.data_as(C.POINTER(C.c_uint32)))
+        return out, stats
+
     def debug_sample_direct(self, ref, ref_n, u):
         """ppg_debug_sample_direct: emitter_sample_direct per (ref [n, 3], ref_n [n, 3], u [n, 2]); a structured array (DEBUG_DIRECT_DTYPE)."""
         ref = np.ascontiguousarray(ref, np.float32).reshape(-1, 3)

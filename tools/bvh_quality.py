@@ -28,7 +28,7 @@ PAD_REL = 2e-6  # ppg_set_scene's box padding, relative to the scene's extent
 
 class Stats(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32), ("depth", C.c_uint32), ("n_binary_nodes", C.c_uint32),
-                ("leaf_hist", C.c_uint32 * 9), ("reserved", C.c_uint32),
+                ("leaf_hist", C.c_uint32 * 9), ("stack_need", C.c_uint32),
                 ("sa_interior", C.c_double), ("sa_leaf", C.c_double), ("sa_tris", C.c_double), ("build_seconds", C.c_double)]
 
 
@@ -52,7 +52,7 @@ def stats(lib, pos, idx, pad, max_leaf=4):
     st = Stats()
     rc = lib.ppg_debug_bvh_stats(pos.ctypes.data, idx.ctypes.data, idx.shape[0], float(pad), max_leaf, C.byref(st))
     assert rc == 0
-    return dict(triangles=int(idx.shape[0]), nodes=st.n_nodes, leaves=st.n_leaves, depth=st.depth, binary_nodes=st.n_binary_nodes,
+    return dict(triangles=int(idx.shape[0]), nodes=st.n_nodes, leaves=st.n_leaves, depth=st.depth, stack_need=st.stack_need, binary_nodes=st.n_binary_nodes,
                 leaf_hist=list(st.leaf_hist), sa_interior=st.sa_interior, sa_leaf=st.sa_leaf, sa_tris=st.sa_tris,
                 expected_node_steps=1.0 + st.sa_interior, build_seconds=st.build_seconds)
 
