@@ -250,7 +250,9 @@ const char *ppg_last_error(const ppg_ctx *ctx); /* ctx may be NULL: error of the
 const char *ppg_description(void);              /* GetDescription(), cobject.h:107: "Guided path tracer" */
 
 /* Replaces Scene::preprocess/initialize as far as this path needs it (scene.cpp:322-384): copies the
-   triangles, builds the BVH that stands in for the SAH kd-tree (skdtree.cpp:112-142), uploads. */
+   triangles, builds the BVH that stands in for the SAH kd-tree (skdtree.cpp:112-142), uploads.
+   The scene is validated and built on the host before the context is touched: PPG_ERR_INVALID leaves the previous scene set and
+   renderable exactly as before, PPG_ERR_DEVICE (a failed upload) leaves no scene set. */
 int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *scene);
 
 /* Multi-GPU image sharding (no reference counterpart; BlockedRenderProcess hands 32×32 blocks to

@@ -34,6 +34,7 @@
 #include "../../include/ppg_testhooks.h"
 #include "ppg_host_kernels.h"
 #include "ppg_launch.h"
+#include "ppg_scene_build.h"
 
 namespace {
 
@@ -208,586 +209,6 @@ int parseEnum(const char *s, const char *dflt, std::initializer_list<const char 
     return -1;
 }
 
-// ------------------------------------------------------------------------------------------------
-// BVH2 construction (binned SAH), stands in for Scene::initialize → ShapeKDTree::build
-// ------------------------------------------------------------------------------------------------
-struct BvhBuilder {
-    const float *pos; const uint32_t *idx;
-    std::vector<uint32_t> order;
-    std::vector<float> bmin, bmax, cent;  // per tri
-    std::vector<BvhNode> nodes;
-    float pad;
-    int maxLeaf = 4;  // triangles per leaf (the BVH4 child code holds up to 8)
-
-    struct Box { float lo[3], hi[3]; };
-    static Box empty() { Box b; for (int a = 0; a < 3; ++a) { b.lo[a] = INFINITY; b.hi[a] = -INFINITY; } return b; }
-    static void grow(Box &b, const float *lo, const float *hi) { for (int a = 0; a < 3; ++a) { b.lo[a] = std::min(b.lo[a], lo[a]); b.hi[a] = std::max(b.hi[a], hi[a]); } }
-    static float area(const Box &b) { float d[3] = {b.hi[0] - b.lo[0], b.hi[1] - b.lo[1], b.hi[2] - b.lo[2]}; if (d[0] < 0) return 0; return 2 * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0]); }
-
-    Box boundsOf(int first, int count) const {
-        Box b = empty();
-        for (int i = first; i < first + count; ++i) grow(b, &bmin[3 * order[i]], &bmax[3 * order[i]]);
-        return b;
-    }
-
-    // ---- the binary tree: one triangle per leaf; which subtrees become leaves of up to maxLeaf triangles is decided by collapse() ----
-    struct N2 {
-        float lo[3], hi[3];  // unpadded
-        int parent, c0, c1;  // c0 < 0: a leaf
-        int tri;             // leaf: its triangle
-        int first, count;    // range in `order` (layout())
-    };
-    std::vector<N2> t2;
-    static float areaN(const N2 &n) { const float d[3] = {n.hi[0] - n.lo[0], n.hi[1] - n.lo[1], n.hi[2] - n.lo[2]}; return 2 * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0]); }
-    static float areaU(const N2 &p, const N2 &q) {
-        float d[3];
-        for (int a = 0; a < 3; ++a) d[a] = std::max(p.hi[a], q.hi[a]) - std::min(p.lo[a], q.lo[a]);
-        return 2 * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0]);
-    }
-    // Ranges of up to SWEEP triangles: the exact SAH — all 3 (count - 1) object partitions along the sorted centroids; above: 16 bins per axis
-    // (the sweep matters in the lower levels, where a bin holds a handful of triangles; higher up the bins see the same planes.  On KITCHEN
-    // thresholds of 0 / 64 / 256 trace 10.8 / 10.0 - 10.6 / 10.7 node steps per ray after the re-optimisation: profiles/bvh_quality.json)
-    static constexpr int SWEEP = 64;
-    std::vector<uint32_t> swCur, swBest;
-    std::vector<float> swArea;
-    int sweepSplit(int first, int count) {
-        swCur.resize((size_t)count); swBest.resize((size_t)count); swArea.resize((size_t)count);
-        float bestCost = INFINITY; int bestI = -1;
-        for (int a = 0; a < 3; ++a) {
-            std::copy(order.begin() + first, order.begin() + first + count, swCur.begin());
-            std::sort(swCur.begin(), swCur.end(), [&](uint32_t x, uint32_t y) { const float cx = cent[3 * x + a], cy = cent[3 * y + a]; return cx < cy || (cx == cy && x < y); });
-            Box acc = empty();
-            for (int i = count - 1; i >= 1; --i) { grow(acc, &bmin[3 * swCur[i]], &bmax[3 * swCur[i]]); swArea[i] = area(acc); }
-            acc = empty();
-            bool better = false;
-            for (int i = 1; i < count; ++i) {
-                grow(acc, &bmin[3 * swCur[i - 1]], &bmax[3 * swCur[i - 1]]);
-                const float cost = area(acc) * i + swArea[i] * (count - i);
-                if (cost < bestCost) { bestCost = cost; bestI = i; better = true; }
-            }
-            if (better) swBest.swap(swCur);
-        }
-        if (bestI < 0) return first + count / 2;  // (areas not finite)
-        std::copy(swBest.begin(), swBest.end(), order.begin() + first);
-        return first + bestI;
-    }
-    int binnedSplit(int first, int count, const Box &cb) {
-        int bestAxis = -1, bestSplit = -1; float bestCost = INFINITY;
-        const int NB = 16;
-        for (int a = 0; a < 3; ++a) {
-            float ext = cb.hi[a] - cb.lo[a];
-            if (!(ext > 0)) continue;
-            Box bb[NB]; int bc[NB];
-            for (int k = 0; k < NB; ++k) { bb[k] = empty(); bc[k] = 0; }
-            for (int i = first; i < first + count; ++i) {
-                int k = std::min(NB - 1, (int)((cent[3 * order[i] + a] - cb.lo[a]) / ext * NB));
-                grow(bb[k], &bmin[3 * order[i]], &bmax[3 * order[i]]); bc[k]++;
-            }
-            float la[NB]; int lc[NB]; Box acc = empty(); int c = 0;
-            for (int k = 0; k < NB; ++k) { if (bc[k]) grow(acc, bb[k].lo, bb[k].hi); c += bc[k]; la[k] = area(acc); lc[k] = c; }
-            acc = empty(); c = 0;
-            for (int k = NB - 1; k > 0; --k) {
-                if (bc[k]) grow(acc, bb[k].lo, bb[k].hi); c += bc[k];
-                if (lc[k - 1] == 0 || c == 0) continue;
-                float cost = la[k - 1] * lc[k - 1] + area(acc) * c;
-                if (cost < bestCost) { bestCost = cost; bestAxis = a; bestSplit = k; }
-            }
-        }
-        if (bestAxis < 0) return first + count / 2;
-        float ext = cb.hi[bestAxis] - cb.lo[bestAxis], lo = cb.lo[bestAxis];
-        auto it = std::partition(order.begin() + first, order.begin() + first + count, [&](uint32_t t) {
-            int k = std::min(NB - 1, (int)((cent[3 * t + bestAxis] - lo) / ext * NB));
-            return k < bestSplit;
-        });
-        int mid = (int)(it - order.begin());
-        if (mid == first || mid == first + count) mid = first + count / 2;
-        return mid;
-    }
-    int build2(int first, int count, int parent) {
-        const int me = (int)t2.size();
-        t2.emplace_back();
-        {
-            N2 &n = t2[(size_t)me];
-            const Box b = boundsOf(first, count);
-            for (int a = 0; a < 3; ++a) { n.lo[a] = b.lo[a]; n.hi[a] = b.hi[a]; }
-            n.parent = parent; n.c0 = n.c1 = -1; n.tri = (int)order[first]; n.first = first; n.count = count;
-        }
-        if (count == 1) return me;
-        Box cb = empty();
-        for (int i = first; i < first + count; ++i) grow(cb, &cent[3 * order[i]], &cent[3 * order[i]]);
-        int mid;
-        if (!(cb.hi[0] > cb.lo[0]) && !(cb.hi[1] > cb.lo[1]) && !(cb.hi[2] > cb.lo[2])) mid = first + count / 2;  // coincident centroids: median
-        else mid = count <= SWEEP ? sweepSplit(first, count) : binnedSplit(first, count, cb);
-        const int l = build2(first, mid - first, me), r = build2(mid, first + count - mid, me);
-        t2[(size_t)me].c0 = l; t2[(size_t)me].c1 = r;
-        return me;
-    }
-
-    // ---- insertion-based re-optimisation of the binary tree (Bittner, Hapala, Havran: Fast insertion-based optimization of bounding volume
-    // hierarchies, CGF 2013).  A top-down build never revisits a split: a large triangle (a wall, a table top) inflates every box above it.
-    // Per batch the interior nodes that promise most (large, with a child much smaller than themselves) are taken out one after the other; the two
-    // subtrees below a removed node are put back where a branch-and-bound search finds the least increase of the tree's total surface area.
-    // Deterministic: one thread, a fixed number of batches, every tie broken by the node index — the same scene gives the same tree on every
-    // rank and in every run. ----
-    void refit(int v) {
-        for (; v >= 0; v = t2[(size_t)v].parent) {
-            N2 &n = t2[(size_t)v];
-            const N2 &p = t2[(size_t)n.c0], &q = t2[(size_t)n.c1];
-            bool same = true;
-            for (int a = 0; a < 3; ++a) {
-                const float lo = std::min(p.lo[a], q.lo[a]), hi = std::max(p.hi[a], q.hi[a]);
-                same = same && lo == n.lo[a] && hi == n.hi[a];
-                n.lo[a] = lo; n.hi[a] = hi;
-            }
-            if (same) break;
-        }
-    }
-    void replaceChild(int p, int was, int now) { N2 &n = t2[(size_t)p]; if (n.c0 == was) n.c0 = now; else n.c1 = now; t2[(size_t)now].parent = p; }
-    typedef std::pair<float, int> QEnt;  // (area the ancestors grow by, node)
-    std::vector<QEnt> heap;
-    int findTarget(int x) {
-        auto later = [](const QEnt &p, const QEnt &q) { return p.first > q.first || (p.first == q.first && p.second > q.second); };
-        const float ax = areaN(t2[(size_t)x]);
-        float best = INFINITY; int bestNode = -1;
-        heap.clear();
-        heap.push_back(QEnt(0.0f, 0));
-        while (!heap.empty()) {
-            std::pop_heap(heap.begin(), heap.end(), later);
-            const QEnt e = heap.back();
-            heap.pop_back();
-            if (e.first + ax >= best && bestNode >= 0) break;
-            const N2 &v = t2[(size_t)e.second];
-            const float total = e.first + areaU(v, t2[(size_t)x]);
-            if (e.second != 0 && (total < best || bestNode < 0)) { best = total; bestNode = e.second; }
-            const float below = total - areaN(v);
-            if (v.c0 >= 0 && (below + ax < best || bestNode < 0)) {
-                heap.push_back(QEnt(below, v.c0)); std::push_heap(heap.begin(), heap.end(), later);
-                heap.push_back(QEnt(below, v.c1)); std::push_heap(heap.begin(), heap.end(), later);
-            }
-        }
-        return bestNode;
-    }
-    void insertAt(int x, int spare) {
-        const int b = findTarget(x), bp = t2[(size_t)b].parent;
-        replaceChild(bp, b, spare);
-        N2 &f = t2[(size_t)spare];
-        f.c0 = b; f.c1 = x;
-        t2[(size_t)b].parent = spare; t2[(size_t)x].parent = spare;
-        for (int a = 0; a < 3; ++a) { f.lo[a] = std::min(t2[(size_t)b].lo[a], t2[(size_t)x].lo[a]); f.hi[a] = std::max(t2[(size_t)b].hi[a], t2[(size_t)x].hi[a]); }
-        refit(bp);
-    }
-    bool movable(int n) const { return n > 0 && t2[(size_t)n].c0 >= 0 && t2[(size_t)n].parent > 0; }
-    void reinsert(int n) {
-        const int p = t2[(size_t)n].parent, g = t2[(size_t)p].parent;
-        const int s = t2[(size_t)p].c0 == n ? t2[(size_t)p].c1 : t2[(size_t)p].c0;
-        replaceChild(g, p, s);
-        refit(g);
-        int l = t2[(size_t)n].c0, r = t2[(size_t)n].c1;
-        if (areaN(t2[(size_t)l]) < areaN(t2[(size_t)r])) std::swap(l, r);
-        insertAt(l, n);   // the two nodes the removal set free carry the two subtrees back
-        insertAt(r, p);
-    }
-    // Eight batches, each the most promising 1 % of the interior nodes — fixed numbers, never a clock.  profiles/bvh_quality.json: KITCHEN's
-    // traced node steps per ray are 10.0 - 10.8 for 4 to 40 batches of 1 - 4 % (14.2 without any) while the build grows from 3.2 to 13 s.
-    static constexpr int REOPT_PART = 100, REOPT_BATCHES = 8;
-    void reoptimise() {
-        if (t2.size() < 16) return;
-        std::vector<QEnt> cand;
-        for (int batch = 0; batch < REOPT_BATCHES; ++batch) {
-            cand.clear();
-            for (int v = 1; v < (int)t2.size(); ++v) {
-                if (!movable(v)) continue;
-                const float a = areaN(t2[(size_t)v]), a0 = areaN(t2[(size_t)t2[(size_t)v].c0]), a1 = areaN(t2[(size_t)t2[(size_t)v].c1]);
-                const float tiny = 1e-30f;
-                const float prio = a * (a / std::max(std::min(a0, a1), tiny)) * (a / std::max(0.5f * (a0 + a1), tiny));  // M_AREA M_MIN M_SUM of the paper
-                if (prio == prio) cand.push_back(QEnt(prio, v));
-            }
-            const size_t k = std::min(cand.size(), std::max<size_t>(1, t2.size() / (2 * REOPT_PART)));
-            auto first = [](const QEnt &p, const QEnt &q) { return p.first > q.first || (p.first == q.first && p.second < q.second); };
-            std::partial_sort(cand.begin(), cand.begin() + (long)k, cand.end(), first);
-            for (size_t i = 0; i < k; ++i) if (movable(cand[i].second)) reinsert(cand[i].second);
-        }
-    }
-
-    // leaf order = the tree's depth-first order, so that every subtree's triangles are contiguous (a leaf is a range); `pre` = the nodes
-    // parents first
-    std::vector<int> pre;
-    void layout() {
-        std::vector<uint32_t> fresh;
-        fresh.reserve(order.size());
-        pre.clear(); pre.reserve(t2.size());
-        std::vector<int> stack(1, 0);
-        while (!stack.empty()) {
-            const int v = stack.back();
-            stack.pop_back();
-            pre.push_back(v);
-            N2 &n = t2[(size_t)v];
-            if (n.c0 < 0) { n.first = (int)fresh.size(); n.count = 1; fresh.push_back((uint32_t)n.tri); }
-            else { stack.push_back(n.c1); stack.push_back(n.c0); }
-        }
-        for (size_t i = pre.size(); i-- > 0;) {
-            N2 &n = t2[(size_t)pre[i]];
-            if (n.c0 >= 0) { n.first = t2[(size_t)n.c0].first; n.count = t2[(size_t)n.c0].count + t2[(size_t)n.c1].count; }
-        }
-        order.swap(fresh);
-    }
-
-    // ---- collapse to 4-wide nodes: a dynamic programme over the binary tree, bottom up.  cost[v][k - 1] = the least expected cost of
-    // presenting v's triangles as exactly k children of a 4-wide node; for k = 1 the cheaper of ONE LEAF with all its triangles (where they are
-    // at most maxLeaf) and a 4-wide node of its own over the best cut of 2..4 descendants.  A child costs its box's area times C_NODE (an
-    // interior child: one more node step) or C_LEAF + C_TRI per triangle.  The constants are in node steps of k_trace: a triangle test in
-    // the (ray, triangle)-pair compaction costs about a quarter of a node step, a leaf visit (pop, vote) about as much once ----
-    static constexpr double C_NODE = 1.0, C_LEAF = 0.25, C_TRI = 0.25;
-    struct Cost4 { double k[4]; };
-    std::vector<Cost4> cost;
-    std::vector<unsigned char> asLeaf;
-    double paddedArea(const N2 &n) const {
-        const double d[3] = {(double)n.hi[0] - n.lo[0] + 2.0 * pad, (double)n.hi[1] - n.lo[1] + 2.0 * pad, (double)n.hi[2] - n.lo[2] + 2.0 * pad};
-        return 2 * (d[0] * d[1] + d[1] * d[2] + d[2] * d[0]);
-    }
-    void collapse() {
-        cost.resize(t2.size()); asLeaf.assign(t2.size(), 0);
-        for (size_t i = pre.size(); i-- > 0;) {
-            const int v = pre[i];
-            const N2 &n = t2[(size_t)v];
-            const double A = paddedArea(n);
-            Cost4 &c = cost[(size_t)v];
-            if (n.c0 < 0) { c.k[0] = A * (C_LEAF + C_TRI); c.k[1] = c.k[2] = c.k[3] = INFINITY; asLeaf[(size_t)v] = 1; continue; }
-            const Cost4 &l = cost[(size_t)n.c0], &r = cost[(size_t)n.c1];
-            double cut = INFINITY;
-            for (int k = 2; k <= 4; ++k) {
-                double best = INFINITY;
-                for (int j = 1; j < k; ++j) best = std::min(best, l.k[j - 1] + r.k[k - j - 1]);
-                c.k[k - 1] = best;
-                cut = std::min(cut, best);
-            }
-            const double node = A * C_NODE + cut, leaf = n.count <= maxLeaf ? A * (C_LEAF + C_TRI * n.count) : INFINITY;
-            asLeaf[(size_t)v] = leaf <= node;
-            c.k[0] = std::min(leaf, node);
-        }
-    }
-    void cut4(int v, int k, int *ch, int &m) const {  // the k descendants of v that cost[v][k - 1] stands for
-        if (k == 1) { ch[m++] = v; return; }
-        const N2 &n = t2[(size_t)v];
-        const Cost4 &l = cost[(size_t)n.c0], &r = cost[(size_t)n.c1];
-        int bj = 1;
-        for (int j = 2; j < k; ++j) if (l.k[j - 1] + r.k[k - j - 1] < l.k[bj - 1] + r.k[k - bj - 1]) bj = j;
-        cut4(n.c0, bj, ch, m);
-        cut4(n.c1, k - bj, ch, m);
-    }
-    int cutOf(int v, int *ch) const {  // the children of the 4-wide node that emit4 makes of v
-        int m = 0, bk = 2;
-        for (int k = 3; k <= 4; ++k) if (cost[(size_t)v].k[k - 1] < cost[(size_t)v].k[bk - 1]) bk = k;
-        cut4(v, bk, ch, m);
-        return m;
-    }
-
-    // ---- the traversal stack's bound.  The ordered walk (trace_closest4, trace_slice_bvh4) descends into the nearest child of a node and
-    // leaves the other children that were hit on its stack: on the way to a node the stack holds at most the sum of (children - 1) over the
-    // interior nodes on the path, that node included.  The STACK NEED of a tree is the largest such sum, and the kernels' stacks hold
-    // STACK_MAX entries without a range check (ppg_device.h TStack).  The SAH has no such bound: on nested geometry the sweep peels one
-    // triangle per level and the collapsed tree is a chain.  Where the need of the tree the collapse would emit exceeds the bound, the
-    // offending subtrees are built again with median splits and the tree is laid out and collapsed again.  A subtree is rebuilt as far
-    // down the offending path as a balanced one is expected to fit, so that as little of the SAH tree as possible is given up (a scene
-    // of a million triangles whose tree needs 51 loses a few subtrees of some dozen triangles, not its top): a balanced subtree of c
-    // triangles is ceil(log2 c) binary levels deep, a 4-wide node takes one to three of them on a path and adds at most 3 — 1.5 per level
-    // where the collapse pairs the levels, at most 3.  The first rounds expect 1.5 per level; a round that has not reached the bound is
-    // followed by one that expects 2, then 3 (the certain figure), which rebuilds higher up; the last resort is medians throughout.
-    // A tree within the bound is not touched. ----
-    static constexpr int STACK_MAX = 48;
-    int stackNeed = 0;  // of the finished tree (run)
-    std::vector<int> need4;
-    int needOf(int v) {  // v heads a 4-wide node
-        int ch[4];
-        const int m = cutOf(v, ch);
-        int below = 0;
-        for (int k = 0; k < m; ++k) if (!asLeaf[(size_t)ch[k]]) below = std::max(below, needOf(ch[k]));
-        return need4[(size_t)v] = m - 1 + below;
-    }
-    int perLevel2 = 3;  // twice the entries per binary level that rebound expects of a balanced subtree
-    int balancedNeed(int count) const { int l = 0; while ((1ll << l) < count) ++l; return (perLevel2 * l + 1) / 2; }
-    int buildMedian(int first, int count, int parent) {
-        const int me = (int)t2.size();
-        t2.emplace_back();
-        {
-            N2 &n = t2[(size_t)me];
-            const Box b = boundsOf(first, count);
-            for (int a = 0; a < 3; ++a) { n.lo[a] = b.lo[a]; n.hi[a] = b.hi[a]; }
-            n.parent = parent; n.c0 = n.c1 = -1; n.tri = (int)order[first]; n.first = first; n.count = count;
-        }
-        if (count == 1) return me;
-        Box cb = empty();
-        for (int i = first; i < first + count; ++i) grow(cb, &cent[3 * order[i]], &cent[3 * order[i]]);
-        int a = 0;
-        for (int k = 1; k < 3; ++k) if (cb.hi[k] - cb.lo[k] > cb.hi[a] - cb.lo[a]) a = k;
-        std::sort(order.begin() + first, order.begin() + first + count, [&](uint32_t x, uint32_t y) { const float cx = cent[3 * x + a], cy = cent[3 * y + a]; return cx < cy || (cx == cy && x < y); });
-        const int mid = first + count / 2;
-        const int l = buildMedian(first, mid - first, me), r = buildMedian(mid, first + count - mid, me);
-        t2[(size_t)me].c0 = l; t2[(size_t)me].c1 = r;
-        return me;
-    }
-    void rebuildBalanced(int v) {  // v's triangles are order[first, first + count) (layout)
-        const int first = t2[(size_t)v].first, count = t2[(size_t)v].count, p = t2[(size_t)v].parent;
-        const int fresh = buildMedian(first, count, p);
-        if (p >= 0) { replaceChild(p, v, fresh); return; }
-        t2[0] = t2[(size_t)fresh];  // the root stays node 0
-        t2[0].parent = -1;
-        t2[(size_t)t2[0].c0].parent = 0; t2[(size_t)t2[0].c1].parent = 0;
-    }
-    // v heads a 4-wide node that `above` entries lie under and whose subtree overruns the bound; a balanced subtree in v's place is expected to fit
-    void rebound(int v, int above) {
-        int ch[4];
-        const int m = cutOf(v, ch), here = above + m - 1;
-        bool deeper = true;  // every offending child can be mended below v
-        for (int k = 0; k < m; ++k) {
-            const int c = ch[k];
-            if (!asLeaf[(size_t)c] && here + need4[(size_t)c] > STACK_MAX && here + balancedNeed(t2[(size_t)c].count) > STACK_MAX) deeper = false;
-        }
-        if (!deeper) { rebuildBalanced(v); return; }
-        for (int k = 0; k < m; ++k) if (!asLeaf[(size_t)ch[k]] && here + need4[(size_t)ch[k]] > STACK_MAX) rebound(ch[k], here);
-    }
-    void boundStack() {
-        for (int round = 0; round < 8; ++round) {
-            need4.assign(t2.size(), 0);
-            if (needOf(0) <= STACK_MAX) return;
-            perLevel2 = round < 3 ? 3 : (round < 5 ? 4 : 6);
-            if (round < 7) rebound(0, 0);
-            else rebuildBalanced(0);  // (the collapse above a mended subtree may change; should that never settle: medians throughout)
-            layout();
-            collapse();
-        }
-    }
-    // the stack need of the finished nodes
-    static int stackNeedOf(const std::vector<Bvh4Node> &nodes4) {
-        int need = 0;
-        std::vector<std::pair<int, int>> todo(1, {0, 0});
-        while (!todo.empty()) {
-            const std::pair<int, int> e = todo.back();
-            todo.pop_back();
-            const Bvh4Node &nd = nodes4[(size_t)e.first];
-            int m = 0;
-            for (int k = 0; k < 4; ++k) m += nd.child[k] != PPG_BVH4_EMPTY ? 1 : 0;
-            const int here = e.second + std::max(0, m - 1);
-            need = std::max(need, here);
-            for (int k = 0; k < 4; ++k) if (nd.child[k] >= 0 && nd.child[k] != PPG_BVH4_EMPTY) todo.push_back({nd.child[k], here});
-        }
-        return need;
-    }
-
-    std::vector<Bvh4Node> nodes4;
-    int emit4(int v) {
-        int ch[4];
-        const int m = cutOf(v, ch);
-        const int me = (int)nodes4.size();
-        nodes4.emplace_back();
-        Bvh4Node nd;
-        for (int k = 0; k < 4; ++k) {
-            if (k < m) {
-                const N2 &c = t2[(size_t)ch[k]];
-                nd.lox[k] = c.lo[0] - pad; nd.loy[k] = c.lo[1] - pad; nd.loz[k] = c.lo[2] - pad;
-                nd.hix[k] = c.hi[0] + pad; nd.hiy[k] = c.hi[1] + pad; nd.hiz[k] = c.hi[2] + pad;
-                if (asLeaf[(size_t)ch[k]]) nd.child[k] = ~((c.first << 3) | (c.count - 1));
-                else nd.child[k] = emit4(ch[k]);
-            } else {
-                nd.lox[k] = nd.loy[k] = nd.loz[k] = 0; nd.hix[k] = nd.hiy[k] = nd.hiz[k] = 0; nd.child[k] = PPG_BVH4_EMPTY;
-            }
-            nd.pad[k] = 0;
-        }
-        nodes4[(size_t)me] = nd;
-        return me;
-    }
-    // the binary node array (BvhNode) with the same leaves
-    int emit2(int v) {
-        const int me = (int)nodes.size();
-        nodes.emplace_back();
-        BvhNode nd;
-        const int ch[2] = {t2[(size_t)v].c0, t2[(size_t)v].c1};
-        int ref[2], cnt[2];
-        for (int k = 0; k < 2; ++k) {
-            const N2 &c = t2[(size_t)ch[k]];
-            if (asLeaf[(size_t)ch[k]]) { ref[k] = c.first; cnt[k] = c.count; }
-            else { ref[k] = emit2(ch[k]); cnt[k] = 0; }
-            float *lo = k ? nd.lo1 : nd.lo0, *hi = k ? nd.hi1 : nd.hi0;
-            for (int a = 0; a < 3; ++a) { lo[a] = c.lo[a] - pad; hi[a] = c.hi[a] + pad; }
-        }
-        nd.c0 = ref[0]; nd.n0 = cnt[0]; nd.c1 = ref[1]; nd.n1 = cnt[1];
-        nodes[(size_t)me] = nd;
-        return me;
-    }
-
-    // quantise the child boxes of every BVH4 node (Bvh4QNode, ppg_device.h); conservativeness is verified in the device's arithmetic
-    std::vector<Bvh4QNode> nodes4q;
-    static float scaleOf(unsigned int e) { const uint32_t bits = e << 23; float f; memcpy(&f, &bits, 4); return f; }
-    void quantise() {
-        nodes4q.resize(nodes4.size());
-        for (size_t i = 0; i < nodes4.size(); ++i) {
-            const Bvh4Node &nd = nodes4[i];
-            Bvh4QNode q{};
-            const float *lo[3] = {nd.lox, nd.loy, nd.loz}, *hi[3] = {nd.hix, nd.hiy, nd.hiz};
-            float org[3];
-            unsigned int ex[3], qlo[3] = {0, 0, 0}, qhi[3] = {0, 0, 0};
-            for (int a = 0; a < 3; ++a) {
-                float mn = INFINITY, mx = -INFINITY;
-                for (int k = 0; k < 4; ++k) if (nd.child[k] != PPG_BVH4_EMPTY) { mn = std::min(mn, lo[a][k]); mx = std::max(mx, hi[a][k]); }
-                if (!(mn <= mx)) { mn = 0; mx = 0; }
-                org[a] = mn;
-                int x = 0;
-                (void)std::frexp((double)(mx - mn) / 255.0, &x);  // value = m 2^x, m in [0.5, 1): 2^x >= value
-                // exponent range: bvh4_children scales the ray by 2^-e and 1/d (up to 1e30, safe_inv) by 2^e — both stay finite within 64..154
-                // (cells of 1e-19 .. 1.3e8 scene units; ppg_set_scene refuses scenes of more than 1e9 units)
-                int e = std::max(64, std::min(154, x + 127));
-                for (;;) {  // find a cell size for which all four boxes fit into 0..255 conservatively
-                    const float s = scaleOf((unsigned int)e);
-                    bool ok = true;
-                    unsigned int wl = 0, wh = 0;
-                    for (int k = 0; k < 4 && ok; ++k) {
-                        if (nd.child[k] == PPG_BVH4_EMPTY) { wl |= 255u << (8 * k); continue; }  // inverted box: never entered
-                        long ql = (long)std::floor(((double)lo[a][k] - (double)mn) / (double)s), qh = (long)std::ceil(((double)hi[a][k] - (double)mn) / (double)s);
-                        ql = std::max(0l, std::min(255l, ql)); qh = std::max(0l, qh);
-                        // neither the float decode (trace_closest4_wave) nor the exact plane (bvh4_children) may cut into the box
-                        auto below = [&](long qq) { return mn + (float)qq * s <= lo[a][k] && (double)mn + (double)qq * (double)s <= (double)lo[a][k]; };
-                        auto above = [&](long qq) { return mn + (float)qq * s >= hi[a][k] && (double)mn + (double)qq * (double)s >= (double)hi[a][k]; };
-                        while (ql > 0 && !below(ql)) --ql;
-                        while (qh <= 255 && !above(qh)) ++qh;
-                        if (qh > 255 || !below(ql)) { ok = false; break; }
-                        wl |= (unsigned int)ql << (8 * k); wh |= (unsigned int)qh << (8 * k);
-                    }
-                    if (ok) { qlo[a] = wl; qhi[a] = wh; break; }
-                    if (++e > 154) { e = 154; qlo[a] = 0; qhi[a] = 0xffffffffu; break; }  // (unreachable below 1e9 scene units)
-                }
-                ex[a] = (unsigned int)e;
-            }
-            q.ox = org[0]; q.oy = org[1]; q.oz = org[2];
-            q.exps = ex[0] | (ex[1] << 8) | (ex[2] << 16);
-            q.qlox = qlo[0]; q.qloy = qlo[1]; q.qloz = qlo[2]; q.qhix = qhi[0]; q.qhiy = qhi[1]; q.qhiz = qhi[2];
-            for (int k = 0; k < 4; ++k) q.child[k] = nd.child[k];
-            nodes4q[i] = q;
-        }
-    }
-
-    // The TOP CUT of the tree for trace_closest4_wave (a whole wave walking ONE ray): up to 64 subtrees that partition the scene — the root's
-    // descendants after opening, level by level and then by surface area, as many interior entries as fit —, each with its box exactly as the
-    // traversal would decode it from its parent (float decode of Bvh4QNode) and its child reference.  The wave tests all of them in ONE step,
-    // one lane each, instead of descending the first three levels one dependent step at a time.  Two float4 per entry: (lo, ref) (hi, -).
-    std::vector<float> topCut;
-    void buildTopCut() {
-        struct Ent { float lo[3], hi[3]; int ref; };
-        auto childrenOfQ = [&](int node, Ent out[4]) {
-            const Bvh4QNode &q = nodes4q[(size_t)node];
-            const float sx = scaleOf(q.exps & 255u), sy = scaleOf((q.exps >> 8) & 255u), sz = scaleOf((q.exps >> 16) & 255u);
-            int m = 0;
-            for (int k = 0; k < 4; ++k) {
-                if (q.child[k] == PPG_BVH4_EMPTY) continue;
-                const int sh = 8 * k;
-                Ent e;
-                e.lo[0] = q.ox + (float)((q.qlox >> sh) & 255u) * sx; e.lo[1] = q.oy + (float)((q.qloy >> sh) & 255u) * sy; e.lo[2] = q.oz + (float)((q.qloz >> sh) & 255u) * sz;
-                e.hi[0] = q.ox + (float)((q.qhix >> sh) & 255u) * sx; e.hi[1] = q.oy + (float)((q.qhiy >> sh) & 255u) * sy; e.hi[2] = q.oz + (float)((q.qhiz >> sh) & 255u) * sz;
-                e.ref = q.child[k];
-                out[m++] = e;
-            }
-            return m;
-        };
-        std::vector<Ent> cut;
-        {
-            Ent ch[4];
-            const int m = nodes4q.empty() ? 0 : childrenOfQ(0, ch);
-            for (int k = 0; k < m; ++k) cut.push_back(ch[k]);
-        }
-        auto areaOf = [](const Ent &e) { const float d[3] = {e.hi[0] - e.lo[0], e.hi[1] - e.lo[1], e.hi[2] - e.lo[2]}; return d[0] * d[1] + d[1] * d[2] + d[2] * d[0]; };
-        for (;;) {  // open the interior entry with the largest box while the cut stays within 64 entries
-            int pick = -1; float best = -1;
-            for (size_t k = 0; k < cut.size(); ++k) if (cut[k].ref >= 0 && areaOf(cut[k]) > best) { best = areaOf(cut[k]); pick = (int)k; }
-            if (pick < 0) break;
-            Ent ch[4];
-            const int m = childrenOfQ(cut[(size_t)pick].ref, ch);
-            if (cut.size() - 1 + (size_t)m > 64) break;
-            cut.erase(cut.begin() + pick);
-            for (int k = 0; k < m; ++k) cut.push_back(ch[k]);
-        }
-        topCut.assign(8 * cut.size(), 0.0f);
-        for (size_t k = 0; k < cut.size(); ++k) {
-            float *o = &topCut[8 * k];
-            o[0] = cut[k].lo[0]; o[1] = cut[k].lo[1]; o[2] = cut[k].lo[2]; memcpy(o + 3, &cut[k].ref, 4);
-            o[4] = cut[k].hi[0]; o[5] = cut[k].hi[1]; o[6] = cut[k].hi[2];
-        }
-    }
-
-    void run(const float *positions, const uint32_t *indices, uint32_t nTris, float padAbs) {
-        runTree(positions, indices, nTris, padAbs);
-        buildTopCut();
-    }
-    void runTree(const float *positions, const uint32_t *indices, uint32_t nTris, float padAbs) {
-        pos = positions; idx = indices; pad = padAbs;
-        order.resize(nTris); bmin.resize(3 * (size_t)nTris); bmax.resize(3 * (size_t)nTris); cent.resize(3 * (size_t)nTris);
-        for (uint32_t t = 0; t < nTris; ++t) {
-            order[t] = t;
-            for (int a = 0; a < 3; ++a) {
-                float v0 = pos[3 * idx[3 * t] + a], v1 = pos[3 * idx[3 * t + 1] + a], v2 = pos[3 * idx[3 * t + 2] + a];
-                bmin[3 * t + a] = std::min(v0, std::min(v1, v2)); bmax[3 * t + a] = std::max(v0, std::max(v1, v2));
-                cent[3 * t + a] = 0.5f * (bmin[3 * t + a] + bmax[3 * t + a]);
-            }
-        }
-        nodes.clear();
-        nodes.reserve(nTris);
-        nodes.emplace_back();  // root placeholder, must be an interior node
-        if (nTris == 0) {  // spheres only: one node without children
-            nodes4.assign(1, Bvh4Node{});
-            for (int k = 0; k < 4; ++k) nodes4[0].child[k] = PPG_BVH4_EMPTY;
-            quantise();
-            return;
-        }
-        if (nTris <= 4) {  // one node with one leaf
-            BvhNode &nd = nodes[0];
-            Box bb = boundsOf(0, (int)nTris);
-            for (int a = 0; a < 3; ++a) { nd.lo0[a] = bb.lo[a] - pad; nd.hi0[a] = bb.hi[a] + pad; nd.lo1[a] = 0; nd.hi1[a] = 0; }
-            nd.c0 = 0; nd.n0 = (int)nTris; nd.c1 = 0; nd.n1 = -1;
-            Bvh4Node n4{};
-            for (int k = 0; k < 4; ++k) n4.child[k] = PPG_BVH4_EMPTY;
-            n4.lox[0] = nd.lo0[0]; n4.loy[0] = nd.lo0[1]; n4.loz[0] = nd.lo0[2]; n4.hix[0] = nd.hi0[0]; n4.hiy[0] = nd.hi0[1]; n4.hiz[0] = nd.hi0[2];
-            n4.child[0] = ~((0 << 3) | ((int)nTris - 1));
-            nodes4.assign(1, n4);
-            quantise();
-            return;
-        }
-        nodes.pop_back();
-        t2.clear(); t2.reserve(2 * (size_t)nTris);
-        build2(0, (int)nTris, -1);  // nTris > 4 ⇒ the root is interior
-        reoptimise();
-        layout();
-        collapse();
-        boundStack();
-        nodes4.clear(); nodes4.reserve(t2.size() / 4 + 1);
-        emit4(0);
-        emit2(0);
-        stackNeed = stackNeedOf(nodes4);
-        quantise();
-    }
-};
-
-// TriAccel::load (triaccel.h:62-97), same float operations as the oracle's: the three words of a triangle's record (tri_hit_regs), orig in a2.w
-static void triAccelLoad(const float *A, const float *B, const float *C, int orig, float4 out[3]) {
-    static const int waldModulo[4] = {1, 2, 0, 1};
-    const float b[3] = {C[0] - A[0], C[1] - A[1], C[2] - A[2]}, c[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
-    const float N[3] = {c[1] * b[2] - c[2] * b[1], c[2] * b[0] - c[0] * b[2], c[0] * b[1] - c[1] * b[0]};
-    int kk = 0;
-    for (int j = 0; j < 3; j++) if (ppg_abs(N[j]) > ppg_abs(N[kk])) kk = j;
-    const int u = waldModulo[kk], v = waldModulo[kk + 1];
-    const float n_k = N[kk], denom = b[u] * c[v] - b[v] * c[u];
-    float n_u = 0, n_v = 0, n_d = 0, a_u = 0, a_v = 0, b_nu = 0, b_nv = 0, c_nu = 0, c_nv = 0;
-    if (denom == 0) {
-        kk = 3;
-    } else {
-        n_u = N[u] / n_k; n_v = N[v] / n_k;
-        n_d = (A[0] * N[0] + A[1] * N[1] + A[2] * N[2]) / n_k;
-        b_nu = b[u] / denom; b_nv = -b[v] / denom;
-        a_u = A[u]; a_v = A[v];
-        c_nu = c[v] / denom; c_nv = -c[u] / denom;
-    }
-    out[0] = make_float4(n_u, n_v, n_d, __builtin_bit_cast(float, kk));
-    out[1] = make_float4(a_u, a_v, b_nu, b_nv);
-    out[2] = make_float4(c_nu, c_nv, 0.0f, __builtin_bit_cast(float, orig));
-}
-
 struct KernelTimer {
     struct Rec { hipEvent_t a, b; int id; uint64_t units; };
     std::vector<std::string> names;
@@ -923,6 +344,7 @@ struct ppg_ctx {
     ppg_lens lens{};
     std::vector<ppg_material_textures> materialTextures;  // ppg_set_material_textures: kept until replaced; ppg_set_scene validates and packs it
     std::vector<ppg_delta_emitter> deltaEmitters;  // ppg_set_delta_emitters: kept until replaced; ppg_set_scene builds d_delta from it
+    std::vector<ppg_delta_emitter> sceneDelta;     // ... as the scene that is set was built with (ppg_set_lens: the scene box)
     DevBuf<float4> d_delta;
     std::vector<ppg_shape> shapes;  // ppg_set_shapes: kept until replaced; ppg_set_scene validates it and builds d_shapes from it
     DevBuf<float4> d_shapes;
@@ -1060,6 +482,7 @@ struct ppg_ctx {
     int tuneBvhLeaf = 4;              // PPG_BVH_LEAF: triangles per BVH leaf (1..8).  KITCHEN 720p, driver's command: 4 -> 3 +3.5 % once the node test had become
                                       // cheap (130.9 -> 135.6, A/B on one box; with the world-space decode 2 / 3 / 4 / 6 / 8 gave 125.8 / 125.9 / 124.5 / 119.6 / 115.2)
     float tuneBvhPad = 2e-6f;         // PPG_BVH_PAD: box padding relative to the scene extent
+    bool tuneNoTopCut = false;        // PPG_NO_TOPCUT: trace_closest4_wave starts at the root instead of the top cut
     DevBuf<unsigned int> d_leaves, d_counts, d_offsets, d_grid;
     DevBuf<unsigned int> d_dfs[2], d_refEv, d_refLv, d_refEvOff, d_refLvOff;  // S-tree refine: leaves in the reference's (right-first) visiting order
     int dfsCur = 0;
@@ -2847,6 +2270,68 @@ int dumpSDTreeFile(ppg_ctx *ctx, const char *path) {  // GP:1191-1208 + STree::d
     return PPG_OK;
 }
 
+// Host tables to the device.  One call per table: into `buf`, grown to at least minCap elements; it gives the device pointer, or null for
+// an empty table that asked for no capacity (the optional ones).  After a failure the later calls do nothing: `e` keeps the first error.
+struct Upload {
+    hipError_t e = hipSuccess;
+    template <typename T> const T *operator()(DevBuf<T> &buf, const std::vector<T> &v, size_t minCap = 0) {
+        if (e == hipSuccess) e = buf.reserve(std::max(v.size(), minCap));
+        if (e == hipSuccess && !v.empty()) e = hipMemcpy(buf.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+        return e == hipSuccess && (!v.empty() || minCap) ? buf.p : nullptr;
+    }
+};
+
+// Every table of H into the context's buffers; S: H's scalars with the pointers of the uploaded tables.
+int uploadScene(ppg_ctx *ctx, const HostScene &H, DevScene &S) {
+    Upload up;
+    S = H.scene;
+    S.tris = up(ctx->d_tris, H.tris, 3); S.accel = up(ctx->d_accel, H.accel, 3); S.accel_small = up(ctx->d_accelSmall, H.accelSmall, 3);
+    S.normals = up(ctx->d_normals, H.normals); S.uvs = up(ctx->d_uvs, H.uvs);
+    S.bvh = up(ctx->d_bvh, H.nodes, 1); S.bvh4 = up(ctx->d_bvh4, H.nodes4q); S.bvh_top = up(ctx->d_bvhTop, H.topCut, 2);
+    S.materials = up(ctx->d_materials, H.mats); S.emitters = up(ctx->d_emitters, H.ems); S.rtrans = up(ctx->d_rtrans, H.rtrans);
+    S.mfd = up(ctx->d_mfd, H.mfd); S.coat = up(ctx->d_coat, H.coat); S.blend = up(ctx->d_blend, H.blend);
+    std::vector<DevTex> textures = H.textures;  // ... completed by the texel pointers
+    ctx->d_texTexels.clear();
+    ctx->d_texTexels.resize(textures.size());
+    for (size_t i = 0; i < textures.size(); ++i) textures[i].texels = up(ctx->d_texTexels[i], H.texTexels[i]);
+    S.textures = up(ctx->d_textures, textures);
+    S.em_texels = up(ctx->d_emTexels, H.envTexels); S.em_cdf_rows = up(ctx->d_emCdfRows, H.envCdfRows);
+    S.em_cdf_cols = up(ctx->d_emCdfCols, H.envCdfCols); S.em_row_weights = up(ctx->d_emRowWeights, H.envRowWeights);
+    S.em_sel_cdf = up(ctx->d_emSel, H.emSel); S.em_area_cdf = up(ctx->d_emArea, H.emArea); S.em_info = up(ctx->d_emInfo, H.emInfo);
+    S.em_tris = up(ctx->d_emTris, H.emTris); S.em_normals = up(ctx->d_emNrm, H.emNormals);
+    S.delta = up(ctx->d_delta, H.delta); S.shapes = up(ctx->d_shapes, H.shapes); S.spheres = up(ctx->d_spheres, H.spheres);
+    HIP_CHECK(up.e);
+    // Every array the path kernels walk must be there before a launch can chase it: an unset pointer here is a hung GPU, not a wrong pixel
+    // (round 5 lost 40 GPU minutes to five assignments that an edit had turned into a comment).
+    if (!S.materials || !S.bvh4 || (S.n_tris > 0 && (!S.tris || !S.accel || !S.bvh)) || (S.n_spheres > 0 && !S.spheres) || (S.n_delta > 0 && !S.delta) ||
+        (S.n_shapes > 0 && !S.shapes) || !S.em_sel_cdf || !S.em_info || !S.em_area_cdf || !S.em_tris || (S.env.w == 2.0f && !S.em_texels)) {
+        ctx->error = "internal: device scene incomplete";
+        return PPG_ERR_STATE;
+    }
+    return PPG_OK;
+}
+
+// scene and shard size the per-pass buffers (path state, vertex slots, queues, film)
+int sizeBuffers(ppg_ctx *ctx) {
+    ctx->pathsReady = false;
+    if (!ctx->haveScene) return PPG_OK;
+    int rc = allocPaths(ctx);
+    if (rc) return rc;
+    if ((rc = allocFilm(ctx))) return rc;
+    if ((rc = presizeRounds(ctx))) return rc;
+    ctx->pathsReady = true;
+    return PPG_OK;
+}
+
+// The per-material side lists: kept until replaced, validated against the scene and packed by ppg_set_scene.  A null list with n > 0
+// clears the list, or is refused where the list has no "none" (nullClears = false).
+template <typename T> int setSideList(ppg_ctx *ctx, const char *name, std::vector<T> &list, const T *items, uint32_t n, bool nullClears) {
+    if (ctx->renderOpen) { ctx->error = std::string(name) + ": not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (n && !items && !nullClears) { ctx->error = std::string(name) + ": no list"; return PPG_ERR_INVALID; }
+    if (!items) n = 0;
+    list.assign(items, items + n);
+    return PPG_OK;
+}
 }  // namespace
 
 // ================================================================================================
@@ -2916,6 +2401,7 @@ int ppg_create(const ppg_config *cfg, ppg_ctx **out) {
         if (const char *e = getenv("PPG_BVH_PAD")) c->tuneBvhPad = (float)atof(e);
         if (const char *e = getenv("PPG_SPLIT_DEPTH")) c->tuneSplitDepth = std::max(0, atoi(e));
         c->tuneFinalHalves = getenv("PPG_FINAL_HALVES") != nullptr;
+        c->tuneNoTopCut = getenv("PPG_NO_TOPCUT") != nullptr;
     }
     if (c->sppPerPass <= 0) { g_createError = "sppPerPass must be > 0"; return PPG_ERR_INVALID; }
     int ndev = 0;
@@ -2963,795 +2449,26 @@ void ppg_destroy(ppg_ctx *ctx) {
 
 const char *ppg_last_error(const ppg_ctx *ctx) { return ctx ? ctx->error.c_str() : g_createError.c_str(); }
 
-// Scene::getAABB() (scene.cpp:386-414): the kd-tree's box expanded by the sensor's box — the pinhole position (perspective.cpp:444-446) or,
-// with a thin lens, the aperture disk (-r, -r, 0) .. (r, r, 0) through the camera's world transform (thinlens.cpp:516-520, track.cpp:123-143)
-// ... and by every emitter's box (scene.cpp:400-413): the position of a point or spot emitter (getTranslationBounds of its static
-// transform); a directional emitter's box is empty
-static void deltaBox(ppg_ctx *ctx) {
-    for (const ppg_delta_emitter &e : ctx->deltaEmitters) {
-        if (e.type == PPG_EMITTER_DIRECTIONAL) continue;
-        for (int a = 0; a < 3; ++a) {
-            ctx->aabbMin[a] = ppg_min(ctx->aabbMin[a], e.position[a]);
-            ctx->aabbMax[a] = ppg_max(ctx->aabbMax[a], e.position[a]);
-        }
-    }
-}
-static void sceneBox(ppg_ctx *ctx, const float *c2w) {
-    for (int a = 0; a < 3; ++a) { ctx->aabbMin[a] = ctx->geomMin[a]; ctx->aabbMax[a] = ctx->geomMax[a]; }
-    if (!ctx->lensOn) {
-        for (int a = 0; a < 3; ++a) {
-            float c = c2w[4 * a + 3];
-            ctx->aabbMin[a] = ppg_min(ctx->aabbMin[a], c);
-            ctx->aabbMax[a] = ppg_max(ctx->aabbMax[a], c);
-        }
-    } else {
-        const float r = ctx->lens.aperture_radius;
-        for (int j = 0; j < 8; ++j) {  // AABB::getCorner(j) of the flat box, Transform::operator()(Point)
-            const float p[3] = {(j & 1) ? r : -r, (j & 2) ? r : -r, 0.0f};
-            float q[4];
-            for (int a = 0; a < 4; ++a) q[a] = c2w[4 * a] * p[0] + c2w[4 * a + 1] * p[1] + c2w[4 * a + 2] * p[2] + c2w[4 * a + 3];
-            for (int a = 0; a < 3; ++a) {
-                const float v = q[3] == 1.0f ? q[a] : q[a] / q[3];
-                ctx->aabbMin[a] = ppg_min(ctx->aabbMin[a], v);
-                ctx->aabbMax[a] = ppg_max(ctx->aabbMax[a], v);
-            }
-        }
-    }
-    deltaBox(ctx);
-}
-
-// Constant / EnvironmentMap: bounding sphere of createShape() (constant.cpp:67-78, envmap.cpp:330-355) around Scene::getAABB()
-static void envBSphere(ppg_ctx *ctx) {
-    float c[3], r2 = 0;
-    for (int a = 0; a < 3; ++a) { c[a] = (ctx->aabbMax[a] + ctx->aabbMin[a]) * 0.5f; }
-    const float dx = c[0] - ctx->aabbMax[0], dy = c[1] - ctx->aabbMax[1], dz = c[2] - ctx->aabbMax[2];
-    r2 = dx * dx + dy * dy + dz * dz;
-    ctx->scene.bsphere = make_float4(c[0], c[1], c[2], ppg_max(PPG_EPSILON, std::sqrt(r2) * 1.5f));
-}
-
-// One record of ppg_set_shapes: Mitsuba's own checks (disk.cpp:101-112; cylinder.cpp:99-107 leaves a rotation) and the inverse of its
-// affine transform (in double, rounded once).
-static bool shapeCheck(const ppg_shape &sh, float *inv, std::string &err) {
-    if (sh.type != PPG_SHAPE_DISK && sh.type != PPG_SHAPE_CYLINDER) { err = "unknown type"; return false; }
-    const float *m = sh.to_world;
-    for (int i = 0; i < 12; ++i) if (!std::isfinite(m[i])) { err = "a value is not finite"; return false; }
-    const bool cyl = sh.type == PPG_SHAPE_CYLINDER;
-    if (cyl && (!std::isfinite(sh.radius) || !std::isfinite(sh.length))) { err = "a value is not finite"; return false; }
-    if (cyl && !(sh.radius > 0)) { err = "cylinder: radius must be > 0"; return false; }
-    if (cyl && !(sh.length > 0)) { err = "cylinder: length must be > 0"; return false; }
-    double c[3][3], len[3];
-    for (int j = 0; j < 3; ++j) {
-        for (int a = 0; a < 3; ++a) c[j][a] = m[4 * a + j];
-        len[j] = std::sqrt(c[j][0] * c[j][0] + c[j][1] * c[j][1] + c[j][2] * c[j][2]);
-    }
-    const double det = c[0][0] * (c[1][1] * c[2][2] - c[1][2] * c[2][1]) - c[0][1] * (c[1][0] * c[2][2] - c[1][2] * c[2][0]) +
-                       c[0][2] * (c[1][0] * c[2][1] - c[1][1] * c[2][0]);
-    if (len[0] == 0 || len[1] == 0 || len[2] == 0 || !(std::abs(det) > 1e-9 * len[0] * len[1] * len[2])) { err = "its transformation is singular"; return false; }
-    auto ndot = [&](int i, int j) { return std::abs((c[i][0] * c[j][0] + c[i][1] * c[j][1] + c[i][2] * c[j][2]) / (len[i] * len[j])); };
-    if (!cyl) {
-        if (ndot(0, 1) > 1e-3) { err = "disk: its transformation contains shear"; return false; }
-        if (std::abs(len[0] / len[1] - 1) > 1e-3) { err = "disk: its transformation contains a non-uniform scale"; return false; }
-    } else {
-        if (ndot(0, 1) > 1e-3 || ndot(0, 2) > 1e-3 || ndot(1, 2) > 1e-3 || std::abs(len[0] / len[1] - 1) > 1e-3 || std::abs(len[0] / len[2] - 1) > 1e-3 ||
-            std::abs(len[0] - 1) > 1e-3) {
-            err = "cylinder: the linear part of its transformation is not a rotation (the scale belongs in radius and length)"; return false;
-        }
-    }
-    // inverse of [L | t]: [L^-1 | -L^-1 t]; row i of L^-1 = cross products of L's columns / det
-    double li[3][3];
-    for (int i = 0; i < 3; ++i) {
-        const double *a = c[(i + 1) % 3], *b = c[(i + 2) % 3];
-        li[i][0] = (a[1] * b[2] - a[2] * b[1]) / det; li[i][1] = (a[2] * b[0] - a[0] * b[2]) / det; li[i][2] = (a[0] * b[1] - a[1] * b[0]) / det;
-    }
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) inv[4 * i + j] = (float)li[i][j];
-        inv[4 * i + 3] = (float)-(li[i][0] * (double)m[3] + li[i][1] * (double)m[7] + li[i][2] * (double)m[11]);
-    }
-    return true;
-}
-
 int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
-    // a scene needs materials and at least one primitive; triangle arrays may be absent when it consists of analytic shapes only
-    if (!s || !s->materials || (s->n_triangles == 0 && s->n_spheres == 0 && ctx->shapes.empty()) ||
-        (s->n_triangles > 0 && (!s->positions || !s->indices || !s->tri_material || !s->tri_emitter))) {
-        ctx->error = "incomplete scene";
-        return PPG_ERR_INVALID;
-    }
+    const SceneInputs in{s, ctx->materialTextures, ctx->microfacet, ctx->coatings, ctx->blends, ctx->deltaEmitters, ctx->shapes,
+                         ctx->lensOn ? &ctx->lens : nullptr, ctx->tuneBvhPad, ctx->tuneBvhLeaf, ctx->tuneNoTopCut};
+    if (!sceneComplete(in)) { ctx->error = "incomplete scene"; return PPG_ERR_INVALID; }
     HIP_CHECK(hipSetDevice(ctx->device));
     ctx->quiesce();
-    for (uint32_t t = 0; t < s->n_triangles; ++t) {
-        if (s->tri_material[t] >= s->n_materials || s->tri_emitter[t] >= (int32_t)s->n_emitters) { ctx->error = "index out of range"; return PPG_ERR_INVALID; }
-        if (s->materials[s->tri_material[t]].type < 0 || s->materials[s->tri_material[t]].type > PPG_BSDF_LAST) { ctx->error = "unsupported BSDF type"; return PPG_ERR_INVALID; }
-        for (int k = 0; k < 3; ++k) if (s->indices[3 * t + k] >= s->n_vertices) { ctx->error = "vertex index out of range"; return PPG_ERR_INVALID; }
-    }
-    std::vector<int> emitterSphere(s->n_emitters, -1);  // per emitter: the analytic sphere carrying it
-    if (s->n_spheres) {
-        if (!s->spheres) { ctx->error = "spheres: n_spheres > 0 but no array"; return PPG_ERR_INVALID; }
-        std::vector<int> users(s->n_emitters, 0);
-        for (uint32_t t = 0; t < s->n_triangles; ++t) if (s->tri_emitter[t] >= 0) users[s->tri_emitter[t]] = 1;
-        for (uint32_t k = 0; k < s->n_spheres; ++k) {
-            const ppg_sphere &sp = s->spheres[k];
-            if (!(sp.radius > 0)) { ctx->error = "sphere: radius must be > 0"; return PPG_ERR_INVALID; }
-            if (sp.material >= s->n_materials || sp.emitter >= (int32_t)s->n_emitters) { ctx->error = "index out of range"; return PPG_ERR_INVALID; }
-            if (s->materials[sp.material].type < 0 || s->materials[sp.material].type > PPG_BSDF_LAST) { ctx->error = "unsupported BSDF type"; return PPG_ERR_INVALID; }
-            if (sp.emitter >= 0 && users[sp.emitter]++) { ctx->error = "sphere: its emitter is shared with another shape"; return PPG_ERR_INVALID; }
-            if (sp.emitter >= 0) emitterSphere[sp.emitter] = (int)k;
-        }
-    }
-    std::vector<int> emitterShape(s->n_emitters, -1);  // per emitter: the disk or cylinder carrying it
-    std::vector<float> shapeInv(12 * ctx->shapes.size());  // the inverses, row-major 3x4
-    if (!ctx->shapes.empty()) {
-        std::vector<int> users(s->n_emitters, 0);
-        for (uint32_t t = 0; t < s->n_triangles; ++t) if (s->tri_emitter[t] >= 0) users[s->tri_emitter[t]] = 1;
-        for (uint32_t k = 0; k < s->n_spheres; ++k) if (s->spheres[k].emitter >= 0) users[s->spheres[k].emitter] = 1;
-        for (size_t k = 0; k < ctx->shapes.size(); ++k) {
-            std::string err;
-            if (!shapeCheck(ctx->shapes[k], &shapeInv[12 * k], err)) { ctx->error = "shape " + std::to_string(k) + ": " + err; return PPG_ERR_INVALID; }
-            const ppg_shape &sh = ctx->shapes[k];
-            const std::string who = "shape " + std::to_string(k) + ": ";
-            if (sh.material >= s->n_materials) { ctx->error = who + "material index out of range"; return PPG_ERR_INVALID; }
-            if (sh.emitter >= (int32_t)s->n_emitters) { ctx->error = who + "emitter index out of range"; return PPG_ERR_INVALID; }
-            if (s->materials[sh.material].type < 0 || s->materials[sh.material].type > PPG_BSDF_LAST) { ctx->error = who + "unsupported BSDF type"; return PPG_ERR_INVALID; }
-            if (sh.emitter >= 0 && users[sh.emitter]++) { ctx->error = who + "its emitter is shared with another shape"; return PPG_ERR_INVALID; }
-            if (sh.emitter >= 0) emitterShape[sh.emitter] = (int)k;
-        }
-    }
-    // Scene::getAABB(): kd-tree box enlarged by MTS_KD_AABB_EPSILON (gkdtree.h:1213-1220) + sensor position (scene.cpp:386-414)
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (size_t t = 0; t < 3 * (size_t)s->n_triangles; ++t)
-        for (int a = 0; a < 3; ++a) { float v = s->positions[3 * s->indices[t] + a]; mn[a] = ppg_min(mn[a], v); mx[a] = ppg_max(mx[a], v); }
-    for (uint32_t k = 0; k < s->n_spheres; ++k)  // Sphere::getAABB, sphere.cpp:152-157
-        for (int a = 0; a < 3; ++a) { mn[a] = ppg_min(mn[a], s->spheres[k].center[a] - s->spheres[k].radius); mx[a] = ppg_max(mx[a], s->spheres[k].center[a] + s->spheres[k].radius); }
-    for (const ppg_shape &sh : ctx->shapes) {
-        const float *m = sh.to_world;
-        for (int a = 0; a < 3; ++a) {
-            if (sh.type == PPG_SHAPE_DISK) {  // Disk::getAABB, disk.cpp:117-130: the points (+-1, 0, 0), (0, +-1, 0) transformed
-                for (int c = 0; c < 2; ++c) for (int sg = 0; sg < 2; ++sg) {
-                    const float v = (sg ? -m[4 * a + c] : m[4 * a + c]) + m[4 * a + 3];
-                    mn[a] = ppg_min(mn[a], v); mx[a] = ppg_max(mx[a], v);
-                }
-            } else {  // Cylinder::getAABB, cylinder.cpp:252-273: the two end circles, component-wise
-                const float x1 = m[4 * a] * sh.radius, x2 = m[4 * a + 1] * sh.radius;
-                const float p0 = m[4 * a + 3], p1 = m[4 * a + 2] * sh.length + m[4 * a + 3];
-                const float range = std::sqrt(x1 * x1 + x2 * x2);
-                mn[a] = ppg_min(ppg_min(mn[a], p0 - range), p1 - range);
-                mx[a] = ppg_max(ppg_max(mx[a], p0 + range), p1 + range);
-            }
-        }
-    }
-    const float eps = 1e-3f;
-    for (int a = 0; a < 3; ++a) {
-        ctx->geomMin[a] = mn[a] - ((mx[a] - mn[a]) * eps + eps);
-        ctx->geomMax[a] = mx[a] + ((mx[a] - ctx->geomMin[a]) * eps + eps);
-    }
-    sceneBox(ctx, s->camera.camera_to_world);
-    float ext = 0;
-    for (int a = 0; a < 3; ++a) ext = std::max(ext, mx[a] - mn[a]);
-    if (!(ext < 1e9f)) { ctx->error = "scene extent of 1e9 units or more (or not finite)"; return PPG_ERR_INVALID; }  // BvhBuilder::quantise
-    BvhBuilder bb;
-    // Box padding: the BVH must return what brute force returns.  A slab test carries a few ulps of error in t, i.e. up to
-    // ~4 * 2^-24 * (distance travelled) in position; 2e-6 * (scene extent) leaves an 8x margin.  (1e-4 * extent, the first
-    // choice, made the leaf boxes of a finely tessellated model under a 100 m sky dome several triangles thick: 4x slower.)
-    const float padRel = ctx->tuneBvhPad;
-    bb.maxLeaf = ctx->tuneBvhLeaf;
-    bb.run(s->positions, s->indices, s->n_triangles, padRel * ext + 1e-30f);
-    if (bb.stackNeed > BvhBuilder::STACK_MAX) {  // (not reached by medians below 2^16 triangles per offending subtree: BvhBuilder::boundStack)
-        ctx->error = "the scene's BVH needs a traversal stack of " + std::to_string(bb.stackNeed) + " entries, the kernels' holds " + std::to_string(BvhBuilder::STACK_MAX);
-        return PPG_ERR_INVALID;
-    }
-    std::vector<float4> tris(3 * (size_t)s->n_triangles), nrm, accel(3 * (size_t)s->n_triangles);
-    if (s->normals) nrm.resize(tris.size());
-    for (uint32_t k = 0; k < s->n_triangles; ++k) {
-        uint32_t t = bb.order[k];
-        triAccelLoad(s->positions + 3 * s->indices[3 * t], s->positions + 3 * s->indices[3 * t + 1], s->positions + 3 * s->indices[3 * t + 2], (int)t, &accel[3 * k]);
-        for (int v = 0; v < 3; ++v) {
-            const float *p = s->positions + 3 * s->indices[3 * t + v];
-            float w = v == 0 ? __builtin_bit_cast(float, (int)s->tri_material[t]) : (v == 1 ? __builtin_bit_cast(float, (int)s->tri_emitter[t]) : __builtin_bit_cast(float, (int)t));
-            tris[3 * k + v] = make_float4(p[0], p[1], p[2], w);
-            if (s->normals) { const float *n = s->normals + 3 * s->indices[3 * t + v]; nrm[3 * k + v] = make_float4(n[0], n[1], n[2], 0); }
-        }
-    }
-    // material table: 4 x float4 per BSDF = (reflectance, type) (specular, alpha) (eta, flags) (k, fdrInt) (opacity, rtrans slice); the lean kernels read
-    // only the first.  configure()-time normalisation as in the plugins: "none" conductor = (eta 0, k 1) (conductor.cpp:171-173),
-    // GGX alpha clamped (microfacet.h:135), plastic's internal diffuse Fresnel reflectance (plastic.cpp:191-193)
-    std::vector<float4> mats(PPG_MAT_STRIDE * (size_t)s->n_materials), ems(std::max<uint32_t>(1, s->n_emitters));
-    ctx->fullMaterials = false;
-    bool hasNull = false;
-    if (!ctx->materialTextures.empty() && ctx->materialTextures.size() != s->n_materials) {
-        ctx->error = "material textures: the list has " + std::to_string(ctx->materialTextures.size()) + " entries, the scene " + std::to_string(s->n_materials) + " materials";
-        return PPG_ERR_INVALID;
-    }
-    for (uint32_t i = 0; i < s->n_materials; ++i) {
-        ppg_material m = s->materials[i];
-        const ppg_material_textures mt = ctx->materialTextures.empty() ? ppg_material_textures{0u, 0u, 0u, 0u} : ctx->materialTextures[i];
-        if (m.type == PPG_BSDF_DIFFUSE && m.flags == PPG_MAT_TWOSIDED) { m.type = PPG_BSDF_TWOSIDED_DIFFUSE; m.flags = 0; }
-        if (m.type == PPG_BSDF_TWOSIDED_DIFFUSE) m.flags &= ~PPG_MAT_TWOSIDED;
-        if (m.type == PPG_BSDF_MIRROR) for (int c = 0; c < 3; ++c) { m.eta[c] = 0.0f; m.k[c] = 1.0f; }
-        if (m.type == PPG_BSDF_ROUGHCONDUCTOR || m.type == PPG_BSDF_ROUGHDIELECTRIC || m.type == PPG_BSDF_ROUGHPLASTIC) m.alpha = ppg_max(m.alpha, 1e-4f);
-        if ((m.type == PPG_BSDF_PLASTIC || m.type == PPG_BSDF_DIELECTRIC || m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_ROUGHDIELECTRIC) && !(m.eta[0] > 0)) { ctx->error = "plastic / dielectric need eta[0] = intIOR / extIOR > 0"; return PPG_ERR_INVALID; }
-        float fdrInt = m.type == PPG_BSDF_PLASTIC ? ppg_fresnel_diffuse_reflectance(1 / m.eta[0]) : 0.0f;
-        if (m.type == PPG_BSDF_ROUGHPLASTIC) {  // Fdr = 1 - internal diffuse transmittance, the last entry of the slice (roughplastic.cpp:372)
-            if (m.rtrans < 0 || (uint32_t)m.rtrans >= s->n_rtrans || !s->rtrans || s->rtrans_samples < 2) { ctx->error = "roughplastic: material.rtrans is not a slice of scene.rtrans"; return PPG_ERR_INVALID; }
-            if (!(m.eta[0] > 0)) { ctx->error = "plastic / dielectric need eta[0] = intIOR / extIOR > 0"; return PPG_ERR_INVALID; }
-            fdrInt = 1 - s->rtrans[(size_t)m.rtrans * (s->rtrans_samples + 1) + s->rtrans_samples];
-        } else m.rtrans = 0;
-        if (m.type > PPG_BSDF_MIRROR || m.flags != 0) ctx->fullMaterials = true;
-        if (m.type == PPG_BSDF_THINDIELECTRIC || (m.flags & PPG_MAT_MASK)) hasNull = true;
-        mats[PPG_MAT_STRIDE * i + 0] = make_float4(m.reflectance[0], m.reflectance[1], m.reflectance[2], (float)m.type);
-        mats[PPG_MAT_STRIDE * i + 1] = make_float4(m.specular[0], m.specular[1], m.specular[2], m.alpha);
-        mats[PPG_MAT_STRIDE * i + 2] = make_float4(m.eta[0], m.eta[1], m.eta[2], __builtin_bit_cast(float, m.flags));
-        mats[PPG_MAT_STRIDE * i + 3] = make_float4(m.k[0], m.k[1], m.k[2], fdrInt);
-        mats[PPG_MAT_STRIDE * i + 4] = make_float4(m.opacity[0], m.opacity[1], m.opacity[2], __builtin_bit_cast(float, m.rtrans));
-        {   // bitmap on the diffuse reflectance / bump map around the BSDF
-            const uint32_t ta = m.texture & 0xffffu, tb = m.texture >> 16;
-            if (ta > s->n_textures || tb > s->n_textures || (m.texture && !s->textures)) { ctx->error = "material.texture: index out of range"; return PPG_ERR_INVALID; }
-            // (every BSDF type reads `reflectance`: the diffuse reflectance, or the specularReflectance of conductors and dielectrics)
-            // bitmaps on specular / alpha / opacity: ppg_set_material_textures
-            const std::string who = "material " + std::to_string(i) + ": texture slot ";
-            const bool readsSpecular = m.type == PPG_BSDF_PLASTIC || m.type == PPG_BSDF_ROUGHPLASTIC || m.type == PPG_BSDF_DIELECTRIC ||
-                                       m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_ROUGHDIELECTRIC;
-            if (mt._reserved) { ctx->error = who + "_reserved must be 0"; return PPG_ERR_INVALID; }
-            if ((mt.specular || mt.alpha || mt.opacity) && !s->textures) { ctx->error = who + "set, but the scene has no textures"; return PPG_ERR_INVALID; }
-            if (mt.specular > s->n_textures) { ctx->error = who + "specular: index out of range"; return PPG_ERR_INVALID; }
-            if (mt.alpha > s->n_textures) { ctx->error = who + "alpha: index out of range"; return PPG_ERR_INVALID; }
-            if (mt.opacity > s->n_textures) { ctx->error = who + "opacity: index out of range"; return PPG_ERR_INVALID; }
-            if (mt.specular && !readsSpecular) { ctx->error = who + "specular: only plastic, roughplastic and the dielectrics read `specular`"; return PPG_ERR_INVALID; }
-            if (mt.alpha && m.type == PPG_BSDF_ROUGHPLASTIC) {
-                ctx->error = who + "alpha: roughplastic's rough-transmittance slice is tabulated for one alpha; a roughness map is not supported"; return PPG_ERR_INVALID;
-            }
-            if (mt.alpha && m.type != PPG_BSDF_ROUGHCONDUCTOR && m.type != PPG_BSDF_ROUGHDIELECTRIC) {
-                ctx->error = who + "alpha: only roughconductor and roughdielectric read `alpha`"; return PPG_ERR_INVALID;
-            }
-            if (mt.opacity && !(m.flags & PPG_MAT_MASK)) { ctx->error = who + "opacity: the material is not masked (PPG_MAT_MASK)"; return PPG_ERR_INVALID; }
-            if (m.texture || mt.specular || mt.alpha || mt.opacity) ctx->fullMaterials = true;  // the texture code lives in the FULL kernel variants
-            if (mt.opacity || (mt.specular && m.type == PPG_BSDF_THINDIELECTRIC))  // what mat_eval_null reads is a bitmap (ppg_device.h)
-                mats[PPG_MAT_STRIDE * i + 2].w = __builtin_bit_cast(float, m.flags | PPG_MATF_NULL_TEXTURED);
-            mats[PPG_MAT_STRIDE * i + 5] = make_float4(__builtin_bit_cast(float, m.texture), __builtin_bit_cast(float, mt.specular), __builtin_bit_cast(float, mt.alpha),
-                                                       __builtin_bit_cast(float, mt.opacity));
-        }
-    }
-    for (uint32_t k = 0; k < s->n_spheres; ++k) {
-        const uint32_t sm = s->spheres[k].material;
-        if (s->materials[sm].texture) { ctx->error = "sphere: textured BSDFs are only supported on triangle meshes (not on spheres, disks or cylinders)"; return PPG_ERR_INVALID; }
-        if (!ctx->materialTextures.empty() && (ctx->materialTextures[sm].specular || ctx->materialTextures[sm].alpha || ctx->materialTextures[sm].opacity)) {
-            ctx->error = "sphere: material " + std::to_string(sm) + ": a texture slot (specular / alpha / opacity) is set; textured BSDFs are only supported on triangle meshes";
-            return PPG_ERR_INVALID;
-        }
-    }
-    for (size_t k = 0; k < ctx->shapes.size(); ++k) {
-        const uint32_t sm = ctx->shapes[k].material;
-        if (s->materials[sm].texture) { ctx->error = "shape " + std::to_string(k) + ": textured BSDFs are only supported on triangle meshes"; return PPG_ERR_INVALID; }
-        if (!ctx->materialTextures.empty() && (ctx->materialTextures[sm].specular || ctx->materialTextures[sm].alpha || ctx->materialTextures[sm].opacity)) {
-            ctx->error = "shape " + std::to_string(k) + ": material " + std::to_string(sm) + ": a texture slot (specular / alpha / opacity) is set; textured BSDFs are only supported on triangle meshes";
-            return PPG_ERR_INVALID;
-        }
-    }
-    // ppg_set_microfacet: the general MicrofacetDistribution of the three rough plug-ins
-    bool anyGeneral = false;
-    std::vector<float4> mfdTab;
-    if (!ctx->microfacet.empty()) {
-        if (ctx->microfacet.size() != s->n_materials) {
-            ctx->error = "microfacet: the list has " + std::to_string(ctx->microfacet.size()) + " entries, the scene " + std::to_string(s->n_materials) + " materials";
-            return PPG_ERR_INVALID;
-        }
-        mfdTab.assign(s->n_materials, make_float4(0, 0, 0, 0));
-        for (uint32_t i = 0; i < s->n_materials; ++i) {
-            const ppg_microfacet &g = ctx->microfacet[i];
-            const ppg_material &m = s->materials[i];
-            const std::string who = "material " + std::to_string(i) + ": microfacet: ";
-            if (g._reserved[0] || g._reserved[1] || g._reserved[2]) { ctx->error = who + "_reserved must be 0"; return PPG_ERR_INVALID; }
-            if (!g.general) continue;
-            if (m.type != PPG_BSDF_ROUGHCONDUCTOR && m.type != PPG_BSDF_ROUGHDIELECTRIC && m.type != PPG_BSDF_ROUGHPLASTIC) {
-                ctx->error = who + "only roughconductor, roughdielectric and roughplastic have a microfacet distribution"; return PPG_ERR_INVALID;
-            }
-            if (g.distribution != 0 && g.distribution != 1) { ctx->error = who + "distribution must be 0 (ggx / beckmann) or 1 (phong)"; return PPG_ERR_INVALID; }
-            if (!std::isfinite(g.alpha_v)) { ctx->error = who + "alpha_v is not finite"; return PPG_ERR_INVALID; }
-            if (g.alpha_v_texture > s->n_textures || (g.alpha_v_texture && !s->textures)) { ctx->error = who + "alpha_v_texture: index out of range"; return PPG_ERR_INVALID; }
-            const float alphaU = ppg_max(m.alpha, 1e-4f), alphaV = ppg_max(g.alpha_v, 1e-4f);
-            if (m.type == PPG_BSDF_ROUGHPLASTIC && g.alpha_v_texture) {
-                ctx->error = who + "alpha_v_texture: roughplastic's rough-transmittance slice is tabulated for one alpha; a roughness map is not supported"; return PPG_ERR_INVALID;
-            }
-            if (m.type == PPG_BSDF_ROUGHPLASTIC && alphaU != alphaV) {  // roughplastic.cpp:221
-                ctx->error = who + "roughplastic: the 'roughplastic' plugin currently does not support anisotropic microfacet distributions!"; return PPG_ERR_INVALID;
-            }
-            const bool alphaTextured = g.alpha_v_texture || (!ctx->materialTextures.empty() && ctx->materialTextures[i].alpha);
-            uint32_t bits = PPG_MFDF_GENERAL;
-            if (g.distribution == 1) bits |= PPG_MFDF_PHONG | PPG_MFDF_SAMPLE_ALL;  // microfacet.h:141-142
-            if (g.sample_all) bits |= PPG_MFDF_SAMPLE_ALL;
-            if (alphaU != alphaV || alphaTextured) bits |= PPG_MFDF_ANISO;
-            mfdTab[i] = make_float4(alphaV, __builtin_bit_cast(float, bits), __builtin_bit_cast(float, g.alpha_v_texture), 0.0f);
-            anyGeneral = true;
-        }
-        for (uint32_t k = 0; anyGeneral && k < s->n_spheres; ++k)
-            if (__builtin_bit_cast(uint32_t, mfdTab[s->spheres[k].material].z)) { ctx->error = "sphere: a textured alphaV is only supported on triangle meshes"; return PPG_ERR_INVALID; }
-        for (size_t k = 0; anyGeneral && k < ctx->shapes.size(); ++k)
-            if (__builtin_bit_cast(uint32_t, mfdTab[ctx->shapes[k].material].z)) { ctx->error = "shape " + std::to_string(k) + ": a textured alphaV is only supported on triangle meshes"; return PPG_ERR_INVALID; }
-        // an anisotropic BSDF needs UV tangents, which need texture coordinates (trimesh.cpp:686-691)
-        for (uint32_t t = 0; anyGeneral && t < s->n_triangles; ++t) {
-            if (!(__builtin_bit_cast(uint32_t, mfdTab[s->tri_material[t]].y) & PPG_MFDF_ANISO)) continue;
-            bool has = s->texcoords != nullptr;
-            for (int v = 0; has && v < 3; ++v) { const float q = s->texcoords[2 * (size_t)s->indices[3 * (size_t)t + v]]; if (q != q) has = false; }
-            if (!has) {
-                ctx->error = "triangle " + std::to_string(t) + ": material " + std::to_string(s->tri_material[t]) +
-                             ": anisotropic microfacet distribution: the mesh is missing texture coordinates! The tangent space cannot be computed";
-                return PPG_ERR_INVALID;
-            }
-        }
-    }
-    ctx->scene.mfd = nullptr;
-    ctx->nMaterials = s->n_materials;
-    if (anyGeneral) {
-        HIP_CHECK(ctx->d_mfd.reserve(mfdTab.size()));
-        HIP_CHECK(hipMemcpy(ctx->d_mfd.p, mfdTab.data(), mfdTab.size() * sizeof(float4), hipMemcpyHostToDevice));
-        ctx->scene.mfd = ctx->d_mfd.p;
-        ctx->fullMaterials = true;  // (the rough types are FULL anyway)
-    }
-    // ppg_set_coatings: the coating / roughcoating adapters
-    bool anyCoat = false;
-    std::vector<float4> coatTab;
-    if (!ctx->coatings.empty()) {
-        if (ctx->coatings.size() != s->n_materials) {
-            ctx->error = "coatings: the list has " + std::to_string(ctx->coatings.size()) + " entries, the scene " + std::to_string(s->n_materials) + " materials";
-            return PPG_ERR_INVALID;
-        }
-        coatTab.assign(PPG_COAT_STRIDE * (size_t)s->n_materials, make_float4(0, 0, 0, 0));
-        for (uint32_t i = 0; i < s->n_materials; ++i) {
-            const ppg_coating &c = ctx->coatings[i];
-            const ppg_material &m = s->materials[i];
-            const std::string who = "material " + std::to_string(i) + ": coating: ";
-            if (c._reserved[0] || c._reserved[1] || c._reserved[2]) { ctx->error = who + "_reserved must be 0"; return PPG_ERR_INVALID; }
-            if (c.kind == 0) continue;
-            if (c.kind != 1 && c.kind != 2) { ctx->error = who + "kind must be 0 (none), 1 (coating) or 2 (roughcoating)"; return PPG_ERR_INVALID; }
-            const char *name = c.kind == 1 ? "coating" : "roughcoating";
-            if (m.type == PPG_BSDF_DIELECTRIC || m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_ROUGHDIELECTRIC || m.type < 0 || m.type > PPG_BSDF_LAST) {
-                ctx->error = who + name + " over dielectric, thindielectric or roughdielectric is not supported"; return PPG_ERR_INVALID;
-            }
-            if (c.kind == 2 && (m.type == PPG_BSDF_MIRROR || m.type == PPG_BSDF_CONDUCTOR || m.type == PPG_BSDF_PLASTIC)) {
-                ctx->error = who + "roughcoating over a BSDF with a delta component (conductor, plastic) is not supported"; return PPG_ERR_INVALID;
-            }
-            bool finite = std::isfinite(c.eta) && std::isfinite(c.thickness);
-            for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(c.sigma_a[k]) && std::isfinite(c.specular[k]);
-            if (c.kind == 2) finite = finite && std::isfinite(c.alpha);
-            if (!finite) { ctx->error = who + "a value is not finite"; return PPG_ERR_INVALID; }
-            if (!(c.eta > 0) || c.eta == 1.0f) { ctx->error = who + "the interior and exterior indices of refraction must be positive and differ (eta > 0, eta != 1)"; return PPG_ERR_INVALID; }
-            if (c.thickness < 0) { ctx->error = who + "thickness must not be negative"; return PPG_ERR_INVALID; }
-            if (c.sigma_a[0] < 0 || c.sigma_a[1] < 0 || c.sigma_a[2] < 0) { ctx->error = who + "sigma_a must not be negative"; return PPG_ERR_INVALID; }
-            uint32_t bits = (uint32_t)c.kind;
-            int rows = 0;
-            if (c.kind == 2) {
-                if (c.distribution < 0 || c.distribution > 2) { ctx->error = who + "distribution must be 0 (beckmann), 1 (ggx) or 2 (phong)"; return PPG_ERR_INVALID; }
-                if (c.rtrans < 0 || (uint32_t)c.rtrans >= s->n_rtrans || !s->rtrans || s->rtrans_samples < 2) {
-                    ctx->error = who + "rtrans is not a slice of scene.rtrans"; return PPG_ERR_INVALID;
-                }
-                bits |= (uint32_t)c.distribution << PPG_COATF_TYPE_SHIFT;
-                if (c.sample_all || c.distribution == 2) bits |= PPG_COATF_SAMPLE_ALL;  // microfacet.h:141-142
-                rows = c.rtrans - (m.type == PPG_BSDF_ROUGHPLASTIC ? m.rtrans : 0);  // from the slice the material record names (Mat::rt)
-            }
-            // m_specularSamplingWeight (coating.cpp:178-181), once, with the library's own exp: every host gets the same bits
-            float sum = 0.0f;
-            for (int k = 0; k < 3; ++k) sum += ppg_exp(c.sigma_a[k] * (-2 * c.thickness));
-            const float avgAbsorption = sum * (1.0f / 3);
-            const float weight = 1.0f / (avgAbsorption + 1.0f);
-            coatTab[PPG_COAT_STRIDE * (size_t)i + 0] = make_float4(c.eta, c.thickness, weight, __builtin_bit_cast(float, bits));
-            coatTab[PPG_COAT_STRIDE * (size_t)i + 1] = make_float4(c.sigma_a[0], c.sigma_a[1], c.sigma_a[2], c.kind == 2 ? c.alpha : 0.0f);
-            coatTab[PPG_COAT_STRIDE * (size_t)i + 2] = make_float4(c.specular[0], c.specular[1], c.specular[2], __builtin_bit_cast(float, rows));
-            anyCoat = true;
-        }
-    }
-    ctx->scene.coat = nullptr;
-    if (anyCoat) {
-        HIP_CHECK(ctx->d_coat.reserve(coatTab.size()));
-        HIP_CHECK(hipMemcpy(ctx->d_coat.p, coatTab.data(), coatTab.size() * sizeof(float4), hipMemcpyHostToDevice));
-        ctx->scene.coat = ctx->d_coat.p;
-        ctx->fullMaterials = true;
-    }
-    // ppg_set_blends: the blendbsdf / mixturebsdf combinators.  Everything the device code relies on is checked here — every child index,
-    // and that a child is a plain leaf —, so its loops over the children are bounded and nothing recurses.
-    bool anyBlend = false;
-    std::vector<float4> blendTab;
-    if (!ctx->blends.empty()) {
-        if (ctx->blends.size() != s->n_materials) {
-            ctx->error = "blends: the list has " + std::to_string(ctx->blends.size()) + " entries, the scene " + std::to_string(s->n_materials) + " materials";
-            return PPG_ERR_INVALID;
-        }
-        blendTab.assign(PPG_BLEND_STRIDE * (size_t)s->n_materials, make_float4(0, 0, 0, 0));
-        std::vector<unsigned char> readsBitmap(s->n_materials, 0), anisoChild(s->n_materials, 0);
-        const auto mtOf = [&](uint32_t i) { return ctx->materialTextures.empty() ? ppg_material_textures{0u, 0u, 0u, 0u} : ctx->materialTextures[i]; };
-        for (uint32_t i = 0; i < s->n_materials; ++i) {
-            const ppg_blend &b = ctx->blends[i];
-            const ppg_material &m = s->materials[i];
-            const std::string who = "material " + std::to_string(i) + ": blend: ";
-            if (b._reserved[0] || b._reserved[1] || b._reserved[2] || b._reserved[3]) { ctx->error = who + "_reserved must be 0"; return PPG_ERR_INVALID; }
-            if (b.kind == 0) continue;
-            if (b.kind != 1 && b.kind != 2) { ctx->error = who + "kind must be 0 (none), 1 (blendbsdf) or 2 (mixturebsdf)"; return PPG_ERR_INVALID; }
-            const char *name = b.kind == 1 ? "blendbsdf" : "mixturebsdf";
-            if (b.kind == 1 && b.n != 2) { ctx->error = who + "blendbsdf takes exactly two nested BSDFs (n = " + std::to_string(b.n) + ")"; return PPG_ERR_INVALID; }
-            if (b.n < 1 || b.n > PPG_BLEND_MAX) { ctx->error = who + "mixturebsdf takes 1 .. " + std::to_string(PPG_BLEND_MAX) + " nested BSDFs (n = " + std::to_string(b.n) + ")"; return PPG_ERR_INVALID; }
-            if (m.type != PPG_BSDF_DIFFUSE) { ctx->error = who + "the blended material's own record must be of type PPG_BSDF_DIFFUSE (it only carries the adapters)"; return PPG_ERR_INVALID; }
-            if (!ctx->coatings.empty() && ctx->coatings[i].kind) { ctx->error = who + "coating(" + name + ") is not supported"; return PPG_ERR_INVALID; }
-            if (m.texture & 0xffffu) { ctx->error = who + "a reflectance bitmap on the blended record itself is not supported (set it on a child)"; return PPG_ERR_INVALID; }
-            if (mtOf(i).specular || mtOf(i).alpha) { ctx->error = who + "a specular / alpha texture slot on the blended record itself is not supported (set it on a child)"; return PPG_ERR_INVALID; }
-            if (!ctx->microfacet.empty() && ctx->microfacet[i].general) { ctx->error = who + "a microfacet entry on the blended record itself is not supported (set it on a child)"; return PPG_ERR_INVALID; }
-            for (uint32_t k = 0; k < b.n; ++k) {
-                const uint32_t c = b.child[k];
-                const std::string kid = who + "child " + std::to_string(k) + " (material " + std::to_string(c) + ")";
-                if (c >= s->n_materials) { ctx->error = kid + ": index out of range"; return PPG_ERR_INVALID; }
-                const ppg_material &cm = s->materials[c];
-                if (ctx->blends[c].kind) { ctx->error = kid + " is itself blended: blends of blends are not supported"; return PPG_ERR_INVALID; }
-                if (!ctx->coatings.empty() && ctx->coatings[c].kind) { ctx->error = kid + " is coated: coated children are not supported"; return PPG_ERR_INVALID; }
-                if (cm.type == PPG_BSDF_DIELECTRIC || cm.type == PPG_BSDF_THINDIELECTRIC || cm.type == PPG_BSDF_ROUGHDIELECTRIC || cm.type < 0 || cm.type > PPG_BSDF_LAST) {
-                    ctx->error = kid + ": dielectric, thindielectric and roughdielectric children are not supported"; return PPG_ERR_INVALID;
-                }
-                if ((cm.flags & (PPG_MAT_TWOSIDED | PPG_MAT_MASK)) || cm.type == PPG_BSDF_TWOSIDED_DIFFUSE || (cm.texture >> 16)) {
-                    ctx->error = kid + " is masked, two-sided or bump-mapped: the adapters go around the blend, on its own record"; return PPG_ERR_INVALID;
-                }
-                if ((cm.texture & 0xffffu) || mtOf(c).specular || mtOf(c).alpha || (!ctx->microfacet.empty() && ctx->microfacet[c].general && ctx->microfacet[c].alpha_v_texture))
-                    readsBitmap[i] = 1;
-                if (!mfdTab.empty() && (__builtin_bit_cast(uint32_t, mfdTab[c].y) & PPG_MFDF_ANISO)) anisoChild[i] = 1;
-            }
-            for (uint32_t k = b.n; k < PPG_BLEND_MAX; ++k)
-                if (b.child[k] || b.weight[k] != 0.0f) { ctx->error = who + "child and weight beyond n must be 0"; return PPG_ERR_INVALID; }
-            float we[PPG_BLEND_MAX] = {0, 0, 0, 0}, cdf[PPG_BLEND_MAX + 1] = {0, 0, 0, 0, 0};
-            uint32_t weightTex = 0;
-            if (b.kind == 1) {
-                if (!std::isfinite(b.weight[0]) || b.weight[0] < 0) { ctx->error = who + "weight must be finite and not negative"; return PPG_ERR_INVALID; }
-                if (b.weight[1] != 0.0f) { ctx->error = who + "blendbsdf reads weight[0] only; weight[1] must be 0"; return PPG_ERR_INVALID; }
-                if (b.ensure_energy_conservation) { ctx->error = who + "ensure_energy_conservation belongs to mixturebsdf; must be 0"; return PPG_ERR_INVALID; }
-                if (b.weight_texture > s->n_textures || (b.weight_texture && !s->textures)) { ctx->error = who + "weight_texture: index out of range"; return PPG_ERR_INVALID; }
-                weightTex = b.weight_texture;
-                if (weightTex) readsBitmap[i] = 1;
-                const float w = ppg_min(1.0f, ppg_max(0.0f, b.weight[0]));  // blendbsdf.cpp:136-137
-                we[0] = 1 - w; we[1] = w;
-                cdf[1] = we[0]; cdf[2] = 1.0f;  // (the device chooses by sample.x < weights[0], as the plug-in does: not read)
-            } else {
-                if (b.weight_texture) { ctx->error = who + "weight_texture belongs to blendbsdf; must be 0"; return PPG_ERR_INVALID; }
-                float total = 0.0f;
-                for (uint32_t k = 0; k < b.n; ++k) {
-                    if (!std::isfinite(b.weight[k]) || b.weight[k] < 0) { ctx->error = who + "weights must be finite and not negative"; return PPG_ERR_INVALID; }
-                    we[k] = b.weight[k];
-                    total += we[k];  // mixturebsdf.cpp:123-125
-                }
-                if (!std::isfinite(total)) { ctx->error = who + "weights must be finite and not negative"; return PPG_ERR_INVALID; }
-                if (!(total > 0)) { ctx->error = who + "The weights must sum to a value greater than zero!"; return PPG_ERR_INVALID; }
-                if (b.ensure_energy_conservation && total > 1) {  // mixturebsdf.cpp:130-141
-                    const float scale = 1.0f / total;
-                    for (uint32_t k = 0; k < b.n; ++k) we[k] *= scale;
-                }
-                for (uint32_t k = 0; k < b.n; ++k) cdf[k + 1] = cdf[k] + we[k];  // DiscreteDistribution::append, pmf.h:68-70
-                const float norm = 1.0f / cdf[b.n];                                // ... ::normalize, pmf.h:101-114
-                for (uint32_t k = 1; k <= b.n; ++k) cdf[k] *= norm;
-                cdf[b.n] = 1.0f;
-            }
-            bool smoothAny = false;
-            for (uint32_t k = 0; k < b.n; ++k) {
-                const int t = s->materials[b.child[k]].type;
-                smoothAny = smoothAny || t == PPG_BSDF_DIFFUSE || t == PPG_BSDF_ROUGHCONDUCTOR || t == PPG_BSDF_PLASTIC || t == PPG_BSDF_ROUGHPLASTIC;
-            }
-            uint32_t bits = (uint32_t)b.kind | (b.n << PPG_BLENDF_N_SHIFT);
-            if (readsBitmap[i] || anisoChild[i]) bits |= PPG_BLENDF_TEXTURED;
-            if (smoothAny) bits |= PPG_BLENDF_SMOOTH;
-            float4 *row = &blendTab[PPG_BLEND_STRIDE * (size_t)i];
-            row[0] = make_float4(__builtin_bit_cast(float, b.child[0]), __builtin_bit_cast(float, b.child[1]), __builtin_bit_cast(float, b.child[2]), __builtin_bit_cast(float, b.child[3]));
-            row[1] = make_float4(we[0], we[1], we[2], we[3]);
-            row[2] = make_float4(cdf[0], cdf[1], cdf[2], cdf[3]);
-            row[3] = make_float4(cdf[4], __builtin_bit_cast(float, bits), __builtin_bit_cast(float, weightTex), 0.0f);
-            anyBlend = true;
-        }
-        for (uint32_t k = 0; anyBlend && k < s->n_spheres; ++k)
-            if (readsBitmap[s->spheres[k].material]) {
-                ctx->error = "sphere: material " + std::to_string(s->spheres[k].material) + ": blend: textured BSDFs are only supported on triangle meshes"; return PPG_ERR_INVALID;
-            }
-        for (size_t k = 0; anyBlend && k < ctx->shapes.size(); ++k)
-            if (readsBitmap[ctx->shapes[k].material]) {
-                ctx->error = "shape " + std::to_string(k) + ": material " + std::to_string(ctx->shapes[k].material) + ": blend: textured BSDFs are only supported on triangle meshes"; return PPG_ERR_INVALID;
-            }
-        for (uint32_t t = 0; anyBlend && t < s->n_triangles; ++t) {  // an anisotropic child needs UV tangents, as an anisotropic material does
-            if (!anisoChild[s->tri_material[t]]) continue;
-            bool has = s->texcoords != nullptr;
-            for (int v = 0; has && v < 3; ++v) { const float q = s->texcoords[2 * (size_t)s->indices[3 * (size_t)t + v]]; if (q != q) has = false; }
-            if (!has) {
-                ctx->error = "triangle " + std::to_string(t) + ": material " + std::to_string(s->tri_material[t]) +
-                             ": blend: anisotropic microfacet distribution: the mesh is missing texture coordinates! The tangent space cannot be computed";
-                return PPG_ERR_INVALID;
-            }
-        }
-    }
-    ctx->scene.blend = nullptr;
-    if (anyBlend) {
-        HIP_CHECK(ctx->d_blend.reserve(blendTab.size()));
-        HIP_CHECK(hipMemcpy(ctx->d_blend.p, blendTab.data(), blendTab.size() * sizeof(float4), hipMemcpyHostToDevice));
-        ctx->scene.blend = ctx->d_blend.p;
-        ctx->fullMaterials = true;
-    }
-    ctx->scene.uvs = nullptr; ctx->scene.textures = nullptr;
-    if (s->texcoords) {
-        std::vector<float2> uv(3 * (size_t)s->n_triangles);
-        for (uint32_t k = 0; k < s->n_triangles; ++k) {
-            const uint32_t t = bb.order[k];
-            for (int v = 0; v < 3; ++v) { const float *q = s->texcoords + 2 * (size_t)s->indices[3 * t + v]; uv[3 * (size_t)k + v] = make_float2(q[0], q[1]); }
-        }
-        HIP_CHECK(ctx->d_uvs.reserve(uv.size()));
-        HIP_CHECK(hipMemcpy(ctx->d_uvs.p, uv.data(), uv.size() * sizeof(float2), hipMemcpyHostToDevice));
-        ctx->scene.uvs = ctx->d_uvs.p;
-    }
-    ctx->d_texTexels.clear();
-    if (s->n_textures) {
-        if (!s->textures) { ctx->error = "textures: n_textures > 0 but no array"; return PPG_ERR_INVALID; }
-        std::vector<DevTex> table(s->n_textures);
-        ctx->d_texTexels.resize(s->n_textures);
-        for (uint32_t i = 0; i < s->n_textures; ++i) {
-            const ppg_texture &t = s->textures[i];
-            if (!t.rgb || t.width == 0 || t.height == 0 || t.width > 0x7fff || t.height > 0x7fff || t.wrap_u < 0 || t.wrap_u > PPG_WRAP_ONE || t.wrap_v < 0 || t.wrap_v > PPG_WRAP_ONE) {
-                ctx->error = "texture: needs pixels, 0 < width, height < 32768 and valid wrap modes"; return PPG_ERR_INVALID;
-            }
-            const size_t n = (size_t)t.width * t.height;
-            std::vector<float4> px(n);
-            for (size_t k = 0; k < n; ++k) px[k] = make_float4(t.rgb[3 * k], t.rgb[3 * k + 1], t.rgb[3 * k + 2], 0.0f);
-            HIP_CHECK(ctx->d_texTexels[i].reserve(n));
-            HIP_CHECK(hipMemcpy(ctx->d_texTexels[i].p, px.data(), n * sizeof(float4), hipMemcpyHostToDevice));
-            DevTex &d = table[i];
-            d.texels = ctx->d_texTexels[i].p; d.w = (int)t.width; d.h = (int)t.height; d.su = t.uv_scale[0]; d.sv = t.uv_scale[1]; d.ou = t.uv_offset[0]; d.ov = t.uv_offset[1];
-            d.wrap_u = t.wrap_u; d.wrap_v = t.wrap_v; d.nearest = t.nearest != 0; d.pad = 0;
-        }
-        HIP_CHECK(ctx->d_textures.reserve(table.size()));
-        HIP_CHECK(hipMemcpy(ctx->d_textures.p, table.data(), table.size() * sizeof(DevTex), hipMemcpyHostToDevice));
-        ctx->scene.textures = ctx->d_textures.p;
-    }
-    for (uint32_t i = 0; i < s->n_emitters; ++i) ems[i] = make_float4(s->emitters[i].radiance[0], s->emitters[i].radiance[1], s->emitters[i].radiance[2], 0);
-    HIP_CHECK(ctx->d_tris.reserve(std::max<size_t>(tris.size(), 3)));
-    HIP_CHECK(hipMemcpy(ctx->d_tris.p, tris.data(), tris.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIP_CHECK(ctx->d_accel.reserve(std::max<size_t>(accel.size(), 3)));
-    HIP_CHECK(hipMemcpy(ctx->d_accel.p, accel.data(), accel.size() * sizeof(float4), hipMemcpyHostToDevice));
-    {   // small scenes are traced by brute force from LDS: the same records grouped by projection axis (degenerate ones dropped,
-        // the rest padded with never-hit records so that n_tris records can always be staged), leaf-order index in record[2].z
-        std::vector<float4> small(accel.size(), make_float4(0, 0, 0, __builtin_bit_cast(float, 3)));
-        int n[3] = {0, 0, 0};
-        if (s->n_triangles <= 64) {
-            size_t w = 0;
-            for (int axis = 0; axis < 3; ++axis)
-                for (uint32_t k = 0; k < s->n_triangles; ++k)
-                    if (__builtin_bit_cast(int, accel[3 * k].w) == axis) {
-                        small[3 * w] = accel[3 * k]; small[3 * w + 1] = accel[3 * k + 1]; small[3 * w + 2] = accel[3 * k + 2];
-                        small[3 * w + 2].z = __builtin_bit_cast(float, (int)k);
-                        ++w; ++n[axis];
-                    }
-        }
-        HIP_CHECK(ctx->d_accelSmall.reserve(std::max<size_t>(small.size(), 3)));
-        HIP_CHECK(hipMemcpy(ctx->d_accelSmall.p, small.data(), small.size() * sizeof(float4), hipMemcpyHostToDevice));
-        for (int axis = 0; axis < 3; ++axis) ctx->scene.small_n[axis] = n[axis];
-        ctx->scene.accel_small = ctx->d_accelSmall.p;
-    }
-    if (s->normals) { HIP_CHECK(ctx->d_normals.reserve(nrm.size())); HIP_CHECK(hipMemcpy(ctx->d_normals.p, nrm.data(), nrm.size() * sizeof(float4), hipMemcpyHostToDevice)); }
-    HIP_CHECK(ctx->d_bvh.reserve(std::max<size_t>(bb.nodes.size(), 1)));
-    HIP_CHECK(hipMemcpy(ctx->d_bvh.p, bb.nodes.data(), bb.nodes.size() * sizeof(BvhNode), hipMemcpyHostToDevice));
-    HIP_CHECK(ctx->d_bvh4.reserve(bb.nodes4q.size()));
-    HIP_CHECK(hipMemcpy(ctx->d_bvh4.p, bb.nodes4q.data(), bb.nodes4q.size() * sizeof(Bvh4QNode), hipMemcpyHostToDevice));
-    HIP_CHECK(ctx->d_bvhTop.reserve(std::max<size_t>(2, bb.topCut.size() / 4)));
-    if (!bb.topCut.empty()) HIP_CHECK(hipMemcpy(ctx->d_bvhTop.p, bb.topCut.data(), bb.topCut.size() * sizeof(float), hipMemcpyHostToDevice));
-    const int nTop = getenv("PPG_NO_TOPCUT") ? 0 : (int)(bb.topCut.size() / 8);
-    if (s->n_rtrans && s->rtrans) {
-        const size_t n = (size_t)s->n_rtrans * (s->rtrans_samples + 1);
-        HIP_CHECK(ctx->d_rtrans.reserve(n));
-        HIP_CHECK(hipMemcpy(ctx->d_rtrans.p, s->rtrans, n * sizeof(float), hipMemcpyHostToDevice));
-    }
-    HIP_CHECK(ctx->d_materials.reserve(mats.size()));
-    HIP_CHECK(hipMemcpy(ctx->d_materials.p, mats.data(), mats.size() * sizeof(float4), hipMemcpyHostToDevice));
-    HIP_CHECK(ctx->d_emitters.reserve(ems.size()));
-    HIP_CHECK(hipMemcpy(ctx->d_emitters.p, ems.data(), ems.size() * sizeof(float4), hipMemcpyHostToDevice));
-    ctx->scene.em_texels = nullptr; ctx->scene.em_w = ctx->scene.em_h = 0;
-    if (s->envmap) {  // EnvironmentMap::configure (envmap.cpp:255-322): the same float running sums as the oracle's
-        const ppg_envmap &em = *s->envmap;
-        if (s->environment) { ctx->error = "envmap: a scene has one environment emitter (`environment` is set as well)"; return PPG_ERR_INVALID; }
-        if (!em.rgb || em.width == 0 || em.height == 0 || em.width > 0xFFFF || em.height > 0xFFFF) { ctx->error = "envmap: needs pixels and 0 < width, height < 65536"; return PPG_ERR_INVALID; }
-        const int w = (int)em.width, h = (int)em.height;
-        std::vector<float4> tex((size_t)w * h);
-        std::vector<float> cdfCols((size_t)(w + 1) * h, 0.0f), cdfRows(h + 1, 0.0f), rowWeights(h, 0.0f);
-        size_t colPos = 0, rowPos = 0;
-        float rowSum = 0.0f;
-        cdfRows[rowPos++] = 0;
-        for (int y = 0; y < h; ++y) {
-            float colSum = 0;
-            cdfCols[colPos++] = 0;
-            for (int x = 0; x < w; ++x) {
-                const float *px = em.rgb + 3 * ((size_t)y * w + x);
-                tex[(size_t)y * w + x] = make_float4(px[0], px[1], px[2], 0.0f);
-                colSum += px[0] * 0.212671f + px[1] * 0.715160f + px[2] * 0.072169f;
-                cdfCols[colPos++] = colSum;
-            }
-            const float normalization = 1.0f / colSum;
-            for (int x = 1; x < w; ++x) cdfCols[colPos - x - 1] *= normalization;
-            cdfCols[colPos - 1] = 1.0f;
-            float weight, cosUnused;
-            ppg_sincos((y + 0.5f) * PPG_PI_F / h, &weight, &cosUnused);
-            rowWeights[y] = weight;
-            rowSum += colSum * weight;
-            cdfRows[rowPos++] = rowSum;
-        }
-        const float norm = 1.0f / rowSum;
-        for (int y = 1; y < h; ++y) cdfRows[rowPos - y - 1] *= norm;
-        cdfRows[rowPos - 1] = 1.0f;
-        if (!(rowSum > 0) || !std::isfinite(rowSum)) { ctx->error = "envmap: the environment map is completely black or holds nan / inf (envmap.cpp:308-312)"; return PPG_ERR_INVALID; }
-        HIP_CHECK(ctx->d_emTexels.reserve(tex.size())); HIP_CHECK(hipMemcpy(ctx->d_emTexels.p, tex.data(), tex.size() * sizeof(float4), hipMemcpyHostToDevice));
-        HIP_CHECK(ctx->d_emCdfRows.reserve(cdfRows.size())); HIP_CHECK(hipMemcpy(ctx->d_emCdfRows.p, cdfRows.data(), cdfRows.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(ctx->d_emCdfCols.reserve(cdfCols.size())); HIP_CHECK(hipMemcpy(ctx->d_emCdfCols.p, cdfCols.data(), cdfCols.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(ctx->d_emRowWeights.reserve(rowWeights.size())); HIP_CHECK(hipMemcpy(ctx->d_emRowWeights.p, rowWeights.data(), rowWeights.size() * 4, hipMemcpyHostToDevice));
-        DevScene &E = ctx->scene;
-        E.em_texels = ctx->d_emTexels.p; E.em_cdf_rows = ctx->d_emCdfRows.p; E.em_cdf_cols = ctx->d_emCdfCols.p; E.em_row_weights = ctx->d_emRowWeights.p;
-        E.em_w = w; E.em_h = h; E.em_scale = em.scale;
-        E.em_norm = 1.0f / (rowSum * (2 * PPG_PI_F / w) * (PPG_PI_F / h));
-        E.em_px = 2 * PPG_PI_F / w; E.em_py = PPG_PI_F / h;
-        memcpy(E.em_R, em.to_world, sizeof E.em_R);
-    }
-    {   // luminaire sampling tables: TriMesh::prepareSamplingTable (trimesh.cpp:388-403) per emitter (= the triangles
-        // carrying its id, in index order) and Scene::configure's emitter pmf (scene.cpp:375-380, samplingWeight = 1);
-        // float running sums and DiscreteDistribution::normalize() (pmf.h:101-114) exactly as the oracle builds them
-        const uint32_t ne = s->n_emitters;
-        std::vector<std::vector<uint32_t>> emTris(ne);
-        for (uint32_t t = 0; t < s->n_triangles; ++t) if (s->tri_emitter[t] >= 0) emTris[s->tri_emitter[t]].push_back(t);
-        std::vector<float> selCdf(1, 0.0f), areaCdf;
-        std::vector<int4> info(std::max<uint32_t>(1, ne));
-        std::vector<float4> etris, enrm;
-        auto normalize = [](std::vector<float> &cdf, size_t first, size_t entries, float &sum) {
-            sum = cdf[first + entries - 1];
-            if (sum > 0) {
-                float normalization = 1.0f / sum;
-                for (size_t i = 1; i < entries; ++i) cdf[first + i] *= normalization;
-                cdf[first + entries - 1] = 1.0f;
-                return normalization;
-            }
-            return 0.0f;
-        };
-        for (uint32_t e = 0; e < ne; ++e) {
-            const size_t first = areaCdf.size();
-            areaCdf.push_back(0.0f);
-            const int firstTri = (int)(etris.size() / 3);
-            for (uint32_t t : emTris[e]) {
-                const float *p0 = s->positions + 3 * s->indices[3 * t], *p1 = s->positions + 3 * s->indices[3 * t + 1], *p2 = s->positions + 3 * s->indices[3 * t + 2];
-                const float ax = p1[0] - p0[0], ay = p1[1] - p0[1], az = p1[2] - p0[2];
-                const float bx = p2[0] - p0[0], by = p2[1] - p0[1], bz = p2[2] - p0[2];
-                const float cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
-                areaCdf.push_back(areaCdf.back() + 0.5f * std::sqrt(cx * cx + cy * cy + cz * cz));  // Triangle::surfaceArea, triangle.cpp:61-67
-                for (int v = 0; v < 3; ++v) {
-                    const float *p = s->positions + 3 * s->indices[3 * t + v];
-                    etris.push_back(make_float4(p[0], p[1], p[2], 0));
-                    if (s->normals) { const float *n = s->normals + 3 * s->indices[3 * t + v]; enrm.push_back(make_float4(n[0], n[1], n[2], 0)); }
-                }
-            }
-            float area = 0, inv = -1;
-            if (!emTris[e].empty()) { normalize(areaCdf, first, emTris[e].size() + 1, area); inv = 1.0f / area; }
-            info[e] = make_int4(firstTri, (int)emTris[e].size(), (int)first, __builtin_bit_cast(int, inv));
-            if (emitterSphere[e] >= 0) info[e].y = -(emitterSphere[e] + 1);  // sampled analytically (sphere_sample_direct)
-            if (emitterShape[e] >= 0) {  // a disk or a cylinder: (-(shape + 1), 1, -, invSurfaceArea): sampled by shape_sample_direct; on the hit
-                                         // side the count of 1 sends it down the generic invSurfaceArea * dist^2 / |dn| density
-                const ppg_shape &sh = ctx->shapes[emitterShape[e]];
-                float invArea;
-                if (sh.type == PPG_SHAPE_DISK) {  // Disk::configure, disk.cpp:101-115
-                    const float *m = sh.to_world;
-                    const float len = std::sqrt(m[0] * m[0] + m[4] * m[4] + m[8] * m[8]);
-                    invArea = 1.0f / (PPG_PI_F * len * len);
-                } else invArea = 1 / (2 * PPG_PI_F * sh.radius * sh.length);  // cylinder.cpp:106
-                info[e] = make_int4(-(emitterShape[e] + 1), 1, (int)first, __builtin_bit_cast(int, invArea));
-            }
-            selCdf.push_back(selCdf.back() + 1.0f);
-        }
-        for (size_t k = 0; k < ctx->deltaEmitters.size(); ++k) selCdf.push_back(selCdf.back() + 1.0f);  // delta emitters follow the area emitters
-        if (s->environment || s->envmap) selCdf.push_back(selCdf.back() + 1.0f);  // the environment emitter is the last one
-        float selSum = 0, selNorm = 0;
-        if (selCdf.size() > 1) selNorm = normalize(selCdf, 0, selCdf.size(), selSum);
-        if (etris.empty()) etris.push_back(make_float4(0, 0, 0, 0));
-        if (areaCdf.empty()) areaCdf.push_back(0.0f);
-        HIP_CHECK(ctx->d_emSel.reserve(selCdf.size())); HIP_CHECK(hipMemcpy(ctx->d_emSel.p, selCdf.data(), selCdf.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(ctx->d_emArea.reserve(areaCdf.size())); HIP_CHECK(hipMemcpy(ctx->d_emArea.p, areaCdf.data(), areaCdf.size() * 4, hipMemcpyHostToDevice));
-        HIP_CHECK(ctx->d_emInfo.reserve(info.size())); HIP_CHECK(hipMemcpy(ctx->d_emInfo.p, info.data(), info.size() * sizeof(int4), hipMemcpyHostToDevice));
-        HIP_CHECK(ctx->d_emTris.reserve(etris.size())); HIP_CHECK(hipMemcpy(ctx->d_emTris.p, etris.data(), etris.size() * sizeof(float4), hipMemcpyHostToDevice));
-        if (!enrm.empty()) { HIP_CHECK(ctx->d_emNrm.reserve(enrm.size())); HIP_CHECK(hipMemcpy(ctx->d_emNrm.p, enrm.data(), enrm.size() * sizeof(float4), hipMemcpyHostToDevice)); }
-        DevScene &S = ctx->scene;
-        if (s->environment || s->envmap) {
-            if (s->environment) S.env = make_float4(s->environment[0], s->environment[1], s->environment[2], 1.0f);
-            else S.env = make_float4(0, 0, 0, 2.0f);  // image based: DevScene::em_*
-            envBSphere(ctx);
-            ctx->fullMaterials = true;  // the environment code lives in the FULL kernel variants
-        } else {
-            S.env = make_float4(0, 0, 0, 0); S.bsphere = make_float4(0, 0, 0, 0);
-        }
-        S.n_emitters = (int)ne; S.em_sel_cdf = ctx->d_emSel.p; S.em_sel_norm = selNorm; S.em_info = ctx->d_emInfo.p;
-        S.em_area_cdf = ctx->d_emArea.p; S.em_tris = ctx->d_emTris.p; S.em_normals = enrm.empty() ? nullptr : ctx->d_emNrm.p;
-    }
-    DevScene &S = ctx->scene;
-    S.tris = ctx->d_tris.p; S.accel = ctx->d_accel.p; S.normals = s->normals ? ctx->d_normals.p : nullptr; S.bvh = ctx->d_bvh.p; S.bvh4 = ctx->d_bvh4.p; S.bvh_top = ctx->d_bvhTop.p; S.n_top = nTop;
-    S.materials = ctx->d_materials.p; S.emitters = ctx->d_emitters.p; S.n_tris = (int)s->n_triangles; S.has_null = hasNull ? 1 : 0;
-    S.rtrans = s->n_rtrans ? ctx->d_rtrans.p : nullptr; S.rtrans_n = (int)s->rtrans_samples;
-    S.spheres = nullptr; S.n_spheres = (int)s->n_spheres;
-    S.delta = nullptr; S.n_delta = (int)ctx->deltaEmitters.size(); S.dir_sphere = make_float4(0, 0, 0, 0);
-    if (S.n_delta) {
-        std::vector<float4> tab(PPG_DELTA_STRIDE * ctx->deltaEmitters.size());
-        for (size_t k = 0; k < ctx->deltaEmitters.size(); ++k) {
-            const ppg_delta_emitter &e = ctx->deltaEmitters[k];
-            const float *v = e.type == PPG_EMITTER_DIRECTIONAL ? e.direction : e.position;
-            float4 *Q = &tab[PPG_DELTA_STRIDE * k];
-            Q[0] = make_float4(e.intensity[0], e.intensity[1], e.intensity[2], __builtin_bit_cast(float, (int)e.type));
-            Q[1] = make_float4(v[0], v[1], v[2], e.cutoff_angle);
-            Q[2] = Q[3] = make_float4(0, 0, 0, 0);
-            if (e.type == PPG_EMITTER_SPOT) {  // SpotEmitter::configure (spot.cpp:89-94)
-                Q[2] = make_float4(e.to_local[6], e.to_local[7], e.to_local[8], 1.0f / (e.cutoff_angle - e.beam_width));
-                Q[3] = make_float4(std::cos(e.cutoff_angle), std::cos(e.beam_width), 0, 0);
-            }
-        }
-        HIP_CHECK(ctx->d_delta.reserve(tab.size()));
-        HIP_CHECK(hipMemcpy(ctx->d_delta.p, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice));
-        S.delta = ctx->d_delta.p;
-        {   // DirectionalEmitter::createShape (directional.cpp:88-94): AABB::getBSphere (aabb.h) of the kd-tree's box, radius * 1.1
-            float c[3];
-            for (int a = 0; a < 3; ++a) c[a] = (ctx->geomMax[a] + ctx->geomMin[a]) * 0.5f;
-            const float dx = c[0] - ctx->geomMax[0], dy = c[1] - ctx->geomMax[1], dz = c[2] - ctx->geomMax[2];
-            S.dir_sphere = make_float4(c[0], c[1], c[2], std::sqrt(dx * dx + dy * dy + dz * dz) * 1.1f);
-        }
-        ctx->fullMaterials = true;  // the delta-emitter code lives in the FULL kernel variants
-    }
-    S.shapes = nullptr; S.n_shapes = (int)ctx->shapes.size();
-    if (S.n_shapes) {
-        std::vector<float4> tab(PPG_SHAPE_STRIDE * ctx->shapes.size());
-        for (size_t k = 0; k < ctx->shapes.size(); ++k) {
-            const ppg_shape &sh = ctx->shapes[k];
-            float4 *Q = &tab[PPG_SHAPE_STRIDE * k];
-            const float *m = sh.to_world, *iv = &shapeInv[12 * k];
-            for (int r = 0; r < 3; ++r) {
-                Q[r] = make_float4(m[4 * r], m[4 * r + 1], m[4 * r + 2], m[4 * r + 3]);
-                Q[3 + r] = make_float4(iv[4 * r], iv[4 * r + 1], iv[4 * r + 2], iv[4 * r + 3]);
-            }
-            Q[6] = make_float4(sh.type == PPG_SHAPE_CYLINDER ? sh.radius : 1.0f, sh.type == PPG_SHAPE_CYLINDER ? sh.length : 0.0f, 0.0f, __builtin_bit_cast(float, (int)sh.type));
-            Q[7] = make_float4(__builtin_bit_cast(float, (int)sh.material), __builtin_bit_cast(float, sh.emitter), __builtin_bit_cast(float, sh.flip_normals ? 1 : 0), 0.0f);
-        }
-        HIP_CHECK(ctx->d_shapes.reserve(tab.size()));
-        HIP_CHECK(hipMemcpy(ctx->d_shapes.p, tab.data(), tab.size() * sizeof(float4), hipMemcpyHostToDevice));
-        S.shapes = ctx->d_shapes.p;
-        ctx->fullMaterials = true;  // the shape code lives in the FULL kernel variants, on the BVH path
-    }
-    if (s->n_spheres) {
-        std::vector<float4> sph(4 * (size_t)s->n_spheres);
-        for (uint32_t k = 0; k < s->n_spheres; ++k) {
-            const ppg_sphere &sp = s->spheres[k];
-            sph[4 * k + 0] = make_float4(sp.center[0], sp.center[1], sp.center[2], sp.radius);
-            sph[4 * k + 1] = make_float4(sp.to_world[0], sp.to_world[1], sp.to_world[2], __builtin_bit_cast(float, (int)sp.material));
-            sph[4 * k + 2] = make_float4(sp.to_world[3], sp.to_world[4], sp.to_world[5], __builtin_bit_cast(float, sp.emitter));
-            sph[4 * k + 3] = make_float4(sp.to_world[6], sp.to_world[7], sp.to_world[8], __builtin_bit_cast(float, sp.flip_normals ? 1 : 0));
-        }
-        HIP_CHECK(ctx->d_spheres.reserve(sph.size()));
-        HIP_CHECK(hipMemcpy(ctx->d_spheres.p, sph.data(), sph.size() * sizeof(float4), hipMemcpyHostToDevice));
-        S.spheres = ctx->d_spheres.p;
-        ctx->fullMaterials = true;  // the sphere code lives in the FULL kernel variants, on the BVH path
-    }
-    memcpy(S.cam.s2c, s->camera.sample_to_camera, 64); memcpy(S.cam.c2w, s->camera.camera_to_world, 64);
-    S.cam.near_clip = s->camera.near_clip; S.cam.far_clip = s->camera.far_clip;
-    S.cam.width = s->camera.width; S.cam.height = s->camera.height;
-    S.cam.inv_w = 1.0f / (float)s->camera.width; S.cam.inv_h = 1.0f / (float)s->camera.height;
-    S.cam.lens = ctx->lensOn ? 1 : 0; S.cam.aperture = ctx->lens.aperture_radius; S.cam.focus = ctx->lens.focus_distance;
-    ctx->W = s->camera.width; ctx->H = s->camera.height;
-    {   // LDS budget of k_trace: 32 KB keeps 5 workgroups per CU resident
-        const size_t budget = 32 * 1024;
-        ctx->ldsNodes = (int)std::min<size_t>(bb.nodes.size(), budget / 64);
-        size_t left = budget - (size_t)ctx->ldsNodes * 64;
-        ctx->ldsTris = ((size_t)s->n_triangles * 48 <= left) ? (int)s->n_triangles : 0;
-    }
-    // Every array the path kernels walk must be there before a launch can chase it: an unset pointer here is a hung GPU, not a wrong pixel
-    // (round 5 lost 40 GPU minutes to five assignments that an edit had turned into a comment).
-    if (!S.materials || !S.bvh4 || (S.n_tris > 0 && (!S.tris || !S.accel || !S.bvh)) || (S.n_spheres > 0 && !S.spheres) || (S.n_delta > 0 && !S.delta) ||
-        (S.n_shapes > 0 && !S.shapes)) {
-        ctx->error = "internal: device scene incomplete";
-        return PPG_ERR_STATE;
-    }
+    HostScene H;
+    if (int rc = buildScene(in, H, ctx->error)) return rc;  // refused: nothing of the context has been touched, the previous scene stays set
+    // From here on the buffers the previous scene points into are re-used: no scene is set until the new one is complete
+    ctx->haveScene = false; ctx->treeAlive = false; ctx->renderOpen = false; ctx->pathsReady = false;
+    DevScene S;
+    if (int rc = uploadScene(ctx, H, S)) return rc;
+    ctx->scene = S;
+    for (int a = 0; a < 3; ++a) { ctx->geomMin[a] = H.geomMin[a]; ctx->geomMax[a] = H.geomMax[a]; ctx->aabbMin[a] = H.aabbMin[a]; ctx->aabbMax[a] = H.aabbMax[a]; }
+    ctx->sceneDelta = std::move(H.deltaEmitters);
+    ctx->fullMaterials = H.fullMaterials; ctx->nMaterials = H.nMaterials;
+    ctx->ldsNodes = H.ldsNodes; ctx->ldsTris = H.ldsTris;
+    ctx->W = H.W; ctx->H = H.H;
     ctx->haveScene = true;
-    ctx->treeAlive = false;
-    ctx->renderOpen = false;
-    ctx->pathsReady = false;
-    {   // scene preprocessing also sizes the per-pass buffers (path state, vertex slots, queues, film)
-        int rc = allocPaths(ctx);
-        if (rc) return rc;
-        if ((rc = allocFilm(ctx))) return rc;
-        if ((rc = presizeRounds(ctx))) return rc;
-        ctx->pathsReady = true;
-    }
-    return PPG_OK;
+    return sizeBuffers(ctx);
 }
 
 int ppg_set_shard(ppg_ctx *ctx, int32_t rank, int32_t world, int32_t tile_size) {
@@ -3760,15 +2477,7 @@ int ppg_set_shard(ppg_ctx *ctx, int32_t rank, int32_t world, int32_t tile_size) 
     if (world < 1 || rank < 0 || rank >= world || tile_size < 1) { ctx->error = "bad shard"; return PPG_ERR_INVALID; }
     if (world > 1 && ctx->filtered && !ctx->footHook) { ctx->error = kShardedFilter; return PPG_ERR_INVALID; }
     ctx->shardRank = rank; ctx->shardWorld = world; ctx->tileSize = tile_size;
-    ctx->pathsReady = false;
-    if (ctx->haveScene) {
-        int rc = allocPaths(ctx);
-        if (rc) return rc;
-        if ((rc = allocFilm(ctx))) return rc;
-        if ((rc = presizeRounds(ctx))) return rc;
-        ctx->pathsReady = true;
-    }
-    return PPG_OK;
+    return sizeBuffers(ctx);
 }
 
 // every entry point re-selects the context's device: the caller (torch / RCCL in a multi-GPU process) may have changed it
@@ -4042,40 +2751,18 @@ int ppg_set_lens(ppg_ctx *ctx, const ppg_lens *lens) {
     ctx->lens = lens ? *lens : ppg_lens{};
     DevScene &S = ctx->scene;
     S.cam.lens = ctx->lensOn ? 1 : 0; S.cam.aperture = ctx->lens.aperture_radius; S.cam.focus = ctx->lens.focus_distance;
-    if (ctx->haveScene) {  // the scene's box and what depends on it, with the new sensor box
-        sceneBox(ctx, S.cam.c2w);
-        if (S.env.w != 0) envBSphere(ctx);
+    if (ctx->haveScene) {  // the scene's box and what depends on it, with the new sensor box (and the delta emitters the scene was built with)
+        const SceneBox box = sceneBox(ctx->geomMin, ctx->geomMax, ctx->lensOn ? &ctx->lens : nullptr, S.cam.c2w, ctx->sceneDelta);
+        for (int a = 0; a < 3; ++a) { ctx->aabbMin[a] = box.mn[a]; ctx->aabbMax[a] = box.mx[a]; }
+        if (S.env.w != 0) S.bsphere = envBSphere(ctx->aabbMin, ctx->aabbMax);
     }
     return PPG_OK;
 }
 
-int ppg_set_material_textures(ppg_ctx *ctx, const ppg_material_textures *slots, uint32_t n_materials) {
-    if (ctx->renderOpen) { ctx->error = "material textures: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
-    if (n_materials && !slots) { ctx->error = "material textures: no list"; return PPG_ERR_INVALID; }
-    ctx->materialTextures.assign(slots, slots + n_materials);  // validated against the scene by ppg_set_scene
-    return PPG_OK;
-}
-
-int ppg_set_microfacet(ppg_ctx *ctx, const ppg_microfacet *m, uint32_t n_materials) {
-    if (ctx->renderOpen) { ctx->error = "microfacet: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
-    if (!m) n_materials = 0;
-    ctx->microfacet.assign(m, m + n_materials);  // validated against the scene by ppg_set_scene
-    return PPG_OK;
-}
-
-int ppg_set_coatings(ppg_ctx *ctx, const ppg_coating *c, uint32_t n_materials) {
-    if (ctx->renderOpen) { ctx->error = "coatings: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
-    if (!c) n_materials = 0;
-    ctx->coatings.assign(c, c + n_materials);  // validated against the scene by ppg_set_scene
-    return PPG_OK;
-}
-
-int ppg_set_blends(ppg_ctx *ctx, const ppg_blend *b, uint32_t n_materials) {
-    if (ctx->renderOpen) { ctx->error = "blends: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
-    if (!b) n_materials = 0;
-    ctx->blends.assign(b, b + n_materials);  // validated against the scene by ppg_set_scene
-    return PPG_OK;
-}
+int ppg_set_material_textures(ppg_ctx *ctx, const ppg_material_textures *slots, uint32_t n) { return setSideList(ctx, "material textures", ctx->materialTextures, slots, n, false); }
+int ppg_set_microfacet(ppg_ctx *ctx, const ppg_microfacet *m, uint32_t n) { return setSideList(ctx, "microfacet", ctx->microfacet, m, n, true); }
+int ppg_set_coatings(ppg_ctx *ctx, const ppg_coating *c, uint32_t n) { return setSideList(ctx, "coatings", ctx->coatings, c, n, true); }
+int ppg_set_blends(ppg_ctx *ctx, const ppg_blend *b, uint32_t n) { return setSideList(ctx, "blends", ctx->blends, b, n, true); }
 
 int ppg_set_delta_emitters(ppg_ctx *ctx, const ppg_delta_emitter *em, uint32_t n) {
     if (ctx->renderOpen) { ctx->error = "delta emitters: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
