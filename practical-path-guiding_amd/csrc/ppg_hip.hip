@@ -32,9 +32,14 @@
 
 #include "../../include/ppg.h"
 #include "../../include/ppg_testhooks.h"
+#include "ppg_batch_plan.h"
 #include "ppg_host_kernels.h"
 #include "ppg_launch.h"
 #include "ppg_scene_build.h"
+
+using namespace ppg_plan;
+static_assert(kSpatialFilterBox == SF_BOX && kNeeKickstart == NEE_KICKSTART && kBlock == PPG_BLOCK && kDenseChunk == PPG_DCHUNK && kAdamLeafShift == PPG_ADAM_LEAF_SHIFT,
+              "ppg_batch_plan.h restates these values");
 
 namespace {
 
@@ -450,10 +455,8 @@ struct ppg_ctx {
     DevBuf<unsigned long long> d_ownerBounds;     // [world + 1] first record of every owner
     // unbounded paths: live paths after each bulk bounce of the last batch → how many bulk bounces the next batch runs before k_tail
     DevBuf<unsigned int> d_bounceCounts, d_ticket;
-    unsigned int *h_round = nullptr;  // pinned: [0..63] bounce counts, [64] Adam record count / overflow, [65] Σ nV, [68..69] paths handed to k_tail, [70..71] stragglers
-    // the previous batch's survival curve (live paths after each wavefront bounce it ran) sizes the schedule of the next batch
-    int prevBounces = 0;
-    unsigned int prevPaths = 0, prevLive[64] = {};
+    RoundReadback *h_round = nullptr;  // pinned (ppg_batch_plan.h)
+    SurvivalCurve survival;           // of the previous batch: sizes the schedule of the next one (planBounces)
     int bounceMargin = 3;             // PPG_BOUNCE_MARGIN: bounces launched beyond the predicted need (the device skips what it does not need)
     // Tuning switches, read ONCE from the environment by ppg_create (DESIGN.md "Tuning switches"); none of them changes a result.
     unsigned int tailThreshold = 0;   // PPG_TAIL_THRESHOLD: live paths below which k_tail takes over (0 = automatic: max(tailMin, paths / tailDiv))
@@ -572,6 +575,8 @@ template <typename F> void timedLaunch(ppg_ctx *ctx, const char *name, uint64_t 
     (void)hipEventRecord(r.b, ctx->stream);
     ctx->timer.pending.push_back(r);
 }
+
+bool sideStreamsAllowed(const ppg_ctx *ctx) { return ppg_plan::sideStreamsAllowed(ctx->timer.enabled, ctx->tuneNoOverlap); }
 
 int gridFor(size_t n, int block = PPG_BLOCK, int maxBlocks = 256 * 8) {
     size_t b = (n + block - 1) / block;
@@ -835,7 +840,7 @@ int allocPaths(ppg_ctx *ctx) {
     HIP_CHECK(ctx->d_offsets.reserve(nb)); HIP_CHECK(ctx->d_total.reserve(2));
     HIP_CHECK(ctx->d_bounceCounts.reserve(72)); HIP_CHECK(ctx->d_ticket.reserve(1));
     HIP_CHECK(ctx->d_adamCount.reserve(2));
-    if (!ctx->h_round) HIP_CHECK(hipHostMalloc((void **)&ctx->h_round, 72 * sizeof(unsigned int), hipHostMallocDefault));
+    if (!ctx->h_round) HIP_CHECK(hipHostMalloc((void **)&ctx->h_round, sizeof(RoundReadback), hipHostMallocDefault));
     ctx->queues.items[0] = ctx->d_queue[0].p; ctx->queues.items[1] = ctx->d_queue[1].p;
     ctx->queues.count[0] = ctx->d_qcount[0].p; ctx->queues.count[1] = ctx->d_qcount[1].p;
     ctx->queues.cap = (unsigned int)cap; ctx->queues.stats = ctx->d_stats.p; ctx->queues.n_blocks = (unsigned int)nb;
@@ -875,7 +880,7 @@ int allocPaths(ppg_ctx *ctx) {
 // still grows what turns out too small.
 int presizeRounds(ppg_ctx *ctx) {
     g_blockCache.prewarm();
-    if (ctx->loss == LOSS_NONE || ctx->budgetType != 0 || ctx->spatialFilter == SF_BOX) return PPG_OK;
+    if (ctx->loss == LOSS_NONE || ctx->budgetType != 0 || !recordPositionsKnown(ctx->spatialFilter, false, ctx->nee)) return PPG_OK;  // (no iteration has sampled luminaires yet)
     const int nPasses = (int)std::ceil((size_t)ctx->budget / (float)ctx->sppPerPass);
     int rendered = 0, largest = 0;
     for (int it = 0; rendered < nPasses; ++it) {  // renderSPP, GP:1342-1426
@@ -938,7 +943,7 @@ int applyAdamRound(ppg_ctx *ctx, size_t nRecords) {
         ~Join() { now(); }
     } join{ctx};
     // (without a round hook the optimiser's kernels leave the context's stream too: ppg_ctx::treePending)
-    const bool aside = ctx->sortedCommit && !ctx->passHook && !ctx->timer.enabled && !ctx->tuneNoOverlap && !ctx->tuneNoAside;
+    const bool aside = ctx->sortedCommit && !ctx->passHook && sideStreamsAllowed(ctx) && !ctx->tuneNoAside;
     hipStream_t sa = aside ? ctx->stream3 : s;  // where the order / apply kernels go
     struct AsideGuard {  // an early return with kernels already on stream3: the event joinTree() waits for must lie behind them
         ppg_ctx *c; bool on;
@@ -965,7 +970,7 @@ int applyAdamRound(ppg_ctx *ctx, size_t nRecords) {
         } else if (ctx->sortedCommit) {  // DTree::recordIrradiance of every record of the round, D-tree by D-tree (ppg_kernels.h "The commit of a ROUND")
             const unsigned int chunks = (unsigned int)((n + PPG_SPLAT_CHUNK - 1) / PPG_SPLAT_CHUNK);
             SplatLaunch a{(int)std::max(1u, std::min(chunks, 256u * 8u)), s, ctx->devTree(), ctx->d_adamKeys[1].p, ctx->d_adamIdx[1].p, ctx->d_splat.p, (unsigned int)n, leafBits, ctx->tuneSplatLdsNodes};
-            if (!ctx->timer.enabled && !ctx->tuneNoOverlap) {
+            if (sideStreamsAllowed(ctx)) {
                 HIP_CHECK(hipEventRecord(ctx->evFork, s));
                 HIP_CHECK(hipStreamWaitEvent(ctx->stream2, ctx->evFork, 0));
                 a.stream = ctx->stream2;
@@ -1075,14 +1080,53 @@ int stragglerState(ppg_ctx *ctx, ppg_ctx::Stragglers &G, const PathState &batch,
     return PPG_OK;
 }
 
-// After the first k_tail of a batch: nStrag paths wait in the current set.  Take their vertex slots and the batch's radiance, start their own
+// A batch on its way through renderBatch: what it works on, what planBatch decided about it, what has been counted so far.
+struct Batch {
+    PathState P, Pc;                // Pc: P with the contiguous copy of the path words, once copyMisc has made it
+    DevScene S;
+    DevTree T;
+    RenderParams R;
+    Queues Q;
+    BatchPlan plan;
+    int grid = 0, gridAll = 0;      // workgroups of the wavefront kernels / of a kernel over every path
+    bool smallScene = false;
+    size_t ldsBytes = 0;            // k_tail's dynamic LDS
+    unsigned int *dense = nullptr;  // the live paths in one list (k_tail's work list)
+    unsigned int hostCount = 0;     // live paths as far as the host knows (kernel timing wants the units of every launch)
+    int bouncesRun = 0;
+    bool miscCopied = false;
+    size_t nRecordsOwn = 0, nRecords = 0;  // record positions of the round's own paths / with those of the previous round's stragglers
+    unsigned int nStrag = 0;        // paths alive at the hand-over depth of a split tail
+};
+
+// variant of ppg_launch_tail
+int tailVariant(const ppg_ctx *ctx) { return (isSmallScene(ctx) ? 4 : 0) | (ctx->doNee ? 2 : 0) | (ctx->fullMaterials ? 1 : 0); }
+
+// The commit of a launch's vertices: in a round that commits through records (`records`) k_commit_records, else k_commit.
+const char *commitName(bool records) { return records ? "k_commit_records" : "k_commit"; }
+void launchCommitKernels(ppg_ctx *ctx, const CommitLaunch &a, bool records) {
+    if (records) ppg_launch_commit_records(ctx->spatialFilter, a);
+    else ppg_launch_commit(ctx->spatialFilter, ctx->directionalFilter, a);
+}
+
+// The record arrays of a round with n positions, every key a hole.  (The caller's DevTree is stale afterwards.)
+int reserveRoundRecords(ppg_ctx *ctx, size_t n) {
+    HIP_CHECK(ctx->d_adamKeys[0].reserve(std::max<size_t>(1, n))); HIP_CHECK(ctx->d_adamRecs.reserve(std::max<size_t>(1, n)));
+    if (ctx->sortedCommit) HIP_CHECK(ctx->d_splat.reserve(std::max<size_t>(1, n)));
+    if (n) HIP_CHECK(hipMemsetAsync(ctx->d_adamKeys[0].p, 0xff, n * 8, ctx->stream));
+    return PPG_OK;
+}
+
+// After the first k_tail of a batch: B.nStrag paths wait in the current set.  Take their vertex slots and the batch's radiance, start their own
 // k_tail (on stream4 when side streams are allowed), and leave the set pending.
-int launchStragglers(ppg_ctx *ctx, const PathState &P, const DevScene &S, const DevTree &T, const RenderParams &R, unsigned int nStrag, bool commit, bool adam,
-                     bool beside, int tailVariant, size_t ldsBytes) {
+int launchStragglers(ppg_ctx *ctx, const Batch &B) {
     hipStream_t s = ctx->stream;
+    const PathState &P = B.P;
+    const unsigned int nStrag = B.nStrag;
+    const bool commit = B.plan.commit, beside = B.plan.beside;
     ppg_ctx::Stragglers &G = ctx->strag[ctx->stragCur];
     { int rc = stragglerState(ctx, G, P, nStrag, commit); if (rc) return rc; }
-    G.n = nStrag; G.commit = commit; G.adam = adam && commit;
+    G.n = nStrag; G.commit = commit; G.adam = B.plan.deferRecords && commit;
     const int small = gridFor(nStrag, 64, 1024);
     if (commit) hipLaunchKernelGGL(k_extract_vertices, dim3(small), dim3(256), 0, s, P, G.P, nStrag, (unsigned int)ctx->maxVertices);
     else if (P.nee_cos) hipLaunchKernelGGL(k_extract_nee_cos, dim3(small), dim3(256), 0, s, P, G.P, nStrag);  // (nothing recorded: a final iteration)
@@ -1095,11 +1139,8 @@ int launchStragglers(ppg_ctx *ctx, const PathState &P, const DevScene &S, const 
         G.iotaN = m;
     }
     HIP_CHECK(hipMemsetAsync(G.ticket.p, 0, 4, s));
-    // thinly: as many waves as there are stragglers while the GPU has room for them (a lone path's bounce is 12 us, 64 in one wave 120)
-    const unsigned int waves = 1024u * (PPG_BLOCK / 64u);
-    const unsigned int laneLimit = std::max(1u, std::min(64u, (nStrag + waves - 1u) / waves));
-    const int tailGrid = (int)std::max(1u, std::min(1024u, (nStrag + laneLimit * (PPG_BLOCK / 64u) - 1u) / (laneLimit * (PPG_BLOCK / 64u))));
-    DevTree Tt = T;
+    const TailShape shape = stragglerShape(nStrag);
+    DevTree Tt = B.T;
     if (ctx->loss != LOSS_NONE && ctx->isBuilt) {  // the fractions of THIS round, whatever the optimiser does to the headers meanwhile
         const unsigned int nn = (unsigned int)ctx->snodes.size();
         HIP_CHECK(G.theta.reserve(nn));
@@ -1113,11 +1154,11 @@ int launchStragglers(ppg_ctx *ctx, const PathState &P, const DevScene &S, const 
         st = ctx->stream4;
     }
     auto launch = [&] {
-        RenderParams Rt = R;
+        RenderParams Rt = B.R;
         Rt.defer_depth = 0u;
-        TailLaunch a{tailGrid, ldsBytes, st, G.P, S, Tt, Rt, G.iota.p, G.count.p, G.ticket.p, ctx->queues.stats, ctx->ldsTris,
-                     ctx->d_tailLongest.p + (ctx->tailLaunches++ % PPG_TAIL_LOG), StragOut{nullptr, nullptr, nullptr}, laneLimit};
-        ppg_launch_tail(tailVariant, a);
+        TailLaunch a{shape.grid, B.ldsBytes, st, G.P, B.S, Tt, Rt, G.iota.p, G.count.p, G.ticket.p, ctx->queues.stats, ctx->ldsTris,
+                     ctx->d_tailLongest.p + (ctx->tailLaunches++ % PPG_TAIL_LOG), StragOut{nullptr, nullptr, nullptr}, shape.laneLimit};
+        ppg_launch_tail(tailVariant(ctx), a);
     };
     if (beside) { launch(); HIP_CHECK(hipEventRecord(ctx->evStragDone, ctx->stream4)); }
     else timedLaunch(ctx, "k_tail(stragglers)", nStrag, launch);  // (its own timer entry: in the product it runs beside the next batch, not on the critical path)
@@ -1156,10 +1197,8 @@ int drainStragglers(ppg_ctx *ctx, size_t recordsFirst) {
             T.adam_base = G.base.p;
         }
         CommitLaunch a{gridFor(G.n, 64, ctx->nBlocks), s, G.P, T, R, ctx->queues, G.nv8.p, nullptr, nullptr, ctx->d_splat.p, ctx->adamFlagShift};
-        timedLaunch(ctx, (G.adam && ctx->sortedCommit) ? "k_commit_records" : "k_commit", 0, [&] {
-            if (G.adam && ctx->sortedCommit) ppg_launch_commit_records(ctx->spatialFilter, a);
-            else ppg_launch_commit(ctx->spatialFilter, ctx->directionalFilter, a);
-        });
+        const bool records = G.adam && ctx->sortedCommit;
+        timedLaunch(ctx, commitName(records), 0, [&] { launchCommitKernels(ctx, a, records); });
     }
     HIP_CHECK(hipGetLastError());
     return PPG_OK;
@@ -1172,20 +1211,17 @@ int flushStragglers(ppg_ctx *ctx, bool hookRound) {
     ppg_ctx::Stragglers &G = ctx->stragPrev();
     const bool records = G.pending && G.adam;
     if (!G.pending && !hookRound) return PPG_OK;
-    hipStream_t s = ctx->stream;
     ctx->joinTree();  // (the last round's splats and optimiser steps read the record arrays this round is about to overwrite)
     size_t n = 0;
     if (records || hookRound) {
         ctx->adamActive = true; ctx->adamFast = true;
-        unsigned int leafBits = 1;
-        while ((1u << leafBits) <= (unsigned int)ctx->snodes.size()) ++leafBits;
-        ctx->adamFlagShift = PPG_ADAM_LEAF_SHIFT + leafBits;
+        ctx->adamFlagShift = adamFlagShift(ctx->snodes.size());
         // (a few thousand vertices spread over all D-trees: k_commit's global atomics — k_splat_sorted would stage a D-tree in LDS for every
         // record or two, 5 ms for the 50 000 record positions of KITCHEN's 2-pass rounds; integer sums, the same bits)
         ctx->sortedCommit = false;
         n = records ? (size_t)G.n * (size_t)ctx->maxVertices : 0;
-        HIP_CHECK(ctx->d_adamKeys[0].reserve(std::max<size_t>(1, n))); HIP_CHECK(ctx->d_adamRecs.reserve(std::max<size_t>(1, n)));
-        if (n) HIP_CHECK(hipMemsetAsync(ctx->d_adamKeys[0].p, 0xff, n * 8, s));
+        int rc = reserveRoundRecords(ctx, n);
+        if (rc) return rc;
     }
     int rc = drainStragglers(ctx, 0);
     if (!rc && (records || hookRound)) rc = applyAdamRound(ctx, n);
@@ -1331,31 +1367,32 @@ int exchangeFootprint(ppg_ctx *ctx, float *im, float *sq, float *w, float *film,
     return PPG_OK;
 }
 
-// `batch` BlockedRenderProcesses (GP:1087-1106 / renderBlock GP:1587-1641) over all owned pixels in one set of launches.
-// adamRound: this batch is one round of the sampling-fraction optimiser.
-// A launch of whole groups of a final iteration's passes (include/ppg.h "Final iteration: groups of passes"): `batch` passes = groups of
-// groupPasses passes (the last one may be shorter; or a part of ONE group when groupPasses >= batch), the first starting at pass
-// firstPass of the render, consecutive groups of the launch stridePasses apart; group k accumulates into slot slot0 + k * slotStride.
-int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl = nullptr, bool last = true, const unsigned int *regionPixels = nullptr,
-                unsigned int regionCount = 0) {
-    PathState P = ctx->paths;
-    if (regionPixels) { P.n_pix = regionCount; P.pixels = regionPixels; }  // a round over ONE group of blocks (include/ppg.h "Rounds by image region")
-    if (gl && gl->wholeFilm && ctx->shardWorld > 1) { P.n_pix = ctx->nPixAll; P.pixels = ctx->d_pixelsAll.p; }  // the whole film, not this rank's tiles
-    P.n_paths = (unsigned int)((size_t)P.n_pix * ctx->sppPerPass * (size_t)batch);
-    if (P.n_paths == 0 && !(adamRound && ctx->passHook)) return PPG_OK;
+// ---- The stages of renderBatch, in the order they run.  What each may do was decided by planBatch (ppg_batch_plan.h): B.plan. ----
+
+// 1. B.P is the batch's pixels and paths.  The plan, the context's round state, the slow round's buffers, the launch arguments.
+int prepareBatch(ppg_ctx *ctx, Batch &B, int batch, bool adamRound, const GroupLaunch *gl, bool last) {
+    const PathState &P = B.P;
     hipStream_t s = ctx->stream;
-    // Adam records: positions are known in advance unless one vertex can make several records (box spatial filter) or records are made
-    // while the paths are still being traced (the direct-light vertex of nee = kickstart)
-    ctx->adamActive = adamRound;
-    ctx->adamFast = adamRound && ctx->spatialFilter != SF_BOX && !(ctx->doNee && ctx->nee == NEE_KICKSTART);
-    if (adamRound && !ctx->adamFast) {
+    const ppg_ctx::Stragglers &prev = ctx->stragPrev();
+    BatchFacts f;
+    f.paths = P.n_paths; f.maxDepth = ctx->maxDepth; f.isFinalIter = ctx->isFinalIter; f.adamRound = adamRound; f.last = last;
+    f.spatialFilter = ctx->spatialFilter; f.nee = ctx->nee; f.doNee = ctx->doNee;
+    f.timerOn = ctx->timer.enabled; f.tuneNoOverlap = ctx->tuneNoOverlap; f.tuneNoSortedCommit = ctx->tuneNoSortedCommit; f.tuneSplitDepth = ctx->tuneSplitDepth;
+    f.tailThreshold = ctx->tailThreshold; f.tailMin = ctx->tailMin; f.tailDiv = ctx->tailDiv;
+    f.deferDepthAdam = ctx->deferDepthAdam; f.streeNodes = ctx->snodes.size();
+    f.prevPendingWithRecords = prev.pending && prev.adam; f.prevStragglers = prev.n; f.maxVertices = ctx->maxVertices;
+    B.plan = planBatch(f);
+    // (the round state that devTree(), applyAdamRound and drainStragglers read)
+    ctx->adamActive = adamRound; ctx->adamFast = B.plan.adamFast; ctx->sortedCommit = B.plan.sortedCommit; ctx->adamFlagShift = B.plan.adamFlagShift;
+    if (adamRound && !B.plan.adamFast) {  // record positions are handed out as the records are made: room for 48 per path, the device counts
         const size_t cap = std::max<size_t>((size_t)1 << 16, std::min<size_t>((size_t)48 * P.n_paths, 0xfffffff0u));
         HIP_CHECK(ctx->d_adamKeys[0].reserve(cap)); HIP_CHECK(ctx->d_adamRecs.reserve(cap));
         HIP_CHECK(hipMemsetAsync(ctx->d_adamCount.p, 0, 8, s));
     }
-    DevScene S = ctx->scene;
-    DevTree T = ctx->devTree();
-    RenderParams R = ctx->params();
+    B.S = ctx->scene;
+    B.T = ctx->devTree();
+    RenderParams &R = B.R;
+    R = ctx->params();
     R.spp = ctx->sppPerPass * batch;  // sample j of the batch has sample index pass_index * sppPerPass + j, j < spp * batch
     R.pass_index_spp = (unsigned int)ctx->passesRendered * (unsigned int)ctx->sppPerPass;
     if (gl) {
@@ -1363,352 +1400,324 @@ int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl =
         R.group_samples = gl->groupPasses * (unsigned int)ctx->sppPerPass;
         R.group_stride = gl->stridePasses * (unsigned int)ctx->sppPerPass;
     }
-    Queues Q = ctx->queues;
-    // Workgroups of this batch's wavefront kernels.  A batch of a few million paths runs faster on fewer, larger queue slices (ray replacement
-    // and the slice sort have more to work with, fewer half-empty workgroups per launch: +1 % on the driver's command with 2048), the 59 M-path
-    // launches of a long render on more (4096: +1.6 % at 1023 passes) — so the grid follows the batch.  Slices are sized for the largest batch on
-    // nBlocks workgroups: a smaller grid is taken only if this batch's slices still fit.
-    int grid = ctx->nBlocks;
-    if (ctx->tuneBlocksSmall > 0 && ctx->tuneBlocksSmall < ctx->nBlocks && (size_t)P.n_paths <= ctx->tuneSmallPaths) {
-        const size_t chunks = ((size_t)P.n_paths + PPG_DCHUNK - 1) / PPG_DCHUNK;
-        if (((chunks + (size_t)ctx->tuneBlocksSmall - 1) / (size_t)ctx->tuneBlocksSmall) * PPG_DCHUNK <= (size_t)ctx->queues.cap) grid = ctx->tuneBlocksSmall;
-    }
-    const int gridAll = gridFor(P.n_paths);
-    const bool smallScene = isSmallScene(ctx);
+    B.Q = ctx->queues;
+    B.dense = B.Q.items[1];
+    B.grid = wavefrontGrid(ctx->nBlocks, ctx->tuneBlocksSmall, ctx->tuneSmallPaths, P.n_paths, ctx->queues.cap);
+    B.gridAll = gridFor(P.n_paths);
+    B.smallScene = isSmallScene(ctx);
+    B.ldsBytes = B.smallScene ? (size_t)ctx->ldsTris * 48 : (size_t)PPG_LDS_STACK * PPG_BLOCK * 4;
+    B.hostCount = P.n_paths;
+    B.Pc = P;
+    return PPG_OK;
+}
+
+// 2. k_generate and the wavefront bounces (B.P.n_paths > 0).
+// Bounce 1 works on all paths of the batch; every later bounce on the dense list of live paths that k_scan_counts + k_gather_slices
+// rebuild from k_shade's output slices (ppg_kernels.h "Queues").  Bounded paths (maxDepth > 0) run maxDepth bounces.  Unbounded
+// paths run wavefront bounces until fewer than `stopBelow` paths are alive and hand those to the persistent-thread tail (k_tail).
+// Nothing is read back in between: the host launches as many bounces as the previous batch's survival curve says this batch needs
+// (planBounces); the device raises a stop flag when the live count has fallen below the threshold, and the kernels of the
+// bounces launched beyond that point return at once.  The host synchronises once per batch.
+int runWavefront(ppg_ctx *ctx, Batch &B) {
+    const PathState &P = B.P;
+    const DevScene &S = B.S;
+    Queues &Q = B.Q;
+    hipStream_t s = ctx->stream;
+    const int grid = B.grid;
+    const bool smallScene = B.smallScene;
     // (small scenes go through k_trace too: tracing them inside k_generate / k_shade was measured slower, DESIGN.md "Tuning switches")
     const bool neeOn = ctx->doNee;  // m_doNee of this iteration (doNeeWithSpp, GP:1331-1340)
     const bool fullMats = ctx->fullMaterials;  // any BSDF beyond diffuse / two-sided diffuse / mirror: the FULL kernel variants
     const size_t triBytes = (size_t)ctx->scene.n_tris * 48;
-    const bool unbounded = ctx->maxDepth < 0;
-    const size_t ldsBytes = smallScene ? (size_t)ctx->ldsTris * 48 : (size_t)PPG_LDS_STACK * PPG_BLOCK * 4;
-    const size_t traceLds = smallScene ? ldsBytes : (size_t)PPG_TRACE_STACK * PPG_BLOCK * 4 + (PPG_BLOCK / 64) * sizeof(PairLds);  // k_trace: + a wave's pair scratch
-    // live paths below which the wavefront stops (unbounded paths: k_tail takes over; bounded paths: nothing is left)
-    const unsigned int stopBelow = unbounded ? (ctx->tailThreshold ? ctx->tailThreshold : std::max(ctx->tailMin, P.n_paths / ctx->tailDiv)) : 1u;
-    unsigned int hostCount = P.n_paths;
-    int bouncesRun = 0;
-    if (P.n_paths > 0) {
-        int qin = QIN_FIRST;
-        timedLaunch(ctx, "k_generate", P.n_paths, [&] { hipLaunchKernelGGL(k_generate, dim3(gridAll), dim3(PPG_BLOCK), 0, s, P, S, R, Q); });
-        // Bounce 1 works on all paths of the batch; every later bounce on the dense list of live paths that k_scan_counts + k_gather_slices
-        // rebuild from k_shade's output slices (ppg_kernels.h "Queues").  Bounded paths (maxDepth > 0) run maxDepth bounces.  Unbounded
-        // paths run wavefront bounces until fewer than `stopBelow` paths are alive and hand those to the persistent-thread tail (k_tail).
-        // Nothing is read back in between: the host launches as many bounces as the previous batch's survival curve says this batch needs
-        // (plus a margin); the device raises a stop flag when the live count has fallen below the threshold, and the kernels of the
-        // bounces launched beyond that point return at once.  The host synchronises once per batch.
-        int maxBounces = ctx->maxDepth;
-        if (unbounded) {
-            if (ctx->tuneBulkBounces >= 0) maxBounces = std::min(64, ctx->tuneBulkBounces);
-            else {
-                // live(b) of this batch ~ (live(b) / paths of the previous batch) * paths of this one; beyond what was observed, the last ratio
-                int need = 8;
-                if (ctx->prevBounces > 0 && ctx->prevPaths > 0) {
-                    const double scale = (double)P.n_paths / (double)ctx->prevPaths;
-                    need = -1;
-                    for (int b = 0; b < ctx->prevBounces; ++b) if (ctx->prevLive[b] * scale < stopBelow) { need = b + 1; break; }
-                    if (need < 0) {
-                        double live = ctx->prevLive[ctx->prevBounces - 1] * scale;
-                        const double before = ctx->prevBounces > 1 ? ctx->prevLive[ctx->prevBounces - 2] : (double)ctx->prevPaths;
-                        const double ratio = std::min(0.97, std::max(0.5, before > 0 ? ctx->prevLive[ctx->prevBounces - 1] / before : 0.9));
-                        need = ctx->prevBounces;
-                        while (live >= stopBelow && need < 64) { live *= ratio; ++need; }
-                    }
-                }
-                maxBounces = std::max(1, std::min(64, need + ctx->bounceMargin));
-                // (a batch smaller than the hand-over threshold stops after its first bounce whatever happens: no margin — every launch beyond the
-                // stop returns at once, but three kernels and two small ones per bounce are still 30 us of launches, 0.5 ms in a first batch)
-                if (P.n_paths < stopBelow) maxBounces = 1;
-            }
-            // (a round whose stragglers' records are deferred: a path alive after wavefront bounce b has depth b, and which paths are
-            // stragglers is decided where k_tail takes them — never beyond the depth of the rule, include/ppg.h "STRAGGLERS")
-            if (adamRound && ctx->adamFast) maxBounces = std::min(maxBounces, std::max(1, ctx->deferDepthAdam));
-        }
-        const bool liveCount = ctx->timer.enabled;  // kernel timing wants the units of every launch
-        unsigned int *counts = ctx->d_bounceCounts.p;  // [0..63] live paths after bounce b, [64] the stop flag
-        HIP_CHECK(hipMemsetAsync(counts, 0, 72 * 4, s));
-        Q.stop = counts + 64;
-        Q.dense_n = ctx->d_total.p;
-        for (int b = 0; b < maxBounces; ++b) {
-            // (the first bounce — every path of the batch, camera rays — is sorted only for the sake of the split into material classes)
-            const bool sortSlices = fullMats && (qin == QIN_DENSE || (Q.n_common && !neeOn && !ctx->tuneNoSortFirst)) && ctx->d_queueSorted.p;
-            // k_trace sorts its own slice when it has traced it (sort_slice, ppg_kernels.h)
-            unsigned int *const trSorted = sortSlices ? ctx->d_queueSorted.p : nullptr;
-            unsigned char *const trKeys = sortSlices ? ctx->d_sortKeys.p : nullptr;
-            timedLaunch(ctx, "k_trace", hostCount, [&] {
-                TraceLaunch a{grid, traceLds, s, P, S, Q, qin, smallScene ? 0 : ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys, smallScene, ctx->timer.enabled};
-                launcher(ppg_path_kernels[sceneFamily(S)].trace)(a);
-            });
-            int shadeIn = sortSlices ? QIN_SORTED : qin;
-            ctx->joinTree();  // (k_generate and the first k_trace ran beside the previous round's optimiser: k_shade needs its result)
-            // FULL scene, sorted slice, no luminaire sampling: the common material classes first, in their own leaner kernel (MSET_COMMON)
-            // (also for a scene with disks or cylinders, although this kernel is compiled without their code: it shades triangle hits of the
-            // common classes only — sort_slice keeps every non-triangle hit out of them —, traces nothing and, without luminaire sampling,
-            // never calls emitter_sample_direct, where a shape's em_info entry would be read as a triangle range.  A variant of it that
-            // traces or samples emitters must go through the scene's family like the others: ppg_launch_shade / ppg_launch_tail.)
-            const bool split = shadeIn == QIN_SORTED && Q.n_common && !neeOn;
-            if (split) {
-                timedLaunch(ctx, "k_shade<common>", hostCount, [&] {
-                    ShadeLaunch a{grid, 0, s, P, S, T, R, Q, QIN_SORTED_COMMON, smallScene ? 1 : 0, ctx->d_queueSorted.p};
-                    ppg_launch_shade_common(a);
-                });
-                shadeIn = QIN_SORTED_REST;
-            }
-            timedLaunch(ctx, neeOn ? "k_shade<nee>" : (fullMats ? (split ? "k_shade<rest>" : "k_shade<full>") : "k_shade"), hostCount, [&] {
-                const int small = smallScene ? 1 : 0;
-                // dynamic LDS: the staged triangles (luminaire sampling on a small scene) or the shadow rays' BVH stack columns
-                const size_t neeBytes = smallScene ? triBytes : (size_t)PPG_LDS_STACK * PPG_BLOCK * 4;
-                const size_t lds = (neeOn || ctx->scene.has_null) ? neeBytes : 0;
-                const int variant = (neeOn ? 2 : 0) | (fullMats ? 1 : 0);
-                ShadeLaunch a{grid, lds, s, P, S, T, R, Q, shadeIn, small, ctx->d_queueSorted.p};
-                ppg_launch_shade(variant, a);
-            });
-            qin = QIN_DENSE;
-            ++bouncesRun;
-            hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, Q.count[0], ctx->d_offsets.p, (unsigned int)grid, ctx->d_total.p,
-                               counts + std::min(b, 63), counts + 64, stopBelow);
-            hipLaunchKernelGGL(k_gather_slices, dim3(grid), dim3(PPG_BLOCK), 0, s, Q.items[0], Q.count[0], ctx->d_offsets.p, Q.cap, Q.items[1]);
-            if (liveCount) {
-                HIP_CHECK(hipMemcpyAsync(&hostCount, ctx->d_total.p, 4, hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipStreamSynchronize(s));
-                if (hostCount == 0 || (unbounded && hostCount < stopBelow)) break;
-            }
-        }
-    }
-    // What follows the wavefront bounces of a batch:
-    //   unbounded paths   persistent threads finish the survivors (k_tail): ONE launch, every lane carries a path from the dense list until it
-    //                     ends.  Its length is set by the batch's LONGEST path (KITCHEN: 300-900 dependent bounces among 1-12 M paths); the
-    //                     crowd of short paths dies away around it and the wave that holds it speeds up as it empties;
-    //   training batches  k_commit splats every recorded vertex into the building tree.
-    // With both, k_commit for the paths that HAVE ended runs on a second stream beside k_tail, and a second, small k_commit takes the
-    // stragglers afterwards.  Integer accumulation makes the split invisible in the result.  In a round of the optimiser, the record
-    // positions must then be known before the tail has run: a straggler reserves max_vertices positions (unused ones stay holes).
-    ctx->joinTree();  // (a batch without a wavefront bounce)
-    const bool tail = unbounded && P.n_paths > 0;
-    const bool commit = !ctx->isFinalIter && P.n_paths > 0;
-    const bool fastRound = adamRound && ctx->adamFast && P.n_paths > 0;
-    // STRAGGLERS.  k_tail hands the paths still alive at depth `deferDepth` over to a second launch that runs beside the NEXT batch (see
-    // "Stragglers" above drainStragglers).  In a round of the optimiser whose record positions are known the depth is part of the result
-    // (include/ppg.h "STRAGGLERS": their records are applied one round late); elsewhere it is scheduling only, and worth it only when another
-    // batch follows at once (`last` = false).
-    const bool deferRecords = adamRound && ctx->adamFast && unbounded;
-    const unsigned int deferDepth = !tail ? 0u : (deferRecords ? (unsigned int)ctx->deferDepthAdam : ((!last && !adamRound && !ctx->timer.enabled && !ctx->tuneNoOverlap) ? (unsigned int)ctx->tuneSplitDepth : 0u));
-    const bool splitTail = deferDepth > 0;
-    const bool beside = !ctx->timer.enabled && !ctx->tuneNoOverlap;  // side streams may be used
-    // k_commit of the paths that HAVE ended when k_tail takes over runs beside it; with a split tail the two-phase commit is needed anyway
-    // (the hand-over must be known before the tail runs)
-    const bool overlap = tail && commit && (beside || splitTail);
-    // A round whose record positions are known commits in three steps — records, the optimiser's sort, splats D-tree by D-tree
-    // (ppg_kernels.h "The commit of a ROUND") — instead of one lane per vertex adding to the pool with global atomics.
-    {
-        unsigned int leafBits = 1;
-        while ((1u << leafBits) <= (unsigned int)ctx->snodes.size()) ++leafBits;
-        ctx->adamFlagShift = PPG_ADAM_LEAF_SHIFT + leafBits;
-    }
-    // (the flag needs a key bit above the leaf: an S-tree of 2^23 nodes or more — never seen — commits with k_commit)
-    ctx->sortedCommit = adamRound && ctx->adamFast && !ctx->tuneNoSortedCommit && ctx->adamFlagShift < 63u;
-    size_t nRecords = 0;
-    unsigned int *dense = Q.items[1];  // the live paths in one list (k_tail's work list)
-    ppg_ctx::Stragglers &G = ctx->strag[ctx->stragCur];  // the set this batch's stragglers go to (the other one may be pending: the previous batch's)
-    // the records of the PREVIOUS round's stragglers are applied with this round's: they take the positions behind its own
-    const size_t nDeferredIn = (adamRound && ctx->adamFast && ctx->stragPrev().pending && ctx->stragPrev().adam) ? (size_t)ctx->stragPrev().n * (size_t)ctx->maxVertices : 0;
-    // (handedPaths: how many paths the launch will find in the list, when the host knows — 0 = unknown)
-    auto launchTail = [&](unsigned int depth, size_t handedPaths = 0) {
-        HIP_CHECK(hipMemsetAsync(ctx->d_ticket.p, 0, 4, s));
-        // (the persistent workgroups of k_tail hold their registers until their last path has ended: no more of them than fit the GPU at once)
-        const int tailGrid = std::min(grid, ctx->tuneTailBlocks ? ctx->tuneTailBlocks : 1024);
-        // Fewer paths than lanes — a rank's share of a small round, a round over one group of blocks —: dealt THINLY, the same number of
-        // lanes in every wave, instead of 64 to the first waves and none to the rest: a wave's bounce costs the union of its lanes' branches
-        // and its longest traversal, and idle SIMDs cost nothing.
-        const size_t tailWaves = (size_t)tailGrid * (PPG_BLOCK / 64);
-        const unsigned int laneLimit = handedPaths ? (unsigned int)std::max<size_t>(1, std::min<size_t>(64, (handedPaths + tailWaves - 1) / tailWaves)) : 64u;
-        timedLaunch(ctx, "k_tail", hostCount, [&] {
-            RenderParams Rt = R;
-            Rt.defer_depth = depth;
-            // (the launch's longest path is logged for launches that run their paths to the END: the sum is the tails' critical path; a launch that
-            // hands its stragglers over writes to a spare slot nobody reads)
-            TailLaunch a{tailGrid, ldsBytes, s, P, S, T, Rt, dense, ctx->d_total.p, ctx->d_ticket.p, Q.stats, ctx->ldsTris,
-                         ctx->d_tailLongest.p + (depth ? PPG_TAIL_LOG : (ctx->tailLaunches++ % PPG_TAIL_LOG)), StragOut{G.rec.p, G.orig.p, G.count.p}, laneLimit};
-            ppg_launch_tail((smallScene ? 4 : 0) | (neeOn ? 2 : 0) | (fullMats ? 1 : 0), a);
+    const size_t traceLds = smallScene ? B.ldsBytes : (size_t)PPG_TRACE_STACK * PPG_BLOCK * 4 + (PPG_BLOCK / 64) * sizeof(PairLds);  // k_trace: + a wave's pair scratch
+    const unsigned int stopBelow = B.plan.stopBelow;
+    int qin = QIN_FIRST;
+    timedLaunch(ctx, "k_generate", P.n_paths, [&] { hipLaunchKernelGGL(k_generate, dim3(B.gridAll), dim3(PPG_BLOCK), 0, s, P, S, B.R, Q); });
+    const int maxBounces = planBounces(ctx->survival, P.n_paths, stopBelow, ctx->maxDepth, ctx->tuneBulkBounces, ctx->bounceMargin, B.plan.adamFast, ctx->deferDepthAdam);
+    const bool liveCount = ctx->timer.enabled;  // kernel timing wants the units of every launch
+    unsigned int *counts = ctx->d_bounceCounts.p;  // [0..63] live paths after bounce b, [64] the stop flag
+    HIP_CHECK(hipMemsetAsync(counts, 0, 72 * 4, s));
+    Q.stop = counts + 64;
+    Q.dense_n = ctx->d_total.p;
+    for (int b = 0; b < maxBounces; ++b) {
+        // (the first bounce — every path of the batch, camera rays — is sorted only for the sake of the split into material classes)
+        const bool sortSlices = fullMats && (qin == QIN_DENSE || (Q.n_common && !neeOn && !ctx->tuneNoSortFirst)) && ctx->d_queueSorted.p;
+        // k_trace sorts its own slice when it has traced it (sort_slice, ppg_kernels.h)
+        unsigned int *const trSorted = sortSlices ? ctx->d_queueSorted.p : nullptr;
+        unsigned char *const trKeys = sortSlices ? ctx->d_sortKeys.p : nullptr;
+        timedLaunch(ctx, "k_trace", B.hostCount, [&] {
+            TraceLaunch a{grid, traceLds, s, P, S, Q, qin, smallScene ? 0 : ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys, smallScene, ctx->timer.enabled};
+            launcher(ppg_path_kernels[sceneFamily(S)].trace)(a);
         });
-        return PPG_OK;
-    };
-    // interleaved path records: k_commit and k_path_nv sweep the per-path word once per (slot, path) item — from a contiguous copy
-    PathState Pc = P;
-    bool miscCopied = false;
-    auto copyMisc = [&] {  // k_commit_prepare: a byte per path for k_commit's work items (+ the contiguous copy of the path words)
-        if (miscCopied || P.n_paths == 0) return PPG_OK;
-        HIP_CHECK(ctx->d_nv8.reserve(P.n_paths));
-        hipLaunchKernelGGL(k_commit_prepare, dim3((P.n_paths + 255) / 256), dim3(256), 0, s, P, ctx->aosPaths ? ctx->d_miscCompact.p : (uint4 *)nullptr, ctx->d_nv8.p,
-                           overlap ? (const unsigned char *)ctx->d_straggler.p : (const unsigned char *)nullptr);
-        if (ctx->aosPaths) Pc.misc = {ctx->d_miscCompact.p, 1};
-        miscCopied = true;
-        return PPG_OK;
-    };
-    // mode 0: every path; 1: paths not flagged as stragglers; 2: the paths of the dense list
-    auto launchCommit = [&](hipStream_t st, int mode) {
-        const unsigned char *nv8 = ctx->d_nv8.p;  // (mode 1: the stragglers' bytes are 0; mode 2: by list position, written just before)
-        if (mode == 2) hipLaunchKernelGGL(k_commit_prepare_list, dim3(std::max(1, std::min(grid, 1024))), dim3(256), 0, st, P, dense, ctx->d_total.p, ctx->d_nv8.p);
-        const unsigned int *list = mode == 2 ? dense : nullptr;
-        const unsigned long long *listN = mode == 2 ? ctx->d_total.p : nullptr;
-        const PathState &PP = mode == 2 ? P : Pc;  // the stragglers' words changed in the tail: read them in place
-        CommitLaunch a{grid, st, PP, T, R, Q, nv8, list, listN, ctx->d_splat.p, ctx->adamFlagShift};
-        if (ctx->sortedCommit) ppg_launch_commit_records(ctx->spatialFilter, a);
-        else ppg_launch_commit(ctx->spatialFilter, ctx->directionalFilter, a);
-    };
-    if (tail) {
-        if (bouncesRun == 0)  // no wavefront bounce was run: every path of the batch goes to the persistent threads
-            hipLaunchKernelGGL(k_iota_total, dim3(gridAll), dim3(PPG_BLOCK), 0, s, dense, P.n_paths, ctx->d_total.p);
-        if (overlap) {
+        int shadeIn = sortSlices ? QIN_SORTED : qin;
+        ctx->joinTree();  // (k_generate and the first k_trace ran beside the previous round's optimiser: k_shade needs its result)
+        // FULL scene, sorted slice, no luminaire sampling: the common material classes first, in their own leaner kernel (MSET_COMMON)
+        // (also for a scene with disks or cylinders, although this kernel is compiled without their code: it shades triangle hits of the
+        // common classes only — sort_slice keeps every non-triangle hit out of them —, traces nothing and, without luminaire sampling,
+        // never calls emitter_sample_direct, where a shape's em_info entry would be read as a triangle range.  A variant of it that
+        // traces or samples emitters must go through the scene's family like the others: ppg_launch_shade / ppg_launch_tail.)
+        const bool split = shadeIn == QIN_SORTED && Q.n_common && !neeOn;
+        if (split) {
+            timedLaunch(ctx, "k_shade<common>", B.hostCount, [&] {
+                ShadeLaunch a{grid, 0, s, P, S, B.T, B.R, Q, QIN_SORTED_COMMON, smallScene ? 1 : 0, ctx->d_queueSorted.p};
+                ppg_launch_shade_common(a);
+            });
+            shadeIn = QIN_SORTED_REST;
+        }
+        timedLaunch(ctx, neeOn ? "k_shade<nee>" : (fullMats ? (split ? "k_shade<rest>" : "k_shade<full>") : "k_shade"), B.hostCount, [&] {
+            const int small = smallScene ? 1 : 0;
+            // dynamic LDS: the staged triangles (luminaire sampling on a small scene) or the shadow rays' BVH stack columns
+            const size_t neeBytes = smallScene ? triBytes : (size_t)PPG_LDS_STACK * PPG_BLOCK * 4;
+            const size_t lds = (neeOn || ctx->scene.has_null) ? neeBytes : 0;
+            const int variant = (neeOn ? 2 : 0) | (fullMats ? 1 : 0);
+            ShadeLaunch a{grid, lds, s, P, S, B.T, B.R, Q, shadeIn, small, ctx->d_queueSorted.p};
+            ppg_launch_shade(variant, a);
+        });
+        qin = QIN_DENSE;
+        ++B.bouncesRun;
+        hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, s, Q.count[0], ctx->d_offsets.p, (unsigned int)grid, ctx->d_total.p,
+                           counts + std::min(b, 63), counts + 64, stopBelow);
+        hipLaunchKernelGGL(k_gather_slices, dim3(grid), dim3(PPG_BLOCK), 0, s, Q.items[0], Q.count[0], ctx->d_offsets.p, Q.cap, Q.items[1]);
+        if (liveCount) {
+            HIP_CHECK(hipMemcpyAsync(&B.hostCount, ctx->d_total.p, 4, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            if (B.hostCount == 0 || (ctx->maxDepth < 0 && B.hostCount < stopBelow)) break;
+        }
+    }
+    return PPG_OK;
+}
+
+// k_tail over the dense list, up to `depth` (0: every path to its end).  handedPaths: how many paths it will find, when the host knows — 0 = unknown.
+int launchTail(ppg_ctx *ctx, Batch &B, unsigned int depth, size_t handedPaths) {
+    hipStream_t s = ctx->stream;
+    ppg_ctx::Stragglers &G = ctx->strag[ctx->stragCur];  // the set this batch's stragglers go to (the other one may be pending: the previous batch's)
+    HIP_CHECK(hipMemsetAsync(ctx->d_ticket.p, 0, 4, s));
+    const TailShape shape = tailShape(B.grid, ctx->tuneTailBlocks, handedPaths);
+    timedLaunch(ctx, "k_tail", B.hostCount, [&] {
+        RenderParams Rt = B.R;
+        Rt.defer_depth = depth;
+        // (the launch's longest path is logged for launches that run their paths to the END: the sum is the tails' critical path; a launch that
+        // hands its stragglers over writes to a spare slot nobody reads)
+        TailLaunch a{shape.grid, B.ldsBytes, s, B.P, B.S, B.T, Rt, B.dense, ctx->d_total.p, ctx->d_ticket.p, B.Q.stats, ctx->ldsTris,
+                     ctx->d_tailLongest.p + (depth ? PPG_TAIL_LOG : (ctx->tailLaunches++ % PPG_TAIL_LOG)), StragOut{G.rec.p, G.orig.p, G.count.p}, shape.laneLimit};
+        ppg_launch_tail(tailVariant(ctx), a);
+    });
+    return PPG_OK;
+}
+
+// k_commit_prepare: a byte per path for k_commit's work items (+ the contiguous copy of the path words: with interleaved path records k_commit
+// and k_path_nv would sweep the per-path word once per (slot, path) item)
+int copyMisc(ppg_ctx *ctx, Batch &B) {
+    const PathState &P = B.P;
+    if (B.miscCopied || P.n_paths == 0) return PPG_OK;
+    HIP_CHECK(ctx->d_nv8.reserve(P.n_paths));
+    hipLaunchKernelGGL(k_commit_prepare, dim3((P.n_paths + 255) / 256), dim3(256), 0, ctx->stream, P, ctx->aosPaths ? ctx->d_miscCompact.p : (uint4 *)nullptr, ctx->d_nv8.p,
+                       B.plan.overlap ? (const unsigned char *)ctx->d_straggler.p : (const unsigned char *)nullptr);
+    if (ctx->aosPaths) B.Pc.misc = {ctx->d_miscCompact.p, 1};
+    B.miscCopied = true;
+    return PPG_OK;
+}
+
+// The batch's commit on stream st.  Ended: copyMisc left the stragglers' bytes 0; List: by list position, the bytes written just before.
+void launchCommit(ppg_ctx *ctx, const Batch &B, hipStream_t st, CommitSet set) {
+    const bool list = set == CommitSet::List;
+    if (list) hipLaunchKernelGGL(k_commit_prepare_list, dim3(std::max(1, std::min(B.grid, 1024))), dim3(256), 0, st, B.P, B.dense, ctx->d_total.p, ctx->d_nv8.p);
+    // (the stragglers' words changed in the tail: the list's paths are read in place)
+    CommitLaunch a{B.grid, st, list ? B.P : B.Pc, B.T, B.R, B.Q, ctx->d_nv8.p, list ? B.dense : nullptr, list ? ctx->d_total.p : nullptr, ctx->d_splat.p, ctx->adamFlagShift};
+    launchCommitKernels(ctx, a, ctx->sortedCommit);
+}
+// ... on the context's stream, with its timer entry (kernel timing is on only where side streams are not allowed)
+void launchCommitTimed(ppg_ctx *ctx, const Batch &B, CommitSet set, uint64_t units) {
+    timedLaunch(ctx, commitName(ctx->sortedCommit), units, [&] { launchCommit(ctx, B, ctx->stream, set); });
+}
+
+// k_tail, and with plan.overlap the commit of the paths that have ENDED when it takes over: beside it on stream2 — forked before the tail's
+// launch, joined behind it —, or after it where side streams are not allowed.
+int launchTailAndEndedCommit(ppg_ctx *ctx, Batch &B, unsigned int depth, size_t handedPaths) {
+    hipStream_t s = ctx->stream;
+    if (B.plan.overlap) HIP_CHECK(hipEventRecord(ctx->evFork, s));
+    { int rc = launchTail(ctx, B, depth, handedPaths); if (rc) return rc; }
+    if (!B.plan.overlap) return PPG_OK;
+    if (B.plan.beside) {
+        HIP_CHECK(hipStreamWaitEvent(ctx->stream2, ctx->evFork, 0));
+        launchCommit(ctx, B, ctx->stream2, CommitSet::Ended);
+        HIP_CHECK(hipEventRecord(ctx->evJoin, ctx->stream2));
+        HIP_CHECK(hipStreamWaitEvent(s, ctx->evJoin, 0));
+    } else launchCommitTimed(ctx, B, CommitSet::Ended, B.P.n_paths);
+    return PPG_OK;
+}
+
+// 3. What follows the wavefront bounces of a batch (the shapes by plan: DESIGN.md "Launch structure on MI355X"):
+//   unbounded paths   persistent threads finish the survivors (k_tail): ONE launch, every lane carries a path from the dense list until it
+//                     ends.  Its length is set by the batch's LONGEST path (KITCHEN: 300-900 dependent bounces among 1-12 M paths); the
+//                     crowd of short paths dies away around it and the wave that holds it speeds up as it empties;
+//   training batches  k_commit splats every recorded vertex into the building tree.
+// With both, k_commit for the paths that HAVE ended runs on a second stream beside k_tail, and a second, small k_commit takes the
+// stragglers afterwards.  Integer accumulation makes the split invisible in the result.  In a round of the optimiser, the record
+// positions must then be known before the tail has run: a straggler reserves max_vertices positions (unused ones stay holes).
+// A split tail hands the paths still alive at plan.deferDepth over to a second launch that runs beside the NEXT batch ("Stragglers").
+int finishPaths(ppg_ctx *ctx, Batch &B) {
+    const PathState &P = B.P;
+    const BatchPlan &plan = B.plan;
+    hipStream_t s = ctx->stream;
+    RoundReadback *const h = ctx->h_round;
+    ctx->joinTree();  // (a batch without a wavefront bounce)
+    if (plan.tail) {
+        if (B.bouncesRun == 0)  // no wavefront bounce was run: every path of the batch goes to the persistent threads
+            hipLaunchKernelGGL(k_iota_total, dim3(B.gridAll), dim3(PPG_BLOCK), 0, s, B.dense, P.n_paths, ctx->d_total.p);
+        if (plan.overlap) {
             HIP_CHECK(ctx->d_straggler.reserve(P.n_paths));
             HIP_CHECK(hipMemsetAsync(ctx->d_straggler.p, 0, P.n_paths, s));
-            hipLaunchKernelGGL(k_mark_list, dim3(grid), dim3(PPG_BLOCK), 0, s, dense, ctx->d_total.p, ctx->d_straggler.p);
-        } else if (!splitTail) {
-            int rc = launchTail(0u);
+            hipLaunchKernelGGL(k_mark_list, dim3(B.grid), dim3(PPG_BLOCK), 0, s, B.dense, ctx->d_total.p, ctx->d_straggler.p);
+        } else if (!plan.splitTail) {
+            int rc = launchTail(ctx, B, 0u, 0);
             if (rc) return rc;
         }
     }
-    if (fastRound) {
+    if (plan.fastRound) {
         // position of path i's records = exclusive scan of the vertex counts
         HIP_CHECK(ctx->d_adamNv.reserve(P.n_paths)); HIP_CHECK(ctx->d_adamBase.reserve(P.n_paths));
-        { int rc = copyMisc(); if (rc) return rc; }
-        hipLaunchKernelGGL(k_path_nv, dim3((P.n_paths + 255) / 256), dim3(256), 0, s, Pc, ctx->d_adamNv.p, overlap ? ctx->d_straggler.p : nullptr, (unsigned int)ctx->maxVertices);
+        { int rc = copyMisc(ctx, B); if (rc) return rc; }
+        hipLaunchKernelGGL(k_path_nv, dim3((P.n_paths + 255) / 256), dim3(256), 0, s, B.Pc, ctx->d_adamNv.p, plan.overlap ? ctx->d_straggler.p : nullptr, (unsigned int)ctx->maxVertices);
         size_t bytes = 0;
         HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, ctx->d_adamNv.p, ctx->d_adamBase.p, 0u, (size_t)P.n_paths, rocprim::plus<unsigned int>(), s));
         HIP_CHECK(ctx->d_sortTemp.reserve(std::max<size_t>(bytes, 16)));
         HIP_CHECK(rocprim::exclusive_scan((void *)ctx->d_sortTemp.p, bytes, ctx->d_adamNv.p, ctx->d_adamBase.p, 0u, (size_t)P.n_paths, rocprim::plus<unsigned int>(), s));
-        HIP_CHECK(hipMemcpyAsync(ctx->h_round + 65, ctx->d_adamBase.p + (P.n_paths - 1), 4, hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipMemcpyAsync(ctx->h_round + 66, ctx->d_adamNv.p + (P.n_paths - 1), 4, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(&h->sumBase, ctx->d_adamBase.p + (P.n_paths - 1), 4, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(&h->lastNv, ctx->d_adamNv.p + (P.n_paths - 1), 4, hipMemcpyDeviceToHost, s));
     }
-    size_t nRecordsOwn = 0;
-    if (tail || fastRound) {
-        if (unbounded) HIP_CHECK(hipMemcpyAsync(ctx->h_round, ctx->d_bounceCounts.p, 64 * 4, hipMemcpyDeviceToHost, s));
-        if (splitTail) HIP_CHECK(hipMemcpyAsync(ctx->h_round + 68, ctx->d_total.p, 8, hipMemcpyDeviceToHost, s));  // the paths handed to k_tail
+    if (plan.tail || plan.fastRound) {
+        if (plan.tail) HIP_CHECK(hipMemcpyAsync(h->live, ctx->d_bounceCounts.p, sizeof h->live, hipMemcpyDeviceToHost, s));
+        if (plan.splitTail) HIP_CHECK(hipMemcpyAsync(&h->handed, ctx->d_total.p, 8, hipMemcpyDeviceToHost, s));  // the paths handed to k_tail
         HIP_CHECK(hipStreamSynchronize(s));  // the one host round trip of a batch of unbounded paths / of a round
-        if (tail) {
+        if (plan.tail) {
             // the survival curve of this batch sizes the schedule of the next one
-            int ran = bouncesRun;
-            for (int b = 0; b < bouncesRun; ++b) if (ctx->h_round[b] < stopBelow) { ran = b + 1; break; }
-            ctx->prevBounces = ran; ctx->prevPaths = P.n_paths;
-            for (int b = 0; b < ran; ++b) ctx->prevLive[b] = ctx->h_round[b];
+            const int ran = observeBounces(ctx->survival, h->live, B.bouncesRun, P.n_paths, plan.stopBelow);
             if (ctx->debugBatch) {
-                fprintf(stderr, "[ppg batch] iter %d paths %u built %d final %d launched %d ran %d stop<%u live:", ctx->iter, P.n_paths, (int)ctx->isBuilt, (int)ctx->isFinalIter, bouncesRun, ran, stopBelow);
-                for (int b = 0; b < ran; ++b) fprintf(stderr, " %u", ctx->h_round[b]);
+                fprintf(stderr, "[ppg batch] iter %d paths %u built %d final %d launched %d ran %d stop<%u live:", ctx->iter, P.n_paths, (int)ctx->isBuilt, (int)ctx->isFinalIter, B.bouncesRun, ran, plan.stopBelow);
+                for (int b = 0; b < ran; ++b) fprintf(stderr, " %u", h->live[b]);
                 fprintf(stderr, "\n");
             }
         }
-        if (fastRound) {
-            nRecordsOwn = (size_t)ctx->h_round[65] + ctx->h_round[66];
-            nRecords = nRecordsOwn + nDeferredIn;
-            if (nRecords > 0xfffffff0ull) { ctx->error = "too many Adam records in one round"; return PPG_ERR_NOMEM; }
-            HIP_CHECK(ctx->d_adamKeys[0].reserve(std::max<size_t>(1, nRecords))); HIP_CHECK(ctx->d_adamRecs.reserve(std::max<size_t>(1, nRecords)));
-            if (ctx->sortedCommit) HIP_CHECK(ctx->d_splat.reserve(std::max<size_t>(1, nRecords)));
-            if (nRecords) HIP_CHECK(hipMemsetAsync(ctx->d_adamKeys[0].p, 0xff, nRecords * 8, s));
-            T = ctx->devTree();
+        if (plan.fastRound) {
+            B.nRecordsOwn = (size_t)h->sumBase + h->lastNv;
+            if (B.nRecordsOwn + plan.nDeferredIn > 0xfffffff0ull) { ctx->error = "too many Adam records in one round"; return PPG_ERR_NOMEM; }
         }
     }
-    if (adamRound && ctx->adamFast && !fastRound && nDeferredIn) {  // an empty round (a cancelled rank kept in step) that still owes the previous round's stragglers
-        nRecords = nDeferredIn;
-        HIP_CHECK(ctx->d_adamKeys[0].reserve(nRecords)); HIP_CHECK(ctx->d_adamRecs.reserve(nRecords));
-        if (ctx->sortedCommit) HIP_CHECK(ctx->d_splat.reserve(nRecords));
-        HIP_CHECK(hipMemsetAsync(ctx->d_adamKeys[0].p, 0xff, nRecords * 8, s));
-        T = ctx->devTree();
+    // (without paths of its own — a cancelled rank kept in step — a round may still owe the previous round's stragglers)
+    if (plan.fastRound || (plan.adamFast && plan.nDeferredIn)) {
+        B.nRecords = B.nRecordsOwn + plan.nDeferredIn;
+        int rc = reserveRoundRecords(ctx, B.nRecords);
+        if (rc) return rc;
+        B.T = ctx->devTree();
     }
-    if (commit) { int rc = copyMisc(); if (rc) return rc; }
-    unsigned int nStrag = 0;
-    if (splitTail) {
+    if (plan.commit) { int rc = copyMisc(ctx, B); if (rc) return rc; }
+    if (plan.splitTail) {
         // k_tail up to depth deferDepth; what is alive then is written to the straggler set (at most every path handed over)
-        const size_t handed = (size_t)(((unsigned long long)ctx->h_round[69] << 32) | ctx->h_round[68]);
+        ppg_ctx::Stragglers &G = ctx->strag[ctx->stragCur];
+        const size_t handed = (size_t)h->handed;
         HIP_CHECK(G.rec.reserve(std::max<size_t>(1, handed) * 8)); HIP_CHECK(G.orig.reserve(std::max<size_t>(1, handed)));
         HIP_CHECK(G.count.reserve(2)); HIP_CHECK(G.ticket.reserve(1));
         HIP_CHECK(hipMemsetAsync(G.count.p, 0, 16, s));
-        if (overlap) HIP_CHECK(hipEventRecord(ctx->evFork, s));
-        { int rc = launchTail(deferDepth, handed); if (rc) return rc; }
-        if (overlap) {
-            if (beside) {
-                HIP_CHECK(hipStreamWaitEvent(ctx->stream2, ctx->evFork, 0));
-                launchCommit(ctx->stream2, 1);
-                HIP_CHECK(hipEventRecord(ctx->evJoin, ctx->stream2));
-                HIP_CHECK(hipStreamWaitEvent(s, ctx->evJoin, 0));
-            } else timedLaunch(ctx, ctx->sortedCommit ? "k_commit_records" : "k_commit", P.n_paths, [&] { launchCommit(s, 1); });
-        }
-        HIP_CHECK(hipMemcpyAsync(ctx->h_round + 70, G.count.p, 8, hipMemcpyDeviceToHost, s));
+        { int rc = launchTailAndEndedCommit(ctx, B, plan.deferDepth, handed); if (rc) return rc; }
+        HIP_CHECK(hipMemcpyAsync(&h->stragglers, G.count.p, 8, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));  // the second host round trip of a batch with a split tail: how many stragglers
-        nStrag = ctx->h_round[70];
-        if (ctx->debugBatch) fprintf(stderr, "[ppg batch] iter %d stragglers %u of %zu handed over at depth %u\n", ctx->iter, nStrag, handed, deferDepth);
-        // (the previous batch's set is consumed before this batch's stragglers start: one event, one kept copy of the radiance)
-        if (nStrag) { int rc = drainStragglers(ctx, nRecordsOwn); if (rc) return rc; }
-        if (nStrag) {
-            int rc = launchStragglers(ctx, P, S, T, R, nStrag, commit, deferRecords, beside, (smallScene ? 4 : 0) | (neeOn ? 2 : 0) | (fullMats ? 1 : 0), ldsBytes);
+        B.nStrag = (unsigned int)h->stragglers;
+        if (ctx->debugBatch) fprintf(stderr, "[ppg batch] iter %d stragglers %u of %zu handed over at depth %u\n", ctx->iter, B.nStrag, handed, plan.deferDepth);
+        if (B.nStrag) {
+            // (the previous batch's set is consumed before this batch's stragglers start: one event, one kept copy of the radiance)
+            int rc = drainStragglers(ctx, B.nRecordsOwn);
+            if (!rc) rc = launchStragglers(ctx, B);
             if (rc) return rc;
         }
-        if (overlap) {
-            if (beside) launchCommit(s, 2);
-            else timedLaunch(ctx, ctx->sortedCommit ? "k_commit_records" : "k_commit", 0, [&] { launchCommit(s, 2); });
-        }
-    } else if (overlap) {
-        HIP_CHECK(hipEventRecord(ctx->evFork, s));
-        int rc = launchTail(0u);
+        if (plan.overlap) launchCommitTimed(ctx, B, CommitSet::List, 0);
+    } else if (plan.overlap) {
+        int rc = launchTailAndEndedCommit(ctx, B, 0u, 0);
         if (rc) return rc;
-        HIP_CHECK(hipStreamWaitEvent(ctx->stream2, ctx->evFork, 0));
-        launchCommit(ctx->stream2, 1);
-        HIP_CHECK(hipEventRecord(ctx->evJoin, ctx->stream2));
-        HIP_CHECK(hipStreamWaitEvent(s, ctx->evJoin, 0));
-        launchCommit(s, 2);
-    } else if (commit) {
-        timedLaunch(ctx, ctx->sortedCommit ? "k_commit_records" : "k_commit", P.n_paths, [&] { launchCommit(s, 0); });
-    }
+        launchCommitTimed(ctx, B, CommitSet::List, 0);
+    } else if (plan.commit) launchCommitTimed(ctx, B, CommitSet::All, P.n_paths);
     // what an earlier batch still owes (its film kernel, its stragglers' commit) comes before this batch's own sort and film kernel
-    if (!(splitTail && nStrag)) { int rc = drainStragglers(ctx, nRecordsOwn); if (rc) return rc; }  // (a batch with stragglers of its own consumed it above)
-    if (adamRound) {
-        if (!ctx->adamFast) {
-            HIP_CHECK(hipMemcpyAsync(ctx->h_round + 64, ctx->d_adamCount.p, 8, hipMemcpyDeviceToHost, s));
-            HIP_CHECK(hipStreamSynchronize(s));
-            if (ctx->h_round[65]) { ctx->error = "Adam record buffer overflow (box spatial filter / next-event estimation with a bsdfSamplingFractionLoss)"; return PPG_ERR_NOMEM; }
-            nRecords = ctx->h_round[64];
-        }
-        int rc = applyAdamRound(ctx, nRecords);
-        ctx->adamActive = false;
-        if (rc) return rc;
+    if (!B.nStrag) return drainStragglers(ctx, B.nRecordsOwn);  // (a batch with stragglers of its own consumed it above)
+    return PPG_OK;
+}
+
+// 4. The round of the optimiser: its records are counted — a slow round's by the device —, sorted and applied.
+int optimiserRound(ppg_ctx *ctx, Batch &B) {
+    if (!ctx->adamFast) {
+        RoundReadback *const h = ctx->h_round;
+        HIP_CHECK(hipMemcpyAsync(&h->slowCount, ctx->d_adamCount.p, 8, hipMemcpyDeviceToHost, ctx->stream));  // (and slowOverflow)
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (h->slowOverflow) { ctx->error = "Adam record buffer overflow (box spatial filter / next-event estimation with a bsdfSamplingFractionLoss)"; return PPG_ERR_NOMEM; }
+        B.nRecords = h->slowCount;
     }
-    if (P.n_paths > 0) {
-        // the batch's film kernel — at once, or, when stragglers of this batch are still running, from the copy of its paths' radiance once
-        // they have ended (drainStragglers): the sums a pixel's samples go through are the same either way
-        PathState Pf = P;
-        const bool defer = splitTail && nStrag > 0;
-        if (defer) Pf.li = {ctx->d_liKeep.p, 1};
-        const int sppBatch = ctx->sppPerPass * batch;
-        const bool hasGl = gl != nullptr;
-        const GroupLaunch glv = gl ? *gl : GroupLaunch{};
-        const unsigned long long seed = R.seed;
-        const unsigned int base = R.pass_index_spp, gs = R.group_samples, gstride = R.group_stride;
-        auto film = [ctx, Pf, sppBatch, hasGl, glv, seed, base, gs, gstride] {
-            hipStream_t st = ctx->stream;
-            if (ctx->filtered) {  // footprint partials; a final launch's groups one by one, each resolved into its slot once it is complete
-                if (!hasGl) launchFilmFilter(ctx, Pf, seed, base, 0u, 0u, 0, sppBatch);
-                else {
-                    const size_t n = ctx->nPixAll;
-                    for (int j0 = 0, k = 0; j0 < sppBatch; j0 += (int)gs, ++k) {
-                        launchFilmFilter(ctx, Pf, seed, base, gs, gstride, j0, std::min(sppBatch, j0 + (int)gs));
-                        if (!glv.groupsDone || glv.exchange) continue;
-                        float *slot = ctx->d_partials.p + (ctx->shardWorld > 1 ? 4 * n : 0) + (size_t)(glv.slot0 + (unsigned int)k * glv.slotStride) * 7u * n;
-                        launchFilmResolve(ctx, slot, slot + 3 * n, slot + 6 * n, nullptr, nullptr);
-                    }
+    const int rc = applyAdamRound(ctx, B.nRecords);
+    ctx->adamActive = false;
+    return rc;
+}
+
+// 5. The batch's film kernel — at once, or, when stragglers of this batch are still running, from the copy of its paths' radiance once
+// they have ended (drainStragglers): the sums a pixel's samples go through are the same either way.
+void filmOrDefer(ppg_ctx *ctx, const Batch &B, int batch, const GroupLaunch *gl) {
+    PathState Pf = B.P;
+    const bool defer = B.nStrag > 0;
+    if (defer) Pf.li = {ctx->d_liKeep.p, 1};
+    const int sppBatch = ctx->sppPerPass * batch;
+    const bool hasGl = gl != nullptr;
+    const GroupLaunch glv = gl ? *gl : GroupLaunch{};
+    const unsigned long long seed = B.R.seed;
+    const unsigned int base = B.R.pass_index_spp, gs = B.R.group_samples, gstride = B.R.group_stride;
+    auto film = [ctx, Pf, sppBatch, hasGl, glv, seed, base, gs, gstride] {
+        hipStream_t st = ctx->stream;
+        if (ctx->filtered) {  // footprint partials; a final launch's groups one by one, each resolved into its slot once it is complete
+            if (!hasGl) launchFilmFilter(ctx, Pf, seed, base, 0u, 0u, 0, sppBatch);
+            else {
+                const size_t n = ctx->nPixAll;
+                for (int j0 = 0, k = 0; j0 < sppBatch; j0 += (int)gs, ++k) {
+                    launchFilmFilter(ctx, Pf, seed, base, gs, gstride, j0, std::min(sppBatch, j0 + (int)gs));
+                    if (!glv.groupsDone || glv.exchange) continue;
+                    float *slot = ctx->d_partials.p + (ctx->shardWorld > 1 ? 4 * n : 0) + (size_t)(glv.slot0 + (unsigned int)k * glv.slotStride) * 7u * n;
+                    launchFilmResolve(ctx, slot, slot + 3 * n, slot + 6 * n, nullptr, nullptr);
                 }
-                if (hasGl && glv.addCount) (void)addGroups(ctx, 0, glv.addCount);
-                return;
             }
-            timedLaunch(ctx, "k_film", Pf.n_pix, [&] {
-                if (hasGl) hipLaunchKernelGGL(k_film_groups, dim3((Pf.n_pix + 255) / 256), dim3(256), 0, st, Pf, sppBatch, glv.groupPasses * (unsigned int)ctx->sppPerPass,
-                                              ctx->d_partials.p + (ctx->shardWorld > 1 ? 4 * (size_t)ctx->nPixAll : 0), glv.slot0, glv.slotStride, ctx->nPixAll);
-                else hipLaunchKernelGGL(k_film, dim3((Pf.n_pix + 255) / 256), dim3(256), 0, st, Pf, sppBatch, ctx->d_image.p, ctx->d_sq.p, ctx->d_imageW.p,
-                                        ctx->d_film.p, ctx->d_filmW.p);
-            });
             if (hasGl && glv.addCount) (void)addGroups(ctx, 0, glv.addCount);
-        };
-        if (defer) ctx->stragPrev().film = film; else film();  // (launchStragglers made this batch's set the previous one)
-    }
+            return;
+        }
+        timedLaunch(ctx, "k_film", Pf.n_pix, [&] {
+            if (hasGl) hipLaunchKernelGGL(k_film_groups, dim3((Pf.n_pix + 255) / 256), dim3(256), 0, st, Pf, sppBatch, glv.groupPasses * (unsigned int)ctx->sppPerPass,
+                                          ctx->d_partials.p + (ctx->shardWorld > 1 ? 4 * (size_t)ctx->nPixAll : 0), glv.slot0, glv.slotStride, ctx->nPixAll);
+            else hipLaunchKernelGGL(k_film, dim3((Pf.n_pix + 255) / 256), dim3(256), 0, st, Pf, sppBatch, ctx->d_image.p, ctx->d_sq.p, ctx->d_imageW.p,
+                                    ctx->d_film.p, ctx->d_filmW.p);
+        });
+        if (hasGl && glv.addCount) (void)addGroups(ctx, 0, glv.addCount);
+    };
+    if (defer) ctx->stragPrev().film = film; else film();  // (launchStragglers made this batch's set the previous one)
+}
+
+
+// `batch` BlockedRenderProcesses (GP:1087-1106 / renderBlock GP:1587-1641) over all owned pixels in one set of launches.
+// adamRound: this batch is one round of the sampling-fraction optimiser.
+// A launch of whole groups of a final iteration's passes (include/ppg.h "Final iteration: groups of passes"): `batch` passes = groups of
+// groupPasses passes (the last one may be shorter; or a part of ONE group when groupPasses >= batch), the first starting at pass
+// firstPass of the render, consecutive groups of the launch stridePasses apart; group k accumulates into slot slot0 + k * slotStride.
+int renderBatch(ppg_ctx *ctx, int batch, bool adamRound, const GroupLaunch *gl = nullptr, bool last = true, const unsigned int *regionPixels = nullptr,
+                unsigned int regionCount = 0) {
+    Batch B{};
+    PathState &P = B.P;
+    P = ctx->paths;
+    if (regionPixels) { P.n_pix = regionCount; P.pixels = regionPixels; }  // a round over ONE group of blocks (include/ppg.h "Rounds by image region")
+    if (gl && gl->wholeFilm && ctx->shardWorld > 1) { P.n_pix = ctx->nPixAll; P.pixels = ctx->d_pixelsAll.p; }  // the whole film, not this rank's tiles
+    P.n_paths = (unsigned int)((size_t)P.n_pix * ctx->sppPerPass * (size_t)batch);
+    if (P.n_paths == 0 && !(adamRound && ctx->passHook)) return PPG_OK;
+    int rc = prepareBatch(ctx, B, batch, adamRound, gl, last);
+    if (!rc && P.n_paths > 0) rc = runWavefront(ctx, B);
+    if (!rc) rc = finishPaths(ctx, B);
+    if (!rc && adamRound) rc = optimiserRound(ctx, B);
+    if (rc) return rc;
+    if (P.n_paths > 0) filmOrDefer(ctx, B, batch, gl);
     HIP_CHECK(hipGetLastError());
     return PPG_OK;
 }
+
 
 // The passes of a FINAL iteration (spp budget), include/ppg.h "Final iteration: groups of passes": groups of ppg_final_group_passes(numPasses)
 // passes, each summed on its own (k_film_groups) and added to image / film in group order (k_add_groups).  One GPU renders them all, several
@@ -1745,7 +1754,7 @@ int renderFinalGroups(ppg_ctx *ctx, int numPasses) {
         unsigned int minePasses = 0;
         for (unsigned int g : mine) minePasses += passesOf(g);
         const size_t pixels = byRank || world == 1 ? n : (size_t)ctx->nPix;
-        if (ctx->tuneFinalHalves && ctx->maxDepth < 0 && ctx->tuneSplitDepth > 0 && !ctx->timer.enabled && !ctx->tuneNoOverlap && minePasses >= 2 && minePasses <= launchPasses &&
+        if (ctx->tuneFinalHalves && ctx->maxDepth < 0 && ctx->tuneSplitDepth > 0 && sideStreamsAllowed(ctx) && minePasses >= 2 && minePasses <= launchPasses &&
             pixels * (size_t)ctx->sppPerPass * (size_t)(minePasses / 2) >= ((size_t)1 << 21)) {
             launchPasses = (minePasses + 1) / 2;
             if (G < launchPasses) launchPasses = std::max(G, launchPasses / G * G);  // whole groups per launch
@@ -1902,7 +1911,7 @@ int renderPassesBody(ppg_ctx *ctx, int numPasses) {  // GP:1217-1286
     // what the last batch still owes ("Stragglers"); in a sharded render with rounds whose stragglers' records are deferred, the round of the
     // last stragglers' records is one more call of the round hook on EVERY rank (include/ppg.h "STRAGGLERS")
     {
-        const bool deferRounds = rounds && ctx->maxDepth < 0 && ctx->spatialFilter != SF_BOX && !(ctx->doNee && ctx->nee == NEE_KICKSTART);
+        const bool deferRounds = rounds && ctx->maxDepth < 0 && recordPositionsKnown(ctx->spatialFilter, ctx->doNee, ctx->nee);
         int rc = flushStragglers(ctx, deferRounds && ctx->passHook != nullptr);
         if (rc) return rc;
     }
