@@ -93,8 +93,17 @@ enum {
     PPG_BSDF_ROUGHPLASTIC = 9      /* roughplastic.cpp:330-501: rough dielectric coating (GGX / Beckmann, visible normals) over a diffuse base; the
                                       energy balance between the two comes from Mitsuba's precomputed rough-transmittance tables
                                       (data/microfacet/{ggx,beckmann}.dat, rtrans.h), handed over as the per-material slice `ppg_scene.rtrans[material.rtrans]` */
+    ,
+    /* The three lobes below run on the HIP library only (its sixth kernel family, csrc/ppg_device.h PPG_LOBES); the CPU oracle refuses them. */
+    PPG_BSDF_ROUGHDIFFUSE = 10,    /* roughdiffuse.cpp:128-252: Oren-Nayar, the full model or (PPG_MAT_FAST_APPROX) the qualitative one; sigma =
+                                      alpha / sqrt(2); cosine-hemisphere sampling, weight = eval / pdf; one-sided, smooth */
+    PPG_BSDF_DIFFTRANS = 11,       /* difftrans.cpp:76-116: ideal diffuse TRANSMITTER — a smooth transmissive BSDF, guided on both sides; the
+                                      cosine hemisphere on the side opposite wi, weight = transmittance; cannot be two-sided */
+    PPG_BSDF_PHONG = 12            /* phong.cpp:122-240: modified Phong, a glossy lobe pow(alpha, exponent) around the mirror direction plus a
+                                      diffuse one, chosen by specularSamplingWeight = sAvg / (dAvg + sAvg); weight = eval / pdf of the whole */
 };
-#define PPG_BSDF_LAST PPG_BSDF_ROUGHPLASTIC
+#define PPG_BSDF_LAST PPG_BSDF_ROUGHPLASTIC /* the last type the CPU oracle knows */
+#define PPG_BSDF_LAST_HIP PPG_BSDF_PHONG    /* the last type the HIP library knows */
 enum {
     PPG_MAT_TWOSIDED = 1,          /* wrap the (one-sided) BRDF in twosided.cpp:100-180, same BRDF on both sides */
     PPG_MAT_NONLINEAR = 2,         /* plastic: nonlinear = true (plastic.cpp:164) */
@@ -103,6 +112,8 @@ enum {
     PPG_MAT_MASK = 4               /* wrap the BSDF (outside a two-sided adapter, if any) in mask.cpp:108-214 with constant `opacity`: a
                                       smooth/null hybrid — its sampled pass-through is recorded for the sampling-fraction optimiser
                                       (GP:2047-2068) */
+    ,
+    PPG_MAT_FAST_APPROX = 16       /* roughdiffuse: useFastApprox = true (roughdiffuse.cpp:159-174); refused on every other type */
 };
 enum { PPG_WRAP_REPEAT = 0, PPG_WRAP_MIRROR = 1, PPG_WRAP_CLAMP = 2, PPG_WRAP_ZERO = 3, PPG_WRAP_ONE = 4 }; /* ReconstructionFilter::EBoundaryCondition, mipmap.h:503-560 */
 
@@ -123,10 +134,12 @@ typedef struct ppg_texture {
 
 typedef struct ppg_material {
     int32_t type;         /* PPG_BSDF_* */
-    float reflectance[3]; /* linear RGB (SPECTRUM_SAMPLES=3 build of the reference): diffuse `reflectance`; plastic
-                             `diffuseReflectance`; conductors and dielectric `specularReflectance` */
-    float specular[3];    /* plastic `specularReflectance`; dielectric / thindielectric `specularTransmittance` */
-    float alpha;          /* roughconductor / roughdielectric: roughness `alpha` (clamped to >= 1e-4 like microfacet.h:135) */
+    float reflectance[3]; /* linear RGB (SPECTRUM_SAMPLES=3 build of the reference): diffuse / roughdiffuse `reflectance`; plastic / phong
+                             `diffuseReflectance`; conductors and dielectric `specularReflectance`; difftrans `transmittance` */
+    float specular[3];    /* plastic / phong `specularReflectance`; dielectric / thindielectric `specularTransmittance` */
+    float alpha;          /* roughconductor / roughdielectric: roughness `alpha` (clamped to >= 1e-4 like microfacet.h:135);
+                             roughdiffuse: `alpha` (default 0.2; NOT clamped, 0 is legal); phong: `exponent` (default 30).  The last two
+                             must be finite and >= 0 */
     float eta[3];         /* conductors: eta per channel (already divided by extEta, roughconductor.cpp:185-186);
                              plastic / (rough / thin) dielectric: eta[0] = intIOR / extIOR */
     float k[3];           /* conductors: k per channel */
@@ -140,6 +153,12 @@ typedef struct ppg_material {
                              bits 16..31: 1 + index of the displacement texture of a `bumpmap` adapter around this BSDF (bumpmap.cpp:135-219:
                              shading frame perturbed by the texture's gradient); 0 = none */
 } ppg_material;           /* 80 bytes; bitmaps on specular / alpha / opacity: ppg_set_material_textures */
+/* roughdiffuse, difftrans and phong (HIP library only).  PPG_MAT_TWOSIDED (not on difftrans), PPG_MAT_MASK and both halves of `texture` apply
+   as they do to diffuse: bumpmap(mask(twosided(x))).  ppg_set_scene answers PPG_ERR_INVALID, names the material and leaves the context
+   usable for: PPG_MAT_TWOSIDED on difftrans (twosided.cpp:84-88 refuses transmissive BSDFs); a phong whose reflectance and specular both
+   have luminance 0 (specularSamplingWeight = 0 / 0); a negative or non-finite alpha / exponent; PPG_MAT_FAST_APPROX on another type; any slot
+   of ppg_set_material_textures but `opacity`; a general ppg_set_microfacet entry; a coat (ppg_set_coatings); their use as a child of a blend
+   or as the blended record (ppg_set_blends); and, as for every type, a bitmap on a material of a sphere, disk or cylinder. */
 
 typedef struct ppg_emitter {
     float radiance[3]; /* area light, mitsuba/src/emitters/area.cpp:104-109 */

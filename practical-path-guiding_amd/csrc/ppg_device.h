@@ -36,12 +36,14 @@
                              //           sampleVisible = false), with or without analytic shapes
 #define PPG_FAMILY_COAT 3    // _coat     the coating / roughcoating adapters (ppg_set_coatings), whatever else the scene holds
 #define PPG_FAMILY_BLEND 4   // _blend    the blendbsdf / mixturebsdf combinators (ppg_set_blends), whatever else the scene holds
-#define PPG_FAMILIES 5
+#define PPG_FAMILY_LOBES 5   // _lobes    the roughdiffuse, difftrans and phong BSDFs (PPG_BSDF_ROUGHDIFFUSE ..), whatever else the scene holds
+#define PPG_FAMILIES 6
 #define PPG_SUFFIX_0
 #define PPG_SUFFIX_1 _shapes
 #define PPG_SUFFIX_2 _ext
 #define PPG_SUFFIX_3 _coat
 #define PPG_SUFFIX_4 _blend
+#define PPG_SUFFIX_5 _lobes
 #ifndef PPG_FAMILY
 #define PPG_FAMILY 0  // (a digit: it is pasted to PPG_SUFFIX_)
 #endif
@@ -49,6 +51,7 @@
 #define PPG_MFD (PPG_FAMILY >= PPG_FAMILY_EXT)
 #define PPG_COAT (PPG_FAMILY >= PPG_FAMILY_COAT)
 #define PPG_BLEND (PPG_FAMILY >= PPG_FAMILY_BLEND)
+#define PPG_LOBES (PPG_FAMILY >= PPG_FAMILY_LOBES)
 #define PPG_CAT2(a, b) a##b
 #define PPG_CAT(a, b) PPG_CAT2(a, b)
 #define PPG_FAMILY_NAME(name) PPG_CAT(name, PPG_CAT(PPG_SUFFIX_, PPG_FAMILY))
@@ -219,6 +222,9 @@ struct DevScene {
     // numbers n_tris + n_spheres, ..
     const float4 *shapes;
     int n_shapes;
+    // a material is a roughdiffuse, difftrans or phong lobe: the scene runs the lobes kernels (PPG_LOBES), which alone compile them.  (It
+    // stands in the padding behind n_shapes: no other member and no kernel argument behind the scene moves.)
+    int lobes;
     // ppg_set_microfacet with a general entry (extended kernels only, PPG_MFD): one float4 per material = (alphaV, PPG_MFDF_* bits,
     // alphaV texture: 1 + index as bits, -); nullptr otherwise
     const float4 *mfd;
@@ -1668,14 +1674,23 @@ D bool mat_is_smooth(const Mat &M) {
     // a roughcoating's own component is glossy, a coating's is a delta: "nested smooth, or roughcoating"
     if (M.coat && (__float_as_uint(M.coat[0].w) & PPG_COATF_KIND) == 2u) return true;
 #endif
+#if PPG_LOBES
+    if (M.type == PPG_BSDF_ROUGHDIFFUSE || M.type == PPG_BSDF_DIFFTRANS || M.type == PPG_BSDF_PHONG) return true;
+#endif
     return M.type == PPG_BSDF_DIFFUSE || M.type == PPG_BSDF_ROUGHCONDUCTOR || M.type == PPG_BSDF_PLASTIC || M.type == PPG_BSDF_ROUGHDIELECTRIC ||
            M.type == PPG_BSDF_ROUGHPLASTIC;
 }
 D bool mat_two_sided(const Mat &M) {
+#if PPG_LOBES
+    if (M.type == PPG_BSDF_DIFFTRANS) return false;  // (a transmitter: ppg_set_scene refuses the flag on it)
+#endif
     return (M.flags & PPG_MAT_TWOSIDED) && M.type != PPG_BSDF_DIELECTRIC && M.type != PPG_BSDF_THINDIELECTRIC && M.type != PPG_BSDF_ROUGHDIELECTRIC;
 }
 D bool mat_masked(const Mat &M) { return (M.flags & PPG_MAT_MASK) != 0; }
 D bool mat_backside_or_transmission(const Mat &M) {
+#if PPG_LOBES
+    if (M.type == PPG_BSDF_DIFFTRANS) return true;  // (light on the far side of a diffuse transmitter must not be culled)
+#endif
     return (M.flags & (PPG_MAT_TWOSIDED | PPG_MAT_MASK)) || M.type == PPG_BSDF_DIELECTRIC || M.type == PPG_BSDF_THINDIELECTRIC ||
            M.type == PPG_BSDF_ROUGHDIELECTRIC;
 }
@@ -2102,6 +2117,111 @@ D F3 mat_eval_null(const Mat &M, float cosThetaI) {
     return M.spec * (1 - thin_R(M, cosThetaI));
 }
 
+#if PPG_LOBES
+// ------------------------------------------------------------------------------------------------
+// The lobes kernels (PPG_LOBES): roughdiffuse (roughdiffuse.cpp:128-252), difftrans (difftrans.cpp:76-116) and phong (phong.cpp:122-240),
+// each float operation in the plug-in's order.  Out of line (MFD_CALL), scalars in and out: shade_one<FULL> has no registers left for
+// inlined copies.  All three are smooth, never delta, never null, eta = 1, and draw nothing from the path's sampler.
+// ------------------------------------------------------------------------------------------------
+D float frame_sin_theta(F3 v) {  // Frame::sinTheta, frame.h:107-118
+    const float temp = 1.0f - v.z * v.z;
+    if (temp <= 0.0f) return 0.0f;
+    return __builtin_sqrtf(temp);
+}
+D float clamp_unit(float v) { return v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v); }  // math::clamp(v, -1, 1)
+// std::pow where exp(y log x) has no answer: pow(x, 0) = 1 — a phong exponent of 0 —, pow(0, y > 0) = 0 — sample.y = 0 —; x >= 0 always
+D float lobe_pow(float x, float y) {
+    if (y == 0.0f) return 1.0f;
+    if (x == 0.0f) return 0.0f;
+    return dm_pow(x, y);
+}
+MFD_CALL F3 roughdiffuse_eval(F3 rho, float alpha, bool fast, F3 wi, F3 wo) {  // roughdiffuse.cpp:128-218
+    if (wi.z <= 0 || wo.z <= 0) return f3s(0.0f);
+    const float conversionFactor = 1 / __builtin_sqrtf(2.0f);
+    const float sigma = alpha * conversionFactor;
+    const float sigma2 = sigma * sigma;
+    const float sinThetaI = frame_sin_theta(wi), sinThetaO = frame_sin_theta(wo);
+    float cosPhiDiff = 0;
+    if (sinThetaI > PPG_EPSILON && sinThetaO > PPG_EPSILON) {  // Frame::sinPhi / cosPhi, frame.h:140-154
+        const float sinPhiI = clamp_unit(wi.y / sinThetaI), cosPhiI = clamp_unit(wi.x / sinThetaI);
+        const float sinPhiO = clamp_unit(wo.y / sinThetaO), cosPhiO = clamp_unit(wo.x / sinThetaO);
+        cosPhiDiff = cosPhiI * cosPhiO + sinPhiI * sinPhiO;
+    }
+    if (fast) {
+        const float A = 1.0f - 0.5f * sigma2 / (sigma2 + 0.33f), B = 0.45f * sigma2 / (sigma2 + 0.09f);
+        float sinAlpha, tanBeta;
+        if (wi.z > wo.z) { sinAlpha = sinThetaO; tanBeta = sinThetaI / wi.z; }
+        else { sinAlpha = sinThetaI; tanBeta = sinThetaO / wo.z; }
+        return rho * (PPG_INV_PI_F * wo.z * (A + B * ppg_max(cosPhiDiff, 0.0f) * sinAlpha * tanBeta));
+    }
+    const float thetaI = dm_acos(wi.z), thetaO = dm_acos(wo.z);
+    const float alphaA = ppg_max(thetaI, thetaO), beta = ppg_min(thetaI, thetaO);
+    float sinAlpha, sinBeta, tanBeta;
+    if (wi.z > wo.z) { sinAlpha = sinThetaO; sinBeta = sinThetaI; tanBeta = sinThetaI / wi.z; }
+    else { sinAlpha = sinThetaI; sinBeta = sinThetaO; tanBeta = sinThetaO / wo.z; }
+    const float tmp = sigma2 / (sigma2 + 0.09f), tmp2 = (4 * PPG_INV_PI_F * PPG_INV_PI_F) * alphaA * beta, tmp3 = 2 * beta * PPG_INV_PI_F;
+    const float C1 = 1.0f - 0.5f * sigma2 / (sigma2 + 0.33f);
+    float C2 = 0.45f * tmp;
+    const float C3 = 0.125f * tmp * tmp2 * tmp2, C4 = 0.17f * sigma2 / (sigma2 + 0.13f);
+    if (cosPhiDiff > 0) C2 *= sinAlpha;
+    else C2 *= sinAlpha - tmp3 * tmp3 * tmp3;
+    const float tanHalf = (sinAlpha + sinBeta) / (__builtin_sqrtf(ppg_max(0.0f, 1.0f - sinAlpha * sinAlpha)) + __builtin_sqrtf(ppg_max(0.0f, 1.0f - sinBeta * sinBeta)));
+    const F3 snglScat = rho * (C1 + cosPhiDiff * C2 * tanBeta + (1.0f - ppg_abs(cosPhiDiff)) * C3 * tanHalf);
+    const F3 dblScat = mul3(rho, rho) * (C4 * (1.0f - cosPhiDiff * tmp3 * tmp3));
+    return (snglScat + dblScat) * (PPG_INV_PI_F * wo.z);
+}
+// m_specularSamplingWeight (phong.cpp:97-99), from the luminances of the RECORD's values, as plastic_prob_specular takes them
+D float phong_weight(const Mat &M) {
+    const float dAvg = M.refl_lum, sAvg = mat_spec_lum(M);
+    return sAvg / (dAvg + sAvg);
+}
+MFD_CALL F3 phong_eval(F3 diff, F3 spec, float exponent, F3 wi, F3 wo) {  // phong.cpp:122-147
+    if (wi.z <= 0 || wo.z <= 0) return f3s(0.0f);
+    F3 result = f3s(0.0f);
+    const float alpha = dot3(wo, f3(-wi.x, -wi.y, wi.z));
+    if (alpha > 0.0f) result = result + spec * ((exponent + 2) * 0.15915494309189533577f * lobe_pow(alpha, exponent));
+    result = result + diff * PPG_INV_PI_F;
+    return result * wo.z;
+}
+MFD_CALL float phong_pdf(float weight, float exponent, F3 wi, F3 wo) {  // phong.cpp:149-181
+    if (wi.z <= 0 || wo.z <= 0) return 0.0f;
+    const float diffuseProb = PPG_INV_PI_F * wo.z;
+    float specProb = 0.0f;
+    const float alpha = dot3(wo, f3(-wi.x, -wi.y, wi.z));
+    if (alpha > 0) specProb = lobe_pow(alpha, exponent) * (exponent + 1.0f) / (2.0f * PPG_PI_F);
+    return weight * specProb + (1 - weight) * diffuseProb;
+}
+// the direction of phong.cpp:183-231 (.w = 0: the rotated lobe direction lies below the surface)
+MFD_CALL float4 phong_sample_dir(float weight, float exponent, F3 wi, float sx, float sy) {
+    F3 wo;
+    if (sx <= weight) {
+        sx /= weight;
+        const F3 n = f3(-wi.x, -wi.y, wi.z);
+        const float sinAlpha = __builtin_sqrtf(ppg_max(0.0f, 1 - lobe_pow(sy, 2 / (exponent + 1))));
+        const float cosAlpha = lobe_pow(sy, 1 / (exponent + 1));
+        const float phi = (2.0f * PPG_PI_F) * sx;
+        float sinPhi, cosPhi;
+        dm_sincos(phi, &sinPhi, &cosPhi);
+        const F3 l = f3(sinAlpha * cosPhi, sinAlpha * sinPhi, cosAlpha);
+        F3 tF;  // Frame(R): coordinateSystem, util.cpp:592-601
+        if (ppg_abs(n.x) > ppg_abs(n.y)) {
+            const float invLen = 1.0f / __builtin_sqrtf(n.x * n.x + n.z * n.z);
+            tF = f3(n.z * invLen, 0.0f, -n.x * invLen);
+        } else {
+            const float invLen = 1.0f / __builtin_sqrtf(n.y * n.y + n.z * n.z);
+            tF = f3(0.0f, n.z * invLen, -n.y * invLen);
+        }
+        const F3 sF = cross3(tF, n);
+        wo = sF * l.x + tF * l.y + n * l.z;
+        if (wo.z <= 0) return make_float4(wo.x, wo.y, wo.z, 0.0f);
+    } else {
+        sx = (sx - weight) / (1 - weight);
+        wo = cosine_hemisphere(sx, sy);
+    }
+    return make_float4(wo.x, wo.y, wo.z, 1.0f);
+}
+#endif
+
 // one-sided plugins, solid-angle measure
 D F3 mat_eval_one(const Mat &M, F3 wi, F3 wo) {
     if (M.type == PPG_BSDF_DIFFUSE) return diffuse_eval(M.refl, wi, wo);
@@ -2162,6 +2282,14 @@ D F3 mat_eval_one(const Mat &M, F3 wi, F3 wo) {
         const float invEta2 = 1 / (M.eta.x * M.eta.x);
         return plastic_diff_term(M) * ((PPG_INV_PI_F * wo.z) * invEta2 * (1 - Fi) * (1 - Fo));
     }
+#if PPG_LOBES
+    if (M.type == PPG_BSDF_ROUGHDIFFUSE) return roughdiffuse_eval(M.refl, M.alpha, (M.flags & PPG_MAT_FAST_APPROX) != 0, wi, wo);
+    if (M.type == PPG_BSDF_DIFFTRANS) {  // difftrans.cpp:76-83
+        if (wi.z * wo.z >= 0) return f3s(0.0f);
+        return M.refl * (PPG_INV_PI_F * ppg_abs(wo.z));
+    }
+    if (M.type == PPG_BSDF_PHONG) return phong_eval(M.refl, M.spec, M.alpha, wi, wo);
+#endif
     return f3s(0.0f);
 }
 D float mat_pdf_one(const Mat &M, F3 wi, F3 wo) {
@@ -2222,6 +2350,14 @@ D float mat_pdf_one(const Mat &M, F3 wi, F3 wo) {
         float Fi = fresnel_dielectric_ext(wi.z, M.eta.x);
         return (PPG_INV_PI_F * wo.z) * (1 - plastic_prob_specular(M, Fi));
     }
+#if PPG_LOBES
+    if (M.type == PPG_BSDF_ROUGHDIFFUSE) return diffuse_pdf(wi, wo);  // roughdiffuse.cpp:220-227
+    if (M.type == PPG_BSDF_DIFFTRANS) {  // difftrans.cpp:85-91
+        if (wi.z * wo.z >= 0) return 0.0f;
+        return ppg_abs(wo.z) * PPG_INV_PI_F;
+    }
+    if (M.type == PPG_BSDF_PHONG) return phong_pdf(phong_weight(M), M.alpha, wi, wo);
+#endif
     return 0.0f;
 }
 #if PPG_COAT
@@ -2394,6 +2530,28 @@ D F3 mat_sample_one(const Mat &M, F3 wi, float sx, float sy, F3 &wo, float &pdf,
             pdf = 1 - Rr;
             return M.spec;
         }
+#if PPG_LOBES
+        case PPG_BSDF_ROUGHDIFFUSE:  // roughdiffuse.cpp:241-251
+            if (wi.z <= 0) return f3s(0.0f);
+            wo = cosine_hemisphere(sx, sy);
+            pdf = PPG_INV_PI_F * wo.z;
+            return div3(roughdiffuse_eval(M.refl, M.alpha, (M.flags & PPG_MAT_FAST_APPROX) != 0, wi, wo), pdf);
+        case PPG_BSDF_DIFFTRANS:  // difftrans.cpp:105-116: the hemisphere opposite wi, weight = the transmittance
+            wo = cosine_hemisphere(sx, sy);
+            if (wi.z > 0) wo.z *= -1;
+            pdf = ppg_abs(wo.z) * PPG_INV_PI_F;
+            return M.refl;
+        case PPG_BSDF_PHONG: {  // phong.cpp:183-240
+            if (wi.z <= 0) return f3s(0.0f);  // (its pdf() is 0 there)
+            const float w = phong_weight(M);
+            const float4 sd = phong_sample_dir(w, M.alpha, wi, sx, sy);
+            wo = f3(sd.x, sd.y, sd.z);
+            if (sd.w == 0.0f) return f3s(0.0f);
+            pdf = phong_pdf(w, M.alpha, wi, wo);
+            if (pdf == 0) return f3s(0.0f);
+            return div3(phong_eval(M.refl, M.spec, M.alpha, wi, wo), pdf);
+        }
+#endif
     }
     return f3s(0.0f);
 }

@@ -546,6 +546,7 @@ PathKernels ppg_path_kernels[PPG_FAMILIES];  // filled by the units of ppg_inst.
 
 // The kernel family a scene runs: the lowest that has everything the scene needs (ppg_device.h).
 static int sceneFamily(const DevScene &S) {
+    if (S.lobes) return PPG_FAMILY_LOBES;      // a roughdiffuse, difftrans or phong material: the lobes family, whatever else the scene holds
     if (S.blend) return PPG_FAMILY_BLEND;      // a blended material: the blend family, whatever else the scene holds
     if (S.coat) return PPG_FAMILY_COAT;        // a coated material: the coat family, shapes and general entries or not
     if (S.mfd) return PPG_FAMILY_EXT;          // a general microfacet entry: the extended family, shapes or not

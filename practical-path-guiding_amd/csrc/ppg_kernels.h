@@ -487,6 +487,9 @@ D void sort_slice(const SortArgs &a, const Work &work, unsigned int b, unsigned 
                     const bool general = sort_side_table(a, m);
                     if ((flags & PPG_MAT_MASK) || (tex >> 16) || slots || general) key = 13u;
                     else if (mset_common_type(type)) key = type == PPG_BSDF_ROUGHPLASTIC ? 6u : (unsigned int)type;  // 0..6
+#if PPG_LOBES
+                    else if (type >= PPG_BSDF_ROUGHDIFFUSE) key = type == PPG_BSDF_DIFFTRANS ? 12u : 9u;  // roughdiffuse and phong 9, difftrans 12
+#endif
                     else key = 8u + ((unsigned int)type & 3u);  // dielectric 10, thin dielectric 11, rough dielectric 8
                 }
             }

@@ -767,7 +767,7 @@ struct SceneBuilder {
         const bool named = !who.empty();
         if (material >= s->n_materials) return refuse(named ? who + "material index out of range" : "index out of range");
         if (emitter >= (int32_t)s->n_emitters) return refuse(named ? who + "emitter index out of range" : "index out of range");
-        if (s->materials[material].type < 0 || s->materials[material].type > PPG_BSDF_LAST) return refuse(who + "unsupported BSDF type");
+        if (s->materials[material].type < 0 || s->materials[material].type > PPG_BSDF_LAST_HIP) return refuse(who + "unsupported BSDF type");
         return PPG_OK;
     }
     // a per-material side list is empty or has one entry per material
@@ -941,6 +941,24 @@ int SceneBuilder::materials() {
             if (!(m.eta[0] > 0)) return refuse("plastic / dielectric need eta[0] = intIOR / extIOR > 0");
             fdrInt = 1 - s->rtrans[(size_t)m.rtrans * (s->rtrans_samples + 1) + s->rtrans_samples];
         } else m.rtrans = 0;
+        {   // roughdiffuse, difftrans and phong: the lobes kernels (ppg_device.h PPG_LOBES)
+            const std::string who = "material " + std::to_string(i) + ": ";
+            const bool lobe = m.type == PPG_BSDF_ROUGHDIFFUSE || m.type == PPG_BSDF_DIFFTRANS || m.type == PPG_BSDF_PHONG;
+            if ((m.flags & PPG_MAT_FAST_APPROX) && m.type != PPG_BSDF_ROUGHDIFFUSE) return refuse(who + "PPG_MAT_FAST_APPROX (useFastApprox) is a flag of roughdiffuse only");
+            if (m.type == PPG_BSDF_DIFFTRANS && (m.flags & PPG_MAT_TWOSIDED))
+                return refuse(who + "difftrans cannot be two-sided: only BRDFs can be (twosided.cpp:84-88)");
+            if (m.type == PPG_BSDF_ROUGHDIFFUSE && !(std::isfinite(m.alpha) && m.alpha >= 0)) return refuse(who + "roughdiffuse: alpha must be finite and not negative");
+            if (m.type == PPG_BSDF_PHONG) {
+                if (!(std::isfinite(m.alpha) && m.alpha >= 0)) return refuse(who + "phong: exponent must be finite and not negative");
+                const float dAvg = m.reflectance[0] * 0.212671f + m.reflectance[1] * 0.715160f + m.reflectance[2] * 0.072169f;
+                const float sAvg = m.specular[0] * 0.212671f + m.specular[1] * 0.715160f + m.specular[2] * 0.072169f;
+                if (dAvg == 0 && sAvg == 0)
+                    return refuse(who + "phong: diffuseReflectance and specularReflectance both have luminance 0 (specularSamplingWeight would be 0 / 0)");
+            }
+            if (lobe && (mt.specular || mt.alpha))
+                return refuse(who + "texture slot " + (mt.specular ? "specular" : "alpha") + ": roughdiffuse, difftrans and phong read no bitmap but `reflectance` and `opacity`");
+            if (lobe) H.scene.lobes = 1;
+        }
         if (m.type > PPG_BSDF_MIRROR || m.flags != 0) H.fullMaterials = true;
         if (m.type == PPG_BSDF_THINDIELECTRIC || (m.flags & PPG_MAT_MASK)) hasNull = true;
         mats[PPG_MAT_STRIDE * i + 0] = make_float4(m.reflectance[0], m.reflectance[1], m.reflectance[2], (float)m.type);
@@ -1046,7 +1064,9 @@ int SceneBuilder::coatings() {
             if (c.kind == 0) continue;
             if (c.kind != 1 && c.kind != 2) return refuse(who + "kind must be 0 (none), 1 (coating) or 2 (roughcoating)");
             const char *name = c.kind == 1 ? "coating" : "roughcoating";
-            if (m.type == PPG_BSDF_DIELECTRIC || m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_ROUGHDIELECTRIC || m.type < 0 || m.type > PPG_BSDF_LAST)
+            if (m.type == PPG_BSDF_ROUGHDIFFUSE || m.type == PPG_BSDF_DIFFTRANS || m.type == PPG_BSDF_PHONG)
+                return refuse(who + name + " over roughdiffuse, difftrans or phong is not supported");
+            if (m.type == PPG_BSDF_DIELECTRIC || m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_ROUGHDIELECTRIC || m.type < 0 || m.type > PPG_BSDF_LAST_HIP)
                 return refuse(who + name + " over dielectric, thindielectric or roughdielectric is not supported");
             if (c.kind == 2 && (m.type == PPG_BSDF_MIRROR || m.type == PPG_BSDF_CONDUCTOR || m.type == PPG_BSDF_PLASTIC))
                 return refuse(who + "roughcoating over a BSDF with a delta component (conductor, plastic) is not supported");
@@ -1116,7 +1136,9 @@ int SceneBuilder::blends() {
                 const ppg_material &cm = s->materials[c];
                 if (in.blends[c].kind) return refuse(kid + " is itself blended: blends of blends are not supported");
                 if (!in.coatings.empty() && in.coatings[c].kind) return refuse(kid + " is coated: coated children are not supported");
-                if (cm.type == PPG_BSDF_DIELECTRIC || cm.type == PPG_BSDF_THINDIELECTRIC || cm.type == PPG_BSDF_ROUGHDIELECTRIC || cm.type < 0 || cm.type > PPG_BSDF_LAST)
+                if (cm.type == PPG_BSDF_ROUGHDIFFUSE || cm.type == PPG_BSDF_DIFFTRANS || cm.type == PPG_BSDF_PHONG)
+                    return refuse(kid + ": roughdiffuse, difftrans and phong children are not supported");
+                if (cm.type == PPG_BSDF_DIELECTRIC || cm.type == PPG_BSDF_THINDIELECTRIC || cm.type == PPG_BSDF_ROUGHDIELECTRIC || cm.type < 0 || cm.type > PPG_BSDF_LAST_HIP)
                     return refuse(kid + ": dielectric, thindielectric and roughdielectric children are not supported");
                 if ((cm.flags & (PPG_MAT_TWOSIDED | PPG_MAT_MASK)) || cm.type == PPG_BSDF_TWOSIDED_DIFFUSE || (cm.texture >> 16))
                     return refuse(kid + " is masked, two-sided or bump-mapped: the adapters go around the blend, on its own record");

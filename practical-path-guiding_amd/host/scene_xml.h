@@ -1592,6 +1592,8 @@ private:
             if (isCoated) throw std::runtime_error(t + "(" + it + "): coated children are not supported");
             if (m.type == PPG_BSDF_DIELECTRIC || m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_ROUGHDIELECTRIC)
                 throw std::runtime_error(t + "(" + it + "): dielectric, thindielectric and roughdielectric children are not supported");
+            if (m.type == PPG_BSDF_ROUGHDIFFUSE || m.type == PPG_BSDF_DIFFTRANS || m.type == PPG_BSDF_PHONG)
+                throw std::runtime_error(t + "(" + it + "): roughdiffuse, difftrans and phong children are not supported");
             if (m.type == PPG_BSDF_TWOSIDED_DIFFUSE || (m.flags & (PPG_MAT_TWOSIDED | PPG_MAT_MASK)) || (m.texture >> 16))
                 throw std::runtime_error(t + "(" + it + ") is not supported: the nesting order is bumpmap(mask(twosided(" + t + "(..))))");
             spec.kids.push_back(m);
@@ -1664,6 +1666,8 @@ private:
         ppg_material m = makeBsdf(*in[0], false, out);
         if (m.type == PPG_BSDF_DIELECTRIC || m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_ROUGHDIELECTRIC)
             throw std::runtime_error(t + "(" + it + "): a coat on dielectric, thindielectric or roughdielectric is not supported");
+        if (m.type == PPG_BSDF_ROUGHDIFFUSE || m.type == PPG_BSDF_DIFFTRANS || m.type == PPG_BSDF_PHONG)
+            throw std::runtime_error(t + "(" + it + "): a coat on roughdiffuse, difftrans or phong is not supported");
         if (t == "roughcoating" && (m.type == PPG_BSDF_MIRROR || m.type == PPG_BSDF_CONDUCTOR || m.type == PPG_BSDF_PLASTIC))
             throw std::runtime_error("roughcoating(" + it + "): a roughcoating over a BSDF with a delta component (conductor, plastic) is not supported");
         const double intIOR = lookupIOR(p, "intIOR", "bk7"), extIOR = lookupIOR(p, "extIOR", "air");
@@ -1707,6 +1711,58 @@ private:
         m_coat = c;
         return m;
     }
+    // roughdiffuse (roughdiffuse.cpp:88-122), difftrans (difftrans.cpp:49-74) and phong (phong.cpp:60-107) with Mitsuba's parameter names and
+    // defaults, then BSDF::ensureEnergyConservation (bsdf.cpp:88-146) as their configure() calls it: the same rules and the same float
+    // arithmetic as ppg_host/mitsuba_xml.py.  This loader reads no parameter bitmaps.
+    ppg_material lobe(const XmlNode &e, std::map<std::string, std::string> &p, const std::string &t, LoadedScene &out) const {
+        ppg_material m{};
+        auto textured = [&](const std::string &name) {
+            for (auto &c : e.children) if ((c.tag == "texture" || c.tag == "ref") && c.get("name") == name) return true;
+            return false;
+        };
+        auto number = [&](const std::string &name, float dflt) {
+            if (textured(name)) {
+                if (m_strict) throw std::runtime_error(t + ": a texture on '" + name + "' is not supported (a bitmap on its reflectance is)");
+                m_lenientNotes.push_back("texture on '" + name + "' ignored: the plug-in's default value is used");
+                return dflt;
+            }
+            return p.count(name) ? std::stof(p[name]) : dflt;
+        };
+        float *pair[2] = {m.reflectance, nullptr};
+        std::string names = "\"reflectance\"";
+        if (t == "roughdiffuse") {
+            m.type = PPG_BSDF_ROUGHDIFFUSE; defaults(m);
+            m.alpha = number("alpha", 0.2f);
+            colour(e, hasChildNamed(e, "reflectance") || !hasChildNamed(e, "diffuseReflectance") ? "reflectance" : "diffuseReflectance", 0.5f, m.reflectance);
+            if (flag(p, "useFastApprox", false)) m.flags |= PPG_MAT_FAST_APPROX;
+        } else if (t == "difftrans") {
+            m.type = PPG_BSDF_DIFFTRANS; defaults(m);
+            colour(e, hasChildNamed(e, "transmittance") || !hasChildNamed(e, "diffuseTransmittance") ? "transmittance" : "diffuseTransmittance", 0.5f, m.reflectance);
+            names = "\"transmittance\"";
+        } else {
+            m.type = PPG_BSDF_PHONG; defaults(m);
+            if (m_strict && textured("specularReflectance"))
+                throw std::runtime_error("phong: a texture on 'specularReflectance' is not supported (a bitmap on its diffuseReflectance is)");
+            m.alpha = number("exponent", 30.0f);
+            colour(e, "specularReflectance", 0.2f, m.specular);
+            colour(e, "diffuseReflectance", 0.5f, m.reflectance);
+            pair[0] = m.specular; pair[1] = m.reflectance;
+            names = "\"specularReflectance\" and \"diffuseReflectance\"";
+        }
+        if (flag(p, "ensureEnergyConservation", true)) {
+            float actual = 0.0f;
+            for (int k = 0; k < 3; ++k) actual = std::max(actual, 0.0f + pair[0][k] + (pair[1] ? pair[1][k] : 0.0f));
+            if (actual > 1) {
+                const float scale = 0.99f * (1.0f / actual);
+                std::ostringstream w;
+                w << "bsdf '" << t << "' violates energy conservation: " << names << (pair[1] ? " sum to" : " has") << " a component-wise maximum of " << actual
+                  << " (> 1) and will be scaled by " << scale << " (ensureEnergyConservation=false prevents this)";
+                out.warnings.push_back(w.str());
+                for (int k = 0; k < 3; ++k) { pair[0][k] *= scale; if (pair[1]) pair[1][k] *= scale; }
+            }
+        }
+        return m;
+    }
     ppg_material makeBsdf(const XmlNode &e, bool allowWrap, LoadedScene &out) const {
         std::string t = e.get("type");
         auto p = props(e);
@@ -1718,6 +1774,7 @@ private:
             if (in.size() == 1) {
                 m = makeBsdf(*in[0], false, out);
                 if (m.type == PPG_BSDF_DIELECTRIC || m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_ROUGHDIELECTRIC) throw std::runtime_error("twosided(dielectric): only BRDFs can be two-sided (twosided.cpp:84-88)");
+                if (m.type == PPG_BSDF_DIFFTRANS) throw std::runtime_error("twosided(difftrans): only BRDFs can be two-sided (twosided.cpp:84-88)");
                 if (m.type == PPG_BSDF_DIFFUSE && !(m.flags & PPG_MAT_MASK) && !m_blend.b.kind) { m.type = PPG_BSDF_TWOSIDED_DIFFUSE; return m; }
                 m.flags |= PPG_MAT_TWOSIDED;
                 return m;
@@ -1792,6 +1849,7 @@ private:
             }
             return m;
         }
+        if (t == "roughdiffuse" || t == "difftrans" || t == "phong") return lobe(e, p, t, out);
         if (t == "coating" || t == "roughcoating") {  // SmoothCoating (coating.cpp:109-200), RoughCoating (roughcoating.cpp:114-227): the innermost adapter
             auto in = inner();
             try { return coated(e, p, t, in, out); }
@@ -1819,7 +1877,7 @@ private:
             auto in = inner();
             if (in.size() == 1) { out.warnings.push_back("bsdf '" + t + "' dropped around its nested bsdf"); return makeBsdf(*in[0], allowWrap, out); }
         }
-        if (m_strict) throw std::runtime_error("bsdf type '" + t + "' is not supported yet (diffuse, conductor, roughconductor, plastic, roughplastic, dielectric, thindielectric, roughdielectric, mask, twosided; SURVEY.md §8 f1)");
+        if (m_strict) throw std::runtime_error("bsdf type '" + t + "' is not supported yet (diffuse, roughdiffuse, difftrans, phong, conductor, roughconductor, plastic, roughplastic, dielectric, thindielectric, roughdielectric, mask, twosided; SURVEY.md §8 f1)");
         out.warnings.push_back("bsdf '" + t + "' replaced by diffuse(0.5)");
         m = ppg_material{}; m.type = PPG_BSDF_DIFFUSE; defaults(m);
         m.reflectance[0] = m.reflectance[1] = m.reflectance[2] = 0.5f;

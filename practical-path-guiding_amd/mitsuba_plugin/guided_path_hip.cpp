@@ -156,7 +156,8 @@ private:
         if (!ok) {
             /* A flat plug-in without an id: its Properties are the parameters the scene file gave it.  They are handed to the scene loader's own
                <bsdf> handling as the element they came from (ppg::xml::bsdfFromProperties) — one code path for every plug-in the HIP path
-               knows (diffuse, conductor, roughconductor, plastic, roughplastic, dielectric, thindielectric, roughdielectric), named materials,
+               knows (diffuse, roughdiffuse with alpha / useFastApprox, difftrans, phong with exponent, conductor, roughconductor, plastic,
+               roughplastic, dielectric, thindielectric, roughdielectric), ensureEnergyConservation, named materials,
                IOR names and rough-transmittance slices included.  Spectra arrive as linear RGB (this is an RGB build of Mitsuba). */
             std::vector<ppg::xml::BsdfParam> params;
             std::vector<std::string> names;

@@ -65,12 +65,16 @@ class Material(C.Structure):
     specular, alpha, eta (3 values, or one number for plastic / dielectric), k, twosided, nonlinear, opacity (a mask adapter), distribution ("ggx" | "beckmann"), rtrans (roughplastic: row of SceneDesc.rtrans).
     The rest of the microfacet model travels beside it (Microfacet): alpha_v, distribution = "phong", sample_visible; so does a coating /
     roughcoating adapter around the BSDF (Coating): coating = dict(kind, eta, ...), and a blendbsdf / mixturebsdf of other materials (Blend):
-    blend = dict(kind, children, ...)."""
+    blend = dict(kind, children, ...).
+    roughdiffuse: reflectance, alpha (0.2), fast_approx; difftrans: reflectance (its transmittance); phong: reflectance (diffuse), specular (0.2),
+    exponent (30) — the HIP library only."""
     _fields_ = [("type", C.c_int32), ("reflectance", C.c_float * 3), ("specular", C.c_float * 3), ("alpha", C.c_float),
                 ("eta", C.c_float * 3), ("k", C.c_float * 3), ("flags", C.c_int32), ("rtrans", C.c_int32),
                 ("opacity", C.c_float * 3), ("texture", C.c_uint32)]
 
-    BSDF = dict(diffuse=0, twosided_diffuse=1, mirror=2, conductor=3, roughconductor=4, plastic=5, dielectric=6, thindielectric=7, roughdielectric=8, roughplastic=9)
+    BSDF = dict(diffuse=0, twosided_diffuse=1, mirror=2, conductor=3, roughconductor=4, plastic=5, dielectric=6, thindielectric=7, roughdielectric=8, roughplastic=9,
+                roughdiffuse=10, difftrans=11, phong=12)
+    LOBES = (10, 11, 12)  # the types only the HIP library knows
 
     @classmethod
     def from_dict(cls, m):
@@ -81,13 +85,15 @@ class Material(C.Structure):
         o = cls()
         t = m.get("type", 0)
         o.type = cls.BSDF[t] if isinstance(t, str) else int(t)
-        o.reflectance[:] = three(m.get("reflectance"), 0.5 if o.type in (0, 1, 5, 9) else 1.0)
-        o.specular[:] = three(m.get("specular"), 1.0)
-        o.alpha = float(m.get("alpha", 0.1))
+        o.reflectance[:] = three(m.get("reflectance"), 0.5 if o.type in (0, 1, 5, 9, 10, 11, 12) else 1.0)
+        o.specular[:] = three(m.get("specular"), 0.2 if o.type == 12 else 1.0)
+        o.alpha = float(m.get("alpha", 0.2 if o.type == 10 else 0.1))
+        if o.type == 12:  # phong: the record's alpha carries the exponent
+            o.alpha = float(m.get("exponent", m.get("alpha", 30.0)))
         o.eta[:] = three(m.get("eta"), 0.0 if o.type in (2, 3, 4) else 1.5046)  # dielectric / plastic default: bk7 / polypropylene-ish
         o.k[:] = three(m.get("k"), 1.0)
         o.flags = ((1 if m.get("twosided") else 0) | (2 if m.get("nonlinear") else 0) | (4 if m.get("opacity") is not None else 0)
-                   | (8 if m.get("distribution", "ggx") == "beckmann" else 0))
+                   | (8 if m.get("distribution", "ggx") == "beckmann" else 0) | (16 if m.get("fast_approx") else 0))
         o.opacity[:] = three(m.get("opacity"), 0.0)
         o.rtrans = int(m.get("rtrans", 0))
         # texture: index into SceneDesc.textures of the bitmap on the diffuse reflectance; bump: of a bumpmap adapter's displacement texture
@@ -617,6 +623,8 @@ class Engine:
             import copy
             desc = copy.copy(desc)
             desc.materials = expand_blends(desc.materials)
+        if self.prefix != "ppg_" and any(Material.from_dict(m).type in Material.LOBES for m in desc.materials):
+            raise NotImplementedError("%s: roughdiffuse, difftrans and phong are not implemented here" % self.prefix)
         s = Scene()
         pos = np.ascontiguousarray(desc.positions, np.float32)
         idx = np.ascontiguousarray(desc.indices, np.uint32)

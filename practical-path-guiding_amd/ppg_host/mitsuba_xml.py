@@ -1101,6 +1101,8 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 m = make_bsdf(inner[0], allow_twosided=False)
                 if m["type"] in (6, 7, 8):
                     raise SceneError("twosided(dielectric): only BRDFs can be two-sided (twosided.cpp:84-88)")
+                if m["type"] == 11:
+                    raise SceneError("twosided(difftrans): only BRDFs can be two-sided (twosided.cpp:84-88)")
                 if m["type"] == 0 and not m.get("_substituted") and "blend" not in m:
                     return dict({k: v for k, v in m.items() if k in TEXTURE_KEYS + ("coating",)}, type=1, reflectance=m["reflectance"])
                 return dict(m, twosided=True)  # (a blended material's own record stays diffuse + two-sided: it only carries the adapters)
@@ -1160,6 +1162,8 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             if int_ior < 0 or ext_ior < 0 or int_ior == ext_ior:
                 raise SceneError("roughdielectric: the interior and exterior indices of refraction must be positive and differ")
             return microfacet(elem, p, specular(textured(dict(type=8, eta=float(f32(int_ior / ext_ior))), "specularReflectance", 1.0), "specularTransmittance"), t)
+        elif t in ("roughdiffuse", "difftrans", "phong"):  # roughdiffuse.cpp:88-122, difftrans.cpp:49-74, phong.cpp:60-107
+            return lobe(elem, p, t, textured)
         if t in ("coating", "roughcoating"):  # SmoothCoating (coating.cpp:109-200), RoughCoating (roughcoating.cpp:114-227): the innermost adapter
             inner = [c for c in elem if c.tag == "bsdf"]
             try:
@@ -1200,11 +1204,63 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 warnings.append("bsdf %r dropped around its nested bsdf" % t)
                 return make_bsdf(inner[0], allow_twosided)
         if strict:
-            raise SceneError("bsdf type %r is not supported yet (diffuse, conductor, roughconductor, plastic, roughplastic, dielectric, thindielectric, roughdielectric, "
-                             "mask(...), twosided(...); "
+            raise SceneError("bsdf type %r is not supported yet (diffuse, roughdiffuse, difftrans, phong, conductor, roughconductor, plastic, roughplastic, dielectric, "
+                             "thindielectric, roughdielectric, mask(...), twosided(...); "
                              "SURVEY.md §8 f1)" % t)
         warnings.append("bsdf %r replaced by diffuse(0.5)" % t)
         return dict(type=0, reflectance=(0.5, 0.5, 0.5), _substituted=True)
+
+    def lobe(elem, p, t, textured):
+        """roughdiffuse, difftrans and phong with Mitsuba's parameter names and defaults; the colours may be bitmaps, the numbers and phong's
+        specularReflectance are constants.  BSDF::ensureEnergyConservation (bsdf.cpp:88-146) as their configure() calls it."""
+        def number(name, default):
+            if any(c.get("name") == name and c.tag in ("texture", "ref") for c in elem):
+                if strict:
+                    raise SceneError("%s: a texture on %r is not supported (a bitmap on its reflectance is)" % (t, name))
+                warnings.append("texture on %r ignored: the plug-in's default value is used" % name)
+                return float(f32(default))
+            return float(f32(p.get(name, default)))
+        has = lambda n: any(c.get("name") == n for c in elem)  # noqa: E731
+        if t == "roughdiffuse":
+            m = textured(dict(type=10, alpha=number("alpha", 0.2)), "reflectance" if has("reflectance") or not has("diffuseReflectance") else "diffuseReflectance", 0.5)
+            if p.get("useFastApprox", False):
+                m["fast_approx"] = True
+            return conserve_energy(m, p, t, [("reflectance", "reflectance", "texture")])
+        if t == "difftrans":
+            m = textured(dict(type=11), "transmittance" if has("transmittance") or not has("diffuseTransmittance") else "diffuseTransmittance", 0.5)
+            return conserve_energy(m, p, t, [("transmittance", "reflectance", "texture")])
+        if strict and any(c.get("name") == "specularReflectance" and c.tag in ("texture", "ref") for c in elem):
+            raise SceneError("phong: a texture on 'specularReflectance' is not supported (a bitmap on its diffuseReflectance is)")
+        m = dict(type=12, exponent=number("exponent", 30.0), specular=tuple(float(v) for v in colour(elem, "specularReflectance", 0.2)))
+        m = textured(m, "diffuseReflectance", 0.5)
+        return conserve_energy(m, p, t, [("specularReflectance", "specular", None), ("diffuseReflectance", "reflectance", "texture")])
+
+    def conserve_energy(m, p, t, params):
+        """params: (Mitsuba's name, the dict's field, the key of its bitmap or None) — one, or the pair whose maxima are added.  A
+        component-wise maximum above 1 scales them by 0.99 / max; a bitmap's maximum is taken over its texels, and a scaled bitmap is a
+        texture of its own (the `scale` texture around it)."""
+        if not p.get("ensureEnergyConservation", True):
+            return m
+        total = np.zeros(3, f32)
+        for _, field, key in params:
+            ti = m.get(key) if key else None
+            total = total + (np.asarray(m[field], f32) if ti is None else textures[ti]["rgb"].reshape(-1, 3).max(0).astype(f32))
+        actual = f32(total.max())
+        if not actual > 1:
+            return m
+        scale = f32(0.99) * (f32(1.0) / actual)
+        names = " and ".join('"%s"' % n for n, _, _ in params)
+        warnings.append("bsdf %r violates energy conservation: %s %s a component-wise maximum of %s (> 1) and will be scaled by %s "
+                        "(ensureEnergyConservation=false prevents this)" % (t, names, "has" if len(params) == 1 else "sum to", float(actual), float(scale)))
+        for _, field, key in params:
+            m[field] = tuple(float(f32(v) * scale) for v in m[field])
+            if key and m.get(key) is not None:
+                src = textures[m[key]]
+                scaled = dict({k: v for k, v in src.items() if k != "srgb8"}, rgb=np.ascontiguousarray(src["rgb"] * scale, f32),
+                              average=[float(f32(v) * scale) for v in src["average"]])
+                textures.append(scaled)
+                m[key] = len(textures) - 1
+        return m
 
     def coated(elem, p, t, inner):
         """the nested BSDF's dict with the adapter's parameters under `coating` (bindings.Coating).  The nesting order this build knows is
@@ -1223,6 +1279,8 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         m = make_bsdf(inner[0], allow_twosided=False)
         if m["type"] in (6, 7, 8):
             raise SceneError("%s(%s): a coat on dielectric, thindielectric or roughdielectric is not supported" % (t, it))
+        if m["type"] in (10, 11, 12):
+            raise SceneError("%s(%s): a coat on roughdiffuse, difftrans or phong is not supported" % (t, it))
         if t == "roughcoating" and m["type"] in (2, 3, 5):
             raise SceneError("roughcoating(%s): a roughcoating over a BSDF with a delta component (conductor, plastic) is not supported" % it)
         int_ior, ext_ior = lookup_ior(p, "intIOR", "bk7"), lookup_ior(p, "extIOR", "air")
@@ -1282,6 +1340,8 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 raise SceneError("%s(%s): coated children are not supported" % (t, it))
             if m["type"] in (6, 7, 8):
                 raise SceneError("%s(%s): dielectric, thindielectric and roughdielectric children are not supported" % (t, it))
+            if m["type"] in (10, 11, 12):
+                raise SceneError("%s(%s): roughdiffuse, difftrans and phong children are not supported" % (t, it))
             if m["type"] == 1 or m.get("twosided") or "opacity" in m or "bump" in m:
                 raise SceneError("%s(%s) is not supported: the nesting order is bumpmap(mask(twosided(%s(..))))" % (t, it, t))
             children.append({k: v for k, v in m.items() if not k.startswith("_")})
@@ -1646,6 +1706,12 @@ def save_scene_xml(desc, props, directory, name="scene"):
             9: '<bsdf type="roughplastic"%%s>%s%s'
                '<rgb name="diffuseReflectance" value="%s"/><rgb name="specularReflectance" value="%s"/><boolean name="nonlinear" value="%s"/></bsdf>'
                % (rough, one, R, S, "true" if M.flags & 2 else "false"),
+            # (the values are the configured ones: whatever ensureEnergyConservation made of them when the scene was read)
+            10: '<bsdf type="roughdiffuse"%%s><rgb name="reflectance" value="%s"/><float name="alpha" value="%r"/><boolean name="useFastApprox" value="%s"/>'
+                '<boolean name="ensureEnergyConservation" value="false"/></bsdf>' % (R, float(M.alpha), "true" if M.flags & 16 else "false"),
+            11: '<bsdf type="difftrans"%%s><rgb name="transmittance" value="%s"/><boolean name="ensureEnergyConservation" value="false"/></bsdf>' % R,
+            12: '<bsdf type="phong"%%s><rgb name="diffuseReflectance" value="%s"/><rgb name="specularReflectance" value="%s"/><float name="exponent" value="%r"/>'
+                '<boolean name="ensureEnergyConservation" value="false"/></bsdf>' % (R, S, float(M.alpha)),
         }[t]
         K = Coating.from_dict(m)  # a coating / roughcoating goes around the leaf, inside the other adapters
         if K.kind:
@@ -1667,7 +1733,7 @@ def save_scene_xml(desc, props, directory, name="scene"):
             else:
                 body = '<bsdf type="mixturebsdf"%%s><string name="weights" value="%s"/><boolean name="ensureEnergyConservation" value="%s"/>%s</bsdf>' % (
                     ", ".join(repr(float(B.weight[k])) for k in range(B.n)), "true" if B.ensure_energy_conservation else "false", kids)
-        twos = t == 1 or (M.flags & 1 and t not in (6, 7, 8))
+        twos = t == 1 or (M.flags & 1 and t not in (6, 7, 8, 11))
         if M.flags & 4:
             inner = ('<bsdf type="twosided">%s</bsdf>' % (body % "")) if twos else body % ""
             out.append('\t<bsdf type="mask" id="mat%d"><rgb name="opacity" value="%s"/>%s</bsdf>' % (i, c(M.opacity), inner))

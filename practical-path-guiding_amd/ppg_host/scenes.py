@@ -200,6 +200,8 @@ def load_scene_file(path):
             d["opacity"] = tuple(m.opacity)
         if m.flags & 8:
             d["distribution"] = "beckmann"
+        if m.flags & 16:
+            d["fast_approx"] = True
         if m.texture & 0xffff:
             d["texture"] = (m.texture & 0xffff) - 1
         if m.texture >> 16:
