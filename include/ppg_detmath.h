@@ -5,10 +5,48 @@
  * warp.cpp:81-102).  libm results differ in the last ulp between glibc and the AMD device library, which
  * would make "same seed ⇒ same path" impossible across CPU and GPU.  Both sides therefore evaluate
  * these functions with the fixed sequences of IEEE-754 single-precision +,-,*,/ below (Cephes-style
- * range reduction + polynomial, max error ≈ 1–2 ulp on the ranges used), and both are compiled with
- * -ffp-contract=off, so every result is bit-identical on x86-64 and gfx950.
+ * range reduction + polynomial), and both are compiled with -ffp-contract=off, so every result is
+ * bit-identical on x86-64 (g++ for the oracle, clang's host pass for csrc/ppg_scene_build.h) and gfx950.
  *
- * tests/test_detmath.py checks these against numpy's libm within a stated ulp bound.
+ * What is checked, and where.  include/ppg_mathcheck.h defines, per function, the DOMAIN — the inputs for which every C++ step is
+ * defined — and a block checksum over all 2^32 float patterns.  tests/golden/detmath_exhaustive.json (tools/make_detmath_golden.py)
+ * holds the oracle's checksums and the EXHAUSTIVE worst error against float64 quoted below; tests/test_detmath.py holds the host to
+ * it, tests/test_detmath_gpu.py every kernel-family module of the device and clang's host pass, bit for bit over the whole domain.
+ * Bit equality holds on the whole domain; accuracy is claimed on the accuracy range only.
+ *
+ *   function      domain (bits agree)     accuracy range      worst error there, exhaustive         outside the accuracy range
+ *   ppg_sincos    |x| <= 2^30             |x| <= 8192         sin 7.77e-8, cos 7.82e-8 absolute     degrades with |x|; at 2^30 the "sine" is -1.06e6.
+ *                                                             (at 1204.019, 1698.8168)              Beyond 2^30, and for NaN, the (int) cast of the
+ *                                                                                                   quadrant is undefined (x86-64 gives INT_MIN,
+ *                                                                                                   gfx950 saturates): UNSUPPORTED, not clamped —
+ *                                                                                                   a clamp would cost every kernel instructions
+ *                                                                                                   for inputs no call site produces
+ *   ppg_tan       |x| <= 2^30             |x| <= 1.5          2.87 ulp (at 1.3111897)               sin / cos of the above
+ *   ppg_atan      every float             every finite x      2.83 ulp (at +-0.43632123)            atan(+-inf) = +-pi/2, atan(-0) = +0, NaN -> NaN
+ *   ppg_acos      every float             [-1, 1]             3.73 ulp (at 0.92116708)              |x| > 1 (the infinities too): acos(+-1) = 0 / pi; NaN -> NaN
+ *   ppg_atan2     every pair              both normal         2.29 ulp on the 1024^2 x 4 grid       signed zeros as C99; a finite y over an infinite x gives
+ *                                                             of the tests                          0 or +-pi, an infinite y over a finite x +-pi/2,
+ *                                                                                                   inf over inf NaN (C99: pi/4, 3pi/4); NaN -> NaN
+ *   ppg_exp       every float             [-80, 80]           0.990 ulp (at 70.403099)              the argument is CLAMPED to +-80: exp(x < -80) = exp(-80)
+ *                                                                                                   = 1.8048513e-35, never 0; exp(x > 80) = exp(80) =
+ *                                                                                                   5.5406226e34, never inf; NaN -> NaN
+ *   ppg_log       every float             normal x > 0        0.829 ulp (at 0.6999768)              log(+-0) = -inf; x < 0 and NaN -> NaN; +inf is read as
+ *                                                                                                   2^128: 88.72284; a DENORMAL is read as if its exponent
+ *                                                                                                   field were that of 2^-127 with an implicit one: up to
+ *                                                                                                   2.0e6 ulp off (at 2^-149), within 1 ulp on 128 of them
+ *   ppg_pow       every pair              x > 0 normal,       152 ulp on the tests' grid            exp(y log x) with both of the above: pow(0, y > 0) =
+ *                                         |y ln x| <= 80      (x in [2^-40, 1], y in [2^-10, 2^20];  1.8048513e-35, pow(0, 0) = NaN, pow(x, y) for
+ *                                                             the error grows like |y ln x| ulp:    |y ln x| > 80 the clamped exp.  Call sites that can
+ *                                                             at 0.597682, 152.17986)               meet x = 0 guard it themselves (lobe_pow)
+ *   ppg_powi      0 <= n < 4096           -                   n 2^-24 relative                      -
+ *   ppg_adam_learning_rate  1 <= iter <= 2^24   -             the double expression, rounded once   -
+ *   ppg_to_fixed  every float             [2^-25, 2^26)       round to nearest even, exact          NaN, +-0, every negative x and x < 2^-25 -> 0 (negatives
+ *                                                                                                   explicitly, before the cast); x >= 2^26 and +inf -> 2^50
+ *   ppg_to_sfixed every float             |x| <= 2^40         round to nearest even, exact          |x| > 2^40 and +-inf -> +-2^60; NaN -> +2^60
+ *   ppg_from_fixed, ppg_from_sfixed   every word   -          one rounding of the 64-bit integer    -
+ *
+ * No kernel call site is known to leave an accuracy range; the table is what a new one has to respect.  ppg_exp's clamp and ppg_log on
+ * denormals are pinned by the oracle's golden vectors: documented, not "fixed".
  */
 #ifndef PPG_DETMATH_H
 #define PPG_DETMATH_H
@@ -38,7 +76,7 @@ PPG_HD float ppg_abs(float x) { return ppg_u2f(ppg_f2u(x) & 0x7fffffffu); }
 /* 2^n for -126 <= n <= 127, exact. */
 PPG_HD float ppg_exp2i(int n) { return ppg_u2f((uint32_t)(n + 127) << 23); }
 
-/* sin and cos of x (|x| < ~8192), Cephes sinf/cosf scheme. */
+/* sin and cos of x, Cephes sinf/cosf scheme: accurate for |x| <= 8192, defined for |x| <= 2^30 (the table above). */
 PPG_HD void ppg_sincos(float xx, float *s_out, float *c_out) {
     float x = ppg_abs(xx);
     int sin_neg = (xx < 0.0f);
@@ -71,7 +109,7 @@ PPG_HD float ppg_atan(float xx) {
     return (xx < 0.0f) ? -y : y;
 }
 
-/* atan2(y, x) with the usual quadrant rules (finite inputs), the signed zeros of C99 F.9.1.4 included: atan2(+-0, +0) = +-0 and
+/* atan2(y, x) with the usual quadrant rules (finite inputs; infinite ones: the table above), the signed zeros of C99 F.9.1.4 included: atan2(+-0, +0) = +-0 and
    atan2(+-0, -0) = +-pi — the reference's dirToCanonical (GP:597-608) sends the pole direction (-0, +-0, +-1), which its own
    canonicalToDir produces (sinTheta * cosPhi = 0 * negative), to phi = pi, not to phi = 0. */
 PPG_HD float ppg_atan2(float y, float x) {
@@ -92,7 +130,7 @@ PPG_HD float ppg_atan2(float y, float x) {
 PPG_HD float ppg_acos(float x) { return ppg_atan2(__builtin_sqrtf(ppg_max(0.0f, (1.0f - x) * (1.0f + x))), x); }
 PPG_HD float ppg_tan(float x) { float s, c; ppg_sincos(x, &s, &c); return s / c; }
 
-/* exp(x) for |x| <= 80, Cephes expf scheme. */
+/* exp(x), Cephes expf scheme; x is clamped to [-80, 80] (the table above). */
 PPG_HD float ppg_exp(float x) {
     if (x > 80.0f) x = 80.0f;
     if (x < -80.0f) x = -80.0f;
@@ -169,6 +207,7 @@ PPG_HD float ppg_adam_learning_rate(float learningRate, float beta1, float beta2
 PPG_HD uint64_t ppg_to_fixed(float x) {
     float v = x * 16777216.0f;
     if (v != v) return 0ull;
+    if (v < 0.0f) return 0ull; /* before the cast: a negative float to uint64_t is undefined in C++, and x86-64 and gfx950 disagree on it */
     if (!(v < 1125899906842624.0f)) return 1ull << 50;
     return (uint64_t)__builtin_rintf(v); /* exactly specified: nearest-even (v_rndne_f32 / rintf) */
 }

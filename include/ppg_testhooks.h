@@ -140,6 +140,20 @@ struct ppg_debug_bsdf_out {
 };  /* 64 bytes */
 int ppg_debug_bsdf(struct ppg_ctx *ctx, uint32_t n, const struct ppg_debug_bsdf_item *items, struct ppg_debug_bsdf_out *out);
 
+/* The shared float math (include/ppg_detmath.h, ppg_rng.h) as ONE module of this library compiled it; no scene is needed.  The ops, their
+   arguments (bit patterns), their domains and the block checksum are those of include/ppg_mathcheck.h.
+     family  0 .. 5: the TRACE unit of that kernel family (csrc/ppg_device.h) — every family's module holds its own copy of the header's
+             functions and its own out-of-line dm_sincos / dm_atan2 / dm_exp / dm_log.  -1: this library's HOST code, i.e. clang's host
+             pass, which compiles the tables csrc/ppg_scene_build.h bakes with ppg_exp and ppg_sincos.
+     via     0: the header's functions, inlined.  1: what the kernels call — dm_sincos, dm_atan2, dm_exp, dm_log, dm_acos, dm_tan, dm_pow;
+             refused (PPG_ERR_INVALID) for an op without such a copy and for family -1.
+   ppg_debug_math_eval: element i of out0 / out1 receives op(a[i], b[i]); an element outside the op's domain, and out1 of an op with one
+   output, keeps what the caller put there.  ppg_debug_math_checksum: out[k] = the checksum of block first_block + k of the 256 blocks of
+   2^24 float patterns, for an op of one argument. */
+int ppg_debug_math_eval(struct ppg_ctx *ctx, int32_t family, int32_t via, int32_t op, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t *out0,
+                        uint32_t *out1);
+int ppg_debug_math_checksum(struct ppg_ctx *ctx, int32_t family, int32_t via, int32_t op, uint32_t first_block, uint32_t n_blocks, uint64_t *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,7 @@
 #include "../include/ppg.h"
 #include "../include/ppg_detmath.h"
 #include "../include/ppg_rng.h"
+#include "../include/ppg_mathcheck.h"
 #include "ppg_oracle.h"
 
 #include <algorithm>
@@ -3736,26 +3737,34 @@ void ppgo_dir_to_canonical(const float *d, float *xy) {
     xy[0] = p.x; xy[1] = p.y;
 }
 
-// element-wise evaluation of the shared numerical contract (tests/test_detmath.py)
+// element-wise evaluation of the shared numerical contract (include/ppg_mathcheck.h; tests/test_detmath.py).  a, b, out0, out1 are float
+// arrays read and written as bit patterns; an element outside the op's domain is not evaluated and its outputs are left as they are.
 int ppgo_math_eval(int32_t op, uint32_t n, const float *a, const float *b, float *out0, float *out1) {
-    for (uint32_t i = 0; i < n; ++i) {
-        switch (op) {
-            case 0: ppg_sincos(a[i], &out0[i], &out1[i]); break;
-            case 1: out0[i] = ppg_atan2(a[i], b[i]); break;
-            case 2: out0[i] = ppg_exp(a[i]); break;
-            case 3: out0[i] = ppg_from_fixed(ppg_to_fixed(a[i])); break;
-            case 4: out0[i] = ppg_rand((uint32_t)i * 2654435761u + 17u, (uint32_t)b[i]); break;
-            case 5: out0[i] = ppg_powi(a[i], (int)b[i]); break;
-            case 9: out0[i] = ppg_adam_learning_rate(0.01f, 0.9f, 0.999f, (int)a[i]); break;  // AdamOptimizer::step's learning rate at iteration a
-            case 6: out0[i] = ppg_log(a[i]); break;
-            case 7: out0[i] = ppg_pow(a[i], b[i]); break;
-            case 8: {  // draw `dim` of the path (seed, pixel, sample index): a = pixel, b = seed << 16 | sample << 4 | dim, as bit patterns
-                const uint32_t pixel = ppg_f2u(a[i]), w = ppg_f2u(b[i]);
-                out0[i] = ppg_rand(ppg_path_key((uint64_t)(w >> 16), pixel, (w >> 4) & 0xfffu), w & 15u);
-                break;
-            }
-            default: return PPG_ERR_INVALID;
-        }
+    if (!ppg_mathcheck_known(op)) return PPG_ERR_INVALID;
+    const bool two = ppg_mathcheck_outputs(op) == 2;
+#pragma omp parallel for schedule(static) if (n >= (1u << 16))
+    for (int64_t i = 0; i < (int64_t)n; ++i) {
+        uint32_t ua, ub, o0 = 0u, o1 = 0u;
+        memcpy(&ua, a + i, 4); memcpy(&ub, b + i, 4);
+        ua = ppg_mathcheck_arg_a(op, (uint32_t)i, ua);
+        if (!ppg_mathcheck_in_domain(op, ua, ub)) continue;
+        ppg_mathcheck_eval(op, ua, ub, &o0, &o1);
+        memcpy(out0 + i, &o0, 4);
+        if (two) memcpy(out1 + i, &o1, 4);
+    }
+    return PPG_OK;
+}
+// out[k] = the checksum of block first_block + k of the float patterns under the one-argument op (include/ppg_mathcheck.h)
+int ppgo_math_checksum(int32_t op, uint32_t first_block, uint32_t n_blocks, uint64_t *out) {
+    if (!ppg_mathcheck_unary(op) || !out || first_block > PPG_MATHCHECK_BLOCKS || n_blocks > PPG_MATHCHECK_BLOCKS - first_block) return PPG_ERR_INVALID;
+    const int64_t chunks = 256, per = (int64_t)(1u << PPG_MATHCHECK_BLOCK_BITS) / chunks;
+    for (uint32_t k = 0; k < n_blocks; ++k) {
+        const uint32_t base = (first_block + k) << PPG_MATHCHECK_BLOCK_BITS;
+        uint64_t sum = 0;
+#pragma omp parallel for schedule(static) reduction(+ : sum)
+        for (int64_t c = 0; c < chunks; ++c)
+            for (int64_t i = c * per; i < (c + 1) * per; ++i) sum += ppg_mathcheck_term(op, base | (uint32_t)i);
+        out[k] = sum;
     }
     return PPG_OK;
 }

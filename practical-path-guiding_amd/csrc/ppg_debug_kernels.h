@@ -2,11 +2,13 @@
  * ppg_debug_kernels.h — the kernels of the test hooks (include/ppg_testhooks.h) that run the render's own device functions, included by the
  * k_trace unit of a family (ppg_inst.hip): k_debug_intersect, the kernels of ppg_debug_intersect_mode and k_debug_sample_direct in the shapes family, which the hooks always use;
  * k_debug_bsdf in the ext family, k_debug_bsdf_coat in the coat family, which ppg_debug_bsdf uses for a scene with a coated material, and
- * k_debug_bsdf_blend in the blend family, which it uses for a scene with a blended one.
+ * k_debug_bsdf_blend in the blend family, which it uses for a scene with a blended one.  Every family holds k_debug_math_eval and
+ * k_debug_math_checksum (ppg_debug_math_*): the shared float math as this module compiled it, its own out-of-line dm_ copies included.
  */
 #ifndef PPG_DEBUG_KERNELS_H
 #define PPG_DEBUG_KERNELS_H
 
+#include "../../include/ppg_mathcheck.h"
 #include "../../include/ppg_testhooks.h"
 #include "ppg_launch.h"
 
@@ -224,8 +226,75 @@ static void launch_debug_bsdf(int grid, int block, hipStream_t stream, const Dev
 }
 #endif
 
+// ---- ppg_debug_math_eval / ppg_debug_math_checksum: include/ppg_mathcheck.h on the device, in every family's module ----
+#define k_debug_math_eval PPG_FAMILY_NAME(k_debug_math_eval)
+#define k_debug_math_checksum PPG_FAMILY_NAME(k_debug_math_checksum)
+// VIA = 0: the header's functions, inlined here.  VIA = 1: what the kernels of this module call — its out-of-line dm_sincos, dm_atan2, dm_exp,
+// dm_log and the dm_acos, dm_tan, dm_pow built on them (ppg_device.h); only for the ops of ppg_mathcheck_has_dm.
+template <int VIA> D void debug_math_eval(int op, uint32_t a, uint32_t b, uint32_t *o0, uint32_t *o1) {
+    if (VIA == 0) { ppg_mathcheck_eval(op, a, b, o0, o1); return; }
+    const float fa = ppg_u2f(a), fb = ppg_u2f(b);
+    switch (op) {
+        case 0: { const float2 r = dm_sincos(fa); *o0 = ppg_f2u(r.x); *o1 = ppg_f2u(r.y); break; }
+        case 1: *o0 = ppg_f2u(dm_atan2(fa, fb)); break;
+        case 2: *o0 = ppg_f2u(dm_exp(fa)); break;
+        case 6: *o0 = ppg_f2u(dm_log(fa)); break;
+        case 7: *o0 = ppg_f2u(dm_pow(fa, fb)); break;
+        case 11: *o0 = ppg_f2u(dm_acos(fa)); break;
+        case 12: *o0 = ppg_f2u(dm_tan(fa)); break;
+        default: break;  // (the hook has refused the op)
+    }
+}
+template <int VIA> __global__ void k_debug_math_eval(int op, unsigned int n, const uint32_t *a, const uint32_t *b, uint32_t *out0, uint32_t *out1) {
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t ua = ppg_mathcheck_arg_a(op, i, a[i]), ub = b[i];
+    if (!ppg_mathcheck_in_domain(op, ua, ub)) return;  // (its outputs stay as the host sent them)
+    uint32_t o0 = 0u, o1 = 0u;
+    debug_math_eval<VIA>(op, ua, ub, &o0, &o1);
+    out0[i] = o0;
+    if (ppg_mathcheck_outputs(op) == 2) out1[i] = o1;
+}
+// PPG_MATH_GROUPS workgroups of 256 share a block of 2^24 patterns: slot = blockIdx.x / PPG_MATH_GROUPS < n_blocks by the size of the grid.
+// Each lane sums the terms of its stride, a wave adds its lanes' sums by shuffles, its first lane adds the wave's to the block's slot.
+#define PPG_MATH_GROUPS 64u
+template <int VIA> __global__ __launch_bounds__(256) void k_debug_math_checksum(int op, unsigned int first_block, unsigned int n_blocks, unsigned long long *out) {
+    const unsigned int slot = blockIdx.x / PPG_MATH_GROUPS;
+    if (slot >= n_blocks) return;
+    const uint32_t base = (first_block + slot) << PPG_MATHCHECK_BLOCK_BITS;
+    const unsigned int stride = PPG_MATH_GROUPS * 256u;
+    const int nf = ppg_mathcheck_float_outputs(op);
+    unsigned long long sum = 0ull;
+    for (unsigned int i = (blockIdx.x % PPG_MATH_GROUPS) * 256u + threadIdx.x; i < (1u << PPG_MATHCHECK_BLOCK_BITS); i += stride) {
+        const uint32_t u = base | i;
+        if (!ppg_mathcheck_in_domain(op, u, 0u)) continue;
+        uint32_t o0 = 0u, o1 = 0u;
+        debug_math_eval<VIA>(op, u, 0u, &o0, &o1);
+        if (nf > 0) o0 = ppg_mathcheck_canon(o0);
+        if (nf > 1) o1 = ppg_mathcheck_canon(o1);
+        sum += ppg_mathcheck_mix(u, o0, o1);
+    }
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned int lo = __shfl_down((unsigned int)sum, d, 64), hi = __shfl_down((unsigned int)(sum >> 32), d, 64);
+        sum += ((unsigned long long)hi << 32) | lo;
+    }
+    if ((threadIdx.x & 63u) == 0u) atomicAdd(out + slot, sum);
+}
+static void launch_debug_math_eval(hipStream_t stream, int via, int op, unsigned int n, const uint32_t *a, const uint32_t *b, uint32_t *out0, uint32_t *out1) {
+    const dim3 grid((n + 255u) / 256u), block(256);
+    if (via) hipLaunchKernelGGL((k_debug_math_eval<1>), grid, block, 0, stream, op, n, a, b, out0, out1);
+    else hipLaunchKernelGGL((k_debug_math_eval<0>), grid, block, 0, stream, op, n, a, b, out0, out1);
+}
+static void launch_debug_math_checksum(hipStream_t stream, int via, int op, unsigned int first_block, unsigned int n_blocks, unsigned long long *out) {
+    const dim3 grid(n_blocks * PPG_MATH_GROUPS), block(256);
+    if (via) hipLaunchKernelGGL((k_debug_math_checksum<1>), grid, block, 0, stream, op, first_block, n_blocks, out);
+    else hipLaunchKernelGGL((k_debug_math_checksum<0>), grid, block, 0, stream, op, first_block, n_blocks, out);
+}
+
 // the hooks' launchers of this family, into its row
 static void fill_debug_kernels(PathKernels &K) {
+    K.debug_math_eval = launch_debug_math_eval;
+    K.debug_math_checksum = launch_debug_math_checksum;
 #if PPG_FAMILY == PPG_FAMILY_SHAPES
     K.debug_intersect = launch_debug_intersect;
     K.debug_sample_direct = launch_debug_sample_direct;

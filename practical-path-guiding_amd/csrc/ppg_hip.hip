@@ -28,9 +28,11 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/ppg.h"
+#include "../../include/ppg_mathcheck.h"
 #include "../../include/ppg_testhooks.h"
 #include "ppg_batch_plan.h"
 #include "ppg_host_kernels.h"
@@ -2925,6 +2927,80 @@ int ppg_debug_bsdf(ppg_ctx *ctx, uint32_t n, const ppg_debug_bsdf_item *items, p
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_bsdf_out), hipMemcpyDeviceToHost));
+    return PPG_OK;
+}
+
+// include/ppg_mathcheck.h in one family's TRACE unit, or (family = -1) in this translation unit's host code; no scene is needed
+static int debugMathRefusal(ppg_ctx *ctx, const char *who, int32_t family, int32_t via, int32_t op) {
+    if (ctx->renderOpen) { ctx->error = std::string(who) + ": not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (!ppg_mathcheck_known(op)) { ctx->error = std::string(who) + ": no such op"; return PPG_ERR_INVALID; }
+    if (family < -1 || family >= PPG_FAMILIES) { ctx->error = std::string(who) + ": no such kernel family"; return PPG_ERR_INVALID; }
+    if (via != 0 && via != 1) { ctx->error = std::string(who) + ": via is 0 (the header's functions) or 1 (the module's dm_ copies)"; return PPG_ERR_INVALID; }
+    if (via == 1 && family < 0) { ctx->error = std::string(who) + ": the host has no dm_ copies"; return PPG_ERR_INVALID; }
+    if (via == 1 && !ppg_mathcheck_has_dm(op)) { ctx->error = std::string(who) + ": the kernels have no dm_ copy of this op"; return PPG_ERR_INVALID; }
+    return PPG_OK;
+}
+int ppg_debug_math_eval(ppg_ctx *ctx, int32_t family, int32_t via, int32_t op, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t *out0, uint32_t *out1) {
+    if (const int rc = debugMathRefusal(ctx, "ppg_debug_math_eval", family, via, op)) return rc;
+    if (n && (!a || !b || !out0 || !out1)) { ctx->error = "ppg_debug_math_eval: no arrays"; return PPG_ERR_INVALID; }
+    if (n == 0) return PPG_OK;
+    const bool two = ppg_mathcheck_outputs(op) == 2;
+    if (family < 0) {
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t ua = ppg_mathcheck_arg_a(op, i, a[i]);
+            if (!ppg_mathcheck_in_domain(op, ua, b[i])) continue;
+            uint32_t o0 = 0u, o1 = 0u;
+            ppg_mathcheck_eval(op, ua, b[i], &o0, &o1);
+            out0[i] = o0;
+            if (two) out1[i] = o1;
+        }
+        return PPG_OK;
+    }
+    HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->quiesce();
+    const size_t bytes = (size_t)n * sizeof(uint32_t);
+    DebugBuf dA, dB, d0, d1;
+    HIP_CHECK(dA.fill(a, bytes));
+    HIP_CHECK(dB.fill(b, bytes));
+    HIP_CHECK(d0.fill(out0, bytes));  // (an element outside the op's domain keeps what the caller sent)
+    HIP_CHECK(d1.fill(out1, bytes));
+    launcher(ppg_path_kernels[family].debug_math_eval)(ctx->stream, via, op, n, (const uint32_t *)dA.p, (const uint32_t *)dB.p, (uint32_t *)d0.p, (uint32_t *)d1.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    HIP_CHECK(hipMemcpy(out0, d0.p, bytes, hipMemcpyDeviceToHost));
+    if (two) HIP_CHECK(hipMemcpy(out1, d1.p, bytes, hipMemcpyDeviceToHost));
+    return PPG_OK;
+}
+int ppg_debug_math_checksum(ppg_ctx *ctx, int32_t family, int32_t via, int32_t op, uint32_t first_block, uint32_t n_blocks, uint64_t *out) {
+    if (const int rc = debugMathRefusal(ctx, "ppg_debug_math_checksum", family, via, op)) return rc;
+    if (!ppg_mathcheck_unary(op)) { ctx->error = "ppg_debug_math_checksum: only the ops of one argument have block checksums"; return PPG_ERR_INVALID; }
+    if (first_block > PPG_MATHCHECK_BLOCKS || n_blocks > PPG_MATHCHECK_BLOCKS - first_block) { ctx->error = "ppg_debug_math_checksum: blocks beyond 256"; return PPG_ERR_INVALID; }
+    if (n_blocks && !out) { ctx->error = "ppg_debug_math_checksum: no array"; return PPG_ERR_INVALID; }
+    if (n_blocks == 0) return PPG_OK;
+    if (family < 0) {
+        std::vector<std::thread> pool;  // one thread per block, sixteen at a time
+        for (uint32_t k0 = 0; k0 < n_blocks; k0 += 16) {
+            for (uint32_t k = k0; k < std::min(n_blocks, k0 + 16); ++k)
+                pool.emplace_back([=] {
+                    const uint32_t base = (first_block + k) << PPG_MATHCHECK_BLOCK_BITS;
+                    uint64_t sum = 0;
+                    for (uint32_t i = 0; i < (1u << PPG_MATHCHECK_BLOCK_BITS); ++i) sum += ppg_mathcheck_term(op, base | i);
+                    out[k] = sum;
+                });
+            for (auto &t : pool) t.join();
+            pool.clear();
+        }
+        return PPG_OK;
+    }
+    HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->quiesce();
+    DebugBuf dOut;
+    HIP_CHECK(dOut.fill(nullptr, (size_t)n_blocks * sizeof(uint64_t)));
+    HIP_CHECK(hipMemsetAsync(dOut.p, 0, (size_t)n_blocks * sizeof(uint64_t), ctx->stream));
+    launcher(ppg_path_kernels[family].debug_math_checksum)(ctx->stream, via, op, first_block, n_blocks, (unsigned long long *)dOut.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n_blocks * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return PPG_OK;
 }
 

@@ -83,6 +83,9 @@ struct PathKernels {
     void (*debug_sample_direct)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float *ref, const float *ref_n, const float *u,
                                 ppg_debug_direct *out);
     void (*debug_bsdf)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out);
+    // every family: include/ppg_mathcheck.h as the family's TRACE unit compiled it (via = 1: through the unit's dm_ copies)
+    void (*debug_math_eval)(hipStream_t stream, int via, int op, unsigned int n, const uint32_t *a, const uint32_t *b, uint32_t *out0, uint32_t *out1);
+    void (*debug_math_checksum)(hipStream_t stream, int via, int op, unsigned int first_block, unsigned int n_blocks, unsigned long long *out);
 };
 extern PathKernels ppg_path_kernels[PPG_FAMILIES];
 

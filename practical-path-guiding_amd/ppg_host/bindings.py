@@ -840,6 +840,30 @@ class Engine:
         self._call("debug_bsdf", C.c_uint32(n), items.ctypes.data_as(C.POINTER(DebugBsdfItem)), out.ctypes.data_as(C.POINTER(DebugBsdfOut)))
         return out
 
+    def debug_math_eval(self, family, via, op, a, b=None):
+        """ppg_debug_math_eval (include/ppg_testhooks.h): op of include/ppg_mathcheck.h on the bit patterns a, b (float32 or uint32 arrays),
+        in kernel family `family`'s module (-1: the library's host code), via 0 the header's functions or 1 the module's dm_ copies.
+        -> (out0, out1) uint32; an element outside the op's domain stays 0."""
+        def bits(v):
+            v = np.ascontiguousarray(v)
+            return np.ascontiguousarray(v.view(np.uint32) if v.dtype == np.float32 else v.astype(np.uint32, casting="same_kind")).ravel()
+        a = bits(a)
+        b = np.zeros_like(a) if b is None else bits(b)
+        assert a.size == b.size
+        o0, o1 = np.zeros_like(a), np.zeros_like(a)
+        up = C.POINTER(C.c_uint32)
+        self._call("debug_math_eval", C.c_int32(family), C.c_int32(via), C.c_int32(op), C.c_uint32(a.size), a.ctypes.data_as(up), b.ctypes.data_as(up),
+                   o0.ctypes.data_as(up), o1.ctypes.data_as(up))
+        return o0, o1
+
+    def debug_math_checksum(self, family, via, op, first_block=0, n_blocks=256):
+        """ppg_debug_math_checksum: the checksums of blocks first_block .. first_block + n_blocks - 1 of the float patterns under a
+        one-argument op; uint64 [n_blocks]."""
+        out = np.zeros(n_blocks, np.uint64)
+        self._call("debug_math_checksum", C.c_int32(family), C.c_int32(via), C.c_int32(op), C.c_uint32(first_block), C.c_uint32(n_blocks),
+                   out.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return out
+
     def set_lens(self, lens):
         """ppg_set_lens: lens = {"aperture_radius", "focus_distance"} (Lens) or None for the pinhole"""
         self._lens = None if lens is None else Lens.from_dict(lens)
