@@ -1,6 +1,10 @@
 /*
  * ppg_testhooks.h — entry points of libppg_hip.so that exist for the tests only.  Not part of the drop-in boundary (include/ppg.h): nothing
  * a host of the integrator needs, no reference counterpart.
+ *   host only   ppg_debug_build_bvh, ppg_debug_bvh_stats, ppg_debug_bvh_trace, ppg_debug_rfilter_table, ppg_debug_stree_depth
+ *   a scene     ppg_debug_intersect, ppg_debug_intersect_mode, ppg_debug_sample_direct, ppg_debug_bsdf
+ *   a render    ppg_debug_set_defer_depth, ppg_debug_commit (inside an open training iteration)
+ *   no scene    ppg_debug_math_eval, ppg_debug_math_checksum
  */
 #ifndef PPG_TESTHOOKS_H
 #define PPG_TESTHOOKS_H
@@ -153,6 +157,61 @@ int ppg_debug_bsdf(struct ppg_ctx *ctx, uint32_t n, const struct ppg_debug_bsdf_
 int ppg_debug_math_eval(struct ppg_ctx *ctx, int32_t family, int32_t via, int32_t op, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t *out0,
                         uint32_t *out1);
 int ppg_debug_math_checksum(struct ppg_ctx *ctx, int32_t family, int32_t via, int32_t op, uint32_t first_block, uint32_t n_blocks, uint64_t *out);
+
+/* EXPLICIT VERTICES through the commit of a batch: Vertex::commit (GP:1730-1768) of every vertex of every path, then the end of the round.
+   Valid between ppg_begin_iteration(ctx, 0) and ppg_build_sdtree, outside ppg_render_passes; the vertices go into the context's current
+   building tree and leaf headers under its spatialFilter, directionalFilter, loss, nee and do_nee (ppg_set_do_nee), through the render's
+   own launchers: the hook builds a PathState from the arrays below — one small kernel finds every vertex's leaf and voxel size with
+   stree_lookup, as k_shade does — and runs launchCommitKernels, reserveRoundRecords, applyAdamRound and the fold of the weight replicas.
+   The optimiser's path id of path i is i (n_pix = n_paths, identity pixel list).  The oracle has the same entry, ppgo_debug_commit: there
+   every vertex becomes a Vertex whose dTree is STree::dTreeWrapper(p, voxel), committed by Vertex::commit with the sampler at
+   (key, dim + 3 v), and the round ends with the oracle's applyAdamRound.
+     route  COMMIT          k_commit over all paths.
+            COMMIT_SPLIT    k_commit with the late paths left out (their nv8 byte is 0), then k_commit over the list of the late paths: a
+                            batch with a tail.
+            RECORDS         k_commit_records, the sort, k_splat_sorted, k_adam_apply: a round with known record positions.  Refused unless
+                            a round runs (a loss is set and the tree is built), recordPositionsKnown holds for the context and the flag
+                            bit fits the key.  The route is the caller's choice: PPG_NO_SORTED_COMMIT, which makes the RENDER commit its
+                            rounds with k_commit, does not change what a route of this hook runs.
+            RECORDS_SPLIT   the same with the late paths through the list launch; they reserve max_vertices positions each, as a path
+                            handed to k_tail does (the unused ones stay holes).
+     per path    nv (0 .. max_vertices of the context), key, dim (the sampler's dimension when Li returned), late (NULL: none)
+     per vertex  (n_vertices = sum nv, path after path) p, d, radiance, throughput, bsdf_val [3]; wo_pdf, bsdf_pdf, dtree_pdf; is_delta
+   Out: committed (vertices Vertex::commit accepted); the valid sorted keys of a record route, "splat only" flag bit (just above the leaf
+   bits) included — *n_keys is their number also when it exceeds keys_cap —; the optimiser's records in key order (likewise); and the
+   optimiser's state of every S-tree node after the round, 6 words as ppg_adam_state gives them (adam_state: NULL or n_stree_nodes * 6).
+   Every count and index is checked on the host (PPG_ERR_INVALID, ppg_last_error names the argument; PPG_ERR_STATE outside an iteration)
+   and a refused call leaves the context as it was; PPG_ERR_STATE also while a round hook (ppg_set_pass_hook) is installed.  The floats may be anything: no kernel indexes with them. */
+enum { PPG_DEBUG_COMMIT = 0, PPG_DEBUG_COMMIT_SPLIT = 1, PPG_DEBUG_COMMIT_RECORDS = 2, PPG_DEBUG_COMMIT_RECORDS_SPLIT = 3 };
+struct ppg_adam_record;
+struct ppg_debug_commit_in {
+    int32_t route;
+    uint32_t n_paths;
+    uint64_t n_vertices;
+    const uint32_t *nv, *key, *dim;
+    const uint8_t *late;
+    const float *p, *d, *radiance, *throughput, *bsdf_val;
+    const float *wo_pdf, *bsdf_pdf, *dtree_pdf;
+    const uint8_t *is_delta;
+};
+struct ppg_debug_commit_out {
+    uint64_t committed;
+    uint64_t n_keys, keys_cap;
+    uint64_t *keys;
+    uint64_t n_records, records_cap;
+    struct ppg_adam_record *records;
+    uint32_t *adam_state;
+};
+int ppg_debug_commit(struct ppg_ctx *ctx, const struct ppg_debug_commit_in *in, struct ppg_debug_commit_out *out);
+/* Host only: the depth of an S-tree given as ppg_sdtree_read_stree gives it (children[2 i], children[2 i + 1]; 0, 0 = a leaf; a child's
+   index is above its parent's) — levels below the root of its deepest leaf — and what the refine step answers to it under the spatial
+   filter (0 nearest, 1 stochastic, 2 box): PPG_OK, or PPG_ERR_NOMEM for a tree deeper than PPG_STREE_MAX_DEPTH under the box filter.
+   The box filter's splat (stree_record_box, csrc/ppg_kernels.h) walks the S-tree depth first with a stack of 96 entries: an interior
+   node d levels below the root is popped with d entries left — one sibling per level above it — and pushes its two children, d + 2 <= 96.
+   The 96 entries therefore serve interior nodes down to level 94, i.e. trees whose deepest leaf lies 95 levels below the root; the limit
+   is set one level below that.  PPG_ERR_INVALID: a child index that is not above its parent's or beyond n_nodes. */
+#define PPG_STREE_MAX_DEPTH 94
+int ppg_debug_stree_depth(const uint32_t *children, uint32_t n_nodes, int32_t spatial_filter, uint32_t *depth);
 
 #ifdef __cplusplus
 }

@@ -47,6 +47,7 @@
 #include "../include/ppg_detmath.h"
 #include "../include/ppg_rng.h"
 #include "../include/ppg_mathcheck.h"
+#include "../include/ppg_testhooks.h"
 #include "ppg_oracle.h"
 
 #include <algorithm>
@@ -2522,6 +2523,7 @@ public:
 
     void buildSDTree(ppg_tree_stats *st) {  // GP:1115-1189
         m_sdTree->forEachDTreeWrapper([this](DTreeWrapper *dTree) { dTree->build(modes); });
+        m_iterOpen = false;
         int maxDepth = 0, minDepth = std::numeric_limits<int>::max();
         Float avgDepth = 0, maxAvgRadiance = 0, minAvgRadiance = std::numeric_limits<Float>::max(), avgAvgRadiance = 0;
         size_t maxNodes = 0, minNodes = std::numeric_limits<size_t>::max();
@@ -3155,6 +3157,7 @@ public:
         m_iter = 0;
         m_isFinalIter = false;
         m_isBuilt = false;
+        m_iterOpen = false;
         size_t n = (size_t)W() * H();
         m_image.assign(3 * n, 0); m_squaredImage.assign(3 * n, 0); m_imageW.assign(n, 0);
         m_film.assign(3 * n, 0); m_filmW.assign(n, 0); m_varianceBuffer.assign(3 * n, 0);
@@ -3173,7 +3176,9 @@ public:
         std::fill(m_film.begin(), m_film.end(), 0.0f);
         std::fill(m_filmW.begin(), m_filmW.end(), 0.0f);
         resetSDTree();
+        m_iterOpen = !isFinal;
     }
+    bool m_iterOpen = false;  // between beginIteration(false) and buildSDTree: the building tree takes records (ppgo_debug_commit)
     void endIteration() {  // GP:1417-1422
         if (m_dumpSDTree && !m_isFinalIter && !m_dumpPrefix.empty()) {
             char buf[1024];
@@ -3599,6 +3604,76 @@ int ppgo_set_adam_regions(ppgo_ctx *ctx, int32_t regions) {  // include/ppg.h "R
     return PPG_OK;
 }
 int ppgo_debug_set_defer_depth(ppgo_ctx *ctx, int32_t depth) { if (depth < 1 || depth > 64) return PPG_ERR_INVALID; ctx->gpt.m_deferDepth = depth; return PPG_OK; }
+// include/ppg_testhooks.h, ppg_debug_commit: the same vertices through Vertex::commit and the round's end (no arithmetic of its own)
+int ppgo_debug_commit(ppgo_ctx *ctx, const ppg_debug_commit_in *in, ppg_debug_commit_out *out) {
+    NEED_TREE
+    GuidedPathTracer &g = ctx->gpt;
+    if (!g.m_iterOpen) { g.error = "ppg_debug_commit: only between ppg_begin_iteration(ctx, 0) and ppg_build_sdtree"; return PPG_ERR_STATE; }
+    if (g.passHook) { g.error = "ppg_debug_commit: not while a round hook is installed (ppg_set_pass_hook): it may replace the round's records"; return PPG_ERR_STATE; }
+    if (!in || !out) { g.error = "ppg_debug_commit: in / out is NULL"; return PPG_ERR_INVALID; }
+    const bool round = g.m_bsdfSamplingFractionLoss != ENone && g.modes.adam != PPGO_ADAM_SEQUENTIAL && g.m_isBuilt;
+    const bool known = g.m_spatialFilter != ESBox && !(g.m_doNee && g.m_nee == EKickstart);
+    const uint32_t maxVertices = g.m_maxDepth > 0 ? (uint32_t)std::max(1, std::min(32, g.m_maxDepth - 1)) : 32u;
+    auto &nodes = g.m_sdTree->nodes();
+    if (in->route < PPG_DEBUG_COMMIT || in->route > PPG_DEBUG_COMMIT_RECORDS_SPLIT) { g.error = "ppg_debug_commit: route: no such route"; return PPG_ERR_INVALID; }
+    if (in->n_paths >= PPG_ADAM_DEFER_PATH_BIT) { g.error = "ppg_debug_commit: n_paths must be below 2^26"; return PPG_ERR_INVALID; }
+    if (in->n_paths && (!in->nv || !in->key || !in->dim)) { g.error = "ppg_debug_commit: nv, key and dim are needed per path"; return PPG_ERR_INVALID; }
+    uint64_t sum = 0;
+    for (uint32_t i = 0; i < in->n_paths; ++i) {
+        if (in->nv[i] > maxVertices) { g.error = "ppg_debug_commit: nv: a path has more vertices than the context's max_vertices"; return PPG_ERR_INVALID; }
+        sum += in->nv[i];
+    }
+    if (sum != in->n_vertices) { g.error = "ppg_debug_commit: n_vertices is not the sum of nv"; return PPG_ERR_INVALID; }
+    if (sum && (!in->p || !in->d || !in->radiance || !in->throughput || !in->bsdf_val || !in->wo_pdf || !in->bsdf_pdf || !in->dtree_pdf || !in->is_delta)) {
+        g.error = "ppg_debug_commit: a per-vertex array is NULL"; return PPG_ERR_INVALID;
+    }
+    if (in->route >= PPG_DEBUG_COMMIT_RECORDS && !(round && known)) { g.error = "ppg_debug_commit: route: the record routes need a round of the optimiser with known record positions"; return PPG_ERR_INVALID; }
+    if ((out->keys_cap && !out->keys) || (out->records_cap && !out->records)) { g.error = "ppg_debug_commit: out: a capacity without its array"; return PPG_ERR_INVALID; }
+    out->committed = 0; out->n_keys = 0; out->n_records = 0;
+    if (g.m_blockSinks.empty()) g.m_blockSinks.assign(1, std::vector<AdamRecord>());
+    for (auto &sink : g.m_blockSinks) sink.clear();
+    g.m_deferredRecords.clear();
+    Modes tm = g.modes;
+    tm.sink = &g.m_blockSinks[0];
+    const Float statisticalWeight = g.m_nee == EKickstart && g.m_doNee ? 0.5f : 1.0f;
+    const ELoss loss = g.m_isBuilt ? g.m_bsdfSamplingFractionLoss : ENone;
+    auto S = [](const float *a, uint64_t k) { return Spectrum(a[3 * k], a[3 * k + 1], a[3 * k + 2]); };
+    uint64_t k = 0;
+    for (uint32_t i = 0; i < in->n_paths; ++i) {
+        tm.path = i;
+        for (uint32_t v = 0; v < in->nv[i]; ++v, ++k) {
+            GuidedPathTracer::Vertex vx;
+            vx.rayO = Point(in->p[3 * k], in->p[3 * k + 1], in->p[3 * k + 2]);
+            vx.dTree = g.m_sdTree->dTreeWrapper(vx.rayO, vx.dTreeVoxelSize);
+            vx.rayD = Vec(in->d[3 * k], in->d[3 * k + 1], in->d[3 * k + 2]);
+            vx.throughput = S(in->throughput, k); vx.bsdfVal = S(in->bsdf_val, k); vx.radiance = S(in->radiance, k);
+            vx.woPdf = in->wo_pdf[k]; vx.bsdfPdf = in->bsdf_pdf[k]; vx.dTreePdf = in->dtree_pdf[k];
+            vx.isDelta = in->is_delta[k] != 0;
+            Sampler sampler{in->key[i], in->dim[i] + 3u * v};
+            if (vx.commit(*g.m_sdTree, statisticalWeight, g.m_spatialFilter, g.m_directionalFilter, loss, &sampler, tm, (uint32_t)PPG_ADAM_CODE_VERTEX + v))
+                ++out->committed;
+        }
+    }
+    if (round) {
+        // the records applyAdamRound is about to apply, in the order it applies them
+        std::vector<GuidedPathTracer::PackedAdamRecord> recs;
+        for (const AdamRecord &r : g.m_blockSinks[0]) {
+            const uint64_t leaf = (uint64_t)(((const char *)r.dTree - (const char *)&nodes[0].dTree) / sizeof(STreeNode));
+            recs.push_back({(leaf << PPG_ADAM_LEAF_SHIFT) | ((uint64_t)r.path << PPG_ADAM_CODE_BITS) | r.code, r.product, r.woPdf, r.bsdfPdf, r.dTreePdf, r.weight, 0.0f});
+        }
+        std::sort(recs.begin(), recs.end(), [](const GuidedPathTracer::PackedAdamRecord &a, const GuidedPathTracer::PackedAdamRecord &b) { return a.key < b.key; });
+        for (const auto &r : recs) {
+            if (out->n_keys < out->keys_cap) out->keys[out->n_keys] = r.key;
+            ++out->n_keys;
+            if (out->n_records < out->records_cap) memcpy((char *)out->records + 32 * out->n_records, &r, 32);
+            ++out->n_records;
+        }
+        g.applyAdamRound();
+    }
+    if (out->adam_state)
+        for (size_t i = 0; i < nodes.size(); ++i) nodes[i].dTree.bsdfSamplingFractionOptimizer.exportState(out->adam_state + 6 * i);
+    return PPG_OK;
+}
 int ppgo_path_length_histogram(ppgo_ctx *ctx, uint64_t *out) { memcpy(out, ctx->gpt.m_lenHist, sizeof ctx->gpt.m_lenHist); return PPG_OK; }
 int ppgo_set_stop_hook(ppgo_ctx *ctx, ppg_stop_hook hook, void *user) { ctx->gpt.stopHook = hook; ctx->gpt.stopHookUser = user; return PPG_OK; }
 int ppgo_set_pass_hook(ppgo_ctx *ctx, ppg_pass_hook hook, void *user) { ctx->gpt.passHook = hook; ctx->gpt.passHookUser = user; return PPG_OK; }

@@ -73,6 +73,12 @@ int ppgo_work_counters(ppgo_ctx *ctx, uint64_t *out8);
 int ppgo_path_length_histogram(ppgo_ctx *ctx, uint64_t *out);
 /* the tests' switch of include/ppg_testhooks.h (ppg_debug_set_defer_depth), same meaning */
 int ppgo_debug_set_defer_depth(ppgo_ctx *ctx, int32_t depth);
+/* ppg_debug_commit of include/ppg_testhooks.h, same arrays: every vertex a Vertex with dTree = STree::dTreeWrapper(p, voxel) and the sampler
+   at (key, dim + 3 v), through Vertex::commit with the round's code numbering; then applyAdamRound.  The route only decides whether the
+   call is refused (as the product refuses it); keys = the keys of the optimiser's records (no "splat only" records exist here). */
+struct ppg_debug_commit_in;
+struct ppg_debug_commit_out;
+int ppgo_debug_commit(ppgo_ctx *ctx, const struct ppg_debug_commit_in *in, struct ppg_debug_commit_out *out);
 int ppgo_set_adam_regions(ppgo_ctx *ctx, int32_t regions);  /* = ppg_set_adam_regions */
 int ppgo_set_pass_hook(ppgo_ctx *ctx, ppg_pass_hook hook, void *user);
 /* host-memory counterparts of ppg_adam_records / ppg_adam_records_replace (valid inside the round hook) */

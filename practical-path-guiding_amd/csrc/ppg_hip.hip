@@ -495,6 +495,7 @@ struct ppg_ctx {
     int ldsNodes = 0, ldsTris = 0;  // scene part cached in LDS by k_trace
     float treeMin[3], treeMax[3], treeExt[3];
     bool isBuilt = false, isFinalIter = false, doNee = false;
+    bool iterOpen = false;  // between ppg_begin_iteration(ctx, 0) and ppg_build_sdtree: the building tree takes records (ppg_debug_commit)
     int iter = 0, passesRendered = 0, passesRenderedThisIter = 0, passesLocal = 0;
     std::chrono::steady_clock::time_point startTime, passStart;
     std::atomic<bool> cancelled{false};
@@ -621,6 +622,24 @@ int uploadTree(ppg_ctx *ctx, bool nodes) {
     return PPG_OK;
 }
 
+// The depth of an S-tree (children[2 i], children[2 i + 1]; 0, 0 = a leaf; a child's index is above its parent's: one forward pass) —
+// levels below the root of its deepest leaf — and whether the box spatial filter's splat can walk it (include/ppg_testhooks.h
+// PPG_STREE_MAX_DEPTH).  PPG_ERR_INVALID: a child index that is not above its parent's or beyond the array.
+int streeDepthCheck(const uint32_t *children, uint32_t n_nodes, int32_t spatial_filter, uint32_t *depth) {
+    std::vector<uint32_t> d(n_nodes, 0u);
+    uint32_t deepest = 0;
+    for (uint32_t i = 0; i < n_nodes; ++i) {
+        if (children[2 * (size_t)i] == 0) { deepest = std::max(deepest, d[i]); continue; }
+        for (int c = 0; c < 2; ++c) {
+            const uint32_t k = children[2 * (size_t)i + c];
+            if (k <= i || k >= n_nodes) return PPG_ERR_INVALID;
+            d[k] = d[i] + 1u;
+        }
+    }
+    *depth = deepest;
+    return (spatial_filter == SF_BOX && deepest > (uint32_t)PPG_STREE_MAX_DEPTH) ? PPG_ERR_NOMEM : PPG_OK;
+}
+
 // STree::refine (GP:957-998) + subdivide (GP:876-895) on the device (k_refine_count → scans → k_refine_fill, ppg_kernels.h);
 // the host mirror (node array, leaf headers) is then downloaded — it feeds the statistics log, the dumps and the readers.
 int refineDevice(ppg_ctx *ctx, size_t sTreeThreshold, int maxMB) {
@@ -659,6 +678,14 @@ int refineDevice(ppg_ctx *ctx, size_t sTreeThreshold, int maxMB) {
     HIP_CHECK(hipStreamSynchronize(s));
     nodes.resize((size_t)nNew);
     for (size_t i = 0; i < nodes.size(); ++i) { nodes[i].axis = st[i].x; nodes[i].child[0] = (uint32_t)st[i].y; nodes[i].child[1] = (uint32_t)st[i].z; }
+    if (ctx->spatialFilter == SF_BOX) {  // stree_record_box walks this tree with a stack of 96 entries (DESIGN.md "Stack bounds of the splats")
+        std::vector<uint32_t> ch(2 * nodes.size());
+        for (size_t i = 0; i < nodes.size(); ++i) { ch[2 * i] = nodes[i].child[0]; ch[2 * i + 1] = nodes[i].child[1]; }
+        uint32_t depth = 0;
+        const int rc = streeDepthCheck(ch.data(), (uint32_t)nodes.size(), ctx->spatialFilter, &depth);
+        if (rc == PPG_ERR_INVALID) { ctx->error = "internal: an S-tree child that is not above its parent"; return PPG_ERR_STATE; }
+        if (rc) { ctx->error = "S-tree deeper than " + std::to_string(PPG_STREE_MAX_DEPTH) + " levels (" + std::to_string(depth) + ") with the box spatial filter"; return rc; }
+    }
     return PPG_OK;
 }
 
@@ -756,6 +783,7 @@ int buildSDTree(ppg_ctx *ctx, ppg_tree_stats *st) {  // GP:1115-1189
         st->n_leaves = (uint32_t)nPoints; st->n_stree_nodes = (uint32_t)ctx->snodes.size(); st->n_dtree_nodes = totalNodes;
     }
     ctx->isBuilt = true;
+    ctx->iterOpen = false;
     return PPG_OK;
 }
 
@@ -2050,7 +2078,7 @@ int beginRender(ppg_ctx *ctx) {  // GP:1519-1550
         ctx->dfsCur = 0; ctx->dfsCount = 1;
     }
     ctx->nSamplingNodes = 1; ctx->nBuildingNodes = 0;
-    ctx->iter = 0; ctx->isFinalIter = false; ctx->isBuilt = false;
+    ctx->iter = 0; ctx->isFinalIter = false; ctx->isBuilt = false; ctx->iterOpen = false;
     size_t n = (size_t)ctx->W * ctx->H;
     HIP_CHECK(hipMemsetAsync(ctx->d_film.p, 0, 3 * n * 4, ctx->stream));
     HIP_CHECK(hipMemsetAsync(ctx->d_filmW.p, 0, n * 4, ctx->stream));
@@ -2080,10 +2108,13 @@ int beginRender(ppg_ctx *ctx) {  // GP:1519-1550
 
 int beginIteration(ppg_ctx *ctx, bool isFinal) {  // GP:1378-1381
     ctx->isFinalIter = isFinal;
+    ctx->iterOpen = false;
     size_t n = (size_t)ctx->W * ctx->H;
     HIP_CHECK(hipMemsetAsync(ctx->d_film.p, 0, 3 * n * 4, ctx->stream));
     HIP_CHECK(hipMemsetAsync(ctx->d_filmW.p, 0, n * 4, ctx->stream));
-    return resetSDTree(ctx);
+    const int rc = resetSDTree(ctx);
+    ctx->iterOpen = rc == PPG_OK && !isFinal;
+    return rc;
 }
 
 int dumpSDTreeFile(ppg_ctx *ctx, const char *path);
@@ -3262,6 +3293,183 @@ int ppg_query_sample(ppg_ctx *ctx, uint32_t n, const float *positions, uint64_t 
     hipLaunchKernelGGL(k_query_sample, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->devTree(), n, dp.p, (unsigned long long)seed, dout.p);
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     HIP_CHECK(hipMemcpy(dirs_out, dout.p, 12 * (size_t)n, hipMemcpyDeviceToHost));
+    return PPG_OK;
+}
+
+int ppg_debug_stree_depth(const uint32_t *children, uint32_t n_nodes, int32_t spatial_filter, uint32_t *depth) {  // include/ppg_testhooks.h
+    if (!children || !depth || n_nodes == 0) return PPG_ERR_INVALID;
+    return streeDepthCheck(children, n_nodes, spatial_filter, depth);
+}
+
+// ---- ppg_debug_commit (include/ppg_testhooks.h): explicit vertices through the commit and the round end of a batch ----
+// the host-side checks of ppg_debug_commit: nullptr when the arrays may be read and the counts hold, else the complaint
+static const char *debugCommitCheck(const ppg_debug_commit_in *in, int32_t max_vertices, int32_t round, int32_t positions_known, uint32_t flag_shift) {
+    if (!in) return "ppg_debug_commit: in is NULL";
+    if (in->route < PPG_DEBUG_COMMIT || in->route > PPG_DEBUG_COMMIT_RECORDS_SPLIT) return "ppg_debug_commit: route: no such route";
+    if (in->n_paths >= PPG_ADAM_DEFER_PATH_BIT) return "ppg_debug_commit: n_paths must be below 2^26";
+    if (max_vertices < 1 || max_vertices > PPG_MAX_VERTICES) return "ppg_debug_commit: the context has no vertex slots";
+    if (in->n_paths && (!in->nv || !in->key || !in->dim)) return "ppg_debug_commit: nv, key and dim are needed per path";
+    uint64_t sum = 0;
+    for (uint32_t i = 0; i < in->n_paths; ++i) {
+        if (in->nv[i] > (uint32_t)max_vertices) return "ppg_debug_commit: nv: a path has more vertices than the context's max_vertices";
+        sum += in->nv[i];
+    }
+    if (sum != in->n_vertices) return "ppg_debug_commit: n_vertices is not the sum of nv";
+    if (sum && (!in->p || !in->d || !in->radiance || !in->throughput || !in->bsdf_val || !in->wo_pdf || !in->bsdf_pdf || !in->dtree_pdf || !in->is_delta))
+        return "ppg_debug_commit: a per-vertex array is NULL";
+    if (in->route >= PPG_DEBUG_COMMIT_RECORDS) {
+        if (!round) return "ppg_debug_commit: route: the record routes need a round of the optimiser (a bsdfSamplingFractionLoss and a built tree)";
+        if (!positions_known) return "ppg_debug_commit: route: the record routes need known record positions (no box spatial filter, no kickstart luminaire sampling)";
+        if (flag_shift >= 63u) return "ppg_debug_commit: route: the S-tree leaves no key bit for the record routes";
+    }
+    return nullptr;
+}
+
+int ppg_debug_commit(ppg_ctx *ctx, const ppg_debug_commit_in *in, ppg_debug_commit_out *out) {
+    if (!ctx) return PPG_ERR_INVALID;
+    NEED_TREE
+    if (!ctx->iterOpen || ctx->inHook) { ctx->error = "ppg_debug_commit: only between ppg_begin_iteration(ctx, 0) and ppg_build_sdtree, outside the round hook"; return PPG_ERR_STATE; }
+    if (ctx->passHook) { ctx->error = "ppg_debug_commit: not while a round hook is installed (ppg_set_pass_hook): it may replace the round's records"; return PPG_ERR_STATE; }
+    if (!out) { ctx->error = "ppg_debug_commit: out is NULL"; return PPG_ERR_INVALID; }
+    const bool round = ctx->loss != LOSS_NONE && ctx->isBuilt;
+    const bool known = recordPositionsKnown(ctx->spatialFilter, ctx->doNee, ctx->nee);
+    const unsigned int flagShift = adamFlagShift(ctx->snodes.size());
+    if (const char *why = debugCommitCheck(in, ctx->maxVertices, round ? 1 : 0, known ? 1 : 0, flagShift)) { ctx->error = why; return PPG_ERR_INVALID; }
+    if ((out->keys_cap && !out->keys) || (out->records_cap && !out->records)) { ctx->error = "ppg_debug_commit: out: a capacity without its array"; return PPG_ERR_INVALID; }
+    if (round && ctx->snodes.size() >= (1u << 24)) { ctx->error = "S-tree exceeds 2^24 nodes with a bsdfSamplingFractionLoss"; return PPG_ERR_NOMEM; }
+    ctx->quiesce();
+    hipStream_t s = ctx->stream;
+    const unsigned int n = in->n_paths, nNodes = (unsigned int)ctx->snodes.size();
+    const bool records = in->route >= PPG_DEBUG_COMMIT_RECORDS;
+    const bool split = in->route == PPG_DEBUG_COMMIT_SPLIT || in->route == PPG_DEBUG_COMMIT_RECORDS_SPLIT;
+    out->committed = 0; out->n_keys = 0; out->n_records = 0;
+    size_t nRecords = 0;
+    if (n) {
+        // the arrays, and the paths of a batch over them (one array per field, as allocPaths lays them out)
+        unsigned int slots = 1;
+        std::vector<unsigned int> first(n), lateList;
+        std::vector<unsigned char> lateFlag(n, 0);
+        {
+            uint64_t f = 0;
+            for (unsigned int i = 0; i < n; ++i) {
+                first[i] = (unsigned int)f; f += in->nv[i]; slots = std::max(slots, in->nv[i]);
+                if (split && in->late && in->late[i]) { lateFlag[i] = 1; lateList.push_back(i); }
+            }
+            if (f > 0xfffffff0ull) { ctx->error = "ppg_debug_commit: n_vertices: too many vertices"; return PPG_ERR_INVALID; }
+        }
+        const size_t nvx = (size_t)in->n_vertices, nv4 = (size_t)slots * n * sizeof(float4);
+        const bool filtered = ctx->spatialFilter != SF_NEAREST;
+        DebugBuf aNv, aKey, aDim, aFirst, aP, aD, aRad, aThr, aBsdf, aWo, aBp, aDp, aDelta, bMisc, bVd, bVthr, bVbsdf, bVrad, bVo, bVvox, bPix, bStats, bLate, bList, bListN;
+        HIP_CHECK(aNv.fill(in->nv, (size_t)n * 4)); HIP_CHECK(aKey.fill(in->key, (size_t)n * 4)); HIP_CHECK(aDim.fill(in->dim, (size_t)n * 4));
+        HIP_CHECK(aFirst.fill(first.data(), (size_t)n * 4));
+        HIP_CHECK(aP.fill(in->p, nvx * 12)); HIP_CHECK(aD.fill(in->d, nvx * 12)); HIP_CHECK(aRad.fill(in->radiance, nvx * 12));
+        HIP_CHECK(aThr.fill(in->throughput, nvx * 12)); HIP_CHECK(aBsdf.fill(in->bsdf_val, nvx * 12));
+        HIP_CHECK(aWo.fill(in->wo_pdf, nvx * 4)); HIP_CHECK(aBp.fill(in->bsdf_pdf, nvx * 4)); HIP_CHECK(aDp.fill(in->dtree_pdf, nvx * 4));
+        HIP_CHECK(aDelta.fill(in->is_delta, nvx));
+        HIP_CHECK(bMisc.fill(nullptr, (size_t)n * sizeof(uint4)));
+        HIP_CHECK(bVd.fill(nullptr, nv4)); HIP_CHECK(bVthr.fill(nullptr, nv4)); HIP_CHECK(bVbsdf.fill(nullptr, nv4)); HIP_CHECK(bVrad.fill(nullptr, nv4));
+        if (filtered) { HIP_CHECK(bVo.fill(nullptr, nv4)); HIP_CHECK(bVvox.fill(nullptr, nv4)); }
+        HIP_CHECK(bPix.fill(nullptr, (size_t)n * 4));
+        const int grid = wavefrontGrid(ctx->nBlocks, ctx->tuneBlocksSmall, ctx->tuneSmallPaths, n, ctx->queues.cap);
+        HIP_CHECK(bStats.fill(nullptr, (size_t)grid * sizeof(BlockStats)));
+        HIP_CHECK(hipMemsetAsync(bStats.p, 0, (size_t)grid * sizeof(BlockStats), s));
+        HIP_CHECK(bLate.fill(lateFlag.data(), n));
+        const unsigned long long listN = lateList.size();
+        HIP_CHECK(bList.fill(lateList.data(), lateList.size() * 4)); HIP_CHECK(bListN.fill(&listN, 8));
+        hipLaunchKernelGGL(k_iota, dim3((n + 255) / 256), dim3(256), 0, s, (unsigned int *)bPix.p, n);
+        PathState P{};
+        P.n_paths = n; P.n_pix = n; P.pixels = (const unsigned int *)bPix.p;
+        P.misc = {(uint4 *)bMisc.p, 1u};
+        P.v_d = {(float4 *)bVd.p, 1u}; P.v_thr = {(float4 *)bVthr.p, 1u}; P.v_bsdf = {(float4 *)bVbsdf.p, 1u}; P.v_rad = {(float4 *)bVrad.p, 1u};
+        P.v_o = {filtered ? (float4 *)bVo.p : nullptr, 1u}; P.v_vox = {filtered ? (float4 *)bVvox.p : nullptr, 1u};
+        const DebugCommitArrays A{(const unsigned int *)aNv.p, (const unsigned int *)aKey.p, (const unsigned int *)aDim.p, (const unsigned int *)aFirst.p,
+                                  (const float *)aP.p, (const float *)aD.p, (const float *)aRad.p, (const float *)aThr.p, (const float *)aBsdf.p,
+                                  (const float *)aWo.p, (const float *)aBp.p, (const float *)aDp.p, (const unsigned char *)aDelta.p};
+        hipLaunchKernelGGL(k_debug_commit_fill, dim3((n + 255) / 256), dim3(256), 0, s, P, ctx->devTree(), A, slots);
+        HIP_CHECK(hipGetLastError());
+        // the round's state, as prepareBatch sets it
+        ctx->adamActive = round; ctx->adamFast = round && known; ctx->sortedCommit = records; ctx->adamFlagShift = flagShift;
+        struct RoundEnd { ppg_ctx *c; ~RoundEnd() { c->adamActive = false; } } roundEnd{ctx};
+        const unsigned char *late = split ? (const unsigned char *)bLate.p : nullptr;
+        if (round && !ctx->adamFast) {  // positions handed out as the records are made (prepareBatch)
+            const size_t cap = std::max<size_t>((size_t)1 << 16, std::min<size_t>((size_t)48 * n, 0xfffffff0u));
+            HIP_CHECK(ctx->d_adamKeys[0].reserve(cap)); HIP_CHECK(ctx->d_adamRecs.reserve(cap));
+            HIP_CHECK(hipMemsetAsync(ctx->d_adamCount.p, 0, 8, s));
+        }
+        if (ctx->adamFast) {  // positions = exclusive scan of the vertex counts; a late path reserves max_vertices (finishPaths)
+            HIP_CHECK(ctx->d_adamNv.reserve(n)); HIP_CHECK(ctx->d_adamBase.reserve(n));
+            hipLaunchKernelGGL(k_path_nv, dim3((n + 255) / 256), dim3(256), 0, s, P, ctx->d_adamNv.p, late, (unsigned int)ctx->maxVertices);
+            size_t bytes = 0;
+            HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, ctx->d_adamNv.p, ctx->d_adamBase.p, 0u, (size_t)n, rocprim::plus<unsigned int>(), s));
+            HIP_CHECK(ctx->d_sortTemp.reserve(std::max<size_t>(bytes, 16)));
+            HIP_CHECK(rocprim::exclusive_scan((void *)ctx->d_sortTemp.p, bytes, ctx->d_adamNv.p, ctx->d_adamBase.p, 0u, (size_t)n, rocprim::plus<unsigned int>(), s));
+            unsigned int sumBase = 0, lastNv = 0;
+            HIP_CHECK(hipMemcpyAsync(&sumBase, ctx->d_adamBase.p + (n - 1), 4, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(&lastNv, ctx->d_adamNv.p + (n - 1), 4, hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipStreamSynchronize(s));
+            nRecords = (size_t)sumBase + lastNv;
+            int rc = reserveRoundRecords(ctx, nRecords);
+            if (rc) return rc;
+        }
+        HIP_CHECK(ctx->d_nv8.reserve(n));
+        hipLaunchKernelGGL(k_commit_prepare, dim3((n + 255) / 256), dim3(256), 0, s, P, (uint4 *)nullptr, ctx->d_nv8.p, late);
+        Queues Q = ctx->queues;
+        Q.stats = (BlockStats *)bStats.p; Q.n_blocks = (unsigned int)grid;
+        RenderParams R = ctx->params();
+        R.img_pixels = n;
+        {
+            CommitLaunch a{grid, s, P, ctx->devTree(), R, Q, ctx->d_nv8.p, nullptr, nullptr, ctx->d_splat.p, ctx->adamFlagShift};
+            timedLaunch(ctx, commitName(records), n, [&] { launchCommitKernels(ctx, a, records); });
+        }
+        if (split) {  // launchCommit(.., CommitSet::List)
+            hipLaunchKernelGGL(k_commit_prepare_list, dim3(std::max(1, std::min(grid, 1024))), dim3(256), 0, s, P, (const unsigned int *)bList.p, (const unsigned long long *)bListN.p, ctx->d_nv8.p);
+            CommitLaunch a{grid, s, P, ctx->devTree(), R, Q, ctx->d_nv8.p, (const unsigned int *)bList.p, (const unsigned long long *)bListN.p, ctx->d_splat.p, ctx->adamFlagShift};
+            timedLaunch(ctx, commitName(records), 0, [&] { launchCommitKernels(ctx, a, records); });
+        }
+        HIP_CHECK(hipGetLastError());
+        if (round) {  // optimiserRound
+            if (!ctx->adamFast) {
+                unsigned int cnt[2] = {0, 0};
+                HIP_CHECK(hipMemcpyAsync(cnt, ctx->d_adamCount.p, 8, hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipStreamSynchronize(s));
+                if (cnt[1]) { ctx->error = "Adam record buffer overflow (box spatial filter / next-event estimation with a bsdfSamplingFractionLoss)"; return PPG_ERR_NOMEM; }
+                nRecords = cnt[0];
+            }
+            int rc = applyAdamRound(ctx, nRecords);
+            if (rc) return rc;
+        }
+        { int rc = foldWeights(ctx); if (rc) return rc; }  // (joins the side streams of the round end)
+        HIP_CHECK(hipStreamSynchronize(s));
+        std::vector<BlockStats> bs((size_t)grid);
+        HIP_CHECK(hipMemcpy(bs.data(), bStats.p, bs.size() * sizeof(BlockStats), hipMemcpyDeviceToHost));
+        for (const BlockStats &b : bs) out->committed += b.committed;
+        if (round && nRecords) {  // the sorted keys without the holes; the optimiser's records are those without the flag bit
+            std::vector<unsigned long long> keys(nRecords);
+            std::vector<unsigned int> idx(nRecords);
+            std::vector<AdamRec> recs(nRecords);
+            static_assert(sizeof(AdamRec) == sizeof(ppg_adam_record), "AdamRec = ppg_adam_record");
+            HIP_CHECK(hipMemcpy(keys.data(), ctx->d_adamKeys[1].p, nRecords * 8, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(idx.data(), ctx->d_adamIdx[1].p, nRecords * 4, hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(recs.data(), ctx->d_adamRecs.p, nRecords * sizeof(AdamRec), hipMemcpyDeviceToHost));
+            const unsigned long long flag = records ? (1ull << flagShift) : ~0ull;
+            for (size_t k = 0; k < nRecords; ++k) {
+                if (keys[k] == ~0ull) continue;
+                if (out->n_keys < out->keys_cap) out->keys[out->n_keys] = keys[k];
+                ++out->n_keys;
+                if (keys[k] >= flag) continue;
+                if (idx[k] >= nRecords) { ctx->error = "internal: a record index beyond the round's positions"; return PPG_ERR_STATE; }
+                if (out->n_records < out->records_cap) memcpy(&out->records[out->n_records], &recs[idx[k]], sizeof(AdamRec));
+                ++out->n_records;
+            }
+        }
+    }
+    if (out->adam_state) {
+        DebugBuf st;
+        HIP_CHECK(st.fill(nullptr, (size_t)nNodes * 24));
+        hipLaunchKernelGGL((k_adam_state<false>), dim3((nNodes + 255u) / 256u), dim3(256), 0, s, ctx->d_hdr.p, nNodes, (unsigned int *)st.p);
+        HIP_CHECK(hipStreamSynchronize(s));
+        HIP_CHECK(hipMemcpy(out->adam_state, st.p, (size_t)nNodes * 24, hipMemcpyDeviceToHost));
+    }
     return PPG_OK;
 }
 

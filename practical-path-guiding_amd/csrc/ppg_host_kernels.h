@@ -841,4 +841,34 @@ static __global__ void k_query_sample(DevTree T, unsigned int n, const float *po
     out[3 * i] = d.x; out[3 * i + 1] = d.y; out[3 * i + 2] = d.z;
 }
 
+// ppg_debug_commit (include/ppg_testhooks.h): the paths and vertex slots of a PathState from explicit arrays, as k_shade leaves them — the
+// per-path word (key, dim, nV), per vertex the leaf and voxel size of stree_lookup at p.  first[i]: path i's first vertex in the arrays.
+struct DebugCommitArrays {
+    const unsigned int *nv, *key, *dim, *first;
+    const float *p, *d, *radiance, *throughput, *bsdf_val, *wo_pdf, *bsdf_pdf, *dtree_pdf;
+    const unsigned char *is_delta;
+};
+static __global__ void k_debug_commit_fill(PathState P, DevTree T, DebugCommitArrays A, unsigned int slots) {
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P.n_paths) return;
+    unsigned int nv = A.nv[i];
+    if (nv > slots) nv = slots;  // (the host checked it)
+    P.misc[i] = make_uint4(A.key[i], A.dim[i], nv << FL_NV_SHIFT, 0u);
+    for (unsigned int v = 0; v < nv; ++v) {
+        const size_t g = (size_t)A.first[i] + v, vi = (size_t)v * P.n_paths + i;
+        F3 vox;
+        const F3 p = f3(A.p[3 * g], A.p[3 * g + 1], A.p[3 * g + 2]);
+        const int leaf = stree_lookup(T, p, vox);
+        P.v_d[vi] = make_float4(A.d[3 * g], A.d[3 * g + 1], A.d[3 * g + 2], A.wo_pdf[g]);
+        P.v_thr[vi] = make_float4(A.throughput[3 * g], A.throughput[3 * g + 1], A.throughput[3 * g + 2], A.bsdf_pdf[g]);
+        P.v_bsdf[vi] = make_float4(A.bsdf_val[3 * g], A.bsdf_val[3 * g + 1], A.bsdf_val[3 * g + 2], A.dtree_pdf[g]);
+        P.v_rad[vi] = make_float4(A.radiance[3 * g], A.radiance[3 * g + 1], A.radiance[3 * g + 2],
+                                  __uint_as_float((unsigned int)leaf | (A.is_delta[g] ? 0x80000000u : 0u)));
+        if (P.v_o) {
+            P.v_o[vi] = make_float4(p.x, p.y, p.z, 0.0f);
+            P.v_vox[vi] = make_float4(vox.x, vox.y, vox.z, 0.0f);
+        }
+    }
+}
+
 #endif

@@ -629,7 +629,7 @@ D void dtree_record_t(const TR &tree, float px, float py, float irradiance, floa
         // ix * 2^-l is exactly what the reference's running `origin + childSize` additions produce — and an entry packs into 64 bits:
         // node (16) | level (5) | ix (21) | iy (21).  With `box_stack` (k_commit, k_splat_sorted: an LDS column per lane) the first
         // PPG_BOX_STACK entries never leave the CU; a 64-entry array in scratch memory — 1 KB per lane, far beyond L1 — was the whole stack before.
-        unsigned long long over[64];
+        unsigned long long over[64];  // a D-tree whose deepest node lies d below the root needs 3 d + 1 entries; DTree::reset caps d at 19: 58
         int sp = 0;
         auto push = [&](unsigned long long v) {
             if (box_stack && sp < PPG_BOX_STACK) box_stack[sp * box_stride] = v; else over[box_stack ? sp - PPG_BOX_STACK : sp] = v;
@@ -737,7 +737,7 @@ D void stree_record_box(const DevTree &T, F3 p, F3 vox, Rec rec, int dfilter, in
     rec.statisticalWeight /= volume;
     F3 min1 = p - vox * 0.5f, max1 = p + vox * 0.5f;
     struct E { int node; float mx, my, mz, sx, sy, sz; };
-    E st[96];
+    E st[96];  // an interior node d levels below the root is popped with d entries left and pushes two: d <= 94, leaves down to level 95; the host refines no tree deeper than PPG_STREE_MAX_DEPTH = 94
     int sp = 0;
     st[sp++] = E{0, T.aabb_min[0], T.aabb_min[1], T.aabb_min[2], T.aabb_ext[0], T.aabb_ext[1], T.aabb_ext[2]};
     while (sp) {

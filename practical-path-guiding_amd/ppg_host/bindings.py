@@ -366,6 +366,24 @@ DEBUG_DIRECT_DTYPE = np.dtype([("emitter", "<i4"), ("d", "<f4", 3), ("dist", "<f
                                ("value", "<f4", 3), ("_pad", "<f4", 3)])
 
 
+class DebugCommitIn(C.Structure):  # ppg_debug_commit_in
+    _fields_ = [("route", C.c_int32), ("n_paths", C.c_uint32), ("n_vertices", C.c_uint64),
+                ("nv", C.POINTER(C.c_uint32)), ("key", C.POINTER(C.c_uint32)), ("dim", C.POINTER(C.c_uint32)), ("late", C.POINTER(C.c_uint8)),
+                ("p", C.POINTER(C.c_float)), ("d", C.POINTER(C.c_float)), ("radiance", C.POINTER(C.c_float)), ("throughput", C.POINTER(C.c_float)),
+                ("bsdf_val", C.POINTER(C.c_float)), ("wo_pdf", C.POINTER(C.c_float)), ("bsdf_pdf", C.POINTER(C.c_float)),
+                ("dtree_pdf", C.POINTER(C.c_float)), ("is_delta", C.POINTER(C.c_uint8))]
+
+
+class DebugCommitOut(C.Structure):  # ppg_debug_commit_out
+    _fields_ = [("committed", C.c_uint64), ("n_keys", C.c_uint64), ("keys_cap", C.c_uint64), ("keys", C.POINTER(C.c_uint64)),
+                ("n_records", C.c_uint64), ("records_cap", C.c_uint64), ("records", C.c_void_p), ("adam_state", C.POINTER(C.c_uint32))]
+
+
+# ppg_adam_record (include/ppg.h)
+ADAM_RECORD_DTYPE = np.dtype([("key", np.uint64), ("product", np.float32), ("wo_pdf", np.float32), ("bsdf_pdf", np.float32),
+                              ("dtree_pdf", np.float32), ("weight", np.float32), ("pad", np.float32)])
+
+
 class EnvMap(C.Structure):
     """ppg_envmap (include/ppg.h).  Scene descriptions carry it as a dict: rgb (float32 [height, width, 3]), scale, to_world (9 floats)."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("rgb", C.POINTER(C.c_float)), ("scale", C.c_float), ("to_world", C.c_float * 9)]
@@ -785,6 +803,48 @@ class Engine:
         assert out.itemsize == C.sizeof(DebugDirect)
         self._call("debug_sample_direct", C.c_uint32(ref.shape[0]), _fp(ref), _fp(ref_n), _fp(u), out.ctypes.data_as(C.POINTER(DebugDirect)))
         return out
+
+    DEBUG_COMMIT_ROUTES = dict(commit=0, commit_split=1, records=2, records_split=3)
+
+    def debug_commit(self, route, nv, key, dim, p, d, radiance, throughput, bsdf_val, wo_pdf, bsdf_pdf, dtree_pdf, is_delta, late=None,
+                     n_vertices=None, records_cap=None):
+        """ppg_debug_commit / ppgo_debug_commit (include/ppg_testhooks.h): explicit vertices through the commit of a batch and the round's
+        end.  Per path nv, key, dim (uint32 [n]) and late (bool [n] or None); per vertex, path after path, p, d, radiance, throughput,
+        bsdf_val (float32 [m, 3]), wo_pdf, bsdf_pdf, dtree_pdf (float32 [m]) and is_delta (bool [m]).  -> dict(committed, keys uint64 [k],
+        records (ADAM_RECORD_DTYPE) in key order, adam_state uint32 [n_stree_nodes, 6]).  n_vertices: what to claim instead of len(wo_pdf); records_cap:
+        room for the keys and records (default 64 per vertex)."""
+        u32 = lambda a: np.ascontiguousarray(a, np.uint32).reshape(-1)
+        f3 = lambda a: np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+        f1 = lambda a: np.ascontiguousarray(a, np.float32).reshape(-1)
+        nv, key, dim = u32(nv), u32(key), u32(dim)
+        p, d, radiance, throughput, bsdf_val = f3(p), f3(d), f3(radiance), f3(throughput), f3(bsdf_val)
+        wo_pdf, bsdf_pdf, dtree_pdf = f1(wo_pdf), f1(bsdf_pdf), f1(dtree_pdf)
+        is_delta = np.ascontiguousarray(is_delta, np.uint8).reshape(-1)
+        m = wo_pdf.shape[0]
+        assert key.shape[0] == nv.shape[0] == dim.shape[0]
+        assert all(a.shape[0] == m for a in (p, d, radiance, throughput, bsdf_val, bsdf_pdf, dtree_pdf, is_delta))
+        late8 = None if late is None else np.ascontiguousarray(late, np.uint8).reshape(-1)
+        assert late8 is None or late8.shape[0] == nv.shape[0]
+        arg = DebugCommitIn()
+        arg.route = self.DEBUG_COMMIT_ROUTES[route] if isinstance(route, str) else int(route)
+        arg.n_paths = nv.shape[0]
+        arg.n_vertices = m if n_vertices is None else int(n_vertices)
+        arg.nv, arg.key, arg.dim = _p(nv, C.c_uint32), _p(key, C.c_uint32), _p(dim, C.c_uint32)
+        arg.late = None if late8 is None else _p(late8, C.c_uint8)
+        arg.p, arg.d, arg.radiance, arg.throughput, arg.bsdf_val = _fp(p), _fp(d), _fp(radiance), _fp(throughput), _fp(bsdf_val)
+        arg.wo_pdf, arg.bsdf_pdf, arg.dtree_pdf, arg.is_delta = _fp(wo_pdf), _fp(bsdf_pdf), _fp(dtree_pdf), _p(is_delta, C.c_uint8)
+        n_nodes = int(self.sdtree_info().n_stree_nodes)
+        state = np.zeros((n_nodes, 6), np.uint32)
+        cap = int(records_cap) if records_cap is not None else 64 * m + 64  # (the box spatial filter: a record per leaf a voxel overlaps)
+        keys = np.zeros(cap, np.uint64)
+        recs = np.zeros(cap, ADAM_RECORD_DTYPE)
+        out = DebugCommitOut()
+        out.keys_cap = out.records_cap = cap
+        out.keys, out.records, out.adam_state = _p(keys, C.c_uint64), recs.ctypes.data_as(C.c_void_p), _p(state, C.c_uint32)
+        self._call("debug_commit", C.byref(arg), C.byref(out))
+        if max(out.n_keys, out.n_records) > cap:  # (the call has been applied; what did not fit was counted only)
+            raise PPGError(-5, "debug_commit: %d records exceed records_cap = %d" % (max(out.n_keys, out.n_records), cap))
+        return dict(committed=int(out.committed), keys=keys[:out.n_keys].copy(), records=recs[:out.n_records].copy(), adam_state=state)
 
     def set_material_textures(self, slots):
         """ppg_set_material_textures: one entry per material — a material dict (its specular_texture / alpha_texture / opacity_texture keys) or
