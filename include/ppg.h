@@ -101,9 +101,15 @@ enum {
                                       cosine hemisphere on the side opposite wi, weight = transmittance; cannot be two-sided */
     PPG_BSDF_PHONG = 12            /* phong.cpp:122-240: modified Phong, a glossy lobe pow(alpha, exponent) around the mirror direction plus a
                                       diffuse one, chosen by specularSamplingWeight = sAvg / (dAvg + sAvg); weight = eval / pdf of the whole */
+    ,
+    PPG_BSDF_NULL = 13             /* null.cpp:36-80: the pass-through BSDF, one component ENull | EFrontSide | EBackSide — sample() gives wo = -wi with
+                                      weight 1, pdf 1, eta 1; eval() and pdf() are 0 for every non-discrete query.  Not smooth: no D-tree, no
+                                      next-event estimation at it; the path takes Li's null branch (GP:2045-2075) and the emitter search and shadow
+                                      segments pass through it with transmittance 1.  Its usual use: the invisible carrier of an area emitter.
+                                      HIP library only, in the kernel family of the three lobes above */
 };
 #define PPG_BSDF_LAST PPG_BSDF_ROUGHPLASTIC /* the last type the CPU oracle knows */
-#define PPG_BSDF_LAST_HIP PPG_BSDF_PHONG    /* the last type the HIP library knows */
+#define PPG_BSDF_LAST_HIP PPG_BSDF_NULL     /* the last type the HIP library knows */
 enum {
     PPG_MAT_TWOSIDED = 1,          /* wrap the (one-sided) BRDF in twosided.cpp:100-180, same BRDF on both sides */
     PPG_MAT_NONLINEAR = 2,         /* plastic: nonlinear = true (plastic.cpp:164) */
@@ -113,7 +119,11 @@ enum {
                                       smooth/null hybrid — its sampled pass-through is recorded for the sampling-fraction optimiser
                                       (GP:2047-2068) */
     ,
-    PPG_MAT_FAST_APPROX = 16       /* roughdiffuse: useFastApprox = true (roughdiffuse.cpp:159-174); refused on every other type */
+    PPG_MAT_FAST_APPROX = 16,      /* roughdiffuse: useFastApprox = true (roughdiffuse.cpp:159-174); refused on every other type */
+    PPG_MAT_NORMALMAP = 32         /* bits 16..31 of `texture` name the RGB normal map of a `normalmap` adapter (normalmap.cpp:47-224) instead of a
+                                      bumpmap's displacement texture: n = 2 * texel - 1 in the unperturbed shading frame, NOT flipped towards the
+                                      geometric normal as bumpmap.cpp does.  HIP library only (the kernel family of the lobes); refused when that
+                                      half of `texture` is 0 */
 };
 enum { PPG_WRAP_REPEAT = 0, PPG_WRAP_MIRROR = 1, PPG_WRAP_CLAMP = 2, PPG_WRAP_ZERO = 3, PPG_WRAP_ONE = 4 }; /* ReconstructionFilter::EBoundaryCondition, mipmap.h:503-560 */
 
@@ -151,14 +161,21 @@ typedef struct ppg_material {
                              thindielectric / roughdielectric — in which case reflectance[] holds the texture's average
                              (Texture::getAverage, used by the plug-ins' configure() for the component sampling weights, plastic.cpp:191-204);
                              bits 16..31: 1 + index of the displacement texture of a `bumpmap` adapter around this BSDF (bumpmap.cpp:135-219:
-                             shading frame perturbed by the texture's gradient); 0 = none */
+                             shading frame perturbed by the texture's gradient) or, with PPG_MAT_NORMALMAP, of the normal map of a `normalmap`
+                             adapter (normalmap.cpp:108-124: shading frame around the texel's normal); 0 = none */
 } ppg_material;           /* 80 bytes; bitmaps on specular / alpha / opacity: ppg_set_material_textures */
 /* roughdiffuse, difftrans and phong (HIP library only).  PPG_MAT_TWOSIDED (not on difftrans), PPG_MAT_MASK and both halves of `texture` apply
    as they do to diffuse: bumpmap(mask(twosided(x))).  ppg_set_scene answers PPG_ERR_INVALID, names the material and leaves the context
    usable for: PPG_MAT_TWOSIDED on difftrans (twosided.cpp:84-88 refuses transmissive BSDFs); a phong whose reflectance and specular both
    have luminance 0 (specularSamplingWeight = 0 / 0); a negative or non-finite alpha / exponent; PPG_MAT_FAST_APPROX on another type; any slot
    of ppg_set_material_textures but `opacity`; a general ppg_set_microfacet entry; a coat (ppg_set_coatings); their use as a child of a blend
-   or as the blended record (ppg_set_blends); and, as for every type, a bitmap on a material of a sphere, disk or cylinder. */
+   or as the blended record (ppg_set_blends); and, as for every type, a bitmap on a material of a sphere, disk or cylinder.
+   PPG_MAT_NORMALMAP (HIP library only) follows the rules of a bump-mapped record — not on a sphere, disk or cylinder, not on the child of a
+   blend, normalmap(mask(twosided(x))) with x a leaf, a coat or a blend — and is refused, in the same way, when bits 16..31 of `texture` are 0.
+   A texel that decodes to the zero vector gives Mitsuba's NaN frame; keep such texels out of a normal map.
+   PPG_BSDF_NULL (HIP library only) is refused, in the same way, with PPG_MAT_TWOSIDED (twosided.cpp:84-88), PPG_MAT_MASK or any other flag, any
+   `texture` word or slot of ppg_set_material_textures, a general ppg_set_microfacet entry, a coat, as a child of a blend or as the blended
+   record, and on a sphere, disk or cylinder.  An emitter id on its triangles works as on any material. */
 
 typedef struct ppg_emitter {
     float radiance[3]; /* area light, mitsuba/src/emitters/area.cpp:104-109 */

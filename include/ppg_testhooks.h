@@ -2,7 +2,7 @@
  * ppg_testhooks.h — entry points of libppg_hip.so that exist for the tests only.  Not part of the drop-in boundary (include/ppg.h): nothing
  * a host of the integrator needs, no reference counterpart.
  *   host only   ppg_debug_build_bvh, ppg_debug_bvh_stats, ppg_debug_bvh_trace, ppg_debug_rfilter_table, ppg_debug_stree_depth
- *   a scene     ppg_debug_intersect, ppg_debug_intersect_mode, ppg_debug_sample_direct, ppg_debug_bsdf
+ *   a scene     ppg_debug_intersect, ppg_debug_intersect_mode, ppg_debug_sample_direct, ppg_debug_bsdf, ppg_debug_shading_frame
  *   a render    ppg_debug_set_defer_depth, ppg_debug_commit (inside an open training iteration)
  *   no scene    ppg_debug_math_eval, ppg_debug_math_checksum
  */
@@ -76,6 +76,20 @@ struct ppg_debug_hit {
     int32_t _pad;
 };  /* 80 bytes */
 int ppg_debug_intersect(struct ppg_ctx *ctx, uint32_t n, const float *rays, struct ppg_debug_hit *out, int32_t any_hit);
+
+/* The shading frame a textured BSDF is queried in, ray by ray (rays as for ppg_debug_intersect, closest hit): one small kernel of the top
+   kernel family whose lanes call what the render's shade_one calls — fill_isect_tex, then bump_frame (bumpmap.cpp:135-160) or normal_frame
+   (normalmap.cpp:108-124) where bits 16..31 of the material's texture word are set.  prim as above (-1: no hit, material = -1, the rest 0);
+   uv = its.uv (0 on a material that reads no bitmap, and on analytic shapes); n, s = the unperturbed shading frame's normal and tangent;
+   ps, pt, pn = the frame the nested BSDF is queried in (= s, t, n where no adapter ran); adapted = 1 where one ran. */
+struct ppg_debug_frame {
+    int32_t prim, material;
+    float uv[2];
+    float n[3], s[3];
+    float ps[3], pt[3], pn[3];
+    int32_t adapted;
+};  /* 80 bytes */
+int ppg_debug_shading_frame(struct ppg_ctx *ctx, uint32_t n, const float *rays, struct ppg_debug_frame *out);
 
 /* The same rays through the OTHER forms of the closest-hit traversal, each of which promises the same hit bit for bit (csrc/ppg_device.h,
    csrc/ppg_kernels.h); rays and records as above, mint as it stands except where noted.  stats_out (4 words, may be NULL) is zeroed, then:

@@ -2,7 +2,8 @@
  * ppg_debug_kernels.h — the kernels of the test hooks (include/ppg_testhooks.h) that run the render's own device functions, included by the
  * k_trace unit of a family (ppg_inst.hip): k_debug_intersect, the kernels of ppg_debug_intersect_mode and k_debug_sample_direct in the shapes family, which the hooks always use;
  * k_debug_bsdf in the ext family, k_debug_bsdf_coat in the coat family, which ppg_debug_bsdf uses for a scene with a coated material, and
- * k_debug_bsdf_blend in the blend family, which it uses for a scene with a blended one.  Every family holds k_debug_math_eval and
+ * k_debug_bsdf_blend in the blend family, which it uses for a scene with a blended one; k_debug_shading_frame in the top (lobes) family, which
+ * ppg_debug_shading_frame always uses.  Every family holds k_debug_math_eval and
  * k_debug_math_checksum (ppg_debug_math_*): the shared float math as this module compiled it, its own out-of-line dm_ copies included.
  */
 #ifndef PPG_DEBUG_KERNELS_H
@@ -226,6 +227,48 @@ static void launch_debug_bsdf(int grid, int block, hipStream_t stream, const Dev
 }
 #endif
 
+#if PPG_FAMILY == PPG_FAMILY_LOBES
+// ppg_debug_shading_frame: the closest hit, then what shade_one does for the frame of a textured BSDF — fill_isect_tex, and bump_frame or
+// normal_frame where the material's texture word names a displacement texture or a normal map
+__global__ void k_debug_shading_frame(DevScene S, unsigned int n, const float4 *rays, ppg_debug_frame *out) {
+    extern __shared__ int dbg_stack[];
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 ro = rays[2 * i], rd = rays[2 * i + 1];
+    const F3 o = f3(ro.x, ro.y, ro.z), d = f3(rd.x, rd.y, rd.z);
+    ppg_debug_frame r;
+    memset(&r, 0, sizeof r);
+    r.material = -1;
+    const Hit h = trace_closest4<false, true>(S, dbg_stack + threadIdx.x, (int)blockDim.x, o, d, ro.w, rd.w);
+    r.prim = h.prim;
+    if (h.prim >= 0) {
+        Isect I;
+        TexInfo X;
+        X.tex = 0u; X.u = 0.0f; X.v = 0.0f;
+        if (h.prim >= S.n_tris) fill_isect_analytic(S, h, o, d, I);
+        else fill_isect_tex<true>(S, h, d, I, X);
+        F3 ps = I.s, pt = I.t, pn = I.n;
+        if (X.tex >> 16) {
+            const int flags = __float_as_int(S.materials[PPG_MAT_STRIDE * (size_t)I.material + 2].w);
+            if (flags & PPG_MAT_NORMALMAP) normal_frame(S, I, X, ps, pt, pn);
+            else bump_frame(S, I, X, ps, pt, pn);
+            r.adapted = 1;
+        }
+        r.material = I.material;
+        r.uv[0] = X.u; r.uv[1] = X.v;
+        r.n[0] = I.n.x; r.n[1] = I.n.y; r.n[2] = I.n.z;
+        r.s[0] = I.s.x; r.s[1] = I.s.y; r.s[2] = I.s.z;
+        r.ps[0] = ps.x; r.ps[1] = ps.y; r.ps[2] = ps.z;
+        r.pt[0] = pt.x; r.pt[1] = pt.y; r.pt[2] = pt.z;
+        r.pn[0] = pn.x; r.pn[1] = pn.y; r.pn[2] = pn.z;
+    }
+    out[i] = r;
+}
+static void launch_debug_shading_frame(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_frame *out) {
+    hipLaunchKernelGGL(k_debug_shading_frame, dim3(grid), dim3(block), (size_t)PPG_LDS_STACK * block * sizeof(int), stream, S, n, rays, out);
+}
+#endif
+
 // ---- ppg_debug_math_eval / ppg_debug_math_checksum: include/ppg_mathcheck.h on the device, in every family's module ----
 #define k_debug_math_eval PPG_FAMILY_NAME(k_debug_math_eval)
 #define k_debug_math_checksum PPG_FAMILY_NAME(k_debug_math_checksum)
@@ -303,6 +346,9 @@ static void fill_debug_kernels(PathKernels &K) {
 #endif
 #if PPG_FAMILY >= PPG_FAMILY_EXT
     K.debug_bsdf = launch_debug_bsdf;
+#endif
+#if PPG_FAMILY == PPG_FAMILY_LOBES
+    K.debug_shading_frame = launch_debug_shading_frame;
 #endif
 }
 

@@ -36,7 +36,8 @@
                              //           sampleVisible = false), with or without analytic shapes
 #define PPG_FAMILY_COAT 3    // _coat     the coating / roughcoating adapters (ppg_set_coatings), whatever else the scene holds
 #define PPG_FAMILY_BLEND 4   // _blend    the blendbsdf / mixturebsdf combinators (ppg_set_blends), whatever else the scene holds
-#define PPG_FAMILY_LOBES 5   // _lobes    the roughdiffuse, difftrans and phong BSDFs (PPG_BSDF_ROUGHDIFFUSE ..), whatever else the scene holds
+#define PPG_FAMILY_LOBES 5   // _lobes    the roughdiffuse, difftrans and phong BSDFs (PPG_BSDF_ROUGHDIFFUSE ..), whatever else the scene holds; being the top
+                             //           family it also compiles the normalmap adapter and the null BSDF (PPG_NORMALMAP_NULL)
 #define PPG_FAMILIES 6
 #define PPG_SUFFIX_0
 #define PPG_SUFFIX_1 _shapes
@@ -52,6 +53,9 @@
 #define PPG_COAT (PPG_FAMILY >= PPG_FAMILY_COAT)
 #define PPG_BLEND (PPG_FAMILY >= PPG_FAMILY_BLEND)
 #define PPG_LOBES (PPG_FAMILY >= PPG_FAMILY_LOBES)
+// the normalmap adapter (PPG_MAT_NORMALMAP) and the null BSDF (PPG_BSDF_NULL): no family of their own — the top family, which holds
+// everything below it, compiles them, and sceneFamily sends a scene with either there
+#define PPG_NORMALMAP_NULL (PPG_FAMILY >= PPG_FAMILY_LOBES)
 #define PPG_CAT2(a, b) a##b
 #define PPG_CAT(a, b) PPG_CAT2(a, b)
 #define PPG_FAMILY_NAME(name) PPG_CAT(name, PPG_CAT(PPG_SUFFIX_, PPG_FAMILY))
@@ -223,7 +227,8 @@ struct DevScene {
     const float4 *shapes;
     int n_shapes;
     // a material is a roughdiffuse, difftrans or phong lobe: the scene runs the lobes kernels (PPG_LOBES), which alone compile them.  (It
-    // stands in the padding behind n_shapes: no other member and no kernel argument behind the scene moves.)
+    // stands in the padding behind n_shapes: no other member and no kernel argument behind the scene moves.)  Bit 0: such a lobe; bit 1: a
+    // normal-mapped or null material (PPG_NORMALMAP_NULL), which the same kernels alone compile.  No kernel reads it.
     int lobes;
     // ppg_set_microfacet with a general entry (extended kernels only, PPG_MFD): one float4 per material = (alphaV, PPG_MFDF_* bits,
     // alphaV texture: 1 + index as bits, -); nullptr otherwise
@@ -1041,6 +1046,19 @@ D void bump_frame(const DevScene &S, const Isect &I, const TexInfo &X, F3 &ps, F
     pt = cross3(pn, ps);
     if (dot3(pn, I.geoN) < 0) pn = pn * -1.0f;
 }
+#if PPG_NORMALMAP_NULL
+static __device__ __attribute__((noinline)) float4 tex_eval_slot(const DevTex *textures, unsigned int slot, float u, float v);
+// NormalMap::getFrame (normalmap.cpp:108-124): the frame (s, t, n) around the normal the RGB texel names in the unperturbed shading frame.
+// Unlike bumpmap.cpp it does not flip a normal that points against the geometric one.  (A texel that decodes to the zero vector gives
+// Mitsuba's NaN frame.)
+D void normal_frame(const DevScene &S, const Isect &I, const TexInfo &X, F3 &ps, F3 &pt, F3 &pn) {
+    const float4 c = tex_eval_slot(S.textures, X.tex >> 16, X.u, X.v);
+    const F3 n = f3(2 * c.x - 1, 2 * c.y - 1, 2 * c.z - 1);
+    pn = norm3(to_world(I, n));
+    ps = norm3(X.dpdu - pn * dot3(pn, X.dpdu));
+    pt = cross3(pn, ps);
+}
+#endif
 
 // AreaLight::eval (area.cpp:104-109)
 D F3 eval_Le(const DevScene &S, const Isect &I, F3 dir) {
@@ -1694,7 +1712,11 @@ D bool mat_backside_or_transmission(const Mat &M) {
     return (M.flags & (PPG_MAT_TWOSIDED | PPG_MAT_MASK)) || M.type == PPG_BSDF_DIELECTRIC || M.type == PPG_BSDF_THINDIELECTRIC ||
            M.type == PPG_BSDF_ROUGHDIELECTRIC;
 }
+#if PPG_NORMALMAP_NULL
+D bool mat_has_null(const Mat &M) { return mat_masked(M) || M.type == PPG_BSDF_THINDIELECTRIC || M.type == PPG_BSDF_NULL; }  // getType() & ENull
+#else
 D bool mat_has_null(const Mat &M) { return mat_masked(M) || M.type == PPG_BSDF_THINDIELECTRIC; }  // getType() & ENull
+#endif
 
 // sAvg of plastic / roughplastic: the luminance of the RECORD's specular.  The translation unit of k_shade<.., MSET_COMMON>, which never
 // looks a parameter texture up, is compiled with PPG_PARAM_TEXTURES = 0 (ppg_inst.hip): the record's value is then M.spec itself and the
@@ -2114,6 +2136,9 @@ D float thin_R(const Mat &M, float cosThetaI) {
 // BSDF::eval(BSDFSamplingRecord(its, -wo, wo), EDiscrete) restricted to the null component: what a ray going straight through keeps
 D F3 mat_eval_null(const Mat &M, float cosThetaI) {
     if (mat_masked(M)) return f3s(1.0f) - M.opacity;  // mask.cpp:115-116
+#if PPG_NORMALMAP_NULL
+    if (M.type == PPG_BSDF_NULL) return f3s(1.0f);  // null.cpp:43-45 (ppg_set_scene refuses a mask around it)
+#endif
     return M.spec * (1 - thin_R(M, cosThetaI));
 }
 
@@ -2551,6 +2576,14 @@ D F3 mat_sample_one(const Mat &M, F3 wi, float sx, float sy, F3 &wo, float &pdf,
             if (pdf == 0) return f3s(0.0f);
             return div3(phong_eval(M.refl, M.spec, M.alpha, wi, wo), pdf);
         }
+#endif
+#if PPG_NORMALMAP_NULL
+        case PPG_BSDF_NULL:  // null.cpp:63-75: straight through, on either side; eval() and pdf() are 0 for every non-discrete query
+            delta = true;
+            isnull = true;
+            wo = -wi;
+            pdf = 1;
+            return f3s(1.0f);
 #endif
     }
     return f3s(0.0f);

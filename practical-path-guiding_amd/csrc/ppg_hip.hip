@@ -549,7 +549,7 @@ PathKernels ppg_path_kernels[PPG_FAMILIES];  // filled by the units of ppg_inst.
 
 // The kernel family a scene runs: the lowest that has everything the scene needs (ppg_device.h).
 static int sceneFamily(const DevScene &S) {
-    if (S.lobes) return PPG_FAMILY_LOBES;      // a roughdiffuse, difftrans or phong material: the lobes family, whatever else the scene holds
+    if (S.lobes) return PPG_FAMILY_LOBES;      // a roughdiffuse, difftrans or phong material, a normal-mapped or a null one: the top family, whatever else the scene holds
     if (S.blend) return PPG_FAMILY_BLEND;      // a blended material: the blend family, whatever else the scene holds
     if (S.coat) return PPG_FAMILY_COAT;        // a coated material: the coat family, shapes and general entries or not
     if (S.mfd) return PPG_FAMILY_EXT;          // a general microfacet entry: the extended family, shapes or not
@@ -2859,6 +2859,24 @@ int ppg_debug_intersect(ppg_ctx *ctx, uint32_t n, const float *rays, ppg_debug_h
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_hit), hipMemcpyDeviceToHost));
+    return PPG_OK;
+}
+int ppg_debug_shading_frame(ppg_ctx *ctx, uint32_t n, const float *rays, ppg_debug_frame *out) {
+    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
+    if (ctx->renderOpen) { ctx->error = "ppg_debug_shading_frame: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (n && (!rays || !out)) { ctx->error = "ppg_debug_shading_frame: no arrays"; return PPG_ERR_INVALID; }
+    if (n == 0) return PPG_OK;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->quiesce();
+    DebugBuf dRays, dOut;
+    HIP_CHECK(dRays.fill(rays, 2 * (size_t)n * sizeof(float4)));
+    HIP_CHECK(dOut.fill(nullptr, (size_t)n * sizeof(ppg_debug_frame)));
+    const unsigned int block = 64;
+    // (the top family compiles the hook's kernel, and every feature a scene may hold)
+    launcher(ppg_path_kernels[PPG_FAMILY_LOBES].debug_shading_frame)((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const float4 *)dRays.p, (ppg_debug_frame *)dOut.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_frame), hipMemcpyDeviceToHost));
     return PPG_OK;
 }
 int ppg_debug_intersect_mode(ppg_ctx *ctx, uint32_t n, const float *rays, ppg_debug_hit *out, int32_t mode, int32_t param, uint32_t *stats_out) {

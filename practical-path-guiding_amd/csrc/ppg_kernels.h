@@ -1077,7 +1077,15 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
         F3 ps = f3s(0.0f), pt = f3s(0.0f), pn = f3s(0.0f);
         if (FULL && X.tex) {
             if (X.tex & 0xffffu) M.refl = tex_eval(S.textures[(X.tex & 0xffffu) - 1u], X.u, X.v);
+#if PPG_NORMALMAP_NULL
+            if (MSET != MSET_COMMON && (X.tex >> 16)) {  // (normalmap.cpp:126-224 queries the nested BSDF exactly as bumpmap.cpp does: only the frame differs)
+                if (M.flags & PPG_MAT_NORMALMAP) normal_frame(S, I, X, ps, pt, pn);
+                else bump_frame(S, I, X, ps, pt, pn);
+                bumped = true;
+            }
+#else
             if (MSET != MSET_COMMON && (X.tex >> 16)) { bump_frame(S, I, X, ps, pt, pn); bumped = true; }
+#endif
         }
         // bitmaps on specular / alpha / opacity (never in the COMMON part: sort_slice keeps such surfaces out of it)
         static_assert(PPG_PARAM_TEXTURES || MSET == MSET_COMMON, "this translation unit was compiled without Mat::spec_lum");

@@ -957,10 +957,24 @@ int SceneBuilder::materials() {
             }
             if (lobe && (mt.specular || mt.alpha))
                 return refuse(who + "texture slot " + (mt.specular ? "specular" : "alpha") + ": roughdiffuse, difftrans and phong read no bitmap but `reflectance` and `opacity`");
-            if (lobe) H.scene.lobes = 1;
+            if (lobe) H.scene.lobes |= 1;
+        }
+        {   // the normalmap adapter and the null BSDF: compiled by the top kernel family alone (ppg_device.h PPG_NORMALMAP_NULL)
+            const std::string who = "material " + std::to_string(i) + ": ";
+            if ((m.flags & PPG_MAT_NORMALMAP) && !(m.texture >> 16))
+                return refuse(who + "PPG_MAT_NORMALMAP without a normal map: bits 16..31 of `texture` are 0");
+            if (m.type == PPG_BSDF_NULL) {
+                if (m.flags & PPG_MAT_TWOSIDED) return refuse(who + "null cannot be two-sided: only BRDFs can be (twosided.cpp:84-88)");
+                if (m.flags & PPG_MAT_MASK) return refuse(who + "null: a mask around the null BSDF is not supported");
+                if (m.flags) return refuse(who + "null takes no flags");
+                if (m.texture) return refuse(who + "null reads no bitmap and takes no bump or normal map: `texture` must be 0");
+                if (mt.specular || mt.alpha || mt.opacity)
+                    return refuse(who + "texture slot " + (mt.specular ? "specular" : mt.alpha ? "alpha" : "opacity") + ": null reads no bitmap");
+            }
+            if ((m.flags & PPG_MAT_NORMALMAP) || m.type == PPG_BSDF_NULL) H.scene.lobes |= 2;
         }
         if (m.type > PPG_BSDF_MIRROR || m.flags != 0) H.fullMaterials = true;
-        if (m.type == PPG_BSDF_THINDIELECTRIC || (m.flags & PPG_MAT_MASK)) hasNull = true;
+        if (m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_NULL || (m.flags & PPG_MAT_MASK)) hasNull = true;
         mats[PPG_MAT_STRIDE * i + 0] = make_float4(m.reflectance[0], m.reflectance[1], m.reflectance[2], (float)m.type);
         mats[PPG_MAT_STRIDE * i + 1] = make_float4(m.specular[0], m.specular[1], m.specular[2], m.alpha);
         mats[PPG_MAT_STRIDE * i + 2] = make_float4(m.eta[0], m.eta[1], m.eta[2], __builtin_bit_cast(float, m.flags));
@@ -994,6 +1008,8 @@ int SceneBuilder::materials() {
     }
     H.scene.has_null = hasNull ? 1 : 0;
     if (int rc = forEachAnalytic([&](const std::string &label, uint32_t sm) {
+            if (s->materials[sm].type == PPG_BSDF_NULL)
+                return refuse(label + ": material " + std::to_string(sm) + ": the null BSDF is only supported on triangle meshes (not on spheres, disks or cylinders)");
             if (s->materials[sm].texture)
                 return refuse(label + ": textured BSDFs are only supported on triangle meshes" + (label == "sphere" ? " (not on spheres, disks or cylinders)" : ""));
             if (mtOf(sm).specular || mtOf(sm).alpha || mtOf(sm).opacity)
@@ -1066,6 +1082,7 @@ int SceneBuilder::coatings() {
             const char *name = c.kind == 1 ? "coating" : "roughcoating";
             if (m.type == PPG_BSDF_ROUGHDIFFUSE || m.type == PPG_BSDF_DIFFTRANS || m.type == PPG_BSDF_PHONG)
                 return refuse(who + name + " over roughdiffuse, difftrans or phong is not supported");
+            if (m.type == PPG_BSDF_NULL) return refuse(who + name + " over the null BSDF is not supported");
             if (m.type == PPG_BSDF_DIELECTRIC || m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_ROUGHDIELECTRIC || m.type < 0 || m.type > PPG_BSDF_LAST_HIP)
                 return refuse(who + name + " over dielectric, thindielectric or roughdielectric is not supported");
             if (c.kind == 2 && (m.type == PPG_BSDF_MIRROR || m.type == PPG_BSDF_CONDUCTOR || m.type == PPG_BSDF_PLASTIC))
@@ -1138,6 +1155,7 @@ int SceneBuilder::blends() {
                 if (!in.coatings.empty() && in.coatings[c].kind) return refuse(kid + " is coated: coated children are not supported");
                 if (cm.type == PPG_BSDF_ROUGHDIFFUSE || cm.type == PPG_BSDF_DIFFTRANS || cm.type == PPG_BSDF_PHONG)
                     return refuse(kid + ": roughdiffuse, difftrans and phong children are not supported");
+                if (cm.type == PPG_BSDF_NULL) return refuse(kid + ": a null child is not supported");
                 if (cm.type == PPG_BSDF_DIELECTRIC || cm.type == PPG_BSDF_THINDIELECTRIC || cm.type == PPG_BSDF_ROUGHDIELECTRIC || cm.type < 0 || cm.type > PPG_BSDF_LAST_HIP)
                     return refuse(kid + ": dielectric, thindielectric and roughdielectric children are not supported");
                 if ((cm.flags & (PPG_MAT_TWOSIDED | PPG_MAT_MASK)) || cm.type == PPG_BSDF_TWOSIDED_DIFFUSE || (cm.texture >> 16))

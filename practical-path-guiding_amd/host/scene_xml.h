@@ -1775,6 +1775,7 @@ private:
                 m = makeBsdf(*in[0], false, out);
                 if (m.type == PPG_BSDF_DIELECTRIC || m.type == PPG_BSDF_THINDIELECTRIC || m.type == PPG_BSDF_ROUGHDIELECTRIC) throw std::runtime_error("twosided(dielectric): only BRDFs can be two-sided (twosided.cpp:84-88)");
                 if (m.type == PPG_BSDF_DIFFTRANS) throw std::runtime_error("twosided(difftrans): only BRDFs can be two-sided (twosided.cpp:84-88)");
+                if (m.type == PPG_BSDF_NULL) throw std::runtime_error("twosided(null): only BRDFs can be two-sided (twosided.cpp:84-88)");
                 if (m.type == PPG_BSDF_DIFFUSE && !(m.flags & PPG_MAT_MASK) && !m_blend.b.kind) { m.type = PPG_BSDF_TWOSIDED_DIFFUSE; return m; }
                 m.flags |= PPG_MAT_TWOSIDED;
                 return m;
@@ -1785,6 +1786,7 @@ private:
             if (in.size() == 1) {
                 m = makeBsdf(*in[0], true, out);
                 if (m.flags & PPG_MAT_MASK) throw std::runtime_error("mask(mask(...)) is not supported");
+                if (m.type == PPG_BSDF_NULL) throw std::runtime_error("mask(null) is not supported");
                 if (m.type == PPG_BSDF_TWOSIDED_DIFFUSE) { m.type = PPG_BSDF_DIFFUSE; m.flags |= PPG_MAT_TWOSIDED; }
                 m.flags |= PPG_MAT_MASK;
                 colour(e, "opacity", 0.5f, m.opacity);
@@ -1850,6 +1852,11 @@ private:
             return m;
         }
         if (t == "roughdiffuse" || t == "difftrans" || t == "phong") return lobe(e, p, t, out);
+        if (t == "null") {  // null.cpp:36-80: no parameters (a coat on it, its use in a blend or on an analytic shape: ppg_set_scene refuses)
+            m.type = PPG_BSDF_NULL; defaults(m);
+            m.reflectance[0] = m.reflectance[1] = m.reflectance[2] = 1.0f;
+            return m;
+        }
         if (t == "coating" || t == "roughcoating") {  // SmoothCoating (coating.cpp:109-200), RoughCoating (roughcoating.cpp:114-227): the innermost adapter
             auto in = inner();
             try { return coated(e, p, t, in, out); }
@@ -1877,7 +1884,7 @@ private:
             auto in = inner();
             if (in.size() == 1) { out.warnings.push_back("bsdf '" + t + "' dropped around its nested bsdf"); return makeBsdf(*in[0], allowWrap, out); }
         }
-        if (m_strict) throw std::runtime_error("bsdf type '" + t + "' is not supported yet (diffuse, roughdiffuse, difftrans, phong, conductor, roughconductor, plastic, roughplastic, dielectric, thindielectric, roughdielectric, mask, twosided; SURVEY.md §8 f1)");
+        if (m_strict) throw std::runtime_error("bsdf type '" + t + "' is not supported yet (diffuse, roughdiffuse, difftrans, phong, conductor, roughconductor, plastic, roughplastic, dielectric, thindielectric, roughdielectric, null, mask, twosided; SURVEY.md §8 f1)");
         out.warnings.push_back("bsdf '" + t + "' replaced by diffuse(0.5)");
         m = ppg_material{}; m.type = PPG_BSDF_DIFFUSE; defaults(m);
         m.reflectance[0] = m.reflectance[1] = m.reflectance[2] = 0.5f;

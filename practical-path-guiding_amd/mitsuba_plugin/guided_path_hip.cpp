@@ -157,7 +157,7 @@ private:
             /* A flat plug-in without an id: its Properties are the parameters the scene file gave it.  They are handed to the scene loader's own
                <bsdf> handling as the element they came from (ppg::xml::bsdfFromProperties) — one code path for every plug-in the HIP path
                knows (diffuse, roughdiffuse with alpha / useFastApprox, difftrans, phong with exponent, conductor, roughconductor, plastic,
-               roughplastic, dielectric, thindielectric, roughdielectric), ensureEnergyConservation, named materials,
+               roughplastic, dielectric, thindielectric, roughdielectric, null), ensureEnergyConservation, named materials,
                IOR names and rough-transmittance slices included.  Spectra arrive as linear RGB (this is an RGB build of Mitsuba). */
             std::vector<ppg::xml::BsdfParam> params;
             std::vector<std::string> names;

@@ -67,14 +67,17 @@ class Material(C.Structure):
     roughcoating adapter around the BSDF (Coating): coating = dict(kind, eta, ...), and a blendbsdf / mixturebsdf of other materials (Blend):
     blend = dict(kind, children, ...).
     roughdiffuse: reflectance, alpha (0.2), fast_approx; difftrans: reflectance (its transmittance); phong: reflectance (diffuse), specular (0.2),
-    exponent (30) — the HIP library only."""
+    exponent (30) — the HIP library only.  So are type = "null" (the pass-through BSDF: no other key applies) and normal_map = the index
+    into SceneDesc.textures of a normalmap adapter's RGB normal map, which takes the place of `bump` (the two are exclusive)."""
     _fields_ = [("type", C.c_int32), ("reflectance", C.c_float * 3), ("specular", C.c_float * 3), ("alpha", C.c_float),
                 ("eta", C.c_float * 3), ("k", C.c_float * 3), ("flags", C.c_int32), ("rtrans", C.c_int32),
                 ("opacity", C.c_float * 3), ("texture", C.c_uint32)]
 
     BSDF = dict(diffuse=0, twosided_diffuse=1, mirror=2, conductor=3, roughconductor=4, plastic=5, dielectric=6, thindielectric=7, roughdielectric=8, roughplastic=9,
-                roughdiffuse=10, difftrans=11, phong=12)
+                roughdiffuse=10, difftrans=11, phong=12, null=13)
     LOBES = (10, 11, 12)  # the types only the HIP library knows
+    NULL = 13             # ... and the pass-through BSDF, likewise
+    NORMALMAP = 32            # PPG_MAT_NORMALMAP
 
     @classmethod
     def from_dict(cls, m):
@@ -97,7 +100,13 @@ class Material(C.Structure):
         o.opacity[:] = three(m.get("opacity"), 0.0)
         o.rtrans = int(m.get("rtrans", 0))
         # texture: index into SceneDesc.textures of the bitmap on the diffuse reflectance; bump: of a bumpmap adapter's displacement texture
-        tex, bump = m.get("texture"), m.get("bump")
+        # normal_map: of a normalmap adapter's normal map, in the same half of the word, with PPG_MAT_NORMALMAP
+        tex, bump, nmap = m.get("texture"), m.get("bump"), m.get("normal_map")
+        if bump is not None and nmap is not None:
+            raise ValueError("a material states either `bump` or `normal_map`, not both (bump=%r, normal_map=%r)" % (bump, nmap))
+        if nmap is not None:
+            o.flags |= cls.NORMALMAP
+            bump = nmap
         o.texture = (0 if tex is None else int(tex) + 1) | ((0 if bump is None else int(bump) + 1) << 16)
         return o
 
@@ -340,6 +349,12 @@ class DebugHit(C.Structure):
                 ("wi", C.c_float * 3), ("material", C.c_int32), ("emitter", C.c_int32), ("_pad", C.c_int32)]
 
 
+class DebugFrame(C.Structure):
+    """ppg_debug_frame (include/ppg_testhooks.h)"""
+    _fields_ = [("prim", C.c_int32), ("material", C.c_int32), ("uv", C.c_float * 2), ("n", C.c_float * 3), ("s", C.c_float * 3),
+                ("ps", C.c_float * 3), ("pt", C.c_float * 3), ("pn", C.c_float * 3), ("adapted", C.c_int32)]
+
+
 class DebugBsdfItem(C.Structure):
     """ppg_debug_bsdf_item (include/ppg_testhooks.h)"""
     _fields_ = [("material", C.c_int32), ("wi", C.c_float * 3), ("wo", C.c_float * 3), ("sample", C.c_float * 2), ("key", C.c_uint32), ("uv", C.c_float * 2)]
@@ -359,6 +374,8 @@ class DebugDirect(C.Structure):
 
 DEBUG_HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("p", "<f4", 3), ("geo_n", "<f4", 3), ("n", "<f4", 3), ("s", "<f4", 3), ("wi", "<f4", 3),
                             ("material", "<i4"), ("emitter", "<i4"), ("_pad", "<i4")])
+DEBUG_FRAME_DTYPE = np.dtype([("prim", "<i4"), ("material", "<i4"), ("uv", "<f4", 2), ("n", "<f4", 3), ("s", "<f4", 3), ("ps", "<f4", 3), ("pt", "<f4", 3),
+                              ("pn", "<f4", 3), ("adapted", "<i4")])
 DEBUG_BSDF_ITEM_DTYPE = np.dtype([("material", "<i4"), ("wi", "<f4", 3), ("wo", "<f4", 3), ("sample", "<f4", 2), ("key", "<u4"), ("uv", "<f4", 2)])
 DEBUG_BSDF_OUT_DTYPE = np.dtype([("eval", "<f4", 3), ("pdf", "<f4"), ("wo", "<f4", 3), ("sampled_pdf", "<f4"), ("weight", "<f4", 3), ("eta", "<f4"),
                                  ("delta", "<i4"), ("is_null", "<i4"), ("_pad", "<i4", 2)])
@@ -643,6 +660,8 @@ class Engine:
             desc.materials = expand_blends(desc.materials)
         if self.prefix != "ppg_" and any(Material.from_dict(m).type in Material.LOBES for m in desc.materials):
             raise NotImplementedError("%s: roughdiffuse, difftrans and phong are not implemented here" % self.prefix)
+        if self.prefix != "ppg_" and any(m.get("normal_map") is not None or Material.from_dict(m).type == Material.NULL for m in desc.materials):
+            raise NotImplementedError("%s: the normalmap adapter and the null BSDF are not implemented here" % self.prefix)
         s = Scene()
         pos = np.ascontiguousarray(desc.positions, np.float32)
         idx = np.ascontiguousarray(desc.indices, np.uint32)
@@ -779,6 +798,17 @@ class Engine:
         out = np.zeros(rays.shape[0], DEBUG_HIT_DTYPE)
         assert out.itemsize == C.sizeof(DebugHit)
         self._call("debug_intersect", C.c_uint32(rays.shape[0]), _fp(rays), out.ctypes.data_as(C.POINTER(DebugHit)), C.c_int32(1 if any_hit else 0))
+        return out
+
+    def debug_shading_frame(self, rays):
+        """ppg_debug_shading_frame (include/ppg_testhooks.h): rays float32 [n, 8] = (o, mint, d, maxt) to their closest hit and the shading
+        frame there, before and after the bumpmap / normalmap adapter; a structured array (DEBUG_FRAME_DTYPE)."""
+        if self.prefix != "ppg_":
+            raise NotImplementedError("%s: ppg_debug_shading_frame is not implemented here" % self.prefix)
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        out = np.zeros(rays.shape[0], DEBUG_FRAME_DTYPE)
+        assert out.itemsize == C.sizeof(DebugFrame)
+        self._call("debug_shading_frame", C.c_uint32(rays.shape[0]), _fp(rays), out.ctypes.data_as(C.POINTER(DebugFrame)))
         return out
 
     DEBUG_TRACE_MODES = dict(lane=0, lane_any=1, lane_vote=2, resume=3, wave=4, ktrace=5)

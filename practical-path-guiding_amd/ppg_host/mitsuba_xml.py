@@ -45,7 +45,7 @@ GUIDED_PATH_PROPS = {  # name → type (GP:1014-1085, integrator.cpp:192-218)
 }
 
 
-TEXTURE_KEYS = ("texture", "bump", "specular_texture", "alpha_texture", "opacity_texture", "alpha_v_texture")  # material keys that hold a texture index
+TEXTURE_KEYS = ("texture", "bump", "normal_map", "specular_texture", "alpha_texture", "opacity_texture", "alpha_v_texture")  # material keys that hold a texture index
 
 
 class SceneError(ValueError):
@@ -905,6 +905,8 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             if target is None:
                 raise SceneError("<ref id=%r>: no such texture" % elem.get("id"))
             elem = target
+        if elem.get("type") == "scale":
+            return scaled_texture(elem, what)
         if elem.get("type") != "bitmap":
             raise SceneError("texture type %r on %s is not supported (bitmap only)" % (elem.get("type"), what))
         tp = _props(elem, sub)
@@ -988,6 +990,44 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         tex_index[key] = len(textures)
         textures.append(t)
         return tex_index[key]
+
+    scaled_index = {}
+
+    def scaled_texture(elem, what):
+        """<texture type="scale"> (textures/scale.cpp:50-156) around one bitmap, or around a scale around one → index into `textures` of a
+        texture of its own whose texels are the nested one's times the factor, in float32: what ScalingTexture::getBitmap does.  Its
+        average and a bump map's gradient scale with it.  (Mitsuba scales the interpolated value; the two differ by rounding only.)"""
+        tp = _props(elem, sub)
+        if any(c.get("name") == "scale" and c.tag in ("rgb", "srgb", "spectrum", "blackbody") for c in elem):
+            factor = np.asarray(colour(elem, "scale", 1.0), f32)
+        else:
+            try:
+                factor = np.full(3, f32(float(tp.get("scale", 1.0))), f32)
+            except (TypeError, ValueError):
+                raise SceneError("scale: could not parse the scale factor %r" % (tp.get("scale"),))
+        if not (np.isfinite(factor).all() and (factor > 0).all()):  # Assert(m_scale.min() > 0), scale.cpp:62
+            raise SceneError("scale: the scale factor must be finite and > 0 (got %s)" % ", ".join(repr(float(v)) for v in factor))
+        nested = [c for c in elem if c.tag == "texture" or (c.tag == "ref" and c.get("id") in tex_by_id)]
+        if "value" in tp or any(c.get("name") == "value" for c in elem):
+            raise SceneError("scale: a constant 'value' inside a scale texture is not supported (a bitmap, or a scale around one, is)")
+        if not nested:
+            raise SceneError("scale: The scale plugin needs a nested texture!")  # scale.cpp:73-74
+        if len(nested) > 1:
+            raise SceneError("scale: exactly one nested texture is required (found %d)" % len(nested))
+        inner = tex_by_id[nested[0].get("id")] if nested[0].tag == "ref" else nested[0]
+        if inner.get("type") not in ("bitmap", "scale"):
+            raise SceneError("scale: texture type %r inside a scale texture is not supported (a bitmap, or a scale around one, is)" % inner.get("type"))
+        ti = bitmap_texture(inner, what)
+        src = textures[ti]
+        if "one" in (src["wrap_u"], src["wrap_v"]):
+            raise SceneError("scale around a bitmap with wrap mode 'one' is not supported: the constant outside the image would not scale")
+        key = (ti,) + tuple(float(v) for v in factor)
+        if key not in scaled_index:
+            rgb = np.ascontiguousarray(src["rgb"] * factor, f32)
+            textures.append(dict({k: v for k, v in src.items() if k != "srgb8"}, rgb=rgb,
+                                 average=[float(v) for v in rgb.reshape(-1, 3).mean(0, dtype=np.float64)]))
+            scaled_index[key] = len(textures) - 1
+        return scaled_index[key]
 
     def colour_or_texture(elem, name, default, wrap=False):
         """(rgb, texture index or None) of a parameter that may be a bitmap; rgb is then the bitmap's average.  `wrap`: a loader failure is
@@ -1103,6 +1143,8 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                     raise SceneError("twosided(dielectric): only BRDFs can be two-sided (twosided.cpp:84-88)")
                 if m["type"] == 11:
                     raise SceneError("twosided(difftrans): only BRDFs can be two-sided (twosided.cpp:84-88)")
+                if m["type"] == 13:
+                    raise SceneError("twosided(null): only BRDFs can be two-sided (twosided.cpp:84-88)")
                 if m["type"] == 0 and not m.get("_substituted") and "blend" not in m:
                     return dict({k: v for k, v in m.items() if k in TEXTURE_KEYS + ("coating",)}, type=1, reflectance=m["reflectance"])
                 return dict(m, twosided=True)  # (a blended material's own record stays diffuse + two-sided: it only carries the adapters)
@@ -1113,6 +1155,8 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 m = make_bsdf(inner[0])
                 if "opacity" in m:
                     raise SceneError("mask(mask(...)) is not supported")
+                if m["type"] == 13:
+                    raise SceneError("mask(null) is not supported")
                 if m["type"] == 1:
                     m = dict({k: v for k, v in m.items() if k in TEXTURE_KEYS + ("coating",)}, type=0, reflectance=m["reflectance"], twosided=True)
                 return textured(dict(m), "opacity", 0.5, "opacity", "opacity_texture")
@@ -1164,6 +1208,8 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             return microfacet(elem, p, specular(textured(dict(type=8, eta=float(f32(int_ior / ext_ior))), "specularReflectance", 1.0), "specularTransmittance"), t)
         elif t in ("roughdiffuse", "difftrans", "phong"):  # roughdiffuse.cpp:88-122, difftrans.cpp:49-74, phong.cpp:60-107
             return lobe(elem, p, t, textured)
+        elif t == "null":  # null.cpp:36-80: no parameters
+            return dict(type=13)
         if t in ("coating", "roughcoating"):  # SmoothCoating (coating.cpp:109-200), RoughCoating (roughcoating.cpp:114-227): the innermost adapter
             inner = [c for c in elem if c.tag == "bsdf"]
             try:
@@ -1190,6 +1236,10 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 try:
                     if "bump" in m:
                         raise SceneError("bumpmap(bumpmap(...)) is not supported")
+                    if "normal_map" in m:
+                        raise SceneError("bumpmap(normalmap(...)) is not supported")
+                    if m["type"] == 13:
+                        raise SceneError("bumpmap(null) is not supported: the null BSDF has no shading frame to perturb")
                     if disp[0].tag == "texture" and disp[0].get("type") == "bitmap" and "gamma" not in _props(disp[0], sub):
                         raise SceneError("When using a bitmap texture as a bump map, please explicitly specify the 'gamma' parameter of the bitmap plugin")  # bumpmap.cpp:121-126
                     return dict(m, bump=bitmap_texture(disp[0], "bumpmap"))
@@ -1198,6 +1248,35 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                         raise
                     warnings.append("bump map dropped around its nested bsdf (%s)" % e)
                     return m
+        if t == "normalmap":  # NormalMap (normalmap.cpp:47-106): one nested BSDF + one RGB normal map, where a bumpmap stands
+            inner = [c for c in elem if c.tag == "bsdf"]
+            maps = [c for c in elem if c.tag in ("texture", "ref") and (c.tag == "texture" or c.get("id") in tex_by_id)]
+            if strict:
+                if not inner:
+                    raise SceneError("normalmap: A child BSDF instance is required")  # normalmap.cpp:60-61
+                if len(inner) > 1:
+                    raise SceneError("normalmap: Only a single nested BSDF can be added!")  # normalmap.cpp:91-92
+                if not maps:
+                    raise SceneError("normalmap: A normal map texture must be specified")  # normalmap.cpp:62-63
+                if len(maps) > 1:
+                    raise SceneError("normalmap: Only a single normal texture can be specified!")  # normalmap.cpp:95-96
+            if len(inner) == 1 and len(maps) == 1:
+                m = make_bsdf(inner[0], allow_twosided)
+                try:
+                    if "normal_map" in m:
+                        raise SceneError("normalmap(normalmap(...)) is not supported")
+                    if "bump" in m:
+                        raise SceneError("normalmap(bumpmap(...)) is not supported")
+                    if m["type"] == 13:
+                        raise SceneError("normalmap(null) is not supported: the null BSDF has no shading frame to perturb")
+                    if maps[0].tag == "texture" and maps[0].get("type") == "bitmap" and "gamma" not in _props(maps[0], sub):
+                        raise SceneError("When using a bitmap texture as a normal map, please explicitly specify the 'gamma' parameter of the bitmap plugin")  # normalmap.cpp:97-100
+                    return dict(m, normal_map=bitmap_texture(maps[0], "normalmap"))
+                except SceneError as e:
+                    if strict:
+                        raise
+                    warnings.append("normal map dropped around its nested bsdf (%s)" % e)
+                    return m
         if not strict and t in ("bumpmap", "normalmap"):  # adapters around one nested BSDF: render the nested one
             inner = [c for c in elem if c.tag == "bsdf"]
             if len(inner) == 1:
@@ -1205,7 +1284,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 return make_bsdf(inner[0], allow_twosided)
         if strict:
             raise SceneError("bsdf type %r is not supported yet (diffuse, roughdiffuse, difftrans, phong, conductor, roughconductor, plastic, roughplastic, dielectric, "
-                             "thindielectric, roughdielectric, mask(...), twosided(...); "
+                             "thindielectric, roughdielectric, null, mask(...), twosided(...), bumpmap(...), normalmap(...); "
                              "SURVEY.md §8 f1)" % t)
         warnings.append("bsdf %r replaced by diffuse(0.5)" % t)
         return dict(type=0, reflectance=(0.5, 0.5, 0.5), _substituted=True)
@@ -1269,8 +1348,10 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         if len(inner) != 1:
             raise SceneError("%s: exactly one nested bsdf is required (found %d)" % (t, len(inner)))
         it = inner[0].get("type")
-        if it in ("coating", "roughcoating", "twosided", "mask", "bumpmap"):
+        if it in ("coating", "roughcoating", "twosided", "mask", "bumpmap", "normalmap"):
             raise SceneError("%s(%s) is not supported: the nesting order is bumpmap(mask(twosided(coating(..))))" % (t, it))
+        if it == "null":
+            raise SceneError("%s(null): a coat on the null BSDF is not supported" % t)
         if it in ("blendbsdf", "mixturebsdf"):
             raise SceneError("%s(%s) is not supported: neither a coat around a blend nor a coated child" % (t, it))
         for c in elem:
@@ -1331,7 +1412,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 m, it = dict(materials[by_id[c.get("id")]]), "ref " + c.get("id")
             else:
                 it = c.get("type")
-                if it in ("twosided", "mask", "bumpmap"):
+                if it in ("twosided", "mask", "bumpmap", "normalmap"):
                     raise SceneError("%s(%s) is not supported: the nesting order is bumpmap(mask(twosided(%s(..))))" % (t, it, t))
                 m = make_bsdf(c, allow_twosided=False)
             if "blend" in m:
@@ -1342,7 +1423,9 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 raise SceneError("%s(%s): dielectric, thindielectric and roughdielectric children are not supported" % (t, it))
             if m["type"] in (10, 11, 12):
                 raise SceneError("%s(%s): roughdiffuse, difftrans and phong children are not supported" % (t, it))
-            if m["type"] == 1 or m.get("twosided") or "opacity" in m or "bump" in m:
+            if m["type"] == 13:
+                raise SceneError("%s(%s): a null child is not supported" % (t, it))
+            if m["type"] == 1 or m.get("twosided") or "opacity" in m or "bump" in m or "normal_map" in m:
                 raise SceneError("%s(%s) is not supported: the nesting order is bumpmap(mask(twosided(%s(..))))" % (t, it, t))
             children.append({k: v for k, v in m.items() if not k.startswith("_")})
         b = dict(kind=t, children=tuple(children))
@@ -1577,6 +1660,8 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             collected.append((mesh, mat, em))
         if t in ("sphere", "disk", "cylinder") and "blend" in materials[mat] and reads_bitmap(materials[mat]):
             raise SceneError("%s: %s: textured BSDFs are only supported on triangle meshes (not on spheres, disks or cylinders)" % (t, materials[mat]["blend"]["kind"]))
+        if t in ("sphere", "disk", "cylinder") and materials[mat].get("type") == 13:
+            raise SceneError("%s: the null BSDF is only supported on triangle meshes (not on spheres, disks or cylinders)" % t)
         if t == "sphere":
             spheres.append(dict(sphere, material=mat, emitter=em))
         if t in ("disk", "cylinder"):
@@ -1712,6 +1797,7 @@ def save_scene_xml(desc, props, directory, name="scene"):
             11: '<bsdf type="difftrans"%%s><rgb name="transmittance" value="%s"/><boolean name="ensureEnergyConservation" value="false"/></bsdf>' % R,
             12: '<bsdf type="phong"%%s><rgb name="diffuseReflectance" value="%s"/><rgb name="specularReflectance" value="%s"/><float name="exponent" value="%r"/>'
                 '<boolean name="ensureEnergyConservation" value="false"/></bsdf>' % (R, S, float(M.alpha)),
+            13: '<bsdf type="null"%s/>',
         }[t]
         K = Coating.from_dict(m)  # a coating / roughcoating goes around the leaf, inside the other adapters
         if K.kind:
@@ -1723,6 +1809,22 @@ def save_scene_xml(desc, props, directory, name="scene"):
             body = '<bsdf type="%s"%%s>%s%s</bsdf>' % ("coating" if K.kind == 1 else "roughcoating", coat, body % "")
         return body, t, M
 
+    def normal_map_element(k):
+        """the <texture type="bitmap"> of a normalmap adapter: texture k of the description written out as a PFM file — the texels as they
+        are, a `scale` texture the loader folded into them included — with the lookup's parameters"""
+        from . import imageio
+        tex = desc.textures[k]
+        fn = "%s_tex%d.pfm" % (name, k)
+        imageio.write_pfm(os.path.join(directory, fn), np.ascontiguousarray(tex["rgb"], np.float32))
+        wrap = lambda w: w if isinstance(w, str) else ("repeat", "mirror", "clamp", "zero", "one")[int(w)]  # noqa: E731
+        su, sv = tex.get("uv_scale", (1.0, 1.0))
+        ou, ov = tex.get("uv_offset", (0.0, 0.0))
+        return ('<texture type="bitmap"><string name="filename" value="%s"/><float name="gamma" value="1.0"/><string name="wrapModeU" value="%s"/>'
+                '<string name="wrapModeV" value="%s"/><string name="filterType" value="%s"/><float name="uscale" value="%r"/><float name="vscale" value="%r"/>'
+                '<float name="uoffset" value="%r"/><float name="voffset" value="%r"/></texture>'
+                % (fn, wrap(tex.get("wrap_u", "repeat")), wrap(tex.get("wrap_v", "repeat")), "nearest" if tex.get("nearest") else "bilinear",
+                   float(np.float32(su)), float(np.float32(sv)), float(np.float32(ou)), float(np.float32(ov))))
+
     for i, m in enumerate(mats):
         body, t, M = leaf(m)
         B = Blend.from_dict(m)  # a blendbsdf / mixturebsdf stands where the leaf would, its children nested in it (a bitmap weight as its constant)
@@ -1733,14 +1835,20 @@ def save_scene_xml(desc, props, directory, name="scene"):
             else:
                 body = '<bsdf type="mixturebsdf"%%s><string name="weights" value="%s"/><boolean name="ensureEnergyConservation" value="%s"/>%s</bsdf>' % (
                     ", ".join(repr(float(B.weight[k])) for k in range(B.n)), "true" if B.ensure_energy_conservation else "false", kids)
-        twos = t == 1 or (M.flags & 1 and t not in (6, 7, 8, 11))
+        twos = t == 1 or (M.flags & 1 and t not in (6, 7, 8, 11, 13))
+        ident = ' id="mat%d"' % i
+        nmap = (M.texture >> 16) - 1 if M.flags & Material.NORMALMAP and M.texture >> 16 else None  # a normalmap adapter goes around everything else
+        own = "" if nmap is not None else ident
         if M.flags & 4:
             inner = ('<bsdf type="twosided">%s</bsdf>' % (body % "")) if twos else body % ""
-            out.append('\t<bsdf type="mask" id="mat%d"><rgb name="opacity" value="%s"/>%s</bsdf>' % (i, c(M.opacity), inner))
+            element = '<bsdf type="mask"%s><rgb name="opacity" value="%s"/>%s</bsdf>' % (own, c(M.opacity), inner)
         elif twos:
-            out.append('\t<bsdf type="twosided" id="mat%d">%s</bsdf>' % (i, body % ""))
+            element = '<bsdf type="twosided"%s>%s</bsdf>' % (own, body % "")
         else:
-            out.append('\t' + body % (' id="mat%d"' % i))
+            element = body % own
+        if nmap is not None:
+            element = '<bsdf type="normalmap"%s>%s%s</bsdf>' % (ident, normal_map_element(nmap), element)
+        out.append('\t' + element)
     tm, te = np.asarray(desc.tri_material), np.asarray(desc.tri_emitter)
     idx, pos = np.asarray(desc.indices), np.asarray(desc.positions)
     groups = sorted({(int(a), int(b)) for a, b in zip(tm, te)}, key=lambda g: (g[1] < 0, g[1], g[0]))  # emitters first, in emitter order

@@ -27,7 +27,7 @@ class SceneDesc:
         self.spheres = spheres or []    # analytic spheres: dicts {center, radius, material, emitter, flip_normals, to_world} (bindings.Sphere)
         self.texcoords = texcoords      # None or float32 [n_vertices, 2] (NaN rows: vertices of meshes without texture coordinates)
         self.textures = textures or []  # bitmap textures: dicts {rgb, uv_scale, uv_offset, wrap_u, wrap_v, nearest} (bindings.Texture); materials refer
-                                        # to them by index: material["texture"] (diffuse reflectance), material["bump"] (bumpmap displacement)
+                                        # to them by index: material["texture"] (diffuse reflectance), material["bump"] (bumpmap displacement), material["normal_map"] (normalmap)
         self.rfilter = rfilter          # None (the default box) or the film's reconstruction filter: dict (bindings.RFilter)
         self.lens = lens                # None (pinhole) or a thin lens: {"aperture_radius", "focus_distance"} (bindings.Lens)
         self.delta_emitters = list(delta_emitters or [])  # point / spot / directional emitters: dicts (bindings.DeltaEmitter); they are numbered
@@ -204,8 +204,8 @@ def load_scene_file(path):
             d["fast_approx"] = True
         if m.texture & 0xffff:
             d["texture"] = (m.texture & 0xffff) - 1
-        if m.texture >> 16:
-            d["bump"] = (m.texture >> 16) - 1
+        if m.texture >> 16:  # the displacement texture of a bumpmap or (flag 32, PPG_MAT_NORMALMAP) the normal map of a normalmap
+            d["normal_map" if m.flags & 32 else "bump"] = (m.texture >> 16) - 1
         mats.append(d)
     ems = [dict(radiance=tuple(float(v) for v in take(np.float32, 4)[:3])) for _ in range(ne)]
     cam = dict(sample_to_camera=take(np.float32, 16).reshape(4, 4).copy(), camera_to_world=take(np.float32, 16).reshape(4, 4).copy())
