@@ -599,6 +599,66 @@ int ppg_read_variance(ppg_ctx *ctx, float *rgb);
 int ppg_dump_sdtree(ppg_ctx *ctx, const char *path);
 
 /* ------------------------------------------------------------------------------------------------
+ * Feature buffers of the first hit (HIP library only): Mitsuba's `field` integrator (mitsuba/src/integrators/misc/field.cpp:122-175) —
+ * what a denoiser wants beside the radiance: albedo, normals, position, depth — one image per requested field, filtered with the film's
+ * reconstruction filter (ppg_set_rfilter) exactly as the radiance is.
+ *
+ * When: after ppg_set_scene and not between ppg_begin_render and ppg_end_render (PPG_ERR_STATE).  The call reads the scene, the camera,
+ * the lens, the film's filter and the configured seed and changes nothing of the context — no film, image, SD-tree, record or RNG state —:
+ * a render before or after it is bit-identical to one without it.  A context with a shard (ppg_set_shard) still renders the WHOLE film's
+ * fields: they cost a handful of primary rays, and every rank then holds the same bits.
+ *
+ * Sample j (0 .. spp - 1) of pixel p is the camera ray the render gives that pixel for sample index first_sample + j: the key is
+ * ppg_path_key(seed, p, first_sample + j) (include/ppg_rng.h), dimensions 0 and 1 the position in the pixel, 2 and 3 the aperture point
+ * of a thin lens; mint and maxt come from the clip planes.  A sample whose ray leaves the scene has the field's `undefined` value
+ * (field.cpp:96-101; any float, NaN included).  Where the ray hits (field.cpp:130-169):
+ *   POSITION      its.p
+ *   REL_POSITION  its.p in camera space (field.cpp:134-139): the inverse of ppg_camera.camera_to_world, computed once on the host in
+ *                 double from the camera's floats and rounded to float, applied as Transform::operator()(Point)
+ *   DISTANCE      its.t in all three channels
+ *   GEO_NORMAL, SH_NORMAL   its.geoFrame.n, its.shFrame.n.  Bump and normal maps do not enter: they act inside the BSDF, as in Mitsuba.
+ *   UV            (u, v, 0): on a triangle with texture coordinates their interpolation, on a triangle without them the barycentrics
+ *                 (b1, b2) (skdtree.h:403-410) whether or not the material reads a texture, on spheres, disks and cylinders (0, 0) (their
+ *                 parameterisation is not computed: no BSDF on them reads a texture).  The XML loaders keep a mesh's coordinates only
+ *                 where its BSDF reads them; elsewhere a loaded mesh shows barycentrics.
+ *   PRIM_INDEX    the primitive's index in the scene description as a float in all three channels: the triangles in ppg_scene order (not
+ *                 the BVH's leaf order), then the spheres, then the shapes of ppg_set_shapes.  Mitsuba counts per shape; the loaders
+ *                 flatten shapes, so this scene-wide index is the only one there is, and `shapeIndex` is not offered.
+ *   ALBEDO        BSDF::getDiffuseReflectance(its).  diffuse, roughdiffuse, phong: the diffuse reflectance — the bitmap of `texture`'s low
+ *                 half at the hit's uv where there is one, else the constant (diffuse.cpp:106, roughdiffuse.cpp:124, phong.cpp:109).
+ *                 plastic: that times 1 - fresnelDiffuseReflectance(eta) (plastic.cpp:195, 219-221).  roughplastic: the diffuse
+ *                 reflectance WITHOUT roughplastic.cpp:309-315's factor Ftr — a deviation: the external rough-transmittance table's
+ *                 diffuse value is not part of ppg_scene.rtrans.  Conductors, dielectrics, thindielectric, difftrans, null and the mirror:
+ *                 0, they have no diffuse reflection (bsdf.cpp:82-86).  PPG_MAT_TWOSIDED, bump and normal maps: the nested value
+ *                 (twosided.cpp:198-203, bumpmap.cpp:108, normalmap.cpp:80); a coat (ppg_set_coatings): the coated BSDF's value.
+ *                 PPG_MAT_MASK: opacity (its bitmap where a slot names one) times the nested value — an own rule: mask.cpp has no
+ *                 override, and BSDF's default would evaluate the nested diffuse lobe at normal incidence, 0 for roughdiffuse.
+ *                 A scene with a blended material (ppg_set_blends) is refused when ALBEDO is among the fields ("albedo: blendbsdf /
+ *                 mixturebsdf materials are not supported yet"); every other field works on such scenes.
+ *
+ * The image (ImageBlock::put with the film's filter: table, radius, border B and footprint clipping of ppg_set_rfilter; the default box is
+ * the sample's own pixel with weight 1).  Summation goes by pass, then by tap, in the order (j, dy, dx): for j = 0 .. spp - 1 ascending a
+ * sample pass, then a resolve pass in which each target pixel t adds w * V per channel and w to its accumulators over its taps dy = -B .. B
+ * and within each dy dx = -B .. B; the tap (dx, dy) is source pixel t - (dx, dy)'s sample j, if that pixel is inside the film and t inside
+ * that sample's clipped footprint.  At the end out = sum * (w != 0 ? 1 / w : 0).  No atomics: the result does not depend on the launch
+ * shape.
+ *
+ * PPG_ERR_INVALID: a NULL pointer, n_fields 0 or above PPG_MAX_FIELDS, an unknown field, spp outside 1 .. 65536, the blend case.
+ * Not offered by the C++ driver, the .ppgs container (they carry scenes, not requests), the Mitsuba plug-in or the CPU oracle.
+ * ---------------------------------------------------------------------------------------------- */
+enum { PPG_FIELD_POSITION = 0, PPG_FIELD_REL_POSITION = 1, PPG_FIELD_DISTANCE = 2, PPG_FIELD_GEO_NORMAL = 3,
+       PPG_FIELD_SH_NORMAL = 4, PPG_FIELD_UV = 5, PPG_FIELD_ALBEDO = 6, PPG_FIELD_PRIM_INDEX = 7 };
+#define PPG_MAX_FIELDS 8
+typedef struct ppg_fields {
+    uint32_t n_fields;                       /* 1 .. PPG_MAX_FIELDS */
+    int32_t  field[PPG_MAX_FIELDS];          /* PPG_FIELD_*, repeats allowed */
+    float    undefined[PPG_MAX_FIELDS][3];   /* field.cpp:96-101: the value of a sample whose ray leaves the scene; any float, NaN included */
+    uint32_t spp;                            /* samples per pixel, 1 .. 65536 */
+    uint32_t first_sample;                   /* sample index of the first one */
+} ppg_fields;
+int ppg_render_fields(ppg_ctx *ctx, const ppg_fields *f, float *out /* [n_fields][height][width][3] */);
+
+/* ------------------------------------------------------------------------------------------------
  * SD-tree access (parity tests, multi-GPU reduction, visualisation).
  * ---------------------------------------------------------------------------------------------- */
 typedef struct ppg_sdtree_info {

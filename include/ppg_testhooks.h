@@ -2,7 +2,8 @@
  * ppg_testhooks.h — entry points of libppg_hip.so that exist for the tests only.  Not part of the drop-in boundary (include/ppg.h): nothing
  * a host of the integrator needs, no reference counterpart.
  *   host only   ppg_debug_build_bvh, ppg_debug_bvh_stats, ppg_debug_bvh_trace, ppg_debug_rfilter_table, ppg_debug_stree_depth
- *   a scene     ppg_debug_intersect, ppg_debug_intersect_mode, ppg_debug_sample_direct, ppg_debug_bsdf, ppg_debug_shading_frame
+ *   a scene     ppg_debug_intersect, ppg_debug_intersect_mode, ppg_debug_sample_direct, ppg_debug_bsdf, ppg_debug_shading_frame,
+ *               ppg_debug_camera_rays
  *   a render    ppg_debug_set_defer_depth, ppg_debug_commit (inside an open training iteration)
  *   no scene    ppg_debug_math_eval, ppg_debug_math_checksum
  */
@@ -90,6 +91,12 @@ struct ppg_debug_frame {
     int32_t adapted;
 };  /* 80 bytes */
 int ppg_debug_shading_frame(struct ppg_ctx *ctx, uint32_t n, const float *rays, struct ppg_debug_frame *out);
+
+/* The camera rays of the context's scene (after ppg_set_scene, outside a render): the function k_generate and ppg_render_fields make a
+   sample's ray with (csrc/ppg_device.h camera_ray), over the WHOLE film (a shard does not enter) for the sample indices first_sample ..
+   first_sample + n_samples - 1 under the configured seed.  rays[(j * n_pixels + p) * 8 ..] = { ox, oy, oz, mint, dx, dy, dz, maxt } of
+   pixel p (row-major), sample first_sample + j: the layout ppg_debug_intersect takes. */
+int ppg_debug_camera_rays(struct ppg_ctx *ctx, uint32_t first_sample, uint32_t n_samples, float *rays /* [n_samples][n_pixels][8] */);
 
 /* The same rays through the OTHER forms of the closest-hit traversal, each of which promises the same hit bit for bit (csrc/ppg_device.h,
    csrc/ppg_kernels.h); rays and records as above, mint as it stands except where noted.  stats_out (4 words, may be NULL) is zeroed, then:

@@ -1503,6 +1503,38 @@ D void disk_concentric(float sx, float sy, float &px, float &py) {
     dm_sincos(phi, &s, &c);
     px = r * c; py = r * s;
 }
+// The camera ray of one sample: renderBlock's sample position (GP:1620) + PerspectiveCamera::sampleRayDifferential (or ThinLens's:
+// cam.lens, a uniform branch; the pinhole's arithmetic is the same as without it).  Dimensions 0 and 1 of the path key are the position
+// in the pixel, 2 and 3 the aperture point of a thin lens; `dim` counts what was drawn.  k_generate, k_fields_sample and the hook
+// ppg_debug_camera_rays all call this one function.
+D void camera_ray(const DevCamera &cam, unsigned int key, unsigned int pixel, F3 &o, F3 &d, float &mint, float &maxt, unsigned int &dim) {
+    dim = 0;
+    float u1 = ppg_rand(key, dim++);
+    float u2 = ppg_rand(key, dim++);
+    int px = (int)(pixel % (unsigned int)cam.width), py = (int)(pixel / (unsigned int)cam.width);
+    float sx = (float)px + u1, sy = (float)py + u2;  // GP:1620
+    F3 nearP = xf_point(cam.s2c, f3(sx * cam.inv_w, sy * cam.inv_h, 0.0f));
+    F3 dl;
+    if (cam.lens) {
+        // ThinLens::sampleRayDifferential (thinlens.cpp:321-356): the aperture sample is dims 2, 3 (GP:1613-1630); every path has
+        // its own origin on the aperture disk
+        const float u3 = ppg_rand(key, dim++);
+        const float u4 = ppg_rand(key, dim++);
+        float ax, ay;
+        disk_concentric(u3, u4, ax, ay);
+        ax = ax * cam.aperture; ay = ay * cam.aperture;
+        const float fDist = cam.focus / nearP.z;
+        dl = norm3(nearP * fDist - f3(ax, ay, 0.0f));
+        const float *m = cam.c2w;  // Transform::transformAffine(apertureP)
+        o = f3(m[0] * ax + m[1] * ay + m[2] * 0.0f + m[3], m[4] * ax + m[5] * ay + m[6] * 0.0f + m[7], m[8] * ax + m[9] * ay + m[10] * 0.0f + m[11]);
+    } else {
+        dl = norm3(nearP);
+        o = f3(cam.c2w[3], cam.c2w[7], cam.c2w[11]);
+    }
+    float invZ = 1.0f / dl.z;
+    mint = cam.near_clip * invZ; maxt = cam.far_clip * invZ;
+    d = xf_vec(cam.c2w, dl);
+}
 D F3 cosine_hemisphere(float sx, float sy) {
     float px, py;
     disk_concentric(sx, sy, px, py);

@@ -2879,6 +2879,113 @@ int ppg_debug_shading_frame(ppg_ctx *ctx, uint32_t n, const float *rays, ppg_deb
     HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_frame), hipMemcpyDeviceToHost));
     return PPG_OK;
 }
+int ppg_debug_camera_rays(ppg_ctx *ctx, uint32_t first_sample, uint32_t n_samples, float *rays) {
+    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
+    if (ctx->renderOpen) { ctx->error = "ppg_debug_camera_rays: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (n_samples && !rays) { ctx->error = "ppg_debug_camera_rays: no array"; return PPG_ERR_INVALID; }
+    if (n_samples == 0) return PPG_OK;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->quiesce();
+    const unsigned int nPix = (unsigned int)ctx->W * (unsigned int)ctx->H;
+    const size_t bytes = 2 * (size_t)n_samples * nPix * sizeof(float4);
+    DebugBuf dRays;
+    HIP_CHECK(dRays.fill(nullptr, bytes));
+    hipLaunchKernelGGL(k_debug_camera_rays, dim3((nPix + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->scene.cam, (unsigned long long)ctx->seed, first_sample, n_samples, nPix,
+                       (float4 *)dRays.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    HIP_CHECK(hipMemcpy(rays, dRays.p, bytes, hipMemcpyDeviceToHost));
+    return PPG_OK;
+}
+
+// ---- include/ppg.h "Feature buffers of the first hit" ----
+// the inverse of a row-major 4x4 in double (Gauss-Jordan with partial pivoting); false: singular
+static bool invert4x4(const float *m, double inv[16]) {
+    double a[4][8];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) { a[i][j] = (double)m[4 * i + j]; a[i][4 + j] = i == j ? 1.0 : 0.0; }
+    for (int c = 0; c < 4; ++c) {
+        int piv = c;
+        for (int i = c + 1; i < 4; ++i) if (std::fabs(a[i][c]) > std::fabs(a[piv][c])) piv = i;
+        if (!(std::fabs(a[piv][c]) > 0.0)) return false;
+        if (piv != c) for (int j = 0; j < 8; ++j) std::swap(a[piv][j], a[c][j]);
+        const double d = a[c][c];
+        for (int j = 0; j < 8; ++j) a[c][j] /= d;
+        for (int i = 0; i < 4; ++i) {
+            if (i == c) continue;
+            const double f = a[i][c];
+            if (f != 0.0) for (int j = 0; j < 8; ++j) a[i][j] -= f * a[c][j];
+        }
+    }
+    for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) inv[4 * i + j] = a[i][4 + j];
+    return true;
+}
+int ppg_render_fields(ppg_ctx *ctx, const ppg_fields *f, float *out) {
+    if (!ctx) return PPG_ERR_INVALID;
+    if (!f || !out) { ctx->error = "ppg_render_fields: no fields or no output array"; return PPG_ERR_INVALID; }
+    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
+    if (ctx->renderOpen) { ctx->error = "ppg_render_fields: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (f->n_fields < 1 || f->n_fields > PPG_MAX_FIELDS) { ctx->error = "ppg_render_fields: n_fields must be 1 .. " + std::to_string(PPG_MAX_FIELDS); return PPG_ERR_INVALID; }
+    FieldsRequest F{};
+    F.n_fields = (int)f->n_fields;
+    for (uint32_t k = 0; k < f->n_fields; ++k) {
+        if (f->field[k] < PPG_FIELD_POSITION || f->field[k] > PPG_FIELD_PRIM_INDEX) {
+            ctx->error = "ppg_render_fields: field " + std::to_string(k) + ": unknown field " + std::to_string(f->field[k]); return PPG_ERR_INVALID;
+        }
+        F.field[k] = f->field[k];
+        memcpy(F.undefined[k], f->undefined[k], sizeof F.undefined[k]);
+        if (f->field[k] == PPG_FIELD_ALBEDO) F.albedo = 1;
+    }
+    if (f->spp < 1 || f->spp > 65536) { ctx->error = "ppg_render_fields: spp must be 1 .. 65536"; return PPG_ERR_INVALID; }
+    if (F.albedo && ctx->scene.blend) { ctx->error = "albedo: blendbsdf / mixturebsdf materials are not supported yet"; return PPG_ERR_INVALID; }
+    double inv[16];
+    if (!invert4x4(ctx->scene.cam.c2w, inv)) { ctx->error = "ppg_render_fields: camera_to_world is not invertible"; return PPG_ERR_INVALID; }
+    for (int i = 0; i < 16; ++i) F.w2c[i] = (float)inv[i];
+    HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->quiesce();
+    const size_t n = (size_t)ctx->W * (size_t)ctx->H, planes = (size_t)f->n_fields * 3 * n;
+    // what multiplies a material's diffuse reflectance: 1 - fdrExt of a plastic (plastic.cpp:195, 219-221), 0 where there is no diffuse reflection
+    std::vector<float> scale(std::max<uint32_t>(1u, ctx->nMaterials), 0.0f);
+    if (F.albedo && ctx->nMaterials) {
+        std::vector<float4> mats(PPG_MAT_STRIDE * (size_t)ctx->nMaterials);
+        HIP_CHECK(hipMemcpy(mats.data(), ctx->scene.materials, mats.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < ctx->nMaterials; ++i) {
+            const int type = (int)mats[PPG_MAT_STRIDE * (size_t)i].w;
+            if (type == PPG_BSDF_DIFFUSE || type == PPG_BSDF_TWOSIDED_DIFFUSE || type == PPG_BSDF_ROUGHDIFFUSE || type == PPG_BSDF_PHONG || type == PPG_BSDF_ROUGHPLASTIC) scale[i] = 1.0f;
+            else if (type == PPG_BSDF_PLASTIC) scale[i] = 1 - ppg_fresnel_diffuse_reflectance(mats[PPG_MAT_STRIDE * (size_t)i + 2].x);
+        }
+    }
+    DebugBuf dScale, dVals, dPos, dSum, dW, dOut;
+    HIP_CHECK(dScale.fill(scale.data(), scale.size() * sizeof(float)));
+    HIP_CHECK(dVals.fill(nullptr, planes * sizeof(float)));
+    HIP_CHECK(dPos.fill(nullptr, 2 * n * sizeof(float)));
+    HIP_CHECK(dSum.fill(nullptr, planes * sizeof(float)));
+    HIP_CHECK(dW.fill(nullptr, n * sizeof(float)));
+    HIP_CHECK(dOut.fill(nullptr, planes * sizeof(float)));
+    HIP_CHECK(hipMemsetAsync(dSum.p, 0, planes * sizeof(float), ctx->stream));
+    HIP_CHECK(hipMemsetAsync(dW.p, 0, n * sizeof(float), ctx->stream));
+    // (the top family compiles the kernels, and every feature a scene may hold)
+    const PathKernels &K = ppg_path_kernels[PPG_FAMILY_LOBES];
+    FieldsSampleLaunch s{ctx->stream, ctx->scene, F, (unsigned long long)ctx->seed, 0u, (const float *)dScale.p, (float *)dVals.p, (float *)dPos.p};
+    FieldsResolveLaunch r{ctx->stream, ctx->rf, ctx->rfBorder, F.n_fields, (const float *)dVals.p, (const float *)dPos.p, (float *)dSum.p, (float *)dW.p};
+    r.ff.W = ctx->W; r.ff.H = ctx->H;
+    if (!ctx->filtered) {  // the default box: the sample's own pixel with weight 1, as k_film has it
+        for (float &t : r.ff.table) t = 1.0f;
+        r.ff.radius = 0.5f; r.ff.scale = 62.0f; r.border = 0;
+    }
+    for (uint32_t j = 0; j < f->spp; ++j) {
+        s.sample = f->first_sample + j;
+        launcher(K.fields_sample)(s);
+        launcher(K.fields_resolve)(r);
+    }
+    for (uint32_t k = 0; k < f->n_fields; ++k)
+        hipLaunchKernelGGL(k_normalise, dim3(((unsigned int)n + 255) / 256), dim3(256), 0, ctx->stream, (int)n, (const float *)dSum.p + (size_t)k * 3 * n, (const float *)dW.p,
+                           (float *)dOut.p + (size_t)k * 3 * n);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    HIP_CHECK(hipMemcpy(out, dOut.p, planes * sizeof(float), hipMemcpyDeviceToHost));
+    return PPG_OK;
+}
 int ppg_debug_intersect_mode(ppg_ctx *ctx, uint32_t n, const float *rays, ppg_debug_hit *out, int32_t mode, int32_t param, uint32_t *stats_out) {
     if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
     if (ctx->renderOpen) { ctx->error = "ppg_debug_intersect_mode: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }

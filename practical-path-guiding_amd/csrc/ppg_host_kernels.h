@@ -8,8 +8,7 @@
 #include "ppg_kernels.h"
 
 // ------------------------------------------------------------------------------------------------
-// k_generate — renderBlock's sample loop head (GP:1613-1630) + PerspectiveCamera::sampleRayDifferential (or ThinLens's: S.cam.lens,
-// a uniform branch; the pinhole's arithmetic is the same as without it)
+// k_generate — renderBlock's sample loop head (GP:1613-1630) + the camera ray of the sample (camera_ray, ppg_device.h)
 // ------------------------------------------------------------------------------------------------
 static __global__ __launch_bounds__(PPG_BLOCK) void k_generate(PathState P, DevScene S, RenderParams R, Queues Q) {
     for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < P.n_paths; i += gridDim.x * blockDim.x) {
@@ -17,37 +16,33 @@ static __global__ __launch_bounds__(PPG_BLOCK) void k_generate(PathState P, DevS
         unsigned int pixel = P.pixels[k];
         const unsigned int sample = R.group_samples ? R.pass_index_spp + (j / R.group_samples) * R.group_stride + (j % R.group_samples) : R.pass_index_spp + j;
         unsigned int key = ppg_path_key(R.seed, pixel, sample);
-        unsigned int dim = 0;
-        float u1 = ppg_rand(key, dim++);
-        float u2 = ppg_rand(key, dim++);
-        int px = (int)(pixel % (unsigned int)S.cam.width), py = (int)(pixel / (unsigned int)S.cam.width);
-        float sx = (float)px + u1, sy = (float)py + u2;  // GP:1620
-        F3 nearP = xf_point(S.cam.s2c, f3(sx * S.cam.inv_w, sy * S.cam.inv_h, 0.0f));
-        F3 dl, o;
-        if (S.cam.lens) {
-            // ThinLens::sampleRayDifferential (thinlens.cpp:321-356): the aperture sample is dims 2, 3 (GP:1613-1630); every path has
-            // its own origin on the aperture disk
-            const float u3 = ppg_rand(key, dim++);
-            const float u4 = ppg_rand(key, dim++);
-            float ax, ay;
-            disk_concentric(u3, u4, ax, ay);
-            ax = ax * S.cam.aperture; ay = ay * S.cam.aperture;
-            const float fDist = S.cam.focus / nearP.z;
-            dl = norm3(nearP * fDist - f3(ax, ay, 0.0f));
-            const float *m = S.cam.c2w;  // Transform::transformAffine(apertureP)
-            o = f3(m[0] * ax + m[1] * ay + m[2] * 0.0f + m[3], m[4] * ax + m[5] * ay + m[6] * 0.0f + m[7], m[8] * ax + m[9] * ay + m[10] * 0.0f + m[11]);
-        } else {
-            dl = norm3(nearP);
-            o = f3(S.cam.c2w[3], S.cam.c2w[7], S.cam.c2w[11]);
-        }
-        float invZ = 1.0f / dl.z;
-        float mint = S.cam.near_clip * invZ, maxt = S.cam.far_clip * invZ;
-        F3 d = xf_vec(S.cam.c2w, dl);
+        unsigned int dim;
+        F3 o, d;
+        float mint, maxt;
+        camera_ray(S.cam, key, pixel, o, d, mint, maxt, dim);
         P.ray_o[i] = make_float4(o.x, o.y, o.z, mint);
         P.ray_d[i] = make_float4(d.x, d.y, d.z, maxt);
         P.thr[i] = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
         P.li[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         P.misc[i] = make_uint4(key, dim, 1u | FL_EMITTED_OK, 0u);
+    }
+}
+
+// ppg_debug_camera_rays (include/ppg_testhooks.h): camera_ray over the whole film for the samples first .. first + n_samples - 1, as
+// { o, mint } { d, maxt } per (sample, pixel)
+static __global__ __launch_bounds__(256) void k_debug_camera_rays(DevCamera cam, unsigned long long seed, unsigned int first, unsigned int n_samples, unsigned int n_pix,
+                                                                  float4 *rays) {
+    const unsigned int pixel = blockIdx.x * blockDim.x + threadIdx.x;
+    if (pixel >= n_pix) return;
+    for (unsigned int j = 0; j < n_samples; ++j) {
+        const unsigned int key = ppg_path_key(seed, pixel, first + j);
+        unsigned int dim;
+        F3 o, d;
+        float mint, maxt;
+        camera_ray(cam, key, pixel, o, d, mint, maxt, dim);
+        const size_t i = (size_t)j * n_pix + pixel;
+        rays[2 * i] = make_float4(o.x, o.y, o.z, mint);
+        rays[2 * i + 1] = make_float4(d.x, d.y, d.z, maxt);
     }
 }
 
@@ -423,12 +418,7 @@ static __global__ void k_add_groups(unsigned int n_img, float *partials, unsigne
 //   pixels of a row) read and write 64 consecutive floats per (o, c), and the resolve's lanes (neighbouring targets) read 64 consecutive
 //   floats too (DESIGN.md "Film reconstruction filter").  c = image RGB, squared image RGB, weight.
 // ------------------------------------------------------------------------------------------------
-#define PPG_RFILTER_MAX_BORDER 3
-struct FilmFilter {
-    float table[32];     // m_values: 31 normalised samples of eval at radius * i / 31, then 0
-    float radius, scale; // m_radius, m_scaleFactor = 31 / m_radius
-    int W, H;            // film size
-};
+// (FilmFilter: ppg_kernels.h, which the feature-buffer kernels share it through)
 
 // Source pixel P.pixels[k] (one thread each) adds the launch's samples [j0, j1) — w·L, w·L², w per tap, in sample order — to its footprint
 // slots.  The sample position is recomputed from the path key exactly as k_generate draws it (same sample index formula, dims 0 and 1).

@@ -2,7 +2,8 @@
  * ppg_inst.hip — the large path kernels, a few instantiations per translation unit (ppg_launch.h).  A unit is compiled for a kernel family,
  * -DPPG_FAMILY=f (ppg_device.h), and for one role in it:
  *   -DPPG_UNIT_SHADE         k_shade<NEE, FULL>           -DPPG_UNIT_TAIL          k_tail<SMALL, NEE, FULL>
- *   -DPPG_UNIT_TRACE         k_trace<SMALL, COUNT>, and the kernels of the test hooks that belong to the family (ppg_debug_kernels.h)
+ *   -DPPG_UNIT_TRACE         k_trace<SMALL, COUNT>, the kernels of the test hooks that belong to the family (ppg_debug_kernels.h) and, in the
+ *                            top family, those of ppg_render_fields (ppg_fields_kernels.h)
  * A family above the base is three such units: its scenes are FULL and never SMALL.  The base family splits the first two further, one
  * -DPPG_UNIT_PART=p per unit (k_shade: p = NEE; k_tail: p = SMALL * 2 + NEE; both FULL settings each), and has two units outside the families:
  *   -DPPG_UNIT_SHADE_COMMON  k_shade<false, true, MSET_COMMON>: the common material classes of a FULL scene
@@ -58,6 +59,7 @@ PPG_FILL_ROW {
 }
 #elif defined(PPG_UNIT_TRACE)
 #include "ppg_debug_kernels.h"
+#include "ppg_fields_kernels.h"
 template <bool SMALL, bool COUNT> static void launch_trace(const TraceLaunch &a) {
     hipLaunchKernelGGL((k_trace<SMALL, COUNT>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, a.P, a.S, a.Q, a.qin, a.lds_nodes, a.lds_tris, a.sorted, a.keys);
 }
@@ -71,6 +73,7 @@ static void trace(const TraceLaunch &a) {
 PPG_FILL_ROW {
     ROW.trace = trace;
     fill_debug_kernels(ROW);
+    fill_fields_kernels(ROW);
 }
 #elif defined(PPG_UNIT_SHADE_COMMON)
 void ppg_launch_shade_common(const ShadeLaunch &a) {

@@ -1884,4 +1884,13 @@ __global__ __launch_bounds__(PPG_BLOCK) void k_splat_sorted(DevTree T, const uns
     }
 }
 
+// The film's discretised reconstruction filter (ppg_set_rfilter), as the film kernels (ppg_host_kernels.h k_film_filter) and the
+// feature-buffer kernels (ppg_fields_kernels.h k_fields_resolve) take it.
+#define PPG_RFILTER_MAX_BORDER 3
+struct FilmFilter {
+    float table[32];     // m_values: 31 normalised samples of eval at radius * i / 31, then 0
+    float radius, scale; // m_radius, m_scaleFactor = 31 / m_radius
+    int W, H;            // film size
+};
+
 #endif

@@ -64,6 +64,32 @@ struct SplatLaunch {
     unsigned int lds_nodes;     // D-trees of up to this many nodes are staged in LDS (<= PPG_SPLAT_NODES)
 };
 
+// ppg_render_fields (ppg_fields_kernels.h): one sample pass of the whole film, then its resolve pass
+struct FieldsRequest {
+    int n_fields;
+    int field[PPG_MAX_FIELDS];          // PPG_FIELD_*
+    float undefined[PPG_MAX_FIELDS][3];
+    int albedo;                         // PPG_FIELD_ALBEDO is among them: the hit's material and its bitmaps are read
+    float w2c[16];                      // the inverse of the camera's camera_to_world (REL_POSITION)
+};
+struct FieldsSampleLaunch {
+    hipStream_t stream;
+    DevScene S;
+    FieldsRequest F;
+    unsigned long long seed;
+    unsigned int sample;                // the sample index of this pass
+    const float *albedo_scale;          // per material: what multiplies the diffuse reflectance (0: no diffuse reflection)
+    float *vals;                        // [n_fields][3][W * H]: the sample's value per field, channel and pixel
+    float *pos;                         // [2][W * H]: its film position - 0.5 (ImageBlock::put)
+};
+struct FieldsResolveLaunch {
+    hipStream_t stream;
+    FilmFilter ff;
+    int border, n_fields;
+    const float *vals, *pos;
+    float *sum;                         // [n_fields][W * H][3]
+    float *wsum;                        // [W * H]
+};
 
 // One row per kernel family (ppg_device.h PPG_FAMILY): the launchers of its k_shade, k_tail and k_trace.  Every unit of ppg_inst.hip enters the
 // launchers it defines into its family's row when the library is loaded; the host picks the row with sceneFamily (ppg_hip.hip).
@@ -85,6 +111,9 @@ struct PathKernels {
                                 ppg_debug_direct *out);
     void (*debug_bsdf)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out);
     void (*debug_shading_frame)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_frame *out);
+    // the top family: the kernels of ppg_render_fields (ppg_fields_kernels.h), which know every material and shape a scene may hold
+    void (*fields_sample)(const FieldsSampleLaunch &a);
+    void (*fields_resolve)(const FieldsResolveLaunch &a);
     // every family: include/ppg_mathcheck.h as the family's TRACE unit compiled it (via = 1: through the unit's dm_ copies)
     void (*debug_math_eval)(hipStream_t stream, int via, int op, unsigned int n, const uint32_t *a, const uint32_t *b, uint32_t *out0, uint32_t *out1);
     void (*debug_math_checksum)(hipStream_t stream, int via, int op, unsigned int first_block, unsigned int n_blocks, unsigned long long *out);

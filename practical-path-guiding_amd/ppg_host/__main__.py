@@ -3,6 +3,8 @@
 The role of `mitsuba scene.xml -o out.exr -D ...` (mitsuba.cpp:58-87, 300-400) for this path: load the scene-XML
 subset (mitsuba_xml.py), render with the guided path tracer on the GPU, print the reference's per-iteration log
 lines (GP:1176-1186, 1321-1326, 1376), write an EXR (render log attached like hdrfilm.cpp:525-533) or a PFM.
+`--fields a,b,c [--fields-spp N]`, or the `field` integrators of a `multichannel` scene, add the feature buffers of the first hit
+(Engine.render_fields) as layers name.R/G/B of the EXR.
 `--ppgs FILE` only converts the scene to the flat binary that the C++ driver `bin/ppg_render` reads.
 """
 import argparse
@@ -22,9 +24,21 @@ def main(argv=None):
     ap.add_argument("--lenient", action="store_true", help="replace unsupported BSDFs by diffuse(0.5) instead of failing")
     ap.add_argument("--data-dir", help="`data` directory of a Mitsuba tree (roughplastic reads data/microfacet/*.dat); default $PPG_MITSUBA_DATA")
     ap.add_argument("--constant-env", metavar="R,G,B", help="add a constant environment emitter (stand-in lighting when --lenient skipped the scene's own, e.g. sunsky)")
+    ap.add_argument("--fields", metavar="a,b,c", help="feature buffers of the first hit, written as layers name.R/G/B of the EXR (Mitsuba's field "
+                    "integrator): position, relPosition, distance, geoNormal, shNormal, uv, albedo, primIndex; added to those of a multichannel scene")
+    ap.add_argument("--fields-spp", type=int, metavar="N", help="samples per pixel of the feature buffers (default: the scene's sppPerPass)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("-q", "--quiet", action="store_true")
     a = ap.parse_args(argv)
+    from .bindings import FIELD_NAMES  # (no GPU is touched by the import)
+    asked = [(n, (0.0, 0.0, 0.0)) for n in (a.fields.split(",") if a.fields else [])]
+    for n, _ in asked:
+        if n not in FIELD_NAMES:
+            ap.error("--fields: unknown field %r (known: %s)" % (n, ", ".join(FIELD_NAMES)))
+    if a.fields_spp is not None and not 1 <= a.fields_spp <= 65536:
+        ap.error("--fields-spp must be 1 .. 65536")
+    if asked and (a.output or "").lower().endswith(".pfm"):
+        ap.error("--fields needs an EXR output: a PFM holds no layers")
 
     import torch  # noqa: F401  (its bundled HIP runtime must be loaded before libppg_hip.so, see tests/conftest.py)
     from . import GuidedPathTracer, load_scene, save_scene
@@ -36,6 +50,13 @@ def main(argv=None):
     if a.size:
         w, h = (int(v) for v in a.size.lower().split("x"))
     desc, props, info = load_scene(a.scene, defines, strict=not a.lenient, width=w, height=h, data_dir=a.data_dir)
+    fields = {}  # name -> undefined rgb: the scene's field integrators, then --fields
+    for n, undefined in list(info["fields"]) + asked:
+        fields.setdefault(n, undefined)
+    if fields and (a.output or "").lower().endswith(".pfm"):
+        ap.error("the scene's field integrators need an EXR output: a PFM holds no layers")
+    if len(fields) > 8:
+        ap.error("at most 8 fields")
     if a.constant_env:
         if desc.environment is not None or desc.envmap is not None:
             ap.error("--constant-env: the scene already has an environment emitter")
@@ -83,12 +104,17 @@ def main(argv=None):
     spp = sum(s["samples"] for it in gpt.iterations for s in it["stats"]) / float(info["width"] * info["height"])
     line = "Render time: %.3f s (%.1f spp, %.2f Msamples/s)" % (dt, spp, spp * info["width"] * info["height"] / dt / 1e6)
     log_lines.append(line); say(line)
+    layers = None
+    if fields:  # the feature buffers of the first hit, with the film's filter (Engine.render_fields)
+        fspp = a.fields_spp if a.fields_spp is not None else int(gpt.props.get("sppPerPass", 4))
+        layers = gpt.engine.render_fields(list(fields), spp=fspp, undefined=list(fields.values()))
+        say("Feature buffers: %s (%d spp)" % (", ".join(fields), fspp))
     if out.lower().endswith(".pfm"):
         write_pfm(out, img)
     else:
         if not out.lower().endswith(".exr"):
             out += ".exr"
-        write_exr(out, img, {"log": "\n".join(log_lines), "generatedBy": "practical-path-guiding_amd guided_path (MI355X)"})
+        write_exr(out, img, {"log": "\n".join(log_lines), "generatedBy": "practical-path-guiding_amd guided_path (MI355X)"}, layers=layers)
     say("Writing image to \"%s\" .." % out)
     return 0
 

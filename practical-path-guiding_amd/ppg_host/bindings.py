@@ -383,6 +383,24 @@ DEBUG_DIRECT_DTYPE = np.dtype([("emitter", "<i4"), ("d", "<f4", 3), ("dist", "<f
                                ("value", "<f4", 3), ("_pad", "<f4", 3)])
 
 
+MAX_FIELDS = 8  # PPG_MAX_FIELDS
+# Mitsuba's names of the field integrator's fields (field.cpp:72-91) -> PPG_FIELD_*; `shapeIndex` is not offered (include/ppg.h)
+FIELD_NAMES = dict(position=0, relPosition=1, distance=2, geoNormal=3, shNormal=4, uv=5, albedo=6, primIndex=7)
+
+
+class Fields(C.Structure):
+    """ppg_fields (include/ppg.h)"""
+    _fields_ = [("n_fields", C.c_uint32), ("field", C.c_int32 * MAX_FIELDS), ("undefined", (C.c_float * 3) * MAX_FIELDS), ("spp", C.c_uint32),
+                ("first_sample", C.c_uint32)]
+
+
+def field_code(name):
+    """PPG_FIELD_* of one of Mitsuba's field names; ValueError (listing the known ones) for any other"""
+    if name not in FIELD_NAMES:
+        raise ValueError("unknown field %r: the known fields are %s" % (name, ", ".join(FIELD_NAMES)))
+    return FIELD_NAMES[name]
+
+
 class DebugCommitIn(C.Structure):  # ppg_debug_commit_in
     _fields_ = [("route", C.c_int32), ("n_paths", C.c_uint32), ("n_vertices", C.c_uint64),
                 ("nv", C.POINTER(C.c_uint32)), ("key", C.POINTER(C.c_uint32)), ("dim", C.POINTER(C.c_uint32)), ("late", C.POINTER(C.c_uint8)),
@@ -810,6 +828,40 @@ class Engine:
         assert out.itemsize == C.sizeof(DebugFrame)
         self._call("debug_shading_frame", C.c_uint32(rays.shape[0]), _fp(rays), out.ctypes.data_as(C.POINTER(DebugFrame)))
         return out
+
+    def debug_camera_rays(self, first_sample=0, n_samples=1):
+        """ppg_debug_camera_rays (include/ppg_testhooks.h): the camera rays of the whole film for the sample indices first_sample ..
+        first_sample + n_samples - 1, float32 [n_samples, height * width, 8] = (o, mint, d, maxt): what debug_intersect takes."""
+        if self.prefix != "ppg_":
+            raise NotImplementedError("%s: ppg_debug_camera_rays is not implemented here" % self.prefix)
+        out = np.zeros((int(n_samples), self.height * self.width, 8), np.float32)
+        self._call("debug_camera_rays", C.c_uint32(int(first_sample)), C.c_uint32(int(n_samples)), _fp(out))
+        return out
+
+    def render_field_planes(self, fields, spp=1, undefined=None, first_sample=0):
+        """ppg_render_fields (include/ppg.h): `fields` = Mitsuba's field names (FIELD_NAMES; repeats allowed), `undefined` = per field the
+        value of a sample whose ray leaves the scene (a number or an rgb triple; None: 0) -> float32 [len(fields), height, width, 3]."""
+        if self.prefix != "ppg_":
+            raise NotImplementedError("%s: ppg_render_fields is not implemented here" % self.prefix)
+        fields = list(fields)
+        codes = [field_code(name) for name in fields]
+        f = Fields()
+        f.n_fields, f.spp, f.first_sample = len(fields), int(spp), int(first_sample)
+        undefined = list(undefined) if undefined is not None else [0.0] * len(fields)
+        if len(undefined) != len(fields):
+            raise ValueError("undefined: one value per field")
+        for k in range(min(len(fields), MAX_FIELDS)):
+            f.field[k] = codes[k]
+            f.undefined[k][:] = [float(v) for v in np.broadcast_to(np.asarray(undefined[k], np.float32), (3,))]
+        out = np.zeros((max(1, min(len(fields), MAX_FIELDS)), self.height, self.width, 3), np.float32)
+        self._call("render_fields", C.byref(f), _fp(out))
+        return out
+
+    def render_fields(self, fields, spp=1, undefined=None, first_sample=0):
+        """The feature buffers of the first hit as a dict from field name to a float32 array [height, width, 3] (render_field_planes)."""
+        fields = list(fields)
+        planes = self.render_field_planes(fields, spp, undefined, first_sample)
+        return {name: planes[k] for k, name in enumerate(fields)}
 
     DEBUG_TRACE_MODES = dict(lane=0, lane_any=1, lane_vote=2, resume=3, wave=4, ktrace=5)
 

@@ -12,13 +12,21 @@ def _attr(name, typ, payload):
     return name.encode() + b"\0" + typ.encode() + b"\0" + struct.pack("<i", len(payload)) + payload
 
 
-def write_exr(path, rgb, attributes=None):
-    """rgb: float array [H, W, 3]; attributes: {name: str} stored as EXR `string` attributes (e.g. "log")."""
+def write_exr(path, rgb, attributes=None, layers=None):
+    """rgb: float array [H, W, 3]; attributes: {name: str} stored as EXR `string` attributes (e.g. "log"); layers: {name: float array
+    [H, W, 3]} written as float channels name.R / name.G / name.B beside R / G / B (the feature buffers of `python -m ppg_host --fields`)."""
     img = np.ascontiguousarray(rgb, np.float32)
     H, W, C = img.shape
     assert C == 3
+    planes = {"R": img[:, :, 0], "G": img[:, :, 1], "B": img[:, :, 2]}
+    for lname, arr in (layers or {}).items():
+        arr = np.ascontiguousarray(arr, np.float32)
+        assert arr.shape == (H, W, 3) and lname and "\0" not in lname
+        for c, cname in enumerate("RGB"):
+            planes["%s.%s" % (lname, cname)] = arr[:, :, c]
+    order = sorted(planes, key=lambda s: s.encode())  # channels are stored in alphabetical order: B, G, R without layers
     chans = b""
-    for name in ("B", "G", "R"):  # channels are stored in alphabetical order
+    for name in order:
         chans += name.encode() + b"\0" + struct.pack("<iB3xii", 2, 0, 1, 1)  # FLOAT, pLinear 0, no subsampling
     chans += b"\0"
     box = struct.pack("<4i", 0, 0, W - 1, H - 1)
@@ -33,18 +41,20 @@ def write_exr(path, rgb, attributes=None):
     for k, v in (attributes or {}).items():
         hdr += _attr(k, "string", str(v).encode("utf-8", "replace"))
     hdr += b"\0"
-    line_bytes = 3 * 4 * W
+    line_bytes = len(order) * 4 * W
     first = len(hdr) + 8 * H
     offsets = struct.pack("<%dQ" % H, *[first + y * (8 + line_bytes) for y in range(H)])
     with open(path, "wb") as f:
         f.write(hdr); f.write(offsets)
         for y in range(H):
             f.write(struct.pack("<ii", y, line_bytes))
-            f.write(img[y, :, 2].tobytes()); f.write(img[y, :, 1].tobytes()); f.write(img[y, :, 0].tobytes())
+            for name in order:
+                f.write(planes[name][y].tobytes())
 
 
-def read_exr(path):
-    """→ (rgb float32 [H, W, 3], {string attribute: str}); scanline files, compression NONE / ZIPS / ZIP, half or float channels."""
+def read_exr(path, layers=False):
+    """→ (rgb float32 [H, W, 3], {string attribute: str}); scanline files, compression NONE / ZIPS / ZIP, half or float channels.
+    layers = True: a third value, {name: float32 [H, W, 3]} of the channels name.R / name.G / name.B."""
     import zlib
     buf = open(path, "rb").read()
     assert struct.unpack_from("<I", buf, 0)[0] == _MAGIC, "not an EXR file"
@@ -69,7 +79,7 @@ def read_exr(path):
         chans.append((cname, ptype)); o += 16
     bpp = {1: 2, 2: 4}
     lines = {0: 1, 2: 1, 3: 16}[comp]
-    out = np.zeros((H, W, 3), np.float32)
+    out, lay = np.zeros((H, W, 3), np.float32), {}
     for bo in struct.unpack_from("<%dQ" % ((H + lines - 1) // lines), buf, off):
         y, size = struct.unpack_from("<ii", buf, bo)
         raw = buf[bo + 8:bo + 8 + size]
@@ -90,7 +100,10 @@ def read_exr(path):
                     out[y - y0 + ly, :, "RGB".index(cname)] = arr
                 elif cname == "Y":
                     out[y - y0 + ly] = arr.astype(np.float32)[:, None]
-    return out, {k: v[1].decode("utf-8", "replace") for k, v in attrs.items() if v[0] == "string"}
+                elif layers and cname[-2:] in (".R", ".G", ".B"):
+                    lay.setdefault(cname[:-2], np.zeros((H, W, 3), np.float32))[y - y0 + ly, :, "RGB".index(cname[-1])] = arr
+    strings = {k: v[1].decode("utf-8", "replace") for k, v in attrs.items() if v[0] == "string"}
+    return (out, strings, lay) if layers else (out, strings)
 
 
 def read_pfm(path):

@@ -1,6 +1,7 @@
 """Loader for the subset of Mitsuba 0.6 scene XML the reference's bundled scenes use:
 
-  integrator  guided_path (every property of GP:1014-1085 and integrator.cpp:192-218)
+  integrator  guided_path (every property of GP:1014-1085 and integrator.cpp:192-218), or a multichannel holding exactly one guided_path
+              and any number of field integrators (field, undefined): info["fields"] = [(name, undefined rgb)], the feature buffers
   sensor      perspective (fov, fovAxis or focalLength, nearClip, farClip, toWorld; focusDistance ignored: pinhole),
               thinlens (the same + apertureRadius, focusDistance: SceneDesc.lens; toWorld without scale),
               nested sampler (independent; sampleCount / seed do not steer guided_path, GP:1342-1374) and
@@ -35,6 +36,7 @@ import xml.etree.ElementTree as ET
 import numpy as np
 
 from . import spectrum
+from .bindings import FIELD_NAMES
 from .scenes import SceneDesc, perspective_camera_from_matrix
 
 f32 = np.float32
@@ -814,6 +816,33 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
     integ = root.find("integrator")
     if integ is None:
         raise SceneError("no <integrator>")
+    fields = []  # the `field` integrators of a multichannel integrator (misc/multichannel.cpp, misc/field.cpp): (name, undefined rgb)
+    if integ.get("type") == "multichannel":
+        nested = [c for c in integ if c.tag == "integrator"]
+        guided = [c for c in nested if c.get("type") == "guided_path"]
+        other = [c.get("type") for c in nested if c.get("type") not in ("guided_path", "field")]
+        if len(guided) != 1 or other:
+            raise SceneError("a multichannel integrator must hold exactly one 'guided_path' and otherwise 'field' integrators only (found %s)"
+                             % (", ".join(repr(c.get("type")) for c in nested) or "none"))
+        for c in nested:
+            if c.get("type") != "field":
+                continue
+            fp = _props(c, sub)
+            name = fp.get("field")
+            if name == "shapeIndex":
+                raise SceneError("field integrator: 'shapeIndex' is not offered: shapes are flattened on loading, use 'primIndex'")
+            if name not in FIELD_NAMES:
+                raise SceneError("field integrator: Invalid 'field' parameter. Must be one of 'position', 'relPosition', 'distance', 'geoNormal', "
+                                 "'shNormal', 'primIndex', 'shapeIndex', or 'uv'! (got %r)" % (name,))
+            undefined = np.zeros(3, f32)
+            for u in c:
+                if u.get("name") == "undefined":
+                    if u.tag == "float":
+                        undefined = np.full(3, float(sub(u.get("value"))), f32)
+                    elif u.tag in ("rgb", "srgb", "spectrum"):
+                        undefined = np.asarray(spectrum.parse(u.tag, sub(u.get("value"))), f32)
+            fields.append((name, tuple(float(v) for v in undefined)))
+        integ = guided[0]
     if integ.get("type") != "guided_path":
         raise SceneError("integrator type %r is not supported: this path implements 'guided_path' only" % integ.get("type"))
     props = {}
@@ -863,7 +892,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             raise SceneError("thinlens sensor: apertureRadius and focusDistance must be finite and > 0 (got %r, %r)" % (float(r), float(focus)))
         lens = dict(aperture_radius=float(r), focus_distance=float(focus))
     sampler = sensor.find("sampler")
-    info = dict(width=W, height=H, sample_count=_props(sampler, sub).get("sampleCount") if sampler is not None else None)
+    info = dict(width=W, height=H, sample_count=_props(sampler, sub).get("sampleCount") if sampler is not None else None, fields=fields)
 
     # ---- bsdfs
     materials, mat_index, by_id = [], {}, {}
