@@ -11,17 +11,31 @@
               sphere (center, radius, toWorld = rotation x uniform scale, flipNormals) — analytic, not tessellated,
               disk (toWorld without shear or non-uniform scale, flipNormals), cylinder (p0, p1, radius, toWorld, flipNormals) — analytic
               (SceneDesc.shapes); no textured BSDFs on them; a cylinder must state at least one of p0 / p1 / radius / toWorld
-  bsdfs       diffuse, conductor (material none, explicit eta / k, or a named material read from Mitsuba's data/ior), roughconductor / roughdielectric / roughplastic (ggx / beckmann, isotropic; roughplastic reads Mitsuba's data/microfacet tables),
-              plastic, dielectric, thindielectric,
-              mask (constant opacity), twosided(any of the BRDFs) — top level with id, nested, or <ref id>
+  bsdfs       top level with id, nested in a shape, or <ref id>; one reader per plug-in (_BSDF_READERS):
+              diffuse, roughdiffuse (alpha, useFastApprox), difftrans, phong (exponent) — with ensureEnergyConservation,
+              conductor (material none, explicit eta / k, or a named material read from Mitsuba's data/ior), plastic, dielectric, thindielectric, null,
+              roughconductor / roughdielectric (ggx / beckmann; alpha or alphaU / alphaV, sampleVisible), roughplastic (+ phong; isotropic; reads
+              Mitsuba's data/microfacet tables: SceneDesc.rtrans),
+              and the adapters, nested as bumpmap | normalmap(mask(twosided(coating | roughcoating | blendbsdf | mixturebsdf(..)))):
+              twosided (any of the BRDFs), mask (opacity), coating / roughcoating (intIOR, extIOR, thickness, sigmaA, specularReflectance, alpha;
+              constants only; not on dielectrics or the three lobes), blendbsdf (weight) / mixturebsdf (weights) of two / up to four diffuse, conductor,
+              roughconductor, plastic or roughplastic children, bumpmap and normalmap (one nested bsdf + one texture with an explicit gamma)
+  textures    bitmap (filename, wrapMode[U|V], filterType, gamma, channel, uscale, vscale, uoffset, voffset; .exr / .pfm / .hdr or 8-bit files) and scale
+              around one — nested or <ref id> — on reflectance / transmittance / diffuseReflectance, on the specular colours, on the alpha of roughconductor /
+              roughdielectric, on a mask's opacity, a blendbsdf's weight and as bump or normal map (SceneDesc.textures); on triangle meshes only
   emitters    point (position or toWorld, intensity), spot (toWorld, intensity, cutoffAngle, beamWidth; no texture), directional (direction or
               toWorld without scale, irradiance): SceneDesc.delta_emitters, samplingWeight 1 only;
-              area (nested in a shape), constant (environment), envmap (latitude-longitude .exr / .pfm / .hdr; filename, scale, toWorld = rotation)
-  values      <spectrum>, <rgb>, <srgb>, <blackbody> (spectrum.py), <transform> of translate / rotate / scale / lookAt / matrix,
+              area (nested in a shape), and one environment emitter: constant, envmap (latitude-longitude .exr / .pfm / .hdr; filename, scale, toWorld =
+              rotation) or sunsky (baked into an envmap with the tables of a Mitsuba source tree; toWorld = rotation)
+  values      <spectrum> (value or filename), <rgb>, <srgb>, <blackbody> (spectrum.py), <transform> of translate / rotate / scale / lookAt / matrix,
               <default name value> and $name substitution (mitsuba -D, mitsuba.cpp:58-87)
 
-Anything else raises SceneError naming the plugin (Mitsuba would load it; this path cannot render it yet —
-SURVEY.md §8(f1)/(f2)).  With strict=False unsupported BSDFs become diffuse(0.5) and are listed in `warnings`.
+Anything else raises SceneError naming the plugin (Mitsuba would load it; this path cannot render it yet — SURVEY.md §8(f1)/(f2)).  With
+strict=False unsupported BSDFs become diffuse(0.5), adapters that cannot be kept are dropped around their nested BSDF, unsupported emitters and
+shapes whose file is missing are skipped, and each such step is listed in `warnings`.
+
+load_scene() is a driver over one reader per element — integrator, sensor and film, named BSDFs, emitters, shapes, assembly — all of them methods
+of _Reader, the state of one load.
 
 The OBJ reader follows shapes/obj.cpp:198-342 (fan triangulation of n-gons, negative indices, one mesh per `g` /
 `usemtl` run, vertices merged per mesh on identical (position, normal, uv), normals transformed by the inverse
@@ -743,23 +757,23 @@ def inverse3(m):
                      (c * d - a * f) / det, (d * h - e * g) / det, (b * g - a * h) / det, (a * e - b * d) / det], np.float64).astype(f32)
 
 
-def parse_delta_emitter(em, sub, colour):
+def parse_delta_emitter(em, rd):
     """<emitter type="point" | "spot" | "directional"> (mitsuba/src/emitters/point.cpp:57-69, spot.cpp:68-94, directional.cpp:55-73) → a
-    SceneDesc.delta_emitters dict (bindings.DeltaEmitter).  `colour` reads a spectrum property (default 1: the loader's D65)."""
+    SceneDesc.delta_emitters dict (bindings.DeltaEmitter).  `rd` is the load's reader (a spectrum property defaults to 1: the loader's D65)."""
     t = em.get("type")
-    ep = _props(em, sub)
+    ep = _props(em, rd.sub)
     for c in em:
         if c.tag == "vector":
-            ep[c.get("name")] = tuple(float(sub(c.get(k, "0"))) for k in "xyz")
+            ep[c.get("name")] = tuple(float(rd.sub(c.get(k, "0"))) for k in "xyz")
     tw = next((c for c in em if c.tag == "transform" and c.get("name", "toWorld") == "toWorld"), None)
-    m = _transform(tw, sub) if tw is not None else np.eye(4, dtype=f32)
+    m = _transform(tw, rd.sub) if tw is not None else np.eye(4, dtype=f32)
     if float(ep.get("samplingWeight", 1.0)) != 1.0:
         raise SceneError("%s emitter: a samplingWeight other than 1 is not supported" % t)
     if t == "point":
         if "position" in ep and tw is not None:
             raise SceneError("point emitter: only one of the parameters 'position' and 'toWorld' can be used")
         pos = ep["position"] if "position" in ep else (m[0, 3], m[1, 3], m[2, 3])
-        return dict(type="point", intensity=tuple(float(v) for v in colour(em, "intensity", 1.0)), position=tuple(float(f32(v)) for v in pos))
+        return dict(type="point", intensity=tuple(float(v) for v in rd._colour(em, "intensity", 1.0)), position=tuple(float(f32(v)) for v in pos))
     if t == "spot":
         if any(c.get("name") == "texture" or c.tag == "texture" for c in em):
             raise SceneError("spot emitter: a projection 'texture' is not supported")
@@ -771,7 +785,7 @@ def parse_delta_emitter(em, sub, colour):
             raise SceneError("spot emitter: cutoffAngle must not be smaller than beamWidth")
         if not (0 < beam and cutoff_deg < 90):
             raise SceneError("spot emitter: the angles must satisfy 0 < beamWidth <= cutoffAngle < 90 degrees")
-        return dict(type="spot", intensity=tuple(float(v) for v in colour(em, "intensity", 1.0)), position=(float(m[0, 3]), float(m[1, 3]), float(m[2, 3])),
+        return dict(type="spot", intensity=tuple(float(v) for v in rd._colour(em, "intensity", 1.0)), position=(float(m[0, 3]), float(m[1, 3]), float(m[2, 3])),
                     to_local=[float(v) for v in inverse3(m)], cutoff_angle=float(cutoff), beam_width=float(beam))
     if "direction" in ep and tw is not None:
         raise SceneError("directional emitter: only one of the parameters 'direction' and 'toWorld' can be used at a time")
@@ -785,126 +799,128 @@ def parse_delta_emitter(em, sub, colour):
         if _has_scale(m):
             raise SceneError("directional emitter: scale factors in the emitter-to-world transformation are not allowed")
         d = (float(m[0, 2]), float(m[1, 2]), float(m[2, 2]))
-    return dict(type="directional", intensity=tuple(float(v) for v in colour(em, "irradiance", 1.0)), direction=d)
+    return dict(type="directional", intensity=tuple(float(v) for v in rd._colour(em, "irradiance", 1.0)), direction=d)
 
 
-def load_scene(path, defines=None, strict=True, width=None, height=None, data_dir=None, mitsuba_src=None):
-    """Parse `path` → (SceneDesc, integrator properties for ppg_create, info dict).
+def _decode_bitmap(full, channel, gamma):
+    """The float32 `rgb` texels of an image file and, where they are its own sRGB encoding decoded, the 8-bit texels as `srgb8`: 8-bit files go
+    through the sRGB curve unless `gamma` says otherwise (bitmap.cpp:182-204), luminance and a single `channel` are replicated to RGB"""
+    from . import imageio
+    from .scenes import srgb8_table
+    if os.path.splitext(full)[1].lower() in (".exr", ".pfm", ".hdr", ".rgbe"):
+        rgb = np.ascontiguousarray(imageio.read_image(full), f32)  # floating point data is linear (bitmap.cpp:190-192)
+        if channel:  # a monochrome texture of that channel (bitmap.cpp:238-256)
+            if channel == "a":
+                raise SceneError("bitmap: '%s' has no channel 'a' (channels present: r, g, b)" % full)
+            rgb = np.ascontiguousarray(np.repeat(rgb[:, :, "rgb".index(channel)][:, :, None], 3, 2))
+        return dict(rgb=rgb)
+    try:
+        from PIL import Image
+    except ImportError:
+        raise SceneError("bitmap: decoding '%s' needs PIL (scene conversion only)" % full)
+    im = Image.open(full)
+    if channel:  # one channel of the file as a monochrome texture, replicated to RGB (bitmap.cpp:238-256)
+        if im.mode in ("P", "CMYK", "1"):
+            im = im.convert("RGBA" if "transparency" in im.info else "RGB")
+        names = {"L": "y", "LA": "ya", "RGB": "rgb", "RGBA": "rgba"}.get(im.mode)
+        a = np.asarray(im)
+        if names is None or a.dtype != np.uint8:
+            raise SceneError("bitmap: '%s': only 8-bit images are decoded here" % full)
+        if channel not in names:
+            raise SceneError("bitmap: '%s' has no channel %r (channels present: %s)" % (full, channel, ", ".join(names)))
+        a = np.ascontiguousarray(np.repeat(a.reshape(a.shape[0], a.shape[1], -1)[:, :, names.index(channel)][:, :, None], 3, 2))
+        gamma = 1.0 if channel == "a" else gamma  # alpha is never gamma-corrected (bitmap.cpp:258-263)
+        if gamma == 1.0:
+            return dict(rgb=(a.astype(f32) / f32(255.0)).astype(f32))
+    else:
+        if im.mode in ("P", "RGBA", "LA", "CMYK", "1", "I;16", "I"):  # alpha is dropped for a spectrum texture (bitmap.cpp:218-236: EAuto → RGB / luminance)
+            im = im.convert("RGB" if im.mode != "LA" else "L")
+        a = np.asarray(im)
+        if a.dtype != np.uint8:
+            raise SceneError("bitmap: '%s': only 8-bit images are decoded here" % full)
+        if a.ndim == 2:
+            a = np.repeat(a[:, :, None], 3, 2)
+        a = np.ascontiguousarray(a[:, :, :3])
+    if gamma == 0.0 or gamma == -1.0:  # the file's own encoding: sRGB for 8-bit images
+        return dict(srgb8=a, rgb=srgb8_table()[a])
+    # an explicit gamma (bump maps ask for 1.0, bumpmap.cpp:121-126): value^gamma on value / 255
+    return dict(rgb=np.power(a.astype(np.float64) / 255.0, gamma).astype(f32))
 
-    defines: {"name": "value"} like `mitsuba -D name=value`; width/height override the film size; data_dir: the `data` directory of
-    a Mitsuba tree (default $PPG_MITSUBA_DATA) — only `roughplastic` needs it, for data/microfacet/*.dat."""
-    root = ET.parse(path).getroot()
-    if root.tag != "scene":
-        raise SceneError("%s: root element is <%s>, expected <scene>" % (path, root.tag))
-    base = os.path.dirname(os.path.abspath(path))
-    params = dict(defines or {})
-    for d in root.iter("default"):
-        params.setdefault(d.get("name"), d.get("value"))
 
-    def sub(text):
+# ---------------------------------------------------------------------------------------------- what several readers ask of an element or a material
+_nested_bsdfs = lambda elem: [c for c in elem if c.tag == "bsdf"]  # noqa: E731
+_texture_on = lambda elem, *names: any(c.get("name") in names and c.tag in ("texture", "ref") for c in elem)  # noqa: E731 (a <texture> or <ref> on one of them)
+_stated = lambda elem, name: any(c.get("name") == name for c in elem)  # noqa: E731
+_blend_children = lambda m: [c for c in (m.get("blend") or {}).get("children", ()) if isinstance(c, dict)]  # noqa: E731
+_IOR = {"vacuum": 1.0, "air": 1.000277, "water": 1.3330, "polypropylene": 1.49, "bk7": 1.5046, "diamond": 2.419}  # well-known constants (cf. ior.h)
+
+
+def _lookup_ior(p, name, default):  # lookupIOR, ior.h:95-111: a number or a material name
+    v = p.get(name, default)
+    if isinstance(v, (int, float)):
+        return float(v)
+    if str(v).lower() not in _IOR:
+        raise SceneError("IOR name %r is not in the built-in list %s; give a number" % (v, sorted(_IOR)))
+    return _IOR[str(v).lower()]
+
+
+def _dielectric_eta(p, what, int_default):  # intIOR / extIOR of the rough plug-ins (roughdielectric.cpp:183-211, roughplastic.cpp:197-227)
+    int_ior, ext_ior = _lookup_ior(p, "intIOR", int_default), _lookup_ior(p, "extIOR", "air")
+    if int_ior < 0 or ext_ior < 0 or int_ior == ext_ior:
+        raise SceneError("%s: the interior and exterior indices of refraction must be positive and differ" % what)
+    return float(f32(int_ior / ext_ior))
+
+
+def _freeze(v):  # a material dict's value as something hashable
+    if isinstance(v, dict):
+        return tuple(sorted((a, _freeze(b)) for a, b in v.items()))
+    return tuple(_freeze(x) for x in v) if isinstance(v, (tuple, list)) else v
+
+
+def _reads_bitmap(m):  # whether the material, the weight of its blend or a child of it reads a bitmap at the hit's uv
+    return (any(k in m for k in TEXTURE_KEYS) or (m.get("blend") or {}).get("weight_texture") is not None
+            or any(_reads_bitmap(c) for c in _blend_children(m)))
+
+
+def _anisotropic(m):
+    """EAnisotropic: alphaU != alphaV, or either a bitmap — in the material or in a child of its blend.  Needs the UV tangents (trimesh.cpp:380, 683-735)."""
+    own = m.get("alpha_v") is not None and (max(f32(m["alpha_v"]), f32(1e-4)) != max(f32(m.get("alpha", 0.1)), f32(1e-4))
+                                            or m.get("alpha_texture") is not None or m.get("alpha_v_texture") is not None)
+    return own or any(_anisotropic(c) for c in _blend_children(m))
+
+
+# ---------------------------------------------------------------------------------------------- the state of one load
+class _Reader:
+    """One load_scene() call: the state its readers share, and the readers as methods.  The tables only grow, in the order in which the
+    scene file names their entries: materials and textures are referred to by index."""
+
+    def __init__(self, root, path, defines, strict, data_dir, mitsuba_src):
+        self.params = dict(defines or {})  # -D name=value, then the file's <default>s
+        for d in root.iter("default"):
+            self.params.setdefault(d.get("name"), d.get("value"))
+        self.strict, self.warnings = strict, []  # refuse what cannot be rendered, or substitute or skip it and say so in `warnings`
+        self.base = os.path.dirname(os.path.abspath(path))  # relative file names start here
+        self.data_dir, self.mitsuba_src = data_dir, mitsuba_src
+        self.tex_by_id = {t.get("id"): t for t in root.findall("texture") if t.get("id")}  # top-level <texture id> elements, for <ref>
+        self.textures, self.tex_index, self.scaled_index = [], {}, {}  # SceneDesc.textures; bitmap key → index; (index, factor) → index of the scaled copy
+        self.materials, self.mat_index, self.by_id = [], {}, {}  # material dicts; frozen dict → index; bsdf id → index
+        self.rt_slices, self.rt_index = [], {}  # rough-transmittance slices; (distribution, alpha, eta) → index
+
+    def sub(self, text):  # $name → its -D or <default> value (mitsuba.cpp:58-87)
         if text is None or "$" not in text:
             return text
-        def rep(mo):
-            k = mo.group(1)
-            if k not in params:
+        for k in re.findall(r"\$(\w+)", text):
+            if k not in self.params:
                 raise SceneError("undefined parameter $%s (pass it with -D %s=...)" % (k, k))
-            return str(params[k])
-        return re.sub(r"\$(\w+)", rep, text)
+        return re.sub(r"\$(\w+)", lambda mo: str(self.params[mo.group(1)]), text)
 
-    warnings = []
-    # ---- integrator
-    integ = root.find("integrator")
-    if integ is None:
-        raise SceneError("no <integrator>")
-    fields = []  # the `field` integrators of a multichannel integrator (misc/multichannel.cpp, misc/field.cpp): (name, undefined rgb)
-    if integ.get("type") == "multichannel":
-        nested = [c for c in integ if c.tag == "integrator"]
-        guided = [c for c in nested if c.get("type") == "guided_path"]
-        other = [c.get("type") for c in nested if c.get("type") not in ("guided_path", "field")]
-        if len(guided) != 1 or other:
-            raise SceneError("a multichannel integrator must hold exactly one 'guided_path' and otherwise 'field' integrators only (found %s)"
-                             % (", ".join(repr(c.get("type")) for c in nested) or "none"))
-        for c in nested:
-            if c.get("type") != "field":
-                continue
-            fp = _props(c, sub)
-            name = fp.get("field")
-            if name == "shapeIndex":
-                raise SceneError("field integrator: 'shapeIndex' is not offered: shapes are flattened on loading, use 'primIndex'")
-            if name not in FIELD_NAMES:
-                raise SceneError("field integrator: Invalid 'field' parameter. Must be one of 'position', 'relPosition', 'distance', 'geoNormal', "
-                                 "'shNormal', 'primIndex', 'shapeIndex', or 'uv'! (got %r)" % (name,))
-            undefined = np.zeros(3, f32)
-            for u in c:
-                if u.get("name") == "undefined":
-                    if u.tag == "float":
-                        undefined = np.full(3, float(sub(u.get("value"))), f32)
-                    elif u.tag in ("rgb", "srgb", "spectrum"):
-                        undefined = np.asarray(spectrum.parse(u.tag, sub(u.get("value"))), f32)
-            fields.append((name, tuple(float(v) for v in undefined)))
-        integ = guided[0]
-    if integ.get("type") != "guided_path":
-        raise SceneError("integrator type %r is not supported: this path implements 'guided_path' only" % integ.get("type"))
-    props = {}
-    for k, v in _props(integ, sub).items():
-        if k not in GUIDED_PATH_PROPS:
-            warnings.append("integrator property %r is not used by guided_path" % k)  # Mitsuba warns about unqueried properties, too
-            continue
-        props[k] = GUIDED_PATH_PROPS[k](v)
-    # ---- sensor / film
-    sensor = root.find("sensor")
-    if sensor is None:
-        raise SceneError("no <sensor>")
-    stype = sensor.get("type")
-    if stype not in ("perspective", "thinlens"):
-        raise SceneError("sensor type %r is not supported (perspective, thinlens)" % stype)
-    sp = _props(sensor, sub)
-    film = sensor.find("film")
-    fp = _props(film, sub) if film is not None else {}
-    if film is not None and film.get("type") not in ("hdrfilm", "ldrfilm", None):
-        raise SceneError("film type %r is not supported" % film.get("type"))
-    rf = film.find("rfilter") if film is not None else None
-    rfilter = parse_rfilter(rf, sub) if rf is not None else None
-    if rf is None:
-        warnings.append("no <rfilter>: Mitsuba would default to gaussian; the box filter is used")
-    W = int(width or fp.get("width", 768)); H = int(height or fp.get("height", 576))
-    if "fov" in sp and "focalLength" in sp:  # PerspectiveCamera::PerspectiveCamera, sensor.cpp:226-228
-        raise SceneError("%s sensor: please specify either a focal length ('focalLength') or a field of view ('fov')" % stype)
-    if "fov" in sp:
-        fov, fov_axis = sp["fov"], str(sp.get("fovAxis", "x")).lower()
-    else:
-        fov, fov_axis = focal_length_fov(str(sp.get("focalLength", "50mm"))), "diagonal"
-    tw = sensor.find("transform")
-    c2w = _transform(tw, sub) if tw is not None else np.eye(4, dtype=f32)
-    camera = perspective_camera_from_matrix(c2w, fov, fov_axis, sp.get("nearClip", 1e-2), sp.get("farClip", 1e4), W, H)
-    lens = None
-    if stype == "thinlens":  # ThinLens::ThinLens, thinlens.cpp:124-142; focusDistance defaults to farClip (sensor.cpp:162)
-        if "apertureRadius" not in sp:
-            raise SceneError("thinlens sensor without 'apertureRadius'")
-        r = f32(sp["apertureRadius"])
-        if r == 0:
-            warnings.append("thinlens: can't have a zero aperture radius -- setting to 0.0001")
-            r = f32(1e-4)
-        focus = f32(sp.get("focusDistance", sp.get("farClip", 1e4)))
-        if _has_scale(c2w):
-            raise SceneError("thinlens sensor: scale factors in the camera-to-world transformation are not allowed")
-        if not (np.isfinite(r) and r > 0 and np.isfinite(focus) and focus > 0):
-            raise SceneError("thinlens sensor: apertureRadius and focusDistance must be finite and > 0 (got %r, %r)" % (float(r), float(focus)))
-        lens = dict(aperture_radius=float(r), focus_distance=float(focus))
-    sampler = sensor.find("sampler")
-    info = dict(width=W, height=H, sample_count=_props(sampler, sub).get("sampleCount") if sampler is not None else None, fields=fields)
-
-    # ---- bsdfs
-    materials, mat_index, by_id = [], {}, {}
-    tex_by_id = {t.get("id"): t for t in root.findall("texture") if t.get("id")}
-
-    def colour(elem, name, default):
+    def _colour(self, elem, name, default):  # the rgb of the spectrum property `name` of `elem`, `default` in all three channels where it is absent
         for c in elem:
             if c.get("name") == name:
                 if c.tag in ("rgb", "srgb", "spectrum"):
                     if c.get("filename"):  # InterpolatedSpectrum(path) (spectrum.cpp:575-600): "wavelength value" lines, # comments
-                        fn = sub(c.get("filename"))
-                        full = fn if os.path.isabs(fn) else os.path.join(base, fn)
+                        fn = self.sub(c.get("filename"))
+                        full = fn if os.path.isabs(fn) else os.path.join(self.base, fn)
                         if c.tag != "spectrum" or c.get("value") is not None or not os.path.exists(full):
                             raise SceneError("<%s filename=%r>: %s" % (c.tag, fn, "file not found" if c.tag == "spectrum" and c.get("value") is None
                                                                          else "please provide one of 'value' or 'filename'"))
@@ -912,37 +928,34 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                         if len(pairs) < 2:
                             raise SceneError("<spectrum filename=%r>: fewer than two samples" % fn)
                         return spectrum.interpolated_to_rgb(pairs)
-                    return spectrum.parse(c.tag, sub(c.get("value")))
+                    return spectrum.parse(c.tag, self.sub(c.get("value")))
                 if c.tag == "blackbody":
-                    t = sub(c.get("temperature", "")).strip()
-                    return spectrum.blackbody_to_rgb(float(t[:-1] if t[-1:] in "kK" else t), float(sub(c.get("scale", "1"))))
+                    t = self.sub(c.get("temperature", "")).strip()
+                    return spectrum.blackbody_to_rgb(float(t[:-1] if t[-1:] in "kK" else t), float(self.sub(c.get("scale", "1"))))
                 if c.tag == "texture" or c.tag == "ref":
-                    if strict:
+                    if self.strict:
                         raise SceneError("a texture on %r is not supported (bitmaps on reflectances, specular colours, roughconductor / roughdielectric alpha, mask opacity and bump maps are)" % name)
-                    warnings.append("texture on %r ignored: the plug-in's default value is used" % name)
+                    self.warnings.append("texture on %r ignored: the plug-in's default value is used" % name)
                     break
         return np.full(3, default, f32)
 
-    textures, tex_index = [], {}
-
-    def bitmap_texture(elem, what):
-        """<texture type="bitmap"> (textures/bitmap.cpp:90-330) → index into `textures`.  The image is decoded here — 8-bit files through the
-        sRGB curve unless `gamma` says otherwise (bitmap.cpp:182-204), luminance replicated to RGB — because the integrator only ever
-        reads level 0 of the MIP map (include/ppg.h ppg_texture)."""
+    def _bitmap_texture(self, elem, what):
+        """<texture type="bitmap"> (textures/bitmap.cpp:90-330) → index into `self.textures`.  The image is decoded here because the integrator only
+        ever reads level 0 of the MIP map (include/ppg.h ppg_texture)."""
         if elem.tag == "ref":
-            target = tex_by_id.get(elem.get("id"))
+            target = self.tex_by_id.get(elem.get("id"))
             if target is None:
                 raise SceneError("<ref id=%r>: no such texture" % elem.get("id"))
             elem = target
         if elem.get("type") == "scale":
-            return scaled_texture(elem, what)
+            return self._scaled_texture(elem, what)
         if elem.get("type") != "bitmap":
             raise SceneError("texture type %r on %s is not supported (bitmap only)" % (elem.get("type"), what))
-        tp = _props(elem, sub)
+        tp = _props(elem, self.sub)
         fn = tp.get("filename")
         if not fn:
             raise SceneError("bitmap texture without filename")
-        full = fn if os.path.isabs(fn) else os.path.join(base, fn)
+        full = fn if os.path.isabs(fn) else os.path.join(self.base, fn)
         wrap = str(tp.get("wrapMode", "repeat")).lower()
         wu, wv = str(tp.get("wrapModeU", wrap)).lower(), str(tp.get("wrapModeV", wrap)).lower()
         for wm in (wu, wv):
@@ -952,83 +965,30 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         if filt not in ("ewa", "trilinear", "nearest", "bilinear"):
             raise SceneError("bitmap: invalid filter type %r" % filt)
         gamma = float(tp.get("gamma", 0.0))
-        key = (full, wu, wv, filt == "nearest", gamma, float(tp.get("uscale", 1.0)), float(tp.get("vscale", 1.0)), float(tp.get("uoffset", 0.0)), float(tp.get("voffset", 0.0)),
-               str(tp.get("channel", "")))
-        if key in tex_index:
-            return tex_index[key]
+        su, sv, ou, ov = (float(tp.get(k, d)) for k, d in (("uscale", 1.0), ("vscale", 1.0), ("uoffset", 0.0), ("voffset", 0.0)))
+        key = (full, wu, wv, filt == "nearest", gamma, su, sv, ou, ov, str(tp.get("channel", "")))
+        if key in self.tex_index:
+            return self.tex_index[key]
         if not os.path.exists(full):
             raise SceneError("bitmap: file '%s' not found" % full)
         channel = str(tp.get("channel", "")).lower()
         if channel and channel not in ("r", "g", "b", "a"):
             raise SceneError("bitmap: channel %r is not supported (r, g, b, a)" % tp.get("channel"))
-        from . import imageio
-        from .scenes import srgb8_table
-        t = dict(uv_scale=(float(tp.get("uscale", 1.0)), float(tp.get("vscale", 1.0))), uv_offset=(float(tp.get("uoffset", 0.0)), float(tp.get("voffset", 0.0))),
-                 wrap_u=wu, wrap_v=wv, nearest=filt == "nearest", source=os.path.basename(full))
-        ext = os.path.splitext(full)[1].lower()
-        if ext in (".exr", ".pfm", ".hdr", ".rgbe"):
-            t["rgb"] = np.ascontiguousarray(imageio.read_image(full), f32)  # floating point data is linear (bitmap.cpp:190-192)
-            if channel:  # a monochrome texture of that channel (bitmap.cpp:238-256)
-                if channel == "a":
-                    raise SceneError("bitmap: '%s' has no channel 'a' (channels present: r, g, b)" % full)
-                t["rgb"] = np.ascontiguousarray(np.repeat(t["rgb"][:, :, "rgb".index(channel)][:, :, None], 3, 2))
-        elif channel:  # one channel of the file as a monochrome texture, replicated to RGB (bitmap.cpp:238-256)
-            try:
-                from PIL import Image
-            except ImportError:
-                raise SceneError("bitmap: decoding '%s' needs PIL (scene conversion only)" % full)
-            im = Image.open(full)
-            if im.mode in ("P", "CMYK", "1"):
-                im = im.convert("RGBA" if "transparency" in im.info else "RGB")
-            names = {"L": "y", "LA": "ya", "RGB": "rgb", "RGBA": "rgba"}.get(im.mode)
-            a = np.asarray(im)
-            if names is None or a.dtype != np.uint8:
-                raise SceneError("bitmap: '%s': only 8-bit images are decoded here" % full)
-            if channel not in names:
-                raise SceneError("bitmap: '%s' has no channel %r (channels present: %s)" % (full, channel, ", ".join(names)))
-            a = np.ascontiguousarray(np.repeat(a.reshape(a.shape[0], a.shape[1], -1)[:, :, names.index(channel)][:, :, None], 3, 2))
-            g = 1.0 if channel == "a" else gamma  # alpha is never gamma-corrected (bitmap.cpp:258-263)
-            if g == 0.0 or g == -1.0:
-                t["srgb8"] = a
-                t["rgb"] = srgb8_table()[a]
-            elif g == 1.0:
-                t["rgb"] = (a.astype(f32) / f32(255.0)).astype(f32)
-            else:
-                t["rgb"] = np.power(a.astype(np.float64) / 255.0, g).astype(f32)
-        else:
-            try:
-                from PIL import Image
-            except ImportError:
-                raise SceneError("bitmap: decoding '%s' needs PIL (scene conversion only)" % full)
-            im = Image.open(full)
-            if im.mode in ("P", "RGBA", "LA", "CMYK", "1", "I;16", "I"):  # alpha is dropped for a spectrum texture (bitmap.cpp:218-236: EAuto → RGB / luminance)
-                im = im.convert("RGB" if im.mode != "LA" else "L")
-            a = np.asarray(im)
-            if a.dtype != np.uint8:
-                raise SceneError("bitmap: '%s': only 8-bit images are decoded here" % full)
-            if a.ndim == 2:
-                a = np.repeat(a[:, :, None], 3, 2)
-            a = np.ascontiguousarray(a[:, :, :3])
-            if gamma == 0.0 or gamma == -1.0:  # the file's own encoding: sRGB for 8-bit images
-                t["srgb8"] = a
-                t["rgb"] = srgb8_table()[a]
-            else:  # an explicit gamma (bump maps ask for 1.0, bumpmap.cpp:121-126): value^gamma on value / 255
-                t["rgb"] = np.power(a.astype(np.float64) / 255.0, gamma).astype(f32)
+        t = dict(uv_scale=(su, sv), uv_offset=(ou, ov), wrap_u=wu, wrap_v=wv, nearest=filt == "nearest", source=os.path.basename(full))
+        t.update(_decode_bitmap(full, channel, gamma))
         # Texture::getAverage: the mean of the full-resolution image (the MIP map's 1x1 level; exact for power-of-two sizes)
         t["average"] = [float(v) for v in t["rgb"].reshape(-1, 3).mean(0, dtype=np.float64)]
-        tex_index[key] = len(textures)
-        textures.append(t)
-        return tex_index[key]
+        self.tex_index[key] = len(self.textures)
+        self.textures.append(t)
+        return self.tex_index[key]
 
-    scaled_index = {}
-
-    def scaled_texture(elem, what):
-        """<texture type="scale"> (textures/scale.cpp:50-156) around one bitmap, or around a scale around one → index into `textures` of a
+    def _scaled_texture(self, elem, what):
+        """<texture type="scale"> (textures/scale.cpp:50-156) around one bitmap, or around a scale around one → index into `self.textures` of a
         texture of its own whose texels are the nested one's times the factor, in float32: what ScalingTexture::getBitmap does.  Its
         average and a bump map's gradient scale with it.  (Mitsuba scales the interpolated value; the two differ by rounding only.)"""
-        tp = _props(elem, sub)
+        tp = _props(elem, self.sub)
         if any(c.get("name") == "scale" and c.tag in ("rgb", "srgb", "spectrum", "blackbody") for c in elem):
-            factor = np.asarray(colour(elem, "scale", 1.0), f32)
+            factor = np.asarray(self._colour(elem, "scale", 1.0), f32)
         else:
             try:
                 factor = np.full(3, f32(float(tp.get("scale", 1.0))), f32)
@@ -1036,56 +996,65 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 raise SceneError("scale: could not parse the scale factor %r" % (tp.get("scale"),))
         if not (np.isfinite(factor).all() and (factor > 0).all()):  # Assert(m_scale.min() > 0), scale.cpp:62
             raise SceneError("scale: the scale factor must be finite and > 0 (got %s)" % ", ".join(repr(float(v)) for v in factor))
-        nested = [c for c in elem if c.tag == "texture" or (c.tag == "ref" and c.get("id") in tex_by_id)]
+        nested = [c for c in elem if c.tag == "texture" or (c.tag == "ref" and c.get("id") in self.tex_by_id)]
         if "value" in tp or any(c.get("name") == "value" for c in elem):
             raise SceneError("scale: a constant 'value' inside a scale texture is not supported (a bitmap, or a scale around one, is)")
         if not nested:
             raise SceneError("scale: The scale plugin needs a nested texture!")  # scale.cpp:73-74
         if len(nested) > 1:
             raise SceneError("scale: exactly one nested texture is required (found %d)" % len(nested))
-        inner = tex_by_id[nested[0].get("id")] if nested[0].tag == "ref" else nested[0]
+        inner = self.tex_by_id[nested[0].get("id")] if nested[0].tag == "ref" else nested[0]
         if inner.get("type") not in ("bitmap", "scale"):
             raise SceneError("scale: texture type %r inside a scale texture is not supported (a bitmap, or a scale around one, is)" % inner.get("type"))
-        ti = bitmap_texture(inner, what)
-        src = textures[ti]
+        ti = self._bitmap_texture(inner, what)
+        src = self.textures[ti]
         if "one" in (src["wrap_u"], src["wrap_v"]):
             raise SceneError("scale around a bitmap with wrap mode 'one' is not supported: the constant outside the image would not scale")
         key = (ti,) + tuple(float(v) for v in factor)
-        if key not in scaled_index:
+        if key not in self.scaled_index:
             rgb = np.ascontiguousarray(src["rgb"] * factor, f32)
-            textures.append(dict({k: v for k, v in src.items() if k != "srgb8"}, rgb=rgb,
-                                 average=[float(v) for v in rgb.reshape(-1, 3).mean(0, dtype=np.float64)]))
-            scaled_index[key] = len(textures) - 1
-        return scaled_index[key]
+            self.textures.append(dict({k: v for k, v in src.items() if k != "srgb8"}, rgb=rgb,
+                                    average=[float(v) for v in rgb.reshape(-1, 3).mean(0, dtype=np.float64)]))
+            self.scaled_index[key] = len(self.textures) - 1
+        return self.scaled_index[key]
 
-    def colour_or_texture(elem, name, default, wrap=False):
+    def _is_texture(self, c):  # whether the child element is a <texture>, or a <ref> to a top-level one
+        return c.tag == "texture" or (c.tag == "ref" and c.get("id") in self.tex_by_id)
+
+    def _colour_or_texture(self, elem, name, default, wrap=False):
         """(rgb, texture index or None) of a parameter that may be a bitmap; rgb is then the bitmap's average.  `wrap`: a loader failure is
         reported as "texture on <name>: ..." (the parameters other than the diffuse reflectance)."""
         for c in elem:
-            if c.get("name") == name and c.tag in ("texture", "ref") and (c.tag == "texture" or c.get("id") in tex_by_id):
+            if c.get("name") == name and self._is_texture(c):
                 try:
-                    ti = bitmap_texture(c, name)
+                    ti = self._bitmap_texture(c, name)
                 except SceneError as e:
-                    if strict:
+                    if self.strict:
                         if wrap:
                             raise SceneError("texture on %r: %s" % (name, e))
                         raise
-                    warnings.append("texture on %r ignored (%s): the plug-in's default value is used" % (name, e))
+                    self.warnings.append("texture on %r ignored (%s): the plug-in's default value is used" % (name, e))
                     return np.full(3, default, f32), None
-                return np.asarray(textures[ti]["average"], f32), ti
-        return colour(elem, name, default), None
+                return np.asarray(self.textures[ti]["average"], f32), ti
+        return self._colour(elem, name, default), None
 
-    IOR = {"vacuum": 1.0, "air": 1.000277, "water": 1.3330, "polypropylene": 1.49, "bk7": 1.5046, "diamond": 2.419}  # well-known constants (cf. ior.h)
+    def _textured(self, elem, m, name, d, field="reflectance", key="texture"):  # m[field] = the colour `name`; a bitmap on it gives its average, and its index as m[key]
+        c, ti = self._colour_or_texture(elem, name, d, wrap=name != "reflectance" and name != "diffuseReflectance")
+        m[field] = tuple(float(v) for v in c)
+        if ti is not None:
+            m[key] = ti
+        return m
 
-    def lookup_ior(p, name, default):  # lookupIOR, ior.h:95-111: a number or a material name
-        v = p.get(name, default)
-        if isinstance(v, (int, float)):
-            return float(v)
-        if str(v).lower() not in IOR:
-            raise SceneError("IOR name %r is not in the built-in list %s; give a number" % (v, sorted(IOR)))
-        return IOR[str(v).lower()]
+    def _specular(self, elem, m, name):  # the `specular` field: plastic specularReflectance, dielectric specularTransmittance
+        return self._textured(elem, m, name, 1.0, "specular", "specular_texture")
 
-    def microfacet(elem, p, m, what):
+    def _alpha_value(self, elem, p, tex, name):  # (a roughness, its texture index or None): a number, or a bitmap read as eval(its).average(), the constant
+        if name not in tex:
+            return float(p[name]), None
+        c, ti = self._colour_or_texture(elem, name, 0.1, wrap=True)
+        return float((f32(c[0]) + f32(c[1]) + f32(c[2])) / f32(3.0)), ti  # Spectrum::average (spectrum.h:481-486)
+
+    def _microfacet(self, elem, p, m, what):
         """MicrofacetDistribution(props) (microfacet.h:99-145) plus the plug-ins' texture children on alpha / alphaU / alphaV: fills the
         material's alpha (alphaU) and, where the BSDF states alphaU / alphaV, phong or sampleVisible = false, the keys of the general entry
         (alpha_v, alpha_v_texture, distribution = "phong", sample_visible = False; bindings.Microfacet)."""
@@ -1098,39 +1067,31 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             raise SceneError("%s: distribution %r is not supported by the scene loaders on this plug-in (ggx, beckmann; phong on roughplastic)" % (what, distr))
         tex = {c.get("name") for c in elem if c.tag in ("texture", "ref")} & {"alpha", "alphaU", "alphaV"}
         has = lambda n: n in p or n in tex  # noqa: E731
-
-        def value(name):  # a number, or a bitmap read as eval(its).average(): the constant is then the texture's average
-            if name not in tex:
-                return float(p[name]), None
-            c, ti = colour_or_texture(elem, name, 0.1, wrap=True)
-            return float((f32(c[0]) + f32(c[1]) + f32(c[2])) / f32(3.0)), ti  # Spectrum::average (spectrum.h:481-486)
         if has("alpha"):
             if has("alphaU") or has("alphaV"):
                 raise SceneError("%s: Microfacet model: please specify either 'alpha' or 'alphaU'/'alphaV'." % what)
-            m["alpha"], ti = value("alpha")
+            m["alpha"], ti = self._alpha_value(elem, p, tex, "alpha")
             if ti is not None:
                 m["alpha_texture"] = ti
         elif has("alphaU") or has("alphaV"):
             if not has("alphaU") or not has("alphaV"):
                 raise SceneError("%s: Microfacet model: both 'alphaU' and 'alphaV' must be specified." % what)
-            m["alpha"], tu = value("alphaU")
-            m["alpha_v"], tv = value("alphaV")
+            m["alpha"], tu = self._alpha_value(elem, p, tex, "alphaU")
+            m["alpha_v"], tv = self._alpha_value(elem, p, tex, "alphaV")
             if tu is not None:
                 m["alpha_texture"] = tu
             if tv is not None:
                 m["alpha_v_texture"] = tv
         else:
             m["alpha"] = 0.1
-        if distr in ("phong", "as"):
-            m["distribution"] = "phong"
-        elif distr == "beckmann":  # Mitsuba's default (microfacet.h:99)
-            m["distribution"] = "beckmann"
+        if distr != "ggx":  # (beckmann is Mitsuba's default, microfacet.h:99)
+            m["distribution"] = "beckmann" if distr == "beckmann" else "phong"
         if not p.get("sampleVisible", True):
             m["sample_visible"] = False
         return m
 
-    def conductor_ior(elem, p, what):  # conductor.cpp:160-186 / roughconductor.cpp:174-186
-        ext = lookup_ior(p, "extEta", "air")
+    def _conductor_ior(self, elem, p, what):  # conductor.cpp:160-186 / roughconductor.cpp:174-186
+        ext = _lookup_ior(p, "extEta", "air")
         name = str(p.get("material", "Cu"))
         if name.lower() == "none":
             int_eta, int_k = np.zeros(3, f32), np.ones(3, f32)
@@ -1138,242 +1099,159 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             have = {c.get("name") for c in elem}
             int_eta = int_k = None
             if not ({"eta", "k"} <= have):  # the measured spectra ship with Mitsuba (data/ior/<name>.{eta,k}.spd), not with this repository
-                ddir = data_dir or os.environ.get("PPG_MITSUBA_DATA")
+                ddir = self.data_dir or os.environ.get("PPG_MITSUBA_DATA")
                 files = [os.path.join(ddir, "ior", "%s.%s.spd" % (name, part)) for part in ("eta", "k")] if ddir else []
                 if not ddir or not all(os.path.exists(f) for f in files):
                     raise SceneError("%s(material=%s): the measured IOR spectra data/ior/%s.{eta,k}.spd come with Mitsuba: pass data_dir (--data-dir) / "
                                      "PPG_MITSUBA_DATA, or give <spectrum|rgb name=\"eta\"> and \"k\"" % (what, name, name))
                 int_eta, int_k = (spectrum.interpolated_to_rgb(spectrum.read_spd(f), zero_extend=False, clamp=False) for f in files)
-        eta = colour(elem, "eta", 0.0) if any(c.get("name") == "eta" for c in elem) else int_eta
-        k = colour(elem, "k", 1.0) if any(c.get("name") == "k" for c in elem) else int_k
+        eta = self._colour(elem, "eta", 0.0) if _stated(elem, "eta") else int_eta
+        k = self._colour(elem, "k", 1.0) if _stated(elem, "k") else int_k
         return tuple(float(v) for v in (eta / f32(ext))), tuple(float(v) for v in (k / f32(ext)))  # roughconductor.cpp:185-186
 
-    rt_slices, rt_index = [], {}
-
-    def make_bsdf(elem, allow_twosided=True):
-        t = elem.get("type")
-        p = _props(elem, sub)
-        rgb = lambda name, d: tuple(float(v) for v in colour(elem, name, d))  # noqa: E731
-        def textured(m, name, d, field="reflectance", key="texture"):  # a bitmap on a colour: constant = its average, plus the texture index
-            c, ti = colour_or_texture(elem, name, d, wrap=name != "reflectance" and name != "diffuseReflectance")
-            m[field] = tuple(float(v) for v in c)
-            if ti is not None:
-                m[key] = ti
-            return m
-        def specular(m, name):  # the `specular` field: plastic specularReflectance, dielectric specularTransmittance
-            return textured(m, name, 1.0, "specular", "specular_texture")
-        if t == "diffuse":
-            return textured(dict(type=0), "reflectance", 0.5)
-        if t == "twosided" and allow_twosided:
-            inner = [c for c in elem if c.tag == "bsdf"]
-            if len(inner) == 1:
-                m = make_bsdf(inner[0], allow_twosided=False)
-                if m["type"] in (6, 7, 8):
-                    raise SceneError("twosided(dielectric): only BRDFs can be two-sided (twosided.cpp:84-88)")
-                if m["type"] == 11:
-                    raise SceneError("twosided(difftrans): only BRDFs can be two-sided (twosided.cpp:84-88)")
-                if m["type"] == 13:
-                    raise SceneError("twosided(null): only BRDFs can be two-sided (twosided.cpp:84-88)")
-                if m["type"] == 0 and not m.get("_substituted") and "blend" not in m:
-                    return dict({k: v for k, v in m.items() if k in TEXTURE_KEYS + ("coating",)}, type=1, reflectance=m["reflectance"])
-                return dict(m, twosided=True)  # (a blended material's own record stays diffuse + two-sided: it only carries the adapters)
-            t = "twosided(%s)" % ",".join(c.get("type", "?") for c in inner)
-        elif t == "mask" and allow_twosided:
-            inner = [c for c in elem if c.tag == "bsdf"]
-            if len(inner) == 1:
-                m = make_bsdf(inner[0])
-                if "opacity" in m:
-                    raise SceneError("mask(mask(...)) is not supported")
-                if m["type"] == 13:
-                    raise SceneError("mask(null) is not supported")
-                if m["type"] == 1:
-                    m = dict({k: v for k, v in m.items() if k in TEXTURE_KEYS + ("coating",)}, type=0, reflectance=m["reflectance"], twosided=True)
-                return textured(dict(m), "opacity", 0.5, "opacity", "opacity_texture")
-            t = "mask(%s)" % ",".join(c.get("type", "?") for c in inner)
-        elif t == "conductor":
-            if str(p.get("material", "Cu")).lower() == "none":
-                return textured(dict(type=2), "specularReflectance", 1.0)
-            eta, k = conductor_ior(elem, p, t)
-            return textured(dict(type=3, eta=eta, k=k), "specularReflectance", 1.0)
-        elif t == "roughconductor":
-            eta, k = conductor_ior(elem, p, t)
-            return microfacet(elem, p, textured(dict(type=4, eta=eta, k=k), "specularReflectance", 1.0), t)
-        elif t == "plastic":
-            eta = lookup_ior(p, "intIOR", "polypropylene") / lookup_ior(p, "extIOR", "air")
-            return textured(specular(dict(type=5, eta=float(f32(eta)), nonlinear=bool(p.get("nonlinear", False))), "specularReflectance"),
-                            "diffuseReflectance", 0.5)
-        elif t == "dielectric":
-            eta = lookup_ior(p, "intIOR", "bk7") / lookup_ior(p, "extIOR", "air")
-            return specular(textured(dict(type=6, eta=float(f32(eta))), "specularReflectance", 1.0), "specularTransmittance")
-        elif t == "thindielectric":
-            eta = lookup_ior(p, "intIOR", "bk7") / lookup_ior(p, "extIOR", "air")
-            return specular(textured(dict(type=7, eta=float(f32(eta))), "specularReflectance", 1.0), "specularTransmittance")
-        elif t == "roughplastic":  # roughplastic.cpp:197-227, 285-305
-            from . import rtrans as _rt
-            if any(c.get("name") in ("alpha", "alphaU", "alphaV") and c.tag in ("texture", "ref") for c in elem):
-                # its rough-transmittance slice is reduced to ONE alpha at conversion; a varying alpha needs the 2-D table (roughplastic.cpp:295-298)
-                raise SceneError("roughplastic: a texture on 'alpha' is not supported (roughness maps are, on roughconductor and roughdielectric)")
-            int_ior, ext_ior = lookup_ior(p, "intIOR", "polypropylene"), lookup_ior(p, "extIOR", "air")
-            if int_ior < 0 or ext_ior < 0 or int_ior == ext_ior:
-                raise SceneError("roughplastic: the interior and exterior indices of refraction must be positive and differ")
-            mf = microfacet(elem, p, {}, t)
-            if mf.get("alpha_v", mf["alpha"]) != mf["alpha"]:  # roughplastic.cpp:221-223
-                raise SceneError("roughplastic: The 'roughplastic' plugin currently does not support anisotropic microfacet distributions!")
-            alpha, eta = mf["alpha"], float(f32(int_ior / ext_ior))
-            distr = mf.get("distribution", "ggx")  # the name of its table, data/microfacet/<name>.dat
-            key = (distr, float(f32(alpha)), eta)
-            if key not in rt_index:
-                try:
-                    rt_slices.append(_rt.roughplastic_slice(distr, alpha, eta, data_dir))
-                except _rt.RoughTransmittanceError as e:
-                    raise SceneError("roughplastic: %s" % e)
-                rt_index[key] = len(rt_slices) - 1
-            return textured(specular(dict(mf, type=9, eta=eta, nonlinear=bool(p.get("nonlinear", False)), rtrans=rt_index[key]), "specularReflectance"),
-                            "diffuseReflectance", 0.5)
-        elif t == "roughdielectric":  # roughdielectric.cpp:183-211
-            int_ior, ext_ior = lookup_ior(p, "intIOR", "bk7"), lookup_ior(p, "extIOR", "air")
-            if int_ior < 0 or ext_ior < 0 or int_ior == ext_ior:
-                raise SceneError("roughdielectric: the interior and exterior indices of refraction must be positive and differ")
-            return microfacet(elem, p, specular(textured(dict(type=8, eta=float(f32(int_ior / ext_ior))), "specularReflectance", 1.0), "specularTransmittance"), t)
-        elif t in ("roughdiffuse", "difftrans", "phong"):  # roughdiffuse.cpp:88-122, difftrans.cpp:49-74, phong.cpp:60-107
-            return lobe(elem, p, t, textured)
-        elif t == "null":  # null.cpp:36-80: no parameters
-            return dict(type=13)
-        if t in ("coating", "roughcoating"):  # SmoothCoating (coating.cpp:109-200), RoughCoating (roughcoating.cpp:114-227): the innermost adapter
-            inner = [c for c in elem if c.tag == "bsdf"]
+    def _rt_slice(self, what, distr, alpha, eta):  # index into `self.rt_slices` of the rough-transmittance slice, read from Mitsuba's data/microfacet/<distr>.dat
+        from . import rtrans
+        key = (distr, float(f32(alpha)), eta)
+        if key not in self.rt_index:
             try:
-                return coated(elem, p, t, inner)
-            except SceneError as e:
-                if strict:
-                    raise
-                if len(inner) == 1:  # where a strict load refuses this coat, a lenient one renders the nested BSDF
-                    warnings.append("bsdf %r dropped around its nested bsdf (%s)" % (t, e))
-                    return make_bsdf(inner[0], allow_twosided)
-        if t in ("blendbsdf", "mixturebsdf"):  # BlendBSDF (blendbsdf.cpp:70-133), MixtureBSDF (mixturebsdf.cpp:64-172): where a leaf stands
-            try:
-                return blended(elem, p, t)
-            except SceneError as e:
-                if strict:
-                    raise
-                warnings.append("bsdf %r replaced by diffuse(0.5) (%s)" % (t, e))
-                return dict(type=0, reflectance=(0.5, 0.5, 0.5), _substituted=True)
-        if t == "bumpmap":  # BumpMap (bumpmap.cpp:60-133): one nested BSDF + one displacement texture, the outermost adapter
-            inner = [c for c in elem if c.tag == "bsdf"]
-            disp = [c for c in elem if c.tag in ("texture", "ref") and (c.tag == "texture" or c.get("id") in tex_by_id)]
-            if len(inner) == 1 and len(disp) == 1:
-                m = make_bsdf(inner[0], allow_twosided)
-                try:
-                    if "bump" in m:
-                        raise SceneError("bumpmap(bumpmap(...)) is not supported")
-                    if "normal_map" in m:
-                        raise SceneError("bumpmap(normalmap(...)) is not supported")
-                    if m["type"] == 13:
-                        raise SceneError("bumpmap(null) is not supported: the null BSDF has no shading frame to perturb")
-                    if disp[0].tag == "texture" and disp[0].get("type") == "bitmap" and "gamma" not in _props(disp[0], sub):
-                        raise SceneError("When using a bitmap texture as a bump map, please explicitly specify the 'gamma' parameter of the bitmap plugin")  # bumpmap.cpp:121-126
-                    return dict(m, bump=bitmap_texture(disp[0], "bumpmap"))
-                except SceneError as e:
-                    if strict:
-                        raise
-                    warnings.append("bump map dropped around its nested bsdf (%s)" % e)
-                    return m
-        if t == "normalmap":  # NormalMap (normalmap.cpp:47-106): one nested BSDF + one RGB normal map, where a bumpmap stands
-            inner = [c for c in elem if c.tag == "bsdf"]
-            maps = [c for c in elem if c.tag in ("texture", "ref") and (c.tag == "texture" or c.get("id") in tex_by_id)]
-            if strict:
-                if not inner:
-                    raise SceneError("normalmap: A child BSDF instance is required")  # normalmap.cpp:60-61
-                if len(inner) > 1:
-                    raise SceneError("normalmap: Only a single nested BSDF can be added!")  # normalmap.cpp:91-92
-                if not maps:
-                    raise SceneError("normalmap: A normal map texture must be specified")  # normalmap.cpp:62-63
-                if len(maps) > 1:
-                    raise SceneError("normalmap: Only a single normal texture can be specified!")  # normalmap.cpp:95-96
-            if len(inner) == 1 and len(maps) == 1:
-                m = make_bsdf(inner[0], allow_twosided)
-                try:
-                    if "normal_map" in m:
-                        raise SceneError("normalmap(normalmap(...)) is not supported")
-                    if "bump" in m:
-                        raise SceneError("normalmap(bumpmap(...)) is not supported")
-                    if m["type"] == 13:
-                        raise SceneError("normalmap(null) is not supported: the null BSDF has no shading frame to perturb")
-                    if maps[0].tag == "texture" and maps[0].get("type") == "bitmap" and "gamma" not in _props(maps[0], sub):
-                        raise SceneError("When using a bitmap texture as a normal map, please explicitly specify the 'gamma' parameter of the bitmap plugin")  # normalmap.cpp:97-100
-                    return dict(m, normal_map=bitmap_texture(maps[0], "normalmap"))
-                except SceneError as e:
-                    if strict:
-                        raise
-                    warnings.append("normal map dropped around its nested bsdf (%s)" % e)
-                    return m
-        if not strict and t in ("bumpmap", "normalmap"):  # adapters around one nested BSDF: render the nested one
-            inner = [c for c in elem if c.tag == "bsdf"]
-            if len(inner) == 1:
-                warnings.append("bsdf %r dropped around its nested bsdf" % t)
-                return make_bsdf(inner[0], allow_twosided)
-        if strict:
-            raise SceneError("bsdf type %r is not supported yet (diffuse, roughdiffuse, difftrans, phong, conductor, roughconductor, plastic, roughplastic, dielectric, "
-                             "thindielectric, roughdielectric, null, mask(...), twosided(...), bumpmap(...), normalmap(...); "
-                             "SURVEY.md §8 f1)" % t)
-        warnings.append("bsdf %r replaced by diffuse(0.5)" % t)
-        return dict(type=0, reflectance=(0.5, 0.5, 0.5), _substituted=True)
+                self.rt_slices.append(rtrans.roughplastic_slice(distr, alpha, eta, self.data_dir))
+            except rtrans.RoughTransmittanceError as e:
+                raise SceneError("%s: %s" % (what, e))
+            self.rt_index[key] = len(self.rt_slices) - 1
+        return self.rt_index[key]
 
-    def lobe(elem, p, t, textured):
-        """roughdiffuse, difftrans and phong with Mitsuba's parameter names and defaults; the colours may be bitmaps, the numbers and phong's
-        specularReflectance are constants.  BSDF::ensureEnergyConservation (bsdf.cpp:88-146) as their configure() calls it."""
-        def number(name, default):
-            if any(c.get("name") == name and c.tag in ("texture", "ref") for c in elem):
-                if strict:
-                    raise SceneError("%s: a texture on %r is not supported (a bitmap on its reflectance is)" % (t, name))
-                warnings.append("texture on %r ignored: the plug-in's default value is used" % name)
-                return float(f32(default))
-            return float(f32(p.get(name, default)))
-        has = lambda n: any(c.get("name") == n for c in elem)  # noqa: E731
-        if t == "roughdiffuse":
-            m = textured(dict(type=10, alpha=number("alpha", 0.2)), "reflectance" if has("reflectance") or not has("diffuseReflectance") else "diffuseReflectance", 0.5)
-            if p.get("useFastApprox", False):
-                m["fast_approx"] = True
-            return conserve_energy(m, p, t, [("reflectance", "reflectance", "texture")])
-        if t == "difftrans":
-            m = textured(dict(type=11), "transmittance" if has("transmittance") or not has("diffuseTransmittance") else "diffuseTransmittance", 0.5)
-            return conserve_energy(m, p, t, [("transmittance", "reflectance", "texture")])
-        if strict and any(c.get("name") == "specularReflectance" and c.tag in ("texture", "ref") for c in elem):
-            raise SceneError("phong: a texture on 'specularReflectance' is not supported (a bitmap on its diffuseReflectance is)")
-        m = dict(type=12, exponent=number("exponent", 30.0), specular=tuple(float(v) for v in colour(elem, "specularReflectance", 0.2)))
-        m = textured(m, "diffuseReflectance", 0.5)
-        return conserve_energy(m, p, t, [("specularReflectance", "specular", None), ("diffuseReflectance", "reflectance", "texture")])
-
-    def conserve_energy(m, p, t, params):
-        """params: (Mitsuba's name, the dict's field, the key of its bitmap or None) — one, or the pair whose maxima are added.  A
-        component-wise maximum above 1 scales them by 0.99 / max; a bitmap's maximum is taken over its texels, and a scaled bitmap is a
-        texture of its own (the `scale` texture around it)."""
+    def _conserve_energy(self, m, p, t, params):
+        """BSDF::ensureEnergyConservation (bsdf.cpp:88-146) as the lobes' configure() calls it.  params: (Mitsuba's name, the dict's field, the key
+        of its bitmap or None) — one, or the pair whose maxima are added.  A component-wise maximum above 1 scales them by 0.99 / max; a bitmap's
+        maximum is taken over its texels, and a scaled bitmap is a texture of its own (the `scale` texture around it)."""
         if not p.get("ensureEnergyConservation", True):
             return m
         total = np.zeros(3, f32)
         for _, field, key in params:
             ti = m.get(key) if key else None
-            total = total + (np.asarray(m[field], f32) if ti is None else textures[ti]["rgb"].reshape(-1, 3).max(0).astype(f32))
+            total = total + (np.asarray(m[field], f32) if ti is None else self.textures[ti]["rgb"].reshape(-1, 3).max(0).astype(f32))
         actual = f32(total.max())
         if not actual > 1:
             return m
         scale = f32(0.99) * (f32(1.0) / actual)
         names = " and ".join('"%s"' % n for n, _, _ in params)
-        warnings.append("bsdf %r violates energy conservation: %s %s a component-wise maximum of %s (> 1) and will be scaled by %s "
-                        "(ensureEnergyConservation=false prevents this)" % (t, names, "has" if len(params) == 1 else "sum to", float(actual), float(scale)))
+        self.warnings.append("bsdf %r violates energy conservation: %s %s a component-wise maximum of %s (> 1) and will be scaled by %s "
+                             "(ensureEnergyConservation=false prevents this)" % (t, names, "has" if len(params) == 1 else "sum to", float(actual), float(scale)))
         for _, field, key in params:
             m[field] = tuple(float(f32(v) * scale) for v in m[field])
             if key and m.get(key) is not None:
-                src = textures[m[key]]
-                scaled = dict({k: v for k, v in src.items() if k != "srgb8"}, rgb=np.ascontiguousarray(src["rgb"] * scale, f32),
-                              average=[float(f32(v) * scale) for v in src["average"]])
-                textures.append(scaled)
-                m[key] = len(textures) - 1
+                src = self.textures[m[key]]
+                self.textures.append(dict({k: v for k, v in src.items() if k != "srgb8"}, rgb=np.ascontiguousarray(src["rgb"] * scale, f32),
+                                          average=[float(f32(v) * scale) for v in src["average"]]))
+                m[key] = len(self.textures) - 1
         return m
 
-    def coated(elem, p, t, inner):
-        """the nested BSDF's dict with the adapter's parameters under `coating` (bindings.Coating).  The nesting order this build knows is
-        bumpmap(mask(twosided(coating(leaf)))); the plug-ins' parameters are constants."""
-        from . import rtrans as _rt
+    def _unsupported_bsdf(self, t):  # where every reader that cannot make anything of its element ends: refused by name, or the lenient load's diffuse(0.5)
+        if self.strict:
+            raise SceneError("bsdf type %r is not supported yet (diffuse, roughdiffuse, difftrans, phong, conductor, roughconductor, plastic, roughplastic, dielectric, "
+                             "thindielectric, roughdielectric, null, mask(...), twosided(...), bumpmap(...), normalmap(...); SURVEY.md §8 f1)" % t)
+        self.warnings.append("bsdf %r replaced by diffuse(0.5)" % t)
+        return dict(type=0, reflectance=(0.5, 0.5, 0.5), _substituted=True)
+
+    def _read_twosided(self, elem, p, allow_twosided):
+        inner = _nested_bsdfs(elem)
+        if len(inner) != 1:
+            return self._unsupported_bsdf("twosided(%s)" % ",".join(c.get("type", "?") for c in inner))
+        m = self._make_bsdf(inner[0], allow_twosided=False)
+        transmissive = {6: "dielectric", 7: "dielectric", 8: "dielectric", 11: "difftrans", 13: "null"}.get(m["type"])
+        if transmissive:
+            raise SceneError("twosided(%s): only BRDFs can be two-sided (twosided.cpp:84-88)" % transmissive)
+        if m["type"] == 0 and not m.get("_substituted") and "blend" not in m:
+            return dict({k: v for k, v in m.items() if k in TEXTURE_KEYS + ("coating",)}, type=1, reflectance=m["reflectance"])
+        return dict(m, twosided=True)  # (a blended material's own record stays diffuse + two-sided: it only carries the adapters)
+
+    def _read_mask(self, elem, p, allow_twosided):
+        inner = _nested_bsdfs(elem)
+        if len(inner) != 1:
+            return self._unsupported_bsdf("mask(%s)" % ",".join(c.get("type", "?") for c in inner))
+        m = self._make_bsdf(inner[0])
+        if "opacity" in m:
+            raise SceneError("mask(mask(...)) is not supported")
+        if m["type"] == 13:
+            raise SceneError("mask(null) is not supported")
+        if m["type"] == 1:
+            m = dict({k: v for k, v in m.items() if k in TEXTURE_KEYS + ("coating",)}, type=0, reflectance=m["reflectance"], twosided=True)
+        return self._textured(elem, dict(m), "opacity", 0.5, "opacity", "opacity_texture")
+
+    def _read_conductor(self, elem, p, allow_twosided):  # conductor and roughconductor
+        t = elem.get("type")
+        if t == "conductor" and str(p.get("material", "Cu")).lower() == "none":
+            return self._textured(elem, dict(type=2), "specularReflectance", 1.0)
+        eta, k = self._conductor_ior(elem, p, t)
+        m = self._textured(elem, dict(type=3 if t == "conductor" else 4, eta=eta, k=k), "specularReflectance", 1.0)
+        return m if t == "conductor" else self._microfacet(elem, p, m, t)
+
+    def _read_plastic(self, elem, p, allow_twosided):
+        eta = _lookup_ior(p, "intIOR", "polypropylene") / _lookup_ior(p, "extIOR", "air")
+        m = self._specular(elem, dict(type=5, eta=float(f32(eta)), nonlinear=bool(p.get("nonlinear", False))), "specularReflectance")
+        return self._textured(elem, m, "diffuseReflectance", 0.5)
+
+    def _read_dielectric(self, elem, p, allow_twosided):  # dielectric and thindielectric
+        eta = _lookup_ior(p, "intIOR", "bk7") / _lookup_ior(p, "extIOR", "air")
+        m = self._textured(elem, dict(type=6 if elem.get("type") == "dielectric" else 7, eta=float(f32(eta))), "specularReflectance", 1.0)
+        return self._specular(elem, m, "specularTransmittance")
+
+    def _read_roughplastic(self, elem, p, allow_twosided):  # roughplastic.cpp:197-227, 285-305
+        if _texture_on(elem, "alpha", "alphaU", "alphaV"):
+            # its rough-transmittance slice is reduced to ONE alpha at conversion; a varying alpha needs the 2-D table (roughplastic.cpp:295-298)
+            raise SceneError("roughplastic: a texture on 'alpha' is not supported (roughness maps are, on roughconductor and roughdielectric)")
+        eta = _dielectric_eta(p, "roughplastic", "polypropylene")
+        mf = self._microfacet(elem, p, {}, "roughplastic")
+        if mf.get("alpha_v", mf["alpha"]) != mf["alpha"]:  # roughplastic.cpp:221-223
+            raise SceneError("roughplastic: The 'roughplastic' plugin currently does not support anisotropic microfacet distributions!")
+        # (the distribution is also the name of its table, data/microfacet/<name>.dat)
+        m = dict(mf, type=9, eta=eta, nonlinear=bool(p.get("nonlinear", False)), rtrans=self._rt_slice("roughplastic", mf.get("distribution", "ggx"), mf["alpha"], eta))
+        return self._textured(elem, self._specular(elem, m, "specularReflectance"), "diffuseReflectance", 0.5)
+
+    def _read_roughdielectric(self, elem, p, allow_twosided):
+        m = self._textured(elem, dict(type=8, eta=_dielectric_eta(p, "roughdielectric", "bk7")), "specularReflectance", 1.0)
+        return self._microfacet(elem, p, self._specular(elem, m, "specularTransmittance"), "roughdielectric")
+
+    def _lobe_number(self, elem, p, name, default):  # a float32 parameter of roughdiffuse / phong that must be a constant
+        if _texture_on(elem, name):
+            if self.strict:
+                raise SceneError("%s: a texture on %r is not supported (a bitmap on its reflectance is)" % (elem.get("type"), name))
+            self.warnings.append("texture on %r ignored: the plug-in's default value is used" % name)
+            return float(f32(default))
+        return float(f32(p.get(name, default)))
+
+    def _read_roughdiffuse(self, elem, p, allow_twosided):  # roughdiffuse.cpp:88-122
+        old_name = _stated(elem, "diffuseReflectance") and not _stated(elem, "reflectance")
+        m = self._textured(elem, dict(type=10, alpha=self._lobe_number(elem, p, "alpha", 0.2)), "diffuseReflectance" if old_name else "reflectance", 0.5)
+        if p.get("useFastApprox", False):
+            m["fast_approx"] = True
+        return self._conserve_energy(m, p, "roughdiffuse", [("reflectance", "reflectance", "texture")])
+
+    def _read_difftrans(self, elem, p, allow_twosided):  # difftrans.cpp:49-74
+        old_name = _stated(elem, "diffuseTransmittance") and not _stated(elem, "transmittance")
+        m = self._textured(elem, dict(type=11), "diffuseTransmittance" if old_name else "transmittance", 0.5)
+        return self._conserve_energy(m, p, "difftrans", [("transmittance", "reflectance", "texture")])
+
+    def _read_phong(self, elem, p, allow_twosided):  # phong.cpp:60-107: the colours may be bitmaps, the exponent and specularReflectance are constants
+        if self.strict and _texture_on(elem, "specularReflectance"):
+            raise SceneError("phong: a texture on 'specularReflectance' is not supported (a bitmap on its diffuseReflectance is)")
+        m = dict(type=12, exponent=self._lobe_number(elem, p, "exponent", 30.0), specular=tuple(float(v) for v in self._colour(elem, "specularReflectance", 0.2)))
+        m = self._textured(elem, m, "diffuseReflectance", 0.5)
+        return self._conserve_energy(m, p, "phong", [("specularReflectance", "specular", None), ("diffuseReflectance", "reflectance", "texture")])
+
+    def _read_coating(self, elem, p, allow_twosided):  # SmoothCoating (coating.cpp:109-200), RoughCoating (roughcoating.cpp:114-227): the innermost adapter
+        t, inner = elem.get("type"), _nested_bsdfs(elem)
+        try:
+            return self._coated(elem, p, t, inner)
+        except SceneError as e:
+            if self.strict:
+                raise
+            if len(inner) != 1:
+                return self._unsupported_bsdf(t)
+            self.warnings.append("bsdf %r dropped around its nested bsdf (%s)" % (t, e))  # where a strict load refuses this coat, a lenient one renders the nested BSDF
+            return self._make_bsdf(inner[0], allow_twosided)
+
+    def _coated(self, elem, p, t, inner):  # the nested BSDF's dict with the adapter's parameters under `coating` (bindings.Coating); the plug-ins' parameters are constants
         if len(inner) != 1:
             raise SceneError("%s: exactly one nested bsdf is required (found %d)" % (t, len(inner)))
         it = inner[0].get("type")
@@ -1386,20 +1264,20 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         for c in elem:
             if c.tag in ("texture", "ref") and c.get("name") in ("sigmaA", "specularReflectance", "alpha", "alphaU", "alphaV"):
                 raise SceneError("%s: a texture on %r is not supported" % (t, c.get("name")))
-        m = make_bsdf(inner[0], allow_twosided=False)
+        m = self._make_bsdf(inner[0], allow_twosided=False)
         if m["type"] in (6, 7, 8):
             raise SceneError("%s(%s): a coat on dielectric, thindielectric or roughdielectric is not supported" % (t, it))
         if m["type"] in (10, 11, 12):
             raise SceneError("%s(%s): a coat on roughdiffuse, difftrans or phong is not supported" % (t, it))
         if t == "roughcoating" and m["type"] in (2, 3, 5):
             raise SceneError("roughcoating(%s): a roughcoating over a BSDF with a delta component (conductor, plastic) is not supported" % it)
-        int_ior, ext_ior = lookup_ior(p, "intIOR", "bk7"), lookup_ior(p, "extIOR", "air")
+        int_ior, ext_ior = _lookup_ior(p, "intIOR", "bk7"), _lookup_ior(p, "extIOR", "air")
         if int_ior < 0 or ext_ior < 0 or int_ior == ext_ior:
             raise SceneError("%s: The interior and exterior indices of refraction must be positive and differ!" % t)
         eta = float(f32(int_ior / ext_ior))
         thickness = float(f32(p.get("thickness", 1.0)))
-        sigma_a = tuple(float(v) for v in colour(elem, "sigmaA", 0.0))
-        spec = tuple(float(v) for v in colour(elem, "specularReflectance", 1.0))
+        sigma_a = tuple(float(v) for v in self._colour(elem, "sigmaA", 0.0))
+        spec = tuple(float(v) for v in self._colour(elem, "specularReflectance", 1.0))
         if not (eta > 0 and eta != 1.0):
             raise SceneError("%s: The interior and exterior indices of refraction must be positive and differ!" % t)
         if not all(math.isfinite(v) for v in (eta, thickness) + sigma_a + spec):
@@ -1408,59 +1286,62 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             raise SceneError("%s: thickness and sigmaA must not be negative" % t)
         c = dict(kind=t, eta=eta, thickness=thickness, sigma_a=sigma_a, specular=spec)
         if t == "roughcoating":
-            mf = microfacet(elem, p, {}, t)
+            mf = self._microfacet(elem, p, {}, t)
             if mf.get("alpha_v", mf["alpha"]) != mf["alpha"]:  # roughcoating.cpp:143-145 (the plug-in's own words)
                 raise SceneError("roughcoating: The 'roughplastic' plugin currently does not support anisotropic microfacet distributions!")
             if not math.isfinite(mf["alpha"]):
                 raise SceneError("roughcoating: a parameter is not finite")
             distr = mf.get("distribution", "ggx")
-            key = (distr, float(f32(mf["alpha"])), eta)  # the reduction roughplastic uses, interned with its slices
-            if key not in rt_index:
-                try:
-                    rt_slices.append(_rt.roughplastic_slice(distr, mf["alpha"], eta, data_dir))
-                except _rt.RoughTransmittanceError as e:
-                    raise SceneError("roughcoating: %s" % e)
-                rt_index[key] = len(rt_slices) - 1
-            c.update(alpha=float(f32(mf["alpha"])), distribution=distr, sample_visible=bool(mf.get("sample_visible", True)), slice=rt_index[key])
+            c.update(alpha=float(f32(mf["alpha"])), distribution=distr, sample_visible=bool(mf.get("sample_visible", True)),
+                     slice=self._rt_slice(t, distr, mf["alpha"], eta))  # the reduction roughplastic uses, interned with its slices
         return dict(m, coating=c)
 
-    def blended(elem, p, t):
+    def _read_blend(self, elem, p, allow_twosided):  # BlendBSDF (blendbsdf.cpp:70-133), MixtureBSDF (mixturebsdf.cpp:64-172): where a leaf stands
+        t = elem.get("type")
+        try:
+            return self._blended(elem, p, t)
+        except SceneError as e:
+            if self.strict:
+                raise
+            self.warnings.append("bsdf %r replaced by diffuse(0.5) (%s)" % (t, e))
+            return dict(type=0, reflectance=(0.5, 0.5, 0.5), _substituted=True)
+
+    def _blend_child(self, t, c):  # one child of a blend as a material dict: a nested <bsdf>, or a <ref> to a <bsdf> with an id that stands before it
+        if c.tag == "ref":
+            if c.get("id") not in self.by_id:
+                raise SceneError('%s: <ref id="%s">: no such bsdf before it' % (t, c.get("id")))
+            m, it = dict(self.materials[self.by_id[c.get("id")]]), "ref " + c.get("id")
+        else:
+            it = c.get("type")
+            if it in ("twosided", "mask", "bumpmap", "normalmap"):
+                raise SceneError("%s(%s) is not supported: the nesting order is bumpmap(mask(twosided(%s(..))))" % (t, it, t))
+            m = self._make_bsdf(c, allow_twosided=False)
+        if "blend" in m:
+            raise SceneError("%s(%s): blends of blends are not supported" % (t, it))
+        if "coating" in m:
+            raise SceneError("%s(%s): coated children are not supported" % (t, it))
+        if m["type"] in (6, 7, 8):
+            raise SceneError("%s(%s): dielectric, thindielectric and roughdielectric children are not supported" % (t, it))
+        if m["type"] in (10, 11, 12):
+            raise SceneError("%s(%s): roughdiffuse, difftrans and phong children are not supported" % (t, it))
+        if m["type"] == 13:
+            raise SceneError("%s(%s): a null child is not supported" % (t, it))
+        if m["type"] == 1 or m.get("twosided") or "opacity" in m or "bump" in m or "normal_map" in m:
+            raise SceneError("%s(%s) is not supported: the nesting order is bumpmap(mask(twosided(%s(..))))" % (t, it, t))
+        return {k: v for k, v in m.items() if not k.startswith("_")}
+
+    def _blended(self, elem, p, t):
         """the blended material's own record — diffuse, carrying nothing but the adapters that go around it — with the combinator under
-        `blend` (bindings.Blend), its children as material dicts.  The nesting order this build knows is bumpmap(mask(twosided(blend(leaf,
-        ..)))); a child is a nested <bsdf> or a <ref> to a <bsdf> with an id that stands before it."""
-        kids = [c for c in elem if c.tag == "bsdf" or (c.tag == "ref" and c.get("name") != "weight" and c.get("id") not in tex_by_id)]
+        `blend` (bindings.Blend), its children as material dicts"""
+        kids = [c for c in elem if c.tag == "bsdf" or (c.tag == "ref" and c.get("name") != "weight" and c.get("id") not in self.tex_by_id)]
         if len(kids) > 4:
             raise SceneError("%s: more than 4 nested bsdfs are not supported (found %d)" % (t, len(kids)))
         if t == "blendbsdf" and len(kids) != 2:
             raise SceneError("blendbsdf: BSDF count mismatch: expected two nested BSDF instances! (found %d)" % len(kids))
-        children = []
-        for c in kids:
-            if c.tag == "ref":
-                if c.get("id") not in by_id:
-                    raise SceneError('%s: <ref id="%s">: no such bsdf before it' % (t, c.get("id")))
-                m, it = dict(materials[by_id[c.get("id")]]), "ref " + c.get("id")
-            else:
-                it = c.get("type")
-                if it in ("twosided", "mask", "bumpmap", "normalmap"):
-                    raise SceneError("%s(%s) is not supported: the nesting order is bumpmap(mask(twosided(%s(..))))" % (t, it, t))
-                m = make_bsdf(c, allow_twosided=False)
-            if "blend" in m:
-                raise SceneError("%s(%s): blends of blends are not supported" % (t, it))
-            if "coating" in m:
-                raise SceneError("%s(%s): coated children are not supported" % (t, it))
-            if m["type"] in (6, 7, 8):
-                raise SceneError("%s(%s): dielectric, thindielectric and roughdielectric children are not supported" % (t, it))
-            if m["type"] in (10, 11, 12):
-                raise SceneError("%s(%s): roughdiffuse, difftrans and phong children are not supported" % (t, it))
-            if m["type"] == 13:
-                raise SceneError("%s(%s): a null child is not supported" % (t, it))
-            if m["type"] == 1 or m.get("twosided") or "opacity" in m or "bump" in m or "normal_map" in m:
-                raise SceneError("%s(%s) is not supported: the nesting order is bumpmap(mask(twosided(%s(..))))" % (t, it, t))
-            children.append({k: v for k, v in m.items() if not k.startswith("_")})
-        b = dict(kind=t, children=tuple(children))
+        b = dict(kind=t, children=tuple([self._blend_child(t, c) for c in kids]))
         if t == "blendbsdf":
-            if any(c.get("name") == "weight" and c.tag in ("texture", "ref") for c in elem):
-                w, ti = colour_or_texture(elem, "weight", 0.5, wrap=True)
+            if _texture_on(elem, "weight"):
+                w, ti = self._colour_or_texture(elem, "weight", 0.5, wrap=True)
                 b["weight"] = float((f32(w[0]) + f32(w[1]) + f32(w[2])) * (f32(1.0) / f32(3)))  # Spectrum::average (spectrum.h:481-486)
                 b["weight_texture"] = ti
             else:
@@ -1478,8 +1359,8 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 weights = tuple(float(f32(float(w))) for w in tokens)
             except ValueError:
                 raise SceneError("mixturebsdf: Could not parse the BSDF weights!")
-            if len(weights) != len(children):
-                raise SceneError("mixturebsdf: BSDF count mismatch: %d bsdfs, but specified %d weights" % (len(children), len(weights)))
+            if len(weights) != len(kids):
+                raise SceneError("mixturebsdf: BSDF count mismatch: %d bsdfs, but specified %d weights" % (len(kids), len(weights)))
             if not all(math.isfinite(w) and w >= 0 for w in weights):
                 raise SceneError("mixturebsdf: weights must be finite and not negative")
             if not sum(weights) > 0:
@@ -1487,149 +1368,252 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
             b.update(weights=weights, ensure_energy_conservation=bool(p.get("ensureEnergyConservation", True)))
         return dict(type=0, reflectance=(0.5, 0.5, 0.5), blend=b)
 
-    def blend_children(m):
-        return [c for c in (m.get("blend") or {}).get("children", ()) if isinstance(c, dict)]
+    def _normal_adapter(self, elem, allow_twosided, key, label, strict_counts):
+        """bumpmap (bumpmap.cpp:60-133: a displacement texture, `key` = bump) and normalmap (normalmap.cpp:47-106: an RGB normal map, normal_map): one nested BSDF +
+        one texture, the outermost adapter.  `label` names the texture in the messages; strict_counts: a strict load refuses other child counts in the plug-in's words."""
+        t, inner, maps = elem.get("type"), _nested_bsdfs(elem), [c for c in elem if self._is_texture(c)]
+        if strict_counts and self.strict:  # normalmap.cpp:60-63, 91-96
+            for bad, why in ((not inner, "A child BSDF instance is required"), (len(inner) > 1, "Only a single nested BSDF can be added!"),
+                             (not maps, "A normal map texture must be specified"), (len(maps) > 1, "Only a single normal texture can be specified!")):
+                if bad:
+                    raise SceneError("normalmap: " + why)
+        if len(inner) != 1 or (len(maps) != 1 and self.strict):
+            return self._unsupported_bsdf(t)
+        if len(maps) != 1:  # adapters around one nested BSDF: a lenient load renders the nested one
+            self.warnings.append("bsdf %r dropped around its nested bsdf" % t)
+            return self._make_bsdf(inner[0], allow_twosided)
+        m = self._make_bsdf(inner[0], allow_twosided)
+        try:
+            for other, name in (("bump", "bumpmap"), ("normal_map", "normalmap")):
+                if other in m:
+                    raise SceneError("%s(%s(...)) is not supported" % (t, name))
+            if m["type"] == 13:
+                raise SceneError("%s(null) is not supported: the null BSDF has no shading frame to perturb" % t)
+            if maps[0].tag == "texture" and maps[0].get("type") == "bitmap" and "gamma" not in _props(maps[0], self.sub):  # bumpmap.cpp:121-126, normalmap.cpp:97-100
+                raise SceneError("When using a bitmap texture as a %s, please explicitly specify the 'gamma' parameter of the bitmap plugin" % label)
+            return dict(m, **{key: self._bitmap_texture(maps[0], t)})
+        except SceneError as e:
+            if self.strict:
+                raise
+            self.warnings.append("%s dropped around its nested bsdf (%s)" % (label, e))
+            return m
 
-    def reads_bitmap(m):
-        """whether the material, the weight of its blend or a child of it reads a bitmap at the hit's uv"""
-        return (any(k in m for k in TEXTURE_KEYS) or (m.get("blend") or {}).get("weight_texture") is not None
-                or any(reads_bitmap(c) for c in blend_children(m)))
+    def _make_bsdf(self, elem, allow_twosided=True):
+        """<bsdf> → material dict (bindings.Material.from_dict), by the reader of its plug-in: _BSDF_READERS below.  allow_twosided = False inside a
+        twosided, a coat or a blend: no twosided or mask goes there."""
+        t, p = elem.get("type"), _props(elem, self.sub)
+        reader = _BSDF_READERS.get(t)
+        if reader is None or (t in ("twosided", "mask") and not allow_twosided):
+            return self._unsupported_bsdf(t)
+        return reader(self, elem, p, allow_twosided)
 
-    def intern(m):
-        m = {k: v for k, v in m.items() if not k.startswith("_")}
-        freeze = lambda v: tuple(freeze(x) for x in v) if isinstance(v, (tuple, list)) else (tuple(sorted((a, freeze(b)) for a, b in v.items())) if isinstance(v, dict) else v)  # noqa: E731
-        key = tuple(sorted((k, freeze(v)) for k, v in m.items()))
-        if key not in mat_index:
-            mat_index[key] = len(materials)
-            materials.append(m)
-        return mat_index[key]
+    def _intern(self, m):  # index of the material dict in `self.materials`, appended where no equal one is there yet, without its private `_` keys
+        m ={k: v for k, v in m.items() if not k.startswith("_")}
+        key = tuple(sorted((k, _freeze(v)) for k, v in m.items()))
+        if key not in self.mat_index:
+            self.mat_index[key] = len(self.materials)
+            self.materials.append(m)
+        return self.mat_index[key]
 
-    for b in root.findall("bsdf"):
-        if b.get("id"):
-            by_id[b.get("id")] = intern(make_bsdf(b))
-    # an id may also sit on a NESTED bsdf (KITCHEN references the twosided element inside a bumpmap): every element with an id is a named
-    # object in Mitsuba (scenehandler.cpp: namedObjects)
-    for top in root.findall("bsdf"):
-        for b in top.iter("bsdf"):
-            if b is not top and b.get("id") and b.get("id") not in by_id:
-                by_id[b.get("id")] = intern(make_bsdf(b))
-    environment = envmap = None
-    delta_emitters = []
-    for em in root.findall("emitter"):
-        if em.get("type") in ("point", "spot", "directional"):
-            delta_emitters.append(parse_delta_emitter(em, sub, colour))
-            continue
-        if em.get("type") == "constant" and environment is None and envmap is None:
-            environment = tuple(float(v) for v in colour(em, "radiance", 1.0))
-            continue
-        if em.get("type") == "envmap" and environment is None and envmap is None:  # EnvironmentMap::EnvironmentMap, envmap.cpp:100-190
-            from . import imageio
-            ep = _props(em, sub)
-            fn = ep.get("filename")
-            if not fn:
-                raise SceneError("envmap emitter without filename")
-            full = fn if os.path.isabs(fn) else os.path.join(base, fn)
-            if not os.path.exists(full):
-                raise SceneError("envmap: file '%s' not found" % full)
-            try:
-                rgb = imageio.read_image(full)
-            except (ValueError, AssertionError) as e:
-                raise SceneError("envmap: %s" % e)
-            tw = em.find("transform")
-            R = (_transform(tw, sub) if tw is not None else np.eye(4, dtype=f32))[:3, :3].astype(f32)
-            if not np.allclose(R @ R.T, np.eye(3), atol=1e-4):
-                raise SceneError("envmap: toWorld must be a rotation")
-            envmap = dict(rgb=rgb, scale=float(ep.get("scale", 1.0)), to_world=[float(v) for v in R.reshape(-1)])
-            continue
-        if em.get("type") == "sunsky" and environment is None and envmap is None:
-            # SunSkyEmitter (sunsky.cpp:100-235) bakes sun + sky into a radiance map and instantiates `envmap` on it: same bake here
-            # (ppg_host/sunsky.py); the Hosek-Wilkie / Preetham tables are read from the operator's Mitsuba source tree
-            from . import sunsky
-            ddir = data_dir or os.environ.get("PPG_MITSUBA_DATA")
-            src = mitsuba_src or os.environ.get("PPG_MITSUBA_SRC") or (os.path.dirname(os.path.abspath(ddir)) if ddir else None)
-            if not src or not os.path.exists(os.path.join(src, "src", "emitters", "sunsky", "skymodeldata.h")):
-                if strict:
-                    raise SceneError("sunsky: the sky model's coefficient tables (src/emitters/sunsky/skymodeldata.h, sunmodel.h) come with Mitsuba's "
-                                     "source tree: pass mitsuba_src / --data-dir <tree>/data / PPG_MITSUBA_SRC")
-                warnings.append("emitter 'sunsky' skipped (no Mitsuba source tree for the sky model's tables)")
-                continue
-            ep = _props(em, sub)
-            for c in em:
-                if c.get("name") == "albedo" and c.tag in ("rgb", "srgb", "spectrum"):
-                    ep["albedo"] = [float(v) for v in spectrum.parse(c.tag, sub(c.get("value")))]
-            try:
-                rgb, _ = sunsky.bake(ep, src)
-            except (ValueError, NotImplementedError) as e:
-                raise SceneError("sunsky: %s" % e)
-            tw = em.find("transform")
-            R = (_transform(tw, sub) if tw is not None else np.eye(4, dtype=f32))[:3, :3].astype(f32)
-            if not np.allclose(R @ R.T, np.eye(3), atol=1e-4):
-                raise SceneError("sunsky: toWorld must be a rotation")
-            envmap = dict(rgb=rgb, scale=1.0, to_world=[float(v) for v in R.reshape(-1)])
-            continue
-        if not strict:
-            warnings.append("emitter %r skipped (not supported)" % em.get("type"))
-            continue
-        raise SceneError("emitter type %r is not supported (area emitters on shapes, `point`, `spot` and `directional` emitters, and one "
-                         "`constant`, `envmap` or `sunsky` environment emitter; SURVEY.md §8 f2)" % em.get("type"))
+    def _read_integrator(self, root):
+        """→ (the guided_path properties for ppg_create, the `field` integrators of a multichannel integrator (misc/multichannel.cpp))"""
+        integ = root.find("integrator")
+        if integ is None:
+            raise SceneError("no <integrator>")
+        fields = []
+        if integ.get("type") == "multichannel":
+            nested = [c for c in integ if c.tag == "integrator"]
+            guided = [c for c in nested if c.get("type") == "guided_path"]
+            other = [c.get("type") for c in nested if c.get("type") not in ("guided_path", "field")]
+            if len(guided) != 1 or other:
+                raise SceneError("a multichannel integrator must hold exactly one 'guided_path' and otherwise 'field' integrators only (found %s)"
+                                 % (", ".join(repr(c.get("type")) for c in nested) or "none"))
+            for c in nested:  # the `field` integrators (misc/field.cpp): (name, undefined rgb)
+                if c.get("type") != "field":
+                    continue
+                name = _props(c, self.sub).get("field")
+                if name == "shapeIndex":
+                    raise SceneError("field integrator: 'shapeIndex' is not offered: shapes are flattened on loading, use 'primIndex'")
+                if name not in FIELD_NAMES:
+                    raise SceneError("field integrator: Invalid 'field' parameter. Must be one of 'position', 'relPosition', 'distance', 'geoNormal', "
+                                     "'shNormal', 'primIndex', 'shapeIndex', or 'uv'! (got %r)" % (name,))
+                undefined = np.zeros(3, f32)
+                for u in c:
+                    if u.get("name") == "undefined":
+                        if u.tag == "float":
+                            undefined = np.full(3, float(self.sub(u.get("value"))), f32)
+                        elif u.tag in ("rgb", "srgb", "spectrum"):
+                            undefined = np.asarray(spectrum.parse(u.tag, self.sub(u.get("value"))), f32)
+                fields.append((name, tuple(float(v) for v in undefined)))
+            integ = guided[0]
+        if integ.get("type") != "guided_path":
+            raise SceneError("integrator type %r is not supported: this path implements 'guided_path' only" % integ.get("type"))
+        props = {}
+        for k, v in _props(integ, self.sub).items():
+            if k in GUIDED_PATH_PROPS:
+                props[k] = GUIDED_PATH_PROPS[k](v)
+            else:
+                self.warnings.append("integrator property %r is not used by guided_path" % k)  # Mitsuba warns about unqueried properties, too
+        return props, fields
 
-    # ---- shapes
-    collected, emitters, spheres, shapes = [], [], [], []
-    default_mat = None
-    for sh in root.findall("shape"):
+    def _read_sensor(self, root, width, height):
+        """<sensor> with its film and sampler → (the SceneDesc's camera, lens and rfilter, the info dict's width, height and sample_count)"""
+        sensor = root.find("sensor")
+        if sensor is None:
+            raise SceneError("no <sensor>")
+        stype = sensor.get("type")
+        if stype not in ("perspective", "thinlens"):
+            raise SceneError("sensor type %r is not supported (perspective, thinlens)" % stype)
+        sp = _props(sensor, self.sub)
+        film = sensor.find("film")
+        fp = _props(film, self.sub) if film is not None else {}
+        if film is not None and film.get("type") not in ("hdrfilm", "ldrfilm", None):
+            raise SceneError("film type %r is not supported" % film.get("type"))
+        rf = film.find("rfilter") if film is not None else None
+        rfilter = parse_rfilter(rf, self.sub) if rf is not None else None
+        if rf is None:
+            self.warnings.append("no <rfilter>: Mitsuba would default to gaussian; the box filter is used")
+        W = int(width or fp.get("width", 768)); H = int(height or fp.get("height", 576))
+        if "fov" in sp and "focalLength" in sp:  # PerspectiveCamera::PerspectiveCamera, sensor.cpp:226-228
+            raise SceneError("%s sensor: please specify either a focal length ('focalLength') or a field of view ('fov')" % stype)
+        if "fov" in sp:
+            fov, fov_axis = sp["fov"], str(sp.get("fovAxis", "x")).lower()
+        else:
+            fov, fov_axis = focal_length_fov(str(sp.get("focalLength", "50mm"))), "diagonal"
+        tw = sensor.find("transform")
+        c2w = _transform(tw, self.sub) if tw is not None else np.eye(4, dtype=f32)
+        camera = perspective_camera_from_matrix(c2w, fov, fov_axis, sp.get("nearClip", 1e-2), sp.get("farClip", 1e4), W, H)
+        lens = None
+        if stype == "thinlens":  # ThinLens::ThinLens, thinlens.cpp:124-142; focusDistance defaults to farClip (sensor.cpp:162)
+            if "apertureRadius" not in sp:
+                raise SceneError("thinlens sensor without 'apertureRadius'")
+            r = f32(sp["apertureRadius"])
+            if r == 0:
+                self.warnings.append("thinlens: can't have a zero aperture radius -- setting to 0.0001")
+                r = f32(1e-4)
+            focus = f32(sp.get("focusDistance", sp.get("farClip", 1e4)))
+            if _has_scale(c2w):
+                raise SceneError("thinlens sensor: scale factors in the camera-to-world transformation are not allowed")
+            if not (np.isfinite(r) and r > 0 and np.isfinite(focus) and focus > 0):
+                raise SceneError("thinlens sensor: apertureRadius and focusDistance must be finite and > 0 (got %r, %r)" % (float(r), float(focus)))
+            lens = dict(aperture_radius=float(r), focus_distance=float(focus))
+        sampler = sensor.find("sampler")
+        info = dict(width=W, height=H, sample_count=_props(sampler, self.sub).get("sampleCount") if sampler is not None else None)
+        return dict(camera=camera, lens=lens, rfilter=rfilter), info
+
+    def _read_named_bsdfs(self, root):  # the <bsdf id=...> elements → self.by_id
+        for b in root.findall("bsdf"):
+            if b.get("id"):
+                self.by_id[b.get("id")] = self._intern(self._make_bsdf(b))
+        # an id may also sit on a NESTED bsdf (KITCHEN references the twosided element inside a bumpmap): every element with an id is a named
+        # object in Mitsuba (scenehandler.cpp: namedObjects)
+        for top in root.findall("bsdf"):
+            for b in top.iter("bsdf"):
+                if b is not top and b.get("id") and b.get("id") not in self.by_id:
+                    self.by_id[b.get("id")] = self._intern(self._make_bsdf(b))
+
+    def _rotation(self, em, what):  # the 3x3 of an environment emitter's toWorld, which must be a rotation
+        tw = em.find("transform")
+        R = (_transform(tw, self.sub) if tw is not None else np.eye(4, dtype=f32))[:3, :3].astype(f32)
+        if not np.allclose(R @ R.T, np.eye(3), atol=1e-4):
+            raise SceneError("%s: toWorld must be a rotation" % what)
+        return [float(v) for v in R.reshape(-1)]
+
+    def _read_sunsky(self, em):
+        """SunSkyEmitter (sunsky.cpp:100-235) bakes sun + sky into a radiance map and instantiates `envmap` on it: same bake here (ppg_host/sunsky.py);
+        the Hosek-Wilkie / Preetham tables are read from the operator's Mitsuba source tree.  None where a lenient load finds no such tree."""
+        from . import sunsky
+        ddir = self.data_dir or os.environ.get("PPG_MITSUBA_DATA")
+        src = self.mitsuba_src or os.environ.get("PPG_MITSUBA_SRC") or (os.path.dirname(os.path.abspath(ddir)) if ddir else None)
+        if not src or not os.path.exists(os.path.join(src, "src", "emitters", "sunsky", "skymodeldata.h")):
+            if self.strict:
+                raise SceneError("sunsky: the sky model's coefficient tables (src/emitters/sunsky/skymodeldata.h, sunmodel.h) come with Mitsuba's "
+                                 "source tree: pass mitsuba_src / --data-dir <tree>/data / PPG_MITSUBA_SRC")
+            self.warnings.append("emitter 'sunsky' skipped (no Mitsuba source tree for the sky model's tables)")
+            return None
+        ep = _props(em, self.sub)
+        for c in em:
+            if c.get("name") == "albedo" and c.tag in ("rgb", "srgb", "spectrum"):
+                ep["albedo"] = [float(v) for v in spectrum.parse(c.tag, self.sub(c.get("value")))]
+        try:
+            rgb, _ = sunsky.bake(ep, src)
+        except (ValueError, NotImplementedError) as e:
+            raise SceneError("sunsky: %s" % e)
+        return dict(rgb=rgb, scale=1.0, to_world=self._rotation(em, "sunsky"))
+
+    def _read_emitters(self, root):  # the top-level <emitter>s → SceneDesc's environment, envmap, delta_emitters; only the first environment emitter counts
+        environment = envmap = None
+        delta_emitters = []
+        for em in root.findall("emitter"):
+            t = em.get("type")
+            if t in ("point", "spot", "directional"):
+                delta_emitters.append(parse_delta_emitter(em, self))
+            elif t == "constant" and environment is None and envmap is None:
+                environment = tuple(float(v) for v in self._colour(em, "radiance", 1.0))
+            elif t == "envmap" and environment is None and envmap is None:  # EnvironmentMap::EnvironmentMap, envmap.cpp:100-190
+                from . import imageio
+                ep = _props(em, self.sub)
+                fn = ep.get("filename")
+                if not fn:
+                    raise SceneError("envmap emitter without filename")
+                full = fn if os.path.isabs(fn) else os.path.join(self.base, fn)
+                if not os.path.exists(full):
+                    raise SceneError("envmap: file '%s' not found" % full)
+                try:
+                    rgb = imageio.read_image(full)
+                except (ValueError, AssertionError) as e:
+                    raise SceneError("envmap: %s" % e)
+                envmap = dict(rgb=rgb, scale=float(ep.get("scale", 1.0)), to_world=self._rotation(em, "envmap"))
+            elif t == "sunsky" and environment is None and envmap is None:
+                envmap = self._read_sunsky(em)
+            elif not self.strict:
+                self.warnings.append("emitter %r skipped (not supported)" % t)
+            else:
+                raise SceneError("emitter type %r is not supported (area emitters on shapes, `point`, `spot` and `directional` emitters, and one "
+                                 "`constant`, `envmap` or `sunsky` environment emitter; SURVEY.md §8 f2)" % t)
+        return dict(environment=environment, envmap=envmap, delta_emitters=delta_emitters)
+
+    def _mesh_file(self, t, sprops):
+        """The file of an obj / ply / serialized shape, or None where a lenient load skips a shape without one.  (obj.cpp tests its properties before it opens the file.)"""
+        fn, label = sprops.get("filename"), {"obj": "Wavefront OBJ file", "ply": "PLY file", "serialized": "serialized mesh file"}[t]
+        if not fn:
+            raise SceneError("%s shape without filename" % t)
+        if t == "obj" and "shapeIndex" in sprops:
+            raise SceneError("obj: shapeIndex is not supported")
+        both = "maxSmoothAngle" in sprops and sprops.get("faceNormals", False)
+        if t == "obj" and both:
+            raise SceneError("The properties 'maxSmoothAngle' and 'faceNormals' can't be specified at the same time!")  # obj.cpp:337-339
+        full = fn if os.path.isabs(fn) else os.path.join(self.base, fn)
+        if not os.path.exists(full):
+            if self.strict:
+                raise SceneError("%s '%s' not found%s" % (label, full, "!" if t == "obj" else ""))  # obj.cpp:230
+            self.warnings.append("shape skipped: %s '%s' not found" % (label, full))
+            return None
+        if both:
+            raise SceneError("The properties 'maxSmoothAngle' and 'faceNormals' can't be specified at the same time!")
+        return full
+
+    def _shape_geometry(self, sh):  # (the triangle meshes of a <shape>, its analytic record or None); None where a lenient load skips the shape
         t = sh.get("type")
-        sprops = _props(sh, sub)
+        sprops = _props(sh, self.sub)
         tw = sh.find("transform")
-        m = _transform(tw, sub) if tw is not None else np.eye(4, dtype=f32)
-        if t == "obj":
-            fn = sprops.get("filename")
-            if not fn:
-                raise SceneError("obj shape without filename")
-            if "shapeIndex" in sprops:
-                raise SceneError("obj: shapeIndex is not supported")
-            if "maxSmoothAngle" in sprops and sprops.get("faceNormals", False):
-                raise SceneError("The properties 'maxSmoothAngle' and 'faceNormals' can't be specified at the same time!")  # obj.cpp:337-339
-            full = fn if os.path.isabs(fn) else os.path.join(base, fn)
-            if not os.path.exists(full):
-                if strict:
-                    raise SceneError("Wavefront OBJ file '%s' not found!" % full)  # obj.cpp:230
-                warnings.append("shape skipped: Wavefront OBJ file '%s' not found" % full)
-                continue
-            meshes = load_obj(full, m, bool(sprops.get("faceNormals", False)), bool(sprops.get("flipNormals", False)),
-                              bool(sprops.get("flipTexCoords", True)), bool(sprops.get("collapse", False)), sprops.get("maxSmoothAngle"))
-        elif t == "ply":
-            fn = sprops.get("filename")
-            if not fn:
-                raise SceneError("ply shape without filename")
-            full = fn if os.path.isabs(fn) else os.path.join(base, fn)
-            if not os.path.exists(full):
-                if strict:
-                    raise SceneError("PLY file '%s' not found" % full)
-                warnings.append("shape skipped: PLY file '%s' not found" % full)
-                continue
-            if "maxSmoothAngle" in sprops and sprops.get("faceNormals", False):
-                raise SceneError("The properties 'maxSmoothAngle' and 'faceNormals' can't be specified at the same time!")
-            meshes = [load_ply(full, m, bool(sprops.get("faceNormals", False)), bool(sprops.get("flipNormals", False)), sprops.get("maxSmoothAngle"))]
-        elif t == "serialized":
-            fn = sprops.get("filename")
-            if not fn:
-                raise SceneError("serialized shape without filename")
-            full = fn if os.path.isabs(fn) else os.path.join(base, fn)
-            if not os.path.exists(full):
-                if strict:
-                    raise SceneError("serialized mesh file '%s' not found" % full)
-                warnings.append("shape skipped: serialized mesh file '%s' not found" % full)
-                continue
-            if "maxSmoothAngle" in sprops and sprops.get("faceNormals", False):
-                raise SceneError("The properties 'maxSmoothAngle' and 'faceNormals' can't be specified at the same time!")
-            meshes = [load_serialized(full, m, int(sprops.get("shapeIndex", 0)), bool(sprops.get("faceNormals", False)), bool(sprops.get("flipNormals", False)),
-                                      sprops.get("maxSmoothAngle"))]
-        elif t == "rectangle":
-            meshes = [rectangle_mesh(m, bool(sprops.get("flipNormals", False)))]
-        elif t == "cube":
-            meshes = [cube_mesh(m, bool(sprops.get("flipNormals", False)))]
-        elif t == "sphere":  # Sphere::Sphere, sphere.cpp:108-131: the scale of toWorld goes into the radius, the rest stays a rotation
-            meshes = []
+        m = _transform(tw, self.sub) if tw is not None else np.eye(4, dtype=f32)
+        face_normals, flip_normals = bool(sprops.get("faceNormals", False)), bool(sprops.get("flipNormals", False))
+        if t in ("obj", "ply", "serialized"):
+            full = self._mesh_file(t, sprops)
+            if full is None:
+                return None
+            if t == "obj":
+                return load_obj(full, m, face_normals, flip_normals, bool(sprops.get("flipTexCoords", True)), bool(sprops.get("collapse", False)),
+                                sprops.get("maxSmoothAngle")), None
+            if t == "ply":
+                return [load_ply(full, m, face_normals, flip_normals, sprops.get("maxSmoothAngle"))], None
+            return [load_serialized(full, m, int(sprops.get("shapeIndex", 0)), face_normals, flip_normals, sprops.get("maxSmoothAngle"))], None
+        if t == "rectangle":
+            return [rectangle_mesh(m, flip_normals)], None
+        if t == "cube":
+            return [cube_mesh(m, flip_normals)], None
+        if t == "sphere":  # Sphere::Sphere, sphere.cpp:108-131: the scale of toWorld goes into the radius, the rest stays a rotation
             c = np.asarray(sprops.get("center", (0.0, 0.0, 0.0)), f32)
             o2w = _translate(*[float(v) for v in c])
             radius = f32(sprops.get("radius", 1.0))
@@ -1640,116 +1624,143 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
                 radius = f32(radius * scale)
             if not radius > 0:
                 raise SceneError("Cannot create spheres of radius <= 0")
-            sphere = dict(center=tuple(float(v) for v in o2w[:3, 3]), radius=float(radius), to_world=[float(v) for v in o2w[:3, :3].reshape(-1)],
-                          flip_normals=bool(sprops.get("flipNormals", False)))
-        elif t == "disk":
-            meshes = []
-            analytic = disk_shape(_transform64(tw, sub) if tw is not None else np.eye(4), bool(sprops.get("flipNormals", False)))
-        elif t == "cylinder":
-            meshes = []
+            return [], dict(center=tuple(float(v) for v in o2w[:3, 3]), radius=float(radius), to_world=[float(v) for v in o2w[:3, :3].reshape(-1)],
+                            flip_normals=flip_normals)
+        if t == "disk":
+            return [], disk_shape(_transform64(tw, self.sub) if tw is not None else np.eye(4), flip_normals)
+        if t == "cylinder":
             # (An element that states nothing — no p0, p1, radius or toWorld — is refused, although Mitsuba would make the unit cylinder of
             # it: `<shape type="cylinder"/>` is what the suite has always used as its example of a shape this loader names and refuses
             # (tests/test_mitsuba_xml.py, tests/test_cpp_host.py), and that pin stays.  Every cylinder of a real scene states its geometry.)
             if tw is None and not any(k in sprops for k in ("p0", "p1", "radius")):
                 raise SceneError("cylinder: none of p0, p1, radius, toWorld is given; state the cylinder's geometry (Mitsuba's defaults — the "
                                  "unit cylinder from the origin along z — are not assumed here)")
-            analytic = cylinder_shape(_transform64(tw, sub) if tw is not None else None, sprops.get("p0", (0.0, 0.0, 0.0)), sprops.get("p1", (0.0, 0.0, 1.0)),
-                                      sprops.get("radius", 1.0), bool(sprops.get("flipNormals", False)))
-        else:
-            raise SceneError("shape type %r is not supported (obj, ply, serialized, rectangle, cube, sphere, disk, cylinder)" % t)
-        # material: nested <bsdf> or <ref id>
-        mat = None
+            return [], cylinder_shape(_transform64(tw, self.sub) if tw is not None else None, sprops.get("p0", (0.0, 0.0, 0.0)), sprops.get("p1", (0.0, 0.0, 1.0)),
+                                      sprops.get("radius", 1.0), flip_normals)
+        raise SceneError("shape type %r is not supported (obj, ply, serialized, rectangle, cube, sphere, disk, cylinder)" % t)
+
+    def _attach(self, sh, meshes, analytic, out):
+        """Give a <shape>'s geometry its material (nested <bsdf> or <ref id>) and area emitter and append it to `out`; refuses what analytic shapes cannot carry"""
+        t, e, mat, em = sh.get("type"), sh.find("emitter"), None, -1
         for c in sh:
             if c.tag == "bsdf":
-                mat = intern(make_bsdf(c))
+                mat = self._intern(self._make_bsdf(c))
             elif c.tag == "ref":
                 rid = c.get("id")
-                if rid not in by_id:
+                if rid not in self.by_id:
                     raise SceneError("<ref id=%r>: no such bsdf" % rid)
-                mat = by_id[rid]
+                mat = self.by_id[rid]
         if mat is None:  # Shape::configure (shape.cpp:48-72): all-absorbing under an emitter, otherwise a 0.5 Lambertian "for convenience"
-            if sh.find("emitter") is not None:
-                mat = intern(dict(type=0, reflectance=(0.0, 0.0, 0.0)))
-            else:
-                if default_mat is None:
-                    default_mat = intern(dict(type=0, reflectance=(0.5, 0.5, 0.5)))
-                mat = default_mat
-        em = -1
-        e = sh.find("emitter")
+            mat = self._intern(dict(type=0, reflectance=(0.0, 0.0, 0.0) if e is not None else (0.5, 0.5, 0.5)))
         if e is not None:
             if e.get("type") != "area":
                 raise SceneError("emitter type %r on a shape is not supported (area only)" % e.get("type"))
             if len(meshes) > 1:
                 raise SceneError("Cannot attach an emitter to an OBJ file containing multiple objects!")  # obj.cpp:757-759
             if t == "obj" and not meshes:
-                continue
-            em = len(emitters)
-            emitters.append(dict(radiance=tuple(float(v) for v in colour(e, "radiance", 1.0))))
-        for mesh in meshes:
-            collected.append((mesh, mat, em))
-        if t in ("sphere", "disk", "cylinder") and "blend" in materials[mat] and reads_bitmap(materials[mat]):
-            raise SceneError("%s: %s: textured BSDFs are only supported on triangle meshes (not on spheres, disks or cylinders)" % (t, materials[mat]["blend"]["kind"]))
-        if t in ("sphere", "disk", "cylinder") and materials[mat].get("type") == 13:
+                return
+            em = len(out["emitters"])
+            out["emitters"].append(dict(radiance=tuple(float(v) for v in self._colour(e, "radiance", 1.0))))
+        out["meshes"] += [(mesh, mat, em) for mesh in meshes]
+        if analytic is None:
+            return
+        material = self.materials[mat]
+        if "blend" in material and _reads_bitmap(material):
+            raise SceneError("%s: %s: textured BSDFs are only supported on triangle meshes (not on spheres, disks or cylinders)" % (t, material["blend"]["kind"]))
+        if material.get("type") == 13:
             raise SceneError("%s: the null BSDF is only supported on triangle meshes (not on spheres, disks or cylinders)" % t)
         if t == "sphere":
-            spheres.append(dict(sphere, material=mat, emitter=em))
-        if t in ("disk", "cylinder"):
-            if any(materials[mat].get(k) is not None for k in TEXTURE_KEYS):
+            out["spheres"].append(dict(analytic, material=mat, emitter=em))
+        else:
+            if any(material.get(k) is not None for k in TEXTURE_KEYS):
                 raise SceneError("%s: textured BSDFs are only supported on triangle meshes (not on spheres, disks or cylinders)" % t)
-            shapes.append(dict(analytic, material=mat, emitter=em))
-    if not collected and not spheres and not shapes:
-        raise SceneError("scene without shapes")
-    # one vertex-normal array for the whole scene: a faceNormals mesh living next to smooth ones gets its vertices
-    # un-shared and its face normals written out (same shading frame as "no normals": skdtree.h:388-401)
-    any_normals = any(m["normals"] is not None for m, _, _ in collected)
-    # texture coordinates only matter on meshes whose BSDF reads a bitmap; the others get NaN rows (= none)
-    # ... or is anisotropic (EAnisotropic: alphaU != alphaV, or either a bitmap), which needs the UV tangents (trimesh.cpp:380, 683-735)
-    # (a blended material asks for what its weight or any of its children asks for)
-    def anisotropic(m):
-        if any(anisotropic(c) for c in blend_children(m)):
-            return True
-        if m.get("alpha_v") is None:
-            return False
-        return (max(f32(m["alpha_v"]), f32(1e-4)) != max(f32(m.get("alpha", 0.1)), f32(1e-4)) or m.get("alpha_texture") is not None
-                or m.get("alpha_v_texture") is not None)
-    wants_uvs = lambda mat: reads_bitmap(materials[mat]) or anisotropic(materials[mat])  # noqa: E731
-    any_uvs = any(m.get("uvs") is not None and wants_uvs(mat) for m, mat, _ in collected)
-    uvl = []
-    pos, nrm, idx, tmat, tem = [], [], [], [], []
-    nv = 0
-    for mesh, mat, em in collected:
-        p, i, n = mesh["positions"], mesh["indices"], mesh["normals"]
-        uv = mesh.get("uvs") if wants_uvs(mat) else None
-        if uv is None and anisotropic(materials[mat]):  # trimesh.cpp:686-691
-            raise SceneError('"%s": computeUVTangents(): texture coordinates are required to generate tangent vectors. If you want to render with an '
-                             'anisotropic material, please make sure that all associated shapes have valid texture coordinates.%s'
-                             % (mesh.get("name", "mesh"), " (This loader's rectangle and cube carry none.)" if mesh.get("name") in ("rectangle", "cube") else ""))
-        if any_normals and n is None:
-            if uv is not None:
-                uv = uv[i.reshape(-1)]
-            p = p[i.reshape(-1)]
-            a, b = p[1::3] - p[0::3], p[2::3] - p[0::3]
-            fnrm = np.cross(a, b).astype(f32)
-            ln = np.sqrt(np.sum(fnrm * fnrm, 1)).astype(f32)
-            fnrm[ln != 0] = fnrm[ln != 0] / ln[ln != 0, None]
-            n = np.repeat(fnrm, 3, 0)
-            i = np.arange(p.shape[0], dtype=np.uint32).reshape(-1, 3)
-        T = i.shape[0]
-        pos.append(p); idx.append(i + np.uint32(nv)); nrm.append(n)
-        uvl.append(uv.astype(f32) if uv is not None else np.full((p.shape[0], 2), np.nan, f32))
-        nv += p.shape[0]
-        tmat.append(np.full(T, mat, np.uint32)); tem.append(np.full(T, em, np.int32))
-    normals = np.concatenate(nrm).astype(f32) if any_normals else None
-    if not collected:  # analytic spheres only
+            out["shapes"].append(dict(analytic, material=mat, emitter=em))
+
+    def _read_shapes(self, root):  # the <shape>s → meshes [(mesh dict, material index, emitter index or -1)], SceneDesc's emitters, spheres and shapes
+        out = dict(meshes=[], emitters=[], spheres=[], shapes=[])
+        for sh in root.findall("shape"):
+            geometry = self._shape_geometry(sh)
+            if geometry is not None:
+                self._attach(sh, *geometry, out)
+        if not out["meshes"] and not out["spheres"] and not out["shapes"]:
+            raise SceneError("scene without shapes")
+        return out.pop("meshes"), out
+
+    def _flatten(self, meshes):
+        """The scene's meshes as one vertex and one triangle list → the SceneDesc's positions, indices, tri_material, tri_emitter, normals, texcoords.
+        One vertex-normal array serves the whole scene: a faceNormals mesh living next to smooth ones gets its vertices un-shared and its face
+        normals written out (same shading frame as "no normals": skdtree.h:388-401).  Texture coordinates only matter on meshes whose BSDF reads a
+        bitmap or is anisotropic; the others get NaN rows (= none).  (A blended material asks for what its weight or any of its children asks for.)"""
+        wants_uvs = lambda mat: _reads_bitmap(self.materials[mat]) or _anisotropic(self.materials[mat])  # noqa: E731
+        any_normals = any(m["normals"] is not None for m, _, _ in meshes)
+        any_uvs = any(m.get("uvs") is not None and wants_uvs(mat) for m, mat, _ in meshes)
+        # (each list starts with an empty array of its type: a scene of analytic shapes only has no mesh to concatenate)
         pos, idx, tmat, tem = [np.zeros((0, 3), f32)], [np.zeros((0, 3), np.uint32)], [np.zeros(0, np.uint32)], [np.zeros(0, np.int32)]
-    from .bindings import expand_blends  # (children of blended materials join the list, behind everything a shape refers to)
-    desc = SceneDesc(np.concatenate(pos).astype(f32), np.concatenate(idx).astype(np.uint32), np.concatenate(tmat), np.concatenate(tem),
-                     expand_blends(materials), emitters, camera, normals, environment, np.stack(rt_slices).astype(f32) if rt_slices else None, spheres, envmap,
-                     np.concatenate(uvl).astype(f32) if any_uvs else None, textures, rfilter, lens, delta_emitters, shapes)
-    if delta_emitters and str(props.get("nee", "never")) != "always":
-        warnings.append("point / spot / directional emitters are reached by next-event estimation only: with nee = %s they contribute nothing in "
-                        "every iteration that runs without it (as in Mitsuba)" % props.get("nee", "never"))
-    info["warnings"] = warnings
+        nrm, uvl, nv = [], [], 0
+        for mesh, mat, em in meshes:
+            p, i, n = mesh["positions"], mesh["indices"], mesh["normals"]
+            uv = mesh.get("uvs") if wants_uvs(mat) else None
+            if uv is None and _anisotropic(self.materials[mat]):  # trimesh.cpp:686-691
+                raise SceneError('"%s": computeUVTangents(): texture coordinates are required to generate tangent vectors. If you want to render with an '
+                                 'anisotropic material, please make sure that all associated shapes have valid texture coordinates.%s'
+                                 % (mesh.get("name", "mesh"), " (This loader's rectangle and cube carry none.)" if mesh.get("name") in ("rectangle", "cube") else ""))
+            if any_normals and n is None:
+                if uv is not None:
+                    uv = uv[i.reshape(-1)]
+                p = p[i.reshape(-1)]
+                a, b = p[1::3] - p[0::3], p[2::3] - p[0::3]
+                fnrm = np.cross(a, b).astype(f32)
+                ln = np.sqrt(np.sum(fnrm * fnrm, 1)).astype(f32)
+                fnrm[ln != 0] = fnrm[ln != 0] / ln[ln != 0, None]
+                n = np.repeat(fnrm, 3, 0)
+                i = np.arange(p.shape[0], dtype=np.uint32).reshape(-1, 3)
+            T = i.shape[0]
+            pos.append(p); idx.append(i + np.uint32(nv)); nrm.append(n)
+            uvl.append(uv.astype(f32) if uv is not None else np.full((p.shape[0], 2), np.nan, f32))
+            nv += p.shape[0]
+            tmat.append(np.full(T, mat, np.uint32)); tem.append(np.full(T, em, np.int32))
+        return dict(positions=np.concatenate(pos).astype(f32), indices=np.concatenate(idx).astype(np.uint32), tri_material=np.concatenate(tmat),
+                    tri_emitter=np.concatenate(tem), normals=np.concatenate(nrm).astype(f32) if any_normals else None,
+                    texcoords=np.concatenate(uvl).astype(f32) if any_uvs else None)
+
+    def _assemble(self, meshes, **fields):  # the SceneDesc of the reader's tables, the flattened meshes and what the element readers returned
+        from .bindings import expand_blends  # (children of blended materials join the list, behind everything a shape refers to)
+        return SceneDesc(materials=expand_blends(self.materials), textures=self.textures, rtrans=np.stack(self.rt_slices).astype(f32) if self.rt_slices else None,
+                         **self._flatten(meshes), **fields)
+
+
+_BSDF_READERS = {  # plug-in → its reader (the reader object, the <bsdf> element, its simple properties, allow_twosided) → material dict
+    "diffuse": lambda rd, elem, p, allow_twosided: rd._textured(elem, dict(type=0), "reflectance", 0.5),
+    "null": lambda rd, elem, p, allow_twosided: dict(type=13),  # null.cpp:36-80: no parameters
+    "bumpmap": lambda rd, elem, p, allow_twosided: rd._normal_adapter(elem, allow_twosided, "bump", "bump map", strict_counts=False),
+    "normalmap": lambda rd, elem, p, allow_twosided: rd._normal_adapter(elem, allow_twosided, "normal_map", "normal map", strict_counts=True),
+    "roughdiffuse": _Reader._read_roughdiffuse, "difftrans": _Reader._read_difftrans, "phong": _Reader._read_phong,
+    "conductor": _Reader._read_conductor, "roughconductor": _Reader._read_conductor, "plastic": _Reader._read_plastic, "roughplastic": _Reader._read_roughplastic,
+    "dielectric": _Reader._read_dielectric, "thindielectric": _Reader._read_dielectric, "roughdielectric": _Reader._read_roughdielectric,
+    "twosided": _Reader._read_twosided, "mask": _Reader._read_mask, "coating": _Reader._read_coating, "roughcoating": _Reader._read_coating,
+    "blendbsdf": _Reader._read_blend, "mixturebsdf": _Reader._read_blend,
+}
+
+
+def load_scene(path, defines=None, strict=True, width=None, height=None, data_dir=None, mitsuba_src=None):
+    """Parse `path` → (SceneDesc, integrator properties for ppg_create, info dict).
+
+    defines: {"name": "value"} like `mitsuba -D name=value`; width/height override the film size; data_dir: the `data` directory of a Mitsuba tree
+    (default $PPG_MITSUBA_DATA), for data/microfacet/*.dat and data/ior/*.spd; mitsuba_src: the tree (default $PPG_MITSUBA_SRC, or data_dir's parent), for `sunsky`."""
+    root = ET.parse(path).getroot()
+    if root.tag != "scene":
+        raise SceneError("%s: root element is <%s>, expected <scene>" % (path, root.tag))
+    rd = _Reader(root, path, defines, strict, data_dir, mitsuba_src)
+    props, fields = rd._read_integrator(root)
+    sensor, info = rd._read_sensor(root, width, height)
+    rd._read_named_bsdfs(root)
+    lights = rd._read_emitters(root)
+    meshes, shapes = rd._read_shapes(root)
+    desc = rd._assemble(meshes, **sensor, **lights, **shapes)
+    if desc.delta_emitters and str(props.get("nee", "never")) != "always":
+        rd.warnings.append("point / spot / directional emitters are reached by next-event estimation only: with nee = %s they contribute nothing in "
+                           "every iteration that runs without it (as in Mitsuba)" % props.get("nee", "never"))
+    info.update(fields=fields, warnings=rd.warnings)
     return desc, props, info
 
 
