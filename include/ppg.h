@@ -599,6 +599,50 @@ int ppg_read_variance(ppg_ctx *ctx, float *rgb);
 int ppg_dump_sdtree(ppg_ctx *ctx, const char *path);
 
 /* ------------------------------------------------------------------------------------------------
+ * Loading a dumped SD-tree (HIP library only): train once, render many.  The file is what ppg_dump_sdtree, the dumpSDTree property, the
+ * reference's own dumpSDTree or the CPU oracle wrote; the context continues from it as if it had trained the tree itself — a final
+ * iteration from another camera or at a higher sample count, or further training iterations.
+ *
+ * When: after ppg_begin_render, with no iteration open (before ppg_begin_iteration, or after ppg_build_sdtree); otherwise PPG_ERR_STATE.
+ * With a shard set (ppg_set_shard, world > 1) the call is refused by name (PPG_ERR_INVALID, "not supported yet").
+ *
+ * Afterwards the context is in the state that ppg_build_sdtree + ppg_end_iteration of iteration opts->iter - 1 leave: S-tree, leaf
+ * headers, lookup grid, sampling D-trees, is_built, and m_iter / m_passesRendered as given.  Every call works from there unchanged:
+ * ppg_begin_iteration (refines the S-tree by the loaded weights, resets the building trees from the loaded sampling trees),
+ * ppg_render_passes, ppg_build_sdtree, ppg_dump_sdtree, the ppg_sdtree_read_* readers, ppg_query_pdf / ppg_query_sample.  Until that
+ * ppg_begin_iteration the building trees read as the sampling trees' topology with empty accumulators.
+ *
+ * The S-tree is not in the file: it is rebuilt from the leaf boxes.  From the context's tree box (ppg_sdtree_info.aabb_min / aabb_max) and
+ * axis 0, with the dump's own float arithmetic (size[axis] /= 2; child 1: p[axis] += size[axis]; next axis = (axis + 1) % 3), the next
+ * leaf of the file either IS the region (exact float equality), lies inside it (the region is split), or the region is a hole.  S-tree
+ * nodes are numbered in preorder; the numbering of the context that wrote the file cannot be recovered, and nothing depends on it.
+ *
+ * What the format loses:
+ *   - statistical weights are truncated to integers (they are integers under the nearest spatial filter, fractional under the others);
+ *   - `mean` stands in for the D-tree's sum: sum = mean * (4 pi * weight), up to 4 ulp from the sum that was dumped;
+ *   - there is no optimiser state: with bsdfSamplingFractionLoss != none the learned fraction restarts at 0.5 in every leaf;
+ *   - leaves of weight 0 are not in the file: each maximal region without a leaf becomes ONE leaf with an empty D-tree (one node, four zero
+ *     sums, weight 0), which samples uniformly as the leaves it replaces did.
+ * With the nearest filters and no loss a render continued from a file is therefore bit-identical to the uninterrupted one (film, variance,
+ * pass statistics, further dumps); with the other settings it is a valid, slightly different guiding distribution.
+ *
+ * Refusals — all decided on the host (csrc/ppg_sdt_load.h) before a byte is uploaded or a kernel launched; the context keeps the tree it
+ * had and stays usable; ppg_last_error names the leaf and the file offset.  PPG_ERR_INVALID: a file that cannot be read; a truncated file
+ * or trailing bytes that do not form a leaf; numNodes 0, above 65536 or beyond the bytes that remain; a child index >= numNodes, not above
+ * its parent's, or referenced twice; a node no node refers to; a sum that is negative or not finite; a mean or box that is not finite (or
+ * a size <= 0); a D-tree deeper than 20 levels; a leaf box that is not a region of this context's tree box ("the tree was trained on
+ * another scene"); leaves out of depth-first order or overlapping; opts->iter outside 0 .. 30, a negative passes_rendered.  PPG_ERR_NOMEM:
+ * 2^27 S-tree nodes or 2^32 sampling nodes; with the box spatial filter an S-tree deeper than PPG_STREE_MAX_DEPTH (ppg_testhooks.h).
+ * Not offered by the C++ driver, the .ppgs tools, the Mitsuba plug-in or the CPU oracle.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct ppg_sdtree_load {
+    int32_t iter;            /* m_iter of the state the file was dumped from (ppg_sdtree_info.iter of the dumping context) */
+    int32_t passes_rendered; /* m_passesRendered there: sample indices go on from passes_rendered * sppPerPass */
+    int32_t _reserved[2];    /* 0 */
+} ppg_sdtree_load;
+int ppg_load_sdtree(ppg_ctx *ctx, const char *path, const ppg_sdtree_load *opts /* NULL: zeros */);
+
+/* ------------------------------------------------------------------------------------------------
  * Feature buffers of the first hit (HIP library only): Mitsuba's `field` integrator (mitsuba/src/integrators/misc/field.cpp:122-175) —
  * what a denoiser wants beside the radiance: albedo, normals, position, depth — one image per requested field, filtered with the film's
  * reconstruction filter (ppg_set_rfilter) exactly as the radiance is.

@@ -38,10 +38,14 @@
 #include "ppg_host_kernels.h"
 #include "ppg_launch.h"
 #include "ppg_scene_build.h"
+#include "ppg_sdt_load.h"
 
 using namespace ppg_plan;
 static_assert(kSpatialFilterBox == SF_BOX && kNeeKickstart == NEE_KICKSTART && kBlock == PPG_BLOCK && kDenseChunk == PPG_DCHUNK && kAdamLeafShift == PPG_ADAM_LEAF_SHIFT,
               "ppg_batch_plan.h restates these values");
+static_assert(ppg_sdt::kOk == PPG_OK && ppg_sdt::kErrInvalid == PPG_ERR_INVALID && ppg_sdt::kErrNoMem == PPG_ERR_NOMEM && ppg_sdt::kSpatialFilterBox == SF_BOX &&
+                  ppg_sdt::kStreeMaxDepth == PPG_STREE_MAX_DEPTH && ppg_sdt::kPi == PPG_PI_F && sizeof(ppg_sdt::Node) == ppg_sdt::kNodeBytes,
+              "ppg_sdt_load.h restates these values");
 
 namespace {
 
@@ -622,23 +626,8 @@ int uploadTree(ppg_ctx *ctx, bool nodes) {
     return PPG_OK;
 }
 
-// The depth of an S-tree (children[2 i], children[2 i + 1]; 0, 0 = a leaf; a child's index is above its parent's: one forward pass) —
-// levels below the root of its deepest leaf — and whether the box spatial filter's splat can walk it (include/ppg_testhooks.h
-// PPG_STREE_MAX_DEPTH).  PPG_ERR_INVALID: a child index that is not above its parent's or beyond the array.
-int streeDepthCheck(const uint32_t *children, uint32_t n_nodes, int32_t spatial_filter, uint32_t *depth) {
-    std::vector<uint32_t> d(n_nodes, 0u);
-    uint32_t deepest = 0;
-    for (uint32_t i = 0; i < n_nodes; ++i) {
-        if (children[2 * (size_t)i] == 0) { deepest = std::max(deepest, d[i]); continue; }
-        for (int c = 0; c < 2; ++c) {
-            const uint32_t k = children[2 * (size_t)i + c];
-            if (k <= i || k >= n_nodes) return PPG_ERR_INVALID;
-            d[k] = d[i] + 1u;
-        }
-    }
-    *depth = deepest;
-    return (spatial_filter == SF_BOX && deepest > (uint32_t)PPG_STREE_MAX_DEPTH) ? PPG_ERR_NOMEM : PPG_OK;
-}
+// The depth of an S-tree and whether the box spatial filter's splat can walk it: ppg_sdt_load.h (the import of a dumped tree asks the same).
+using ppg_sdt::streeDepthCheck;
 
 // STree::refine (GP:957-998) + subdivide (GP:876-895) on the device (k_refine_count → scans → k_refine_fill, ppg_kernels.h);
 // the host mirror (node array, leaf headers) is then downloaded — it feeds the statistics log, the dumps and the readers.
@@ -2313,6 +2302,66 @@ int dumpSDTreeFile(ppg_ctx *ctx, const char *path) {  // GP:1191-1208 + STree::d
     return PPG_OK;
 }
 
+// ppg_load_sdtree (include/ppg.h "Loading a dumped SD-tree"): the file through ppg_sdt_load.h — every refusal is decided there, on the host,
+// before the context is touched —, then the state that buildSDTree + endIteration of iteration opts.iter - 1 leave.
+int loadSDTreeFile(ppg_ctx *ctx, const char *path, int iter, int passesRendered) {
+    std::vector<uint8_t> bytes;
+    {
+        FILE *f = fopen(path, "rb");
+        if (!f) { ctx->error = std::string("ppg_load_sdtree: cannot open ") + path; return PPG_ERR_INVALID; }
+        uint8_t buf[1 << 16];
+        size_t got;
+        while ((got = fread(buf, 1, sizeof buf, f)) > 0) bytes.insert(bytes.end(), buf, buf + got);
+        const bool bad = ferror(f) != 0;
+        fclose(f);
+        if (bad) { ctx->error = std::string("ppg_load_sdtree: cannot read ") + path; return PPG_ERR_INVALID; }
+    }
+    ppg_sdt::Tree T;
+    {
+        std::string why;
+        const int rc = ppg_sdt::importTree(bytes.data(), bytes.size(), ctx->treeMin, ctx->treeMax, ctx->spatialFilter, ppg_sdt::Limits(), T, why);
+        if (rc) { ctx->error = std::string("ppg_load_sdtree: ") + path + ": " + why; return rc; }
+    }
+    bytes.clear(); bytes.shrink_to_fit();
+    const size_t nS = T.axis.size(), nD = T.nodes.size();
+    std::vector<SNode> pool(nD);
+    std::vector<ushort4> bchild(nD);
+    for (size_t k = 0; k < nD; ++k) {
+        const ppg_sdt::Node &n = T.nodes[k];
+        for (int j = 0; j < 4; ++j) { pool[k].sum[j] = n.sum[j]; pool[k].child[j] = n.child[j]; }
+        pool[k].pad[0] = pool[k].pad[1] = 0;
+        bchild[k] = make_ushort4(n.child[0], n.child[1], n.child[2], n.child[3]);
+    }
+    ctx->joinTree();
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    // the sampling pool; the building trees have its topology and empty accumulators until the next ppg_begin_iteration resets them
+    HIP_CHECK(ctx->d_snodes[ctx->cur].reserve(nD));
+    HIP_CHECK(ctx->d_bchild.reserve(nD));
+    HIP_CHECK(ctx->d_bacc.reserve(nD * 4));
+    HIP_CHECK(ctx->d_dfs[0].reserve(T.dfsRightFirst.size()));
+    HIP_CHECK(hipMemcpyAsync(ctx->d_snodes[ctx->cur].p, pool.data(), nD * sizeof(SNode), hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(ctx->d_bchild.p, bchild.data(), nD * sizeof(ushort4), hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipMemsetAsync(ctx->d_bacc.p, 0, nD * 4 * 8, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(ctx->d_dfs[0].p, T.dfsRightFirst.data(), T.dfsRightFirst.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    ctx->dfsCur = 0; ctx->dfsCount = (unsigned int)T.dfsRightFirst.size();
+    ctx->snodes.assign(nS, HostSNode());
+    ctx->hdr.assign(nS, LeafHdr{});  // theta and the optimiser's state: a fresh leaf's (the file does not carry them)
+    for (size_t i = 0; i < nS; ++i) {
+        ctx->snodes[i].axis = T.axis[i]; ctx->snodes[i].child[0] = T.children[2 * i]; ctx->snodes[i].child[1] = T.children[2 * i + 1];
+        if (!ctx->snodes[i].isLeaf()) continue;
+        const ppg_sdt::Leaf &l = T.hdr[i];
+        LeafHdr &h = ctx->hdr[i];
+        h.s_base = l.base; h.s_num = l.num; h.s_sum = l.sum; h.s_statw = l.statw; h.s_depth = l.depth;
+        h.b_base = l.base; h.b_num = l.num; h.b_depth = l.depth;
+        h.b_statw = l.statw;  // as k_dtree_build leaves it: the next refine splits by it
+    }
+    ctx->nSamplingNodes = nD; ctx->nBuildingNodes = nD;
+    { int rc = uploadTree(ctx, true); if (rc) return rc; }  // S-tree, headers, leaf list, lookup grid; waits for the copies above
+    ctx->isBuilt = true; ctx->isFinalIter = false; ctx->iterOpen = false;
+    ctx->iter = iter; ctx->passesRendered = passesRendered; ctx->passesRenderedThisIter = 0;
+    return PPG_OK;
+}
+
 // Host tables to the device.  One call per table: into `buf`, grown to at least minCap elements; it gives the device pointer, or null for
 // an empty table that asked for no capacity (the optional ones).  After a failure the later calls do nothing: `e` keeps the first error.
 struct Upload {
@@ -3200,6 +3249,22 @@ int ppg_read_variance(ppg_ctx *ctx, float *rgb) {
     return PPG_OK;
 }
 int ppg_dump_sdtree(ppg_ctx *ctx, const char *path) { NEED_TREE return dumpSDTreeFile(ctx, path); }
+
+int ppg_load_sdtree(ppg_ctx *ctx, const char *path, const ppg_sdtree_load *opts) {
+    if (!ctx) return PPG_ERR_INVALID;
+    if (!ctx->treeAlive || !ctx->renderOpen) { ctx->error = "ppg_load_sdtree: render not begun (call it after ppg_begin_render)"; return PPG_ERR_STATE; }
+    if (ctx->iterOpen) { ctx->error = "ppg_load_sdtree: an iteration is open (call it before ppg_begin_iteration, or after ppg_build_sdtree)"; return PPG_ERR_STATE; }
+    if (ctx->shardWorld > 1) { ctx->error = "ppg_load_sdtree: a sharded render (ppg_set_shard with world > 1) is not supported yet"; return PPG_ERR_INVALID; }
+    if (!path) { ctx->error = "ppg_load_sdtree: no path"; return PPG_ERR_INVALID; }
+    ppg_sdtree_load o{};
+    if (opts) o = *opts;
+    if (o.iter < 0 || o.iter > 30 || o.passes_rendered < 0 || o._reserved[0] || o._reserved[1]) {
+        ctx->error = "ppg_load_sdtree: iter must be 0 .. 30, passes_rendered >= 0 and the reserved fields 0";
+        return PPG_ERR_INVALID;
+    }
+    NEED_TREE
+    return loadSDTreeFile(ctx, path, o.iter, o.passes_rendered);
+}
 
 int ppg_sdtree_info_get(ppg_ctx *ctx, ppg_sdtree_info *info) {
     NEED_TREE

@@ -5,15 +5,26 @@ subset (mitsuba_xml.py), render with the guided path tracer on the GPU, print th
 lines (GP:1176-1186, 1321-1326, 1376), write an EXR (render log attached like hdrfilm.cpp:525-533) or a PFM.
 `--fields a,b,c [--fields-spp N]`, or the `field` integrators of a `multichannel` scene, add the feature buffers of the first hit
 (Engine.render_fields) as layers name.R/G/B of the EXR.
+`--sdtree FILE [--sdtree-iter K] [--sdtree-passes P] [--guide-only]` starts from a dumped SD-tree (Engine.load_sdtree) instead of an untrained
+one: the usual schedule goes on at iteration K, or — `--guide-only` — the whole budget goes into one final iteration guided by the file.
 `--ppgs FILE` only converts the scene to the flat binary that the C++ driver `bin/ppg_render` reads.
 """
 import argparse
 import os
+import re
 import sys
 import time
 
 
-def main(argv=None):
+def sdtree_iter_from_name(path):
+    """The iteration a render goes on with after loading `path`, from the name the dumpSDTree property gives its files: "<dest>-%02d.sdt" is
+    written at the end of iteration NN, BEFORE m_iter is incremented (GP:1417-1422), so the context that wrote it went on with NN + 1.  None
+    for any other name."""
+    m = re.search(r"-(\d\d)\.sdt$", os.path.basename(path))
+    return int(m.group(1)) + 1 if m else None
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="python -m ppg_host", description=__doc__.split("\n\n")[0])
     ap.add_argument("scene", help="Mitsuba scene XML (guided_path integrator, supported subset)")
     ap.add_argument("-o", "--output", help="output image (.exr or .pfm); default: scene name + .exr")
@@ -27,9 +38,34 @@ def main(argv=None):
     ap.add_argument("--fields", metavar="a,b,c", help="feature buffers of the first hit, written as layers name.R/G/B of the EXR (Mitsuba's field "
                     "integrator): position, relPosition, distance, geoNormal, shNormal, uv, albedo, primIndex; added to those of a multichannel scene")
     ap.add_argument("--fields-spp", type=int, metavar="N", help="samples per pixel of the feature buffers (default: the scene's sppPerPass)")
+    ap.add_argument("--sdtree", metavar="FILE", help="start from this dumped SD-tree (.sdt) instead of an untrained one")
+    ap.add_argument("--sdtree-iter", type=int, metavar="K", help="the iteration the schedule goes on with: sdtree_info().iter of the context that dumped "
+                    "FILE; default for a name that ends -NN.sdt (the dumpSDTree property's): NN + 1; required for any other name")
+    ap.add_argument("--sdtree-passes", type=int, metavar="P", help="passes rendered before FILE was dumped (default 2^K - 1, the usual schedule): they "
+                    "count towards an spp budget, and sample indices go on behind them")
+    ap.add_argument("--guide-only", action="store_true", help="with --sdtree: no training, the whole budget goes into one final iteration")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("-q", "--quiet", action="store_true")
     a = ap.parse_args(argv)
+    if a.sdtree is None:
+        if a.guide_only or a.sdtree_iter is not None or a.sdtree_passes is not None:
+            ap.error("--guide-only, --sdtree-iter and --sdtree-passes need --sdtree")
+    else:
+        if a.sdtree_iter is None:
+            a.sdtree_iter = sdtree_iter_from_name(a.sdtree)
+        if a.sdtree_iter is None:
+            ap.error("--sdtree-iter is required: the name %r does not end in -NN.sdt" % os.path.basename(a.sdtree))
+        if not 0 <= a.sdtree_iter <= 30:
+            ap.error("--sdtree-iter must be 0 .. 30")
+        if a.sdtree_passes is not None and a.sdtree_passes < 0:
+            ap.error("--sdtree-passes must not be negative")
+        if a.ppgs:
+            ap.error("--sdtree: the .ppgs container carries scenes, not trees")
+    return ap, a
+
+
+def main(argv=None):
+    ap, a = parse_args(argv)
     from .bindings import FIELD_NAMES  # (no GPU is touched by the import)
     asked = [(n, (0.0, 0.0, 0.0)) for n in (a.fields.split(",") if a.fields else [])]
     for n, _ in asked:
@@ -97,7 +133,8 @@ def main(argv=None):
     out = a.output or os.path.splitext(a.scene)[0] + ".exr"
     if props.get("dumpSDTree") and not props.get("dumpPrefix"):
         props["dumpPrefix"] = os.path.splitext(out)[0]  # "<dest>-%02d.sdt", GP:1192-1195
-    gpt = GuidedPathTracer(log=log, device=a.device, **props)
+    gpt = GuidedPathTracer(log=log, device=a.device, sdtree=a.sdtree, sdtree_iter=a.sdtree_iter or 0, sdtree_passes=a.sdtree_passes,
+                           guide_only=a.guide_only, **props)
     t0 = time.monotonic()
     img = gpt.render(desc)
     dt = time.monotonic() - t0

@@ -607,6 +607,39 @@ class SDTreeInfo(C.Structure):
                 ("iter", C.c_int32), ("is_built", C.c_int32)]
 
 
+class SDTreeLoad(C.Structure):
+    """ppg_sdtree_load (include/ppg.h)"""
+    _fields_ = [("iter", C.c_int32), ("passes_rendered", C.c_int32), ("_reserved", C.c_int32 * 2)]
+
+
+def read_sdt(path):
+    """An .sdt dump (ppg_dump_sdtree / dumpSDTree, the reference's DTreeWrapper::dump, GP:699-711) as numpy arrays — no GPU, no library; for
+    inspection and tests.  Returns {"camera": float32 [4, 4], "leaves": [...]}, the leaves in file order (depth first, child 0 before child
+    1; leaves of statistical weight 0 are not in the file), each a dict: p, size (float32 [3]), mean (float32), weight (int), num_nodes,
+    node_sums (float32 [n, 4]) and node_children (uint16 [n, 4]).  Only the framing is checked here (ValueError for a truncated file): what
+    the engine refuses beyond that is Engine.load_sdtree's business."""
+    with open(path, "rb") as f:
+        data = f.read()
+    if len(data) < 64:
+        raise ValueError("%s: truncated: %d bytes, the camera matrix alone takes 64" % (path, len(data)))
+    node = np.dtype([("sum", "<f4"), ("child", "<u2")])
+    out = {"camera": np.frombuffer(data, "<f4", 16).reshape(4, 4).copy(), "leaves": []}
+    off = 64
+    while off < len(data):
+        if len(data) - off < 44:
+            raise ValueError("%s: leaf %d at offset %d: truncated: %d trailing bytes do not form a leaf" % (path, len(out["leaves"]), off, len(data) - off))
+        head = np.frombuffer(data, "<f4", 7, off)
+        weight, n = (int(v) for v in np.frombuffer(data, "<u8", 2, off + 28))
+        if n * 24 > len(data) - off - 44:
+            raise ValueError("%s: leaf %d at offset %d: truncated: numNodes %d needs more than the %d bytes that remain"
+                             % (path, len(out["leaves"]), off, n, len(data) - off - 44))
+        nodes = np.frombuffer(data, node, 4 * n, off + 44).reshape(n, 4)
+        out["leaves"].append({"offset": off, "p": head[0:3].copy(), "size": head[3:6].copy(), "mean": np.float32(head[6]), "weight": weight,
+                              "num_nodes": n, "node_sums": np.ascontiguousarray(nodes["sum"]), "node_children": np.ascontiguousarray(nodes["child"])})
+        off += 44 + 24 * n
+    return out
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char_p), ("ms", C.c_double), ("launches", C.c_uint64), ("units", C.c_uint64)]
 
@@ -1078,6 +1111,14 @@ class Engine:
 
     def dump_sdtree(self, path):
         self._call("dump_sdtree", path.encode())
+
+    def load_sdtree(self, path, iter=0, passes_rendered=0):
+        """ppg_load_sdtree (include/ppg.h "Loading a dumped SD-tree"): after begin_render(), with no iteration open.  iter and passes_rendered
+        are sdtree_info().iter and the passes_rendered_total of the context that dumped the file.  HIP library only."""
+        if self.prefix != "ppg_":
+            raise NotImplementedError("%s: loading a dumped SD-tree is not implemented here" % self.prefix)
+        opts = SDTreeLoad(int(iter), int(passes_rendered))
+        self._call("load_sdtree", os.fsencode(path), C.byref(opts))
 
     # -- SD-tree access ----------------------------------------------------------------------
     def sdtree_info(self):

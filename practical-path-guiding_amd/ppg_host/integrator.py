@@ -13,7 +13,19 @@ from .bindings import Engine
 
 
 class GuidedPathTracer:
-    def __init__(self, engine=None, reducer=None, log=None, **props):
+    def __init__(self, engine=None, reducer=None, log=None, sdtree=None, sdtree_iter=0, sdtree_passes=None, guide_only=False, **props):
+        """sdtree: an .sdt dump to start from (Engine.load_sdtree) instead of an untrained tree — sdtree_iter = the iteration the schedule goes
+        on with (sdtree_info().iter of the context that dumped it: one more than the NN of the property's "<dest>-NN.sdt"), sdtree_passes = the
+        passes rendered up to there (default: the 2^sdtree_iter - 1 of the usual schedule); they count towards an spp budget, and sample
+        indices go on behind them.  guide_only: the whole budget, spp or seconds, goes into ONE final iteration with the loaded tree."""
+        if guide_only and sdtree is None:
+            raise ValueError("guide_only needs an sdtree to guide with")
+        if sdtree is not None and reducer is not None:
+            raise NotImplementedError("sdtree: loading a dumped SD-tree into a sharded render is not supported yet")
+        if sdtree is not None and not 0 <= int(sdtree_iter) <= 30:
+            raise ValueError("sdtree_iter must be 0 .. 30")
+        self.sdtree, self.sdtree_iter, self.guide_only = sdtree, int(sdtree_iter), bool(guide_only)
+        self.sdtree_passes = int(sdtree_passes) if sdtree_passes is not None else (1 << self.sdtree_iter) - 1
         self.engine = engine if engine is not None else Engine.hip(**props)
         self.props = self.engine.props
         self.reducer = reducer
@@ -118,9 +130,31 @@ class GuidedPathTracer:
         spp = p["sppPerPass"]
         automatic = p["sampleCombination"] == "automatic"
         it, passes_rendered = 0, 0
+        if self.sdtree is not None:  # the state after iteration sdtree_iter - 1, from the file
+            it, passes_rendered = self.sdtree_iter, self.sdtree_passes
+            e.load_sdtree(self.sdtree, it, passes_rendered)
         current_var_at_end = float("inf")
         t_start = time.monotonic()
-        if p["budgetType"] == "spp":  # renderSPP, guided_path.cpp:1342-1426
+        if self.guide_only:  # one final iteration over the whole budget: nothing is recorded, the loaded tree guides every path
+            e.set_do_nee(self._do_nee(passes_rendered * spp))
+            self._final, self._recorded = True, False
+            e.begin_iteration(True)
+            if p["budgetType"] == "spp":
+                n = int(math.ceil(int(p["budget"]) / float(spp)))
+                rec = dict(iter=it, passes=n, stats=[self._passes(n).as_dict()])
+            else:
+                rec = dict(iter=it, passes=0, stats=[])
+                while True:
+                    rec["stats"].append(self._passes(1 << it).as_dict())
+                    rec["passes"] += 1 << it
+                    if time.monotonic() - t_start >= float(p["budget"]):
+                        break
+            rec["tree"] = self._build().as_dict()
+            e.end_iteration()
+            self.iterations.append(rec)
+            if self.log:
+                self.log(rec)
+        elif p["budgetType"] == "spp":  # renderSPP, guided_path.cpp:1342-1426
             n_passes = int(math.ceil(int(p["budget"]) / float(spp)))
             while passes_rendered < n_passes:
                 spp_rendered = passes_rendered * spp
