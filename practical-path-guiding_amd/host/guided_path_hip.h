@@ -26,61 +26,10 @@
 #include <string>
 #include <vector>
 
-#include "../../include/ppg.h"
+#include "integrator_props.h"
+#include "scene_data.h"
 
 namespace ppg {
-
-// Flat scene owned by the host (what ppg_set_scene copies from)
-struct SceneData {
-    std::vector<float> positions, normals;
-    std::vector<uint32_t> indices, triMaterial;
-    std::vector<int32_t> triEmitter;
-    std::vector<ppg_material> materials;
-    std::vector<ppg_emitter> emitters;
-    ppg_camera camera{};
-    bool hasEnvironment = false;  // constant environment emitter
-    float environment[3] = {0, 0, 0};
-    std::vector<float> rtrans;    // rough-transmittance slices of the roughplastic materials, rtransSamples + 1 floats each
-    uint32_t rtransSamples = 0;
-    std::vector<ppg_sphere> spheres;  // analytic spheres
-    bool hasEnvmap = false;           // image-based environment emitter: envmap (pixels in envmapRgb)
-    mutable ppg_envmap envmap{};
-    std::vector<float> envmapRgb;
-    std::vector<float> texcoords;                  // per-vertex texture coordinates (NaN rows: none) or empty
-    mutable std::vector<ppg_texture> textures;     // bitmap textures; their pixels in texturePixels
-    std::vector<std::vector<float>> texturePixels;
-    bool hasRFilter = false;                       // the film's reconstruction filter (ppg_set_rfilter) when it is not the default box
-    ppg_rfilter rfilter{};
-    bool hasLens = false;                          // thin-lens camera (ppg_set_lens); false = pinhole
-    ppg_lens lens{};
-    std::vector<ppg_delta_emitter> deltaEmitters;  // point / spot / directional emitters (ppg_set_delta_emitters, before ppg_set_scene)
-    std::vector<ppg_shape> shapes;  // analytic disks and cylinders (ppg_set_shapes, before ppg_set_scene)
-    std::vector<ppg_microfacet> microfacet;  // the general microfacet entries (alphaU / alphaV, phong, sampleVisible = false): empty, or one
-                                             // per material (ppg_set_microfacet, before ppg_set_scene)
-    std::vector<ppg_coating> coatings;  // the coating / roughcoating adapters: empty, or one per material (ppg_set_coatings, before ppg_set_scene)
-    std::vector<ppg_blend> blends;      // the blendbsdf / mixturebsdf combinators: empty, or one per material (ppg_set_blends, before ppg_set_scene)
-    std::vector<ppg_material_textures> materialTextures;  // bitmaps on specular / alpha / opacity: empty, or one entry per material
-                                                          // (ppg_set_material_textures, before ppg_set_scene)
-
-    ppg_scene view() const {
-        ppg_scene s{};
-        s.n_vertices = (uint32_t)(positions.size() / 3); s.positions = positions.data();
-        s.normals = normals.empty() ? nullptr : normals.data();
-        s.n_triangles = (uint32_t)(indices.size() / 3); s.indices = indices.data();
-        s.tri_material = triMaterial.data(); s.tri_emitter = triEmitter.data();
-        s.n_materials = (uint32_t)materials.size(); s.materials = materials.data();
-        s.n_emitters = (uint32_t)emitters.size(); s.emitters = emitters.data();
-        s.camera = camera;
-        s.environment = hasEnvironment ? environment : nullptr;
-        if (hasEnvmap) { envmap.rgb = envmapRgb.data(); s.envmap = &envmap; }
-        if (!spheres.empty()) { s.n_spheres = (uint32_t)spheres.size(); s.spheres = spheres.data(); }
-        if (rtransSamples && !rtrans.empty()) { s.n_rtrans = (uint32_t)(rtrans.size() / (rtransSamples + 1)); s.rtrans_samples = rtransSamples; s.rtrans = rtrans.data(); }
-        s.texcoords = texcoords.empty() ? nullptr : texcoords.data();
-        for (size_t i = 0; i < textures.size(); ++i) textures[i].rgb = texturePixels[i].data();
-        if (!textures.empty()) { s.n_textures = (uint32_t)textures.size(); s.textures = textures.data(); }
-        return s;
-    }
-};
 
 // Properties: string map with the typed getters of mitsuba/core/properties.h as far as this plugin uses them
 class Properties {
@@ -126,26 +75,9 @@ public:
 
     explicit GuidedPathTracerHIP(const Properties &props) {  // GP:1014-1085 + MonteCarloIntegrator (integrator.cpp:190-225)
         ppg_config_default(&m_cfg);
-        m_str[0] = props.getString("nee", "never"); m_cfg.nee = m_str[0].c_str();
-        m_str[1] = props.getString("sampleCombination", "automatic"); m_cfg.sampleCombination = m_str[1].c_str();
-        m_str[2] = props.getString("spatialFilter", "nearest"); m_cfg.spatialFilter = m_str[2].c_str();
-        m_str[3] = props.getString("directionalFilter", "nearest"); m_cfg.directionalFilter = m_str[3].c_str();
-        m_str[4] = props.getString("bsdfSamplingFractionLoss", "none"); m_cfg.bsdfSamplingFractionLoss = m_str[4].c_str();
-        m_str[5] = props.getString("budgetType", "seconds"); m_cfg.budgetType = m_str[5].c_str();
-        m_str[6] = props.getString("dumpPrefix", ""); m_cfg.dumpPrefix = m_str[6].empty() ? nullptr : m_str[6].c_str();
-        m_cfg.sdTreeMaxMemory = props.getInteger("sdTreeMaxMemory", -1);
-        m_cfg.sTreeThreshold = props.getInteger("sTreeThreshold", 12000);
-        m_cfg.dTreeThreshold = props.getFloat("dTreeThreshold", 0.01f);
-        m_cfg.bsdfSamplingFraction = props.getFloat("bsdfSamplingFraction", 0.5f);
-        m_cfg.sppPerPass = props.getInteger("sppPerPass", 4);
-        m_cfg.budget = props.getFloat("budget", 300.0f);
-        m_cfg.dumpSDTree = props.getBoolean("dumpSDTree", false);
-        m_cfg.rrDepth = props.getInteger("rrDepth", 5);
-        m_cfg.maxDepth = props.getInteger("maxDepth", -1);
-        m_cfg.strictNormals = props.getBoolean("strictNormals", false);
-        m_cfg.hideEmitters = props.getBoolean("hideEmitters", false);
+        readIntegratorProperties(props, m_cfg, m_str);
+        m_dump = props.getString("dumpPrefix", ""); m_cfg.dumpPrefix = m_dump.empty() ? nullptr : m_dump.c_str();
         m_cfg.seed = (uint64_t)std::stoull(props.getString("seed", "0"));
-        m_cfg.device = props.getInteger("device", 0);
         if (ppg_create(&m_cfg, &m_ctx) != PPG_OK) throw std::runtime_error(std::string("ppg_create: ") + ppg_last_error(nullptr));
         // not a property of the reference: rounds by image region in the early iterations (include/ppg.h ppg_set_adam_regions), 0 = off
         const int regions = props.getInteger("adamRegions", 0);
@@ -169,16 +101,8 @@ public:
         // (the footprint hook of a filtered film comes before the filter and the shard meet: the library refuses the combination without it)
         if (reducer) check(ppg_set_footprint_hook(m_ctx, &GuidedPathTracerHIP::footprintHook, this), "ppg_set_footprint_hook");
         const bool spp = std::string(m_cfg.budgetType) == "spp";
-        ppg_scene sv = scene.view();
-        check(ppg_set_delta_emitters(m_ctx, scene.deltaEmitters.data(), (uint32_t)scene.deltaEmitters.size()), "ppg_set_delta_emitters");
-        check(ppg_set_material_textures(m_ctx, scene.materialTextures.data(), (uint32_t)scene.materialTextures.size()), "ppg_set_material_textures");
-        check(ppg_set_shapes(m_ctx, scene.shapes.data(), (uint32_t)scene.shapes.size()), "ppg_set_shapes");
-        check(ppg_set_microfacet(m_ctx, scene.microfacet.data(), (uint32_t)scene.microfacet.size()), "ppg_set_microfacet");
-        check(ppg_set_coatings(m_ctx, scene.coatings.data(), (uint32_t)scene.coatings.size()), "ppg_set_coatings");
-        check(ppg_set_blends(m_ctx, scene.blends.data(), (uint32_t)scene.blends.size()), "ppg_set_blends");
-        check(ppg_set_scene(m_ctx, &sv), "ppg_set_scene");
-        check(ppg_set_rfilter(m_ctx, scene.hasRFilter ? &scene.rfilter : nullptr), "ppg_set_rfilter");
-        check(ppg_set_lens(m_ctx, scene.hasLens ? &scene.lens : nullptr), "ppg_set_lens");
+        const SceneData::Applied applied = scene.apply(m_ctx);
+        check(applied.rc, applied.call);
         if (reducer) check(ppg_set_shard(m_ctx, reducer->rank(), reducer->world(), 32), "ppg_set_shard");
         m_w = scene.camera.width; m_h = scene.camera.height;
         {
@@ -384,7 +308,7 @@ private:
     std::exception_ptr m_hookError;
     ppg_config m_cfg;
     ppg_ctx *m_ctx = nullptr;
-    std::string m_str[7];
+    std::string m_str[6], m_dump;
     int m_w = 0, m_h = 0, m_passesRendered = 0;
 };
 

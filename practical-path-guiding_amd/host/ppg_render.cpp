@@ -8,8 +8,8 @@
  * A Mitsuba scene XML is converted first: `python -m ppg_host scene.xml --ppgs scene.ppgs` (also writes scene.ppgs.props,
  * the XML's integrator properties, which are picked up here).
  *
- * scene.ppgs is the flat binary scene written by ppg_host.scenes.save_scene() (header "PPGS", then the arrays of
- * include/ppg.h's ppg_scene).  --cbox builds scenes/cbox/cbox.xml procedurally like ppg_host.scenes.cbox_scene.
+ * scene.ppgs is the flat binary scene written by ppg_host.scenes.save_scene() and by --ppgs (the format: host/scene_file.h).
+ * --cbox builds scenes/cbox/cbox.xml procedurally like ppg_host.scenes.cbox_scene.
  * -D sets integrator properties (reference names: budget, budgetType, sppPerPass, sTreeThreshold, ...).
  * Output: PFM (little endian RGB float), the log lines of the reference on stdout.
  */
@@ -22,131 +22,10 @@
 #include "guided_path_hip.h"
 #include "plugin_core.h"
 #include "rccl_reducer.h"
+#include "scene_file.h"
 #include "scene_xml.h"
 
 using namespace ppg;
-
-static bool loadSceneChecked(const char *path, SceneData &s);
-// a corrupt or truncated file is "cannot load scene", never an allocation of whatever size its header claims
-static bool loadScene(const char *path, SceneData &s) {
-    try { return loadSceneChecked(path, s); } catch (const std::exception &) { return false; }
-}
-static bool loadSceneChecked(const char *path, SceneData &s) {
-    std::ifstream f(path, std::ios::binary);
-    f.seekg(0, std::ios::end);
-    const uint64_t fileSize = f ? (uint64_t)f.tellg() : 0;
-    f.seekg(0);
-    // every count read from the file is checked against what is left of it before anything is sized by it
-    auto fits = [&](uint64_t bytes) { const std::streamoff p = f.tellg(); return p >= 0 && bytes <= fileSize - (uint64_t)p; };
-    char magic[4];
-    uint32_t hdr[6];
-    if (!f.read(magic, 4) || memcmp(magic, "PPGS", 4) != 0 || !f.read((char *)hdr, sizeof hdr)) return false;
-    const uint32_t nv = hdr[0], nt = hdr[1], nm = hdr[2], ne = hdr[3], hasN = hdr[4];
-    if (!fits((uint64_t)nv * 12 * (hasN ? 2 : 1) + (uint64_t)nt * 20 + (uint64_t)nm * sizeof(ppg_material) + (uint64_t)ne * sizeof(ppg_emitter) + sizeof(ppg_camera))) return false;
-    s.positions.resize(3 * (size_t)nv); f.read((char *)s.positions.data(), s.positions.size() * 4);
-    if (hasN) { s.normals.resize(3 * (size_t)nv); f.read((char *)s.normals.data(), s.normals.size() * 4); }
-    s.indices.resize(3 * (size_t)nt); f.read((char *)s.indices.data(), s.indices.size() * 4);
-    s.triMaterial.resize(nt); f.read((char *)s.triMaterial.data(), (size_t)nt * 4);
-    s.triEmitter.resize(nt); f.read((char *)s.triEmitter.data(), (size_t)nt * 4);
-    s.materials.resize(nm); f.read((char *)s.materials.data(), (size_t)nm * sizeof(ppg_material));
-    s.emitters.resize(ne); f.read((char *)s.emitters.data(), (size_t)ne * sizeof(ppg_emitter));
-    f.read((char *)&s.camera, sizeof(ppg_camera));
-    s.hasEnvironment = (hdr[5] & 1) != 0;  // hdr[5]: optional blocks, bit 0 environment, bit 1 rtrans, bit 2 spheres, bit 3 envmap
-    if (s.hasEnvironment) f.read((char *)s.environment, 12);
-    if (hdr[5] & 2) {
-        uint32_t rt[2];
-        f.read((char *)rt, 8);
-        if (!f || rt[1] < 2 || !fits((uint64_t)rt[0] * ((uint64_t)rt[1] + 1) * 4)) return false;
-        s.rtransSamples = rt[1];
-        s.rtrans.resize((size_t)rt[0] * (rt[1] + 1)); f.read((char *)s.rtrans.data(), s.rtrans.size() * 4);
-    }
-    if (hdr[5] & 4) {
-        uint32_t n = 0;
-        f.read((char *)&n, 4);
-        if (!f || !fits((uint64_t)n * sizeof(ppg_sphere))) return false;
-        s.spheres.resize(n); f.read((char *)s.spheres.data(), (size_t)n * sizeof(ppg_sphere));
-    }
-    if (hdr[5] & 8) {
-        uint32_t wh[2];
-        f.read((char *)wh, 8); f.read((char *)&s.envmap.scale, 4); f.read((char *)s.envmap.to_world, 36);
-        if (!f || wh[0] == 0 || wh[1] == 0 || wh[0] > 0x7fffu || wh[1] > 0x7fffu || !fits((uint64_t)wh[0] * wh[1] * 12)) return false;
-        s.envmap.width = wh[0]; s.envmap.height = wh[1]; s.hasEnvmap = true;
-        s.envmapRgb.resize((size_t)wh[0] * wh[1] * 3); f.read((char *)s.envmapRgb.data(), s.envmapRgb.size() * 4);
-    }
-    if ((hdr[5] & 16) && !fits((uint64_t)nv * 8)) return false;
-    if (hdr[5] & 16) { s.texcoords.resize(2 * (size_t)nv); f.read((char *)s.texcoords.data(), s.texcoords.size() * 4); }  // bit 4: texture coordinates
-    if (hdr[5] & 32) {  // bit 5: bitmap textures (pixels as float32 RGB, or as the 8-bit sRGB source decoded through the conversion's 256-entry table)
-        uint32_t n = 0;
-        f.read((char *)&n, 4);
-        if (!f) return false;
-        float srgb[256];
-        for (int i = 0; i < 256; ++i) { const double v = i / 255.0; srgb[i] = (float)(v <= 0.04045 ? v / 12.92 : std::pow((v + 0.055) / 1.055, 2.4)); }
-        for (uint32_t k = 0; k < n; ++k) {
-            uint32_t wh[2], storage = 0; float sc[4]; int32_t wr[3];
-            f.read((char *)wh, 8); f.read((char *)sc, 16); f.read((char *)wr, 12); f.read((char *)&storage, 4);
-            // (ppg_set_scene accepts textures below 32768 x 32768)
-            if (!f || wh[0] == 0 || wh[1] == 0 || wh[0] > 0x7fffu || wh[1] > 0x7fffu || !fits((uint64_t)wh[0] * wh[1] * 3 * (storage == 1 ? 1 : 4))) return false;
-            ppg_texture t{};
-            t.width = wh[0]; t.height = wh[1]; t.uv_scale[0] = sc[0]; t.uv_scale[1] = sc[1]; t.uv_offset[0] = sc[2]; t.uv_offset[1] = sc[3];
-            t.wrap_u = wr[0]; t.wrap_v = wr[1]; t.nearest = wr[2];
-            std::vector<float> px((size_t)wh[0] * wh[1] * 3);
-            if (storage == 1) {
-                std::vector<unsigned char> raw(px.size());
-                f.read((char *)raw.data(), raw.size());
-                for (size_t i = 0; i < px.size(); ++i) px[i] = srgb[raw[i]];
-            } else f.read((char *)px.data(), px.size() * 4);
-            s.textures.push_back(t); s.texturePixels.push_back(std::move(px));
-        }
-    }
-    if (hdr[5] & 64) {  // bit 6: the film's reconstruction filter (ppg_rfilter), only when it is not the default box
-        if (!fits(sizeof(ppg_rfilter))) return false;
-        f.read((char *)&s.rfilter, sizeof(ppg_rfilter));
-        s.hasRFilter = true;
-    }
-    if (hdr[5] & 128) {  // bit 7: the thin lens (ppg_lens), only for a thin-lens camera
-        if (!fits(sizeof(ppg_lens))) return false;
-        f.read((char *)&s.lens, sizeof(ppg_lens));
-        s.hasLens = true;
-    }
-    if (hdr[5] & 256) {  // bit 8: point / spot / directional emitters (uint32 n, n x ppg_delta_emitter), only when there are any
-        uint32_t n = 0;
-        if (!fits(4)) return false;
-        f.read((char *)&n, 4);
-        if (!fits((uint64_t)n * sizeof(ppg_delta_emitter))) return false;
-        s.deltaEmitters.resize(n);
-        f.read((char *)s.deltaEmitters.data(), (std::streamsize)(n * sizeof(ppg_delta_emitter)));
-    }
-    if (hdr[5] & 512) {  // bit 9: bitmaps on specular / alpha / opacity (n_materials x ppg_material_textures), only when a material has one
-        if (!fits((uint64_t)nm * sizeof(ppg_material_textures))) return false;
-        s.materialTextures.resize(nm);
-        f.read((char *)s.materialTextures.data(), (std::streamsize)((size_t)nm * sizeof(ppg_material_textures)));
-    }
-    if (hdr[5] & 1024) {  // bit 10: analytic disks and cylinders (uint32 n, n x ppg_shape), only when there are any
-        uint32_t n = 0;
-        if (!fits(4)) return false;
-        f.read((char *)&n, 4);
-        if (!fits((uint64_t)n * sizeof(ppg_shape))) return false;
-        s.shapes.resize(n);
-        f.read((char *)s.shapes.data(), (std::streamsize)(n * sizeof(ppg_shape)));
-    }
-    if (hdr[5] & 2048) {  // bit 11: the general microfacet entries (n_materials x ppg_microfacet), only when a material has one
-        if (!fits((uint64_t)nm * sizeof(ppg_microfacet))) return false;
-        s.microfacet.resize(nm);
-        f.read((char *)s.microfacet.data(), (std::streamsize)((size_t)nm * sizeof(ppg_microfacet)));
-    }
-    if (hdr[5] & 4096) {  // bit 12: the coatings (n_materials x ppg_coating), only when a material is coated
-        if (!fits((uint64_t)nm * sizeof(ppg_coating))) return false;
-        s.coatings.resize(nm);
-        f.read((char *)s.coatings.data(), (std::streamsize)((size_t)nm * sizeof(ppg_coating)));
-    }
-    if (hdr[5] & 8192) {  // bit 13: the blends (n_materials x ppg_blend), only when a material is blended
-        if (!fits((uint64_t)nm * sizeof(ppg_blend))) return false;
-        s.blends.resize(nm);
-        f.read((char *)s.blends.data(), (std::streamsize)((size_t)nm * sizeof(ppg_blend)));
-    }
-    if (hdr[5] >> 14) return false;  // a block this reader does not know
-    return (bool)f;
-}
 
 struct M4 { double m[16]; };  // row major
 
@@ -207,69 +86,6 @@ static void writePFM(const char *path, const std::vector<float> &rgb, int w, int
     std::ofstream f(path, std::ios::binary);
     f << "PF\n" << w << " " << h << "\n-1.0\n";
     for (int y = h - 1; y >= 0; --y) f.write((const char *)&rgb[(size_t)y * w * 3], (size_t)w * 12);  // PFM is bottom-up
-}
-
-// the flat scene file of ppg_host.save_scene (for tests and for handing a loaded XML scene to other tools)
-static bool saveScene(const char *path, const SceneData &s) {
-    std::ofstream f(path, std::ios::binary);
-    const uint32_t hdr[6] = {(uint32_t)(s.positions.size() / 3), (uint32_t)(s.indices.size() / 3), (uint32_t)s.materials.size(), (uint32_t)s.emitters.size(),
-                             s.normals.empty() ? 0u : 1u, (s.hasEnvironment ? 1u : 0u) | (s.rtrans.empty() ? 0u : 2u) | (s.spheres.empty() ? 0u : 4u) | (s.hasEnvmap ? 8u : 0u) |
-                                 (s.texcoords.empty() ? 0u : 16u) | (s.textures.empty() ? 0u : 32u) | (s.hasRFilter ? 64u : 0u) | (s.hasLens ? 128u : 0u) |
-                                 (s.deltaEmitters.empty() ? 0u : 256u) | (s.materialTextures.empty() ? 0u : 512u) | (s.shapes.empty() ? 0u : 1024u) |
-                                 (s.microfacet.empty() ? 0u : 2048u) | (s.coatings.empty() ? 0u : 4096u) | (s.blends.empty() ? 0u : 8192u)};
-    f.write("PPGS", 4); f.write((const char *)hdr, sizeof hdr);
-    f.write((const char *)s.positions.data(), s.positions.size() * 4);
-    if (!s.normals.empty()) f.write((const char *)s.normals.data(), s.normals.size() * 4);
-    f.write((const char *)s.indices.data(), s.indices.size() * 4);
-    f.write((const char *)s.triMaterial.data(), s.triMaterial.size() * 4);
-    f.write((const char *)s.triEmitter.data(), s.triEmitter.size() * 4);
-    f.write((const char *)s.materials.data(), s.materials.size() * sizeof(ppg_material));
-    f.write((const char *)s.emitters.data(), s.emitters.size() * sizeof(ppg_emitter));
-    f.write((const char *)&s.camera, sizeof(ppg_camera));
-    if (s.hasEnvironment) f.write((const char *)s.environment, 12);
-    if (!s.rtrans.empty()) {
-        const uint32_t rt[2] = {(uint32_t)(s.rtrans.size() / (s.rtransSamples + 1)), s.rtransSamples};
-        f.write((const char *)rt, 8); f.write((const char *)s.rtrans.data(), s.rtrans.size() * 4);
-    }
-    if (!s.spheres.empty()) {
-        const uint32_t n = (uint32_t)s.spheres.size();
-        f.write((const char *)&n, 4); f.write((const char *)s.spheres.data(), (size_t)n * sizeof(ppg_sphere));
-    }
-    if (s.hasEnvmap) {
-        const uint32_t wh[2] = {s.envmap.width, s.envmap.height};
-        f.write((const char *)wh, 8); f.write((const char *)&s.envmap.scale, 4); f.write((const char *)s.envmap.to_world, 36);
-        f.write((const char *)s.envmapRgb.data(), s.envmapRgb.size() * 4);
-    }
-    if (!s.texcoords.empty()) f.write((const char *)s.texcoords.data(), s.texcoords.size() * 4);
-    if (!s.textures.empty()) {
-        const uint32_t n = (uint32_t)s.textures.size();
-        f.write((const char *)&n, 4);
-        for (uint32_t k = 0; k < n; ++k) {
-            const ppg_texture &t = s.textures[k];
-            const uint32_t wh[2] = {t.width, t.height}, storage = 0;
-            const float sc[4] = {t.uv_scale[0], t.uv_scale[1], t.uv_offset[0], t.uv_offset[1]};
-            const int32_t wr[3] = {t.wrap_u, t.wrap_v, t.nearest};
-            f.write((const char *)wh, 8); f.write((const char *)sc, 16); f.write((const char *)wr, 12); f.write((const char *)&storage, 4);
-            f.write((const char *)s.texturePixels[k].data(), s.texturePixels[k].size() * 4);
-        }
-    }
-    if (s.hasRFilter) f.write((const char *)&s.rfilter, sizeof(ppg_rfilter));
-    if (s.hasLens) f.write((const char *)&s.lens, sizeof(ppg_lens));
-    if (!s.deltaEmitters.empty()) {
-        const uint32_t n = (uint32_t)s.deltaEmitters.size();
-        f.write((const char *)&n, 4);
-        f.write((const char *)s.deltaEmitters.data(), (std::streamsize)(n * sizeof(ppg_delta_emitter)));
-    }
-    if (!s.materialTextures.empty()) f.write((const char *)s.materialTextures.data(), (std::streamsize)(s.materialTextures.size() * sizeof(ppg_material_textures)));
-    if (!s.shapes.empty()) {
-        const uint32_t n = (uint32_t)s.shapes.size();
-        f.write((const char *)&n, 4);
-        f.write((const char *)s.shapes.data(), (std::streamsize)(n * sizeof(ppg_shape)));
-    }
-    if (!s.microfacet.empty()) f.write((const char *)s.microfacet.data(), (std::streamsize)(s.microfacet.size() * sizeof(ppg_microfacet)));
-    if (!s.coatings.empty()) f.write((const char *)s.coatings.data(), (std::streamsize)(s.coatings.size() * sizeof(ppg_coating)));
-    if (!s.blends.empty()) f.write((const char *)s.blends.data(), (std::streamsize)(s.blends.size() * sizeof(ppg_blend)));
-    return (bool)f;
 }
 
 int main(int argc, char **argv) {
@@ -363,14 +179,6 @@ int main(int argc, char **argv) {
     if (pluginCore) {
         PluginCore core;
         core.configure(props);
-        core.setRFilter(scene.hasRFilter ? &scene.rfilter : nullptr);
-        core.setLens(scene.hasLens ? &scene.lens : nullptr);
-        core.setDeltaEmitters(scene.deltaEmitters.data(), scene.deltaEmitters.size());
-        core.setMaterialTextures(scene.materialTextures.data(), scene.materialTextures.size());
-        core.setShapes(scene.shapes.data(), scene.shapes.size());
-        core.setMicrofacet(scene.microfacet.data(), scene.microfacet.size());
-        core.setCoatings(scene.coatings.data(), scene.coatings.size());
-        core.setBlends(scene.blends.data(), scene.blends.size());
         core.setSeed((uint64_t)std::stoull(props.getString("seed", "0")));
         std::string dest = out;
         const size_t dot = dest.find_last_of('.');
@@ -379,8 +187,7 @@ int main(int argc, char **argv) {
         if (cancelAfterMs == 0) core.cancel();
         else if (cancelAfterMs > 0) canceller = std::thread([&] { std::this_thread::sleep_for(std::chrono::milliseconds(cancelAfterMs)); core.cancel(); });
         std::string err;
-        const ppg_scene sv = scene.view();
-        const int rc = core.render(sv, dest, err);
+        const int rc = core.render(scene, dest, err);
         if (canceller.joinable()) canceller.join();
         if (rc != PPG_OK && rc != PPG_ERR_CANCELLED) { std::cerr << "error: " << err << std::endl; return 3; }
         if (rc == PPG_ERR_CANCELLED && !quiet) std::cout << "(cancelled)" << std::endl;

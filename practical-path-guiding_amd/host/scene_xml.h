@@ -1037,11 +1037,9 @@ public:
         }
         {   // the children of blended materials join the list here, in the blended materials' order (as bindings.expand_blends does)
             const size_t n0 = S.materials.size();
-            std::vector<ppg_blend> blends(n0);
-            bool any = false;
+            S.blends.assign(n0, ppg_blend{});
             for (size_t i = 0; i < n0; ++i) {
                 if (!m_blendOf[i].b.kind) continue;
-                any = true;
                 ppg_blend b = m_blendOf[i].b;
                 for (size_t k = 0; k < m_blendOf[i].kids.size(); ++k) {
                     b.child[k] = (uint32_t)S.materials.size();
@@ -1049,12 +1047,11 @@ public:
                     m_mfdOf.push_back(m_blendOf[i].kidMfd[k]);
                     m_coatOf.push_back(ppg_coating{});
                 }
-                blends[i] = b;
+                S.blends[i] = b;
             }
-            if (any) { blends.resize(S.materials.size()); S.blends = blends; }
         }
-        for (const ppg_microfacet &g : m_mfdOf) if (g.general) { S.microfacet = m_mfdOf; break; }  // one entry per material, or none
-        for (const ppg_coating &c : m_coatOf) if (c.kind) { S.coatings = m_coatOf; break; }  // likewise
+        S.microfacet = m_mfdOf; S.coatings = m_coatOf;
+        S.trimSideLists();  // one entry per material, or none
         out.warnings.insert(out.warnings.end(), m_lenientNotes.begin(), m_lenientNotes.end());
         return out;
     }

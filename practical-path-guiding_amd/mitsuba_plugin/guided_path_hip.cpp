@@ -47,7 +47,7 @@
 #include <vector>
 
 #include "ppg.h"
-#include "guided_path_hip.h"   /* ppg::SceneData (host side of the C-ABI) */
+#include "scene_data.h"        /* ppg::SceneData (host side of the C-ABI) */
 #include "plugin_core.h"       /* ppg::PluginCore: property mapping + create / scene / render / cancel, shared with the stand-alone driver */
 #include "scene_xml.h"         /* ppg::xml: the <bsdf> parser of the stand-alone driver */
 
@@ -75,35 +75,11 @@ public:
             Log(EError, "guided_path_hip: %s", why.c_str());
             return false;                 /* (EError normally throws; if it is configured not to, stop here) */
         }
-        const ppg_scene desc = data.view();
-        m_core.setLens(data.hasLens ? &data.lens : nullptr);
-        m_core.setDeltaEmitters(data.deltaEmitters.data(), data.deltaEmitters.size());
-        m_core.setShapes(data.shapes.data(), data.shapes.size());
-        {   /* the general microfacet entries materialOf() collected: one per material, or none */
-            bool any = false;
-            for (size_t k = 0; k < data.microfacet.size(); ++k) any = any || data.microfacet[k].general != 0;
-            if (any) data.microfacet.resize(data.materials.size());
-            else data.microfacet.clear();
-            m_core.setMicrofacet(data.microfacet.data(), data.microfacet.size());
-        }
-        {   /* the coating / roughcoating adapters materialOf() collected, likewise */
-            bool any = false;
-            for (size_t k = 0; k < data.coatings.size(); ++k) any = any || data.coatings[k].kind != 0;
-            if (any) data.coatings.resize(data.materials.size());
-            else data.coatings.clear();
-            m_core.setCoatings(data.coatings.data(), data.coatings.size());
-        }
-        {   /* the blendbsdf / mixturebsdf combinators materialOf() collected, likewise */
-            bool any = false;
-            for (size_t k = 0; k < data.blends.size(); ++k) any = any || data.blends[k].kind != 0;
-            if (any) data.blends.resize(data.materials.size());
-            else data.blends.clear();
-            m_core.setBlends(data.blends.data(), data.blends.size());
-        }
+        data.trimSideLists();   /* what materialOf() collected material by material: one entry per material, or none */
         Log(EInfo, "Starting render job (%ix%i, MI355X, %i triangles, %i analytic spheres) ..", film->getCropSize().x, film->getCropSize().y,
             (int) (data.indices.size() / 3), (int) data.spheres.size());
         /* create → scene → render; SD-tree dumps to "<dest>-NN.sdt" (GP:1192-1195) */
-        const int rc = m_core.render(desc, scene->getDestinationFile().string(), why);
+        const int rc = m_core.render(data, scene->getDestinationFile().string(), why);
         if (rc != PPG_OK && rc != PPG_ERR_CANCELLED) {
             Log(EError, "guided_path_hip: %s", why.c_str());   /* unknown enum strings: where GP:1023.. Assert(false) */
             return false;

@@ -771,76 +771,62 @@ class Engine:
         s.camera.near_clip, s.camera.far_clip = cam["near_clip"], cam["far_clip"]
         s.camera.width, s.camera.height = cam["width"], cam["height"]
         self._scene_keep = (pos, idx, tm, te, nrm, mats, ems, rt, sph_arr, envmap, uvs, tex_arr, tex_keep)
-        # the point / spot / directional emitters go first: ppg_set_scene consumes the context's list.  (A context that never had any is
-        # left alone; after a scene with such lights an empty list clears them.)
-        delta = getattr(desc, "delta_emitters", None) or []
-        if self.prefix == "ppg_":
-            if delta or getattr(self, "_delta", None):
-                self.set_delta_emitters(delta)
-        elif delta:
-            raise NotImplementedError("%s: point, spot and directional emitters are not implemented here" % self.prefix)
-        # the analytic disks and cylinders: always sent — the scene's list, or the empty list that clears the context's
-        shapes = getattr(desc, "shapes", None) or []
-        if self.prefix == "ppg_":
-            self.set_shapes(shapes)
-        elif shapes:
-            raise NotImplementedError("%s: analytic disks and cylinders are not implemented here" % self.prefix)
-        # the bitmaps on specular / alpha / opacity: always sent — one entry per material, or the empty list that clears the context's
-        if self.prefix == "ppg_":
-            self.set_material_textures(desc.materials if has_parameter_textures(desc) else [])
-        elif has_parameter_textures(desc):
-            raise NotImplementedError("%s: bitmaps on specular / alpha / opacity (specular_texture, alpha_texture, opacity_texture) are not implemented here"
-                                      % self.prefix)
-        # the general microfacet entries, likewise: one per material, or the empty list that clears the context's
-        if self.prefix == "ppg_":
-            self.set_microfacet(desc.materials if has_general_microfacet(desc) else [])
-        elif has_general_microfacet(desc):
-            raise NotImplementedError("%s: alpha_v, distribution = phong and sample_visible = False are not implemented here" % self.prefix)
-        # the coatings, likewise (a description may also state the list itself, as `coatings`: Coating records or dicts)
-        if self.prefix == "ppg_":
-            explicit = getattr(desc, "coatings", None)
-            self.set_coatings(explicit if explicit is not None else (desc.materials if has_coatings(desc) else []))
-        elif has_coatings(desc):
-            raise NotImplementedError("%s: the coating / roughcoating adapters are not implemented here" % self.prefix)
-        # the blends, likewise (or the list itself, as `blends`: Blend records or dicts)
-        if self.prefix == "ppg_":
-            explicit = getattr(desc, "blends", None)
-            self.set_blends(explicit if explicit is not None else (desc.materials if has_blends(desc) else []))
+        self._send_side_lists(self._BEFORE_SET_SCENE, desc)
         self._call("set_scene", C.byref(s))
         self.width, self.height = cam["width"], cam["height"]
-        # the film's reconstruction filter comes with the scene description (None / absent: the default box)
-        # (a context that never had a filter is left alone: ppg_set_rfilter is only called for a filtered scene or to reset one)
-        rf = getattr(desc, "rfilter", None)
-        if self.prefix == "ppg_":
-            if rf is not None or getattr(self, "_rfilter", None) is not None:
-                self.set_rfilter(rf)
-        elif rf is not None:
-            raise NotImplementedError("%s: reconstruction filters other than the default box are not implemented here" % self.prefix)
-        # the thin lens, likewise (None / absent: pinhole).  The context keeps its lens across ppg_set_scene; it is re-applied here so that
-        # a scene without one renders with the pinhole after a scene with one.
-        lens = getattr(desc, "lens", None)
-        if self.prefix == "ppg_":
-            if lens is not None or getattr(self, "_lens", None) is not None:
-                self.set_lens(lens)
-        elif lens is not None:
-            raise NotImplementedError("%s: the thin-lens camera is not implemented here" % self.prefix)
+        self._send_side_lists(self._AFTER_SET_SCENE, desc)
+
+    # What set_scene sends beside the scene itself: (setter, whether the description carries it, what to send, the attribute that remembers
+    # what the context holds — None: always sent —, what a library other than ppg_ says to a description that carries it — None: nothing left to say).  The lists go
+    # first, ppg_set_scene consumes the context's: shapes and the per-material lists are always sent — one entry per material, or the empty
+    # list that clears the context's; a description may also state `coatings` / `blends` itself, as records or dicts.  Delta emitters, the
+    # film filter and the lens are sent for a description that has one, or to reset what an earlier one left: a context that never had one
+    # is left alone.
+    _BEFORE_SET_SCENE = (
+        ("set_delta_emitters", lambda d: bool(getattr(d, "delta_emitters", None)), lambda d: getattr(d, "delta_emitters", None) or [], "_delta",
+         "point, spot and directional emitters are not implemented here"),
+        ("set_shapes", lambda d: bool(getattr(d, "shapes", None)), lambda d: getattr(d, "shapes", None) or [], None,
+         "analytic disks and cylinders are not implemented here"),
+        ("set_material_textures", has_parameter_textures, lambda d: d.materials if has_parameter_textures(d) else [], None,
+         "bitmaps on specular / alpha / opacity (specular_texture, alpha_texture, opacity_texture) are not implemented here"),
+        ("set_microfacet", has_general_microfacet, lambda d: d.materials if has_general_microfacet(d) else [], None,
+         "alpha_v, distribution = phong and sample_visible = False are not implemented here"),
+        ("set_coatings", has_coatings, lambda d: d.coatings if getattr(d, "coatings", None) is not None else (d.materials if has_coatings(d) else []), None,
+         "the coating / roughcoating adapters are not implemented here"),
+        ("set_blends", has_blends, lambda d: d.blends if getattr(d, "blends", None) is not None else (d.materials if has_blends(d) else []), None,
+         None),  # (set_scene has refused a blend for another library before it expanded the children)
+    )
+    _AFTER_SET_SCENE = (
+        ("set_rfilter", lambda d: getattr(d, "rfilter", None) is not None, lambda d: getattr(d, "rfilter", None), "_rfilter",
+         "reconstruction filters other than the default box are not implemented here"),
+        ("set_lens", lambda d: getattr(d, "lens", None) is not None, lambda d: getattr(d, "lens", None), "_lens",
+         "the thin-lens camera is not implemented here"),
+    )
+
+    def _send_side_lists(self, rows, desc):
+        for setter, carries, items, remembered, refusal in rows:
+            if self.prefix != "ppg_":
+                if refusal and carries(desc):
+                    raise NotImplementedError("%s: %s" % (self.prefix, refusal))
+            elif remembered is None or carries(desc) or getattr(self, remembered, None):
+                getattr(self, setter)(items(desc))
+
+    def _set_list(self, name, cls, items):
+        """ppg_set_<name>(array, n): `items` are records of `cls` or what cls.from_dict takes"""
+        items = list(items or [])
+        arr = (cls * max(1, len(items)))()
+        for i, d in enumerate(items):
+            arr[i] = d if isinstance(d, cls) else cls.from_dict(d)
+        self._call("set_" + name, arr, C.c_uint32(len(items)))
+        return items
 
     def set_delta_emitters(self, emitters):
         """ppg_set_delta_emitters: a list of emitter dicts (DeltaEmitter); an empty list clears it.  Takes effect at the next set_scene."""
-        emitters = list(emitters or [])
-        arr = (DeltaEmitter * max(1, len(emitters)))()
-        for i, d in enumerate(emitters):
-            arr[i] = d if isinstance(d, DeltaEmitter) else DeltaEmitter.from_dict(d)
-        self._call("set_delta_emitters", arr, C.c_uint32(len(emitters)))
-        self._delta = emitters
+        self._delta = self._set_list("delta_emitters", DeltaEmitter, emitters)
 
     def set_shapes(self, shapes):
         """ppg_set_shapes: a list of shape dicts (Shape); an empty list clears it.  Takes effect at, and is validated by, the next set_scene."""
-        shapes = list(shapes or [])
-        arr = (Shape * max(1, len(shapes)))()
-        for i, d in enumerate(shapes):
-            arr[i] = d if isinstance(d, Shape) else Shape.from_dict(d)
-        self._call("set_shapes", arr, C.c_uint32(len(shapes)))
+        self._set_list("shapes", Shape, shapes)
 
     def debug_intersect(self, rays, any_hit=False):
         """ppg_debug_intersect (include/ppg_testhooks.h): rays float32 [n, 8] = (o, mint, d, maxt) through the scene's closest-hit (or
@@ -964,38 +950,22 @@ class Engine:
     def set_material_textures(self, slots):
         """ppg_set_material_textures: one entry per material — a material dict (its specular_texture / alpha_texture / opacity_texture keys) or
         a MaterialTextures; an empty list clears it.  Takes effect at the next set_scene."""
-        slots = list(slots or [])
-        arr = (MaterialTextures * max(1, len(slots)))()
-        for i, d in enumerate(slots):
-            arr[i] = d if isinstance(d, MaterialTextures) else MaterialTextures.from_dict(d)
-        self._call("set_material_textures", arr, C.c_uint32(len(slots)))
+        self._set_list("material_textures", MaterialTextures, slots)
 
     def set_microfacet(self, entries):
         """ppg_set_microfacet: one entry per material — a material dict (its alpha_v / alpha_v_texture / distribution / sample_visible keys) or
         a Microfacet; an empty list clears it.  Takes effect at, and is validated by, the next set_scene."""
-        entries = list(entries or [])
-        arr = (Microfacet * max(1, len(entries)))()
-        for i, d in enumerate(entries):
-            arr[i] = d if isinstance(d, Microfacet) else Microfacet.from_dict(d)
-        self._call("set_microfacet", arr, C.c_uint32(len(entries)))
+        self._set_list("microfacet", Microfacet, entries)
 
     def set_coatings(self, entries):
         """ppg_set_coatings: one entry per material — a material dict (its `coating` key), a coating dict or a Coating; an empty list clears
         it.  Takes effect at, and is validated by, the next set_scene."""
-        entries = list(entries or [])
-        arr = (Coating * max(1, len(entries)))()
-        for i, d in enumerate(entries):
-            arr[i] = d if isinstance(d, Coating) else Coating.from_dict(d)
-        self._call("set_coatings", arr, C.c_uint32(len(entries)))
+        self._set_list("coatings", Coating, entries)
 
     def set_blends(self, entries):
         """ppg_set_blends: one entry per material — a material dict (its `blend` key, children as indices), a blend dict or a Blend; an empty
         list clears it.  Takes effect at, and is validated by, the next set_scene."""
-        entries = list(entries or [])
-        arr = (Blend * max(1, len(entries)))()
-        for i, d in enumerate(entries):
-            arr[i] = d if isinstance(d, Blend) else Blend.from_dict(d)
-        self._call("set_blends", arr, C.c_uint32(len(entries)))
+        self._set_list("blends", Blend, entries)
 
     def debug_bsdf(self, material, wi, wo, sample, key=None, uv=None):
         """ppg_debug_bsdf (include/ppg_testhooks.h): the render's mat_eval / mat_pdf / mat_sample on material(s) `material` of the scene, per

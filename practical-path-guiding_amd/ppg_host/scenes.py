@@ -10,9 +10,13 @@ box has no /root/reference, hence code instead of files.
 a slit, filled with tessellated boxes — many triangles, hard indirect light; Lambertian, or (glossy=True) the S3 material mix
 with GGX metal and plastic.
 """
+import ctypes as C
 import math
+import struct
 
 import numpy as np
+
+from . import bindings as B
 
 
 class SceneDesc:
@@ -40,120 +44,246 @@ class SceneDesc:
         return int(np.asarray(self.indices).shape[0])
 
 
+# ------------------------------------------------------------------------------------------------ the .ppgs container
+# The format is described in host/scene_file.h, beside the C++ table of its optional blocks; BLOCKS below is the same table.  A block is
+# (gather(desc) -> payload or None, put(payload) -> bytes, get(reader, scene)), its bit its row: the header's block word, save_scene and
+# load_scene_file all walk it.  `scene` is the dict of SceneDesc's arguments as read so far (materials, textures, rtrans, ...).
+def _f32(values):
+    return [float(np.float32(v)) for v in values]
+
+
+def _records(items):
+    return b"".join(bytes(x) for x in items)
+
+
+def _put_counted(items):      # uint32 n, n x record
+    return struct.pack("<I", len(items)) + _records(items)
+
+
+_put_per_material = _records  # n_materials x record
+
+
+class _Reader:
+    def __init__(self, path):
+        self.path, self.buf, self.off = path, open(path, "rb").read(), 0
+
+    def fail(self, what="truncated or corrupt flat scene file"):
+        raise ValueError("%s: %s" % (self.path, what))
+
+    def take(self, dtype, count):
+        # every count comes from the file: checked against what is left of it (a corrupt or truncated file is a ValueError, not an
+        # allocation of whatever size its header claims)
+        need = int(count) * np.dtype(dtype).itemsize
+        if count < 0 or need > len(self.buf) - self.off:
+            self.fail()
+        a = np.frombuffer(self.buf, dtype, count, self.off)
+        self.off += a.nbytes
+        return a
+
+    def records(self, cls, n):
+        size = C.sizeof(cls)
+        raw = bytes(self.take(np.uint8, n * size))
+        return [cls.from_buffer_copy(raw, k * size) for k in range(n)]
+
+    def counted(self, cls):
+        return self.records(cls, int(self.take(np.uint32, 1)[0]))
+
+    def per_material(self, scene, cls):
+        return zip(scene["materials"], self.records(cls, len(scene["materials"])))
+
+    def image_size(self):
+        w, h = (int(v) for v in self.take(np.uint32, 2))
+        if not (0 < w < 0x8000 and 0 < h < 0x8000):  # what ppg_set_scene accepts
+            self.fail("image of %d x %d pixels" % (w, h))
+        return w, h
+
+
+def _gather_rtrans(desc):
+    rt = getattr(desc, "rtrans", None)
+    return None if rt is None or not len(rt) else np.ascontiguousarray(rt, np.float32)
+
+
+def _get_rtrans(r, scene):
+    n, samples = (int(v) for v in r.take(np.uint32, 2))
+    scene["rtrans"] = r.take(np.float32, n * (samples + 1)).reshape(n, samples + 1).copy()
+
+
+def _get_spheres(r, scene):
+    scene["spheres"] = [dict(center=tuple(sp.center), radius=float(sp.radius), to_world=list(sp.to_world), material=int(sp.material), emitter=int(sp.emitter),
+                             flip_normals=bool(sp.flip_normals)) for sp in r.counted(B.Sphere)]
+
+
+def _put_envmap(em):
+    rgb = np.ascontiguousarray(em["rgb"], np.float32)
+    return struct.pack("<2If9f", rgb.shape[1], rgb.shape[0], float(np.float32(em.get("scale", 1.0))),
+                       *_f32(np.asarray(em.get("to_world", np.eye(3)), np.float32).reshape(-1))) + rgb.tobytes()
+
+
+def _get_envmap(r, scene):
+    w, h = r.image_size()
+    scale = float(r.take(np.float32, 1)[0])
+    R = [float(v) for v in r.take(np.float32, 9)]
+    scene["envmap"] = dict(rgb=r.take(np.float32, w * h * 3).reshape(h, w, 3).copy(), scale=scale, to_world=R)
+
+
+def _put_textures(textures):
+    out = [struct.pack("<I", len(textures))]
+    for t in textures:
+        rgb = np.ascontiguousarray(t["rgb"], np.float32)
+        wu, wv = t.get("wrap_u", "repeat"), t.get("wrap_v", "repeat")
+        src8 = t.get("srgb8")  # the 8-bit source of an sRGB-decoded image: stored instead of the floats (4x smaller)
+        out.append(struct.pack("<2I4f3iI", rgb.shape[1], rgb.shape[0], *_f32(t.get("uv_scale", (1, 1))), *_f32(t.get("uv_offset", (0, 0))),
+                               B.Texture.WRAP[wu] if isinstance(wu, str) else int(wu), B.Texture.WRAP[wv] if isinstance(wv, str) else int(wv),
+                               1 if t.get("nearest") else 0, 0 if src8 is None else 1))
+        out.append(rgb.tobytes() if src8 is None else np.ascontiguousarray(src8, np.uint8).tobytes())
+    return b"".join(out)
+
+
+def _get_textures(r, scene):
+    names = ["repeat", "mirror", "clamp", "zero", "one"]
+    for _ in range(int(r.take(np.uint32, 1)[0])):
+        w, h = r.image_size()
+        sc = [float(v) for v in r.take(np.float32, 4)]
+        wu, wv, nearest = (int(v) for v in r.take(np.int32, 3))
+        storage = int(r.take(np.uint32, 1)[0])
+        t = dict(uv_scale=tuple(sc[:2]), uv_offset=tuple(sc[2:]), wrap_u=names[wu], wrap_v=names[wv], nearest=bool(nearest))
+        if storage == 1:
+            t["srgb8"] = r.take(np.uint8, w * h * 3).reshape(h, w, 3).copy()
+            t["rgb"] = srgb8_table()[t["srgb8"]]
+        else:
+            t["rgb"] = r.take(np.float32, w * h * 3).reshape(h, w, 3).copy()
+        scene["textures"].append(t)
+
+
+def _gather_rfilter(desc):
+    rf = B.RFilter.from_dict(getattr(desc, "rfilter", None))
+    return rf if rf.as_dict() is not None else None
+
+
+def _get_rfilter(r, scene):
+    rf, = r.records(B.RFilter, 1)
+    if not 0 <= rf.type < len(B.RFilter.TYPES):
+        r.fail("unknown reconstruction filter %d" % rf.type)
+    scene["rfilter"] = rf.as_dict()
+
+
+def _get_typed(key, cls, what):
+    """counted records with a `type` that indexes cls.TYPES: delta emitters, shapes"""
+    def get(r, scene):
+        for e in r.counted(cls):
+            if not 0 <= e.type < len(cls.TYPES):
+                r.fail("unknown %s type %d" % (what, e.type))
+            scene[key].append(e.as_dict())
+    return get
+
+
+def _get_material_textures(r, scene):
+    for d, mt in r.per_material(scene, B.MaterialTextures):
+        for k, v in zip(B.MaterialTextures.KEYS, (mt.specular, mt.alpha, mt.opacity)):
+            if v > len(scene["textures"]) or mt._reserved:
+                r.fail("material texture slot out of range")
+            if v:
+                d[k] = int(v) - 1
+
+
+def _get_microfacet(r, scene):
+    for d, g in r.per_material(scene, B.Microfacet):
+        if any(g._reserved) or g.alpha_v_texture > len(scene["textures"]) or g.distribution not in (0, 1):
+            r.fail("microfacet entry out of range")
+        if g.general:
+            d["alpha_v"] = float(g.alpha_v)
+            if g.distribution == 1:
+                d["distribution"] = "phong"
+            if g.sample_all:
+                d["sample_visible"] = False
+            if g.alpha_v_texture:
+                d["alpha_v_texture"] = int(g.alpha_v_texture) - 1
+
+
+def _get_coatings(r, scene):
+    n_slices = 0 if scene["rtrans"] is None else len(scene["rtrans"])
+    for d, c in r.per_material(scene, B.Coating):
+        if any(c._reserved) or c.kind not in (0, 1, 2) or (c.kind == 2 and (c.distribution not in (0, 1, 2) or not 0 <= c.rtrans < n_slices)):
+            r.fail("coating entry out of range")
+        if c.kind:
+            d["coating"] = c.as_dict()
+
+
+def _get_blends(r, scene):
+    nm = len(scene["materials"])
+    for d, b in r.per_material(scene, B.Blend):
+        if any(b._reserved) or b.kind not in (0, 1, 2) or (b.kind and (not 1 <= b.n <= B.Blend.MAX or any(b.child[i] >= nm for i in range(b.n))
+                                                                       or b.weight_texture > len(scene["textures"]))):
+            r.fail("blend entry out of range")
+        if b.kind:
+            d["blend"] = b.as_dict()
+
+
+def _converted(key, cls):
+    """the description's list `key` as records of `cls`, or None"""
+    return lambda desc: [cls.from_dict(d) for d in (getattr(desc, key, None) or [])] or None
+
+
+def _per_material(cls, live):
+    """one record of `cls` per material (blends: save_scene has appended the children stated as dicts), or None when none of them is live"""
+    def gather(desc):
+        items = [cls.from_dict(m) for m in desc.materials]
+        return items if any(live(x) for x in items) else None
+    return gather
+
+
+BLOCKS = [  # row k is the block of bit k: environment, rtrans, spheres, envmap, texcoords, textures, rfilter, lens, delta emitters,
+           # material textures, shapes, microfacet, coatings, blends
+    (lambda desc: getattr(desc, "environment", None), lambda env: struct.pack("<3f", *_f32(env)),
+     lambda r, scene: scene.update(environment=tuple(float(v) for v in r.take(np.float32, 3)))),
+    (_gather_rtrans, lambda rt: struct.pack("<2I", rt.shape[0], rt.shape[1] - 1) + rt.tobytes(), _get_rtrans),
+    (_converted("spheres", B.Sphere), _put_counted, _get_spheres),
+    (lambda desc: getattr(desc, "envmap", None), _put_envmap, _get_envmap),
+    (lambda desc: getattr(desc, "texcoords", None), lambda uv: np.ascontiguousarray(uv, np.float32).tobytes(),
+     lambda r, scene: scene.update(texcoords=r.take(np.float32, 2 * len(scene["positions"])).reshape(-1, 2).copy())),
+    (lambda desc: getattr(desc, "textures", None) or None, _put_textures, _get_textures),
+    (_gather_rfilter, bytes, _get_rfilter),              # only for a filter other than the default box
+    (lambda desc: B.Lens.from_dict(desc.lens) if getattr(desc, "lens", None) is not None else None, bytes,  # only for a thin-lens camera
+     lambda r, scene: scene.update(lens=r.records(B.Lens, 1)[0].as_dict())),
+    (_converted("delta_emitters", B.DeltaEmitter), _put_counted, _get_typed("delta_emitters", B.DeltaEmitter, "delta emitter")),
+    (_per_material(B.MaterialTextures, lambda t: t.specular or t.alpha or t.opacity), _put_per_material, _get_material_textures),
+    (_converted("shapes", B.Shape), _put_counted, _get_typed("shapes", B.Shape, "shape")),
+    (_per_material(B.Microfacet, lambda g: g.general), _put_per_material, _get_microfacet),
+    (_per_material(B.Coating, lambda c: c.kind), _put_per_material, _get_coatings),
+    (_per_material(B.Blend, lambda b: b.kind), _put_per_material, _get_blends),
+]
+
+
 def save_scene(desc, path):
-    """Write the flat binary scene read by host/ppg_render.cpp: "PPGS", 6 x uint32 {n_vertices, n_triangles, n_materials,
-    n_emitters, has_normals, blocks (bit 0: environment, bit 1: rtrans, bit 2: spheres, bit 3: envmap, bit 4: texcoords, bit 5: textures, bit 6: rfilter, bit 7: lens, bit 8: delta emitters, bit 9: material textures, bit 10: shapes, bit 11: microfacet, bit 12: coatings, bit 13: blends)}, then positions, [normals], indices, tri_material,
-    tri_emitter, materials (ppg_material, 80 bytes each), emitters (4 floats), camera (ppg_camera), [environment radiance:
-    3 floats], [rtrans: 2 x uint32 {n_slices, samples}, then n_slices x (samples + 1) floats], [spheres: uint32 n, then n x ppg_sphere
-    (64 bytes)], [envmap: 2 x uint32 {width, height}, float scale, 9 floats to_world, then height x width x 3 floats], [texcoords: n_vertices x 2
-    floats], [textures: uint32 n, then per texture 2 x uint32 {width, height}, 4 floats uv scale / offset, 3 x int32 {wrap_u, wrap_v, nearest}, uint32
-    storage (0: float32 RGB, 1: uint8 sRGB-encoded RGB — decoded on load with the exact 256-entry table of the 8-bit → float conversion), pixels],
-    [rfilter: ppg_rfilter, 24 bytes {int32 type, float radius, stddev, B, C, int32 lobes} — only for a filter other than the default box],
-    [lens: ppg_lens, 2 floats {aperture_radius, focus_distance} — only for a thin-lens camera],
-    [delta emitters: uint32 n, then n x ppg_delta_emitter (84 bytes) — only when there are point / spot / directional emitters],
-    [material textures: n_materials x ppg_material_textures (16 bytes) — only when a material has a bitmap on specular / alpha / opacity],
-    [shapes: uint32 n, then n x ppg_shape (80 bytes) — only when there are analytic disks or cylinders],
-    [microfacet: n_materials x ppg_microfacet (32 bytes) — only when a material states alphaU / alphaV, distribution = phong or sampleVisible = false],
-    [coatings: n_materials x ppg_coating (64 bytes) — only when a material has a coating / roughcoating],
-    [blends: n_materials x ppg_blend (64 bytes) — only when a material is a blendbsdf / mixturebsdf; children that the description states
-    as dicts are appended to the material list first (bindings.expand_blends)]."""
-    import struct
-    from .bindings import (Blend, Coating, DeltaEmitter, Lens, MaterialTextures, Microfacet, RFilter, Shape, expand_blends, has_blends, has_coatings,
-                           has_general_microfacet, has_parameter_textures)
-    blends = []
-    if has_blends(desc):
+    """Write the flat binary scene that load_scene_file() and host/ppg_render.cpp read (the format: host/scene_file.h).  Children that
+    blended materials state as dicts are appended to the material list first (bindings.expand_blends)."""
+    if B.has_blends(desc):
         import copy
         desc = copy.copy(desc)
-        desc.materials = expand_blends(desc.materials)
-        blends = [Blend.from_dict(m) for m in desc.materials]
-        if not any(b.kind for b in blends):
-            blends = []
-    coats = [Coating.from_dict(m) for m in desc.materials] if has_coatings(desc) else []
-    if not any(c.kind for c in coats):
-        coats = []
-    mfd = [Microfacet.from_dict(m) for m in desc.materials] if has_general_microfacet(desc) else []
-    mat_tex = [MaterialTextures.from_dict(m) for m in desc.materials] if has_parameter_textures(desc) else []
-    rf = RFilter.from_dict(getattr(desc, "rfilter", None))
-    rf = rf if rf.as_dict() is not None else None
-    lens = getattr(desc, "lens", None)
-    lens = None if lens is None else Lens.from_dict(lens)
-    delta = [DeltaEmitter.from_dict(d) for d in (getattr(desc, "delta_emitters", None) or [])]
-    shapes = [Shape.from_dict(d) for d in (getattr(desc, "shapes", None) or [])]
+        desc.materials = B.expand_blends(desc.materials)
+    payloads = [(put, gather(desc)) for gather, put, _ in BLOCKS]
     pos = np.ascontiguousarray(desc.positions, np.float32)
     idx = np.ascontiguousarray(desc.indices, np.uint32)
+    c = desc.camera
     with open(path, "wb") as f:
         f.write(b"PPGS")
-        env = getattr(desc, "environment", None)
-        rt = getattr(desc, "rtrans", None)
-        rt = None if rt is None or not len(rt) else np.ascontiguousarray(rt, np.float32)
         f.write(struct.pack("<6I", pos.shape[0], idx.shape[0], len(desc.materials), len(desc.emitters), 0 if desc.normals is None else 1,
-                            (0 if env is None else 1) | (0 if rt is None else 2) | (4 if getattr(desc, "spheres", None) else 0) | (8 if getattr(desc, "envmap", None) is not None else 0)
-                            | (16 if getattr(desc, "texcoords", None) is not None else 0) | (32 if getattr(desc, "textures", None) else 0) | (0 if rf is None else 64)
-                            | (0 if lens is None else 128) | (256 if delta else 0) | (512 if mat_tex else 0) | (1024 if shapes else 0) | (2048 if mfd else 0) | (4096 if coats else 0) | (8192 if blends else 0)))
+                            sum(1 << k for k, (_, payload) in enumerate(payloads) if payload is not None)))
         f.write(pos.tobytes())
         if desc.normals is not None:
             f.write(np.ascontiguousarray(desc.normals, np.float32).tobytes())
         f.write(idx.tobytes())
         f.write(np.ascontiguousarray(desc.tri_material, np.uint32).tobytes())
         f.write(np.ascontiguousarray(desc.tri_emitter, np.int32).tobytes())
-        from .bindings import Material
-        for m in desc.materials:
-            f.write(bytes(Material.from_dict(m)))  # ppg_material, 80 bytes
+        f.write(_records(B.Material.from_dict(m) for m in desc.materials))
         for e in desc.emitters:
-            f.write(struct.pack("<4f", *[float(np.float32(v)) for v in e["radiance"]], 0))
-        c = desc.camera
+            f.write(struct.pack("<4f", *_f32(e["radiance"]), 0))
         f.write(np.asarray(c["sample_to_camera"], np.float32).tobytes())
         f.write(np.asarray(c["camera_to_world"], np.float32).tobytes())
         f.write(struct.pack("<2f2i", c["near_clip"], c["far_clip"], c["width"], c["height"]))
-        if env is not None:
-            f.write(struct.pack("<3f", *[float(np.float32(v)) for v in env]))
-        if rt is not None:
-            f.write(struct.pack("<2I", rt.shape[0], rt.shape[1] - 1))
-            f.write(rt.tobytes())
-        if getattr(desc, "spheres", None):
-            from .bindings import Sphere
-            f.write(struct.pack("<I", len(desc.spheres)))
-            for d in desc.spheres:
-                f.write(bytes(Sphere.from_dict(d)))
-        if getattr(desc, "envmap", None) is not None:
-            em = desc.envmap
-            rgb = np.ascontiguousarray(em["rgb"], np.float32)
-            f.write(struct.pack("<2If9f", rgb.shape[1], rgb.shape[0], float(np.float32(em.get("scale", 1.0))),
-                                *[float(np.float32(v)) for v in np.asarray(em.get("to_world", np.eye(3)), np.float32).reshape(-1)]))
-            f.write(rgb.tobytes())
-        if getattr(desc, "texcoords", None) is not None:
-            f.write(np.ascontiguousarray(desc.texcoords, np.float32).tobytes())
-        if getattr(desc, "textures", None):
-            from .bindings import Texture
-            f.write(struct.pack("<I", len(desc.textures)))
-            for t in desc.textures:
-                rgb = np.ascontiguousarray(t["rgb"], np.float32)
-                wu, wv = t.get("wrap_u", "repeat"), t.get("wrap_v", "repeat")
-                src8 = t.get("srgb8")  # the 8-bit source of an sRGB-decoded image: stored instead of the floats (4x smaller)
-                f.write(struct.pack("<2I4f3iI", rgb.shape[1], rgb.shape[0], *[float(np.float32(v)) for v in t.get("uv_scale", (1, 1))],
-                                    *[float(np.float32(v)) for v in t.get("uv_offset", (0, 0))], Texture.WRAP[wu] if isinstance(wu, str) else int(wu),
-                                    Texture.WRAP[wv] if isinstance(wv, str) else int(wv), 1 if t.get("nearest") else 0, 0 if src8 is None else 1))
-                f.write(rgb.tobytes() if src8 is None else np.ascontiguousarray(src8, np.uint8).tobytes())
-        if rf is not None:
-            f.write(bytes(rf))
-        if lens is not None:
-            f.write(bytes(lens))
-        if delta:
-            f.write(struct.pack("<I", len(delta)))
-            for d in delta:
-                f.write(bytes(d))
-        for mt in mat_tex:
-            f.write(bytes(mt))
-        if shapes:
-            f.write(struct.pack("<I", len(shapes)))
-            for sh in shapes:
-                f.write(bytes(sh))
-        for g in mfd:
-            f.write(bytes(g))
-        for c in coats:
-            f.write(bytes(c))
-        for b in blends:
-            f.write(bytes(b))
+        for put, payload in payloads:
+            if payload is not None:
+                f.write(put(payload))
 
 
 def srgb8_table():
@@ -162,171 +292,54 @@ def srgb8_table():
     return np.where(v <= 0.04045, v / 12.92, ((v + 0.055) / 1.055) ** 2.4).astype(np.float32)
 
 
+def _material_dict(m):
+    d = dict(type=int(m.type), reflectance=tuple(m.reflectance), specular=tuple(m.specular), alpha=float(m.alpha), eta=tuple(m.eta), k=tuple(m.k),
+             twosided=bool(m.flags & 1), nonlinear=bool(m.flags & 2), rtrans=int(m.rtrans))
+    if m.flags & 4:
+        d["opacity"] = tuple(m.opacity)
+    if m.flags & 8:
+        d["distribution"] = "beckmann"
+    if m.flags & 16:
+        d["fast_approx"] = True
+    if m.texture & 0xffff:
+        d["texture"] = (m.texture & 0xffff) - 1
+    if m.texture >> 16:  # the displacement texture of a bumpmap or (flag 32, PPG_MAT_NORMALMAP) the normal map of a normalmap
+        d["normal_map" if m.flags & 32 else "bump"] = (m.texture >> 16) - 1
+    return d
+
+
 def load_scene_file(path):
-    """Read a flat scene written by save_scene() / `ppg_render --ppgs` back into a SceneDesc."""
-    import struct
-    from .bindings import Material, Sphere
-    buf = open(path, "rb").read()
-    if buf[:4] != b"PPGS":
-        raise ValueError("%s: not a flat scene file" % path)
-    nv, nt, nm, ne, has_n, blocks = struct.unpack_from("<6I", buf, 4)
-    off = [28]
-
-    def take(dtype, count):
-        # every count comes from the file: checked against what is left of it (a corrupt or truncated file is a ValueError, not an
-        # allocation of whatever size its header claims)
-        need = int(count) * np.dtype(dtype).itemsize
-        if count < 0 or need > len(buf) - off[0]:
-            raise ValueError("%s: truncated or corrupt flat scene file" % path)
-        a = np.frombuffer(buf, dtype, count, off[0])
-        off[0] += a.nbytes
-        return a
-
-    def image_size():
-        w, h = (int(v) for v in take(np.uint32, 2))
-        if not (0 < w < 0x8000 and 0 < h < 0x8000):  # what ppg_set_scene accepts
-            raise ValueError("%s: image of %d x %d pixels" % (path, w, h))
-        return w, h
-    pos = take(np.float32, 3 * nv).reshape(-1, 3).copy()
-    nrm = take(np.float32, 3 * nv).reshape(-1, 3).copy() if has_n else None
-    idx = take(np.uint32, 3 * nt).reshape(-1, 3).copy()
-    tm, te = take(np.uint32, nt).copy(), take(np.int32, nt).copy()
-    mats = []
-    for _ in range(nm):
-        m = Material.from_buffer_copy(bytes(take(np.uint8, 80)))
-        d = dict(type=int(m.type), reflectance=tuple(m.reflectance), specular=tuple(m.specular), alpha=float(m.alpha), eta=tuple(m.eta), k=tuple(m.k),
-                 twosided=bool(m.flags & 1), nonlinear=bool(m.flags & 2), rtrans=int(m.rtrans))
-        if m.flags & 4:
-            d["opacity"] = tuple(m.opacity)
-        if m.flags & 8:
-            d["distribution"] = "beckmann"
-        if m.flags & 16:
-            d["fast_approx"] = True
-        if m.texture & 0xffff:
-            d["texture"] = (m.texture & 0xffff) - 1
-        if m.texture >> 16:  # the displacement texture of a bumpmap or (flag 32, PPG_MAT_NORMALMAP) the normal map of a normalmap
-            d["normal_map" if m.flags & 32 else "bump"] = (m.texture >> 16) - 1
-        mats.append(d)
-    ems = [dict(radiance=tuple(float(v) for v in take(np.float32, 4)[:3])) for _ in range(ne)]
-    cam = dict(sample_to_camera=take(np.float32, 16).reshape(4, 4).copy(), camera_to_world=take(np.float32, 16).reshape(4, 4).copy())
-    cam["near_clip"], cam["far_clip"] = (float(v) for v in take(np.float32, 2))
-    cam["width"], cam["height"] = (int(v) for v in take(np.int32, 2))
-    env = tuple(float(v) for v in take(np.float32, 3)) if blocks & 1 else None
-    rt = None
-    if blocks & 2:
-        n, samples = (int(v) for v in take(np.uint32, 2))
-        rt = take(np.float32, n * (samples + 1)).reshape(n, samples + 1).copy()
-    spheres = []
-    if blocks & 4:
-        for _ in range(int(take(np.uint32, 1)[0])):
-            sp = Sphere.from_buffer_copy(bytes(take(np.uint8, 64)))
-            spheres.append(dict(center=tuple(sp.center), radius=float(sp.radius), to_world=list(sp.to_world), material=int(sp.material), emitter=int(sp.emitter),
-                                flip_normals=bool(sp.flip_normals)))
-    envmap = None
-    if blocks & 8:
-        w, h = image_size()
-        scale = float(take(np.float32, 1)[0])
-        R = [float(v) for v in take(np.float32, 9)]
-        envmap = dict(rgb=take(np.float32, w * h * 3).reshape(h, w, 3).copy(), scale=scale, to_world=R)
-    uvs = take(np.float32, 2 * nv).reshape(-1, 2).copy() if blocks & 16 else None
-    textures = []
-    if blocks & 32:
-        names = ["repeat", "mirror", "clamp", "zero", "one"]
-        for _ in range(int(take(np.uint32, 1)[0])):
-            w, h = image_size()
-            sc = [float(v) for v in take(np.float32, 4)]
-            wu, wv, nearest = (int(v) for v in take(np.int32, 3))
-            storage = int(take(np.uint32, 1)[0])
-            t = dict(uv_scale=tuple(sc[:2]), uv_offset=tuple(sc[2:]), wrap_u=names[wu], wrap_v=names[wv], nearest=bool(nearest))
-            if storage == 1:
-                t["srgb8"] = take(np.uint8, w * h * 3).reshape(h, w, 3).copy()
-                t["rgb"] = srgb8_table()[t["srgb8"]]
-            else:
-                t["rgb"] = take(np.float32, w * h * 3).reshape(h, w, 3).copy()
-            textures.append(t)
-    rfilter = None
-    if blocks & 64:
-        from .bindings import RFilter
-        rf = RFilter.from_buffer_copy(bytes(take(np.uint8, C_RFILTER_BYTES)))
-        if not 0 <= rf.type < len(RFilter.TYPES):
-            raise ValueError("%s: unknown reconstruction filter %d" % (path, rf.type))
-        rfilter = rf.as_dict()
-    lens = None
-    if blocks & 128:
-        from .bindings import Lens
-        lens = Lens.from_buffer_copy(bytes(take(np.uint8, C_LENS_BYTES))).as_dict()
-    delta = []
-    if blocks & 256:
-        from .bindings import DeltaEmitter
-        for _ in range(int(take(np.uint32, 1)[0])):
-            e = DeltaEmitter.from_buffer_copy(bytes(take(np.uint8, C_DELTA_EMITTER_BYTES)))
-            if not 0 <= e.type < len(DeltaEmitter.TYPES):
-                raise ValueError("%s: unknown delta emitter type %d" % (path, e.type))
-            delta.append(e.as_dict())
-    if blocks & 512:
-        from .bindings import MaterialTextures
-        for d in mats:
-            mt = MaterialTextures.from_buffer_copy(bytes(take(np.uint8, C_MATERIAL_TEXTURES_BYTES)))
-            for k, v in zip(MaterialTextures.KEYS, (mt.specular, mt.alpha, mt.opacity)):
-                if v > len(textures) or mt._reserved:
-                    raise ValueError("%s: material texture slot out of range" % path)
-                if v:
-                    d[k] = int(v) - 1
-    shapes = []
-    if blocks & 1024:
-        from .bindings import Shape
-        for _ in range(int(take(np.uint32, 1)[0])):
-            sh = Shape.from_buffer_copy(bytes(take(np.uint8, C_SHAPE_BYTES)))
-            if not 0 <= sh.type < len(Shape.TYPES):
-                raise ValueError("%s: unknown shape type %d" % (path, sh.type))
-            shapes.append(sh.as_dict())
-    if blocks & 2048:
-        from .bindings import Microfacet
-        for d in mats:
-            g = Microfacet.from_buffer_copy(bytes(take(np.uint8, C_MICROFACET_BYTES)))
-            if any(g._reserved) or g.alpha_v_texture > len(textures) or g.distribution not in (0, 1):
-                raise ValueError("%s: microfacet entry out of range" % path)
-            if g.general:
-                d["alpha_v"] = float(g.alpha_v)
-                if g.distribution == 1:
-                    d["distribution"] = "phong"
-                if g.sample_all:
-                    d["sample_visible"] = False
-                if g.alpha_v_texture:
-                    d["alpha_v_texture"] = int(g.alpha_v_texture) - 1
-    if blocks & 4096:
-        from .bindings import Coating
-        n_slices = 0 if rt is None else len(rt)
-        for d in mats:
-            c = Coating.from_buffer_copy(bytes(take(np.uint8, C_COATING_BYTES)))
-            if any(c._reserved) or c.kind not in (0, 1, 2) or (c.kind == 2 and (c.distribution not in (0, 1, 2) or not 0 <= c.rtrans < n_slices)):
-                raise ValueError("%s: coating entry out of range" % path)
-            if c.kind:
-                d["coating"] = c.as_dict()
-    if blocks & 8192:
-        from .bindings import Blend
-        n_tex = len(textures) if textures else 0
-        for d in mats:
-            b = Blend.from_buffer_copy(bytes(take(np.uint8, C_BLEND_BYTES)))
-            if any(b._reserved) or b.kind not in (0, 1, 2) or (b.kind and (not 1 <= b.n <= Blend.MAX or any(b.child[i] >= nm for i in range(b.n)) or b.weight_texture > n_tex)):
-                raise ValueError("%s: blend entry out of range" % path)
-            if b.kind:
-                d["blend"] = b.as_dict()
-    if blocks >> 14:
-        raise ValueError("%s: a block this reader does not know" % path)
-    if off[0] != len(buf):
-        raise ValueError("%s: trailing bytes" % path)
-    return SceneDesc(pos, idx, tm, te, mats, ems, cam, nrm, env, rt, spheres, envmap, uvs, textures, rfilter, lens, delta, shapes)
+    """Read a flat scene written by save_scene() / `ppg_render --ppgs` back into a SceneDesc; ValueError for a file that is truncated,
+    corrupt or carries a block this reader does not know."""
+    r = _Reader(path)
+    if r.buf[:4] != b"PPGS":
+        r.fail("not a flat scene file")
+    r.off = 4
+    nv, nt, nm, ne, has_n, flags = (int(v) for v in r.take(np.uint32, 6))
+    scene = dict(environment=None, rtrans=None, spheres=[], envmap=None, texcoords=None, textures=[], rfilter=None, lens=None, delta_emitters=[], shapes=[])
+    scene["positions"] = r.take(np.float32, 3 * nv).reshape(-1, 3).copy()
+    scene["normals"] = r.take(np.float32, 3 * nv).reshape(-1, 3).copy() if has_n else None
+    scene["indices"] = r.take(np.uint32, 3 * nt).reshape(-1, 3).copy()
+    scene["tri_material"], scene["tri_emitter"] = r.take(np.uint32, nt).copy(), r.take(np.int32, nt).copy()
+    scene["materials"] = [_material_dict(m) for m in r.records(B.Material, nm)]
+    scene["emitters"] = [dict(radiance=tuple(float(v) for v in r.take(np.float32, 4)[:3])) for _ in range(ne)]
+    cam = dict(sample_to_camera=r.take(np.float32, 16).reshape(4, 4).copy(), camera_to_world=r.take(np.float32, 16).reshape(4, 4).copy())
+    cam["near_clip"], cam["far_clip"] = (float(v) for v in r.take(np.float32, 2))
+    cam["width"], cam["height"] = (int(v) for v in r.take(np.int32, 2))
+    scene["camera"] = cam
+    for k, (_, _, get) in enumerate(BLOCKS):
+        if flags >> k & 1:
+            get(r, scene)
+    if flags >> len(BLOCKS):
+        r.fail("a block this reader does not know")
+    if r.off != len(r.buf):
+        r.fail("trailing bytes")
+    return SceneDesc(**scene)
 
 
-C_RFILTER_BYTES = 24  # sizeof(ppg_rfilter)
-C_LENS_BYTES = 8      # sizeof(ppg_lens)
-C_SHAPE_BYTES = 80    # sizeof(ppg_shape)
-C_MICROFACET_BYTES = 32  # sizeof(ppg_microfacet)
-C_COATING_BYTES = 64  # sizeof(ppg_coating)
-C_BLEND_BYTES = 64    # sizeof(ppg_blend)
-C_MATERIAL_TEXTURES_BYTES = 16  # sizeof(ppg_material_textures)
-C_DELTA_EMITTER_BYTES = 84  # sizeof(ppg_delta_emitter)
+# sizeof the C structs, as the bindings' ctypes mirrors know them
+(C_RFILTER_BYTES, C_LENS_BYTES, C_SHAPE_BYTES, C_MICROFACET_BYTES, C_COATING_BYTES, C_BLEND_BYTES, C_MATERIAL_TEXTURES_BYTES, C_DELTA_EMITTER_BYTES) = (
+    C.sizeof(c) for c in (B.RFilter, B.Lens, B.Shape, B.Microfacet, B.Coating, B.Blend, B.MaterialTextures, B.DeltaEmitter))
 
 
 def _sample_to_camera(fov_deg, fov_axis, near, far, width, height):
