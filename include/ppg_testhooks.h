@@ -2,8 +2,8 @@
  * ppg_testhooks.h — entry points of libppg_hip.so that exist for the tests only.  Not part of the drop-in boundary (include/ppg.h): nothing
  * a host of the integrator needs, no reference counterpart.
  *   host only   ppg_debug_build_bvh, ppg_debug_bvh_stats, ppg_debug_bvh_trace, ppg_debug_rfilter_table, ppg_debug_stree_depth
- *   a scene     ppg_debug_intersect, ppg_debug_intersect_mode, ppg_debug_sample_direct, ppg_debug_bsdf, ppg_debug_shading_frame,
- *               ppg_debug_camera_rays
+ *   a scene     ppg_debug_intersect, ppg_debug_intersect_mode, ppg_debug_sample_direct, ppg_debug_sample_direct_as, ppg_debug_pdf_direct,
+ *               ppg_debug_bsdf, ppg_debug_shading_frame, ppg_debug_camera_rays
  *   a render    ppg_debug_set_defer_depth, ppg_debug_commit (inside an open training iteration)
  *   no scene    ppg_debug_math_eval, ppg_debug_math_checksum
  */
@@ -125,7 +125,26 @@ int ppg_debug_intersect_mode(struct ppg_ctx *ctx, uint32_t n, const float *rays,
 /* emitter_sample_direct of the FULL kernels, sample by sample: per item a reference point ref[3], its normal ref_n[3] and the 2-D sample
    u[2].  Out: the emitter chosen (the hook repeats the render's pmf_sample on the same table and sample: the record does not carry the
    index), and of its direct-sampling record the direction d, the distance, the emitter's normal n, the density in
-   solid angle (0 where the facing tests fail), the emitter-choice probability and value = radiance / pdf. */
+   solid angle (0 where the facing tests fail), the emitter-choice probability and value = radiance / pdf.  ppg_debug_direct_ex, the record
+   of ppg_debug_sample_direct_as, adds what the render reads of the record besides: the direction sd and length sdist of the shadow ray (Scene::evalTransmittance recomputes them from the two end
+   points, scene.cpp:621-623) and whether the emitter is the environment emitter (is_env) or a point / spot / directional one (is_delta).
+   The record is what the device function left in its DirectSample, also for a failed sample (pdf = 0), of which the render reads nothing:
+   an emitter without triangles, a missed bounding sphere and a failed envmap sample leave all of it 0 but em_pdf (and is_env); a failed
+   facing test leaves the sampled point's d, dist, n, sd, sdist.  ppg_debug_sample_direct runs emitter_sample_direct<true> of the shapes
+   family, whatever the scene.
+
+   ppg_debug_sample_direct_as runs emitter_sample_direct<full != 0> as the TRACE unit of kernel family `family` (0 .. 5, csrc/ppg_device.h)
+   compiled it: every family holds its own copy of the function, and a render calls the one of its scene's family.  full = 0 exists in
+   the base family only (a scene of diffuse, two-sided diffuse and mirror materials; it knows no delta emitters, no environment map and no
+   shapes: the host gives it no scene that holds one).  family = -1: the family and the FULL setting a render of this context's scene
+   would use (`full` is ignored).  PPG_ERR_INVALID for an instantiation that does not exist — full = 0 above the base family — and for one
+   that cannot read the scene: a family below the scene's own, or full = 0 for a scene whose render is FULL.
+   ref and ref_n may be any floats; u is a sample, 0 <= u <= 1 (ppg_rand returns at most 1 - 2^-23), and both hooks check that on the host
+   (PPG_ERR_INVALID names the first item outside, NaN included): every table index the functions form is clamped or wrapped for such a
+   value (pmf_sample, envmap_sample_reuse, envmap_texel, envmap_clamp_row), while a u.y above 1 would step pmf_sample's forward skip past a
+   last triangle of area 0 and read one entry beyond the emitter's tables.
+   The oracle has the same entry without the two selectors, ppgo_debug_sample_direct (oracle/ppg_oracle.h): Scene::sampleEmitterDirect up to
+   the shadow ray.  It fills the same record, which the device must equal bit for bit. */
 struct ppg_debug_direct {
     int32_t emitter;
     float d[3];
@@ -135,7 +154,48 @@ struct ppg_debug_direct {
     float value[3];
     float _pad[3];
 };  /* 64 bytes */
+struct ppg_debug_direct_ex {  /* ppg_debug_direct (its first 52 bytes), then the rest of the DirectSample */
+    int32_t emitter;
+    float d[3];
+    float dist;
+    float n[3];
+    float pdf, em_pdf;
+    float value[3];
+    float sd[3];
+    float sdist;
+    int32_t is_env, is_delta;
+    int32_t _pad;
+};  /* 80 bytes */
 int ppg_debug_sample_direct(struct ppg_ctx *ctx, uint32_t n, const float *ref, const float *ref_n, const float *u, struct ppg_debug_direct *out);
+int ppg_debug_sample_direct_as(struct ppg_ctx *ctx, int32_t family, int32_t full, uint32_t n, const float *ref, const float *ref_n, const float *u,
+                               struct ppg_debug_direct_ex *out);
+
+/* The other half of multiple importance sampling: the density next-event estimation would have had for an emitter that a BSDF-sampled
+   ray found — the FL_PENDING branch of k_shade / k_tail (csrc/ppg_kernels.h shade_one; GP:2078-2111), ray by ray.  rays as for
+   ppg_debug_intersect (mint as it stands: Scene::rayIntersect scales a mint of exactly 1e-4f by max(|o|_inf, 1e-4), pass the scaled
+   value); ref_n[3 i ..] = the normal of the DirectSamplingRecord of the vertex the ray left, three zeros = it has none (a BSDF with a
+   back side or transmission).  One lane per ray runs the closest hit and the intersection record of ppg_debug_intersect (fill_isect_full:
+   the mesh's shading normal; the render's fill_isect_tex gives the same normal, since bump and normal maps perturb the frame the BSDF is
+   queried in, not Intersection::shFrame.n, which AreaLight::eval and pdfDirect read), eval_Le of the hit,
+   or — the ray left the scene — env_fill_direct and env_radiance; then, from ref_n exactly as the render keeps them across the bounce,
+   FL_PEND_REFN = dot(d, ref_n) >= 0 and nee_cos = dot(d, ref_n) (-2 without a ref_n), and with them emitter_pdf_direct, the function the
+   render calls (csrc/ppg_device.h).  Like the render it asks for the density only where value is not zero: pdf_direct = 0 elsewhere.
+   The search for an emitter behind null surfaces (GP:2184-2245) is not followed: the hook stops at the first hit.
+     family  0 .. 5: the TRACE unit of that kernel family, FULL; -1: the scene's own.  PPG_ERR_INVALID below the scene's own.
+     prim    as ppg_debug_intersect (-1: the ray left the scene; the oracle's is the triangle's index in the scene, not in leaf order)
+     emitter the emitter found, as an index of the selection table (area emitters, delta emitters, the environment emitter last);
+             -1 for none
+     value   its radiance towards the ray's origin (0 from behind)
+     pdf_direct   Emitter::pdfDirect, solid angle;  emitter_pdf = pdf_direct * the normalisation of the selection table
+                  (Scene::pdfEmitterDirect, scene.cpp:949-952)
+   The oracle's entry is ppgo_debug_pdf_direct: rayIntersect, Scene::Le or envFillDirectSamplingRecord + envEval, pdfEmitterDirect. */
+struct ppg_debug_pdf {
+    int32_t prim, emitter;
+    float value[3];
+    float pdf_direct, emitter_pdf;
+    int32_t _pad;
+};  /* 32 bytes */
+int ppg_debug_pdf_direct(struct ppg_ctx *ctx, int32_t family, uint32_t n, const float *rays, const float *ref_n, struct ppg_debug_pdf *out);
 
 /* The BSDF layer of the context's materials (after ppg_set_scene, outside a render), item by item: one small kernel of the extended
    units (csrc: PPG_MFD) whose lanes prepare the material as the render does at a hit with texture coordinates uv — the record, the bitmaps

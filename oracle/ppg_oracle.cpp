@@ -975,9 +975,15 @@ struct EnvMap {
     }
     int clampRow(int y) const { return y < 0 ? 0 : (y > h - 1 ? h - 1 : y); }
     // internalSampleDirection (envmap.cpp:557-595): d in the emitter's frame
+    // DEVIATION: a chosen interval of width 0 — a sample component of exactly 0 in front of a black first row or column — is a
+    // failed sample (value = 0, pdf = 0) instead of the reference's 0 / 0, which its film drops (imageblock.h:150-153) and ours would keep.
     void sampleDirection(Point2 sample, Vec &d, Spectrum &value, Float &pdf) const {
+        d = Vec(0.0f); value = Spectrum(0.0f); pdf = 0.0f;
         uint32_t row = sampleReuse(cdfRows.data(), (uint32_t)h, sample.y);
-        uint32_t col = sampleReuse(cdfCols.data() + (size_t)row * (w + 1), (uint32_t)w, sample.x);
+        if (cdfRows[row + 1] - cdfRows[row] == 0) return;
+        const float *cols = cdfCols.data() + (size_t)row * (w + 1);
+        uint32_t col = sampleReuse(cols, (uint32_t)w, sample.x);
+        if (cols[col + 1] - cols[col] == 0) return;
         const Float posX = (Float)col + intervalToTent(sample.x), posY = (Float)row + intervalToTent(sample.y);
         const int xPos = floorToInt(posX), yPos = floorToInt(posY);
         const Float dx1 = posX - xPos, dx2 = 1.0f - dx1, dy1 = posY - yPos, dy2 = 1.0f - dy1;
@@ -1401,14 +1407,16 @@ struct Scene {
         return transmittance;
     }
 
-    template <typename HasNull, typename EvalNull>
-    Spectrum sampleEmitterDirect(DRec &dRec, Point2 sample, uint64_t &shadowRays, int interactions, HasNull hasNull, EvalNull evalNull) const {
+    // The part up to the shadow ray: the emitter choice and Emitter::sampleDirect.  dRec.pdf is the solid-angle density BEFORE the choice
+    // probability emPdf and the return value is radiance / dRec.pdf; a failed sample has dRec.pdf = 0.  (What emitter_sample_direct returns on
+    // the device; ppgo_debug_sample_direct shows it item by item.)
+    Spectrum sampleEmitterDirectUnshadowed(DRec &dRec, Point2 sample, Float &emPdf, size_t &index, bool &isEnv) const {
         dRec.pdf = 0;
+        emPdf = 0; index = 0; isEnv = false;
         if (emMesh.empty() && !hasEnv) return Spectrum(0.0f);
-        Float emPdf;
-        size_t index = emitterPDF.sampleReuse(sample.x, emPdf);
+        index = emitterPDF.sampleReuse(sample.x, emPdf);
         Spectrum value(0.0f);
-        const bool isEnv = hasEnv && (int)index == envIndex();
+        isEnv = hasEnv && (int)index == envIndex();
         if (isEnv) {
             value = envSampleDirect(dRec, sample);
         } else if (emitterSphere[index] >= 0) {  // AreaLight::sampleDirect (area.cpp:158-173) on a sphere
@@ -1447,6 +1455,14 @@ struct Scene {
             const float *r = emitters[index].radiance;
             value = Spectrum(r[0], r[1], r[2]) / dRec.pdf;
         }
+        return value;
+    }
+    template <typename HasNull, typename EvalNull>
+    Spectrum sampleEmitterDirect(DRec &dRec, Point2 sample, uint64_t &shadowRays, int interactions, HasNull hasNull, EvalNull evalNull) const {
+        Float emPdf;
+        size_t index;
+        bool isEnv;
+        Spectrum value = sampleEmitterDirectUnshadowed(dRec, sample, emPdf, index, isEnv);
         if (dRec.pdf == 0) return Spectrum(0.0f);  // scene.cpp:885, 896
         // value *= evalTransmittance(its.p, true, dRec.p, emitter->isOnSurface(), ...) / emPdf
         if (!isZero(value)) {
@@ -1462,6 +1478,11 @@ struct Scene {
     // (shape.cpp:117-126), solid-angle measure
     Float pdfEmitterDirect(const DRec &dRec) const {
         if (dRec.emitter < 0) return 0.0f;
+        return pdfEmitterDirectSolidAngle(dRec) * (1.0f * emitterPDF.normalization);  // pdfEmitterDiscrete, scene.h:848-850
+    }
+    // Emitter::pdfDirect of dRec.emitter, before the choice probability
+    Float pdfEmitterDirectSolidAngle(const DRec &dRec) const {
+        if (dRec.emitter < 0) return 0.0f;
         Float pdf = 0.0f;
         if (hasEnv && dRec.emitter == envIndex() && envMap.valid) {  // EnvironmentMap::pdfDirect, envmap.cpp:540-552 (solid angle)
             pdf = envMap.pdfDirection(envMap.toLocal(dRec.d));
@@ -1472,7 +1493,7 @@ struct Scene {
             if (emitterSphere[dRec.emitter] >= 0) pdf = spherePdfDirect(spheres[emitterSphere[dRec.emitter]], dRec);
             else pdf = emMesh[dRec.emitter].invSurfaceArea * (dRec.dist * dRec.dist) / ppg_abs(dot(dRec.d, dRec.n));
         }
-        return pdf * (1.0f * emitterPDF.normalization);  // pdfEmitterDiscrete, scene.h:848-850
+        return pdf;
     }
 
     void triBounds(uint32_t t, Point &mn, Point &mx) const {
@@ -3604,6 +3625,79 @@ int ppgo_set_adam_regions(ppgo_ctx *ctx, int32_t regions) {  // include/ppg.h "R
     return PPG_OK;
 }
 int ppgo_debug_set_defer_depth(ppgo_ctx *ctx, int32_t depth) { if (depth < 1 || depth > 64) return PPG_ERR_INVALID; ctx->gpt.m_deferDepth = depth; return PPG_OK; }
+// include/ppg_testhooks.h, ppg_debug_sample_direct_as: Scene::sampleEmitterDirect up to the shadow ray, item by item.  sd, sdist are the
+// shadow ray as Scene::evalTransmittance makes it from the two end points (scene.cpp:621-623); a sample that produced no point (no normal,
+// no distance) has none.
+int ppgo_debug_sample_direct(ppgo_ctx *ctx, uint32_t n, const float *ref, const float *ref_n, const float *u, ppg_debug_direct_ex *out) {
+    NEED_SCENE
+    if (n && (!ref || !ref_n || !u || !out)) { ctx->gpt.error = "ppg_debug_sample_direct: no arrays"; return PPG_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; ++i)  // (as the product: beyond 1 DiscreteDistribution::sample can leave its table)
+        if (!(u[2 * i] >= 0.0f && u[2 * i] <= 1.0f && u[2 * i + 1] >= 0.0f && u[2 * i + 1] <= 1.0f)) { ctx->gpt.error = "ppg_debug_sample_direct: item " + std::to_string(i) + ": a sample outside [0, 1]"; return PPG_ERR_INVALID; }
+    const Scene &sc = ctx->gpt.scene;
+    for (uint32_t i = 0; i < n; ++i) {
+        DRec dRec;
+        dRec.ref = Point(ref[3 * i], ref[3 * i + 1], ref[3 * i + 2]);
+        dRec.refN = Vec(ref_n[3 * i], ref_n[3 * i + 1], ref_n[3 * i + 2]);
+        Float emPdf; size_t index; bool isEnv;
+        const Spectrum value = sc.sampleEmitterDirectUnshadowed(dRec, Point2{u[2 * i], u[2 * i + 1]}, emPdf, index, isEnv);
+        ppg_debug_direct_ex r;
+        memset(&r, 0, sizeof r);
+        const bool any = !sc.emMesh.empty() || sc.hasEnv;
+        r.emitter = any ? (int32_t)index : -1;
+        r.d[0] = dRec.d.x; r.d[1] = dRec.d.y; r.d[2] = dRec.d.z; r.dist = dRec.dist;
+        r.n[0] = dRec.n.x; r.n[1] = dRec.n.y; r.n[2] = dRec.n.z;
+        r.pdf = dRec.pdf; r.em_pdf = emPdf;
+        r.value[0] = value.x; r.value[1] = value.y; r.value[2] = value.z;
+        if (!(dRec.dist == 0 && dRec.n.x == 0 && dRec.n.y == 0 && dRec.n.z == 0)) {
+            Vec sd = dRec.p - dRec.ref;
+            const Float remaining = length(sd);
+            sd = sd / remaining;
+            r.sd[0] = sd.x; r.sd[1] = sd.y; r.sd[2] = sd.z; r.sdist = remaining;
+        }
+        r.is_env = isEnv ? 1 : 0;
+        out[i] = r;
+    }
+    return PPG_OK;
+}
+// include/ppg_testhooks.h, ppg_debug_pdf_direct: rayIntersect (a mint of exactly Epsilon is scaled there), Scene::Le of the hit or the
+// environment emitter for a ray that left the scene, then Scene::pdfEmitterDirect where the integrator asks for it (GP:2083-2085)
+int ppgo_debug_pdf_direct(ppgo_ctx *ctx, uint32_t n, const float *rays, const float *ref_n, ppg_debug_pdf *out) {
+    NEED_SCENE
+    if (n && (!rays || !ref_n || !out)) { ctx->gpt.error = "ppg_debug_pdf_direct: no arrays"; return PPG_ERR_INVALID; }
+    const Scene &sc = ctx->gpt.scene;
+    for (uint32_t i = 0; i < n; ++i) {
+        const float *q = rays + 8 * (size_t)i;
+        const Point o(q[0], q[1], q[2]);
+        const Vec d(q[4], q[5], q[6]);
+        DRec dRec;
+        dRec.ref = o;
+        dRec.refN = Vec(ref_n[3 * i], ref_n[3 * i + 1], ref_n[3 * i + 2]);
+        Intersection its;
+        const bool surface = sc.rayIntersect(o, d, q[3], q[7], its);
+        Spectrum value(0.0f);
+        ppg_debug_pdf r;
+        memset(&r, 0, sizeof r);
+        r.prim = surface ? its.prim : -1;
+        r.emitter = -1;
+        if (surface) {
+            r.emitter = its.emitter;
+            if (its.emitter >= 0) {  // dRec.setQuery(ray, its), records.inl:170-178
+                dRec.p = its.p; dRec.n = its.shFrame.n; dRec.d = d; dRec.dist = its.t; dRec.emitter = its.emitter;
+                value = sc.Le(its, -d);
+            }
+        } else if (sc.hasEnv && sc.envFillDirectSamplingRecord(dRec, o, d)) {
+            value = sc.envEval(d);
+            r.emitter = dRec.emitter;
+        }
+        r.value[0] = value.x; r.value[1] = value.y; r.value[2] = value.z;
+        if (!isZero(value)) {
+            r.emitter_pdf = sc.pdfEmitterDirect(dRec);
+            r.pdf_direct = sc.pdfEmitterDirectSolidAngle(dRec);
+        }
+        out[i] = r;
+    }
+    return PPG_OK;
+}
 // include/ppg_testhooks.h, ppg_debug_commit: the same vertices through Vertex::commit and the round's end (no arithmetic of its own)
 int ppgo_debug_commit(ppgo_ctx *ctx, const ppg_debug_commit_in *in, ppg_debug_commit_out *out) {
     NEED_TREE

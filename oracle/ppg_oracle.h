@@ -73,6 +73,13 @@ int ppgo_work_counters(ppgo_ctx *ctx, uint64_t *out8);
 int ppgo_path_length_histogram(ppgo_ctx *ctx, uint64_t *out);
 /* the tests' switch of include/ppg_testhooks.h (ppg_debug_set_defer_depth), same meaning */
 int ppgo_debug_set_defer_depth(ppgo_ctx *ctx, int32_t depth);
+/* ppg_debug_sample_direct_as and ppg_debug_pdf_direct of include/ppg_testhooks.h without the family selectors, same arrays and records:
+   Scene::sampleEmitterDirect up to the shadow ray (before the transmittance and the division by the choice probability), and
+   rayIntersect + Scene::Le / the environment emitter + Scene::pdfEmitterDirect.  prim is the triangle's index in the scene. */
+struct ppg_debug_direct_ex;
+struct ppg_debug_pdf;
+int ppgo_debug_sample_direct(ppgo_ctx *ctx, uint32_t n, const float *ref, const float *ref_n, const float *u, struct ppg_debug_direct_ex *out);
+int ppgo_debug_pdf_direct(ppgo_ctx *ctx, uint32_t n, const float *rays, const float *ref_n, struct ppg_debug_pdf *out);
 /* ppg_debug_commit of include/ppg_testhooks.h, same arrays: every vertex a Vertex with dTree = STree::dTreeWrapper(p, voxel) and the sampler
    at (key, dim + 3 v), through Vertex::commit with the round's code numbering; then applyAdamRound.  The route only decides whether the
    call is refused (as the product refuses it); keys = the keys of the optimiser's records (no "splat only" records exist here). */

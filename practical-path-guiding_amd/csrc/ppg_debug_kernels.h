@@ -1,10 +1,11 @@
 /*
  * ppg_debug_kernels.h — the kernels of the test hooks (include/ppg_testhooks.h) that run the render's own device functions, included by the
- * k_trace unit of a family (ppg_inst.hip): k_debug_intersect, the kernels of ppg_debug_intersect_mode and k_debug_sample_direct in the shapes family, which the hooks always use;
+ * k_trace unit of a family (ppg_inst.hip): k_debug_intersect and the kernels of ppg_debug_intersect_mode in the shapes family, which the hooks always use;
  * k_debug_bsdf in the ext family, k_debug_bsdf_coat in the coat family, which ppg_debug_bsdf uses for a scene with a coated material, and
  * k_debug_bsdf_blend in the blend family, which it uses for a scene with a blended one; k_debug_shading_frame in the top (lobes) family, which
  * ppg_debug_shading_frame always uses.  Every family holds k_debug_math_eval and
- * k_debug_math_checksum (ppg_debug_math_*): the shared float math as this module compiled it, its own out-of-line dm_ copies included.
+ * k_debug_math_checksum (ppg_debug_math_*): the shared float math as this module compiled it, its own out-of-line dm_ copies included;
+ * and k_debug_sample_direct / k_debug_pdf_direct (ppg_debug_sample_direct_as, ppg_debug_pdf_direct): its own copy of the direct-light functions.
  */
 #ifndef PPG_DEBUG_KERNELS_H
 #define PPG_DEBUG_KERNELS_H
@@ -40,22 +41,6 @@ __global__ void k_debug_intersect(DevScene S, unsigned int n, const float4 *rays
             r.material = I.material; r.emitter = I.emitter;
         }
     }
-    out[i] = r;
-}
-__global__ void k_debug_sample_direct(DevScene S, unsigned int n, const float *ref, const float *refN, const float *u, ppg_debug_direct *out) {
-    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    DirectSample ds;
-    const F3 value = emitter_sample_direct<true>(S, f3(ref[3 * i], ref[3 * i + 1], ref[3 * i + 2]), f3(refN[3 * i], refN[3 * i + 1], refN[3 * i + 2]),
-                                                 u[2 * i], u[2 * i + 1], ds);
-    ppg_debug_direct r;
-    memset(&r, 0, sizeof r);
-    const int n_sel = S.n_emitters + S.n_delta + (S.env.w != 0 ? 1 : 0);
-    r.emitter = n_sel ? pmf_sample(S.em_sel_cdf, n_sel + 1, u[2 * i]) : -1;  // the choice emitter_sample_direct makes
-    r.d[0] = ds.d.x; r.d[1] = ds.d.y; r.d[2] = ds.d.z; r.dist = ds.dist;
-    r.n[0] = ds.n.x; r.n[1] = ds.n.y; r.n[2] = ds.n.z;
-    r.pdf = ds.pdf; r.em_pdf = ds.em_pdf;
-    r.value[0] = value.x; r.value[1] = value.y; r.value[2] = value.z;
     out[i] = r;
 }
 // ---- ppg_debug_intersect_mode: the other forms of the closest-hit traversal, ray by ray ----
@@ -182,10 +167,6 @@ static void launch_debug_hit_records(hipStream_t stream, const DevScene &S, unsi
 static void launch_debug_intersect(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_hit *out, int any) {
     hipLaunchKernelGGL(k_debug_intersect, dim3(grid), dim3(block), (size_t)PPG_LDS_STACK * block * sizeof(int), stream, S, n, rays, out, any);
 }
-static void launch_debug_sample_direct(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float *ref, const float *ref_n, const float *u,
-                                       ppg_debug_direct *out) {
-    hipLaunchKernelGGL(k_debug_sample_direct, dim3(grid), dim3(block), 0, stream, S, n, ref, ref_n, u, out);
-}
 #endif
 
 #if PPG_FAMILY >= PPG_FAMILY_EXT
@@ -269,6 +250,71 @@ static void launch_debug_shading_frame(int grid, int block, hipStream_t stream, 
 }
 #endif
 
+// ---- ppg_debug_sample_direct(_as) / ppg_debug_pdf_direct: the two halves of the direct-light MIS, in every family's module ----
+#define k_debug_sample_direct PPG_FAMILY_NAME(k_debug_sample_direct)
+#define k_debug_pdf_direct PPG_FAMILY_NAME(k_debug_pdf_direct)
+// emitter_sample_direct<FULL> as this module compiled it; the record is the DirectSample as the function left it
+template <bool FULL>
+__global__ void k_debug_sample_direct(DevScene S, unsigned int n, const float *ref, const float *refN, const float *u, ppg_debug_direct_ex *out) {
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    DirectSample ds;
+    const F3 value = emitter_sample_direct<FULL>(S, f3(ref[3 * i], ref[3 * i + 1], ref[3 * i + 2]), f3(refN[3 * i], refN[3 * i + 1], refN[3 * i + 2]),
+                                                 u[2 * i], u[2 * i + 1], ds);
+    ppg_debug_direct_ex r;
+    memset(&r, 0, sizeof r);
+    const int n_sel = S.n_emitters + (FULL ? S.n_delta : 0) + (S.env.w != 0 ? 1 : 0);
+    r.emitter = n_sel ? pmf_sample(S.em_sel_cdf, n_sel + 1, u[2 * i]) : -1;  // the choice emitter_sample_direct makes
+    r.d[0] = ds.d.x; r.d[1] = ds.d.y; r.d[2] = ds.d.z; r.dist = ds.dist;
+    r.n[0] = ds.n.x; r.n[1] = ds.n.y; r.n[2] = ds.n.z;
+    r.pdf = ds.pdf; r.em_pdf = ds.em_pdf;
+    r.value[0] = value.x; r.value[1] = value.y; r.value[2] = value.z;
+    r.sd[0] = ds.sd.x; r.sd[1] = ds.sd.y; r.sd[2] = ds.sd.z; r.sdist = ds.sdist;
+    r.is_env = ds.is_env ? 1 : 0; r.is_delta = ds.is_delta ? 1 : 0;
+    out[i] = r;
+}
+// the FL_PENDING branch of shade_one (ppg_kernels.h) up to emitterPdf, for a ray that left a vertex whose DirectSamplingRecord normal is
+// refN (0: none): closest hit, the FULL kernels' record, eval_Le or the environment emitter, then the render's own emitter_pdf_direct
+__global__ void k_debug_pdf_direct(DevScene S, unsigned int n, const float4 *rays, const float *refN, ppg_debug_pdf *out) {
+    extern __shared__ int dbg_stack[];
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 ro = rays[2 * i], rd = rays[2 * i + 1];
+    const F3 o = f3(ro.x, ro.y, ro.z), d = f3(rd.x, rd.y, rd.z), rn = f3(refN[3 * i], refN[3 * i + 1], refN[3 * i + 2]);
+    ppg_debug_pdf r;
+    memset(&r, 0, sizeof r);
+    const Hit h = trace_closest4<false, true>(S, dbg_stack + threadIdx.x, (int)blockDim.x, o, d, ro.w, rd.w);
+    const bool valid = h.prim >= 0;
+    Isect I;
+    I.n = f3s(0.0f); I.emitter = -1;
+    if (valid) fill_isect_full(S, h, o, d, I);
+    F3 value = valid ? eval_Le(S, I, -d) : f3s(0.0f);
+    const F3 em_n = I.n;
+    const float em_dist = h.t;
+    int em_id = I.emitter;
+    if (!valid && S.env.w != 0 && env_fill_direct(S, o, d)) { value = env_radiance(S, d); em_id = S.n_emitters + S.n_delta; }
+    const bool noRefN = rn.x == 0 && rn.y == 0 && rn.z == 0;
+    const bool refn_ok = dot3(d, rn) >= 0;                    // FL_PEND_REFN as shade_one sets it when it samples the bounce
+    const float nee_cos = noRefN ? -2.0f : dot3(d, rn);       // P.nee_cos likewise
+    float pdfDirect = 0.0f;
+    if (!iszero3(value)) pdfDirect = emitter_pdf_direct<true>(S, em_id, d, em_n, em_dist, refn_ok, [&]() { return nee_cos; }, [&]() { return ro; });
+    r.prim = h.prim; r.emitter = em_id;
+    r.value[0] = value.x; r.value[1] = value.y; r.value[2] = value.z;
+    r.pdf_direct = pdfDirect;
+    r.emitter_pdf = pdfDirect * (1.0f * S.em_sel_norm);
+    out[i] = r;
+}
+static void launch_debug_sample_direct(int full, int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float *ref, const float *ref_n,
+                                       const float *u, ppg_debug_direct_ex *out) {
+#if PPG_FAMILY == PPG_FAMILY_BASE
+    if (!full) { hipLaunchKernelGGL((k_debug_sample_direct<false>), dim3(grid), dim3(block), 0, stream, S, n, ref, ref_n, u, out); return; }
+#endif
+    hipLaunchKernelGGL((k_debug_sample_direct<true>), dim3(grid), dim3(block), 0, stream, S, n, ref, ref_n, u, out);  // (the hook has refused full = 0 elsewhere)
+}
+static void launch_debug_pdf_direct(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, const float *ref_n, ppg_debug_pdf *out) {
+    hipLaunchKernelGGL(k_debug_pdf_direct, dim3(grid), dim3(block), (size_t)PPG_LDS_STACK * block * sizeof(int), stream, S, n, rays, ref_n, out);
+}
+
 // ---- ppg_debug_math_eval / ppg_debug_math_checksum: include/ppg_mathcheck.h on the device, in every family's module ----
 #define k_debug_math_eval PPG_FAMILY_NAME(k_debug_math_eval)
 #define k_debug_math_checksum PPG_FAMILY_NAME(k_debug_math_checksum)
@@ -338,9 +384,10 @@ static void launch_debug_math_checksum(hipStream_t stream, int via, int op, unsi
 static void fill_debug_kernels(PathKernels &K) {
     K.debug_math_eval = launch_debug_math_eval;
     K.debug_math_checksum = launch_debug_math_checksum;
+    K.debug_sample_direct = launch_debug_sample_direct;
+    K.debug_pdf_direct = launch_debug_pdf_direct;
 #if PPG_FAMILY == PPG_FAMILY_SHAPES
     K.debug_intersect = launch_debug_intersect;
-    K.debug_sample_direct = launch_debug_sample_direct;
     K.debug_trace = launch_debug_trace;
     K.debug_hit_records = launch_debug_hit_records;
 #endif

@@ -1173,10 +1173,16 @@ D float interval_to_tent(float sample) {  // warp.cpp:143-155
     else { sign = -1; sample = 2 * (sample - 0.5f); }
     return sign * (1 - __builtin_sqrtf(sample));
 }
-// internalSampleDirection (envmap.cpp:557-595): direction in the emitter's frame
+// internalSampleDirection (envmap.cpp:557-595): direction in the emitter's frame.  DEVIATION: a chosen interval of width 0 — a
+// sample component of exactly 0 in front of a black first row or column — is a failed sample (value = 0, pdf = 0) instead of the
+// reference's 0 / 0, which its film drops (imageblock.h:150-153) and k_film would keep.
 D void envmap_sample_direction(const DevScene &S, float sx, float sy, F3 &d, F3 &value, float &pdf) {
+    d = f3s(0.0f); value = f3s(0.0f); pdf = 0.0f;
     const int row = envmap_sample_reuse(S.em_cdf_rows, S.em_h, sy);
-    const int col = envmap_sample_reuse(S.em_cdf_cols + (size_t)row * (S.em_w + 1), S.em_w, sx);
+    if (S.em_cdf_rows[row + 1] - S.em_cdf_rows[row] == 0) return;
+    const float *cols = S.em_cdf_cols + (size_t)row * (S.em_w + 1);
+    const int col = envmap_sample_reuse(cols, S.em_w, sx);
+    if (cols[col + 1] - cols[col] == 0) return;
     const float posX = (float)col + interval_to_tent(sx), posY = (float)row + interval_to_tent(sy);
     const int xPos = (int)__builtin_floorf(posX), yPos = (int)__builtin_floorf(posY);
     const float dx1 = posX - xPos, dx2 = 1.0f - dx1, dy1 = posY - yPos, dy2 = 1.0f - dy1;
@@ -1470,6 +1476,27 @@ D F3 emitter_sample_direct(const DevScene &S, F3 ref, F3 refN, float sx, float s
     }
     const float4 r = S.emitters[e];
     return div3(f3(r.x, r.y, r.z), ds.pdf);
+}
+// Scene::pdfEmitterDirect (scene.cpp:949-952) before the choice probability: the solid-angle density with which emitter em_id (its index in
+// the selection table, the environment emitter last) would have been sampled along d from the ray's origin — EnvironmentMap::pdfDirect
+// (envmap.cpp:540-552), ConstantBackgroundEmitter::pdfDirect (constant.cpp:216-231), AreaLight::pdfDirect (area.cpp:175-183) on
+// Sphere::pdfDirect or Shape::pdfDirect (shape.cpp:117-126).  em_n, em_dist: the emitter's normal and its distance at the hit; refn_ok:
+// dot(d, dRec.refN) >= 0.  nee_cos() (dot(d, dRec.refN), -2 without a refN) and ray_origin() (a float4) are called only by the branches
+// that need them: the constant environment, and a sphere, whose pdfDirect needs dRec.ref = the previous vertex = the ray's origin.
+template <bool FULL, typename NeeCos, typename RayOrigin>
+D float emitter_pdf_direct(const DevScene &S, int em_id, F3 d, F3 em_n, float em_dist, bool refn_ok, NeeCos nee_cos, RayOrigin ray_origin) {
+    float pdfDirect = 0.0f;
+    const float dn = dot3(d, em_n);
+    if (FULL && em_id == S.n_emitters + S.n_delta) {
+        pdfDirect = S.env.w == 2.0f ? envmap_pdf_direction(S, envmap_to_local(S, d)) : env_pdf_direct(nee_cos());
+    } else if (refn_ok && dn < 0) {
+        const int4 info = S.em_info[em_id];
+        if (FULL && info.y < 0) {
+            const float4 ro4 = ray_origin();
+            pdfDirect = sphere_pdf_direct(S.spheres + 4 * (-info.y - 1), f3(ro4.x, ro4.y, ro4.z), d, em_n, em_dist);
+        } else pdfDirect = __int_as_float(info.w) * (em_dist * em_dist) / ppg_abs(dn);
+    }
+    return pdfDirect;
 }
 
 // Transform::operator()(Point) (transform.h:108-125) and operator()(Vector) (:175-183)

@@ -3093,10 +3093,12 @@ int ppg_debug_intersect_mode(ppg_ctx *ctx, uint32_t n, const float *rays, ppg_de
     }
     return PPG_OK;
 }
-int ppg_debug_sample_direct(ppg_ctx *ctx, uint32_t n, const float *ref, const float *ref_n, const float *u, ppg_debug_direct *out) {
-    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
-    if (ctx->renderOpen) { ctx->error = "ppg_debug_sample_direct: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
-    if (n && (!ref || !ref_n || !u || !out)) { ctx->error = "ppg_debug_sample_direct: no arrays"; return PPG_ERR_INVALID; }
+// emitter_sample_direct<full> of kernel family `family` (both checked by the caller).  A sample outside [0, 1] is refused: beyond 1 pmf_sample's
+// forward skip can leave the emitter's tables (include/ppg_testhooks.h).
+static int debugSampleDirect(ppg_ctx *ctx, const char *who, int family, int full, uint32_t n, const float *ref, const float *ref_n, const float *u, ppg_debug_direct_ex *out) {
+    if (n && (!ref || !ref_n || !u || !out)) { ctx->error = std::string(who) + ": no arrays"; return PPG_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; ++i)
+        if (!(u[2 * i] >= 0.0f && u[2 * i] <= 1.0f && u[2 * i + 1] >= 0.0f && u[2 * i + 1] <= 1.0f)) { ctx->error = std::string(who) + ": item " + std::to_string(i) + ": a sample outside [0, 1]"; return PPG_ERR_INVALID; }
     if (n == 0) return PPG_OK;
     HIP_CHECK(hipSetDevice(ctx->device));
     ctx->quiesce();
@@ -3104,13 +3106,65 @@ int ppg_debug_sample_direct(ppg_ctx *ctx, uint32_t n, const float *ref, const fl
     HIP_CHECK(dRef.fill(ref, 3 * (size_t)n * sizeof(float)));
     HIP_CHECK(dRefN.fill(ref_n, 3 * (size_t)n * sizeof(float)));
     HIP_CHECK(dU.fill(u, 2 * (size_t)n * sizeof(float)));
-    HIP_CHECK(dOut.fill(nullptr, (size_t)n * sizeof(ppg_debug_direct)));
+    HIP_CHECK(dOut.fill(nullptr, (size_t)n * sizeof(ppg_debug_direct_ex)));
     const unsigned int block = 64;
-    launcher(ppg_path_kernels[PPG_FAMILY_SHAPES].debug_sample_direct)((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const float *)dRef.p,
-                                                                      (const float *)dRefN.p, (const float *)dU.p, (ppg_debug_direct *)dOut.p);
+    launcher(ppg_path_kernels[family].debug_sample_direct)(full, (int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const float *)dRef.p,
+                                                           (const float *)dRefN.p, (const float *)dU.p, (ppg_debug_direct_ex *)dOut.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_direct), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_direct_ex), hipMemcpyDeviceToHost));
+    return PPG_OK;
+}
+int ppg_debug_sample_direct(ppg_ctx *ctx, uint32_t n, const float *ref, const float *ref_n, const float *u, ppg_debug_direct *out) {
+    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
+    if (ctx->renderOpen) { ctx->error = "ppg_debug_sample_direct: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (n && !out) { ctx->error = "ppg_debug_sample_direct: no arrays"; return PPG_ERR_INVALID; }
+    std::vector<ppg_debug_direct_ex> ex(n);
+    if (const int rc = debugSampleDirect(ctx, "ppg_debug_sample_direct", PPG_FAMILY_SHAPES, 1, n, ref, ref_n, u, ex.data())) return rc;
+    static_assert(offsetof(ppg_debug_direct, _pad) == offsetof(ppg_debug_direct_ex, sd), "the extended record starts with the plain one");
+    for (uint32_t i = 0; i < n; ++i) {  // the plain record: the extended one's first 52 bytes, the padding 0
+        memset(&out[i], 0, sizeof out[i]);
+        memcpy(&out[i], &ex[i], offsetof(ppg_debug_direct, _pad));
+    }
+    return PPG_OK;
+}
+// a kernel family can read the scene if it is the scene's own or one above it (every family knows what the families below it know)
+static int debugFamily(ppg_ctx *ctx, const char *who, int32_t family, int *out) {
+    const int own = sceneFamily(ctx->scene);
+    if (family < -1 || family >= PPG_FAMILIES) { ctx->error = std::string(who) + ": no such kernel family"; return PPG_ERR_INVALID; }
+    if (family >= 0 && family < own) { ctx->error = std::string(who) + ": the scene needs kernel family " + std::to_string(own) + " or above"; return PPG_ERR_INVALID; }
+    *out = family < 0 ? own : family;
+    return PPG_OK;
+}
+int ppg_debug_sample_direct_as(ppg_ctx *ctx, int32_t family, int32_t full, uint32_t n, const float *ref, const float *ref_n, const float *u, ppg_debug_direct_ex *out) {
+    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
+    if (ctx->renderOpen) { ctx->error = "ppg_debug_sample_direct_as: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    int fam = 0;
+    if (const int rc = debugFamily(ctx, "ppg_debug_sample_direct_as", family, &fam)) return rc;
+    if (family < 0) full = ctx->fullMaterials ? 1 : 0;
+    if (!full && fam != PPG_FAMILY_BASE) { ctx->error = "ppg_debug_sample_direct_as: full = 0 exists in the base family only"; return PPG_ERR_INVALID; }
+    if (!full && ctx->fullMaterials) { ctx->error = "ppg_debug_sample_direct_as: the scene needs the FULL kernels"; return PPG_ERR_INVALID; }
+    return debugSampleDirect(ctx, "ppg_debug_sample_direct_as", fam, full ? 1 : 0, n, ref, ref_n, u, out);
+}
+int ppg_debug_pdf_direct(ppg_ctx *ctx, int32_t family, uint32_t n, const float *rays, const float *ref_n, ppg_debug_pdf *out) {
+    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
+    if (ctx->renderOpen) { ctx->error = "ppg_debug_pdf_direct: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    int fam = 0;
+    if (const int rc = debugFamily(ctx, "ppg_debug_pdf_direct", family, &fam)) return rc;
+    if (n && (!rays || !ref_n || !out)) { ctx->error = "ppg_debug_pdf_direct: no arrays"; return PPG_ERR_INVALID; }
+    if (n == 0) return PPG_OK;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->quiesce();
+    DebugBuf dRays, dRefN, dOut;
+    HIP_CHECK(dRays.fill(rays, 2 * (size_t)n * sizeof(float4)));
+    HIP_CHECK(dRefN.fill(ref_n, 3 * (size_t)n * sizeof(float)));
+    HIP_CHECK(dOut.fill(nullptr, (size_t)n * sizeof(ppg_debug_pdf)));
+    const unsigned int block = 64;
+    launcher(ppg_path_kernels[fam].debug_pdf_direct)((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const float4 *)dRays.p, (const float *)dRefN.p,
+                                                     (ppg_debug_pdf *)dOut.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_pdf), hipMemcpyDeviceToHost));
     return PPG_OK;
 }
 

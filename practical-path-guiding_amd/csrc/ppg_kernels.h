@@ -984,17 +984,7 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
         const bool hasTree = (flags & FL_PEND_TREE) != 0;
         float emitterPdf = 0.0f;  // GP:2085: scene->pdfEmitterDirect(dRec) (scene.cpp:949-952, area.cpp:175-183, shape.cpp:117-126)
         if (NEE && R.do_nee && !isDelta && !iszero3(value)) {
-            float pdfDirect = 0.0f;
-            const float dn = dot3(d, em_n);
-            if (FULL && em_id == S.n_emitters + S.n_delta) {
-                pdfDirect = S.env.w == 2.0f ? envmap_pdf_direction(S, envmap_to_local(S, d)) : env_pdf_direct(P.nee_cos[i]);
-            } else if ((flags & FL_PEND_REFN) && dn < 0) {
-                const int4 info = S.em_info[em_id];
-                if (FULL && info.y < 0) {  // Sphere::pdfDirect needs dRec.ref = the previous vertex = this ray's origin
-                    const float4 ro4 = ray_origin();
-                    pdfDirect = sphere_pdf_direct(S.spheres + 4 * (-info.y - 1), f3(ro4.x, ro4.y, ro4.z), d, em_n, em_dist);
-                } else pdfDirect = __int_as_float(info.w) * (em_dist * em_dist) / ppg_abs(dn);
-            }
+            const float pdfDirect = emitter_pdf_direct<FULL>(S, em_id, d, em_n, em_dist, (flags & FL_PEND_REFN) != 0, [&]() { return P.nee_cos[i]; }, ray_origin);
             emitterPdf = pdfDirect * (1.0f * S.em_sel_norm);
         }
         float pa = woPdf * woPdf, pb = emitterPdf * emitterPdf;  // miWeight(woPdf, emitterPdf), GP:2247-2250

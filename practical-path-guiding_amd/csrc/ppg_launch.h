@@ -94,7 +94,8 @@ struct FieldsResolveLaunch {
 // One row per kernel family (ppg_device.h PPG_FAMILY): the launchers of its k_shade, k_tail and k_trace.  Every unit of ppg_inst.hip enters the
 // launchers it defines into its family's row when the library is loaded; the host picks the row with sceneFamily (ppg_hip.hip).
 struct ppg_debug_hit;
-struct ppg_debug_direct;
+struct ppg_debug_direct_ex;
+struct ppg_debug_pdf;
 struct ppg_debug_bsdf_item;
 struct ppg_debug_bsdf_out;
 struct ppg_debug_frame;
@@ -102,13 +103,11 @@ struct PathKernels {
     void (*shade[2])(int variant, const ShadeLaunch &a);  // [NEE]; variant = (NEE ? 2 : 0) | (FULL ? 1 : 0)
     void (*tail[4])(int variant, const TailLaunch &a);    // [SMALL * 2 + NEE]; variant = (SMALL ? 4 : 0) | (NEE ? 2 : 0) | (FULL ? 1 : 0)
     void (*trace)(const TraceLaunch &a);
-    // The kernels of the test hooks (ppg_debug_kernels.h), in the families that compile them: the shapes family those of ppg_debug_intersect /
-    // ppg_debug_sample_direct, the families from ext on that of ppg_debug_bsdf, the top family that of ppg_debug_shading_frame
+    // The kernels of the test hooks (ppg_debug_kernels.h), in the families that compile them: the shapes family those of ppg_debug_intersect,
+    // the families from ext on that of ppg_debug_bsdf, the top family that of ppg_debug_shading_frame
     void (*debug_intersect)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_hit *out, int any);
     void (*debug_trace)(int mode, int param, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_hit *out, unsigned int *stats);
     void (*debug_hit_records)(hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, const float4 *hits, ppg_debug_hit *out);
-    void (*debug_sample_direct)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float *ref, const float *ref_n, const float *u,
-                                ppg_debug_direct *out);
     void (*debug_bsdf)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out);
     void (*debug_shading_frame)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_frame *out);
     // the top family: the kernels of ppg_render_fields (ppg_fields_kernels.h), which know every material and shape a scene may hold
@@ -117,6 +116,10 @@ struct PathKernels {
     // every family: include/ppg_mathcheck.h as the family's TRACE unit compiled it (via = 1: through the unit's dm_ copies)
     void (*debug_math_eval)(hipStream_t stream, int via, int op, unsigned int n, const uint32_t *a, const uint32_t *b, uint32_t *out0, uint32_t *out1);
     void (*debug_math_checksum)(hipStream_t stream, int via, int op, unsigned int first_block, unsigned int n_blocks, unsigned long long *out);
+    // every family: its copy of emitter_sample_direct<full != 0> (full = 0: the base family only) and of the pending bounce's emitter density
+    void (*debug_sample_direct)(int full, int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float *ref, const float *ref_n,
+                                const float *u, ppg_debug_direct_ex *out);
+    void (*debug_pdf_direct)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, const float *ref_n, ppg_debug_pdf *out);
 };
 extern PathKernels ppg_path_kernels[PPG_FAMILIES];
 

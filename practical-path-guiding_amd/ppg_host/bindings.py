@@ -372,6 +372,17 @@ class DebugDirect(C.Structure):
                 ("value", C.c_float * 3), ("_pad", C.c_float * 3)]
 
 
+class DebugDirectEx(C.Structure):
+    """ppg_debug_direct_ex (include/ppg_testhooks.h)"""
+    _fields_ = [("emitter", C.c_int32), ("d", C.c_float * 3), ("dist", C.c_float), ("n", C.c_float * 3), ("pdf", C.c_float), ("em_pdf", C.c_float),
+                ("value", C.c_float * 3), ("sd", C.c_float * 3), ("sdist", C.c_float), ("is_env", C.c_int32), ("is_delta", C.c_int32), ("_pad", C.c_int32)]
+
+
+class DebugPdf(C.Structure):
+    """ppg_debug_pdf (include/ppg_testhooks.h)"""
+    _fields_ = [("prim", C.c_int32), ("emitter", C.c_int32), ("value", C.c_float * 3), ("pdf_direct", C.c_float), ("emitter_pdf", C.c_float), ("_pad", C.c_int32)]
+
+
 DEBUG_HIT_DTYPE = np.dtype([("prim", "<i4"), ("t", "<f4"), ("p", "<f4", 3), ("geo_n", "<f4", 3), ("n", "<f4", 3), ("s", "<f4", 3), ("wi", "<f4", 3),
                             ("material", "<i4"), ("emitter", "<i4"), ("_pad", "<i4")])
 DEBUG_FRAME_DTYPE = np.dtype([("prim", "<i4"), ("material", "<i4"), ("uv", "<f4", 2), ("n", "<f4", 3), ("s", "<f4", 3), ("ps", "<f4", 3), ("pt", "<f4", 3),
@@ -381,6 +392,9 @@ DEBUG_BSDF_OUT_DTYPE = np.dtype([("eval", "<f4", 3), ("pdf", "<f4"), ("wo", "<f4
                                  ("delta", "<i4"), ("is_null", "<i4"), ("_pad", "<i4", 2)])
 DEBUG_DIRECT_DTYPE = np.dtype([("emitter", "<i4"), ("d", "<f4", 3), ("dist", "<f4"), ("n", "<f4", 3), ("pdf", "<f4"), ("em_pdf", "<f4"),
                                ("value", "<f4", 3), ("_pad", "<f4", 3)])
+DEBUG_DIRECT_EX_DTYPE = np.dtype([("emitter", "<i4"), ("d", "<f4", 3), ("dist", "<f4"), ("n", "<f4", 3), ("pdf", "<f4"), ("em_pdf", "<f4"),
+                                  ("value", "<f4", 3), ("sd", "<f4", 3), ("sdist", "<f4"), ("is_env", "<i4"), ("is_delta", "<i4"), ("_pad", "<i4")])
+DEBUG_PDF_DTYPE = np.dtype([("prim", "<i4"), ("emitter", "<i4"), ("value", "<f4", 3), ("pdf_direct", "<f4"), ("emitter_pdf", "<f4"), ("_pad", "<i4")])
 
 
 MAX_FIELDS = 8  # PPG_MAX_FIELDS
@@ -903,6 +917,37 @@ class Engine:
         out = np.zeros(ref.shape[0], DEBUG_DIRECT_DTYPE)
         assert out.itemsize == C.sizeof(DebugDirect)
         self._call("debug_sample_direct", C.c_uint32(ref.shape[0]), _fp(ref), _fp(ref_n), _fp(u), out.ctypes.data_as(C.POINTER(DebugDirect)))
+        return out
+
+    def debug_sample_direct_as(self, ref, ref_n, u, family=-1, full=1):
+        """ppg_debug_sample_direct_as: emitter_sample_direct<full> of kernel family `family` (-1: what a render of the scene would run); on the
+        oracle ppgo_debug_sample_direct, which has no such selectors.  Arrays as debug_sample_direct; a structured array (DEBUG_DIRECT_EX_DTYPE)."""
+        ref = np.ascontiguousarray(ref, np.float32).reshape(-1, 3)
+        ref_n = np.ascontiguousarray(ref_n, np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(u, np.float32).reshape(-1, 2)
+        assert ref.shape[0] == ref_n.shape[0] == u.shape[0]
+        out = np.zeros(ref.shape[0], DEBUG_DIRECT_EX_DTYPE)
+        assert out.itemsize == C.sizeof(DebugDirectEx)
+        args = (C.c_uint32(ref.shape[0]), _fp(ref), _fp(ref_n), _fp(u), out.ctypes.data_as(C.POINTER(DebugDirectEx)))
+        if self.prefix == "ppg_":
+            self._call("debug_sample_direct_as", C.c_int32(int(family)), C.c_int32(int(full)), *args)
+        else:
+            self._call("debug_sample_direct", *args)
+        return out
+
+    def debug_pdf_direct(self, rays, ref_n, family=-1):
+        """ppg_debug_pdf_direct / ppgo_debug_pdf_direct: per ray (float32 [n, 8] = (o, mint, d, maxt)) and normal of the vertex it left (ref_n
+        [n, 3], zeros = none) the emitter it finds and the density next-event estimation has for it; a structured array (DEBUG_PDF_DTYPE)."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        ref_n = np.ascontiguousarray(ref_n, np.float32).reshape(-1, 3)
+        assert rays.shape[0] == ref_n.shape[0]
+        out = np.zeros(rays.shape[0], DEBUG_PDF_DTYPE)
+        assert out.itemsize == C.sizeof(DebugPdf)
+        args = (C.c_uint32(rays.shape[0]), _fp(rays), _fp(ref_n), out.ctypes.data_as(C.POINTER(DebugPdf)))
+        if self.prefix == "ppg_":
+            self._call("debug_pdf_direct", C.c_int32(int(family)), *args)
+        else:
+            self._call("debug_pdf_direct", *args)
         return out
 
     DEBUG_COMMIT_ROUTES = dict(commit=0, commit_split=1, records=2, records_split=3)
