@@ -3,7 +3,7 @@
  * a host of the integrator needs, no reference counterpart.
  *   host only   ppg_debug_build_bvh, ppg_debug_bvh_stats, ppg_debug_bvh_trace, ppg_debug_rfilter_table, ppg_debug_stree_depth
  *   a scene     ppg_debug_intersect, ppg_debug_intersect_mode, ppg_debug_sample_direct, ppg_debug_sample_direct_as, ppg_debug_pdf_direct,
- *               ppg_debug_bsdf, ppg_debug_shading_frame, ppg_debug_camera_rays
+ *               ppg_debug_bsdf, ppg_debug_bsdf_as, ppg_debug_shading_frame, ppg_debug_camera_rays
  *   a render    ppg_debug_set_defer_depth, ppg_debug_commit (inside an open training iteration)
  *   no scene    ppg_debug_math_eval, ppg_debug_math_checksum
  */
@@ -224,6 +224,34 @@ struct ppg_debug_bsdf_out {
     int32_t _pad[2];
 };  /* 64 bytes */
 int ppg_debug_bsdf(struct ppg_ctx *ctx, uint32_t n, const struct ppg_debug_bsdf_item *items, struct ppg_debug_bsdf_out *out);
+
+/* The same items and record through ONE compiled copy of the BSDF layer.  mat_eval / mat_pdf / mat_sample are compiled into every kernel
+   family (csrc/ppg_device.h: the families differ by preprocessor — PPG_MFD, PPG_COAT with the nested BSDF behind real calls, PPG_BLEND with
+   the scene as a further argument), the base family also holds the lean bsdf_eval / bsdf_pdf / bsdf_sample and a unit compiled with
+   PPG_PARAM_TEXTURES = 0, where Mat has another layout and mat_spec_lum is computed; a render calls the copies of its scene's family.
+     family  0 .. 5: that kernel family; -1: the family, and FULL or LEAN, that a render of this context's scene would use (`unit` is
+             ignored).
+     unit    FULL    mat_eval / mat_pdf / mat_sample as the TRACE unit of `family` compiled them, the material prepared as for ppg_debug_bsdf
+             LEAN    base family only: the material as the !FULL branch of shade_one loads it (the type, flags = 0, the reflectance), then
+                     bsdf_eval / bsdf_pdf / bsdf_sample; eta = 1 and is_null = 0, as shade_one leaves them
+             COMMON  base family only: a kernel inside the translation unit of k_shade<false, true, MSET_COMMON>, calling that unit's
+                     mat_*; it looks up no bitmap on specular / alpha / opacity, as the unit never does
+   _pad[0] of the record carries what the render derives from the material beside the BSDF values: bit 0 mat_is_smooth (LEAN:
+   bsdf_is_smooth; only such a vertex is guided), bit 1 mat_backside_or_transmission (LEAN: the type is two-sided diffuse; such a vertex
+   hands emitter sampling no normal), bit 2 mat_has_null (null surfaces are searched behind it); _pad[1] stays 0.  ppg_debug_bsdf is
+   ppg_debug_bsdf_as(max(the scene's family, 2), FULL) and fills the same bits.
+   PPG_ERR_INVALID, ppg_last_error naming the reason, for an instantiation that does not exist (LEAN or COMMON above the base family, an
+   unknown unit or family); for one that cannot read the scene (a family below the scene's own, LEAN for a scene whose render is FULL); for
+   COMMON with an item whose material sort_slice would keep out of the common part of a slice (csrc/ppg_kernels.h: a type outside diffuse /
+   two-sided diffuse / mirror / conductor / roughconductor / plastic / roughplastic, a mask, a bitmap on specular / alpha / opacity, a bump
+   or normal map); for a material index out of range; and — both entries — for a sample outside [0, 1], NaN included (the plug-ins divide a
+   sample by a probability and index the rough-transmittance slice and a blend's cdf with the result).  PPG_ERR_STATE inside a render.  A
+   refused call launches nothing.
+   The oracle's entries are ppgo_bsdf_eval, ppgo_bsdf_sample_ex and ppgo_bsdf_flags (oracle/ppg_oracle.h), which every copy must equal bit
+   for bit. */
+enum { PPG_DEBUG_BSDF_FULL = 0, PPG_DEBUG_BSDF_LEAN = 1, PPG_DEBUG_BSDF_COMMON = 2 };
+int ppg_debug_bsdf_as(struct ppg_ctx *ctx, int32_t family, int32_t unit, uint32_t n, const struct ppg_debug_bsdf_item *items,
+                      struct ppg_debug_bsdf_out *out);
 
 /* The shared float math (include/ppg_detmath.h, ppg_rng.h) as ONE module of this library compiled it; no scene is needed.  The ops, their
    arguments (bit patterns), their domains and the block checksum are those of include/ppg_mathcheck.h.

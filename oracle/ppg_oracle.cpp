@@ -1911,6 +1911,10 @@ struct GGX {
         Float result;
         if (beckmann) {
             result = ppg_exp(-beckmannExponent) / (PPG_PI_F * alpha * alpha * cosTheta2 * cosTheta2);
+            // math::fastexp (math.h:185-203) underflows towards 0 where ppg_exp is clamped to exp(-80) = 1.8e-35: a normal within 1e-3 of the
+            // horizon divided that by cos^4 into a positive D where microfacet.h:203 gives 0.  Beyond the clamp the reference's own value
+            // falls under its cut (microfacet.h:230) for every alpha^2 < 1e24, so 0 is its answer (csrc/ppg_device.h ggx_eval).
+            if (beckmannExponent > 80.0f) result = 0;
         } else {
             Float root = ((Float)1 + beckmannExponent) * cosTheta2;
             result = (Float)1 / (PPG_PI_F * alpha * alpha * root * root);
@@ -3992,8 +3996,9 @@ int ppgo_bsdf_eval(const ppg_material *mat, uint32_t n, const float *wi, const f
     }
     return PPG_OK;
 }
-int ppgo_bsdf_sample(const ppg_material *mat, uint32_t n, const float *wi, const float *sample_xy, float *wo_out, float *weight_out,
-                     float *pdf_out, float *eta_out, int32_t *delta_out) {
+// ... and whether the sample is the null component (sampledType == ENull; null_out may be NULL)
+int ppgo_bsdf_sample_ex(const ppg_material *mat, uint32_t n, const float *wi, const float *sample_xy, float *wo_out, float *weight_out,
+                        float *pdf_out, float *eta_out, int32_t *delta_out, int32_t *null_out) {
     Material m; static_cast<ppg_material &>(m) = *mat;
     if (m.type < 0 || m.type > PPG_BSDF_LAST || !testSlice(m)) return PPG_ERR_INVALID;
     m.configure();
@@ -4005,7 +4010,18 @@ int ppgo_bsdf_sample(const ppg_material *mat, uint32_t n, const float *wi, const
         wo_out[3 * i] = b.wo.x; wo_out[3 * i + 1] = b.wo.y; wo_out[3 * i + 2] = b.wo.z;
         weight_out[3 * i] = w.x; weight_out[3 * i + 1] = w.y; weight_out[3 * i + 2] = w.z;
         pdf_out[i] = pdf; eta_out[i] = b.eta; delta_out[i] = b.sampledDelta ? 1 : 0;
+        if (null_out) null_out[i] = b.sampledNull ? 1 : 0;
     }
+    return PPG_OK;
+}
+int ppgo_bsdf_sample(const ppg_material *mat, uint32_t n, const float *wi, const float *sample_xy, float *wo_out, float *weight_out,
+                     float *pdf_out, float *eta_out, int32_t *delta_out) {
+    return ppgo_bsdf_sample_ex(mat, n, wi, sample_xy, wo_out, weight_out, pdf_out, eta_out, delta_out, nullptr);
+}
+// getType() & ENull of the material: the third of the bits ppg_debug_bsdf_as leaves in its record (include/ppg_testhooks.h)
+int ppgo_bsdf_has_null(const ppg_material *mat, int32_t *has_null) {
+    Material m; static_cast<ppg_material &>(m) = *mat;
+    *has_null = BSDF::hasNull(m);
     return PPG_OK;
 }
 // EnvironmentMap, element-wise (tests): radiance and solid-angle density for world directions; sampled directions with value / pdf

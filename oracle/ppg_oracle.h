@@ -123,6 +123,10 @@ int ppgo_bsdf_eval(const ppg_material *mat, uint32_t n, const float *wi, const f
 int ppgo_bsdf_sample(const ppg_material *mat, uint32_t n, const float *wi, const float *sample_xy, float *wo_out, float *weight_out,
                      float *pdf_out, float *eta_out, int32_t *delta_out);
 int ppgo_bsdf_flags(const ppg_material *mat, int32_t *is_smooth, int32_t *all_delta, int32_t *backside_or_transmission);
+/* ppgo_bsdf_sample plus whether the sample is the null component (null_out may be NULL); getType() & ENull of the material */
+int ppgo_bsdf_sample_ex(const ppg_material *mat, uint32_t n, const float *wi, const float *sample_xy, float *wo_out, float *weight_out,
+                        float *pdf_out, float *eta_out, int32_t *delta_out, int32_t *null_out);
+int ppgo_bsdf_has_null(const ppg_material *mat, int32_t *has_null);
 /* D-tree exercise: record `n` (canonical xy, irradiance, weight) samples into a fresh wrapper with the
    given filter / acc mode, build, reset(rho), record again, build; then evaluate pdf at `m` query
    points and draw `m` samples keyed (seed, i).  Outputs node arrays of the final sampling tree. */

@@ -1,9 +1,9 @@
 /*
  * ppg_debug_kernels.h — the kernels of the test hooks (include/ppg_testhooks.h) that run the render's own device functions, included by the
  * k_trace unit of a family (ppg_inst.hip): k_debug_intersect and the kernels of ppg_debug_intersect_mode in the shapes family, which the hooks always use;
- * k_debug_bsdf in the ext family, k_debug_bsdf_coat in the coat family, which ppg_debug_bsdf uses for a scene with a coated material, and
- * k_debug_bsdf_blend in the blend family, which it uses for a scene with a blended one; k_debug_shading_frame in the top (lobes) family, which
- * ppg_debug_shading_frame always uses.  Every family holds k_debug_math_eval and
+ * k_debug_shading_frame in the top (lobes) family, which ppg_debug_shading_frame always uses.  Every family holds its k_debug_bsdf
+ * (ppg_debug_bsdf_as; k_debug_bsdf_base .. k_debug_bsdf_lobes, the ext family's unsuffixed: ppg_debug_bsdf uses that one, or the coat / blend /
+ * lobes family's for a scene that needs it), the base family also k_debug_bsdf_lean; every family holds k_debug_math_eval and
  * k_debug_math_checksum (ppg_debug_math_*): the shared float math as this module compiled it, its own out-of-line dm_ copies included;
  * and k_debug_sample_direct / k_debug_pdf_direct (ppg_debug_sample_direct_as, ppg_debug_pdf_direct): its own copy of the direct-light functions.
  */
@@ -13,6 +13,7 @@
 #include "../../include/ppg_mathcheck.h"
 #include "../../include/ppg_testhooks.h"
 #include "ppg_launch.h"
+#include "ppg_debug_bsdf.h"
 
 #if PPG_FAMILY == PPG_FAMILY_SHAPES
 __global__ void k_debug_intersect(DevScene S, unsigned int n, const float4 *rays, ppg_debug_hit *out, int any) {
@@ -169,44 +170,52 @@ static void launch_debug_intersect(int grid, int block, hipStream_t stream, cons
 }
 #endif
 
-#if PPG_FAMILY >= PPG_FAMILY_EXT
-#if PPG_FAMILY > PPG_FAMILY_EXT
+// ---- ppg_debug_bsdf(_as): the BSDF layer as this family's TRACE unit compiled it, in every family's module ----
+#if PPG_FAMILY == PPG_FAMILY_BASE
+#define k_debug_bsdf k_debug_bsdf_base
+#elif PPG_FAMILY != PPG_FAMILY_EXT
 #define k_debug_bsdf PPG_FAMILY_NAME(k_debug_bsdf)  // (the ext family's is the unsuffixed one)
 #endif
-// ppg_debug_bsdf: the material as shade_one prepares it at a hit with texture coordinates uv, then the render's mat_eval / mat_pdf / mat_sample
+// unit FULL: the material as shade_one prepares it at a hit with texture coordinates uv, then the render's mat_eval / mat_pdf / mat_sample
 __global__ void k_debug_bsdf(DevScene S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out) {
     const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
+    out[i] = debug_bsdf_full(S, items[i]);
+}
+#if PPG_FAMILY == PPG_FAMILY_BASE
+// unit LEAN: the material as the !FULL branch of shade_one loads it — type, no flags, the reflectance — then bsdf_eval / bsdf_pdf /
+// bsdf_sample; eta and the null flag are what shade_one keeps beside them (sampledEta = 1, sampledNull = false)
+__global__ void k_debug_bsdf_lean(DevScene S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out) {
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
     const ppg_debug_bsdf_item it = items[i];
-    Mat M = load_material(S, it.material);
-    const unsigned int tex = __float_as_uint(S.materials[PPG_MAT_STRIDE * (size_t)it.material + 5].x);
-    if (tex & 0xffffu) M.refl = tex_eval(S.textures[(tex & 0xffffu) - 1u], it.uv[0], it.uv[1]);
-    mat_apply_textures(S, it.material, it.uv[0], it.uv[1], M);
-    mat_apply_mfd_textures(S, it.material, it.uv[0], it.uv[1], M);
-#if PPG_BLEND
-    M.bu = it.uv[0]; M.bv = it.uv[1];
-#endif
+    const float4 mat = S.materials[PPG_MAT_STRIDE * (size_t)it.material];
+    const int type = (int)mat.w;
+    const F3 refl = f3(mat.x, mat.y, mat.z);
     const F3 wi = f3(it.wi[0], it.wi[1], it.wi[2]), wo = f3(it.wo[0], it.wo[1], it.wo[2]);
     ppg_debug_bsdf_out r;
     memset(&r, 0, sizeof r);
-    const F3 f = mat_eval(M, wi, wo MAT_SCENE_ARG);
+    const F3 f = bsdf_eval(type, refl, wi, wo);
     r.eval[0] = f.x; r.eval[1] = f.y; r.eval[2] = f.z;
-    r.pdf = mat_pdf(M, wi, wo MAT_SCENE_ARG);
+    r.pdf = bsdf_pdf(type, wi, wo);
     F3 swo;
-    float spdf, seta;
-    bool delta, isnull;
-    unsigned int dim = 0;
-    const F3 w = mat_sample(M, wi, it.sample[0], it.sample[1], swo, spdf, delta, seta, isnull, it.key, dim MAT_SCENE_ARG);
+    float spdf;
+    bool delta;
+    const F3 w = bsdf_sample(type, refl, wi, it.sample[0], it.sample[1], swo, spdf, delta);
     r.wo[0] = swo.x; r.wo[1] = swo.y; r.wo[2] = swo.z;
     r.sampled_pdf = spdf;
     r.weight[0] = w.x; r.weight[1] = w.y; r.weight[2] = w.z;
-    r.eta = seta; r.delta = delta ? 1 : 0; r.is_null = isnull ? 1 : 0;
+    r.eta = 1.0f; r.delta = delta ? 1 : 0;
+    r._pad[0] = debug_bsdf_flag_bits(bsdf_is_smooth(type), type == PPG_BSDF_TWOSIDED_DIFFUSE, false);
     out[i] = r;
 }
-static void launch_debug_bsdf(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out) {
-    hipLaunchKernelGGL(k_debug_bsdf, dim3(grid), dim3(block), 0, stream, S, n, items, out);
-}
 #endif
+static void launch_debug_bsdf(int lean, int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out) {
+#if PPG_FAMILY == PPG_FAMILY_BASE
+    if (lean) { hipLaunchKernelGGL(k_debug_bsdf_lean, dim3(grid), dim3(block), 0, stream, S, n, items, out); return; }
+#endif
+    hipLaunchKernelGGL(k_debug_bsdf, dim3(grid), dim3(block), 0, stream, S, n, items, out);  // (the hook has refused LEAN elsewhere)
+}
 
 #if PPG_FAMILY == PPG_FAMILY_LOBES
 // ppg_debug_shading_frame: the closest hit, then what shade_one does for the frame of a textured BSDF — fill_isect_tex, and bump_frame or
@@ -391,9 +400,7 @@ static void fill_debug_kernels(PathKernels &K) {
     K.debug_trace = launch_debug_trace;
     K.debug_hit_records = launch_debug_hit_records;
 #endif
-#if PPG_FAMILY >= PPG_FAMILY_EXT
     K.debug_bsdf = launch_debug_bsdf;
-#endif
 #if PPG_FAMILY == PPG_FAMILY_LOBES
     K.debug_shading_frame = launch_debug_shading_frame;
 #endif

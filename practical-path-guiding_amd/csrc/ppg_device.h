@@ -1868,6 +1868,7 @@ D float ggx_eval(Mfd d, F3 m) {
     float result;
     if (d.beckmann) {
         result = dm_exp(-beckmannExponent) / (PPG_PI_F * alpha * alpha * cosTheta2 * cosTheta2);
+        if (beckmannExponent > 80.0f) result = 0;  // (fastexp underflows where dm_exp is clamped: see the extended kernels' copy below)
     } else {
         float root = (1.0f + beckmannExponent) * cosTheta2;
         result = 1.0f / (PPG_PI_F * alpha * alpha * root * root);
@@ -1919,6 +1920,11 @@ MFD_CALL float ggx_eval(Mfd d, F3 m) {  // eval, microfacet.h:191-234
     float result;
     if (d.type == MFD_BECKMANN) {
         result = dm_exp(-beckmannExponent) / (PPG_PI_F * d.alphaU * d.alphaV * cosTheta2 * cosTheta2);
+        // math::fastexp (math.h:185-203) underflows towards 0 where dm_exp is clamped to exp(-80) = 1.8e-35 (ppg_detmath.h), and a normal
+        // within 1e-3 of the horizon divides that by cos^4: D came out positive, up to 1e-5 and more, where microfacet.h:203 gives 0.
+        // Beyond the clamp the reference's own value falls under its cut (microfacet.h:230) for every alphaU * alphaV < 1e24: exp(-e) /
+        // (pi aU aV cos^3) >= 1e-20 with e = tan^2 / a^2 > 80 has no solution below that.  So D = 0 there is the reference's answer.
+        if (beckmannExponent > 80.0f) result = 0;
     } else if (d.type == MFD_GGX) {
         float root = (1.0f + beckmannExponent) * cosTheta2;
         result = 1.0f / (PPG_PI_F * d.alphaU * d.alphaV * root * root);

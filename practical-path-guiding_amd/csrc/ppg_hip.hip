@@ -3168,25 +3168,63 @@ int ppg_debug_pdf_direct(ppg_ctx *ctx, int32_t family, uint32_t n, const float *
     return PPG_OK;
 }
 
-int ppg_debug_bsdf(ppg_ctx *ctx, uint32_t n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out) {
-    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
-    if (ctx->renderOpen) { ctx->error = "ppg_debug_bsdf: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
-    if (n && (!items || !out)) { ctx->error = "ppg_debug_bsdf: no arrays"; return PPG_ERR_INVALID; }
-    for (uint32_t i = 0; i < n; ++i)
-        if (items[i].material < 0 || (uint32_t)items[i].material >= ctx->nMaterials) { ctx->error = "ppg_debug_bsdf: item " + std::to_string(i) + ": material out of range"; return PPG_ERR_INVALID; }
+// mat_eval / mat_pdf / mat_sample of kernel family `family` and unit `unit` (both checked by the caller), item by item.  A sample outside
+// [0, 1] is refused: the plug-ins divide it by a probability and hand it to table lookups (the rough-transmittance slice, a blend's cdf).
+static int debugBsdf(ppg_ctx *ctx, const char *who, int family, int unit, uint32_t n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out) {
+    if (n && (!items || !out)) { ctx->error = std::string(who) + ": no arrays"; return PPG_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; ++i) {
+        if (items[i].material < 0 || (uint32_t)items[i].material >= ctx->nMaterials) { ctx->error = std::string(who) + ": item " + std::to_string(i) + ": material out of range"; return PPG_ERR_INVALID; }
+        const float *u = items[i].sample;
+        if (!(u[0] >= 0.0f && u[0] <= 1.0f && u[1] >= 0.0f && u[1] <= 1.0f)) { ctx->error = std::string(who) + ": item " + std::to_string(i) + ": a sample outside [0, 1]"; return PPG_ERR_INVALID; }
+    }
     if (n == 0) return PPG_OK;
     HIP_CHECK(hipSetDevice(ctx->device));
     ctx->quiesce();
+    if (unit == PPG_DEBUG_BSDF_COMMON) {  // what sort_slice keeps out of the common part of a slice (ppg_kernels.h), k_shade<.., MSET_COMMON> never sees
+        std::vector<float4> mats(PPG_MAT_STRIDE * (size_t)ctx->nMaterials);
+        HIP_CHECK(hipMemcpy(mats.data(), ctx->scene.materials, mats.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < n; ++i) {
+            const float4 *mr = mats.data() + PPG_MAT_STRIDE * (size_t)items[i].material;
+            const int type = (int)mr[0].w, flags = ppg_f2u(mr[2].w);
+            const uint32_t tex = ppg_f2u(mr[5].x), slots = ppg_f2u(mr[5].y) | ppg_f2u(mr[5].z) | ppg_f2u(mr[5].w);
+            const char *why = nullptr;
+            if (!(type == PPG_BSDF_DIFFUSE || type == PPG_BSDF_TWOSIDED_DIFFUSE || type == PPG_BSDF_MIRROR || type == PPG_BSDF_CONDUCTOR || type == PPG_BSDF_ROUGHCONDUCTOR ||
+                  type == PPG_BSDF_PLASTIC || type == PPG_BSDF_ROUGHPLASTIC)) why = "its BSDF type is not one of the common classes";
+            else if (flags & PPG_MAT_MASK) why = "a masked material is not in the common classes";
+            else if (slots) why = "a bitmap on specular / alpha / opacity keeps the material out of the common classes";
+            else if (tex >> 16) why = "a bump or normal map keeps the material out of the common classes";
+            if (why) { ctx->error = std::string(who) + ": item " + std::to_string(i) + ": " + why; return PPG_ERR_INVALID; }
+        }
+    }
     DebugBuf dItems, dOut;
     HIP_CHECK(dItems.fill(items, (size_t)n * sizeof(ppg_debug_bsdf_item)));
     HIP_CHECK(dOut.fill(nullptr, (size_t)n * sizeof(ppg_debug_bsdf_out)));
     const unsigned int block = 64;
-    const int family = std::max(sceneFamily(ctx->scene), PPG_FAMILY_EXT);  // (the lowest family that compiles the hook's kernel)
-    launcher(ppg_path_kernels[family].debug_bsdf)((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->scene, n, (const ppg_debug_bsdf_item *)dItems.p, (ppg_debug_bsdf_out *)dOut.p);
+    const int grid = (int)((n + block - 1) / block);
+    if (unit == PPG_DEBUG_BSDF_COMMON) ppg_launch_debug_bsdf_common(grid, (int)block, ctx->stream, ctx->scene, n, (const ppg_debug_bsdf_item *)dItems.p, (ppg_debug_bsdf_out *)dOut.p);
+    else launcher(ppg_path_kernels[family].debug_bsdf)(unit == PPG_DEBUG_BSDF_LEAN ? 1 : 0, grid, (int)block, ctx->stream, ctx->scene, n, (const ppg_debug_bsdf_item *)dItems.p, (ppg_debug_bsdf_out *)dOut.p);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_bsdf_out), hipMemcpyDeviceToHost));
     return PPG_OK;
+}
+int ppg_debug_bsdf_as(ppg_ctx *ctx, int32_t family, int32_t unit, uint32_t n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out) {
+    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
+    if (ctx->renderOpen) { ctx->error = "ppg_debug_bsdf_as: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    int fam = 0;
+    if (const int rc = debugFamily(ctx, "ppg_debug_bsdf_as", family, &fam)) return rc;
+    if (family < 0) unit = ctx->fullMaterials ? PPG_DEBUG_BSDF_FULL : PPG_DEBUG_BSDF_LEAN;
+    if (unit != PPG_DEBUG_BSDF_FULL && unit != PPG_DEBUG_BSDF_LEAN && unit != PPG_DEBUG_BSDF_COMMON) { ctx->error = "ppg_debug_bsdf_as: no such unit"; return PPG_ERR_INVALID; }
+    if (unit == PPG_DEBUG_BSDF_LEAN && fam != PPG_FAMILY_BASE) { ctx->error = "ppg_debug_bsdf_as: the LEAN functions exist in the base family only"; return PPG_ERR_INVALID; }
+    if (unit == PPG_DEBUG_BSDF_COMMON && fam != PPG_FAMILY_BASE) { ctx->error = "ppg_debug_bsdf_as: the COMMON unit exists in the base family only"; return PPG_ERR_INVALID; }
+    if (unit == PPG_DEBUG_BSDF_LEAN && ctx->fullMaterials) { ctx->error = "ppg_debug_bsdf_as: the scene needs the FULL kernels"; return PPG_ERR_INVALID; }
+    return debugBsdf(ctx, "ppg_debug_bsdf_as", fam, unit, n, items, out);
+}
+int ppg_debug_bsdf(ppg_ctx *ctx, uint32_t n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out) {
+    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
+    if (ctx->renderOpen) { ctx->error = "ppg_debug_bsdf: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    const int family = std::max(sceneFamily(ctx->scene), PPG_FAMILY_EXT);  // (as before the base and shapes families compiled the hook's kernel)
+    return debugBsdf(ctx, "ppg_debug_bsdf", family, PPG_DEBUG_BSDF_FULL, n, items, out);
 }
 
 // include/ppg_mathcheck.h in one family's TRACE unit, or (family = -1) in this translation unit's host code; no scene is needed

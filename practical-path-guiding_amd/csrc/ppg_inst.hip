@@ -6,7 +6,8 @@
  *                            top family, those of ppg_render_fields (ppg_fields_kernels.h)
  * A family above the base is three such units: its scenes are FULL and never SMALL.  The base family splits the first two further, one
  * -DPPG_UNIT_PART=p per unit (k_shade: p = NEE; k_tail: p = SMALL * 2 + NEE; both FULL settings each), and has two units outside the families:
- *   -DPPG_UNIT_SHADE_COMMON  k_shade<false, true, MSET_COMMON>: the common material classes of a FULL scene
+ *   -DPPG_UNIT_SHADE_COMMON  k_shade<false, true, MSET_COMMON>: the common material classes of a FULL scene; k_debug_bsdf_common, the
+ *                            test hook's kernel over this unit's copy of the BSDF layer (ppg_debug_bsdf.h)
  *   -DPPG_UNIT_COMMIT        k_commit (all six), k_commit_records and k_splat_sorted
  * The unit enters its launchers into its family's row of ppg_path_kernels when the library is loaded.
  */
@@ -76,8 +77,19 @@ PPG_FILL_ROW {
     fill_fields_kernels(ROW);
 }
 #elif defined(PPG_UNIT_SHADE_COMMON)
+#include "ppg_debug_bsdf.h"
 void ppg_launch_shade_common(const ShadeLaunch &a) {
     hipLaunchKernelGGL((k_shade<false, true, MSET_COMMON>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, a.P, a.S, a.T, a.R, a.Q, a.qin, a.small_scene, a.sorted_items);
+}
+// ppg_debug_bsdf_as, unit COMMON: this unit's mat_eval / mat_pdf / mat_sample, item by item (the host has refused what sort_slice keeps out
+// of the common part)
+__global__ void k_debug_bsdf_common(DevScene S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out) {
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = debug_bsdf_full(S, items[i]);
+}
+void ppg_launch_debug_bsdf_common(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out) {
+    hipLaunchKernelGGL(k_debug_bsdf_common, dim3(grid), dim3(block), 0, stream, S, n, items, out);
 }
 #elif defined(PPG_UNIT_COMMIT)
 void ppg_launch_commit(int sf, int df, const CommitLaunch &a) {

@@ -104,11 +104,10 @@ struct PathKernels {
     void (*tail[4])(int variant, const TailLaunch &a);    // [SMALL * 2 + NEE]; variant = (SMALL ? 4 : 0) | (NEE ? 2 : 0) | (FULL ? 1 : 0)
     void (*trace)(const TraceLaunch &a);
     // The kernels of the test hooks (ppg_debug_kernels.h), in the families that compile them: the shapes family those of ppg_debug_intersect,
-    // the families from ext on that of ppg_debug_bsdf, the top family that of ppg_debug_shading_frame
+    // the top family that of ppg_debug_shading_frame
     void (*debug_intersect)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_hit *out, int any);
     void (*debug_trace)(int mode, int param, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_hit *out, unsigned int *stats);
     void (*debug_hit_records)(hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, const float4 *hits, ppg_debug_hit *out);
-    void (*debug_bsdf)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out);
     void (*debug_shading_frame)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, ppg_debug_frame *out);
     // the top family: the kernels of ppg_render_fields (ppg_fields_kernels.h), which know every material and shape a scene may hold
     void (*fields_sample)(const FieldsSampleLaunch &a);
@@ -120,12 +119,16 @@ struct PathKernels {
     void (*debug_sample_direct)(int full, int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float *ref, const float *ref_n,
                                 const float *u, ppg_debug_direct_ex *out);
     void (*debug_pdf_direct)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, const float *ref_n, ppg_debug_pdf *out);
+    // every family: its copy of mat_eval / mat_pdf / mat_sample (lean != 0: bsdf_eval / bsdf_pdf / bsdf_sample, the base family only)
+    void (*debug_bsdf)(int lean, int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out);
 };
 extern PathKernels ppg_path_kernels[PPG_FAMILIES];
 
 // The kernels outside the families, each defined in the unit that compiles it.
 // k_shade<false, FULL, MSET_COMMON> over the front part of the sorted slices (a.qin = QIN_SORTED_COMMON)
 void ppg_launch_shade_common(const ShadeLaunch &a);
+// ppg_debug_bsdf_as, unit COMMON: mat_eval / mat_pdf / mat_sample as that unit compiled them (PPG_PARAM_TEXTURES = 0)
+void ppg_launch_debug_bsdf_common(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out);
 void ppg_launch_commit(int spatial_filter, int directional_filter, const CommitLaunch &a);
 // a round of the optimiser: k_commit_records (nearest / stochastic spatial filter), then — after the sort — k_splat_sorted
 void ppg_launch_commit_records(int spatial_filter, const CommitLaunch &a);

@@ -1030,6 +1030,19 @@ class Engine:
         self._call("debug_bsdf", C.c_uint32(n), items.ctypes.data_as(C.POINTER(DebugBsdfItem)), out.ctypes.data_as(C.POINTER(DebugBsdfOut)))
         return out
 
+    DEBUG_BSDF_UNITS = {"FULL": 0, "LEAN": 1, "COMMON": 2}
+
+    def debug_bsdf_as(self, items, family=-1, unit="FULL"):
+        """ppg_debug_bsdf_as (include/ppg_testhooks.h): `items` (a DEBUG_BSDF_ITEM_DTYPE array, in one launch) through the BSDF layer as kernel
+        family `family` (-1: what a render of the scene would run) and unit FULL / LEAN / COMMON compiled it; a structured array
+        (DEBUG_BSDF_OUT_DTYPE) whose _pad[0] carries the smooth / backside-or-transmission / has-null bits."""
+        items = np.ascontiguousarray(items, DEBUG_BSDF_ITEM_DTYPE)
+        out = np.zeros(len(items), DEBUG_BSDF_OUT_DTYPE)
+        assert items.itemsize == C.sizeof(DebugBsdfItem) and out.itemsize == C.sizeof(DebugBsdfOut)
+        self._call("debug_bsdf_as", C.c_int32(int(family)), C.c_int32(int(self.DEBUG_BSDF_UNITS.get(unit, unit))), C.c_uint32(len(items)),
+                   items.ctypes.data_as(C.POINTER(DebugBsdfItem)), out.ctypes.data_as(C.POINTER(DebugBsdfOut)))
+        return out
+
     def debug_math_eval(self, family, via, op, a, b=None):
         """ppg_debug_math_eval (include/ppg_testhooks.h): op of include/ppg_mathcheck.h on the bit patterns a, b (float32 or uint32 arrays),
         in kernel family `family`'s module (-1: the library's host code), via 0 the header's functions or 1 the module's dm_ copies.
