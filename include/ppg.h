@@ -562,6 +562,63 @@ typedef struct ppg_blend {
 int ppg_set_blends(ppg_ctx *ctx, const ppg_blend *b, uint32_t n_materials);
 
 /* ------------------------------------------------------------------------------------------------
+ * Homogeneous participating media (medium/homogeneous.cpp) with the `isotropic` and `hg` phase functions (phase/isotropic.cpp, hg.cpp):
+ * the medium branch of GuidedPathTracer::Li (GP:1803-1893), its failure factor (GP:1899-1911), the medium carried through surface
+ * bounces (GP:2041-2042), shadow segments (Scene::evalTransmittance, scene.cpp:619-679) and the search for an emitter behind null
+ * surfaces (GP:2184-2245).  The SD-tree guides at surfaces only: a medium event makes no vertex and looks up no D-tree, and the radiance
+ * found behind it is recorded into the surface vertices in front of it.
+ * One more side list, with the ordering rules of the others: call before ppg_set_scene, which validates and consumes it; the context
+ * keeps it until it is replaced (NULL or n_media = 0 clears it, and a cleared list renders exactly as a fresh context does);
+ * PPG_ERR_STATE between ppg_begin_render and ppg_end_render.
+ *   media          the media.  sigma_a, sigma_s are Mitsuba's sigmaA, sigmaS AFTER `scale` (sigmaT + albedo: sigma_s = sigmaT * albedo,
+ *                  sigma_a = sigmaT - sigma_s, medium.cpp); sigmaT = sigma_a + sigma_s is derived inside ppg_set_scene
+ *   strategy       PPG_MEDIUM_BALANCE (a second random number picks the channel whose sigmaT is the sampling density), _SINGLE
+ *                  (sampling density = sigmaT[channel]; channel < 0: the channel with the smallest sigmaT) or _MANUAL (sampling_density)
+ *   sampling_weight  mediumSamplingWeight in [0, 1], or -1: derive it — the highest albedo over the channels with sigmaT != 0, raised to
+ *                  at least 0.5 when it is positive (homogeneous.cpp:168-184); a pure absorber gets 0 and never scatters
+ *   phase, g       PPG_PHASE_ISOTROPIC, or PPG_PHASE_HG with g in (-1, 1)
+ * A binding word names the media on the two sides of a primitive: low 16 bits = 1 + the interior medium, high 16 bits = 1 + the exterior
+ * medium, 0 = none (Shape::m_interiorMedium / m_exteriorMedium); a word other than 0 makes the primitive a medium transition
+ * (Intersection::isMediumTransition), at which a path that leaves along d continues in the exterior medium when dot(d, geometric normal)
+ * > 0, else in the interior one (getTargetMedium).  tri_media, sphere_media, shape_media: one word per triangle, per ppg_scene.spheres
+ * entry, per ppg_set_shapes entry; NULL = all 0.  camera_medium: 1 + the medium the sensor lies in, 0 = none.
+ * Random numbers, per medium event, in the reference's order: sampleDistance 1 (+ 1 under balance when the first falls below the
+ * sampling weight), the emitter sample 2, the phase sample 2, Russian roulette 1.  exp / log are include/ppg_detmath.h's.
+ * ppg_set_scene returns PPG_ERR_INVALID, names the entry in ppg_last_error and leaves the previous scene set for: more than 65535 media;
+ * binding counts that differ from the scene's (n_tri_media / n_sphere_media / n_shape_media against n_triangles, n_spheres and the
+ * ppg_set_shapes list, each checked when its array is given); a medium index out of range; a coefficient that is negative or not finite;
+ * an unknown strategy or phase; channel > 2; g outside (-1, 1); sampling_density <= 0 or not finite under manual; sampling_weight
+ * outside [0, 1] and not -1; a non-zero reserved word.
+ * A scene with a media list that binds at least one medium (a non-zero word or camera_medium) runs the "media" kernels (csrc:
+ * PPG_MEDIA), whatever else it holds; a list without a binding renders exactly as no list does.  Sharded renders (ppg_set_shard with
+ * world > 1) refuse such a scene.  ppg_render_fields does not see media (Mitsuba's field integrator does not).  The CPU oracle does not
+ * know media: they are pinned against a float64 restatement item by item, by reduction and by closed forms.
+ * ---------------------------------------------------------------------------------------------- */
+enum { PPG_MEDIUM_BALANCE = 0, PPG_MEDIUM_SINGLE = 1, PPG_MEDIUM_MANUAL = 2 };
+enum { PPG_PHASE_ISOTROPIC = 0, PPG_PHASE_HG = 1 };
+typedef struct ppg_medium {
+    float sigma_a[3], sigma_s[3]; /* already scaled                                                  offset  0, 12 */
+    int32_t strategy;             /* PPG_MEDIUM_*                                                            24 */
+    int32_t channel;              /* single: 0..2, or < 0 = the channel with the smallest sigmaT              28 */
+    float sampling_density;       /* manual                                                                  32 */
+    float sampling_weight;        /* [0, 1], or -1 = derive                                                  36 */
+    int32_t phase;                /* PPG_PHASE_*                                                             40 */
+    float g;                      /* hg                                                                      44 */
+    uint32_t _reserved[4];        /* must be 0                                                               48 */
+} ppg_medium;                     /* 64 bytes */
+typedef struct ppg_media {
+    uint32_t n_media;
+    uint32_t camera_medium;       /* 1 + index, 0 = none */
+    const ppg_medium *media;      /* [n_media] */
+    uint32_t n_tri_media, n_sphere_media, n_shape_media;  /* entries of the three arrays below (ignored where the array is NULL) */
+    uint32_t _reserved;           /* must be 0 */
+    const uint32_t *tri_media;    /* [n_triangles] or NULL */
+    const uint32_t *sphere_media; /* [n_spheres] or NULL */
+    const uint32_t *shape_media;  /* [entries of ppg_set_shapes] or NULL */
+} ppg_media;
+int ppg_set_media(ppg_ctx *ctx, const ppg_media *media);
+
+/* ------------------------------------------------------------------------------------------------
  * Rendering.  ppg_render() is GuidedPathTracer::render() (GP:1516-1585, IH:74-75) in one call.
  * The stepwise calls expose its phases so a multi-GPU driver can all-reduce the SD-tree statistics
  * between ppg_render_passes() and ppg_build_sdtree(); ppg_render() is exactly their composition

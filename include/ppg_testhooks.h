@@ -322,6 +322,28 @@ int ppg_debug_commit(struct ppg_ctx *ctx, const struct ppg_debug_commit_in *in, 
 #define PPG_STREE_MAX_DEPTH 94
 int ppg_debug_stree_depth(const uint32_t *children, uint32_t n_nodes, int32_t spatial_filter, uint32_t *depth);
 
+/* The media family's device functions (csrc/ppg_device.h: medium_sample_distance, medium_transmittance, phase_sample, phase_eval), item by
+   item, over the media of the scene that is set — which must bind a medium (include/ppg.h ppg_set_media), else PPG_ERR_STATE.  Per item:
+   HomogeneousMedium::sampleDistance on a ray that starts at the origin, runs along -wi and ends after `length` (may be infinite), with
+   u[0] as its first random number and u[1] as the second one where it draws one; evalTransmittance over `length`; the phase function's
+   sample with (u[2], u[3]) for wi, its value and its density for the sampled direction.  t is the sampled distance as sampleDistance leaves
+   it: the distance of the medium event, or `length` on failure.  PPG_ERR_INVALID: a medium index out of range, a u outside [0, 1]. */
+struct ppg_debug_medium_item {
+    int32_t medium;
+    float length;
+    float wi[3];
+    float u[4];
+};                                /* 36 bytes */
+struct ppg_debug_medium_out {
+    int32_t success;
+    float t, pdf_success, pdf_failure;
+    float transmittance[3];       /* mRec.transmittance */
+    float eval_transmittance[3];
+    float wo[3];
+    float phase_eval, phase_pdf;
+};                                /* 60 bytes */
+int ppg_debug_medium(struct ppg_ctx *ctx, uint32_t n, const struct ppg_debug_medium_item *items, struct ppg_debug_medium_out *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -389,6 +389,36 @@ static void launch_debug_math_checksum(hipStream_t stream, int via, int op, unsi
     else hipLaunchKernelGGL((k_debug_math_checksum<0>), grid, block, 0, stream, op, first_block, n_blocks, out);
 }
 
+#if PPG_FAMILY == PPG_FAMILY_MEDIA
+// ppg_debug_medium: medium_sample_distance, medium_transmittance, phase_sample and phase_eval as this family's kernels compile them, item by
+// item.  The ray starts at the origin and runs along -wi; u[0], u[1] feed sampleDistance (u[1] only where it draws a second number),
+// u[2], u[3] the phase sample.
+__global__ void k_debug_medium(MediaArgs M, unsigned int n, const ppg_debug_medium_item *items, ppg_debug_medium_out *out) {
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const ppg_debug_medium_item it = items[i];
+    const float4 *Q = medium_record(M.media, (unsigned int)it.medium + 1u);
+    const F3 wi = f3(it.wi[0], it.wi[1], it.wi[2]);
+    ppg_debug_medium_out r;
+    memset(&r, 0, sizeof r);
+    MediumSample ms;
+    int drawn = 0;
+    r.success = medium_sample_distance(Q, f3s(0.0f), -wi, it.length, [&]() { return it.u[drawn++ ? 1 : 0]; }, ms) ? 1 : 0;
+    r.t = ms.t; r.pdf_success = ms.pdfSuccess; r.pdf_failure = ms.pdfFailure;
+    r.transmittance[0] = ms.transmittance.x; r.transmittance[1] = ms.transmittance.y; r.transmittance[2] = ms.transmittance.z;
+    const F3 tr = medium_transmittance(Q, it.length);
+    r.eval_transmittance[0] = tr.x; r.eval_transmittance[1] = tr.y; r.eval_transmittance[2] = tr.z;
+    F3 wo;
+    r.phase_pdf = phase_sample(Q, wi, it.u[2], it.u[3], wo);
+    r.wo[0] = wo.x; r.wo[1] = wo.y; r.wo[2] = wo.z;
+    r.phase_eval = phase_eval(Q, wi, wo);
+    out[i] = r;
+}
+static void launch_debug_medium(int grid, int block, hipStream_t stream, const MediaArgs &M, unsigned int n, const ppg_debug_medium_item *items, ppg_debug_medium_out *out) {
+    hipLaunchKernelGGL(k_debug_medium, dim3(grid), dim3(block), 0, stream, M, n, items, out);
+}
+#endif
+
 // the hooks' launchers of this family, into its row
 static void fill_debug_kernels(PathKernels &K) {
     K.debug_math_eval = launch_debug_math_eval;
@@ -403,6 +433,9 @@ static void fill_debug_kernels(PathKernels &K) {
     K.debug_bsdf = launch_debug_bsdf;
 #if PPG_FAMILY == PPG_FAMILY_LOBES
     K.debug_shading_frame = launch_debug_shading_frame;
+#endif
+#if PPG_FAMILY == PPG_FAMILY_MEDIA
+    K.debug_medium = launch_debug_medium;
 #endif
 }
 

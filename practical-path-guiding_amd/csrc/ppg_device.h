@@ -38,13 +38,16 @@
 #define PPG_FAMILY_BLEND 4   // _blend    the blendbsdf / mixturebsdf combinators (ppg_set_blends), whatever else the scene holds
 #define PPG_FAMILY_LOBES 5   // _lobes    the roughdiffuse, difftrans and phong BSDFs (PPG_BSDF_ROUGHDIFFUSE ..), whatever else the scene holds; being the top
                              //           family it also compiles the normalmap adapter and the null BSDF (PPG_NORMALMAP_NULL)
-#define PPG_FAMILIES 6
+#define PPG_FAMILY_MEDIA 6   // _media    homogeneous participating media (ppg_set_media with a binding), whatever else the scene holds: now the top family
+#define PPG_FAMILIES 7
+#define PPG_DEBUG_FAMILIES 6  // the families whose copies the item-by-item test hooks address by number (the media family adds nothing to that code)
 #define PPG_SUFFIX_0
 #define PPG_SUFFIX_1 _shapes
 #define PPG_SUFFIX_2 _ext
 #define PPG_SUFFIX_3 _coat
 #define PPG_SUFFIX_4 _blend
 #define PPG_SUFFIX_5 _lobes
+#define PPG_SUFFIX_6 _media
 #ifndef PPG_FAMILY
 #define PPG_FAMILY 0  // (a digit: it is pasted to PPG_SUFFIX_)
 #endif
@@ -53,6 +56,7 @@
 #define PPG_COAT (PPG_FAMILY >= PPG_FAMILY_COAT)
 #define PPG_BLEND (PPG_FAMILY >= PPG_FAMILY_BLEND)
 #define PPG_LOBES (PPG_FAMILY >= PPG_FAMILY_LOBES)
+#define PPG_MEDIA (PPG_FAMILY >= PPG_FAMILY_MEDIA)
 // the normalmap adapter (PPG_MAT_NORMALMAP) and the null BSDF (PPG_BSDF_NULL): no family of their own — the top family, which holds
 // everything below it, compiles them, and sceneFamily sends a scene with either there
 #define PPG_NORMALMAP_NULL (PPG_FAMILY >= PPG_FAMILY_LOBES)
@@ -237,6 +241,32 @@ struct DevScene {
     // specularSamplingWeight, PPG_COATF_* bits), (sigmaA, alpha), (specularReflectance, rough-transmittance slice as int); nullptr otherwise
     const float4 *coat;
 };
+// ppg_set_media with a binding: what the media kernels (PPG_MEDIA) get on top of DevScene and PathState.  The kernels of the other families
+// keep their arguments — and with them their code — as they are: the host carries this record beside the scene (ppg_launch.h), and the
+// launchers of the media family append it to the two structs (SceneArg here, PathArg in ppg_kernels.h).
+//   media       PPG_MEDIUM_STRIDE float4 per medium = (sigmaS, mediumSamplingWeight) (sigmaT, samplingDensity) (g, strategy, phase, -)
+//   prim_media  one binding word per primitive — triangles in LEAF order, then the spheres, then the shapes —: low 16 bits = 1 + interior
+//               medium, high 16 bits = 1 + exterior medium, 0 = no transition
+//   camera_medium  1 + the medium the sensor lies in, 0 = none
+//   path_medium, path_stride  the paths' medium words (PathArg::medium); nullptr everywhere: the scene binds no medium
+struct MediaArgs {
+    const float4 *media;
+    const unsigned int *prim_media;
+    unsigned int camera_medium;
+    int n_media;
+    unsigned int *path_medium;
+    unsigned int path_stride;
+};
+#if PPG_MEDIA
+struct DevSceneMedia : DevScene {
+    const float4 *media;
+    const unsigned int *prim_media;
+};
+typedef DevSceneMedia SceneArg;
+#else
+typedef DevScene SceneArg;
+#endif
+#define PPG_MEDIUM_STRIDE 3
 #define PPG_BLEND_STRIDE 4
 #define PPG_BLENDW_CHILD 0        // word offsets into a material's 16 words
 #define PPG_BLENDW_WEIGHT 4
@@ -1498,6 +1528,132 @@ D float emitter_pdf_direct(const DevScene &S, int em_id, F3 d, F3 em_n, float em
     }
     return pdfDirect;
 }
+
+#if PPG_MEDIA
+// ------------------------------------------------------------------------------------------------
+// Homogeneous media (medium/homogeneous.cpp) and their phase functions (phase/isotropic.cpp, hg.cpp), restated.  A medium is
+// PPG_MEDIUM_STRIDE float4 of DevScene::media.  math::fastexp / fastlog and Spectrum::exp are the deterministic dm_exp / dm_log.
+// ------------------------------------------------------------------------------------------------
+// exp of a non-positive argument: the deterministic exp clamps its argument at -80, so what lies beyond is flushed to zero here — an
+// infinite segment through a medium is opaque, as in the reference; NaN (0 * inf: a channel without extinction over an infinite
+// segment, homogeneous.cpp:326, 344) stays NaN, as there
+D float medium_exp(float x) {
+    if (x != x) return x;
+    if (x < -80.0f) return 0.0f;
+    return dm_exp(x);
+}
+D const float4 *medium_record(const float4 *media, unsigned int med) { return media + PPG_MEDIUM_STRIDE * (size_t)(med - 1u); }  // med = 1 + index
+// HomogeneousMedium::evalTransmittance (homogeneous.cpp:266-273) over a segment of the given length (ray.maxt - ray.mint)
+D F3 medium_transmittance(const float4 *Q, float length) {
+    const float4 q1 = Q[1];
+    const float negLength = -length;
+    return f3(q1.x != 0 ? medium_exp(q1.x * negLength) : 1.0f, q1.y != 0 ? medium_exp(q1.y * negLength) : 1.0f, q1.z != 0 ? medium_exp(q1.z * negLength) : 1.0f);
+}
+struct MediumSample {
+    float t, pdfSuccess, pdfFailure;
+    F3 transmittance, sigmaS;
+};
+// HomogeneousMedium::sampleDistance (homogeneous.cpp:275-352) on the ray (o, d) with mint = 0 and maxt = distSurf; next() is the sampler's
+// next1D().  ms.t is sampledDistance as the function leaves it (the distance to the surface on failure).
+template <typename Next>
+D bool medium_sample_distance(const float4 *Q, F3 o, F3 d, float distSurf, Next next, MediumSample &ms) {
+    const float4 q0 = Q[0], q1 = Q[1];
+    const int strategy = __float_as_int(Q[2].y);
+    const F3 sigmaT = f3(q1.x, q1.y, q1.z);
+    const float weight = q0.w;
+    float rand = next(), sampledDistance, samplingDensity = q1.w;
+    if (rand < weight) {
+        rand /= weight;
+        if (strategy == PPG_MEDIUM_BALANCE) {
+            const int channel = min((int)(next() * 3), 2);
+            samplingDensity = comp3(sigmaT, channel);
+        }
+        sampledDistance = -dm_log(1 - rand) / samplingDensity;
+    } else {
+        sampledDistance = __builtin_inff();
+    }
+    bool success = true;
+    if (sampledDistance < distSurf) {
+        const F3 p = o + d * sampledDistance;
+        if (p.x == o.x && p.y == o.y && p.z == o.z) success = false;  // no forward progress
+    } else {
+        sampledDistance = distSurf;
+        success = false;
+    }
+    float pdfFailure, pdfSuccess;
+    if (strategy == PPG_MEDIUM_BALANCE) {
+        pdfFailure = 0; pdfSuccess = 0;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const float tmp = medium_exp(-comp3(sigmaT, i) * sampledDistance);
+            pdfFailure += tmp;
+            pdfSuccess += comp3(sigmaT, i) * tmp;
+        }
+        pdfFailure /= 3;
+        pdfSuccess /= 3;
+    } else {
+        pdfFailure = medium_exp(-samplingDensity * sampledDistance);
+        pdfSuccess = samplingDensity * pdfFailure;
+    }
+    F3 tr = f3(medium_exp(sigmaT.x * -sampledDistance), medium_exp(sigmaT.y * -sampledDistance), medium_exp(sigmaT.z * -sampledDistance));
+    ms.pdfSuccess = pdfSuccess * weight;
+    ms.pdfFailure = weight * pdfFailure + (1 - weight);
+    if (max3(tr) < 1e-20f) tr = f3s(0.0f);
+    ms.transmittance = tr;
+    ms.sigmaS = f3(q0.x, q0.y, q0.z);
+    ms.t = sampledDistance;
+    return success;
+}
+// PhaseFunction::eval: isotropic (warp::squareToUniformSpherePdf) or Henyey-Greenstein (hg.cpp:107-110); wi points back along the ray
+D float phase_eval(const float4 *Q, F3 wi, F3 wo) {
+    const float4 q2 = Q[2];
+    const float INV_FOURPI = 0.07957747154594766788f;
+    if (__float_as_int(q2.z) == PPG_PHASE_ISOTROPIC) return INV_FOURPI;
+    const float g = q2.x;
+    const float temp = 1.0f + g * g + 2.0f * g * dot3(wi, wo);
+    return INV_FOURPI * (1 - g * g) / (temp * __builtin_sqrtf(temp));
+}
+// PhaseFunction::sample(pRec, pdf, sampler) with the 2-D sample (sx, sy): the value is 1, the density is returned (isotropic.cpp:69-74,
+// warp.cpp:25-31; hg.cpp:74-105 with Frame(-wi), util.cpp:592-601)
+D float phase_sample(const float4 *Q, F3 wi, float sx, float sy, F3 &wo) {
+    const float4 q2 = Q[2];
+    if (__float_as_int(q2.z) == PPG_PHASE_ISOTROPIC) {
+        const float z = 1.0f - 2.0f * sy;
+        const float r = __builtin_sqrtf(ppg_max(0.0f, 1.0f - z * z));
+        float sinPhi, cosPhi;
+        dm_sincos(2.0f * PPG_PI_F * sx, &sinPhi, &cosPhi);
+        wo = f3(r * cosPhi, r * sinPhi, z);
+        return 0.07957747154594766788f;
+    }
+    const float g = q2.x;
+    float cosTheta;
+    if (ppg_abs(g) < PPG_EPSILON) {
+        cosTheta = 1 - 2 * sx;
+    } else {
+        const float sqrTerm = (1 - g * g) / (1 - g + 2 * g * sx);
+        cosTheta = (1 + g * g - sqrTerm * sqrTerm) / (2 * g);
+    }
+    const float sinTheta = __builtin_sqrtf(ppg_max(0.0f, 1.0f - cosTheta * cosTheta));
+    float sinPhi, cosPhi;
+    dm_sincos(2 * PPG_PI_F * sy, &sinPhi, &cosPhi);
+    const F3 a = -wi;
+    F3 b, c;
+    if (ppg_abs(a.x) > ppg_abs(a.y)) {
+        const float invLen = 1.0f / __builtin_sqrtf(a.x * a.x + a.z * a.z);
+        c = f3(a.z * invLen, 0.0f, -a.x * invLen);
+    } else {
+        const float invLen = 1.0f / __builtin_sqrtf(a.y * a.y + a.z * a.z);
+        c = f3(0.0f, a.z * invLen, -a.y * invLen);
+    }
+    b = cross3(c, a);
+    wo = b * (sinTheta * cosPhi) + c * (sinTheta * sinPhi) + a * cosTheta;
+    return phase_eval(Q, wi, wo);
+}
+// Intersection::isMediumTransition / getTargetMedium (shape.h): the medium (1 + index, 0 = none) a path continues in when it leaves
+// primitive `prim` along d — the exterior one when dot(d, geometric normal) > 0, else the interior one; `word` = 0: no transition
+D unsigned int medium_target(unsigned int word, F3 d, F3 geoN) { return dot3(d, geoN) > 0 ? (word >> 16) : (word & 0xffffu); }
+D unsigned int medium_word(const DevSceneMedia &S, int prim) { return S.prim_media ? S.prim_media[prim] : 0u; }
+#endif
 
 // Transform::operator()(Point) (transform.h:108-125) and operator()(Vector) (:175-183)
 D F3 xf_point(const float *m, F3 p) {

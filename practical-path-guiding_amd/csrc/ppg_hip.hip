@@ -365,6 +365,14 @@ struct ppg_ctx {
     DevBuf<float4> d_coat;
     std::vector<ppg_blend> blends;  // ppg_set_blends: kept until replaced; ppg_set_scene validates it and builds d_blend from it
     DevBuf<float4> d_blend;
+    // ppg_set_media: kept until replaced (mediaList points into the four vectors; n_media = 0: none); ppg_set_scene validates it and builds
+    // d_media and d_primMedia from it.  d_pathMedium: PathState::medium of a scene that binds a medium
+    ppg_media mediaList{};
+    std::vector<ppg_medium> media;
+    std::vector<uint32_t> triMedia, sphereMedia, shapeMedia;
+    DevBuf<float4> d_media;
+    DevBuf<unsigned int> d_primMedia, d_pathMedium;
+    MediaArgs mediaArgs{};         // of the scene that is set: what the media kernels get beside it (all zero: the scene binds no medium)
     uint32_t nMaterials = 0;       // of the scene set last (ppg_debug_bsdf checks its items against it)
     bool renderOpen = false;       // between ppg_begin_render and ppg_end_render
     int W = 0, H = 0;
@@ -552,7 +560,8 @@ struct ppg_ctx {
 PathKernels ppg_path_kernels[PPG_FAMILIES];  // filled by the units of ppg_inst.hip when the library is loaded
 
 // The kernel family a scene runs: the lowest that has everything the scene needs (ppg_device.h).
-static int sceneFamily(const DevScene &S) {
+static int sceneFamily(const DevScene &S, const MediaArgs &M) {
+    if (M.media) return PPG_FAMILY_MEDIA;      // a medium is bound to a primitive or to the camera: the top family, whatever else the scene holds
     if (S.lobes) return PPG_FAMILY_LOBES;      // a roughdiffuse, difftrans or phong material, a normal-mapped or a null one: the top family, whatever else the scene holds
     if (S.blend) return PPG_FAMILY_BLEND;      // a blended material: the blend family, whatever else the scene holds
     if (S.coat) return PPG_FAMILY_COAT;        // a coated material: the coat family, shapes and general entries or not
@@ -566,12 +575,12 @@ template <typename F> static F launcher(F f) {
     return f;
 }
 // variant = (NEE ? 2 : 0) | (FULL ? 1 : 0)
-static void ppg_launch_shade(int variant, const ShadeLaunch &a) { launcher(ppg_path_kernels[sceneFamily(a.S)].shade[variant >> 1])(variant, a); }
+static void ppg_launch_shade(int variant, const ShadeLaunch &a) { launcher(ppg_path_kernels[sceneFamily(a.S, a.M)].shade[variant >> 1])(variant, a); }
 // variant = (SMALL ? 4 : 0) | (NEE ? 2 : 0) | (FULL ? 1 : 0)
-static void ppg_launch_tail(int variant, const TailLaunch &a) { launcher(ppg_path_kernels[sceneFamily(a.S)].tail[variant >> 1])(variant, a); }
+static void ppg_launch_tail(int variant, const TailLaunch &a) { launcher(ppg_path_kernels[sceneFamily(a.S, a.M)].tail[variant >> 1])(variant, a); }
 // the scene is traced from LDS without a BVH (k_trace<true>, k_tail<true, ..>)
 static bool isSmallScene(const ppg_ctx *ctx) {
-    return ctx->scene.n_tris <= 64 && ctx->ldsTris == ctx->scene.n_tris && ctx->scene.n_spheres == 0 && sceneFamily(ctx->scene) == PPG_FAMILY_BASE && !ctx->tuneForceBvh;
+    return ctx->scene.n_tris <= 64 && ctx->ldsTris == ctx->scene.n_tris && ctx->scene.n_spheres == 0 && sceneFamily(ctx->scene, ctx->mediaArgs) == PPG_FAMILY_BASE && !ctx->tuneForceBvh;
 }
 namespace {
 
@@ -867,7 +876,8 @@ int allocPaths(ppg_ctx *ctx) {
     ctx->queues.n_common = nullptr;
     if (ctx->fullMaterials && !ctx->tuneNoSort) {
         HIP_CHECK(ctx->d_queueSorted.reserve(cap * nb)); HIP_CHECK(ctx->d_sortKeys.reserve(cap * nb));
-        if (!ctx->tuneNoSplit) { HIP_CHECK(ctx->d_qcommon.reserve(nb)); ctx->queues.n_common = ctx->d_qcommon.p; }
+        // (not with media: the kernel of the common classes lies outside the families and knows no medium branch)
+        if (!ctx->tuneNoSplit && !ctx->mediaArgs.media) { HIP_CHECK(ctx->d_qcommon.reserve(nb)); ctx->queues.n_common = ctx->d_qcommon.p; }
     }
     size_t nv = nTrain * (size_t)ctx->maxVertices;
     const bool filtered = ctx->spatialFilter != SF_NEAREST;
@@ -890,6 +900,8 @@ int allocPaths(ppg_ctx *ctx) {
     }
     P.nee_cos = nullptr;
     if (ctx->scene.env.w != 0 && ctx->nee != NEE_NEVER) { HIP_CHECK(ctx->d_neeCos.reserve(nn)); P.nee_cos = ctx->d_neeCos.p; }
+    ctx->mediaArgs.path_medium = nullptr; ctx->mediaArgs.path_stride = 1;
+    if (ctx->mediaArgs.media) { HIP_CHECK(ctx->d_pathMedium.reserve(nn)); ctx->mediaArgs.path_medium = ctx->d_pathMedium.p; }
     return PPG_OK;
 }
 
@@ -1104,6 +1116,7 @@ int stragglerState(ppg_ctx *ctx, ppg_ctx::Stragglers &G, const PathState &batch,
 struct Batch {
     PathState P, Pc;                // Pc: P with the contiguous copy of the path words, once copyMisc has made it
     DevScene S;
+    MediaArgs M;                    // the media family's extra arguments
     DevTree T;
     RenderParams R;
     Queues Q;
@@ -1177,7 +1190,8 @@ int launchStragglers(ppg_ctx *ctx, const Batch &B) {
         RenderParams Rt = B.R;
         Rt.defer_depth = 0u;
         TailLaunch a{shape.grid, B.ldsBytes, st, G.P, B.S, Tt, Rt, G.iota.p, G.count.p, G.ticket.p, ctx->queues.stats, ctx->ldsTris,
-                     ctx->d_tailLongest.p + (ctx->tailLaunches++ % PPG_TAIL_LOG), StragOut{nullptr, nullptr, nullptr}, shape.laneLimit};
+                     ctx->d_tailLongest.p + (ctx->tailLaunches++ % PPG_TAIL_LOG), StragOut{nullptr, nullptr, nullptr}, shape.laneLimit, B.M};
+        if (a.M.path_medium) { a.M.path_medium = reinterpret_cast<unsigned int *>(G.rec.p + 6); a.M.path_stride = 32; }  // (k_tail left the word in the record's seventh float4)
         ppg_launch_tail(tailVariant(ctx), a);
     };
     if (beside) { launch(); HIP_CHECK(hipEventRecord(ctx->evStragDone, ctx->stream4)); }
@@ -1271,6 +1285,7 @@ template <typename F> void forEachBorderSlot(int W, int H, int ts, int world, in
                 }
         }
 }
+const char *kShardedMedia = "participating media are not supported in a sharded render (ppg_set_shard with world > 1): the scene binds a medium";
 const char *kShardedFilter = "sharded filtered renders are not supported yet without a footprint hook: a reconstruction filter other than the default box "
                              "needs world = 1, or ppg_set_footprint_hook before the filter and the shard meet";
 int prepareHalo(ppg_ctx *ctx) {
@@ -1410,6 +1425,7 @@ int prepareBatch(ppg_ctx *ctx, Batch &B, int batch, bool adamRound, const GroupL
         HIP_CHECK(hipMemsetAsync(ctx->d_adamCount.p, 0, 8, s));
     }
     B.S = ctx->scene;
+    B.M = ctx->mediaArgs;
     B.T = ctx->devTree();
     RenderParams &R = B.R;
     R = ctx->params();
@@ -1453,6 +1469,7 @@ int runWavefront(ppg_ctx *ctx, Batch &B) {
     const unsigned int stopBelow = B.plan.stopBelow;
     int qin = QIN_FIRST;
     timedLaunch(ctx, "k_generate", P.n_paths, [&] { hipLaunchKernelGGL(k_generate, dim3(B.gridAll), dim3(PPG_BLOCK), 0, s, P, S, B.R, Q); });
+    if (B.M.path_medium) hipLaunchKernelGGL(k_fill_u32, dim3(B.gridAll), dim3(PPG_BLOCK), 0, s, B.M.path_medium, P.n_paths, B.M.camera_medium);  // every path starts in the sensor's medium
     const int maxBounces = planBounces(ctx->survival, P.n_paths, stopBelow, ctx->maxDepth, ctx->tuneBulkBounces, ctx->bounceMargin, B.plan.adamFast, ctx->deferDepthAdam);
     const bool liveCount = ctx->timer.enabled;  // kernel timing wants the units of every launch
     unsigned int *counts = ctx->d_bounceCounts.p;  // [0..63] live paths after bounce b, [64] the stop flag
@@ -1467,7 +1484,7 @@ int runWavefront(ppg_ctx *ctx, Batch &B) {
         unsigned char *const trKeys = sortSlices ? ctx->d_sortKeys.p : nullptr;
         timedLaunch(ctx, "k_trace", B.hostCount, [&] {
             TraceLaunch a{grid, traceLds, s, P, S, Q, qin, smallScene ? 0 : ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys, smallScene, ctx->timer.enabled};
-            launcher(ppg_path_kernels[sceneFamily(S)].trace)(a);
+            launcher(ppg_path_kernels[sceneFamily(S, B.M)].trace)(a);
         });
         int shadeIn = sortSlices ? QIN_SORTED : qin;
         ctx->joinTree();  // (k_generate and the first k_trace ran beside the previous round's optimiser: k_shade needs its result)
@@ -1479,7 +1496,7 @@ int runWavefront(ppg_ctx *ctx, Batch &B) {
         const bool split = shadeIn == QIN_SORTED && Q.n_common && !neeOn;
         if (split) {
             timedLaunch(ctx, "k_shade<common>", B.hostCount, [&] {
-                ShadeLaunch a{grid, 0, s, P, S, B.T, B.R, Q, QIN_SORTED_COMMON, smallScene ? 1 : 0, ctx->d_queueSorted.p};
+                ShadeLaunch a{grid, 0, s, P, S, B.T, B.R, Q, QIN_SORTED_COMMON, smallScene ? 1 : 0, ctx->d_queueSorted.p, B.M};
                 ppg_launch_shade_common(a);
             });
             shadeIn = QIN_SORTED_REST;
@@ -1490,7 +1507,7 @@ int runWavefront(ppg_ctx *ctx, Batch &B) {
             const size_t neeBytes = smallScene ? triBytes : (size_t)PPG_LDS_STACK * PPG_BLOCK * 4;
             const size_t lds = (neeOn || ctx->scene.has_null) ? neeBytes : 0;
             const int variant = (neeOn ? 2 : 0) | (fullMats ? 1 : 0);
-            ShadeLaunch a{grid, lds, s, P, S, B.T, B.R, Q, shadeIn, small, ctx->d_queueSorted.p};
+            ShadeLaunch a{grid, lds, s, P, S, B.T, B.R, Q, shadeIn, small, ctx->d_queueSorted.p, B.M};
             ppg_launch_shade(variant, a);
         });
         qin = QIN_DENSE;
@@ -1519,7 +1536,7 @@ int launchTail(ppg_ctx *ctx, Batch &B, unsigned int depth, size_t handedPaths) {
         // (the launch's longest path is logged for launches that run their paths to the END: the sum is the tails' critical path; a launch that
         // hands its stragglers over writes to a spare slot nobody reads)
         TailLaunch a{shape.grid, B.ldsBytes, s, B.P, B.S, B.T, Rt, B.dense, ctx->d_total.p, ctx->d_ticket.p, B.Q.stats, ctx->ldsTris,
-                     ctx->d_tailLongest.p + (depth ? PPG_TAIL_LOG : (ctx->tailLaunches++ % PPG_TAIL_LOG)), StragOut{G.rec.p, G.orig.p, G.count.p}, shape.laneLimit};
+                     ctx->d_tailLongest.p + (depth ? PPG_TAIL_LOG : (ctx->tailLaunches++ % PPG_TAIL_LOG)), StragOut{G.rec.p, G.orig.p, G.count.p}, shape.laneLimit, B.M};
         ppg_launch_tail(tailVariant(ctx), a);
     });
     return PPG_OK;
@@ -2392,7 +2409,12 @@ int uploadScene(ppg_ctx *ctx, const HostScene &H, DevScene &S) {
     S.em_sel_cdf = up(ctx->d_emSel, H.emSel); S.em_area_cdf = up(ctx->d_emArea, H.emArea); S.em_info = up(ctx->d_emInfo, H.emInfo);
     S.em_tris = up(ctx->d_emTris, H.emTris); S.em_normals = up(ctx->d_emNrm, H.emNormals);
     S.delta = up(ctx->d_delta, H.delta); S.shapes = up(ctx->d_shapes, H.shapes); S.spheres = up(ctx->d_spheres, H.spheres);
+    MediaArgs &M = ctx->mediaArgs;
+    M = MediaArgs{};
+    M.media = up(ctx->d_media, H.media); M.prim_media = up(ctx->d_primMedia, H.primMedia);
+    M.camera_medium = H.cameraMedium; M.n_media = (int)(H.media.size() / PPG_MEDIUM_STRIDE);
     HIP_CHECK(up.e);
+    if (!H.media.empty() && (!M.media || !M.prim_media)) { ctx->error = "internal: device scene incomplete"; return PPG_ERR_STATE; }
     // Every array the path kernels walk must be there before a launch can chase it: an unset pointer here is a hung GPU, not a wrong pixel
     // (round 5 lost 40 GPU minutes to five assignments that an edit had turned into a comment).
     if (!S.materials || !S.bvh4 || (S.n_tris > 0 && (!S.tris || !S.accel || !S.bvh)) || (S.n_spheres > 0 && !S.spheres) || (S.n_delta > 0 && !S.delta) ||
@@ -2543,12 +2565,13 @@ const char *ppg_last_error(const ppg_ctx *ctx) { return ctx ? ctx->error.c_str()
 
 int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
     const SceneInputs in{s, ctx->materialTextures, ctx->microfacet, ctx->coatings, ctx->blends, ctx->deltaEmitters, ctx->shapes,
-                         ctx->lensOn ? &ctx->lens : nullptr, ctx->tuneBvhPad, ctx->tuneBvhLeaf, ctx->tuneNoTopCut};
+                         ctx->lensOn ? &ctx->lens : nullptr, ctx->tuneBvhPad, ctx->tuneBvhLeaf, ctx->tuneNoTopCut, ctx->mediaList.n_media ? &ctx->mediaList : nullptr};
     if (!sceneComplete(in)) { ctx->error = "incomplete scene"; return PPG_ERR_INVALID; }
     HIP_CHECK(hipSetDevice(ctx->device));
     ctx->quiesce();
     HostScene H;
     if (int rc = buildScene(in, H, ctx->error)) return rc;  // refused: nothing of the context has been touched, the previous scene stays set
+    if (!H.media.empty() && ctx->shardWorld > 1) { ctx->error = kShardedMedia; return PPG_ERR_INVALID; }
     // From here on the buffers the previous scene points into are re-used: no scene is set until the new one is complete
     ctx->haveScene = false; ctx->treeAlive = false; ctx->renderOpen = false; ctx->pathsReady = false;
     DevScene S;
@@ -2568,6 +2591,7 @@ int ppg_set_shard(ppg_ctx *ctx, int32_t rank, int32_t world, int32_t tile_size) 
     ctx->quiesce();
     if (world < 1 || rank < 0 || rank >= world || tile_size < 1) { ctx->error = "bad shard"; return PPG_ERR_INVALID; }
     if (world > 1 && ctx->filtered && !ctx->footHook) { ctx->error = kShardedFilter; return PPG_ERR_INVALID; }
+    if (world > 1 && ctx->haveScene && ctx->mediaArgs.media) { ctx->error = kShardedMedia; return PPG_ERR_INVALID; }
     ctx->shardRank = rank; ctx->shardWorld = world; ctx->tileSize = tile_size;
     return sizeBuffers(ctx);
 }
@@ -2876,6 +2900,28 @@ int ppg_set_delta_emitters(ppg_ctx *ctx, const ppg_delta_emitter *em, uint32_t n
     return PPG_OK;
 }
 
+int ppg_set_media(ppg_ctx *ctx, const ppg_media *media) {
+    if (ctx->renderOpen) { ctx->error = "media: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (media && media->n_media && !media->media) { ctx->error = "media: n_media > 0 but no array"; return PPG_ERR_INVALID; }  // (the kept list stays)
+    ctx->mediaList = ppg_media{};
+    ctx->media.clear(); ctx->triMedia.clear(); ctx->sphereMedia.clear(); ctx->shapeMedia.clear();
+    if (!media || media->n_media == 0) return PPG_OK;  // cleared
+    // the list is copied as it is and validated against the scene by ppg_set_scene
+    ctx->media.assign(media->media, media->media + media->n_media);
+    if (media->tri_media) ctx->triMedia.assign(media->tri_media, media->tri_media + media->n_tri_media);
+    if (media->sphere_media) ctx->sphereMedia.assign(media->sphere_media, media->sphere_media + media->n_sphere_media);
+    if (media->shape_media) ctx->shapeMedia.assign(media->shape_media, media->shape_media + media->n_shape_media);
+    ppg_media &L = ctx->mediaList;
+    L = *media;
+    L.media = ctx->media.data();
+    // (an array of no entries is still an array: its count is checked against the scene's)
+    static const uint32_t none = 0;
+    L.tri_media = media->tri_media ? (ctx->triMedia.empty() ? &none : ctx->triMedia.data()) : nullptr;
+    L.sphere_media = media->sphere_media ? (ctx->sphereMedia.empty() ? &none : ctx->sphereMedia.data()) : nullptr;
+    L.shape_media = media->shape_media ? (ctx->shapeMedia.empty() ? &none : ctx->shapeMedia.data()) : nullptr;
+    return PPG_OK;
+}
+
 int ppg_set_shapes(ppg_ctx *ctx, const ppg_shape *shapes, uint32_t n) {
     if (ctx->renderOpen) { ctx->error = "shapes: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
     if (n && !shapes) { ctx->error = "shapes: no list"; return PPG_ERR_INVALID; }
@@ -2908,6 +2954,30 @@ int ppg_debug_intersect(ppg_ctx *ctx, uint32_t n, const float *rays, ppg_debug_h
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_hit), hipMemcpyDeviceToHost));
+    return PPG_OK;
+}
+int ppg_debug_medium(ppg_ctx *ctx, uint32_t n, const ppg_debug_medium_item *items, ppg_debug_medium_out *out) {
+    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
+    if (ctx->renderOpen) { ctx->error = "ppg_debug_medium: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (!ctx->mediaArgs.media) { ctx->error = "ppg_debug_medium: the scene binds no medium"; return PPG_ERR_STATE; }
+    if (n && (!items || !out)) { ctx->error = "ppg_debug_medium: no arrays"; return PPG_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; ++i) {
+        if (items[i].medium < 0 || items[i].medium >= ctx->mediaArgs.n_media) { ctx->error = "ppg_debug_medium: item " + std::to_string(i) + ": medium out of range"; return PPG_ERR_INVALID; }
+        for (int k = 0; k < 4; ++k)
+            if (!(items[i].u[k] >= 0.0f && items[i].u[k] <= 1.0f)) { ctx->error = "ppg_debug_medium: item " + std::to_string(i) + ": a sample outside [0, 1]"; return PPG_ERR_INVALID; }
+    }
+    if (n == 0) return PPG_OK;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->quiesce();
+    DebugBuf dItems, dOut;
+    HIP_CHECK(dItems.fill(items, (size_t)n * sizeof(ppg_debug_medium_item)));
+    HIP_CHECK(dOut.fill(nullptr, (size_t)n * sizeof(ppg_debug_medium_out)));
+    const unsigned int block = 64;
+    launcher(ppg_path_kernels[PPG_FAMILY_MEDIA].debug_medium)((int)((n + block - 1) / block), (int)block, ctx->stream, ctx->mediaArgs, n, (const ppg_debug_medium_item *)dItems.p,
+                                                              (ppg_debug_medium_out *)dOut.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_medium_out), hipMemcpyDeviceToHost));
     return PPG_OK;
 }
 int ppg_debug_shading_frame(ppg_ctx *ctx, uint32_t n, const float *rays, ppg_debug_frame *out) {
@@ -3077,7 +3147,7 @@ int ppg_debug_intersect_mode(ppg_ctx *ctx, uint32_t n, const float *rays, ppg_de
         const bool smallScene = isSmallScene(ctx);
         const size_t traceLds = smallScene ? (size_t)ctx->ldsTris * 48 : (size_t)PPG_TRACE_STACK * PPG_BLOCK * 4 + (PPG_BLOCK / 64) * sizeof(PairLds);
         TraceLaunch a{grid, traceLds, ctx->stream, P, ctx->scene, Q, QIN_FIRST, smallScene ? 0 : ctx->ldsNodes, ctx->ldsTris, nullptr, nullptr, smallScene, false};
-        launcher(ppg_path_kernels[sceneFamily(ctx->scene)].trace)(a);
+        launcher(ppg_path_kernels[sceneFamily(ctx->scene, ctx->mediaArgs)].trace)(a);
         HIP_CHECK(hipGetLastError());
         launcher(K.debug_hit_records)(ctx->stream, ctx->scene, n, (const float4 *)dRays.p, (const float4 *)dHit.p, (ppg_debug_hit *)dOut.p);
         HIP_CHECK(hipGetLastError());
@@ -3130,8 +3200,8 @@ int ppg_debug_sample_direct(ppg_ctx *ctx, uint32_t n, const float *ref, const fl
 }
 // a kernel family can read the scene if it is the scene's own or one above it (every family knows what the families below it know)
 static int debugFamily(ppg_ctx *ctx, const char *who, int32_t family, int *out) {
-    const int own = sceneFamily(ctx->scene);
-    if (family < -1 || family >= PPG_FAMILIES) { ctx->error = std::string(who) + ": no such kernel family"; return PPG_ERR_INVALID; }
+    const int own = sceneFamily(ctx->scene, ctx->mediaArgs);
+    if (family < -1 || family >= PPG_DEBUG_FAMILIES) { ctx->error = std::string(who) + ": no such kernel family"; return PPG_ERR_INVALID; }
     if (family >= 0 && family < own) { ctx->error = std::string(who) + ": the scene needs kernel family " + std::to_string(own) + " or above"; return PPG_ERR_INVALID; }
     *out = family < 0 ? own : family;
     return PPG_OK;
@@ -3223,7 +3293,7 @@ int ppg_debug_bsdf_as(ppg_ctx *ctx, int32_t family, int32_t unit, uint32_t n, co
 int ppg_debug_bsdf(ppg_ctx *ctx, uint32_t n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out) {
     if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
     if (ctx->renderOpen) { ctx->error = "ppg_debug_bsdf: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
-    const int family = std::max(sceneFamily(ctx->scene), PPG_FAMILY_EXT);  // (as before the base and shapes families compiled the hook's kernel)
+    const int family = std::max(sceneFamily(ctx->scene, ctx->mediaArgs), PPG_FAMILY_EXT);  // (as before the base and shapes families compiled the hook's kernel)
     return debugBsdf(ctx, "ppg_debug_bsdf", family, PPG_DEBUG_BSDF_FULL, n, items, out);
 }
 
@@ -3231,7 +3301,7 @@ int ppg_debug_bsdf(ppg_ctx *ctx, uint32_t n, const ppg_debug_bsdf_item *items, p
 static int debugMathRefusal(ppg_ctx *ctx, const char *who, int32_t family, int32_t via, int32_t op) {
     if (ctx->renderOpen) { ctx->error = std::string(who) + ": not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
     if (!ppg_mathcheck_known(op)) { ctx->error = std::string(who) + ": no such op"; return PPG_ERR_INVALID; }
-    if (family < -1 || family >= PPG_FAMILIES) { ctx->error = std::string(who) + ": no such kernel family"; return PPG_ERR_INVALID; }
+    if (family < -1 || family >= PPG_DEBUG_FAMILIES) { ctx->error = std::string(who) + ": no such kernel family"; return PPG_ERR_INVALID; }
     if (via != 0 && via != 1) { ctx->error = std::string(who) + ": via is 0 (the header's functions) or 1 (the module's dm_ copies)"; return PPG_ERR_INVALID; }
     if (via == 1 && family < 0) { ctx->error = std::string(who) + ": the host has no dm_ copies"; return PPG_ERR_INVALID; }
     if (via == 1 && !ppg_mathcheck_has_dm(op)) { ctx->error = std::string(who) + ": the kernels have no dm_ copy of this op"; return PPG_ERR_INVALID; }

@@ -154,6 +154,10 @@ static __global__ void k_iota_total(unsigned int *a, unsigned int n, unsigned lo
     for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) a[i] = i;
     if (blockIdx.x == 0 && threadIdx.x == 0) *total = n;
 }
+// a[i] = v (PathState::medium of a new batch: the sensor's medium)
+static __global__ void k_fill_u32(unsigned int *a, unsigned int n, unsigned int v) {
+    for (unsigned int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) a[i] = v;
+}
 static __global__ void k_iota(unsigned int *a, unsigned int n) {
     unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) a[i] = i;

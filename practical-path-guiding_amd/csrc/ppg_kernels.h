@@ -131,6 +131,19 @@ struct PathState {
     // from, whose n_pix / pixels stay in force — the Adam records it leaves carry that path's id and the "deferred" bit.  nullptr: a batch.
     const unsigned int *orig;
 };
+#if PPG_MEDIA
+// The path's medium word (media kernels only; MediaArgs::path_medium, nullptr when the scene binds no medium): low 16 bits = 1 + the medium
+// the path is in (rRec.medium), 0 = none; PPG_MW_PEND_PHASE: the pending bounce was sampled from a phase function (GP:1852-1862), so its
+// second half is GP:1864-1893.
+struct PathStateMedia : PathState {
+    Field<unsigned int> medium;
+};
+typedef PathStateMedia PathArg;
+#else
+typedef PathState PathArg;
+#endif
+#define PPG_MW_MEDIUM 0xffffu
+#define PPG_MW_PEND_PHASE (1u << 16)
 
 // Where k_tail puts a straggler (RenderParams::defer_depth): one interleaved record of eight float4 per path — ray origin, direction,
 // throughput, Li, hit, (key, dim, flags, leaf), two unused — at position j = atomic count, and the path's index in its batch.
@@ -827,6 +840,12 @@ D Hit trace_inline(const DevScene &S, const float4 *small_tris, int *stack_col, 
     rayMinT *= ppg_max(ppg_max(ppg_max(ppg_abs(o.x), ppg_abs(o.y)), ppg_abs(o.z)), PPG_EPSILON);
     return trace_closest4<false, true>(S, stack_col, PPG_BLOCK, o, d, rayMinT, maxt);
 }
+#if PPG_MEDIA
+// ... from a point inside a medium: the ray starts at mint itself (0: Ray::mint of a segment that leaves a medium event), no ray epsilon
+D Hit trace_inline_from(const DevScene &S, int *stack_col, F3 o, F3 d, float mint, float maxt) {
+    return trace_closest4<false, true>(S, stack_col, PPG_BLOCK, o, d, mint, maxt);
+}
+#endif
 // intersection record of a hit found by trace_inline / k_trace in a FULL kernel: triangle or sphere (`o` = that ray's origin)
 D void fill_isect_full(const DevScene &S, const Hit &h, F3 o, F3 d, Isect &I) {
     if (h.prim >= S.n_tris) fill_isect_analytic(S, h, o, d, I);
@@ -843,23 +862,43 @@ D void fill_isect_null(const DevScene &S, const Hit &h, F3 o, F3 d, Isect &I, Ma
 
 // Scene::evalTransmittance (scene.cpp:619-679), surfaces only, for scenes with null-component BSDFs: zero behind an occluder,
 // otherwise the product of the null components (evaluated in the geometric frame) of the surfaces passed.
-D F3 shadow_transmittance(const DevScene &S, const float4 *small_tris, int *stack_col, F3 p1, F3 d, float remaining, float lengthFactor,
-                          int maxInteractions, unsigned int &traced) {
+// PPG_MEDIA: `med` (1 + index, 0 = none) is the medium the segment starts in — its transmittance is taken per piece, it switches at a medium
+// transition, and a transition whose near side names another medium than the one the segment is in gives zero ("inconsistent media");
+// p1OnSurface = false (the segment starts at a medium event): the first piece starts at mint = 0 instead of Epsilon.
+D F3 shadow_transmittance(const SceneArg &S, const float4 *small_tris, int *stack_col, F3 p1, F3 d, float remaining, float lengthFactor,
+                          int maxInteractions, unsigned int &traced
+#if PPG_MEDIA
+                          , unsigned int med = 0u, bool p1OnSurface = true
+#endif
+                          ) {
     F3 o = p1;
     float maxt = remaining * lengthFactor;
     F3 transmittance = f3s(1.0f);
     int interactions = 0;
     while (remaining > 0) {
         ++traced;
+#if PPG_MEDIA
+        const Hit h = (p1OnSurface || interactions > 0) ? trace_inline(S, small_tris, stack_col, o, d, maxt) : trace_inline_from(S, stack_col, o, d, 0.0f, maxt);
+#else
         const Hit h = trace_inline(S, small_tris, stack_col, o, d, maxt);
+#endif
         const bool surface = h.prim >= 0;
         Mat M;
         Isect I;
         if (surface) fill_isect_null(S, h, o, d, I, M);
         if (surface && (interactions == maxInteractions || !mat_has_null(M))) return f3s(0.0f);
+#if PPG_MEDIA
+        if (med) transmittance = mul3(transmittance, medium_transmittance(medium_record(S.media, med), ppg_min(surface ? h.t : __builtin_inff(), remaining)));
+#endif
         if (!surface || iszero3(transmittance)) break;
         const float cosThetaI = dot3(I.geoN, -d);
         transmittance = mul3(transmittance, mat_eval_null(M, cosThetaI));
+#if PPG_MEDIA
+        if (const unsigned int word = medium_word(S, h.prim)) {  // its.isMediumTransition(), scene.cpp:659-665
+            if (med != medium_target(word, -d, I.geoN)) return f3s(0.0f);
+            med = medium_target(word, d, I.geoN);
+        }
+#endif
         if (++interactions > 100) break;
         o = o + d * h.t;
         remaining -= h.t;
@@ -884,12 +923,15 @@ struct NeeLds {
 // of its links.  Memory receives the words others read afterwards (misc, li) when the path ends.
 struct Carried {
     uint4 misc; float4 thr, li, hit, ro, rd;
+#if PPG_MEDIA
+    unsigned int medium;  // PathState::medium
+#endif
 #ifdef PPG_PROBE
     unsigned long long *plds, pt, prt; bool pon;
 #endif
 };
 template <bool NEE, bool FULL, bool CARRY = false, int MSET = MSET_ALL>
-D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const RenderParams &R, const unsigned int i, const LdsColumn &fcol,
+D bool shade_one(const PathArg &P, const SceneArg &S, const DevTree &T, const RenderParams &R, const unsigned int i, const LdsColumn &fcol,
                  unsigned long long &plen, unsigned int &traced, const NeeLds &nee, unsigned long long &committed,
                  Carried *cs = nullptr) {
     bool alive = false;
@@ -925,6 +967,22 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
     }
     PROBE_MARK(cs, 2);
     bool go = true;
+#if PPG_MEDIA
+    // rRec.medium and the flavour of the pending bounce (PathState::medium)
+    const bool haveMedia = FULL && MSET != MSET_COMMON && (bool)P.medium;
+    unsigned int mword = haveMedia ? (CARRY ? cs->medium : P.medium[i]) : 0u;
+    unsigned int med = mword & PPG_MW_MEDIUM;
+    const bool pendPhase = (mword & PPG_MW_PEND_PHASE) != 0;
+    const float4 *const medQ = med ? medium_record(S.media, med) : nullptr;  // the medium the ray that ends here travelled in
+    auto record_radiance = [&](F3 L_) {  // recordRadiance, GP:1791-1796
+        Li = Li + L_;
+        for (unsigned int v0 = 0; v0 < nV; ++v0) {
+            float4 rr = P.v_rad[(size_t)v0 * P.n_paths + i];
+            rr.x += L_.x; rr.y += L_.y; rr.z += L_.z;
+            P.v_rad[(size_t)v0 * P.n_paths + i] = rr;
+        }
+    };
+#endif
 
     if (FULL && (flags & FL_PENDING) && (flags & FL_PEND_NULL)) {
         // ---- the previous bounce passed straight through a null component, GP:2045-2075: no emitter lookup, no MIS,
@@ -944,6 +1002,11 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
             const float4 ro4 = ray_origin();
             if (env_fill_direct(S, f3(ro4.x, ro4.y, ro4.z), d)) { value = env_radiance(S, d); em_id = S.n_emitters + S.n_delta; }
         }
+#if PPG_MEDIA
+        // rayIntersectAndLookForEmitter with a medium, GP:2195-2196: the transmittance of every piece of the search, this first one included
+        F3 mtr = f3s(1.0f);
+        if (medQ) { mtr = medium_transmittance(medQ, valid ? h.t : __builtin_inff()); value = mul3(mtr, value); }
+#endif
         if (FULL && MSET != MSET_COMMON && S.has_null && valid && I.emitter < 0) {
             // rayIntersectAndLookForEmitter GP:2184-2245: the path continues from THIS hit, but the search for an emitter
             // goes on through surfaces that have a null component (traced in place)
@@ -953,6 +1016,10 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
                 const float4 ro4 = ray_origin();
                 F3 ro = f3(ro4.x, ro4.y, ro4.z);
                 F3 transmittance = f3s(1.0f);
+#if PPG_MEDIA
+                transmittance = mtr;
+                unsigned int lmed = med;  // the search's own medium: the path's does not follow it
+#endif
                 const int maxInteractions = R.max_depth - (int)depth - 1;
                 int interactions = 0;
                 bool abandoned = false, surface = true;
@@ -961,12 +1028,18 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
                 for (;;) {
                     if (interactions == maxInteractions || !mat_has_null(Mc) || Ic.emitter >= 0) break;
                     if (iszero3(transmittance)) { abandoned = true; break; }
+#if PPG_MEDIA
+                    if (haveMedia) { if (const unsigned int word = medium_word(S, hc.prim)) lmed = medium_target(word, d, Ic.geoN); }  // GP:2211-2212
+#endif
                     const float cosThetaI = -to_local(Ic, d).z;  // bRec(its, -wo, wo) in the shading frame
                     transmittance = mul3(transmittance, mat_eval_null(Mc, cosThetaI));
                     ro = ro + d * hc.t;
                     if (++interactions > 100) { abandoned = true; break; }
                     hc = trace_inline(S, nee.small_tris, nee.stack_col, ro, d, __builtin_inff());
                     ++traced;
+#if PPG_MEDIA
+                    if (lmed) transmittance = mul3(transmittance, medium_transmittance(medium_record(S.media, lmed), hc.prim < 0 ? __builtin_inff() : hc.t));
+#endif
                     if (hc.prim < 0) { surface = false; break; }
                     fill_isect_null(S, hc, ro, d, Ic, Mc);
                 }
@@ -983,6 +1056,13 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
         const bool isDelta = (flags & FL_PEND_DELTA) != 0;
         const bool hasTree = (flags & FL_PEND_TREE) != 0;
         float emitterPdf = 0.0f;  // GP:2085: scene->pdfEmitterDirect(dRec) (scene.cpp:949-952, area.cpp:175-183, shape.cpp:117-126)
+#if PPG_MEDIA
+        if (pendPhase) {
+            // GP:1869-1872: not conditioned on m_doNee; dRec.refN = 0 at a medium event
+            if (!iszero3(value))
+                emitterPdf = emitter_pdf_direct<FULL>(S, em_id, d, em_n, em_dist, true, []() { return -2.0f; }, ray_origin) * (1.0f * S.em_sel_norm);
+        } else
+#endif
         if (NEE && R.do_nee && !isDelta && !iszero3(value)) {
             const float pdfDirect = emitter_pdf_direct<FULL>(S, em_id, d, em_n, em_dist, (flags & FL_PEND_REFN) != 0, [&]() { return P.nee_cos[i]; }, ray_origin);
             emitterPdf = pdfDirect * (1.0f * S.em_sel_norm);
@@ -1021,6 +1101,9 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
                 if (!T.is_built) successProb = max3(thr) * eta * eta;
                 successProb = ppg_max(0.1f, ppg_min(successProb, 0.99f));
             }
+#if PPG_MEDIA
+            if (pendPhase) successProb = ppg_min(max3(thr) * eta * eta, 0.95f);  // the medium branch's own rule, GP:1883-1893
+#endif
             if (ppg_rand(key, dim++) >= successProb) go = false;
             else thr = div3(thr, successProb);
         }
@@ -1032,8 +1115,66 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
     }
 
     PROBE_MARK(cs, 3);
+#if PPG_MEDIA
+    mword &= ~PPG_MW_PEND_PHASE;
+    if (go && medQ) {
+        // ---- the medium branch, GP:1803-1893 (first half: up to the new ray) and the failure factor, GP:1899-1900 ----
+        const float4 ro4 = ray_origin();
+        const F3 ro = f3(ro4.x, ro4.y, ro4.z);
+        MediumSample ms;
+        if (medium_sample_distance(medQ, ro, d, valid ? h.t : __builtin_inff(), [&]() { return ppg_rand(key, dim++); }, ms)) {
+            if ((int)depth >= R.max_depth && R.max_depth != -1) go = false;  // GP:1809
+            if (go) {
+                thr = mul3(thr, div3(mul3(ms.sigmaS, ms.transmittance), ms.pdfSuccess));  // GP:1812
+                const F3 mp = ro + d * ms.t;  // mRec.p
+                const F3 mwi = -d;
+                {   // luminaire sampling, GP:1819-1846: whatever m_doNee says
+                    const float ex = ppg_rand(key, dim++);
+                    const float ey = ppg_rand(key, dim++);
+                    DirectSample ds;
+                    F3 value = emitter_sample_direct<FULL>(S, mp, f3s(0.0f), ex, ey, ds);
+                    if (ds.pdf != 0) {  // value *= evalTransmittance(dRec.ref, false, dRec.p, ..) / emPdf, scene.cpp:864-870
+                        const F3 tr = shadow_transmittance(S, nee.small_tris, nee.stack_col, mp, ds.sd, ds.sdist, (ds.is_env || ds.is_delta) ? 1.0f : 1 - PPG_SHADOW_EPSILON,
+                                                           R.max_depth - (int)depth - 1, traced, med, false);
+                        if (iszero3(tr)) value = f3s(0.0f);
+                        else { value = div3(mul3(value, tr), ds.em_pdf); ds.pdf *= ds.em_pdf; }
+                    }
+                    if (!iszero3(value)) {
+                        const float phaseVal = phase_eval(medQ, mwi, ds.d);
+                        if (phaseVal != 0) {
+                            const float phasePdfE = ds.is_delta ? 0.0f : phaseVal;  // phase->pdf = phase->eval for both phase functions
+                            const float qa = ds.pdf * ds.pdf, qb = phasePdfE * phasePdfE;
+                            record_radiance(mul3(thr, value) * phaseVal * (qa / (qa + qb)));
+                        }
+                    }
+                }
+                // phase function sampling, GP:1852-1862: the value is 1 for both phase functions, never 0
+                const float px = ppg_rand(key, dim++);
+                const float py = ppg_rand(key, dim++);
+                F3 wo;
+                const float phasePdf = phase_sample(medQ, mwi, px, py, wo);
+                d = wo;
+                if (CARRY) { cs->ro = make_float4(mp.x, mp.y, mp.z, 0.0f); cs->rd = make_float4(wo.x, wo.y, wo.z, __builtin_inff()); }
+                else { P.ray_o[i] = make_float4(mp.x, mp.y, mp.z, 0.0f); P.ray_d[i] = make_float4(wo.x, wo.y, wo.z, __builtin_inff()); }
+                flags |= FL_PENDING;
+                mword |= PPG_MW_PEND_PHASE;
+                l4.w = phasePdf;
+                alive = true;
+            }
+            go = false;  // the surface branch is not taken
+        } else {
+            thr = mul3(thr, div3(ms.transmittance, ms.pdfFailure));  // GP:1899-1900
+        }
+    }
+#endif
     // ---- first half of this bounce: GP:1902-2040 ----
     if (MSET != MSET_COMMON && go && !valid) {  // GP:1902-1914: possibly radiance from a background luminaire, then the path ends
+#if PPG_MEDIA
+        if (medQ) {  // GP:1907-1910: value *= rRec.medium->evalTransmittance(ray), the ray as it was traced (mint, maxt)
+            if (FULL && S.env.w != 0 && (flags & FL_EMITTED_OK) && (!R.hide_emitters || (flags & FL_SCATTERED)))
+                Li = Li + mul3(mul3(thr, env_radiance(S, d)), medium_transmittance(medQ, d4.w - ray_origin().w));
+        } else
+#endif
         if (FULL && S.env.w != 0 && (flags & FL_EMITTED_OK) && (!R.hide_emitters || (flags & FL_SCATTERED)))
             Li = Li + mul3(thr, env_radiance(S, d));  // (nVertices == 0 whenever emission is still enabled)
         go = false;
@@ -1206,8 +1347,15 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
             F3 value = emitter_sample_direct<FULL>(S, I.p, refN, ex, ey, ds);
             if (ds.pdf != 0) {
                 if (FULL && S.has_null) {  // value *= evalTransmittance(...) / emPdf, scene.cpp:887-889
+#if PPG_MEDIA
+                    unsigned int smed = med;  // scene.cpp:888-889: at a medium transition the segment starts in the medium on dRec.d's side
+                    if (haveMedia) { if (const unsigned int word = medium_word(S, h.prim)) smed = medium_target(word, ds.d, I.geoN); }
+                    const F3 tr = shadow_transmittance(S, nee.small_tris, nee.stack_col, I.p, ds.sd, ds.sdist, (ds.is_env || ds.is_delta) ? 1.0f : 1 - PPG_SHADOW_EPSILON,
+                                                       R.max_depth - (int)depth - 1, traced, smed, true);
+#else
                     const F3 tr = shadow_transmittance(S, nee.small_tris, nee.stack_col, I.p, ds.sd, ds.sdist, (ds.is_env || ds.is_delta) ? 1.0f : 1 - PPG_SHADOW_EPSILON,
                                                        R.max_depth - (int)depth - 1, traced);
+#endif
                     if (iszero3(tr)) value = f3s(0.0f);
                     else { value = div3(mul3(value, tr), ds.em_pdf); ds.pdf *= ds.em_pdf; }
                 } else {
@@ -1273,6 +1421,9 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
             if (go) {
                 thr = mul3(thr, bsdfWeight);  // GP:2039-2040
                 if (FULL) eta *= sampledEta;
+#if PPG_MEDIA
+                if (haveMedia) { if (const unsigned int word = medium_word(S, h.prim)) med = medium_target(word, wo, I.geoN); }  // GP:2041-2042
+#endif
                 d = wo;
                 if (CARRY) cs->ro = make_float4(I.p.x, I.p.y, I.p.z, PPG_EPSILON);
                 else P.ray_o[i] = make_float4(I.p.x, I.p.y, I.p.z, PPG_EPSILON);
@@ -1310,6 +1461,12 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
         }
     }
     flags = (flags & ~(FL_DEPTH_MASK | FL_NV_MASK)) | (depth & FL_DEPTH_MASK) | (nV << FL_NV_SHIFT);
+#if PPG_MEDIA
+    if (haveMedia && alive) {
+        mword = (mword & ~PPG_MW_MEDIUM) | med;
+        if (CARRY) cs->medium = mword; else P.medium[i] = mword;
+    }
+#endif
     if (CARRY && alive) {
         cs->misc = make_uint4(key, dim, flags, m.w);
         cs->li = make_float4(Li.x, Li.y, Li.z, l4.w);
@@ -1327,7 +1484,7 @@ D bool shade_one(const PathState &P, const DevScene &S, const DevTree &T, const 
 
 // One queue slice through Li's loop body.
 template <bool NEE, bool FULL, int MSET = MSET_ALL>
-D void shade_slice(const PathState &P, const DevScene &S, const DevTree &T, const RenderParams &R, const Work &work,
+D void shade_slice(const PathArg &P, const SceneArg &S, const DevTree &T, const RenderParams &R, const Work &work,
                    unsigned int b, unsigned int nb, unsigned int *out_items, unsigned int *out_count, const LdsColumn &fcol,
                    unsigned long long &plen_sum, unsigned int &traced, const NeeLds &nee, unsigned long long &committed) {
     const unsigned int rounds = (work.count + PPG_BLOCK - 1) / PPG_BLOCK;
@@ -1351,7 +1508,7 @@ D void shade_slice(const PathState &P, const DevScene &S, const DevTree &T, cons
 }
 
 template <bool NEE, bool FULL, int MSET = MSET_ALL>
-__global__ __launch_bounds__(PPG_BLOCK, (MSET == MSET_COMMON ? PPG_SHADE_WAVES_COMMON : (FULL ? PPG_SHADE_WAVES_FULL : PPG_SHADE_WAVES))) void k_shade(PathState P, DevScene S, DevTree T, RenderParams R, Queues Q, int qin,
+__global__ __launch_bounds__(PPG_BLOCK, (MSET == MSET_COMMON ? PPG_SHADE_WAVES_COMMON : (FULL ? PPG_SHADE_WAVES_FULL : PPG_SHADE_WAVES))) void k_shade(PathArg P, SceneArg S, DevTree T, RenderParams R, Queues Q, int qin,
                                                                      int small_scene, const unsigned int *sorted_items) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     __shared__ float pdf_factors[20 * PPG_BLOCK];  // QuadTreeNode::pdf's per-level factors (tree depth <= 20, GP:1112)
@@ -1394,7 +1551,7 @@ __global__ __launch_bounds__(PPG_BLOCK, (MSET == MSET_COMMON ? PPG_SHADE_WAVES_C
 // "one lane per path, until it ends" beat every re-compaction of the survivors into dense waves that was tried (generations of launches
 // on shrinking or on full grids, tails on side streams beside the next sub-batch's wavefront: profiles/r03_tail_experiments.json).
 template <bool SMALL, bool NEE, bool FULL>
-__global__ __launch_bounds__(PPG_BLOCK, (FULL ? PPG_TAIL_WAVES_FULL : PPG_SHADE_WAVES)) void k_tail(PathState P, DevScene S, DevTree T, RenderParams R, const unsigned int *dense,
+__global__ __launch_bounds__(PPG_BLOCK, (FULL ? PPG_TAIL_WAVES_FULL : PPG_SHADE_WAVES)) void k_tail(PathArg P, SceneArg S, DevTree T, RenderParams R, const unsigned int *dense,
                                                                     const unsigned long long *total_ptr, unsigned int *ticket, BlockStats *stats,
                                                                     int lds_tris, unsigned int *longest, StragOut so, unsigned int lane_limit) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -1425,6 +1582,9 @@ __global__ __launch_bounds__(PPG_BLOCK, (FULL ? PPG_TAIL_WAVES_FULL : PPG_SHADE_
     Carried cs;
     cs.misc = make_uint4(0u, 0u, 0u, 0u);
     cs.thr = cs.li = cs.hit = cs.ro = cs.rd = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#if PPG_MEDIA
+    cs.medium = 0u;
+#endif
 #ifdef PPG_PROBE
     cs.plds = probe_lds; cs.pt = 0; cs.pon = false;
 #endif
@@ -1447,6 +1607,9 @@ __global__ __launch_bounds__(PPG_BLOCK, (FULL ? PPG_TAIL_WAVES_FULL : PPG_SHADE_
                 if (k < total) {
                     i = dense[k]; have = true; pending = false;
                     cs.misc = P.misc[i]; cs.thr = P.thr[i]; cs.li = P.li[i]; cs.ro = P.ray_o[i]; cs.rd = P.ray_d[i];
+#if PPG_MEDIA
+                    cs.medium = P.medium ? P.medium[i] : 0u;
+#endif
                 } else drained = true;
             }
         }
@@ -1468,6 +1631,9 @@ __global__ __launch_bounds__(PPG_BLOCK, (FULL ? PPG_TAIL_WAVES_FULL : PPG_SHADE_
                     float4 *r = so.rec + 8 * j;
                     r[0] = cs.ro; r[1] = cs.rd; r[2] = cs.thr; r[3] = cs.li; r[4] = cs.hit;
                     r[5] = make_float4(__uint_as_float(cs.misc.x), __uint_as_float(cs.misc.y), __uint_as_float(cs.misc.z), __uint_as_float(cs.misc.w));
+#if PPG_MEDIA
+                    r[6] = make_float4(__uint_as_float(cs.medium), 0.0f, 0.0f, 0.0f);  // (the stragglers' PathState::medium points here)
+#endif
                     so.orig[j] = i;
                     P.misc[i] = make_uint4(cs.misc.x, cs.misc.y, cs.misc.z & ~FL_NV_MASK, cs.misc.w);
                     have = false; pending = false;  // (a suspended traversal is not carried over: the stragglers' launch traces the ray anew)

@@ -17,6 +17,7 @@ struct ShadeLaunch {
     PathState P; DevScene S; DevTree T; RenderParams R; Queues Q;
     int qin, small_scene;
     const unsigned int *sorted_items;
+    MediaArgs M;             // the media family's extra arguments (ppg_device.h); zero: the scene binds no medium
 };
 struct TailLaunch {
     int grid;
@@ -31,6 +32,7 @@ struct TailLaunch {
     unsigned int *longest;   // the longest path (bounces) this launch finishes: what its duration is made of
     StragOut strag;          // R.defer_depth > 0: where the paths still alive at that depth go
     unsigned int lane_limit; // paths a wave takes at a time (64; fewer for a launch over a handful of stragglers)
+    MediaArgs M;             // the media family's extra arguments (ppg_device.h); zero: the scene binds no medium
 };
 struct TraceLaunch {
     int grid;
@@ -99,6 +101,8 @@ struct ppg_debug_pdf;
 struct ppg_debug_bsdf_item;
 struct ppg_debug_bsdf_out;
 struct ppg_debug_frame;
+struct ppg_debug_medium_item;
+struct ppg_debug_medium_out;
 struct PathKernels {
     void (*shade[2])(int variant, const ShadeLaunch &a);  // [NEE]; variant = (NEE ? 2 : 0) | (FULL ? 1 : 0)
     void (*tail[4])(int variant, const TailLaunch &a);    // [SMALL * 2 + NEE]; variant = (SMALL ? 4 : 0) | (NEE ? 2 : 0) | (FULL ? 1 : 0)
@@ -121,6 +125,8 @@ struct PathKernels {
     void (*debug_pdf_direct)(int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const float4 *rays, const float *ref_n, ppg_debug_pdf *out);
     // every family: its copy of mat_eval / mat_pdf / mat_sample (lean != 0: bsdf_eval / bsdf_pdf / bsdf_sample, the base family only)
     void (*debug_bsdf)(int lean, int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out);
+    // the media family: its medium_sample_distance / medium_transmittance / phase_sample / phase_eval (ppg_debug_medium)
+    void (*debug_medium)(int grid, int block, hipStream_t stream, const MediaArgs &M, unsigned int n, const ppg_debug_medium_item *items, ppg_debug_medium_out *out);
 };
 extern PathKernels ppg_path_kernels[PPG_FAMILIES];
 

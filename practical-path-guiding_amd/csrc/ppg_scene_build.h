@@ -701,6 +701,7 @@ struct SceneInputs {
     float bvhPad;          // PPG_BVH_PAD
     int bvhLeaf;           // PPG_BVH_LEAF
     bool noTopCut;         // PPG_NO_TOPCUT
+    const ppg_media *media = nullptr;  // ppg_set_media's list as the context keeps it, or nullptr: none
 };
 
 // Every table of a scene as the device reads it, on the host; `scene` carries every scalar of the DevScene and no pointer (the upload fills
@@ -720,6 +721,9 @@ struct HostScene {
     std::vector<int4> emInfo;
     std::vector<float4> emTris, emNormals;
     std::vector<float4> delta, shapes, spheres;
+    std::vector<float4> media;            // PPG_MEDIUM_STRIDE per medium; media and primMedia: empty unless the list binds a medium
+    std::vector<unsigned int> primMedia;  // one binding word per primitive: triangles in leaf order, spheres, shapes
+    unsigned int cameraMedium = 0;        // 1 + the sensor's medium
     std::vector<float> rtrans;
     std::vector<ppg_delta_emitter> deltaEmitters;  // the list the scene's box was built with (ppg_set_lens builds it again)
     DevScene scene{};
@@ -797,7 +801,7 @@ struct SceneBuilder {
     }
 
     int primitives(), geometry(), materials(), microfacet(), coatings(), blends(), textures(), envmap(), emitterTables(), deltaEmitters(), shapesAndSpheres(),
-        cameraAndLds();
+        media(), cameraAndLds();
 };
 
 // The references of every primitive — triangles, spheres, shapes — and who carries which emitter
@@ -1417,6 +1421,99 @@ int SceneBuilder::shapesAndSpheres() {
     return PPG_OK;
 }
 
+// ppg_set_media: homogeneous media and who lies in which.  Everything the device code relies on is checked here — every medium index of
+// every binding word, every coefficient —, and what HomogeneousMedium's constructor derives is derived here: sigmaT = sigmaA + sigmaS
+// (medium.cpp), the default mediumSamplingWeight (homogeneous.cpp:168-184) and `single`'s sampling density (:188-204).
+int SceneBuilder::media() {
+    DevScene &S = H.scene;
+    const ppg_media *L = in.media;
+    if (!L || L->n_media == 0) return PPG_OK;
+    if (L->_reserved) return refuse("media: a reserved word is not 0");
+    if (!L->media) return refuse("media: n_media > 0 but no array");
+    if (L->n_media > 65535u) return refuse("media: " + std::to_string(L->n_media) + " media, at most 65535 are supported");
+    if (L->tri_media && L->n_tri_media != s->n_triangles)
+        return refuse("media: tri_media has " + std::to_string(L->n_tri_media) + " entries, the scene " + std::to_string(s->n_triangles) + " triangles");
+    if (L->sphere_media && L->n_sphere_media != s->n_spheres)
+        return refuse("media: sphere_media has " + std::to_string(L->n_sphere_media) + " entries, the scene " + std::to_string(s->n_spheres) + " spheres");
+    if (L->shape_media && L->n_shape_media != in.shapes.size())
+        return refuse("media: shape_media has " + std::to_string(L->n_shape_media) + " entries, the scene " + std::to_string(in.shapes.size()) + " shapes");
+    std::vector<float4> tab(PPG_MEDIUM_STRIDE * (size_t)L->n_media);
+    for (uint32_t k = 0; k < L->n_media; ++k) {
+        const ppg_medium &m = L->media[k];
+        const std::string who = "medium " + std::to_string(k) + ": ";
+        for (int c = 0; c < 3; ++c) {
+            if (!std::isfinite(m.sigma_a[c]) || !std::isfinite(m.sigma_s[c])) return refuse(who + "a coefficient is not finite");
+            if (m.sigma_a[c] < 0 || m.sigma_s[c] < 0) return refuse(who + "a coefficient is negative");
+        }
+        for (int c = 0; c < 4; ++c) if (m._reserved[c]) return refuse(who + "a reserved word is not 0");
+        if (m.strategy != PPG_MEDIUM_BALANCE && m.strategy != PPG_MEDIUM_SINGLE && m.strategy != PPG_MEDIUM_MANUAL) return refuse(who + "unknown sampling strategy");
+        if (m.phase != PPG_PHASE_ISOTROPIC && m.phase != PPG_PHASE_HG) return refuse(who + "unknown phase function");
+        if (m.phase == PPG_PHASE_HG && !(m.g > -1.0f && m.g < 1.0f)) return refuse(who + "hg: g must lie in (-1, 1)");
+        if (!(m.sampling_weight == -1.0f || (m.sampling_weight >= 0.0f && m.sampling_weight <= 1.0f))) return refuse(who + "mediumSamplingWeight must lie in [0, 1] (or be -1: derive it)");
+        if (m.strategy == PPG_MEDIUM_SINGLE && m.channel > 2) return refuse(who + "single: channel must be 0, 1 or 2 (or negative: the smallest sigmaT)");
+        if (m.strategy == PPG_MEDIUM_MANUAL && !(std::isfinite(m.sampling_density) && m.sampling_density > 0)) return refuse(who + "manual: samplingDensity must be finite and > 0");
+        float sigmaT[3];
+        for (int c = 0; c < 3; ++c) {
+            sigmaT[c] = m.sigma_a[c] + m.sigma_s[c];
+            if (!std::isfinite(sigmaT[c])) return refuse(who + "a coefficient is not finite");
+        }
+        float weight = m.sampling_weight;
+        if (weight == -1.0f) {  // the highest albedo over the channels that extinguish at all; at least one half if the medium scatters
+            for (int c = 0; c < 3; ++c) {
+                const float albedo = m.sigma_s[c] / sigmaT[c];
+                if (albedo > weight && sigmaT[c] != 0) weight = albedo;
+            }
+            if (weight > 0) weight = ppg_max(weight, 0.5f);
+            // (a medium without extinction keeps -1 in the reference and never samples a distance; 0 says the same)
+            if (weight < 0) weight = 0.0f;
+        }
+        float density = 0.0f;
+        if (m.strategy == PPG_MEDIUM_SINGLE) {
+            int channel = 0;
+            float smallest = INFINITY;
+            for (int c = 0; c < 3; ++c) if (sigmaT[c] < smallest) { smallest = sigmaT[c]; channel = c; }
+            if (m.channel >= 0) channel = m.channel;
+            density = sigmaT[channel];
+        } else if (m.strategy == PPG_MEDIUM_MANUAL) {
+            density = m.sampling_density;
+        }
+        float4 *Q = &tab[PPG_MEDIUM_STRIDE * (size_t)k];
+        Q[0] = make_float4(m.sigma_s[0], m.sigma_s[1], m.sigma_s[2], weight);
+        Q[1] = make_float4(sigmaT[0], sigmaT[1], sigmaT[2], density);
+        Q[2] = make_float4(m.phase == PPG_PHASE_HG ? m.g : 0.0f, __builtin_bit_cast(float, (int)m.strategy), __builtin_bit_cast(float, (int)m.phase), 0.0f);
+    }
+    auto checkWord = [&](uint32_t w, const std::string &who) {
+        if ((w & 0xffffu) > L->n_media || (w >> 16) > L->n_media) return refuse("media: " + who + ": medium index out of range");
+        return (int)PPG_OK;
+    };
+    if (L->camera_medium > L->n_media) return refuse("media: camera_medium: medium index out of range");
+    bool bound = L->camera_medium != 0;
+    const size_t nPrims = (size_t)s->n_triangles + s->n_spheres + in.shapes.size();
+    std::vector<unsigned int> words(nPrims, 0u);
+    if (L->tri_media)
+        for (uint32_t k = 0; k < s->n_triangles; ++k) {  // leaf order, as the kernels number the triangles
+            const uint32_t t = bb.order[k], w = L->tri_media[t];
+            if (int rc = checkWord(w, "triangle " + std::to_string(t))) return rc;
+            words[k] = w; bound = bound || w != 0;
+        }
+    if (L->sphere_media)
+        for (uint32_t k = 0; k < s->n_spheres; ++k) {
+            if (int rc = checkWord(L->sphere_media[k], "sphere " + std::to_string(k))) return rc;
+            words[s->n_triangles + k] = L->sphere_media[k]; bound = bound || L->sphere_media[k] != 0;
+        }
+    if (L->shape_media)
+        for (size_t k = 0; k < in.shapes.size(); ++k) {
+            if (int rc = checkWord(L->shape_media[k], "shape " + std::to_string(k))) return rc;
+            words[(size_t)s->n_triangles + s->n_spheres + k] = L->shape_media[k]; bound = bound || L->shape_media[k] != 0;
+        }
+    if (!bound) return PPG_OK;  // a list that binds nothing renders as no list does
+    H.media = std::move(tab); H.primMedia = std::move(words);
+    H.cameraMedium = L->camera_medium;
+    S.has_null = 1;             // shadow segments and the search for emitters walk their pieces (transmittance per piece) as behind null surfaces
+    H.fullMaterials = true;     // the media code lives in the FULL kernel variants
+    return PPG_OK;
+}
+
 // the sensor, the film size and how much of the scene k_trace caches in LDS
 int SceneBuilder::cameraAndLds() {
     DevScene &S = H.scene;
@@ -1442,7 +1539,7 @@ static int buildScene(const SceneInputs &in, HostScene &H, std::string &err) {
     SceneBuilder b{in, H, err, in.s, {}, {}, {}, {}};
     for (auto stage : {&SceneBuilder::primitives, &SceneBuilder::geometry, &SceneBuilder::materials, &SceneBuilder::microfacet, &SceneBuilder::coatings,
                        &SceneBuilder::blends, &SceneBuilder::textures, &SceneBuilder::envmap, &SceneBuilder::emitterTables, &SceneBuilder::deltaEmitters,
-                       &SceneBuilder::shapesAndSpheres, &SceneBuilder::cameraAndLds})
+                       &SceneBuilder::shapesAndSpheres, &SceneBuilder::media, &SceneBuilder::cameraAndLds})
         if (int rc = (b.*stage)()) return rc;
     return PPG_OK;
 }

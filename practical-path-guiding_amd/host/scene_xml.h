@@ -771,6 +771,23 @@ public:
             out.scene.lens.aperture_radius = r; out.scene.lens.focus_distance = focus;
         }
         for (auto &c : root.children) if (c.tag == "texture" && c.attr("id")) m_textureIds.insert(c.get("id"));
+        {   // participating media (the library's ppg_set_media) are not offered by this loader: refused by name, or dropped by a lenient load
+            int media = 0, subsurface = 0;
+            std::function<void(const XmlNode &)> walk = [&](const XmlNode &n) {
+                for (auto &c : n.children) {
+                    if (c.tag == "medium" || (c.tag == "ref" && (c.get("name") == "interior" || c.get("name") == "exterior"))) ++media;
+                    if (c.tag == "subsurface") ++subsurface;
+                    walk(c);
+                }
+            };
+            walk(root);
+            if (m_strict && subsurface) throw std::runtime_error("subsurface plug-ins (<subsurface>) are not supported");
+            if (m_strict && media)
+                throw std::runtime_error("participating media (<medium>) are not offered by this loader: load the scene with the Python loader (ppg_host.mitsuba_xml), which "
+                                         "supports homogeneous media");
+            if (media) out.warnings.push_back("participating media dropped (" + std::to_string(media) + " <medium> elements or references): this loader does not offer them");
+            if (subsurface) out.warnings.push_back("subsurface plug-ins dropped (not supported)");
+        }
         // bsdfs
         for (auto &b : root.children) if (b.tag == "bsdf" && b.attr("id")) { const ppg_material bm = makeBsdfTop(b, out); m_byId[b.get("id")] = intern(bm, out, m_mfd, m_coat, m_blend); }
         {   // an id may also sit on a NESTED bsdf (KITCHEN references the twosided element inside a bumpmap): every element with an id is a named object
@@ -961,6 +978,7 @@ public:
             int mat = -1;
             for (auto &c : sh.children) {
                 if (c.tag == "bsdf") { const ppg_material bm = makeBsdfTop(c, out); mat = (int)intern(bm, out, m_mfd, m_coat, m_blend); }
+                else if (c.tag == "ref" && (c.get("name") == "interior" || c.get("name") == "exterior")) continue;  // (a lenient load: the medium was dropped above)
                 else if (c.tag == "ref") {
                     auto it = m_byId.find(c.get("id"));
                     if (it == m_byId.end()) throw std::runtime_error("<ref id=\"" + c.get("id") + "\">: no such bsdf");

@@ -199,6 +199,16 @@ private:
                 anyNormals |= mesh->getVertexNormals() != NULL;
                 anyUVs |= mesh->getVertexTexcoords() != NULL;
             }
+        /* Participating media and subsurface plug-ins are not offered through this plug-in (the library's ppg_set_media is reached through
+           the Python loader only): refused by name, never rendered without them.  (Compiled only where Mitsuba's headers are: no test
+           of this repository runs it.) */
+        if (sensor->getMedium()) { why = "participating media are not supported by the HIP plug-in: the sensor lies in a medium"; return false; }
+        for (size_t i = 0; i < shapes.size(); ++i) {
+            const std::string name = shapes[i]->getProperties().getPluginName();
+            if (shapes[i]->isMediumTransition()) { why = "participating media are not supported by the HIP plug-in: shape '" + name + "' has an interior or exterior medium"; return false; }
+            if (shapes[i]->hasSubsurface()) { why = "subsurface plug-ins are not supported by the HIP plug-in: shape '" + name + "' has one"; return false; }
+        }
+        if (!scene->getMedia().empty()) { why = "participating media are not supported by the HIP plug-in: the scene holds a medium"; return false; }
         const float nan = std::numeric_limits<float>::quiet_NaN();
         for (size_t i = 0; i < shapes.size(); ++i) {
             const Shape *shape = shapes[i].get();

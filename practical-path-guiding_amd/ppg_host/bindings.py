@@ -257,6 +257,79 @@ class Blend(C.Structure):
         return d
 
 
+class Medium(C.Structure):
+    """ppg_medium (include/ppg.h): a homogeneous medium (medium/homogeneous.cpp) with its phase function.  Scene descriptions carry media
+    as dicts (SceneDesc.media): sigma_a + sigma_s, or sigma_t + albedo (sigma_s = sigma_t * albedo, sigma_a = sigma_t - sigma_s, as
+    medium.cpp derives them), each a number or an RGB triple; scale (1) multiplies both; strategy ("balance" | "single" | "manual"),
+    channel (single; None: the smallest sigma_t), sampling_density (manual), sampling_weight (None: derive it), phase ("isotropic" | "hg"), g."""
+    _fields_ = [("sigma_a", C.c_float * 3), ("sigma_s", C.c_float * 3), ("strategy", C.c_int32), ("channel", C.c_int32),
+                ("sampling_density", C.c_float), ("sampling_weight", C.c_float), ("phase", C.c_int32), ("g", C.c_float), ("_reserved", C.c_uint32 * 4)]
+    STRATEGIES = ("balance", "single", "manual")
+    PHASES = ("isotropic", "hg")
+
+    @classmethod
+    def from_dict(cls, d):
+        def rgb(v):
+            a = np.asarray(v, np.float32).reshape(-1)
+            return np.repeat(a, 3) if a.size == 1 else a
+        m = cls()
+        scale = np.float32(d.get("scale", 1.0))
+        if "sigma_t" in d or "albedo" in d:
+            if "sigma_a" in d or "sigma_s" in d or "sigma_t" not in d or "albedo" not in d:
+                raise ValueError("medium: state sigma_a and sigma_s, or sigma_t and albedo")
+            st = rgb(d["sigma_t"]) * scale   # medium.cpp: the scale first, then sigmaS = sigmaT * albedo, sigmaA = sigmaT - sigmaS
+            ss = st * rgb(d["albedo"])
+            sa = st - ss
+        else:
+            if "sigma_a" not in d or "sigma_s" not in d:
+                raise ValueError("medium: state sigma_a and sigma_s, or sigma_t and albedo")
+            sa, ss = rgb(d["sigma_a"]) * scale, rgb(d["sigma_s"]) * scale
+        m.sigma_a[:] = [float(v) for v in sa]
+        m.sigma_s[:] = [float(v) for v in ss]
+        strategy = d.get("strategy", "balance")
+        m.strategy = cls.STRATEGIES.index(strategy) if isinstance(strategy, str) else int(strategy)
+        channel = d.get("channel")
+        m.channel = -1 if channel is None else int(channel)
+        m.sampling_density = float(d.get("sampling_density", 0.0))
+        weight = d.get("sampling_weight")
+        m.sampling_weight = -1.0 if weight is None else float(weight)
+        phase = d.get("phase", "isotropic")
+        m.phase = cls.PHASES.index(phase) if isinstance(phase, str) else int(phase)
+        m.g = float(d.get("g", 0.0))
+        return m
+
+
+class Media(C.Structure):
+    """ppg_media (include/ppg.h)"""
+    _fields_ = [("n_media", C.c_uint32), ("camera_medium", C.c_uint32), ("media", C.POINTER(Medium)),
+                ("n_tri_media", C.c_uint32), ("n_sphere_media", C.c_uint32), ("n_shape_media", C.c_uint32), ("_reserved", C.c_uint32),
+                ("tri_media", C.POINTER(C.c_uint32)), ("sphere_media", C.POINTER(C.c_uint32)), ("shape_media", C.POINTER(C.c_uint32))]
+
+
+def media_word(interior=None, exterior=None):
+    """The binding word of a primitive (ppg_media): low 16 bits = 1 + the interior medium's index, high 16 bits = 1 + the exterior one's."""
+    return (0 if interior is None else 1 + int(interior)) | ((0 if exterior is None else 1 + int(exterior)) << 16)
+
+
+def has_media(desc):
+    """Whether `desc` carries participating media (what the CPU oracle, the .ppgs container and the C++ loader do not implement)."""
+    return bool(getattr(desc, "media", None))
+
+
+class DebugMediumItem(C.Structure):
+    _fields_ = [("medium", C.c_int32), ("length", C.c_float), ("wi", C.c_float * 3), ("u", C.c_float * 4)]
+
+
+class DebugMediumOut(C.Structure):
+    _fields_ = [("success", C.c_int32), ("t", C.c_float), ("pdf_success", C.c_float), ("pdf_failure", C.c_float), ("transmittance", C.c_float * 3),
+                ("eval_transmittance", C.c_float * 3), ("wo", C.c_float * 3), ("phase_eval", C.c_float), ("phase_pdf", C.c_float)]
+
+
+DEBUG_MEDIUM_ITEM_DTYPE = np.dtype([("medium", "<i4"), ("length", "<f4"), ("wi", "<f4", 3), ("u", "<f4", 4)])
+DEBUG_MEDIUM_OUT_DTYPE = np.dtype([("success", "<i4"), ("t", "<f4"), ("pdf_success", "<f4"), ("pdf_failure", "<f4"), ("transmittance", "<f4", 3),
+                                   ("eval_transmittance", "<f4", 3), ("wo", "<f4", 3), ("phase_eval", "<f4"), ("phase_pdf", "<f4")])
+
+
 def has_blends(desc):
     """Whether a material of `desc` carries a `blend` entry (what the CPU oracle does not implement)."""
     return any(m.get("blend") is not None for m in desc.materials)
@@ -717,6 +790,8 @@ class Engine:
 
     # -- scene -------------------------------------------------------------------------------
     def set_scene(self, desc):
+        if has_media(desc) and self.prefix != "ppg_":
+            raise NotImplementedError("%s: participating media are not implemented here" % self.prefix)
         if has_blends(desc):  # children stated as dicts join the material list
             if self.prefix != "ppg_":
                 raise NotImplementedError("%s: the blendbsdf / mixturebsdf combinators are not implemented here" % self.prefix)
@@ -786,7 +861,17 @@ class Engine:
         s.camera.width, s.camera.height = cam["width"], cam["height"]
         self._scene_keep = (pos, idx, tm, te, nrm, mats, ems, rt, sph_arr, envmap, uvs, tex_arr, tex_keep)
         self._send_side_lists(self._BEFORE_SET_SCENE, desc)
-        self._call("set_scene", C.byref(s))
+        if self.prefix == "ppg_" and (has_media(desc) or getattr(self, "_media", False)):  # (or to clear what an earlier description left)
+            self.set_media(getattr(desc, "media", None), getattr(desc, "tri_media", None), getattr(desc, "sphere_media", None),
+                           getattr(desc, "shape_media", None), getattr(desc, "camera_medium", 0))
+        try:
+            self._call("set_scene", C.byref(s))
+        except PPGError:
+            # a refused scene leaves the previous one set: its media list must not stay behind in the context, where a later
+            # ppg_set_scene of another description would consume it
+            if getattr(self, "_media", False):
+                self.set_media([])
+            raise
         self.width, self.height = cam["width"], cam["height"]
         self._send_side_lists(self._AFTER_SET_SCENE, desc)
 
@@ -837,6 +922,40 @@ class Engine:
     def set_delta_emitters(self, emitters):
         """ppg_set_delta_emitters: a list of emitter dicts (DeltaEmitter); an empty list clears it.  Takes effect at the next set_scene."""
         self._delta = self._set_list("delta_emitters", DeltaEmitter, emitters)
+
+    def set_media(self, media, tri_media=None, sphere_media=None, shape_media=None, camera_medium=0):
+        """ppg_set_media: a list of medium dicts (Medium), the binding words per triangle / sphere / shape (media_word; None: none) and the
+        sensor's medium (1 + index, 0: none); an empty list clears it.  Takes effect at, and is validated by, the next set_scene."""
+        if self.prefix != "ppg_":
+            raise NotImplementedError("%s: participating media are not implemented here" % self.prefix)
+        media = list(media or [])
+        m = Media()
+        arr = (Medium * max(1, len(media)))()
+        for i, d in enumerate(media):
+            arr[i] = d if isinstance(d, Medium) else Medium.from_dict(d)
+        m.n_media, m.media, m.camera_medium = len(media), arr, int(camera_medium)
+        keep = [arr]
+        for name, words in (("tri_media", tri_media), ("sphere_media", sphere_media), ("shape_media", shape_media)):
+            if words is None:
+                continue
+            w = np.ascontiguousarray(words, np.uint32).reshape(-1)
+            w = w if w.size else np.zeros(1, np.uint32)  # (an array of no entries is still an array)
+            keep.append(w)
+            setattr(m, "n_" + name, int(np.asarray(words).size))
+            setattr(m, name, _p(w, C.c_uint32))
+        self._call("set_media", C.byref(m))
+        self._media = bool(media)
+
+    def debug_medium(self, items):
+        """ppg_debug_medium (include/ppg_testhooks.h): items a structured array (DEBUG_MEDIUM_ITEM_DTYPE) through the media family's
+        sampleDistance / evalTransmittance / phase sample and eval; a structured array (DEBUG_MEDIUM_OUT_DTYPE)."""
+        if self.prefix != "ppg_":
+            raise NotImplementedError("%s: ppg_debug_medium is not implemented here" % self.prefix)
+        items = np.ascontiguousarray(items, DEBUG_MEDIUM_ITEM_DTYPE).reshape(-1)
+        out = np.zeros(items.shape[0], DEBUG_MEDIUM_OUT_DTYPE)
+        assert out.itemsize == C.sizeof(DebugMediumOut) and items.itemsize == C.sizeof(DebugMediumItem)
+        self._call("debug_medium", C.c_uint32(items.shape[0]), items.ctypes.data_as(C.POINTER(DebugMediumItem)), out.ctypes.data_as(C.POINTER(DebugMediumOut)))
+        return out
 
     def set_shapes(self, shapes):
         """ppg_set_shapes: a list of shape dicts (Shape); an empty list clears it.  Takes effect at, and is validated by, the next set_scene."""

@@ -905,6 +905,7 @@ class _Reader:
         self.textures, self.tex_index, self.scaled_index = [], {}, {}  # SceneDesc.textures; bitmap key → index; (index, factor) → index of the scaled copy
         self.materials, self.mat_index, self.by_id = [], {}, {}  # material dicts; frozen dict → index; bsdf id → index
         self.rt_slices, self.rt_index = [], {}  # rough-transmittance slices; (distribution, alpha, eta) → index
+        self.media, self.medium_by_id = [], {}  # medium dicts (bindings.Medium); medium id → index, or None for one a lenient load dropped
 
     def sub(self, text):  # $name → its -D or <default> value (mitsuba.cpp:58-87)
         if text is None or "$" not in text:
@@ -1497,9 +1498,113 @@ class _Reader:
             if not (np.isfinite(r) and r > 0 and np.isfinite(focus) and focus > 0):
                 raise SceneError("thinlens sensor: apertureRadius and focusDistance must be finite and > 0 (got %r, %r)" % (float(r), float(focus)))
             lens = dict(aperture_radius=float(r), focus_distance=float(focus))
+        camera_medium = 0
+        for c in sensor:  # the medium the sensor lies in (Sensor::m_medium)
+            if self._is_medium(c):
+                index = self._medium_index(c, "the sensor's")
+                camera_medium = 0 if index is None else 1 + index
         sampler = sensor.find("sampler")
         info = dict(width=W, height=H, sample_count=_props(sampler, self.sub).get("sampleCount") if sampler is not None else None)
-        return dict(camera=camera, lens=lens, rfilter=rfilter), info
+        return dict(camera=camera, lens=lens, rfilter=rfilter, camera_medium=camera_medium), info
+
+    # ---- participating media: <medium type="homogeneous"> with a nested <phase> (medium/homogeneous.cpp, medium.cpp, phase/isotropic.cpp, hg.cpp)
+    def _make_medium(self, elem):
+        """A <medium> element → its dict (bindings.Medium).  What cannot be rendered is refused by name."""
+        t = elem.get("type")
+        if t == "heterogeneous":
+            raise SceneError("medium type 'heterogeneous' is not supported (homogeneous media only)")
+        if t != "homogeneous":
+            raise SceneError("medium type %r is not supported (homogeneous media only)" % t)
+        p = _props(elem, self.sub)
+        stated = {c.get("name") for c in elem if c.tag in ("rgb", "srgb", "spectrum", "blackbody")}
+        if "material" in p:
+            raise SceneError("homogeneous medium: the 'material' presets (%r) are not supported: state sigmaA and sigmaS, or sigmaT and albedo" % p["material"])
+        pair_as, pair_ta = {"sigmaA", "sigmaS"} & stated, {"sigmaT", "albedo"} & stated
+        if pair_as and pair_ta:
+            raise SceneError("homogeneous medium: please provide *either* sigmaA & sigmaS *or* sigmaT & albedo, but no other combinations!")  # materials.h:154-170
+        if len(pair_as) != 2 and len(pair_ta) != 2:
+            raise SceneError("homogeneous medium: state both sigmaA and sigmaS, or both sigmaT and albedo (Mitsuba fills what is missing from its "
+                             "'material' preset table, which is not supported)")
+        strategy = str(p.get("strategy", "balance"))
+        if strategy == "maximum":
+            raise SceneError("homogeneous medium: strategy 'maximum' is not supported (balance, single, manual)")
+        if strategy not in ("balance", "single", "manual"):
+            raise SceneError("homogeneous medium: Specified an unknown sampling strategy (%r)" % strategy)
+        if p.get("monochromatic", False):
+            raise SceneError("homogeneous medium: 'monochromatic' is not supported")
+        colour = lambda name: tuple(float(v) for v in self._colour(elem, name, 0.0))  # noqa: E731
+        m = dict(scale=float(p.get("scale", 1.0)), strategy=strategy)
+        if len(pair_as) == 2:
+            m.update(sigma_a=colour("sigmaA"), sigma_s=colour("sigmaS"))
+        else:
+            m.update(sigma_t=colour("sigmaT"), albedo=colour("albedo"))
+        if strategy == "single" and "channel" in p:
+            if int(p["channel"]) not in (0, 1, 2):
+                raise SceneError("homogeneous medium: channel must be 0, 1 or 2")
+            m["channel"] = int(p["channel"])
+        if strategy == "manual":
+            if "samplingDensity" not in p:
+                raise SceneError("homogeneous medium: strategy 'manual' needs 'samplingDensity'")
+            m["sampling_density"] = float(p["samplingDensity"])
+        if "mediumSamplingWeight" in p and float(p["mediumSamplingWeight"]) != -1:
+            m["sampling_weight"] = float(p["mediumSamplingWeight"])
+        phases = [c for c in elem if c.tag == "phase"]
+        if len(phases) > 1:
+            raise SceneError("homogeneous medium: more than one <phase>")
+        if phases:  # (none: Medium::configure instantiates `isotropic`)
+            pt, pp = phases[0].get("type"), _props(phases[0], self.sub)
+            if pt == "hg":
+                g = float(pp.get("g", 0.8))  # hg.cpp:49-52
+                if g >= 1 or g <= -1:
+                    raise SceneError("hg: The asymmetry parameter must lie in the interval (-1, 1)!")
+                m.update(phase="hg", g=g)
+            elif pt != "isotropic":
+                raise SceneError("phase function type %r is not supported (isotropic, hg)" % pt)
+        return m
+
+    def _medium_index(self, elem, where):
+        """The index in self.media of a <medium> or a <ref> to a top-level one; None where a lenient load has dropped it (with a warning)."""
+        if elem.tag == "ref":
+            rid = elem.get("id")
+            if rid not in self.medium_by_id:
+                raise SceneError("<ref id=%r>: no such medium" % rid)
+            return self.medium_by_id[rid]
+        try:
+            m = self._make_medium(elem)
+        except SceneError as e:
+            if self.strict:
+                raise
+            self.warnings.append("medium dropped (%s): %s" % (where, e))
+            return None
+        self.media.append(m)
+        if len(self.media) > 65535:
+            raise SceneError("more than 65535 media")
+        return len(self.media) - 1
+
+    def _read_media(self, root):  # the top-level <medium id=...> elements → self.medium_by_id
+        for m in root.findall("medium"):
+            index = self._medium_index(m, "id %r" % m.get("id"))
+            if m.get("id"):
+                self.medium_by_id[m.get("id")] = index
+
+    def _is_medium(self, c):  # whether the child element is a <medium>, or a <ref> to one (by its name or by its target)
+        return c.tag == "medium" or (c.tag == "ref" and (c.get("name") in ("interior", "exterior") or c.get("id") in self.medium_by_id))
+
+    def _shape_media_word(self, sh):  # the binding word of a <shape>: its interior / exterior media (bindings.media_word)
+        from .bindings import media_word
+        sides = dict(interior=None, exterior=None)
+        for c in sh:
+            if c.tag == "subsurface":
+                if self.strict:
+                    raise SceneError("subsurface plug-ins (<subsurface type=%r>) are not supported" % c.get("type"))
+                self.warnings.append("subsurface %r on a shape dropped (not supported)" % c.get("type"))
+            if not self._is_medium(c):
+                continue
+            name = c.get("name")
+            if name not in sides:
+                raise SceneError("a medium on a shape must be named 'interior' or 'exterior' (got %r)" % name)
+            sides[name] = self._medium_index(c, "%s of a %s shape" % (name, sh.get("type")))
+        return media_word(**sides)
 
     def _read_named_bsdfs(self, root):  # the <bsdf id=...> elements → self.by_id
         for b in root.findall("bsdf"):
@@ -1546,6 +1651,10 @@ class _Reader:
         delta_emitters = []
         for em in root.findall("emitter"):
             t = em.get("type")
+            if any(self._is_medium(c) for c in em):
+                if self.strict:
+                    raise SceneError("a <medium> inside an emitter (%r) is not supported: media are attached to shapes and to the sensor" % t)
+                self.warnings.append("medium inside emitter %r dropped (not supported)" % t)
             if t in ("point", "spot", "directional"):
                 delta_emitters.append(parse_delta_emitter(em, self))
             elif t == "constant" and environment is None and envmap is None:
@@ -1642,10 +1751,11 @@ class _Reader:
     def _attach(self, sh, meshes, analytic, out):
         """Give a <shape>'s geometry its material (nested <bsdf> or <ref id>) and area emitter and append it to `out`; refuses what analytic shapes cannot carry"""
         t, e, mat, em = sh.get("type"), sh.find("emitter"), None, -1
+        word = self._shape_media_word(sh)
         for c in sh:
             if c.tag == "bsdf":
                 mat = self._intern(self._make_bsdf(c))
-            elif c.tag == "ref":
+            elif c.tag == "ref" and not self._is_medium(c):
                 rid = c.get("id")
                 if rid not in self.by_id:
                     raise SceneError("<ref id=%r>: no such bsdf" % rid)
@@ -1661,7 +1771,7 @@ class _Reader:
                 return
             em = len(out["emitters"])
             out["emitters"].append(dict(radiance=tuple(float(v) for v in self._colour(e, "radiance", 1.0))))
-        out["meshes"] += [(mesh, mat, em) for mesh in meshes]
+        out["meshes"] += [(dict(mesh, media_word=word), mat, em) for mesh in meshes]
         if analytic is None:
             return
         material = self.materials[mat]
@@ -1669,6 +1779,7 @@ class _Reader:
             raise SceneError("%s: %s: textured BSDFs are only supported on triangle meshes (not on spheres, disks or cylinders)" % (t, material["blend"]["kind"]))
         if material.get("type") == 13:
             raise SceneError("%s: the null BSDF is only supported on triangle meshes (not on spheres, disks or cylinders)" % t)
+        out["sphere_media" if t == "sphere" else "shape_media"].append(word)
         if t == "sphere":
             out["spheres"].append(dict(analytic, material=mat, emitter=em))
         else:
@@ -1677,13 +1788,15 @@ class _Reader:
             out["shapes"].append(dict(analytic, material=mat, emitter=em))
 
     def _read_shapes(self, root):  # the <shape>s → meshes [(mesh dict, material index, emitter index or -1)], SceneDesc's emitters, spheres and shapes
-        out = dict(meshes=[], emitters=[], spheres=[], shapes=[])
+        out = dict(meshes=[], emitters=[], spheres=[], shapes=[], sphere_media=[], shape_media=[])
         for sh in root.findall("shape"):
             geometry = self._shape_geometry(sh)
             if geometry is not None:
                 self._attach(sh, *geometry, out)
         if not out["meshes"] and not out["spheres"] and not out["shapes"]:
             raise SceneError("scene without shapes")
+        for k in ("sphere_media", "shape_media"):  # (None: no transitions among them)
+            out[k] = np.asarray(out[k], np.uint32) if any(out[k]) else None
         return out.pop("meshes"), out
 
     def _flatten(self, meshes):
@@ -1696,7 +1809,7 @@ class _Reader:
         any_uvs = any(m.get("uvs") is not None and wants_uvs(mat) for m, mat, _ in meshes)
         # (each list starts with an empty array of its type: a scene of analytic shapes only has no mesh to concatenate)
         pos, idx, tmat, tem = [np.zeros((0, 3), f32)], [np.zeros((0, 3), np.uint32)], [np.zeros(0, np.uint32)], [np.zeros(0, np.int32)]
-        nrm, uvl, nv = [], [], 0
+        nrm, uvl, nv, tmed = [], [], 0, [np.zeros(0, np.uint32)]
         for mesh, mat, em in meshes:
             p, i, n = mesh["positions"], mesh["indices"], mesh["normals"]
             uv = mesh.get("uvs") if wants_uvs(mat) else None
@@ -1718,14 +1831,15 @@ class _Reader:
             pos.append(p); idx.append(i + np.uint32(nv)); nrm.append(n)
             uvl.append(uv.astype(f32) if uv is not None else np.full((p.shape[0], 2), np.nan, f32))
             nv += p.shape[0]
-            tmat.append(np.full(T, mat, np.uint32)); tem.append(np.full(T, em, np.int32))
-        return dict(positions=np.concatenate(pos).astype(f32), indices=np.concatenate(idx).astype(np.uint32), tri_material=np.concatenate(tmat),
+            tmat.append(np.full(T, mat, np.uint32)); tem.append(np.full(T, em, np.int32)); tmed.append(np.full(T, mesh.get("media_word", 0), np.uint32))
+        tri_media = np.concatenate(tmed)
+        return dict(tri_media=tri_media if tri_media.any() else None, positions=np.concatenate(pos).astype(f32), indices=np.concatenate(idx).astype(np.uint32), tri_material=np.concatenate(tmat),
                     tri_emitter=np.concatenate(tem), normals=np.concatenate(nrm).astype(f32) if any_normals else None,
                     texcoords=np.concatenate(uvl).astype(f32) if any_uvs else None)
 
     def _assemble(self, meshes, **fields):  # the SceneDesc of the reader's tables, the flattened meshes and what the element readers returned
         from .bindings import expand_blends  # (children of blended materials join the list, behind everything a shape refers to)
-        return SceneDesc(materials=expand_blends(self.materials), textures=self.textures, rtrans=np.stack(self.rt_slices).astype(f32) if self.rt_slices else None,
+        return SceneDesc(materials=expand_blends(self.materials), textures=self.textures, media=self.media, rtrans=np.stack(self.rt_slices).astype(f32) if self.rt_slices else None,
                          **self._flatten(meshes), **fields)
 
 
@@ -1752,6 +1866,7 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
         raise SceneError("%s: root element is <%s>, expected <scene>" % (path, root.tag))
     rd = _Reader(root, path, defines, strict, data_dir, mitsuba_src)
     props, fields = rd._read_integrator(root)
+    rd._read_media(root)
     sensor, info = rd._read_sensor(root, width, height)
     rd._read_named_bsdfs(root)
     lights = rd._read_emitters(root)
@@ -1768,6 +1883,8 @@ def load_scene(path, defines=None, strict=True, width=None, height=None, data_di
 def save_scene_xml(desc, props, directory, name="scene"):
     """Write `desc` as <directory>/<name>.xml + meshes/*.obj in the subset above (one OBJ per material / emitter group),
     so that a procedural scene can be rendered by the reference itself — or read back by load_scene().  Returns the XML path."""
+    if getattr(desc, "media", None):
+        raise NotImplementedError("save_scene_xml: participating media (SceneDesc.media) are not written")
     os.makedirs(os.path.join(directory, "meshes"), exist_ok=True)
     cam = desc.camera
     c = lambda v: ", ".join(repr(float(x)) for x in v)  # noqa: E731

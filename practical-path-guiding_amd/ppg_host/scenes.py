@@ -21,7 +21,8 @@ from . import bindings as B
 
 class SceneDesc:
     def __init__(self, positions, indices, tri_material, tri_emitter, materials, emitters, camera, normals=None, environment=None, rtrans=None, spheres=None, envmap=None,
-                 texcoords=None, textures=None, rfilter=None, lens=None, delta_emitters=None, shapes=None):
+                 texcoords=None, textures=None, rfilter=None, lens=None, delta_emitters=None, shapes=None, media=None, tri_media=None,
+                 sphere_media=None, shape_media=None, camera_medium=0):
         self.positions, self.indices = positions, indices
         self.tri_material, self.tri_emitter = tri_material, tri_emitter
         self.materials, self.emitters, self.camera, self.normals = materials, emitters, camera, normals
@@ -38,6 +39,12 @@ class SceneDesc:
                                                           # after the area emitters and before the environment emitter
         self.shapes = list(shapes or [])  # analytic disks and cylinders: dicts {type, to_world, radius, length, material, emitter, flip_normals}
                                           # (bindings.Shape); primitives after the triangles and the spheres
+        # homogeneous participating media (include/ppg.h ppg_set_media; HIP library only): dicts (bindings.Medium), and who lies in which —
+        # one binding word per triangle / sphere / shape (bindings.media_word(interior, exterior); None: no transitions among them) and the
+        # sensor's medium as 1 + its index (0: none)
+        self.media = list(media or [])
+        self.tri_media, self.sphere_media, self.shape_media = tri_media, sphere_media, shape_media
+        self.camera_medium = int(camera_medium)
 
     @property
     def n_triangles(self):
@@ -257,6 +264,8 @@ BLOCKS = [  # row k is the block of bit k: environment, rtrans, spheres, envmap,
 def save_scene(desc, path):
     """Write the flat binary scene that load_scene_file() and host/ppg_render.cpp read (the format: host/scene_file.h).  Children that
     blended materials state as dicts are appended to the material list first (bindings.expand_blends)."""
+    if B.has_media(desc):
+        raise NotImplementedError("save_scene: participating media (SceneDesc.media) are not part of the .ppgs container")
     if B.has_blends(desc):
         import copy
         desc = copy.copy(desc)
