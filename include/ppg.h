@@ -619,6 +619,60 @@ typedef struct ppg_media {
 int ppg_set_media(ppg_ctx *ctx, const ppg_media *media);
 
 /* ------------------------------------------------------------------------------------------------
+ * Heterogeneous participating media (medium/heterogeneous.cpp with method = woodcock, its default) over constant and grid volumes
+ * (volume/constvolume.cpp, volume/gridvolume.cpp, float32 data): a density field and an albedo field, delta (Woodcock) tracking for
+ * sampleDistance (heterogeneous.cpp:613-662) and the two-run tracking estimate for evalTransmittance (:553-585), which draws random
+ * numbers from the path's own stream, in the reference's order.
+ * One more side list: call before ppg_set_media / ppg_set_scene; ppg_set_scene validates and consumes it together with the media list;
+ * the context keeps it until it is replaced (NULL, or n_entries = 0, clears it); PPG_ERR_STATE between ppg_begin_render and
+ * ppg_end_render.  ppg_medium and ppg_media stay as they are: an entry here names a medium of ppg_media's list and makes it heterogeneous.
+ * Of such a medium sigma_a, sigma_s, strategy, channel, sampling_density are not read and must be 0, sampling_weight 0 or -1; phase and g
+ * hold as for a homogeneous medium.
+ *   volumes   PPG_VOLUME_CONST: `value` (channels = 1: value[0]; 3: an RGB triple).  PPG_VOLUME_GRID: res = (x, y, z) nodes, channels 1 or
+ *             3, float32 data in the order ((z * res[1] + y) * res[0] + x) * channels + c, the data's box aabb_min / aabb_max in the
+ *             volume's own space and to_world (row-major 4x4, affine).  The lookup is trilinear between the nodes and 0 outside them
+ *             (gridvolume.cpp:337-388).  ppg_set_scene derives worldToGrid = scale((res - 1) / extents) * translate(-aabb_min) *
+ *             to_world^-1 (gridvolume.cpp:188-201) and the world-space box of the eight transformed corners.
+ *   entries   medium = index into ppg_media.media; density = a one-channel volume; albedo = a three-channel volume; scale multiplies the
+ *             density.  maxDensity = scale * (1 for a grid: Mitsuba's tracking assumes a grid density of at most 1; the value for a
+ *             const volume) and its inverse are derived as heterogeneous.cpp:239-242 does.  A const density has the reference's default
+ *             box, on which AABB::rayIntersect answers (-inf, +inf) — and false for a ray with a zero direction component.
+ * ppg_set_scene returns PPG_ERR_INVALID, names the entry in ppg_last_error and leaves the previous scene set for: a list without a media
+ * list; an index out of range; a medium named twice; a density volume with channels != 1 or an albedo volume with channels != 3; an
+ * unknown kind; a res component below 2; an empty or non-finite data box; a singular or non-finite to_world; a scale that is not finite
+ * and positive; a const density that is not finite and positive; a grid density texel outside [0, 1] or not finite; an albedo value
+ * outside [0, 1] or not finite; a coefficient of the named medium that is not 0; a non-zero reserved word; a grid without data; and a grid
+ * density whose expected tracking length is too long: scale * the diagonal of its world box above PPG_HETMEDIUM_MAX_MEAN_STEPS majorant
+ * free paths (one segment's loop would run that many steps per lane).  Sharded renders refuse such a scene as they refuse every medium.
+ * A scene that binds a heterogeneous medium runs the "hetmedia" kernels (csrc: PPG_HETMEDIA), whatever else it holds.
+ * ---------------------------------------------------------------------------------------------- */
+enum { PPG_VOLUME_CONST = 0, PPG_VOLUME_GRID = 1 };
+#define PPG_HETMEDIUM_MAX_MEAN_STEPS 4096.0f
+typedef struct ppg_volume {
+    int32_t kind;                 /* PPG_VOLUME_*                                                     offset   0 */
+    int32_t channels;             /* 1 or 3                                                                    4 */
+    float value[3];               /* const                                                                     8 */
+    int32_t res[3];               /* grid: nodes along x, y, z                                                20 */
+    float aabb_min[3], aabb_max[3]; /* grid: the data's box                                               32, 44 */
+    float to_world[16];           /* grid: row-major                                                          56 */
+    uint32_t _reserved[2];        /* must be 0                                                               120 */
+    const float *data;            /* grid: [res[2] * res[1] * res[0] * channels]                             128 */
+} ppg_volume;                     /* 136 bytes */
+typedef struct ppg_medium_volumes {
+    uint32_t medium;              /* index into ppg_media.media                                                0 */
+    uint32_t density, albedo;     /* indices into ppg_media_volumes.volumes                                 4, 8 */
+    float scale;                  /*                                                                          12 */
+    uint32_t _reserved[4];        /* must be 0                                                                16 */
+} ppg_medium_volumes;             /* 32 bytes */
+typedef struct ppg_media_volumes {
+    uint32_t n_volumes, n_entries;      /*                                                                  0, 4 */
+    const ppg_volume *volumes;          /* [n_volumes]                                                         8 */
+    const ppg_medium_volumes *entries;  /* [n_entries]                                                        16 */
+    uint32_t _reserved[4];              /* must be 0                                                          24 */
+} ppg_media_volumes;                    /* 40 bytes */
+int ppg_set_media_volumes(ppg_ctx *ctx, const ppg_media_volumes *volumes);
+
+/* ------------------------------------------------------------------------------------------------
  * Rendering.  ppg_render() is GuidedPathTracer::render() (GP:1516-1585, IH:74-75) in one call.
  * The stepwise calls expose its phases so a multi-GPU driver can all-reduce the SD-tree statistics
  * between ppg_render_passes() and ppg_build_sdtree(); ppg_render() is exactly their composition

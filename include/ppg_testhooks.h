@@ -344,6 +344,39 @@ struct ppg_debug_medium_out {
 };                                /* 60 bytes */
 int ppg_debug_medium(struct ppg_ctx *ctx, uint32_t n, const struct ppg_debug_medium_item *items, struct ppg_debug_medium_out *out);
 
+/* The hetmedia family's device functions (csrc/ppg_device.h: volume_lookup_float / volume_lookup_rgb, hetmedium_sample_distance,
+   hetmedium_transmittance), item by item, over the volumes and media of the scene that is set — which must bind a heterogeneous medium
+   (include/ppg.h ppg_set_media_volumes), else PPG_ERR_STATE.
+   ppg_debug_volume: the lookup of volume `volume` at the world-space point p; a one-channel volume answers in value[0] (value[1], value[2] = 0).
+   ppg_debug_hetmedium: HeterogeneousMedium::sampleDistance on the ray (o, d) with mint = 0 and the given maxt (may be infinite), then
+   evalTransmittance on the same ray; the random numbers are ppg_rand(key, dim), ppg_rand(key, dim + 1), ..: sampleDistance takes `draws`
+   of them, evalTransmittance the next `eval_draws`.  t, sigma_s and transmittance are mRec's (t = 0 and zeros on failure); medium must name
+   a heterogeneous medium.  PPG_ERR_INVALID: an index out of range, a medium that is not heterogeneous. */
+struct ppg_debug_volume_item {
+    int32_t volume;
+    float p[3];
+};                                /* 16 bytes */
+struct ppg_debug_volume_out {
+    float value[3];
+};                                /* 12 bytes */
+int ppg_debug_volume(struct ppg_ctx *ctx, uint32_t n, const struct ppg_debug_volume_item *items, struct ppg_debug_volume_out *out);
+struct ppg_debug_hetmedium_item {
+    int32_t medium;
+    float o[3], d[3];
+    float maxt;
+    uint32_t key, dim;
+};                                /* 40 bytes */
+struct ppg_debug_hetmedium_out {
+    int32_t success;
+    float t;
+    float sigma_s[3];
+    float transmittance;
+    uint32_t draws;
+    float eval_transmittance;
+    uint32_t eval_draws;
+};                                /* 36 bytes */
+int ppg_debug_hetmedium(struct ppg_ctx *ctx, uint32_t n, const struct ppg_debug_hetmedium_item *items, struct ppg_debug_hetmedium_out *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -419,6 +419,48 @@ static void launch_debug_medium(int grid, int block, hipStream_t stream, const M
 }
 #endif
 
+#if PPG_FAMILY == PPG_FAMILY_HETMEDIA
+// ppg_debug_volume: volume_lookup_float / volume_lookup_rgb as this family's kernels compile them, item by item (the host has checked
+// every index)
+__global__ void k_debug_volume(HetArgs V, unsigned int n, const ppg_debug_volume_item *items, ppg_debug_volume_out *out) {
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const ppg_debug_volume_item it = items[i];
+    const F3 p = f3(it.p[0], it.p[1], it.p[2]);
+    ppg_debug_volume_out r;
+    const int channels = __float_as_int(V.volumes[PPG_VOLUME_STRIDE * (size_t)it.volume].x) >> 8;
+    if (channels == 1) { r.value[0] = volume_lookup_float(V.volumes, V.pool, it.volume, p); r.value[1] = r.value[2] = 0.0f; }
+    else { const F3 v = volume_lookup_rgb(V.volumes, V.pool, it.volume, p); r.value[0] = v.x; r.value[1] = v.y; r.value[2] = v.z; }
+    out[i] = r;
+}
+static void launch_debug_volume(int grid, int block, hipStream_t stream, const HetArgs &V, unsigned int n, const ppg_debug_volume_item *items, ppg_debug_volume_out *out) {
+    hipLaunchKernelGGL(k_debug_volume, dim3(grid), dim3(block), 0, stream, V, n, items, out);
+}
+// ppg_debug_hetmedium: hetmedium_sample_distance on the ray over [0, maxt], then hetmedium_transmittance on the same ray, the random
+// numbers ppg_rand(key, dim), ppg_rand(key, dim + 1), .. in that order
+__global__ void k_debug_hetmedium(HetArgs V, unsigned int n, const ppg_debug_hetmedium_item *items, ppg_debug_hetmedium_out *out) {
+    const unsigned int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const ppg_debug_hetmedium_item it = items[i];
+    const float4 *Hr = het_record(V.het, (unsigned int)it.medium + 1u);
+    const F3 o = f3(it.o[0], it.o[1], it.o[2]), d = f3(it.d[0], it.d[1], it.d[2]);
+    unsigned int dim = it.dim;
+    const unsigned int key = it.key;
+    ppg_debug_hetmedium_out r;
+    HetSample hs;
+    r.success = hetmedium_sample_distance(V.volumes, V.pool, Hr, o, d, 0.0f, it.maxt, [&]() { return ppg_rand(key, dim++); }, hs) ? 1 : 0;
+    r.t = hs.t; r.sigma_s[0] = hs.sigmaS.x; r.sigma_s[1] = hs.sigmaS.y; r.sigma_s[2] = hs.sigmaS.z; r.transmittance = hs.transmittance;
+    r.draws = dim - it.dim;
+    const unsigned int dim1 = dim;
+    r.eval_transmittance = hetmedium_transmittance(V.volumes, V.pool, Hr, o, d, 0.0f, it.maxt, [&]() { return ppg_rand(key, dim++); });
+    r.eval_draws = dim - dim1;
+    out[i] = r;
+}
+static void launch_debug_hetmedium(int grid, int block, hipStream_t stream, const HetArgs &V, unsigned int n, const ppg_debug_hetmedium_item *items, ppg_debug_hetmedium_out *out) {
+    hipLaunchKernelGGL(k_debug_hetmedium, dim3(grid), dim3(block), 0, stream, V, n, items, out);
+}
+#endif
+
 // the hooks' launchers of this family, into its row
 static void fill_debug_kernels(PathKernels &K) {
     K.debug_math_eval = launch_debug_math_eval;
@@ -436,6 +478,10 @@ static void fill_debug_kernels(PathKernels &K) {
 #endif
 #if PPG_FAMILY == PPG_FAMILY_MEDIA
     K.debug_medium = launch_debug_medium;
+#endif
+#if PPG_FAMILY == PPG_FAMILY_HETMEDIA
+    K.debug_volume = launch_debug_volume;
+    K.debug_hetmedium = launch_debug_hetmedium;
 #endif
 }
 

@@ -38,8 +38,9 @@
 #define PPG_FAMILY_BLEND 4   // _blend    the blendbsdf / mixturebsdf combinators (ppg_set_blends), whatever else the scene holds
 #define PPG_FAMILY_LOBES 5   // _lobes    the roughdiffuse, difftrans and phong BSDFs (PPG_BSDF_ROUGHDIFFUSE ..), whatever else the scene holds; being the top
                              //           family it also compiles the normalmap adapter and the null BSDF (PPG_NORMALMAP_NULL)
-#define PPG_FAMILY_MEDIA 6   // _media    homogeneous participating media (ppg_set_media with a binding), whatever else the scene holds: now the top family
-#define PPG_FAMILIES 7
+#define PPG_FAMILY_MEDIA 6   // _media    homogeneous participating media (ppg_set_media with a binding), whatever else the scene holds
+#define PPG_FAMILY_HETMEDIA 7  // _hetmedia  heterogeneous participating media (ppg_set_media_volumes names a bound medium), whatever else the scene holds: now the top family
+#define PPG_FAMILIES 8
 #define PPG_DEBUG_FAMILIES 6  // the families whose copies the item-by-item test hooks address by number (the media family adds nothing to that code)
 #define PPG_SUFFIX_0
 #define PPG_SUFFIX_1 _shapes
@@ -48,6 +49,7 @@
 #define PPG_SUFFIX_4 _blend
 #define PPG_SUFFIX_5 _lobes
 #define PPG_SUFFIX_6 _media
+#define PPG_SUFFIX_7 _hetmedia
 #ifndef PPG_FAMILY
 #define PPG_FAMILY 0  // (a digit: it is pasted to PPG_SUFFIX_)
 #endif
@@ -57,6 +59,7 @@
 #define PPG_BLEND (PPG_FAMILY >= PPG_FAMILY_BLEND)
 #define PPG_LOBES (PPG_FAMILY >= PPG_FAMILY_LOBES)
 #define PPG_MEDIA (PPG_FAMILY >= PPG_FAMILY_MEDIA)
+#define PPG_HETMEDIA (PPG_FAMILY >= PPG_FAMILY_HETMEDIA)
 // the normalmap adapter (PPG_MAT_NORMALMAP) and the null BSDF (PPG_BSDF_NULL): no family of their own — the top family, which holds
 // everything below it, compiles them, and sceneFamily sends a scene with either there
 #define PPG_NORMALMAP_NULL (PPG_FAMILY >= PPG_FAMILY_LOBES)
@@ -257,7 +260,31 @@ struct MediaArgs {
     unsigned int *path_medium;
     unsigned int path_stride;
 };
-#if PPG_MEDIA
+// ppg_set_media_volumes with a bound heterogeneous medium: what the hetmedia kernels (PPG_HETMEDIA) get on top of MediaArgs, carried and
+// appended the same way (the media family's kernels, ppg_debug_medium's among them, keep MediaArgs as it is).
+//   volumes  PPG_VOLUME_STRIDE float4 per volume = (kind | channels << 8, res x, res y, res z as ints) (worldToGrid rows 0, 1, 2: an affine 3x4)
+//            (value r, g, b; the grid's first float in `pool` as an int)
+//   pool     the grids' float32 data, one after the other, each in the reference's order ((z * ry + y) * rx + x) * channels + c
+//   het      PPG_HET_STRIDE float4 per medium = (1 + density volume, 0 = a homogeneous medium; albedo volume; scale; invMaxDensity)
+//            (the density's world box min, -) (its max, -): the reference's default box (+inf, -inf) for a const density
+struct HetArgs {
+    const float4 *volumes;
+    const float *pool;
+    const float4 *het;
+    int n_volumes;
+};
+#if PPG_HETMEDIA
+struct DevSceneMedia : DevScene {
+    const float4 *media;
+    const unsigned int *prim_media;
+};
+struct DevSceneHet : DevSceneMedia {
+    const float4 *volumes;
+    const float *pool;
+    const float4 *het;
+};
+typedef DevSceneHet SceneArg;
+#elif PPG_MEDIA
 struct DevSceneMedia : DevScene {
     const float4 *media;
     const unsigned int *prim_media;
@@ -267,6 +294,9 @@ typedef DevSceneMedia SceneArg;
 typedef DevScene SceneArg;
 #endif
 #define PPG_MEDIUM_STRIDE 3
+#define PPG_VOLUME_STRIDE 5
+#define PPG_HET_STRIDE 3
+#define PPG_HETMEDIUM_STEP_CAP 65536  // a tracking loop's steps: sixteen times the host's bound on their mean (PPG_HETMEDIUM_MAX_MEAN_STEPS); reaching it ends the segment as opaque
 #define PPG_BLEND_STRIDE 4
 #define PPG_BLENDW_CHILD 0        // word offsets into a material's 16 words
 #define PPG_BLENDW_WEIGHT 4
@@ -1653,6 +1683,155 @@ D float phase_sample(const float4 *Q, F3 wi, float sx, float sy, F3 &wo) {
 // primitive `prim` along d — the exterior one when dot(d, geometric normal) > 0, else the interior one; `word` = 0: no transition
 D unsigned int medium_target(unsigned int word, F3 d, F3 geoN) { return dot3(d, geoN) > 0 ? (word >> 16) : (word & 0xffffu); }
 D unsigned int medium_word(const DevSceneMedia &S, int prim) { return S.prim_media ? S.prim_media[prim] : 0u; }
+#endif
+
+#if PPG_HETMEDIA
+// ------------------------------------------------------------------------------------------------
+// Heterogeneous media (medium/heterogeneous.cpp, method = woodcock) over const and grid volumes (volume/constvolume.cpp, gridvolume.cpp),
+// restated.  A volume is PPG_VOLUME_STRIDE float4 of DevSceneHet::volumes, a medium's heterogeneous record PPG_HET_STRIDE float4 of ::het.
+// ------------------------------------------------------------------------------------------------
+D const float4 *het_record(const float4 *het, unsigned int med) { return het + PPG_HET_STRIDE * (size_t)(med - 1u); }  // med = 1 + index
+D bool het_is(const float4 *Hr) { return __float_as_int(Hr[0].x) != 0; }
+// a lookup's cell: m_worldToGrid.transformAffine(p), floorToInt, the bounds test (gridvolume.cpp:338-346); false: the lookup answers 0
+struct VolumeCell {
+    int i000, sx, sy, sz;  // index of the node (x1, y1, z1) and the strides to x2, y2, z2, in nodes
+    float fx, fy, fz;
+};
+D bool volume_cell(const float4 *V, F3 p_, VolumeCell &c) {
+    const float4 q0 = V[0], r0 = V[1], r1 = V[2], r2 = V[3];
+    const int rx = __float_as_int(q0.y), ry = __float_as_int(q0.z), rz = __float_as_int(q0.w);
+    const float px = r0.x * p_.x + r0.y * p_.y + r0.z * p_.z + r0.w;
+    const float py = r1.x * p_.x + r1.y * p_.y + r1.z * p_.z + r1.w;
+    const float pz = r2.x * p_.x + r2.y * p_.y + r2.z * p_.z + r2.w;
+    // (a NaN coordinate fails this test, where the reference's floorToInt is undefined; anything beyond int's range lies outside as well)
+    if (!(px >= 0.0f && py >= 0.0f && pz >= 0.0f && px < (float)rx && py < (float)ry && pz < (float)rz)) return false;
+    const int x1 = (int)__builtin_floorf(px), y1 = (int)__builtin_floorf(py), z1 = (int)__builtin_floorf(pz);
+    if (x1 + 1 >= rx || y1 + 1 >= ry || z1 + 1 >= rz) return false;
+    c.fx = px - x1; c.fy = py - y1; c.fz = pz - z1;
+    c.i000 = (z1 * ry + y1) * rx + x1;
+    c.sx = 1; c.sy = rx; c.sz = ry * rx;
+    return true;
+}
+// VolumeDataSource::lookupFloat: constvolume.cpp, or gridvolume.cpp:337-388 (EFloat32) with its order of operations
+D float volume_lookup_float(const float4 *volumes, const float *pool, int vol, F3 p) {
+    const float4 *V = volumes + PPG_VOLUME_STRIDE * (size_t)vol;
+    const float4 q4 = V[4];
+    if ((__float_as_int(V[0].x) & 0xff) == PPG_VOLUME_CONST) return q4.x;
+    VolumeCell c;
+    if (!volume_cell(V, p, c)) return 0.0f;
+    const float *D0 = pool + (size_t)__float_as_int(q4.w) + c.i000;
+    // eight independent loads, issued together
+    const float d000 = D0[0], d001 = D0[c.sx], d010 = D0[c.sy], d011 = D0[c.sy + c.sx];
+    const float d100 = D0[c.sz], d101 = D0[c.sz + c.sx], d110 = D0[c.sz + c.sy], d111 = D0[c.sz + c.sy + c.sx];
+    const float fx = c.fx, fy = c.fy, fz = c.fz, _fx = 1.0f - fx, _fy = 1.0f - fy, _fz = 1.0f - fz;
+    return ((d000 * _fx + d001 * fx) * _fy + (d010 * _fx + d011 * fx) * fy) * _fz + ((d100 * _fx + d101 * fx) * _fy + (d110 * _fx + d111 * fx) * fy) * fz;
+}
+// VolumeDataSource::lookupSpectrum: constvolume.cpp, or gridvolume.cpp's RGB twin of the above (float3 texels)
+D F3 volume_lookup_rgb(const float4 *volumes, const float *pool, int vol, F3 p) {
+    const float4 *V = volumes + PPG_VOLUME_STRIDE * (size_t)vol;
+    const float4 q4 = V[4];
+    if ((__float_as_int(V[0].x) & 0xff) == PPG_VOLUME_CONST) return f3(q4.x, q4.y, q4.z);
+    VolumeCell c;
+    if (!volume_cell(V, p, c)) return f3s(0.0f);
+    const float *D0 = pool + (size_t)__float_as_int(q4.w) + 3 * (size_t)c.i000;
+    const int sx = 3 * c.sx, sy = 3 * c.sy, sz = 3 * c.sz;
+    const float fx = c.fx, fy = c.fy, fz = c.fz, _fx = 1.0f - fx, _fy = 1.0f - fy, _fz = 1.0f - fz;
+    float r[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float d000 = D0[k], d001 = D0[sx + k], d010 = D0[sy + k], d011 = D0[sy + sx + k];
+        const float d100 = D0[sz + k], d101 = D0[sz + sx + k], d110 = D0[sz + sy + k], d111 = D0[sz + sy + sx + k];
+        r[k] = ((d000 * _fx + d001 * fx) * _fy + (d010 * _fx + d011 * fx) * fy) * _fz + ((d100 * _fx + d101 * fx) * _fy + (d110 * _fx + d111 * fx) * fy) * fz;
+    }
+    return f3(r[0], r[1], r[2]);
+}
+// AABB::rayIntersect (aabb.h:317-347), dRcp = 1 / d per component (ray.h).  On the default box (min = +inf, max = -inf) of a const volume
+// it answers (-inf, +inf) — and false for a ray with a zero direction component, as the reference does.
+D bool aabb_ray_intersect(F3 mn, F3 mx, F3 o, F3 d, float &nearT, float &farT) {
+    nearT = -__builtin_inff();
+    farT = __builtin_inff();
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float origin = comp3(o, i), minVal = comp3(mn, i), maxVal = comp3(mx, i), di = comp3(d, i);
+        if (di == 0) {
+            if (origin < minVal || origin > maxVal) return false;
+        } else {
+            const float rcp = 1.0f / di;
+            float t1 = (minVal - origin) * rcp, t2 = (maxVal - origin) * rcp;
+            if (t1 > t2) { const float tmp = t1; t1 = t2; t2 = tmp; }
+            nearT = ppg_max(t1, nearT);  // std::max(t1, nearT) = (t1 < nearT) ? nearT : t1
+            farT = ppg_min(t2, farT);
+            if (!(nearT <= farT)) return false;
+        }
+    }
+    return true;
+}
+struct HetSample {
+    float t, transmittance;
+    F3 sigmaS;
+};
+// HeterogeneousMedium::sampleDistance, Woodcock branch (heterogeneous.cpp:613-662), on the ray (o, d) over [mint, maxt]; next() is the
+// sampler's next1D().  pdfSuccess = pdfFailure = 1; on failure mRec.transmittance = 1, which hs.transmittance says as well.  The loop
+// leaves when !(t < maxt), so a NaN cannot keep it running, and after PPG_HETMEDIUM_STEP_CAP steps, as opaque (transmittance 0, no event).
+template <typename Next>
+D bool hetmedium_sample_distance(const float4 *volumes, const float *pool, const float4 *Hr, F3 o, F3 d, float rmint, float rmaxt, Next next, HetSample &hs) {
+    const float4 h0 = Hr[0], h1 = Hr[1], h2 = Hr[2];
+    const int densityVol = __float_as_int(h0.x) - 1, albedoVol = __float_as_int(h0.y);
+    const float scale = h0.z, invMaxDensity = h0.w;
+    hs.t = 0.0f; hs.transmittance = 1.0f; hs.sigmaS = f3s(0.0f);
+    float mint, maxt;
+    if (!aabb_ray_intersect(f3(h1.x, h1.y, h1.z), f3(h2.x, h2.y, h2.z), o, d, mint, maxt)) return false;
+    mint = ppg_max(mint, rmint);
+    maxt = ppg_min(maxt, rmaxt);
+    float t = mint;
+    for (int step = 0; step < PPG_HETMEDIUM_STEP_CAP; ++step) {
+        t -= dm_log(1 - next()) * invMaxDensity;
+        if (!(t < maxt)) return false;
+        const F3 p = o + d * t;
+        const float densityAtT = volume_lookup_float(volumes, pool, densityVol, p) * scale;
+        if (densityAtT * invMaxDensity > next()) {
+            hs.t = t;
+            const F3 albedo = volume_lookup_rgb(volumes, pool, albedoVol, p);
+            hs.sigmaS = albedo * densityAtT;
+            float tr = densityAtT != 0.0f ? 1.0f / densityAtT : 0.0f;
+            if (!(ppg_abs(tr) < __builtin_inff())) tr = 0.0f;  // !std::isfinite: prevent rare overflow
+            hs.transmittance = tr;
+            return true;
+        }
+    }
+    hs.transmittance = 0.0f;
+    return false;
+}
+// HeterogeneousMedium::evalTransmittance with a sampler (heterogeneous.cpp:553-585): the mean of two tracked runs — one of 0, 0.5, 1
+template <typename Next>
+D float hetmedium_transmittance(const float4 *volumes, const float *pool, const float4 *Hr, F3 o, F3 d, float rmint, float rmaxt, Next next) {
+    const float4 h0 = Hr[0], h1 = Hr[1], h2 = Hr[2];
+    const int densityVol = __float_as_int(h0.x) - 1;
+    const float scale = h0.z, invMaxDensity = h0.w;
+    float mint, maxt;
+    if (!aabb_ray_intersect(f3(h1.x, h1.y, h1.z), f3(h2.x, h2.y, h2.z), o, d, mint, maxt)) return 1.0f;
+    mint = ppg_max(mint, rmint);
+    maxt = ppg_min(maxt, rmaxt);
+    float result = 0;
+    for (int i = 0; i < 2; ++i) {
+        float t = mint;
+        for (int step = 0; step < PPG_HETMEDIUM_STEP_CAP; ++step) {
+            t -= dm_log(1 - next()) * invMaxDensity;
+            if (!(t < maxt)) { result += 1; break; }
+            const F3 p = o + d * t;
+            const float density = volume_lookup_float(volumes, pool, densityVol, p) * scale;
+            if (density * invMaxDensity > next()) break;
+        }
+    }
+    return result / 2;
+}
+// Medium::evalTransmittance of medium `med` (1 + index) over [mint, maxt] of the ray (o, d), whichever kind it is
+template <typename Next>
+D F3 any_medium_transmittance(const DevSceneHet &S, unsigned int med, F3 o, F3 d, float mint, float maxt, Next next) {
+    const float4 *Hr = het_record(S.het, med);
+    if (het_is(Hr)) return f3s(hetmedium_transmittance(S.volumes, S.pool, Hr, o, d, mint, maxt, next));
+    return medium_transmittance(medium_record(S.media, med), maxt - mint);
+}
 #endif
 
 // Transform::operator()(Point) (transform.h:108-125) and operator()(Vector) (:175-183)

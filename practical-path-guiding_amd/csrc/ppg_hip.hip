@@ -373,6 +373,16 @@ struct ppg_ctx {
     DevBuf<float4> d_media;
     DevBuf<unsigned int> d_primMedia, d_pathMedium;
     MediaArgs mediaArgs{};         // of the scene that is set: what the media kernels get beside it (all zero: the scene binds no medium)
+    // ppg_set_media_volumes: kept until replaced (volumesList points into the vectors; n_entries = 0: none); ppg_set_scene validates it and
+    // builds d_volumes, d_volPool and d_het from it
+    ppg_media_volumes volumesList{};
+    std::vector<ppg_volume> volumes;
+    std::vector<std::vector<float>> volumeData;
+    std::vector<ppg_medium_volumes> volumeEntries;
+    DevBuf<float4> d_volumes, d_het;
+    DevBuf<float> d_volPool;
+    std::vector<char> hetMedium;   // of the scene that is set: per medium, whether it is heterogeneous
+    HetArgs hetArgs{};             // of the scene that is set: what the hetmedia kernels get on top (all zero: no bound medium is heterogeneous)
     uint32_t nMaterials = 0;       // of the scene set last (ppg_debug_bsdf checks its items against it)
     bool renderOpen = false;       // between ppg_begin_render and ppg_end_render
     int W = 0, H = 0;
@@ -560,8 +570,9 @@ struct ppg_ctx {
 PathKernels ppg_path_kernels[PPG_FAMILIES];  // filled by the units of ppg_inst.hip when the library is loaded
 
 // The kernel family a scene runs: the lowest that has everything the scene needs (ppg_device.h).
-static int sceneFamily(const DevScene &S, const MediaArgs &M) {
-    if (M.media) return PPG_FAMILY_MEDIA;      // a medium is bound to a primitive or to the camera: the top family, whatever else the scene holds
+static int sceneFamily(const DevScene &S, const MediaArgs &M, const HetArgs &V) {
+    if (V.het) return PPG_FAMILY_HETMEDIA;     // a bound medium is heterogeneous: the top family, whatever else the scene holds
+    if (M.media) return PPG_FAMILY_MEDIA;      // a medium is bound to a primitive or to the camera: the media family, whatever else the scene holds
     if (S.lobes) return PPG_FAMILY_LOBES;      // a roughdiffuse, difftrans or phong material, a normal-mapped or a null one: the top family, whatever else the scene holds
     if (S.blend) return PPG_FAMILY_BLEND;      // a blended material: the blend family, whatever else the scene holds
     if (S.coat) return PPG_FAMILY_COAT;        // a coated material: the coat family, shapes and general entries or not
@@ -575,12 +586,12 @@ template <typename F> static F launcher(F f) {
     return f;
 }
 // variant = (NEE ? 2 : 0) | (FULL ? 1 : 0)
-static void ppg_launch_shade(int variant, const ShadeLaunch &a) { launcher(ppg_path_kernels[sceneFamily(a.S, a.M)].shade[variant >> 1])(variant, a); }
+static void ppg_launch_shade(int variant, const ShadeLaunch &a) { launcher(ppg_path_kernels[sceneFamily(a.S, a.M, a.V)].shade[variant >> 1])(variant, a); }
 // variant = (SMALL ? 4 : 0) | (NEE ? 2 : 0) | (FULL ? 1 : 0)
-static void ppg_launch_tail(int variant, const TailLaunch &a) { launcher(ppg_path_kernels[sceneFamily(a.S, a.M)].tail[variant >> 1])(variant, a); }
+static void ppg_launch_tail(int variant, const TailLaunch &a) { launcher(ppg_path_kernels[sceneFamily(a.S, a.M, a.V)].tail[variant >> 1])(variant, a); }
 // the scene is traced from LDS without a BVH (k_trace<true>, k_tail<true, ..>)
 static bool isSmallScene(const ppg_ctx *ctx) {
-    return ctx->scene.n_tris <= 64 && ctx->ldsTris == ctx->scene.n_tris && ctx->scene.n_spheres == 0 && sceneFamily(ctx->scene, ctx->mediaArgs) == PPG_FAMILY_BASE && !ctx->tuneForceBvh;
+    return ctx->scene.n_tris <= 64 && ctx->ldsTris == ctx->scene.n_tris && ctx->scene.n_spheres == 0 && sceneFamily(ctx->scene, ctx->mediaArgs, ctx->hetArgs) == PPG_FAMILY_BASE && !ctx->tuneForceBvh;
 }
 namespace {
 
@@ -1117,6 +1128,7 @@ struct Batch {
     PathState P, Pc;                // Pc: P with the contiguous copy of the path words, once copyMisc has made it
     DevScene S;
     MediaArgs M;                    // the media family's extra arguments
+    HetArgs V;                      // the hetmedia family's
     DevTree T;
     RenderParams R;
     Queues Q;
@@ -1190,7 +1202,7 @@ int launchStragglers(ppg_ctx *ctx, const Batch &B) {
         RenderParams Rt = B.R;
         Rt.defer_depth = 0u;
         TailLaunch a{shape.grid, B.ldsBytes, st, G.P, B.S, Tt, Rt, G.iota.p, G.count.p, G.ticket.p, ctx->queues.stats, ctx->ldsTris,
-                     ctx->d_tailLongest.p + (ctx->tailLaunches++ % PPG_TAIL_LOG), StragOut{nullptr, nullptr, nullptr}, shape.laneLimit, B.M};
+                     ctx->d_tailLongest.p + (ctx->tailLaunches++ % PPG_TAIL_LOG), StragOut{nullptr, nullptr, nullptr}, shape.laneLimit, B.M, B.V};
         if (a.M.path_medium) { a.M.path_medium = reinterpret_cast<unsigned int *>(G.rec.p + 6); a.M.path_stride = 32; }  // (k_tail left the word in the record's seventh float4)
         ppg_launch_tail(tailVariant(ctx), a);
     };
@@ -1426,6 +1438,7 @@ int prepareBatch(ppg_ctx *ctx, Batch &B, int batch, bool adamRound, const GroupL
     }
     B.S = ctx->scene;
     B.M = ctx->mediaArgs;
+    B.V = ctx->hetArgs;
     B.T = ctx->devTree();
     RenderParams &R = B.R;
     R = ctx->params();
@@ -1484,7 +1497,7 @@ int runWavefront(ppg_ctx *ctx, Batch &B) {
         unsigned char *const trKeys = sortSlices ? ctx->d_sortKeys.p : nullptr;
         timedLaunch(ctx, "k_trace", B.hostCount, [&] {
             TraceLaunch a{grid, traceLds, s, P, S, Q, qin, smallScene ? 0 : ctx->ldsNodes, ctx->ldsTris, trSorted, trKeys, smallScene, ctx->timer.enabled};
-            launcher(ppg_path_kernels[sceneFamily(S, B.M)].trace)(a);
+            launcher(ppg_path_kernels[sceneFamily(S, B.M, B.V)].trace)(a);
         });
         int shadeIn = sortSlices ? QIN_SORTED : qin;
         ctx->joinTree();  // (k_generate and the first k_trace ran beside the previous round's optimiser: k_shade needs its result)
@@ -1496,7 +1509,7 @@ int runWavefront(ppg_ctx *ctx, Batch &B) {
         const bool split = shadeIn == QIN_SORTED && Q.n_common && !neeOn;
         if (split) {
             timedLaunch(ctx, "k_shade<common>", B.hostCount, [&] {
-                ShadeLaunch a{grid, 0, s, P, S, B.T, B.R, Q, QIN_SORTED_COMMON, smallScene ? 1 : 0, ctx->d_queueSorted.p, B.M};
+                ShadeLaunch a{grid, 0, s, P, S, B.T, B.R, Q, QIN_SORTED_COMMON, smallScene ? 1 : 0, ctx->d_queueSorted.p, B.M, B.V};
                 ppg_launch_shade_common(a);
             });
             shadeIn = QIN_SORTED_REST;
@@ -1507,7 +1520,7 @@ int runWavefront(ppg_ctx *ctx, Batch &B) {
             const size_t neeBytes = smallScene ? triBytes : (size_t)PPG_LDS_STACK * PPG_BLOCK * 4;
             const size_t lds = (neeOn || ctx->scene.has_null) ? neeBytes : 0;
             const int variant = (neeOn ? 2 : 0) | (fullMats ? 1 : 0);
-            ShadeLaunch a{grid, lds, s, P, S, B.T, B.R, Q, shadeIn, small, ctx->d_queueSorted.p, B.M};
+            ShadeLaunch a{grid, lds, s, P, S, B.T, B.R, Q, shadeIn, small, ctx->d_queueSorted.p, B.M, B.V};
             ppg_launch_shade(variant, a);
         });
         qin = QIN_DENSE;
@@ -1536,7 +1549,7 @@ int launchTail(ppg_ctx *ctx, Batch &B, unsigned int depth, size_t handedPaths) {
         // (the launch's longest path is logged for launches that run their paths to the END: the sum is the tails' critical path; a launch that
         // hands its stragglers over writes to a spare slot nobody reads)
         TailLaunch a{shape.grid, B.ldsBytes, s, B.P, B.S, B.T, Rt, B.dense, ctx->d_total.p, ctx->d_ticket.p, B.Q.stats, ctx->ldsTris,
-                     ctx->d_tailLongest.p + (depth ? PPG_TAIL_LOG : (ctx->tailLaunches++ % PPG_TAIL_LOG)), StragOut{G.rec.p, G.orig.p, G.count.p}, shape.laneLimit, B.M};
+                     ctx->d_tailLongest.p + (depth ? PPG_TAIL_LOG : (ctx->tailLaunches++ % PPG_TAIL_LOG)), StragOut{G.rec.p, G.orig.p, G.count.p}, shape.laneLimit, B.M, B.V};
         ppg_launch_tail(tailVariant(ctx), a);
     });
     return PPG_OK;
@@ -2413,8 +2426,15 @@ int uploadScene(ppg_ctx *ctx, const HostScene &H, DevScene &S) {
     M = MediaArgs{};
     M.media = up(ctx->d_media, H.media); M.prim_media = up(ctx->d_primMedia, H.primMedia);
     M.camera_medium = H.cameraMedium; M.n_media = (int)(H.media.size() / PPG_MEDIUM_STRIDE);
+    HetArgs &V = ctx->hetArgs;
+    V = HetArgs{};
+    V.volumes = up(ctx->d_volumes, H.volumes); V.pool = up(ctx->d_volPool, H.volPool); V.het = up(ctx->d_het, H.het);
+    V.n_volumes = (int)(H.volumes.size() / PPG_VOLUME_STRIDE);
+    ctx->hetMedium.assign(H.het.size() / PPG_HET_STRIDE, 0);
+    for (size_t k = 0; k < ctx->hetMedium.size(); ++k) ctx->hetMedium[k] = __builtin_bit_cast(int, H.het[PPG_HET_STRIDE * k].x) != 0;
     HIP_CHECK(up.e);
     if (!H.media.empty() && (!M.media || !M.prim_media)) { ctx->error = "internal: device scene incomplete"; return PPG_ERR_STATE; }
+    if (!H.het.empty() && (!V.volumes || !V.pool || !V.het || !M.media)) { ctx->error = "internal: device scene incomplete"; return PPG_ERR_STATE; }
     // Every array the path kernels walk must be there before a launch can chase it: an unset pointer here is a hung GPU, not a wrong pixel
     // (round 5 lost 40 GPU minutes to five assignments that an edit had turned into a comment).
     if (!S.materials || !S.bvh4 || (S.n_tris > 0 && (!S.tris || !S.accel || !S.bvh)) || (S.n_spheres > 0 && !S.spheres) || (S.n_delta > 0 && !S.delta) ||
@@ -2565,7 +2585,8 @@ const char *ppg_last_error(const ppg_ctx *ctx) { return ctx ? ctx->error.c_str()
 
 int ppg_set_scene(ppg_ctx *ctx, const ppg_scene *s) {
     const SceneInputs in{s, ctx->materialTextures, ctx->microfacet, ctx->coatings, ctx->blends, ctx->deltaEmitters, ctx->shapes,
-                         ctx->lensOn ? &ctx->lens : nullptr, ctx->tuneBvhPad, ctx->tuneBvhLeaf, ctx->tuneNoTopCut, ctx->mediaList.n_media ? &ctx->mediaList : nullptr};
+                         ctx->lensOn ? &ctx->lens : nullptr, ctx->tuneBvhPad, ctx->tuneBvhLeaf, ctx->tuneNoTopCut, ctx->mediaList.n_media ? &ctx->mediaList : nullptr,
+                         ctx->volumesList.n_entries ? &ctx->volumesList : nullptr};
     if (!sceneComplete(in)) { ctx->error = "incomplete scene"; return PPG_ERR_INVALID; }
     HIP_CHECK(hipSetDevice(ctx->device));
     ctx->quiesce();
@@ -2922,6 +2943,41 @@ int ppg_set_media(ppg_ctx *ctx, const ppg_media *media) {
     return PPG_OK;
 }
 
+int ppg_set_media_volumes(ppg_ctx *ctx, const ppg_media_volumes *volumes) {
+    if (ctx->renderOpen) { ctx->error = "media volumes: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (volumes && volumes->n_entries) {  // (what cannot even be copied is refused here; the kept list stays)
+        if (!volumes->entries || (volumes->n_volumes && !volumes->volumes)) { ctx->error = "media volumes: a count > 0 but no array"; return PPG_ERR_INVALID; }
+        for (uint32_t k = 0; k < volumes->n_volumes; ++k) {
+            const ppg_volume &v = volumes->volumes[k];
+            if (v.kind != PPG_VOLUME_GRID) continue;
+            const std::string who = "media volumes: volume " + std::to_string(k) + ": ";
+            if (v.channels != 1 && v.channels != 3) { ctx->error = who + "channels must be 1 or 3"; return PPG_ERR_INVALID; }
+            for (int a = 0; a < 3; ++a) if (v.res[a] < 2) { ctx->error = who + "a res component is below 2"; return PPG_ERR_INVALID; }
+            if ((double)v.res[0] * v.res[1] * v.res[2] * v.channels > 536870912.0) { ctx->error = who + "more than 2^29 floats"; return PPG_ERR_INVALID; }
+            if (!v.data) { ctx->error = who + "a grid without data"; return PPG_ERR_INVALID; }
+        }
+    }
+    ctx->volumesList = ppg_media_volumes{};
+    ctx->volumes.clear(); ctx->volumeData.clear(); ctx->volumeEntries.clear();
+    if (!volumes || volumes->n_entries == 0) return PPG_OK;  // cleared
+    // the list is copied as it is, the grids' data with it, and validated against the media list by ppg_set_scene
+    ctx->volumes.assign(volumes->volumes, volumes->volumes + volumes->n_volumes);
+    ctx->volumeEntries.assign(volumes->entries, volumes->entries + volumes->n_entries);
+    ctx->volumeData.resize(volumes->n_volumes);
+    for (uint32_t k = 0; k < volumes->n_volumes; ++k) {
+        ppg_volume &v = ctx->volumes[k];
+        if (v.kind != PPG_VOLUME_GRID) { v.data = nullptr; continue; }
+        const size_t count = (size_t)v.res[0] * v.res[1] * v.res[2] * v.channels;
+        ctx->volumeData[k].assign(v.data, v.data + count);
+        v.data = ctx->volumeData[k].data();
+    }
+    ppg_media_volumes &L = ctx->volumesList;
+    L = *volumes;
+    L.volumes = ctx->volumes.data();
+    L.entries = ctx->volumeEntries.data();
+    return PPG_OK;
+}
+
 int ppg_set_shapes(ppg_ctx *ctx, const ppg_shape *shapes, uint32_t n) {
     if (ctx->renderOpen) { ctx->error = "shapes: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
     if (n && !shapes) { ctx->error = "shapes: no list"; return PPG_ERR_INVALID; }
@@ -2979,6 +3035,49 @@ int ppg_debug_medium(ppg_ctx *ctx, uint32_t n, const ppg_debug_medium_item *item
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(ppg_debug_medium_out), hipMemcpyDeviceToHost));
     return PPG_OK;
+}
+// ppg_debug_volume, ppg_debug_hetmedium: what both refuse, then upload, launch and read back
+extern "C++" {
+template <typename Item, typename Out, typename Launch>
+static int debugHet(ppg_ctx *ctx, const char *who, uint32_t n, const Item *items, Out *out, Launch launch) {
+    if (n == 0) return PPG_OK;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    ctx->quiesce();
+    DebugBuf dItems, dOut;
+    HIP_CHECK(dItems.fill(items, (size_t)n * sizeof(Item)));
+    HIP_CHECK(dOut.fill(nullptr, (size_t)n * sizeof(Out)));
+    const unsigned int block = 64;
+    launch((int)((n + block - 1) / block), (int)block, (const Item *)dItems.p, (Out *)dOut.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    HIP_CHECK(hipMemcpy(out, dOut.p, (size_t)n * sizeof(Out), hipMemcpyDeviceToHost));
+    return PPG_OK;
+}
+static int debugHetRefusal(ppg_ctx *ctx, const std::string &who, uint32_t n, const void *items, const void *out) {
+    if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
+    if (ctx->renderOpen) { ctx->error = who + ": not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
+    if (!ctx->hetArgs.het) { ctx->error = who + ": the scene binds no heterogeneous medium"; return PPG_ERR_STATE; }
+    if (n && (!items || !out)) { ctx->error = who + ": no arrays"; return PPG_ERR_INVALID; }
+    return PPG_OK;
+}
+}  // extern "C++"
+int ppg_debug_volume(ppg_ctx *ctx, uint32_t n, const ppg_debug_volume_item *items, ppg_debug_volume_out *out) {
+    if (int rc = debugHetRefusal(ctx, "ppg_debug_volume", n, items, out)) return rc;
+    for (uint32_t i = 0; i < n; ++i)
+        if (items[i].volume < 0 || items[i].volume >= ctx->hetArgs.n_volumes) { ctx->error = "ppg_debug_volume: item " + std::to_string(i) + ": volume out of range"; return PPG_ERR_INVALID; }
+    return debugHet(ctx, "ppg_debug_volume", n, items, out, [&](int grid, int block, const ppg_debug_volume_item *dIn, ppg_debug_volume_out *dOut) {
+        launcher(ppg_path_kernels[PPG_FAMILY_HETMEDIA].debug_volume)(grid, block, ctx->stream, ctx->hetArgs, n, dIn, dOut);
+    });
+}
+int ppg_debug_hetmedium(ppg_ctx *ctx, uint32_t n, const ppg_debug_hetmedium_item *items, ppg_debug_hetmedium_out *out) {
+    if (int rc = debugHetRefusal(ctx, "ppg_debug_hetmedium", n, items, out)) return rc;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (items[i].medium < 0 || items[i].medium >= ctx->mediaArgs.n_media) { ctx->error = "ppg_debug_hetmedium: item " + std::to_string(i) + ": medium out of range"; return PPG_ERR_INVALID; }
+        if (!ctx->hetMedium[items[i].medium]) { ctx->error = "ppg_debug_hetmedium: item " + std::to_string(i) + ": the medium is not heterogeneous"; return PPG_ERR_INVALID; }
+    }
+    return debugHet(ctx, "ppg_debug_hetmedium", n, items, out, [&](int grid, int block, const ppg_debug_hetmedium_item *dIn, ppg_debug_hetmedium_out *dOut) {
+        launcher(ppg_path_kernels[PPG_FAMILY_HETMEDIA].debug_hetmedium)(grid, block, ctx->stream, ctx->hetArgs, n, dIn, dOut);
+    });
 }
 int ppg_debug_shading_frame(ppg_ctx *ctx, uint32_t n, const float *rays, ppg_debug_frame *out) {
     if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
@@ -3147,7 +3246,7 @@ int ppg_debug_intersect_mode(ppg_ctx *ctx, uint32_t n, const float *rays, ppg_de
         const bool smallScene = isSmallScene(ctx);
         const size_t traceLds = smallScene ? (size_t)ctx->ldsTris * 48 : (size_t)PPG_TRACE_STACK * PPG_BLOCK * 4 + (PPG_BLOCK / 64) * sizeof(PairLds);
         TraceLaunch a{grid, traceLds, ctx->stream, P, ctx->scene, Q, QIN_FIRST, smallScene ? 0 : ctx->ldsNodes, ctx->ldsTris, nullptr, nullptr, smallScene, false};
-        launcher(ppg_path_kernels[sceneFamily(ctx->scene, ctx->mediaArgs)].trace)(a);
+        launcher(ppg_path_kernels[sceneFamily(ctx->scene, ctx->mediaArgs, ctx->hetArgs)].trace)(a);
         HIP_CHECK(hipGetLastError());
         launcher(K.debug_hit_records)(ctx->stream, ctx->scene, n, (const float4 *)dRays.p, (const float4 *)dHit.p, (ppg_debug_hit *)dOut.p);
         HIP_CHECK(hipGetLastError());
@@ -3200,7 +3299,7 @@ int ppg_debug_sample_direct(ppg_ctx *ctx, uint32_t n, const float *ref, const fl
 }
 // a kernel family can read the scene if it is the scene's own or one above it (every family knows what the families below it know)
 static int debugFamily(ppg_ctx *ctx, const char *who, int32_t family, int *out) {
-    const int own = sceneFamily(ctx->scene, ctx->mediaArgs);
+    const int own = sceneFamily(ctx->scene, ctx->mediaArgs, ctx->hetArgs);
     if (family < -1 || family >= PPG_DEBUG_FAMILIES) { ctx->error = std::string(who) + ": no such kernel family"; return PPG_ERR_INVALID; }
     if (family >= 0 && family < own) { ctx->error = std::string(who) + ": the scene needs kernel family " + std::to_string(own) + " or above"; return PPG_ERR_INVALID; }
     *out = family < 0 ? own : family;
@@ -3293,7 +3392,7 @@ int ppg_debug_bsdf_as(ppg_ctx *ctx, int32_t family, int32_t unit, uint32_t n, co
 int ppg_debug_bsdf(ppg_ctx *ctx, uint32_t n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out) {
     if (!ctx->haveScene) { ctx->error = "no scene"; return PPG_ERR_STATE; }
     if (ctx->renderOpen) { ctx->error = "ppg_debug_bsdf: not between ppg_begin_render and ppg_end_render"; return PPG_ERR_STATE; }
-    const int family = std::max(sceneFamily(ctx->scene, ctx->mediaArgs), PPG_FAMILY_EXT);  // (as before the base and shapes families compiled the hook's kernel)
+    const int family = std::max(sceneFamily(ctx->scene, ctx->mediaArgs, ctx->hetArgs), PPG_FAMILY_EXT);  // (as before the base and shapes families compiled the hook's kernel)
     return debugBsdf(ctx, "ppg_debug_bsdf", family, PPG_DEBUG_BSDF_FULL, n, items, out);
 }
 

@@ -22,17 +22,25 @@
 #define ROW ppg_path_kernels[PPG_FAMILY]               // this unit's family's
 #define PPG_FILL_ROW __attribute__((constructor)) static void fill_row()
 // the media family's kernels take the scene and the path state with MediaArgs appended (ppg_device.h SceneArg, ppg_kernels.h PathArg)
+// (and the hetmedia family's with HetArgs on top of that)
 #if PPG_MEDIA
 static PathArg path_arg(const PathState &P, const MediaArgs &M) { PathArg r; static_cast<PathState &>(r) = P; r.medium = {M.path_medium, M.path_stride}; return r; }
-static SceneArg scene_arg(const DevScene &S, const MediaArgs &M) { SceneArg r; static_cast<DevScene &>(r) = S; r.media = M.media; r.prim_media = M.prim_media; return r; }
 #else
 static const PathState &path_arg(const PathState &P, const MediaArgs &) { return P; }
-static const DevScene &scene_arg(const DevScene &S, const MediaArgs &) { return S; }
+#endif
+#if PPG_HETMEDIA
+static SceneArg scene_arg(const DevScene &S, const MediaArgs &M, const HetArgs &V) {
+    SceneArg r; static_cast<DevScene &>(r) = S; r.media = M.media; r.prim_media = M.prim_media; r.volumes = V.volumes; r.pool = V.pool; r.het = V.het; return r;
+}
+#elif PPG_MEDIA
+static SceneArg scene_arg(const DevScene &S, const MediaArgs &M, const HetArgs &) { SceneArg r; static_cast<DevScene &>(r) = S; r.media = M.media; r.prim_media = M.prim_media; return r; }
+#else
+static const DevScene &scene_arg(const DevScene &S, const MediaArgs &, const HetArgs &) { return S; }
 #endif
 
 #if defined(PPG_UNIT_SHADE)
 template <bool NEE, bool FULL> static void launch_shade(const ShadeLaunch &a) {
-    hipLaunchKernelGGL((k_shade<NEE, FULL>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, path_arg(a.P, a.M), scene_arg(a.S, a.M), a.T, a.R, a.Q, a.qin, a.small_scene, a.sorted_items);
+    hipLaunchKernelGGL((k_shade<NEE, FULL>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, path_arg(a.P, a.M), scene_arg(a.S, a.M, a.V), a.T, a.R, a.Q, a.qin, a.small_scene, a.sorted_items);
 }
 template <bool NEE> static void shade(int variant, const ShadeLaunch &a) {
 #if PPG_BASE_ONLY
@@ -50,7 +58,7 @@ PPG_FILL_ROW {
 }
 #elif defined(PPG_UNIT_TAIL)
 template <bool SMALL, bool NEE, bool FULL> static void launch_tail(const TailLaunch &a) {
-    hipLaunchKernelGGL((k_tail<SMALL, NEE, FULL>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, path_arg(a.P, a.M), scene_arg(a.S, a.M), a.T, a.R, a.dense, a.total, a.ticket, a.stats, a.lds_tris, a.longest, a.strag, a.lane_limit);
+    hipLaunchKernelGGL((k_tail<SMALL, NEE, FULL>), dim3(a.grid), dim3(PPG_BLOCK), a.lds, a.stream, path_arg(a.P, a.M), scene_arg(a.S, a.M, a.V), a.T, a.R, a.dense, a.total, a.ticket, a.stats, a.lds_tris, a.longest, a.strag, a.lane_limit);
 }
 template <bool SMALL, bool NEE> static void tail(int variant, const TailLaunch &a) {
 #if PPG_BASE_ONLY

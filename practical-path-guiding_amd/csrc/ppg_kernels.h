@@ -870,6 +870,10 @@ D F3 shadow_transmittance(const SceneArg &S, const float4 *small_tris, int *stac
 #if PPG_MEDIA
                           , unsigned int med = 0u, bool p1OnSurface = true
 #endif
+#if PPG_HETMEDIA
+                          // (a heterogeneous piece's tracking estimate draws from the path's stream, scene.cpp:643-645)
+                          , unsigned int key = 0u, unsigned int *dimp = nullptr
+#endif
                           ) {
     F3 o = p1;
     float maxt = remaining * lengthFactor;
@@ -887,7 +891,9 @@ D F3 shadow_transmittance(const SceneArg &S, const float4 *small_tris, int *stac
         Isect I;
         if (surface) fill_isect_null(S, h, o, d, I, M);
         if (surface && (interactions == maxInteractions || !mat_has_null(M))) return f3s(0.0f);
-#if PPG_MEDIA
+#if PPG_HETMEDIA
+        if (med) transmittance = mul3(transmittance, any_medium_transmittance(S, med, o, d, 0.0f, ppg_min(surface ? h.t : __builtin_inff(), remaining), [&]() { return ppg_rand(key, (*dimp)++); }));
+#elif PPG_MEDIA
         if (med) transmittance = mul3(transmittance, medium_transmittance(medium_record(S.media, med), ppg_min(surface ? h.t : __builtin_inff(), remaining)));
 #endif
         if (!surface || iszero3(transmittance)) break;
@@ -1005,7 +1011,15 @@ D bool shade_one(const PathArg &P, const SceneArg &S, const DevTree &T, const Re
 #if PPG_MEDIA
         // rayIntersectAndLookForEmitter with a medium, GP:2195-2196: the transmittance of every piece of the search, this first one included
         F3 mtr = f3s(1.0f);
+#if PPG_HETMEDIA
+        if (medQ) {
+            const float4 ro4 = ray_origin();
+            mtr = any_medium_transmittance(S, med, f3(ro4.x, ro4.y, ro4.z), d, 0.0f, valid ? h.t : __builtin_inff(), [&]() { return ppg_rand(key, dim++); });
+            value = mul3(mtr, value);
+        }
+#else
         if (medQ) { mtr = medium_transmittance(medQ, valid ? h.t : __builtin_inff()); value = mul3(mtr, value); }
+#endif
 #endif
         if (FULL && MSET != MSET_COMMON && S.has_null && valid && I.emitter < 0) {
             // rayIntersectAndLookForEmitter GP:2184-2245: the path continues from THIS hit, but the search for an emitter
@@ -1037,7 +1051,9 @@ D bool shade_one(const PathArg &P, const SceneArg &S, const DevTree &T, const Re
                     if (++interactions > 100) { abandoned = true; break; }
                     hc = trace_inline(S, nee.small_tris, nee.stack_col, ro, d, __builtin_inff());
                     ++traced;
-#if PPG_MEDIA
+#if PPG_HETMEDIA
+                    if (lmed) transmittance = mul3(transmittance, any_medium_transmittance(S, lmed, ro, d, 0.0f, hc.prim < 0 ? __builtin_inff() : hc.t, [&]() { return ppg_rand(key, dim++); }));
+#elif PPG_MEDIA
                     if (lmed) transmittance = mul3(transmittance, medium_transmittance(medium_record(S.media, lmed), hc.prim < 0 ? __builtin_inff() : hc.t));
 #endif
                     if (hc.prim < 0) { surface = false; break; }
@@ -1122,7 +1138,17 @@ D bool shade_one(const PathArg &P, const SceneArg &S, const DevTree &T, const Re
         const float4 ro4 = ray_origin();
         const F3 ro = f3(ro4.x, ro4.y, ro4.z);
         MediumSample ms;
+#if PPG_HETMEDIA
+        bool mediumEvent;
+        if (het_is(het_record(S.het, med))) {  // HeterogeneousMedium::sampleDistance: pdfSuccess = pdfFailure = 1
+            HetSample hs;
+            mediumEvent = hetmedium_sample_distance(S.volumes, S.pool, het_record(S.het, med), ro, d, 0.0f, valid ? h.t : __builtin_inff(), [&]() { return ppg_rand(key, dim++); }, hs);
+            ms.t = hs.t; ms.pdfSuccess = 1.0f; ms.pdfFailure = 1.0f; ms.transmittance = f3s(hs.transmittance); ms.sigmaS = hs.sigmaS;
+        } else mediumEvent = medium_sample_distance(medQ, ro, d, valid ? h.t : __builtin_inff(), [&]() { return ppg_rand(key, dim++); }, ms);
+        if (mediumEvent) {
+#else
         if (medium_sample_distance(medQ, ro, d, valid ? h.t : __builtin_inff(), [&]() { return ppg_rand(key, dim++); }, ms)) {
+#endif
             if ((int)depth >= R.max_depth && R.max_depth != -1) go = false;  // GP:1809
             if (go) {
                 thr = mul3(thr, div3(mul3(ms.sigmaS, ms.transmittance), ms.pdfSuccess));  // GP:1812
@@ -1135,7 +1161,11 @@ D bool shade_one(const PathArg &P, const SceneArg &S, const DevTree &T, const Re
                     F3 value = emitter_sample_direct<FULL>(S, mp, f3s(0.0f), ex, ey, ds);
                     if (ds.pdf != 0) {  // value *= evalTransmittance(dRec.ref, false, dRec.p, ..) / emPdf, scene.cpp:864-870
                         const F3 tr = shadow_transmittance(S, nee.small_tris, nee.stack_col, mp, ds.sd, ds.sdist, (ds.is_env || ds.is_delta) ? 1.0f : 1 - PPG_SHADOW_EPSILON,
-                                                           R.max_depth - (int)depth - 1, traced, med, false);
+                                                           R.max_depth - (int)depth - 1, traced, med, false
+#if PPG_HETMEDIA
+                                                           , key, &dim
+#endif
+                                                           );
                         if (iszero3(tr)) value = f3s(0.0f);
                         else { value = div3(mul3(value, tr), ds.em_pdf); ds.pdf *= ds.em_pdf; }
                     }
@@ -1172,7 +1202,14 @@ D bool shade_one(const PathArg &P, const SceneArg &S, const DevTree &T, const Re
 #if PPG_MEDIA
         if (medQ) {  // GP:1907-1910: value *= rRec.medium->evalTransmittance(ray), the ray as it was traced (mint, maxt)
             if (FULL && S.env.w != 0 && (flags & FL_EMITTED_OK) && (!R.hide_emitters || (flags & FL_SCATTERED)))
+#if PPG_HETMEDIA
+            {
+                const float4 ro4 = ray_origin();
+                Li = Li + mul3(mul3(thr, env_radiance(S, d)), any_medium_transmittance(S, med, f3(ro4.x, ro4.y, ro4.z), d, ro4.w, d4.w, [&]() { return ppg_rand(key, dim++); }));
+            }
+#else
                 Li = Li + mul3(mul3(thr, env_radiance(S, d)), medium_transmittance(medQ, d4.w - ray_origin().w));
+#endif
         } else
 #endif
         if (FULL && S.env.w != 0 && (flags & FL_EMITTED_OK) && (!R.hide_emitters || (flags & FL_SCATTERED)))
@@ -1351,7 +1388,11 @@ D bool shade_one(const PathArg &P, const SceneArg &S, const DevTree &T, const Re
                     unsigned int smed = med;  // scene.cpp:888-889: at a medium transition the segment starts in the medium on dRec.d's side
                     if (haveMedia) { if (const unsigned int word = medium_word(S, h.prim)) smed = medium_target(word, ds.d, I.geoN); }
                     const F3 tr = shadow_transmittance(S, nee.small_tris, nee.stack_col, I.p, ds.sd, ds.sdist, (ds.is_env || ds.is_delta) ? 1.0f : 1 - PPG_SHADOW_EPSILON,
-                                                       R.max_depth - (int)depth - 1, traced, smed, true);
+                                                       R.max_depth - (int)depth - 1, traced, smed, true
+#if PPG_HETMEDIA
+                                                       , key, &dim
+#endif
+                                                       );
 #else
                     const F3 tr = shadow_transmittance(S, nee.small_tris, nee.stack_col, I.p, ds.sd, ds.sdist, (ds.is_env || ds.is_delta) ? 1.0f : 1 - PPG_SHADOW_EPSILON,
                                                        R.max_depth - (int)depth - 1, traced);

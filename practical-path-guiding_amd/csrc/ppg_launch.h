@@ -18,6 +18,7 @@ struct ShadeLaunch {
     int qin, small_scene;
     const unsigned int *sorted_items;
     MediaArgs M;             // the media family's extra arguments (ppg_device.h); zero: the scene binds no medium
+    HetArgs V;               // the hetmedia family's, on top of M; zero: no bound medium is heterogeneous
 };
 struct TailLaunch {
     int grid;
@@ -33,6 +34,7 @@ struct TailLaunch {
     StragOut strag;          // R.defer_depth > 0: where the paths still alive at that depth go
     unsigned int lane_limit; // paths a wave takes at a time (64; fewer for a launch over a handful of stragglers)
     MediaArgs M;             // the media family's extra arguments (ppg_device.h); zero: the scene binds no medium
+    HetArgs V;               // the hetmedia family's, on top of M; zero: no bound medium is heterogeneous
 };
 struct TraceLaunch {
     int grid;
@@ -103,6 +105,10 @@ struct ppg_debug_bsdf_out;
 struct ppg_debug_frame;
 struct ppg_debug_medium_item;
 struct ppg_debug_medium_out;
+struct ppg_debug_volume_item;
+struct ppg_debug_volume_out;
+struct ppg_debug_hetmedium_item;
+struct ppg_debug_hetmedium_out;
 struct PathKernels {
     void (*shade[2])(int variant, const ShadeLaunch &a);  // [NEE]; variant = (NEE ? 2 : 0) | (FULL ? 1 : 0)
     void (*tail[4])(int variant, const TailLaunch &a);    // [SMALL * 2 + NEE]; variant = (SMALL ? 4 : 0) | (NEE ? 2 : 0) | (FULL ? 1 : 0)
@@ -127,6 +133,9 @@ struct PathKernels {
     void (*debug_bsdf)(int lean, int grid, int block, hipStream_t stream, const DevScene &S, unsigned int n, const ppg_debug_bsdf_item *items, ppg_debug_bsdf_out *out);
     // the media family: its medium_sample_distance / medium_transmittance / phase_sample / phase_eval (ppg_debug_medium)
     void (*debug_medium)(int grid, int block, hipStream_t stream, const MediaArgs &M, unsigned int n, const ppg_debug_medium_item *items, ppg_debug_medium_out *out);
+    // the hetmedia family: its volume lookups (ppg_debug_volume) and its tracking routines (ppg_debug_hetmedium)
+    void (*debug_volume)(int grid, int block, hipStream_t stream, const HetArgs &V, unsigned int n, const ppg_debug_volume_item *items, ppg_debug_volume_out *out);
+    void (*debug_hetmedium)(int grid, int block, hipStream_t stream, const HetArgs &V, unsigned int n, const ppg_debug_hetmedium_item *items, ppg_debug_hetmedium_out *out);
 };
 extern PathKernels ppg_path_kernels[PPG_FAMILIES];
 

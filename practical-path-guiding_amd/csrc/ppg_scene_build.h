@@ -702,6 +702,7 @@ struct SceneInputs {
     int bvhLeaf;           // PPG_BVH_LEAF
     bool noTopCut;         // PPG_NO_TOPCUT
     const ppg_media *media = nullptr;  // ppg_set_media's list as the context keeps it, or nullptr: none
+    const ppg_media_volumes *mediaVolumes = nullptr;  // ppg_set_media_volumes' list as the context keeps it, or nullptr: none
 };
 
 // Every table of a scene as the device reads it, on the host; `scene` carries every scalar of the DevScene and no pointer (the upload fills
@@ -724,6 +725,10 @@ struct HostScene {
     std::vector<float4> media;            // PPG_MEDIUM_STRIDE per medium; media and primMedia: empty unless the list binds a medium
     std::vector<unsigned int> primMedia;  // one binding word per primitive: triangles in leaf order, spheres, shapes
     unsigned int cameraMedium = 0;        // 1 + the sensor's medium
+    // ppg_set_media_volumes (HetArgs, ppg_device.h): PPG_VOLUME_STRIDE per volume, the grids' data, PPG_HET_STRIDE per medium; all empty
+    // unless a bound medium is heterogeneous
+    std::vector<float4> volumes, het;
+    std::vector<float> volPool;
     std::vector<float> rtrans;
     std::vector<ppg_delta_emitter> deltaEmitters;  // the list the scene's box was built with (ppg_set_lens builds it again)
     DevScene scene{};
@@ -801,7 +806,7 @@ struct SceneBuilder {
     }
 
     int primitives(), geometry(), materials(), microfacet(), coatings(), blends(), textures(), envmap(), emitterTables(), deltaEmitters(), shapesAndSpheres(),
-        media(), cameraAndLds();
+        media(), mediaVolumes(), cameraAndLds();
 };
 
 // The references of every primitive — triangles, spheres, shapes — and who carries which emitter
@@ -1514,6 +1519,136 @@ int SceneBuilder::media() {
     return PPG_OK;
 }
 
+// ppg_set_media_volumes: heterogeneous media (medium/heterogeneous.cpp, Woodcock tracking) over const and grid volumes.  Everything the
+// tracking loops rely on is checked here — every index, every texel of a density grid against [0, 1], the expected length of a loop —, and
+// what the reference's configure() calls derive is derived here: worldToGrid and the world box (gridvolume.cpp:188-201), maxDensity and
+// its inverse (heterogeneous.cpp:239-242).
+int SceneBuilder::mediaVolumes() {
+    const ppg_media_volumes *L = in.mediaVolumes;
+    if (!L || L->n_entries == 0) return PPG_OK;
+    const std::string list = "media volumes: ";
+    for (int c = 0; c < 4; ++c) if (L->_reserved[c]) return refuse(list + "a reserved word is not 0");
+    if (!L->entries || (L->n_volumes && !L->volumes)) return refuse(list + "a count > 0 but no array");
+    const ppg_media *M = in.media;
+    if (!M || M->n_media == 0) return refuse(list + "no media list (ppg_set_media) to name a medium of");
+    struct Derived { float w2g[12]; float mn[3], mx[3]; float diag; size_t offset; };
+    std::vector<Derived> derived(L->n_volumes);
+    std::vector<float4> vtab(PPG_VOLUME_STRIDE * (size_t)L->n_volumes);
+    std::vector<float> pool;
+    for (uint32_t k = 0; k < L->n_volumes; ++k) {
+        const ppg_volume &v = L->volumes[k];
+        const std::string who = list + "volume " + std::to_string(k) + ": ";
+        Derived &G = derived[k];
+        memset(&G, 0, sizeof G);
+        if (v._reserved[0] || v._reserved[1]) return refuse(who + "a reserved word is not 0");
+        if (v.kind != PPG_VOLUME_CONST && v.kind != PPG_VOLUME_GRID) return refuse(who + "unknown kind");
+        if (v.channels != 1 && v.channels != 3) return refuse(who + "channels must be 1 or 3");
+        float4 *Q = &vtab[PPG_VOLUME_STRIDE * (size_t)k];
+        for (int i = 0; i < PPG_VOLUME_STRIDE; ++i) Q[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        Q[0].x = __builtin_bit_cast(float, (int)(v.kind | (v.channels << 8)));
+        if (v.kind == PPG_VOLUME_CONST) {
+            for (int c = 0; c < v.channels; ++c) if (!std::isfinite(v.value[c])) return refuse(who + "a value is not finite");
+            Q[4] = v.channels == 1 ? make_float4(v.value[0], v.value[0], v.value[0], 0.0f) : make_float4(v.value[0], v.value[1], v.value[2], 0.0f);
+            continue;
+        }
+        for (int a = 0; a < 3; ++a) if (v.res[a] < 2) return refuse(who + "a res component is below 2");
+        if ((double)v.res[0] * v.res[1] * v.res[2] * v.channels > 536870912.0) return refuse(who + "more than 2^29 floats");
+        if (!v.data) return refuse(who + "a grid without data");
+        double ext[3];
+        for (int a = 0; a < 3; ++a) {
+            if (!std::isfinite(v.aabb_min[a]) || !std::isfinite(v.aabb_max[a])) return refuse(who + "the data box is not finite");
+            ext[a] = (double)v.aabb_max[a] - (double)v.aabb_min[a];
+            if (!(ext[a] > 0)) return refuse(who + "the data box is empty");
+        }
+        const float *m = v.to_world;
+        for (int i = 0; i < 16; ++i) if (!std::isfinite(m[i])) return refuse(who + "to_world is not finite");
+        if (m[12] != 0 || m[13] != 0 || m[14] != 0 || m[15] != 1) return refuse(who + "to_world is not affine (its last row must be 0 0 0 1)");
+        double c[3][3], len[3];
+        for (int j = 0; j < 3; ++j) {
+            for (int a = 0; a < 3; ++a) c[j][a] = m[4 * a + j];
+            len[j] = std::sqrt(c[j][0] * c[j][0] + c[j][1] * c[j][1] + c[j][2] * c[j][2]);
+        }
+        const double det = c[0][0] * (c[1][1] * c[2][2] - c[1][2] * c[2][1]) - c[0][1] * (c[1][0] * c[2][2] - c[1][2] * c[2][0]) +
+                           c[0][2] * (c[1][0] * c[2][1] - c[1][1] * c[2][0]);
+        if (len[0] == 0 || len[1] == 0 || len[2] == 0 || !(std::abs(det) > 1e-9 * len[0] * len[1] * len[2])) return refuse(who + "to_world is singular");
+        // worldToGrid = scale((res - 1) / extents) * translate(-min) * to_world^-1; row i of L^-1 = cross products of L's columns / det
+        for (int i = 0; i < 3; ++i) {
+            const double *a = c[(i + 1) % 3], *b = c[(i + 2) % 3];
+            const double li[3] = {(a[1] * b[2] - a[2] * b[1]) / det, (a[2] * b[0] - a[0] * b[2]) / det, (a[0] * b[1] - a[1] * b[0]) / det};
+            const double tr = -(li[0] * (double)m[3] + li[1] * (double)m[7] + li[2] * (double)m[11]);
+            const double sc = (v.res[i] - 1) / ext[i];
+            for (int j = 0; j < 3; ++j) G.w2g[4 * i + j] = (float)(sc * li[j]);
+            G.w2g[4 * i + 3] = (float)(sc * (tr - (double)v.aabb_min[i]));
+        }
+        for (int a = 0; a < 3; ++a) { G.mn[a] = INFINITY; G.mx[a] = -INFINITY; }
+        for (int corner = 0; corner < 8; ++corner) {  // m_aabb.expandBy(m_volumeToWorld(m_dataAABB.getCorner(i)))
+            const float p[3] = {(corner & 1) ? v.aabb_max[0] : v.aabb_min[0], (corner & 2) ? v.aabb_max[1] : v.aabb_min[1], (corner & 4) ? v.aabb_max[2] : v.aabb_min[2]};
+            for (int a = 0; a < 3; ++a) {
+                const float w = m[4 * a] * p[0] + m[4 * a + 1] * p[1] + m[4 * a + 2] * p[2] + m[4 * a + 3];
+                G.mn[a] = std::min(G.mn[a], w); G.mx[a] = std::max(G.mx[a], w);
+            }
+        }
+        const double dx = (double)G.mx[0] - G.mn[0], dy = (double)G.mx[1] - G.mn[1], dz = (double)G.mx[2] - G.mn[2];
+        G.diag = (float)std::sqrt(dx * dx + dy * dy + dz * dz);
+        if (!std::isfinite(G.diag)) return refuse(who + "the world box is not finite");
+        const size_t count = (size_t)v.res[0] * v.res[1] * v.res[2] * v.channels;
+        for (size_t i = 0; i < count; ++i)
+            if (!(v.data[i] >= 0.0f && v.data[i] <= 1.0f)) return refuse(who + "texel " + std::to_string(i) + " lies outside [0, 1] or is not finite");
+        G.offset = pool.size();
+        if (G.offset + count > 1073741824u) return refuse(who + "the grids hold more than 2^30 floats");
+        pool.insert(pool.end(), v.data, v.data + count);
+        Q[0].y = __builtin_bit_cast(float, (int)v.res[0]); Q[0].z = __builtin_bit_cast(float, (int)v.res[1]); Q[0].w = __builtin_bit_cast(float, (int)v.res[2]);
+        for (int i = 0; i < 3; ++i) Q[1 + i] = make_float4(G.w2g[4 * i], G.w2g[4 * i + 1], G.w2g[4 * i + 2], G.w2g[4 * i + 3]);
+        Q[4] = make_float4(0.0f, 0.0f, 0.0f, __builtin_bit_cast(float, (int)G.offset));
+    }
+    std::vector<float4> htab(PPG_HET_STRIDE * (size_t)M->n_media, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    std::vector<char> named(M->n_media, 0);
+    for (uint32_t k = 0; k < L->n_entries; ++k) {
+        const ppg_medium_volumes &e = L->entries[k];
+        const std::string who = list + "entry " + std::to_string(k) + ": ";
+        for (int c = 0; c < 4; ++c) if (e._reserved[c]) return refuse(who + "a reserved word is not 0");
+        if (e.medium >= M->n_media) return refuse(who + "medium index out of range");
+        if (e.density >= L->n_volumes || e.albedo >= L->n_volumes) return refuse(who + "volume index out of range");
+        if (named[e.medium]) return refuse(who + "medium " + std::to_string(e.medium) + " is named twice");
+        named[e.medium] = 1;
+        const ppg_volume &dv = L->volumes[e.density], &av = L->volumes[e.albedo];
+        if (dv.channels != 1) return refuse(who + "the density volume must have 1 channel");
+        if (av.channels != 3) return refuse(who + "the albedo volume must have 3 channels");
+        if (!(std::isfinite(e.scale) && e.scale > 0)) return refuse(who + "scale must be finite and > 0");
+        if (dv.kind == PPG_VOLUME_CONST && !(std::isfinite(dv.value[0]) && dv.value[0] > 0)) return refuse(who + "a const density must be finite and > 0");
+        if (av.kind == PPG_VOLUME_CONST)
+            for (int c = 0; c < 3; ++c) if (!(av.value[c] >= 0.0f && av.value[c] <= 1.0f)) return refuse(who + "the albedo lies outside [0, 1] or is not finite");
+        const ppg_medium &md = M->media[e.medium];
+        bool plain = md.strategy == 0 && md.sampling_density == 0.0f && (md.sampling_weight == 0.0f || md.sampling_weight == -1.0f) && (md.channel == 0 || md.channel == -1);
+        for (int c = 0; c < 3; ++c) plain = plain && md.sigma_a[c] == 0.0f && md.sigma_s[c] == 0.0f;
+        if (!plain) return refuse(who + "medium " + std::to_string(e.medium) + " states coefficients or a sampling strategy: a heterogeneous medium takes its density and albedo from volumes");
+        // m_maxDensity = m_scale * m_density->getMaximumFloatValue(): 1 for a grid, the value for a const volume
+        const float maxDensity = e.scale * (dv.kind == PPG_VOLUME_GRID ? 1.0f : dv.value[0]);
+        const float invMaxDensity = 1.0f / maxDensity;
+        if (!(std::isfinite(maxDensity) && maxDensity > 0 && std::isfinite(invMaxDensity) && invMaxDensity > 0)) return refuse(who + "scale times the maximum density is not finite and positive");
+        if (dv.kind == PPG_VOLUME_GRID && !((double)maxDensity * derived[e.density].diag <= (double)PPG_HETMEDIUM_MAX_MEAN_STEPS))
+            return refuse(who + "the grid is too long to track: scale times the diagonal of its world box is " + std::to_string((double)maxDensity * derived[e.density].diag) +
+                          " majorant free paths, at most " + std::to_string((int)PPG_HETMEDIUM_MAX_MEAN_STEPS) + " are supported");
+        float4 *Hr = &htab[PPG_HET_STRIDE * (size_t)e.medium];
+        Hr[0] = make_float4(__builtin_bit_cast(float, (int)(e.density + 1u)), __builtin_bit_cast(float, (int)e.albedo), e.scale, invMaxDensity);
+        if (dv.kind == PPG_VOLUME_GRID) {
+            const Derived &G = derived[e.density];
+            Hr[1] = make_float4(G.mn[0], G.mn[1], G.mn[2], maxDensity); Hr[2] = make_float4(G.mx[0], G.mx[1], G.mx[2], 0.0f);
+        } else {  // AABB's default: invalid
+            Hr[1] = make_float4(INFINITY, INFINITY, INFINITY, maxDensity); Hr[2] = make_float4(-INFINITY, -INFINITY, -INFINITY, 0.0f);
+        }
+    }
+    // which media are bound: the hetmedia kernels are needed when one of them is heterogeneous
+    bool bound = false;
+    auto side = [&](unsigned int med) { if (med && named[med - 1]) bound = true; };
+    side(H.cameraMedium);
+    for (unsigned int w : H.primMedia) { side(w & 0xffffu); side(w >> 16); }
+    if (!bound) return PPG_OK;  // (nothing of the list is reachable: the scene renders as without it)
+    if (pool.empty()) pool.push_back(0.0f);
+    H.volumes = std::move(vtab); H.volPool = std::move(pool); H.het = std::move(htab);
+    return PPG_OK;
+}
+
 // the sensor, the film size and how much of the scene k_trace caches in LDS
 int SceneBuilder::cameraAndLds() {
     DevScene &S = H.scene;
@@ -1539,7 +1674,7 @@ static int buildScene(const SceneInputs &in, HostScene &H, std::string &err) {
     SceneBuilder b{in, H, err, in.s, {}, {}, {}, {}};
     for (auto stage : {&SceneBuilder::primitives, &SceneBuilder::geometry, &SceneBuilder::materials, &SceneBuilder::microfacet, &SceneBuilder::coatings,
                        &SceneBuilder::blends, &SceneBuilder::textures, &SceneBuilder::envmap, &SceneBuilder::emitterTables, &SceneBuilder::deltaEmitters,
-                       &SceneBuilder::shapesAndSpheres, &SceneBuilder::media, &SceneBuilder::cameraAndLds})
+                       &SceneBuilder::shapesAndSpheres, &SceneBuilder::media, &SceneBuilder::mediaVolumes, &SceneBuilder::cameraAndLds})
         if (int rc = (b.*stage)()) return rc;
     return PPG_OK;
 }

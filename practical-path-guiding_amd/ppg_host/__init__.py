@@ -9,5 +9,5 @@
 """
 from .bindings import Engine, PPGError, Config, PassStats, TreeStats, hip_library_path, read_sdt  # noqa: F401
 from .scenes import SceneDesc, cbox_scene, perspective_camera, perspective_camera_from_matrix, resize_camera, room_scene, torus_scene, save_scene, load_scene_file  # noqa: F401
-from .mitsuba_xml import load_scene, load_obj, save_scene_xml, SceneError  # noqa: F401
+from .mitsuba_xml import load_scene, load_obj, save_scene_xml, SceneError, read_vol, write_vol  # noqa: F401
 from .integrator import GuidedPathTracer  # noqa: F401,E402

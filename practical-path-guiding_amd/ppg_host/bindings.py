@@ -261,7 +261,10 @@ class Medium(C.Structure):
     """ppg_medium (include/ppg.h): a homogeneous medium (medium/homogeneous.cpp) with its phase function.  Scene descriptions carry media
     as dicts (SceneDesc.media): sigma_a + sigma_s, or sigma_t + albedo (sigma_s = sigma_t * albedo, sigma_a = sigma_t - sigma_s, as
     medium.cpp derives them), each a number or an RGB triple; scale (1) multiplies both; strategy ("balance" | "single" | "manual"),
-    channel (single; None: the smallest sigma_t), sampling_density (manual), sampling_weight (None: derive it), phase ("isotropic" | "hg"), g."""
+    channel (single; None: the smallest sigma_t), sampling_density (manual), sampling_weight (None: derive it), phase ("isotropic" | "hg"), g.
+    A heterogeneous medium (medium/heterogeneous.cpp, Woodcock tracking) reads dict(type="heterogeneous", density=V, albedo=V, scale=1.0,
+    phase=.., g=..) with V a volume dict (Volume): its record here keeps phase and g and zero coefficients, and flatten_media_volumes
+    makes the entry of ppg_set_media_volumes' list that names it."""
     _fields_ = [("sigma_a", C.c_float * 3), ("sigma_s", C.c_float * 3), ("strategy", C.c_int32), ("channel", C.c_int32),
                 ("sampling_density", C.c_float), ("sampling_weight", C.c_float), ("phase", C.c_int32), ("g", C.c_float), ("_reserved", C.c_uint32 * 4)]
     STRATEGIES = ("balance", "single", "manual")
@@ -274,7 +277,14 @@ class Medium(C.Structure):
             return np.repeat(a, 3) if a.size == 1 else a
         m = cls()
         scale = np.float32(d.get("scale", 1.0))
-        if "sigma_t" in d or "albedo" in d:
+        if d.get("type") == "heterogeneous":  # (density, albedo and scale travel in ppg_set_media_volumes' list: flatten_media_volumes)
+            for k in ("sigma_a", "sigma_s", "sigma_t", "strategy", "channel", "sampling_density", "sampling_weight"):
+                if k in d:
+                    raise ValueError("heterogeneous medium: %r belongs to homogeneous media; give `density` and `albedo` volumes" % k)
+            if "density" not in d or "albedo" not in d:
+                raise ValueError("heterogeneous medium: state `density` and `albedo` volumes")
+            sa = ss = np.zeros(3, np.float32)
+        elif "sigma_t" in d or "albedo" in d:
             if "sigma_a" in d or "sigma_s" in d or "sigma_t" not in d or "albedo" not in d:
                 raise ValueError("medium: state sigma_a and sigma_s, or sigma_t and albedo")
             st = rgb(d["sigma_t"]) * scale   # medium.cpp: the scale first, then sigmaS = sigmaT * albedo, sigmaA = sigmaT - sigmaS
@@ -306,6 +316,71 @@ class Media(C.Structure):
                 ("tri_media", C.POINTER(C.c_uint32)), ("sphere_media", C.POINTER(C.c_uint32)), ("shape_media", C.POINTER(C.c_uint32))]
 
 
+class Volume(C.Structure):
+    """ppg_volume (include/ppg.h): a constant or a grid volume.  Media dicts carry volumes as dicts: dict(value=0.5 | (r, g, b)), or
+    dict(data=ndarray[z, y, x] | [z, y, x, 3], min=(x, y, z), max=(x, y, z), to_world=4x4 (None: the identity))."""
+    _fields_ = [("kind", C.c_int32), ("channels", C.c_int32), ("value", C.c_float * 3), ("res", C.c_int32 * 3), ("aabb_min", C.c_float * 3),
+                ("aabb_max", C.c_float * 3), ("to_world", C.c_float * 16), ("_reserved", C.c_uint32 * 2), ("data", C.POINTER(C.c_float))]
+    CONST, GRID = 0, 1
+
+    @classmethod
+    def from_dict(cls, d, channels, keep):
+        """`channels`: what the volume is asked for (1: density, 3: albedo) — a const value given as one number serves both; `keep`
+        receives the arrays the record points into."""
+        v = cls()
+        if "value" in d:
+            a = np.asarray(d["value"], np.float32).reshape(-1)
+            if a.size not in (1, 3) or (a.size == 3 and channels == 1):
+                raise ValueError("volume: a const %s takes %s" % ("density" if channels == 1 else "albedo", "one number" if channels == 1 else "a number or an RGB triple"))
+            a = np.repeat(a, 3) if (a.size == 1 and channels == 3) else a
+            v.kind, v.channels = cls.CONST, int(a.size)
+            v.value[:a.size] = [float(x) for x in a]
+            return v
+        data = np.ascontiguousarray(d["data"], np.float32)
+        if data.ndim not in (3, 4) or (data.ndim == 4 and data.shape[3] not in (1, 3)):
+            raise ValueError("volume: data must be [z, y, x] or [z, y, x, 3]")
+        keep.append(data)
+        v.kind, v.channels = cls.GRID, (1 if data.ndim == 3 else int(data.shape[3]))
+        v.res[:] = [int(data.shape[2]), int(data.shape[1]), int(data.shape[0])]
+        v.aabb_min[:] = [float(x) for x in np.asarray(d["min"], np.float32).reshape(3)]
+        v.aabb_max[:] = [float(x) for x in np.asarray(d["max"], np.float32).reshape(3)]
+        tw = d.get("to_world")
+        v.to_world[:] = [float(x) for x in (np.eye(4, dtype=np.float32) if tw is None else np.asarray(tw, np.float32).reshape(4, 4)).reshape(-1)]
+        v.data = data.ctypes.data_as(C.POINTER(C.c_float))
+        return v
+
+
+class MediumVolumes(C.Structure):
+    """ppg_medium_volumes (include/ppg.h)"""
+    _fields_ = [("medium", C.c_uint32), ("density", C.c_uint32), ("albedo", C.c_uint32), ("scale", C.c_float), ("_reserved", C.c_uint32 * 4)]
+
+
+class MediaVolumes(C.Structure):
+    """ppg_media_volumes (include/ppg.h)"""
+    _fields_ = [("n_volumes", C.c_uint32), ("n_entries", C.c_uint32), ("volumes", C.POINTER(Volume)), ("entries", C.POINTER(MediumVolumes)),
+                ("_reserved", C.c_uint32 * 4)]
+
+
+def flatten_media_volumes(media):
+    """The side list of ppg_set_media_volumes for a list of medium dicts: (volumes, entries) — every heterogeneous medium's `density` and
+    `albedo` dicts as Volume records (a dict that two media share is one volume) and one MediumVolumes entry per such medium —, and the
+    arrays they point into."""
+    volumes, entries, keep, seen = [], [], [], {}
+
+    def volume(d, channels):
+        key = (id(d), channels)
+        if key not in seen:
+            seen[key] = len(volumes)
+            volumes.append(Volume.from_dict(d, channels, keep))
+        return seen[key]
+    for i, m in enumerate(media or []):
+        if isinstance(m, dict) and m.get("type") == "heterogeneous":
+            e = MediumVolumes()
+            e.medium, e.density, e.albedo, e.scale = i, volume(m["density"], 1), volume(m["albedo"], 3), float(m.get("scale", 1.0))
+            entries.append(e)
+    return volumes, entries, keep
+
+
 def media_word(interior=None, exterior=None):
     """The binding word of a primitive (ppg_media): low 16 bits = 1 + the interior medium's index, high 16 bits = 1 + the exterior one's."""
     return (0 if interior is None else 1 + int(interior)) | ((0 if exterior is None else 1 + int(exterior)) << 16)
@@ -325,6 +400,28 @@ class DebugMediumOut(C.Structure):
                 ("eval_transmittance", C.c_float * 3), ("wo", C.c_float * 3), ("phase_eval", C.c_float), ("phase_pdf", C.c_float)]
 
 
+class DebugVolumeItem(C.Structure):
+    _fields_ = [("volume", C.c_int32), ("p", C.c_float * 3)]
+
+
+class DebugVolumeOut(C.Structure):
+    _fields_ = [("value", C.c_float * 3)]
+
+
+class DebugHetmediumItem(C.Structure):
+    _fields_ = [("medium", C.c_int32), ("o", C.c_float * 3), ("d", C.c_float * 3), ("maxt", C.c_float), ("key", C.c_uint32), ("dim", C.c_uint32)]
+
+
+class DebugHetmediumOut(C.Structure):
+    _fields_ = [("success", C.c_int32), ("t", C.c_float), ("sigma_s", C.c_float * 3), ("transmittance", C.c_float), ("draws", C.c_uint32),
+                ("eval_transmittance", C.c_float), ("eval_draws", C.c_uint32)]
+
+
+DEBUG_VOLUME_ITEM_DTYPE = np.dtype([("volume", "<i4"), ("p", "<f4", 3)])
+DEBUG_VOLUME_OUT_DTYPE = np.dtype([("value", "<f4", 3)])
+DEBUG_HETMEDIUM_ITEM_DTYPE = np.dtype([("medium", "<i4"), ("o", "<f4", 3), ("d", "<f4", 3), ("maxt", "<f4"), ("key", "<u4"), ("dim", "<u4")])
+DEBUG_HETMEDIUM_OUT_DTYPE = np.dtype([("success", "<i4"), ("t", "<f4"), ("sigma_s", "<f4", 3), ("transmittance", "<f4"), ("draws", "<u4"),
+                                      ("eval_transmittance", "<f4"), ("eval_draws", "<u4")])
 DEBUG_MEDIUM_ITEM_DTYPE = np.dtype([("medium", "<i4"), ("length", "<f4"), ("wi", "<f4", 3), ("u", "<f4", 4)])
 DEBUG_MEDIUM_OUT_DTYPE = np.dtype([("success", "<i4"), ("t", "<f4"), ("pdf_success", "<f4"), ("pdf_failure", "<f4"), ("transmittance", "<f4", 3),
                                    ("eval_transmittance", "<f4", 3), ("wo", "<f4", 3), ("phase_eval", "<f4"), ("phase_pdf", "<f4")])
@@ -925,10 +1022,14 @@ class Engine:
 
     def set_media(self, media, tri_media=None, sphere_media=None, shape_media=None, camera_medium=0):
         """ppg_set_media: a list of medium dicts (Medium), the binding words per triangle / sphere / shape (media_word; None: none) and the
-        sensor's medium (1 + index, 0: none); an empty list clears it.  Takes effect at, and is validated by, the next set_scene."""
+        sensor's medium (1 + index, 0: none); an empty list clears it.  Heterogeneous media among them send their volumes first
+        (set_media_volumes).  Takes effect at, and is validated by, the next set_scene."""
         if self.prefix != "ppg_":
             raise NotImplementedError("%s: participating media are not implemented here" % self.prefix)
         media = list(media or [])
+        volumes, entries, keep_volumes = flatten_media_volumes(media)  # heterogeneous media: their volumes go first
+        if entries or getattr(self, "_media_volumes", False):
+            self.set_media_volumes(volumes, entries)
         m = Media()
         arr = (Medium * max(1, len(media)))()
         for i, d in enumerate(media):
@@ -945,6 +1046,37 @@ class Engine:
             setattr(m, name, _p(w, C.c_uint32))
         self._call("set_media", C.byref(m))
         self._media = bool(media)
+
+    def set_media_volumes(self, volumes, entries):
+        """ppg_set_media_volumes: Volume and MediumVolumes records (flatten_media_volumes makes them of medium dicts; set_media calls this
+        itself); no entries clear the list.  Takes effect at, and is validated by, the next set_scene."""
+        if self.prefix != "ppg_":
+            raise NotImplementedError("%s: participating media are not implemented here" % self.prefix)
+        volumes, entries = list(volumes or []), list(entries or [])
+        v = MediaVolumes()
+        varr, earr = (Volume * max(1, len(volumes)))(*volumes), (MediumVolumes * max(1, len(entries)))(*entries)
+        v.n_volumes, v.n_entries, v.volumes, v.entries = len(volumes), len(entries), varr, earr
+        self._call("set_media_volumes", C.byref(v))
+        self._media_volumes = bool(entries)
+
+    def _debug_items(self, name, items, item_dtype, out_dtype, item_cls, out_cls):
+        if self.prefix != "ppg_":
+            raise NotImplementedError("%s: ppg_%s is not implemented here" % (self.prefix, name))
+        items = np.ascontiguousarray(items, item_dtype).reshape(-1)
+        out = np.zeros(items.shape[0], out_dtype)
+        assert out.itemsize == C.sizeof(out_cls) and items.itemsize == C.sizeof(item_cls)
+        self._call(name, C.c_uint32(items.shape[0]), items.ctypes.data_as(C.POINTER(item_cls)), out.ctypes.data_as(C.POINTER(out_cls)))
+        return out
+
+    def debug_volume(self, items):
+        """ppg_debug_volume (include/ppg_testhooks.h): items a structured array (DEBUG_VOLUME_ITEM_DTYPE) through the hetmedia family's
+        volume lookups; a structured array (DEBUG_VOLUME_OUT_DTYPE)."""
+        return self._debug_items("debug_volume", items, DEBUG_VOLUME_ITEM_DTYPE, DEBUG_VOLUME_OUT_DTYPE, DebugVolumeItem, DebugVolumeOut)
+
+    def debug_hetmedium(self, items):
+        """ppg_debug_hetmedium (include/ppg_testhooks.h): items a structured array (DEBUG_HETMEDIUM_ITEM_DTYPE) through the hetmedia
+        family's sampleDistance and evalTransmittance; a structured array (DEBUG_HETMEDIUM_OUT_DTYPE)."""
+        return self._debug_items("debug_hetmedium", items, DEBUG_HETMEDIUM_ITEM_DTYPE, DEBUG_HETMEDIUM_OUT_DTYPE, DebugHetmediumItem, DebugHetmediumOut)
 
     def debug_medium(self, items):
         """ppg_debug_medium (include/ppg_testhooks.h): items a structured array (DEBUG_MEDIUM_ITEM_DTYPE) through the media family's

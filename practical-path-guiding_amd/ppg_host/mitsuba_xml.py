@@ -27,6 +27,9 @@
               toWorld without scale, irradiance): SceneDesc.delta_emitters, samplingWeight 1 only;
               area (nested in a shape), and one environment emitter: constant, envmap (latitude-longitude .exr / .pfm / .hdr; filename, scale, toWorld =
               rotation) or sunsky (baked into an envmap with the tables of a Mitsuba source tree; toWorld = rotation)
+  media       homogeneous (sigmaA + sigmaS or sigmaT + albedo, scale, strategy, mediumSamplingWeight) and heterogeneous (method = woodcock; density and
+              albedo <volume>s of type constvolume or gridvolume: value, filename of a float32 / uint8 .vol file, toWorld, min / max; scale) with an
+              isotropic or hg <phase>, as interior / exterior of a shape or on the sensor, inline or by <ref> (SceneDesc.media)
   values      <spectrum> (value or filename), <rgb>, <srgb>, <blackbody> (spectrum.py), <transform> of translate / rotate / scale / lookAt / matrix,
               <default name value> and $name substitution (mitsuba -D, mitsuba.cpp:58-87)
 
@@ -1507,14 +1510,15 @@ class _Reader:
         info = dict(width=W, height=H, sample_count=_props(sampler, self.sub).get("sampleCount") if sampler is not None else None)
         return dict(camera=camera, lens=lens, rfilter=rfilter, camera_medium=camera_medium), info
 
-    # ---- participating media: <medium type="homogeneous"> with a nested <phase> (medium/homogeneous.cpp, medium.cpp, phase/isotropic.cpp, hg.cpp)
+    # ---- participating media: <medium type="homogeneous"> with a nested <phase> (medium/homogeneous.cpp, medium.cpp, phase/isotropic.cpp, hg.cpp);
+    # <medium type="heterogeneous"> further down
     def _make_medium(self, elem):
         """A <medium> element → its dict (bindings.Medium).  What cannot be rendered is refused by name."""
         t = elem.get("type")
         if t == "heterogeneous":
-            raise SceneError("medium type 'heterogeneous' is not supported (homogeneous media only)")
+            return self._make_heterogeneous(elem)
         if t != "homogeneous":
-            raise SceneError("medium type %r is not supported (homogeneous media only)" % t)
+            raise SceneError("medium type %r is not supported (homogeneous, heterogeneous)" % t)
         p = _props(elem, self.sub)
         stated = {c.get("name") for c in elem if c.tag in ("rgb", "srgb", "spectrum", "blackbody")}
         if "material" in p:
@@ -1548,18 +1552,88 @@ class _Reader:
             m["sampling_density"] = float(p["samplingDensity"])
         if "mediumSamplingWeight" in p and float(p["mediumSamplingWeight"]) != -1:
             m["sampling_weight"] = float(p["mediumSamplingWeight"])
+        m.update(self._read_phase(elem, "homogeneous medium"))
+        return m
+
+    def _read_phase(self, elem, who):  # the nested <phase> of a <medium> → the dict's phase / g entries (none: Medium::configure instantiates `isotropic`)
         phases = [c for c in elem if c.tag == "phase"]
         if len(phases) > 1:
-            raise SceneError("homogeneous medium: more than one <phase>")
-        if phases:  # (none: Medium::configure instantiates `isotropic`)
-            pt, pp = phases[0].get("type"), _props(phases[0], self.sub)
-            if pt == "hg":
-                g = float(pp.get("g", 0.8))  # hg.cpp:49-52
-                if g >= 1 or g <= -1:
-                    raise SceneError("hg: The asymmetry parameter must lie in the interval (-1, 1)!")
-                m.update(phase="hg", g=g)
-            elif pt != "isotropic":
-                raise SceneError("phase function type %r is not supported (isotropic, hg)" % pt)
+            raise SceneError("%s: more than one <phase>" % who)
+        if not phases:
+            return {}
+        pt, pp = phases[0].get("type"), _props(phases[0], self.sub)
+        if pt == "hg":
+            g = float(pp.get("g", 0.8))  # hg.cpp:49-52
+            if g >= 1 or g <= -1:
+                raise SceneError("hg: The asymmetry parameter must lie in the interval (-1, 1)!")
+            return dict(phase="hg", g=g)
+        if pt != "isotropic":
+            raise SceneError("phase function type %r is not supported (isotropic, hg)" % pt)
+        return {}
+
+    # ---- <medium type="heterogeneous"> (medium/heterogeneous.cpp, method = woodcock) over <volume type="constvolume|gridvolume">
+    def _make_volume(self, elem, name):
+        """A <volume name="density|albedo"> → its dict (bindings.Volume)"""
+        t, want = elem.get("type"), (1 if name == "density" else 3)
+        if t not in ("constvolume", "gridvolume"):
+            raise SceneError("medium type 'heterogeneous': volume type %r (%s) is not supported (constvolume, gridvolume)" % (t, name))
+        p = _props(elem, self.sub)  # (sendData is read by nobody)
+        if t == "constvolume":
+            values = [c for c in elem if c.get("name") == "value"]
+            if len(values) != 1:
+                raise SceneError("medium type 'heterogeneous': constvolume (%s) needs one 'value'" % name)
+            if values[0].tag == "float":
+                v = float(p["value"])
+                return dict(value=v if want == 1 else (v, v, v))
+            if values[0].tag in ("rgb", "srgb", "spectrum", "blackbody") and want == 3:
+                return dict(value=tuple(float(x) for x in self._colour(elem, "value", 0.0)))
+            raise SceneError("medium type 'heterogeneous': the constvolume for %s must hold a %s value (got <%s>)" % (name, "float" if want == 1 else "float or spectrum", values[0].tag))
+        fn = p.get("filename")
+        if not fn:
+            raise SceneError("medium type 'heterogeneous': gridvolume (%s) without filename" % name)
+        full = fn if os.path.isabs(fn) else os.path.join(self.base, fn)
+        try:
+            vol = read_vol(full)
+        except (OSError, ValueError) as e:
+            raise SceneError("medium type 'heterogeneous': gridvolume (%s) %r: %s" % (name, fn, e))
+        if vol["data"].ndim == 4 and want == 1:
+            raise SceneError("medium type 'heterogeneous': gridvolume %r has 3 channels: a density volume must have 1" % fn)  # Assert(m_channels == 1)
+        if vol["data"].ndim == 3 and want == 3:
+            raise SceneError("medium type 'heterogeneous': gridvolume %r has 1 channel: an albedo volume must have 3" % fn)  # Assert(m_channels == 3)
+        to_world = None
+        for c in elem:
+            if c.tag == "transform" and c.get("name") == "toWorld":
+                to_world = _transform(c, self.sub)
+        lo, hi = (p["min"], p["max"]) if ("min" in p and "max" in p) else (vol["min"], vol["max"])  # gridvolume.cpp:104-110
+        return dict(data=vol["data"], min=tuple(float(x) for x in lo), max=tuple(float(x) for x in hi), to_world=to_world)
+
+    def _make_heterogeneous(self, elem):
+        p = _props(elem, self.sub)
+        stated = {c.get("name") for c in elem if c.tag in ("rgb", "srgb", "spectrum", "blackbody", "float")} & {"sigmaA", "sigmaS", "sigmaT", "albedo"}
+        if stated:
+            raise SceneError("medium type 'heterogeneous' is not supported (homogeneous media only) with %s: these belong to homogeneous media; give `density` and "
+                             "`albedo` volumes" % " / ".join(repr(n) for n in sorted(stated)))
+        method = str(p.get("method", "woodcock")).lower()
+        if method == "simpson":
+            raise SceneError("medium type 'heterogeneous': method 'simpson' is not supported (woodcock)")
+        if method != "woodcock":
+            raise SceneError("medium type 'heterogeneous': Unsupported integration method %r" % method)
+        volumes = {}
+        for c in elem:
+            if c.tag != "volume":
+                continue
+            name = c.get("name")
+            if name == "orientation":
+                raise SceneError("medium type 'heterogeneous': an 'orientation' volume (anisotropic media) is not supported")
+            if name not in ("density", "albedo"):
+                raise SceneError("medium type 'heterogeneous': volume name %r is not supported (density, albedo)" % name)
+            volumes[name] = self._make_volume(c, name)
+        for name in ("density", "albedo"):
+            if name not in volumes:
+                raise SceneError("medium type 'heterogeneous': No %s specified!" % name)  # heterogeneous.cpp:229-232
+        scale = float(p.get("scale", 1.0))
+        m = dict(type="heterogeneous", density=volumes["density"], albedo=volumes["albedo"], scale=scale)  # (stepSize: tracking never reads it)
+        m.update(self._read_phase(elem, "heterogeneous medium"))
         return m
 
     def _medium_index(self, elem, where):
@@ -1854,6 +1928,59 @@ _BSDF_READERS = {  # plug-in → its reader (the reader object, the <bsdf> eleme
     "twosided": _Reader._read_twosided, "mask": _Reader._read_mask, "coating": _Reader._read_coating, "roughcoating": _Reader._read_coating,
     "blendbsdf": _Reader._read_blend, "mixturebsdf": _Reader._read_blend,
 }
+
+
+VOL_ENCODINGS = {1: "float32", 2: "float16", 3: "uint8", 4: "quantized directions"}
+
+
+def read_vol(path):
+    """Mitsuba's .vol container (gridvolume.cpp:64-81: 'VOL', version 3, encoding, x / y / z cells, channels, the data's box; 48 bytes, little
+    endian) → dict(data=float32 [z, y, x] or [z, y, x, 3], min, max, encoding).  uint8 texels become float32 as i / 255.0f, the reference's
+    m_densityMap.  float16 and quantized directions are refused (the reference's float lookup answers 0 for them); so is a bad header."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if len(raw) < 48 or raw[:3] != b"VOL":
+        raise ValueError("bad header: not a .vol file (no 'VOL' signature in 48 header bytes)")
+    if raw[3] != 3:
+        raise ValueError("bad header: file format version %d (3 is supported)" % raw[3])
+    enc, rx, ry, rz, ch = (int(v) for v in np.frombuffer(raw, "<i4", 5, 4))
+    box = np.frombuffer(raw, "<f4", 6, 24)
+    if enc not in VOL_ENCODINGS:
+        raise ValueError("bad header: unknown encoding %d" % enc)
+    if enc in (2, 4):
+        raise ValueError("encoding %s is not supported (float32, uint8)" % VOL_ENCODINGS[enc])
+    if min(rx, ry, rz) < 1 or ch not in (1, 3):
+        raise ValueError("bad header: %d x %d x %d cells, %d channels (1 or 3 are supported)" % (rx, ry, rz, ch))
+    n = rx * ry * rz * ch
+    size = n * (4 if enc == 1 else 1)
+    if len(raw) < 48 + size:
+        raise ValueError("bad header: the file holds %d data bytes, %d x %d x %d x %d %s texels need %d" % (len(raw) - 48, rx, ry, rz, ch, VOL_ENCODINGS[enc], size))
+    if enc == 1:
+        data = np.frombuffer(raw, "<f4", n, 48).astype(f32)
+    else:
+        data = (np.arange(256, dtype=f32) / f32(255.0))[np.frombuffer(raw, np.uint8, n, 48)]
+    data = data.reshape((rz, ry, rx) if ch == 1 else (rz, ry, rx, ch))
+    return dict(data=np.ascontiguousarray(data), min=tuple(float(v) for v in box[:3]), max=tuple(float(v) for v in box[3:]), encoding=VOL_ENCODINGS[enc])
+
+
+def write_vol(path, data, min, max, encoding="float32"):  # noqa: A002 (Mitsuba's names)
+    """Write `data` ([z, y, x] or [z, y, x, 3]) as a .vol file; encoding "float32" or "uint8" (texels rounded to i / 255)."""
+    data = np.asarray(data)
+    if data.ndim not in (3, 4) or (data.ndim == 4 and data.shape[3] not in (1, 3)):
+        raise ValueError("write_vol: data must be [z, y, x] or [z, y, x, 3]")
+    if encoding not in ("float32", "uint8"):
+        raise ValueError("write_vol: encoding %r is not supported (float32, uint8)" % (encoding,))
+    rz, ry, rx = data.shape[:3]
+    ch = 1 if data.ndim == 3 else data.shape[3]
+    head = b"VOL\x03" + np.asarray([1 if encoding == "float32" else 3, rx, ry, rz, ch], "<i4").tobytes() + np.asarray(list(min) + list(max), "<f4").tobytes()
+    if encoding == "float32":
+        body = np.ascontiguousarray(data, "<f4").tobytes()
+    elif data.dtype == np.uint8:
+        body = np.ascontiguousarray(data).tobytes()
+    else:
+        body = np.clip(np.rint(np.asarray(data, np.float64) * 255.0), 0, 255).astype(np.uint8).tobytes()
+    with open(path, "wb") as f:
+        f.write(head + body)
 
 
 def load_scene(path, defines=None, strict=True, width=None, height=None, data_dir=None, mitsuba_src=None):

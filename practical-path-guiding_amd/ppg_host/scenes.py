@@ -39,7 +39,8 @@ class SceneDesc:
                                                           # after the area emitters and before the environment emitter
         self.shapes = list(shapes or [])  # analytic disks and cylinders: dicts {type, to_world, radius, length, material, emitter, flip_normals}
                                           # (bindings.Shape); primitives after the triangles and the spheres
-        # homogeneous participating media (include/ppg.h ppg_set_media; HIP library only): dicts (bindings.Medium), and who lies in which —
+        # participating media (include/ppg.h ppg_set_media, ppg_set_media_volumes; HIP library only): dicts (bindings.Medium: homogeneous, or
+        # type="heterogeneous" with density / albedo volume dicts, bindings.Volume), and who lies in which —
         # one binding word per triangle / sphere / shape (bindings.media_word(interior, exterior); None: no transitions among them) and the
         # sensor's medium as 1 + its index (0: none)
         self.media = list(media or [])
